@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: 256x256 tiles/s of the htc_lite_swin tile-inference path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 16] [--dump-outputs DIR] [--full]
 
 One step = one nuhtc_infer call on one batch of `--batch` synthetic 256x256x3 tiles already resident in HBM
 (the full path: pre-processing, Swin-T, FPN, RPN, proposals, 3-stage cascade, detection NMS, mask head, paste,
@@ -15,10 +15,14 @@ WSI path ships: heads, ring vertices, bit-packed mask crops (nuhtc_amd.wsi.pack_
 over RCCL (nuhtc_amd.parallel.gather_blobs), inside the timed region, as before the host-side merge of a slide.
 Prints ONE JSON line on rank 0.
 
-Besides `value`: `roofline` (dominant kernel, live HIP-event timing), `roofline.pipeline_frac` (SURVEY 8d headline: executed
-FLOP of the whole step / step time / fp32-MFMA peak), `kernel_groups` (per group: TFLOP/s / 157.3 for the dense groups,
-algorithmic GB/s / 8000 for the gather / scan groups), `real_slide_roi_load` (the same step with 40-100 px RoIs, the size of
-40x nuclei after the x2 resize), `cpu_baseline` (the oracle on the host cores, bounded sample) with the parity of the run.
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the configuration and the exchange).
+`--dump-outputs DIR` writes what step K computed as DIR/<name>.npy (float32 / float64, see dump_outputs) for output-for-output
+comparisons of two builds.  Everything else needs runs of its own and is measured with `--full` only: `value_steady` (the pipeline
+already full), `sequential` (one batch at a time), `roofline` (dominant kernel, live HIP-event timing), `roofline.pipeline_frac`
+(SURVEY 8d headline: executed FLOP of the whole step / step time / fp32-MFMA peak), `kernel_groups` (per group: TFLOP/s / 157.3 for
+the dense groups, algorithmic GB/s / 8000 for the gather / scan groups), `real_slide_roi_load` (the same step with 40-100 px RoIs,
+the size of 40x nuclei after the x2 resize), `fp32_mfma_pipe`, `power`, and `cpu_baseline` (the oracle on the host cores, bounded
+sample) with the parity of the run.
 """
 import argparse
 import json
@@ -240,6 +244,55 @@ class PowerLog:
         return out
 
 
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir, e, B, gathered, sample=64, max_tiles=16, max_records=4096, seed=0):
+    """What step K computed, as a caller of the path receives it, into out_dir/<name>.npy, float32 / float64 (every integer here is exact in
+    them).  From engine `e` (the one that ran step K), for a seeded sample of at most `max_tiles` of the B tiles (`tile_index`; all of them at
+    the default B = 16): every detection of those tiles in (tile, slot) order -- `det_tile`, `det_boxes` (x0, y0, x1, y1, score),
+    `det_labels`, `det_keep` (the per-tile mask-NMS verdict), `det_mask_area` (set pixels of its mask) -- the per-pixel number of masks
+    covering each of those tiles (`mask_coverage`) and the full masks of a seeded sample of `sample` of those detections (`mask_sample`, their
+    indices into the detection list in `mask_sample_index`).  From the exchange, a seeded sample of at most `max_records` of all ranks'
+    records (nuhtc_amd.wsi.pack_records; `records_index`): `records_head`, `records_rings` (their rings, concatenated), `records_crops`.
+    About 20 MB at B = 16; more than DUMP_MAX_BYTES is refused before anything is written."""
+    H, W = e.image_hw
+    rng = np.random.default_rng(seed)
+    tiles = np.sort(rng.choice(B, min(B, max_tiles), replace=False))
+    counts = e.counts[:B].cpu().numpy()[tiles]
+    tile = np.repeat(tiles, counts)
+    slot = np.concatenate([np.arange(c) for c in counts]) if len(tiles) else np.zeros(0, np.int64)
+    pick = np.sort(rng.choice(len(tile), min(sample, len(tile)), replace=False))
+    first = np.concatenate([[0], np.cumsum(counts)])           # index of each sampled tile's first detection
+    sel = lambda t: t[:B].cpu().numpy()[tile, slot]
+    shifts = torch.arange(32, device=e.masks.device, dtype=torch.int32)
+    area, cover, masks = [], np.zeros((len(tiles), H, W), np.float32), []
+    for j, b in enumerate(tiles):       # one tile's masks unpacked on the device at a time; only the sampled ones are kept, on the host
+        bits = ((e.masks[b, :int(counts[j])].unsqueeze(-1) >> shifts) & 1).to(torch.uint8)     # bit j of word w = column 32 w + j
+        bits = bits.reshape(-1, e.cfg.tile_h, e.cfg.tile_w)[:, :H, :W]                          # (rows are padded to a multiple of 32)
+        area.append(bits.sum((1, 2), dtype=torch.int64).cpu().numpy())
+        cover[j] = bits.sum(0, dtype=torch.float32).cpu().numpy()
+        mine = pick[(pick >= first[j]) & (pick < first[j + 1])] - first[j]
+        masks.append(bits[torch.from_numpy(mine).to(bits.device)].cpu().numpy())
+    head, verts, crops = (np.concatenate([g[i].cpu().numpy() for g in gathered], 0) for i in range(3))
+    off = np.concatenate([[0], np.cumsum(head[:, 6].astype(np.int64))])      # head column 6 = ring length; rings in record order
+    assert off[-1] == len(verts), (off[-1], len(verts))
+    rec = np.sort(rng.choice(len(head), min(len(head), max_records), replace=False))
+    arrays = dict(tile_index=tiles, det_tile=tile, det_boxes=sel(e.boxes), det_labels=sel(e.labels), det_keep=sel(e.keep),
+                  det_mask_area=np.concatenate(area) if area else np.zeros(0), mask_coverage=cover,
+                  mask_sample=np.concatenate(masks) if masks else np.zeros((0, H, W)), mask_sample_index=pick,
+                  records_index=rec, records_head=head[rec].astype(np.float64), records_crops=crops[rec].astype(np.float64),
+                  records_rings=(np.concatenate([verts[off[i]:off[i + 1]] for i in rec]) if len(rec) else np.zeros((0, 2))).astype(np.float64))
+    arrays = {k: a.astype(np.float64 if a.dtype == np.float64 else np.float32) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f'--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte bound')
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return sorted(arrays)
+
+
 def self_launch(n):
     """Run this script as `n` ranks (one per GPU) under torch.distributed.run as a CHILD process and relay its output: the JSON line
     of rank 0 goes to stdout, everything else to stderr.  Returns the job's exit code.  Nothing here initialises the GPU."""
@@ -275,7 +328,15 @@ def main():
     ap.add_argument('--no-force-collective', action='store_true', help='N = 1: do not form the one-rank RCCL communicator; the exchange short-circuits (rounds 1-4)')
     ap.add_argument('--no-host-bind', action='store_true', help="leave the process on whatever CPUs the scheduler picks instead of the GPU's NUMA node (A/B of hip.bind_host_thread)")
     ap.add_argument('--roi-sort', action='store_true', help='--fixed-load (dev): hand the RoIs over sorted by position (locality experiment)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also measure everything else: value_steady, sequential, roofline / per-kernel figures, RoI-load and '
+                         'fp32-pipe legs, power, CPU baseline with parity (--no-cpu-baseline, --no-roi-load, --no-fp32-pipe, --cpu-*, --gemm-shapes and '
+                         '--power-csv act on these)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='write the outputs of the last timed step to DIR/<name>.npy (float32 / float64; bench_outputs/ is ignored by git)')
     args = ap.parse_args()
+    for flag in ('cpu_full', 'gemm_shapes', 'power_csv'):
+        if getattr(args, flag) and not args.full:
+            ap.error(f"--{flag.replace('_', '-')} belongs to --full")
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process becomes the launcher (one rank per GPU under
@@ -338,7 +399,7 @@ def main():
 
     from nuhtc_amd import hip, synth, weights
     from nuhtc_amd.engine import Engine
-    plog = PowerLog() if rank == 0 else None          # 10 Hz power / clock / temperature beside every phase of the run (sysfs)
+    plog = PowerLog() if rank == 0 and args.full else None          # 10 Hz power / clock / temperature beside every phase of the run (sysfs)
     mark = (lambda name: plog.mark(name)) if plog else (lambda name: None)
     mark('_setup')
     torch.cuda.set_device(local_rank)
@@ -462,6 +523,59 @@ def main():
     total_tiles = args.steps * B * world
     counts = eng.counts[:B].cpu().numpy()
     roi_counts = eng.buffer('roi_counts')[:B].cpu().numpy()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, B, gathered)          # the outputs of step K (engine `last` ran it), before anything else runs
+    out = None
+    if rank == 0:
+        out = {
+            'metric': 'tiles/sec (256x256) whole-node', 'value': total_tiles / dt, 'unit': 'tiles/s', 'n_gpus': world,
+            'steps': args.steps, 'warmup': args.warmup, 'settle_steps_before_warmup': settle_steps, 'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True,
+            'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+            'dtype_note': ('fp32 operands, results and accumulation everywhere; matrix products on the bf16 matrix pipe with every fp32 operand split exactly into '
+                           'three bf16 numbers (six exact bf16 products per fp32 product; the three dropped cross terms are at most 2^-23 |a b| together): measured error against fp64 at or '
+                           'below the fp32 MFMA chain (tests/test_hip_dense.py::test_split_bf16_pipe_is_fp32_arithmetic)') if args.pipe == 'split' else
+                          'fp32 MFMA (v_mfma_f32_32x32x2_f32) for every matrix product',
+            'config': {'workload': 'htc_lite_swin PanNuke config, batch_size=16 256x256 tiles per GPU (BASELINE configs[1]), full path '
+                                   'incl. proposals, cascade, masks, per-tile mask-NMS' + (' [fixed load: 1064 RoIs, 64 detections per tile]' if args.fixed_load else ''), 'batch_per_gpu': B,
+                       'weights': 'seeded synthetic (weights.bench_state_dict); pannuke.pth not distributed',
+                       'tiles': 'synthetic nuclei tiles (nuhtc_amd.synth), resident in HBM',
+                       'batches_in_flight': depth, 'schedule': 'NUHTC_SCHED_THROUGHPUT for the engines in flight (one stream, 256-row tiles); NUHTC_SCHED_LATENCY for `sequential` and the per-kernel figures' if depth > 1 else 'NUHTC_SCHED_LATENCY', 'hw_queues': os.environ.get('GPU_MAX_HW_QUEUES', 'runtime default (4)'),
+                       'mean_rois_per_tile': float(roi_counts.mean()), 'mean_dets_per_tile': float(counts.mean())},
+            'exchange': {'collective': 'all_gather (header) + all_gather (one packed byte buffer): nuhtc_amd.parallel.gather_blobs',
+                         'backend': (dist.get_backend() if dist is not None else 'none: one rank, short-circuit'),
+                         'communicator_ranks': (dist.get_world_size() if dist is not None else 1),
+                         **({'note': collective_note} if collective_note else {}),
+                         'ranks_seen': ranks_seen, 'records': gathered_records, 'bytes': gathered_bytes, 'seconds_inside_timed_region': round(exchange_s, 4),
+                         'layout': 'head f64[n,9] | ring vertices i32[*,2] | crop boxes i64[n,6] | bit-packed mask crops i32[*] | rank id'},
+        }
+
+    def write_line(out):
+        """Rank 0 prints the line, with the power summary (--full) and where the submitting thread ran; every rank leaves the process group."""
+        if rank == 0:
+            bdf = None
+            try:
+                pr = torch.cuda.get_device_properties(local_rank)
+                bdf = f'{pr.pci_domain_id:04x}:{pr.pci_bus_id:02x}:{pr.pci_device_id:02x}.0'
+            except Exception:
+                pass
+            if plog:
+                out['power'] = plog.summary(args.power_csv, bdf)
+            node = None
+            try:
+                node = int(open(f'/sys/bus/pci/devices/{bdf}/numa_node').read())
+            except (OSError, ValueError, TypeError):
+                pass
+            out['host'] = dict(submitting_thread_bound_to_gpu_numa_node=bool(host_bound), gpu_pci=bdf, gpu_numa_node=node, cpus_during_gpu_legs=len(cpus_gpu), cpus_of_process=len(cpus0),
+                               note='hip.bind_host_thread (nuhtc_bind_host_thread): from the other socket every dispatch packet costs the command processor 1.4-2.9 us more '
+                                    '(0.3-0.4 ms per sequential step); the CPU baseline runs on the process\'s original CPUs')
+            json_out.write(json.dumps(out) + '\n')
+            json_out.flush()
+        if dist is not None:
+            dist.destroy_process_group()
+
+    if not args.full:          # a plain run: the headline only
+        write_line(out)
+        return
 
     # What the K-step window above leaves out: it starts with the `depth` engines empty and ends when the last of them has drained, so
     # depth - 1 steps' worth of the window run on a partly filled GPU (K = 20 at the driver's settings).  `value_steady` is the same step
@@ -734,20 +848,7 @@ def main():
                      'note': 'NUHTC_PIPE_FP32: every matrix product on v_mfma_f32_32x32x2_f32 (the kernels of round 1)'}
         e32.close()
     if rank == 0:
-        out = {
-            'metric': 'tiles/sec (256x256) whole-node', 'value': total_tiles / dt, 'unit': 'tiles/s', 'n_gpus': world,
-            'steps': args.steps, 'warmup': args.warmup, 'settle_steps_before_warmup': settle_steps, 'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True,
-            'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-            'dtype_note': ('fp32 operands, results and accumulation everywhere; matrix products on the bf16 matrix pipe with every fp32 operand split exactly into '
-                           'three bf16 numbers (six exact bf16 products per fp32 product; the three dropped cross terms are at most 2^-23 |a b| together): measured error against fp64 at or '
-                           'below the fp32 MFMA chain (tests/test_hip_dense.py::test_split_bf16_pipe_is_fp32_arithmetic)') if args.pipe == 'split' else
-                          'fp32 MFMA (v_mfma_f32_32x32x2_f32) for every matrix product',
-            'config': {'workload': 'htc_lite_swin PanNuke config, batch_size=16 256x256 tiles per GPU (BASELINE configs[1]), full path '
-                                   'incl. proposals, cascade, masks, per-tile mask-NMS' + (' [fixed load: 1064 RoIs, 64 detections per tile]' if args.fixed_load else ''), 'batch_per_gpu': B,
-                       'weights': 'seeded synthetic (weights.bench_state_dict); pannuke.pth not distributed',
-                       'tiles': 'synthetic nuclei tiles (nuhtc_amd.synth), resident in HBM',
-                       'batches_in_flight': depth, 'schedule': 'NUHTC_SCHED_THROUGHPUT for the engines in flight (one stream, 256-row tiles); NUHTC_SCHED_LATENCY for `sequential` and the per-kernel figures' if depth > 1 else 'NUHTC_SCHED_LATENCY', 'hw_queues': os.environ.get('GPU_MAX_HW_QUEUES', 'runtime default (4)'),
-                       'mean_rois_per_tile': float(roi_counts.mean()), 'mean_dets_per_tile': float(counts.mean())},
+        out.update({
             'roofline': {'bound': 'mfma', 'kernel': DOMINANT + (' (Swin-T linears: gemm_split_kernel<3,0>, 6 x v_mfma_f32_32x32x16_bf16 per 32x32x16 fp32 product)' if args.pipe == 'split'
                                                                 else ' (Swin-T linears, fp32 v_mfma_f32_32x32x2_f32)'), 'achieved': achieved,
                          'peak': PEAK_F32_MFMA_TFLOPS, 'unit': 'TFLOP/s', 'frac': achieved / PEAK_F32_MFMA_TFLOPS,
@@ -769,13 +870,7 @@ def main():
                          'share_of_step_kernel_time': dom['ms'] / tot_ms},
             'kernel_ms_per_step': breakdown,
             'kernel_groups': groups,
-            'exchange': {'collective': 'all_gather (header) + all_gather (one packed byte buffer): nuhtc_amd.parallel.gather_blobs',
-                         'backend': (dist.get_backend() if dist is not None else 'none: one rank, short-circuit'),
-                         'communicator_ranks': (dist.get_world_size() if dist is not None else 1),
-                         **({'note': collective_note} if collective_note else {}),
-                         'ranks_seen': ranks_seen, 'records': gathered_records, 'bytes': gathered_bytes, 'seconds_inside_timed_region': round(exchange_s, 4),
-                         'layout': 'head f64[n,9] | ring vertices i32[*,2] | crop boxes i64[n,6] | bit-packed mask crops i32[*] | rank id'},
-        }
+        })
         if steady:
             out['value_steady'] = steady['value']
             out['value_steady_detail'] = {**steady, 'unit': 'tiles/s',
@@ -805,25 +900,7 @@ def main():
                 out['cpu_baseline'] = cpu_baseline(sd, synth.nuclei_tiles(160, 256, start=0), eng, mode, batch=16, timed=10, warm=16, warm_batches=2, host_cpus=cpus0)
             else:
                 out['cpu_baseline'] = cpu_baseline(sd, tiles_np, eng, mode, batch=args.cpu_batch, host_cpus=cpus0)
-        bdf = None
-        try:
-            pr = torch.cuda.get_device_properties(local_rank)
-            bdf = f'{pr.pci_domain_id:04x}:{pr.pci_bus_id:02x}:{pr.pci_device_id:02x}.0'
-        except Exception:
-            pass
-        out['power'] = plog.summary(args.power_csv, bdf)
-        node = None
-        try:
-            node = int(open(f'/sys/bus/pci/devices/{bdf}/numa_node').read())
-        except (OSError, ValueError, TypeError):
-            pass
-        out['host'] = dict(submitting_thread_bound_to_gpu_numa_node=bool(host_bound), gpu_pci=bdf, gpu_numa_node=node, cpus_during_gpu_legs=len(cpus_gpu), cpus_of_process=len(cpus0),
-                           note='hip.bind_host_thread (nuhtc_bind_host_thread): from the other socket every dispatch packet costs the command processor 1.4-2.9 us more '
-                                '(0.3-0.4 ms per sequential step); the CPU baseline runs on the process\'s original CPUs')
-        json_out.write(json.dumps(out) + '\n')
-        json_out.flush()
-    if dist is not None:
-        dist.destroy_process_group()
+    write_line(out)
 
 
 if __name__ == '__main__':

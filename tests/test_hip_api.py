@@ -612,7 +612,7 @@ def test_eight_ranks_end_to_end_on_one_device(hip_device, tmp_path):
             b = open(tmp_path / f'{name}_eight/nuclei/{name}' / f, 'rb').read()
             assert a == b and len(a) > 2, f
         assert not [f for f in os.listdir(tmp_path / f'{name}_eight') if f.startswith('.host_phase_done')]       # rank 0 removed its marker
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1', '--no-settle', '--no-fp32-pipe',
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '8', '--steps', '2', '--warmup', '1', '--no-settle', '--no-fp32-pipe',
                           '--no-roi-load', '--batch', '2', '--in-flight', '2'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
     print(out.stderr[-3000:])
     assert out.returncode == 0
@@ -669,7 +669,7 @@ def test_bench_launches_its_own_ranks(hip_device):
     import sys
     env = _two_rank_env()
     env.pop('WORLD_SIZE', None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--no-settle', '--no-fp32-pipe',
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '2', '--steps', '3', '--warmup', '1', '--no-settle', '--no-fp32-pipe',
                           '--no-roi-load', '--batch', '4'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     print(out.stderr[-3000:])
     assert out.returncode == 0

@@ -6,7 +6,7 @@
 mkdir -p gpurun_out; O=gpurun_out/r05_mt2_min.txt; : > $O
 NUHTC_EXTRA_CFLAGS=-DNUHTC_DEV python -m nuhtc_amd.build --force > /dev/null || exit 1
 for r in 1 2 3; do for v in 0 192 300 600; do
-  NUHTC_SPLIT_MT2_MIN=$v timeout 300 python bench.py --no-cpu-baseline --no-roi-load --no-fp32-pipe --steps 100 2>/dev/null | python -c "
+  NUHTC_SPLIT_MT2_MIN=$v timeout 300 python bench.py --full --no-cpu-baseline --no-roi-load --no-fp32-pipe --steps 100 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('SPLIT_MT2_MIN=$v in flight', round(d['value'],1), 'sequential', round(d['sequential']['value'],1), 'clock', round(d['roofline']['shader_clock_ghz_under_step'],3))" >> $O

@@ -8,7 +8,7 @@ NUHTC_EXTRA_CFLAGS=-DNUHTC_DEV python -m nuhtc_amd.build --force > /dev/null || 
 timeout 300 python tools/dev/knob_ab.py ATTN_PADBITS 0 1 --rounds 12 --tags gemm,window_attn,layernorm,swin_lnqkv >> $O 2>/dev/null
 timeout 300 python tools/dev/knob_ab.py MERGE_LN_IN_A 0 1 --rounds 12 --tags gemm,merge_ln,layernorm,swin_mlp >> $O 2>/dev/null
 for r in 1 2; do for v in "0 0" "1 0" "0 1" "1 1"; do set -- $v
-  NUHTC_ATTN_PADBITS=$1 NUHTC_MERGE_LN_IN_A=$2 timeout 300 python bench.py --no-cpu-baseline --no-roi-load --no-fp32-pipe --steps 100 2>/dev/null | python -c "
+  NUHTC_ATTN_PADBITS=$1 NUHTC_MERGE_LN_IN_A=$2 timeout 300 python bench.py --full --no-cpu-baseline --no-roi-load --no-fp32-pipe --steps 100 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernel_ms_per_step']
 print('ATTN_PADBITS=$1 MERGE_LN_IN_A=$2 in flight', round(d['value'],1), 'sequential', round(d['sequential']['value'],1), 'window_attn', k.get('window_attn'), 'gemm<3>', k.get('gemm_kernel<3>'), 'merge_ln', k.get('merge_ln'), 'clock', d['roofline']['shader_clock_ghz_under_step'])" >> $O

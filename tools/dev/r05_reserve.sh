@@ -4,7 +4,7 @@
 # registers) a pad of 16 KB lets only TWO of its workgroups onto a CU and leaves a third of the registers and ~36 KB of LDS to whoever else has work.
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out; O=gpurun_out/r05_reserve.txt; : > $O
 NUHTC_EXTRA_CFLAGS="-DNUHTC_DEV" python -m nuhtc_amd.build --force > /dev/null 2>&1 || exit 1
-run() { python bench.py --no-cpu-baseline --no-roi-load --no-fp32-pipe --steps 100 2>/dev/null | python -c "
+run() { python bench.py --full --no-cpu-baseline --no-roi-load --no-fp32-pipe --steps 100 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1: in flight', round(d['value'],1), 'sequential', round(d['sequential']['value'],1), 'clock', round(d['roofline']['shader_clock_ghz_under_step'] or 0, 3))" >> $O; }
 for r in 1 2; do

@@ -29,15 +29,15 @@ python3 $GRAFT_REPO_ROOT/tools/dev/pmc_util.py '/tmp/ut/**/*counter_collection.c
 # ---- bench lines (the default command with its 10 Hz power log; three more processes back to back: the state of the dense launches
 # differs by process, the power / clock columns go with each)
 cd $GRAFT_REPO_ROOT
-python bench.py --power-csv $OUT/${R}_power_bench.csv > $OUT/${R}_bench.json 2> $OUT/${R}_bench.err; tail -c 300 $OUT/${R}_bench.json; echo
-for i in 1 2 3; do python bench.py --no-cpu-baseline --no-roi-load --no-fp32-pipe --steps 300 --power-csv $OUT/${R}_power_run$i.csv > $OUT/${R}_bench_run$i.json 2>/dev/null; done
-python bench.py --no-cpu-baseline --no-roi-load --no-fp32-pipe --in-flight 0 --fixed-load > $OUT/${R}_bench_fixed_load.json 2>/dev/null
-python bench.py --batch 64 --steps 30 --no-cpu-baseline --no-fp32-pipe --no-roi-load > $OUT/${R}_bench_b64.json 2>/dev/null
+python bench.py --full --power-csv $OUT/${R}_power_bench.csv > $OUT/${R}_bench.json 2> $OUT/${R}_bench.err; tail -c 300 $OUT/${R}_bench.json; echo
+for i in 1 2 3; do python bench.py --full --no-cpu-baseline --no-roi-load --no-fp32-pipe --steps 300 --power-csv $OUT/${R}_power_run$i.csv > $OUT/${R}_bench_run$i.json 2>/dev/null; done
+python bench.py --full --no-cpu-baseline --no-roi-load --no-fp32-pipe --in-flight 0 --fixed-load > $OUT/${R}_bench_fixed_load.json 2>/dev/null
+python bench.py --full --batch 64 --steps 30 --no-cpu-baseline --no-fp32-pipe --no-roi-load > $OUT/${R}_bench_b64.json 2>/dev/null
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-roi-load --no-fp32-pipe --in-flight 0 > $OUT/${R}_bench_under_rocprof.json 2>/dev/null
 cp /tmp/prof/*/*kernel_stats.csv $OUT/${R}_kernel_stats.csv; head -8 $OUT/${R}_kernel_stats.csv | cut -c1-140
 cd $GRAFT_REPO_ROOT
 if [ "$1" != "quick" ]; then
   timeout 900 python tools/bench_wsi.py > $OUT/${R}_bench_wsi.json 2> $OUT/${R}_bench_wsi.err; tail -c 400 $OUT/${R}_bench_wsi.json; echo
-  timeout 1500 python bench.py --cpu-full --no-roi-load --no-fp32-pipe --steps 20 > $OUT/${R}_cpu_baseline_full.json 2> $OUT/${R}_cpu_baseline_full.err; tail -c 700 $OUT/${R}_cpu_baseline_full.json; echo
+  timeout 1500 python bench.py --full --cpu-full --no-roi-load --no-fp32-pipe --steps 20 > $OUT/${R}_cpu_baseline_full.json 2> $OUT/${R}_cpu_baseline_full.err; tail -c 700 $OUT/${R}_cpu_baseline_full.json; echo
 fi
