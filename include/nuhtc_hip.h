@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define NUHTC_ABI_VERSION 10
+#define NUHTC_ABI_VERSION 11
 
 enum {
   NUHTC_OK = 0,
@@ -112,6 +112,10 @@ typedef struct nuhtc_config {
                               * feature maps are on a CUDA device -- it casts that branch to fp16 there (nuhtc/models/roi_extractors_cus.py:203,231):
                               * every tensor operation of :231-237 rounds to fp16 (reductions accumulate in fp32), the fp16 result is added
                               * into the fp32 RoI features.  Only the level-2 / level-3 tables change; see INTEGRATION.md section 6. */
+  int32_t features_only;     /* 0 (default): the detection engine.  1 (v11): an engine for nuhtc_features only -- nuhtc_finalize requires and
+                              * packs the backbone.* / neck.* tensors alone (nuhtc_load_weight accepts the checkpoint's other tensors of the
+                              * schema and drops them), no workspace is allocated for the heads or the RoI path (max_batch can then be large),
+                              * nuhtc_infer / nuhtc_infer_fixed_load return NUHTC_E_STATE. */
 } nuhtc_config;
 
 /* Fills `cfg` with the PanNuke defaults listed above. */
@@ -149,6 +153,14 @@ typedef struct nuhtc_dets {
  * detections.  Replaces `inference_detector(model, [ndarray]*B)` (mmdet/apis/inference.py:90) and,
  * when out->keep != NULL, tools/infer_wsi.py:510-531.  Enqueues on `stream`; does not synchronise. */
 int nuhtc_infer(nuhtc_engine* e, const uint8_t* tiles_dev, int B, int channel_mode, void* stream, const nuhtc_dets* out);
+
+/* Tile embeddings (v11): B tiles (B <= max_batch) as for nuhtc_infer -> feat_dev [B][256] float32 = the per-channel mean of the four FPN
+ * maps over their whole padded grid (pad_shape / 4 .. / 32), levels 0..3 of 64 channels each.  Replaces `model_feat` of the reference's
+ * tools/extract_features_nuhtc.py:37-91 (`model.extract_feat` = Swin-T + FPN, then `features_lvl[l].mean(dim=(2, 3))`, concatenated).
+ * Runs the backbone and the FPN (laterals + fpn_convs, without the semantic head's lateral in their epilogue), nothing of the heads, then
+ * the pooling (csrc/pool.hip: fp64 partials in a fixed layout, no float atomics -- bitwise the same features for a tile in any batch, on
+ * any call).  nuhtc_get_buffer("x0".."x3") returns the maps afterwards.  Enqueues on `stream`; does not synchronise. */
+int nuhtc_features(nuhtc_engine* e, const uint8_t* tiles_dev, int B, int channel_mode, void* stream, float* feat_dev);
 
 /* Fixed-load variant for benchmarking with synthetic weights: the proposal stage is
  * computed but replaced by `rois_dev` (dev [B*n_rois*4] x1,y1,x2,y2 in network pixels), and exactly

@@ -2,6 +2,7 @@
 
     init_detector(config, checkpoint=None, device='cuda:0', cfg_options=None)   nuhtc/apis/inference.py:11-57
     inference_detector(model, imgs)                                             mmdet/apis/inference.py:90-153
+    model_feat(model, imgs)                                                     tools/extract_features_nuhtc.py:37-91
 
 Same names, argument meaning and result format — `(bbox_results, segm_results)` per image with per-class (k,5) float32
 arrays in original-tile pixels and per-class lists of (H,W) bool masks.  Everything between the uint8 pixels and
@@ -62,6 +63,31 @@ class Detector:
             nc = opts.pop('num_classes')
             return EnginePipeline(self.state_dict, device=self.device, depth=depth, max_batch=self.max_batch, tile=key[:2],
                                   num_classes=nc, max_cc_proposals=self.max_cc_proposals, bind_host=self.bind_host, **opts)
+        return self._cached(key, make)
+
+    def feature_engine(self, tile_hw):
+        """A features_only engine (nuhtc_features: backbone + FPN + channel means, no heads) for tiles of `tile_hw`, cached like engine()."""
+        from .engine import Engine
+        key = ('features', int(tile_hw[0]), int(tile_hw[1]))
+
+        def make():
+            opts = dict(self.opts)
+            nc = opts.pop('num_classes')
+            return Engine(self.state_dict, device=self.device, max_batch=self.max_batch, tile=key[1:], num_classes=nc,
+                          bind_host=self.bind_host, features_only=1, **opts)
+        return self._cached(key, make)
+
+    def feature_pipeline(self, tile_hw, depth=4, max_batch=None):
+        """`depth` features_only engines of capacity `max_batch` (default: the detector's) on their own streams (EnginePipeline)."""
+        from .pipeline import EnginePipeline
+        mb = int(max_batch or self.max_batch)
+        key = ('features', int(tile_hw[0]), int(tile_hw[1]), int(depth), mb)
+
+        def make():
+            opts = dict(self.opts)
+            nc = opts.pop('num_classes')
+            return EnginePipeline(self.state_dict, device=self.device, depth=depth, max_batch=mb, tile=key[1:3], num_classes=nc,
+                                  bind_host=self.bind_host, features_only=1, **opts)
         return self._cached(key, make)
 
     def eval(self):
@@ -158,6 +184,32 @@ def inference_detector(model, imgs):
         for i, r in zip(idx, eng(np.stack([arrs[i] for i in idx]), mode)):
             results[i] = r
     return results if is_batch else results[0]
+
+
+def model_feat(model, imgs):
+    """tools/extract_features_nuhtc.py:37-91: imgs (str | ndarray | list of either) -> (N, 256) float32 ndarray, per image the means over
+    the whole padded map of the four FPN levels (`model.extract_feat(img)[l].mean(dim=(2, 3))`, levels 0..3 concatenated).  Channel
+    handling as inference_detector: ndarrays take the LoadImageFromWebcam branch (taken as BGR and swapped), paths are read as
+    tools/infer.py reads them.  Runs on the detector's features_only engines (nuhtc_features); images are grouped by size -- the reference
+    pads a mixed list to its largest member, which would put the padding of its batch mates into an image's mean."""
+    if not isinstance(imgs, (list, tuple)):
+        imgs = [imgs]
+    if len(imgs) == 0:
+        return np.zeros((0, 256), np.float32)
+    if isinstance(imgs[0], np.ndarray):
+        arrs, mode = [np.asarray(i) for i in imgs], hip.CH_SWAP
+    else:
+        arrs, mode = [_load_image_rgb(p) for p in imgs], hip.CH_AS_IS
+    for a in arrs:
+        if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8:
+            raise ValueError('images must be uint8 HxWx3')
+    by_shape = {}
+    for i, a in enumerate(arrs):
+        by_shape.setdefault(a.shape[:2], []).append(i)
+    out = np.zeros((len(arrs), 256), np.float32)
+    for hw, idx in by_shape.items():
+        out[idx] = model.feature_engine(hw).features(np.stack([arrs[i] for i in idx]), mode)
+    return out
 
 
 def concat_results(result):

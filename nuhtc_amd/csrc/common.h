@@ -228,6 +228,14 @@ int launch_conv1x1_n1(const float* x, const float* w, const float* b, float* y, 
 int launch_rownorm_inv(const float* x, float* inv, int rows, int C, hipStream_t s);
 int launch_transpose(const float* x, float* y, int batch, int rows, int cols, hipStream_t s);
 
+// ----------------------------------------------------------------------------- tile embeddings (pool.hip)
+// per-channel means of the four NHWC 64-channel FPN maps x[l] [B][hw[l]][64] -> feat [B][256] (level-major); the slab holds
+// [B][choff[4]][64] fp64 partials, POOL_CHUNK pixels of one (tile, level) per entry, level l's chunks at [choff[l], choff[l + 1])
+#define POOL_CHUNK 256
+struct PoolLevels { const float* x[4]; int hw[4]; int choff[5]; };
+int pool_chunks(const int hw[4], int choff[5]);
+int launch_fpn_mean_pool(const PoolLevels& p, int B, double* slab, float* feat, hipStream_t s);
+
 // ----------------------------------------------------------------------------- RoI path (roi.hip)
 int launch_roi_align(const float* feat, int N, int H, int W, int C, const float* rois, int R, const int* r_dev, int P,
                      float scale, int sr, float* out, int accumulate, hipStream_t s);

@@ -88,6 +88,9 @@ struct nuhtc_engine {
                                // written by the epilogue of the GEMM that produced the tensor (proj, fc2, patch merging), read by the next A_LN linear
   float *c[4], *lat[4], *x[4], *rpn[4], *semg[4];
   float *tmpA, *tmpB, *tmpR, *sem_feat, *sem_pred, *x0sem;   // tmpR: RPN conv output (side stream)
+  // nuhtc_features (pool.hip): the four maps x[l], their chunk layout and the fp64 partials of the mean
+  PoolLevels pool{};
+  double* pool_slab = nullptr;
   // proposals / roi path
   int roi_cap = 0;          // rois per tile: max_cc_proposals + rpn_max_per_img
   int cand_cap = 0;         // rpn candidates per tile (<= 4 * nms_pre), det candidates per tile
@@ -113,5 +116,8 @@ int alloc_roi_workspace(nuhtc_engine* e);
 int run_roi_path(nuhtc_engine* e, int B, const float* rois_fixed, int n_rois, int n_dets, hipStream_t s, const nuhtc_dets* out);
 int run_backbone(nuhtc_engine* e, int B, hipStream_t s);
 int run_neck_heads(nuhtc_engine* e, int B, hipStream_t s);
+// the FPN half of run_neck_heads (laterals + fpn_convs -> x[0..3]); sem_lateral: the semantic head's lateral 1x1 rides in the
+// fpn_convs' epilogue (Conv3Fuse, detection path) -- off for nuhtc_features
+int run_fpn(nuhtc_engine* e, int B, hipStream_t s, bool sem_lateral);
 int launch_conv1x1_n1_dev(const float* x, const float* w, const float* b, float* y, int rows_cap, const int* rows_dev, int rows_mul,
                           int sigmoid, hipStream_t s);

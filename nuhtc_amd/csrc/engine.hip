@@ -35,6 +35,7 @@ void nuhtc_default_config(nuhtc_config* c) {
   c->matrix_pipe = NUHTC_PIPE_BF16_SPLIT;
   c->schedule = NUHTC_SCHED_LATENCY;
   c->att_pool_fp16 = 0;
+  c->features_only = 0;
 }
 
 const char* nuhtc_last_error(const nuhtc_engine* e) { return e ? e->err.c_str() : g_create_error.c_str(); }
@@ -63,6 +64,7 @@ int nuhtc_create(const nuhtc_config* cfg, int device, nuhtc_engine** out) {
   if (cfg->max_cc_proposals < 0 || cfg->max_cc_proposals > 4096) { g_create_error = "max_cc_proposals out of range"; return NUHTC_E_INVALID; }
   if (cfg->schedule != NUHTC_SCHED_LATENCY && cfg->schedule != NUHTC_SCHED_THROUGHPUT) { g_create_error = "schedule must be NUHTC_SCHED_LATENCY or NUHTC_SCHED_THROUGHPUT"; return NUHTC_E_INVALID; }
   if (cfg->att_pool_fp16 != 0 && cfg->att_pool_fp16 != 1) { g_create_error = "att_pool_fp16 must be 0 or 1"; return NUHTC_E_INVALID; }
+  if (cfg->features_only != 0 && cfg->features_only != 1) { g_create_error = "features_only must be 0 or 1"; return NUHTC_E_INVALID; }
   if (cfg->matrix_pipe != NUHTC_PIPE_BF16_SPLIT && cfg->matrix_pipe != NUHTC_PIPE_FP32) { g_create_error = "matrix_pipe must be NUHTC_PIPE_BF16_SPLIT or NUHTC_PIPE_FP32"; return NUHTC_E_INVALID; }
   {
     const char* probes[4] = {nuhtc_tu_probe_conv(), nuhtc_tu_probe_gemm(), nuhtc_tu_probe_mlp(), nuhtc_tu_probe_swin()};
@@ -165,6 +167,8 @@ int nuhtc_load_weight(nuhtc_engine* e, const char* name, const float* host, cons
   size_t n = 1;
   for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= (size_t)shape[i]; }
   if (t.shape != it->second) FAIL(e, NUHTC_E_INVALID, std::string("nuhtc_load_weight: bad shape for ") + name);
+  // a features-only engine keeps the backbone and the neck: the heads' tensors of a full checkpoint are accepted and dropped
+  if (e->cfg.features_only && strncmp(name, "backbone.", 9) != 0 && strncmp(name, "neck.", 5) != 0) return 0;
   t.data.assign(host, host + n);
   e->raw[name] = std::move(t);
   return 0;
@@ -520,8 +524,16 @@ int nuhtc_finalize(nuhtc_engine* e) {
       if ((rc = upload_gemm_weight(e, &e->lat_wln[i], wl, 64, C)) || (rc = upload(e, &e->lat_bln[i], bl))) return rc;
     }
   }
+  {      // ---- nuhtc_features: chunk layout of the four maps and the slab of the pooling's partial sums (csrc/pool.hip)
+    int hw[4];
+    for (int l = 0; l < 4; ++l) hw[l] = e->st[l].H * e->st[l].W;
+    if ((rc = pool_chunks(hw, e->pool.choff))) FAIL(e, rc, "pool_chunks: empty FPN level");
+    for (int l = 0; l < 4; ++l) e->pool.hw[l] = hw[l];
+    if ((rc = dev_alloc(e, (void**)&e->pool_slab, (size_t)B * e->pool.choff[4] * 64 * sizeof(double)))) return rc;
+  }
+  const bool heads = !c.features_only;      // a features-only engine packs and allocates nothing behind the FPN
   // ---- RPN: 3x3 conv, then cls(3)+reg(12) fused into one N=32 pointwise layer (cols 0-2 cls, 3-14 reg, rest 0)
-  {
+  if (heads) {
     RAW(cw, "rpn_head.rpn_conv.weight", 64, 64, 3, 3); RAW(cb, "rpn_head.rpn_conv.bias", 64);
     RAW(kw, "rpn_head.rpn_cls.weight", 3, 64, 1, 1); RAW(kb, "rpn_head.rpn_cls.bias", 3);
     RAW(rw, "rpn_head.rpn_reg.weight", 12, 64, 1, 1); RAW(rb, "rpn_head.rpn_reg.bias", 12);
@@ -533,7 +545,7 @@ int nuhtc_finalize(nuhtc_engine* e) {
       return rc;
   }
   // ---- semantic head
-  {
+  if (heads) {
     const std::string p = "roi_head.semantic_head.";
     for (int i = 0; i < 4; ++i) {
       RAW(lw, p + "lateral_convs." + std::to_string(i) + ".conv.weight", 64, 64, 1, 1);
@@ -550,7 +562,7 @@ int nuhtc_finalize(nuhtc_engine* e) {
         (rc = upload(e, &e->sem_gb, gb->data)))
       return rc;
   }
-  if ((rc = finalize_roi(e))) return rc;
+  if (heads && (rc = finalize_roi(e))) return rc;
 
   // ---- workspace (sized for max_batch)
   const StageGeom& g0 = e->st[0];
@@ -580,15 +592,18 @@ int nuhtc_finalize(nuhtc_engine* e) {
     const StageGeom& g = e->st[s];
     std::string n = std::to_string(s);
     if ((rc = ws(e, &e->c[s], ("c" + n).c_str(), {B, g.H, g.W, g.C}, 0)) || (rc = ws(e, &e->lat[s], ("lat" + n).c_str(), {B, g.H, g.W, 64}, 0)) ||
-        (rc = ws(e, &e->x[s], ("x" + n).c_str(), {B, g.H, g.W, 64}, 0)) || (rc = ws(e, &e->rpn[s], ("rpn" + n).c_str(), {B, g.H, g.W, 32}, 0)) ||
-        (rc = ws(e, &e->semg[s], nullptr, {B, g.H, g.W, 64}, 0)))
+        (rc = ws(e, &e->x[s], ("x" + n).c_str(), {B, g.H, g.W, 64}, 0)))
+      return rc;
+    e->pool.x[s] = e->x[s];
+    if (heads && ((rc = ws(e, &e->rpn[s], ("rpn" + n).c_str(), {B, g.H, g.W, 32}, 0)) || (rc = ws(e, &e->semg[s], nullptr, {B, g.H, g.W, 64}, 0))))
       return rc;
   }
-  if ((rc = ws(e, &e->tmpA, nullptr, {B, g0.H, g0.W, 64}, 0)) || (rc = ws(e, &e->tmpB, nullptr, {B, g0.H, g0.W, 64}, 0)) ||
-      (rc = ws(e, &e->tmpR, nullptr, {B, g0.H, g0.W, 64}, 0)) ||
-      (rc = ws(e, &e->sem_feat, "sem_feat", {B, g0.H, g0.W, 64}, 0)) || (rc = ws(e, &e->x0sem, "x0sem", {B, g0.H, g0.W, 64}, 0)) || (rc = ws(e, &e->sem_pred, "sem_pred", {B, g0.H, g0.W}, 0)))
+  if (heads && ((rc = ws(e, &e->tmpA, nullptr, {B, g0.H, g0.W, 64}, 0)) || (rc = ws(e, &e->tmpB, nullptr, {B, g0.H, g0.W, 64}, 0)) ||
+                (rc = ws(e, &e->tmpR, nullptr, {B, g0.H, g0.W, 64}, 0)) ||
+                (rc = ws(e, &e->sem_feat, "sem_feat", {B, g0.H, g0.W, 64}, 0)) || (rc = ws(e, &e->x0sem, "x0sem", {B, g0.H, g0.W, 64}, 0)) ||
+                (rc = ws(e, &e->sem_pred, "sem_pred", {B, g0.H, g0.W}, 0))))
     return rc;
-  if ((rc = alloc_roi_workspace(e))) return rc;
+  if (heads && (rc = alloc_roi_workspace(e))) return rc;
   {
     // The side stream carries the RPN branch (and the mid-size RoI class) beside the main stream's semantic branch.  Its NMS
     // launches are large grids of one-wave workgroups that slow a co-running main-stream kernel tenfold while they last (a 20 us
@@ -787,7 +802,7 @@ int run_backbone(nuhtc_engine* e, int B, hipStream_t s) {
   return 0;
 }
 
-int run_neck_heads(nuhtc_engine* e, int B, hipStream_t s) {
+int run_fpn(nuhtc_engine* e, int B, hipStream_t s, bool sem_lateral) {
   // FPN (mmdet/models/necks/fpn.py:152-179): laterals coarse->fine with the nearest-upsampled coarser lateral added in the epilogue
   for (int i = 3; i >= 0; --i) {
     const StageGeom& g = e->st[i];
@@ -799,19 +814,24 @@ int run_neck_heads(nuhtc_engine* e, int B, hipStream_t s) {
     if (i < 3) { p.up = e->lat[i + 1]; p.upH = g.H; p.upW = g.W; }
     RUN(egemm(e, p, s));
   }
-  // Pointwise layers that follow a 3x3 convolution are computed in that convolution's epilogue on the split pipe (conv.hip,
-  // Conv3Fuse): the semantic head's lateral 1x1 rides on the FPN output conv of its level, the RPN's cls + reg layer on the RPN
-  // conv (whose output is then never stored), conv_logits + conv_embedding (+ x0 + sem) on the semantic head's last conv.
-  const bool fuse = e->rpn_hf && conv3_fuse_available();
   for (int i = 0; i < 4; ++i) {
     const StageGeom& g = e->st[i];
-    if (fuse) {
+    if (sem_lateral) {
       const Conv3Fuse f = pointwise(64, e->sem_lf[i], e->sem_lb[i], e->semg[i], ACT_NONE, 1);
       RUN(conv3x3(e, e->lat[i], e->fpn_w[i], e->fpn_b[i], e->x[i], B, g.H, g.W, ACT_NONE, nullptr, 1, s, &f));
     } else {
       RUN(conv3x3(e, e->lat[i], e->fpn_w[i], e->fpn_b[i], e->x[i], B, g.H, g.W, ACT_NONE, nullptr, 1, s));
     }
   }
+  return 0;
+}
+
+int run_neck_heads(nuhtc_engine* e, int B, hipStream_t s) {
+  // Pointwise layers that follow a 3x3 convolution are computed in that convolution's epilogue on the split pipe (conv.hip,
+  // Conv3Fuse): the semantic head's lateral 1x1 rides on the FPN output conv of its level, the RPN's cls + reg layer on the RPN
+  // conv (whose output is then never stored), conv_logits + conv_embedding (+ x0 + sem) on the semantic head's last conv.
+  const bool fuse = e->rpn_hf && conv3_fuse_available();
+  RUN(run_fpn(e, B, s, fuse));
   // RPN head (mmdet/models/dense_heads/rpn_head.py:62-68).  The RPN branch (conv + 1x1 heads here, proposal selection and
   // NMS in run_roi_path) and the semantic branch below both depend only on the FPN maps: the RPN branch runs on the side
   // stream from here on, so the tails of either branch's launches are filled by the other's blocks; joined before build_rois.
@@ -882,6 +902,11 @@ static int check_infer_args(nuhtc_engine* e, const uint8_t* tiles, int B) {
   return 0;
 }
 
+static int check_detect_engine(nuhtc_engine* e) {
+  if (e->cfg.features_only) FAIL(e, NUHTC_E_STATE, "this engine was created with features_only = 1: it serves nuhtc_features only");
+  return 0;
+}
+
 // one step; a step that fails forgets the caller's tile pointer (nuhtc_get_buffer("img") reads it again: include/nuhtc_hip.h)
 static int run_step(nuhtc_engine* e, int B, const float* rois, int n_rois, int n_dets, hipStream_t s, const nuhtc_dets* out) {
   int rc = run_backbone(e, B, s);
@@ -893,7 +918,7 @@ static int run_step(nuhtc_engine* e, int B, const float* rois, int n_rois, int n
 
 int nuhtc_infer(nuhtc_engine* e, const uint8_t* tiles, int B, int channel_mode, void* stream, const nuhtc_dets* out) {
   int rc = check_infer_args(e, tiles, B);
-  if (rc) return rc;
+  if (rc || (rc = check_detect_engine(e))) return rc;
   hipStream_t s = (hipStream_t)stream;
   HIP_CHECK(e, hipSetDevice(e->device));
   e->lastB = B;
@@ -904,13 +929,29 @@ int nuhtc_infer(nuhtc_engine* e, const uint8_t* tiles, int B, int channel_mode, 
 int nuhtc_infer_fixed_load(nuhtc_engine* e, const uint8_t* tiles, int B, int channel_mode, const float* rois, int n_rois, int n_dets,
                            void* stream, const nuhtc_dets* out) {
   int rc = check_infer_args(e, tiles, B);
-  if (rc) return rc;
+  if (rc || (rc = check_detect_engine(e))) return rc;
   if (!rois || n_rois < 1 || n_rois > e->roi_cap || n_dets < 1 || n_dets > e->cfg.max_per_img) FAIL(e, NUHTC_E_INVALID, "bad fixed-load arguments");
   hipStream_t s = (hipStream_t)stream;
   HIP_CHECK(e, hipSetDevice(e->device));
   e->lastB = B;
   e->in_tiles = tiles; e->in_swap = channel_mode == NUHTC_CH_SWAP;      // the backbone's first launch reads the tiles (swin.hip patch_embed_tiles_kernel)
   return run_step(e, B, rois, n_rois, n_dets, s, out);
+}
+
+int nuhtc_features(nuhtc_engine* e, const uint8_t* tiles, int B, int channel_mode, void* stream, float* feat) {
+  int rc = check_infer_args(e, tiles, B);
+  if (rc) return rc;
+  if (!feat) FAIL(e, NUHTC_E_INVALID, "nuhtc_features: null feature buffer");
+  hipStream_t s = (hipStream_t)stream;
+  HIP_CHECK(e, hipSetDevice(e->device));
+  e->lastB = B;
+  e->in_tiles = tiles; e->in_swap = channel_mode == NUHTC_CH_SWAP;      // the backbone's first launch reads the tiles (swin.hip patch_embed_tiles_kernel)
+  // Swin-T + FPN (model.extract_feat), every launch on the caller's stream, then the means of x[0..3] (csrc/pool.hip)
+  rc = run_backbone(e, B, s);
+  if (!rc) rc = run_fpn(e, B, s, false);
+  if (!rc && (rc = launch_fpn_mean_pool(e->pool, B, e->pool_slab, feat, s))) e->err = "fpn_mean_pool launch failed";
+  if (rc) e->in_tiles = nullptr;
+  return rc;
 }
 
 int nuhtc_mask_contours(nuhtc_engine* e, const nuhtc_dets* dets, int B, int cap, int16_t* xy, int32_t* n, void* stream) {

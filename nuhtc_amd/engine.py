@@ -106,9 +106,17 @@ class Engine:
         # a stream of the engine's own (nuhtc_stream): EnginePipeline runs the engine on it; any other stream works as well
         self.stream = torch.cuda.ExternalStream(self.lib.nuhtc_stream(self.h), device=self.device)
         B, K = cfg.max_batch, cfg.max_per_img
+        self.features_only = bool(cfg.features_only)
+        if self.features_only:         # (nuhtc_features only: no detection buffers; nuhtc_infer refuses the engine before it reads `dets`)
+            with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+                self.feat = torch.zeros(B, 256, dtype=torch.float32, device=self.device)
+            self.stream.synchronize()
+            self.dets = hip.Dets()
+            return
         # allocated and zero-filled ON the engine's stream (hipStreamNonBlocking: nothing would order memsets of the caller's stream
         # before the first batch there), so the blocks also live in the allocator pool of the stream they are used on
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            self.feat = torch.zeros(B, 256, dtype=torch.float32, device=self.device)
             self.boxes = torch.zeros(B, K, 5, dtype=torch.float32, device=self.device)
             self.labels = torch.zeros(B, K, dtype=torch.int32, device=self.device)
             self.counts = torch.zeros(B, dtype=torch.int32, device=self.device)
@@ -171,6 +179,27 @@ class Engine:
         self._check(self.lib.nuhtc_infer(self.h, ctypes.c_void_p(tiles_dev.data_ptr()), B, channel_mode, self._stream(),
                                          ctypes.byref(self.dets)))
         return B
+
+    def features_async(self, tiles_dev, channel_mode=hip.CH_AS_IS, out=None):
+        """Enqueue backbone + FPN + the per-level channel means (nuhtc_features) for a device-resident batch; the (B, 256) float32
+        embeddings land in self.feat[:B], or in `out` (a contiguous (B, 256) float32 device tensor).  Returns B."""
+        B = tiles_dev.shape[0]
+        dst = self.feat if out is None else out
+        if dst.dtype != torch.float32 or not dst.is_contiguous() or dst.shape[0] < B or tuple(dst.shape[1:]) != (256,) or dst.device != self.device:
+            raise ValueError('features_async: out must be a contiguous float32 (B, 256) tensor on the engine\'s device')
+        self._last_tiles = tiles_dev
+        self._check(self.lib.nuhtc_features(self.h, ctypes.c_void_p(tiles_dev.data_ptr()), B, channel_mode, self._stream(),
+                                            ctypes.c_void_p(dst.data_ptr())))
+        return B
+
+    def features(self, tiles, channel_mode=hip.CH_AS_IS):
+        """(N, H, W, 3) uint8 tiles (host or device) -> (N, 256) float32 ndarray: per tile the channel means of the FPN levels 0..3
+        over the padded grid (the reference's `model_feat`), max_batch tiles per call."""
+        t = self.to_device(tiles)
+        out = torch.empty(t.shape[0], 256, dtype=torch.float32, device=self.device)
+        for i in range(0, t.shape[0], self.cfg.max_batch):
+            self.features_async(t[i:i + self.cfg.max_batch], channel_mode, out=out[i:i + self.cfg.max_batch])
+        return out.cpu().numpy()
 
     def infer_fixed_load_async(self, tiles_dev, rois_dev, n_dets, channel_mode=hip.CH_AS_IS):
         B, n_rois = tiles_dev.shape[0], rois_dev.shape[1]

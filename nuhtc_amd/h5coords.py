@@ -5,6 +5,10 @@ origins, chunks (1, 2), maxshape (None, 2) -- the reference appends contour by c
 (int64 scalars), `downsample` (float64 (2,)), `downsampled_level_dim`, `level_dim` (int64 (2,)), `name`, `save_path` (variable-length UTF-8
 strings).  Read by Whole_Slide_Bag_FP (:862-865: `coords`, attrs `patch_level`, `patch_size`).
 
+The feature files of tools/extract_features_nuhtc.py, h5_files/<slide_id>.h5 (`write_features` / `read_features`): the same save_hdf5, called
+once per batch with {'features': float32 (B, 256), 'coords': int64 (B, 2)} -- two datasets in that order, chunks (1,) + row shape, maxshape
+(None,) + row shape, no attributes.
+
 Two back ends, the same file either way: `h5py` where it is importable (the reference's own dependency), else the HDF5 C library through
 ctypes (libhdf5 >= 1.10: NUHTC_HDF5_LIB, the loader's search path, then the usual install prefixes).  Neither present: `available()` is False
 and read / write raise -- the `.npz` twin (nuhtc_amd.slides.save_coords) is then the only coordinate file."""
@@ -69,12 +73,14 @@ def _lib():
             'H5Aget_space': (H, [H]), 'H5Aclose': (I, [H]), 'H5Aexists': (I, [H, CP]),
             'H5Tcopy': (H, [H]), 'H5Tset_size': (I, [H, S]), 'H5Tset_cset': (I, [H, I]), 'H5Tget_class': (I, [H]), 'H5Tget_size': (S, [H]),
             'H5Tis_variable_str': (I, [H]), 'H5Tclose': (I, [H]), 'H5free_memory': (I, [P]),
+            'H5Lget_name_by_idx': (ctypes.c_ssize_t, [H, CP, I, I, _hsz, CP, S, H]),
         }
         try:
             for name, (res, args) in proto.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = res, args
-            lib._ids = {n: _hid.in_dll(lib, n + '_g').value for n in ('H5T_NATIVE_INT64', 'H5T_NATIVE_DOUBLE', 'H5T_STD_I64LE', 'H5T_IEEE_F64LE', 'H5T_C_S1')}
+            lib._ids = {n: _hid.in_dll(lib, n + '_g').value for n in ('H5T_NATIVE_INT64', 'H5T_NATIVE_DOUBLE', 'H5T_STD_I64LE', 'H5T_IEEE_F64LE', 'H5T_C_S1',
+                                                              'H5T_NATIVE_FLOAT', 'H5T_IEEE_F32LE')}
             lib._ids['H5P_DATASET_CREATE'] = _hid.in_dll(lib, 'H5P_CLS_DATASET_CREATE_ID_g').value
         except (AttributeError, ValueError):
             continue
@@ -290,3 +296,129 @@ def write_coords(path, coords, attrs):
     finally:
         lib.H5Fclose(f)
     return path
+
+
+FEATURE_DATASETS = ('features', 'coords')      # save_hdf5's order: the keys of tools/extract_features_nuhtc.py:177 asset_dict
+
+
+def write_features(path, features, coords):
+    """h5_files/<slide_id>.h5 as the reference's save_hdf5 leaves it after its batches: `features` float32 (n, F) and `coords` int64 (n, 2),
+    each chunked (1,) + row shape with maxshape (None,) + row shape, no attributes (tools/wsi_core/wsi_utils.py:66-85)."""
+    arrays = dict(features=np.ascontiguousarray(np.asarray(features, np.float32)), coords=np.ascontiguousarray(np.asarray(coords, np.int64).reshape(-1, 2)))
+    if arrays['features'].ndim != 2 or len(arrays['features']) != len(arrays['coords']):
+        raise ValueError('write_features: features must be (n, F) with one row per coordinate')
+    h5 = _h5py()
+    if h5 is not None:
+        with h5.File(path, 'w') as f:
+            for k in FEATURE_DATASETS:
+                a = arrays[k]
+                d = f.create_dataset(k, shape=a.shape, maxshape=(None,) + a.shape[1:], chunks=(1,) + a.shape[1:], dtype=a.dtype)
+                d[:] = a
+        return path
+    lib = _lib()
+    if lib is None:
+        raise H5Error('no HDF5 back end (neither h5py nor libhdf5 >= 1.10; set NUHTC_HDF5_LIB)')
+    f = lib.H5Fcreate(os.fsencode(path), 2, 0, 0)      # H5F_ACC_TRUNC
+    if f < 0:
+        raise H5Error(f'cannot create {path}')
+    try:
+        for k in FEATURE_DATASETS:
+            a = arrays[k]
+            n, w = a.shape
+            ftype, mtype = ((lib._ids['H5T_IEEE_F32LE'], lib._ids['H5T_NATIVE_FLOAT']) if k == 'features' else
+                            (lib._ids['H5T_STD_I64LE'], lib._ids['H5T_NATIVE_INT64']))
+            dims, maxd, chunk = (_hsz * 2)(n, w), (_hsz * 2)(_UNLIMITED, w), (_hsz * 2)(1, w)
+            space = _ck(lib.H5Screate_simple(2, dims, maxd), 'H5Screate_simple')
+            plist = _ck(lib.H5Pcreate(lib._ids['H5P_DATASET_CREATE']), 'H5Pcreate')
+            _ck(lib.H5Pset_chunk(plist, 2, chunk), 'H5Pset_chunk')
+            lib.H5Pset_fill_time(plist, 0)      # H5D_FILL_TIME_ALLOC, as h5py
+            d = lib.H5Dcreate2(f, k.encode(), ftype, space, 0, plist, 0)
+            lib.H5Pclose(plist); lib.H5Sclose(space)
+            _ck(d, 'H5Dcreate2')
+            try:
+                if n:
+                    _ck(lib.H5Dwrite(d, mtype, 0, 0, 0, a.ctypes.data_as(ctypes.c_void_p)), 'H5Dwrite')
+            finally:
+                lib.H5Dclose(d)
+    finally:
+        lib.H5Fclose(f)
+    return path
+
+
+def read_features(path):
+    """-> dict(features=float32 (n, F), coords=int64 (n, 2), names=[dataset names in the file], dtypes / chunks / maxshape / attrs = {name: ...})
+    of a feature file (the layout check of tests; tools read `features` as the reference does, tools/extract_features_nuhtc.py:262-266)."""
+    h5 = _h5py()
+    if h5 is not None:
+        with h5.File(path, 'r') as f:
+            names = sorted(f.keys())
+            out = dict(names=names, dtypes={}, chunks={}, maxshape={}, attrs={})
+            for k in names:
+                d = f[k]
+                out[k] = d[:]
+                out['dtypes'][k], out['chunks'][k], out['maxshape'][k] = d.dtype, d.chunks, d.maxshape
+                out['attrs'][k] = dict(d.attrs)
+            return out
+    lib = _lib()
+    if lib is None:
+        raise H5Error('no HDF5 back end (neither h5py nor libhdf5 >= 1.10; set NUHTC_HDF5_LIB)')
+    f = lib.H5Fopen(os.fsencode(path), 0, 0)      # H5F_ACC_RDONLY
+    if f < 0:
+        raise H5Error(f'cannot open {path} as HDF5')
+    try:
+        names, i = [], 0
+        while True:
+            n = lib.H5Lget_name_by_idx(f, b'.', 0, 0, i, None, 0, 0)      # H5_INDEX_NAME, H5_ITER_INC
+            if n < 0:
+                break
+            buf = ctypes.create_string_buffer(int(n) + 1)
+            lib.H5Lget_name_by_idx(f, b'.', 0, 0, i, buf, int(n) + 1, 0)
+            names.append(buf.value.decode())
+            i += 1
+        out = dict(names=names, dtypes={}, chunks={}, maxshape={}, attrs={})
+        for k in names:
+            d = _ck(lib.H5Dopen2(f, k.encode(), 0), 'H5Dopen2')
+            try:
+                space = _ck(lib.H5Dget_space(d), 'H5Dget_space')
+                shape, maxshape = _dims(lib, space)
+                lib.H5Sclose(space)
+                typ = _ck(lib.H5Dget_type(d), 'H5Dget_type')
+                cls, size = lib.H5Tget_class(typ), int(lib.H5Tget_size(typ))
+                lib.H5Tclose(typ)
+                if cls == _H5T_FLOAT and size == 4:
+                    a, mtype = np.empty(shape, np.float32), lib._ids['H5T_NATIVE_FLOAT']
+                elif cls == _H5T_FLOAT:
+                    a, mtype = np.empty(shape, np.float64), lib._ids['H5T_NATIVE_DOUBLE']
+                elif cls == _H5T_INTEGER:
+                    a, mtype = np.empty(shape, np.int64), lib._ids['H5T_NATIVE_INT64']
+                else:
+                    raise H5Error(f'{path}: dataset {k} is neither integer nor float')
+                if a.size:
+                    _ck(lib.H5Dread(d, mtype, 0, 0, 0, a.ctypes.data_as(ctypes.c_void_p)), 'H5Dread')
+                plist = _ck(lib.H5Dget_create_plist(d), 'H5Dget_create_plist')
+                chunks = None
+                if lib.H5Pget_layout(plist) == 2:      # H5D_CHUNKED
+                    c = (_hsz * len(shape))()
+                    _ck(lib.H5Pget_chunk(plist, len(shape), c), 'H5Pget_chunk')
+                    chunks = tuple(int(v) for v in c)
+                lib.H5Pclose(plist)
+                attrs, j = {}, 0
+                while True:
+                    at = lib.H5Aopen_by_idx(d, b'.', 0, 0, j, 0, 0)
+                    if at < 0:
+                        break
+                    try:
+                        nn = lib.H5Aget_name(at, 0, None)
+                        buf = ctypes.create_string_buffer(int(nn) + 1)
+                        lib.H5Aget_name(at, int(nn) + 1, buf)
+                        attrs[buf.value.decode()] = _read_attr(lib, at)
+                    finally:
+                        lib.H5Aclose(at)
+                    j += 1
+                out[k] = a
+                out['dtypes'][k], out['chunks'][k], out['maxshape'][k], out['attrs'][k] = a.dtype, chunks, tuple(maxshape), attrs
+            finally:
+                lib.H5Dclose(d)
+        return out
+    finally:
+        lib.H5Fclose(f)

@@ -9,6 +9,8 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libnuhtc_hip.so')
 
+ABI_VERSION = 11          # NUHTC_ABI_VERSION of include/nuhtc_hip.h: the layout of Config below
+
 OK, E_INVALID, E_HIP, E_STATE, E_CAPACITY, E_NOTFOUND = 0, -1, -2, -3, -4, -5
 CH_AS_IS, CH_SWAP = 0, 1
 OVERLAP_MASK, OVERLAP_POLYGON = 0, 1
@@ -29,6 +31,7 @@ class Config(ctypes.Structure):
         ('stage_stds', (ctypes.c_float * 4) * 3),
         ('margin', ctypes.c_int32), ('min_area', ctypes.c_int32), ('mask_nms_thr', ctypes.c_float),
         ('matrix_pipe', ctypes.c_int32), ('schedule', ctypes.c_int32), ('att_pool_fp16', ctypes.c_int32),
+        ('features_only', ctypes.c_int32),
     ]
 
 
@@ -42,7 +45,7 @@ EXPORTS = ['nuhtc_default_config', 'nuhtc_create', 'nuhtc_destroy', 'nuhtc_last_
            'nuhtc_op_gemm', 'nuhtc_op_gemm_split', 'nuhtc_op_roi_align', 'nuhtc_op_nms', 'nuhtc_profile_enable', 'nuhtc_profile_read', 'nuhtc_dev_knob', 'nuhtc_export_crops',
            'nuhtc_mask_contours', 'nuhtc_merge_overlap', 'nuhtc_export_kept', 'nuhtc_clock_probe', 'nuhtc_op_swin_mlp', 'nuhtc_stream', 'nuhtc_op_swin_proj_mlp', 'nuhtc_bind_host_thread',
            'nuhtc_bind_host_thread_pci', 'nuhtc_bind_host_thread_at', 'nuhtc_restore_host_thread', 'nuhtc_op_ln_gemm', 'nuhtc_op_gemm_ln_gemm', 'nuhtc_op_merge_ln_gemm', 'nuhtc_write_ring_features',
-           'nuhtc_write_point_features', 'nuhtc_join_features', 'nuhtc_fill_rings']
+           'nuhtc_write_point_features', 'nuhtc_join_features', 'nuhtc_fill_rings', 'nuhtc_features']
 
 _lib = None
 
@@ -70,6 +73,7 @@ def load():
     lib.nuhtc_load_weight.argtypes = [vp, ctypes.c_char_p, vp, ctypes.POINTER(ctypes.c_int64), ci]
     lib.nuhtc_finalize.argtypes = [vp]
     lib.nuhtc_infer.argtypes = [vp, vp, ci, ci, vp, ctypes.POINTER(Dets)]
+    lib.nuhtc_features.argtypes = [vp, vp, ci, ci, vp, vp]
     lib.nuhtc_infer_fixed_load.argtypes = [vp, vp, ci, ci, vp, ci, ci, vp, ctypes.POINTER(Dets)]
     lib.nuhtc_check.argtypes = [vp, vp]
     lib.nuhtc_get_buffer.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64),
@@ -118,6 +122,8 @@ def load():
 def default_config():
     cfg = Config()
     load().nuhtc_default_config(ctypes.byref(cfg))
+    if cfg.abi_version != ABI_VERSION:
+        raise ImportError(f'{LIB_PATH} speaks ABI {cfg.abi_version}, this binding {ABI_VERSION}: rebuild it (`python -m nuhtc_amd.build --force`)')
     return cfg
 
 

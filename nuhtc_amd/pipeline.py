@@ -34,6 +34,9 @@ class EnginePipeline:
             from . import hip
             engine_kw.setdefault('schedule', hip.SCHED_THROUGHPUT)
         self.engines = [Engine(state_dict, device=device, **engine_kw) for _ in range(depth)]
+        # features_only=1 engines: submit() enqueues nuhtc_features and collect() leaves the batch's (B, 256) embeddings in last_features
+        self.features_only = bool(engine_kw.get('features_only', 0))
+        self.last_features = None
         self.device = self.engines[0].device
         # every engine runs on the stream it created next to its side streams (nuhtc_stream: three different pipes of the command
         # processor by construction, include/nuhtc_hip.h)
@@ -80,7 +83,12 @@ class EnginePipeline:
         turn = None
         with torch.cuda.stream(st):
             dev = eng.to_device(src)
-            B = eng.infer_async(dev, channel_mode)
+            if self.features_only:          # a feature batch gets an output of its own: it stays valid after the slot is resubmitted
+                feat = torch.empty(dev.shape[0], 256, dtype=torch.float32, device=self.device)
+                B = eng.features_async(dev, channel_mode, out=feat)
+                dev = (dev, feat)
+            else:
+                B = eng.infer_async(dev, channel_mode)
             if export:                      # contours + gather of the kept detections into pinned host buffers, still asynchronous
                 turn = eng.export_async(B)
             ev = torch.cuda.Event()
@@ -102,9 +110,11 @@ class EnginePipeline:
     def collect(self):
         """Oldest submitted batch: waits for it and returns (engine, B, stream, tag); read the engine's output tensors on
         `stream` (torch.cuda.stream(stream)) before submitting to that slot again -- or, for a batch submitted with export=True,
-        read `engine.export_read(pipeline.last_turn)`: the engine's own tensors may belong to the slot's next batch by then."""
-        slot, B, ev, tag, _, turn = self.pending.popleft()
+        read `engine.export_read(pipeline.last_turn)`: the engine's own tensors may belong to the slot's next batch by then.
+        A pipeline of features_only engines: the batch's (B, 256) device embeddings are `pipeline.last_features`."""
+        slot, B, ev, tag, keep, turn = self.pending.popleft()
         ev.synchronize()
+        self.last_features = keep[0][1] if self.features_only else None
         self.last_turn = turn
         self.engines[slot]._read_turn = turn      # export_read() of the returned engine reads THIS batch, not the slot's next one
         if turn is None:
