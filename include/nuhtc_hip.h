@@ -290,6 +290,19 @@ int nuhtc_op_roi_align(nuhtc_engine* e, const float* feat_nhwc, int N, int H, in
 /* mmcv nms on n boxes (n <= 16384): keep_idx[0..*count) in descending-score order (ties: lower index). */
 int nuhtc_op_nms(nuhtc_engine* e, const float* boxes, const float* scores, int n, float iou_thr, int32_t* keep_idx,
                  int32_t* count_dev, void* stream);
+/* The two halves of the connected-component ("watershed") proposals of nuhtc_infer (htc_roi_head_cus.py:283-342), as test entry points.
+ * nuhtc_op_cc_mask: semantic logits sem_pred [B,h,w] -> bilinear (align_corners) to [H,W], 5x5 Gaussian (sigma 1.1, reflect pad), > 0
+ * -> mask_out [B,H,W] uint8 (0/1).  H, W >= 2.
+ * nuhtc_op_cc_proposals: binary mask [B,H,W] -> opened_out (the mask after open(5x5, 2) when `open`, else a copy) -> filled_out
+ * (binary_fill_holes, 4-connected background) -> labels_out [B,H,W] (4-connected components of the filled mask; label = raster index
+ * of the component's first pixel within its image, -1 for background) -> stats_out [B,H*W,5] (area, xmin, ymin, xmax, ymax at the
+ * root's index; area 0 elsewhere) -> boxes_out [B,cap,4] / counts_out [B] (components with min_area < area < H*W/4 in raster order,
+ * [xmin, ymin, xmax+1, ymax+1]); *overflow_out = number of images with more than `cap` such components (cap <= 4096).
+ * Scratch is allocated per call.  Synchronises `stream`. */
+int nuhtc_op_cc_mask(nuhtc_engine* e, const float* sem_pred_dev, int B, int h, int w, int H, int W, uint8_t* mask_out_dev, void* stream);
+int nuhtc_op_cc_proposals(nuhtc_engine* e, const uint8_t* mask_dev, int B, int H, int W, int open, int min_area, int cap, uint8_t* opened_out,
+                          uint8_t* filled_out, int32_t* labels_out, int32_t* stats_out, float* boxes_out, int32_t* counts_out,
+                          int32_t* overflow_out, void* stream);
 
 /* A HIP stream owned by the engine (valid after nuhtc_finalize) that a caller MAY run this engine on,
  * and should when it keeps several engines busy at once or raises GPU_MAX_HW_QUEUES above the runtime's default of 4: the stream

@@ -68,4 +68,7 @@ int launch_nms(const NmsParams& p, int B, hipStream_t s);
 // needs cap >= sum(round_up(group counts, 64)) and n_groups * max_keep <= 8192
 int launch_nms_levels(const NmsParams& p, int B, hipStream_t s);
 int nms_set_attributes();
+// the connected-component chain in two halves (test entry points nuhtc_op_cc_mask / nuhtc_op_cc_proposals); launch_cc_proposals = both
+int launch_cc_mask(const CcParams& p, int B, hipStream_t s);
+int launch_cc_from_mask(const CcParams& p, int B, bool open, hipStream_t s);
 int launch_cc_proposals(const CcParams& p, int B, hipStream_t s);

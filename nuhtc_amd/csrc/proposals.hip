@@ -889,13 +889,14 @@ __global__ void cc_stats_init_kernel(int* __restrict__ stats, long long total) {
 }
 // roots that pass the area filter are appended (unordered) to a per-image list by all pixels in parallel ...
 __global__ void cc_collect_kernel(const int* __restrict__ lab, const int* __restrict__ stats, int* __restrict__ list, int* __restrict__ nlist,
-                                  int HW, int min_area, int max_area, long long total) {
+                                  int HW, int min_area, long long total) {
   long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= total) return;
   const int p = (int)(idx % HW);
   if (lab[idx] != p) return;
   const int a = stats[idx * 5];
-  if (!(a > min_area && a < max_area)) return;
+  // min_area < a < H*W/4 in true division (htc_roi_head_cus.py:302,332), i.e. 4a < HW exactly: HW/4 in integers would drop a == floor(HW/4)
+  if (!(a > min_area && 4ll * a < HW)) return;
   const int b = (int)(idx / HW);
   const int k = atomicAdd(&nlist[b], 1);
   if (k < CC_LIST_CAP) list[(long long)b * CC_LIST_CAP + k] = p;
@@ -924,12 +925,9 @@ __global__ __launch_bounds__(1024) void cc_emit_kernel(const int* __restrict__ s
   }
 }
 
-int launch_cc_proposals(const CcParams& p, int B, hipStream_t s) {
-  { static const int& skip_ = dev_knob_ref("SKIP", 0); if (skip_ & 128) return 0; }   // dev: ablation of the step (tools/dev/r04_ablate.py)
-  ProfScope ps("cc_proposals", 0, 0, s);
-  const int H = p.img_h, W = p.img_w, HW = H * W;
-  const long long total = (long long)B * HW;
-  const unsigned nb = (unsigned)((total + 255) / 256);
+// logits -> thresholded mask in p.mask_a
+int launch_cc_mask(const CcParams& p, int B, hipStream_t s) {
+  const int H = p.img_h, W = p.img_w;
   Gauss5 gk;
   {   // torchvision gaussian_blur(kernel_size=5): sigma = 0.15*5+0.35 = 1.1, float32 like torch
     float pdf[5], sum = 0.f;
@@ -939,13 +937,23 @@ int launch_cc_proposals(const CcParams& p, int B, hipStream_t s) {
     for (int i = 0; i < 5; ++i)
       for (int j = 0; j < 5; ++j) gk.k[i * 5 + j] = k1[i] * k1[j];
   }
+  hipLaunchKernelGGL(cc_mask_kernel, dim3(cdiv(W, CCM_TW), cdiv(H, CCM_TH), B), dim3(256), 0, s, p.sem_pred, p.mask_a, p.h, p.w, H, W, gk);
+  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+}
+
+// binary mask in p.mask_a -> (opening in place when `open`) -> filled mask in p.mask_b, labels, stats, boxes in raster order
+int launch_cc_from_mask(const CcParams& p, int B, bool open, hipStream_t s) {
+  const int H = p.img_h, W = p.img_w, HW = H * W;
+  const long long total = (long long)B * HW;
+  const unsigned nb = (unsigned)((total + 255) / 256);
   unsigned char *A = p.mask_a, *Bm = p.mask_b;
-  hipLaunchKernelGGL(cc_mask_kernel, dim3(cdiv(W, CCM_TW), cdiv(H, CCM_TH), B), dim3(256), 0, s, p.sem_pred, A, p.h, p.w, H, W, gk);
-  // open(5x5, 2) == erode 9x9 then dilate 9x9 (zero outside), separable
-  hipLaunchKernelGGL((morph9_kernel<0, 0>), dim3(nb), dim3(256), 0, s, A, Bm, H, W, total);
-  hipLaunchKernelGGL((morph9_kernel<0, 1>), dim3(nb), dim3(256), 0, s, Bm, A, H, W, total);
-  hipLaunchKernelGGL((morph9_kernel<1, 0>), dim3(nb), dim3(256), 0, s, A, Bm, H, W, total);
-  hipLaunchKernelGGL((morph9_kernel<1, 1>), dim3(nb), dim3(256), 0, s, Bm, A, H, W, total);
+  if (open) {
+    // open(5x5, 2) == erode 9x9 then dilate 9x9 (zero outside), separable
+    hipLaunchKernelGGL((morph9_kernel<0, 0>), dim3(nb), dim3(256), 0, s, A, Bm, H, W, total);
+    hipLaunchKernelGGL((morph9_kernel<0, 1>), dim3(nb), dim3(256), 0, s, Bm, A, H, W, total);
+    hipLaunchKernelGGL((morph9_kernel<1, 0>), dim3(nb), dim3(256), 0, s, A, Bm, H, W, total);
+    hipLaunchKernelGGL((morph9_kernel<1, 1>), dim3(nb), dim3(256), 0, s, Bm, A, H, W, total);
+  }
   // hole fill: label background, keep only border-connected background
   hipLaunchKernelGGL(ccl_init_kernel, dim3(nb), dim3(256), 0, s, A, p.labels, 0, HW, W, total);
   hipLaunchKernelGGL(ccl_merge_kernel, dim3(nb), dim3(256), 0, s, A, p.labels, 0, H, W, total);
@@ -961,7 +969,14 @@ int launch_cc_proposals(const CcParams& p, int B, hipStream_t s) {
   if ((W & 63) == 0) hipLaunchKernelGGL(cc_stats_strip_kernel, dim3(W / 64, cdiv(H, CCS_ROWS), B), dim3(256), 0, s, p.labels, p.stats, H, W);
   else hipLaunchKernelGGL(cc_stats_kernel, dim3(nb), dim3(256), 0, s, p.labels, p.stats, H, W, total);
   if (hipMemsetAsync(p.nlist, 0, sizeof(int) * B, s) != hipSuccess) return NUHTC_E_HIP;
-  hipLaunchKernelGGL(cc_collect_kernel, dim3(nb), dim3(256), 0, s, p.labels, p.stats, p.list, p.nlist, HW, p.min_area, HW / 4, total);
+  hipLaunchKernelGGL(cc_collect_kernel, dim3(nb), dim3(256), 0, s, p.labels, p.stats, p.list, p.nlist, HW, p.min_area, total);
   hipLaunchKernelGGL(cc_emit_kernel, dim3(B), dim3(1024), 0, s, p.stats, p.list, p.nlist, p.boxes, p.counts, p.overflow, HW, p.cap);
   return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+}
+
+int launch_cc_proposals(const CcParams& p, int B, hipStream_t s) {
+  { static const int& skip_ = dev_knob_ref("SKIP", 0); if (skip_ & 128) return 0; }   // dev: ablation of the step (tools/dev/r04_ablate.py)
+  ProfScope ps("cc_proposals", 0, 0, s);
+  int rc = launch_cc_mask(p, B, s);
+  return rc ? rc : launch_cc_from_mask(p, B, true, s);
 }

@@ -430,3 +430,45 @@ int nuhtc_op_nms(nuhtc_engine* e, const float* boxes, const float* scores, int n
   if (rc) FAIL(e, rc, "nms launch failed");
   return 0;
 }
+
+int nuhtc_op_cc_mask(nuhtc_engine* e, const float* sem_pred, int B, int h, int w, int H, int W, uint8_t* mask_out, void* stream) {
+  if (!e || !sem_pred || !mask_out) return NUHTC_E_INVALID;
+  if (B < 1 || h < 1 || w < 1 || H < 2 || W < 2 || (long long)H * W > (1ll << 26)) FAIL(e, NUHTC_E_INVALID, "cc_mask op: size out of range");
+  HIP_CHECK(e, hipSetDevice(e->device));
+  CcParams cp;
+  memset(&cp, 0, sizeof(cp));
+  cp.sem_pred = sem_pred; cp.h = h; cp.w = w; cp.img_h = H; cp.img_w = W; cp.mask_a = mask_out;
+  int rc = launch_cc_mask(cp, B, (hipStream_t)stream);
+  if (rc) FAIL(e, rc, "cc_mask launch failed");
+  return 0;
+}
+
+int nuhtc_op_cc_proposals(nuhtc_engine* e, const uint8_t* mask, int B, int H, int W, int open, int min_area, int cap, uint8_t* opened_out,
+                          uint8_t* filled_out, int32_t* labels_out, int32_t* stats_out, float* boxes_out, int32_t* counts_out,
+                          int32_t* overflow_out, void* stream) {
+  if (!e || !mask || !opened_out || !filled_out || !labels_out || !stats_out || !boxes_out || !counts_out || !overflow_out) return NUHTC_E_INVALID;
+  if (B < 1 || H < 1 || W < 1 || (long long)H * W > (1ll << 26) || cap < 1 || cap > CC_LIST_CAP)
+    FAIL(e, NUHTC_E_INVALID, "cc_proposals op: size out of range");
+  HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t total = (size_t)B * H * W;
+  // scratch sized for this call (test entry point: allocation cost is irrelevant)
+  unsigned char* touch;
+  int *list, *nlist;
+  HIP_CHECK(e, hipMalloc((void**)&touch, total));
+  HIP_CHECK(e, hipMalloc((void**)&list, (size_t)B * CC_LIST_CAP * sizeof(int)));
+  HIP_CHECK(e, hipMalloc((void**)&nlist, (size_t)B * sizeof(int)));
+  int rc = 0;
+  if (hipMemcpyAsync(opened_out, mask, total, hipMemcpyDeviceToDevice, s) != hipSuccess || hipMemsetAsync(overflow_out, 0, sizeof(int32_t), s) != hipSuccess)
+    rc = NUHTC_E_HIP;
+  CcParams cp;
+  memset(&cp, 0, sizeof(cp));
+  cp.img_h = H; cp.img_w = W; cp.min_area = min_area; cp.cap = cap;
+  cp.mask_a = opened_out; cp.mask_b = filled_out; cp.touch = touch; cp.labels = labels_out; cp.stats = stats_out; cp.list = list; cp.nlist = nlist;
+  cp.boxes = boxes_out; cp.counts = counts_out; cp.overflow = overflow_out;
+  if (!rc) rc = launch_cc_from_mask(cp, B, open != 0, s);
+  hipStreamSynchronize(s);
+  hipFree(touch); hipFree(list); hipFree(nlist);
+  if (rc) FAIL(e, rc, "cc_proposals launch failed");
+  return 0;
+}

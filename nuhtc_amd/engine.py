@@ -467,3 +467,29 @@ class Engine:
         self._check(self.lib.nuhtc_op_nms(self.h, boxes.data_ptr(), scores.data_ptr(), n, float(thr), keep.data_ptr(), cnt.data_ptr(),
                                           self._stream()))
         return keep[:int(cnt.item())].long()
+
+    def op_cc_mask(self, sem_pred, H, W):
+        """Thresholded mask of the connected-component proposals: semantic logits (B, h, w) on the device -> bilinear
+        (align_corners) to (H, W), 5x5 Gaussian, > 0 -> (B, H, W) uint8."""
+        B, h, w = sem_pred.shape
+        sem_pred = sem_pred.contiguous().float()
+        out = torch.empty(B, H, W, dtype=torch.uint8, device=self.device)
+        self._check(self.lib.nuhtc_op_cc_mask(self.h, sem_pred.data_ptr(), B, h, w, int(H), int(W), out.data_ptr(), self._stream()))
+        return out
+
+    def op_cc_proposals(self, mask, open=True, min_area=10, cap=512):
+        """The rest of the chain on a (B, H, W) 0/1 mask on the device: optional opening, hole filling, 4-connected labels, boxes.
+        Returns dict(opened, filled, labels (root = raster index of the component's first pixel, -1 background), stats (B, H*W, 5:
+        area, xmin, ymin, xmax, ymax at the root), area (B, H*W), boxes (B, cap, 4), counts (B,), overflow (images over cap))."""
+        B, H, W = mask.shape
+        mask = mask.contiguous().to(torch.uint8)
+        dev = dict(dtype=torch.int32, device=self.device)
+        r = dict(opened=torch.empty_like(mask), filled=torch.empty_like(mask), labels=torch.empty(B, H, W, **dev),
+                 stats=torch.empty(B, H * W, 5, **dev), boxes=torch.zeros(B, cap, 4, dtype=torch.float32, device=self.device),
+                 counts=torch.empty(B, **dev), overflow=torch.empty(1, **dev))
+        self._check(self.lib.nuhtc_op_cc_proposals(self.h, mask.data_ptr(), B, H, W, 1 if open else 0, int(min_area), int(cap),
+                                                   *(r[k].data_ptr() for k in ('opened', 'filled', 'labels', 'stats', 'boxes', 'counts', 'overflow')),
+                                                   self._stream()))
+        r['area'] = r['stats'][..., 0]
+        r['overflow'] = int(r['overflow'].item())
+        return r
