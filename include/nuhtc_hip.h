@@ -303,6 +303,40 @@ int nuhtc_op_cc_mask(nuhtc_engine* e, const float* sem_pred_dev, int B, int h, i
 int nuhtc_op_cc_proposals(nuhtc_engine* e, const uint8_t* mask_dev, int B, int H, int W, int open, int min_area, int cap, uint8_t* opened_out,
                           uint8_t* filled_out, int32_t* labels_out, int32_t* stats_out, float* boxes_out, int32_t* counts_out,
                           int32_t* overflow_out, void* stream);
+/* A 3x3 convolution 64 -> 64 (zero padding 1) with the options the engine uses, as a test entry point: the weights are packed as
+ * nuhtc_finalize packs them (private copies, freed before the call returns) and the launch goes through the engine's GEMM dispatch,
+ * so the halo kernel (csrc/conv.hip) serves pipe NUHTC_PIPE_BF16_SPLIT and the implicit-GEMM kernel (csrc/gemm.hip) NUHTC_PIPE_FP32.
+ * in / out: device NHWC [nimg][H][W][64]; w: HOST [64][64][3][3] (OIHW); bias: HOST [64] or NULL; act: 0 none, 1 relu.
+ * nimg_dev: optional device int32 image count (images >= *nimg_dev are not written).
+ * N2 = 32 / 64 fuses a pointwise layer 64 -> N2 on the activated output (split pipe only): out2 [..][N2] = act2(w2 . out + b2) with
+ * w2 / b2 HOST [N2][64] / [N2]; store_out = 0 drops `out`; out3 = res2 + out2 (N2 = 64, device [..][64]); outn1 [..] = wn1 . out + bn1
+ * (HOST [64] / [1]).  n_more <= 3 further maps (device more_in / more_out2, more_H x more_W, nimg images each) go through the same layers
+ * in the same launch (only without store_out, out3, outn1 and nimg_dev).  An option the path does not serve returns NUHTC_E_INVALID.
+ * Synchronises `stream`. */
+typedef struct nuhtc_conv3_args {
+  const float* in;
+  float* out;
+  const float* w;
+  const float* bias;
+  int32_t nimg, H, W, act;
+  const int32_t* nimg_dev;
+  int32_t pipe;
+  int32_t N2;
+  const float* w2;
+  const float* b2;
+  int32_t act2, store_out;
+  float* out2;
+  const float* res2;
+  float* out3;
+  const float* wn1;
+  const float* bn1;
+  float* outn1;
+  int32_t n_more;
+  const float* more_in[3];
+  float* more_out2[3];
+  int32_t more_H[3], more_W[3];
+} nuhtc_conv3_args;
+int nuhtc_op_conv3(nuhtc_engine* e, const nuhtc_conv3_args* a, void* stream);
 
 /* A HIP stream owned by the engine (valid after nuhtc_finalize) that a caller MAY run this engine on,
  * and should when it keeps several engines busy at once or raises GPU_MAX_HW_QUEUES above the runtime's default of 4: the stream

@@ -1095,6 +1095,63 @@ int nuhtc_op_gemm_split(nuhtc_engine* e, const float* A, const float* W_dev, con
   return 0;
 }
 
+int nuhtc_op_conv3(nuhtc_engine* e, const nuhtc_conv3_args* a, void* stream) {
+  if (!e || !a) return NUHTC_E_INVALID;
+  if (!a->in || !a->w) FAIL(e, NUHTC_E_INVALID, "conv3 op: null input or weight");
+  if (a->nimg < 1 || a->H < 1 || a->W < 1 || (long long)a->nimg * a->H * a->W * 64 >= (1ll << 31)) FAIL(e, NUHTC_E_INVALID, "conv3 op: size out of range");
+  if (a->pipe != NUHTC_PIPE_BF16_SPLIT && a->pipe != NUHTC_PIPE_FP32) FAIL(e, NUHTC_E_INVALID, "conv3 op: unknown pipe");
+  if (a->n_more < 0 || a->n_more > 3) FAIL(e, NUHTC_E_INVALID, "conv3 op: n_more out of range");
+  if (!a->N2 && (a->n_more || a->out2 || a->out3 || a->outn1 || !a->out)) FAIL(e, NUHTC_E_INVALID, "conv3 op: fused options need N2, a plain conv needs out");
+  for (int k = 0; k < a->n_more; ++k)
+    if ((long long)a->nimg * a->more_H[k] * a->more_W[k] * 64 >= (1ll << 31)) FAIL(e, NUHTC_E_INVALID, "conv3 op: further map out of range");
+  HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
+  // private device copies of the packed weights (the engine's registry is not touched), freed after the launch
+  std::vector<void*> bufs;
+  auto dev_copy = [&](const void* host, size_t bytes) -> const float* {
+    void* d = nullptr;
+    if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
+    bufs.push_back(d);
+    return hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) == hipSuccess ? (const float*)d : nullptr;
+  };
+  int rc = 0;
+  HostTensor wt;
+  wt.shape = {64, 64, 3, 3};
+  wt.data.assign(a->w, a->w + 64 * 64 * 9);
+  const std::vector<float> wp = pack_conv3(wt, 64, 64);
+  GemmParams p = gp(a->in, dev_copy(wp.data(), wp.size() * 4), a->bias ? dev_copy(a->bias, 64 * 4) : nullptr, a->out, a->nimg * a->H * a->W, 64, 576);
+  p.amode = A_CONV3; p.cH = a->H; p.cW = a->W; p.cC = 64; p.act = a->act; p.m_dev = a->nimg_dev; p.m_mul = a->H * a->W;
+  if (!p.W || (a->bias && !p.bias)) rc = NUHTC_E_HIP;
+  if (!rc && a->pipe == NUHTC_PIPE_BF16_SPLIT) {
+    void* sp = nullptr;
+    rc = gemm_make_split(wp.data(), 64, 576, &sp);
+    if (!rc) { bufs.push_back(sp); p.Wsplit = sp; }
+  }
+  Conv3Fuse f;
+  memset(&f, 0, sizeof(f));
+  if (!rc && a->N2) {
+    void* w2f = nullptr;
+    if (!a->w2) rc = NUHTC_E_INVALID;
+    else if (!(rc = conv3_pack_fuse(a->w2, a->N2, &w2f))) bufs.push_back(w2f);
+    if (!rc) {
+      f = pointwise(a->N2, w2f, a->b2 ? dev_copy(a->b2, (size_t)a->N2 * 4) : nullptr, a->out2, a->act2, a->store_out);
+      f.res2 = a->res2; f.out3 = a->out3; f.outn1 = a->outn1;
+      f.wn1 = a->wn1 ? dev_copy(a->wn1, 64 * 4) : nullptr;
+      f.bn1 = a->bn1 ? dev_copy(a->bn1, 4) : nullptr;
+      if ((a->b2 && !f.bias2) || (a->wn1 && !f.wn1) || (a->bn1 && !f.bn1)) rc = NUHTC_E_HIP;
+      f.n_more = a->n_more;
+      for (int k = 0; k < a->n_more; ++k) { f.more_in[k] = a->more_in[k]; f.more_out2[k] = a->more_out2[k]; f.more_H[k] = a->more_H[k]; f.more_W[k] = a->more_W[k]; }
+      p.fuse = &f;
+    }
+  }
+  if (!rc) rc = launch_gemm(p, s);
+  const hipError_t he = hipStreamSynchronize(s);
+  for (void* d : bufs) hipFree(d);
+  if (rc) FAIL(e, rc, "conv3 launch refused or failed (fused options: split pipe, N2 32 / 64, out3 with N2 64 and res2, n_more without store_out / out3 / outn1 / nimg_dev)");
+  if (he != hipSuccess) FAIL(e, NUHTC_E_HIP, "conv3 kernel failed");
+  return 0;
+}
+
 static int fold_ln(const float* W_host, const float* bias_host, const float* g, const float* b, int N, int K, std::vector<float>& w2, std::vector<float>& b2) {
   w2.resize((size_t)N * K); b2.resize(N);
   for (int n = 0; n < N; ++n) {

@@ -493,3 +493,37 @@ class Engine:
         r['area'] = r['stats'][..., 0]
         r['overflow'] = int(r['overflow'].item())
         return r
+
+    def op_conv3(self, x, w, bias=None, act=0, pipe='split', nimg_dev=None, N2=0, w2=None, b2=None, act2=0, store_out=1, res2=None,
+                 wn1=None, bn1=None, more=(), out=None, out2=None, out3=None, outn1=None, more_out2=None):
+        """3x3 convolution 64 -> 64 (zero padding 1) through the engine's dispatch (nuhtc_op_conv3): x (nimg, H, W, 64) NHWC on the device,
+        w (64, 64, 3, 3), bias (64,) anywhere; pipe 'split' (halo kernel, csrc/conv.hip) or 'fp32' (implicit GEMM, csrc/gemm.hip).
+        nimg_dev: device int32 (1,) image count.  N2 = 32 / 64 fuses out2 = act2(x' @ w2.T + b2) on the activated output x'; res2 (device,
+        like x) gives out3 = res2 + out2; wn1 (64,) / bn1 (1,) give outn1 = x' @ wn1 + bn1; `more` holds further maps (device, nimg
+        images each) through the same layers, whose second outputs come back in more_out2.  Outputs not given are allocated (empty).
+        Returns dict(out, out2, out3, outn1, more_out2)."""
+        nimg, H, W, C = x.shape
+        h = lambda t: np.ascontiguousarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, dtype=np.float32) if t is not None else None
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+        dp = lambda t: t.data_ptr() if t is not None else None
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
+        wh, bh, w2h, b2h, wn1h, bn1h = h(w), h(bias), h(w2), h(b2), h(wn1), h(bn1)
+        if out is None:
+            out = new(nimg, H, W, 64)
+        if N2 and out2 is None:
+            out2 = new(nimg, H, W, N2)
+        if res2 is not None and out3 is None:
+            out3 = new(nimg, H, W, 64)
+        if wn1 is not None and outn1 is None:
+            outn1 = new(nimg, H, W)
+        more = list(more)
+        if more_out2 is None:
+            more_out2 = [new(nimg, m.shape[1], m.shape[2], N2 or 32) for m in more]
+        a = hip.Conv3Args(inp=x.data_ptr(), out=dp(out), w=vp(wh), bias=vp(bh), nimg=nimg, H=H, W=W, act=int(act),
+                          nimg_dev=dp(nimg_dev), pipe=hip.PIPE_FP32 if pipe == 'fp32' else hip.PIPE_BF16_SPLIT, N2=int(N2), w2=vp(w2h),
+                          b2=vp(b2h), act2=int(act2), store_out=int(store_out), out2=dp(out2), res2=dp(res2), out3=dp(out3), wn1=vp(wn1h),
+                          bn1=vp(bn1h), outn1=dp(outn1), n_more=len(more))
+        for k, m in enumerate(more[:3]):
+            a.more_in[k], a.more_out2[k], a.more_H[k], a.more_W[k] = m.data_ptr(), more_out2[k].data_ptr(), m.shape[1], m.shape[2]
+        self._check(self.lib.nuhtc_op_conv3(self.h, ctypes.byref(a), self._stream()))
+        return dict(out=out, out2=out2, out3=out3, outn1=outn1, more_out2=more_out2)

@@ -35,6 +35,20 @@ class Config(ctypes.Structure):
     ]
 
 
+class Conv3Args(ctypes.Structure):
+    """nuhtc_conv3_args: the arguments of nuhtc_op_conv3 (a 3x3 convolution and its fused epilogue options)."""
+    _fields_ = [
+        ('inp', ctypes.c_void_p), ('out', ctypes.c_void_p), ('w', ctypes.c_void_p), ('bias', ctypes.c_void_p),
+        ('nimg', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('act', ctypes.c_int32),
+        ('nimg_dev', ctypes.c_void_p), ('pipe', ctypes.c_int32), ('N2', ctypes.c_int32),
+        ('w2', ctypes.c_void_p), ('b2', ctypes.c_void_p), ('act2', ctypes.c_int32), ('store_out', ctypes.c_int32),
+        ('out2', ctypes.c_void_p), ('res2', ctypes.c_void_p), ('out3', ctypes.c_void_p),
+        ('wn1', ctypes.c_void_p), ('bn1', ctypes.c_void_p), ('outn1', ctypes.c_void_p),
+        ('n_more', ctypes.c_int32), ('more_in', ctypes.c_void_p * 3), ('more_out2', ctypes.c_void_p * 3),
+        ('more_H', ctypes.c_int32 * 3), ('more_W', ctypes.c_int32 * 3),
+    ]
+
+
 class Dets(ctypes.Structure):
     _fields_ = [('boxes', ctypes.c_void_p), ('labels', ctypes.c_void_p), ('counts', ctypes.c_void_p),
                 ('masks', ctypes.c_void_p), ('areas', ctypes.c_void_p), ('keep', ctypes.c_void_p)]
@@ -45,7 +59,8 @@ EXPORTS = ['nuhtc_default_config', 'nuhtc_create', 'nuhtc_destroy', 'nuhtc_last_
            'nuhtc_op_gemm', 'nuhtc_op_gemm_split', 'nuhtc_op_roi_align', 'nuhtc_op_nms', 'nuhtc_profile_enable', 'nuhtc_profile_read', 'nuhtc_dev_knob', 'nuhtc_export_crops',
            'nuhtc_mask_contours', 'nuhtc_merge_overlap', 'nuhtc_export_kept', 'nuhtc_clock_probe', 'nuhtc_op_swin_mlp', 'nuhtc_stream', 'nuhtc_op_swin_proj_mlp', 'nuhtc_bind_host_thread',
            'nuhtc_bind_host_thread_pci', 'nuhtc_bind_host_thread_at', 'nuhtc_restore_host_thread', 'nuhtc_op_ln_gemm', 'nuhtc_op_gemm_ln_gemm', 'nuhtc_op_merge_ln_gemm', 'nuhtc_write_ring_features',
-           'nuhtc_write_point_features', 'nuhtc_join_features', 'nuhtc_fill_rings', 'nuhtc_features', 'nuhtc_op_cc_mask', 'nuhtc_op_cc_proposals']
+           'nuhtc_write_point_features', 'nuhtc_join_features', 'nuhtc_fill_rings', 'nuhtc_features', 'nuhtc_op_cc_mask', 'nuhtc_op_cc_proposals',
+           'nuhtc_op_conv3']
 
 _lib = None
 
@@ -89,6 +104,7 @@ def load():
     lib.nuhtc_op_nms.argtypes = [vp, vp, vp, ci, cf, vp, vp, vp]
     lib.nuhtc_op_cc_mask.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp]
     lib.nuhtc_op_cc_proposals.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.nuhtc_op_conv3.argtypes = [vp, ctypes.POINTER(Conv3Args), vp]
     lib.nuhtc_mask_contours.argtypes = [vp, ctypes.POINTER(Dets), ci, ci, vp, vp, vp]
     lib.nuhtc_merge_overlap.argtypes = [ci, vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int64, ci, ctypes.c_double, ci, ci, ci, ci, vp, vp]
     lib.nuhtc_export_kept.argtypes = [vp, ctypes.POINTER(Dets), ci, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
