@@ -50,6 +50,38 @@ struct EngineError {
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// Temporary device memory of one host call (the op entry points, nuhtc_merge_overlap): everything it hands out is freed when it goes
+// out of scope.  A failed allocation or upload returns null and clears ok(), so a caller may check once after a run of them.
+class DevScratch {
+ public:
+  DevScratch() = default;
+  DevScratch(const DevScratch&) = delete;
+  DevScratch& operator=(const DevScratch&) = delete;
+  ~DevScratch() {
+    for (void* p : ptrs_) hipFree(p);
+  }
+  template <typename T = void>
+  T* alloc(size_t bytes) {
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) { ok_ = false; return nullptr; }
+    ptrs_.push_back(p);
+    return static_cast<T*>(p);
+  }
+  template <typename T>
+  T* upload(const T* host, size_t n) {
+    T* d = alloc<T>(n * sizeof(T));
+    if (d && hipMemcpy(d, host, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) { ok_ = false; return nullptr; }
+    return d;
+  }
+  template <typename T>
+  T* upload(const std::vector<T>& v) { return upload(v.data(), v.size()); }
+  bool ok() const { return ok_; }
+
+ private:
+  std::vector<void*> ptrs_;
+  bool ok_ = true;
+};
+
 // per-kernel HIP-event timing (prof.hip); `tag` must be a string literal
 struct ProfScope {
   ProfScope(const char* tag, double flops, double bytes, hipStream_t s);
@@ -72,7 +104,7 @@ enum StoreMode { ST_PLAIN = 0, ST_ROWMAP = 1, ST_DECONV2 = 2 };
 // never leaves the registers on its way into the second product.
 struct Conv3Fuse {
   int N2;                 // output channels of the pointwise layer: 32 or 64 (its input is the convolution's 64 channels)
-  const void* w2f;        // device image of its [N2][64] weight from conv3_pack_fuse()
+  const void* w2f;        // device copy of the conv3_pack_fuse() image of its [N2][64] weight
   const float* bias2;     // [N2] or null
   float* out2;            // [M][N2]
   int act2;               // ACT_NONE / ACT_RELU
@@ -90,7 +122,8 @@ struct Conv3Fuse {
   float* more_out2[3];
   int more_H[3], more_W[3];
 };
-int conv3_pack_fuse(const float* w2_host, int N2, void** out_dev);      // caller hipFree()s the image
+// [N2][64] fp32 weight -> the image Conv3Fuse.w2f points at, on the host (the caller uploads it)
+int conv3_pack_fuse(const float* w2_host, int N2, std::vector<unsigned short>& out);
 
 struct GemmParams {
   const float* A;
@@ -147,9 +180,9 @@ struct GemmParams {
   const Conv3Fuse* fuse;        // host-side: pointwise layer fused into an A_CONV3 product (only on the conv.hip path; else NUHTC_E_INVALID)
 };
 int launch_gemm(const GemmParams& p, hipStream_t s);
-// exact three-way bf16 split of a constant weight matrix (host copy given) -> device buffer Wsplit[n][k/8][plane][8 bf16]; a launch whose
-// GemmParams.Wsplit points at it runs on the bf16 matrix pipe (gemm.hip).  The caller owns the buffer (hipFree).
-int gemm_make_split(const float* w_host, int N, int K, void** out_dev);
+// exact three-way bf16 split of a constant weight matrix [N][K] -> host image Wsplit[n][k/8][plane][8 bf16] (K % 8 == 0); a launch whose
+// GemmParams.Wsplit points at a device copy of it runs on the bf16 matrix pipe (gemm.hip)
+int gemm_make_split(const float* w_host, int N, int K, std::vector<unsigned short>& out);
 
 // 3x3 convolution 64 -> 64 with the input halo resident in LDS as bf16 planes (conv.hip); launch_gemm routes A_CONV3 products with a
 // split weight there

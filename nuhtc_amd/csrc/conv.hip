@@ -403,17 +403,10 @@ bool conv3_split_supported(const GemmParams& p) {      // (with p.fuse the point
 }
 
 // [N2][64] fp32 -> the fragment image the fused epilogue holds in registers (see conv3_split_kernel<N2>)
-static inline unsigned short cv_bf16_rn(float f) {
-  unsigned u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-  return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-static inline float cv_bf16_f(unsigned short h) { unsigned u = (unsigned)h << 16; float f; memcpy(&f, &u, 4); return f; }
-int conv3_pack_fuse(const float* w2, int N2, void** out_dev) {
+int conv3_pack_fuse(const float* w2, int N2, std::vector<unsigned short>& out) {
   if (N2 != 32 && N2 != 64) return NUHTC_E_INVALID;
   const int OB = N2 / 32;
-  std::vector<unsigned short> img((size_t)2 * OB * 2 * 3 * 64 * 8);
+  out.assign((size_t)2 * OB * 2 * 3 * 64 * 8, 0);
   for (int ch = 0; ch < 2; ++ch)
     for (int ob = 0; ob < OB; ++ob)
       for (int u = 0; u < 2; ++u)
@@ -421,18 +414,9 @@ int conv3_pack_fuse(const float* w2, int N2, void** out_dev) {
           for (int e = 0; e < 8; ++e) {
             const int i32 = lane & 31, h = lane >> 5;
             const int k = 32 * ch + 16 * u + 8 * (e >> 2) + 4 * h + (e & 3);
-            const float w = w2[(size_t)(32 * ob + i32) * 64 + k];
-            const unsigned short b1 = cv_bf16_rn(w);
-            const float r1 = w - cv_bf16_f(b1);
-            const unsigned short b2 = cv_bf16_rn(r1);
-            const unsigned short b3 = cv_bf16_rn(r1 - cv_bf16_f(b2));
             const size_t base = ((((size_t)(ch * OB + ob) * 2 + u) * 3) * 64 + lane) * 8 + e;
-            img[base] = b1; img[base + 64 * 8] = b2; img[base + 2 * 64 * 8] = b3;
+            bf16_split3(w2[(size_t)(32 * ob + i32) * 64 + k], out.data() + base, 64 * 8);
           }
-  void* d = nullptr;
-  if (hipMalloc(&d, img.size() * 2) != hipSuccess) return NUHTC_E_HIP;
-  if (hipMemcpy(d, img.data(), img.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); return NUHTC_E_HIP; }
-  *out_dev = d;
   return 0;
 }
 

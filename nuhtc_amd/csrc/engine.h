@@ -45,7 +45,6 @@ struct nuhtc_engine {
   // the entry records the [N][K] geometry the split was made for: egemm hands it out only to a launch of exactly that geometry
   struct WSplit { const void* planes; int N, K; };
   std::unordered_map<const float*, WSplit> wsplit;
-  size_t bytes_allocated = 0;
   bool finalized = false;
   bool debug_tokens = false;
   int lastB = 0;
@@ -106,8 +105,51 @@ struct nuhtc_engine {
   struct RoiWs* rw = nullptr;
 };
 
+// ---- engine construction (engine.hip): device memory that lives until nuhtc_destroy, weights from the checkpoint
+// a device allocation of the engine, rounded up to 256 bytes
+int dev_alloc(nuhtc_engine* e, void** p, size_t bytes);
+// a host image -> new engine memory (the split and stream images of the matrix pipe, see upload for typed vectors)
+int upload_bytes(nuhtc_engine* e, void** dst, const void* host, size_t bytes);
+template <typename T>
+int upload(nuhtc_engine* e, T** dst, const std::vector<T>& v) {
+  return upload_bytes(e, (void**)dst, v.data(), v.size() * sizeof(T));
+}
+// workspace of `shape` elements of T; with a name it is listed for nuhtc_get_buffer
+template <typename T>
+int ws(nuhtc_engine* e, T** p, const char* name, std::vector<int64_t> shape, int dtype) {
+  size_t n = 1;
+  for (auto d : shape) n *= (size_t)d;
+  int rc = dev_alloc(e, (void**)p, n * sizeof(T));
+  if (rc) return rc;
+  if (name) e->bufs[name] = BufInfo{(void*)*p, shape, dtype};
+  return 0;
+}
+// the checkpoint tensor `name`, which must have `shape` (null and e->err set otherwise)
+const HostTensor* raw(nuhtc_engine* e, const std::string& name, std::initializer_list<int64_t> shape);
+#define RAW(var, name, ...)                                 \
+  const HostTensor* var = raw(e, (name), {__VA_ARGS__});    \
+  if (!var) return NUHTC_E_STATE;
+// [O][I][3][3] -> [O][(ky*3+kx)*I + i]
+std::vector<float> pack_conv3(const HostTensor& w, int O, int I);
 // uploads a GEMM weight [N][K] and, unless cfg.matrix_pipe == NUHTC_PIPE_FP32, its exact bf16 split (gemm.hip) into e->wsplit
 int upload_gemm_weight(nuhtc_engine* e, float** dst, const std::vector<float>& v, int N, int K);
+
+// ---- launch sequence
+// a plain product: lda = K, ldc = N, alpha 1, everything else off
+GemmParams gp(const float* A, const float* W, const float* bias, float* C, int M, int N, int K);
+// runs a launch_* call inside a function of the engine that returns an error code; a failure is returned with e->err naming the call
+#define RUN(expr)                                                                                        \
+  do {                                                                                                   \
+    int _rc = (expr);                                                                                    \
+    if (_rc) { e->err = std::string(#expr) + " failed (" + std::to_string(_rc) + ")"; return _rc; }     \
+  } while (0)
+// the end of an op entry point (a test hook) that launched work on `s`: waits for it, then reports a refused launch (rc != 0) or a failed kernel
+inline int op_finish(nuhtc_engine* e, int rc, hipStream_t s, const char* launch_err, const char* kernel_err) {
+  const hipError_t he = hipStreamSynchronize(s);
+  if (rc) FAIL(e, rc, launch_err);
+  if (he != hipSuccess) FAIL(e, NUHTC_E_HIP, kernel_err);
+  return 0;
+}
 // launch_gemm with the split of p.W taken from the engine's table (bf16 matrix pipe) when the engine has one
 int egemm(nuhtc_engine* e, GemmParams p, hipStream_t s);
 int finalize_roi(nuhtc_engine* e);

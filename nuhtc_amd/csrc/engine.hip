@@ -175,19 +175,18 @@ int nuhtc_load_weight(nuhtc_engine* e, const char* name, const float* host, cons
 }
 
 // =============================================================================== device allocation
-static int dev_alloc(nuhtc_engine* e, void** p, size_t bytes) {
+int dev_alloc(nuhtc_engine* e, void** p, size_t bytes) {
   bytes = (bytes + 255) & ~(size_t)255;
   if (bytes == 0) bytes = 256;
   HIP_CHECK(e, hipMalloc(p, bytes));
   e->allocs.push_back(*p);
-  e->bytes_allocated += bytes;
   return 0;
 }
 
-static int upload(nuhtc_engine* e, float** dst, const std::vector<float>& v) {
-  int rc = dev_alloc(e, (void**)dst, v.size() * sizeof(float));
+int upload_bytes(nuhtc_engine* e, void** dst, const void* host, size_t bytes) {
+  int rc = dev_alloc(e, dst, bytes);
   if (rc) return rc;
-  HIP_CHECK(e, hipMemcpy(*dst, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIP_CHECK(e, hipMemcpy(*dst, host, bytes, hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -196,10 +195,11 @@ int upload_gemm_weight(nuhtc_engine* e, float** dst, const std::vector<float>& v
   if (rc) return rc;
   if (e->cfg.matrix_pipe == NUHTC_PIPE_FP32) return 0;
   if ((size_t)N * K != v.size()) FAIL(e, NUHTC_E_INVALID, "upload_gemm_weight: shape mismatch");
-  void* sp = nullptr;
-  rc = gemm_make_split(v.data(), N, K, &sp);
+  std::vector<unsigned short> split;
+  rc = gemm_make_split(v.data(), N, K, split);
   if (rc) FAIL(e, rc, "gemm_make_split failed");
-  e->allocs.push_back(sp);
+  void* sp = nullptr;
+  if ((rc = upload_bytes(e, &sp, split.data(), split.size() * 2))) return rc;
   e->wsplit[*dst] = {sp, N, K};
   return 0;
 }
@@ -227,30 +227,13 @@ static int upload_fuse(nuhtc_engine* e, void** dst, const std::vector<float>& w,
   *dst = nullptr;
   if (e->cfg.matrix_pipe != NUHTC_PIPE_BF16_SPLIT) return 0;
   if (w.size() != (size_t)N2 * 64) FAIL(e, NUHTC_E_INVALID, "upload_fuse: shape mismatch");
-  const int rc = conv3_pack_fuse(w.data(), N2, dst);
+  std::vector<unsigned short> img;
+  const int rc = conv3_pack_fuse(w.data(), N2, img);
   if (rc) FAIL(e, rc, "conv3_pack_fuse failed");
-  e->allocs.push_back(*dst);
-  return 0;
+  return upload_bytes(e, dst, img.data(), img.size() * 2);
 }
 
-static int upload_i(nuhtc_engine* e, int** dst, const std::vector<int>& v) {
-  int rc = dev_alloc(e, (void**)dst, v.size() * sizeof(int));
-  if (rc) return rc;
-  HIP_CHECK(e, hipMemcpy(*dst, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
-  return 0;
-}
-
-template <typename T>
-static int ws(nuhtc_engine* e, T** p, const char* name, std::vector<int64_t> shape, int dtype) {
-  size_t n = 1;
-  for (auto d : shape) n *= (size_t)d;
-  int rc = dev_alloc(e, (void**)p, n * sizeof(T));
-  if (rc) return rc;
-  if (name) e->bufs[name] = BufInfo{(void*)*p, shape, dtype};
-  return 0;
-}
-
-static const HostTensor* raw(nuhtc_engine* e, const std::string& name, std::initializer_list<int64_t> shape) {
+const HostTensor* raw(nuhtc_engine* e, const std::string& name, std::initializer_list<int64_t> shape) {
   auto it = e->raw.find(name);
   if (it == e->raw.end()) { e->err = "missing weight: " + name; return nullptr; }
   std::vector<int64_t> s(shape);
@@ -258,12 +241,7 @@ static const HostTensor* raw(nuhtc_engine* e, const std::string& name, std::init
   return &it->second;
 }
 
-#define RAW(var, name, ...)                                 \
-  const HostTensor* var = raw(e, (name), {__VA_ARGS__});    \
-  if (!var) return NUHTC_E_STATE;
-
-// [O][I][3][3] -> [O][(ky*3+kx)*I + i]
-static std::vector<float> pack_conv3(const HostTensor& w, int O, int I) {
+std::vector<float> pack_conv3(const HostTensor& w, int O, int I) {
   std::vector<float> p((size_t)O * 9 * I);
   for (int o = 0; o < O; ++o)
     for (int i = 0; i < I; ++i)
@@ -305,7 +283,7 @@ static int build_stage_maps(nuhtc_engine* e, int s) {
               size_t row = ((size_t)b * g.nW + (size_t)wy * (g.Wp / WS) + wx) * WS2 + py * WS + px;
               m[row] = (y < g.H && x < g.W) ? (b * g.H * g.W + y * g.W + x) : -1;
             }
-    int rc = upload_i(e, &g.map[sh], m);
+    int rc = upload(e, &g.map[sh], m);
     if (rc) return rc;
     // the non-padding window rows in window order: the QKV / proj GEMMs run on these only (padding rows of the window
     // image hold the QKV bias, see launch_layernorm_windows)
@@ -316,29 +294,29 @@ static int build_stage_maps(nuhtc_engine* e, int s) {
       ci[r] = m[r] >= 0 ? (int)ct.size() : -1;
       if (m[r] >= 0) { ct.push_back(m[r]); vr.push_back((int)r); }
     }
-    rc = upload_i(e, &g.cidx[sh], ci);
+    rc = upload(e, &g.cidx[sh], ci);
     if (rc) return rc;
-    rc = upload_i(e, &g.ctok[sh], ct);
+    rc = upload(e, &g.ctok[sh], ct);
     if (rc) return rc;
-    rc = upload_i(e, &g.vrow[sh], vr);
+    rc = upload(e, &g.vrow[sh], vr);
     if (rc) return rc;
     std::vector<int> pr;                  // padding rows: tile b's are [b * npad, (b + 1) * npad)
     for (size_t r = 0; r < m.size(); ++r)
       if (m[r] < 0) pr.push_back((int)r);
     g.npad = (int)(pr.size() / (size_t)B);
     if (pr.empty()) pr.push_back(0);
-    rc = upload_i(e, &g.prow[sh], pr);
+    rc = upload(e, &g.prow[sh], pr);
     if (rc) return rc;
     std::vector<int> pb((size_t)g.nW * 2, 0);          // 49 bits per window of the image (tile 0's windows; every tile has the same)
     for (int w = 0; w < g.nW; ++w)
       for (int j = 0; j < WS2; ++j)
         if (m[(size_t)w * WS2 + j] < 0) pb[(size_t)2 * w + (j >> 5)] |= 1 << (j & 31);
-    rc = upload_i(e, reinterpret_cast<int**>(&g.padbits[sh]), pb);
+    rc = upload(e, reinterpret_cast<int**>(&g.padbits[sh]), pb);
     if (rc) return rc;
   }
   g.bias_row = B * g.nW * WS2;
   {
-    int rc = upload_i(e, &g.brow, std::vector<int>(1, g.bias_row));
+    int rc = upload(e, &g.brow, std::vector<int>(1, g.bias_row));
     if (rc) return rc;
   }
   // shift mask on the padded grid (swin.py:197-218)
@@ -366,10 +344,44 @@ static int build_stage_maps(nuhtc_engine* e, int s) {
   }
   int rc = upload(e, &g.mask, mp);
   if (rc) return rc;
-  return upload_i(e, &g.mask_any, any);
+  return upload(e, &g.mask_any, any);
 }
 
-static int fold_ln(const float* W_host, const float* bias_host, const float* g, const float* b, int N, int K, std::vector<float>& w2, std::vector<float>& b2);
+// a LayerNorm in the A path of the linear behind it (gemm.hip A_LN): y = ((x - mean) rstd g + b) W^T + bias = rstd ((x - mean) (W diag g)^T) + (bias + W b);
+// W' = W diag(g) is rounded once to fp32 (its split is exact from there), bias' summed in fp64 (bias_host null: 0)
+static void fold_ln(const float* W_host, const float* bias_host, const float* g, const float* b, int N, int K, std::vector<float>& w2, std::vector<float>& b2) {
+  w2.resize((size_t)N * K); b2.resize(N);
+  for (int n = 0; n < N; ++n) {
+    double acc = bias_host ? bias_host[n] : 0.0;
+    for (int k = 0; k < K; ++k) {
+      w2[(size_t)n * K + k] = W_host[(size_t)n * K + k] * g[k];
+      acc += (double)W_host[(size_t)n * K + k] * (double)b[k];
+    }
+    b2[n] = (float)acc;
+  }
+}
+
+// PatchMerging of a [B][H][W][C] token tensor: norm (g, b [4C]) and reduction weight (w [2C][4C]) from nn.Unfold order k = c*4 + q
+// (q = kh*2+kw) to gather order k' = q*C + c (transformer.py:363-385), and the merged row -> its top-left token (b, 2 y2, 2 x2)
+struct MergePack {
+  std::vector<float> g, b, w;
+  std::vector<int> src;
+};
+static MergePack pack_merge(const float* g, const float* b, const float* w, int C, int B, int H, int W) {
+  MergePack m;
+  m.g.resize(4 * C); m.b.resize(4 * C); m.w.resize((size_t)2 * C * 4 * C);
+  for (int q = 0; q < 4; ++q)
+    for (int ch = 0; ch < C; ++ch) {
+      m.g[q * C + ch] = g[ch * 4 + q];
+      m.b[q * C + ch] = b[ch * 4 + q];
+      for (int n = 0; n < 2 * C; ++n) m.w[(size_t)n * 4 * C + q * C + ch] = w[(size_t)n * 4 * C + ch * 4 + q];
+    }
+  m.src.resize((size_t)B * (H / 2) * (W / 2));
+  for (int bi = 0; bi < B; ++bi)
+    for (int y2 = 0; y2 < H / 2; ++y2)
+      for (int x2 = 0; x2 < W / 2; ++x2) m.src[((size_t)bi * (H / 2) + y2) * (W / 2) + x2] = (bi * H + 2 * y2) * W + 2 * x2;
+  return m;
+}
 
 int nuhtc_finalize(nuhtc_engine* e) {
   if (!e) return NUHTC_E_INVALID;
@@ -387,7 +399,7 @@ int nuhtc_finalize(nuhtc_engine* e) {
     std::vector<int> tx, ty;
     cv_linear_tables(e->vw, e->Wv, true, tx);
     cv_linear_tables(e->vh, e->Hv, false, ty);
-    if ((rc = upload_i(e, &e->rs_xtab, tx)) || (rc = upload_i(e, &e->rs_ytab, ty))) return rc;
+    if ((rc = upload(e, &e->rs_xtab, tx)) || (rc = upload(e, &e->rs_ytab, ty))) return rc;
   }
   // ---- geometry
   for (int s = 0; s < 4; ++s) {
@@ -440,19 +452,11 @@ int nuhtc_finalize(nuhtc_engine* e) {
           (rc = upload(e, &bw.f2_b, f2b->data)))
         return rc;
       if (e->cfg.matrix_pipe == NUHTC_PIPE_BF16_SPLIT && !lnqkv_supported(C) && !mlp_supported(C)) {
-        // the two norms of the block ride in the A path of the linear behind them (gemm.hip A_LN): y = ((x - mean) rstd gamma + beta) W^T + b
-        //   = rstd ((x - mean) (W diag gamma)^T) + (b + W beta); W' is rounded once to fp32 (its split is exact from there), b' summed in fp64
+        // the two norms of the block ride in the A path of the linear behind them (gemm.hip A_LN, fold_ln)
         auto fold = [&](const std::vector<float>& W, const std::vector<float>& bias, const std::vector<float>& gam, const std::vector<float>& bet, int N,
                         float** wdev, float** bdev) -> int {
-          std::vector<float> w2((size_t)N * C), b2(N);
-          for (int n = 0; n < N; ++n) {
-            double acc = bias[n];
-            for (int k = 0; k < C; ++k) {
-              w2[(size_t)n * C + k] = W[(size_t)n * C + k] * gam[k];
-              acc += (double)W[(size_t)n * C + k] * (double)bet[k];
-            }
-            b2[n] = (float)acc;
-          }
+          std::vector<float> w2, b2;
+          fold_ln(W.data(), bias.data(), gam.data(), bet.data(), N, C, w2, b2);
           int r = upload_gemm_weight(e, wdev, w2, N, C);
           return r ? r : upload(e, bdev, b2);
         };
@@ -463,17 +467,14 @@ int nuhtc_finalize(nuhtc_engine* e) {
       if (e->cfg.matrix_pipe == NUHTC_PIPE_BF16_SPLIT && lnqkv_supported(C)) {
         std::vector<unsigned short> st;
         lnqkv_pack_stream(qw->data.data(), C, st);
-        if ((rc = dev_alloc(e, &bw.qkv_stream, st.size() * 2))) return rc;
-        HIP_CHECK(e, hipMemcpy(bw.qkv_stream, st.data(), st.size() * 2, hipMemcpyHostToDevice));
+        if ((rc = upload_bytes(e, &bw.qkv_stream, st.data(), st.size() * 2))) return rc;
       }
       if (e->cfg.matrix_pipe == NUHTC_PIPE_BF16_SPLIT && mlp_supported(C)) {
         std::vector<unsigned short> st;
         mlp_pack_stream(f1w->data.data(), f2w->data.data(), C, st);
-        if ((rc = dev_alloc(e, &bw.mlp_stream, st.size() * 2))) return rc;
-        HIP_CHECK(e, hipMemcpy(bw.mlp_stream, st.data(), st.size() * 2, hipMemcpyHostToDevice));
+        if ((rc = upload_bytes(e, &bw.mlp_stream, st.data(), st.size() * 2))) return rc;
         proj_pack_stream(pw->data.data(), C, st);
-        if ((rc = dev_alloc(e, &bw.proj_stream, st.size() * 2))) return rc;
-        HIP_CHECK(e, hipMemcpy(bw.proj_stream, st.data(), st.size() * 2, hipMemcpyHostToDevice));
+        if ((rc = upload_bytes(e, &bw.proj_stream, st.data(), st.size() * 2))) return rc;
       }
       e->blocks[s].push_back(bw);
     }
@@ -484,27 +485,17 @@ int nuhtc_finalize(nuhtc_engine* e) {
       on_g_host[s] = w->data; on_b_host[s] = b->data;
     }
     if (s < 3) {
-      // PatchMerging: nn.Unfold order k = c*4 + q (q = kh*2+kw)  ->  gather order k' = q*C + c   (transformer.py:363-385)
+      // PatchMerging: norm and reduction weight in gather order (pack_merge)
       std::string p = "backbone.stages." + std::to_string(s) + ".downsample.";
       RAW(nw, p + "norm.weight", 4 * C); RAW(nb, p + "norm.bias", 4 * C); RAW(rw, p + "reduction.weight", 2 * C, 4 * C);
-      std::vector<float> g2(4 * C), b2(4 * C), w2((size_t)2 * C * 4 * C);
-      for (int q = 0; q < 4; ++q)
-        for (int ch = 0; ch < C; ++ch) {
-          g2[q * C + ch] = nw->data[ch * 4 + q];
-          b2[q * C + ch] = nb->data[ch * 4 + q];
-          for (int n = 0; n < 2 * C; ++n) w2[(size_t)n * 4 * C + q * C + ch] = rw->data[(size_t)n * 4 * C + ch * 4 + q];
-        }
-      if ((rc = upload(e, &e->mg_g[s], g2)) || (rc = upload(e, &e->mg_b[s], b2)) || (rc = upload_gemm_weight(e, &e->mg_w[s], w2, 2 * C, 4 * C))) return rc;
-      if (e->cfg.matrix_pipe == NUHTC_PIPE_BF16_SPLIT && e->st[s].H % 2 == 0 && e->st[s].W % 2 == 0) {
+      const StageGeom& g = e->st[s];
+      const MergePack m = pack_merge(nw->data.data(), nb->data.data(), rw->data.data(), C, B, g.H, g.W);
+      if ((rc = upload(e, &e->mg_g[s], m.g)) || (rc = upload(e, &e->mg_b[s], m.b)) || (rc = upload_gemm_weight(e, &e->mg_w[s], m.w, 2 * C, 4 * C))) return rc;
+      if (e->cfg.matrix_pipe == NUHTC_PIPE_BF16_SPLIT && g.H % 2 == 0 && g.W % 2 == 0) {
         // the merging norm in the A path of the reduction linear (gemm.hip A_LN, two segments per row): W' = W diag(gamma), b' = W beta
         std::vector<float> wl, bl;
-        fold_ln(w2.data(), nullptr, g2.data(), b2.data(), 2 * C, 4 * C, wl, bl);
-        const StageGeom& g = e->st[s];
-        std::vector<int> src((size_t)B * (g.H / 2) * (g.W / 2));
-        for (int b = 0; b < B; ++b)
-          for (int y2 = 0; y2 < g.H / 2; ++y2)
-            for (int x2 = 0; x2 < g.W / 2; ++x2) src[((size_t)b * (g.H / 2) + y2) * (g.W / 2) + x2] = (b * g.H + 2 * y2) * g.W + 2 * x2;
-        if ((rc = upload_gemm_weight(e, &e->mg_wln[s], wl, 2 * C, 4 * C)) || (rc = upload(e, &e->mg_bln[s], bl)) || (rc = upload_i(e, &e->mg_src[s], src))) return rc;
+        fold_ln(m.w.data(), nullptr, m.g.data(), m.b.data(), 2 * C, 4 * C, wl, bl);
+        if ((rc = upload_gemm_weight(e, &e->mg_wln[s], wl, 2 * C, 4 * C)) || (rc = upload(e, &e->mg_bln[s], bl)) || (rc = upload(e, &e->mg_src[s], m.src))) return rc;
       }
     }
   }
@@ -639,18 +630,12 @@ int nuhtc_finalize(nuhtc_engine* e) {
 }
 
 // =============================================================================== dense part of the path
-static GemmParams gp(const float* A, const float* W, const float* bias, float* C, int M, int N, int K) {
+GemmParams gp(const float* A, const float* W, const float* bias, float* C, int M, int N, int K) {
   GemmParams p;
   memset(&p, 0, sizeof(p));
   p.A = A; p.W = W; p.bias = bias; p.C = C; p.M = M; p.N = N; p.K = K; p.lda = K; p.ldc = N; p.alpha = 1.f; p.m_mul = 1;
   return p;
 }
-
-#define RUN(expr)                                                                          \
-  do {                                                                                     \
-    int _rc = (expr);                                                                      \
-    if (_rc) { e->err = std::string(#expr) + " failed (" + std::to_string(_rc) + ")"; return _rc; } \
-  } while (0)
 
 static int conv3x3(nuhtc_engine* e, const float* in, const float* w, const float* b, float* out, int nimg, int H, int W, int act,
                    const int* m_dev, int m_mul, hipStream_t s, const Conv3Fuse* fuse = nullptr) {
@@ -1081,18 +1066,17 @@ int nuhtc_op_gemm_split(nuhtc_engine* e, const float* A, const float* W_dev, con
                         int K, int act, void* stream) {
   if (!e || !A || !W_dev || !W_host || !C) return NUHTC_E_INVALID;
   HIP_CHECK(e, hipSetDevice(e->device));
-  void* sp = nullptr;              // a private split of this call's weight: the registry of the engines' weights is not touched
-  int rc = gemm_make_split(W_host, N, K, &sp);
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<unsigned short> split;      // a private split of this call's weight: the registry of the engines' weights is not touched
+  int rc = gemm_make_split(W_host, N, K, split);
   if (rc) FAIL(e, rc, "gemm_make_split failed (K % 8)");
+  DevScratch sc;
   GemmParams p = gp(A, W_dev, bias, C, M, N, K);
   p.act = act;
-  p.Wsplit = sp;
-  rc = launch_gemm(p, (hipStream_t)stream);
-  hipError_t he = hipStreamSynchronize((hipStream_t)stream);
-  hipFree(sp);
-  if (rc) FAIL(e, rc, "gemm launch failed (K%32, N%32 required)");
-  if (he != hipSuccess) FAIL(e, NUHTC_E_HIP, "gemm kernel failed");
-  return 0;
+  p.Wsplit = sc.upload(split);
+  if (!sc.ok()) FAIL(e, NUHTC_E_HIP, "gemm_split op: scratch upload failed");
+  rc = launch_gemm(p, s);
+  return op_finish(e, rc, s, "gemm launch failed (K%32, N%32 required)", "gemm kernel failed");
 }
 
 int nuhtc_op_conv3(nuhtc_engine* e, const nuhtc_conv3_args* a, void* stream) {
@@ -1107,92 +1091,57 @@ int nuhtc_op_conv3(nuhtc_engine* e, const nuhtc_conv3_args* a, void* stream) {
   HIP_CHECK(e, hipSetDevice(e->device));
   hipStream_t s = (hipStream_t)stream;
   // private device copies of the packed weights (the engine's registry is not touched), freed after the launch
-  std::vector<void*> bufs;
-  auto dev_copy = [&](const void* host, size_t bytes) -> const float* {
-    void* d = nullptr;
-    if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
-    bufs.push_back(d);
-    return hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) == hipSuccess ? (const float*)d : nullptr;
-  };
+  DevScratch sc;
   int rc = 0;
   HostTensor wt;
   wt.shape = {64, 64, 3, 3};
   wt.data.assign(a->w, a->w + 64 * 64 * 9);
   const std::vector<float> wp = pack_conv3(wt, 64, 64);
-  GemmParams p = gp(a->in, dev_copy(wp.data(), wp.size() * 4), a->bias ? dev_copy(a->bias, 64 * 4) : nullptr, a->out, a->nimg * a->H * a->W, 64, 576);
+  GemmParams p = gp(a->in, sc.upload(wp), a->bias ? sc.upload(a->bias, 64) : nullptr, a->out, a->nimg * a->H * a->W, 64, 576);
   p.amode = A_CONV3; p.cH = a->H; p.cW = a->W; p.cC = 64; p.act = a->act; p.m_dev = a->nimg_dev; p.m_mul = a->H * a->W;
-  if (!p.W || (a->bias && !p.bias)) rc = NUHTC_E_HIP;
-  if (!rc && a->pipe == NUHTC_PIPE_BF16_SPLIT) {
-    void* sp = nullptr;
-    rc = gemm_make_split(wp.data(), 64, 576, &sp);
-    if (!rc) { bufs.push_back(sp); p.Wsplit = sp; }
+  if (a->pipe == NUHTC_PIPE_BF16_SPLIT) {
+    std::vector<unsigned short> split;
+    if (!(rc = gemm_make_split(wp.data(), 64, 576, split))) p.Wsplit = sc.upload(split);
   }
   Conv3Fuse f;
   memset(&f, 0, sizeof(f));
   if (!rc && a->N2) {
-    void* w2f = nullptr;
-    if (!a->w2) rc = NUHTC_E_INVALID;
-    else if (!(rc = conv3_pack_fuse(a->w2, a->N2, &w2f))) bufs.push_back(w2f);
+    std::vector<unsigned short> img;
+    rc = a->w2 ? conv3_pack_fuse(a->w2, a->N2, img) : NUHTC_E_INVALID;
     if (!rc) {
-      f = pointwise(a->N2, w2f, a->b2 ? dev_copy(a->b2, (size_t)a->N2 * 4) : nullptr, a->out2, a->act2, a->store_out);
+      f = pointwise(a->N2, sc.upload(img), a->b2 ? sc.upload(a->b2, a->N2) : nullptr, a->out2, a->act2, a->store_out);
       f.res2 = a->res2; f.out3 = a->out3; f.outn1 = a->outn1;
-      f.wn1 = a->wn1 ? dev_copy(a->wn1, 64 * 4) : nullptr;
-      f.bn1 = a->bn1 ? dev_copy(a->bn1, 4) : nullptr;
-      if ((a->b2 && !f.bias2) || (a->wn1 && !f.wn1) || (a->bn1 && !f.bn1)) rc = NUHTC_E_HIP;
+      f.wn1 = a->wn1 ? sc.upload(a->wn1, 64) : nullptr;
+      f.bn1 = a->bn1 ? sc.upload(a->bn1, 1) : nullptr;
       f.n_more = a->n_more;
       for (int k = 0; k < a->n_more; ++k) { f.more_in[k] = a->more_in[k]; f.more_out2[k] = a->more_out2[k]; f.more_H[k] = a->more_H[k]; f.more_W[k] = a->more_W[k]; }
       p.fuse = &f;
     }
   }
+  if (!sc.ok()) FAIL(e, NUHTC_E_HIP, "conv3 op: scratch upload failed");
   if (!rc) rc = launch_gemm(p, s);
-  const hipError_t he = hipStreamSynchronize(s);
-  for (void* d : bufs) hipFree(d);
-  if (rc) FAIL(e, rc, "conv3 launch refused or failed (fused options: split pipe, N2 32 / 64, out3 with N2 64 and res2, n_more without store_out / out3 / outn1 / nimg_dev)");
-  if (he != hipSuccess) FAIL(e, NUHTC_E_HIP, "conv3 kernel failed");
-  return 0;
-}
-
-static int fold_ln(const float* W_host, const float* bias_host, const float* g, const float* b, int N, int K, std::vector<float>& w2, std::vector<float>& b2) {
-  w2.resize((size_t)N * K); b2.resize(N);
-  for (int n = 0; n < N; ++n) {
-    double acc = bias_host ? bias_host[n] : 0.0;
-    for (int k = 0; k < K; ++k) {
-      w2[(size_t)n * K + k] = W_host[(size_t)n * K + k] * g[k];
-      acc += (double)W_host[(size_t)n * K + k] * (double)b[k];
-    }
-    b2[n] = (float)acc;
-  }
-  return 0;
+  return op_finish(e, rc, s, "conv3 launch refused or failed (fused options: split pipe, N2 32 / 64, out3 with N2 64 and res2, n_more without store_out / out3 / outn1 / nimg_dev)",
+                   "conv3 kernel failed");
 }
 
 int nuhtc_op_ln_gemm(nuhtc_engine* e, const float* X_dev, int T, const int* rows_dev, const float* W_host, const float* bias_host, const float* ln_g_host,
                      const float* ln_b_host, float* C_dev, int M, int N, int K, int act, void* stream) {
   if (!e || !X_dev || !W_host || !ln_g_host || !ln_b_host || !C_dev || M < 1 || N < 1 || K < 1 || T < 1) return NUHTC_E_INVALID;
   HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
   std::vector<float> w2, b2;
   fold_ln(W_host, bias_host, ln_g_host, ln_b_host, N, K, w2, b2);
-  void* sp = nullptr;
-  int rc = gemm_make_split(w2.data(), N, K, &sp);
+  std::vector<unsigned short> split;
+  int rc = gemm_make_split(w2.data(), N, K, split);
   if (rc) FAIL(e, rc, "gemm_make_split failed (K % 8)");
-  float *wd = nullptr, *bd = nullptr, *st = nullptr;
-  hipError_t he = hipMalloc(&wd, w2.size() * 4);
-  if (he == hipSuccess) he = hipMalloc(&bd, b2.size() * 4);
-  if (he == hipSuccess) he = hipMalloc(&st, (size_t)T * 8);
-  if (he == hipSuccess) he = hipMemcpy(wd, w2.data(), w2.size() * 4, hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipMemcpy(bd, b2.data(), b2.size() * 4, hipMemcpyHostToDevice);
-  if (he == hipSuccess) {
-    rc = launch_ln_stats(X_dev, st, T, K, (hipStream_t)stream);
-    if (!rc) {
-      GemmParams p = gp(X_dev, wd, bd, C_dev, M, N, K);
-      p.act = act; p.Wsplit = sp; p.amode = A_LN; p.ln_part = st; p.ln_nparts = 1; p.a_rows = rows_dev;
-      rc = launch_gemm(p, (hipStream_t)stream);
-    }
-    he = hipStreamSynchronize((hipStream_t)stream);
-  }
-  hipFree(sp); hipFree(wd); hipFree(bd); hipFree(st);
-  if (rc) FAIL(e, rc, "ln_gemm launch failed (N % 96, K % 32 required)");
-  if (he != hipSuccess) FAIL(e, NUHTC_E_HIP, "ln_gemm failed");
-  return 0;
+  DevScratch sc;
+  float* st = sc.alloc<float>((size_t)T * 8);
+  GemmParams p = gp(X_dev, sc.upload(w2), sc.upload(b2), C_dev, M, N, K);
+  p.act = act; p.Wsplit = sc.upload(split); p.amode = A_LN; p.ln_part = st; p.ln_nparts = 1; p.a_rows = rows_dev;
+  if (!sc.ok()) FAIL(e, NUHTC_E_HIP, "ln_gemm op: scratch upload failed");
+  rc = launch_ln_stats(X_dev, st, T, K, s);
+  if (!rc) rc = launch_gemm(p, s);
+  return op_finish(e, rc, s, "ln_gemm launch failed (N % 96, K % 32 required)", "ln_gemm failed");
 }
 
 int nuhtc_op_gemm_ln_gemm(nuhtc_engine* e, const float* A_dev, const float* Wp_host, const float* bp_host, const float* res_dev, const int* row_map_dev,
@@ -1200,83 +1149,47 @@ int nuhtc_op_gemm_ln_gemm(nuhtc_engine* e, const float* A_dev, const float* Wp_h
                           int Kp, int K, int N, int act, void* stream) {
   if (!e || !A_dev || !Wp_host || !W_host || !ln_g_host || !ln_b_host || !Y_dev || !C_dev || M < 1 || N < 1 || K < 1 || Kp < 1 || K % 96) return NUHTC_E_INVALID;
   HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
   std::vector<float> w2, b2;
   fold_ln(W_host, bias_host, ln_g_host, ln_b_host, N, K, w2, b2);
-  void *sp = nullptr, *spp = nullptr;
-  int rc = gemm_make_split(w2.data(), N, K, &sp);
-  if (!rc) rc = gemm_make_split(Wp_host, K, Kp, &spp);
-  if (rc) { hipFree(sp); FAIL(e, rc, "gemm_make_split failed (K % 8)"); }
-  float *wd = nullptr, *bd = nullptr, *st = nullptr, *wpd = nullptr, *bpd = nullptr;
-  hipError_t he = hipMalloc(&wd, w2.size() * 4);
-  if (he == hipSuccess) he = hipMalloc(&bd, b2.size() * 4);
-  if (he == hipSuccess) he = hipMalloc(&st, (size_t)M * (K / 96) * 8);
-  if (he == hipSuccess) he = hipMalloc(&wpd, (size_t)K * Kp * 4);
-  if (he == hipSuccess && bp_host) he = hipMalloc(&bpd, (size_t)K * 4);
-  if (he == hipSuccess) he = hipMemcpy(wd, w2.data(), w2.size() * 4, hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipMemcpy(bd, b2.data(), b2.size() * 4, hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipMemcpy(wpd, Wp_host, (size_t)K * Kp * 4, hipMemcpyHostToDevice);
-  if (he == hipSuccess && bp_host) he = hipMemcpy(bpd, bp_host, (size_t)K * 4, hipMemcpyHostToDevice);
-  if (he == hipSuccess) {
-    GemmParams q = gp(A_dev, wpd, bpd, Y_dev, M, K, Kp);              // the producer: Y[row_map(m)] = A Wp^T + bp (+ res), statistics on the way out
-    q.Wsplit = spp; q.stats_out = st;
-    if (res_dev) { q.res = res_dev; q.ldr = K; }
-    if (row_map_dev) { q.store = ST_ROWMAP; q.row_map = row_map_dev; }
-    rc = launch_gemm(q, (hipStream_t)stream);
-    if (!rc) {
-      GemmParams p = gp(Y_dev, wd, bd, C_dev, M, N, K);
-      p.act = act; p.Wsplit = sp; p.amode = A_LN; p.ln_part = st; p.ln_nparts = K / 96;
-      rc = launch_gemm(p, (hipStream_t)stream);
-    }
-    he = hipStreamSynchronize((hipStream_t)stream);
-  }
-  hipFree(sp); hipFree(spp); hipFree(wd); hipFree(bd); hipFree(st); hipFree(wpd); hipFree(bpd);
-  if (rc) FAIL(e, rc, "gemm_ln_gemm launch failed");
-  if (he != hipSuccess) FAIL(e, NUHTC_E_HIP, "gemm_ln_gemm failed");
-  return 0;
+  std::vector<unsigned short> split, split_p;
+  int rc = gemm_make_split(w2.data(), N, K, split);
+  if (!rc) rc = gemm_make_split(Wp_host, K, Kp, split_p);
+  if (rc) FAIL(e, rc, "gemm_make_split failed (K % 8)");
+  DevScratch sc;
+  float* st = sc.alloc<float>((size_t)M * (K / 96) * 8);
+  GemmParams q = gp(A_dev, sc.upload(Wp_host, (size_t)K * Kp), bp_host ? sc.upload(bp_host, K) : nullptr, Y_dev, M, K, Kp);   // the producer: Y[row_map(m)] = A Wp^T + bp (+ res), statistics on the way out
+  q.Wsplit = sc.upload(split_p); q.stats_out = st;
+  if (res_dev) { q.res = res_dev; q.ldr = K; }
+  if (row_map_dev) { q.store = ST_ROWMAP; q.row_map = row_map_dev; }
+  GemmParams p = gp(Y_dev, sc.upload(w2), sc.upload(b2), C_dev, M, N, K);
+  p.act = act; p.Wsplit = sc.upload(split); p.amode = A_LN; p.ln_part = st; p.ln_nparts = K / 96;
+  if (!sc.ok()) FAIL(e, NUHTC_E_HIP, "gemm_ln_gemm op: scratch upload failed");
+  rc = launch_gemm(q, s);
+  if (!rc) rc = launch_gemm(p, s);
+  return op_finish(e, rc, s, "gemm_ln_gemm launch failed", "gemm_ln_gemm failed");
 }
 
 int nuhtc_op_merge_ln_gemm(nuhtc_engine* e, const float* X_dev, int B, int H, int W, int C, const float* W_host, const float* ln_g_host, const float* ln_b_host,
                            float* Y_dev, void* stream) {
   if (!e || !X_dev || !W_host || !ln_g_host || !ln_b_host || !Y_dev || B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || C < 96 || C % 96) return NUHTC_E_INVALID;
   HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
   const int T = B * H * W, M = T / 4;
-  std::vector<float> g2(4 * C), b2(4 * C), w2((size_t)2 * C * 4 * C), wl, bl;      // gather order k' = q*C + c, q = kh*2 + kw (nuhtc_finalize)
-  for (int q = 0; q < 4; ++q)
-    for (int ch = 0; ch < C; ++ch) {
-      g2[q * C + ch] = ln_g_host[ch * 4 + q];
-      b2[q * C + ch] = ln_b_host[ch * 4 + q];
-      for (int n = 0; n < 2 * C; ++n) w2[(size_t)n * 4 * C + q * C + ch] = W_host[(size_t)n * 4 * C + ch * 4 + q];
-    }
-  fold_ln(w2.data(), nullptr, g2.data(), b2.data(), 2 * C, 4 * C, wl, bl);
-  std::vector<int> src(M);
-  for (int b = 0; b < B; ++b)
-    for (int y2 = 0; y2 < H / 2; ++y2)
-      for (int x2 = 0; x2 < W / 2; ++x2) src[((size_t)b * (H / 2) + y2) * (W / 2) + x2] = (b * H + 2 * y2) * W + 2 * x2;
-  void* sp = nullptr;
-  int rc = gemm_make_split(wl.data(), 2 * C, 4 * C, &sp);
+  const MergePack m = pack_merge(ln_g_host, ln_b_host, W_host, C, B, H, W);      // the packing of nuhtc_finalize
+  std::vector<float> wl, bl;
+  fold_ln(m.w.data(), nullptr, m.g.data(), m.b.data(), 2 * C, 4 * C, wl, bl);
+  std::vector<unsigned short> split;
+  int rc = gemm_make_split(wl.data(), 2 * C, 4 * C, split);
   if (rc) FAIL(e, rc, "gemm_make_split failed");
-  float *wd = nullptr, *bd = nullptr, *st = nullptr;
-  int* sd = nullptr;
-  hipError_t he = hipMalloc(&wd, wl.size() * 4);
-  if (he == hipSuccess) he = hipMalloc(&bd, bl.size() * 4);
-  if (he == hipSuccess) he = hipMalloc(&st, (size_t)T * (C / 96) * 8);
-  if (he == hipSuccess) he = hipMalloc(&sd, (size_t)M * 4);
-  if (he == hipSuccess) he = hipMemcpy(wd, wl.data(), wl.size() * 4, hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipMemcpy(bd, bl.data(), bl.size() * 4, hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipMemcpy(sd, src.data(), (size_t)M * 4, hipMemcpyHostToDevice);
-  if (he == hipSuccess) {
-    rc = launch_ln_stats(X_dev, st, T * (C / 96), 96, (hipStream_t)stream);       // a partial per token and 96 channels: what the producers' epilogues leave
-    if (!rc) {
-      GemmParams p = gp(X_dev, wd, bd, Y_dev, M, 2 * C, 4 * C);
-      p.Wsplit = sp; p.lda = C; p.amode = A_LN; p.ln_part = st; p.ln_nparts = 4 * (C / 96); p.a_rows = sd; p.seg_k = 2 * C; p.seg_rows = W;
-      rc = launch_gemm(p, (hipStream_t)stream);
-    }
-    he = hipStreamSynchronize((hipStream_t)stream);
-  }
-  hipFree(sp); hipFree(wd); hipFree(bd); hipFree(st); hipFree(sd);
-  if (rc) FAIL(e, rc, "merge_ln_gemm launch failed");
-  if (he != hipSuccess) FAIL(e, NUHTC_E_HIP, "merge_ln_gemm failed");
-  return 0;
+  DevScratch sc;
+  float* st = sc.alloc<float>((size_t)T * (C / 96) * 8);
+  GemmParams p = gp(X_dev, sc.upload(wl), sc.upload(bl), Y_dev, M, 2 * C, 4 * C);
+  p.Wsplit = sc.upload(split); p.lda = C; p.amode = A_LN; p.ln_part = st; p.ln_nparts = 4 * (C / 96); p.a_rows = sc.upload(m.src); p.seg_k = 2 * C; p.seg_rows = W;
+  if (!sc.ok()) FAIL(e, NUHTC_E_HIP, "merge_ln_gemm op: scratch upload failed");
+  rc = launch_ln_stats(X_dev, st, T * (C / 96), 96, s);       // a partial per token and 96 channels: what the producers' epilogues leave
+  if (!rc) rc = launch_gemm(p, s);
+  return op_finish(e, rc, s, "merge_ln_gemm launch failed", "merge_ln_gemm failed");
 }
 
 int nuhtc_op_swin_mlp(nuhtc_engine* e, const float* x_dev, const float* ln_g_dev, const float* ln_b_dev, const float* w1_host, const float* b1_dev,
@@ -1284,17 +1197,14 @@ int nuhtc_op_swin_mlp(nuhtc_engine* e, const float* x_dev, const float* ln_g_dev
   if (!e || !x_dev || !ln_g_dev || !ln_b_dev || !w1_host || !b1_dev || !w2_host || !b2_dev || !out_dev || T < 1) return NUHTC_E_INVALID;
   if (!mlp_supported(C)) FAIL(e, NUHTC_E_INVALID, "nuhtc_op_swin_mlp: unsupported channel count");
   HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
   std::vector<unsigned short> st;
   mlp_pack_stream(w1_host, w2_host, C, st);
-  void* d = nullptr;
-  HIP_CHECK(e, hipMalloc(&d, st.size() * 2));
-  if (hipMemcpy(d, st.data(), st.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); FAIL(e, NUHTC_E_HIP, "weight stream upload failed"); }
-  int rc = launch_swin_mlp(x_dev, out_dev, ln_g_dev, ln_b_dev, d, b1_dev, b2_dev, T, C, (hipStream_t)stream);
-  hipError_t he = hipStreamSynchronize((hipStream_t)stream);
-  hipFree(d);
-  if (rc) FAIL(e, rc, "swin_mlp launch failed");
-  if (he != hipSuccess) FAIL(e, NUHTC_E_HIP, "swin_mlp kernel failed");
-  return 0;
+  DevScratch sc;
+  const void* d = sc.upload(st);
+  if (!sc.ok()) FAIL(e, NUHTC_E_HIP, "weight stream upload failed");
+  const int rc = launch_swin_mlp(x_dev, out_dev, ln_g_dev, ln_b_dev, d, b1_dev, b2_dev, T, C, s);
+  return op_finish(e, rc, s, "swin_mlp launch failed", "swin_mlp kernel failed");
 }
 
 int nuhtc_op_swin_proj_mlp(nuhtc_engine* e, const float* x_dev, const float* att_dev, const float* wp_host, const float* bp_dev, const float* ln_g_dev,
@@ -1303,22 +1213,18 @@ int nuhtc_op_swin_proj_mlp(nuhtc_engine* e, const float* x_dev, const float* att
   if (!e || !x_dev || !att_dev || !wp_host || !bp_dev || !ln_g_dev || !ln_b_dev || !w1_host || !b1_dev || !w2_host || !b2_dev || !out_dev || T < 1) return NUHTC_E_INVALID;
   if (!mlp_supported(C)) FAIL(e, NUHTC_E_INVALID, "nuhtc_op_swin_proj_mlp: unsupported channel count");
   HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
   std::vector<unsigned short> st, sp;
   mlp_pack_stream(w1_host, w2_host, C, st);
   proj_pack_stream(wp_host, C, sp);
-  void *d = nullptr, *dp = nullptr;
-  HIP_CHECK(e, hipMalloc(&d, st.size() * 2));
-  if (hipMalloc(&dp, sp.size() * 2) != hipSuccess) { hipFree(d); FAIL(e, NUHTC_E_HIP, "hipMalloc failed"); }
-  bool ok = hipMemcpy(d, st.data(), st.size() * 2, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dp, sp.data(), sp.size() * 2, hipMemcpyHostToDevice) == hipSuccess;
+  DevScratch sc;
+  const void *d = sc.upload(st), *dp = sc.upload(sp);
+  if (!sc.ok()) FAIL(e, NUHTC_E_HIP, "weight stream upload failed");
   // the kernel works in place (its FFN residual re-reads x' where the projection stored it): out <- x first
-  if (ok && out_dev != x_dev) ok = hipMemcpyAsync(out_dev, x_dev, (size_t)T * C * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess;
-  int rc = ok ? launch_swin_mlp(out_dev, out_dev, ln_g_dev, ln_b_dev, d, b1_dev, b2_dev, T, C, (hipStream_t)stream, att_dev, dp, bp_dev) : NUHTC_E_HIP;
-  hipError_t he = hipStreamSynchronize((hipStream_t)stream);
-  hipFree(d);
-  hipFree(dp);
-  if (rc) FAIL(e, rc, "swin_proj_mlp launch failed");
-  if (he != hipSuccess) FAIL(e, NUHTC_E_HIP, "swin_proj_mlp kernel failed");
-  return 0;
+  int rc = 0;
+  if (out_dev != x_dev && hipMemcpyAsync(out_dev, x_dev, (size_t)T * C * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = NUHTC_E_HIP;
+  if (!rc) rc = launch_swin_mlp(out_dev, out_dev, ln_g_dev, ln_b_dev, d, b1_dev, b2_dev, T, C, s, att_dev, dp, bp_dev);
+  return op_finish(e, rc, s, "swin_proj_mlp launch failed", "swin_proj_mlp kernel failed");
 }
 
 #ifdef NUHTC_DEV

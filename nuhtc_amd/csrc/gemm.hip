@@ -850,39 +850,12 @@ static const float* zero_page() {
 }
 
 // ---- split weights: Wsplit[n][k/8][3][8 bf16] on the same device, owned by the engine that uploaded the weight (engine.hip egemm)
-static inline unsigned short bf16_rn_bits(float f) {     // round to nearest even; a NaN stays a NaN (the integer carry would turn some into 0 / Inf)
-  unsigned u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x0040u);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-static inline float bf16_bits_to_float(unsigned short h) {
-  unsigned u = (unsigned)h << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-
-// host split of a constant weight matrix -> device buffer Wsplit[n][k/8][plane][8 bf16] (caller frees with hipFree)
-int gemm_make_split(const float* w_host, int N, int K, void** out) {
-  if (!w_host || !out || N <= 0 || K <= 0 || K % 8) return NUHTC_E_INVALID;
-  std::vector<unsigned short> sp((size_t)N * K * 3);
+int gemm_make_split(const float* w_host, int N, int K, std::vector<unsigned short>& out) {
+  if (!w_host || N <= 0 || K <= 0 || K % 8) return NUHTC_E_INVALID;
+  out.assign((size_t)N * K * 3, 0);
   for (int n = 0; n < N; ++n)
-    for (int k = 0; k < K; ++k) {
-      const float b = w_host[(size_t)n * K + k];
-      const unsigned short b1 = bf16_rn_bits(b);
-      const float r1 = b - bf16_bits_to_float(b1);           // exact
-      const unsigned short b2 = bf16_rn_bits(r1);
-      const float r2 = r1 - bf16_bits_to_float(b2);          // exact
-      const unsigned short b3 = bf16_rn_bits(r2);
-      unsigned short* dst = sp.data() + (((size_t)n * (K / 8) + k / 8) * 3) * 8 + (k & 7);
-      dst[0] = b1; dst[8] = b2; dst[16] = b3;
-    }
-  void* d = nullptr;
-  if (hipMalloc(&d, sp.size() * 2) != hipSuccess) return NUHTC_E_HIP;
-  if (hipMemcpy(d, sp.data(), sp.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); return NUHTC_E_HIP; }
-  *out = d;
+    for (int k = 0; k < K; ++k)
+      bf16_split3(w_host[(size_t)n * K + k], out.data() + (((size_t)n * (K / 8) + k / 8) * 3) * 8 + (k & 7), 8);
   return 0;
 }
 

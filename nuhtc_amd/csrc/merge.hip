@@ -532,29 +532,28 @@ extern "C" int nuhtc_merge_overlap(int device, const int32_t* boxes, const float
   a.ncx = (x_max - x_min) / MG_CELL + 1; a.ncy = (y_max - y_min) / MG_CELL + 1;
   const long long ncell = (long long)a.ncx * a.ncy;
   if (ncell > (1LL << 28)) return NUHTC_E_INVALID;
-  std::vector<void*> tmp;
-  auto alloc = [&](void** p, size_t bytes) { if (hipMalloc(p, bytes ? bytes : 16) != hipSuccess) return false; tmp.push_back(*p); return true; };
-  auto release = [&]() { for (void* p : tmp) hipFree(p); };
-  int rc = 0;
+  DevScratch tmp;      // every temporary of the call, freed on the way out
   int h_flags[3] = {0, 0, 0};
-  long long total = 0;
   const unsigned nb = (unsigned)((n + 255) / 256);
-  if (!alloc((void**)&a.cell_count, (ncell + 1) * sizeof(int)) || !alloc((void**)&a.cell_start, (ncell + 1) * sizeof(int)) ||
-      !alloc((void**)&a.sup, (size_t)n * MG_MAXSUP * sizeof(int)) || !alloc((void**)&a.nsup, (size_t)n * sizeof(int)) ||
-      !alloc((void**)&a.spill_head, (size_t)n * sizeof(int)) ||
-      !alloc((void**)&a.state, (size_t)n) || !alloc((void**)&a.flags, 4 * sizeof(int))) { rc = NUHTC_E_HIP; goto done; }
-  if (hipMemsetAsync(a.cell_count, 0, (ncell + 1) * sizeof(int), s) != hipSuccess || hipMemsetAsync(a.flags, 0, 4 * sizeof(int), s) != hipSuccess) { rc = NUHTC_E_HIP; goto done; }
+  a.cell_count = tmp.alloc<int>((ncell + 1) * sizeof(int)); a.cell_start = tmp.alloc<int>((ncell + 1) * sizeof(int));
+  a.sup = tmp.alloc<int>((size_t)n * MG_MAXSUP * sizeof(int)); a.nsup = tmp.alloc<int>((size_t)n * sizeof(int));
+  a.spill_head = tmp.alloc<int>((size_t)n * sizeof(int));
+  a.state = tmp.alloc<uint8_t>((size_t)n); a.flags = tmp.alloc<int>(4 * sizeof(int));
+  if (!tmp.ok()) return NUHTC_E_HIP;
+  if (hipMemsetAsync(a.cell_count, 0, (ncell + 1) * sizeof(int), s) != hipSuccess || hipMemsetAsync(a.flags, 0, 4 * sizeof(int), s) != hipSuccess) return NUHTC_E_HIP;
   if (a.polygon) {
     // mask crops -> pixel sets of the ring polygons + their areas in quarter cells (scratch copies; the inputs stay untouched)
     int h_maxw = 0;
     int* d_maxw = a.flags + 3;
     hipLaunchKernelGGL(merge_maxwords_kernel, dim3(nb), dim3(256), 0, s, a, d_maxw);
-    if (hipMemcpyAsync(&h_maxw, d_maxw, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = NUHTC_E_HIP; goto done; }
+    if (hipMemcpyAsync(&h_maxw, d_maxw, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return NUHTC_E_HIP;
     a.max_words = h_maxw > 0 ? h_maxw : 1;
     const size_t lds = (size_t)7 * a.max_words * sizeof(uint32_t);
-    if (lds > 160 * 1024) { rc = NUHTC_E_INVALID; goto done; }       // a crop beyond ~430x430 pixels is no nucleus
-    if (hipFuncSetAttribute((const void*)merge_prepare_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) { rc = NUHTC_E_HIP; goto done; }
-    if (!alloc((void**)&a.poly_bits, (size_t)(n_words > 0 ? n_words : 1) * sizeof(uint32_t)) || !alloc((void**)&a.poly_area4, (size_t)n * sizeof(int32_t))) { rc = NUHTC_E_HIP; goto done; }
+    if (lds > 160 * 1024) return NUHTC_E_INVALID;       // a crop beyond ~430x430 pixels is no nucleus
+    if (hipFuncSetAttribute((const void*)merge_prepare_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return NUHTC_E_HIP;
+    a.poly_bits = tmp.alloc<uint32_t>((size_t)(n_words > 0 ? n_words : 1) * sizeof(uint32_t));
+    a.poly_area4 = tmp.alloc<int32_t>((size_t)n * sizeof(int32_t));
+    if (!tmp.ok()) return NUHTC_E_HIP;
     a.raw_bits = bits;
     hipLaunchKernelGGL(merge_prepare_kernel, dim3((unsigned)n), dim3(64), lds, s, a);
     a.bits = a.poly_bits;
@@ -562,34 +561,29 @@ extern "C" int nuhtc_merge_overlap(int device, const int32_t* boxes, const float
   }
   hipLaunchKernelGGL(merge_count_kernel, dim3(nb), dim3(256), 0, s, a, 0);
   hipLaunchKernelGGL(merge_scan_kernel, dim3(1), dim3(1024), 0, s, a);
-  {
-    int h_total = 0;
-    if (hipMemcpyAsync(&h_total, a.cell_start + ncell, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = NUHTC_E_HIP; goto done; }
-    total = h_total;
-  }
-  if (!alloc((void**)&a.cell_items, (size_t)(total > 0 ? total : 1) * sizeof(int))) { rc = NUHTC_E_HIP; goto done; }
+  int total = 0;
+  if (hipMemcpyAsync(&total, a.cell_start + ncell, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return NUHTC_E_HIP;
+  if (!(a.cell_items = tmp.alloc<int>((size_t)(total > 0 ? total : 1) * sizeof(int)))) return NUHTC_E_HIP;
   hipLaunchKernelGGL(merge_count_kernel, dim3(nb), dim3(256), 0, s, a, 1);
   // suppressor lists: 24 inline + chunks in a spill pool; a dense clump that exhausts the pool makes the pass run again with
   // a larger one
   a.spill_cap = (int)std::min<long long>(std::max<long long>(1 << 16, n), 1LL << 30);
   for (int attempt = 0;; ++attempt) {
-    if (!alloc((void**)&a.spill, (size_t)a.spill_cap * sizeof(int))) { rc = NUHTC_E_HIP; goto done; }
-    if (hipMemsetAsync(a.flags, 0, 3 * sizeof(int), s) != hipSuccess) { rc = NUHTC_E_HIP; goto done; }
+    if (!(a.spill = tmp.alloc<int>((size_t)a.spill_cap * sizeof(int)))) return NUHTC_E_HIP;
+    if (hipMemsetAsync(a.flags, 0, 3 * sizeof(int), s) != hipSuccess) return NUHTC_E_HIP;
     hipLaunchKernelGGL(merge_pairs_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, a);
-    if (hipMemcpyAsync(h_flags, a.flags, 3 * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = NUHTC_E_HIP; goto done; }
+    if (hipMemcpyAsync(h_flags, a.flags, 3 * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return NUHTC_E_HIP;
     if (!h_flags[1]) break;
-    if (attempt >= 6 || a.spill_cap >= (1 << 30)) { rc = NUHTC_E_CAPACITY; goto done; }
+    if (attempt >= 6 || a.spill_cap >= (1 << 30)) return NUHTC_E_CAPACITY;
     a.spill_cap = (int)std::min<long long>(std::max<long long>((long long)h_flags[2] + 1024, 4LL * a.spill_cap), 1LL << 30);
   }
   for (int round = 0; round < 4096; ++round) {
-    if (hipMemsetAsync(a.flags, 0, sizeof(int), s) != hipSuccess) { rc = NUHTC_E_HIP; goto done; }
+    if (hipMemsetAsync(a.flags, 0, sizeof(int), s) != hipSuccess) return NUHTC_E_HIP;
     for (int k = 0; k < 4; ++k) hipLaunchKernelGGL(merge_round_kernel, dim3(nb), dim3(256), 0, s, a);
-    if (hipMemcpyAsync(h_flags, a.flags, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = NUHTC_E_HIP; goto done; }
+    if (hipMemcpyAsync(h_flags, a.flags, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return NUHTC_E_HIP;
     if (!h_flags[0]) break;
   }
   hipLaunchKernelGGL(merge_finish_kernel, dim3(nb), dim3(256), 0, s, a, keep_dev);
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) rc = NUHTC_E_HIP;
-done:
-  release();
-  return rc;
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return NUHTC_E_HIP;
+  return 0;
 }

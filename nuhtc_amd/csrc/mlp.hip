@@ -535,26 +535,6 @@ __global__ __launch_bounds__(256) void qkv_pad_rows_kernel(float* __restrict__ q
 }
 
 // ---- host side: the weight stream of one block (permuted k axes, split planes, chunk-major)
-static inline unsigned short mlp_bf16_rn(float f) {
-  unsigned u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x0040u);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-static inline float mlp_bf16_f(unsigned short h) {
-  unsigned u = (unsigned)h << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-static inline void mlp_split3(float b, unsigned short* dst) {   // dst[0], dst[8], dst[16] = planes 1..3 of one element of a k-group
-  const unsigned short b1 = mlp_bf16_rn(b);
-  const float r1 = b - mlp_bf16_f(b1);
-  const unsigned short b2 = mlp_bf16_rn(r1);
-  const float r2 = r1 - mlp_bf16_f(b2);
-  dst[0] = b1; dst[8] = b2; dst[16] = mlp_bf16_rn(r2);
-}
 // position k' of a permuted 16-group -> original position: k' = 8 hh + e  <->  8 (e / 4) + 4 hh + e % 4
 static inline int mlp_perm16(int kp) { const int hh = (kp >> 3) & 1, e = kp & 7; return 8 * (e >> 2) + 4 * hh + (e & 3); }
 
@@ -570,7 +550,7 @@ void mlp_pack_stream(const float* w1, const float* w2, int C, std::vector<unsign
       for (int kg = 0; kg < C / 8; ++kg) {
         for (int e = 0; e < 8; ++e) {
           const int kp = 8 * kg + e, k = (kp & ~15) + mlp_perm16(kp & 15);
-          mlp_split3(w1[(size_t)(32 * j + r) * C + k], o + e);
+          bf16_split3(w1[(size_t)(32 * j + r) * C + k], o + e, 8);
         }
         o += 24;
       }
@@ -578,7 +558,7 @@ void mlp_pack_stream(const float* w1, const float* w2, int C, std::vector<unsign
       for (int kg = 0; kg < 4; ++kg) {
         for (int e = 0; e < 8; ++e) {
           const int kp = 8 * kg + e, k = 32 * j + (kp & ~15) + mlp_perm16(kp & 15);
-          mlp_split3(w2[(size_t)c * HID + k], o + e);
+          bf16_split3(w2[(size_t)c * HID + k], o + e, 8);
         }
         o += 24;
       }
@@ -596,7 +576,7 @@ void proj_pack_stream(const float* w, int C, std::vector<unsigned short>& out) {
     for (int kg = 0; kg < C / 8; ++kg) {
       for (int e = 0; e < 8; ++e) {
         const int kp = 8 * kg + e, k = (kp & ~15) + mlp_perm16(kp & 15);
-        mlp_split3(w[(size_t)r * C + k], o + e);
+        bf16_split3(w[(size_t)r * C + k], o + e, 8);
       }
       o += 24;
     }
@@ -666,7 +646,7 @@ void lnqkv_pack_stream(const float* w, int C, std::vector<unsigned short>& out) 
     for (int kg = 0; kg < C / 8; ++kg) {
       for (int e = 0; e < 8; ++e) {
         const int kp = 8 * kg + e, k = (kp & ~15) + mlp_perm16(kp & 15);
-        mlp_split3(w[(size_t)r * C + k], o + e);
+        bf16_split3(w[(size_t)r * C + k], o + e, 8);
       }
       o += 24;
     }

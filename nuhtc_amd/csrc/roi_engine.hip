@@ -52,57 +52,15 @@ struct RoiWs {
   unsigned char* keep_own;
 };
 
-template <typename T>
-static int wsa(nuhtc_engine* e, T** p, const char* name, std::vector<int64_t> shape, int dtype) {
-  size_t n = 1;
-  for (auto d : shape) n *= (size_t)d;
-  size_t bytes = (n * sizeof(T) + 255) & ~(size_t)255;
-  if (hipMalloc((void**)p, bytes ? bytes : 256) != hipSuccess) {
-    e->err = std::string("hipMalloc failed for ") + (name ? name : "workspace") + " (" + std::to_string(bytes) + " bytes)";
-    return NUHTC_E_HIP;
-  }
-  e->allocs.push_back(*p);
-  e->bytes_allocated += bytes;
-  if (name) e->bufs[name] = BufInfo{(void*)*p, shape, dtype};
-  return 0;
-}
-
-static const HostTensor* rawt(nuhtc_engine* e, const std::string& name, std::initializer_list<int64_t> shape) {
-  auto it = e->raw.find(name);
-  if (it == e->raw.end()) { e->err = "missing weight: " + name; return nullptr; }
-  if (it->second.shape != std::vector<int64_t>(shape)) { e->err = "bad shape for weight: " + name; return nullptr; }
-  return &it->second;
-}
-#define RAWT(var, name, ...)                               \
-  const HostTensor* var = rawt(e, (name), {__VA_ARGS__});  \
-  if (!var) return NUHTC_E_STATE;
-
-static int up(nuhtc_engine* e, float** dst, const std::vector<float>& v) {
-  size_t bytes = (v.size() * sizeof(float) + 255) & ~(size_t)255;
-  if (hipMalloc((void**)dst, bytes) != hipSuccess) { e->err = "hipMalloc failed (weights)"; return NUHTC_E_HIP; }
-  e->allocs.push_back(*dst);
-  e->bytes_allocated += bytes;
-  if (hipMemcpy(*dst, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { e->err = "hipMemcpy failed (weights)"; return NUHTC_E_HIP; }
-  return 0;
-}
-
-static std::vector<float> pack3(const HostTensor& w, int O, int I) {
-  std::vector<float> p((size_t)O * 9 * I);
-  for (int o = 0; o < O; ++o)
-    for (int i = 0; i < I; ++i)
-      for (int t = 0; t < 9; ++t) p[((size_t)o * 9 + t) * I + i] = w.data[((size_t)o * I + i) * 9 + t];
-  return p;
-}
-
 int finalize_roi(nuhtc_engine* e) {
   const int nc = e->cfg.num_classes;
   int rc;
   for (int k = 0; k < 3; ++k) {
     const std::string p = "roi_head.bbox_head." + std::to_string(k) + ".";
-    RAWT(w1, p + "shared_fcs.0.weight", 256, 3136); RAWT(b1, p + "shared_fcs.0.bias", 256);
-    RAWT(w2, p + "shared_fcs.1.weight", 256, 256); RAWT(b2, p + "shared_fcs.1.bias", 256);
-    RAWT(wc, p + "fc_cls.weight", nc + 2, 256); RAWT(bc, p + "fc_cls.bias", nc + 2);
-    RAWT(wr, p + "fc_reg.weight", 4, 256); RAWT(br, p + "fc_reg.bias", 4);
+    RAW(w1, p + "shared_fcs.0.weight", 256, 3136); RAW(b1, p + "shared_fcs.0.bias", 256);
+    RAW(w2, p + "shared_fcs.1.weight", 256, 256); RAW(b2, p + "shared_fcs.1.bias", 256);
+    RAW(wc, p + "fc_cls.weight", nc + 2, 256); RAW(bc, p + "fc_cls.bias", nc + 2);
+    RAW(wr, p + "fc_reg.weight", 4, 256); RAW(br, p + "fc_reg.bias", 4);
     // flatten order of the reference is (c, ph, pw); the RoI kernel emits (ph, pw, c)
     std::vector<float> w1p((size_t)256 * 3136);
     for (int n = 0; n < 256; ++n)
@@ -121,19 +79,19 @@ int finalize_roi(nuhtc_engine* e) {
       for (int k2 = 0; k2 < 256; ++k2) hw[(nc + 2 + n) * 256 + k2] = wr->data[n * 256 + k2];
       hb[nc + 2 + n] = br->data[n];
     }
-    if ((rc = upload_gemm_weight(e, &e->fc1_w[k], w1p, 256, 3136)) || (rc = up(e, &e->fc1_b[k], b1->data)) || (rc = upload_gemm_weight(e, &e->fc2_w[k], w2->data, 256, 256)) ||
-        (rc = up(e, &e->fc2_b[k], b2->data)) || (rc = up(e, &e->head_w[k], hw)) || (rc = up(e, &e->head_b[k], hb)))
+    if ((rc = upload_gemm_weight(e, &e->fc1_w[k], w1p, 256, 3136)) || (rc = upload(e, &e->fc1_b[k], b1->data)) || (rc = upload_gemm_weight(e, &e->fc2_w[k], w2->data, 256, 256)) ||
+        (rc = upload(e, &e->fc2_b[k], b2->data)) || (rc = upload(e, &e->head_w[k], hw)) || (rc = upload(e, &e->head_b[k], hb)))
       return rc;
   }
   {
     const std::string p = "roi_head.mask_head.0.";
     for (int j = 0; j < 4; ++j) {
-      RAWT(w, p + "convs." + std::to_string(j) + ".conv.weight", 64, 64, 3, 3);
-      RAWT(b, p + "convs." + std::to_string(j) + ".conv.bias", 64);
-      if ((rc = upload_gemm_weight(e, &e->mk_w[j], pack3(*w, 64, 64), 64, 576)) || (rc = up(e, &e->mk_b[j], b->data))) return rc;
+      RAW(w, p + "convs." + std::to_string(j) + ".conv.weight", 64, 64, 3, 3);
+      RAW(b, p + "convs." + std::to_string(j) + ".conv.bias", 64);
+      if ((rc = upload_gemm_weight(e, &e->mk_w[j], pack_conv3(*w, 64, 64), 64, 576)) || (rc = upload(e, &e->mk_b[j], b->data))) return rc;
     }
-    RAWT(uw, p + "upsample.weight", 64, 64, 2, 2); RAWT(ub, p + "upsample.bias", 64);
-    RAWT(lw, p + "conv_logits.weight", 1, 64, 1, 1); RAWT(lb, p + "conv_logits.bias", 1);
+    RAW(uw, p + "upsample.weight", 64, 64, 2, 2); RAW(ub, p + "upsample.bias", 64);
+    RAW(lw, p + "conv_logits.weight", 1, 64, 1, 1); RAW(lb, p + "conv_logits.bias", 1);
     // ConvTranspose2d(k=2,s=2) weight [in][out][kh][kw] -> GEMM weight [(kh*2+kw)*64 + oc][ic]
     std::vector<float> w((size_t)256 * 64), b(256);
     for (int ic = 0; ic < 64; ++ic)
@@ -141,7 +99,7 @@ int finalize_roi(nuhtc_engine* e) {
         for (int t = 0; t < 4; ++t) w[((size_t)t * 64 + oc) * 64 + ic] = uw->data[((size_t)ic * 64 + oc) * 4 + t];
     for (int t = 0; t < 4; ++t)
       for (int oc = 0; oc < 64; ++oc) b[t * 64 + oc] = ub->data[oc];
-    if ((rc = upload_gemm_weight(e, &e->mk_up_w, w, 256, 64)) || (rc = up(e, &e->mk_up_b, b)) || (rc = up(e, &e->mk_lw, lw->data)) || (rc = up(e, &e->mk_lb, lb->data))) return rc;
+    if ((rc = upload_gemm_weight(e, &e->mk_up_w, w, 256, 64)) || (rc = upload(e, &e->mk_up_b, b)) || (rc = upload(e, &e->mk_lw, lw->data)) || (rc = upload(e, &e->mk_lb, lb->data))) return rc;
   }
   return 0;
 }
@@ -170,67 +128,54 @@ int alloc_roi_workspace(nuhtc_engine* e) {
   if (maxc > NMS_MAX_CAP || w->det_cap > NMS_MAX_CAP) { e->err = "candidate capacity exceeds NMS_MAX_CAP (reduce rpn_nms_pre / max_cc_proposals)"; return NUHTC_E_INVALID; }
   const int nmscap = std::max(w->rpn_cap, w->det_cap);
   w->rpn_key_stride = round_up(e->st[0].H * e->st[0].W * 3, 64);
-  if ((rc = wsa(e, &w->rpn_keys, nullptr, {B, 4, w->rpn_key_stride}, 1)) ||
-      (rc = wsa(e, &w->cand_boxes, "rpn_cand_boxes", {B, 4, w->rpn_slot, 4}, 0)) || (rc = wsa(e, &w->cand_scores, "rpn_cand_scores", {B, 4, w->rpn_slot}, 0)) ||
-      (rc = wsa(e, &w->cand_count, "rpn_cand_count", {B, 4}, 1)) || (rc = wsa(e, &w->nms_sboxes, nullptr, {B, nmscap, 4}, 0)) ||
-      (rc = wsa(e, &w->nms_src, nullptr, {B, nmscap}, 1)) || (rc = wsa(e, &w->nms_ntotal, nullptr, {B}, 1)) ||
-      (rc = wsa(e, &w->nms_seg_start, nullptr, {B, 4}, 1)) || (rc = wsa(e, &w->nms_seg_n, nullptr, {B, 4}, 1)) ||
-      (rc = wsa(e, &w->nms_pos, nullptr, {B, nmscap}, 1)) || (rc = wsa(e, &w->nms_keepbits, nullptr, {B, nmscap / 64}, 3)) ||
-      (rc = wsa(e, &w->nms_mask, nullptr, {B, nmscap, nmscap / 64}, 3)) || (rc = wsa(e, &w->rpn_dets, "rpn_props", {B, c.rpn_max_per_img, 5}, 0)) ||
-      (rc = wsa(e, &w->rpn_src, nullptr, {B, c.rpn_max_per_img}, 1)) || (rc = wsa(e, &w->rpn_counts, "rpn_counts", {B}, 1)))
+  if ((rc = ws(e, &w->rpn_keys, nullptr, {B, 4, w->rpn_key_stride}, 1)) ||
+      (rc = ws(e, &w->cand_boxes, "rpn_cand_boxes", {B, 4, w->rpn_slot, 4}, 0)) || (rc = ws(e, &w->cand_scores, "rpn_cand_scores", {B, 4, w->rpn_slot}, 0)) ||
+      (rc = ws(e, &w->cand_count, "rpn_cand_count", {B, 4}, 1)) || (rc = ws(e, &w->nms_sboxes, nullptr, {B, nmscap, 4}, 0)) ||
+      (rc = ws(e, &w->nms_src, nullptr, {B, nmscap}, 1)) || (rc = ws(e, &w->nms_ntotal, nullptr, {B}, 1)) ||
+      (rc = ws(e, &w->nms_seg_start, nullptr, {B, 4}, 1)) || (rc = ws(e, &w->nms_seg_n, nullptr, {B, 4}, 1)) ||
+      (rc = ws(e, &w->nms_pos, nullptr, {B, nmscap}, 1)) || (rc = ws(e, &w->nms_keepbits, nullptr, {B, nmscap / 64}, 3)) ||
+      (rc = ws(e, &w->nms_mask, nullptr, {B, nmscap, nmscap / 64}, 3)) || (rc = ws(e, &w->rpn_dets, "rpn_props", {B, c.rpn_max_per_img, 5}, 0)) ||
+      (rc = ws(e, &w->rpn_src, nullptr, {B, c.rpn_max_per_img}, 1)) || (rc = ws(e, &w->rpn_counts, "rpn_counts", {B}, 1)))
     return rc;
   const int64_t HW = (int64_t)Hn * Wn;
   const int ccc = std::max(c.max_cc_proposals, 1);
-  if ((rc = wsa(e, &w->cc_a, nullptr, {B, HW}, 2)) || (rc = wsa(e, &w->cc_b, "cc_mask", {B, Hn, Wn}, 2)) || (rc = wsa(e, &w->cc_touch, nullptr, {B, HW}, 2)) ||
-      (rc = wsa(e, &w->cc_labels, "cc_labels", {B, Hn, Wn}, 1)) || (rc = wsa(e, &w->cc_stats, nullptr, {B, HW, 5}, 1)) ||
-      (rc = wsa(e, &w->cc_list, nullptr, {B, CC_LIST_CAP}, 1)) || (rc = wsa(e, &w->cc_nlist, nullptr, {B}, 1)) ||
-      (rc = wsa(e, &w->cc_boxes, "cc_props", {B, ccc, 4}, 0)) || (rc = wsa(e, &w->cc_counts, "cc_counts", {B}, 1)) ||
-      (rc = wsa(e, &e->overflow, nullptr, {4}, 1)))
+  if ((rc = ws(e, &w->cc_a, nullptr, {B, HW}, 2)) || (rc = ws(e, &w->cc_b, "cc_mask", {B, Hn, Wn}, 2)) || (rc = ws(e, &w->cc_touch, nullptr, {B, HW}, 2)) ||
+      (rc = ws(e, &w->cc_labels, "cc_labels", {B, Hn, Wn}, 1)) || (rc = ws(e, &w->cc_stats, nullptr, {B, HW, 5}, 1)) ||
+      (rc = ws(e, &w->cc_list, nullptr, {B, CC_LIST_CAP}, 1)) || (rc = ws(e, &w->cc_nlist, nullptr, {B}, 1)) ||
+      (rc = ws(e, &w->cc_boxes, "cc_props", {B, ccc, 4}, 0)) || (rc = ws(e, &w->cc_counts, "cc_counts", {B}, 1)) ||
+      (rc = ws(e, &e->overflow, nullptr, {4}, 1)))
     return rc;
   w->total_cap = B * e->roi_cap;
   const int T = w->total_cap;
-  if ((rc = wsa(e, &w->rois, "rois", {T, 5}, 0)) || (rc = wsa(e, &w->roi_off, "roi_off", {B}, 1)) || (rc = wsa(e, &w->roi_cnt, "roi_counts", {B}, 1)) ||
-      (rc = wsa(e, &w->roi_total, "roi_total", {1}, 1)) || (rc = wsa(e, &w->G2, "G2", {B, e->st[2].H * e->st[2].W, 64}, 0)) ||
-      (rc = wsa(e, &w->G3, "G3", {B, e->st[3].H * e->st[3].W, 64}, 0)) || (rc = wsa(e, &w->feats, "bbox_feats", {T, 49, 64}, 0)) ||
-      (rc = wsa(e, &w->h1, nullptr, {T, 256}, 0)) || (rc = wsa(e, &w->h2, nullptr, {T, 256}, 0)) ||
-      (rc = wsa(e, &w->ap_inv, nullptr, {B, e->st[2].H * e->st[2].W}, 0)) ||
-      (rc = wsa(e, &w->ap_S, nullptr, {B, (int64_t)e->st[2].H * e->st[2].W, (int64_t)e->st[2].H * e->st[2].W}, 0)) ||
-      (rc = wsa(e, &w->ap_Ft, nullptr, {B, 64, e->st[2].H * e->st[2].W}, 0)) ||
-      (rc = wsa(e, &w->fb_count, "roi_fallback_count", {8}, 1)) || (rc = wsa(e, &w->mid_list, nullptr, {T}, 1)) || (rc = wsa(e, &w->fb_list, nullptr, {T}, 1)) || (rc = wsa(e, &w->fb_flag, nullptr, {T}, 2)))
+  if ((rc = ws(e, &w->rois, "rois", {T, 5}, 0)) || (rc = ws(e, &w->roi_off, "roi_off", {B}, 1)) || (rc = ws(e, &w->roi_cnt, "roi_counts", {B}, 1)) ||
+      (rc = ws(e, &w->roi_total, "roi_total", {1}, 1)) || (rc = ws(e, &w->G2, "G2", {B, e->st[2].H * e->st[2].W, 64}, 0)) ||
+      (rc = ws(e, &w->G3, "G3", {B, e->st[3].H * e->st[3].W, 64}, 0)) || (rc = ws(e, &w->feats, "bbox_feats", {T, 49, 64}, 0)) ||
+      (rc = ws(e, &w->h1, nullptr, {T, 256}, 0)) || (rc = ws(e, &w->h2, nullptr, {T, 256}, 0)) ||
+      (rc = ws(e, &w->ap_inv, nullptr, {B, e->st[2].H * e->st[2].W}, 0)) ||
+      (rc = ws(e, &w->ap_S, nullptr, {B, (int64_t)e->st[2].H * e->st[2].W, (int64_t)e->st[2].H * e->st[2].W}, 0)) ||
+      (rc = ws(e, &w->ap_Ft, nullptr, {B, 64, e->st[2].H * e->st[2].W}, 0)) ||
+      (rc = ws(e, &w->fb_count, "roi_fallback_count", {8}, 1)) || (rc = ws(e, &w->mid_list, nullptr, {T}, 1)) || (rc = ws(e, &w->fb_list, nullptr, {T}, 1)) || (rc = ws(e, &w->fb_flag, nullptr, {T}, 2)))
     return rc;
-  if ((rc = wsa(e, &w->big_part, nullptr, {BIG_SPLIT_MAX, 3, 49, 64}, 0))) return rc;
+  if ((rc = ws(e, &w->big_part, nullptr, {BIG_SPLIT_MAX, 3, 49, 64}, 0))) return rc;
   for (int k = 0; k < 3; ++k) {
     std::string n = std::to_string(k);
-    if ((rc = wsa(e, &w->cls[k], ("cls" + n).c_str(), {T, 16}, 0)) || (rc = wsa(e, &w->reg[k], ("reg" + n).c_str(), {T, 4}, 0))) return rc;
+    if ((rc = ws(e, &w->cls[k], ("cls" + n).c_str(), {T, 16}, 0)) || (rc = ws(e, &w->reg[k], ("reg" + n).c_str(), {T, 4}, 0))) return rc;
     std::string rn = "rois_stage" + n;
     float* snap;
-    if ((rc = wsa(e, &snap, rn.c_str(), {T, 5}, 0))) return rc;
+    if ((rc = ws(e, &snap, rn.c_str(), {T, 5}, 0))) return rc;
   }
-  if ((rc = wsa(e, &w->dc_boxes, nullptr, {B, w->det_cap, 4}, 0)) || (rc = wsa(e, &w->dc_scores, nullptr, {B, w->det_cap}, 0)) ||
-      (rc = wsa(e, &w->dc_ids, nullptr, {B, w->det_cap}, 1)) || (rc = wsa(e, &w->dc_count, "det_cand_count", {B}, 1)) ||
-      (rc = wsa(e, &w->det_src, nullptr, {B, c.max_per_img}, 1)) || (rc = wsa(e, &w->det_counts, nullptr, {B}, 1)))
+  if ((rc = ws(e, &w->dc_boxes, nullptr, {B, w->det_cap, 4}, 0)) || (rc = ws(e, &w->dc_scores, nullptr, {B, w->det_cap}, 0)) ||
+      (rc = ws(e, &w->dc_ids, nullptr, {B, w->det_cap}, 1)) || (rc = ws(e, &w->dc_count, "det_cand_count", {B}, 1)) ||
+      (rc = ws(e, &w->det_src, nullptr, {B, c.max_per_img}, 1)) || (rc = ws(e, &w->det_counts, nullptr, {B}, 1)))
     return rc;
   w->mask_cap = B * c.max_per_img;
   const int D = w->mask_cap;
-  if ((rc = wsa(e, &w->mask_rois, "mask_rois", {D, 5}, 0)) || (rc = wsa(e, &w->det_off, "det_off", {B}, 1)) || (rc = wsa(e, &w->det_total, "det_total", {1}, 1)) ||
-      (rc = wsa(e, &w->mfeat, "mask_feats", {D, 196, 64}, 0)) || (rc = wsa(e, &w->mtmpA, nullptr, {D, 196, 64}, 0)) || (rc = wsa(e, &w->mtmpB, nullptr, {D, 196, 64}, 0)) ||
-      (rc = wsa(e, &w->mup, nullptr, {D, 784, 64}, 0)) || (rc = wsa(e, &w->mprob, "mask_prob", {D, 28, 28}, 0)))
+  if ((rc = ws(e, &w->mask_rois, "mask_rois", {D, 5}, 0)) || (rc = ws(e, &w->det_off, "det_off", {B}, 1)) || (rc = ws(e, &w->det_total, "det_total", {1}, 1)) ||
+      (rc = ws(e, &w->mfeat, "mask_feats", {D, 196, 64}, 0)) || (rc = ws(e, &w->mtmpA, nullptr, {D, 196, 64}, 0)) || (rc = ws(e, &w->mtmpB, nullptr, {D, 196, 64}, 0)) ||
+      (rc = ws(e, &w->mup, nullptr, {D, 784, 64}, 0)) || (rc = ws(e, &w->mprob, "mask_prob", {D, 28, 28}, 0)))
     return rc;
   if (hipMemset(e->overflow, 0, 16) != hipSuccess) { e->err = "hipMemset failed"; return NUHTC_E_HIP; }
   return 0;
-}
-
-#define RUN(expr)                                                                          \
-  do {                                                                                     \
-    int _rc = (expr);                                                                      \
-    if (_rc) { e->err = std::string(#expr) + " failed (" + std::to_string(_rc) + ")"; return _rc; } \
-  } while (0)
-
-static GemmParams gpr(const float* A, const float* W, const float* bias, float* C, int M, int N, int K) {
-  GemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = A; p.W = W; p.bias = bias; p.C = C; p.M = M; p.N = N; p.K = K; p.lda = K; p.ldc = N; p.alpha = 1.f; p.m_mul = 1;
-  return p;
 }
 
 int run_roi_path(nuhtc_engine* e, int B, const float* rois_fixed, int n_rois, int n_dets, hipStream_t s, const nuhtc_dets* out) {
@@ -281,12 +226,12 @@ int run_roi_path(nuhtc_engine* e, int B, const float* rois_fixed, int n_rois, in
     } else if (HW % 32 == 0) {
       // S = relu(cos(F_q, F_p) - tau) + tau as one batched GEMM F·Fᵀ with the cosine epilogue, then G = S·F / HW
       RUN(launch_rownorm_inv(e->x[l], w->ap_inv, B * HW, 64, s));
-      GemmParams p1 = gpr(e->x[l], e->x[l], nullptr, w->ap_S, HW, HW, 64);
+      GemmParams p1 = gp(e->x[l], e->x[l], nullptr, w->ap_S, HW, HW, 64);
       p1.act = ACT_COS; p1.cos_ri = w->ap_inv; p1.cos_rj = w->ap_inv; p1.cos_tau = c.att_thres;
       p1.batch = B; p1.sA = (long long)HW * 64; p1.sW = (long long)HW * 64; p1.sC = (long long)HW * HW; p1.sRi = HW; p1.sRj = HW;
       RUN(egemm(e, p1, s));
       RUN(launch_transpose(e->x[l], w->ap_Ft, B, HW, 64, s));
-      GemmParams p2 = gpr(w->ap_S, w->ap_Ft, nullptr, G, HW, 64, HW);
+      GemmParams p2 = gp(w->ap_S, w->ap_Ft, nullptr, G, HW, 64, HW);
       p2.alpha = 1.0f / (float)HW;
       p2.batch = B; p2.sA = (long long)HW * HW; p2.sW = (long long)HW * 64; p2.sC = (long long)HW * 64;
       RUN(egemm(e, p2, s));
@@ -315,12 +260,12 @@ int run_roi_path(nuhtc_engine* e, int B, const float* rois_fixed, int n_rois, in
       if (hipMemcpyAsync(it->second.ptr, w->rois, (size_t)Rcap * 5 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) FAIL(e, NUHTC_E_HIP, "memcpy failed");
     RUN(launch_roi_feat(fp, 7, Rcap, s, e->cfg.schedule == NUHTC_SCHED_THROUGHPUT ? nullptr : e->side, e->ev_fpn, e->ev_side, e->side2, e->ev_side2));   // (both events are free again after the RPN join)
     {
-      GemmParams p = gpr(w->feats, e->fc1_w[k], e->fc1_b[k], w->h1, Rcap, 256, 3136);
+      GemmParams p = gp(w->feats, e->fc1_w[k], e->fc1_b[k], w->h1, Rcap, 256, 3136);
       p.act = ACT_RELU; p.m_dev = w->roi_total;
       RUN(egemm(e, p, s));
     }
     {
-      GemmParams p = gpr(w->h1, e->fc2_w[k], e->fc2_b[k], w->h2, Rcap, 256, 256);
+      GemmParams p = gp(w->h1, e->fc2_w[k], e->fc2_b[k], w->h2, Rcap, 256, 256);
       p.act = ACT_RELU; p.m_dev = w->roi_total;
       RUN(egemm(e, p, s));
     }
@@ -365,14 +310,14 @@ int run_roi_path(nuhtc_engine* e, int B, const float* rois_fixed, int n_rois, in
   float* a = w->mfeat;
   float* b = w->mtmpA;
   for (int j = 0; j < 4; ++j) {
-    GemmParams p = gpr(a, e->mk_w[j], e->mk_b[j], b, Dcap * 196, 64, 576);
+    GemmParams p = gp(a, e->mk_w[j], e->mk_b[j], b, Dcap * 196, 64, 576);
     p.amode = A_CONV3; p.cH = 14; p.cW = 14; p.cC = 64; p.act = ACT_RELU; p.m_dev = w->det_total; p.m_mul = 196;
     RUN(egemm(e, p, s));
     a = b;
     b = (b == w->mtmpA) ? w->mtmpB : w->mtmpA;
   }
   {
-    GemmParams p = gpr(a, e->mk_up_w, e->mk_up_b, w->mup, Dcap * 196, 256, 64);
+    GemmParams p = gp(a, e->mk_up_w, e->mk_up_b, w->mup, Dcap * 196, 256, 64);
     p.act = ACT_RELU; p.store = ST_DECONV2; p.cH = 14; p.cW = 14; p.ldc = 64; p.m_dev = w->det_total; p.m_mul = 196;
     RUN(egemm(e, p, s));
   }
@@ -409,26 +354,16 @@ int nuhtc_op_nms(nuhtc_engine* e, const float* boxes, const float* scores, int n
   hipStream_t s = (hipStream_t)stream;
   // scratch sized for this call (test entry point: allocation cost is irrelevant)
   const int cap = std::max(round_up(n, 64), 64);
-  float *sb, *dets;
-  int *src, *ntot, *cnt;
-  unsigned long long* mask;
-  HIP_CHECK(e, hipMalloc((void**)&sb, (size_t)cap * 16));
-  HIP_CHECK(e, hipMalloc((void**)&dets, (size_t)cap * 20));
-  HIP_CHECK(e, hipMalloc((void**)&src, (size_t)cap * 4));
-  HIP_CHECK(e, hipMalloc((void**)&ntot, 4));
-  HIP_CHECK(e, hipMalloc((void**)&cnt, 4));
-  HIP_CHECK(e, hipMalloc((void**)&mask, (size_t)cap * (cap / 64) * 8));
-  HIP_CHECK(e, hipMemcpyAsync(cnt, &n, 4, hipMemcpyHostToDevice, s));
+  DevScratch sc;
   NmsParams np;
   memset(&np, 0, sizeof(np));
-  np.boxes = boxes; np.scores = scores; np.ids = nullptr; np.group_count = cnt; np.n_groups = 1; np.slot = cap; np.cap = cap; np.cap_pow2 = pow2_ge(std::max(n, 2));
-  np.iou_thr = iou_thr; np.max_keep = cap; np.sorted_boxes = sb; np.sorted_src = src; np.n_total = ntot; np.mask = mask; np.out_dets = dets;
+  np.boxes = boxes; np.scores = scores; np.ids = nullptr; np.group_count = sc.upload(&n, 1); np.n_groups = 1; np.slot = cap; np.cap = cap; np.cap_pow2 = pow2_ge(std::max(n, 2));
+  np.iou_thr = iou_thr; np.max_keep = cap; np.sorted_boxes = sc.alloc<float>((size_t)cap * 16); np.sorted_src = sc.alloc<int>((size_t)cap * 4);
+  np.n_total = sc.alloc<int>(4); np.mask = sc.alloc<unsigned long long>((size_t)cap * (cap / 64) * 8); np.out_dets = sc.alloc<float>((size_t)cap * 20);
   np.out_src = keep_idx; np.out_counts = count_dev;
-  int rc = launch_nms(np, 1, s);
-  hipStreamSynchronize(s);
-  hipFree(sb); hipFree(dets); hipFree(src); hipFree(ntot); hipFree(cnt); hipFree(mask);
-  if (rc) FAIL(e, rc, "nms launch failed");
-  return 0;
+  if (!sc.ok()) FAIL(e, NUHTC_E_HIP, "nms op: scratch allocation failed");
+  const int rc = launch_nms(np, 1, s);
+  return op_finish(e, rc, s, "nms launch failed", "nms kernel failed");
 }
 
 int nuhtc_op_cc_mask(nuhtc_engine* e, const float* sem_pred, int B, int h, int w, int H, int W, uint8_t* mask_out, void* stream) {
@@ -453,22 +388,17 @@ int nuhtc_op_cc_proposals(nuhtc_engine* e, const uint8_t* mask, int B, int H, in
   hipStream_t s = (hipStream_t)stream;
   const size_t total = (size_t)B * H * W;
   // scratch sized for this call (test entry point: allocation cost is irrelevant)
-  unsigned char* touch;
-  int *list, *nlist;
-  HIP_CHECK(e, hipMalloc((void**)&touch, total));
-  HIP_CHECK(e, hipMalloc((void**)&list, (size_t)B * CC_LIST_CAP * sizeof(int)));
-  HIP_CHECK(e, hipMalloc((void**)&nlist, (size_t)B * sizeof(int)));
-  int rc = 0;
-  if (hipMemcpyAsync(opened_out, mask, total, hipMemcpyDeviceToDevice, s) != hipSuccess || hipMemsetAsync(overflow_out, 0, sizeof(int32_t), s) != hipSuccess)
-    rc = NUHTC_E_HIP;
+  DevScratch sc;
   CcParams cp;
   memset(&cp, 0, sizeof(cp));
   cp.img_h = H; cp.img_w = W; cp.min_area = min_area; cp.cap = cap;
-  cp.mask_a = opened_out; cp.mask_b = filled_out; cp.touch = touch; cp.labels = labels_out; cp.stats = stats_out; cp.list = list; cp.nlist = nlist;
+  cp.mask_a = opened_out; cp.mask_b = filled_out; cp.touch = sc.alloc<unsigned char>(total); cp.labels = labels_out; cp.stats = stats_out;
+  cp.list = sc.alloc<int>((size_t)B * CC_LIST_CAP * sizeof(int)); cp.nlist = sc.alloc<int>((size_t)B * sizeof(int));
   cp.boxes = boxes_out; cp.counts = counts_out; cp.overflow = overflow_out;
+  if (!sc.ok()) FAIL(e, NUHTC_E_HIP, "cc_proposals op: scratch allocation failed");
+  int rc = 0;
+  if (hipMemcpyAsync(opened_out, mask, total, hipMemcpyDeviceToDevice, s) != hipSuccess || hipMemsetAsync(overflow_out, 0, sizeof(int32_t), s) != hipSuccess)
+    rc = NUHTC_E_HIP;
   if (!rc) rc = launch_cc_from_mask(cp, B, open != 0, s);
-  hipStreamSynchronize(s);
-  hipFree(touch); hipFree(list); hipFree(nlist);
-  if (rc) FAIL(e, rc, "cc_proposals launch failed");
-  return 0;
+  return op_finish(e, rc, s, "cc_proposals launch failed", "cc_proposals kernel failed");
 }

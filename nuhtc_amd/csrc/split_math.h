@@ -1,7 +1,9 @@
-// Device helpers shared by the kernels that run fp32 products on the bf16 matrix pipe (gemm.hip, mlp.hip): the exact three-way
-// bf16 split of an fp32 value, the order of the six products, and the erf-GELU of the FFN.
+// Helpers shared by the code that runs fp32 products on the bf16 matrix pipe (gemm.hip, conv.hip, mlp.hip): the exact three-way
+// bf16 split of an fp32 value (device and host), the order of the six products, and the erf-GELU of the FFN.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <cstring>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -49,6 +51,29 @@ __device__ __forceinline__ Split3 split3_pair(float x, float y) {
   return o;
 }
 #define NUHTC_SPLIT3_INTO(P_, d_, x_, y_) { const Split3 s3_ = split3_pair(x_, y_); (P_)[0][d_] = s3_.p1; (P_)[1][d_] = s3_.p2; (P_)[2][d_] = s3_.p3; }
+
+// the same split on the host, for the weight images packed once (gemm_make_split, conv3_pack_fuse, the mlp.hip streams)
+inline unsigned short bf16_rn_bits(float f) {     // round to nearest even; a NaN stays a NaN (the integer carry would turn some into 0 / Inf)
+  unsigned u;
+  memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x0040u);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (unsigned short)(u >> 16);
+}
+inline float bf16_bits_to_float(unsigned short h) {
+  unsigned u = (unsigned)h << 16;
+  float f;
+  memcpy(&f, &u, 4);
+  return f;
+}
+// planes 1..3 of f -> dst[0], dst[stride], dst[2 stride]; the residuals are exact fp32 subtractions
+inline void bf16_split3(float f, unsigned short* dst, size_t stride) {
+  const unsigned short b1 = bf16_rn_bits(f);
+  const float r1 = f - bf16_bits_to_float(b1);
+  const unsigned short b2 = bf16_rn_bits(r1);
+  const float r2 = r1 - bf16_bits_to_float(b2);
+  dst[0] = b1; dst[stride] = b2; dst[2 * stride] = bf16_rn_bits(r2);
+}
 
 // the six products of one 16-deep step, smallest terms first: a3b1, a1b3, a2b2, a2b1, a1b2, a1b1 (planes 0..2 = a1..a3)
 __device__ __forceinline__ f32x16 mfma_split6(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x16 acc) {
