@@ -337,6 +337,29 @@ typedef struct nuhtc_conv3_args {
   int32_t more_H[3], more_W[3];
 } nuhtc_conv3_args;
 int nuhtc_op_conv3(nuhtc_engine* e, const nuhtc_conv3_args* a, void* stream);
+/* The attention half of a Swin block up to the attention output (mmdet swin.py:356-363 -> ShiftWindowMSA -> WindowMSA up to, not including,
+ * `proj`), as a test entry point: LN1, pad to a multiple of 7, roll(-3, -3) when `shifted`, window partition, QKV, softmax(scale q k^T +
+ * relative-position bias [+ shift mask]) v, reverse partition, roll back, crop.  x: device [B][H][W][C] tokens before LN1; out: device
+ * [B*H*W][C], rows in token order (out_order NUHTC_ORDER_TOKEN: b*H*W + y*W + x) or in the compact window order of the (shift state's)
+ * window image (NUHTC_ORDER_COMPACT: the non-padding window rows in window order).  ln_g / ln_b [C], qkv_w [3C][C], qkv_b [3C], rel_table
+ * [169][C/32] are HOST arrays, packed as nuhtc_finalize packs them.  The geometry (window maps, padding rows, shift mask) is built by the
+ * code the engine builds its own with, for this (B, H, W), and the launches are the engine's route for (pipe, C): on the split pipe the
+ * fused LN1 + QKV kernel (C = 96) or ln_stats + the A_LN linear (C > 96), one bias row behind the window image and the attention kernel that
+ * reads it for every padding row; on the fp32 pipe layernorm_windows + the linear + the fp32 attention kernel.  Private scratch, freed
+ * before the call returns.  C in {96, 192, 384, 768}; B, H, W >= 1.  Synchronises `stream`. */
+enum { NUHTC_ORDER_TOKEN = 0, NUHTC_ORDER_COMPACT = 1 };
+typedef struct nuhtc_wmsa_args {
+  const float* x;
+  float* out;
+  const float* ln_g;
+  const float* ln_b;
+  const float* qkv_w;
+  const float* qkv_b;
+  const float* rel_table;
+  int32_t B, H, W, C;
+  int32_t shifted, pipe, out_order;
+} nuhtc_wmsa_args;
+int nuhtc_op_window_msa(nuhtc_engine* e, const nuhtc_wmsa_args* a, void* stream);
 
 /* A HIP stream owned by the engine (valid after nuhtc_finalize) that a caller MAY run this engine on,
  * and should when it keeps several engines busy at once or raises GPU_MAX_HW_QUEUES above the runtime's default of 4: the stream

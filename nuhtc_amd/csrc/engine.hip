@@ -267,12 +267,28 @@ static void pack_attn_terms(const float* qk /* [49][49] query-major */, float* o
           }
 }
 
-static int build_stage_maps(nuhtc_engine* e, int s) {
-  StageGeom& g = e->st[s];
-  const int B = e->cfg.max_batch;
+// The window geometry of a stage for B images of H x W tokens (mmdet/models/backbones/swin.py:182-226,254-283), host side: what
+// build_stage_maps uploads for the engine and nuhtc_op_window_msa for one call.  g: H, W, Hp, Wp, nW set (stage_dims).
+struct StageMaps {
+  std::vector<int> map[2], cidx[2], ctok[2], vrow[2], prow[2];   // see StageGeom, per shift state
+  std::vector<int> padbits[2];        // 2 words per window of the image
+  int npad = 0;
+  std::vector<float> mask;            // shift mask, packed per lane [nW][4096]
+  std::vector<int> mask_any;          // [nW]
+};
+
+static void stage_dims(StageGeom& g, int H, int W, int C) {
+  g.H = H; g.W = W; g.C = C; g.nH = C / 32;
+  g.Hp = cdiv(H, WS) * WS; g.Wp = cdiv(W, WS) * WS;
+  g.nW = (g.Hp / WS) * (g.Wp / WS);
+}
+
+static StageMaps stage_maps(const StageGeom& g, int B) {
+  StageMaps o;
   // window-row -> token maps (un-shifted and shifted), (mmdet/models/backbones/swin.py:182-226,254-283)
   for (int sh = 0; sh < 2; ++sh) {
-    std::vector<int> m((size_t)B * g.nW * WS2);
+    std::vector<int>& m = o.map[sh];
+    m.resize((size_t)B * g.nW * WS2);
     for (int b = 0; b < B; ++b)
       for (int wy = 0; wy < g.Hp / WS; ++wy)
         for (int wx = 0; wx < g.Wp / WS; ++wx)
@@ -283,41 +299,26 @@ static int build_stage_maps(nuhtc_engine* e, int s) {
               size_t row = ((size_t)b * g.nW + (size_t)wy * (g.Wp / WS) + wx) * WS2 + py * WS + px;
               m[row] = (y < g.H && x < g.W) ? (b * g.H * g.W + y * g.W + x) : -1;
             }
-    int rc = upload(e, &g.map[sh], m);
-    if (rc) return rc;
     // the non-padding window rows in window order: the QKV / proj GEMMs run on these only (padding rows of the window
     // image hold the QKV bias, see launch_layernorm_windows)
-    std::vector<int> ci(m.size()), ct, vr;
+    std::vector<int>&ci = o.cidx[sh], &ct = o.ctok[sh], &vr = o.vrow[sh];
+    ci.resize(m.size());
     ct.reserve((size_t)B * g.H * g.W);
     vr.reserve((size_t)B * g.H * g.W);
     for (size_t r = 0; r < m.size(); ++r) {
       ci[r] = m[r] >= 0 ? (int)ct.size() : -1;
       if (m[r] >= 0) { ct.push_back(m[r]); vr.push_back((int)r); }
     }
-    rc = upload(e, &g.cidx[sh], ci);
-    if (rc) return rc;
-    rc = upload(e, &g.ctok[sh], ct);
-    if (rc) return rc;
-    rc = upload(e, &g.vrow[sh], vr);
-    if (rc) return rc;
-    std::vector<int> pr;                  // padding rows: tile b's are [b * npad, (b + 1) * npad)
+    std::vector<int>& pr = o.prow[sh];    // padding rows: tile b's are [b * npad, (b + 1) * npad)
     for (size_t r = 0; r < m.size(); ++r)
       if (m[r] < 0) pr.push_back((int)r);
-    g.npad = (int)(pr.size() / (size_t)B);
+    o.npad = (int)(pr.size() / (size_t)B);
     if (pr.empty()) pr.push_back(0);
-    rc = upload(e, &g.prow[sh], pr);
-    if (rc) return rc;
-    std::vector<int> pb((size_t)g.nW * 2, 0);          // 49 bits per window of the image (tile 0's windows; every tile has the same)
+    std::vector<int>& pb = o.padbits[sh];    // 49 bits per window of the image (tile 0's windows; every tile has the same)
+    pb.assign((size_t)g.nW * 2, 0);
     for (int w = 0; w < g.nW; ++w)
       for (int j = 0; j < WS2; ++j)
         if (m[(size_t)w * WS2 + j] < 0) pb[(size_t)2 * w + (j >> 5)] |= 1 << (j & 31);
-    rc = upload(e, reinterpret_cast<int**>(&g.padbits[sh]), pb);
-    if (rc) return rc;
-  }
-  g.bias_row = B * g.nW * WS2;
-  {
-    int rc = upload(e, &g.brow, std::vector<int>(1, g.bias_row));
-    if (rc) return rc;
   }
   // shift mask on the padded grid (swin.py:197-218)
   std::vector<int> ids((size_t)g.Hp * g.Wp);
@@ -335,16 +336,60 @@ static int build_stage_maps(nuhtc_engine* e, int s) {
           mask[((size_t)w * WS2 + p) * WS2 + q] = ip == iq ? 0.f : -100.f;
         }
     }
-  std::vector<float> mp((size_t)g.nW * 4096);
-  std::vector<int> any(g.nW, 0);
+  o.mask.resize((size_t)g.nW * 4096);
+  o.mask_any.assign(g.nW, 0);
   for (int w = 0; w < g.nW; ++w) {
-    pack_attn_terms(mask.data() + (size_t)w * WS2 * WS2, mp.data() + (size_t)w * 4096);
+    pack_attn_terms(mask.data() + (size_t)w * WS2 * WS2, o.mask.data() + (size_t)w * 4096);
     for (int i = 0; i < WS2 * WS2; ++i)
-      if (mask[(size_t)w * WS2 * WS2 + i] != 0.f) { any[w] = 1; break; }
+      if (mask[(size_t)w * WS2 * WS2 + i] != 0.f) { o.mask_any[w] = 1; break; }
   }
-  int rc = upload(e, &g.mask, mp);
-  if (rc) return rc;
-  return upload(e, &g.mask_any, any);
+  return o;
+}
+
+// StageMaps -> the device pointers of g through `up` (a host vector -> device copy, null on failure); the bias row sits behind the window
+// image of B images
+template <typename Up>
+static bool upload_stage_maps(StageGeom& g, const StageMaps& m, int B, Up up) {
+  bool ok = true;
+  for (int sh = 0; sh < 2; ++sh) {
+    ok &= (g.map[sh] = up(m.map[sh])) != nullptr;
+    ok &= (g.cidx[sh] = up(m.cidx[sh])) != nullptr;
+    ok &= (g.ctok[sh] = up(m.ctok[sh])) != nullptr;
+    ok &= (g.vrow[sh] = up(m.vrow[sh])) != nullptr;
+    ok &= (g.prow[sh] = up(m.prow[sh])) != nullptr;
+    ok &= (g.padbits[sh] = reinterpret_cast<unsigned long long*>(up(m.padbits[sh]))) != nullptr;
+  }
+  g.npad = m.npad;
+  g.bias_row = B * g.nW * WS2;
+  ok &= (g.brow = up(std::vector<int>(1, g.bias_row))) != nullptr;
+  ok &= (g.mask = up(m.mask)) != nullptr;
+  ok &= (g.mask_any = up(m.mask_any)) != nullptr;
+  return ok;
+}
+
+static int build_stage_maps(nuhtc_engine* e, int s) {
+  StageGeom& g = e->st[s];
+  const int B = e->cfg.max_batch;
+  int rc = 0;
+  auto up = [&](const auto& v) {
+    typename std::remove_const<typename std::remove_reference<decltype(v[0])>::type>::type* p = nullptr;
+    if (!rc) rc = upload(e, &p, v);
+    return rc ? nullptr : p;
+  };
+  upload_stage_maps(g, stage_maps(g, B), B, up);
+  return rc;
+}
+
+// the relative-position bias table [169][nH] -> the per-lane packed terms of the attention kernel, [nH][4096] (pack_attn_terms)
+static std::vector<float> pack_rel_bias(const float* tab, int nH) {
+  std::vector<float> rb((size_t)nH * WS2 * WS2), rbT((size_t)nH * 4096);
+  for (int a = 0; a < WS2; ++a)
+    for (int b = 0; b < WS2; ++b) {
+      const int rel = (a / WS - b / WS + WS - 1) * (2 * WS - 1) + (a % WS - b % WS + WS - 1);
+      for (int h = 0; h < nH; ++h) rb[(size_t)h * WS2 * WS2 + a * WS2 + b] = tab[(size_t)rel * nH + h];
+    }
+  for (int h = 0; h < nH; ++h) pack_attn_terms(rb.data() + (size_t)h * WS2 * WS2, rbT.data() + (size_t)h * 4096);
+  return rbT;
 }
 
 // a LayerNorm in the A path of the linear behind it (gemm.hip A_LN): y = ((x - mean) rstd g + b) W^T + bias = rstd ((x - mean) (W diag g)^T) + (bias + W b);
@@ -403,10 +448,7 @@ int nuhtc_finalize(nuhtc_engine* e) {
   }
   // ---- geometry
   for (int s = 0; s < 4; ++s) {
-    StageGeom& g = e->st[s];
-    g.H = Hn >> (2 + s); g.W = Wn >> (2 + s); g.C = 96 << s; g.nH = NHEADS[s];
-    g.Hp = cdiv(g.H, WS) * WS; g.Wp = cdiv(g.W, WS) * WS;
-    g.nW = (g.Hp / WS) * (g.Wp / WS);
+    stage_dims(e->st[s], Hn >> (2 + s), Wn >> (2 + s), 96 << s);
     if ((rc = build_stage_maps(e, s))) return rc;
   }
   // ---- patch embed: [96][3][4][4] -> [48][96], k = (kh*4+kw)*3 + c
@@ -425,9 +467,6 @@ int nuhtc_finalize(nuhtc_engine* e) {
       return rc;
   }
   // ---- Swin blocks
-  std::vector<int> rel(WS2 * WS2);
-  for (int a = 0; a < WS2; ++a)
-    for (int b2 = 0; b2 < WS2; ++b2) rel[a * WS2 + b2] = (a / WS - b2 / WS + WS - 1) * (2 * WS - 1) + (a % WS - b2 % WS + WS - 1);
   for (int s = 0; s < 4; ++s) {
     const int C = 96 << s, nH = NHEADS[s];
     for (int b = 0; b < DEPTHS[s]; ++b) {
@@ -440,12 +479,7 @@ int nuhtc_finalize(nuhtc_engine* e) {
       RAW(n2w, p + "norm2.weight", C); RAW(n2b, p + "norm2.bias", C);
       RAW(f1w, p + "ffn.layers.0.0.weight", 4 * C, C); RAW(f1b, p + "ffn.layers.0.0.bias", 4 * C);
       RAW(f2w, p + "ffn.layers.1.weight", C, 4 * C); RAW(f2b, p + "ffn.layers.1.bias", C);
-      std::vector<float> rb((size_t)nH * WS2 * WS2);
-      for (int h = 0; h < nH; ++h)
-        for (int i = 0; i < WS2 * WS2; ++i) rb[(size_t)h * WS2 * WS2 + i] = tab->data[(size_t)rel[i] * nH + h];
-      std::vector<float> rbT((size_t)nH * 4096);        // per-lane packed terms of the attention kernel (pack_attn_terms)
-      for (int h = 0; h < nH; ++h) pack_attn_terms(rb.data() + (size_t)h * WS2 * WS2, rbT.data() + (size_t)h * 4096);
-      if ((rc = upload(e, &bw.relbT, rbT))) return rc;
+      if ((rc = upload(e, &bw.relbT, pack_rel_bias(tab->data.data(), nH)))) return rc;
       if ((rc = upload(e, &bw.n1g, n1w->data)) || (rc = upload(e, &bw.n1b, n1b->data)) ||           (rc = upload_gemm_weight(e, &bw.qkv_w, qw->data, 3 * C, C)) || (rc = upload(e, &bw.qkv_b, qb->data)) || (rc = upload_gemm_weight(e, &bw.proj_w, pw->data, C, C)) ||
           (rc = upload(e, &bw.proj_b, pb->data)) || (rc = upload(e, &bw.n2g, n2w->data)) || (rc = upload(e, &bw.n2b, n2b->data)) ||
           (rc = upload_gemm_weight(e, &bw.f1_w, f1w->data, 4 * C, C)) || (rc = upload(e, &bw.f1_b, f1b->data)) || (rc = upload_gemm_weight(e, &bw.f2_w, f2w->data, C, 4 * C)) ||
@@ -650,6 +684,45 @@ static Conv3Fuse pointwise(int N2, const void* w2f, const float* bias2, float* o
   return f;
 }
 
+// The attention half of a block up to the attention output (swin.py:356-363 up to proj): the QKV front writes the window image `qkv` of B
+// images (geometry g, shift state sh), the window attention writes its rows to att[out_map[window row]] (g.map: token order, g.cidx: compact
+// window order).  Only the T real tokens go through the QKV linear: LN1 writes them in window order without the padding rows (xw, T rows) and
+// the linear scatters its rows into the window image, whose padding rows are the QKV bias (LN of a zero-padded token is 0 after swin.py:341-343's
+// F.pad, so its qkv is the bias).  Routes: the fused LN1 + QKV kernel where the block has its weight stream; the norm in the linear's A path where
+// it has the folded weights and a_ln (statistics ln_epi, C / 96 partials per row left by the producer's epilogue, or computed here into
+// ln_scratch); else layernorm_windows + the linear.  qkv_split: the bf16 split of the folded weight (null: the engine's table).
+static int run_attn_front(nuhtc_engine* e, const StageGeom& g, const BlockW& w, int B, int sh, const float* x, float* xw, float* qkv, float* att,
+                          const int* out_map, bool a_ln, const float* ln_epi, float* ln_scratch, const void* qkv_split, bool split_attn, hipStream_t s) {
+  const int T = B * g.H * g.W, Mw = B * g.nW * WS2, C = g.C;
+  // the Swin linears take the block-tile form of the engine's schedule (nuhtc_config.schedule, gemm.hip)
+  auto linear = [&](GemmParams p) { p.throughput = e->cfg.schedule == NUHTC_SCHED_THROUGHPUT; return egemm(e, p, s); };
+  static const int& fused_qkv = dev_knob_ref("FUSED_QKV", 1);
+  // On the split pipe the attention kernel never reads a padding row (StageGeom::padbits): the launch that writes the window image writes ONE
+  // bias row instead of the padding rows (stage 4: 72 % of the image's rows, stages 2-3: 20 %).  dev knob 0 = round 4's image
+  static const int& attn_padbits = dev_knob_ref("ATTN_PADBITS", 1);
+  bool one_bias_row = false;
+  if (w.qkv_stream && fused_qkv) {       // one kernel: LN1, window gather, QKV linear (mlp.hip) + the bias rows of the padding tokens
+    one_bias_row = split_attn && attn_padbits;
+    RUN(launch_swin_lnqkv(x, qkv, g.ctok[sh], g.vrow[sh], one_bias_row ? g.brow : g.prow[sh], one_bias_row ? 1 : B * g.npad, w.n1g, w.n1b, w.qkv_stream, w.qkv_b, T, C, s));
+  } else if (w.qkv_wln && a_ln) {        // the norm rides in the linear's A path; the launch's extra workgroups write the bias rows of the padding tokens
+    if (!ln_epi) RUN(launch_ln_stats(x, ln_scratch, T, C, s));
+    GemmParams p = gp(x, w.qkv_wln, w.qkv_bln, qkv, T, 3 * C, C);
+    p.amode = A_LN; p.ln_part = ln_epi ? ln_epi : ln_scratch; p.ln_nparts = ln_epi ? C / 96 : 1; p.a_rows = g.ctok[sh]; p.Wsplit = qkv_split;
+    one_bias_row = split_attn && attn_padbits;
+    p.pad_rows = one_bias_row ? g.brow : g.prow[sh]; p.n_pad = one_bias_row ? 1 : B * g.npad; p.pad_val = w.qkv_b;
+    p.store = ST_ROWMAP; p.row_map = g.vrow[sh];
+    RUN(linear(p));
+  } else {
+    RUN(launch_layernorm_windows(x, g.map[sh], g.cidx[sh], w.n1g, w.n1b, xw, qkv, w.qkv_b, Mw, C, s));
+    GemmParams p = gp(xw, w.qkv_w, w.qkv_b, qkv, T, 3 * C, C);
+    p.store = ST_ROWMAP; p.row_map = g.vrow[sh];
+    RUN(linear(p));
+  }
+  RUN(launch_window_attn(qkv, w.relbT, sh ? g.mask : nullptr, sh ? g.mask_any : nullptr, out_map, att, B * g.nW, g.nW, C, g.nH, split_attn, s,
+                         one_bias_row ? g.padbits[sh] : nullptr, g.bias_row));
+  return 0;
+}
+
 int run_backbone(nuhtc_engine* e, int B, hipStream_t s) {
   const int Hn = e->Hn, Wn = e->Wn;
   // the Swin linears take the block-tile form of the engine's schedule (nuhtc_config.schedule, gemm.hip)
@@ -681,7 +754,7 @@ int run_backbone(nuhtc_engine* e, int B, hipStream_t s) {
   e->last_batch = B;
   for (int st = 0; st < 4; ++st) {
     const StageGeom& g = e->st[st];
-    const int T = B * g.H * g.W, Mw = B * g.nW * WS2, C = g.C;
+    const int T = B * g.H * g.W, C = g.C;
     const bool merge_a = st < 3 && e->mg_wln[st] && ln_in_a >= 2 && merge_ln_in_a && !e->blocks[st].empty();
     const bool final_stats = merge_a || e->out_ln_folded;      // the last block's FFN leaves the partials of the stage's final tensor in ln_out[st]
     float* xalt = st < 3 ? e->tok[st + 1] : nullptr;
@@ -689,44 +762,19 @@ int run_backbone(nuhtc_engine* e, int B, hipStream_t s) {
       const BlockW& w = e->blocks[st][b];
       const int sh = (int)(b & 1);
       // x += proj(attn(LN1(x)))      (mmdet swin.py:356-363)
-      // Only the T real tokens go through the two linears: LN1 writes them in window order without the padding rows
-      // (xw, T rows), the QKV GEMM scatters its rows into the window image, whose padding rows are the QKV bias
-      // (LN of a zero-padded token is 0 after swin.py:341-343's F.pad, so its qkv is the bias), attention writes the
-      // non-padding rows of its output compactly again and proj scatters them back to token order.
-      static const int& fused_qkv = dev_knob_ref("FUSED_QKV", 1);
-      // On the split pipe the attention kernel never reads a padding row (StageGeom::padbits): the launch that writes the window image writes ONE
-      // bias row instead of the padding rows (stage 4: 72 % of the image's rows, stages 2-3: 20 %).  dev knob 0 = round 4's image
-      static const int& attn_padbits = dev_knob_ref("ATTN_PADBITS", 1);
-      const bool split_attn = e->cfg.matrix_pipe != NUHTC_PIPE_FP32;
-      bool one_bias_row = false;
-      if (w.qkv_stream && fused_qkv) {       // one kernel: LN1, window gather, QKV linear (mlp.hip) + the bias rows of the padding tokens
-        one_bias_row = split_attn && attn_padbits;
-        RUN(launch_swin_lnqkv(x, e->qkv, g.ctok[sh], g.vrow[sh], one_bias_row ? g.brow : g.prow[sh], one_bias_row ? 1 : B * g.npad, w.n1g, w.n1b, w.qkv_stream, w.qkv_b, T, C, s));
-      } else if (w.qkv_wln && ln_in_a) {     // the norm rides in the linear's A path; the launch's extra workgroups write the bias rows of the padding tokens
-        const bool epi = ln_in_a >= 2;       // the statistics were left by the epilogue of the GEMM that produced x (fc2, or the patch merging)
-        if (!epi) RUN(launch_ln_stats(x, e->ln_part, T, C, s));
-        GemmParams p = gp(x, w.qkv_wln, w.qkv_bln, e->qkv, T, 3 * C, C);
-        p.amode = A_LN; p.ln_part = epi && b == 0 ? first_part : e->ln_part; p.ln_nparts = epi ? C / 96 : 1; p.a_rows = g.ctok[sh];
-        one_bias_row = split_attn && attn_padbits;
-        p.pad_rows = one_bias_row ? g.brow : g.prow[sh]; p.n_pad = one_bias_row ? 1 : B * g.npad; p.pad_val = w.qkv_b;
-        p.store = ST_ROWMAP; p.row_map = g.vrow[sh];
-        RUN(linear(p));
-      } else {
-      RUN(launch_layernorm_windows(x, g.map[sh], g.cidx[sh], w.n1g, w.n1b, e->xw, e->qkv, w.qkv_b, Mw, C, s));
-      {
-        GemmParams p = gp(e->xw, w.qkv_w, w.qkv_b, e->qkv, T, 3 * C, C);
-        p.store = ST_ROWMAP; p.row_map = g.vrow[sh];
-        RUN(linear(p));
-      }
-      }
-      // x += W2·gelu(W1·LN2(x))      (swin.py:365-367, mmcv FFN)
       static const int& fused_mlp = dev_knob_ref("FUSED_MLP", 1);
       static const int& fused_proj = dev_knob_ref("FUSED_PROJ", 1);
       const bool mlp1 = w.mlp_stream && fused_mlp, proj1 = mlp1 && w.proj_stream && fused_proj;
       // Where the projection rides in front of the fused FFN kernel (stage 1, round 4) the attention kernel writes its rows in TOKEN
       // order (window row -> token map) instead of the compact window order the projection GEMM scatters from
-      RUN(launch_window_attn(e->qkv, w.relbT, sh ? g.mask : nullptr, sh ? g.mask_any : nullptr, proj1 ? g.map[sh] : g.cidx[sh], e->att, B * g.nW, g.nW, C, g.nH,
-                             split_attn, s, one_bias_row ? g.padbits[sh] : nullptr, g.bias_row));
+      // (ln_in_a >= 2: the LN1 statistics were left by the epilogue of the GEMM that produced x -- fc2, or the patch merging)
+      RUN(run_attn_front(e, g, w, B, sh, x, e->xw, e->qkv, e->att, proj1 ? g.map[sh] : g.cidx[sh], ln_in_a != 0,
+                         ln_in_a >= 2 ? (b == 0 ? first_part : e->ln_part) : nullptr, e->ln_part, nullptr, e->cfg.matrix_pipe != NUHTC_PIPE_FP32, s));
+      if (e->debug_tokens) {
+        auto it = e->bufs.find("att_s" + std::to_string(st) + "b" + std::to_string(b));
+        if (it != e->bufs.end()) hipMemcpyAsync(it->second.ptr, e->att, (size_t)T * C * sizeof(float), hipMemcpyDeviceToDevice, s);
+      }
+      // x += W2·gelu(W1·LN2(x))      (swin.py:365-367, mmcv FFN)
       if (!proj1) {
         GemmParams p = gp(e->att, w.proj_w, w.proj_b, x, T, C, C);
         p.store = ST_ROWMAP; p.row_map = g.ctok[sh]; p.res = x; p.ldr = C;
@@ -1005,13 +1053,16 @@ int nuhtc_check(nuhtc_engine* e, void* stream) {
 int nuhtc_get_buffer(nuhtc_engine* e, const char* name, void** ptr, int64_t* shape, int* ndim, int* dtype) {
   if (!e || !name || !ptr) return NUHTC_E_INVALID;
   if (strcmp(name, "__enable_token_dump") == 0) {
-    // allocate per-block token snapshots (parity tests only)
+    // allocate per-block token and attention-output snapshots (parity tests only)
     if (!e->debug_tokens) {
       for (int s = 0; s < 4; ++s)
         for (int b = 0; b < DEPTHS[s]; ++b) {
           float* p;
           const StageGeom& g = e->st[s];
           int rc = ws(e, &p, ("tok_s" + std::to_string(s) + "b" + std::to_string(b)).c_str(), {e->cfg.max_batch, g.H * g.W, g.C}, 0);
+          if (rc) return rc;
+          // the block's attention output as the kernel wrote it: token order where proj is fused into the FFN kernel, else compact window order
+          rc = ws(e, &p, ("att_s" + std::to_string(s) + "b" + std::to_string(b)).c_str(), {e->cfg.max_batch, g.H * g.W, g.C}, 0);
           if (rc) return rc;
         }
       e->debug_tokens = true;
@@ -1225,6 +1276,55 @@ int nuhtc_op_swin_proj_mlp(nuhtc_engine* e, const float* x_dev, const float* att
   if (out_dev != x_dev && hipMemcpyAsync(out_dev, x_dev, (size_t)T * C * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = NUHTC_E_HIP;
   if (!rc) rc = launch_swin_mlp(out_dev, out_dev, ln_g_dev, ln_b_dev, d, b1_dev, b2_dev, T, C, s, att_dev, dp, bp_dev);
   return op_finish(e, rc, s, "swin_proj_mlp launch failed", "swin_proj_mlp kernel failed");
+}
+
+int nuhtc_op_window_msa(nuhtc_engine* e, const nuhtc_wmsa_args* a, void* stream) {
+  if (!e || !a) return NUHTC_E_INVALID;
+  if (!a->x || !a->out || !a->ln_g || !a->ln_b || !a->qkv_w || !a->qkv_b || !a->rel_table) FAIL(e, NUHTC_E_INVALID, "window_msa op: null argument");
+  const int C = a->C, B = a->B, H = a->H, W = a->W;
+  if (C != 96 && C != 192 && C != 384 && C != 768) FAIL(e, NUHTC_E_INVALID, "window_msa op: C must be 96, 192, 384 or 768");
+  if (a->pipe != NUHTC_PIPE_BF16_SPLIT && a->pipe != NUHTC_PIPE_FP32) FAIL(e, NUHTC_E_INVALID, "window_msa op: unknown pipe");
+  if (a->out_order != NUHTC_ORDER_TOKEN && a->out_order != NUHTC_ORDER_COMPACT) FAIL(e, NUHTC_E_INVALID, "window_msa op: unknown out_order");
+  if (a->shifted != 0 && a->shifted != 1) FAIL(e, NUHTC_E_INVALID, "window_msa op: shifted must be 0 or 1");
+  if (B < 1 || H < 1 || W < 1) FAIL(e, NUHTC_E_INVALID, "window_msa op: B, H, W must be >= 1");
+  // the window image (B images of Hp x Wp rows of 3C floats, + the bias row) must stay below 2^31 elements: row counts and element
+  // offsets of the launches are 32-bit
+  if (((long long)B * (cdiv(H, WS) * (long long)WS) * (cdiv(W, WS) * (long long)WS) + 1) * 3 * C >= (1ll << 31))
+    FAIL(e, NUHTC_E_INVALID, "window_msa op: size out of range (window image >= 2^31 elements)");
+  HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
+  const bool split = a->pipe == NUHTC_PIPE_BF16_SPLIT;
+  StageGeom g{};
+  stage_dims(g, H, W, C);
+  const int T = B * H * W, sh = a->shifted;
+  // the geometry of the engine's stages for B images and the weights packed as nuhtc_finalize packs them, in private scratch
+  DevScratch sc;
+  bool ok = upload_stage_maps(g, stage_maps(g, B), B, [&](const auto& v) { return sc.upload(v); });
+  BlockW w{};
+  w.n1g = sc.upload(a->ln_g, C); w.n1b = sc.upload(a->ln_b, C);
+  w.qkv_w = sc.upload(a->qkv_w, (size_t)3 * C * C); w.qkv_b = sc.upload(a->qkv_b, (size_t)3 * C);
+  w.relbT = sc.upload(pack_rel_bias(a->rel_table, g.nH));
+  const void* qkv_split = nullptr;
+  int rc = 0;
+  if (split && lnqkv_supported(C)) {
+    std::vector<unsigned short> st;
+    lnqkv_pack_stream(a->qkv_w, C, st);
+    w.qkv_stream = sc.upload(st);
+  } else if (split && !mlp_supported(C)) {
+    std::vector<float> w2, b2;
+    fold_ln(a->qkv_w, a->qkv_b, a->ln_g, a->ln_b, 3 * C, C, w2, b2);
+    std::vector<unsigned short> sp;
+    if ((rc = gemm_make_split(w2.data(), 3 * C, C, sp))) FAIL(e, rc, "window_msa op: gemm_make_split failed");
+    w.qkv_wln = sc.upload(w2); w.qkv_bln = sc.upload(b2);
+    qkv_split = sc.upload(sp);
+  }
+  float* qkv = sc.alloc<float>(((size_t)B * g.nW * WS2 + 1) * 3 * C * sizeof(float));
+  float* xw = sc.alloc<float>((size_t)T * C * sizeof(float));
+  float* st = sc.alloc<float>((size_t)T * 2 * sizeof(float));
+  if (!ok || !sc.ok()) FAIL(e, NUHTC_E_HIP, "window_msa op: scratch upload failed");
+  rc = run_attn_front(e, g, w, B, sh, a->x, xw, qkv, a->out, a->out_order == NUHTC_ORDER_TOKEN ? g.map[sh] : g.cidx[sh], true, nullptr, st, qkv_split,
+                      split, s);
+  return op_finish(e, rc, s, "window_msa launch failed", "window_msa kernels failed");
 }
 
 #ifdef NUHTC_DEV

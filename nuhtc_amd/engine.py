@@ -527,3 +527,24 @@ class Engine:
             a.more_in[k], a.more_out2[k], a.more_H[k], a.more_W[k] = m.data_ptr(), more_out2[k].data_ptr(), m.shape[1], m.shape[2]
         self._check(self.lib.nuhtc_op_conv3(self.h, ctypes.byref(a), self._stream()))
         return dict(out=out, out2=out2, out3=out3, outn1=outn1, more_out2=more_out2)
+
+    def op_window_msa(self, x, ln_g, ln_b, qkv_w, qkv_b, rel_table, shifted, pipe='split', order='token', out=None):
+        """The attention half of a Swin block up to the attention output, before proj (nuhtc_op_window_msa): x (B, H, W, C) tokens before
+        LN1 on the device; ln_g / ln_b (C,), qkv_w (3C, C), qkv_b (3C,), rel_table (169, C / 32) anywhere.  pipe 'split' or 'fp32' (the
+        engine's route for that pipe and C); order 'token' (row b*H*W + y*W + x) or 'compact' (the non-padding rows of the shift state's window
+        image in window order).  Returns out (B*H*W, C), allocated when not given."""
+        B, H, W, C = x.shape
+        h = lambda t: np.ascontiguousarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, dtype=np.float32)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        arrs = [h(t) for t in (ln_g, ln_b, qkv_w, qkv_b, rel_table)]
+        want = [(C,), (C,), (3 * C, C), (3 * C,), (169, C // 32)]
+        if [a.shape for a in arrs] != want:
+            raise ValueError(f'op_window_msa: weight shapes {[a.shape for a in arrs]}, expected {want}')
+        if out is None:
+            out = torch.empty(B * H * W, C, dtype=torch.float32, device=self.device)
+        a = hip.WmsaArgs(x=x.data_ptr(), out=out.data_ptr(), ln_g=vp(arrs[0]), ln_b=vp(arrs[1]), qkv_w=vp(arrs[2]), qkv_b=vp(arrs[3]),
+                         rel_table=vp(arrs[4]), B=B, H=H, W=W, C=C, shifted=int(bool(shifted)),
+                         pipe=hip.PIPE_FP32 if pipe == 'fp32' else hip.PIPE_BF16_SPLIT,
+                         out_order=hip.ORDER_COMPACT if order == 'compact' else hip.ORDER_TOKEN)
+        self._check(self.lib.nuhtc_op_window_msa(self.h, ctypes.byref(a), self._stream()))
+        return out

@@ -15,6 +15,7 @@ OK, E_INVALID, E_HIP, E_STATE, E_CAPACITY, E_NOTFOUND = 0, -1, -2, -3, -4, -5
 CH_AS_IS, CH_SWAP = 0, 1
 OVERLAP_MASK, OVERLAP_POLYGON = 0, 1
 PIPE_BF16_SPLIT, PIPE_FP32 = 0, 1
+ORDER_TOKEN, ORDER_COMPACT = 0, 1
 SCHED_LATENCY, SCHED_THROUGHPUT = 0, 1
 
 
@@ -49,6 +50,16 @@ class Conv3Args(ctypes.Structure):
     ]
 
 
+class WmsaArgs(ctypes.Structure):
+    """nuhtc_wmsa_args: the arguments of nuhtc_op_window_msa (the attention half of a Swin block up to the attention output)."""
+    _fields_ = [
+        ('x', ctypes.c_void_p), ('out', ctypes.c_void_p), ('ln_g', ctypes.c_void_p), ('ln_b', ctypes.c_void_p),
+        ('qkv_w', ctypes.c_void_p), ('qkv_b', ctypes.c_void_p), ('rel_table', ctypes.c_void_p),
+        ('B', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('C', ctypes.c_int32),
+        ('shifted', ctypes.c_int32), ('pipe', ctypes.c_int32), ('out_order', ctypes.c_int32),
+    ]
+
+
 class Dets(ctypes.Structure):
     _fields_ = [('boxes', ctypes.c_void_p), ('labels', ctypes.c_void_p), ('counts', ctypes.c_void_p),
                 ('masks', ctypes.c_void_p), ('areas', ctypes.c_void_p), ('keep', ctypes.c_void_p)]
@@ -60,7 +71,7 @@ EXPORTS = ['nuhtc_default_config', 'nuhtc_create', 'nuhtc_destroy', 'nuhtc_last_
            'nuhtc_mask_contours', 'nuhtc_merge_overlap', 'nuhtc_export_kept', 'nuhtc_clock_probe', 'nuhtc_op_swin_mlp', 'nuhtc_stream', 'nuhtc_op_swin_proj_mlp', 'nuhtc_bind_host_thread',
            'nuhtc_bind_host_thread_pci', 'nuhtc_bind_host_thread_at', 'nuhtc_restore_host_thread', 'nuhtc_op_ln_gemm', 'nuhtc_op_gemm_ln_gemm', 'nuhtc_op_merge_ln_gemm', 'nuhtc_write_ring_features',
            'nuhtc_write_point_features', 'nuhtc_join_features', 'nuhtc_fill_rings', 'nuhtc_features', 'nuhtc_op_cc_mask', 'nuhtc_op_cc_proposals',
-           'nuhtc_op_conv3']
+           'nuhtc_op_conv3', 'nuhtc_op_window_msa']
 
 _lib = None
 
@@ -105,6 +116,7 @@ def load():
     lib.nuhtc_op_cc_mask.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp]
     lib.nuhtc_op_cc_proposals.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.nuhtc_op_conv3.argtypes = [vp, ctypes.POINTER(Conv3Args), vp]
+    lib.nuhtc_op_window_msa.argtypes = [vp, ctypes.POINTER(WmsaArgs), vp]
     lib.nuhtc_mask_contours.argtypes = [vp, ctypes.POINTER(Dets), ci, ci, vp, vp, vp]
     lib.nuhtc_merge_overlap.argtypes = [ci, vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int64, ci, ctypes.c_double, ci, ci, ci, ci, vp, vp]
     lib.nuhtc_export_kept.argtypes = [vp, ctypes.POINTER(Dets), ci, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
