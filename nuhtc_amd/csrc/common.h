@@ -187,7 +187,6 @@ int gemm_make_split(const float* w_host, int N, int K, std::vector<unsigned shor
 // 3x3 convolution 64 -> 64 with the input halo resident in LDS as bf16 planes (conv.hip); launch_gemm routes A_CONV3 products with a
 // split weight there
 bool conv3_split_supported(const GemmParams& p);
-bool conv3_fuse_available();      // false when the dev knob CONV_HALO routes 3x3 convolutions to the implicit-GEMM path
 int launch_conv3_split(const GemmParams& p, hipStream_t s);
 
 // ----------------------------------------------------------------------------- fused FFN half of a Swin block (mlp.hip)
@@ -232,13 +231,11 @@ int launch_preproc(const uint8_t* tiles, float* img, int B, int th, int tw, int 
                    const float* mean_istd, hipStream_t s);
 int launch_patch_embed_tiles(const uint8_t* tiles, int B, int th, int tw, int Hn, int Wn, int Hv, int Wv, const int* xtab, const int* ytab, int swap,
                              const float* mean_istd, const float* w, const float* b, const float* g, const float* beta, float* tok, hipStream_t s);
-int launch_patch_embed(const float* img, const float* w, const float* b, const float* g, const float* beta, float* tok,
-                       int B, int Hn, int Wn, hipStream_t s);
 // LayerNorm of `rows` rows of C channels: dst row m reads src row src_map[m] (or m when src_map==null); src_map[m]<0 -> zeros
 int launch_layernorm(const float* x, const int* src_map, const float* g, const float* b, float* y, int rows, int C, hipStream_t s);
 // per-row LayerNorm statistics for a product in A_LN mode, as ONE partial per row (GemmParams.ln_part with ln_nparts = 1):
 // stats[2r] = mean, stats[2r + 1] = sum of squared deviations of row r of x (rows [0, rows)), computed with the loads, the two passes and
-// the summation order of layernorm_kernel.  Stand-alone op and dev fallback: in the engine the producer GEMM's epilogue leaves the partials.
+// the summation order of layernorm_kernel.  The op entry points use it: in the engine the producer GEMM's epilogue leaves the partials.
 int launch_ln_stats(const float* x, float* stats, int rows, int C, hipStream_t s);
 // LN1 of a Swin block over the `rows` window rows: row r with src_map[r] >= 0 is normalised into y[dst_map[r]] (the compact,
 // padding-free window order); a padding row writes pad_val[0..3C) (the QKV bias) into pad_dst[r] (the window QKV image).

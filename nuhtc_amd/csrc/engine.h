@@ -11,8 +11,6 @@ struct StageGeom {
   int* cidx[2];        // dev: window-row -> index among the non-padding window rows (-1 = padding); tile b's rows are [b*H*W, (b+1)*H*W)
   int* ctok[2];        // dev: that compact index -> token index, [max_batch*H*W]
   int* vrow[2];        // dev: that compact index -> window row
-  int* prow[2];        // dev: the padding rows of the window image (map < 0), per-tile lists back to back; npad per tile
-  int npad;
   // the attention kernel of the split pipe never reads a padding row: bit j of padbits[shift][window of the image] says row j of the window
   // is one, and the kernel reads row `bias_row` (one row behind the window image of the largest batch, holding the block's QKV bias) instead
   unsigned long long* padbits[2];
@@ -22,14 +20,20 @@ struct StageGeom {
   int* mask_any;       // dev: [nW] 1 where the window's mask has a non-zero entry
 };
 
+// Which kernels a Swin block runs through (engine.hip block_route): layernorm kernels + plain linears | the norms in the A path of the QKV / fc1
+// linears | the fused LN1 + QKV kernel and the fused projection + FFN kernel (mlp.hip)
+enum BlockRoute { ROUTE_PLAIN, ROUTE_A_LN, ROUTE_FUSED };
+
 struct BlockW {
+  BlockRoute route;
   float *n1g, *n1b, *relbT /* relative-position bias packed per lane [nH][4096] */, *qkv_w, *qkv_b, *proj_w, *proj_b, *n2g, *n2b, *f1_w, *f1_b, *f2_w, *f2_b;
-  // LayerNorm in the A path of the linear that follows it (stages 2-4 on the split pipe, gemm.hip A_LN): the norm's affine part folded into
-  // the linear -- W' = W diag(gamma), b' = b + W beta (fp64 on the host, rounded once) -- null where the norm runs as a kernel of its own
+  // ROUTE_A_LN (gemm.hip A_LN): the norm's affine part folded into the linear behind it -- W' = W diag(gamma), b' = b + W beta (fp64 on the
+  // host, rounded once); null on the other routes
   float *qkv_wln, *qkv_bln, *f1_wln, *f1_bln;
-  void* qkv_stream;    // fused LN1 + QKV (mlp.hip): k-permuted split planes of qkv_w, null where LN + GEMM run separately
-  void* mlp_stream;    // fused FFN half (mlp.hip): chunk-major split planes of f1_w / f2_w, null where the three separate launches run
-  void* proj_stream;   // attention projection in front of the fused FFN half (mlp.hip): k-permuted split planes of proj_w, null where proj is a GEMM launch
+  // ROUTE_FUSED (mlp.hip), null on the other routes:
+  void* qkv_stream;    // fused LN1 + QKV: k-permuted split planes of qkv_w
+  void* mlp_stream;    // fused FFN half: chunk-major split planes of f1_w / f2_w
+  void* proj_stream;   // attention projection in front of the fused FFN half: k-permuted split planes of proj_w
 };
 
 struct nuhtc_engine {
@@ -57,8 +61,11 @@ struct nuhtc_engine {
   // backbone weights
   float *pe_w = nullptr, *pe_b = nullptr, *pe_g = nullptr, *pe_beta = nullptr;
   std::vector<BlockW> blocks[4];
+  // decided at finalize from what was packed: PatchMerging of stage st in one launch (mg_wln[st]: split pipe and even H, W), the output norms in the
+  // FPN laterals (lat_wln: split pipe), the pointwise layers in the 3x3 convolutions' epilogues (rpn_hf: split pipe and detection heads)
+  bool merge_one_launch[3] = {}, out_ln_folded = false, conv_fuse = false;
   float *on_g[4], *on_b[4], *mg_g[3], *mg_b[3], *mg_w[3];
-  float *mg_wln[3] = {}, *mg_bln[3] = {};   // PatchMerging norm folded into its reduction linear (gemm.hip A_LN, two segments): W diag(gamma), W beta; split pipe only
+  float *mg_wln[3] = {}, *mg_bln[3] = {};   // PatchMerging norm folded into its reduction linear (gemm.hip A_LN, two segments): W diag(gamma), W beta
   int* mg_src[3] = {};                     // dev: merged row -> its top-left token (b, 2 y2, 2 x2) of the stage's token tensor, [max_batch * H/2 * W/2]
   // neck / dense heads
   float *lat_w[4], *lat_b[4], *fpn_w[4], *fpn_b[4];
@@ -71,16 +78,14 @@ struct nuhtc_engine {
 
   // workspace
   float *img, *tokA, *tokB, *xw, *qkv, *att, *hid;
-  // Output norms of the stages (swin.py:756-762) in the A path of the FPN lateral that consumes them (round 5): every stage keeps its own token
+  // Output norms of the stages (swin.py:756-762) in the A path of the FPN lateral that consumes them (split pipe): every stage keeps its own token
   // buffer and the partials of its final tensor until the neck has run; c[st] then exists only on request (nuhtc_get_buffer computes it)
   float* tok[4] = {};           // tok[0] = tokA, tok[1] = tokB, two more
   float* ln_out[4] = {};        // partials of the stage's final tensor, left by its last block's FFN
   float *lat_wln[4] = {}, *lat_bln[4] = {};   // lateral 1x1 with the output norm folded in: W diag(gamma), b + W beta
-  // pre-processing inside the patch embedding (round 5): the tiles of the running call; `img` is then computed only on request (nuhtc_get_buffer)
+  // pre-processing inside the patch embedding: the tiles of the running call; `img` is computed only on request (nuhtc_get_buffer)
   const uint8_t* in_tiles = nullptr;
   int in_swap = 0;
-  bool img_stale = false;
-  bool out_ln_folded = false;   // the last run took that path (c[st] is stale until requested)
   int last_batch = 0;
   float* ln_part2 = nullptr;   // the partials the patch-merging GEMM leaves for the next stage's first block (it READS ln_part in the same launch)
   float* ln_part = nullptr;    // LayerNorm partials of the current token tensor, [token][C / 96][2] = {mean, sum of squared deviations} per 96 channels:

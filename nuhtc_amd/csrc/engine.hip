@@ -270,9 +270,8 @@ static void pack_attn_terms(const float* qk /* [49][49] query-major */, float* o
 // The window geometry of a stage for B images of H x W tokens (mmdet/models/backbones/swin.py:182-226,254-283), host side: what
 // build_stage_maps uploads for the engine and nuhtc_op_window_msa for one call.  g: H, W, Hp, Wp, nW set (stage_dims).
 struct StageMaps {
-  std::vector<int> map[2], cidx[2], ctok[2], vrow[2], prow[2];   // see StageGeom, per shift state
+  std::vector<int> map[2], cidx[2], ctok[2], vrow[2];   // see StageGeom, per shift state
   std::vector<int> padbits[2];        // 2 words per window of the image
-  int npad = 0;
   std::vector<float> mask;            // shift mask, packed per lane [nW][4096]
   std::vector<int> mask_any;          // [nW]
 };
@@ -309,11 +308,6 @@ static StageMaps stage_maps(const StageGeom& g, int B) {
       ci[r] = m[r] >= 0 ? (int)ct.size() : -1;
       if (m[r] >= 0) { ct.push_back(m[r]); vr.push_back((int)r); }
     }
-    std::vector<int>& pr = o.prow[sh];    // padding rows: tile b's are [b * npad, (b + 1) * npad)
-    for (size_t r = 0; r < m.size(); ++r)
-      if (m[r] < 0) pr.push_back((int)r);
-    o.npad = (int)(pr.size() / (size_t)B);
-    if (pr.empty()) pr.push_back(0);
     std::vector<int>& pb = o.padbits[sh];    // 49 bits per window of the image (tile 0's windows; every tile has the same)
     pb.assign((size_t)g.nW * 2, 0);
     for (int w = 0; w < g.nW; ++w)
@@ -356,10 +350,8 @@ static bool upload_stage_maps(StageGeom& g, const StageMaps& m, int B, Up up) {
     ok &= (g.cidx[sh] = up(m.cidx[sh])) != nullptr;
     ok &= (g.ctok[sh] = up(m.ctok[sh])) != nullptr;
     ok &= (g.vrow[sh] = up(m.vrow[sh])) != nullptr;
-    ok &= (g.prow[sh] = up(m.prow[sh])) != nullptr;
     ok &= (g.padbits[sh] = reinterpret_cast<unsigned long long*>(up(m.padbits[sh]))) != nullptr;
   }
-  g.npad = m.npad;
   g.bias_row = B * g.nW * WS2;
   ok &= (g.brow = up(std::vector<int>(1, g.bias_row))) != nullptr;
   ok &= (g.mask = up(m.mask)) != nullptr;
@@ -428,6 +420,13 @@ static MergePack pack_merge(const float* g, const float* b, const float* w, int 
   return m;
 }
 
+// The route of a Swin block, from what is known at finalize.  The fp32 pipe has the plain kernels only; on the split pipe the block runs through the
+// fused kernels of mlp.hip where they exist for its channel count (stage 1), else with its two norms in the A path of the QKV / fc1 linears.
+static BlockRoute block_route(int matrix_pipe, int C) {
+  if (matrix_pipe != NUHTC_PIPE_BF16_SPLIT) return ROUTE_PLAIN;
+  return lnqkv_supported(C) && mlp_supported(C) ? ROUTE_FUSED : ROUTE_A_LN;
+}
+
 int nuhtc_finalize(nuhtc_engine* e) {
   if (!e) return NUHTC_E_INVALID;
   if (e->finalized) FAIL(e, NUHTC_E_STATE, "finalize called twice");
@@ -471,6 +470,7 @@ int nuhtc_finalize(nuhtc_engine* e) {
     const int C = 96 << s, nH = NHEADS[s];
     for (int b = 0; b < DEPTHS[s]; ++b) {
       BlockW bw{};
+      bw.route = block_route(c.matrix_pipe, C);
       std::string p = "backbone.stages." + std::to_string(s) + ".blocks." + std::to_string(b) + ".";
       RAW(n1w, p + "norm1.weight", C); RAW(n1b, p + "norm1.bias", C);
       RAW(tab, p + "attn.w_msa.relative_position_bias_table", 169, nH);
@@ -485,7 +485,7 @@ int nuhtc_finalize(nuhtc_engine* e) {
           (rc = upload_gemm_weight(e, &bw.f1_w, f1w->data, 4 * C, C)) || (rc = upload(e, &bw.f1_b, f1b->data)) || (rc = upload_gemm_weight(e, &bw.f2_w, f2w->data, C, 4 * C)) ||
           (rc = upload(e, &bw.f2_b, f2b->data)))
         return rc;
-      if (e->cfg.matrix_pipe == NUHTC_PIPE_BF16_SPLIT && !lnqkv_supported(C) && !mlp_supported(C)) {
+      if (bw.route == ROUTE_A_LN) {
         // the two norms of the block ride in the A path of the linear behind them (gemm.hip A_LN, fold_ln)
         auto fold = [&](const std::vector<float>& W, const std::vector<float>& bias, const std::vector<float>& gam, const std::vector<float>& bet, int N,
                         float** wdev, float** bdev) -> int {
@@ -498,13 +498,10 @@ int nuhtc_finalize(nuhtc_engine* e) {
             (rc = fold(f1w->data, f1b->data, n2w->data, n2b->data, 4 * C, &bw.f1_wln, &bw.f1_bln)))
           return rc;
       }
-      if (e->cfg.matrix_pipe == NUHTC_PIPE_BF16_SPLIT && lnqkv_supported(C)) {
+      if (bw.route == ROUTE_FUSED) {
         std::vector<unsigned short> st;
         lnqkv_pack_stream(qw->data.data(), C, st);
         if ((rc = upload_bytes(e, &bw.qkv_stream, st.data(), st.size() * 2))) return rc;
-      }
-      if (e->cfg.matrix_pipe == NUHTC_PIPE_BF16_SPLIT && mlp_supported(C)) {
-        std::vector<unsigned short> st;
         mlp_pack_stream(f1w->data.data(), f2w->data.data(), C, st);
         if ((rc = upload_bytes(e, &bw.mlp_stream, st.data(), st.size() * 2))) return rc;
         proj_pack_stream(pw->data.data(), C, st);
@@ -525,7 +522,8 @@ int nuhtc_finalize(nuhtc_engine* e) {
       const StageGeom& g = e->st[s];
       const MergePack m = pack_merge(nw->data.data(), nb->data.data(), rw->data.data(), C, B, g.H, g.W);
       if ((rc = upload(e, &e->mg_g[s], m.g)) || (rc = upload(e, &e->mg_b[s], m.b)) || (rc = upload_gemm_weight(e, &e->mg_w[s], m.w, 2 * C, 4 * C))) return rc;
-      if (e->cfg.matrix_pipe == NUHTC_PIPE_BF16_SPLIT && g.H % 2 == 0 && g.W % 2 == 0) {
+      e->merge_one_launch[s] = c.matrix_pipe == NUHTC_PIPE_BF16_SPLIT && g.H % 2 == 0 && g.W % 2 == 0;
+      if (e->merge_one_launch[s]) {
         // the merging norm in the A path of the reduction linear (gemm.hip A_LN, two segments per row): W' = W diag(gamma), b' = W beta
         std::vector<float> wl, bl;
         fold_ln(m.w.data(), nullptr, m.g.data(), m.b.data(), 2 * C, 4 * C, wl, bl);
@@ -534,6 +532,7 @@ int nuhtc_finalize(nuhtc_engine* e) {
     }
   }
   // ---- FPN
+  e->out_ln_folded = c.matrix_pipe == NUHTC_PIPE_BF16_SPLIT;
   for (int i = 0; i < 4; ++i) {
     const int C = 96 << i;
     RAW(lw, "neck.lateral_convs." + std::to_string(i) + ".conv.weight", 64, C, 1, 1);
@@ -543,7 +542,7 @@ int nuhtc_finalize(nuhtc_engine* e) {
     if ((rc = upload_gemm_weight(e, &e->lat_w[i], lw->data, 64, C)) || (rc = upload(e, &e->lat_b[i], lb->data)) ||
         (rc = upload_gemm_weight(e, &e->fpn_w[i], pack_conv3(*fw, 64, 64), 64, 576)) || (rc = upload(e, &e->fpn_b[i], fb->data)))
       return rc;
-    if (e->cfg.matrix_pipe == NUHTC_PIPE_BF16_SPLIT) {      // the stage's output norm folded into its lateral (gemm.hip A_LN, N = 64)
+    if (e->out_ln_folded) {      // the stage's output norm folded into its lateral (gemm.hip A_LN, N = 64)
       std::vector<float> wl, bl;
       fold_ln(lw->data.data(), lb->data.data(), on_g_host[i].data(), on_b_host[i].data(), 64, C, wl, bl);
       if ((rc = upload_gemm_weight(e, &e->lat_wln[i], wl, 64, C)) || (rc = upload(e, &e->lat_bln[i], bl))) return rc;
@@ -568,6 +567,7 @@ int nuhtc_finalize(nuhtc_engine* e) {
     if ((rc = upload_gemm_weight(e, &e->rpn_w, pack_conv3(*cw, 64, 64), 64, 576)) || (rc = upload(e, &e->rpn_b, cb->data)) ||
         (rc = upload_gemm_weight(e, &e->rpn_hw, w, 32, 64)) || (rc = upload(e, &e->rpn_hb, b)) || (rc = upload_fuse(e, &e->rpn_hf, w, 32)))
       return rc;
+    e->conv_fuse = e->rpn_hf != nullptr;
   }
   // ---- semantic head
   if (heads) {
@@ -686,40 +686,43 @@ static Conv3Fuse pointwise(int N2, const void* w2f, const float* bias2, float* o
 
 // The attention half of a block up to the attention output (swin.py:356-363 up to proj): the QKV front writes the window image `qkv` of B
 // images (geometry g, shift state sh), the window attention writes its rows to att[out_map[window row]] (g.map: token order, g.cidx: compact
-// window order).  Only the T real tokens go through the QKV linear: LN1 writes them in window order without the padding rows (xw, T rows) and
-// the linear scatters its rows into the window image, whose padding rows are the QKV bias (LN of a zero-padded token is 0 after swin.py:341-343's
-// F.pad, so its qkv is the bias).  Routes: the fused LN1 + QKV kernel where the block has its weight stream; the norm in the linear's A path where
-// it has the folded weights and a_ln (statistics ln_epi, C / 96 partials per row left by the producer's epilogue, or computed here into
-// ln_scratch); else layernorm_windows + the linear.  qkv_split: the bf16 split of the folded weight (null: the engine's table).
+// window order).  Only the T real tokens go through the QKV linear, which scatters its rows into the window image; a padding row of the image is
+// the QKV bias (LN of a zero-padded token is 0 after swin.py:341-343's F.pad, so its qkv is the bias).  By the block's route:
+//   ROUTE_FUSED    one kernel: LN1, window gather, QKV linear (mlp.hip)
+//   ROUTE_A_LN     the norm in the linear's A path: statistics ln_epi (C / 96 partials per row, left by the producer's epilogue) or, with ln_epi
+//                  null, computed here into ln_scratch; qkv_split: the bf16 split of the folded weight (null: the engine's table)
+//   ROUTE_PLAIN    layernorm_windows writes the tokens in window order without the padding rows (xw, T rows) and the padding rows, then the linear
+// On the first two the attention kernel never reads a padding row (StageGeom::padbits): the launch that writes the window image writes ONE bias row
+// instead of the padding rows (stage 4: 72 % of the image's rows, stages 2-3: 20 %; profiles/r05_padbits_merge_ln.txt).
 static int run_attn_front(nuhtc_engine* e, const StageGeom& g, const BlockW& w, int B, int sh, const float* x, float* xw, float* qkv, float* att,
-                          const int* out_map, bool a_ln, const float* ln_epi, float* ln_scratch, const void* qkv_split, bool split_attn, hipStream_t s) {
+                          const int* out_map, const float* ln_epi, float* ln_scratch, const void* qkv_split, hipStream_t s) {
   const int T = B * g.H * g.W, Mw = B * g.nW * WS2, C = g.C;
   // the Swin linears take the block-tile form of the engine's schedule (nuhtc_config.schedule, gemm.hip)
   auto linear = [&](GemmParams p) { p.throughput = e->cfg.schedule == NUHTC_SCHED_THROUGHPUT; return egemm(e, p, s); };
-  static const int& fused_qkv = dev_knob_ref("FUSED_QKV", 1);
-  // On the split pipe the attention kernel never reads a padding row (StageGeom::padbits): the launch that writes the window image writes ONE
-  // bias row instead of the padding rows (stage 4: 72 % of the image's rows, stages 2-3: 20 %).  dev knob 0 = round 4's image
-  static const int& attn_padbits = dev_knob_ref("ATTN_PADBITS", 1);
-  bool one_bias_row = false;
-  if (w.qkv_stream && fused_qkv) {       // one kernel: LN1, window gather, QKV linear (mlp.hip) + the bias rows of the padding tokens
-    one_bias_row = split_attn && attn_padbits;
-    RUN(launch_swin_lnqkv(x, qkv, g.ctok[sh], g.vrow[sh], one_bias_row ? g.brow : g.prow[sh], one_bias_row ? 1 : B * g.npad, w.n1g, w.n1b, w.qkv_stream, w.qkv_b, T, C, s));
-  } else if (w.qkv_wln && a_ln) {        // the norm rides in the linear's A path; the launch's extra workgroups write the bias rows of the padding tokens
-    if (!ln_epi) RUN(launch_ln_stats(x, ln_scratch, T, C, s));
-    GemmParams p = gp(x, w.qkv_wln, w.qkv_bln, qkv, T, 3 * C, C);
-    p.amode = A_LN; p.ln_part = ln_epi ? ln_epi : ln_scratch; p.ln_nparts = ln_epi ? C / 96 : 1; p.a_rows = g.ctok[sh]; p.Wsplit = qkv_split;
-    one_bias_row = split_attn && attn_padbits;
-    p.pad_rows = one_bias_row ? g.brow : g.prow[sh]; p.n_pad = one_bias_row ? 1 : B * g.npad; p.pad_val = w.qkv_b;
-    p.store = ST_ROWMAP; p.row_map = g.vrow[sh];
-    RUN(linear(p));
-  } else {
-    RUN(launch_layernorm_windows(x, g.map[sh], g.cidx[sh], w.n1g, w.n1b, xw, qkv, w.qkv_b, Mw, C, s));
-    GemmParams p = gp(xw, w.qkv_w, w.qkv_b, qkv, T, 3 * C, C);
-    p.store = ST_ROWMAP; p.row_map = g.vrow[sh];
-    RUN(linear(p));
+  switch (w.route) {
+    case ROUTE_FUSED:
+      RUN(launch_swin_lnqkv(x, qkv, g.ctok[sh], g.vrow[sh], g.brow, 1, w.n1g, w.n1b, w.qkv_stream, w.qkv_b, T, C, s));
+      break;
+    case ROUTE_A_LN: {      // the launch's extra workgroups write the bias row
+      if (!ln_epi) RUN(launch_ln_stats(x, ln_scratch, T, C, s));
+      GemmParams p = gp(x, w.qkv_wln, w.qkv_bln, qkv, T, 3 * C, C);
+      p.amode = A_LN; p.ln_part = ln_epi ? ln_epi : ln_scratch; p.ln_nparts = ln_epi ? C / 96 : 1; p.a_rows = g.ctok[sh]; p.Wsplit = qkv_split;
+      p.pad_rows = g.brow; p.n_pad = 1; p.pad_val = w.qkv_b;
+      p.store = ST_ROWMAP; p.row_map = g.vrow[sh];
+      RUN(linear(p));
+      break;
+    }
+    case ROUTE_PLAIN: {
+      RUN(launch_layernorm_windows(x, g.map[sh], g.cidx[sh], w.n1g, w.n1b, xw, qkv, w.qkv_b, Mw, C, s));
+      GemmParams p = gp(xw, w.qkv_w, w.qkv_b, qkv, T, 3 * C, C);
+      p.store = ST_ROWMAP; p.row_map = g.vrow[sh];
+      RUN(linear(p));
+      break;
+    }
   }
-  RUN(launch_window_attn(qkv, w.relbT, sh ? g.mask : nullptr, sh ? g.mask_any : nullptr, out_map, att, B * g.nW, g.nW, C, g.nH, split_attn, s,
-                         one_bias_row ? g.padbits[sh] : nullptr, g.bias_row));
+  const bool split = w.route != ROUTE_PLAIN;
+  RUN(launch_window_attn(qkv, w.relbT, sh ? g.mask : nullptr, sh ? g.mask_any : nullptr, out_map, att, B * g.nW, g.nW, C, g.nH, split, s,
+                         split ? g.padbits[sh] : nullptr, g.bias_row));
   return 0;
 }
 
@@ -727,102 +730,75 @@ int run_backbone(nuhtc_engine* e, int B, hipStream_t s) {
   const int Hn = e->Hn, Wn = e->Wn;
   // the Swin linears take the block-tile form of the engine's schedule (nuhtc_config.schedule, gemm.hip)
   auto linear = [&](GemmParams p) { p.throughput = e->cfg.schedule == NUHTC_SCHED_THROUGHPUT; return egemm(e, p, s); };
-  {
-    // dev: 1 (the tree) = resize + Normalize + Pad inside the patch embedding (one launch, no `img` tensor); 0 = preproc_kernel, then patch_embed_kernel
-    static const int& preproc_fused = dev_knob_ref("PREPROC_FUSED", 1);
+  {      // resize + Normalize + Pad inside the patch embedding: one launch, no `img` tensor (profiles/r05_preproc_fused.txt)
     float mi[6];
     for (int i = 0; i < 3; ++i) { mi[i] = e->cfg.mean[i]; mi[3 + i] = (float)(1.0 / (double)e->cfg.std[i]); }
-    e->img_stale = preproc_fused != 0;
-    if (preproc_fused) {
-      RUN(launch_patch_embed_tiles(e->in_tiles, B, e->cfg.tile_h, e->cfg.tile_w, Hn, Wn, e->Hv, e->Wv, e->rs_xtab, e->rs_ytab, e->in_swap, mi, e->pe_w, e->pe_b, e->pe_g, e->pe_beta,
-                                   e->tokA, s));
-    } else {
-      RUN(launch_preproc(e->in_tiles, e->img, B, e->cfg.tile_h, e->cfg.tile_w, Hn, Wn, e->Hv, e->Wv, e->rs_xtab, e->rs_ytab, e->in_swap, mi, s));
-      RUN(launch_patch_embed(e->img, e->pe_w, e->pe_b, e->pe_g, e->pe_beta, e->tokA, B, Hn, Wn, s));
-    }
+    RUN(launch_patch_embed_tiles(e->in_tiles, B, e->cfg.tile_h, e->cfg.tile_w, Hn, Wn, e->Hv, e->Wv, e->rs_xtab, e->rs_ytab, e->in_swap, mi, e->pe_w, e->pe_b, e->pe_g, e->pe_beta,
+                                 e->tokA, s));
   }
   float* x = e->tok[0];
-  // dev: 0 = the norms of stages 2-4 as kernels of their own (round 4); 1 = in the A path of the linear behind them, statistics by a kernel
-  // of their own; 2 (the tree) = statistics left by the epilogue of the GEMM that produced the tensor
-  static const int& ln_in_a = dev_knob_ref("LN_IN_A", 2);
-  // dev: 1 (the tree) = the PatchMerging norms as well (two-segment rows, statistics from the last block's FFN); 0 = merge_ln_kernel + plain GEMM
-  static const int& merge_ln_in_a = dev_knob_ref("MERGE_LN_IN_A", 1);
+  // On ROUTE_A_LN the statistics of a norm are left by the epilogue of the GEMM that produced the tensor (profiles/r05_ln_in_a.txt), in ln_part.
   const float* first_part = e->ln_part;      // where the first block of the stage finds its LN1 partials: ln_part2 behind a merging linear in A_LN form
-  // dev: 1 (the tree) = the stages' output norms in the A path of the FPN laterals (run_neck_heads); 0 = layernorm kernels writing c[st]
-  static const int& out_ln_in_a = dev_knob_ref("OUT_LN_IN_A", 1);
-  e->out_ln_folded = e->lat_wln[0] && ln_in_a >= 2 && out_ln_in_a;
   e->last_batch = B;
   for (int st = 0; st < 4; ++st) {
     const StageGeom& g = e->st[st];
     const int T = B * g.H * g.W, C = g.C;
-    const bool merge_a = st < 3 && e->mg_wln[st] && ln_in_a >= 2 && merge_ln_in_a && !e->blocks[st].empty();
-    const bool final_stats = merge_a || e->out_ln_folded;      // the last block's FFN leaves the partials of the stage's final tensor in ln_out[st]
+    const size_t nb = e->blocks[st].size();
+    const bool merge_a = st < 3 && e->merge_one_launch[st];
+    // the last block's FFN leaves the partials of the stage's final tensor in ln_out[st]: for the merging norm in the reduction linear, the output norm in the FPN lateral
+    const bool final_stats = merge_a || e->out_ln_folded;
     float* xalt = st < 3 ? e->tok[st + 1] : nullptr;
-    for (size_t b = 0; b < e->blocks[st].size(); ++b) {
+    for (size_t b = 0; b < nb; ++b) {
       const BlockW& w = e->blocks[st][b];
       const int sh = (int)(b & 1);
+      float* last_stats = final_stats && b + 1 == nb ? e->ln_out[st] : nullptr;
       // x += proj(attn(LN1(x)))      (mmdet swin.py:356-363)
-      static const int& fused_mlp = dev_knob_ref("FUSED_MLP", 1);
-      static const int& fused_proj = dev_knob_ref("FUSED_PROJ", 1);
-      const bool mlp1 = w.mlp_stream && fused_mlp, proj1 = mlp1 && w.proj_stream && fused_proj;
-      // Where the projection rides in front of the fused FFN kernel (stage 1, round 4) the attention kernel writes its rows in TOKEN
-      // order (window row -> token map) instead of the compact window order the projection GEMM scatters from
-      // (ln_in_a >= 2: the LN1 statistics were left by the epilogue of the GEMM that produced x -- fc2, or the patch merging)
-      RUN(run_attn_front(e, g, w, B, sh, x, e->xw, e->qkv, e->att, proj1 ? g.map[sh] : g.cidx[sh], ln_in_a != 0,
-                         ln_in_a >= 2 ? (b == 0 ? first_part : e->ln_part) : nullptr, e->ln_part, nullptr, e->cfg.matrix_pipe != NUHTC_PIPE_FP32, s));
+      // ROUTE_FUSED: the projection rides in front of the fused FFN kernel, and the attention kernel writes its rows in TOKEN order (window
+      // row -> token map) instead of the compact window order the projection GEMM scatters from
+      RUN(run_attn_front(e, g, w, B, sh, x, e->xw, e->qkv, e->att, w.route == ROUTE_FUSED ? g.map[sh] : g.cidx[sh], b == 0 ? first_part : e->ln_part, nullptr, nullptr, s));
       if (e->debug_tokens) {
         auto it = e->bufs.find("att_s" + std::to_string(st) + "b" + std::to_string(b));
         if (it != e->bufs.end()) hipMemcpyAsync(it->second.ptr, e->att, (size_t)T * C * sizeof(float), hipMemcpyDeviceToDevice, s);
       }
       // x += W2·gelu(W1·LN2(x))      (swin.py:365-367, mmcv FFN)
-      if (!proj1) {
+      if (w.route == ROUTE_FUSED) {      // one kernel: attention projection + residual, LN2, both linears, GELU and the residual (mlp.hip)
+        RUN(launch_swin_mlp(x, x, w.n2g, w.n2b, w.mlp_stream, w.f1_b, w.f2_b, T, C, s, e->att, w.proj_stream, w.proj_b, last_stats));
+      } else {
+        const bool ln_a = w.route == ROUTE_A_LN;
         GemmParams p = gp(e->att, w.proj_w, w.proj_b, x, T, C, C);
         p.store = ST_ROWMAP; p.row_map = g.ctok[sh]; p.res = x; p.ldr = C;
-        if (w.f1_wln && ln_in_a >= 2) p.stats_out = e->ln_part;      // LN2 rides in fc1: its statistics leave with the rows
+        if (ln_a) p.stats_out = e->ln_part;      // LN2 rides in fc1: its statistics leave with the rows
         RUN(linear(p));
-      }
-      if (mlp1) {      // one kernel: [attention projection + residual,] LN2, both linears, GELU and the residual (mlp.hip)
-        RUN(launch_swin_mlp(x, x, w.n2g, w.n2b, w.mlp_stream, w.f1_b, w.f2_b, T, C, s, proj1 ? e->att : nullptr, w.proj_stream, w.proj_b,
-                            final_stats && b + 1 == e->blocks[st].size() ? e->ln_out[st] : nullptr));      // the merging / output norm's partials leave with the last block's rows
-      } else {
-      if (w.f1_wln && ln_in_a) {
-        const bool epi = ln_in_a >= 2;
-        if (!epi) RUN(launch_ln_stats(x, e->ln_part, T, C, s));
-        GemmParams p = gp(x, w.f1_wln, w.f1_bln, e->hid, T, 4 * C, C);
-        p.amode = A_LN; p.ln_part = e->ln_part; p.ln_nparts = epi ? C / 96 : 1;
+        if (ln_a) {
+          p = gp(x, w.f1_wln, w.f1_bln, e->hid, T, 4 * C, C);
+          p.amode = A_LN; p.ln_part = e->ln_part; p.ln_nparts = C / 96;
+        } else {
+          RUN(launch_layernorm(x, nullptr, w.n2g, w.n2b, e->xw, T, C, s));
+          p = gp(e->xw, w.f1_w, w.f1_b, e->hid, T, 4 * C, C);
+        }
         p.act = ACT_GELU;
         RUN(linear(p));
-      } else {
-      RUN(launch_layernorm(x, nullptr, w.n2g, w.n2b, e->xw, T, C, s));
-      {
-        GemmParams p = gp(e->xw, w.f1_w, w.f1_b, e->hid, T, 4 * C, C);
-        p.act = ACT_GELU;
-        RUN(linear(p));
-      }
-      }
-      {
-        GemmParams p = gp(e->hid, w.f2_w, w.f2_b, x, T, C, 4 * C);
+        p = gp(e->hid, w.f2_w, w.f2_b, x, T, C, 4 * C);
         p.res = x; p.ldr = C;
-        if (ln_in_a >= 2 && b + 1 < e->blocks[st].size() && e->blocks[st][b + 1].qkv_wln) p.stats_out = e->ln_part;   // LN1 of the next block rides in its QKV linear
-        if (final_stats && b + 1 == e->blocks[st].size()) p.stats_out = e->ln_out[st];                                   // ... the merging norm in the reduction linear, the output norm in the FPN lateral
+        p.stats_out = b + 1 < nb ? (ln_a ? e->ln_part : nullptr) : last_stats;      // LN1 of the next block rides in its QKV linear
         RUN(linear(p));
-      }
       }
       if (e->debug_tokens) {
         auto it = e->bufs.find("tok_s" + std::to_string(st) + "b" + std::to_string(b));
         if (it != e->bufs.end()) hipMemcpyAsync(it->second.ptr, x, (size_t)T * C * sizeof(float), hipMemcpyDeviceToDevice, s);
       }
     }
-    if (!e->out_ln_folded) RUN(launch_layernorm(x, nullptr, e->on_g[st], e->on_b[st], e->c[st], T, C, s));   // swin.py:756-762 (tokens == NHWC); else: in the lateral's A path
+    // swin.py:756-762 (tokens == NHWC) on the fp32 pipe; else the output norm runs in the lateral's A path (run_fpn, profiles/r05_out_ln.txt)
+    if (!e->out_ln_folded) RUN(launch_layernorm(x, nullptr, e->on_g[st], e->on_b[st], e->c[st], T, C, s));
     if (st < 3) {
-      const bool next_ln = ln_in_a >= 2 && !e->blocks[st + 1].empty() && e->blocks[st + 1][0].qkv_wln;   // LN1 of the next stage's first block rides in its QKV linear
+      const bool next_ln = e->blocks[st + 1][0].route == ROUTE_A_LN;   // LN1 of the next stage's first block rides in its QKV linear
       if (merge_a) {     // transformer.py:363-385 in one launch: row m = LayerNorm of the 2 x 2 tokens at mg_src[m] (two runs of 2 C floats, W tokens apart)
         GemmParams p = gp(x, e->mg_wln[st], e->mg_bln[st], xalt, T / 4, 2 * C, 4 * C);
         p.lda = C; p.amode = A_LN; p.ln_part = e->ln_out[st]; p.ln_nparts = 4 * (C / 96); p.a_rows = e->mg_src[st]; p.seg_k = 2 * C; p.seg_rows = g.W;
         if (next_ln) p.stats_out = e->ln_part2;      // not ln_part: other workgroups of this launch are still reading it
         RUN(linear(p));
         first_part = e->ln_part2;
-      } else {
+      } else {           // fp32 pipe, or a map with an odd side: merge_ln_kernel + the plain reduction linear
         RUN(launch_merge_ln(x, e->mg_g[st], e->mg_b[st], e->xw, B, g.H, g.W, C, s));
         GemmParams p = gp(e->xw, e->mg_w[st], nullptr, xalt, T / 4, 2 * C, 4 * C);
         if (next_ln) p.stats_out = e->ln_part;
@@ -863,7 +839,7 @@ int run_neck_heads(nuhtc_engine* e, int B, hipStream_t s) {
   // Pointwise layers that follow a 3x3 convolution are computed in that convolution's epilogue on the split pipe (conv.hip,
   // Conv3Fuse): the semantic head's lateral 1x1 rides on the FPN output conv of its level, the RPN's cls + reg layer on the RPN
   // conv (whose output is then never stored), conv_logits + conv_embedding (+ x0 + sem) on the semantic head's last conv.
-  const bool fuse = e->rpn_hf && conv3_fuse_available();
+  const bool fuse = e->conv_fuse;
   RUN(run_fpn(e, B, s, fuse));
   // RPN head (mmdet/models/dense_heads/rpn_head.py:62-68).  The RPN branch (conv + 1x1 heads here, proposal selection and
   // NMS in run_roi_path) and the semantic branch below both depend only on the FPN maps: the RPN branch runs on the side
@@ -874,23 +850,17 @@ int run_neck_heads(nuhtc_engine* e, int B, hipStream_t s) {
     FAIL(e, NUHTC_E_HIP, "side-stream fork failed");
   // the RPN head shares its weights across the levels (rpn_head.py:62-68 runs forward_single per level with the same modules): the four
   // maps go through ONE launch of the fused conv + cls/reg kernel -- the tiles of levels 1-3 (a third of level 0's) fill the tail of
-  // level 0's persistent grid instead of three launches of 32-512 tiles on 256 CUs (dev knob RPN_ONE_LAUNCH=0: one launch per level)
-  static const int& rpn_one = dev_knob_ref("RPN_ONE_LAUNCH", 1);
-  if (fuse && rpn_one) {
+  // level 0's persistent grid instead of three launches of 32-512 tiles on 256 CUs (profiles/r06_rpn_one_launch_ab.txt)
+  if (fuse) {
     Conv3Fuse f = pointwise(32, e->rpn_hf, e->rpn_hb, e->rpn[0], ACT_NONE, 0);
     f.n_more = 3;
     for (int i = 1; i < 4; ++i) { f.more_in[i - 1] = e->x[i]; f.more_out2[i - 1] = e->rpn[i]; f.more_H[i - 1] = e->st[i].H; f.more_W[i - 1] = e->st[i].W; }
     RUN(conv3x3(e, e->x[0], e->rpn_w, e->rpn_b, e->tmpR, B, e->st[0].H, e->st[0].W, ACT_RELU, nullptr, 1, s2, &f));
   }
-  for (int i = 0; i < 4 && !(fuse && rpn_one); ++i) {
+  for (int i = 0; i < 4 && !fuse; ++i) {      // fp32 pipe: conv, then the pointwise layer, per level
     const StageGeom& g = e->st[i];
-    if (fuse) {
-      const Conv3Fuse f = pointwise(32, e->rpn_hf, e->rpn_hb, e->rpn[i], ACT_NONE, 0);
-      RUN(conv3x3(e, e->x[i], e->rpn_w, e->rpn_b, e->tmpR, B, g.H, g.W, ACT_RELU, nullptr, 1, s2, &f));
-    } else {
-      RUN(conv3x3(e, e->x[i], e->rpn_w, e->rpn_b, e->tmpR, B, g.H, g.W, ACT_RELU, nullptr, 1, s2));
-      RUN(egemm(e, gp(e->tmpR, e->rpn_hw, e->rpn_hb, e->rpn[i], B * g.H * g.W, 32, 64), s2));
-    }
+    RUN(conv3x3(e, e->x[i], e->rpn_w, e->rpn_b, e->tmpR, B, g.H, g.W, ACT_RELU, nullptr, 1, s2));
+    RUN(egemm(e, gp(e->tmpR, e->rpn_hw, e->rpn_hb, e->rpn[i], B * g.H * g.W, 32, 64), s2));
   }
   if (s2 != s && hipEventRecord(e->ev_rpn, s2) != hipSuccess) FAIL(e, NUHTC_E_HIP, "hipEventRecord failed");   // RPN maps ready (side stream)
   // FusedSemanticHead (fused_semantic_head.py:97-111)
@@ -1073,7 +1043,7 @@ int nuhtc_get_buffer(nuhtc_engine* e, const char* name, void** ptr, int64_t* sha
   }
   auto it = e->bufs.find(name);
   if (it == e->bufs.end()) FAIL(e, NUHTC_E_NOTFOUND, std::string("unknown buffer: ") + name);
-  if (e->out_ln_folded && name[0] == 'c' && name[1] >= '0' && name[1] <= '3' && name[2] == 0) {
+  if (e->out_ln_folded && e->last_batch && name[0] == 'c' && name[1] >= '0' && name[1] <= '3' && name[2] == 0) {
     // the stage's output norm ran inside the FPN lateral: the tensor is computed now, from the stage's tokens, by the kernel that writes it on the
     // other path (parity tests read c0..c3)
     const int st = name[1] - '0';
@@ -1084,9 +1054,9 @@ int nuhtc_get_buffer(nuhtc_engine* e, const char* name, void** ptr, int64_t* sha
     if (rc) FAIL(e, rc, "layernorm for a requested c buffer failed");
     HIP_CHECK(e, hipDeviceSynchronize());
   }
-  if (e->img_stale && strcmp(name, "img") == 0 && e->in_tiles) {
-    // the pre-processing ran inside the patch embedding: the normalised image is computed now, by the kernel that writes it on the other path, from
-    // the tiles of the last call (which must still be what they were: parity tests read `img` right after the call)
+  if (strcmp(name, "img") == 0 && e->in_tiles) {
+    // the pre-processing runs inside the patch embedding: the normalised image is computed now, by preproc_kernel, from the tiles of the last call
+    // (which must still be what they were: parity tests read `img` right after the call)
     float mi[6];
     for (int i = 0; i < 3; ++i) { mi[i] = e->cfg.mean[i]; mi[3 + i] = (float)(1.0 / (double)e->cfg.std[i]); }
     HIP_CHECK(e, hipSetDevice(e->device));
@@ -1293,7 +1263,6 @@ int nuhtc_op_window_msa(nuhtc_engine* e, const nuhtc_wmsa_args* a, void* stream)
     FAIL(e, NUHTC_E_INVALID, "window_msa op: size out of range (window image >= 2^31 elements)");
   HIP_CHECK(e, hipSetDevice(e->device));
   hipStream_t s = (hipStream_t)stream;
-  const bool split = a->pipe == NUHTC_PIPE_BF16_SPLIT;
   StageGeom g{};
   stage_dims(g, H, W, C);
   const int T = B * H * W, sh = a->shifted;
@@ -1304,13 +1273,14 @@ int nuhtc_op_window_msa(nuhtc_engine* e, const nuhtc_wmsa_args* a, void* stream)
   w.n1g = sc.upload(a->ln_g, C); w.n1b = sc.upload(a->ln_b, C);
   w.qkv_w = sc.upload(a->qkv_w, (size_t)3 * C * C); w.qkv_b = sc.upload(a->qkv_b, (size_t)3 * C);
   w.relbT = sc.upload(pack_rel_bias(a->rel_table, g.nH));
+  w.route = block_route(a->pipe, C);
   const void* qkv_split = nullptr;
   int rc = 0;
-  if (split && lnqkv_supported(C)) {
+  if (w.route == ROUTE_FUSED) {
     std::vector<unsigned short> st;
     lnqkv_pack_stream(a->qkv_w, C, st);
     w.qkv_stream = sc.upload(st);
-  } else if (split && !mlp_supported(C)) {
+  } else if (w.route == ROUTE_A_LN) {
     std::vector<float> w2, b2;
     fold_ln(a->qkv_w, a->qkv_b, a->ln_g, a->ln_b, 3 * C, C, w2, b2);
     std::vector<unsigned short> sp;
@@ -1322,8 +1292,7 @@ int nuhtc_op_window_msa(nuhtc_engine* e, const nuhtc_wmsa_args* a, void* stream)
   float* xw = sc.alloc<float>((size_t)T * C * sizeof(float));
   float* st = sc.alloc<float>((size_t)T * 2 * sizeof(float));
   if (!ok || !sc.ok()) FAIL(e, NUHTC_E_HIP, "window_msa op: scratch upload failed");
-  rc = run_attn_front(e, g, w, B, sh, a->x, xw, qkv, a->out, a->out_order == NUHTC_ORDER_TOKEN ? g.map[sh] : g.cidx[sh], true, nullptr, st, qkv_split,
-                      split, s);
+  rc = run_attn_front(e, g, w, B, sh, a->x, xw, qkv, a->out, a->out_order == NUHTC_ORDER_TOKEN ? g.map[sh] : g.cidx[sh], nullptr, st, qkv_split, s);
   return op_finish(e, rc, s, "window_msa launch failed", "window_msa kernels failed");
 }
 

@@ -875,12 +875,6 @@ static void launch_split(const GemmParams& q, hipStream_t s) {
   } else hipLaunchKernelGGL((gemm_split_kernel<MT, NT, A_PLAIN>), grid, dim3(256), pad, s, q);
 }
 
-bool conv3_fuse_available() {
-  static const int& conv_halo = dev_knob_ref("CONV_HALO", 1);
-  static const int& conv_fuse = dev_knob_ref("CONV_FUSE", 1);
-  return conv_halo && conv_fuse;
-}
-
 int launch_gemm(const GemmParams& p, hipStream_t s) {
   if (p.M <= 0) return 0;
   if (p.K % 32 != 0 || p.N % 32 != 0) return NUHTC_E_INVALID;
@@ -924,9 +918,10 @@ int launch_gemm(const GemmParams& p, hipStream_t s) {
     q.zeros = zero_page();
     if (!q.zeros) return NUHTC_E_HIP;
   }
-  static const int& conv_halo = dev_knob_ref("CONV_HALO", 1);
-  const bool halo = conv_halo && conv3_split_supported(q);      // 3x3 convolutions: halo tile in LDS, split once (conv.hip)
-  if (p.fuse && !halo) return NUHTC_E_INVALID;                  // a fused pointwise layer exists on that path only (the caller checks conv3_fuse_available)
+  // 3x3 convolutions: halo tile in LDS, split once (conv.hip); the others with a split weight (nuhtc_op_conv3 with an activation that kernel
+  // does not have) stay on gemm_split_kernel<.., A_CONV3>
+  const bool halo = conv3_split_supported(q);
+  if (p.fuse && !halo) return NUHTC_E_INVALID;                  // a fused pointwise layer exists on that path only
   const double nb = p.batch > 0 ? p.batch : 1;
   const char* tag = "gemm";
   if (prof_enabled()) {   // per-shape tags, e.g. "gemm_kernel<3>|N288|K96" (strings live for the process lifetime)

@@ -1,7 +1,7 @@
 // Swin-T front-end and per-block non-GEMM kernels (gfx950, wave64).
 //   preproc       : uint8 x2 bilinear resize (cv2 INTER_LINEAR fixed point) + channel swap + normalise
 //                   (mmdet/datasets/pipelines/transforms.py:207-236,686-700)
-//   patch_embed   : conv4x4 s4 (3->96) + LayerNorm(96)          (mmdet/models/utils/transformer.py:236-257)
+//   patch_embed   : preproc + conv4x4 s4 (3->96) + LayerNorm(96) from the uint8 tiles (mmdet/models/utils/transformer.py:236-257)
 //   layernorm     : LN with optional row gather (LN1 + pad + cyclic roll + window partition in one pass;
 //                   padding rows are zeros *after* the norm)    (mmdet/models/backbones/swin.py:182-226,360)
 //   merge_ln      : PatchMerging 2x2 gather + LN(4C)            (transformer.py:363-385)
@@ -84,61 +84,10 @@ int launch_preproc(const uint8_t* tiles, float* img, int B, int th, int tw, int 
 
 // ----------------------------------------------------------------------------- patch embed
 // w: [48][96] k-major with k = (kh*4+kw)*3 + c (NHWC pixel order); 32 tokens per block, 8 lanes x 12 channels per token
-__global__ __launch_bounds__(256) void patch_embed_kernel(const float* __restrict__ img, const float* __restrict__ w,
-                                                          const float* __restrict__ bias, const float* __restrict__ g,
-                                                          const float* __restrict__ beta, float* __restrict__ tok, int nTok,
-                                                          int Hn, int Wn) {
-  __shared__ float wl[48 * 96];
-  __shared__ float pl[32 * 49];
-  const int tid = threadIdx.x;
-  for (int e = tid; e < 48 * 96; e += 256) wl[e] = w[e];
-  const int Wt = Wn >> 2, Ht = Hn >> 2;
-  const int t0 = blockIdx.x * 32;
-  for (int e = tid; e < 32 * 48; e += 256) {
-    int tl = e / 48, k = e - tl * 48;
-    int t = t0 + tl;
-    float v = 0.f;
-    if (t < nTok) {
-      int tx = t % Wt, ty = (t / Wt) % Ht, b = t / (Wt * Ht);
-      int kh = k / 12, r = k - kh * 12;   // r = kw*3 + c
-      v = img[(((long long)b * Hn + 4 * ty + kh) * Wn + 4 * tx) * 3 + r];
-    }
-    pl[tl * 49 + k] = v;
-  }
-  __syncthreads();
-  const int tl = tid >> 3, cg = tid & 7;
-  float acc[12];
-#pragma unroll
-  for (int j = 0; j < 12; ++j) acc[j] = 0.f;
-  for (int k = 0; k < 48; ++k) {
-    float x = pl[tl * 49 + k];
-#pragma unroll
-    for (int j = 0; j < 12; ++j) acc[j] = fmaf(x, wl[k * 96 + cg + 8 * j], acc[j]);
-  }
-  float sum = 0.f;
-#pragma unroll
-  for (int j = 0; j < 12; ++j) { acc[j] += bias[cg + 8 * j]; sum += acc[j]; }
-  sum += __shfl_xor(sum, 1); sum += __shfl_xor(sum, 2); sum += __shfl_xor(sum, 4);
-  const float mean = sum * (1.0f / 96.0f);
-  float var = 0.f;
-#pragma unroll
-  for (int j = 0; j < 12; ++j) { float d = acc[j] - mean; var = fmaf(d, d, var); }
-  var += __shfl_xor(var, 1); var += __shfl_xor(var, 2); var += __shfl_xor(var, 4);
-  const float rstd = 1.0f / sqrtf(var * (1.0f / 96.0f) + 1e-5f);
-  const int t = t0 + tl;
-  if (t < nTok) {
-#pragma unroll
-    for (int j = 0; j < 12; ++j) {
-      int c = cg + 8 * j;
-      tok[(long long)t * 96 + c] = (acc[j] - mean) * rstd * g[c] + beta[c];
-    }
-  }
-}
-
-// The same with the pre-processing inside (round 5): the 48 inputs of a token are computed from the uint8 tile on the way into LDS -- cv2's 8-bit
-// linear resize from the per-axis tables, Normalize, zero Pad: the arithmetic of preproc_kernel, element for element, so the tokens are the
-// same bits -- and the normalised image (12 bytes per network pixel written and read back) never exists.  Every image pixel belongs to exactly
-// one 4 x 4 patch: nothing is computed twice.
+// The pre-processing runs inside: the 48 inputs of a token are computed from the uint8 tile on the way into LDS -- cv2's 8-bit linear resize from
+// the per-axis tables, Normalize, zero Pad: the arithmetic of preproc_kernel, element for element, so `img` computed on request by that kernel is
+// what the tokens were made from -- and the normalised image (12 bytes per network pixel written and read back) never exists.  Every image pixel
+// belongs to exactly one 4 x 4 patch: nothing is computed twice.
 __global__ __launch_bounds__(256) void patch_embed_tiles_kernel(const uint8_t* __restrict__ tiles, int th, int tw, int Hv, int Wv,
                                                                 const int4* __restrict__ xtab, const int4* __restrict__ ytab, int swap, NormConst nc,
                                                                 const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ g,
@@ -208,14 +157,6 @@ int launch_patch_embed_tiles(const uint8_t* tiles, int B, int th, int tw, int Hn
   int nTok = B * (Hn / 4) * (Wn / 4);
   hipLaunchKernelGGL(patch_embed_tiles_kernel, dim3(cdiv(nTok, 32)), dim3(256), 0, s, tiles, th, tw, Hv, Wv, (const int4*)xtab, (const int4*)ytab, swap, nc,
                      w, b, g, beta, tok, nTok, Hn, Wn);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
-}
-
-int launch_patch_embed(const float* img, const float* w, const float* b, const float* g, const float* beta, float* tok, int B,
-                       int Hn, int Wn, hipStream_t s) {
-  ProfScope ps("patch_embed", 2.0 * 48 * 96 * B * (Hn / 4) * (Wn / 4), 4.0 * B * Hn * Wn * 3 + 4.0 * 96 * B * (Hn / 4) * (Wn / 4), s);
-  int nTok = B * (Hn / 4) * (Wn / 4);
-  hipLaunchKernelGGL(patch_embed_kernel, dim3(cdiv(nTok, 32)), dim3(256), 0, s, img, w, b, g, beta, tok, nTok, Hn, Wn);
   return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
 }
 
@@ -365,7 +306,7 @@ int launch_layernorm_windows(const float* x, const int* src_map, const int* dst_
 
 // ---- LayerNorm statistics only (round 5): the norms of Swin stages 2-4 ride in the A path of the linear that consumes them
 // (gemm.hip, A_LN).  In the engine the statistics are left by the epilogue of the GEMM that produced the tensor; this kernel is the
-// stand-alone form (nuhtc_op_ln_gemm, dev fallback LN_IN_A=1): it reads each row once and leaves 8 bytes -- the mean and the sum of
+// stand-alone form (nuhtc_op_ln_gemm, nuhtc_op_window_msa): it reads each row once and leaves 8 bytes -- the mean and the sum of
 // squared deviations, computed with the loads, the two passes and the summation order of layernorm_kernel.  One wave per row.
 template <int NV>
 __global__ __launch_bounds__(256) void ln_stats_kernel(const float* __restrict__ x, float* __restrict__ stats, int rows, int C) {
