@@ -360,6 +360,89 @@ typedef struct nuhtc_wmsa_args {
   int32_t shifted, pipe, out_order;
 } nuhtc_wmsa_args;
 int nuhtc_op_window_msa(nuhtc_engine* e, const nuhtc_wmsa_args* a, void* stream);
+/* The detection tail of nuhtc_infer, op by op, as test entry points (csrc/roi.hip: everything behind the RoI features that turns numbers into
+ * decisions).  Each fills the parameter block nuhtc_infer fills and calls the same launch function; integer arrays a kernel indexes with
+ * (*r_dev, roi_off / roi_cnt, det_off / det_counts) are read back and checked against the stated capacities first.  All pointers are device
+ * memory unless marked HOST.  Each synchronises `stream`.  NUHTC_E_INVALID: a null pointer, nc + 6 > 64 or nc + 2 > 16, max_keep /
+ * max_per_img > 2048, W % 32 != 0, a valid canvas outside H x W, B > 256, counts beyond the capacities.
+ * nuhtc_op_bbox_tail: h [cap][256] (the output of the two shared FCs) -> cls [cap][16] (nc + 2 used: NormedLinear, 20 * h / (|h| + 1e-6) against
+ *   the row-normalised fc_cls), reg [cap][4] (fc_reg) and, with `refine`, rois [cap][5] regressed in place (delta2bbox, stds, clipped to img_w x
+ *   img_h) for the rows below *r_dev; rows from *r_dev on are not written.  cls_w [nc+2][256], cls_b [nc+2], reg_w [4][256], reg_b [4] are HOST
+ *   arrays in the checkpoint's layout, packed as nuhtc_finalize packs them. */
+typedef struct nuhtc_bbox_tail_args {
+  const float* h;
+  const float* cls_w;
+  const float* cls_b;
+  const float* reg_w;
+  const float* reg_b;
+  int32_t nc, cap, refine;
+  float stds[4];
+  float img_w, img_h;
+  const int32_t* r_dev;
+  float* rois;
+  float* cls;
+  float* reg;
+} nuhtc_bbox_tail_args;
+int nuhtc_op_bbox_tail(nuhtc_engine* e, const nuhtc_bbox_tail_args* a, void* stream);
+/* nuhtc_op_det_post: mean of the three stages' logits, Seesaw activation, delta2bbox / scale, score > score_thr -> the candidates of tile b
+ *   (RoIs roi_off[b] .. + roi_cnt[b] of rois [total][5], cls0..2 [total][16], reg2 [total][4]) in (roi, class) order: cand_count [B],
+ *   cand_scores / cand_ids [B][cap], cand_boxes [B][cap][4] (cap: a multiple of 64 up to 16384; candidates beyond it are dropped) -> multiclass
+ *   NMS (mmcv batched_nms: class offset max(boxes of the tile) + 1, IoU > nms_iou) -> dets [B][max_per_img][5], labels [B][max_per_img],
+ *   counts [B] (clamped to `limit`), mask_rois [sum counts][5] (tile, box * scale; room for B * max_per_img rows), det_off [B], det_total [1].
+ *   Needs a finalized engine. */
+typedef struct nuhtc_det_post_args {
+  const float* rois;
+  const float* cls0;
+  const float* cls1;
+  const float* cls2;
+  const float* reg2;
+  const int32_t* roi_off;
+  const int32_t* roi_cnt;
+  int32_t B, nc, total, cap;
+  float stds[4];
+  float img_w, img_h, scale, score_thr, nms_iou;
+  int32_t max_per_img, limit;
+  float* dets;
+  int32_t* labels;
+  int32_t* counts;
+  float* mask_rois;
+  int32_t* det_off;
+  int32_t* det_total;
+  int32_t* cand_count;
+  float* cand_scores;
+  int32_t* cand_ids;
+  float* cand_boxes;
+} nuhtc_det_post_args;
+int nuhtc_op_det_post(nuhtc_engine* e, const nuhtc_det_post_args* a, void* stream);
+/* nuhtc_op_paste: prob [D][28][28] and mask_rois [D][5] (network pixels; detection j of tile b is row det_off[b] + j, j < det_counts[b]) ->
+ *   masks [B][max_keep][H][W/32] (bit x & 31 of word x >> 5: bilinear sample of the box's probability map >= thr, inside the box's integer hull
+ *   and the valid canvas vH x vW) and areas [B][max_keep] (set bits).  Slots from det_counts[b] on are not written. */
+typedef struct nuhtc_paste_args {
+  const float* prob;
+  const float* mask_rois;
+  const int32_t* det_off;
+  const int32_t* det_counts;
+  int32_t B, D, max_keep, H, W, vH, vW;
+  float scale, thr;
+  uint32_t* masks;
+  int32_t* areas;
+} nuhtc_paste_args;
+int nuhtc_op_paste(nuhtc_engine* e, const nuhtc_paste_args* a, void* stream);
+/* nuhtc_op_tile_post: dets [B][max_keep][5], labels, areas [B][max_keep], masks as above (each inside the integer hull of its box: the pair test
+ *   skips masks whose hulls do not meet) -> keep [B][max_keep] uint8 for the slots below det_counts[b]: margin / min_area filter, then greedy
+ *   mask-NMS at IoU > thr (rounded to the double the reference compares with) in the order score descending, ties by class-major position
+ *   descending.  Slots from det_counts[b] on are not written. */
+typedef struct nuhtc_tile_post_args {
+  const float* dets;
+  const int32_t* labels;
+  const int32_t* areas;
+  const int32_t* det_counts;
+  const uint32_t* masks;
+  uint8_t* keep;
+  int32_t B, max_keep, H, W, vH, vW, margin, min_area;
+  float thr;
+} nuhtc_tile_post_args;
+int nuhtc_op_tile_post(nuhtc_engine* e, const nuhtc_tile_post_args* a, void* stream);
 
 /* A HIP stream owned by the engine (valid after nuhtc_finalize) that a caller MAY run this engine on,
  * and should when it keeps several engines busy at once or raises GPU_MAX_HW_QUEUES above the runtime's default of 4: the stream

@@ -52,6 +52,26 @@ struct RoiWs {
   unsigned char* keep_own;
 };
 
+// fc_cls [nc+2][256] / fc_reg [4][256] of one bbox head -> the [nc+6][256] weight and [nc+6] bias bbox_tail_kernel reads (also nuhtc_op_bbox_tail)
+static void pack_bbox_head(const float* wc, const float* bc, const float* wr, const float* br, int nc, std::vector<float>& hw, std::vector<float>& hb) {
+  // NormedLinear: weight_ = W / (||W||_row + 1e-6)   (normed_predictor.py:34-35)
+  hw.assign((size_t)(nc + 6) * 256, 0.f);
+  hb.assign(nc + 6, 0.f);
+  for (int n = 0; n < nc + 2; ++n) {
+    float ss = 0.f;
+    for (int k2 = 0; k2 < 256; ++k2) ss += wc[n * 256 + k2] * wc[n * 256 + k2];
+    float den = sqrtf(ss) + 1e-6f;
+    for (int k2 = 0; k2 < 256; ++k2) hw[n * 256 + k2] = wc[n * 256 + k2] / den;
+    hb[n] = bc[n];
+  }
+  for (int n = 0; n < 4; ++n) {
+    for (int k2 = 0; k2 < 256; ++k2) hw[(nc + 2 + n) * 256 + k2] = wr[n * 256 + k2];
+    hb[nc + 2 + n] = br[n];
+  }
+}
+// the reference compares the mask IoU against the Python double 0.05 (tools/infer_wsi.py:60-84), not against its float image
+static double mask_nms_thr(float thr) { return std::round((double)thr * 1e6) / 1e6; }
+
 int finalize_roi(nuhtc_engine* e) {
   const int nc = e->cfg.num_classes;
   int rc;
@@ -66,19 +86,8 @@ int finalize_roi(nuhtc_engine* e) {
     for (int n = 0; n < 256; ++n)
       for (int c = 0; c < 64; ++c)
         for (int bin = 0; bin < 49; ++bin) w1p[(size_t)n * 3136 + bin * 64 + c] = w1->data[(size_t)n * 3136 + c * 49 + bin];
-    // NormedLinear: weight_ = W / (||W||_row + 1e-6)   (normed_predictor.py:34-35)
-    std::vector<float> hw((size_t)(nc + 6) * 256), hb(nc + 6);
-    for (int n = 0; n < nc + 2; ++n) {
-      float ss = 0.f;
-      for (int k2 = 0; k2 < 256; ++k2) ss += wc->data[n * 256 + k2] * wc->data[n * 256 + k2];
-      float den = sqrtf(ss) + 1e-6f;
-      for (int k2 = 0; k2 < 256; ++k2) hw[n * 256 + k2] = wc->data[n * 256 + k2] / den;
-      hb[n] = bc->data[n];
-    }
-    for (int n = 0; n < 4; ++n) {
-      for (int k2 = 0; k2 < 256; ++k2) hw[(nc + 2 + n) * 256 + k2] = wr->data[n * 256 + k2];
-      hb[nc + 2 + n] = br->data[n];
-    }
+    std::vector<float> hw, hb;
+    pack_bbox_head(wc->data.data(), bc->data.data(), wr->data.data(), br->data.data(), nc, hw, hb);
     if ((rc = upload_gemm_weight(e, &e->fc1_w[k], w1p, 256, 3136)) || (rc = upload(e, &e->fc1_b[k], b1->data)) || (rc = upload_gemm_weight(e, &e->fc2_w[k], w2->data, 256, 256)) ||
         (rc = upload(e, &e->fc2_b[k], b2->data)) || (rc = upload(e, &e->head_w[k], hw)) || (rc = upload(e, &e->head_b[k], hb)))
       return rc;
@@ -150,7 +159,7 @@ int alloc_roi_workspace(nuhtc_engine* e) {
   if ((rc = ws(e, &w->rois, "rois", {T, 5}, 0)) || (rc = ws(e, &w->roi_off, "roi_off", {B}, 1)) || (rc = ws(e, &w->roi_cnt, "roi_counts", {B}, 1)) ||
       (rc = ws(e, &w->roi_total, "roi_total", {1}, 1)) || (rc = ws(e, &w->G2, "G2", {B, e->st[2].H * e->st[2].W, 64}, 0)) ||
       (rc = ws(e, &w->G3, "G3", {B, e->st[3].H * e->st[3].W, 64}, 0)) || (rc = ws(e, &w->feats, "bbox_feats", {T, 49, 64}, 0)) ||
-      (rc = ws(e, &w->h1, nullptr, {T, 256}, 0)) || (rc = ws(e, &w->h2, nullptr, {T, 256}, 0)) ||
+      (rc = ws(e, &w->h1, nullptr, {T, 256}, 0)) || (rc = ws(e, &w->h2, "h2", {T, 256}, 0)) ||
       (rc = ws(e, &w->ap_inv, nullptr, {B, e->st[2].H * e->st[2].W}, 0)) ||
       (rc = ws(e, &w->ap_S, nullptr, {B, (int64_t)e->st[2].H * e->st[2].W, (int64_t)e->st[2].H * e->st[2].W}, 0)) ||
       (rc = ws(e, &w->ap_Ft, nullptr, {B, 64, e->st[2].H * e->st[2].W}, 0)) ||
@@ -330,7 +339,7 @@ int run_roi_path(nuhtc_engine* e, int B, const float* rois_fixed, int n_rois, in
     TilePostParams tp;
     tp.dets = out->boxes; tp.labels = out->labels; tp.areas = out->areas; tp.det_counts = out->counts; tp.masks = out->masks; tp.keep = out->keep;
     tp.max_keep = c.max_per_img; tp.H = c.tile_h; tp.W = c.tile_w; tp.vH = e->vh; tp.vW = e->vw; tp.margin = c.margin; tp.min_area = c.min_area;
-    tp.thr = std::round((double)c.mask_nms_thr * 1e6) / 1e6;   // the reference compares against the Python double 0.05
+    tp.thr = mask_nms_thr(c.mask_nms_thr);
     RUN(launch_tile_post(tp, B, s));
   }
   return 0;
@@ -401,4 +410,113 @@ int nuhtc_op_cc_proposals(nuhtc_engine* e, const uint8_t* mask, int B, int H, in
     rc = NUHTC_E_HIP;
   if (!rc) rc = launch_cc_from_mask(cp, B, open != 0, s);
   return op_finish(e, rc, s, "cc_proposals launch failed", "cc_proposals kernel failed");
+}
+
+// ---- the detection tail, op by op: each fills the parameter block run_roi_path fills and calls the same launch_* function
+// small device int arrays the ops check on the host before a kernel indexes with them (after the stream's earlier work)
+static bool read_ints(const int32_t* dev, int n, std::vector<int>& out, hipStream_t s) {
+  out.resize(n);
+  return hipStreamSynchronize(s) == hipSuccess && hipMemcpy(out.data(), dev, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
+}
+
+int nuhtc_op_bbox_tail(nuhtc_engine* e, const nuhtc_bbox_tail_args* a, void* stream) {
+  if (!e || !a || !a->h || !a->cls_w || !a->cls_b || !a->reg_w || !a->reg_b || !a->r_dev || !a->rois || !a->cls || !a->reg) return NUHTC_E_INVALID;
+  if (a->nc < 1 || a->nc + 6 > 64 || a->nc + 2 > 16) FAIL(e, NUHTC_E_INVALID, "bbox_tail op: nc out of range (nc + 2 <= 16 columns of cls)");
+  if (a->cap < 1) FAIL(e, NUHTC_E_INVALID, "bbox_tail op: cap out of range");
+  HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> r;
+  if (!read_ints(a->r_dev, 1, r, s)) FAIL(e, NUHTC_E_HIP, "bbox_tail op: reading r_dev failed");
+  if (r[0] < 0 || r[0] > a->cap) FAIL(e, NUHTC_E_INVALID, "bbox_tail op: *r_dev exceeds cap");
+  std::vector<float> hw, hb;
+  pack_bbox_head(a->cls_w, a->cls_b, a->reg_w, a->reg_b, a->nc, hw, hb);
+  DevScratch sc;
+  BboxTailParams tp;
+  tp.h = a->h; tp.w = sc.upload(hw); tp.b = sc.upload(hb); tp.nc = a->nc; tp.r_dev = a->r_dev; tp.cls = a->cls; tp.reg = a->reg;
+  tp.refine = a->refine != 0; tp.rois = a->rois;
+  for (int j = 0; j < 4; ++j) tp.stds[j] = a->stds[j];
+  tp.img_w = a->img_w; tp.img_h = a->img_h;
+  if (!sc.ok()) FAIL(e, NUHTC_E_HIP, "bbox_tail op: scratch allocation failed");
+  const int rc = launch_bbox_tail(tp, a->cap, s);
+  return op_finish(e, rc, s, "bbox_tail launch failed", "bbox_tail kernel failed");
+}
+
+int nuhtc_op_det_post(nuhtc_engine* e, const nuhtc_det_post_args* a, void* stream) {
+  if (!e || !a || !a->rois || !a->cls0 || !a->cls1 || !a->cls2 || !a->reg2 || !a->roi_off || !a->roi_cnt || !a->dets || !a->labels || !a->counts ||
+      !a->mask_rois || !a->det_off || !a->det_total || !a->cand_count || !a->cand_scores || !a->cand_ids || !a->cand_boxes)
+    return NUHTC_E_INVALID;
+  if (!e->finalized) FAIL(e, NUHTC_E_STATE, "nuhtc_op_det_post before finalize");
+  if (a->nc < 1 || a->nc + 2 > 16) FAIL(e, NUHTC_E_INVALID, "det_post op: nc out of range (nc + 2 <= 16)");
+  if (a->B < 1 || a->B > 256) FAIL(e, NUHTC_E_INVALID, "det_post op: B out of range (1..256)");
+  if (a->cap < 64 || a->cap % 64 || a->cap > NMS_MAX_CAP) FAIL(e, NUHTC_E_INVALID, "det_post op: cap must be a multiple of 64 up to NMS_MAX_CAP");
+  if (a->max_per_img < 1 || a->max_per_img > 2048 || a->limit < 0 || a->total < 0) FAIL(e, NUHTC_E_INVALID, "det_post op: max_per_img / limit / total out of range");
+  HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int B = a->B;
+  std::vector<int> off, cnt;
+  if (!read_ints(a->roi_off, B, off, s) || !read_ints(a->roi_cnt, B, cnt, s)) FAIL(e, NUHTC_E_HIP, "det_post op: reading roi_off / roi_cnt failed");
+  for (int b = 0; b < B; ++b)
+    if (off[b] < 0 || cnt[b] < 0 || (long long)off[b] + cnt[b] > a->total) FAIL(e, NUHTC_E_INVALID, "det_post op: roi_off + roi_cnt exceeds total");
+  DevScratch sc;
+  DetCandParams dp;
+  dp.rois = a->rois; dp.cls0 = a->cls0; dp.cls1 = a->cls1; dp.cls2 = a->cls2; dp.reg2 = a->reg2; dp.roi_off = a->roi_off; dp.roi_cnt = a->roi_cnt;
+  dp.nc = a->nc;
+  for (int j = 0; j < 4; ++j) dp.stds[j] = a->stds[j];
+  dp.img_w = a->img_w; dp.img_h = a->img_h; dp.scale = a->scale; dp.score_thr = a->score_thr;
+  dp.cand_boxes = a->cand_boxes; dp.cand_scores = a->cand_scores; dp.cand_ids = a->cand_ids; dp.cand_count = a->cand_count; dp.cap = a->cap;
+  NmsParams np;
+  memset(&np, 0, sizeof(np));
+  np.boxes = a->cand_boxes; np.scores = a->cand_scores; np.ids = a->cand_ids; np.group_count = a->cand_count; np.n_groups = 1; np.slot = a->cap;
+  np.cap = a->cap; np.cap_pow2 = pow2_ge(a->cap); np.iou_thr = a->nms_iou; np.max_keep = a->max_per_img;
+  np.sorted_boxes = sc.alloc<float>((size_t)B * a->cap * 16); np.sorted_src = sc.alloc<int>((size_t)B * a->cap * 4); np.n_total = sc.alloc<int>((size_t)B * 4);
+  np.mask = sc.alloc<unsigned long long>((size_t)B * a->cap * (a->cap / 64) * 8);
+  np.out_dets = a->dets; np.out_src = sc.alloc<int>((size_t)B * a->max_per_img * 4); np.out_counts = a->counts;
+  DetFinishParams df;
+  df.B = B; df.max_keep = a->max_per_img; df.dets = a->dets; df.keep_src = np.out_src; df.cand_ids = a->cand_ids; df.det_counts = a->counts;
+  df.labels = a->labels; df.mask_rois = a->mask_rois; df.det_off = a->det_off; df.det_total = a->det_total; df.scale = a->scale;
+  df.limit = a->limit;
+  if (!sc.ok()) FAIL(e, NUHTC_E_HIP, "det_post op: scratch allocation failed");
+  int rc = launch_det_candidates(dp, B, s);
+  if (!rc) rc = launch_nms(np, B, s);
+  if (!rc) rc = launch_det_finish(df, s);
+  return op_finish(e, rc, s, "det_post launch failed", "det_post kernel failed");
+}
+
+int nuhtc_op_paste(nuhtc_engine* e, const nuhtc_paste_args* a, void* stream) {
+  if (!e || !a || !a->prob || !a->mask_rois || !a->det_off || !a->det_counts || !a->masks || !a->areas) return NUHTC_E_INVALID;
+  if (a->B < 1 || a->B > 256) FAIL(e, NUHTC_E_INVALID, "paste op: B out of range (1..256)");
+  if (a->max_keep < 1 || a->max_keep > 2048) FAIL(e, NUHTC_E_INVALID, "paste op: max_keep out of range (1..2048)");
+  if (a->H < 1 || a->W < 32 || a->W % 32 || a->vH < 0 || a->vH > a->H || a->vW < 0 || a->vW > a->W || a->D < 0)
+    FAIL(e, NUHTC_E_INVALID, "paste op: W must be a multiple of 32 and the valid canvas inside H x W");
+  HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> off, cnt;
+  if (!read_ints(a->det_off, a->B, off, s) || !read_ints(a->det_counts, a->B, cnt, s)) FAIL(e, NUHTC_E_HIP, "paste op: reading det_off / det_counts failed");
+  for (int b = 0; b < a->B; ++b)
+    if (off[b] < 0 || cnt[b] < 0 || cnt[b] > a->max_keep || (long long)off[b] + cnt[b] > a->D) FAIL(e, NUHTC_E_INVALID, "paste op: det_off / det_counts exceed D or max_keep");
+  PasteParams pp;
+  pp.prob = a->prob; pp.mask_rois = a->mask_rois; pp.det_off = a->det_off; pp.det_counts = a->det_counts; pp.max_keep = a->max_keep;
+  pp.H = a->H; pp.W = a->W; pp.vH = a->vH; pp.vW = a->vW; pp.scale = a->scale; pp.thr = a->thr; pp.masks = a->masks; pp.areas = a->areas;
+  const int rc = launch_paste(pp, a->B, s);
+  return op_finish(e, rc, s, "paste launch failed", "paste kernel failed");
+}
+
+int nuhtc_op_tile_post(nuhtc_engine* e, const nuhtc_tile_post_args* a, void* stream) {
+  if (!e || !a || !a->dets || !a->labels || !a->areas || !a->det_counts || !a->masks || !a->keep) return NUHTC_E_INVALID;
+  if (a->B < 1 || a->B > 256) FAIL(e, NUHTC_E_INVALID, "tile_post op: B out of range (1..256)");
+  if (a->max_keep < 1 || a->max_keep > 2048) FAIL(e, NUHTC_E_INVALID, "tile_post op: max_keep out of range (1..2048)");
+  if (a->H < 1 || a->W < 32 || a->W % 32 || a->vH < 0 || a->vH > a->H || a->vW < 0 || a->vW > a->W)
+    FAIL(e, NUHTC_E_INVALID, "tile_post op: W must be a multiple of 32 and the valid canvas inside H x W");
+  HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> cnt;
+  if (!read_ints(a->det_counts, a->B, cnt, s)) FAIL(e, NUHTC_E_HIP, "tile_post op: reading det_counts failed");
+  for (int b = 0; b < a->B; ++b)
+    if (cnt[b] < 0 || cnt[b] > a->max_keep) FAIL(e, NUHTC_E_INVALID, "tile_post op: det_counts exceed max_keep");
+  TilePostParams tp;
+  tp.dets = a->dets; tp.labels = a->labels; tp.areas = a->areas; tp.det_counts = a->det_counts; tp.masks = a->masks; tp.keep = a->keep;
+  tp.max_keep = a->max_keep; tp.H = a->H; tp.W = a->W; tp.vH = a->vH; tp.vW = a->vW; tp.margin = a->margin; tp.min_area = a->min_area;
+  tp.thr = mask_nms_thr(a->thr);
+  const int rc = launch_tile_post(tp, a->B, s);
+  return op_finish(e, rc, s, "tile_post launch failed", "tile_post kernel failed");
 }

@@ -548,3 +548,79 @@ class Engine:
                          out_order=hip.ORDER_COMPACT if order == 'compact' else hip.ORDER_TOKEN)
         self._check(self.lib.nuhtc_op_window_msa(self.h, ctypes.byref(a), self._stream()))
         return out
+
+    # ------------------------------------------------------------------ the detection tail, op by op (csrc/roi.hip)
+    def _i32(self, v):
+        return v if isinstance(v, torch.Tensor) else torch.tensor(np.atleast_1d(np.asarray(v)), dtype=torch.int32, device=self.device)
+
+    def op_bbox_tail(self, h, cls_w, cls_b, reg_w, reg_b, rois, r, stds, img_hw, refine, cls=None, reg=None):
+        """The tail of one bbox head (nuhtc_op_bbox_tail): h (cap, 256) and rois (cap, 5) on the device, fc_cls / fc_reg weights and biases
+        anywhere (the checkpoint's layout), r: the device-side RoI count (int or device int32 (1,)).  Rows below r of cls (cap, 16: nc + 2
+        used) and reg (cap, 4) are written, and with `refine` rois is regressed IN PLACE.  Returns (cls, reg), allocated when not given."""
+        f = lambda t: np.ascontiguousarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, dtype=np.float32)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        cw, cb, rw, rb = f(cls_w), f(cls_b), f(reg_w), f(reg_b)
+        nc, cap = cw.shape[0] - 2, h.shape[0]
+        if cw.shape != (nc + 2, 256) or cb.shape != (nc + 2,) or rw.shape != (4, 256) or rb.shape != (4,):
+            raise ValueError('op_bbox_tail: fc_cls (nc + 2, 256) / (nc + 2,), fc_reg (4, 256) / (4,) expected')
+        if cls is None:
+            cls = torch.empty(cap, 16, dtype=torch.float32, device=self.device)
+        if reg is None:
+            reg = torch.empty(cap, 4, dtype=torch.float32, device=self.device)
+        r_dev = self._i32(r)
+        a = hip.BboxTailArgs(h=h.data_ptr(), cls_w=vp(cw), cls_b=vp(cb), reg_w=vp(rw), reg_b=vp(rb), nc=nc, cap=cap, refine=int(bool(refine)),
+                             stds=(ctypes.c_float * 4)(*[float(v) for v in stds]), img_w=float(img_hw[1]), img_h=float(img_hw[0]),
+                             r_dev=r_dev.data_ptr(), rois=rois.data_ptr(), cls=cls.data_ptr(), reg=reg.data_ptr())
+        self._check(self.lib.nuhtc_op_bbox_tail(self.h, ctypes.byref(a), self._stream()))
+        return cls, reg
+
+    def op_det_post(self, rois, cls, reg2, roi_off, roi_cnt, nc, stds, img_hw, scale, score_thr, nms_iou, max_per_img, limit=None, cap=None):
+        """Ensemble + Seesaw candidates + multiclass NMS + labels / mask RoIs (nuhtc_op_det_post): rois (T, 5), cls = the three stages'
+        (T, 16) logits and reg2 (T, 4) on the device; roi_off / roi_cnt per tile (sequences or device int32).  cap: candidates per tile
+        (a multiple of 64; default: room for every (roi, class) pair).  Returns dict(dets (B, max_per_img, 5), labels, counts, mask_rois,
+        det_off, det_total, cand_count (B,), cand_scores / cand_ids (B, cap), cand_boxes (B, cap, 4))."""
+        off, cnt = self._i32(roi_off), self._i32(roi_cnt)
+        B = int(cnt.shape[0])
+        if cap is None:
+            cap = max(64, -(-int(cnt.max().item()) * nc // 64) * 64)
+        K = int(max_per_img)
+        dev = dict(dtype=torch.int32, device=self.device)
+        fl = dict(dtype=torch.float32, device=self.device)
+        r = dict(dets=torch.zeros(B, K, 5, **fl), labels=torch.zeros(B, K, **dev), counts=torch.zeros(B, **dev), mask_rois=torch.zeros(B * K, 5, **fl),
+                 det_off=torch.zeros(B, **dev), det_total=torch.zeros(1, **dev), cand_count=torch.zeros(B, **dev),
+                 cand_scores=torch.zeros(B, cap, **fl), cand_ids=torch.zeros(B, cap, **dev), cand_boxes=torch.zeros(B, cap, 4, **fl))
+        a = hip.DetPostArgs(rois=rois.data_ptr(), cls0=cls[0].data_ptr(), cls1=cls[1].data_ptr(), cls2=cls[2].data_ptr(), reg2=reg2.data_ptr(),
+                            roi_off=off.data_ptr(), roi_cnt=cnt.data_ptr(), B=B, nc=int(nc), total=int(rois.shape[0]), cap=int(cap),
+                            stds=(ctypes.c_float * 4)(*[float(v) for v in stds]), img_w=float(img_hw[1]), img_h=float(img_hw[0]),
+                            scale=float(scale), score_thr=float(score_thr), nms_iou=float(nms_iou), max_per_img=K,
+                            limit=K if limit is None else int(limit), **{k: v.data_ptr() for k, v in r.items()})
+        self._check(self.lib.nuhtc_op_det_post(self.h, ctypes.byref(a), self._stream()))
+        return r
+
+    def op_paste(self, prob, mask_rois, det_off, det_counts, max_keep, H, W, vH, vW, scale, thr=0.5, masks=None, areas=None):
+        """Mask paste (nuhtc_op_paste): prob (D, 28, 28), mask_rois (D, 5) on the device -> (masks (B, max_keep, H, W // 32) int32 words,
+        areas (B, max_keep)); slots from det_counts[b] on are left as they are (zero when allocated here)."""
+        off, cnt = self._i32(det_off), self._i32(det_counts)
+        B = int(cnt.shape[0])
+        if masks is None:
+            masks = torch.zeros(B, max_keep, H, W // 32, dtype=torch.int32, device=self.device)
+        if areas is None:
+            areas = torch.zeros(B, max_keep, dtype=torch.int32, device=self.device)
+        a = hip.PasteArgs(prob=prob.data_ptr(), mask_rois=mask_rois.data_ptr(), det_off=off.data_ptr(), det_counts=cnt.data_ptr(), B=B,
+                          D=int(prob.shape[0]), max_keep=int(max_keep), H=int(H), W=int(W), vH=int(vH), vW=int(vW), scale=float(scale),
+                          thr=float(thr), masks=masks.data_ptr(), areas=areas.data_ptr())
+        self._check(self.lib.nuhtc_op_paste(self.h, ctypes.byref(a), self._stream()))
+        return masks, areas
+
+    def op_tile_post(self, dets, labels, areas, det_counts, masks, H, W, vH, vW, margin=2, min_area=10, thr=0.05, keep=None):
+        """Per-tile filter + mask-NMS (nuhtc_op_tile_post): dets (B, max_keep, 5), labels, areas (B, max_keep), masks (B, max_keep, H, W // 32)
+        on the device -> keep (B, max_keep) uint8; slots from det_counts[b] on are left as they are (zero when allocated here)."""
+        cnt = self._i32(det_counts)
+        B, K = int(dets.shape[0]), int(dets.shape[1])
+        if keep is None:
+            keep = torch.zeros(B, K, dtype=torch.uint8, device=self.device)
+        a = hip.TilePostArgs(dets=dets.data_ptr(), labels=labels.data_ptr(), areas=areas.data_ptr(), det_counts=cnt.data_ptr(),
+                             masks=masks.data_ptr(), keep=keep.data_ptr(), B=B, max_keep=K, H=int(H), W=int(W), vH=int(vH), vW=int(vW),
+                             margin=int(margin), min_area=int(min_area), thr=float(thr))
+        self._check(self.lib.nuhtc_op_tile_post(self.h, ctypes.byref(a), self._stream()))
+        return keep

@@ -60,6 +60,50 @@ class WmsaArgs(ctypes.Structure):
     ]
 
 
+class BboxTailArgs(ctypes.Structure):
+    """nuhtc_bbox_tail_args: the arguments of nuhtc_op_bbox_tail (classifier, regression rows and cascade refinement of one bbox head)."""
+    _fields_ = [
+        ('h', ctypes.c_void_p), ('cls_w', ctypes.c_void_p), ('cls_b', ctypes.c_void_p), ('reg_w', ctypes.c_void_p), ('reg_b', ctypes.c_void_p),
+        ('nc', ctypes.c_int32), ('cap', ctypes.c_int32), ('refine', ctypes.c_int32),
+        ('stds', ctypes.c_float * 4), ('img_w', ctypes.c_float), ('img_h', ctypes.c_float),
+        ('r_dev', ctypes.c_void_p), ('rois', ctypes.c_void_p), ('cls', ctypes.c_void_p), ('reg', ctypes.c_void_p),
+    ]
+
+
+class DetPostArgs(ctypes.Structure):
+    """nuhtc_det_post_args: the arguments of nuhtc_op_det_post (Seesaw candidates, multiclass NMS, labels and mask RoIs)."""
+    _fields_ = [
+        ('rois', ctypes.c_void_p), ('cls0', ctypes.c_void_p), ('cls1', ctypes.c_void_p), ('cls2', ctypes.c_void_p), ('reg2', ctypes.c_void_p),
+        ('roi_off', ctypes.c_void_p), ('roi_cnt', ctypes.c_void_p),
+        ('B', ctypes.c_int32), ('nc', ctypes.c_int32), ('total', ctypes.c_int32), ('cap', ctypes.c_int32),
+        ('stds', ctypes.c_float * 4), ('img_w', ctypes.c_float), ('img_h', ctypes.c_float), ('scale', ctypes.c_float),
+        ('score_thr', ctypes.c_float), ('nms_iou', ctypes.c_float), ('max_per_img', ctypes.c_int32), ('limit', ctypes.c_int32),
+        ('dets', ctypes.c_void_p), ('labels', ctypes.c_void_p), ('counts', ctypes.c_void_p), ('mask_rois', ctypes.c_void_p),
+        ('det_off', ctypes.c_void_p), ('det_total', ctypes.c_void_p),
+        ('cand_count', ctypes.c_void_p), ('cand_scores', ctypes.c_void_p), ('cand_ids', ctypes.c_void_p), ('cand_boxes', ctypes.c_void_p),
+    ]
+
+
+class PasteArgs(ctypes.Structure):
+    """nuhtc_paste_args: the arguments of nuhtc_op_paste (28x28 probabilities -> bit-packed masks and areas)."""
+    _fields_ = [
+        ('prob', ctypes.c_void_p), ('mask_rois', ctypes.c_void_p), ('det_off', ctypes.c_void_p), ('det_counts', ctypes.c_void_p),
+        ('B', ctypes.c_int32), ('D', ctypes.c_int32), ('max_keep', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32),
+        ('vH', ctypes.c_int32), ('vW', ctypes.c_int32), ('scale', ctypes.c_float), ('thr', ctypes.c_float),
+        ('masks', ctypes.c_void_p), ('areas', ctypes.c_void_p),
+    ]
+
+
+class TilePostArgs(ctypes.Structure):
+    """nuhtc_tile_post_args: the arguments of nuhtc_op_tile_post (margin / area filter and greedy mask-NMS of a tile)."""
+    _fields_ = [
+        ('dets', ctypes.c_void_p), ('labels', ctypes.c_void_p), ('areas', ctypes.c_void_p), ('det_counts', ctypes.c_void_p),
+        ('masks', ctypes.c_void_p), ('keep', ctypes.c_void_p),
+        ('B', ctypes.c_int32), ('max_keep', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('vH', ctypes.c_int32),
+        ('vW', ctypes.c_int32), ('margin', ctypes.c_int32), ('min_area', ctypes.c_int32), ('thr', ctypes.c_float),
+    ]
+
+
 class Dets(ctypes.Structure):
     _fields_ = [('boxes', ctypes.c_void_p), ('labels', ctypes.c_void_p), ('counts', ctypes.c_void_p),
                 ('masks', ctypes.c_void_p), ('areas', ctypes.c_void_p), ('keep', ctypes.c_void_p)]
@@ -71,7 +115,7 @@ EXPORTS = ['nuhtc_default_config', 'nuhtc_create', 'nuhtc_destroy', 'nuhtc_last_
            'nuhtc_mask_contours', 'nuhtc_merge_overlap', 'nuhtc_export_kept', 'nuhtc_clock_probe', 'nuhtc_op_swin_mlp', 'nuhtc_stream', 'nuhtc_op_swin_proj_mlp', 'nuhtc_bind_host_thread',
            'nuhtc_bind_host_thread_pci', 'nuhtc_bind_host_thread_at', 'nuhtc_restore_host_thread', 'nuhtc_op_ln_gemm', 'nuhtc_op_gemm_ln_gemm', 'nuhtc_op_merge_ln_gemm', 'nuhtc_write_ring_features',
            'nuhtc_write_point_features', 'nuhtc_join_features', 'nuhtc_fill_rings', 'nuhtc_features', 'nuhtc_op_cc_mask', 'nuhtc_op_cc_proposals',
-           'nuhtc_op_conv3', 'nuhtc_op_window_msa']
+           'nuhtc_op_conv3', 'nuhtc_op_window_msa', 'nuhtc_op_bbox_tail', 'nuhtc_op_det_post', 'nuhtc_op_paste', 'nuhtc_op_tile_post']
 
 _lib = None
 
@@ -117,6 +161,10 @@ def load():
     lib.nuhtc_op_cc_proposals.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.nuhtc_op_conv3.argtypes = [vp, ctypes.POINTER(Conv3Args), vp]
     lib.nuhtc_op_window_msa.argtypes = [vp, ctypes.POINTER(WmsaArgs), vp]
+    lib.nuhtc_op_bbox_tail.argtypes = [vp, ctypes.POINTER(BboxTailArgs), vp]
+    lib.nuhtc_op_det_post.argtypes = [vp, ctypes.POINTER(DetPostArgs), vp]
+    lib.nuhtc_op_paste.argtypes = [vp, ctypes.POINTER(PasteArgs), vp]
+    lib.nuhtc_op_tile_post.argtypes = [vp, ctypes.POINTER(TilePostArgs), vp]
     lib.nuhtc_mask_contours.argtypes = [vp, ctypes.POINTER(Dets), ci, ci, vp, vp, vp]
     lib.nuhtc_merge_overlap.argtypes = [ci, vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int64, ci, ctypes.c_double, ci, ci, ci, ci, vp, vp]
     lib.nuhtc_export_kept.argtypes = [vp, ctypes.POINTER(Dets), ci, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
