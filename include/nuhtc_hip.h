@@ -444,6 +444,59 @@ typedef struct nuhtc_tile_post_args {
 } nuhtc_tile_post_args;
 int nuhtc_op_tile_post(nuhtc_engine* e, const nuhtc_tile_post_args* a, void* stream);
 
+/* Scoring a batch on the device (csrc/eval.hip).  Replaces what the reference's `WSIDataset.evaluate` (nuhtc/datasets/WSI_coco.py:278-545) and
+ * tools/analysis_tools/pannuke/compute_stats.py compute from decoded masks, up to the integer tables the metrics are functions of: the host
+ * finishes with nuhtc_amd.evaluation.*_tables.  nuhtc_config is unchanged (no ABI bump).
+ * nuhtc_eval_batch runs after nuhtc_infer on the same `dets`, enqueues on `stream` and does not synchronise:
+ *   select : per tile, the detections with score >= fg_thr in descending score (equal scores: descending slot -- a stable ascending argsort,
+ *            reversed), greedily suppressed where inter / max(union, 1) > mask_nms_thr, the comparison made in double on the popcounts like
+ *            numpy's (`mask_nms`, nuhtc/utils/stats_utils.py:10-32).  sel [B][max_per_img] = kept slots in that order (-1 behind them),
+ *            nsel [B], sel_labels [B][max_per_img] = their labels.  Unlike the slide path's keep flags there is no margin / min-area filter.
+ *   pairs  : (gt_maps != NULL) gt_maps [B][tile_h][tile_w][num_classes] holds, per class channel, the ROW NUMBER + 1 of the ground-truth
+ *            instance covering a pixel (0 = none; rows in class-major, ascending-id order, below t_cap <= 8192).  area_t [B][t_cap] = pixels of
+ *            each row, area_p [B][max_per_img] = pixels of each selected prediction (in sel order), trips [trip_cap][4] = the non-zero
+ *            intersections as (tile, row, position in sel, pixels), in no particular order.  counters[0] = entries the list needs (beyond
+ *            trip_cap they were not written), counters[1] != 0: entries were dropped, counters[2] != 0: a map value outside [0, t_cap].
+ *   render : (pred_maps != NULL) `convert_format` (WSI_coco.py:863-906) of the selected predictions: NUHTC_EVAL_PANNUKE -> pred_maps
+ *            [B][tile_h][tile_w][num_classes + 1] (channel c = 1-based index within class c, later instances win; last channel 1 - any, all
+ *            zero for a tile without predictions), NUHTC_EVAL_CONIC -> [B][tile_h][tile_w][2] = (1-based index, max class + 1).
+ *   joint  : (gt_maps, pred_maps and joint != NULL, NUHTC_EVAL_PANNUKE) the joint histograms of `get_fast_pq_map` (pannuke/utils.py:7-104)
+ *            between gt_maps and pred_maps, table k < num_classes for class k and table num_classes for the maps `binarize` makes of all
+ *            classes (last non-zero channel wins; ids there are class << 27 | id, which keeps `binarize`'s class-major order):
+ *            joint [joint_cap][5] = (tile, table, true id, pred id, pixels) for every pair that occurs, (0, 0) included;
+ *            counters[4..6] as counters[0..2] (also set when a table holds more than 4096 distinct pairs).
+ * All pointers are device memory; counters is int32 [8]. */
+enum { NUHTC_EVAL_PANNUKE = 0, NUHTC_EVAL_CONIC = 1 };
+typedef struct nuhtc_eval_args {
+  const int32_t* gt_maps;
+  int32_t t_cap, trip_cap, joint_cap, format;
+  float fg_thr;
+  double mask_nms_thr;
+  int32_t* sel;
+  int32_t* nsel;
+  int32_t* sel_labels;
+  int32_t* area_t;
+  int32_t* area_p;
+  int32_t* trips;
+  int32_t* joint;
+  int32_t* counters;
+  int32_t* pred_maps;
+} nuhtc_eval_args;
+int nuhtc_eval_batch(nuhtc_engine* e, const nuhtc_dets* dets, int B, const nuhtc_eval_args* a, void* stream);
+/* The four steps as test entry points on raw device arrays: masks [B][K][H][W/32] (bit x & 31 of word x >> 5), K <= 2048, W % 32 == 0,
+ * C <= 14.  Every index read from device memory is range-checked by the kernels.  Each synchronises `stream`.
+ * nuhtc_op_eval_select: scores[(b * K + j) * score_stride], counts [B]; labels / sel_labels may be NULL.
+ * nuhtc_op_eval_pairs : counters int32 [4].   nuhtc_op_eval_render: out as pred_maps above.
+ * nuhtc_op_eval_joint : true_maps [B][H][W][Ct], pred_maps [B][H][W][Cp] (any non-negative ids, Ct, Cp >= C; W any), counters int32 [4]. */
+int nuhtc_op_eval_select(nuhtc_engine* e, const float* scores, int score_stride, const int32_t* counts, const uint32_t* masks, const int32_t* labels,
+                         int B, int K, int H, int W, float fg_thr, double thr, int32_t* sel, int32_t* nsel, int32_t* sel_labels, void* stream);
+int nuhtc_op_eval_pairs(nuhtc_engine* e, const uint32_t* masks, const int32_t* sel, const int32_t* nsel, const int32_t* gt_maps, int B, int K, int H,
+                        int W, int C, int t_cap, int cap, int32_t* area_t, int32_t* area_p, int32_t* trips, int32_t* counters, void* stream);
+int nuhtc_op_eval_render(nuhtc_engine* e, const uint32_t* masks, const int32_t* sel, const int32_t* nsel, const int32_t* labels, int B, int K, int H,
+                         int W, int C, int format, int32_t* out, void* stream);
+int nuhtc_op_eval_joint(nuhtc_engine* e, const int32_t* true_maps, int Ct, const int32_t* pred_maps, int Cp, int B, int H, int W, int C, int cap,
+                        int32_t* joint, int32_t* counters, void* stream);
+
 /* A HIP stream owned by the engine (valid after nuhtc_finalize) that a caller MAY run this engine on,
  * and should when it keeps several engines busy at once or raises GPU_MAX_HW_QUEUES above the runtime's default of 4: the stream
  * is created next to the engine's two internal side streams, which puts the three on different pipes of the command processor

@@ -14,6 +14,7 @@
 //   paste_kernel       : _do_paste_mask / get_seg_masks (fcn_mask_head.py:229-307,344-412) -> bit-packed masks
 //   tile_post_kernel   : tools/infer_wsi.py:510-531,60-84 margin/min-area filter + greedy mask-NMS (popcount IoU)
 #include "roi.h"
+#include "maskbits.h"
 
 __device__ __forceinline__ float wsum64(float v) {
 #pragma unroll
@@ -1498,16 +1499,7 @@ __global__ __launch_bounds__(TP_NT) void tile_post_kernel(TilePostParams p) {
     if (j < n) keep[j] = 0;
   }
   __syncthreads();
-  for (int k = 2; k <= npad; k <<= 1)
-    for (int jj = k >> 1; jj > 0; jj >>= 1) {
-      for (int t = tid; t < (npad >> 1); t += TP_NT) {
-        int lo = ((t / jj) * (jj << 1)) + (t % jj), hi = lo + jj;
-        bool asc = ((lo & k) == 0);
-        unsigned long long a = okey[lo], c = okey[hi];
-        if ((a > c) == asc) { okey[lo] = c; okey[hi] = a; }
-      }
-      __syncthreads();
-    }
+  bitonic_sort_u64<TP_NT>(okey, npad, tid);
   for (int j = tid; j < n; j += TP_NT) {
     const bool valid = okey[j] != ~0ull;
     const int i = valid ? (int)(okey[j] & 0xFFFF) : 0;
@@ -1548,10 +1540,7 @@ __global__ __launch_bounds__(TP_NT) void tile_post_kernel(TilePostParams p) {
           todo &= todo - 1;
           const int cc = c0 + l;
           const unsigned* mj = masks + (long long)sidx[cc] * words;
-          int cnt = 0;
-          for (int wv = y0 * wpr + lane; wv < y1 * wpr; wv += 64) cnt += __popc(mi[wv] & mj[wv]);
-#pragma unroll
-          for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+          const int cnt = wave_and_popc(mi, mj, y0 * wpr, y1 * wpr, lane);
           if (lane == 0) {
             const int uni = sarea[a] + sarea[cc] - cnt;
             if (uni > 0 && (double)cnt / (double)uni > p.thr) supb[a][cc >> 6] |= 1ull << (cc & 63);    // (this wave owns row a)
@@ -1586,10 +1575,7 @@ __global__ __launch_bounds__(TP_NT) void tile_post_kernel(TilePostParams p) {
       const bool ov = fminf(di.z, dj.z) + 2.f > fmaxf(di.x, dj.x) - 2.f && fminf(di.w, dj.w) + 2.f > fmaxf(di.y, dj.y) - 2.f;
       if (!ov) continue;
       const unsigned* mj = masks + (long long)sidx[c] * words;
-      int cnt = 0;
-      for (int wv = y0 * wpr + lane; wv < y1 * wpr; wv += 64) cnt += __popc(mi[wv] & mj[wv]);
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+      const int cnt = wave_and_popc(mi, mj, y0 * wpr, y1 * wpr, lane);
       if (lane == 0) {
         const int uni = sarea[a] + sarea[c] - cnt;
         if (uni > 0 && (double)cnt / (double)uni > p.thr) sup[c] = 1;

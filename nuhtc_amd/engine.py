@@ -624,3 +624,150 @@ class Engine:
                              margin=int(margin), min_area=int(min_area), thr=float(thr))
         self._check(self.lib.nuhtc_op_tile_post(self.h, ctypes.byref(a), self._stream()))
         return keep
+
+    # ------------------------------------------------------------------ scoring on the device (csrc/eval.hip)
+    def op_eval_select(self, scores, counts, masks, fg_thr, thr, labels=None):
+        """Score filter + greedy mask-NMS of `WSIDataset.evaluate` (nuhtc_op_eval_select): scores (B, K) float32, counts (B,), masks
+        (B, K, H, W // 32) int32 words on the device -> (sel (B, K) kept slots in visiting order, -1 behind them; nsel (B,); sel_labels)."""
+        B, K, H, wpr = masks.shape
+        scores, cnt = scores.contiguous().float(), self._i32(counts)
+        dev = dict(dtype=torch.int32, device=self.device)
+        sel, nsel = torch.zeros(B, K, **dev), torch.zeros(B, **dev)
+        sl = torch.zeros(B, K, **dev) if labels is not None else None
+        self._check(self.lib.nuhtc_op_eval_select(self.h, scores.data_ptr(), 1, cnt.data_ptr(), masks.data_ptr(),
+                                                  labels.data_ptr() if labels is not None else None, B, K, H, wpr * 32, float(fg_thr), float(thr),
+                                                  sel.data_ptr(), nsel.data_ptr(), sl.data_ptr() if sl is not None else None, self._stream()))
+        return sel, nsel, sl
+
+    def op_eval_pairs(self, masks, sel, nsel, gt_maps, t_cap, cap):
+        """Pair tables (nuhtc_op_eval_pairs): gt_maps (B, H, W, C) int32 row + 1 maps -> dict(area_t (B, t_cap), area_p (B, K), trips (cap, 4):
+        (tile, row, position in sel, pixels), n: entries the list needs, overflow, bad)."""
+        B, K, H, wpr = masks.shape
+        C = int(gt_maps.shape[3])
+        dev = dict(dtype=torch.int32, device=self.device)
+        r = dict(area_t=torch.zeros(B, t_cap, **dev), area_p=torch.zeros(B, K, **dev), trips=torch.full((cap + 8, 4), -7, **dev))
+        counters = torch.zeros(4, **dev)
+        self._check(self.lib.nuhtc_op_eval_pairs(self.h, masks.data_ptr(), sel.data_ptr(), nsel.data_ptr(), gt_maps.data_ptr(), B, K, H, wpr * 32, C,
+                                                 int(t_cap), int(cap), r['area_t'].data_ptr(), r['area_p'].data_ptr(), r['trips'].data_ptr(),
+                                                 counters.data_ptr(), self._stream()))
+        c = counters.cpu().numpy()
+        r.update(n=int(c[0]), overflow=bool(c[1]), bad=bool(c[2]), guard=r['trips'][cap:], trips=r['trips'][:cap])
+        return r
+
+    def op_eval_render(self, masks, sel, nsel, labels, C, data_format='pannuke'):
+        """`convert_format` of the selected predictions (nuhtc_op_eval_render) -> (B, H, W, C + 1) ('pannuke') or (B, H, W, 2) ('conic') int32."""
+        B, K, H, wpr = masks.shape
+        fmt = hip.EVAL_PANNUKE if data_format == 'pannuke' else hip.EVAL_CONIC
+        out = torch.empty(B, H, wpr * 32, C + 1 if fmt == hip.EVAL_PANNUKE else 2, dtype=torch.int32, device=self.device)
+        self._check(self.lib.nuhtc_op_eval_render(self.h, masks.data_ptr(), sel.data_ptr(), nsel.data_ptr(), labels.data_ptr(), B, K, H, wpr * 32,
+                                                  int(C), fmt, out.data_ptr(), self._stream()))
+        return out
+
+    def op_eval_joint(self, true_maps, pred_maps, C, cap):
+        """Joint histograms of the PanNuke protocol (nuhtc_op_eval_joint): true_maps, pred_maps (B, H, W, >= C) int32 -> dict(joint (cap, 5):
+        (tile, table, true id, pred id, pixels), n, overflow, bad)."""
+        B, H, W, Ct = true_maps.shape
+        dev = dict(dtype=torch.int32, device=self.device)
+        joint, counters = torch.full((cap + 8, 5), -7, **dev), torch.zeros(4, **dev)
+        self._check(self.lib.nuhtc_op_eval_joint(self.h, true_maps.data_ptr(), Ct, pred_maps.data_ptr(), int(pred_maps.shape[3]), B, H, W, int(C),
+                                                 int(cap), joint.data_ptr(), counters.data_ptr(), self._stream()))
+        c = counters.cpu().numpy()
+        return dict(joint=joint[:cap], guard=joint[cap:], n=int(c[0]), overflow=bool(c[1]), bad=bool(c[2]))
+
+    def eval_async(self, B, gt_maps_dev=None, t_cap=512, fg_thr=0.1, mask_nms_thr=0.05, data_format='pannuke', fetch_maps=True,
+                   trip_cap=None, joint_cap=None):
+        """After infer_async: enqueue, on the current stream, the scoring of the batch (nuhtc_eval_batch) -- score filter and mask-NMS,
+        and from the kept predictions the pair tables against gt_maps_dev ((B, tile_h, tile_w, C) int32 row + 1 maps of
+        evaluation.gt_rows, or None), the `convert_format` label maps and, for 'pannuke' with ground truth, the joint histograms of
+        the PanNuke protocol -- and one copy of the tables (with fetch_maps also the label maps) into pinned host memory.  No host
+        synchronisation; read with eval_read() once the stream has completed.
+        Capacities: t_cap = ground-truth instances per tile (the caller's bound: tools size it to the fold); trip_cap / joint_cap = table
+        entries per batch, by default 4 and 8 per instance the batch may hold (4 * n * max_batch, 8 * n * max_batch with n = max(t_cap, 128): a
+        prediction meets one or two instances, and a joint entry exists per instance, per prediction and per meeting pair, in its class
+        table and in the binarised one); a batch over them is flagged and scored through its masks.  The copy has a fixed size -- the
+        capacities, whatever the batch holds, since its size must be known here, before the counts exist on the host: that is why the
+        capacities follow t_cap and not max_per_img (up to t_cap = 128: 0.46 MB of pairs and joint entries per batch of 16, beside the
+        1.5 MB label map per tile that fetch_maps copies)."""
+        K, H, W, C = self.cfg.max_per_img, self.cfg.tile_h, self.cfg.tile_w, self.cfg.num_classes
+        mb = self.cfg.max_batch
+        fmt = hip.EVAL_PANNUKE if data_format == 'pannuke' else hip.EVAL_CONIC
+        CO = C + 1 if fmt == hip.EVAL_PANNUKE else 2
+        per_tile = max(int(t_cap), 128)
+        trip_cap = int(trip_cap or 4 * per_tile * mb)
+        joint_cap = int(joint_cap or 8 * per_tile * mb)
+        key = (int(t_cap), trip_cap, joint_cap, CO, bool(fetch_maps))
+        ev = getattr(self, '_ev', None)
+        if ev is None or ev['key'] != key:
+            names = dict(counters=(8,), nsel=(mb,), sel=(mb, K), sel_labels=(mb, K), area_p=(mb, K), area_t=(mb, t_cap), trips=(trip_cap, 4),
+                         joint=(joint_cap, 5))
+            if fetch_maps:
+                names['maps'] = (mb, H, W, CO)
+            offs, total = {}, 0
+            for k, sh in names.items():          # every table is a view into ONE int32 device buffer and ONE pinned host buffer: one copy per batch
+                offs[k] = total
+                total += (int(np.prod(sh)) + 63) // 64 * 64
+            with torch.cuda.device(self.device):
+                blob_dev = torch.zeros(total, dtype=torch.int32, device=self.device)
+                maps_dev = None if fetch_maps else torch.zeros(mb, H, W, CO, dtype=torch.int32, device=self.device)
+            blob_hosts = [torch.zeros(total, dtype=torch.int32).pin_memory() for _ in range(self.EXPORT_BUFFERS)]
+            view = lambda blob, k: blob[offs[k]:offs[k] + int(np.prod(names[k]))].view(*names[k])
+            ev = self._ev = dict(key=key, blob_dev=blob_dev, blob_hosts=blob_hosts, turn=0, dev={k: view(blob_dev, k) for k in names},
+                                 hosts=[{k: view(b, k) for k in names} for b in blob_hosts], small=offs.get('maps', total),
+                                 meta=[None] * self.EXPORT_BUFFERS)
+            if not fetch_maps:
+                ev['dev']['maps'] = maps_dev
+        d = ev['dev']
+        if gt_maps_dev is not None and (tuple(gt_maps_dev.shape) != (B, H, W, C) or gt_maps_dev.dtype != torch.int32 or not gt_maps_dev.is_contiguous()):
+            raise ValueError(f'eval_async: gt_maps_dev must be a contiguous int32 {(B, H, W, C)} device tensor')
+        self._ev_gt = gt_maps_dev          # (kept alive until the next call)
+        a = hip.EvalArgs(gt_maps=gt_maps_dev.data_ptr() if gt_maps_dev is not None else None, t_cap=int(t_cap), trip_cap=trip_cap, joint_cap=joint_cap,
+                         format=fmt, fg_thr=float(fg_thr), mask_nms_thr=float(mask_nms_thr), **{k: d[k].data_ptr() for k in
+                         ('sel', 'nsel', 'sel_labels', 'area_t', 'area_p', 'trips', 'joint', 'counters')}, pred_maps=d['maps'].data_ptr())
+        self._check(self.lib.nuhtc_eval_batch(self.h, ctypes.byref(self.dets), B, ctypes.byref(a), self._stream()))
+        ev['turn'] = (ev['turn'] + 1) % self.EXPORT_BUFFERS
+        n = ev['small'] + (B * H * W * CO if fetch_maps else 0)          # the tables, and the label maps of the B tiles behind them
+        ev['blob_hosts'][ev['turn']][:n].copy_(ev['blob_dev'][:n], non_blocking=True)
+        ev['meta'][ev['turn']] = dict(B=B, has_gt=gt_maps_dev is not None, fmt=fmt)          # what eval_read(turn) needs to slice that buffer
+        return ev['turn']
+
+    def eval_read(self, turn=None):
+        """Tables of the batch eval_async scored, as numpy (call after the stream has completed): dict(nsel (B,), labels: per tile the labels
+        of the kept predictions in visiting order, slots: their detection slots, maps (B, tile_h, image width, C + 1 | 2) int32 or None,
+        and with ground truth area_t (B, t_cap), area_p: per tile (n_p,), pairs: per tile (rows, positions, pixels), joint: per tile the
+        C + 1 tables (true ids, pred ids, pixels) of evaluation.pannuke_stats_tables ('pannuke' only), overflow: a table did not fit its
+        capacity -- score the batch on the host then).  Raises when a ground-truth map held a value outside [0, t_cap].
+        `turn` selects the buffer of an earlier eval_async (its return value).  Everything returned is a copy except `maps`, a VIEW of the
+        pinned buffer (1.5 MB per tile: the caller converts or copies what it keeps): like the views of export_read it stays valid through
+        the next TWO eval_async calls of this engine (EXPORT_BUFFERS = 3 buffers used in turn), not the one after those, and all buffers
+        are replaced when a call changes a capacity or the format."""
+        ev = self._ev
+        turn = ev['turn'] if turn is None else turn
+        h, meta = ev['hosts'][turn], ev['meta'][turn]
+        B, C = meta['B'], self.cfg.num_classes
+        cnt = h['counters'].numpy()
+        if cnt[2] or cnt[6]:
+            raise HipError('eval: a ground-truth map holds a value outside [0, t_cap] (evaluation.gt_rows numbers the rows; raise t_cap)')
+        nsel = h['nsel'][:B].numpy().copy()
+        out = dict(nsel=nsel, slots=[h['sel'][b, :nsel[b]].numpy().copy() for b in range(B)],
+                   labels=[h['sel_labels'][b, :nsel[b]].numpy().astype(int) for b in range(B)],
+                   maps=h['maps'][:B, :, :self.image_hw[1]].numpy() if 'maps' in h else None, overflow=False)
+        if not meta['has_gt']:
+            return out
+        out['overflow'] = bool(cnt[1] or cnt[5] or cnt[0] > h['trips'].shape[0] or cnt[4] > h['joint'].shape[0])
+        if out['overflow']:
+            return out
+        tr = h['trips'][:int(cnt[0])].numpy()
+        order = np.argsort(tr[:, 0], kind='stable')
+        tr = tr[order]
+        cut = np.searchsorted(tr[:, 0], np.arange(B + 1))
+        out['pairs'] = [(tr[cut[b]:cut[b + 1], 1], tr[cut[b]:cut[b + 1], 2], tr[cut[b]:cut[b + 1], 3]) for b in range(B)]
+        out['area_t'] = h['area_t'][:B].numpy().copy()
+        out['area_p'] = [h['area_p'][b, :nsel[b]].numpy().copy() for b in range(B)]
+        if meta['fmt'] == hip.EVAL_PANNUKE:
+            jt = h['joint'][:int(cnt[4])].numpy()
+            key = jt[:, 0].astype(np.int64) * (C + 1) + jt[:, 1]
+            jt = jt[np.argsort(key, kind='stable')]
+            cut = np.searchsorted(np.sort(key, kind='stable'), np.arange(B * (C + 1) + 1))
+            out['joint'] = [[(jt[cut[b * (C + 1) + k]:cut[b * (C + 1) + k + 1], 2], jt[cut[b * (C + 1) + k]:cut[b * (C + 1) + k + 1], 3],
+                              jt[cut[b * (C + 1) + k]:cut[b * (C + 1) + k + 1], 4]) for k in range(C + 1)] for b in range(B)]
+        return out

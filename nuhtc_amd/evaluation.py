@@ -370,3 +370,193 @@ def pannuke_stats(true, pred, types, num_classes=5, tissue_types=PANNUKE_TISSUES
         res = dict(class_pq=class_pq, tissue_mpq=t_mpq, tissue_bpq=t_bpq,
                    mPQ=np.nanmean(list(t_mpq.values())), bPQ=np.nanmean(list(t_bpq.values())))
     return res
+
+
+# ----------------------------------------------------------------------------- the same statistics from integer tables
+# Everything above is a function of a few integers: the intersection of every (true, pred) pair and the areas of both sides for the
+# mask-list statistics, the joint histogram of two label maps for the PanNuke protocol.  The twins below take those tables -- built on
+# the device by nuhtc_eval_batch (Engine.eval_async / eval_read) or on the host by pair_tables / joint_tables -- and return what the
+# mask functions return, through the same arithmetic.
+def gt_rows(mask, num_classes=None):
+    """Ground truth of one image, (H, W, >= C) per-class instance maps (PanNuke's mask format), as row maps for the device:
+    -> (maps (H, W, C) int32 holding row number + 1 of the instance covering a pixel, 0 = none; labels (n_t,) int; n_t).
+    Rows are numbered class-major, ascending id within a class: the order of tools/test_pannuke.py `gt_instances`."""
+    mask = np.asarray(mask)
+    nc = mask.shape[2] - 1 if num_classes is None else int(num_classes)
+    maps = np.zeros(mask.shape[:2] + (nc,), np.int32)
+    labels, n = [], 0
+    for c in range(nc):
+        ids, inv = np.unique(mask[:, :, c], return_inverse=True)
+        inv = inv.reshape(mask.shape[:2])
+        row = np.zeros(len(ids), np.int32)
+        nz = ids != 0
+        row[nz] = n + 1 + np.arange(int(nz.sum()), dtype=np.int32)
+        maps[:, :, c] = row[inv]
+        labels += [c] * int(nz.sum())
+        n += int(nz.sum())
+    return maps, np.array(labels, dtype=int), n
+
+
+def pair_tables(gt_maps, n_t, pred_masks):
+    """Host construction of the pair tables the device returns: gt_maps from gt_rows, pred_masks (n_p, H, W) bool
+    -> (inter (n_t, n_p) float64, area_t (n_t,), area_p (n_p,)) with integer values."""
+    pred_masks = np.asarray(pred_masks).astype(bool)
+    n_p = len(pred_masks)
+    inter = np.zeros((n_t, n_p))
+    for j in range(n_p):
+        rows = gt_maps[pred_masks[j].reshape(gt_maps.shape[:2])].ravel()
+        inter[:, j] = np.bincount(rows, minlength=n_t + 1)[1:n_t + 1]
+    area_t = np.bincount(gt_maps.ravel(), minlength=n_t + 1)[1:n_t + 1].astype(np.float64)
+    area_p = pred_masks.reshape(n_p, -1).sum(1).astype(np.float64)
+    return inter, area_t, area_p
+
+
+def dense_pairs(n_t, n_p, rows, cols, counts):
+    """(row, column, pixels) triples -> the dense (n_t, n_p) float64 intersection matrix."""
+    inter = np.zeros((n_t, n_p))
+    inter[np.asarray(rows, dtype=int), np.asarray(cols, dtype=int)] = counts
+    return inter
+
+
+def _area_rows(area):
+    # a mask list enters get_fast_aji / get_fast_aji_plus / get_fast_pq only through len() and through the sums of its flattened rows:
+    # an (n, 1) array holding each instance's area stands in for it
+    return np.asarray(area, dtype=np.float64).reshape(-1, 1)
+
+
+def stat_calc_tables(inter, area_t, area_p, match_iou=0.5):
+    """`stat_calc` from the (n_t, n_p) intersection matrix and the areas of both sides."""
+    t, p = _area_rows(area_t), _area_rows(area_p)
+    inter = np.asarray(inter, dtype=np.float64).reshape(len(t), len(p))
+    union = t + p.T - inter
+    nt, npred = len(t), len(p)
+    if nt == 0 and npred == 0:
+        return None
+    zero = dict(aji=0, aji_plus=0, dq=0, sq=0, pq=0, dice=0, precision=0, recall=0, tp=0, fp=0, fn=0, iou=0)
+    if nt == 0:
+        return dict(zero, fp=npred)
+    if npred == 0:
+        return dict(zero, fn=nt)
+    iou = inter / union
+    iou[iou <= match_iou] = 0.0
+    paired_true, paired_pred = np.nonzero(iou)
+    aji = get_fast_aji(t, p, inter, union)
+    aji_plus = get_fast_aji_plus(t, p, inter, union, paired_true, paired_pred)
+    pq = get_fast_pq(t, p, inter, union, paired_true, paired_pred, match_iou)
+    tp, fp, fn = len(pq[1][0]), len(pq[1][3]), len(pq[1][2])
+    dice = get_fast_dice(t, p, inter, union, paired_true, paired_pred)
+    return dict(aji=aji, aji_plus=aji_plus, dq=pq[0][0], sq=pq[0][1], pq=pq[0][2], dice=dice,
+                precision=tp / (tp + fp + 1e-9), recall=tp / (tp + fn + 1e-9), tp=tp, fp=fp, fn=fn,
+                iou=pq[0][1] * (tp + 1e-6))
+
+
+def multi_stat_calc_tables(inter, area_t, area_p, gt_labels, pred_labels, num_classes, match_iou=0.5):
+    """`multi_stat_calc` from the tables: the class-c block of the intersection matrix is the table of class c."""
+    area_t, area_p = np.asarray(area_t, dtype=np.float64), np.asarray(area_p, dtype=np.float64)
+    gt_labels, pred_labels = np.asarray(gt_labels, dtype=int), np.asarray(pred_labels, dtype=int)
+    inter = np.asarray(inter, dtype=np.float64).reshape(len(area_t), len(area_p))
+    out = []
+    for c in range(num_classes):
+        ti, pi = np.nonzero(gt_labels == c)[0], np.nonzero(pred_labels == c)[0]
+        info = stat_calc_tables(inter[np.ix_(ti, pi)], area_t[ti], area_p[pi], match_iou)
+        out.append([info['tp'], info['fp'], info['fn'], info['iou']] if info else [float('nan')] * 4)
+    return out
+
+
+def update_confusion_matrix_tables(confusion_matrix, inter, area_t, area_p, gt_labels, pred_labels, tp_iou_thr=0.5):
+    """`update_confusion_matrix` from the tables."""
+    gt_labels = np.asarray(gt_labels, dtype=int)
+    pred_labels = np.asarray(pred_labels, dtype=int)
+    t, p = _area_rows(area_t), _area_rows(area_p)
+    if len(t) and len(p):
+        inter = np.asarray(inter, dtype=np.float64).reshape(len(t), len(p))
+        ious = inter / (t + p.T - inter)
+    else:
+        ious = np.zeros((len(t), len(p)))
+    matched = np.zeros(len(gt_labels), dtype=int)
+    for i, dl in enumerate(pred_labels):
+        hit = np.nonzero(ious[:, i] >= tp_iou_thr)[0]
+        for j in hit:
+            matched[j] += 1
+            confusion_matrix[gt_labels[j], dl] += 1
+        if len(hit) == 0:
+            confusion_matrix[-1, dl] += 1
+    for n, gl in zip(matched, gt_labels):
+        if n == 0:
+            confusion_matrix[gl, -1] += 1
+    return confusion_matrix
+
+
+BIN_CLASS_SHIFT = 27     # id of a pixel in a binarised map: class << 27 | id within the class (csrc/eval.hip EJ_CLASS_SHIFT)
+
+
+def _bin_ids(x):
+    out = np.zeros(x.shape[:2], np.int64)
+    for c in range(x.shape[2]):
+        ch = x[:, :, c].astype(np.int64)
+        out = np.where(ch != 0, (c << BIN_CLASS_SHIFT) | ch, out)
+    return out
+
+
+def _joint(t, p):
+    pairs, n = np.unique(np.stack([np.asarray(t).ravel(), np.asarray(p).ravel()], 1).astype(np.int64), axis=0, return_counts=True)
+    return pairs[:, 0], pairs[:, 1], n
+
+
+def joint_tables(true, pred, num_classes):
+    """Host construction of the joint tables the device returns for one image: true, pred (H, W, >= C) per-class instance maps
+    -> list of C + 1 tables (true ids, pred ids, pixels), one row per pair that occurs ((0, 0) included): table c < C for class c,
+    table C for the binarised maps.  `binarize` keeps the last non-zero channel of a pixel and numbers instances class-major; the ids
+    here (class << 27 | id) name the same partition in the same order, which is all PQ depends on."""
+    out = [_joint(true[:, :, c], pred[:, :, c]) for c in range(num_classes)]
+    out.append(_joint(_bin_ids(true[:, :, :num_classes]), _bin_ids(pred[:, :, :num_classes])))
+    return out
+
+
+def pq_from_joint(t, p, n, match_iou=0.5):
+    """PQ of `get_fast_pq_map` from the joint histogram of the two label maps, given as rows (true id, pred id, pixels) with id 0 the
+    background: the ids take the place of the contiguous numbers `remap_label` would give them, in the same (ascending) order.
+    NaN when the true map holds a single value, as `pannuke_stats` scores such an image.  match_iou >= 0.5 only."""
+    assert match_iou >= 0.5
+    t, p, n = np.asarray(t, dtype=np.int64), np.asarray(p, dtype=np.int64), np.asarray(n, dtype=np.float64)
+    if len(np.unique(t)) == 1:
+        return np.nan
+    t_ids, p_ids = np.unique(t[t > 0]), np.unique(p[p > 0])
+    ti, pi = np.searchsorted(t_ids, t), np.searchsorted(p_ids, p)
+    area_t = np.bincount(ti[t > 0], weights=n[t > 0], minlength=len(t_ids))
+    area_p = np.bincount(pi[p > 0], weights=n[p > 0], minlength=len(p_ids))
+    both = (t > 0) & (p > 0)
+    inter = np.zeros((len(t_ids), len(p_ids)))
+    inter[ti[both], pi[both]] = n[both]
+    union = area_t[:, None] + area_p[None, :] - inter
+    with np.errstate(divide='ignore', invalid='ignore'):
+        pairwise_iou = np.where(inter > 0, inter / union, 0.0)
+    pairwise_iou[pairwise_iou <= match_iou] = 0.0
+    paired_true, paired_pred = np.nonzero(pairwise_iou)
+    paired_iou = pairwise_iou[paired_true, paired_pred]
+    tp = len(paired_true)
+    fp = len(p_ids) - len(np.unique(paired_pred))
+    fn = len(t_ids) - len(np.unique(paired_true))
+    dq = tp / (tp + 0.5 * fp + 0.5 * fn)
+    sq = paired_iou.sum() / (tp + 1.0e-6)
+    return dq * sq
+
+
+def pannuke_stats_tables(tables, types, num_classes=5, tissue_types=PANNUKE_TISSUES):
+    """`pannuke_stats` from joint tables: tables[i] = the C + 1 tables of image i (joint_tables, or Engine.eval_read)."""
+    import warnings
+    mpq_all = [[pq_from_joint(*tab[c]) for c in range(num_classes)] for tab in tables]
+    bpq_all = [[pq_from_joint(*tab[num_classes])] for tab in tables]
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', category=RuntimeWarning)   # nanmean of all-NaN slices is NaN, as in the reference
+        mpq_img = [np.nanmean(p) for p in mpq_all]
+        bpq_img = [np.nanmean(p) for p in bpq_all]
+        class_pq = [np.nanmean([p[c] for p in mpq_all]) for c in range(num_classes)]
+        t_mpq, t_bpq = {}, {}
+        for name in tissue_types:
+            idx = [i for i, x in enumerate(types) if x == name]
+            t_mpq[name] = np.nanmean([mpq_img[i] for i in idx]) if idx else np.nan
+            t_bpq[name] = np.nanmean([bpq_img[i] for i in idx]) if idx else np.nan
+        res = dict(class_pq=class_pq, tissue_mpq=t_mpq, tissue_bpq=t_bpq,
+                   mPQ=np.nanmean(list(t_mpq.values())), bPQ=np.nanmean(list(t_bpq.values())))
+    return res

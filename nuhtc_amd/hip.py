@@ -17,6 +17,7 @@ OVERLAP_MASK, OVERLAP_POLYGON = 0, 1
 PIPE_BF16_SPLIT, PIPE_FP32 = 0, 1
 ORDER_TOKEN, ORDER_COMPACT = 0, 1
 SCHED_LATENCY, SCHED_THROUGHPUT = 0, 1
+EVAL_PANNUKE, EVAL_CONIC = 0, 1
 
 
 class Config(ctypes.Structure):
@@ -104,6 +105,16 @@ class TilePostArgs(ctypes.Structure):
     ]
 
 
+class EvalArgs(ctypes.Structure):
+    """nuhtc_eval_args: the arguments of nuhtc_eval_batch (selection, pair tables, label maps and joint histograms of a finished inference)."""
+    _fields_ = [
+        ('gt_maps', ctypes.c_void_p), ('t_cap', ctypes.c_int32), ('trip_cap', ctypes.c_int32), ('joint_cap', ctypes.c_int32), ('format', ctypes.c_int32),
+        ('fg_thr', ctypes.c_float), ('mask_nms_thr', ctypes.c_double),
+        ('sel', ctypes.c_void_p), ('nsel', ctypes.c_void_p), ('sel_labels', ctypes.c_void_p), ('area_t', ctypes.c_void_p), ('area_p', ctypes.c_void_p),
+        ('trips', ctypes.c_void_p), ('joint', ctypes.c_void_p), ('counters', ctypes.c_void_p), ('pred_maps', ctypes.c_void_p),
+    ]
+
+
 class Dets(ctypes.Structure):
     _fields_ = [('boxes', ctypes.c_void_p), ('labels', ctypes.c_void_p), ('counts', ctypes.c_void_p),
                 ('masks', ctypes.c_void_p), ('areas', ctypes.c_void_p), ('keep', ctypes.c_void_p)]
@@ -115,7 +126,8 @@ EXPORTS = ['nuhtc_default_config', 'nuhtc_create', 'nuhtc_destroy', 'nuhtc_last_
            'nuhtc_mask_contours', 'nuhtc_merge_overlap', 'nuhtc_export_kept', 'nuhtc_clock_probe', 'nuhtc_op_swin_mlp', 'nuhtc_stream', 'nuhtc_op_swin_proj_mlp', 'nuhtc_bind_host_thread',
            'nuhtc_bind_host_thread_pci', 'nuhtc_bind_host_thread_at', 'nuhtc_restore_host_thread', 'nuhtc_op_ln_gemm', 'nuhtc_op_gemm_ln_gemm', 'nuhtc_op_merge_ln_gemm', 'nuhtc_write_ring_features',
            'nuhtc_write_point_features', 'nuhtc_join_features', 'nuhtc_fill_rings', 'nuhtc_features', 'nuhtc_op_cc_mask', 'nuhtc_op_cc_proposals',
-           'nuhtc_op_conv3', 'nuhtc_op_window_msa', 'nuhtc_op_bbox_tail', 'nuhtc_op_det_post', 'nuhtc_op_paste', 'nuhtc_op_tile_post']
+           'nuhtc_op_conv3', 'nuhtc_op_window_msa', 'nuhtc_op_bbox_tail', 'nuhtc_op_det_post', 'nuhtc_op_paste', 'nuhtc_op_tile_post',
+           'nuhtc_eval_batch', 'nuhtc_op_eval_select', 'nuhtc_op_eval_pairs', 'nuhtc_op_eval_render', 'nuhtc_op_eval_joint']
 
 _lib = None
 
@@ -165,6 +177,11 @@ def load():
     lib.nuhtc_op_det_post.argtypes = [vp, ctypes.POINTER(DetPostArgs), vp]
     lib.nuhtc_op_paste.argtypes = [vp, ctypes.POINTER(PasteArgs), vp]
     lib.nuhtc_op_tile_post.argtypes = [vp, ctypes.POINTER(TilePostArgs), vp]
+    lib.nuhtc_eval_batch.argtypes = [vp, ctypes.POINTER(Dets), ci, ctypes.POINTER(EvalArgs), vp]
+    lib.nuhtc_op_eval_select.argtypes = [vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, cf, ctypes.c_double, vp, vp, vp, vp]
+    lib.nuhtc_op_eval_pairs.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]
+    lib.nuhtc_op_eval_render.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
+    lib.nuhtc_op_eval_joint.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp]
     lib.nuhtc_mask_contours.argtypes = [vp, ctypes.POINTER(Dets), ci, ci, vp, vp, vp]
     lib.nuhtc_merge_overlap.argtypes = [ci, vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int64, ci, ctypes.c_double, ci, ci, ci, ci, vp, vp]
     lib.nuhtc_export_kept.argtypes = [vp, ctypes.POINTER(Dets), ci, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
