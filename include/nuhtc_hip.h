@@ -561,6 +561,41 @@ int64_t nuhtc_join_features(const char* text, const int64_t* feat_start, const i
 int64_t nuhtc_fill_rings(const int32_t* verts, const int64_t* ring_off, int64_t n, int32_t* boxes, int32_t* areas, int64_t* word_off,
                          uint32_t* bits, int64_t cap_words, int32_t threads);
 
+/* Tissue mask and tile selection of the whole-slide path on the device (csrc/tissue.hip; the host code they equal byte for byte is
+ * nuhtc_amd/tissue.py).  Engine-free like nuhtc_merge_overlap: pointers are device memory of `device` unless marked HOST, each call allocates
+ * and frees its own scratch, runs on `stream` and synchronises it before returning.  Integer arithmetic only. */
+enum {
+  NUHTC_TISSUE_ALL = 0,        /* image -> saturation -> median -> histogram -> threshold -> close */
+  NUHTC_TISSUE_MEDIAN = 1,     /* image -> saturation -> median -> histogram (the first launch of an Otsu run; `med` is an output) */
+  NUHTC_TISSUE_THRESHOLD = 2   /* `med` (an input) -> threshold -> close (the second launch, after the host's Otsu loop over `hist`) */
+};
+/* `segmentTissue` up to the binary image contours are found on.  img: uint8 pixels of >= 3 channels, pixel (y, x) channel c at
+ * img[y * row_stride + x * pix_stride + c] (R, G, B first; pix_stride >= 3, row_stride >= W * pix_stride).  Steps: S of OpenCV's 8-bit RGB2HSV
+ * (12-bit fixed point, 0 where v = 0); mthresh x mthresh median with replicated borders (mthresh odd, 1..15); binary = med > sthresh ?
+ * min(sthresh_up, 255) : 0; close x close rectangular close anchored at close / 2 (0..16; 0 and 1 leave the image as it is; the border never wins).
+ * Outputs [H][W] uint8: `binary` (not in stage MEDIAN), `sat` (nullable), `med` (nullable in stage ALL, required otherwise) and
+ * hist[256] int64 = histogram of the median plane (stages ALL and MEDIAN; ignored in stage THRESHOLD).
+ * NUHTC_E_INVALID (nothing written): a null required pointer, H or W < 1, H * W > 2^31 - 1, bad strides, mthresh even or outside 1..15,
+ * close outside 0..16, sthresh_up < 0, an unknown stage. */
+int nuhtc_tissue_mask(int device, const uint8_t* img, int H, int W, int64_t row_stride, int pix_stride, int stage, int mthresh, int sthresh,
+                      int sthresh_up, int close, uint8_t* binary, uint8_t* sat, uint8_t* med, int64_t* hist, void* stream);
+/* cv2.pointPolygonTest(contour, pt, False) of n integer points against one closed integer contour: out[i] = +1 inside, 0 on an edge or
+ * vertex, -1 outside (on an edge wins, otherwise the parity of the edges a ray towards +x crosses, an edge counting when exactly one of its
+ * ends has y <= py).  contour [n_vert][2], pts [n][2] int32 (x, y); exact for |coordinate| <= 2^30 (differences in 32 bits, products in
+ * 64).  NUHTC_E_INVALID (nothing written): n_vert < 1, n < 0, a null pointer with n > 0. */
+int nuhtc_points_polygon_test(int device, const int32_t* contour, int64_t n_vert, const int32_t* pts, int64_t n, int8_t* out, void* stream);
+/* The grid of one tissue contour (`process_contour`): candidate (ix, iy) = (start_x + ix * step, start_y + iy * step), keep[ix * ny + iy] = 1
+ * when the contour test passes and the point candidate + (hole_dx, hole_dy) is not strictly inside any hole.  The contour test takes
+ * the n_off (1..4) points candidate + offsets[j]: with require_all = 0 one of them inside or on the contour passes ('four_pt'), with 1
+ * all must ('four_pt_hard'); 'basic' / 'center' are n_off = 1.  contour NULL with n_vert = 0: no contour test (every candidate passes it).
+ * holes: the vertices of all holes in one pool [n_pool][2], hole h = rows hole_off[h] .. hole_off[h + 1]; n_holes may be 0 (holes NULL).
+ * HOST: offsets [n_off][2] int32, hole_off [n_holes + 1] int64.  Half-integer patch centres: the caller doubles every coordinate.
+ * NUHTC_E_INVALID (nothing written): nx or ny < 0, nx * ny > 2^31 - 1, step < 1, a grid or tested point beyond +-2^30, n_off outside 1..4,
+ * n_vert < 0, hole offsets that do not start at 0, decrease, leave a hole empty or run past n_pool, a null required pointer. */
+int nuhtc_grid_in_contour(int device, int start_x, int start_y, int nx, int ny, int step, const int32_t* offsets, int n_off, int require_all,
+                          const int32_t* contour, int64_t n_vert, const int32_t* holes, int64_t n_pool, const int64_t* hole_off, int n_holes,
+                          int hole_dx, int hole_dy, uint8_t* keep, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the launch stream (process-wide switch; off by default).
  * nuhtc_profile_read synchronises the device and writes one text line per kernel tag,
  * "tag launches total_ms algorithmic_flops algorithmic_bytes", then resets the records. */

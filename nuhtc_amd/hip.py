@@ -18,6 +18,7 @@ PIPE_BF16_SPLIT, PIPE_FP32 = 0, 1
 ORDER_TOKEN, ORDER_COMPACT = 0, 1
 SCHED_LATENCY, SCHED_THROUGHPUT = 0, 1
 EVAL_PANNUKE, EVAL_CONIC = 0, 1
+TISSUE_ALL, TISSUE_MEDIAN, TISSUE_THRESHOLD = 0, 1, 2
 
 
 class Config(ctypes.Structure):
@@ -127,7 +128,8 @@ EXPORTS = ['nuhtc_default_config', 'nuhtc_create', 'nuhtc_destroy', 'nuhtc_last_
            'nuhtc_bind_host_thread_pci', 'nuhtc_bind_host_thread_at', 'nuhtc_restore_host_thread', 'nuhtc_op_ln_gemm', 'nuhtc_op_gemm_ln_gemm', 'nuhtc_op_merge_ln_gemm', 'nuhtc_write_ring_features',
            'nuhtc_write_point_features', 'nuhtc_join_features', 'nuhtc_fill_rings', 'nuhtc_features', 'nuhtc_op_cc_mask', 'nuhtc_op_cc_proposals',
            'nuhtc_op_conv3', 'nuhtc_op_window_msa', 'nuhtc_op_bbox_tail', 'nuhtc_op_det_post', 'nuhtc_op_paste', 'nuhtc_op_tile_post',
-           'nuhtc_eval_batch', 'nuhtc_op_eval_select', 'nuhtc_op_eval_pairs', 'nuhtc_op_eval_render', 'nuhtc_op_eval_joint']
+           'nuhtc_eval_batch', 'nuhtc_op_eval_select', 'nuhtc_op_eval_pairs', 'nuhtc_op_eval_render', 'nuhtc_op_eval_joint',
+           'nuhtc_tissue_mask', 'nuhtc_points_polygon_test', 'nuhtc_grid_in_contour']
 
 _lib = None
 
@@ -184,6 +186,9 @@ def load():
     lib.nuhtc_op_eval_joint.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp]
     lib.nuhtc_mask_contours.argtypes = [vp, ctypes.POINTER(Dets), ci, ci, vp, vp, vp]
     lib.nuhtc_merge_overlap.argtypes = [ci, vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int64, ci, ctypes.c_double, ci, ci, ci, ci, vp, vp]
+    lib.nuhtc_tissue_mask.argtypes = [ci, vp, ci, ci, ctypes.c_int64, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]
+    lib.nuhtc_points_polygon_test.argtypes = [ci, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp]
+    lib.nuhtc_grid_in_contour.argtypes = [ci, ci, ci, ci, ci, ci, vp, ci, ci, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ci, ci, ci, vp, vp]
     lib.nuhtc_export_kept.argtypes = [vp, ctypes.POINTER(Dets), ci, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.nuhtc_export_crops.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, ci, vp]
     lib.nuhtc_profile_enable.argtypes = [ci]

@@ -216,10 +216,14 @@ def stitch_coords(slide, coords, patch_size, downscale=64, bg_color=(0, 0, 0)):
 def seg_and_patch(source, save_dir, patch_save_dir, mask_save_dir, stitch_save_dir, patch_size=256, step_size=256,
                   seg_params=None, filter_params=None, vis_params=None, patch_params=None, patch_level=0, use_default_params=False,
                   seg=False, save_mask=True, stitch=False, patch=False, no_auto_skip=False, process_list=None,
-                  slides=None, seg_downsample=64, log=print):
+                  slides=None, seg_downsample=64, log=print, seg_on='host', device=0):
     """tools/infer_wsi.py:117-306 with the same arguments (+ `slides`: an explicit list of file names instead of the folder listing,
-    `seg_downsample`: the downsample `seg_level = -1` / `vis_level = -1` resolve to).  Returns (seg_times, patch_times)."""
+    `seg_downsample`: the downsample `seg_level = -1` / `vis_level = -1` resolve to; `seg_on`: 'host' (numpy / scipy) or 'gpu': the tissue
+    mask and the grid's contour / hole tests run on GPU `device` (csrc/tissue.hip) and write the same files).  Returns (seg_times, patch_times)."""
     import pandas as pd
+    if seg_on not in ('host', 'gpu'):
+        raise ValueError(f"seg_on must be 'host' or 'gpu', got {seg_on!r}")
+    tissue_device = device if seg_on == 'gpu' else None
     seg_params = dict(SEG_PARAMS if seg_params is None else seg_params)
     filter_params = dict(FILTER_PARAMS if filter_params is None else filter_params)
     vis_params = dict(VIS_PARAMS if vis_params is None else vis_params)
@@ -299,7 +303,7 @@ def seg_and_patch(source, save_dir, patch_save_dir, mask_save_dir, stitch_save_d
                                                  sthresh=int(cur_seg['sthresh']), mthresh=int(cur_seg['mthresh']),
                                                  close=int(cur_seg['close']), use_otsu=bool(cur_seg['use_otsu']),
                                                  filter_params=dict(a_t=cur_filter['a_t'], a_h=cur_filter['a_h'], max_n_holes=int(cur_filter['max_n_holes'])),
-                                                 keep_ids=keep_ids, exclude_ids=exclude_ids)
+                                                 keep_ids=keep_ids, exclude_ids=exclude_ids, device=tissue_device)
             seg_time = time.time() - t0
         if save_mask:
             vis_mask(img, conts, holes, int(cur_vis['vis_level']), int(cur_vis['line_thickness'])).save(os.path.join(mask_save_dir, slide_id + '.png'))
@@ -311,7 +315,8 @@ def seg_and_patch(source, save_dir, patch_save_dir, mask_save_dir, stitch_save_d
                 # is tiled on the grid np.arange(0, size, step)
                 coords = tilestore.grid_coords(H, W, step_size)
             else:
-                parts = [tissue.contour_coords(c, hs, (W, H), patch_size, step_size, str(cur_patch['contour_fn']), bool(cur_patch['use_padding']))
+                parts = [tissue.contour_coords(c, hs, (W, H), patch_size, step_size, str(cur_patch['contour_fn']), bool(cur_patch['use_padding']),
+                                               device=tissue_device)
                          for c, hs in zip(conts, holes)]
                 coords = np.concatenate(parts, 0) if parts else np.zeros((0, 2), np.int64)
             if len(coords):                                        # the reference creates the .h5 with the first contour that yields tiles (:397-403)

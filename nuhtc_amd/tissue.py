@@ -59,6 +59,26 @@ def otsu_threshold(img):
     return best_t
 
 
+def otsu_threshold_hist(hist):
+    """`otsu_threshold` on a given 256-bin histogram (the device route counts the median plane on the GPU and runs this loop on the host)."""
+    hist = np.asarray(hist).reshape(-1).astype(np.float64)
+    total = hist.sum()
+    mu = (hist * np.arange(256)).sum() / total
+    best, best_t, q1, mu1 = 0.0, 0, 0.0, 0.0
+    for t in range(256):
+        p = hist[t] / total
+        mu1 = (q1 * mu1 + t * p) / (q1 + p) if q1 + p > 0 else 0.0
+        q1 += p
+        q2 = 1.0 - q1
+        if min(q1, q2) < 1e-12 or max(q1, q2) > 1.0 - 1e-12:
+            continue
+        mu2 = (mu - q1 * mu1) / q2
+        s = q1 * q2 * (mu1 - mu2) ** 2
+        if s > best:
+            best, best_t = s, t
+    return best_t
+
+
 def morph_close(binary, k):
     """cv2.morphologyEx(img, MORPH_CLOSE, ones((k, k))): dilate then erode with the anchor at k//2.  The erosion window
     covers offsets -k//2 .. k-k//2-1; OpenCV's dilation reflects kernel and anchor (offsets -(k-k//2-1) .. k//2), which keeps
@@ -107,6 +127,163 @@ def points_polygon_test(contour, pts, chunk=512):
 
 def point_polygon_test(contour, pt):
     return int(points_polygon_test(contour, [pt])[0])
+
+
+def points_polygon_test_int(contour, pts, chunk=512):
+    """`points_polygon_test` for integer input in exact int64 arithmetic -- the arithmetic of the device kernel (csrc/tissue.hip), restated in
+    numpy.  One cross product per edge decides both questions: zero inside the edge's box is "on the edge"; for an edge with exactly one end
+    at y <= py, the float test px < x1 + (py - y1) * (x2 - x1) / dy is (px - x1) * dy < (py - y1) * (x2 - x1) for dy > 0 and > for dy < 0, i.e.
+    the sign of the cross product against the sign of dy.  The two sides are integers: equal means on the edge (where `on` decides), otherwise the
+    float sides differ by at least 1 / |dy|, far beyond float64 rounding -- so this returns what `points_polygon_test` returns."""
+    c = np.asarray(contour, np.int64).reshape(-1, 2)
+    pts = np.asarray(pts, np.int64).reshape(-1, 2)
+    out = np.full(len(pts), -1, np.int64)
+    if len(c) == 0:
+        return out
+    x1, y1 = c[:, 0][None, :], c[:, 1][None, :]
+    x2, y2 = np.roll(x1, -1, 1), np.roll(y1, -1, 1)
+    dx, dy = x2 - x1, y2 - y1
+    for i in range(0, len(pts), chunk):
+        px, py = pts[i:i + chunk, 0][:, None], pts[i:i + chunk, 1][:, None]
+        cross = dx * (py - y1) - dy * (px - x1)
+        on = (cross == 0) & (np.minimum(x1, x2) <= px) & (px <= np.maximum(x1, x2)) & (np.minimum(y1, y2) <= py) & (py <= np.maximum(y1, y2))
+        straddle = (y1 <= py) != (y2 <= py)
+        left = np.where(dy > 0, cross > 0, cross < 0)
+        inside = (np.count_nonzero(straddle & left, axis=1) & 1).astype(bool)
+        out[i:i + chunk] = np.where(on.any(1), 0, np.where(inside, 1, -1))
+    return out
+
+
+# ----------------------------------------------------------------------------- device route (csrc/tissue.hip)
+_COORD_LIMIT = 1 << 30          # the kernels are exact while differences fit 32 bits
+
+
+def _device_index(device):
+    """`device` (int, 'cuda:N' or torch.device) -> its index.  There is no fallback: without a GPU the device route is an error."""
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError('the device route of tissue segmentation needs a GPU (none is visible); device=None is the host route')
+    if isinstance(device, (int, np.integer)):
+        return int(device)
+    return torch.device(device).index or 0
+
+
+def _int32_coords(a, what):
+    a = np.asarray(a)
+    if a.dtype.kind not in 'iu':
+        raise TypeError(f'{what}: integer coordinates expected, got {a.dtype}')
+    a = a.astype(np.int64).reshape(-1, 2)
+    if len(a) and np.abs(a).max() > _COORD_LIMIT:
+        raise ValueError(f'{what}: coordinates beyond +-2^30')
+    return np.ascontiguousarray(a, np.int32)
+
+
+def _dev_call(device, fn):
+    """Runs fn(torch device, upload, stream pointer) with `device` current; upload(ndarray) -> tensor on it."""
+    import ctypes
+    import torch
+    dev = torch.device('cuda', _device_index(device))
+    with torch.cuda.device(dev):
+        return fn(dev, lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+
+
+def tissue_mask_device(img, sthresh=8, sthresh_up=255, mthresh=7, close=4, use_otsu=False, device=0, planes=False):
+    """`segment_tissue` up to the binary image its contours are found on, on the GPU (nuhtc_tissue_mask): saturation_u8 -> median_blur ->
+    threshold -> morph_close, each byte for byte the host function.  img: (H, W, C >= 3) uint8, channels past the third ignored.  With
+    Otsu the device counts the median plane, the host runs `otsu_threshold_hist`, and a second launch thresholds and closes.
+    Returns the (H, W) uint8 binary image; with `planes` a dict(binary, sat, med, hist, thr) for the tests."""
+    import ctypes
+    import torch
+    from . import hip
+    img = np.asarray(img)
+    if img.ndim != 3 or img.shape[2] < 3 or img.dtype != np.uint8:
+        raise ValueError(f'an (H, W, C >= 3) uint8 image expected, got {img.shape} {img.dtype}')
+    H, W, C = img.shape
+    lib = hip.load()
+
+    def run(dev, up, stream):
+        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        d_img = up(img)
+        new = lambda: torch.empty((H, W), dtype=torch.uint8, device=dev)
+        d_bin, d_med, d_sat = new(), new() if planes or use_otsu else None, new() if planes else None
+        d_hist = torch.empty(256, dtype=torch.int64, device=dev)
+        call = lambda stage, thr: lib.nuhtc_tissue_mask(dev.index, vp(d_img), H, W, W * C, C, stage, int(mthresh), int(thr), int(sthresh_up), int(close),
+                                                        vp(d_bin), vp(d_sat), vp(d_med), vp(d_hist), stream)
+        thr = sthresh
+        if use_otsu:
+            rc = call(hip.TISSUE_MEDIAN, 0)
+            if rc == 0:
+                thr = otsu_threshold_hist(d_hist.cpu().numpy())
+                rc = call(hip.TISSUE_THRESHOLD, thr)
+        else:
+            rc = call(hip.TISSUE_ALL, thr)
+        if rc:
+            raise RuntimeError(f'nuhtc_tissue_mask failed ({rc})')
+        binary = d_bin.cpu().numpy()
+        if not planes:
+            return binary
+        return dict(binary=binary, sat=d_sat.cpu().numpy(), med=d_med.cpu().numpy(), hist=d_hist.cpu().numpy(), thr=thr)
+    return _dev_call(device, run)
+
+
+def points_polygon_test_device(contour, pts, device=0):
+    """`points_polygon_test` of integer points against an integer contour on the GPU (nuhtc_points_polygon_test) -> int64 +1 / 0 / -1."""
+    import ctypes
+    import torch
+    from . import hip
+    c, p = _int32_coords(contour, 'contour'), _int32_coords(pts, 'pts')
+    if len(c) == 0:
+        return np.full(len(p), -1, np.int64)
+    if len(p) == 0:
+        return np.zeros(0, np.int64)
+    lib = hip.load()
+
+    def run(dev, up, stream):
+        d_c, d_p = up(c), up(p)
+        out = torch.empty(len(p), dtype=torch.int8, device=dev)
+        rc = lib.nuhtc_points_polygon_test(dev.index, ctypes.c_void_p(d_c.data_ptr()), len(c), ctypes.c_void_p(d_p.data_ptr()), len(p),
+                                           ctypes.c_void_p(out.data_ptr()), stream)
+        if rc:
+            raise RuntimeError(f'nuhtc_points_polygon_test failed ({rc})')
+        return out.cpu().numpy().astype(np.int64)
+    return _dev_call(device, run)
+
+
+def grid_in_contour_device(contour, holes, start_xy, n_xy, step_size, patch_size, contour_fn='four_pt', device=0):
+    """`in_contour(...) & ~in_holes(...)` over the grid start + (ix, iy) * step of one contour, on the GPU (nuhtc_grid_in_contour): bool
+    (nx * ny,) in the meshgrid(indexing='ij') order of `contour_coords`.  No candidate list is uploaded.  An odd patch size makes the hole
+    test's patch_size / 2 a half-integer: every coordinate is then doubled, which keeps the arithmetic integer and the answers the same."""
+    import ctypes
+    import torch
+    from . import hip
+    nx, ny = int(n_xy[0]), int(n_xy[1])
+    if nx * ny == 0:
+        return np.zeros(0, bool)
+    m = 2 if patch_size % 2 else 1
+    c = None if contour is None else _int32_coords(np.asarray(contour).astype(np.int64) * m, 'contour')
+    hs = [_int32_coords(np.asarray(h).astype(np.int64) * m, 'hole') for h in (holes or [])]
+    hs = [h for h in hs if len(h)]                       # (an empty hole contains no point)
+    offs = np.asarray(_check_offsets(patch_size, contour_fn), np.int32).reshape(-1, 2) * m
+    hole_off = np.zeros(len(hs) + 1, np.int64)
+    hole_off[1:] = np.cumsum([len(h) for h in hs])
+    lib = hip.load()
+
+    def run(dev, up, stream):
+        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        if c is not None and len(c) == 0:                # an empty contour contains no point (points_polygon_test: all -1)
+            return np.zeros(nx * ny, bool)
+        d_c = up(c) if c is not None else None
+        d_h = up(np.concatenate(hs, 0)) if hs else None
+        keep = torch.empty(nx * ny, dtype=torch.uint8, device=dev)
+        centre = int(patch_size) * m // 2                # patch_size / 2 in the (doubled) coordinates
+        rc = lib.nuhtc_grid_in_contour(dev.index, int(start_xy[0]) * m, int(start_xy[1]) * m, nx, ny, int(step_size) * m,
+                                       offs.ctypes.data_as(ctypes.c_void_p), len(offs), 1 if contour_fn == 'four_pt_hard' else 0,
+                                       vp(d_c), 0 if c is None else len(c), vp(d_h), int(hole_off[-1]), hole_off.ctypes.data_as(ctypes.c_void_p), len(hs),
+                                       centre, centre, vp(keep), stream)
+        if rc:
+            raise RuntimeError(f'nuhtc_grid_in_contour failed ({rc})')
+        return keep.cpu().numpy().astype(bool)
+    return _dev_call(device, run)
 
 
 def find_contours_ccomp(binary):
@@ -210,13 +387,14 @@ def _trace_all(mask):
 
 # ----------------------------------------------------------------------------- segmentTissue
 def segment_tissue(image, scale=64, sthresh=8, sthresh_up=255, mthresh=7, close=4, use_otsu=False, filter_params=None,
-                   ref_patch_size=512, exclude_ids=(), keep_ids=(), level_image=None):
+                   ref_patch_size=512, exclude_ids=(), keep_ids=(), level_image=None, device=None):
     """`WholeSlideImage.segmentTissue` on an RGB array.  `scale`: downsample factor of the segmentation level (the reference
     picks the pyramid level closest to 64x).  Returns (contours_tissue, holes_tissue) in level-0 pixels: lists of (n,2) int32
     contours and, per contour, a list of hole contours.
     `level_image`: the segmentation level of a pyramid slide as the reference reads it (`read_region((0, 0), seg_level, level_dim)`, :159);
     `scale` is then that level's (x, y) downsample pair (`_assertLevelDownsamples`, :378-386): the area thresholds use scale[0] (:176) and
-    the contours go back to level 0 by `cont * scale` truncated to int32 (`scaleContourDim`, :371)."""
+    the contours go back to level 0 by `cont * scale` truncated to int32 (`scaleContourDim`, :371).
+    `device`: a GPU (index, 'cuda:N' or torch.device) computes the binary image (`tissue_mask_device`, byte-equal); None = the host code."""
     fp = dict(FILTER_PARAMS if filter_params is None else filter_params)
     if level_image is not None:
         scale = np.asarray(scale, np.float64).reshape(-1)
@@ -227,12 +405,15 @@ def segment_tissue(image, scale=64, sthresh=8, sthresh_up=255, mthresh=7, close=
         scale = int(scale)
         img = np.asarray(image[::scale, ::scale])          # (sliced first: a TIFF slide serves this from its pyramid, nuhtc_amd.tiffslide)
         ref_scale = scale
-    sat = saturation_u8(img)
-    med = median_blur(sat, mthresh)
-    thr = otsu_threshold(med) if use_otsu else sthresh
-    binary = np.where(med > thr, np.uint8(min(sthresh_up, 255)), np.uint8(0))
-    if close > 0:
-        binary = morph_close(binary, close)
+    if device is not None:
+        binary = tissue_mask_device(img, sthresh, sthresh_up, mthresh, close, use_otsu, device)
+    else:
+        sat = saturation_u8(img)
+        med = median_blur(sat, mthresh)
+        thr = otsu_threshold(med) if use_otsu else sthresh
+        binary = np.where(med > thr, np.uint8(min(sthresh_up, 255)), np.uint8(0))
+        if close > 0:
+            binary = morph_close(binary, close)
     scaled_ref = round(ref_patch_size / ref_scale)
     a_t, a_h = fp['a_t'] * scaled_ref, fp['a_h'] * scaled_ref
     fore, holes = [], []
@@ -280,8 +461,9 @@ def in_holes(holes, pts, patch_size):
 
 
 def contour_coords(contour, holes, image_wh, patch_size=256, step_size=256, contour_fn='four_pt', use_padding=True,
-                   top_left=None, bot_right=None):
-    """`process_contour` (:407-493) at patch_level 0: (n,2) int64 level-0 (x, y) tile origins of one tissue contour."""
+                   top_left=None, bot_right=None, device=None):
+    """`process_contour` (:407-493) at patch_level 0: (n,2) int64 level-0 (x, y) tile origins of one tissue contour.
+    `device`: a GPU evaluates the grid's contour and hole tests (`grid_in_contour_device`, the same answers); None = the host code."""
     if contour_fn not in ('basic', 'center', 'four_pt', 'four_pt_hard'):
         raise NotImplementedError(contour_fn)
     img_w, img_h = image_wh
@@ -300,20 +482,24 @@ def contour_coords(contour, holes, image_wh, patch_size=256, step_size=256, cont
     ys = np.arange(start_y, stop_y, step=step_size)
     gx, gy = np.meshgrid(xs, ys, indexing='ij')
     cand = np.stack([gx.reshape(-1), gy.reshape(-1)], 1)
-    ok = np.ones(len(cand), bool) if contour is None else in_contour(contour, cand, patch_size, contour_fn)
-    ok &= ~in_holes(holes or [], cand, patch_size)
+    if device is not None:
+        ok = grid_in_contour_device(contour, holes, (start_x, start_y), (len(xs), len(ys)), step_size, patch_size, contour_fn, device)
+    else:
+        ok = np.ones(len(cand), bool) if contour is None else in_contour(contour, cand, patch_size, contour_fn)
+        ok &= ~in_holes(holes or [], cand, patch_size)
     keep = cand[ok].astype(np.int64)
     # the reference stores a contour's coordinates only when it yields more than one (`if len(results) > 1`, :476)
     return keep if len(keep) > 1 else np.zeros((0, 2), np.int64)
 
 
 def tissue_tile_coords(image, patch_size=256, step_size=256, scale=64, seg_params=None, filter_params=None,
-                       contour_fn='four_pt', use_padding=True):
-    """segmentTissue + process_contours: tile origins over all tissue contours, in contour order (the .h5 `coords`)."""
+                       contour_fn='four_pt', use_padding=True, device=None):
+    """segmentTissue + process_contours: tile origins over all tissue contours, in contour order (the .h5 `coords`).
+    `device`: passed to `segment_tissue` and `contour_coords` (None = the host code)."""
     sp = dict(SEG_PARAMS if seg_params is None else seg_params)
-    conts, holes = segment_tissue(image, scale=scale, filter_params=filter_params, **sp)
+    conts, holes = segment_tissue(image, scale=scale, filter_params=filter_params, device=device, **sp)
     H, W = image.shape[:2]
-    parts = [contour_coords(c, h, (W, H), patch_size, step_size, contour_fn, use_padding) for c, h in zip(conts, holes)]
+    parts = [contour_coords(c, h, (W, H), patch_size, step_size, contour_fn, use_padding, device=device) for c, h in zip(conts, holes)]
     coords = np.concatenate(parts, 0) if parts else np.zeros((0, 2), np.int64)
     return coords, conts, holes
 

@@ -70,6 +70,8 @@ def build_parser():
     p.add_argument('--gpus', type=int, default=1, help='one rank per GPU: the tool starts itself N times under torch.distributed.run (a child process) unless a launcher already did')
     p.add_argument('--merge', action='store_true', help='also run the cross-tile merge (tools/nuclei_merge.py) on rank 0 -> <id>_merged.geojson')
     p.add_argument('--overlap_threshold', type=float, default=0.05)
+    p.add_argument('--seg-on', choices=('host', 'gpu'), default='host', dest='seg_on',
+                   help="where --seg / --patch compute the tissue mask and select the tiles: 'host' (numpy / scipy) or 'gpu' (rank 0's own device; same files)")
     return p
 
 
@@ -197,6 +199,8 @@ def main(argv=None):
     import torch
     from nuhtc_amd import parallel, slides, tilestore
     from nuhtc_amd.apis import init_detector
+    if args.seg_on == 'gpu' and not torch.cuda.is_available():
+        raise SystemExit('--seg-on gpu: no GPU is visible (there is no fallback; --seg-on host is the host route)')
     # the process group is formed AFTER seg_and_patch: rank 0's host phase (segmentation, masks, patching, stitching of every slide of the
     # folder) has no time bound, and a rank waiting in an RCCL barrier is aborted by the watchdog after 10 minutes
     rank, local_rank, world = parallel.env_ranks()
@@ -249,7 +253,8 @@ def main(argv=None):
                                  patch_size=args.patch_size, step_size=args.step_size, seg=args.seg, use_default_params=False,
                                  save_mask=True, stitch=args.stitch, patch_level=args.patch_level, patch=args.patch or single,
                                  process_list=process_list, no_auto_skip=args.no_auto_skip or (single and args.coords is None),
-                                 slides=names, seg_downsample=args.seg_downsample)
+                                 slides=names, seg_downsample=args.seg_downsample, seg_on=args.seg_on,
+                                 device=local_rank if world > 1 else (torch.device(args.device).index or 0))
         parallel.host_phase_done(args.save_dir, rank, world)      # the other ranks poll a marker file (no collective, no timeout)
         for entry in slides.slide_list(args.save_dir):        # Dataset_All_Bags over process_list_autogen.csv (:437-439)
             slide_id = entry.split(ext)[0] if ext else entry
