@@ -49,6 +49,8 @@ struct EngineError {
   } while (0)
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// did the kernel launches since the last check go through?  (a launcher ends with `return launched() ? 0 : NUHTC_E_HIP;`)
+static inline bool launched() { return hipGetLastError() == hipSuccess; }
 
 // Temporary device memory of one host call (the op entry points, nuhtc_merge_overlap): everything it hands out is freed when it goes
 // out of scope.  A failed allocation or upload returns null and clears ok(), so a caller may check once after a run of them.
@@ -93,6 +95,12 @@ struct ProfScope {
 bool prof_enabled();
 int dev_knob(const char* name, int dflt);   // development switch NUHTC_<name> (environment, or nuhtc_dev_knob at run time)
 int& dev_knob_ref(const char* name, int dflt);   // the same, as a reference launch code looks up once and reads on every launch
+// dev: ablation of a step (tools/dev/r04_ablate.py): a launcher returns 0 without launching when NUHTC_SKIP has `bit`; one lookup per site
+#define DEV_SKIP(bit)                                    \
+  do {                                                   \
+    static const int& skip_ = dev_knob_ref("SKIP", 0);   \
+    if (skip_ & (bit)) return 0;                         \
+  } while (0)
 
 // ----------------------------------------------------------------------------- GEMM (gemm.hip)
 // C[row_map(m), n] = epilogue( sum_k A(m,k) * W[n,k] )      fp32 in / fp32 accumulate on v_mfma_f32_32x32x2_f32

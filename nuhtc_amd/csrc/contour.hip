@@ -17,7 +17,8 @@
 // for a run start (set pixel, clear west neighbour) the walk did not visit.  None (one blob, no hole: the usual nucleus) ->
 // done.  Otherwise the wave floods the background that is 4-connected to the image frame (bit-parallel, run filling by carry
 // propagation), and every further run start whose west neighbour lies in that region and was not visited starts another
-// top-level border, walked the same way; the last one walked is the answer.
+// top-level border, walked the same way; the last one walked is the answer.  (Wave reductions: block_prims.h.)
+#include "block_prims.h"
 #include "common.h"
 
 struct ContourParams {
@@ -67,12 +68,8 @@ __global__ __launch_bounds__(64 * CT_WAVES) void contour_kernel(ContourParams p,
       first = min(first, i); wy0 = min(wy0, y); wy1 = max(wy1, y); wx0 = min(wx0, x); wx1 = max(wx1, x);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    first = min(first, __shfl_xor(first, o));
-    wy0 = min(wy0, __shfl_xor(wy0, o)); wy1 = max(wy1, __shfl_xor(wy1, o));
-    wx0 = min(wx0, __shfl_xor(wx0, o)); wx1 = max(wx1, __shfl_xor(wx1, o));
-  }
+  first = wave_min(first);
+  wy0 = wave_min(wy0); wy1 = wave_max(wy1); wx0 = wave_min(wx0); wx1 = wave_max(wx1);
   if (first == 0x7fffffff) {          // empty mask
     if (lane == 0) p.n[det] = 0;
     return;
@@ -130,9 +127,7 @@ __global__ __launch_bounds__(64 * CT_WAVES) void contour_kernel(ContourParams p,
       if (need_outer) c &= (O[i] << 1) | (xw > wx0 ? O[i - 1] >> 31 : 1u);
       if (c) best = min(best, y * W + xw * 32 + __ffs(c) - 1);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o));
-    return best;
+    return wave_min(best);
   };
 
   int nout = 0;
@@ -190,7 +185,7 @@ int launch_contours(const uint32_t* masks, const uint8_t* keep, const int32_t* c
   }
   ProfScope ps("contours", 0, 0, s);
   hipLaunchKernelGGL(contour_kernel, dim3(cdiv(total, CT_WAVES)), dim3(64 * CT_WAVES), lds, s, p, total);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 // ----------------------------------------------------------------------------- export of the kept detections
@@ -256,7 +251,7 @@ int launch_export_kept(const ExportParams& p, int32_t* pos_scratch, hipStream_t 
   ProfScope ps("export", 0, 0, s);
   hipLaunchKernelGGL(export_scan_kernel, dim3(1), dim3(1024), 0, s, p, pos_scratch);
   hipLaunchKernelGGL(export_copy_kernel, dim3(cdiv(p.B * p.K, 4)), dim3(256), 0, s, p, pos_scratch);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 
@@ -286,16 +281,12 @@ __global__ __launch_bounds__(256) void crop_bounds_kernel(const uint32_t* __rest
       atomicOr(&colw[wave][t - y * wpr], w);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    ymin = min(ymin, __shfl_xor(ymin, o)); ymax = max(ymax, __shfl_xor(ymax, o)); pc += __shfl_xor(pc, o);
-  }
+  ymin = wave_min(ymin); ymax = wave_max(ymax); pc = wave_sum(pc);
   // first / last set column: lane j looks at column word j (DS operations of a wave complete in order: the atomics above are done)
   const unsigned cw = lane < wpr ? colw[wave][lane] : 0u;
   int xmin = cw ? lane * 32 + __ffs((int)cw) - 1 : 1 << 30;
   int xmax = cw ? lane * 32 + 31 - __clz((int)cw) : -1;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { xmin = min(xmin, __shfl_xor(xmin, o)); xmax = max(xmax, __shfl_xor(xmax, o)); }
+  xmin = wave_min(xmin); xmax = wave_max(xmax);
   if (lane == 0) {
     const bool any = ymax >= 0;
     box[d * 4 + 0] = any ? xmin : 0; box[d * 4 + 1] = any ? ymin : 0; box[d * 4 + 2] = any ? xmax + 1 : 0; box[d * 4 + 3] = any ? ymax + 1 : 0;
@@ -351,5 +342,5 @@ int launch_export_crops(const uint32_t* words, const int32_t* n_dev, int cap, in
   hipLaunchKernelGGL(crop_bounds_kernel, dim3(cdiv(cap, 4)), dim3(256), 0, s, words, n_dev, cap, H, wpr, box, area, size_scratch);
   hipLaunchKernelGGL(crop_scan_kernel, dim3(1), dim3(1024), 0, s, size_scratch, cap, off);
   hipLaunchKernelGGL(crop_write_kernel, dim3(cdiv(cap, 4)), dim3(256), 0, s, words, n_dev, cap, H, wpr, box, off, pool, pool_cap);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }

@@ -509,7 +509,7 @@ int launch_conv3_split(const GemmParams& g, hipStream_t s) {
     }
   }
 #endif
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 const char* nuhtc_tu_probe_conv() {

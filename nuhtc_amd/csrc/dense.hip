@@ -47,7 +47,7 @@ int launch_sem_fuse(const float* g0, const float* g1, const float* g2, const flo
   ProfScope ps("sem_fuse", 0, 4.0 * 64 * B * H * W * 2.33, s);
   long long total = (long long)B * H * W * 16;
   hipLaunchKernelGGL(sem_fuse_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, g0, g1, g2, g3, out, B, H, W);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 // y[row] = act(dot(x[row, 0:64], w) + b);  one 16-lane group per row (float4 per lane), 4 rows per wave.  Grid-stride over the
@@ -78,7 +78,7 @@ int launch_conv1x1_n1(const float* x, const float* w, const float* b, float* y, 
   if (rows <= 0) return 0;
   hipLaunchKernelGGL(conv1x1_n1_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, x, w, b, y, (long long)rows,
                      (const int*)nullptr, 1, 0);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 int launch_conv1x1_n1_dev(const float* x, const float* w, const float* b, float* y, int rows_cap, const int* rows_dev, int rows_mul,
@@ -88,7 +88,7 @@ int launch_conv1x1_n1_dev(const float* x, const float* w, const float* b, float*
   const long long nb = (threads + 255) / 256;
   hipLaunchKernelGGL(conv1x1_n1_kernel, dim3((unsigned)(nb < 8192 ? nb : 8192)), dim3(256), 0, s, x, w, b, y, (long long)rows_cap,
                      rows_dev, rows_mul, sigmoid);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 // inv[row] = 1 / max(||x_row||_2, 1e-8)   (torch cosine_similarity eps), C = 64, 16 lanes per row
@@ -108,7 +108,7 @@ int launch_rownorm_inv(const float* x, float* inv, int rows, int C, hipStream_t 
   if (C != 64) return NUHTC_E_INVALID;
   long long threads = (long long)rows * 16;
   hipLaunchKernelGGL(rownorm_inv_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, x, inv, (long long)rows);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 // y[b][c][r] = x[b][r][c]   (rows x cols -> cols x rows), 32x32 LDS tiles
@@ -131,5 +131,5 @@ __global__ void transpose_kernel(const float* __restrict__ x, float* __restrict_
 
 int launch_transpose(const float* x, float* y, int batch, int rows, int cols, hipStream_t s) {
   hipLaunchKernelGGL(transpose_kernel, dim3(cdiv(cols, 32), cdiv(rows, 32), batch), dim3(256), 0, s, x, y, rows, cols);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }

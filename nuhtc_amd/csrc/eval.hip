@@ -16,7 +16,8 @@
 //                        table of (true id, pred id) -> pixels per (tile, table), emitted as non-zero entries.
 //
 // Every index a kernel reads from device memory (counts, selections, map values) is range-checked before it is used as an address;
-// output lists are written below their capacity only and the needed size is counted past it.
+// output lists are written below their capacity only and the needed size is counted past it (emit_nonempty).  The sort, its total-order
+// score key and the wave reductions come from block_prims.h, the mask-pair verdict and the greedy pass from maskbits.h.
 #include "engine.h"
 #include "maskbits.h"
 
@@ -36,12 +37,6 @@ struct SelectParams {
   int* sel; int* nsel; int* sel_labels;
 };
 
-// float -> unsigned with the same order
-__device__ __forceinline__ unsigned order_bits(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 __global__ __launch_bounds__(ES_NT) void eval_select_kernel(SelectParams p) {
   __shared__ unsigned long long okey[EV_MAXK];
   __shared__ short4 sbb[EV_MAXK];            // rows [x, y) and word columns [z, w) that hold the set bits of the candidate
@@ -59,13 +54,13 @@ __global__ __launch_bounds__(ES_NT) void eval_select_kernel(SelectParams p) {
   const unsigned* masks = p.masks + (long long)b * K * words;
   if (tid == 0) s_m = 0;
   __syncthreads();
-  int npad = 2; while (npad < n) npad <<= 1;
+  const int npad = next_pow2(max(n, 2));
   for (int j = tid; j < npad; j += ES_NT) {
     unsigned long long key = ~0ull;
     if (j < n) {
       const float sc = scores[(long long)j * p.score_stride];
       if (sc >= p.fg_thr) {          // (false for NaN)
-        key = ((unsigned long long)(~order_bits(sc)) << 32) | (unsigned)(0xFFFF - j);
+        key = ((unsigned long long)desc_key_total(sc) << 32) | (unsigned)(0xFFFF - j);      // (scores come in unchecked: any sign)
         atomicAdd(&s_m, 1);
       }
     }
@@ -88,12 +83,8 @@ __global__ __launch_bounds__(ES_NT) void eval_select_kernel(SelectParams p) {
         y0 = min(y0, y); y1 = max(y1, y + 1); x0 = min(x0, x); x1 = max(x1, x + 1);
       }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      cnt += __shfl_xor(cnt, o);
-      y0 = min(y0, __shfl_xor(y0, o)); y1 = max(y1, __shfl_xor(y1, o));
-      x0 = min(x0, __shfl_xor(x0, o)); x1 = max(x1, __shfl_xor(x1, o));
-    }
+    cnt = wave_sum(cnt);
+    y0 = wave_min(y0); y1 = wave_max(y1); x0 = wave_min(x0); x1 = wave_max(x1);
     if (lane == 0) {
       sidx[a] = (short)i;
       sarea[a] = cnt;
@@ -101,26 +92,22 @@ __global__ __launch_bounds__(ES_NT) void eval_select_kernel(SelectParams p) {
     }
   }
   __syncthreads();
-  // greedy pass: the pairs (a, c > a) of a kept candidate a are independent of each other, every wave takes its own c
+  // greedy pass; pre-test: the bounding rows and word columns of the two candidates (disjoint ones still get the verdict on 0 pixels)
+  struct Kept { short4 bb; const unsigned* mi; int area; };
   int nout = 0;                      // (tid 0)
-  for (int a = 0; a < m; ++a) {
-    if (sup[a]) continue;            // uniform: sup[] only changes between barriers
-    if (tid == 0) skept[nout++] = sidx[a];
-    const short4 ba = sbb[a];
-    const unsigned* mi = masks + (long long)sidx[a] * words;
-    for (int c = a + 1 + wave; c < m; c += NWV) {
-      if (sup[c]) continue;
-      const short4 bc = sbb[c];
-      const int y0 = max(ba.x, bc.x), y1 = min(ba.y, bc.y);
-      int cnt = 0;
-      if (y0 < y1 && max(ba.z, bc.z) < min(ba.w, bc.w)) cnt = wave_and_popc(mi, masks + (long long)sidx[c] * words, y0 * wpr, y1 * wpr, lane);
-      if (lane == 0) {
-        const int uni = sarea[a] + sarea[c] - cnt;
-        if ((double)cnt / (double)max(uni, 1) > p.thr) sup[c] = 1;
-      }
-    }
-    __syncthreads();
-  }
+  greedy_mask_pass<ES_NT>(
+      m, sup,
+      [&](int a) {
+        if (tid == 0) skept[nout++] = sidx[a];
+        return Kept{sbb[a], masks + (long long)sidx[a] * words, sarea[a]};
+      },
+      [&](const Kept& k, int c) {
+        const short4 bc = sbb[c];
+        const int y0 = max(k.bb.x, bc.x), y1 = min(k.bb.y, bc.y);
+        if (y0 < y1 && max(k.bb.z, bc.z) < min(k.bb.w, bc.w))
+          return mask_pair_over<true>(k.mi, masks + (long long)sidx[c] * words, y0 * wpr, y1 * wpr, k.area, sarea[c], p.thr, lane);
+        return mask_inter_over<true>(0, k.area, sarea[c], p.thr);
+      });
   if (tid == 0) { s_m = nout; p.nsel[b] = nout; }
   __syncthreads();
   const int kept = s_m;
@@ -129,6 +116,29 @@ __global__ __launch_bounds__(ES_NT) void eval_select_kernel(SelectParams p) {
     p.sel[(long long)b * K + j] = slot;
     if (p.sel_labels) p.sel_labels[(long long)b * K + j] = (slot >= 0 && p.labels) ? p.labels[(long long)b * K + slot] : -1;
   }
+}
+
+// The tail of a kernel that leaves the non-empty ones of its workgroup's `nslots` LDS slots as entries of a global list of `cap`
+// entries: counts them, reserves a range with one atomic on counters[0] (the size the list needs, counted past cap too), writes the
+// entries that lie below cap -- ascending slot index per thread stride -- and flags counters[1] when one did not.  *s_cnt must be 0
+// since a barrier; NT threads; a thread returns from its kernel after this.
+template <int NT, typename NonEmpty, typename Write>
+__device__ __forceinline__ void emit_nonempty(int nslots, int cap, int* counters, int* s_cnt, int* s_base, NonEmpty nonempty, Write write) {
+  const int tid = threadIdx.x;
+  int mine = 0;
+  for (int i = tid; i < nslots; i += NT) mine += nonempty(i);
+  int off = mine ? atomicAdd(s_cnt, mine) : 0;
+  __syncthreads();
+  if (tid == 0) *s_base = *s_cnt ? atomicAdd(&counters[0], *s_cnt) : 0;
+  __syncthreads();
+  if (!mine) return;
+  off += *s_base;
+  for (int i = tid; i < nslots; i += NT)
+    if (nonempty(i)) {
+      if (off < cap) write(i, off);
+      else atomicOr(&counters[1], 1);
+      ++off;
+    }
 }
 
 struct PairsParams {
@@ -196,27 +206,12 @@ __global__ __launch_bounds__(256) void eval_pairs_kernel(PairsParams p) {
   if (area) atomicAdd(&s_area, area);
   if (bad) atomicOr(&p.counters[2], 1);
   __syncthreads();
-  int mine = 0;
-  for (int t = tid; t < p.t_cap; t += 256) mine += hist[t] != 0;
-  int off = mine ? atomicAdd(&s_cnt, mine) : 0;
-  __syncthreads();
-  if (tid == 0) {
-    p.area_p[(long long)b * p.K + q] = s_area;
-    s_base = s_cnt ? atomicAdd(&p.counters[0], s_cnt) : 0;
-  }
-  __syncthreads();
-  if (!mine) return;
-  off += s_base;
-  for (int t = tid; t < p.t_cap; t += 256)
-    if (hist[t]) {
-      if (off < p.cap) {
-        int* o = p.trips + (long long)off * 4;
-        o[0] = b; o[1] = t; o[2] = q; o[3] = hist[t];
-      } else {
-        atomicOr(&p.counters[1], 1);
-      }
-      ++off;
-    }
+  if (tid == 0) p.area_p[(long long)b * p.K + q] = s_area;
+  emit_nonempty<256>(p.t_cap, p.cap, p.counters, &s_cnt, &s_base, [&](int t) { return hist[t] != 0; },
+                     [&](int t, int off) {
+                       int* o = p.trips + (long long)off * 4;
+                       o[0] = b; o[1] = t; o[2] = q; o[3] = hist[t];
+                     });
 }
 
 struct RenderParams {
@@ -332,27 +327,12 @@ __global__ __launch_bounds__(EJ_NT) void eval_joint_kernel(JointParams p) {
   if (bad) atomicOr(&p.counters[2], 1);
   if (full) atomicOr(&p.counters[1], 1);
   __syncthreads();
-  int mine = 0;
-  for (int i = tid; i < EJ_SLOTS; i += EJ_NT) mine += keys[i] != ~0ull;
-  int off = mine ? atomicAdd(&s_cnt, mine) : 0;
-  __syncthreads();
-  if (tid == 0) s_base = s_cnt ? atomicAdd(&p.counters[0], s_cnt) : 0;
-  __syncthreads();
-  if (!mine) return;
-  off += s_base;
-  for (int i = tid; i < EJ_SLOTS; i += EJ_NT)
-    if (keys[i] != ~0ull) {
-      if (off < p.cap) {
-        int* o = p.joint + (long long)off * 5;
-        o[0] = b; o[1] = k; o[2] = (int)(keys[i] >> 32); o[3] = (int)(keys[i] & 0xFFFFFFFFull); o[4] = cnt[i];
-      } else {
-        atomicOr(&p.counters[1], 1);
-      }
-      ++off;
-    }
+  emit_nonempty<EJ_NT>(EJ_SLOTS, p.cap, p.counters, &s_cnt, &s_base, [&](int i) { return keys[i] != ~0ull; },
+                       [&](int i, int off) {
+                         int* o = p.joint + (long long)off * 5;
+                         o[0] = b; o[1] = k; o[2] = (int)(keys[i] >> 32); o[3] = (int)(keys[i] & 0xFFFFFFFFull); o[4] = cnt[i];
+                       });
 }
-
-bool launched() { return hipGetLastError() == hipSuccess; }
 
 int launch_select(const SelectParams& p, int B, hipStream_t s) {
   ProfScope ps("eval_select", 0, 0, s);

@@ -999,7 +999,7 @@ int launch_gemm(const GemmParams& p, hipStream_t s) {
     }
   }
 #endif
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 const char* nuhtc_tu_probe_gemm() {

@@ -28,11 +28,12 @@
 //      runs out (a pair is handled in the one cell that holds the top-left of the box overlap);
 //   3. rounds of: undecided i becomes dead if a suppressor is alive, alive if all suppressors are dead -- until nothing
 //      changes (chains are short: a handful of rounds).
-// Integer work throughout.
+// Integer work throughout.  (Wave reductions: block_prims.h.)
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
+#include "block_prims.h"
 #include "common.h"
 
 #define MG_CELL 64
@@ -200,22 +201,12 @@ __device__ void mg_flood_frame(const MgImg& g, const uint32_t* in, uint32_t* out
   }
 }
 
-__device__ __forceinline__ int mg_wave_min(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ int mg_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 // raster index (y * 32*wpr + x) of the first set pixel of an LDS bit image, 0x7fffffff if empty
 __device__ int mg_first(const MgImg& g, const uint32_t* b) {
   int best = 0x7fffffff;
   for (int t = g.lane; t < g.words; t += 64)
     if (b[t]) { best = min(best, t * 32 + __ffs(b[t]) - 1); break; }
-  return mg_wave_min(best);
+  return wave_min(best);
 }
 
 __global__ __launch_bounds__(64) void merge_prepare_kernel(MergeArgs a) {
@@ -321,7 +312,7 @@ __global__ __launch_bounds__(64) void merge_prepare_kernel(MergeArgs a) {
     LR[t] = lr; LD[t] = ld; REM[t] = rc; K[t] = 0; Kb[t] = 0;
     ncell += __popc(rc);
   }
-  ncell = mg_wave_sum(ncell);
+  ncell = wave_sum(ncell);
   MG_SYNC();
   // ---- 4. parts of the region that hang together through sides; keep the largest (area in quarter cells: 4 / 2 per cell)
   int best_area = -1;
@@ -361,8 +352,8 @@ __global__ __launch_bounds__(64) void merge_prepare_kernel(MergeArgs a) {
       area += 2 * __popc(k) + 2 * __popc(k & f0 & TR & f1 & BR);
       cnt += __popc(k);
     }
-    area = mg_wave_sum(area);
-    cnt = mg_wave_sum(cnt);
+    area = wave_sum(area);
+    cnt = wave_sum(cnt);
     if (guard == 0 && cnt == ncell) { single = true; best_area = area; break; }     // one part: the usual case
     const bool better = area > best_area;
     for (int t = lane; t < g.words; t += 64) {
@@ -584,6 +575,6 @@ extern "C" int nuhtc_merge_overlap(int device, const int32_t* boxes, const float
     if (!h_flags[0]) break;
   }
   hipLaunchKernelGGL(merge_finish_kernel, dim3(nb), dim3(256), 0, s, a, keep_dev);
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return NUHTC_E_HIP;
+  if (!launched() || hipStreamSynchronize(s) != hipSuccess) return NUHTC_E_HIP;
   return 0;
 }

@@ -65,9 +65,9 @@ int launch_fpn_mean_pool(const PoolLevels& p, int B, double* slab, float* feat, 
   {
     ProfScope ps("fpn_mean_pool", (double)B * px * 64, (double)B * px * 64 * 4 + (double)B * p.choff[4] * 64 * 8, s);
     hipLaunchKernelGGL(fpn_mean_pool_kernel, dim3((unsigned)p.choff[4], (unsigned)B), dim3(256), 0, s, p, slab);
-    if (hipGetLastError() != hipSuccess) return NUHTC_E_HIP;
+    if (!launched()) return NUHTC_E_HIP;
   }
   ProfScope ps("fpn_mean_pool_final", (double)B * p.choff[4] * 64, (double)B * p.choff[4] * 64 * 8 + (double)B * 256 * 4, s);
   hipLaunchKernelGGL(fpn_mean_pool_final_kernel, dim3((unsigned)B), dim3(256), 0, s, p, (const double*)slab, feat);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }

@@ -131,5 +131,5 @@ extern "C" int nuhtc_clock_probe(int device, uint64_t ticks_100mhz, uint64_t* ou
   if (!out_dev || ticks_100mhz == 0 || ticks_100mhz > 1000000000ull) return NUHTC_E_INVALID;
   if (hipSetDevice(device) != hipSuccess) return NUHTC_E_HIP;
   hipLaunchKernelGGL(clock_probe_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned long long)ticks_100mhz, (unsigned long long*)out_dev);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }

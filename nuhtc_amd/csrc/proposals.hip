@@ -9,53 +9,13 @@
 //   cc_*             : "watershed" proposals (nuhtc/models/htc_roi_head_cus.py:283-342) = upsample x4 + 5x5
 //                      Gaussian + >0 + open(5x5,2) + hole fill + 4-connected components in raster order + boxes
 //                      (the watershed call is an identity on these inputs)
+// The sort, its score keys, the block scan and the wave reductions come from block_prims.h; the two NMS routes share
+// group_offsets_and_max, box_overlaps, greedy_chunk64 and emit_det (below).
+#include "block_prims.h"   // (scores here are probabilities: desc_key_nonneg)
 #include "common.h"
 #include "proposals.h"
 
 typedef unsigned long long u64;
-
-__device__ __forceinline__ unsigned f2key(float f) { return __float_as_uint(f); }   // scores are >= 0: uint order == float order
-
-// in-LDS bitonic sort of n (power of two) u64 keys, ascending, by the whole block
-__device__ void bitonic_sort_lds(u64* keys, int n) {
-  for (int k = 2; k <= n; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = threadIdx.x; t < (n >> 1); t += blockDim.x) {
-        int lo = ((t / j) * (j << 1)) + (t % j);   // t -> pair (lo, lo+j)
-        int hi = lo + j;
-        bool asc = ((lo & k) == 0);
-        u64 a = keys[lo], b = keys[hi];
-        if ((a > b) == asc) { keys[lo] = b; keys[hi] = a; }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-__device__ __forceinline__ int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
-
-// block-wide exclusive scan of one int per thread (blockDim.x == 1024), returns exclusive prefix, *total gets the sum
-__device__ int block_exscan_1024(int v, int* lds16, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-  if (lane == 63) lds16[wave] = incl;
-  __syncthreads();
-  if (wave == 0) {
-    int w = lane < 16 ? lds16[lane] : 0;
-    int wi = w;
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) { int t = __shfl_up(wi, o); if (lane >= o) wi += t; }
-    if (lane < 16) lds16[lane] = wi - w;
-    if (lane == 15) lds16[16] = wi;
-  }
-  __syncthreads();
-  int res = lds16[wave] + incl - v;
-  *total = lds16[16];
-  __syncthreads();
-  return res;
-}
 
 // ------------------------------------------------------------------------------------------- RPN per-level selection
 __global__ __launch_bounds__(1024) void rpn_level_kernel(RpnLevels lv, RpnSelParams p) {
@@ -88,10 +48,10 @@ __global__ __launch_bounds__(1024) void rpn_level_kernel(RpnLevels lv, RpnSelPar
 #pragma unroll
       for (int j = 0; j < RPN_KPT; ++j) {
         const int idx = tid + j * 1024;
-        myk[j] = idx < n ? f2key(score_of(idx)) : 0u;
+        myk[j] = idx < n ? __float_as_uint(score_of(idx)) : 0u;      // scores are >= 0: uint order == float order
       }
     } else {
-      for (int idx = tid; idx < n; idx += 1024) kk[idx] = f2key(score_of(idx));
+      for (int idx = tid; idx < n; idx += 1024) kk[idx] = __float_as_uint(score_of(idx));
       __syncthreads();
     }
     // radix select: find key T of rank k (descending) over 32-bit score keys
@@ -195,10 +155,10 @@ __global__ __launch_bounds__(1024) void rpn_level_kernel(RpnLevels lv, RpnSelPar
     }
     __syncthreads();
     nsel = k;       // s_cnt >= k entries were written; the sort leaves the k selected ones in front
-    bitonic_sort_lds(keys, 4096);
+    bitonic_sort_u64<1024>(keys, 4096, tid);
   } else {
     // n <= nms_pre: the reference does not sort (rpn_head.py:167) -> index order
-    for (int i = tid; i < 4096; i += 1024) keys[i] = i < n ? (((u64)(~f2key(score_of(i)))) << 32 | (unsigned)i) : ~0ull;
+    for (int i = tid; i < 4096; i += 1024) keys[i] = i < n ? (((u64)desc_key_nonneg(score_of(i))) << 32 | (unsigned)i) : ~0ull;
     __syncthreads();
     nsel = n;
   }
@@ -249,30 +209,26 @@ __global__ __launch_bounds__(1024) void rpn_level_kernel(RpnLevels lv, RpnSelPar
 }
 
 int launch_rpn_select(const RpnLevels& lv, const RpnSelParams& p, int B, hipStream_t s) {
-  { static const int& skip_ = dev_knob_ref("SKIP", 0); if (skip_ & 128) return 0; }   // dev: ablation of the step (tools/dev/r04_ablate.py)
+  DEV_SKIP(128);
   ProfScope ps("rpn_select", 0, 0, s);
   if (p.nms_pre > 4096 || p.slot < p.nms_pre || !p.keys) return NUHTC_E_INVALID;
   for (int l = 0; l < 4; ++l)
     if (lv.h[l] * lv.w[l] * 3 > p.key_stride) return NUHTC_E_INVALID;
   hipLaunchKernelGGL(rpn_level_kernel, dim3(B, 4), dim3(1024), 0, s, lv, p);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 // ------------------------------------------------------------------------------------------- NMS
-// Gather the per-group slots of image b into one ordered candidate list (group-major), apply the batched_nms
-// coordinate offset (id * (max_coord + 1), float32) and sort by (score desc, position asc).
-__global__ __launch_bounds__(1024) void nms_prepare_kernel(NmsParams p) {
-  extern __shared__ u64 keys[];      // npad_max entries
+// Shared by the plain route (launch_nms) and the level-wise one (launch_nms_levels).
+// goff[g] = position of group g's first candidate in the group-major list of image b, goff[n_groups] = their number; returns the
+// max coordinate over all candidate boxes (boxes.max() of mmcv batched_nms), the same in every thread.  blockDim.x == 1024.
+__device__ __forceinline__ float group_offsets_and_max(const NmsParams& p, int b, int (&goff)[NMS_MAX_GROUPS + 1]) {
   __shared__ float red[16];
   __shared__ float s_max;
-  const int b = blockIdx.x, tid = threadIdx.x;
-  // group offsets
-  int goff[NMS_MAX_GROUPS + 1];
+  const int tid = threadIdx.x;
   goff[0] = 0;
   for (int g = 0; g < p.n_groups; ++g) goff[g + 1] = goff[g] + p.group_count[b * p.n_groups + g];
   const int n = goff[p.n_groups];
-  const int npad = next_pow2(n < 2 ? 2 : n);
-  // max coordinate over all candidate boxes (boxes.max() of mmcv batched_nms)
   float mx = -3.0e38f;
   for (int i = tid; i < n; i += 1024) {
     int g = 0;
@@ -280,25 +236,70 @@ __global__ __launch_bounds__(1024) void nms_prepare_kernel(NmsParams p) {
     const float* bx = p.boxes + ((long long)(b * p.n_groups + g) * p.slot + (i - goff[g])) * 4;
     mx = fmaxf(mx, fmaxf(fmaxf(bx[0], bx[1]), fmaxf(bx[2], bx[3])));
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  mx = wave_max(mx);
   if ((tid & 63) == 0) red[tid >> 6] = mx;
   __syncthreads();
   if (tid == 0) { float m = red[0]; for (int i = 1; i < 16; ++i) m = fmaxf(m, red[i]); s_max = m; }
   __syncthreads();
-  const float maxp1 = s_max + 1.0f;
+  return s_max;
+}
+
+// mmcv nms_cuda's test on two boxes and their areas: intersection, then IoU > thr (float32, separate mul / add steps)
+__device__ __forceinline__ float box_inter(const float4& a, const float4& c) {
+  float left = fmaxf(a.x, c.x), right = fminf(a.z, c.z);
+  float top = fmaxf(a.y, c.y), bottom = fminf(a.w, c.w);
+  float wdt = fmaxf(right - left, 0.f), hgt = fmaxf(bottom - top, 0.f);
+  return wdt * hgt;
+}
+__device__ __forceinline__ bool inter_overlaps(float inter, float area_a, float area_c, float thr) {
+  return inter / (area_a + area_c - inter) > thr;
+}
+__device__ __forceinline__ bool box_overlaps(const float4& a, float area_a, const float4& c, float area_c, float thr) {
+  return inter_overlaps(box_inter(a, c), area_a, area_c, thr);
+}
+
+// greedy pass over the sorted rows of one 64-row chunk by one wave: lane i holds d = row i's suppression word within the chunk,
+// cur = the rows of the chunk removed by earlier chunks; rows_left = rows of the group from this chunk on; at most `room` rows are
+// kept.  Returns the kept rows.  (The clamp to 64 stays next to the loop: it is how the compiler knows the shuffle's source lane.)
+__device__ __forceinline__ u64 greedy_chunk64(u64 d, u64 cur, int room, int rows_left) {
+  u64 keep = 0;
+  const int rows_here = min(64, rows_left);
+  for (int i = 0; i < rows_here; ++i) {
+    u64 di = __shfl(d, i);
+    if (!((cur >> i) & 1ull) && room > 0) { keep |= 1ull << i; cur |= di; --room; }
+  }
+  return keep;
+}
+
+// row k of image b's output: box + score of candidate `src`, and where it came from
+__device__ __forceinline__ void emit_det(const NmsParams& p, int b, int k, int src) {
+  const float* bx = p.boxes + (long long)src * 4;
+  float* o = p.out_dets + ((long long)b * p.max_keep + k) * 5;
+  o[0] = bx[0]; o[1] = bx[1]; o[2] = bx[2]; o[3] = bx[3]; o[4] = p.scores[src];
+  p.out_src[(long long)b * p.max_keep + k] = src;
+}
+
+// Gather the per-group slots of image b into one ordered candidate list (group-major), apply the batched_nms
+// coordinate offset (id * (max_coord + 1), float32) and sort by (score desc, position asc).
+__global__ __launch_bounds__(1024) void nms_prepare_kernel(NmsParams p) {
+  extern __shared__ u64 keys[];      // npad_max entries
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int goff[NMS_MAX_GROUPS + 1];
+  const float maxp1 = group_offsets_and_max(p, b, goff) + 1.0f;
+  const int n = goff[p.n_groups];
+  const int npad = next_pow2(n < 2 ? 2 : n);
   for (int i = tid; i < npad; i += 1024) {
     u64 key = ~0ull;
     if (i < n) {
       int g = 0;
       while (i >= goff[g + 1]) ++g;
       float sc = p.scores[(long long)(b * p.n_groups + g) * p.slot + (i - goff[g])];
-      key = ((u64)(~f2key(sc)) << 32) | (unsigned)i;
+      key = ((u64)desc_key_nonneg(sc) << 32) | (unsigned)i;
     }
     keys[i] = key;
   }
   __syncthreads();
-  bitonic_sort_lds(keys, npad);
+  bitonic_sort_u64<1024>(keys, npad, tid);
   for (int r = tid; r < n; r += 1024) {
     int i = (int)(keys[r] & 0xFFFFFFFFu);
     int g = 0;
@@ -333,13 +334,7 @@ __global__ __launch_bounds__(64) void nms_mask_kernel(NmsParams p) {
   const int start = (rb == cb) ? t + 1 : 0;
   for (int j = start; j < ncol; ++j) {
     const float4 c = cbx[j];
-    float left = fmaxf(a.x, c.x), right = fminf(a.z, c.z);
-    float top = fmaxf(a.y, c.y), bottom = fminf(a.w, c.w);
-    float wdt = fmaxf(right - left, 0.f), hgt = fmaxf(bottom - top, 0.f);
-    float inter = wdt * hgt;
-    float sb2 = (c.z - c.x) * (c.w - c.y);
-    float ovr = inter / (sa + sb2 - inter);
-    if (ovr > p.iou_thr) bits |= 1ull << j;
+    if (box_overlaps(a, sa, c, (c.z - c.x) * (c.w - c.y), p.iou_thr)) bits |= 1ull << j;
   }
   p.mask[((long long)b * p.cap + row) * (p.cap / 64) + cb] = bits;
 }
@@ -363,24 +358,11 @@ __global__ __launch_bounds__(256) void nms_reduce_kernel(NmsParams p) {
     if (tid < 64) {
       const int row = c * 64 + lane;
       u64 d = row < n ? mask[(long long)row * nw + c] : 0ull;   // upper-triangular diagonal word
-      u64 cur = removed[c];
-      u64 keep = 0;
-      int room = p.max_keep - kept_before;
-      const int rows_here = min(64, n - c * 64);
-      for (int i = 0; i < rows_here; ++i) {
-        u64 di = __shfl(d, i);
-        if (!((cur >> i) & 1ull) && room > 0) { keep |= 1ull << i; cur |= di; --room; }
-      }
+      const u64 keep = greedy_chunk64(d, removed[c], p.max_keep - kept_before, n - c * 64);
       if (lane == 0) s_keepbits = keep;
       // emit kept rows in order
-      if ((keep >> lane) & 1ull) {
-        int k = kept_before + __popcll(keep & ((1ull << lane) - 1ull));
-        int src = p.sorted_src[(long long)b * p.cap + row];
-        const float* bx = p.boxes + (long long)src * 4;
-        float* o = p.out_dets + ((long long)b * p.max_keep + k) * 5;
-        o[0] = bx[0]; o[1] = bx[1]; o[2] = bx[2]; o[3] = bx[3]; o[4] = p.scores[src];
-        p.out_src[(long long)b * p.max_keep + k] = src;
-      }
+      if ((keep >> lane) & 1ull)
+        emit_det(p, b, kept_before + __popcll(keep & ((1ull << lane) - 1ull)), p.sorted_src[(long long)b * p.cap + row]);
       if (lane == 0) s_kept = kept_before + __popcll(keep);
     }
     __syncthreads();
@@ -405,14 +387,14 @@ __global__ __launch_bounds__(256) void nms_reduce_kernel(NmsParams p) {
 // rows of `mask` that nms_mask_kernel never writes must read as zero: words cb < rb are unused by the reduce (it only
 // reads words >= its chunk), words beyond n likewise; so no clearing pass is needed.
 int launch_nms(const NmsParams& p, int B, hipStream_t s) {
-  { static const int& skip_ = dev_knob_ref("SKIP", 0); if (skip_ & 128) return 0; }   // dev: ablation of the step (tools/dev/r04_ablate.py)
+  DEV_SKIP(128);
   ProfScope ps("nms", 0, 0, s);
   if (p.cap % 64 || p.cap > NMS_MAX_CAP || p.n_groups > NMS_MAX_GROUPS) return NUHTC_E_INVALID;
   size_t lds = (size_t)p.cap_pow2 * sizeof(u64);
   hipLaunchKernelGGL(nms_prepare_kernel, dim3(B), dim3(1024), lds, s, p);
   hipLaunchKernelGGL(nms_mask_kernel, dim3(p.cap / 64, p.cap / 64, B), dim3(64), 0, s, p);
   hipLaunchKernelGGL(nms_reduce_kernel, dim3(B), dim3(256), 0, s, p);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 // ---- level-wise variant ------------------------------------------------------------------------------------------------
@@ -423,53 +405,38 @@ int launch_nms(const NmsParams& p, int B, hipStream_t s) {
 // (score desc, position asc) order, same first max_keep survivors).
 __global__ __launch_bounds__(1024) void nms_prepare_levels_kernel(NmsParams p) {
   extern __shared__ u64 keys[];      // pow2 >= slot entries: one group per block
-  __shared__ float red[16];
-  __shared__ float s_max;
   const int b = blockIdx.x, g = blockIdx.y, tid = threadIdx.x;
-  int goff[NMS_MAX_GROUPS + 1], astart[NMS_MAX_GROUPS + 1];
-  goff[0] = astart[0] = 0;
+  int goff[NMS_MAX_GROUPS + 1];
+  // the offset takes the max coordinate over the candidate boxes of ALL groups
+  const float off = (float)g * (group_offsets_and_max(p, b, goff) + 1.0f);
+  // rows in the sorted arrays: every group starts on a multiple of 64; this group's first row, and one past the last group's
+  int astart = 0, aend = 0;
   for (int h = 0; h < p.n_groups; ++h) {
-    const int c = p.group_count[b * p.n_groups + h];
-    goff[h + 1] = goff[h] + c;
-    astart[h + 1] = astart[h] + ((c + 63) & ~63);
+    const int rows = (goff[h + 1] - goff[h] + 63) & ~63;
+    if (h < g) astart += rows;
+    aend += rows;
   }
-  const int n = goff[p.n_groups];
-  // max coordinate over the candidate boxes of ALL groups (boxes.max() of mmcv batched_nms)
-  float mx = -3.0e38f;
-  for (int i = tid; i < n; i += 1024) {
-    int h = 0;
-    while (i >= goff[h + 1]) ++h;
-    const float* bx = p.boxes + ((long long)(b * p.n_groups + h) * p.slot + (i - goff[h])) * 4;
-    mx = fmaxf(mx, fmaxf(fmaxf(bx[0], bx[1]), fmaxf(bx[2], bx[3])));
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-  if ((tid & 63) == 0) red[tid >> 6] = mx;
-  __syncthreads();
-  if (tid == 0) { float m = red[0]; for (int i = 1; i < 16; ++i) m = fmaxf(m, red[i]); s_max = m; }
-  __syncthreads();
-  const float off = (float)g * (s_max + 1.0f);
   // this group's candidates by (score desc, position asc)
   const int cnt = goff[g + 1] - goff[g];
   const int npad = next_pow2(cnt < 2 ? 2 : cnt);
   const long long base = (long long)(b * p.n_groups + g) * p.slot;
-  for (int i = tid; i < npad; i += 1024) keys[i] = i < cnt ? (((u64)(~f2key(p.scores[base + i]))) << 32 | (unsigned)i) : ~0ull;
+  for (int i = tid; i < npad; i += 1024) keys[i] = i < cnt ? (((u64)desc_key_nonneg(p.scores[base + i])) << 32 | (unsigned)i) : ~0ull;
   __syncthreads();
-  bitonic_sort_lds(keys, npad);
+  bitonic_sort_u64<1024>(keys, npad, tid);
   for (int r = tid; r < cnt; r += 1024) {
     const int i = (int)(keys[r] & 0xFFFFFFFFu);
     const long long src = base + i;
     const float* bx = p.boxes + src * 4;
-    const long long a = (long long)b * p.cap + astart[g] + r;
+    const long long a = (long long)b * p.cap + astart + r;
     float* sb = p.sorted_boxes + a * 4;
     sb[0] = bx[0] + off; sb[1] = bx[1] + off; sb[2] = bx[2] + off; sb[3] = bx[3] + off;
     p.sorted_src[a] = (int)src;
     p.sorted_pos[a] = goff[g] + i;      // group-major position: the tie-break of the reference's single global sort
   }
   if (tid == 0) {
-    p.seg_start[b * p.n_groups + g] = astart[g];
+    p.seg_start[b * p.n_groups + g] = astart;
     p.seg_n[b * p.n_groups + g] = cnt;
-    if (g == 0) p.n_total[b] = astart[p.n_groups];
+    if (g == 0) p.n_total[b] = aend;
   }
 }
 
@@ -518,14 +485,10 @@ __global__ __launch_bounds__(256) void nms_mask_levels_kernel(NmsParams p) {
   const int start = (rb == cb) ? lane + 1 : 0;
   for (int j = (rb == cb) ? 1 : 0; j < ncol; ++j) {
     const float4 c = cbx[j];
-    float left = fmaxf(a.x, c.x), right = fminf(a.z, c.z);
-    float top = fmaxf(a.y, c.y), bottom = fminf(a.w, c.w);
-    float wdt = fmaxf(right - left, 0.f), hgt = fmaxf(bottom - top, 0.f);
-    float inter = wdt * hgt;
+    const float inter = box_inter(a, c);      // by every lane, ahead of the skip: under `mine` it would be computed twice
     const bool mine = live && j >= start;
     if (__ballot(mine && inter > 0.f) == 0) continue;
-    float ovr = inter / (sa + car[j] - inter);
-    if (mine && ovr > p.iou_thr) bits |= 1ull << j;
+    if (mine && inter_overlaps(inter, sa, car[j], p.iou_thr)) bits |= 1ull << j;
   }
   if (live) p.mask[((long long)b * p.cap + row) * (p.cap / 64) + cb] = bits;
 }
@@ -554,14 +517,7 @@ __global__ __launch_bounds__(256) void nms_reduce_levels_kernel(NmsParams p) {
     if (tid < 64) {
       const int row = start + c * 64 + lane;
       u64 d = c * 64 + lane < n ? mask[(long long)row * nw + c0 + c] : 0ull;
-      u64 cur = removed[c];
-      u64 keep = 0;
-      int room = p.max_keep - kept_before;
-      const int rows_here = min(64, n - c * 64);
-      for (int i = 0; i < rows_here; ++i) {
-        u64 di = __shfl(d, i);
-        if (!((cur >> i) & 1ull) && room > 0) { keep |= 1ull << i; cur |= di; --room; }
-      }
+      const u64 keep = greedy_chunk64(d, removed[c], p.max_keep - kept_before, n - c * 64);
       if ((keep >> lane) & 1ull) klist[__popcll(keep & ((1ull << lane) - 1ull))] = (unsigned char)lane;
       if (lane == 0) { s_nk = __popcll(keep); kb_out[c0 + c] = keep; s_kept = kept_before + __popcll(keep); }
     }
@@ -593,7 +549,7 @@ __global__ __launch_bounds__(1024) void nms_select_kernel(NmsParams p) {
       const long long a = (long long)b * p.cap + idx;
       const float sc = p.scores[p.sorted_src[a]];
       const int k = atomicAdd(&s_n, 1);
-      if (k < 8192) keys[k] = ((u64)(~f2key(sc)) << 32) | ((u64)(unsigned)p.sorted_pos[a] << 16) | (unsigned)idx;
+      if (k < 8192) keys[k] = ((u64)desc_key_nonneg(sc) << 32) | ((u64)(unsigned)p.sorted_pos[a] << 16) | (unsigned)idx;
     }
   }
   __syncthreads();
@@ -601,34 +557,28 @@ __global__ __launch_bounds__(1024) void nms_select_kernel(NmsParams p) {
   const int npad = next_pow2(n < 2 ? 2 : n);
   for (int i = n + tid; i < npad; i += 1024) keys[i] = ~0ull;
   __syncthreads();
-  bitonic_sort_lds(keys, npad);
+  bitonic_sort_u64<1024>(keys, npad, tid);
   const int nout = min(n, p.max_keep);
   for (int k = tid; k < nout; k += 1024) {
     const int idx = (int)(keys[k] & 0xFFFFu);
-    const int src = p.sorted_src[(long long)b * p.cap + idx];
-    const float* bx = p.boxes + (long long)src * 4;
-    float* o = p.out_dets + ((long long)b * p.max_keep + k) * 5;
-    o[0] = bx[0]; o[1] = bx[1]; o[2] = bx[2]; o[3] = bx[3]; o[4] = p.scores[src];
-    p.out_src[(long long)b * p.max_keep + k] = src;
+    emit_det(p, b, k, p.sorted_src[(long long)b * p.cap + idx]);
   }
   if (tid == 0) p.out_counts[b] = nout;
 }
 
 int launch_nms_levels(const NmsParams& p, int B, hipStream_t s) {
-  { static const int& skip_ = dev_knob_ref("SKIP", 0); if (skip_ & 128) return 0; }   // dev: ablation of the step (tools/dev/r04_ablate.py)
+  DEV_SKIP(128);
   ProfScope ps("nms", 0, 0, s);
   if (p.cap % 64 || p.cap > NMS_MAX_CAP + 64 * NMS_MAX_GROUPS || p.cap >= 65536 || p.n_groups > NMS_MAX_GROUPS || p.ids ||
       p.n_groups * p.max_keep > 8192 || !p.seg_start || !p.seg_n || !p.sorted_pos || !p.keepbits)
     return NUHTC_E_INVALID;
-  int slot_pow2 = 2;
-  while (slot_pow2 < p.slot) slot_pow2 <<= 1;
-  size_t lds = (size_t)slot_pow2 * sizeof(u64);
+  size_t lds = (size_t)next_pow2(p.slot < 2 ? 2 : p.slot) * sizeof(u64);
   hipLaunchKernelGGL(nms_prepare_levels_kernel, dim3(B, p.n_groups), dim3(1024), lds, s, p);
   const int slot_chunks = (p.slot + 63) / 64;      // a group holds at most `slot` candidates
   hipLaunchKernelGGL(nms_mask_levels_kernel, dim3(cdiv(p.n_groups * (slot_chunks * (slot_chunks + 1) / 2), 4), 1, B), dim3(256), 0, s, p);
   hipLaunchKernelGGL(nms_reduce_levels_kernel, dim3(B, p.n_groups), dim3(256), 0, s, p);
   hipLaunchKernelGGL(nms_select_kernel, dim3(B), dim3(1024), 0, s, p);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 int nms_set_attributes() {
@@ -912,7 +862,7 @@ __global__ __launch_bounds__(1024) void cc_emit_kernel(const int* __restrict__ s
   const int npad = next_pow2(n < 2 ? 2 : n);
   for (int i = tid; i < npad; i += 1024) keys[i] = i < n ? (u64)(unsigned)list[(long long)b * CC_LIST_CAP + i] : ~0ull;
   __syncthreads();
-  bitonic_sort_lds(keys, npad);
+  bitonic_sort_u64<1024>(keys, npad, tid);
   const int* st = stats + (long long)b * HW * 5;
   for (int i = tid; i < n && i < cap; i += 1024) {
     const int* s = st + (long long)(int)keys[i] * 5;
@@ -938,7 +888,7 @@ int launch_cc_mask(const CcParams& p, int B, hipStream_t s) {
       for (int j = 0; j < 5; ++j) gk.k[i * 5 + j] = k1[i] * k1[j];
   }
   hipLaunchKernelGGL(cc_mask_kernel, dim3(cdiv(W, CCM_TW), cdiv(H, CCM_TH), B), dim3(256), 0, s, p.sem_pred, p.mask_a, p.h, p.w, H, W, gk);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 // binary mask in p.mask_a -> (opening in place when `open`) -> filled mask in p.mask_b, labels, stats, boxes in raster order
@@ -971,11 +921,11 @@ int launch_cc_from_mask(const CcParams& p, int B, bool open, hipStream_t s) {
   if (hipMemsetAsync(p.nlist, 0, sizeof(int) * B, s) != hipSuccess) return NUHTC_E_HIP;
   hipLaunchKernelGGL(cc_collect_kernel, dim3(nb), dim3(256), 0, s, p.labels, p.stats, p.list, p.nlist, HW, p.min_area, total);
   hipLaunchKernelGGL(cc_emit_kernel, dim3(B), dim3(1024), 0, s, p.stats, p.list, p.nlist, p.boxes, p.counts, p.overflow, HW, p.cap);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 int launch_cc_proposals(const CcParams& p, int B, hipStream_t s) {
-  { static const int& skip_ = dev_knob_ref("SKIP", 0); if (skip_ & 128) return 0; }   // dev: ablation of the step (tools/dev/r04_ablate.py)
+  DEV_SKIP(128);
   ProfScope ps("cc_proposals", 0, 0, s);
   int rc = launch_cc_mask(p, B, s);
   return rc ? rc : launch_cc_from_mask(p, B, true, s);

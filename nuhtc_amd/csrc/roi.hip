@@ -13,14 +13,9 @@
 //                        (htc_roi_head_cus.py:2283-2303, seesaw_loss.py:157-175, nuhtc/models/bbox_head.py:12-102)
 //   paste_kernel       : _do_paste_mask / get_seg_masks (fcn_mask_head.py:229-307,344-412) -> bit-packed masks
 //   tile_post_kernel   : tools/infer_wsi.py:510-531,60-84 margin/min-area filter + greedy mask-NMS (popcount IoU)
+// Wave reductions, the sort and the block scan come from block_prims.h, the mask-pair verdict and the greedy pass from maskbits.h.
 #include "roi.h"
 #include "maskbits.h"
-
-__device__ __forceinline__ float wsum64(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // ------------------------------------------------------------------------------------------- attention pooling table
 // G[b, q, c] = mean_p( F[b,p,c] * (relu(cos(F[b,q], F[b,p]) - tau) + tau) ),  F: [B, HW, 64] (NHWC level map)
@@ -30,13 +25,13 @@ __global__ __launch_bounds__(256) void attn_pool_kernel(const float* __restrict_
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float* Fb = F + (long long)b * HW * 64;
   const float qv = Fb[(long long)q * 64 + lane];
-  const float qn = fmaxf(sqrtf(wsum64(qv * qv)), 1e-8f);
+  const float qn = fmaxf(sqrtf(wave_sum(qv * qv)), 1e-8f);
   const float qh = qv / qn;
   float acc = 0.f;
   for (int p = wave; p < HW; p += 4) {
     const float v = Fb[(long long)p * 64 + lane];
-    const float pn = fmaxf(sqrtf(wsum64(v * v)), 1e-8f);
-    const float cs = wsum64(qh * (v / pn));
+    const float pn = fmaxf(sqrtf(wave_sum(v * v)), 1e-8f);
+    const float cs = wave_sum(qh * (v / pn));
     const float sim = fmaxf(cs - tau, 0.f) + tau;
     acc += v * sim;
   }
@@ -61,12 +56,12 @@ __global__ __launch_bounds__(256) void attn_pool_fp16_kernel(const float* __rest
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float* Fb = F + (long long)b * HW * 64;
   const float qv = rh(Fb[(long long)q * 64 + lane]);
-  const float w1 = rh(wsum64(rh(qv * qv)));
+  const float w1 = rh(wave_sum(rh(qv * qv)));
   float acc = 0.f;
   for (int p = wave; p < HW; p += 4) {
     const float v = rh(Fb[(long long)p * 64 + lane]);
-    const float w12 = rh(wsum64(rh(qv * v)));
-    const float w2 = rh(wsum64(rh(v * v)));
+    const float w12 = rh(wave_sum(rh(qv * v)));
+    const float w2 = rh(wave_sum(rh(v * v)));
     const float n12 = rh(sqrtf(fmaxf(rh(w1 * w2), 0.f)));
     const float cs = rh(w12 / n12);
     const float sim = rh(fmaxf(rh(cs - tau), 0.f) + tau);     // (fmaxf drops a NaN cosine -- 0 / 0 -- the way torch's relu does not: see below)
@@ -83,13 +78,13 @@ __global__ __launch_bounds__(256) void attn_pool_fp16_kernel(const float* __rest
 int launch_attn_pool_fp16(const float* F, float* G, int B, int HW, float tau, hipStream_t s) {
   ProfScope ps("attn_pool_fp16", 4.0 * 64 * (double)HW * HW * B, 0, s);
   hipLaunchKernelGGL(attn_pool_fp16_kernel, dim3(HW, B), dim3(256), 0, s, F, G, HW, tau);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 int launch_attn_pool(const float* F, float* G, int B, int HW, float tau, hipStream_t s) {
   ProfScope ps("attn_pool", 4.0 * 64 * (double)HW * HW * B, 0, s);
   hipLaunchKernelGGL(attn_pool_kernel, dim3(HW, B), dim3(256), 0, s, F, G, HW, tau);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 // ------------------------------------------------------------------------------------------- RoI list assembly
@@ -130,7 +125,7 @@ int launch_build_rois(const float* cc_boxes, const int* cc_counts, int cc_cap, c
   if (B > 256) return NUHTC_E_INVALID;
   hipLaunchKernelGGL(build_rois_kernel, dim3(1), dim3(256), 0, s, cc_boxes, cc_counts, cc_cap, rpn_dets, rpn_counts, rpn_cap, fixed, n_fixed,
                      rois, roi_off, roi_cnt, total, B);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 // ------------------------------------------------------------------------------------------- fused RoI features
@@ -704,8 +699,7 @@ __device__ __forceinline__ void bg_accumulate(const float* __restrict__ map, int
       smv[is_y][sidx] = v;
       if (v) { lo = min(lo, e.lo); hi = max(hi, e.hi); }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { lo = min(lo, __shfl_xor(lo, o)); hi = max(hi, __shfl_xor(hi, o)); }
+    lo = wave_min(lo); hi = wave_max(hi);
     if (lane == 0) { tb->blo[wave] = lo; tb->bhi[wave] = hi; }
   }
   __syncthreads();
@@ -1167,7 +1161,7 @@ __global__ __launch_bounds__(256) void roi_feat14_kernel(RoiFeatParams p) {
 
 int launch_roi_feat(const RoiFeatParams& p, int P, int r_cap, hipStream_t s, hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join, hipStream_t side2,
                     hipEvent_t ev_join2) {
-  { static const int& skip_ = dev_knob_ref("SKIP", 0); if (skip_ & 32) return 0; }   // dev: ablation of the step (tools/dev/r04_ablate.py)
+  DEV_SKIP(32);
   ProfScope ps(P == 7 ? "roi_feat7" : "roi_feat14", 0, 0, s);
   if (r_cap <= 0) return 0;
   if (P == 7) {
@@ -1199,7 +1193,7 @@ int launch_roi_feat(const RoiFeatParams& p, int P, int r_cap, hipStream_t s, hip
     if (fork2 && hipStreamWaitEvent(s, ev_join2, 0) != hipSuccess) return NUHTC_E_HIP;
   } else if (P == 14) hipLaunchKernelGGL(roi_feat14_kernel, dim3(r_cap, 7), dim3(256), 0, s, p);
   else return NUHTC_E_INVALID;
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 // stand-alone RoIAlign on an NHWC map (kernel-level parity test of the mmcv semantics)
@@ -1221,7 +1215,7 @@ int launch_roi_align(const float* feat, int N, int H, int W, int C, const float*
   if (C != 64 || r_dev || accumulate) return NUHTC_E_INVALID;
   if (R <= 0) return 0;
   hipLaunchKernelGGL(roi_align_kernel, dim3(cdiv(R, 4)), dim3(256), 0, s, feat, H, W, rois, R, P, scale, sr, out);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 // ------------------------------------------------------------------------------------------- bbox head tail
@@ -1247,7 +1241,7 @@ __global__ __launch_bounds__(256) void bbox_tail_kernel(BboxTailParams p) {
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= *p.r_dev) return;
   const float4 hv = reinterpret_cast<const float4*>(p.h + (long long)r * 256)[lane];
-  const float nrm = sqrtf(wsum64(hv.x * hv.x + hv.y * hv.y + hv.z * hv.z + hv.w * hv.w));
+  const float nrm = sqrtf(wave_sum(hv.x * hv.x + hv.y * hv.y + hv.z * hv.z + hv.w * hv.w));
   const float den = nrm + 1e-6f;
   const float4 xn = make_float4(hv.x / den * 20.f, hv.y / den * 20.f, hv.z / den * 20.f, hv.w / den * 20.f);
   const int nout = p.nc + 2;
@@ -1255,7 +1249,7 @@ __global__ __launch_bounds__(256) void bbox_tail_kernel(BboxTailParams p) {
   for (int n = 0; n < nout + 4; ++n) {
     const float4 w = reinterpret_cast<const float4*>(p.w + (long long)n * 256)[lane];
     const float4 x = n < nout ? xn : hv;
-    float d = wsum64(x.x * w.x + x.y * w.y + x.z * w.z + x.w * w.w) + p.b[n];
+    float d = wave_sum(x.x * w.x + x.y * w.y + x.z * w.z + x.w * w.w) + p.b[n];
     if (lane == n) keep = d;
   }
   if (lane < nout) p.cls[(long long)r * 16 + lane] = keep;
@@ -1277,32 +1271,10 @@ int launch_bbox_tail(const BboxTailParams& p, int r_cap, hipStream_t s) {
   ProfScope ps("bbox_tail", 0, 0, s);
   if (p.nc + 6 > 64) return NUHTC_E_INVALID;
   hipLaunchKernelGGL(bbox_tail_kernel, dim3(cdiv(r_cap, 4)), dim3(256), 0, s, p);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 // ------------------------------------------------------------------------------------------- detection candidates
-__device__ int block_exscan(int v, int* lds, int* total) {   // blockDim.x == 1024
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-  if (lane == 63) lds[wave] = incl;
-  __syncthreads();
-  if (wave == 0) {
-    int w = lane < 16 ? lds[lane] : 0;
-    int wi = w;
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) { int t = __shfl_up(wi, o); if (lane >= o) wi += t; }
-    if (lane < 16) lds[lane] = wi - w;
-    if (lane == 15) lds[16] = wi;
-  }
-  __syncthreads();
-  int res = lds[wave] + incl - v;
-  *total = lds[16];
-  __syncthreads();
-  return res;
-}
-
 __global__ __launch_bounds__(1024) void det_candidates_kernel(DetCandParams p) {
   __shared__ int sc[17];
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -1341,7 +1313,7 @@ __global__ __launch_bounds__(1024) void det_candidates_kernel(DetCandParams p) {
       }
     }
     int tot;
-    int o = block_exscan(cnt, sc, &tot) + written;
+    int o = block_exscan_1024(cnt, sc, &tot) + written;
     if (j < n) {
       for (int c = 0; c < nc; ++c)
         if (sc_c[c] > p.score_thr) {
@@ -1362,7 +1334,7 @@ int launch_det_candidates(const DetCandParams& p, int B, hipStream_t s) {
   ProfScope ps("det_candidates", 0, 0, s);
   if (p.nc + 2 > 16) return NUHTC_E_INVALID;
   hipLaunchKernelGGL(det_candidates_kernel, dim3(B), dim3(1024), 0, s, p);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 // labels of the kept detections + mask-branch RoIs (det boxes back in network pixels), compacted over the batch
@@ -1395,7 +1367,7 @@ __global__ __launch_bounds__(256) void det_finish_kernel(DetFinishParams p) {
 int launch_det_finish(const DetFinishParams& p, hipStream_t s) {
   if (p.B > 256) return NUHTC_E_INVALID;
   hipLaunchKernelGGL(det_finish_kernel, dim3(1), dim3(256), 0, s, p);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 // ------------------------------------------------------------------------------------------- mask paste
@@ -1450,7 +1422,7 @@ __global__ __launch_bounds__(256) void paste_kernel(PasteParams p) {
     out[wi] = bits;
     area += __popc(bits);
   }
-  area = (int)wsum64((float)area);   // exact: counts <= 2^24
+  area = (int)wave_sum((float)area);   // exact: counts <= 2^24
   if ((tid & 63) == 0) atomicAdd(&s_area, area);
   __syncthreads();
   if (tid == 0 && p.areas) p.areas[(long long)b * p.max_keep + j] = s_area;
@@ -1459,7 +1431,7 @@ __global__ __launch_bounds__(256) void paste_kernel(PasteParams p) {
 int launch_paste(const PasteParams& p, int B, hipStream_t s) {
   ProfScope ps("paste", 0, 0, s);
   hipLaunchKernelGGL(paste_kernel, dim3(p.max_keep, B), dim3(256), 0, s, p);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 // ------------------------------------------------------------------------------------------- per-tile filter + mask-NMS
@@ -1481,7 +1453,7 @@ __global__ __launch_bounds__(TP_NT) void tile_post_kernel(TilePostParams p) {
   const int* areas = p.areas + (long long)b * K;
   unsigned char* keep = p.keep + (long long)b * K;
   const int wpr = p.W >> 5, words = p.H * wpr;
-  int npad = 2; while (npad < n) npad <<= 1;
+  const int npad = next_pow2(max(n, 2));
   // class-major position of detection j: (#dets with smaller label) + (#dets with equal label before j)
   for (int j = tid; j < npad; j += TP_NT) {
     unsigned long long key = ~0ull;
@@ -1492,7 +1464,7 @@ __global__ __launch_bounds__(TP_NT) void tile_post_kernel(TilePostParams p) {
       const bool ok = d[0] >= (float)p.margin && d[1] >= (float)p.margin && d[2] <= (float)(p.vW - p.margin) &&
                       d[3] <= (float)(p.vH - p.margin) && areas[j] >= p.min_area;
       // order: score desc, ties by class-major position desc (reverse of a stable ascending argsort)
-      if (ok) key = ((unsigned long long)(~__float_as_uint(d[4])) << 32) | ((unsigned)(0xFFFF - pos) << 16) | (unsigned)j;
+      if (ok) key = ((unsigned long long)desc_key_nonneg(d[4]) << 32) | ((unsigned)(0xFFFF - pos) << 16) | (unsigned)j;
     }
     okey[j] = key;
     sup[j] = 0;
@@ -1540,11 +1512,8 @@ __global__ __launch_bounds__(TP_NT) void tile_post_kernel(TilePostParams p) {
           todo &= todo - 1;
           const int cc = c0 + l;
           const unsigned* mj = masks + (long long)sidx[cc] * words;
-          const int cnt = wave_and_popc(mi, mj, y0 * wpr, y1 * wpr, lane);
-          if (lane == 0) {
-            const int uni = sarea[a] + sarea[cc] - cnt;
-            if (uni > 0 && (double)cnt / (double)uni > p.thr) supb[a][cc >> 6] |= 1ull << (cc & 63);    // (this wave owns row a)
-          }
+          const bool hit = mask_pair_over<false>(mi, mj, y0 * wpr, y1 * wpr, sarea[a], sarea[cc], p.thr, lane);
+          if (lane == 0 && hit) supb[a][cc >> 6] |= 1ull << (cc & 63);    // (this wave owns row a)
         }
       }
     }
@@ -1560,34 +1529,27 @@ __global__ __launch_bounds__(TP_NT) void tile_post_kernel(TilePostParams p) {
     }
     return;
   }
-  // more candidates than the bit matrix holds: for a kept candidate a, the pairs (a, c > a) are independent of each other, so every wave
-  // takes its own c and there is one barrier per kept candidate
-  for (int a = 0; a < m; ++a) {
-    if (sup[a]) continue;   // uniform: sup[] only changes between barriers
-    const int i = sidx[a];
-    if (tid == 0) keep[i] = 1;
-    const float4 di = sbox[a];
-    const unsigned* mi = masks + (long long)i * words;
-    const int y0 = max((int)floorf(di.y) - 1, 0), y1 = min((int)ceilf(di.w) + 1, p.H);   // rows of mask i's hull
-    for (int c = a + 1 + wave; c < m; c += NWV) {
-      if (sup[c]) continue;
-      const float4 dj = sbox[c];
-      const bool ov = fminf(di.z, dj.z) + 2.f > fmaxf(di.x, dj.x) - 2.f && fminf(di.w, dj.w) + 2.f > fmaxf(di.y, dj.y) - 2.f;
-      if (!ov) continue;
-      const unsigned* mj = masks + (long long)sidx[c] * words;
-      const int cnt = wave_and_popc(mi, mj, y0 * wpr, y1 * wpr, lane);
-      if (lane == 0) {
-        const int uni = sarea[a] + sarea[c] - cnt;
-        if (uni > 0 && (double)cnt / (double)uni > p.thr) sup[c] = 1;
-      }
-    }
-    __syncthreads();
-  }
+  // more candidates than the bit matrix holds: the barrier-per-kept-candidate pass, with the same hull pre-test
+  struct Kept { float4 di; const unsigned* mi; int w0, w1, area; };
+  greedy_mask_pass<TP_NT>(
+      m, sup,
+      [&](int a) {
+        const int i = sidx[a];
+        if (tid == 0) keep[i] = 1;
+        const float4 di = sbox[a];
+        const int y0 = max((int)floorf(di.y) - 1, 0), y1 = min((int)ceilf(di.w) + 1, p.H);   // rows of mask i's hull
+        return Kept{di, masks + (long long)i * words, y0 * wpr, y1 * wpr, sarea[a]};
+      },
+      [&](const Kept& k, int c) {
+        const float4 dj = sbox[c];
+        const bool ov = fminf(k.di.z, dj.z) + 2.f > fmaxf(k.di.x, dj.x) - 2.f && fminf(k.di.w, dj.w) + 2.f > fmaxf(k.di.y, dj.y) - 2.f;
+        return ov && mask_pair_over<false>(k.mi, masks + (long long)sidx[c] * words, k.w0, k.w1, k.area, sarea[c], p.thr, lane);
+      });
 }
 
 int launch_tile_post(const TilePostParams& p, int B, hipStream_t s) {
   ProfScope ps("tile_post", 0, 0, s);
   if (p.max_keep > 2048) return NUHTC_E_INVALID;
   hipLaunchKernelGGL(tile_post_kernel, dim3(B), dim3(TP_NT), 0, s, p);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }

@@ -8,9 +8,11 @@
 //   window_attn   : softmax(q·s·kᵀ + relpos_bias + shift_mask)·v per (window, head), N=49, d=32
 //                   (swin.py:79-117); one wave per (window, head), K/V staged in LDS, one query row per lane,
 //                   scores/softmax entirely in registers.
+// Full-wave sums (the LayerNorm kernels) come from block_prims.h; the partial-width ones stay with their register layouts.
 #include <cmath>
 #include <cstdlib>
 
+#include "block_prims.h"
 #include "common.h"
 #include "split_math.h"   // f32x16 / v4f typedefs, the exact bf16 split and its six products
 
@@ -79,7 +81,7 @@ int launch_preproc(const uint8_t* tiles, float* img, int B, int th, int tw, int 
   long long total = (long long)B * Hn * Wn;
   hipLaunchKernelGGL(preproc_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, tiles, img, B, th, tw, Hn, Wn, Hv, Wv,
                      (const int4*)xtab, (const int4*)ytab, swap, nc);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 // ----------------------------------------------------------------------------- patch embed
@@ -157,16 +159,10 @@ int launch_patch_embed_tiles(const uint8_t* tiles, int B, int th, int tw, int Hn
   int nTok = B * (Hn / 4) * (Wn / 4);
   hipLaunchKernelGGL(patch_embed_tiles_kernel, dim3(cdiv(nTok, 32)), dim3(256), 0, s, tiles, th, tw, Hv, Wv, (const int4*)xtab, (const int4*)ytab, swap, nc,
                      w, b, g, beta, tok, nTok, Hn, Wn);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 // ----------------------------------------------------------------------------- LayerNorm (+ row gather)
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 template <int NV>   // NV = ceil(C/256) 16-byte chunks per lane (C % 4 == 0): one row per wave
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const int* __restrict__ src_map,
                                                         const int* __restrict__ dst_map, const float* __restrict__ g,
@@ -278,7 +274,7 @@ static int layernorm_any(const float* x, const int* src_map, const int* dst_map,
   if (rows <= 0) return 0;
   if (C == 96) {
     hipLaunchKernelGGL(layernorm96_kernel, dim3(cdiv(rows, 8 * LN96_R)), dim3(256), 0, s, x, src_map, dst_map, g, b, y, pad_dst, pad_val, rows);
-    return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+    return launched() ? 0 : NUHTC_E_HIP;
   }
   dim3 grid(cdiv(rows, 4)), blk(256);
   if (C % 4 != 0) return NUHTC_E_INVALID;
@@ -287,18 +283,18 @@ static int layernorm_any(const float* x, const int* src_map, const int* dst_map,
   else if (nv <= 2) hipLaunchKernelGGL(layernorm_kernel<2>, grid, blk, 0, s, x, src_map, dst_map, g, b, y, pad_dst, pad_val, rows, C);
   else if (nv <= 3) hipLaunchKernelGGL(layernorm_kernel<3>, grid, blk, 0, s, x, src_map, dst_map, g, b, y, pad_dst, pad_val, rows, C);
   else return NUHTC_E_INVALID;
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 int launch_layernorm(const float* x, const int* src_map, const float* g, const float* b, float* y, int rows, int C, hipStream_t s) {
-  { static const int& skip_ = dev_knob_ref("SKIP", 0); if (skip_ & 2) return 0; }   // dev: ablation of the step (tools/dev/r04_ablate.py)
+  DEV_SKIP(2);
   ProfScope ps("layernorm", 0, 8.0 * rows * C, s);
   return layernorm_any(x, src_map, nullptr, g, b, y, nullptr, nullptr, rows, C, s);
 }
 
 int launch_layernorm_windows(const float* x, const int* src_map, const int* dst_map, const float* g, const float* b, float* y,
                              float* pad_dst, const float* pad_val, int rows, int C, hipStream_t s) {
-  { static const int& skip_ = dev_knob_ref("SKIP", 0); if (skip_ & 2) return 0; }   // dev: ablation of the step (tools/dev/r04_ablate.py)
+  DEV_SKIP(2);
   ProfScope ps("layernorm", 0, 8.0 * rows * C, s);
   if (!src_map || !dst_map || !pad_dst || !pad_val) return NUHTC_E_INVALID;
   return layernorm_any(x, src_map, dst_map, g, b, y, pad_dst, pad_val, rows, C, s);
@@ -339,7 +335,7 @@ __global__ __launch_bounds__(256) void ln_stats_kernel(const float* __restrict__
 }
 
 int launch_ln_stats(const float* x, float* stats, int rows, int C, hipStream_t s) {
-  { static const int& skip_ = dev_knob_ref("SKIP", 0); if (skip_ & 2) return 0; }   // dev: ablation of the step (tools/dev/r04_ablate.py)
+  DEV_SKIP(2);
   if (rows <= 0) return 0;
   if (C % 4 != 0) return NUHTC_E_INVALID;
   ProfScope ps("layernorm", 0, 4.0 * rows * C + 8.0 * rows, s);
@@ -349,7 +345,7 @@ int launch_ln_stats(const float* x, float* stats, int rows, int C, hipStream_t s
   else if (nv <= 2) hipLaunchKernelGGL(ln_stats_kernel<2>, grid, blk, 0, s, x, stats, rows, C);
   else if (nv <= 3) hipLaunchKernelGGL(ln_stats_kernel<3>, grid, blk, 0, s, x, stats, rows, C);
   else return NUHTC_E_INVALID;
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 // ----------------------------------------------------------------------------- PatchMerging gather + LN(4C)
@@ -384,7 +380,7 @@ __global__ __launch_bounds__(256) void merge_ln_kernel(const float* __restrict__
 }
 
 int launch_merge_ln(const float* x, const float* g, const float* b, float* y, int B, int H, int W, int C, hipStream_t s) {
-  { static const int& skip_ = dev_knob_ref("SKIP", 0); if (skip_ & 2) return 0; }   // dev: ablation of the step (tools/dev/r04_ablate.py)
+  DEV_SKIP(2);
   ProfScope ps("merge_ln", 0, 8.0 * B * H * W * C, s);
   int rows = B * (H / 2) * (W / 2);
   dim3 grid(cdiv(rows, 4)), blk(256);
@@ -394,7 +390,7 @@ int launch_merge_ln(const float* x, const float* g, const float* b, float* y, in
   else if (nv == 12) hipLaunchKernelGGL(merge_ln_kernel<12>, grid, blk, 0, s, x, g, b, y, rows, H, W, C);
   else if (nv == 24) hipLaunchKernelGGL(merge_ln_kernel<24>, grid, blk, 0, s, x, g, b, y, rows, H, W, C);
   else return NUHTC_E_INVALID;
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 // ----------------------------------------------------------------------------- window attention
@@ -778,7 +774,7 @@ __global__ __launch_bounds__(256, 3) void window_attn_split_kernel(const float* 
 
 int launch_window_attn(const float* qkv, const float* biasP, const float* maskP, const int* mask_any, const int* out_map, float* out,
                        int nWinTotal, int nWperImg, int C, int nH, int split_pipe, hipStream_t s, const unsigned long long* padbits, int bias_row) {
-  { static const int& skip_ = dev_knob_ref("SKIP", 0); if (skip_ & 1) return 0; }   // dev: ablation of the step (tools/dev/r04_ablate.py)
+  DEV_SKIP(1);
   ProfScope ps(C == 96 ? "window_attn|c96" : C == 192 ? "window_attn|c192" : C == 384 ? "window_attn|c384" : C == 768 ? "window_attn|c768" : "window_attn",   // (tags group by the part before '|')
                4.0 * 49 * 49 * 32 * nWinTotal * nH, 16.0 * 49 * C * nWinTotal, s);
   int nPairs = nWinTotal * nH;
@@ -788,7 +784,7 @@ int launch_window_attn(const float* qkv, const float* biasP, const float* maskP,
     hipLaunchKernelGGL(window_attn_split_kernel, dim3(cdiv(nPairs, 4)), dim3(256), 0, s, qkv, biasP, maskP, mask_any, out_map, out, nPairs, nWperImg, C, nH, padbits, bias_row);
   else
     hipLaunchKernelGGL(window_attn_mfma_kernel, dim3(cdiv(nPairs, 4)), dim3(256), 0, s, qkv, biasP, maskP, mask_any, out_map, out, nPairs, nWperImg, C, nH);
-  return hipGetLastError() == hipSuccess ? 0 : NUHTC_E_HIP;
+  return launched() ? 0 : NUHTC_E_HIP;
 }
 
 const char* nuhtc_tu_probe_swin() {

@@ -118,7 +118,7 @@ extern "C" int nuhtc_tissue_mask(int device, const uint8_t* img, int H, int W, i
   }
   if (back)
     hipLaunchKernelGGL(tissue_close_kernel, grid, dim3(256), 0, s, med, H, W, sthresh, sthresh_up > 255 ? 255 : sthresh_up, close > 0 ? close : 1, binary);
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return NUHTC_E_HIP;
+  if (!launched() || hipStreamSynchronize(s) != hipSuccess) return NUHTC_E_HIP;
   return 0;
 }
 
@@ -204,7 +204,7 @@ extern "C" int nuhtc_points_polygon_test(int device, const int32_t* contour, int
   if (hipSetDevice(device) != hipSuccess) return NUHTC_E_HIP;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(pip_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, contour, (long long)n_vert, pts, (long long)n, out);
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return NUHTC_E_HIP;
+  if (!launched() || hipStreamSynchronize(s) != hipSuccess) return NUHTC_E_HIP;
   return 0;
 }
 
@@ -242,6 +242,6 @@ extern "C" int nuhtc_grid_in_contour(int device, int start_x, int start_y, int n
   for (int h = 0; h < n_holes; ++h)            // in stream order after the contour's launch: a hole only clears
     hipLaunchKernelGGL(pip_grid_kernel, dim3((unsigned)((ncand + 255) / 256)), dim3(256), 0, s, g, holes + 2 * hole_off[h],
                        (long long)(hole_off[h + 1] - hole_off[h]), keep);
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return NUHTC_E_HIP;
+  if (!launched() || hipStreamSynchronize(s) != hipSuccess) return NUHTC_E_HIP;
   return 0;
 }
