@@ -443,6 +443,30 @@ typedef struct nuhtc_tile_post_args {
   float thr;
 } nuhtc_tile_post_args;
 int nuhtc_op_tile_post(nuhtc_engine* e, const nuhtc_tile_post_args* a, void* stream);
+/* The RPN half of the proposals of nuhtc_infer, op by op, as test entry points (csrc/proposals.hip, build_rois_kernel of csrc/roi.hip).  Each
+ * fills the parameter block nuhtc_infer fills and calls the same launch function; scratch is allocated per call; counts a kernel indexes with are
+ * read back and checked against the capacities first.  All pointers are device memory.  Each synchronises `stream` and needs a finalized engine.
+ * nuhtc_op_rpn_select: the four level maps out[l] [B][h[l] * w[l]][32] (columns 0-2 objectness logits, 3 + 4 a + j the deltas of anchor a; stride
+ *   4 << l) -> per (image, level) the nms_pre best anchors by (score descending, index ascending) -- all of them in index order when the level has
+ *   no more than nms_pre -- decoded (delta2bbox, stds 1), clipped to img_w x img_h and kept where width and height > min_size:
+ *   cand_boxes [B][4][nms_pre][4], cand_scores [B][4][nms_pre], cand_count [B][4]; slots from the count on are not written.  The key scratch row
+ *   holds the largest level rounded up to 64 (level 0 in the engine).  NUHTC_E_INVALID: nms_pre outside 1..4096, B outside 1..256, h or w < 1.
+ * nuhtc_op_nms_levels: candidates boxes [B][G][slot][4], scores [B][G][slot], group_count [B][G] -> mmcv batched_nms with id = group, the first
+ *   max_keep survivors: dets [B][max_keep][5], src [B][max_keep] (flat index into scores), counts [B].  route 0: launch_nms_levels (the engine's RPN
+ *   route), route 1: launch_nms with ids == null.  The capacity of the sorted list is that of the engine's workspace for G levels of `slot`
+ *   candidates: G * slot rounded up to 64 (at least 64) plus 64 (G - 1).  All scratch of the call (sorted boxes, sources, positions, segment tables,
+ *   survivor words, the mask matrix) is filled with 0xFF bytes before the launch.  NUHTC_E_INVALID: G outside 1..16, slot outside 1..16384, max_keep
+ *   < 1, a count outside 0..slot, and what the launch functions refuse (G * max_keep > 8192 on route 0, a capacity beyond their limits).
+ * nuhtc_op_build_rois: per image cat(cc_boxes [B][cc_cap][4] below cc_counts [B], rpn_dets [B][rpn_cap][5] below rpn_counts [B]) (cc_boxes NULL:
+ *   RPN rows alone), or with `fixed` [B][n_fixed][4] those rows -> rois [cap][5] (image index, box) flattened over the batch, roi_off / roi_cnt [B],
+ *   total [1]; rows from *total on are not written.  NUHTC_E_INVALID: B outside 1..256, counts beyond the capacities, more rows than `cap`. */
+int nuhtc_op_rpn_select(nuhtc_engine* e, const float* const out[4], const int32_t h[4], const int32_t w[4], int B, int nms_pre, int img_h, int img_w,
+                        float min_size, float* cand_boxes, float* cand_scores, int32_t* cand_count, void* stream);
+int nuhtc_op_nms_levels(nuhtc_engine* e, const float* boxes, const float* scores, const int32_t* group_count, int B, int G, int slot, float iou_thr,
+                        int max_keep, int route, float* dets, int32_t* src, int32_t* counts, void* stream);
+int nuhtc_op_build_rois(nuhtc_engine* e, const float* cc_boxes, const int32_t* cc_counts, int cc_cap, const float* rpn_dets, const int32_t* rpn_counts,
+                        int rpn_cap, const float* fixed, int n_fixed, int B, int cap, float* rois, int32_t* roi_off, int32_t* roi_cnt, int32_t* total,
+                        void* stream);
 
 /* Scoring a batch on the device (csrc/eval.hip).  Replaces what the reference's `WSIDataset.evaluate` (nuhtc/datasets/WSI_coco.py:278-545) and
  * tools/analysis_tools/pannuke/compute_stats.py compute from decoded masks, up to the integer tables the metrics are functions of: the host

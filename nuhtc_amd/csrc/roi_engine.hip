@@ -520,3 +520,96 @@ int nuhtc_op_tile_post(nuhtc_engine* e, const nuhtc_tile_post_args* a, void* str
   const int rc = launch_tile_post(tp, a->B, s);
   return op_finish(e, rc, s, "tile_post launch failed", "tile_post kernel failed");
 }
+
+// ---- the RPN half of the proposals, op by op: the same parameter blocks and launch_* functions as run_roi_path
+int nuhtc_op_rpn_select(nuhtc_engine* e, const float* const out[4], const int32_t h[4], const int32_t w[4], int B, int nms_pre, int img_h, int img_w,
+                        float min_size, float* cand_boxes, float* cand_scores, int32_t* cand_count, void* stream) {
+  if (!e || !out || !h || !w || !cand_boxes || !cand_scores || !cand_count) return NUHTC_E_INVALID;
+  for (int l = 0; l < 4; ++l)
+    if (!out[l]) return NUHTC_E_INVALID;
+  if (!e->finalized) FAIL(e, NUHTC_E_STATE, "nuhtc_op_rpn_select before finalize");
+  if (B < 1 || B > 256) FAIL(e, NUHTC_E_INVALID, "rpn_select op: B out of range (1..256)");
+  if (nms_pre < 1 || nms_pre > 4096) FAIL(e, NUHTC_E_INVALID, "rpn_select op: nms_pre out of range (1..4096)");
+  int maxn = 0;
+  for (int l = 0; l < 4; ++l) {
+    if (h[l] < 1 || w[l] < 1 || (long long)h[l] * w[l] * 3 > (1ll << 24)) FAIL(e, NUHTC_E_INVALID, "rpn_select op: level size out of range");
+    maxn = std::max(maxn, h[l] * w[l] * 3);
+  }
+  HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
+  RpnLevels lv;
+  for (int l = 0; l < 4; ++l) { lv.out[l] = out[l]; lv.h[l] = h[l]; lv.w[l] = w[l]; lv.stride[l] = 4 << l; }
+  DevScratch sc;
+  RpnSelParams sp;
+  sp.nms_pre = nms_pre; sp.slot = nms_pre; sp.cand_boxes = cand_boxes; sp.cand_scores = cand_scores; sp.cand_count = cand_count;
+  sp.key_stride = round_up(maxn, 64);
+  sp.keys = sc.alloc<unsigned>((size_t)B * 4 * sp.key_stride * sizeof(unsigned));
+  sp.img_h = img_h; sp.img_w = img_w; sp.min_size = min_size;
+  if (!sc.ok()) FAIL(e, NUHTC_E_HIP, "rpn_select op: scratch allocation failed");
+  const int rc = launch_rpn_select(lv, sp, B, s);
+  return op_finish(e, rc, s, "rpn_select launch refused or failed", "rpn_select kernel failed");
+}
+
+int nuhtc_op_nms_levels(nuhtc_engine* e, const float* boxes, const float* scores, const int32_t* group_count, int B, int G, int slot, float iou_thr,
+                        int max_keep, int route, float* dets, int32_t* src, int32_t* counts, void* stream) {
+  if (!e || !boxes || !scores || !group_count || !dets || !src || !counts) return NUHTC_E_INVALID;
+  if (!e->finalized) FAIL(e, NUHTC_E_STATE, "nuhtc_op_nms_levels before finalize");
+  if (B < 1 || B > 256) FAIL(e, NUHTC_E_INVALID, "nms_levels op: B out of range (1..256)");
+  if (G < 1 || G > NMS_MAX_GROUPS || slot < 1 || slot > NMS_MAX_CAP || max_keep < 1 || (route != 0 && route != 1))
+    FAIL(e, NUHTC_E_INVALID, "nms_levels op: G (1..16), slot (1..16384), max_keep (>= 1) or route (0, 1) out of range");
+  HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> cnt;
+  if (!read_ints(group_count, B * G, cnt, s)) FAIL(e, NUHTC_E_HIP, "nms_levels op: reading group_count failed");
+  for (int c : cnt)
+    if (c < 0 || c > slot) FAIL(e, NUHTC_E_INVALID, "nms_levels op: a group count exceeds slot");
+  // capacities as alloc_roi_workspace derives rpn_cap / rpn_pow2 from G levels of `slot` candidates
+  const int maxc = G * slot;
+  const int cap = round_up(std::max(maxc, 64), 64) + 64 * (G - 1);
+  const size_t nw = (size_t)cap / 64;
+  if ((unsigned long long)B * cap * nw * 8 > (1ull << 32)) FAIL(e, NUHTC_E_INVALID, "nms_levels op: the mask matrix of this call would exceed 4 GiB");
+  DevScratch sc;
+  NmsParams np;
+  memset(&np, 0, sizeof(np));
+  np.boxes = boxes; np.scores = scores; np.ids = nullptr; np.group_count = group_count; np.n_groups = G; np.slot = slot;
+  np.cap = cap; np.cap_pow2 = pow2_ge(maxc); np.iou_thr = iou_thr; np.max_keep = max_keep;
+  np.out_dets = dets; np.out_src = src; np.out_counts = counts;
+  // every scratch array starts as 0xFF bytes: nothing may lean on zeroed or left-over memory
+  struct { void** p; size_t bytes; } parts[] = {
+      {(void**)&np.sorted_boxes, (size_t)B * cap * 16}, {(void**)&np.sorted_src, (size_t)B * cap * 4}, {(void**)&np.n_total, (size_t)B * 4},
+      {(void**)&np.seg_start, (size_t)B * G * 4},       {(void**)&np.seg_n, (size_t)B * G * 4},        {(void**)&np.sorted_pos, (size_t)B * cap * 4},
+      {(void**)&np.keepbits, (size_t)B * nw * 8},       {(void**)&np.mask, (size_t)B * cap * nw * 8}};
+  int rc = 0;
+  for (auto& part : parts) {
+    *part.p = sc.alloc<void>(part.bytes);
+    if (!sc.ok()) FAIL(e, NUHTC_E_HIP, "nms_levels op: scratch allocation failed");
+    if (hipMemsetAsync(*part.p, 0xFF, part.bytes, s) != hipSuccess) rc = NUHTC_E_HIP;
+  }
+  if (!rc) rc = route == 0 ? launch_nms_levels(np, B, s) : launch_nms(np, B, s);
+  return op_finish(e, rc, s, "nms_levels launch refused or failed (route 0: G * max_keep <= 8192; sorted-list capacity within the route's limit)",
+                   "nms_levels kernel failed");
+}
+
+int nuhtc_op_build_rois(nuhtc_engine* e, const float* cc_boxes, const int32_t* cc_counts, int cc_cap, const float* rpn_dets, const int32_t* rpn_counts,
+                        int rpn_cap, const float* fixed, int n_fixed, int B, int cap, float* rois, int32_t* roi_off, int32_t* roi_cnt, int32_t* total,
+                        void* stream) {
+  if (!e || !rois || !roi_off || !roi_cnt || !total) return NUHTC_E_INVALID;
+  if (!fixed && (!rpn_dets || !rpn_counts || (cc_boxes && !cc_counts))) return NUHTC_E_INVALID;
+  if (B < 1 || B > 256) FAIL(e, NUHTC_E_INVALID, "build_rois op: B out of range (1..256)");
+  if (cap < 0 || cc_cap < 0 || rpn_cap < 0 || n_fixed < 0) FAIL(e, NUHTC_E_INVALID, "build_rois op: negative capacity");
+  HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
+  long long rows = (long long)B * n_fixed;
+  if (!fixed) {
+    std::vector<int> nr, ncc(B, 0);
+    if (!read_ints(rpn_counts, B, nr, s) || (cc_boxes && !read_ints(cc_counts, B, ncc, s))) FAIL(e, NUHTC_E_HIP, "build_rois op: reading the counts failed");
+    rows = 0;
+    for (int b = 0; b < B; ++b) {
+      if (nr[b] < 0 || nr[b] > rpn_cap || ncc[b] < 0 || ncc[b] > cc_cap) FAIL(e, NUHTC_E_INVALID, "build_rois op: a count exceeds its capacity");
+      rows += nr[b] + ncc[b];
+    }
+  }
+  if (rows > cap) FAIL(e, NUHTC_E_INVALID, "build_rois op: more rows than cap");
+  const int rc = launch_build_rois(cc_boxes, cc_counts, cc_cap, rpn_dets, rpn_counts, rpn_cap, fixed, n_fixed, rois, roi_off, roi_cnt, total, B, s);
+  return op_finish(e, rc, s, "build_rois launch failed", "build_rois kernel failed");
+}

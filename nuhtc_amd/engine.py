@@ -625,6 +625,76 @@ class Engine:
         self._check(self.lib.nuhtc_op_tile_post(self.h, ctypes.byref(a), self._stream()))
         return keep
 
+    # ------------------------------------------------------------------ the RPN half of the proposals, op by op (csrc/proposals.hip)
+    def op_rpn_select(self, maps, nms_pre, img_hw, min_size, cand_boxes=None, cand_scores=None, cand_count=None):
+        """Per-level selection and decode (nuhtc_op_rpn_select): maps = the four level maps (B, h_l, w_l, 32) on the device (columns 0-2
+        objectness logits, 3.. deltas; stride 4 << l) -> (cand_boxes (B, 4, nms_pre, 4), cand_scores (B, 4, nms_pre), cand_count (B, 4));
+        slots from the count on are left as they are (zero when allocated here)."""
+        if len(maps) != 4 or any(m.dim() != 4 or m.shape[3] != 32 or m.shape[0] != maps[0].shape[0] or m.dtype != torch.float32 for m in maps):
+            raise ValueError('op_rpn_select: four float32 maps (B, h, w, 32) expected')
+        maps = [m.contiguous() for m in maps]
+        B, K = int(maps[0].shape[0]), int(nms_pre)
+        fl = dict(dtype=torch.float32, device=self.device)
+        Ka = max(K, 1)
+        if cand_boxes is None:
+            cand_boxes = torch.zeros(B, 4, Ka, 4, **fl)
+        if cand_scores is None:
+            cand_scores = torch.zeros(B, 4, Ka, **fl)
+        if cand_count is None:
+            cand_count = torch.zeros(B, 4, dtype=torch.int32, device=self.device)
+        ptrs = (ctypes.c_void_p * 4)(*[m.data_ptr() for m in maps])
+        hs = (ctypes.c_int32 * 4)(*[int(m.shape[1]) for m in maps])
+        ws = (ctypes.c_int32 * 4)(*[int(m.shape[2]) for m in maps])
+        self._check(self.lib.nuhtc_op_rpn_select(self.h, ptrs, hs, ws, B, K, int(img_hw[0]), int(img_hw[1]), float(min_size), cand_boxes.data_ptr(),
+                                                 cand_scores.data_ptr(), cand_count.data_ptr(), self._stream()))
+        return cand_boxes, cand_scores, cand_count
+
+    def op_nms_levels(self, boxes, scores, counts, iou_thr, max_keep, route=0, dets=None, src=None):
+        """Level-wise batched NMS (nuhtc_op_nms_levels): boxes (B, G, slot, 4), scores (B, G, slot) on the device, counts (B, G) (array or
+        device int32) -> (dets (B, max_keep, 5), src (B, max_keep) flat index into scores, counts (B,)).  route 0: launch_nms_levels (the
+        engine's RPN route), 1: launch_nms with the group as id.  Rows from the count on are left as they are (zero when allocated here)."""
+        B, G, slot = (int(v) for v in scores.shape)
+        if tuple(boxes.shape) != (B, G, slot, 4):
+            raise ValueError('op_nms_levels: boxes (B, G, slot, 4) and scores (B, G, slot) expected')
+        cnt = self._i32(np.asarray(counts).reshape(-1) if not isinstance(counts, torch.Tensor) else counts)
+        if cnt.numel() != B * G:
+            raise ValueError('op_nms_levels: counts (B, G) expected')
+        K = int(max_keep)
+        if dets is None:
+            dets = torch.zeros(B, max(K, 1), 5, dtype=torch.float32, device=self.device)
+        if src is None:
+            src = torch.zeros(B, max(K, 1), dtype=torch.int32, device=self.device)
+        out_counts = torch.zeros(B, dtype=torch.int32, device=self.device)
+        self._check(self.lib.nuhtc_op_nms_levels(self.h, boxes.contiguous().data_ptr(), scores.contiguous().data_ptr(), cnt.contiguous().data_ptr(), B, G, slot,
+                                                 float(iou_thr), K, int(route), dets.data_ptr(), src.data_ptr(), out_counts.data_ptr(), self._stream()))
+        return dets, src, out_counts
+
+    def op_build_rois(self, rpn_dets=None, rpn_counts=None, cc_boxes=None, cc_counts=None, fixed=None, B=None, rois=None, cap=None):
+        """RoI list assembly (nuhtc_op_build_rois): per image cat(cc_boxes (B, cc_cap, 4) below cc_counts, rpn_dets (B, rpn_cap, 5) below
+        rpn_counts), cc_boxes None: the RPN rows alone; or `fixed` (B, n_fixed, 4).  Returns dict(rois (cap, 5), roi_off, roi_cnt (B,), total
+        (1,)); rows of rois from total on are left as they are (zero when allocated here)."""
+        dev = dict(dtype=torch.int32, device=self.device)
+        if fixed is not None:
+            B, nf = int(fixed.shape[0]), int(fixed.shape[1])
+            need = B * nf
+        else:
+            B, nf = int(rpn_dets.shape[0]), 0
+            rpn_counts = self._i32(rpn_counts)
+            need = B * int(rpn_dets.shape[1])
+            if cc_boxes is not None:
+                cc_counts = self._i32(cc_counts)
+                need += B * int(cc_boxes.shape[1])
+        if rois is None:
+            rois = torch.zeros(max(need if cap is None else int(cap), 1), 5, dtype=torch.float32, device=self.device)
+        cap = int(rois.shape[0]) if cap is None else int(cap)
+        r = dict(rois=rois, roi_off=torch.zeros(B, **dev), roi_cnt=torch.zeros(B, **dev), total=torch.zeros(1, **dev))
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        self._check(self.lib.nuhtc_op_build_rois(self.h, ptr(cc_boxes), ptr(cc_counts), int(cc_boxes.shape[1]) if cc_boxes is not None else 1,
+                                                 ptr(rpn_dets), ptr(rpn_counts), int(rpn_dets.shape[1]) if rpn_dets is not None else 1,
+                                                 ptr(fixed), nf, B, cap, rois.data_ptr(), r['roi_off'].data_ptr(), r['roi_cnt'].data_ptr(),
+                                                 r['total'].data_ptr(), self._stream()))
+        return r
+
     # ------------------------------------------------------------------ scoring on the device (csrc/eval.hip)
     def op_eval_select(self, scores, counts, masks, fg_thr, thr, labels=None):
         """Score filter + greedy mask-NMS of `WSIDataset.evaluate` (nuhtc_op_eval_select): scores (B, K) float32, counts (B,), masks

@@ -128,6 +128,7 @@ EXPORTS = ['nuhtc_default_config', 'nuhtc_create', 'nuhtc_destroy', 'nuhtc_last_
            'nuhtc_bind_host_thread_pci', 'nuhtc_bind_host_thread_at', 'nuhtc_restore_host_thread', 'nuhtc_op_ln_gemm', 'nuhtc_op_gemm_ln_gemm', 'nuhtc_op_merge_ln_gemm', 'nuhtc_write_ring_features',
            'nuhtc_write_point_features', 'nuhtc_join_features', 'nuhtc_fill_rings', 'nuhtc_features', 'nuhtc_op_cc_mask', 'nuhtc_op_cc_proposals',
            'nuhtc_op_conv3', 'nuhtc_op_window_msa', 'nuhtc_op_bbox_tail', 'nuhtc_op_det_post', 'nuhtc_op_paste', 'nuhtc_op_tile_post',
+           'nuhtc_op_rpn_select', 'nuhtc_op_nms_levels', 'nuhtc_op_build_rois',
            'nuhtc_eval_batch', 'nuhtc_op_eval_select', 'nuhtc_op_eval_pairs', 'nuhtc_op_eval_render', 'nuhtc_op_eval_joint',
            'nuhtc_tissue_mask', 'nuhtc_points_polygon_test', 'nuhtc_grid_in_contour']
 
@@ -179,6 +180,10 @@ def load():
     lib.nuhtc_op_det_post.argtypes = [vp, ctypes.POINTER(DetPostArgs), vp]
     lib.nuhtc_op_paste.argtypes = [vp, ctypes.POINTER(PasteArgs), vp]
     lib.nuhtc_op_tile_post.argtypes = [vp, ctypes.POINTER(TilePostArgs), vp]
+    i4 = ctypes.POINTER(ctypes.c_int32)
+    lib.nuhtc_op_rpn_select.argtypes = [vp, ctypes.POINTER(vp), i4, i4, ci, ci, ci, ci, cf, vp, vp, vp, vp]
+    lib.nuhtc_op_nms_levels.argtypes = [vp, vp, vp, vp, ci, ci, ci, cf, ci, ci, vp, vp, vp, vp]
+    lib.nuhtc_op_build_rois.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp]
     lib.nuhtc_eval_batch.argtypes = [vp, ctypes.POINTER(Dets), ci, ctypes.POINTER(EvalArgs), vp]
     lib.nuhtc_op_eval_select.argtypes = [vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, cf, ctypes.c_double, vp, vp, vp, vp]
     lib.nuhtc_op_eval_pairs.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]
