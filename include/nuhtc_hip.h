@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define NUHTC_ABI_VERSION 11
+#define NUHTC_ABI_VERSION 12
 
 enum {
   NUHTC_OK = 0,
@@ -619,6 +619,28 @@ int nuhtc_points_polygon_test(int device, const int32_t* contour, int64_t n_vert
 int nuhtc_grid_in_contour(int device, int start_x, int start_y, int nx, int ny, int step, const int32_t* offsets, int n_off, int require_all,
                           const int32_t* contour, int64_t n_vert, const int32_t* holes, int64_t n_pool, const int64_t* hole_off, int n_holes,
                           int hole_dx, int hole_dy, uint8_t* keep, void* stream);
+
+/* COCO RLE (pycocotools mask.encode / toBbox; tools/infer_wsi.py:600-627) of n bit-packed H x W masks, on the device (v12; csrc/rle.hip): what
+ * cocoapi common/maskApi.c rleEncode + rleToString and rleToBbox compute, byte for byte (nuhtc_amd/cocomask.py encode / to_bbox are the host
+ * twins).  Engine-free like nuhtc_merge_overlap; all pointers are device memory of `device`.  words_dev [n][H * W / 32]: rows of W / 32 words,
+ * pixel x of a row in bit x & 31 of word x >> 5 -- the layout of nuhtc_dets.masks and of words_dev from nuhtc_export_kept.  n = n_max when
+ * n_dev is NULL, else min(*n_dev, n_max) read on the device (n_dev[0] of nuhtc_export_kept chains without a host synchronisation); rows
+ * past n are not touched.  Per mask i < n:
+ *   len_dev [i]     = bytes of the compressed `counts` string (runs in column-major order over the whole frame, the first count the leading
+ *                     run of zeros, from the fourth count on the difference from the count two places back, 5 bits per character + 48 with
+ *                     continuation bit 0x20 and the sign-aware stop rule), or -1 when the mask has more than `run_cap` runs: that one writes
+ *                     no bytes and a zero box, and the caller encodes it on the host (the convention of nuhtc_mask_contours).  run_cap costs
+ *                     4 bytes of LDS per run and is taken as at most 15360;
+ *   off_dev [i]     = byte offset of the string in bytes_dev = sum of max(len, 0) of the masks before it (placement is in mask order and a
+ *                     function of the lengths alone); off_dev [n] = the total: when it exceeds pool_cap, the strings that would end past the
+ *                     pool were not written (nuhtc_export_crops does the same with crop_off_dev) and no byte at or past pool_cap is touched;
+ *   bbox_dev [i][4] = x, y, w, h of rleToBbox, including its quirk (a 1-run that ends in a later column than it began in spans the full
+ *                     height: y = 0, h = H); zeros for an empty mask.
+ * off_dev has n_max + 1 entries, bytes_dev pool_cap bytes (may be NULL with pool_cap = 0: lengths, offsets and boxes only).
+ * NUHTC_E_INVALID (nothing enqueued): W % 32 != 0, H * W > 2^20, run_cap < 1, H or W < 1, n_max or pool_cap < 0, a null required pointer,
+ * n_max * min(run_cap, H * W + 1) * 5 > 2^31 - 1 (the offsets are int32).  Enqueues three launches on `stream`; does not synchronise. */
+int nuhtc_rle_encode(int device, const uint32_t* words_dev, const int32_t* n_dev, int n_max, int H, int W, int run_cap,
+                     int32_t* len_dev, int32_t* off_dev, uint8_t* bytes_dev, int64_t pool_cap, int32_t* bbox_dev, void* stream);
 
 /* Per-kernel timing with HIP events recorded on the launch stream (process-wide switch; off by default).
  * nuhtc_profile_read synchronises the device and writes one text line per kernel tag,

@@ -246,25 +246,65 @@ class Engine:
             out.append(d)
         return out
 
-    def export_async(self, B, cap=None, contour_cap=256, crop_words_per_det=128):
+    def rle_encode(self, words, H, W, run_cap=1024, n=None, pool_cap=None, out=None):
+        """COCO run-length strings and boxes of bit-packed masks on the device (nuhtc_rle_encode: cocomask.encode(m)['counts'] and
+        cocomask.to_bbox, byte for byte).  words: contiguous int32 device tensor (n_max, H * W // 32), rows of W // 32 words, pixel x in
+        bit x & 31 of word x >> 5.  n: None (all n_max masks) or an int32 device tensor whose first element is the number of masks (read on
+        the device).  pool_cap: bytes of the string pool (default: what run_cap allows per mask, at most 5 characters per count).
+        out: (len, off, bytes, bbox) device tensors to write into (int32 (n_max,), int32 (n_max + 1,), uint8 (>= pool_cap,), int32
+        (n_max, 4)); fresh zero-filled ones otherwise.
+        -> (len, off, bytes, bbox): len[i] bytes of string i or -1 (more than run_cap runs: encode that one on the host), off the
+        exclusive scan of max(len, 0) with the total in off[n], string i = bytes[off[i]:off[i] + len[i]] where it ends inside the pool,
+        bbox[i] = x, y, w, h.  Synchronous."""
+        if words.device != self.device or words.dtype != torch.int32 or not words.is_contiguous() or words.dim() != 2 or words.shape[1] * 32 != H * W:
+            raise ValueError('rle_encode: words must be a contiguous int32 (n, H * W // 32) tensor on the engine\'s device')
+        n_max = int(words.shape[0])
+        if pool_cap is None:
+            pool_cap = max(1, n_max) * 5 * min(int(run_cap), H * W + 1) if out is None else int(out[2].numel())
+        if out is None:
+            out = (torch.zeros(n_max, dtype=torch.int32, device=self.device), torch.zeros(n_max + 1, dtype=torch.int32, device=self.device),
+                   torch.zeros(max(1, int(pool_cap)), dtype=torch.uint8, device=self.device), torch.zeros(n_max, 4, dtype=torch.int32, device=self.device))
+        ln, off, data, bbox = out
+        if ln.numel() < n_max or off.numel() < n_max + 1 or data.numel() < pool_cap or bbox.numel() < 4 * n_max:
+            raise ValueError('rle_encode: an output tensor is smaller than the call needs')
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        rc = self.lib.nuhtc_rle_encode(self.device.index, vp(words), vp(n) if n is not None else None, n_max, int(H), int(W), int(run_cap),
+                                       vp(ln), vp(off), vp(data), int(pool_cap), vp(bbox), self._stream())
+        if rc:
+            raise HipError(f'nuhtc_rle_encode failed ({rc})')
+        torch.cuda.current_stream(self.device).synchronize()
+        return ln, off, data, bbox
+
+    def export_async(self, B, cap=None, contour_cap=256, crop_words_per_det=128, rle=False, rle_bytes_per_det=256, rle_run_cap=hip.RLE_MAX_RUNS):
         """After infer_async: enqueue, on the current stream, everything the slide loop needs from the batch -- the outer
         contours (nuhtc_mask_contours), a gather of the kept detections, in (tile, slot) order (nuhtc_export_kept), and their
         masks cropped to their bounding rectangles into one word pool (nuhtc_export_crops) -- into fixed-capacity pinned host
         buffers.  No host synchronisation: every device -> host copy of a result would otherwise block the submitting thread
         behind the other batches in flight.  Read with export_read() once the stream (or an event recorded after this call) has
-        completed.  The full 8 KB masks stay on the device (export_full_mask fetches one when a crop did not fit the pool)."""
+        completed.  The full 8 KB masks stay on the device (export_full_mask fetches one when a crop did not fit the pool).
+        rle=True: the COCO run-length string and box of every kept detection's full-tile mask as well (nuhtc_rle_encode on the compacted
+        masks): the blob gains rle_len [cap], rle_off [cap + 1], rle_bbox [cap, 4] and rle_bytes [cap * rle_bytes_per_det], and the strings
+        leave in the same single copy.  rle_run_cap defaults to the most the kernel takes (60 KB of LDS positions): its workgroups have 1024
+        threads, two of them fill a CU's 2048 thread slots and 2 x 60 KB fit its 160 KB of LDS, so a smaller capacity would buy no occupancy
+        and only send ragged masks to the host encoder.  The image width must be a multiple of 32 (the mask rows are the frame the strings describe)."""
         K, W = self.cfg.max_per_img, self.cfg.tile_h * (self.cfg.tile_w // 32)
+        if rle and self.cfg.tile_w != self.image_hw[1]:
+            raise ValueError(f'export_async(rle=True): image width {self.image_hw[1]} is not a multiple of 32')
         # default capacity: 96 kept detections per tile on average at the x2 resize of a 40x slide, scaled with the nuclei per tile at
         # larger factors (20x slides: x4 -> four times the nuclei per 256-px tile); a batch over it falls back for that batch only
         per_tile = 96 * max(1, int(round((float(self.cfg.scale_factor) / 2.0) ** 2)))
         cap = int(cap or min(self.cfg.max_batch * K, per_tile * self.cfg.max_batch))
         pool = cap * int(crop_words_per_det)
+        rle_pool = cap * int(rle_bytes_per_det) if rle else 0
         ex = getattr(self, '_ex', None)
-        if ex is None or ex['cap'] != cap or ex['ccap'] != contour_cap or ex['pool'] != pool:
+        if ex is None or ex['cap'] != cap or ex['ccap'] != contour_cap or ex['pool'] != pool or ex['rle_pool'] != rle_pool:
             dev = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=self.device)
             names = dict(nk=((2,), torch.int32), idx=((cap,), torch.int64), boxes=((cap, 5), torch.float32), labels=((cap,), torch.int32),
                          cn=((cap,), torch.int32), crop_box=((cap, 4), torch.int32), crop_area=((cap,), torch.int32),
                          crop_off=((cap + 1,), torch.int32), crop_words=((pool,), torch.int32), xy=((cap, contour_cap, 2), torch.int16))
+            if rle:
+                names.update(rle_len=((cap,), torch.int32), rle_off=((cap + 1,), torch.int32), rle_bbox=((cap, 4), torch.int32),
+                             rle_bytes=((rle_pool,), torch.uint8))
             # every field is a view into ONE device buffer and ONE pinned host buffer: a batch's results leave the device in a single
             # copy (each asynchronous copy on a compute stream costs a hand-over between the copy engine and the kernels)
             offs, total = {}, 0
@@ -278,7 +318,7 @@ class Engine:
             # export_async after the one that filled them (i.e. until the slot's next-but-one batch is enqueued)
             blob_hosts = [torch.zeros(total, dtype=torch.uint8).pin_memory() for _ in range(self.EXPORT_BUFFERS)]
             view = lambda blob, k: blob[offs[k]:offs[k] + int(np.prod(names[k][0])) * torch.empty(0, dtype=names[k][1]).element_size()].view(names[k][1]).view(*names[k][0])
-            ex = self._ex = dict(cap=cap, ccap=contour_cap, pool=pool, blob_dev=blob_dev, blob_hosts=blob_hosts, turn=0,
+            ex = self._ex = dict(cap=cap, ccap=contour_cap, pool=pool, rle_pool=rle_pool, blob_dev=blob_dev, blob_hosts=blob_hosts, turn=0,
                                  hosts=[{k: view(b, k) for k in names} for b in blob_hosts], dev={k: view(blob_dev, k) for k in names})
             ex['dev']['words'] = dev(cap, W, dtype=torch.int32)          # full masks of the kept detections: device only
         self.contours_async(B, contour_cap)
@@ -290,6 +330,11 @@ class Engine:
                                                self._stream()))
         self._check(self.lib.nuhtc_export_crops(self.h, vp(d['words']), vp(d['nk']), cap, vp(d['crop_box']), vp(d['crop_area']), vp(d['crop_off']),
                                                 vp(d['crop_words']), pool, self._stream()))
+        if rle:     # behind nuhtc_export_kept on the same stream: n is read from nk[0] on the device
+            rc = self.lib.nuhtc_rle_encode(self.device.index, vp(d['words']), vp(d['nk']), cap, self.cfg.tile_h, self.cfg.tile_w, int(rle_run_cap),
+                                           vp(d['rle_len']), vp(d['rle_off']), vp(d['rle_bytes']), rle_pool, vp(d['rle_bbox']), self._stream())
+            if rc:
+                raise HipError(f'nuhtc_rle_encode failed ({rc})')
         ex['turn'] = (ex['turn'] + 1) % self.EXPORT_BUFFERS
         ex['host'] = ex['hosts'][ex['turn']]
         ex['blob_hosts'][ex['turn']].copy_(ex['blob_dev'], non_blocking=True)
@@ -316,9 +361,14 @@ class Engine:
         K = self.cfg.max_per_img
         idx = ex['idx'][:n].numpy()
         off = ex['crop_off'].numpy()
-        return dict(n=n, tile=idx // K, slot=idx % K, boxes=ex['boxes'][:n].numpy(), labels=ex['labels'][:n].numpy(), cn=ex['cn'][:n].numpy(),
-                    xy=ex['xy'][:n].numpy(), crop_box=ex['crop_box'][:n].numpy(), crop_area=ex['crop_area'][:n].numpy(), crop_off=off[:n],
-                    crop_words=ex['crop_words'].numpy().view(np.uint32), crop_total=int(off[self._ex['cap']]), pool=self._ex['pool'])
+        g = dict(n=n, tile=idx // K, slot=idx % K, boxes=ex['boxes'][:n].numpy(), labels=ex['labels'][:n].numpy(), cn=ex['cn'][:n].numpy(),
+                 xy=ex['xy'][:n].numpy(), crop_box=ex['crop_box'][:n].numpy(), crop_area=ex['crop_area'][:n].numpy(), crop_off=off[:n],
+                 crop_words=ex['crop_words'].numpy().view(np.uint32), crop_total=int(off[self._ex['cap']]), pool=self._ex['pool'])
+        if 'rle_len' in ex:         # exported with rle=True: string k = rle_bytes[rle_off[k]:rle_off[k] + rle_len[k]] where it ends inside rle_pool
+            roff = ex['rle_off'].numpy()
+            g.update(rle_len=ex['rle_len'][:n].numpy(), rle_off=roff[:n], rle_bbox=ex['rle_bbox'][:n].numpy(), rle_bytes=ex['rle_bytes'].numpy(),
+                     rle_total=int(roff[n]), rle_pool=self._ex['rle_pool'])
+        return g
 
     def export_full_mask(self, k):
         """(tile_h, tile_w) bool mask of exported detection k of the last export_async (synchronous device read: the rare crop that

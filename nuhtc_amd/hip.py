@@ -9,7 +9,8 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libnuhtc_hip.so')
 
-ABI_VERSION = 11          # NUHTC_ABI_VERSION of include/nuhtc_hip.h: the layout of Config below
+RLE_MAX_RUNS = 15360      # RLE_LDS_RUNS of csrc/rle.hip: the largest run_cap nuhtc_rle_encode honours (60 KB of LDS positions)
+ABI_VERSION = 12          # NUHTC_ABI_VERSION of include/nuhtc_hip.h: the layout of Config below
 
 OK, E_INVALID, E_HIP, E_STATE, E_CAPACITY, E_NOTFOUND = 0, -1, -2, -3, -4, -5
 CH_AS_IS, CH_SWAP = 0, 1
@@ -130,7 +131,7 @@ EXPORTS = ['nuhtc_default_config', 'nuhtc_create', 'nuhtc_destroy', 'nuhtc_last_
            'nuhtc_op_conv3', 'nuhtc_op_window_msa', 'nuhtc_op_bbox_tail', 'nuhtc_op_det_post', 'nuhtc_op_paste', 'nuhtc_op_tile_post',
            'nuhtc_op_rpn_select', 'nuhtc_op_nms_levels', 'nuhtc_op_build_rois',
            'nuhtc_eval_batch', 'nuhtc_op_eval_select', 'nuhtc_op_eval_pairs', 'nuhtc_op_eval_render', 'nuhtc_op_eval_joint',
-           'nuhtc_tissue_mask', 'nuhtc_points_polygon_test', 'nuhtc_grid_in_contour']
+           'nuhtc_tissue_mask', 'nuhtc_points_polygon_test', 'nuhtc_grid_in_contour', 'nuhtc_rle_encode']
 
 _lib = None
 
@@ -194,6 +195,7 @@ def load():
     lib.nuhtc_tissue_mask.argtypes = [ci, vp, ci, ci, ctypes.c_int64, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]
     lib.nuhtc_points_polygon_test.argtypes = [ci, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp]
     lib.nuhtc_grid_in_contour.argtypes = [ci, ci, ci, ci, ci, ci, vp, ci, ci, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ci, ci, ci, vp, vp]
+    lib.nuhtc_rle_encode.argtypes = [ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, ctypes.c_int64, vp, vp]
     lib.nuhtc_export_kept.argtypes = [vp, ctypes.POINTER(Dets), ci, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.nuhtc_export_crops.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, ci, vp]
     lib.nuhtc_profile_enable.argtypes = [ci]

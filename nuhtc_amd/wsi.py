@@ -122,6 +122,43 @@ class RaggedRings:
         return self.flat[idx], n
 
 
+def _host_rle(crop, x0, y0, H, W):
+    """The host encoder on a mask crop at (x0, y0) of an H x W frame (the loop of tools/infer_wsi.py run_slide):
+    -> (counts string as bytes, [x, y, w, h] of cocomask.to_bbox)."""
+    from . import cocomask
+    full = np.zeros((H, W), np.uint8)
+    full[y0:y0 + crop.shape[0], x0:x0 + crop.shape[1]] = crop
+    r = cocomask.encode(full)
+    return r['counts'].encode('ascii'), [int(v) for v in cocomask.to_bbox(r)]
+
+
+def _rle_of_records(g, order, cb, bits, sizes, frame):
+    """COCO strings of the records `order` of an export with rle=True, in record order: (blob uint8, lengths int64, boxes int32 (m, 4),
+    number encoded on the host).  A record the device gave up on (length -1: more runs than its capacity) or whose string ends past
+    the pool is encoded by the host encoder from its crop (cb: crop boxes in tile pixels; bits / sizes: the crops' words)."""
+    ln = g['rle_len'][order].astype(np.int64)
+    ro = g['rle_off'][order].astype(np.int64)
+    bbox = g['rle_bbox'][order].astype(np.int32)
+    ok = (ln >= 0) & (ro + np.maximum(ln, 0) <= g['rle_pool'])
+    hosted = {}
+    woff = np.cumsum(sizes) - sizes
+    for j in np.flatnonzero(~ok):
+        x0, y0, x1, y1 = (int(v) for v in cb[j])
+        wpr = (x1 - x0 + 31) // 32
+        m = np.unpackbits(bits[int(woff[j]):int(woff[j] + sizes[j])].reshape(y1 - y0, wpr).view(np.uint8), axis=-1, bitorder='little')[:, :x1 - x0]
+        hosted[int(j)], bbox[j] = _host_rle(m, x0, y0, *frame)
+        ln[j] = len(hosted[int(j)])
+    off = np.cumsum(ln) - ln
+    blob = np.zeros(int(ln.sum()), np.uint8)
+    dn = np.where(ok, ln, 0)
+    idx = np.arange(int(dn.sum()), dtype=np.int64)
+    start = np.cumsum(dn) - dn
+    blob[idx + np.repeat(off - start, dn)] = g['rle_bytes'][idx + np.repeat(ro - start, dn)]
+    for j, b in hosted.items():
+        blob[off[j]:off[j] + ln[j]] = np.frombuffer(b, np.uint8)
+    return blob, ln, bbox, len(hosted)
+
+
 def _unpack_packed(eng, g, i0, coords, parts):
     """Vectorised twin of _unpack for a batch exported with device crops (Engine.export_async -> nuhtc_export_crops): appends one
     dict of arrays (the batch's records in the order _unpack produces) to `parts`."""
@@ -182,6 +219,9 @@ def _unpack_packed(eng, g, i0, coords, parts):
     parts.append(dict(tile=i0 + tile[order], box=boxes[order, :4].astype(np.float64) + org4, score=boxes[order, 4].astype(np.float64),
                       label=labels[order].astype(np.int64), crop_box=(cb + org4).astype(np.int32), area=g['crop_area'][order].astype(np.int32),
                       bits=bits, sizes=sizes, ring_n=ring_n, ring_flat=flat))
+    if 'rle_len' in g:                                                    # exported with rle=True: the strings travel with the records
+        blob, ln, bbox, nh = _rle_of_records(g, order, cb, bits, sizes, (eng.cfg.tile_h, eng.cfg.tile_w))
+        parts[-1].update(rle_blob=blob, rle_len=ln, rle_bbox=bbox, rle_host=nh)
 
 
 def _records_from_parts(parts):
@@ -197,6 +237,8 @@ def _records_from_parts(parts):
     rings = RaggedRings(cat('ring_flat'), ring_n)
     rec = dict(tile=tile.tolist(), box=list(box), score=score.tolist(), label=label.tolist(), mask=masks, ring=rings)
     masks.arrays = dict(tile=tile, box=box, score=score, label=label, rings=rings)   # the scalar fields as whole-slide arrays
+    if 'rle_len' in parts[0]:
+        rec.update(rle=(cat('rle_blob'), cat('rle_len')), rle_bbox=cat('rle_bbox'), rle_host=int(sum(p['rle_host'] for p in parts)))
     return rec
 
 
@@ -252,13 +294,17 @@ def _unpack(eng, B, i0, coords, P, rec, exported=False):
         rec['ring'].append(np.concatenate([c, c[:1]], 0) + np.array([ox, oy], np.int64))   # mask2inst + contour_map
 
 
-def infer_tiles(model, tiles, coords, batch_size=16, depth=4):
+def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False):
     """Run the engine over `tiles` (N,P,P,3) and return per-detection records that survive the per-tile margin /
     min-area filter + mask-NMS (computed on the GPU, tools/infer_wsi.py:510-531), in slide coordinates.  `depth` engines
     are kept busy with up to two batches each (nuhtc_amd.pipeline): the host unpacks batch i while the GPU runs the next ones.
 
     Returns dict(tile, box (n,4) float64 slide px, score, label, mask (list of (bool crop, x0, y0)), ring (closed
-    (n+1,2) int64 contour in slide px, traced on the GPU: nuhtc_mask_contours))."""
+    (n+1,2) int64 contour in slide px, traced on the GPU: nuhtc_mask_contours)).
+    rle=True adds the COCO run-length mask of every record inside its tile, encoded on the GPU (nuhtc_rle_encode): rle = (uint8 blob of
+    the `counts` strings concatenated in record order, int64 lengths), rle_bbox int32 (n, 4) = cocomask.to_bbox, and rle_host = how many
+    records the host encoder (cocomask.encode) had to take: more runs than the device capacity, a string past the export pool, or a
+    batch past the export capacity."""
     import torch
     P = tiles.shape[1]
     parts = {}                 # first tile of the batch -> the batch's records (array form), joined in batch order at the end
@@ -282,7 +328,7 @@ def infer_tiles(model, tiles, coords, batch_size=16, depth=4):
     for i in range(0, len(tiles), batch_size):
         if pipe.full(export=True):
             finish()
-        pipe.submit(tiles[i:i + batch_size], hip.CH_SWAP, tag=i, export=True)
+        pipe.submit(tiles[i:i + batch_size], hip.CH_SWAP, tag=i, export=True, rle=rle)
     while pipe.pending:
         finish()
     for i0 in redo:            # the per-detection path (later batches kept the packed path)
@@ -293,7 +339,14 @@ def infer_tiles(model, tiles, coords, batch_size=16, depth=4):
             _unpack(eng, B, i0, coords, P, one, exported=False)
             if one['tile']:
                 parts[i0] = _part_from_lists(one)
-    return _records_from_parts([parts[k] for k in sorted(parts)])
+                if rle:                                            # nothing of this batch was encoded on the device
+                    enc = [_host_rle(m, x0 - int(coords[t][0]), y0 - int(coords[t][1]), *tiles.shape[1:3]) for (m, x0, y0), t in zip(one['mask'], one['tile'])]
+                    parts[i0].update(rle_blob=np.frombuffer(b''.join(e[0] for e in enc), np.uint8), rle_len=np.array([len(e[0]) for e in enc], np.int64),
+                                     rle_bbox=np.array([e[1] for e in enc], np.int32).reshape(-1, 4), rle_host=len(enc))
+    rec = _records_from_parts([parts[k] for k in sorted(parts)])
+    if rle and 'rle' not in rec:
+        rec.update(rle=(np.zeros(0, np.uint8), np.zeros(0, np.int64)), rle_bbox=np.zeros((0, 4), np.int32), rle_host=0)
+    return rec
 
 
 def _part_from_lists(rec):
@@ -388,8 +441,19 @@ def pack_records(rec, keep=None, tile_base=0, rles=None):
     verts int32   (sum ring lengths, 2): the closed rings, concatenated
     crops int64   (n, 6): mask-crop box x0,y0,x1,y1 (x1,y1 exclusive), set pixels, word offset into `bits`
     bits  int32   (words,): the bit-packed mask crops (the merge's input)
-    blob  uint8   (bytes,): optional COCO RLE strings, concatenated"""
+    blob  uint8   (bytes,): optional COCO RLE strings, concatenated
+    rles: a list of `bytes`, one per record of `keep`, or the pair (uint8 blob, lengths) infer_tiles(rle=True) returns as rec['rle']: the
+    strings of ALL records of `rec` concatenated in record order, of which the records `keep` are taken here."""
     import torch
+    if isinstance(rles, tuple):                                    # the device's blob + lengths: one gather, no per-record objects
+        ball, lall = np.asarray(rles[0], np.uint8), np.asarray(rles[1], np.int64)
+        kp_r = np.arange(len(lall), dtype=np.int64) if keep is None else np.asarray(list(keep), np.int64)
+        rle_len = lall[kp_r]
+        src = (np.cumsum(lall) - lall)[kp_r]
+        rle_blob = ball[np.arange(int(rle_len.sum()), dtype=np.int64) + np.repeat(src - (np.cumsum(rle_len) - rle_len), rle_len)]
+    else:
+        rle_len = [len(r) for r in rles] if rles else 0
+        rle_blob = np.frombuffer(b''.join(rles), np.uint8).copy() if rles else np.zeros(0, np.uint8)
     if isinstance(rec['mask'], PackedMasks) and rec['mask'].arrays is not None:          # records of the packed path: whole-slide array operations
         a = rec['mask'].arrays
         kp = np.arange(len(a['score']), dtype=np.int64) if keep is None else np.asarray(list(keep), np.int64)
@@ -397,13 +461,12 @@ def pack_records(rec, keep=None, tile_base=0, rles=None):
         head = np.zeros((n, 9), np.float64)
         vflat, vn = a['rings'].take(kp)
         head[:, :4], head[:, 4], head[:, 5], head[:, 6], head[:, 7] = a['box'][kp], a['score'][kp], a['label'][kp], vn, tile_base + a['tile'][kp]
-        head[:, 8] = [len(r) for r in rles] if rles else 0
+        head[:, 8] = rle_len
         verts = vflat.astype(np.int32).reshape(-1, 2)
         m = rec['mask'].subset(kp)
         crops = np.concatenate([m.boxes.astype(np.int64), m.areas[:, None].astype(np.int64), m.off[:, None]], 1) if n else np.zeros((0, 6), np.int64)
-        blob = np.frombuffer(b''.join(rles), np.uint8).copy() if rles else np.zeros(0, np.uint8)
         return [torch.from_numpy(head), torch.from_numpy(verts), torch.from_numpy(crops), torch.from_numpy(m.bits.view(np.int32).copy()),
-                torch.from_numpy(blob)]
+                torch.from_numpy(rle_blob)]
     keep = list(range(len(rec['score']))) if keep is None else list(keep)
     n = len(keep)
     head = np.zeros((n, 9), np.float64)
@@ -411,15 +474,14 @@ def pack_records(rec, keep=None, tile_base=0, rles=None):
         head[k, :4] = rec['box'][i]
         head[k, 4], head[k, 5], head[k, 6] = rec['score'][i], rec['label'][i], len(rec['ring'][i])
         head[k, 7] = tile_base + rec['tile'][i]
-        head[k, 8] = len(rles[k]) if rles else 0
+    head[:, 8] = rle_len
     verts = np.concatenate([rec['ring'][i] for i in keep], 0).astype(np.int32) if n else np.zeros((0, 2), np.int32)
     mb, ma, mbits, moff = pack_masks([rec['mask'][i] for i in keep])
     crops = np.concatenate([mb.astype(np.int64), ma[:, None].astype(np.int64), moff[:, None]], 1) if n else np.zeros((0, 6), np.int64)
     if n == 0:
         mbits = np.zeros(0, np.uint32)
-    blob = np.frombuffer(b''.join(rles), np.uint8).copy() if rles else np.zeros(0, np.uint8)
     return [torch.from_numpy(head), torch.from_numpy(verts), torch.from_numpy(crops), torch.from_numpy(mbits.view(np.int32).copy()),
-            torch.from_numpy(blob)]
+            torch.from_numpy(rle_blob)]
 
 
 def merge_gathered(gathered, overlap_threshold=0.05, device=0, overlap='polygon'):

@@ -72,6 +72,8 @@ def build_parser():
     p.add_argument('--overlap_threshold', type=float, default=0.05)
     p.add_argument('--seg-on', choices=('host', 'gpu'), default='host', dest='seg_on',
                    help="where --seg / --patch compute the tissue mask and select the tiles: 'host' (numpy / scipy) or 'gpu' (rank 0's own device; same files)")
+    p.add_argument('--rle-on', choices=('host', 'gpu'), default='host', dest='rle_on',
+                   help="where --mode coco / all encode the run-length masks: 'host' (numpy + a Python loop per nucleus) or 'gpu' (every rank's own device; same files)")
     return p
 
 
@@ -87,14 +89,17 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
     coords = bag.coords
     lo, hi = parallel.shard_range(len(bag), rank, world)
     tiles = bag.view(lo, hi)                                  # this rank's tiles only, cut / decoded a batch at a time while earlier batches run
-    rec = wsi.infer_tiles(model, tiles, coords[lo:hi], args.batch_size)
+    want = lambda m: args.mode in (m, 'all')
+    rle_gpu = want('coco') and args.rle_on == 'gpu'                  # strings and boxes come off the device with the records (nuhtc_rle_encode)
+    rec = wsi.infer_tiles(model, tiles, coords[lo:hi], args.batch_size, rle=rle_gpu)
     # contours are traced on the rank that owns the tile; two variable-length gathers: records, then ring vertices
     rings = rec['ring']                                              # traced on the GPU (nuhtc_mask_contours)
     keep = [i for i, r in enumerate(rings) if len(r) >= 3]          # reference :536 tests the CLOSED contour (mask2inst appends the first point): only one-pixel contours go
-    want = lambda m: args.mode in (m, 'all')
     P = bag.patch_size
     rles = []
-    if want('coco'):                                                  # RLE of the instance inside its tile (:611-613)
+    if rle_gpu:
+        rles = rec['rle']
+    elif want('coco'):                                               # RLE of the instance inside its tile (:611-613)
         from nuhtc_amd import cocomask
         for i in keep:
             crop, x0, y0 = rec['mask'][i]
@@ -122,13 +127,23 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
         lab = h0[:, 5].astype(np.int32)
         ptxt, pstart = contours.ring_features_text(v0, h0[:, 6].astype(np.int64), lab, h0[:, 4], model.CLASSES)
         parts += [torch.from_numpy(ptxt), torch.from_numpy(pstart), torch.from_numpy(contours.point_features_text(h0[:, :4], lab, h0[:, 4], model.CLASSES))]
+    if rle_gpu:                                                       # bbox / area of the annotations: rank 0 parses no string
+        kp = np.asarray(keep, np.int64)
+        parts.append(torch.from_numpy(np.ascontiguousarray(rec['rle_bbox'][kp], np.int32)))
+        parts.append(torch.tensor([rec['rle_host']], dtype=torch.int32))
     parts.append(torch.tensor([rank], dtype=torch.int32))           # who sent it (printed by rank 0)
     gathered = parallel.gather_blobs([t.to(dev) for t in parts])
     heads = [g[0] for g in gathered]
     vparts = [g[1] for g in gathered]
     bparts = [g[4] if want('coco') else None for g in gathered]
+    xparts = [g[-3].cpu().numpy() if rle_gpu else None for g in gathered]
     if rank != 0:
         return
+    if rle_gpu:
+        print(f'--rle-on gpu: {int(sum(int(g[-2][0]) for g in gathered))} of {int(sum(len(g[0]) for g in gathered))} run-length masks fell back to the host encoder',
+              file=sys.stderr)
+    if want('coco'):
+        from nuhtc_amd import cocomask
     from nuhtc_amd import outputs
     name = slide_id
     out_dir = os.path.join(args.save_dir, 'nuclei', name)
@@ -136,13 +151,13 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
     dsa, annts, per_tile = [], [], {}
     sql = outputs.SqlContourWriter(os.path.join(out_dir, name + '_dql.db')) if want('sql') else None
     n_records = int(sum(len(h) for h in heads))
-    for h, v, bl in zip(heads, vparts, bparts):
+    for h, v, bl, xb in zip(heads, vparts, bparts, xparts):
         if not (want('dsa') or want('coco') or sql):       # the per-record loop serves the other document kinds only
             break
         h, v = h.cpu().numpy(), v.cpu().numpy()
         bl = bl.cpu().numpy().tobytes() if bl is not None else b''
         off = boff = 0
-        for row in h:
+        for r, row in enumerate(h):
             nv, annidx, nb = int(row[6]), int(row[7]), int(row[8])
             ring = v[off:off + nv].astype(np.int64)
             off += nv
@@ -154,7 +169,7 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
             if want('coco'):
                 rle = {'size': [P, P], 'counts': bl[boff:boff + nb].decode('ascii')}
                 boff += nb
-                bbox = cocomask.to_bbox(rle)
+                bbox = [float(c) for c in xb[r]] if xb is not None else cocomask.to_bbox(rle)
                 annts.append({'bbox': bbox, 'area': bbox[2] * bbox[3], 'image_id': annidx, 'category_id': label, 'id': len(annts),
                               'iscrowd': 0, 'segmentation': rle})
             if sql:
@@ -201,6 +216,11 @@ def main(argv=None):
     from nuhtc_amd.apis import init_detector
     if args.seg_on == 'gpu' and not torch.cuda.is_available():
         raise SystemExit('--seg-on gpu: no GPU is visible (there is no fallback; --seg-on host is the host route)')
+    if args.rle_on == 'gpu' and args.mode in ('coco', 'all'):
+        if not torch.cuda.is_available():
+            raise SystemExit('--rle-on gpu: no GPU is visible (there is no fallback; --rle-on host is the host route)')
+        if args.patch_size % 32:
+            raise SystemExit(f'--rle-on gpu: --patch_size {args.patch_size} is not a multiple of 32 (the device encodes bit-packed rows of 32 pixels; use --rle-on host)')
     # the process group is formed AFTER seg_and_patch: rank 0's host phase (segmentation, masks, patching, stitching of every slide of the
     # folder) has no time bound, and a rank waiting in an RCCL barrier is aborted by the watchdog after 10 minutes
     rank, local_rank, world = parallel.env_ranks()
