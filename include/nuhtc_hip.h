@@ -521,6 +521,56 @@ int nuhtc_op_eval_render(nuhtc_engine* e, const uint32_t* masks, const int32_t* 
 int nuhtc_op_eval_joint(nuhtc_engine* e, const int32_t* true_maps, int Ct, const int32_t* pred_maps, int Cp, int B, int H, int W, int C, int cap,
                         int32_t* joint, int32_t* counters, void* stream);
 
+/* Scoring images larger than a tile on the device (csrc/stitch.hip): the protocol of `CoNSePCocoDataset.evaluate`
+ * (nuhtc/datasets/WSI_coco_CoNSeP.py:117-426) -- overlapping tiles, detections near an inner tile edge dropped, the rest shifted into the image
+ * frame, one mask-NMS per image, statistics against the image's instance map -- up to the integer tables nuhtc_amd.evaluation.*_tables finish.
+ * nuhtc_config is unchanged (no ABI bump).
+ * A store holds the candidates of n_img images, all device memory: per image cand_cap records -- box [n_img][cand_cap][4] = x0, y0, x1, y1 (exclusive)
+ * of the mask's set pixels in image pixels (zeros for an empty mask), area, score, label, key (int64: (tile location * C + label) * K + slot, the
+ * candidate order of the reference within an image), off (int64 word offset of the crop in the image's pool, -1: it did not fit) -- and
+ * pool [n_img][pool_cap] words of crops in the nuhtc_merge_overlap layout.  counters [n_img][4]: [0] candidates and [1] pool words the image needs so
+ * far (counted past the capacities; the caller zeroes them to start an image), [2] bit 0: candidates, bit 1: crops were dropped, [3] != 0: a label
+ * outside [0, C) or a tile record out of range.  work: scratch of work_cap >= 8 * B * K int32.
+ *   gather : tile_meta [B][8] = image, x offset, y offset, first column, last column, first row, last row (flags), tile location.  Slots
+ *            r < counts[b] with score >= fg_thr (false for NaN) become candidates unless x1 < discard_offset on a tile that is not in the first
+ *            column, x2 > tile - discard_offset on one not in the last, and the same for y1 / y2 and rows (float boxes).  Candidates are numbered
+ *            behind those the image holds, in (tile of the batch, slot) order.  Tiles are square, side % 32 == 0.
+ *            nuhtc_stitch_gather runs after nuhtc_infer on the same `dets`, enqueues on `stream` and does not synchronise.
+ *   pairs  : kept [n_kept] = candidate numbers of one image (the survivors of its mask-NMS in visiting order); gt_map [H][W] = row + 1 of the
+ *            ground-truth instance of a pixel, 0 = none, at most t_cap <= 8192.  area_t [t_cap] = pixels per row, trips [trip_cap][3] = (row,
+ *            position in kept, pixels) of the non-zero intersections, in no particular order.  counters [4]: [0] entries needed, [1] entries
+ *            dropped, [2] a map value, candidate number, box or offset out of range, [3] a prediction met more than 64 rows (its entries are
+ *            incomplete).  The call zeroes counters and area_t.
+ *   render : inst_map, type_map [H][W] = max over the kept masks covering a pixel of position + 1, of label + 1 (`convert_format` 'conic',
+ *            WSI_coco.py:863-906); counters[2] is ORed as above and not cleared.
+ * nuhtc_stitch_* enqueue and return; the nuhtc_op_stitch_* twins are the test entry points on raw arrays (boxes [B][K][5], labels [B][K],
+ * counts [B], masks [B][K][tile][tile / 32]) and synchronise `stream`. */
+typedef struct nuhtc_stitch_store {
+  int32_t n_img, cand_cap, pool_cap, work_cap;
+  int32_t* box;
+  int32_t* area;
+  float* score;
+  int32_t* label;
+  int64_t* key;
+  int64_t* off;
+  uint32_t* pool;
+  int32_t* counters;
+  int32_t* work;
+} nuhtc_stitch_store;
+int nuhtc_stitch_gather(nuhtc_engine* e, const nuhtc_dets* dets, int B, const int32_t* tile_meta, float fg_thr, float discard_offset,
+                        const nuhtc_stitch_store* st, void* stream);
+int nuhtc_stitch_pairs(nuhtc_engine* e, const nuhtc_stitch_store* st, int image, const int32_t* kept, int n_kept, const int32_t* gt_map, int H, int W,
+                       int t_cap, int trip_cap, int32_t* area_t, int32_t* trips, int32_t* counters, void* stream);
+int nuhtc_stitch_render(nuhtc_engine* e, const nuhtc_stitch_store* st, int image, const int32_t* kept, int n_kept, int H, int W, int32_t* inst_map,
+                        int32_t* type_map, int32_t* counters, void* stream);
+int nuhtc_op_stitch_gather(nuhtc_engine* e, const float* boxes, const int32_t* labels, const int32_t* counts, const uint32_t* masks,
+                           const int32_t* tile_meta, int B, int K, int tile, int C, float fg_thr, float discard_offset, const nuhtc_stitch_store* st,
+                           void* stream);
+int nuhtc_op_stitch_pairs(nuhtc_engine* e, const nuhtc_stitch_store* st, int image, const int32_t* kept, int n_kept, const int32_t* gt_map, int H,
+                          int W, int t_cap, int trip_cap, int32_t* area_t, int32_t* trips, int32_t* counters, void* stream);
+int nuhtc_op_stitch_render(nuhtc_engine* e, const nuhtc_stitch_store* st, int image, const int32_t* kept, int n_kept, int H, int W, int32_t* inst_map,
+                           int32_t* type_map, int32_t* counters, void* stream);
+
 /* A HIP stream owned by the engine (valid after nuhtc_finalize) that a caller MAY run this engine on,
  * and should when it keeps several engines busy at once or raises GPU_MAX_HW_QUEUES above the runtime's default of 4: the stream
  * is created next to the engine's two internal side streams, which puts the three on different pipes of the command processor

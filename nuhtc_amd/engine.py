@@ -891,3 +891,114 @@ class Engine:
             out['joint'] = [[(jt[cut[b * (C + 1) + k]:cut[b * (C + 1) + k + 1], 2], jt[cut[b * (C + 1) + k]:cut[b * (C + 1) + k + 1], 3],
                               jt[cut[b * (C + 1) + k]:cut[b * (C + 1) + k + 1], 4]) for k in range(C + 1)] for b in range(B)]
         return out
+
+    # ------------------------------------------------------------------ scoring images larger than a tile (csrc/stitch.hip)
+    def stitch_store(self, n_img, cand_cap=8192, pool_cap=1 << 20, slots=None, guard=0):
+        """Device buffers for the candidates of n_img images (nuhtc_stitch_store): cand_cap records and pool_cap crop words per image, scratch
+        for `slots` detection slots per gather (default: max_batch * max_per_img).  `guard`: extra elements behind every buffer, and every
+        buffer filled with -7, for the tests that check nothing is written at or past a capacity."""
+        slots = int(slots or self.cfg.max_batch * self.cfg.max_per_img)
+        n_img, cand_cap, pool_cap = int(n_img), int(cand_cap), int(pool_cap)
+        fill = -7 if guard else 0
+        mk = lambda n, dt: torch.full((n + guard,), fill, dtype=dt, device=self.device)
+        t = dict(box=mk(n_img * cand_cap * 4, torch.int32), area=mk(n_img * cand_cap, torch.int32), score=mk(n_img * cand_cap, torch.float32),
+                 label=mk(n_img * cand_cap, torch.int32), key=mk(n_img * cand_cap, torch.int64), off=mk(n_img * cand_cap, torch.int64),
+                 pool=mk(n_img * pool_cap, torch.int32), work=mk(slots * 8, torch.int32),
+                 counters=torch.zeros(n_img * 4, dtype=torch.int32, device=self.device))
+        st = hip.StitchStore(n_img=n_img, cand_cap=cand_cap, pool_cap=pool_cap, work_cap=slots * 8, **{k: v.data_ptr() for k, v in t.items()})
+        return dict(t, struct=st, n_img=n_img, cand_cap=cand_cap, pool_cap=pool_cap)
+
+    def stitch_reset(self, store, image=None):
+        """Starts image slot `image` (all slots: None) of a store afresh, on the current stream."""
+        c = store['counters'].view(-1, 4)
+        (c if image is None else c[image]).zero_()
+
+    def op_stitch_gather(self, boxes, labels, counts, masks, meta, C, store, fg_thr=0.1, discard_offset=4):
+        """nuhtc_op_stitch_gather on raw device arrays: boxes (B, K, 5) float32, labels (B, K), counts (B,), masks (B, K, T, T // 32) int32
+        words, meta (B, 8) int32 (stitch.tile_meta)."""
+        B, K, T, _ = masks.shape
+        boxes, meta = boxes.contiguous().float(), self._i32(meta)
+        self._check(self.lib.nuhtc_op_stitch_gather(self.h, boxes.data_ptr(), self._i32(labels).data_ptr(), self._i32(counts).data_ptr(), masks.data_ptr(),
+                                                    meta.data_ptr(), B, K, T, int(C), float(fg_thr), float(discard_offset),
+                                                    ctypes.byref(store['struct']), self._stream()))
+
+    def stitch_gather_async(self, B, meta_dev, store, fg_thr=0.1, discard_offset=4):
+        """After infer_async, on the current stream and without synchronising: the detections of the batch's tiles that pass the candidate
+        rules of the stitched protocol are appended to their images in `store` (nuhtc_stitch_gather).  meta_dev: (B, 8) int32 device tensor
+        of stitch.tile_meta records."""
+        if tuple(meta_dev.shape) != (B, 8) or meta_dev.dtype != torch.int32 or not meta_dev.is_contiguous():
+            raise ValueError('stitch_gather_async: meta_dev must be a contiguous int32 (B, 8) device tensor')
+        self._stitch_meta = meta_dev          # (kept alive until the next call)
+        self._check(self.lib.nuhtc_stitch_gather(self.h, ctypes.byref(self.dets), B, meta_dev.data_ptr(), float(fg_thr), float(discard_offset),
+                                                 ctypes.byref(store['struct']), self._stream()))
+
+    def stitch_read(self, store, image):
+        """The candidate records of a gathered image as numpy, in the REFERENCE's candidate order (tile location, class, slot): dict(n,
+        need = (candidates, pool words) the image needs, overflow, dev: the device number of each candidate, box, area, score, label, off).
+        Synchronises.  Raises when a label or tile record was out of range."""
+        cnt = store['counters'].view(-1, 4)[image].cpu().numpy()
+        if cnt[3]:
+            raise HipError('stitch: a label outside [0, num_classes) or a tile record out of range')
+        cap = store['cand_cap']
+        n = int(min(max(cnt[0], 0), cap))
+        sl = slice(image * cap, image * cap + n)
+        order = np.argsort(store['key'][sl].cpu().numpy(), kind='stable')
+        f = lambda k: store[k][sl].cpu().numpy()[order]
+        return dict(n=n, need=(int(cnt[0]), int(cnt[1])), overflow=bool(cnt[2]) or cnt[0] > cap or cnt[1] > store['pool_cap'], dev=order.astype(np.int32),
+                    box=store['box'][image * cap * 4:(image * cap + n) * 4].view(-1, 4).cpu().numpy()[order].astype(np.int64), area=f('area').astype(np.int64),
+                    score=f('score'), label=f('label').astype(int), off=f('off'))
+
+    def stitch_nms(self, store, image, rec, thr, height, width):
+        """The image-level mask-NMS on the device: nuhtc_merge_overlap(NUHTC_OVERLAP_MASK) over the image's crops.  Its tie rule is lower
+        index first and the evaluation's is higher candidate index first, so the records are fed in reversed candidate order.  An empty mask
+        overlaps nothing and is kept (merge_overlap never keeps one, so they stay out of its input).  thr >= 0.
+        -> kept candidates, as indices into `rec`, in visiting order (descending score, ties descending index)."""
+        if not thr >= 0:
+            raise ValueError('stitch_nms: the threshold must not be negative')
+        n = rec['n']
+        alive = rec['area'] == 0
+        idx = np.nonzero(~alive)[0][::-1]          # reversed candidate order
+        if len(idx):
+            dev = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(dt).to(self.device)
+            keep = torch.zeros(len(idx), dtype=torch.uint8, device=self.device)
+            pool = store['pool'][image * store['pool_cap']:(image + 1) * store['pool_cap']]
+            boxes, scores, areas, offs = dev(rec['box'][idx], torch.int32), dev(rec['score'][idx], torch.float32), dev(rec['area'][idx], torch.int32), dev(rec['off'][idx], torch.int64)
+            rc = self.lib.nuhtc_merge_overlap(self.device.index, boxes.data_ptr(), scores.data_ptr(), areas.data_ptr(), pool.data_ptr(), offs.data_ptr(),
+                                              len(idx), store['pool_cap'], hip.OVERLAP_MASK, float(thr), 0, 0, int(width), int(height), keep.data_ptr(),
+                                              self._stream())
+            if rc:
+                raise HipError(f'nuhtc_merge_overlap failed ({rc})')
+            alive[idx[keep.cpu().numpy().astype(bool)]] = True
+        order = np.argsort(rec['score'], kind='stable')[::-1]
+        return order[alive[order]] if n else np.zeros(0, int)
+
+    def _stitch_kept(self, rec, kept):
+        return torch.as_tensor(np.ascontiguousarray(rec['dev'][kept]).astype(np.int32)).to(self.device) if len(kept) else torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def stitch_pairs(self, store, image, rec, kept, gt_map_dev, t_cap, trip_cap, guard=0):
+        """Pair tables of the kept predictions of an image against its ground-truth map (nuhtc_op_stitch_pairs): gt_map_dev (H, W) int32 row + 1
+        -> dict(area_t (t_cap,), pairs (rows, positions, pixels), n: entries needed, overflow: entries dropped or a prediction with more than
+        64 partners, partners: the latter alone).  Raises on a value out of range.  Synchronises."""
+        H, W = gt_map_dev.shape
+        dev = dict(dtype=torch.int32, device=self.device)
+        area_t, trips, counters = torch.zeros(int(t_cap), **dev), torch.full((int(trip_cap) + guard, 3), -7, **dev), torch.zeros(4, **dev)
+        k = self._stitch_kept(rec, kept)
+        self._check(self.lib.nuhtc_op_stitch_pairs(self.h, ctypes.byref(store['struct']), int(image), k.data_ptr(), len(kept), gt_map_dev.data_ptr(), H, W,
+                                                   int(t_cap), int(trip_cap), area_t.data_ptr(), trips.data_ptr(), counters.data_ptr(), self._stream()))
+        c = counters.cpu().numpy()
+        if c[2]:
+            raise HipError('stitch_pairs: a ground-truth value outside [0, t_cap], or a candidate record out of range')
+        tr = trips[:min(int(c[0]), int(trip_cap))].cpu().numpy()
+        return dict(area_t=area_t.cpu().numpy(), pairs=(tr[:, 0], tr[:, 1], tr[:, 2]), n=int(c[0]), overflow=bool(c[1] or c[3] or c[0] > trip_cap),
+                    partners=bool(c[3]), guard=trips[int(trip_cap):])
+
+    def stitch_render(self, store, image, rec, kept, height, width):
+        """inst_map, type_map (H, W) int32 device tensors of the kept predictions (nuhtc_op_stitch_render).  Synchronises."""
+        dev = dict(dtype=torch.int32, device=self.device)
+        inst, typ, counters = torch.empty(height, width, **dev), torch.empty(height, width, **dev), torch.zeros(4, **dev)
+        k = self._stitch_kept(rec, kept)
+        self._check(self.lib.nuhtc_op_stitch_render(self.h, ctypes.byref(store['struct']), int(image), k.data_ptr(), len(kept), int(height), int(width),
+                                                    inst.data_ptr(), typ.data_ptr(), counters.data_ptr(), self._stream()))
+        if int(counters[2]):
+            raise HipError('stitch_render: a candidate record out of range')
+        return inst, typ

@@ -117,6 +117,15 @@ class EvalArgs(ctypes.Structure):
     ]
 
 
+class StitchStore(ctypes.Structure):
+    """nuhtc_stitch_store: the candidate records and crop pools of the images being stitched (csrc/stitch.hip)."""
+    _fields_ = [
+        ('n_img', ctypes.c_int32), ('cand_cap', ctypes.c_int32), ('pool_cap', ctypes.c_int32), ('work_cap', ctypes.c_int32),
+        ('box', ctypes.c_void_p), ('area', ctypes.c_void_p), ('score', ctypes.c_void_p), ('label', ctypes.c_void_p), ('key', ctypes.c_void_p),
+        ('off', ctypes.c_void_p), ('pool', ctypes.c_void_p), ('counters', ctypes.c_void_p), ('work', ctypes.c_void_p),
+    ]
+
+
 class Dets(ctypes.Structure):
     _fields_ = [('boxes', ctypes.c_void_p), ('labels', ctypes.c_void_p), ('counts', ctypes.c_void_p),
                 ('masks', ctypes.c_void_p), ('areas', ctypes.c_void_p), ('keep', ctypes.c_void_p)]
@@ -131,6 +140,7 @@ EXPORTS = ['nuhtc_default_config', 'nuhtc_create', 'nuhtc_destroy', 'nuhtc_last_
            'nuhtc_op_conv3', 'nuhtc_op_window_msa', 'nuhtc_op_bbox_tail', 'nuhtc_op_det_post', 'nuhtc_op_paste', 'nuhtc_op_tile_post',
            'nuhtc_op_rpn_select', 'nuhtc_op_nms_levels', 'nuhtc_op_build_rois',
            'nuhtc_eval_batch', 'nuhtc_op_eval_select', 'nuhtc_op_eval_pairs', 'nuhtc_op_eval_render', 'nuhtc_op_eval_joint',
+           'nuhtc_stitch_gather', 'nuhtc_stitch_pairs', 'nuhtc_stitch_render', 'nuhtc_op_stitch_gather', 'nuhtc_op_stitch_pairs', 'nuhtc_op_stitch_render',
            'nuhtc_tissue_mask', 'nuhtc_points_polygon_test', 'nuhtc_grid_in_contour', 'nuhtc_rle_encode']
 
 _lib = None
@@ -190,6 +200,11 @@ def load():
     lib.nuhtc_op_eval_pairs.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]
     lib.nuhtc_op_eval_render.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
     lib.nuhtc_op_eval_joint.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp]
+    sst = ctypes.POINTER(StitchStore)
+    lib.nuhtc_stitch_gather.argtypes = [vp, ctypes.POINTER(Dets), ci, vp, cf, cf, sst, vp]
+    lib.nuhtc_op_stitch_gather.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, sst, vp]
+    lib.nuhtc_stitch_pairs.argtypes = lib.nuhtc_op_stitch_pairs.argtypes = [vp, sst, ci, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp]
+    lib.nuhtc_stitch_render.argtypes = lib.nuhtc_op_stitch_render.argtypes = [vp, sst, ci, vp, ci, ci, ci, vp, vp, vp, vp]
     lib.nuhtc_mask_contours.argtypes = [vp, ctypes.POINTER(Dets), ci, ci, vp, vp, vp]
     lib.nuhtc_merge_overlap.argtypes = [ci, vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int64, ci, ctypes.c_double, ci, ci, ci, ci, vp, vp]
     lib.nuhtc_tissue_mask.argtypes = [ci, vp, ci, ci, ctypes.c_int64, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]
