@@ -468,6 +468,44 @@ int nuhtc_op_build_rois(nuhtc_engine* e, const float* cc_boxes, const int32_t* c
                         int rpn_cap, const float* fixed, int n_fixed, int B, int cap, float* rois, int32_t* roi_off, int32_t* roi_cnt, int32_t* total,
                         void* stream);
 
+/* The block of nuhtc_infer that turns RoIs into head features, op by op, as test entry points (csrc/roi.hip: the attention-pool tables, roi_classify_kernel,
+ * the LDS-tile, stream, big-box and giant kernels of the 7 x 7 features and roi_feat14_kernel).  Each fills the parameter block nuhtc_infer fills and
+ * calls the same function; scratch is allocated per call; *r_dev and the image index of every live RoI are read back and checked first.  All pointers are
+ * device memory.  Each synchronises `stream` and needs a finalized engine.
+ * nuhtc_op_attn_pool: level map F [B][HW][64] -> G [B][HW][64], G[b][q] = mean_p F[b][p] * (relu(cos(F[b][q], F[b][p]) - tau) + tau), by `route`:
+ *   NUHTC_AP_AUTO what nuhtc_infer picks (attn_pool_fp16_kernel with nuhtc_config.att_pool_fp16, else the cosine-epilogue GEMM pair where HW % 32 == 0
+ *   and attn_pool_kernel otherwise), or one of them by name.  NUHTC_E_INVALID: a null pointer, B outside 1..256, HW outside 1..16384 or B * HW * HW >
+ *   2^28, an unknown route, NUHTC_AP_GEMM with HW % 32 != 0.
+ * nuhtc_op_roi_feats: rois [cap][5] (image, x1, y1, x2, y2 in network pixels; rows below *r_dev are live) on x0 [B][H[0]][W[0]][64] (stride 4),
+ *   x1 (stride 8, H[1] x W[1]), sem and x0sem = fp32 x0 + sem (both H[0] x W[0]) and the tables G2 [B][H[2] * W[2]][64], G3 -> out [cap][P * P][64]:
+ *   RoIAlign(x0) + RoIAlign(x1) + G2[centre] + G3[centre] + the semantic RoIAlign(14, adaptive), average-pooled 2 x 2 for P = 7.  P = 7 also gives
+ *   fb_flag [cap] (the kernel form of each RoI: 0 / 3 LDS tiles small / large, 1 stream, 2 big-box, 4 giant) and counts [3] (the lengths of the big,
+ *   mid-size and giant lists); it runs with the side streams and events of the latency schedule and with the list forms (stream_few, the big-box
+ *   split) as nuhtc_infer sets them.  Rows from *r_dev on are not written.  NUHTC_E_INVALID: a null pointer, P not 7 or 14, B outside 1..256, cap
+ *   outside 1..2^20, a level size outside 1..4096, *r_dev outside 0..cap, a live RoI whose image index is not an integer in 0..B-1 or with a
+ *   coordinate that is not finite. */
+#define NUHTC_AP_AUTO 0
+#define NUHTC_AP_GEMM 1
+#define NUHTC_AP_KERNEL 2
+#define NUHTC_AP_FP16 3
+int nuhtc_op_attn_pool(nuhtc_engine* e, const float* F, int B, int HW, float tau, int route, float* G, void* stream);
+typedef struct nuhtc_roi_feats_args {
+  const float* x0;
+  const float* x1;
+  const float* sem;
+  const float* x0sem;
+  const float* G2;
+  const float* G3;
+  const float* rois;
+  const int32_t* r_dev;
+  int32_t B, cap, P;
+  int32_t H[4], W[4];
+  float* out;
+  uint8_t* fb_flag;
+  int32_t* counts;
+} nuhtc_roi_feats_args;
+int nuhtc_op_roi_feats(nuhtc_engine* e, const nuhtc_roi_feats_args* a, void* stream);
+
 /* Scoring a batch on the device (csrc/eval.hip).  Replaces what the reference's `WSIDataset.evaluate` (nuhtc/datasets/WSI_coco.py:278-545) and
  * tools/analysis_tools/pannuke/compute_stats.py compute from decoded masks, up to the integer tables the metrics are functions of: the host
  * finishes with nuhtc_amd.evaluation.*_tables.  nuhtc_config is unchanged (no ABI bump).

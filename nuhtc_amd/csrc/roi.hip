@@ -486,7 +486,9 @@ __global__ __launch_bounds__(64) void roi_feat7_stream_kernel(RoiFeatParams p) {
 #pragma unroll
     for (int k = 0; k < 49; ++k) acc[k] = 0.f;
     const RoiGeom g0 = roi_geom(roi, 0.25f, 7, 2), g1 = roi_geom(roi, 0.125f, 7, 2), gs = roi_geom(roi, 0.25f, 14, 0);
-    const bool sem2 = gs.gw == 2 || gs.gh == 2;          // (classify guarantees gw, gh in {1, 2})
+    // the semantic grid differs from one sample per 14x14 bin (classify guarantees gw, gh <= 2; a box of zero width or height has gw or gh = 0:
+    // RoIAlign then takes no sample on that axis and the term is 0 -- sm_accumulate returns at once for 2 * 0 samples)
+    const bool sem2 = gs.gw != 1 || gs.gh != 1;
     // FPN level 0 (+ the semantic term when it is sampled at the same points: one sample per 14x14 bin), level 1, and -- when
     // the semantic 14x14 grid takes 2 samples per bin on an axis -- the semantic map itself: average-pooled 2x2 that is 2*g
     // samples per 7x7 bin and axis on the 14-grid's geometry (a 7-grid bin is two 14-grid bins)
@@ -627,7 +629,7 @@ __global__ __launch_bounds__(64 * SMF_W) void roi_feat7_stream_few_kernel(RoiFea
 #pragma unroll
     for (int k = 0; k < 49; ++k) acc[k] = 0.f;
     const RoiGeom g0 = roi_geom(roi, 0.25f, 7, 2), g1 = roi_geom(roi, 0.125f, 7, 2), gs = roi_geom(roi, 0.25f, 14, 0);
-    const bool sem2 = gs.gw == 2 || gs.gh == 2;
+    const bool sem2 = gs.gw != 1 || gs.gh != 1;          // (see roi_feat7_stream_kernel)
     for (int m = 0; m < (sem2 ? 3 : 2); ++m) {
       const float* map = m == 0 ? (sem2 ? p.x0 : p.x0sem) : m == 1 ? p.x1 : p.sem;
       const RoiGeom& g = m == 0 ? g0 : m == 1 ? g1 : gs;
@@ -991,8 +993,9 @@ __global__ __launch_bounds__(1024) void roi_classify_kernel(RoiFeatParams p) {
     const bool sem_g1 = gs.gw == 1 && gs.gh == 1;
     const LevelPlan l0 = plan_level(g0, 7, 2, p.H0, p.W0, TP0, lane);
     const LevelPlan l1 = plan_level(g1, 7, 2, p.H1, p.W1, TP1, lane);
-    // 0: LDS tiles; 1: stream kernel (at most 2x2 semantic samples per 14x14 bin, sides up to SM_MAXSIDE px: footprints of at
-    // most 30 x 30 pixels on stride 4, bins spanning at most SM_J pixels); 2: one block per bin (big proposals)
+    // 0: LDS tiles; 1: stream kernel (at most 2x2 semantic samples per 14x14 bin -- 0, 1 or 2 per axis: a box of zero width or height has none
+    // -- and sides up to SM_MAXSIDE px: footprints of at most 30 x 30 pixels on stride 4, bins spanning at most SM_J pixels); 2: one block per
+    // bin (big proposals)
     const float rwn = roi[3] - roi[1], rhn = roi[4] - roi[2];
     int cls = (sem_g1 && l0.ok && l1.ok) ? 0 : (gs.gw <= 2 && gs.gh <= 2 && rwn <= (float)SM_MAXSIDE && rhn <= (float)SM_MAXSIDE) ? 1 : 2;
     // class 0 is split by footprint: 0 = fits the small tiles (8x8 / 5x5 pixels: boxes up to ~24 px, the usual nucleus), 3 = needs

@@ -187,6 +187,44 @@ int alloc_roi_workspace(nuhtc_engine* e) {
   return 0;
 }
 
+// the route NUHTC_AP_AUTO stands for: the reference-on-CUDA fp16 arithmetic with the switch, else the GEMM pair where HW % 32 == 0, else attn_pool_kernel
+static int attn_pool_route(const nuhtc_engine* e, int HW, int route) {
+  return route != NUHTC_AP_AUTO ? route : e->cfg.att_pool_fp16 ? NUHTC_AP_FP16 : HW % 32 == 0 ? NUHTC_AP_GEMM : NUHTC_AP_KERNEL;
+}
+// One attention-pool table G [B][HW][64] of a level map F [B][HW][64] (roi_extractors_cus.py:220-238), by `route` (NUHTC_AP_*; AUTO: the reference-on-CUDA
+// fp16 arithmetic with the switch, else the GEMM pair where HW % 32 == 0 and attn_pool_kernel otherwise).  inv [B][HW], S [B][HW][HW], Ft [B][64][HW]:
+// scratch of the GEMM route.  Also nuhtc_op_attn_pool.
+static int attn_pool_table(nuhtc_engine* e, const float* F, float* G, int B, int HW, float tau, int route, float* inv, float* S, float* Ft, hipStream_t s) {
+  route = attn_pool_route(e, HW, route);
+  if (route == NUHTC_AP_FP16) {
+    RUN(launch_attn_pool_fp16(F, G, B, HW, tau, s));      // the reference-on-CUDA rounding (roi_extractors_cus.py:203,231)
+  } else if (route == NUHTC_AP_GEMM) {
+    if (HW % 32 != 0) FAIL(e, NUHTC_E_INVALID, "attention pool: the GEMM route needs HW % 32 == 0");
+    // S = relu(cos(F_q, F_p) - tau) + tau as one batched GEMM F·Fᵀ with the cosine epilogue, then G = S·F / HW
+    RUN(launch_rownorm_inv(F, inv, B * HW, 64, s));
+    GemmParams p1 = gp(F, F, nullptr, S, HW, HW, 64);
+    p1.act = ACT_COS; p1.cos_ri = inv; p1.cos_rj = inv; p1.cos_tau = tau;
+    p1.batch = B; p1.sA = (long long)HW * 64; p1.sW = (long long)HW * 64; p1.sC = (long long)HW * HW; p1.sRi = HW; p1.sRj = HW;
+    RUN(egemm(e, p1, s));
+    RUN(launch_transpose(F, Ft, B, HW, 64, s));
+    GemmParams p2 = gp(S, Ft, nullptr, G, HW, 64, HW);
+    p2.alpha = 1.0f / (float)HW;
+    p2.batch = B; p2.sA = (long long)HW * HW; p2.sW = (long long)HW * 64; p2.sC = (long long)HW * 64;
+    RUN(egemm(e, p2, s));
+  } else if (route == NUHTC_AP_KERNEL) {
+    RUN(launch_attn_pool(F, G, B, HW, tau, s));
+  } else FAIL(e, NUHTC_E_INVALID, "attention pool: unknown route");
+  return 0;
+}
+
+// the list forms of the P = 7 RoI features as the engine sets them (also nuhtc_op_roi_feats); big_part: [BIG_SPLIT_MAX][3][49][64]
+static void roi_feat_modes(RoiFeatParams& fp, float* big_part) {
+  static const int& stream_few = dev_knob_ref("STREAM_FEW", 1);
+  static const int& big_split = dev_knob_ref("BIG_SPLIT", 1);
+  fp.stream_few = stream_few;
+  fp.big_part = big_split ? big_part : nullptr; fp.big_split_max = BIG_SPLIT_MAX;
+}
+
 int run_roi_path(nuhtc_engine* e, int B, const float* rois_fixed, int n_rois, int n_dets, hipStream_t s, const nuhtc_dets* out) {
   const nuhtc_config& c = e->cfg;
   RoiWs* w = e->rw;
@@ -227,27 +265,8 @@ int run_roi_path(nuhtc_engine* e, int B, const float* rois_fixed, int n_rois, in
   }
   const bool use_cc = !fixed && c.watershed_proposal && c.max_cc_proposals > 0;
   // ---- attention-pool tables for levels 2, 3 (roi_extractors_cus.py:220-238): independent of the proposals
-  for (int l = 2; l < 4; ++l) {
-    const int HW = e->st[l].H * e->st[l].W;
-    float* G = l == 2 ? w->G2 : w->G3;
-    if (c.att_pool_fp16) {
-      RUN(launch_attn_pool_fp16(e->x[l], G, B, HW, c.att_thres, s));      // the reference-on-CUDA rounding (roi_extractors_cus.py:203,231)
-    } else if (HW % 32 == 0) {
-      // S = relu(cos(F_q, F_p) - tau) + tau as one batched GEMM F·Fᵀ with the cosine epilogue, then G = S·F / HW
-      RUN(launch_rownorm_inv(e->x[l], w->ap_inv, B * HW, 64, s));
-      GemmParams p1 = gp(e->x[l], e->x[l], nullptr, w->ap_S, HW, HW, 64);
-      p1.act = ACT_COS; p1.cos_ri = w->ap_inv; p1.cos_rj = w->ap_inv; p1.cos_tau = c.att_thres;
-      p1.batch = B; p1.sA = (long long)HW * 64; p1.sW = (long long)HW * 64; p1.sC = (long long)HW * HW; p1.sRi = HW; p1.sRj = HW;
-      RUN(egemm(e, p1, s));
-      RUN(launch_transpose(e->x[l], w->ap_Ft, B, HW, 64, s));
-      GemmParams p2 = gp(w->ap_S, w->ap_Ft, nullptr, G, HW, 64, HW);
-      p2.alpha = 1.0f / (float)HW;
-      p2.batch = B; p2.sA = (long long)HW * HW; p2.sW = (long long)HW * 64; p2.sC = (long long)HW * 64;
-      RUN(egemm(e, p2, s));
-    } else {
-      RUN(launch_attn_pool(e->x[l], G, B, HW, c.att_thres, s));
-    }
-  }
+  for (int l = 2; l < 4; ++l)
+    RUN(attn_pool_table(e, e->x[l], l == 2 ? w->G2 : w->G3, B, e->st[l].H * e->st[l].W, c.att_thres, NUHTC_AP_AUTO, w->ap_inv, w->ap_S, w->ap_Ft, s));
   // join: the side stream carries the RPN branch (convs + heads from run_neck_heads, selection + NMS above)
   if (e->cfg.schedule != NUHTC_SCHED_THROUGHPUT && hipStreamWaitEvent(s, fixed ? e->ev_rpn : e->ev_side, 0) != hipSuccess) FAIL(e, NUHTC_E_HIP, "hipStreamWaitEvent failed");
   RUN(launch_build_rois(use_cc ? w->cc_boxes : nullptr, w->cc_counts, std::max(c.max_cc_proposals, 1), w->rpn_dets, w->rpn_counts, c.rpn_max_per_img,
@@ -258,10 +277,7 @@ int run_roi_path(nuhtc_engine* e, int B, const float* rois_fixed, int n_rois, in
   fp.rois = w->rois; fp.r_dev = w->roi_total; fp.x0 = e->x[0]; fp.x1 = e->x[1]; fp.G2 = w->G2; fp.G3 = w->G3; fp.sem = e->sem_feat; fp.x0sem = e->x0sem;
   fp.H0 = e->st[0].H; fp.W0 = e->st[0].W; fp.H1 = e->st[1].H; fp.W1 = e->st[1].W; fp.H2 = e->st[2].H; fp.W2 = e->st[2].W; fp.H3 = e->st[3].H; fp.W3 = e->st[3].W;
   fp.out = w->feats; fp.fb_count = w->fb_count; fp.fb_list = w->fb_list; fp.list_cap = w->total_cap; fp.mid_list = w->mid_list; fp.fb_flag = w->fb_flag;
-  static const int& stream_few = dev_knob_ref("STREAM_FEW", 1);
-  fp.stream_few = stream_few;
-  static const int& big_split = dev_knob_ref("BIG_SPLIT", 1);
-  fp.big_part = big_split ? w->big_part : nullptr; fp.big_split_max = BIG_SPLIT_MAX;
+  roi_feat_modes(fp, w->big_part);
   // ---- 3-stage cascade (htc_roi_head_cus.py:2255-2280)
   for (int k = 0; k < 3; ++k) {
     auto it = e->bufs.find("rois_stage" + std::to_string(k));
@@ -612,4 +628,70 @@ int nuhtc_op_build_rois(nuhtc_engine* e, const float* cc_boxes, const int32_t* c
   if (rows > cap) FAIL(e, NUHTC_E_INVALID, "build_rois op: more rows than cap");
   const int rc = launch_build_rois(cc_boxes, cc_counts, cc_cap, rpn_dets, rpn_counts, rpn_cap, fixed, n_fixed, rois, roi_off, roi_cnt, total, B, s);
   return op_finish(e, rc, s, "build_rois launch failed", "build_rois kernel failed");
+}
+
+// ---- the RoI feature block, op by op: the attention-pool tables and the fused RoI features of run_roi_path on the caller's maps and boxes
+int nuhtc_op_attn_pool(nuhtc_engine* e, const float* F, int B, int HW, float tau, int route, float* G, void* stream) {
+  if (!e || !F || !G) return NUHTC_E_INVALID;
+  if (!e->finalized) FAIL(e, NUHTC_E_STATE, "nuhtc_op_attn_pool before finalize");
+  if (B < 1 || B > 256) FAIL(e, NUHTC_E_INVALID, "attn_pool op: B out of range (1..256)");
+  if (HW < 1 || HW > 16384 || (long long)B * HW * HW > (1ll << 28)) FAIL(e, NUHTC_E_INVALID, "attn_pool op: HW out of range (1..16384, B * HW * HW <= 2^28)");
+  if (route < NUHTC_AP_AUTO || route > NUHTC_AP_FP16) FAIL(e, NUHTC_E_INVALID, "attn_pool op: unknown route");
+  if (route == NUHTC_AP_GEMM && HW % 32 != 0) FAIL(e, NUHTC_E_INVALID, "attn_pool op: the GEMM route needs HW % 32 == 0");
+  HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
+  route = attn_pool_route(e, HW, route);
+  DevScratch sc;
+  float *inv = nullptr, *S = nullptr, *Ft = nullptr;      // scratch of the GEMM route alone
+  if (route == NUHTC_AP_GEMM) {
+    inv = sc.alloc<float>((size_t)B * HW * sizeof(float));
+    S = sc.alloc<float>((size_t)B * HW * HW * sizeof(float));
+    Ft = sc.alloc<float>((size_t)B * HW * 64 * sizeof(float));
+  }
+  if (!sc.ok()) FAIL(e, NUHTC_E_HIP, "attn_pool op: scratch allocation failed");
+  const int rc = attn_pool_table(e, F, G, B, HW, tau, route, inv, S, Ft, s);
+  const hipError_t he = hipStreamSynchronize(s);
+  if (rc) return rc;                                      // (attn_pool_table named the launch that failed)
+  if (he != hipSuccess) FAIL(e, NUHTC_E_HIP, "attn_pool kernel failed");
+  return 0;
+}
+
+int nuhtc_op_roi_feats(nuhtc_engine* e, const nuhtc_roi_feats_args* a, void* stream) {
+  if (!e || !a || !a->x0 || !a->x1 || !a->sem || !a->x0sem || !a->G2 || !a->G3 || !a->rois || !a->r_dev || !a->out) return NUHTC_E_INVALID;
+  if (a->P == 7 && (!a->fb_flag || !a->counts)) return NUHTC_E_INVALID;
+  if (!e->finalized) FAIL(e, NUHTC_E_STATE, "nuhtc_op_roi_feats before finalize");
+  if (a->P != 7 && a->P != 14) FAIL(e, NUHTC_E_INVALID, "roi_feats op: P must be 7 or 14");
+  if (a->B < 1 || a->B > 256) FAIL(e, NUHTC_E_INVALID, "roi_feats op: B out of range (1..256)");
+  if (a->cap < 1 || a->cap > (1 << 20)) FAIL(e, NUHTC_E_INVALID, "roi_feats op: cap out of range (1..2^20)");
+  for (int l = 0; l < 4; ++l)
+    if (a->H[l] < 1 || a->W[l] < 1 || a->H[l] > 4096 || a->W[l] > 4096) FAIL(e, NUHTC_E_INVALID, "roi_feats op: level size out of range (1..4096)");
+  HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> r;
+  if (!read_ints(a->r_dev, 1, r, s)) FAIL(e, NUHTC_E_HIP, "roi_feats op: reading r_dev failed");
+  if (r[0] < 0 || r[0] > a->cap) FAIL(e, NUHTC_E_INVALID, "roi_feats op: *r_dev exceeds cap");
+  {   // column 0 of a live row is the image the kernels index the maps with; the coordinates go through float -> int conversions
+    std::vector<float> rows((size_t)r[0] * 5);
+    if (r[0] && hipMemcpy(rows.data(), a->rois, rows.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) FAIL(e, NUHTC_E_HIP, "roi_feats op: reading rois failed");
+    for (int i = 0; i < r[0]; ++i) {
+      const float* q = &rows[(size_t)i * 5];
+      if (!(q[0] >= 0.f && q[0] < (float)a->B) || q[0] != floorf(q[0])) FAIL(e, NUHTC_E_INVALID, "roi_feats op: a RoI's image index is outside 0..B-1");
+      for (int j = 1; j < 5; ++j)
+        if (!(fabsf(q[j]) <= 1.0e6f)) FAIL(e, NUHTC_E_INVALID, "roi_feats op: a RoI coordinate is not finite (|v| <= 1e6)");
+    }
+  }
+  DevScratch sc;
+  RoiFeatParams fp;
+  fp.rois = a->rois; fp.r_dev = a->r_dev; fp.x0 = a->x0; fp.x1 = a->x1; fp.G2 = a->G2; fp.G3 = a->G3; fp.sem = a->sem; fp.x0sem = a->x0sem;
+  fp.H0 = a->H[0]; fp.W0 = a->W[0]; fp.H1 = a->H[1]; fp.W1 = a->W[1]; fp.H2 = a->H[2]; fp.W2 = a->W[2]; fp.H3 = a->H[3]; fp.W3 = a->W[3];
+  fp.out = a->out; fp.fb_count = sc.alloc<int>(8 * sizeof(int)); fp.fb_list = sc.alloc<int>((size_t)a->cap * sizeof(int)); fp.list_cap = a->cap;
+  fp.mid_list = sc.alloc<int>((size_t)a->cap * sizeof(int)); fp.fb_flag = a->fb_flag;
+  roi_feat_modes(fp, sc.alloc<float>((size_t)BIG_SPLIT_MAX * 3 * 49 * 64 * sizeof(float)));
+  if (!sc.ok()) FAIL(e, NUHTC_E_HIP, "roi_feats op: scratch allocation failed");
+  int rc;
+  if (a->P == 7) {
+    rc = launch_roi_feat(fp, 7, a->cap, s, e->cfg.schedule == NUHTC_SCHED_THROUGHPUT ? nullptr : e->side, e->ev_fpn, e->ev_side, e->side2, e->ev_side2);
+    if (!rc && hipMemcpyAsync(a->counts, fp.fb_count, 3 * sizeof(int), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = NUHTC_E_HIP;
+  } else rc = launch_roi_feat(fp, 14, a->cap, s);
+  return op_finish(e, rc, s, "roi_feats launch failed", "roi_feats kernel failed");
 }

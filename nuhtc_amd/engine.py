@@ -745,6 +745,44 @@ class Engine:
                                                  r['total'].data_ptr(), self._stream()))
         return r
 
+    # ------------------------------------------------------------------ the RoI feature block, op by op (csrc/roi.hip)
+    def op_attn_pool(self, feat, tau, route='auto', out=None):
+        """One attention-pool table (nuhtc_op_attn_pool): feat (B, HW, 64) or (B, H, W, 64) float32 on the device -> G of the same shape.
+        route 'auto' (what the engine picks), 'gemm' (HW % 32 == 0), 'kernel' or 'fp16'."""
+        if feat.dtype != torch.float32 or feat.shape[-1] != 64 or feat.dim() not in (3, 4):
+            raise ValueError('op_attn_pool: a float32 map (B, HW, 64) or (B, H, W, 64) expected')
+        feat = feat.contiguous()
+        B, HW = int(feat.shape[0]), int(feat.numel() // (feat.shape[0] * 64))
+        if out is None:
+            out = torch.empty_like(feat)
+        self._check(self.lib.nuhtc_op_attn_pool(self.h, feat.data_ptr(), B, HW, float(tau), hip.AP_ROUTES[route], out.data_ptr(), self._stream()))
+        return out
+
+    def op_roi_feats(self, x0, x1, sem, x0sem, G2, G3, rois, r, P, out=None, fb_flag=None):
+        """The fused RoI features (nuhtc_op_roi_feats): x0, sem, x0sem (B, H0, W0, 64), x1 (B, H1, W1, 64), the tables G2 (B, H2, W2, 64), G3
+        (B, H3, W3, 64) and rois (cap, 5) on the device, r: the live rows (int or device int32 (1,)), P 7 or 14.  Returns dict(out (cap, P * P,
+        64), and for P = 7 fb_flag (cap,) uint8 -- the kernel form of each RoI -- and counts (3,): big, mid-size, giant list lengths); rows
+        from r on are left as they are (zero when allocated here)."""
+        maps = (x0, x1, G2, G3)
+        if any(m.dim() != 4 or m.shape[3] != 64 or m.shape[0] != x0.shape[0] or m.dtype != torch.float32 for m in maps + (sem, x0sem)) \
+                or sem.shape != x0.shape or x0sem.shape != x0.shape or rois.dim() != 2 or rois.shape[1] != 5 or rois.dtype != torch.float32:
+            raise ValueError('op_roi_feats: float32 maps (B, H, W, 64), sem / x0sem shaped like x0 and rois (cap, 5) expected')
+        x0, x1, sem, x0sem, G2, G3, rois = (t.contiguous() for t in (x0, x1, sem, x0sem, G2, G3, rois))
+        cap, P = int(rois.shape[0]), int(P)
+        if out is None:
+            out = torch.zeros(max(cap, 1), max(P, 1) ** 2, 64, dtype=torch.float32, device=self.device)
+        if fb_flag is None:
+            fb_flag = torch.zeros(max(cap, 1), dtype=torch.uint8, device=self.device)
+        counts = torch.zeros(3, dtype=torch.int32, device=self.device)
+        r_dev = self._i32(r)
+        a = hip.RoiFeatsArgs(x0=x0.data_ptr(), x1=x1.data_ptr(), sem=sem.data_ptr(), x0sem=x0sem.data_ptr(), G2=G2.data_ptr(), G3=G3.data_ptr(),
+                             rois=rois.data_ptr(), r_dev=r_dev.data_ptr(), B=int(x0.shape[0]), cap=cap, P=P,
+                             H=(ctypes.c_int32 * 4)(*[int(m.shape[1]) for m in (x0, x1, G2, G3)]),
+                             W=(ctypes.c_int32 * 4)(*[int(m.shape[2]) for m in (x0, x1, G2, G3)]),
+                             out=out.data_ptr(), fb_flag=fb_flag.data_ptr(), counts=counts.data_ptr())
+        self._check(self.lib.nuhtc_op_roi_feats(self.h, ctypes.byref(a), self._stream()))
+        return dict(out=out, fb_flag=fb_flag, counts=counts)
+
     # ------------------------------------------------------------------ scoring on the device (csrc/eval.hip)
     def op_eval_select(self, scores, counts, masks, fg_thr, thr, labels=None):
         """Score filter + greedy mask-NMS of `WSIDataset.evaluate` (nuhtc_op_eval_select): scores (B, K) float32, counts (B,), masks

@@ -107,6 +107,19 @@ class TilePostArgs(ctypes.Structure):
     ]
 
 
+class RoiFeatsArgs(ctypes.Structure):
+    """nuhtc_roi_feats_args: the arguments of nuhtc_op_roi_feats (the fused RoI features of the box head, P = 7, and the mask head, P = 14)."""
+    _fields_ = [
+        ('x0', ctypes.c_void_p), ('x1', ctypes.c_void_p), ('sem', ctypes.c_void_p), ('x0sem', ctypes.c_void_p), ('G2', ctypes.c_void_p),
+        ('G3', ctypes.c_void_p), ('rois', ctypes.c_void_p), ('r_dev', ctypes.c_void_p),
+        ('B', ctypes.c_int32), ('cap', ctypes.c_int32), ('P', ctypes.c_int32), ('H', ctypes.c_int32 * 4), ('W', ctypes.c_int32 * 4),
+        ('out', ctypes.c_void_p), ('fb_flag', ctypes.c_void_p), ('counts', ctypes.c_void_p),
+    ]
+
+
+AP_ROUTES = {'auto': 0, 'gemm': 1, 'kernel': 2, 'fp16': 3}      # NUHTC_AP_*
+
+
 class EvalArgs(ctypes.Structure):
     """nuhtc_eval_args: the arguments of nuhtc_eval_batch (selection, pair tables, label maps and joint histograms of a finished inference)."""
     _fields_ = [
@@ -138,7 +151,7 @@ EXPORTS = ['nuhtc_default_config', 'nuhtc_create', 'nuhtc_destroy', 'nuhtc_last_
            'nuhtc_bind_host_thread_pci', 'nuhtc_bind_host_thread_at', 'nuhtc_restore_host_thread', 'nuhtc_op_ln_gemm', 'nuhtc_op_gemm_ln_gemm', 'nuhtc_op_merge_ln_gemm', 'nuhtc_write_ring_features',
            'nuhtc_write_point_features', 'nuhtc_join_features', 'nuhtc_fill_rings', 'nuhtc_features', 'nuhtc_op_cc_mask', 'nuhtc_op_cc_proposals',
            'nuhtc_op_conv3', 'nuhtc_op_window_msa', 'nuhtc_op_bbox_tail', 'nuhtc_op_det_post', 'nuhtc_op_paste', 'nuhtc_op_tile_post',
-           'nuhtc_op_rpn_select', 'nuhtc_op_nms_levels', 'nuhtc_op_build_rois',
+           'nuhtc_op_rpn_select', 'nuhtc_op_nms_levels', 'nuhtc_op_build_rois', 'nuhtc_op_attn_pool', 'nuhtc_op_roi_feats',
            'nuhtc_eval_batch', 'nuhtc_op_eval_select', 'nuhtc_op_eval_pairs', 'nuhtc_op_eval_render', 'nuhtc_op_eval_joint',
            'nuhtc_stitch_gather', 'nuhtc_stitch_pairs', 'nuhtc_stitch_render', 'nuhtc_op_stitch_gather', 'nuhtc_op_stitch_pairs', 'nuhtc_op_stitch_render',
            'nuhtc_tissue_mask', 'nuhtc_points_polygon_test', 'nuhtc_grid_in_contour', 'nuhtc_rle_encode']
@@ -195,6 +208,8 @@ def load():
     lib.nuhtc_op_rpn_select.argtypes = [vp, ctypes.POINTER(vp), i4, i4, ci, ci, ci, ci, cf, vp, vp, vp, vp]
     lib.nuhtc_op_nms_levels.argtypes = [vp, vp, vp, vp, ci, ci, ci, cf, ci, ci, vp, vp, vp, vp]
     lib.nuhtc_op_build_rois.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp]
+    lib.nuhtc_op_attn_pool.argtypes = [vp, vp, ci, ci, cf, ci, vp, vp]
+    lib.nuhtc_op_roi_feats.argtypes = [vp, ctypes.POINTER(RoiFeatsArgs), vp]
     lib.nuhtc_eval_batch.argtypes = [vp, ctypes.POINTER(Dets), ci, ctypes.POINTER(EvalArgs), vp]
     lib.nuhtc_op_eval_select.argtypes = [vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, cf, ctypes.c_double, vp, vp, vp, vp]
     lib.nuhtc_op_eval_pairs.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]
