@@ -182,6 +182,50 @@ __device__ __forceinline__ RoiGeom roi_geom(const float* roi, float scale, int P
   return g;
 }
 
+// attention-pooled levels 2, 3: one vector per RoI, added to every bin.  g[0] = the G2 cell, g[1] = the G3 cell of the RoI's centre at
+// channel c (T = float) or channels c, c + 1 (T = v2f).  The callers add the two in orders of their own, which their results depend on
+typedef float v2f __attribute__((ext_vector_type(2)));
+typedef float v4f __attribute__((ext_vector_type(4)));
+template <typename T>
+__device__ __forceinline__ void attn_term(const RoiFeatParams& p, const float* roi, int b, int c, T (&g)[2]) {
+#pragma unroll
+  for (int l = 0; l < 2; ++l) {
+    const int Hl = l ? p.H3 : p.H2, Wl = l ? p.W3 : p.W2;
+    const float st = l ? 32.f : 16.f;
+    float cx = floorf((roi[1] + roi[3]) / (2.0f * st)), cy = floorf((roi[2] + roi[4]) / (2.0f * st));
+    cx = fminf(fmaxf(cx, 0.f), (float)(Wl - 1));
+    cy = fminf(fmaxf(cy, 0.f), (float)(Hl - 1));
+    const float* G = l ? p.G3 : p.G2;
+    g[l] = *reinterpret_cast<const T*>(G + (((long long)b * Hl + (int)cy) * Wl + (int)cx) * 64 + c);
+  }
+}
+
+// ---- the maps of the 7x7 box-head features.  With one sample per bin the 14x14 semantic grid (fused_semantic_head ->
+// adaptive_avg_pool2d to 7x7, htc_roi_head_cus.py) samples exactly the 2x2-per-bin points of the 7x7 grid on the same stride-4
+// geometry, and both results are averaged over the same 4 samples: by linearity one interpolation of the pre-added map x0 + sem
+// serves both.  Any other count and the semantic grid takes samples of its own (gs = roi_geom(roi, 0.25f, 14, 0); a box of zero width
+// or height has gw or gh = 0: RoIAlign then takes no sample on that axis and the semantic term is 0)
+__device__ __forceinline__ bool sem_separate(const RoiGeom& gs) { return gs.gw != 1 || gs.gh != 1; }
+__device__ __forceinline__ int map_count(const RoiGeom& gs) { return sem_separate(gs) ? 3 : 2; }
+
+// map m of a RoI in the separable forms (stream, stream_few, big): 0 = FPN level 0 (+ the semantic term when it is sampled at the same
+// points), 1 = FPN level 1, 2 = the semantic map itself: average-pooled 2x2, that is 2 * g samples per 7x7 bin and axis on the 14-grid's
+// geometry (a 7-grid bin is two 14-grid bins)
+struct MapPlan { const float* map; int H, W; float x1, y1, bw, bh; int Sx, Sy; };   // bin size, samples per 7x7 bin and axis
+__device__ __forceinline__ MapPlan map_plan(const RoiFeatParams& p, const float* roi, const RoiGeom& gs, int m) {
+  const RoiGeom g = m == 0 ? roi_geom(roi, 0.25f, 7, 2) : m == 1 ? roi_geom(roi, 0.125f, 7, 2) : gs;
+  const float bmul = m == 2 ? 2.f : 1.f;
+  MapPlan mp;
+  mp.map = m == 0 ? (sem_separate(gs) ? p.x0 : p.x0sem) : m == 1 ? p.x1 : p.sem;
+  mp.H = m == 1 ? p.H1 : p.H0;
+  mp.W = m == 1 ? p.W1 : p.W0;
+  mp.x1 = g.x1; mp.y1 = g.y1;
+  mp.bw = bmul * g.bw; mp.bh = bmul * g.bh;
+  mp.Sx = m == 2 ? 2 * gs.gw : 2;
+  mp.Sy = m == 2 ? 2 * gs.gh : 2;
+  return mp;
+}
+
 // ---- LDS-staged variant for the 7x7 box-head features ------------------------------------------------------------
 // Nuclei-sized RoIs touch at most an 8x8 pixel footprint on the stride-4 maps (5x5 on stride 8).  One wave per RoI
 // copies the three footprints (FPN level 0, semantic embedding, FPN level 1) into LDS with direct global->LDS loads
@@ -222,17 +266,14 @@ __device__ __forceinline__ int half_max(int v) {
 
 struct LevelPlan { AxisEnt ent; int fx0, fy0, fw, fh; bool ok, empty; };
 
-// lanes 0..n-1 build the x entries, lanes 32..32+n-1 the y entries of a P x P bin grid with g samples per bin and axis
-// (band variant: only the y entries [yfirst, yfirst + ycount) take part, e.g. the sample rows of one output bin row; the
-// footprint limits are then tpw x tph)
-__device__ __forceinline__ LevelPlan plan_band(const RoiGeom& g, int P, int gsx, int gsy, int H, int W, int tpw, int tph, int yfirst, int ycount,
-                                               int lane) {
+// lanes 0..n-1 build the x entries, lanes 32..32+n-1 the y entries of a P x P bin grid with gsamp samples per bin and axis; the
+// footprint fits the tile when it is at most tp x tp pixels
+__device__ __forceinline__ LevelPlan plan_level(const RoiGeom& g, int P, int gsamp, int H, int W, int tp, int lane) {
   LevelPlan lp;
   const bool is_y = lane >= 32;
   const int idx = lane & 31;
-  const int gsamp = is_y ? gsy : gsx;
   const int n = P * gsamp;
-  const bool active = is_y ? (idx >= yfirst && idx < yfirst + ycount && idx < n) : idx < n;
+  const bool active = idx < n;
   const int pb = active ? idx / gsamp : 0, is = active ? idx - pb * gsamp : 0;
   const float start = is_y ? g.y1 : g.x1, bs = is_y ? g.bh : g.bw;
   const float c = start + (float)pb * bs + ((float)is + 0.5f) * bs / (float)gsamp;   // same expression as roi_bin()
@@ -245,14 +286,11 @@ __device__ __forceinline__ LevelPlan plan_band(const RoiGeom& g, int P, int gsx,
   lp.empty = x_hi < 0 || y_hi < 0;
   lp.fx0 = lp.empty ? 0 : x_lo; lp.fy0 = lp.empty ? 0 : y_lo;
   lp.fw = lp.empty ? 0 : x_hi - x_lo + 1; lp.fh = lp.empty ? 0 : y_hi - y_lo + 1;
-  lp.ok = lp.fw <= tpw && lp.fh <= tph;
+  lp.ok = lp.fw <= tp && lp.fh <= tp;
   const int f0 = is_y ? lp.fy0 : lp.fx0;
   if (valid) { lp.ent.lo -= f0; lp.ent.hi -= f0; }   // invalid entries keep offset 0 with zero weights
   else { lp.ent.lo = lp.ent.hi = 0; lp.ent.l = lp.ent.h = 0.f; }
   return lp;
-}
-__device__ __forceinline__ LevelPlan plan_level(const RoiGeom& g, int P, int gsamp, int H, int W, int tp, int lane) {
-  return plan_band(g, P, gsamp, gsamp, H, W, tp, tp, 0, 32, lane);
 }
 
 // the block's 4 waves copy the footprint with 16-byte global->LDS loads: one instruction moves 4 pixels (4 x 256 bytes; the
@@ -272,40 +310,19 @@ __device__ __forceinline__ void stage_tile(const float* __restrict__ map, int H,
   }
 }
 
-// one bin from the LDS image: identical arithmetic to roi_bin() (weights hy*hx.., sample sum iy-outer ix-inner, / count)
+// One bin from the LDS image, two channels per lane (packed fp32: v_pk_mul_f32 / v_pk_add_f32, ds_read_b64): on each channel the
+// arithmetic of roi_bin() (weights hy*hx.., sample sum iy-outer ix-inner, / count) at half the instruction count -- the RoI kernels
+// are bound by VALU issue (address and weight arithmetic per tap), not by LDS or memory.  `cp2` = 2 * (lane & 31) is the lane's
+// first channel; the two half-waves work on different bins, so the axis tables are read per lane.
 template <int G>
-__device__ __forceinline__ float bin_lds(const float* tile, int fw, const AxisEnt* tx, const AxisEnt* ty, int pw, int ph, int lane) {
-  float acc = 0.f;
+__device__ __forceinline__ v2f bin_lds2(const float* tile, const AxisEnt* tx, const AxisEnt* ty, int pw, int ph) {
+  v2f acc = {0.f, 0.f};
 #pragma unroll
   for (int iy = 0; iy < G; ++iy) {
     const AxisEnt ey = ty[ph * G + iy];
 #pragma unroll
     for (int ix = 0; ix < G; ++ix) {
       const AxisEnt ex = tx[pw * G + ix];
-      const float w1 = ey.h * ex.h, w2 = ey.h * ex.l, w3 = ey.l * ex.h, w4 = ey.l * ex.l;
-      const float v1 = tile[(ey.lo * fw + ex.lo) * 64 + lane], v2 = tile[(ey.lo * fw + ex.hi) * 64 + lane];
-      const float v3 = tile[(ey.hi * fw + ex.lo) * 64 + lane], v4 = tile[(ey.hi * fw + ex.hi) * 64 + lane];
-      acc += w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4;
-    }
-  }
-  return acc / (float)(G * G);
-}
-
-// Two channels per lane (packed fp32: v_pk_mul_f32 / v_pk_add_f32, ds_read_b64): the same operations in the same order as
-// bin_lds() on each channel, at half the instruction count -- the RoI kernels are bound by VALU issue (address and weight
-// arithmetic per tap), not by LDS or memory.  `cp2` = 2 * (lane & 31) is the lane's first channel; the two half-waves
-// work on different bins, so the axis tables are read per lane.
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-template <int GX, int GY = GX>
-__device__ __forceinline__ v2f bin_lds2(const float* tile, const AxisEnt* tx, const AxisEnt* ty, int pw, int ph) {
-  v2f acc = {0.f, 0.f};
-#pragma unroll
-  for (int iy = 0; iy < GY; ++iy) {
-    const AxisEnt ey = ty[ph * GY + iy];
-#pragma unroll
-    for (int ix = 0; ix < GX; ++ix) {
-      const AxisEnt ex = tx[pw * GX + ix];
       const float w1 = ey.h * ex.h, w2 = ey.h * ex.l, w3 = ey.l * ex.h, w4 = ey.l * ex.l;
       // (the tables of this path hold element offsets: x entries * 64, y entries * fw * 64; `tile` already includes cp2)
       const v2f v1 = *reinterpret_cast<const v2f*>(tile + (ey.lo + ex.lo));
@@ -315,7 +332,7 @@ __device__ __forceinline__ v2f bin_lds2(const float* tile, const AxisEnt* tx, co
       acc += w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4;
     }
   }
-  return acc / (float)(GX * GY);
+  return acc / (float)(G * G);
 }
 
 // RoIs too large for the square LDS tiles but with at most 2x2 semantic samples per 14x14 bin and sides up to SM_MAXSIDE px
@@ -339,11 +356,29 @@ struct StreamTabs {
   float wx[7][SM_J];        // merged x weights of bin pw, tap j = pixel xlo[pw] + j
   int xlo[7];               // first footprint pixel (relative to fx0) of bin pw
   float wy[7][SM_FH];       // merged y weights of bin ph at footprint row yrel
-  // round 5: the samples of both axes (7 bins x <= 4 each), computed ONCE per map by the lane that owns them; the three tables above are
-  // built from these entries instead of recomputing a sample (coordinate, division, clamps: ~25 instructions) for every table entry it touches
+  // the samples of both axes (7 bins x <= 4 each), computed ONCE per map by the lane that owns them; the three tables above are built
+  // from these entries instead of recomputing a sample (coordinate, division, clamps: ~25 instructions) for every table entry it touches
   AxisEnt smp[2][28];
   unsigned char smv[2][28];   // (bytes: with the tables the kernel's LDS must stay within 20 KB, eight workgroups per CU)
 };
+
+// sample s (0 .. 7*S-1) of an axis: mmcv's coordinate and bilinear entry
+__device__ __forceinline__ AxisEnt sm_sample(float start, float bs, int S, int s, int size, bool& valid) {
+  const int pb = s / S, is = s - pb * S;
+  const float c = start + (float)pb * bs + ((float)is + 0.5f) * bs / (float)S;   // same expression as roi_bin()
+  return axis_entry(c, size, valid);
+}
+
+// merged weight of pixel px on one axis: what the n samples of a bin put on it (a sample's h on its low pixel, its l on its high
+// pixel), summed in sample order and divided by the samples per bin and axis
+__device__ __forceinline__ float merged_weight(const AxisEnt* smp, const unsigned char* smv, int n, int px) {
+  float wsum = 0.f;
+  for (int is = 0; is < n; ++is) {
+    const AxisEnt q = smp[is];
+    if (smv[is]) { if (q.lo == px) wsum += q.h; if (q.hi == px) wsum += q.l; }
+  }
+  return wsum / (float)n;
+}
 
 // wx / wy from the stored samples: the sums run over a bin's samples in the order of the original loops, with the same terms
 __device__ __forceinline__ void sm_weights(StreamTabs* tb, int fx0, int fy0, int Sx, int Sy, int lane) {
@@ -378,85 +413,100 @@ __device__ __forceinline__ void sm_store_samples(StreamTabs* tb, const AxisEnt& 
   if (!is_y && idx < 7 * Sx && idx % Sx == 0) tb->xlo[idx / Sx] = m == (1 << 30) ? 0 : m;
 }
 
-// sample s (0 .. 7*S-1) of an axis: mmcv's coordinate and bilinear entry
-__device__ __forceinline__ AxisEnt sm_sample(float start, float bs, int S, int s, int size, bool& valid) {
-  const int pb = s / S, is = s - pb * S;
-  const float c = start + (float)pb * bs + ((float)is + 0.5f) * bs / (float)S;   // same expression as roi_bin()
-  return axis_entry(c, size, valid);
-}
-
-// one map of one RoI: adds RoIAlign(7x7, Sx x Sy samples per bin) of `map` into acc[49] (lane = channel)
-__device__ __forceinline__ void sm_accumulate(const float* __restrict__ map, int H, int W, int b, float x1, float y1, float bw, float bh,
-                                              int Sx, int Sy, StreamTabs* tb, float* ring, float (&acc)[49], int lane) {
-  // ---- footprint bounds over the valid samples (lanes 0..27: x samples, 32..59: y samples)
+// this lane's sample (lanes 0..27: x samples, 32..59: y samples) and the footprint of the valid samples; `none`: every sample of an
+// axis lies outside the map, the map's term is 0 and the footprint means nothing
+struct StreamFoot { AxisEnt e; bool valid, none; int fx0, fy0, fw, fh; };
+__device__ __forceinline__ StreamFoot sm_footprint(const MapPlan& mp, int lane) {
+  StreamFoot ft;
   const bool is_y = lane >= 32;
   const int idx = lane & 31;
-  const int S = is_y ? Sy : Sx;
-  bool valid = false;
-  AxisEnt e{0, 0, 0.f, 0.f};
-  if (idx < 7 * S) e = sm_sample(is_y ? y1 : x1, is_y ? bh : bw, S, idx, is_y ? H : W, valid);
-  const int lo = half_min(valid ? e.lo : (1 << 30)), hi = half_max(valid ? e.hi : -1);
-  const int fx0 = __shfl(lo, 0), fx1 = __shfl(hi, 0), fy0 = __shfl(lo, 32), fy1 = __shfl(hi, 32);
-  if (fx1 < 0 || fy1 < 0) return;                       // every sample of an axis lies outside the map: the term is 0
-  const int fw = fx1 - fx0 + 1, fh = min(fy1 - fy0 + 1, SM_FH);     // (roi_classify_kernel admits only RoIs with fw <= 32, fh <= SM_FH)
-  // ---- stream the rows: slot (yr & 1) of the ring holds row yr.  Row yr + 1 is loaded into registers (4 pixels = 1 KB per
-  // wave instruction, 16 lanes x 16 bytes per pixel) before row yr is contracted and written to the other slot afterwards
-  // (a wave-wide global->LDS instruction costs the SIMD ~100 issue cycles here, a dwordx4 load + ds_write_b128 pair ~25)
-  const float* base = map + (((long long)b * H + fy0) * W + fx0) * 64;
-  const int sub = lane >> 4, c4 = (lane & 15) * 4;
-  const int n4 = (fw + 3) >> 2;
-  v4f stg[8];
-  auto load_row = [&](int yr) {
-    const float* src = base + (long long)yr * W * 64;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      int px = 4 * q + sub;
-      px = px < fw ? px : fw - 1;                       // groups past the footprint repeat its last pixel (never past the map)
-      if (q < n4) stg[q] = *reinterpret_cast<const v4f*>(src + px * 64 + c4);
-    }
-  };
-  auto store_row = [&](int yr) {
-    float* dst = ring + (yr & 1) * (SM_ROWPX * 64);
-#pragma unroll
-    for (int q = 0; q < 8; ++q)
-      if (q < n4) *reinterpret_cast<v4f*>(dst + (4 * q + sub) * 64 + c4) = stg[q];
-  };
-  load_row(0);                                         // round 5: the first row is requested BEFORE the tables are built and lands while they are
-  // ---- merged per-axis weights from the stored samples.  x: lane = (bin, tap) of the 7 x SM_J table; y: 4 entries of the 7 x SM_FH table per lane
-  sm_store_samples(tb, e, valid, is_y, idx, S, Sx, fx0);
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  sm_weights(tb, fx0, fy0, Sx, Sy, lane);
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  float wxr[7][SM_J];
-  int xbase[7];
+  const int S = is_y ? mp.Sy : mp.Sx;
+  ft.valid = false;
+  ft.e = AxisEnt{0, 0, 0.f, 0.f};
+  if (idx < 7 * S) ft.e = sm_sample(is_y ? mp.y1 : mp.x1, is_y ? mp.bh : mp.bw, S, idx, is_y ? mp.H : mp.W, ft.valid);
+  const int lo = half_min(ft.valid ? ft.e.lo : (1 << 30)), hi = half_max(ft.valid ? ft.e.hi : -1);
+  const int fx1 = __shfl(hi, 0), fy1 = __shfl(hi, 32);
+  ft.fx0 = __shfl(lo, 0); ft.fy0 = __shfl(lo, 32);
+  ft.none = fx1 < 0 || fy1 < 0;
+  ft.fw = fx1 - ft.fx0 + 1;
+  ft.fh = min(fy1 - ft.fy0 + 1, SM_FH);                 // (roi_classify_kernel admits only RoIs with fw <= 32, fh <= SM_FH)
+  return ft;
+}
+
+// A footprint row travels through registers: 4 pixels = 1 KB per wave instruction (16 lanes x 16 bytes per pixel), loaded ahead of
+// their use and written to a ring slot later (a wave-wide global->LDS instruction costs the SIMD ~100 issue cycles here, a dwordx4
+// load + ds_write_b128 pair ~25).  load_row(src): from the row's first footprint pixel; store_row(slot): into a ring slot of SM_ROWPX
+// pixels.  The pair is two lambdas over the caller's `stg`, defined by this macro: as functions that take the row buffer, the eight
+// guards `q < n4` become eight separate skips per row instead of one nested chain, and roi_feat7_stream_kernel, which sits at 256
+// VGPRs, measured 7 % slower (profiles/roi_feat_dedupe_ab.txt)
+#define SM_ROW_STAGING(fw, lane)                                                                                         \
+  const int stg_sub = (lane) >> 4, stg_c4 = ((lane) & 15) * 4, stg_n4 = ((fw) + 3) >> 2;                                 \
+  v4f stg[8];                                                                                                            \
+  auto load_row = [&](const float* src) {                                                                                \
+    _Pragma("unroll") for (int q = 0; q < 8; ++q) {                                                                      \
+      int px = 4 * q + stg_sub;                                                                                          \
+      px = px < (fw) ? px : (fw) - 1;      /* groups past the footprint repeat its last pixel (never past the map) */    \
+      if (q < stg_n4) stg[q] = *reinterpret_cast<const v4f*>(src + px * 64 + stg_c4);                                    \
+    }                                                                                                                    \
+  };                                                                                                                     \
+  auto store_row = [&](float* slot) {                                                                                    \
+    _Pragma("unroll") for (int q = 0; q < 8; ++q)                                                                        \
+      if (q < stg_n4) *reinterpret_cast<v4f*>(slot + (4 * q + stg_sub) * 64 + stg_c4) = stg[q];                          \
+  }
+
+// the x weights and the bins' first elements of a ring slot (lane = channel) into registers
+__device__ __forceinline__ void sm_tabs_to_regs(const StreamTabs* tb, int lane, float (&wxr)[7][SM_J], int (&xbase)[7]) {
 #pragma unroll
   for (int pw = 0; pw < 7; ++pw) {
     xbase[pw] = tb->xlo[pw] * 64 + lane;
 #pragma unroll
     for (int j = 0; j < SM_J; ++j) wxr[pw][j] = tb->wx[pw][j];
   }
-  store_row(0);
-  for (int yr = 0; yr < fh; ++yr) {
-    if (yr + 1 < fh) load_row(yr + 1);                 // stays in flight while row yr is contracted
+}
+
+// footprint row yr from its ring slot: contracted along x into the 7 bin columns, then into the 49 accumulators with the row's y weights
+__device__ __forceinline__ void sm_contract_row(const float* row, const StreamTabs* tb, int yr, const float (&wxr)[7][SM_J], const int (&xbase)[7],
+                                                float (&acc)[49]) {
+  float T[7];
+#pragma unroll
+  for (int pw = 0; pw < 7; ++pw) {
+    float t = 0.f;
+#pragma unroll
+    for (int j = 0; j < SM_J; ++j) t = fmaf(wxr[pw][j], row[xbase[pw] + j * 64], t);
+    T[pw] = t;
+  }
+#pragma unroll
+  for (int ph = 0; ph < 7; ++ph) {
+    const float wyv = tb->wy[ph][yr];
+#pragma unroll
+    for (int pw = 0; pw < 7; ++pw) acc[ph * 7 + pw] = fmaf(wyv, T[pw], acc[ph * 7 + pw]);
+  }
+}
+
+// one map of one RoI: adds RoIAlign(7x7, Sx x Sy samples per bin) of mp.map into acc[49] (lane = channel)
+__device__ __forceinline__ void sm_accumulate(const MapPlan& mp, int b, StreamTabs* tb, float* ring, float (&acc)[49], int lane) {
+  const StreamFoot ft = sm_footprint(mp, lane);
+  if (ft.none) return;
+  // ---- stream the rows: slot (yr & 1) of the ring holds row yr.  Row yr + 1 is loaded into registers before row yr is contracted
+  // and written to the other slot afterwards
+  const float* base = mp.map + (((long long)b * mp.H + ft.fy0) * mp.W + ft.fx0) * 64;
+  SM_ROW_STAGING(ft.fw, lane);
+  load_row(base);                                      // the first row is requested BEFORE the tables are built and lands while they are
+  sm_store_samples(tb, ft.e, ft.valid, lane >= 32, lane & 31, lane >= 32 ? mp.Sy : mp.Sx, mp.Sx, ft.fx0);
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  sm_weights(tb, ft.fx0, ft.fy0, mp.Sx, mp.Sy, lane);
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  float wxr[7][SM_J];
+  int xbase[7];
+  sm_tabs_to_regs(tb, lane, wxr, xbase);
+  store_row(ring);
+  for (int yr = 0; yr < ft.fh; ++yr) {
+    if (yr + 1 < ft.fh) load_row(base + (long long)(yr + 1) * mp.W * 64);     // stays in flight while row yr is contracted
     __builtin_amdgcn_wave_barrier();
-    const float* row = ring + (yr & 1) * (SM_ROWPX * 64);
-    float T[7];
-#pragma unroll
-    for (int pw = 0; pw < 7; ++pw) {
-      float t = 0.f;
-#pragma unroll
-      for (int j = 0; j < SM_J; ++j) t = fmaf(wxr[pw][j], row[xbase[pw] + j * 64], t);
-      T[pw] = t;
-    }
-#pragma unroll
-    for (int ph = 0; ph < 7; ++ph) {
-      const float wyv = tb->wy[ph][yr];
-#pragma unroll
-      for (int pw = 0; pw < 7; ++pw) acc[ph * 7 + pw] = fmaf(wyv, T[pw], acc[ph * 7 + pw]);
-    }
-    if (yr + 1 < fh) store_row(yr + 1);                // (waits for the loads; the other slot's readers are this wave itself)
+    sm_contract_row(ring + (yr & 1) * (SM_ROWPX * 64), tb, yr, wxr, xbase, acc);
+    if (yr + 1 < ft.fh) store_row(ring + ((yr + 1) & 1) * (SM_ROWPX * 64));   // (waits for the loads; the other slot's readers are this wave itself)
     __builtin_amdgcn_wave_barrier();
   }
 }
@@ -486,31 +536,19 @@ __global__ __launch_bounds__(64) void roi_feat7_stream_kernel(RoiFeatParams p) {
 #pragma unroll
     for (int k = 0; k < 49; ++k) acc[k] = 0.f;
     const RoiGeom g0 = roi_geom(roi, 0.25f, 7, 2), g1 = roi_geom(roi, 0.125f, 7, 2), gs = roi_geom(roi, 0.25f, 14, 0);
-    // the semantic grid differs from one sample per 14x14 bin (classify guarantees gw, gh <= 2; a box of zero width or height has gw or gh = 0:
-    // RoIAlign then takes no sample on that axis and the term is 0 -- sm_accumulate returns at once for 2 * 0 samples)
-    const bool sem2 = gs.gw != 1 || gs.gh != 1;
-    // FPN level 0 (+ the semantic term when it is sampled at the same points: one sample per 14x14 bin), level 1, and -- when
-    // the semantic 14x14 grid takes 2 samples per bin on an axis -- the semantic map itself: average-pooled 2x2 that is 2*g
-    // samples per 7x7 bin and axis on the 14-grid's geometry (a 7-grid bin is two 14-grid bins)
-    for (int m = 0; m < (sem2 ? 3 : 2); ++m) {
-      const float* map = m == 0 ? (sem2 ? p.x0 : p.x0sem) : m == 1 ? p.x1 : p.sem;
+    // map_plan() written out with the three geometries formed ahead of the loop: through map_plan() this kernel needs 4 registers more
+    // than the 256 that two waves per SIMD allow (profiles/roi_feat_dedupe_resources.txt)
+    const bool sem_sep = sem_separate(gs);
+    for (int m = 0; m < map_count(gs); ++m) {
+      const float* map = m == 0 ? (sem_sep ? p.x0 : p.x0sem) : m == 1 ? p.x1 : p.sem;
       const RoiGeom& g = m == 0 ? g0 : m == 1 ? g1 : gs;
       const float bmul = m == 2 ? 2.f : 1.f;
-      sm_accumulate(map, m == 1 ? p.H1 : p.H0, m == 1 ? p.W1 : p.W0, b, g.x1, g.y1, bmul * g.bw, bmul * g.bh, m == 2 ? 2 * gs.gw : 2,
-                    m == 2 ? 2 * gs.gh : 2, &tabs, ring, acc, lane);
+      const MapPlan mp{map, m == 1 ? p.H1 : p.H0, m == 1 ? p.W1 : p.W0, g.x1, g.y1, bmul * g.bw, bmul * g.bh, m == 2 ? 2 * gs.gw : 2, m == 2 ? 2 * gs.gh : 2};
+      sm_accumulate(mp, b, &tabs, ring, acc, lane);
     }
-    // attention-pooled levels 2, 3: one vector per RoI, added to every bin
-    float gsum = 0.f;
-#pragma unroll
-    for (int l = 0; l < 2; ++l) {
-      const int Hl = l ? p.H3 : p.H2, Wl = l ? p.W3 : p.W2;
-      const float st = l ? 32.f : 16.f;
-      float cx = floorf((roi[1] + roi[3]) / (2.0f * st)), cy = floorf((roi[2] + roi[4]) / (2.0f * st));
-      cx = fminf(fmaxf(cx, 0.f), (float)(Wl - 1));
-      cy = fminf(fmaxf(cy, 0.f), (float)(Hl - 1));
-      const float* G = l ? p.G3 : p.G2;
-      gsum += G[(((long long)b * Hl + (int)cy) * Wl + (int)cx) * 64 + lane];
-    }
+    float g[2];
+    attn_term(p, roi, b, lane, g);
+    const float gsum = (0.f + g[0]) + g[1];
 #pragma unroll
     for (int k = 0; k < 49; ++k) acc[k] += gsum;
     float* out = p.out + (long long)r * 49 * 64;
@@ -529,27 +567,16 @@ struct StreamFewShared {
   int fx0, fy0, fw, fh;
 };
 
-__device__ __forceinline__ void smf_accumulate(const float* __restrict__ map, int H, int W, int b, float x1, float y1, float bw, float bh,
-                                               int Sx, int Sy, StreamFewShared* sh, float* ring, float (&acc)[49], int lane, int wave) {
+__device__ __forceinline__ void smf_accumulate(const MapPlan& mp, int b, StreamFewShared* sh, float* ring, float (&acc)[49], int lane, int wave) {
   StreamTabs* tb = &sh->tabs;
   if (wave == 0) {
-    // ---- footprint bounds and merged weights: the statements of sm_accumulate
-    const bool is_y = lane >= 32;
-    const int idx = lane & 31;
-    const int S = is_y ? Sy : Sx;
-    bool valid = false;
-    AxisEnt e{0, 0, 0.f, 0.f};
-    if (idx < 7 * S) e = sm_sample(is_y ? y1 : x1, is_y ? bh : bw, S, idx, is_y ? H : W, valid);
-    const int lo = half_min(valid ? e.lo : (1 << 30)), hi = half_max(valid ? e.hi : -1);
-    const int fx0 = __shfl(lo, 0), fx1 = __shfl(hi, 0), fy0 = __shfl(lo, 32), fy1 = __shfl(hi, 32);
-    const bool none = fx1 < 0 || fy1 < 0;
-    const int fw = none ? 0 : fx1 - fx0 + 1, fh = none ? 0 : min(fy1 - fy0 + 1, SM_FH);
-    if (lane == 0) { sh->fx0 = fx0; sh->fy0 = fy0; sh->fw = fw; sh->fh = fh; }
-    if (!none) {
-      sm_store_samples(tb, e, valid, is_y, idx, S, Sx, fx0);
+    const StreamFoot ft = sm_footprint(mp, lane);
+    if (lane == 0) { sh->fx0 = ft.fx0; sh->fy0 = ft.fy0; sh->fw = ft.fw; sh->fh = ft.none ? 0 : ft.fh; }
+    if (!ft.none) {
+      sm_store_samples(tb, ft.e, ft.valid, lane >= 32, lane & 31, lane >= 32 ? mp.Sy : mp.Sx, mp.Sx, ft.fx0);
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
       __builtin_amdgcn_wave_barrier();
-      sm_weights(tb, fx0, fy0, Sx, Sy, lane);
+      sm_weights(tb, ft.fx0, ft.fy0, mp.Sx, mp.Sy, lane);
     }
   }
   __syncthreads();
@@ -557,58 +584,20 @@ __device__ __forceinline__ void smf_accumulate(const float* __restrict__ map, in
   if (fh == 0) { __syncthreads(); return; }             // every sample of an axis lies outside the map (workgroup-uniform)
   float wxr[7][SM_J];
   int xbase[7];
-  if (wave == 0) {
-#pragma unroll
-    for (int pw = 0; pw < 7; ++pw) {
-      xbase[pw] = tb->xlo[pw] * 64 + lane;
-#pragma unroll
-      for (int j = 0; j < SM_J; ++j) wxr[pw][j] = tb->wx[pw][j];
-    }
-  }
-  const float* base = map + (((long long)b * H + fy0) * W + fx0) * 64;
-  const int sub = lane >> 4, c4 = (lane & 15) * 4;
-  const int n4 = (fw + 3) >> 2;
-  v4f stg[8];
-  auto load_row = [&](int yr) {
-    const float* src = base + (long long)yr * W * 64;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      int px = 4 * q + sub;
-      px = px < fw ? px : fw - 1;
-      if (q < n4) stg[q] = *reinterpret_cast<const v4f*>(src + px * 64 + c4);
-    }
-  };
-  auto store_row = [&](int yr) {                        // ring slot of row yr: half (yr / SMF_W) & 1, slot yr % SMF_W
-    float* dst = ring + (((yr / SMF_W) & 1) * SMF_W + (yr % SMF_W)) * (SM_ROWPX * 64);
-#pragma unroll
-    for (int q = 0; q < 8; ++q)
-      if (q < n4) *reinterpret_cast<v4f*>(dst + (4 * q + sub) * 64 + c4) = stg[q];
-  };
-  if (wave < fh) { load_row(wave); store_row(wave); }
+  if (wave == 0) sm_tabs_to_regs(tb, lane, wxr, xbase);
+  const float* base = mp.map + (((long long)b * mp.H + fy0) * mp.W + fx0) * 64;
+  const long long pitch = (long long)mp.W * 64;
+  auto slot = [&](int yr) { return ring + (((yr / SMF_W) & 1) * SMF_W + (yr % SMF_W)) * (SM_ROWPX * 64); };   // half (yr / SMF_W) & 1, slot yr % SMF_W
+  SM_ROW_STAGING(fw, lane);
+  if (wave < fh) { load_row(base + wave * pitch); store_row(slot(wave)); }
   __syncthreads();
   for (int y0 = 0; y0 < fh; y0 += SMF_W) {
     const int ynext = y0 + SMF_W + wave;
-    if (ynext < fh) load_row(ynext);                    // stays in flight while this step's rows are contracted
+    if (ynext < fh) load_row(base + ynext * pitch);     // stays in flight while this step's rows are contracted
     if (wave == 0) {
-      for (int yr = y0; yr < min(y0 + SMF_W, fh); ++yr) {
-        const float* row = ring + (((yr / SMF_W) & 1) * SMF_W + (yr % SMF_W)) * (SM_ROWPX * 64);
-        float T[7];
-#pragma unroll
-        for (int pw = 0; pw < 7; ++pw) {
-          float t = 0.f;
-#pragma unroll
-          for (int j = 0; j < SM_J; ++j) t = fmaf(wxr[pw][j], row[xbase[pw] + j * 64], t);
-          T[pw] = t;
-        }
-#pragma unroll
-        for (int ph = 0; ph < 7; ++ph) {
-          const float wyv = tb->wy[ph][yr];
-#pragma unroll
-          for (int pw = 0; pw < 7; ++pw) acc[ph * 7 + pw] = fmaf(wyv, T[pw], acc[ph * 7 + pw]);
-        }
-      }
+      for (int yr = y0; yr < min(y0 + SMF_W, fh); ++yr) sm_contract_row(slot(yr), tb, yr, wxr, xbase, acc);
     }
-    if (ynext < fh) store_row(ynext);                   // the other half: its readers finished before the previous barrier
+    if (ynext < fh) store_row(slot(ynext));             // the other half: its readers finished before the previous barrier
     __syncthreads();
   }
 }
@@ -628,27 +617,13 @@ __global__ __launch_bounds__(64 * SMF_W) void roi_feat7_stream_few_kernel(RoiFea
     float acc[49];
 #pragma unroll
     for (int k = 0; k < 49; ++k) acc[k] = 0.f;
-    const RoiGeom g0 = roi_geom(roi, 0.25f, 7, 2), g1 = roi_geom(roi, 0.125f, 7, 2), gs = roi_geom(roi, 0.25f, 14, 0);
-    const bool sem2 = gs.gw != 1 || gs.gh != 1;          // (see roi_feat7_stream_kernel)
-    for (int m = 0; m < (sem2 ? 3 : 2); ++m) {
-      const float* map = m == 0 ? (sem2 ? p.x0 : p.x0sem) : m == 1 ? p.x1 : p.sem;
-      const RoiGeom& g = m == 0 ? g0 : m == 1 ? g1 : gs;
-      const float bmul = m == 2 ? 2.f : 1.f;
-      smf_accumulate(map, m == 1 ? p.H1 : p.H0, m == 1 ? p.W1 : p.W0, b, g.x1, g.y1, bmul * g.bw, bmul * g.bh, m == 2 ? 2 * gs.gw : 2,
-                     m == 2 ? 2 * gs.gh : 2, &sh, ring, acc, lane, wave);
-    }
+    const RoiGeom gs = roi_geom(roi, 0.25f, 14, 0);
+    const int nmaps = map_count(gs);
+    for (int m = 0; m < nmaps; ++m) smf_accumulate(map_plan(p, roi, gs, m), b, &sh, ring, acc, lane, wave);
     if (wave == 0) {
-      float gsum = 0.f;
-#pragma unroll
-      for (int l = 0; l < 2; ++l) {
-        const int Hl = l ? p.H3 : p.H2, Wl = l ? p.W3 : p.W2;
-        const float st = l ? 32.f : 16.f;
-        float cx = floorf((roi[1] + roi[3]) / (2.0f * st)), cy = floorf((roi[2] + roi[4]) / (2.0f * st));
-        cx = fminf(fmaxf(cx, 0.f), (float)(Wl - 1));
-        cy = fminf(fmaxf(cy, 0.f), (float)(Hl - 1));
-        const float* G = l ? p.G3 : p.G2;
-        gsum += G[(((long long)b * Hl + (int)cy) * Wl + (int)cx) * 64 + lane];
-      }
+      float g[2];
+      attn_term(p, roi, b, lane, g);
+      const float gsum = (0.f + g[0]) + g[1];
 #pragma unroll
       for (int k = 0; k < 49; ++k) acc[k] += gsum;
       float* out = p.out + (long long)r * 49 * 64;
@@ -683,10 +658,10 @@ struct BigTabs {
 };
 
 // one map of one RoI: adds this wave's column of RoIAlign(7x7, Sx x Sy samples per bin) into acc[ph] (lane = channel)
-__device__ __forceinline__ void bg_accumulate(const float* __restrict__ map, int H, int W, int b, float x1, float y1, float bw, float bh, int Sx, int Sy,
-                                              BigTabs* tb, float (&acc)[7]) {
+__device__ __forceinline__ void bg_accumulate(const MapPlan& mp, int b, BigTabs* tb, float (&acc)[7]) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int pw = wave % 7, rs = wave / 7;
+  const int H = mp.H, W = mp.W, Sx = mp.Sx, Sy = mp.Sy;
   AxisEnt (&smp)[2][7 * BG_S] = tb->smp;
   unsigned char (&smv)[2][7 * BG_S] = tb->smv;
   // ---- the samples of both axes, computed once (wave 0: x, wave 1: y, strided) and kept in LDS; footprint bounds
@@ -696,7 +671,7 @@ __device__ __forceinline__ void bg_accumulate(const float* __restrict__ map, int
     int lo = 1 << 30, hi = -1;
     for (int sidx = lane; sidx < 7 * S; sidx += 64) {
       bool v;
-      const AxisEnt e = sm_sample(is_y ? y1 : x1, is_y ? bh : bw, S, sidx, is_y ? H : W, v);
+      const AxisEnt e = sm_sample(is_y ? mp.y1 : mp.x1, is_y ? mp.bh : mp.bw, S, sidx, is_y ? H : W, v);
       smp[is_y][sidx] = e;
       smv[is_y][sidx] = v;
       if (v) { lo = min(lo, e.lo); hi = max(hi, e.hi); }
@@ -721,7 +696,7 @@ __device__ __forceinline__ void bg_accumulate(const float* __restrict__ map, int
   }
   __syncthreads();
   const int fx0 = tb->fx0, fy0 = tb->fy0, fw = tb->fw, fh = tb->fh;
-  if (fw == 0 || fh == 0) return;                       // every sample of an axis lies outside the map (workgroup-uniform)   // every sample of an axis lies outside the map (block-uniform)
+  if (fw == 0 || fh == 0) return;                       // every sample of an axis lies outside the map (workgroup-uniform)
   int J = 1;
 #pragma unroll
   for (int q = 0; q < 7; ++q) J = max(J, tb->span[q]);
@@ -735,29 +710,17 @@ __device__ __forceinline__ void bg_accumulate(const float* __restrict__ map, int
   // ---- merged per-axis weights from the sample table (sums in sample order: deterministic)
   for (int t = tid; t < 7 * BG_J; t += BG_NT) {
     const int q = t / BG_J, j = t - q * BG_J;
-    float wsum = 0.f;
-    if (j < (padded_ok ? Jr : J)) {                   // (a start moved left puts the bin's pixels at taps up to Jr - 1)
-      const int px = tb->xlo[q] + j;
-      for (int is = 0; is < Sx; ++is) {
-        const AxisEnt e = smp[0][q * Sx + is];
-        if (smv[0][q * Sx + is]) { if (e.lo == px) wsum += e.h; if (e.hi == px) wsum += e.l; }
-      }
-    }
-    tb->wx[q][j] = wsum / (float)Sx;
+    // (a start moved left puts the bin's pixels at taps up to Jr - 1)
+    tb->wx[q][j] = j < (padded_ok ? Jr : J) ? merged_weight(smp[0] + q * Sx, smv[0] + q * Sx, Sx, tb->xlo[q] + j) : 0.f;
   }
   for (int t = tid; t < 7 * fh; t += BG_NT) {
     const int ph = t / fh, yr = t - ph * fh;
-    float wsum = 0.f;
-    for (int is = 0; is < Sy; ++is) {
-      const AxisEnt e = smp[1][ph * Sy + is];
-      if (smv[1][ph * Sy + is]) { if (e.lo == fy0 + yr) wsum += e.h; if (e.hi == fy0 + yr) wsum += e.l; }
-    }
-    tb->wy[ph][yr] = wsum / (float)Sy;
+    tb->wy[ph][yr] = merged_weight(smp[1] + ph * Sy, smv[1] + ph * Sy, Sy, fy0 + yr);
   }
   __syncthreads();
   // ---- this wave's column, its rows
   const int x0 = tb->xlo[pw] - fx0;
-  const float* base = map + (((long long)b * H + fy0) * W + fx0 + (padded_ok ? x0 : 0)) * 64 + lane;
+  const float* base = mp.map + (((long long)b * H + fy0) * W + fx0 + (padded_ok ? x0 : 0)) * 64 + lane;
   const v4f* w4 = reinterpret_cast<const v4f*>(tb->wx[pw]);
   if (padded_ok) {
     // BG_RPS rows per step: their taps (BG_RPS x 16 per chunk) are all requested before the first multiply, so a step exposes one
@@ -851,9 +814,8 @@ __global__ __launch_bounds__(BG_NT) void roi_feat7_big_kernel(RoiFeatParams p) {
     const int r = p.fb_list[bi];
     const float* roi = p.rois + (long long)r * 5;
     const int b = (int)roi[0];
-    bool sem_sep;                                         // the semantic 14 x 14 grid takes its own samples
-    { const RoiGeom gs = roi_geom(roi, 0.25f, 14, 0); sem_sep = gs.gw != 1 || gs.gh != 1; }
-    const int nmaps = sem_sep ? 3 : 2;
+    const RoiGeom gs = roi_geom(roi, 0.25f, 14, 0);
+    const int nmaps = map_count(gs);
     if (only >= nmaps) continue;                          // (workgroup-uniform)
     if (rs == 0) {
 #pragma unroll
@@ -864,11 +826,7 @@ __global__ __launch_bounds__(BG_NT) void roi_feat7_big_kernel(RoiFeatParams p) {
       float acc[7];
 #pragma unroll
       for (int k = 0; k < 7; ++k) acc[k] = 0.f;
-      const float* map = m == 0 ? (sem_sep ? p.x0 : p.x0sem) : m == 1 ? p.x1 : p.sem;
-      const RoiGeom g = m == 0 ? roi_geom(roi, 0.25f, 7, 2) : m == 1 ? roi_geom(roi, 0.125f, 7, 2) : roi_geom(roi, 0.25f, 14, 0);
-      const float bmul = m == 2 ? 2.f : 1.f;             // a 7-grid bin is two 14-grid bins: 2 g samples per bin and axis
-      bg_accumulate(map, m == 1 ? p.H1 : p.H0, m == 1 ? p.W1 : p.W0, b, g.x1, g.y1, bmul * g.bw, bmul * g.bh, m == 2 ? 2 * g.gw : 2,
-                    m == 2 ? 2 * g.gh : 2, &tabs, acc);
+      bg_accumulate(map_plan(p, roi, gs, m), b, &tabs, acc);
       if (rs > 0) {
 #pragma unroll
         for (int ph = 0; ph < 7; ++ph) part[rs - 1][pw][ph][lane] = acc[ph];
@@ -888,17 +846,9 @@ __global__ __launch_bounds__(BG_NT) void roi_feat7_big_kernel(RoiFeatParams p) {
     }
     if (split) continue;                                  // roi_feat7_big_combine_kernel adds the maps (workgroup-uniform)
     if (rs == 0) {
-      float gsum = 0.f;
-#pragma unroll
-      for (int l = 0; l < 2; ++l) {
-        const int Hl = l ? p.H3 : p.H2, Wl = l ? p.W3 : p.W2;
-        const float st = l ? 32.f : 16.f;
-        float cx = floorf((roi[1] + roi[3]) / (2.0f * st)), cy = floorf((roi[2] + roi[4]) / (2.0f * st));
-        cx = fminf(fmaxf(cx, 0.f), (float)(Wl - 1));
-        cy = fminf(fmaxf(cy, 0.f), (float)(Hl - 1));
-        const float* G = l ? p.G3 : p.G2;
-        gsum += G[(((long long)b * Hl + (int)cy) * Wl + (int)cx) * 64 + lane];
-      }
+      float g[2];
+      attn_term(p, roi, b, lane, g);
+      const float gsum = (0.f + g[0]) + g[1];
       float* out = p.out + (long long)r * 49 * 64;
 #pragma unroll
       for (int ph = 0; ph < 7; ++ph) out[(ph * 7 + pw) * 64 + lane] = totl[pw][ph][lane] + gsum;
@@ -915,20 +865,11 @@ __global__ __launch_bounds__(448) void roi_feat7_big_combine_kernel(RoiFeatParam
     const int r = p.fb_list[bi];
     const float* roi = p.rois + (long long)r * 5;
     const int b = (int)roi[0];
-    bool sem_sep;
-    { const RoiGeom gs = roi_geom(roi, 0.25f, 14, 0); sem_sep = gs.gw != 1 || gs.gh != 1; }
-    const int nmaps = sem_sep ? 3 : 2;
-    float gsum = 0.f;
-#pragma unroll
-    for (int l = 0; l < 2; ++l) {
-      const int Hl = l ? p.H3 : p.H2, Wl = l ? p.W3 : p.W2;
-      const float st = l ? 32.f : 16.f;
-      float cx = floorf((roi[1] + roi[3]) / (2.0f * st)), cy = floorf((roi[2] + roi[4]) / (2.0f * st));
-      cx = fminf(fmaxf(cx, 0.f), (float)(Wl - 1));
-      cy = fminf(fmaxf(cy, 0.f), (float)(Hl - 1));
-      const float* G = l ? p.G3 : p.G2;
-      gsum += G[(((long long)b * Hl + (int)cy) * Wl + (int)cx) * 64 + lane];
-    }
+    const RoiGeom gs = roi_geom(roi, 0.25f, 14, 0);
+    const int nmaps = map_count(gs);
+    float g[2];
+    attn_term(p, roi, b, lane, g);
+    const float gsum = (0.f + g[0]) + g[1];
     float* out = p.out + (long long)r * 49 * 64;
 #pragma unroll
     for (int ph = 0; ph < 7; ++ph) {
@@ -953,17 +894,9 @@ __global__ __launch_bounds__(256) void roi_feat7_giant_kernel(RoiFeatParams p) {
     const float* f0 = p.x0 + (long long)b * p.H0 * p.W0 * 64;
     const float* f1 = p.x1 + (long long)b * p.H1 * p.W1 * 64;
     const float* fs = p.sem + (long long)b * p.H0 * p.W0 * 64;
-    float gsum = 0.f;
-#pragma unroll
-    for (int l = 0; l < 2; ++l) {
-      const int Hl = l ? p.H3 : p.H2, Wl = l ? p.W3 : p.W2;
-      const float st = l ? 32.f : 16.f;
-      float cx = floorf((roi[1] + roi[3]) / (2.0f * st)), cy = floorf((roi[2] + roi[4]) / (2.0f * st));
-      cx = fminf(fmaxf(cx, 0.f), (float)(Wl - 1));
-      cy = fminf(fmaxf(cy, 0.f), (float)(Hl - 1));
-      const float* G = l ? p.G3 : p.G2;
-      gsum += G[(((long long)b * Hl + (int)cy) * Wl + (int)cx) * 64 + lane];
-    }
+    float g[2];
+    attn_term(p, roi, b, lane, g);
+    const float gsum = (0.f + g[0]) + g[1];
     for (int bin = wave; bin < 49; bin += 4) {
       const int ph = bin / 7, pw = bin - ph * 7;
       float v = roi_bin(f0, p.H0, p.W0, g0.x1, g0.y1, g0.bw, g0.bh, g0.gw, g0.gh, pw, ph, lane);
@@ -979,7 +912,7 @@ __global__ __launch_bounds__(256) void roi_feat7_giant_kernel(RoiFeatParams p) {
 __global__ __launch_bounds__(1024) void roi_classify_kernel(RoiFeatParams p) {
   // 16 RoIs per workgroup, and ONE atomicAdd per workgroup and list: the RoIs of a list count themselves in LDS first.  With an atomicAdd per
   // RoI a real slide's load -- every one of 17 k boxes mid-size -- queued 17 k atomics on one counter: 193 us per stage against 8 us at the
-  // synthetic load, a quarter of the RoI-feature time (round 4, rocprofv3 trace of the 40-100 px fixed load)
+  // synthetic load, a quarter of the RoI-feature time (rocprofv3 trace of the 40-100 px fixed load)
   __shared__ int cnt[3], base[3];          // lists: 0 = big boxes (class 2), 1 = mid-size (class 1), 2 = giant (class 4)
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 16 + (threadIdx.x >> 6);
@@ -990,7 +923,7 @@ __global__ __launch_bounds__(1024) void roi_classify_kernel(RoiFeatParams p) {
   if (valid) {
     const float* roi = p.rois + (long long)r * 5;
     const RoiGeom g0 = roi_geom(roi, 0.25f, 7, 2), g1 = roi_geom(roi, 0.125f, 7, 2), gs = roi_geom(roi, 0.25f, 14, 0);
-    const bool sem_g1 = gs.gw == 1 && gs.gh == 1;
+    const bool sem_g1 = !sem_separate(gs);
     const LevelPlan l0 = plan_level(g0, 7, 2, p.H0, p.W0, TP0, lane);
     const LevelPlan l1 = plan_level(g1, 7, 2, p.H1, p.W1, TP1, lane);
     // 0: LDS tiles; 1: stream kernel (at most 2x2 semantic samples per 14x14 bin -- 0, 1 or 2 per axis: a box of zero width or height has none
@@ -1017,6 +950,25 @@ __global__ __launch_bounds__(1024) void roi_classify_kernel(RoiFeatParams p) {
   else if (li == 1) p.mid_list[base[1] + slot] = r;
 }
 
+// front of the LDS-tile forms (FPN level 0 + semantic from the pre-added map x0sem, FPN level 1): wave 0 writes the plans' axis entries
+// into the tables, the block's 4 waves stage the two footprints, and everything has landed when the barrier is passed
+__device__ __forceinline__ void lds_front(const RoiFeatParams& p, int b, const LevelPlan& l0, const LevelPlan& l1, float* tile0, float* tile1,
+                                          AxisEnt (&tab)[2][2][16], int lane, int wave) {
+  if (wave == 0) {
+    const int ax = lane >> 5, idx = lane & 31;
+    if (idx < 14) {      // pixel indices -> element offsets inside the staged tile (x: * 64 channels, y: * row pitch)
+      AxisEnt e0 = l0.ent, e1 = l1.ent;
+      const int m0 = ax ? l0.fw * 64 : 64, m1 = ax ? l1.fw * 64 : 64;
+      e0.lo *= m0; e0.hi *= m0; e1.lo *= m1; e1.hi *= m1;
+      tab[0][ax][idx] = e0; tab[1][ax][idx] = e1;
+    }
+  }
+  stage_tile(p.x0sem, p.H0, p.W0, b, l0, tile0, lane, wave);
+  stage_tile(p.x1, p.H1, p.W1, b, l1, tile1, lane, wave);
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  __syncthreads();
+}
+
 template <int T0, int T1, int FLAG>
 __global__ __launch_bounds__(256) void roi_feat7_lds_kernel(RoiFeatParams p) {
   __shared__ float tile0[T0 * T0 * 64];
@@ -1031,38 +983,15 @@ __global__ __launch_bounds__(256) void roi_feat7_lds_kernel(RoiFeatParams p) {
   const int b = (int)roi[0];
   const int cp2 = 2 * (lane & 31), hw = lane >> 5;     // bin loop: 2 channels per lane, one bin per half-wave
   v2f gsum[2];
-#pragma unroll
-  for (int l = 0; l < 2; ++l) {
-    const int Hl = l ? p.H3 : p.H2, Wl = l ? p.W3 : p.W2;
-    const float st = l ? 32.f : 16.f;
-    float cx = floorf((roi[1] + roi[3]) / (2.0f * st)), cy = floorf((roi[2] + roi[4]) / (2.0f * st));
-    cx = fminf(fmaxf(cx, 0.f), (float)(Wl - 1));
-    cy = fminf(fmaxf(cy, 0.f), (float)(Hl - 1));
-    const float* G = l ? p.G3 : p.G2;
-    gsum[l] = *reinterpret_cast<const v2f*>(G + (((long long)b * Hl + (int)cy) * Wl + (int)cx) * 64 + cp2);
-  }
+  attn_term(p, roi, b, cp2, gsum);
   float* out = p.out + (long long)r * 49 * 64;
   const RoiGeom g0 = roi_geom(roi, 0.25f, 7, 2), g1 = roi_geom(roi, 0.125f, 7, 2), gs = roi_geom(roi, 0.25f, 14, 0);
-  const bool sem_g1 = gs.gw == 1 && gs.gh == 1;
+  const bool sem_g1 = !sem_separate(gs);
   const LevelPlan l0 = plan_level(g0, 7, 2, p.H0, p.W0, T0, lane);   // every wave computes the same plan
   const LevelPlan l1 = plan_level(g1, 7, 2, p.H1, p.W1, T1, lane);
-  // With one sample per bin the 14x14 semantic grid (fused_semantic_head -> adaptive_avg_pool2d to 7x7,
-  // htc_roi_head_cus.py) samples exactly the 2x2-per-bin points of the 7x7 grid on the same stride-4 geometry, and both
-  // results are averaged over the same 4 samples: by linearity one interpolation of the pre-added map x0 + sem serves both.
+  // one sample per 14x14 semantic bin: one interpolation of the pre-added map x0 + sem serves both terms (see sem_separate)
   if (!(sem_g1 && l0.ok && l1.ok)) return;   // (cannot happen: roi_classify_kernel ran the same test)
-  if (wave == 0) {
-    const int ax = lane >> 5, idx = lane & 31;
-    if (idx < 14) {      // pixel indices -> element offsets inside the staged tile (x: * 64 channels, y: * row pitch)
-      AxisEnt e0 = l0.ent, e1 = l1.ent;
-      const int m0 = ax ? l0.fw * 64 : 64, m1 = ax ? l1.fw * 64 : 64;
-      e0.lo *= m0; e0.hi *= m0; e1.lo *= m1; e1.hi *= m1;
-      tab[0][ax][idx] = e0; tab[1][ax][idx] = e1;
-    }
-  }
-  stage_tile(p.x0sem, p.H0, p.W0, b, l0, tile0, lane, wave);
-  stage_tile(p.x1, p.H1, p.W1, b, l1, tile1, lane, wave);
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  __syncthreads();
+  lds_front(p, b, l0, l1, tile0, tile1, tab, lane, wave);
   const v2f zero2 = {0.f, 0.f};
   for (int pair = wave; pair < 25; pair += 4) {         // bins 2*pair and 2*pair + 1 (bin 49 does not exist)
     const int bin = 2 * pair + hw;
@@ -1101,29 +1030,8 @@ __global__ __launch_bounds__(256) void roi_feat14_kernel(RoiFeatParams p) {
     if (part != 0) return;
     const int cp2 = 2 * (lane & 31), hw = lane >> 5;
     v2f gsum[2];
-#pragma unroll
-    for (int l = 0; l < 2; ++l) {
-      const int Hl = l ? p.H3 : p.H2, Wl = l ? p.W3 : p.W2;
-      const float st = l ? 32.f : 16.f;
-      float cx = floorf((roi[1] + roi[3]) / (2.0f * st)), cy = floorf((roi[2] + roi[4]) / (2.0f * st));
-      cx = fminf(fmaxf(cx, 0.f), (float)(Wl - 1));
-      cy = fminf(fmaxf(cy, 0.f), (float)(Hl - 1));
-      const float* G = l ? p.G3 : p.G2;
-      gsum[l] = *reinterpret_cast<const v2f*>(G + (((long long)b * Hl + (int)cy) * Wl + (int)cx) * 64 + cp2);
-    }
-    if (wave == 0) {
-      const int ax = lane >> 5, idx = lane & 31;
-      if (idx < 14) {
-        AxisEnt e0 = l0.ent, e1 = l1.ent;
-        const int m0 = ax ? l0.fw * 64 : 64, m1 = ax ? l1.fw * 64 : 64;
-        e0.lo *= m0; e0.hi *= m0; e1.lo *= m1; e1.hi *= m1;
-        tab[0][ax][idx] = e0; tab[1][ax][idx] = e1;
-      }
-    }
-    stage_tile(p.x0sem, p.H0, p.W0, b, l0, tile0, lane, wave);
-    stage_tile(p.x1, p.H1, p.W1, b, l1, tile1, lane, wave);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __syncthreads();
+    attn_term(p, roi, b, cp2, gsum);
+    lds_front(p, b, l0, l1, tile0, tile1, tab, lane, wave);
     const v2f zero2 = {0.f, 0.f};
     for (int pair = wave; pair < 98; pair += 4) {
       const int bin = 2 * pair + hw;
@@ -1141,16 +1049,7 @@ __global__ __launch_bounds__(256) void roi_feat14_kernel(RoiFeatParams p) {
   const float* f0 = p.x0sem + (long long)b * p.H0 * p.W0 * 64;
   const float* f1 = p.x1 + (long long)b * p.H1 * p.W1 * 64;
   float gsum[2];
-#pragma unroll
-  for (int l = 0; l < 2; ++l) {
-    const int Hl = l ? p.H3 : p.H2, Wl = l ? p.W3 : p.W2;
-    const float st = l ? 32.f : 16.f;
-    float cx = floorf((roi[1] + roi[3]) / (2.0f * st)), cy = floorf((roi[2] + roi[4]) / (2.0f * st));
-    cx = fminf(fmaxf(cx, 0.f), (float)(Wl - 1));
-    cy = fminf(fmaxf(cy, 0.f), (float)(Hl - 1));
-    const float* G = l ? p.G3 : p.G2;
-    gsum[l] = G[(((long long)b * Hl + (int)cy) * Wl + (int)cx) * 64 + lane];
-  }
+  attn_term(p, roi, b, lane, gsum);
   for (int bin = part * 4 + wave; bin < 196; bin += 4 * gridDim.y) {
     const int ph = bin / 14, pw = bin - ph * 14;
     float v = 0.f;
