@@ -730,6 +730,28 @@ int nuhtc_grid_in_contour(int device, int start_x, int start_y, int nx, int ny, 
 int nuhtc_rle_encode(int device, const uint32_t* words_dev, const int32_t* n_dev, int n_max, int H, int W, int run_cap,
                      int32_t* len_dev, int32_t* off_dev, uint8_t* bytes_dev, int64_t pool_cap, int32_t* bbox_dev, void* stream);
 
+/* Per-nucleus embeddings (csrc/nucfeat.hip): the FPN maps of a tile averaged under the final mask of a detection.  For a mask M (H x W bits,
+ * A = set pixels) and level l (map x_l [H_l][W_l][64], stride s_l in mask pixels): w_l(i, j) = set pixels (y, x) with y / s_l == i and
+ * x / s_l == j, e_l[c] = (sum over cells of w_l(i, j) * x_l[i][j][c]) / A, row = e_0 | e_1 | e_2 | e_3 (256 float32, the layout of
+ * nuhtc_features, which is this mean under a mask of the whole image when the image fills the padded grid).  A == 0 gives a zero row.  The
+ * sum of a (level, channel) is one fp32 fused multiply-add chain over the non-zero cells in row-major order, then one division: a function
+ * of the mask and the maps alone, bitwise the same in any batch and on any call, and within (n + 3) 2^-24 sum(w |x|) / A of the exact value
+ * (n = non-zero cells of the level).  nuhtc_config is unchanged (no ABI bump).  The reference has no counterpart on the device: its
+ * tools/wsi_feat_extract.py / tools/nuclei_feat_extract.py build a per-nucleus table keyed by nuclei_id on the host.
+ * nuhtc_nucleus_features runs after nuhtc_infer and nuhtc_export_kept of the same batch: idx_dev / n_dev are that export's (entry d = b *
+ * max_per_img + r; n_dev[0] = kept detections), the masks are dets->masks, the maps the engine's x0..x3 at strides (4 << l) / scale_factor
+ * mask pixels (NUHTC_E_INVALID unless scale_factor is 1, 2 or 4).  feat_dev [cap][256]: row d for d < min(n_dev[0], cap), in the export's
+ * (tile, slot) order; later rows are not touched.  Enqueues one launch on `stream`; does not synchronise.
+ * nuhtc_op_nucleus_pool is the test entry point on raw arrays: maps[l] device [B][h[l]][w[l]][64], strides[l] >= 1 with (H - 1) / strides[l] <
+ * h[l] and (W - 1) / strides[l] < w[l] (h, w, strides and the pointer table are HOST arrays); masks device [B][K][H][(W + 31) / 32] (bit x & 31
+ * of word x >> 5, bits from W on zero); pairs_dev device int32 [n_max][2] = (tile, slot), an entry outside [0, B) x [0, K) gives a zero row;
+ * n = n_max when n_dev is NULL, else min(*n_dev, n_max); out device [n_max][256], rows from n on are not written.  Synchronises `stream`. */
+int nuhtc_nucleus_features(nuhtc_engine* e, const nuhtc_dets* dets, int B, const int64_t* idx_dev, const int32_t* n_dev, int cap, float* feat_dev,
+                           void* stream);
+int nuhtc_op_nucleus_pool(nuhtc_engine* e, const float* const maps[4], const int32_t h[4], const int32_t w[4], const int32_t strides[4], int B,
+                          const uint32_t* masks, int K, int H, int W, const int32_t* pairs_dev, const int32_t* n_dev, int n_max, float* out,
+                          void* stream);
+
 /* Per-kernel timing with HIP events recorded on the launch stream (process-wide switch; off by default).
  * nuhtc_profile_read synchronises the device and writes one text line per kernel tag,
  * "tag launches total_ms algorithmic_flops algorithmic_bytes", then resets the records. */

@@ -275,7 +275,8 @@ class Engine:
         torch.cuda.current_stream(self.device).synchronize()
         return ln, off, data, bbox
 
-    def export_async(self, B, cap=None, contour_cap=256, crop_words_per_det=128, rle=False, rle_bytes_per_det=256, rle_run_cap=hip.RLE_MAX_RUNS):
+    def export_async(self, B, cap=None, contour_cap=256, crop_words_per_det=128, rle=False, rle_bytes_per_det=256, rle_run_cap=hip.RLE_MAX_RUNS,
+                     nucfeat=False):
         """After infer_async: enqueue, on the current stream, everything the slide loop needs from the batch -- the outer
         contours (nuhtc_mask_contours), a gather of the kept detections, in (tile, slot) order (nuhtc_export_kept), and their
         masks cropped to their bounding rectangles into one word pool (nuhtc_export_crops) -- into fixed-capacity pinned host
@@ -286,7 +287,9 @@ class Engine:
         masks): the blob gains rle_len [cap], rle_off [cap + 1], rle_bbox [cap, 4] and rle_bytes [cap * rle_bytes_per_det], and the strings
         leave in the same single copy.  rle_run_cap defaults to the most the kernel takes (60 KB of LDS positions): its workgroups have 1024
         threads, two of them fill a CU's 2048 thread slots and 2 x 60 KB fit its 160 KB of LDS, so a smaller capacity would buy no occupancy
-        and only send ragged masks to the host encoder.  The image width must be a multiple of 32 (the mask rows are the frame the strings describe)."""
+        and only send ragged masks to the host encoder.  The image width must be a multiple of 32 (the mask rows are the frame the strings describe).
+        nucfeat=True: the embedding of every kept detection as well (nuhtc_nucleus_features: the FPN maps x0..x3 of its tile averaged under
+        its mask, nuhtc_amd.nucfeat.pool_reference): the blob gains feat [cap, 256] float32, 1 KB per detection in the same single copy."""
         K, W = self.cfg.max_per_img, self.cfg.tile_h * (self.cfg.tile_w // 32)
         if rle and self.cfg.tile_w != self.image_hw[1]:
             raise ValueError(f'export_async(rle=True): image width {self.image_hw[1]} is not a multiple of 32')
@@ -297,7 +300,7 @@ class Engine:
         pool = cap * int(crop_words_per_det)
         rle_pool = cap * int(rle_bytes_per_det) if rle else 0
         ex = getattr(self, '_ex', None)
-        if ex is None or ex['cap'] != cap or ex['ccap'] != contour_cap or ex['pool'] != pool or ex['rle_pool'] != rle_pool:
+        if ex is None or ex['cap'] != cap or ex['ccap'] != contour_cap or ex['pool'] != pool or ex['rle_pool'] != rle_pool or ex['nucfeat'] != bool(nucfeat):
             dev = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=self.device)
             names = dict(nk=((2,), torch.int32), idx=((cap,), torch.int64), boxes=((cap, 5), torch.float32), labels=((cap,), torch.int32),
                          cn=((cap,), torch.int32), crop_box=((cap, 4), torch.int32), crop_area=((cap,), torch.int32),
@@ -305,6 +308,8 @@ class Engine:
             if rle:
                 names.update(rle_len=((cap,), torch.int32), rle_off=((cap + 1,), torch.int32), rle_bbox=((cap, 4), torch.int32),
                              rle_bytes=((rle_pool,), torch.uint8))
+            if nucfeat:
+                names.update(feat=((cap, 256), torch.float32))
             # every field is a view into ONE device buffer and ONE pinned host buffer: a batch's results leave the device in a single
             # copy (each asynchronous copy on a compute stream costs a hand-over between the copy engine and the kernels)
             offs, total = {}, 0
@@ -318,7 +323,7 @@ class Engine:
             # export_async after the one that filled them (i.e. until the slot's next-but-one batch is enqueued)
             blob_hosts = [torch.zeros(total, dtype=torch.uint8).pin_memory() for _ in range(self.EXPORT_BUFFERS)]
             view = lambda blob, k: blob[offs[k]:offs[k] + int(np.prod(names[k][0])) * torch.empty(0, dtype=names[k][1]).element_size()].view(names[k][1]).view(*names[k][0])
-            ex = self._ex = dict(cap=cap, ccap=contour_cap, pool=pool, rle_pool=rle_pool, blob_dev=blob_dev, blob_hosts=blob_hosts, turn=0,
+            ex = self._ex = dict(cap=cap, ccap=contour_cap, pool=pool, rle_pool=rle_pool, nucfeat=bool(nucfeat), blob_dev=blob_dev, blob_hosts=blob_hosts, turn=0,
                                  hosts=[{k: view(b, k) for k in names} for b in blob_hosts], dev={k: view(blob_dev, k) for k in names})
             ex['dev']['words'] = dev(cap, W, dtype=torch.int32)          # full masks of the kept detections: device only
         self.contours_async(B, contour_cap)
@@ -335,6 +340,8 @@ class Engine:
                                            vp(d['rle_len']), vp(d['rle_off']), vp(d['rle_bytes']), rle_pool, vp(d['rle_bbox']), self._stream())
             if rc:
                 raise HipError(f'nuhtc_rle_encode failed ({rc})')
+        if nucfeat:     # behind nuhtc_export_kept on the same stream: the list and its length are read from idx / nk[0] on the device
+            self._check(self.lib.nuhtc_nucleus_features(self.h, ctypes.byref(self.dets), B, vp(d['idx']), vp(d['nk']), cap, vp(d['feat']), self._stream()))
         ex['turn'] = (ex['turn'] + 1) % self.EXPORT_BUFFERS
         ex['host'] = ex['hosts'][ex['turn']]
         ex['blob_hosts'][ex['turn']].copy_(ex['blob_dev'], non_blocking=True)
@@ -368,7 +375,22 @@ class Engine:
             roff = ex['rle_off'].numpy()
             g.update(rle_len=ex['rle_len'][:n].numpy(), rle_off=roff[:n], rle_bbox=ex['rle_bbox'][:n].numpy(), rle_bytes=ex['rle_bytes'].numpy(),
                      rle_total=int(roff[n]), rle_pool=self._ex['rle_pool'])
+        if 'feat' in ex:            # exported with nucfeat=True: row k is the embedding of detection k
+            g.update(feat=ex['feat'][:n].numpy())
         return g
+
+    def nucleus_features(self, B, tile, slot):
+        """Embeddings of the detections (tile[i], slot[i]) of the last infer_async, synchronously (nuhtc_nucleus_features on a list made
+        here; export_async(nucfeat=True) is the asynchronous route) -> float32 (n, 256) ndarray."""
+        n = len(tile)
+        if n == 0:
+            return np.zeros((0, 256), np.float32)
+        idx = torch.from_numpy(np.asarray(tile, np.int64) * self.cfg.max_per_img + np.asarray(slot, np.int64)).to(self.device)
+        cnt = torch.tensor([n], dtype=torch.int32, device=self.device)
+        out = torch.zeros(n, 256, dtype=torch.float32, device=self.device)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        self._check(self.lib.nuhtc_nucleus_features(self.h, ctypes.byref(self.dets), B, vp(idx), vp(cnt), n, vp(out), self._stream()))
+        return out.cpu().numpy()
 
     def export_full_mask(self, k):
         """(tile_h, tile_w) bool mask of exported detection k of the last export_async (synchronous device read: the rare crop that
@@ -784,6 +806,34 @@ class Engine:
         return dict(out=out, fb_flag=fb_flag, counts=counts)
 
     # ------------------------------------------------------------------ scoring on the device (csrc/eval.hip)
+    def op_nucleus_pool(self, maps, strides, masks, pairs, W=None, n=None, out=None):
+        """Per-nucleus embeddings on raw arrays (nuhtc_op_nucleus_pool; nuhtc_amd.nucfeat.pool_reference is the float64 restatement).
+        maps: four contiguous float32 device tensors (B, h_l, w_l, 64); strides: four ints, mask pixels per map cell; masks: contiguous int32
+        device tensor (B, K, H, (W + 31) // 32), bit x & 31 of word x >> 5 (W: the image width, default 32 x the words of a row); pairs: int32
+        device tensor (n_max, 2) of (tile, slot); n: None (all n_max entries) or an int32 device tensor whose first element is the number of
+        entries (read on the device); out: a contiguous float32 (n_max, 256) device tensor to write into (rows from n on stay as they
+        are), a zero-filled one otherwise.  -> out.  Synchronous."""
+        if len(maps) != 4 or len(strides) != 4:
+            raise ValueError('op_nucleus_pool: four maps and four strides')
+        B, K, H, wpr = (int(v) for v in masks.shape)
+        W = wpr * 32 if W is None else int(W)
+        n_max = int(pairs.shape[0])
+        for t, dt in [(m, torch.float32) for m in maps] + [(masks, torch.int32), (pairs, torch.int32)]:
+            if t.device != self.device or t.dtype != dt or not t.is_contiguous():
+                raise ValueError('op_nucleus_pool: contiguous tensors on the engine\'s device (float32 maps, int32 masks and pairs)')
+        if any(m.dim() != 4 or m.shape[0] != B or m.shape[3] != 64 for m in maps) or tuple(pairs.shape[1:]) != (2,) or (W + 31) // 32 != wpr:
+            raise ValueError('op_nucleus_pool: maps (B, h, w, 64), pairs (n, 2), masks (B, K, H, (W + 31) // 32)')
+        if out is None:
+            out = torch.zeros(n_max, 256, dtype=torch.float32, device=self.device)
+        if out.device != self.device or out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (n_max, 256):
+            raise ValueError('op_nucleus_pool: out must be a contiguous float32 (n_max, 256) tensor on the engine\'s device')
+        ptrs = (ctypes.c_void_p * 4)(*[m.data_ptr() for m in maps])
+        i4 = lambda v: (ctypes.c_int32 * 4)(*[int(a) for a in v])
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        self._check(self.lib.nuhtc_op_nucleus_pool(self.h, ptrs, i4([m.shape[1] for m in maps]), i4([m.shape[2] for m in maps]), i4(strides), B,
+                                                   vp(masks), K, H, W, vp(pairs), vp(n) if n is not None else None, n_max, vp(out), self._stream()))
+        return out
+
     def op_eval_select(self, scores, counts, masks, fg_thr, thr, labels=None):
         """Score filter + greedy mask-NMS of `WSIDataset.evaluate` (nuhtc_op_eval_select): scores (B, K) float32, counts (B,), masks
         (B, K, H, W // 32) int32 words on the device -> (sel (B, K) kept slots in visiting order, -1 behind them; nsel (B,); sel_labels)."""

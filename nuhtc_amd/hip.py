@@ -154,7 +154,8 @@ EXPORTS = ['nuhtc_default_config', 'nuhtc_create', 'nuhtc_destroy', 'nuhtc_last_
            'nuhtc_op_rpn_select', 'nuhtc_op_nms_levels', 'nuhtc_op_build_rois', 'nuhtc_op_attn_pool', 'nuhtc_op_roi_feats',
            'nuhtc_eval_batch', 'nuhtc_op_eval_select', 'nuhtc_op_eval_pairs', 'nuhtc_op_eval_render', 'nuhtc_op_eval_joint',
            'nuhtc_stitch_gather', 'nuhtc_stitch_pairs', 'nuhtc_stitch_render', 'nuhtc_op_stitch_gather', 'nuhtc_op_stitch_pairs', 'nuhtc_op_stitch_render',
-           'nuhtc_tissue_mask', 'nuhtc_points_polygon_test', 'nuhtc_grid_in_contour', 'nuhtc_rle_encode']
+           'nuhtc_tissue_mask', 'nuhtc_points_polygon_test', 'nuhtc_grid_in_contour', 'nuhtc_rle_encode',
+           'nuhtc_nucleus_features', 'nuhtc_op_nucleus_pool']
 
 _lib = None
 
@@ -226,6 +227,8 @@ def load():
     lib.nuhtc_points_polygon_test.argtypes = [ci, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp]
     lib.nuhtc_grid_in_contour.argtypes = [ci, ci, ci, ci, ci, ci, vp, ci, ci, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ci, ci, ci, vp, vp]
     lib.nuhtc_rle_encode.argtypes = [ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, ctypes.c_int64, vp, vp]
+    lib.nuhtc_nucleus_features.argtypes = [vp, ctypes.POINTER(Dets), ci, vp, vp, ci, vp, vp]
+    lib.nuhtc_op_nucleus_pool.argtypes = [vp, ctypes.POINTER(vp), i4, i4, i4, ci, vp, ci, ci, ci, vp, vp, ci, vp, vp]
     lib.nuhtc_export_kept.argtypes = [vp, ctypes.POINTER(Dets), ci, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.nuhtc_export_crops.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, ci, vp]
     lib.nuhtc_profile_enable.argtypes = [ci]

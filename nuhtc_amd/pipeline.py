@@ -61,10 +61,10 @@ class EnginePipeline:
     def _held(self, slot):
         return [p for p in self.pending if p[0] == slot]
 
-    def submit(self, tiles, channel_mode, tag=None, export=False, rle=False):
+    def submit(self, tiles, channel_mode, tag=None, export=False, rle=False, nucfeat=False):
         """Enqueue one batch (host ndarray / tensor, or device tensor) on the next slot; returns the slot's engine.
         Raises when that slot cannot take another batch (collect() first: see full()).  export=True also enqueues
-        Engine.export_async (rle=True: with the COCO run-length strings of the kept detections)."""
+        Engine.export_async (rle=True: with the COCO run-length strings of the kept detections; nucfeat=True: with their embeddings)."""
         slot = self.next
         held = self._held(slot)
         if held and (not export or len(held) >= self.per_slot or any(p[5] is None for p in held)):
@@ -90,7 +90,10 @@ class EnginePipeline:
             else:
                 B = eng.infer_async(dev, channel_mode)
             if export:                      # contours + gather of the kept detections into pinned host buffers, still asynchronous
-                turn = eng.export_async(B, rle=True) if rle else eng.export_async(B)
+                kw = dict(rle=True) if rle else {}
+                if nucfeat:
+                    kw['nucfeat'] = True
+                turn = eng.export_async(B, **kw)
             ev = torch.cuda.Event()
             ev.record(st)
         self.pending.append((slot, B, ev, tag, (dev, src), turn))

@@ -25,7 +25,7 @@ def tile_grid(image, patch_size=256, step_size=192):
     return np.stack(tiles), np.array(coords, np.int64)
 
 
-def _gather_sync(eng, B):
+def _gather_sync(eng, B, nucfeat=False):
     """Synchronous twin of Engine.export_async / export_read (any number of kept detections)."""
     import torch
     K = eng.cfg.max_per_img
@@ -35,9 +35,12 @@ def _gather_sync(eng, B):
     kept = (keep != 0) & (np.arange(K)[None, :] < counts[:, None])
     tile, slot = np.nonzero(kept)
     sel = torch.from_numpy(np.stack([tile, slot])).to(eng.device)
-    return dict(n=len(tile), tile=tile, slot=slot, boxes=eng.boxes[sel[0], sel[1]].cpu().numpy(), labels=eng.labels[sel[0], sel[1]].cpu().numpy(),
-                cn=eng.contour_n[sel[0], sel[1]].cpu().numpy(), xy=eng.contour_xy[sel[0], sel[1]].cpu().numpy(),
-                words=eng.masks[sel[0], sel[1]].reshape(len(tile), -1).cpu().numpy().view(np.uint32))
+    g = dict(n=len(tile), tile=tile, slot=slot, boxes=eng.boxes[sel[0], sel[1]].cpu().numpy(), labels=eng.labels[sel[0], sel[1]].cpu().numpy(),
+             cn=eng.contour_n[sel[0], sel[1]].cpu().numpy(), xy=eng.contour_xy[sel[0], sel[1]].cpu().numpy(),
+             words=eng.masks[sel[0], sel[1]].reshape(len(tile), -1).cpu().numpy().view(np.uint32))
+    if nucfeat:
+        g['feat'] = eng.nucleus_features(B, tile, slot)
+    return g
 
 
 class PackedMasks:
@@ -222,6 +225,8 @@ def _unpack_packed(eng, g, i0, coords, parts):
     if 'rle_len' in g:                                                    # exported with rle=True: the strings travel with the records
         blob, ln, bbox, nh = _rle_of_records(g, order, cb, bits, sizes, (eng.cfg.tile_h, eng.cfg.tile_w))
         parts[-1].update(rle_blob=blob, rle_len=ln, rle_bbox=bbox, rle_host=nh)
+    if 'feat' in g:                                                       # exported with nucfeat=True: one embedding row per record
+        parts[-1].update(feat=g['feat'][order])
 
 
 def _records_from_parts(parts):
@@ -239,16 +244,19 @@ def _records_from_parts(parts):
     masks.arrays = dict(tile=tile, box=box, score=score, label=label, rings=rings)   # the scalar fields as whole-slide arrays
     if 'rle_len' in parts[0]:
         rec.update(rle=(cat('rle_blob'), cat('rle_len')), rle_bbox=cat('rle_bbox'), rle_host=int(sum(p['rle_host'] for p in parts)))
+    if 'feat' in parts[0]:
+        rec.update(feat=cat('feat'))
     return rec
 
 
-def _unpack(eng, B, i0, coords, P, rec, exported=False):
+def _unpack(eng, B, i0, coords, P, rec, exported=False, nucfeat=False):
     """Kept detections of one finished batch -> records in slide coordinates.  `exported`: the batch was submitted with
-    export=True (its results already sit in the engine's pinned buffers); otherwise they are fetched here."""
+    export=True (its results already sit in the engine's pinned buffers); otherwise they are fetched here (nucfeat: with the
+    embeddings, appended to rec['feat'])."""
     from . import contours as host
     g = eng.export_read() if exported else None
     if g is None:
-        g = _gather_sync(eng, B)
+        g = _gather_sync(eng, B, nucfeat)
     n = g['n']
     if n == 0:
         return
@@ -292,9 +300,11 @@ def _unpack(eng, B, i0, coords, P, rec, exported=False):
             full = np.unpackbits(g['words'][k].reshape(P, W).view(np.uint8), axis=-1, bitorder='little').astype(bool)
             c = host.trace_outer_contour(full)
         rec['ring'].append(np.concatenate([c, c[:1]], 0) + np.array([ox, oy], np.int64))   # mask2inst + contour_map
+        if 'feat' in g:
+            rec.setdefault('feat', []).append(g['feat'][k])
 
 
-def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False):
+def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False, nucfeat=False):
     """Run the engine over `tiles` (N,P,P,3) and return per-detection records that survive the per-tile margin /
     min-area filter + mask-NMS (computed on the GPU, tools/infer_wsi.py:510-531), in slide coordinates.  `depth` engines
     are kept busy with up to two batches each (nuhtc_amd.pipeline): the host unpacks batch i while the GPU runs the next ones.
@@ -304,7 +314,9 @@ def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False):
     rle=True adds the COCO run-length mask of every record inside its tile, encoded on the GPU (nuhtc_rle_encode): rle = (uint8 blob of
     the `counts` strings concatenated in record order, int64 lengths), rle_bbox int32 (n, 4) = cocomask.to_bbox, and rle_host = how many
     records the host encoder (cocomask.encode) had to take: more runs than the device capacity, a string past the export pool, or a
-    batch past the export capacity."""
+    batch past the export capacity.
+    nucfeat=True adds feat float32 (n, 256): the embedding of every record, the FPN maps of its tile averaged under its mask on the GPU
+    (nuhtc_nucleus_features; nuhtc_amd.nucfeat), row i for record i."""
     import torch
     P = tiles.shape[1]
     parts = {}                 # first tile of the batch -> the batch's records (array form), joined in batch order at the end
@@ -328,7 +340,7 @@ def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False):
     for i in range(0, len(tiles), batch_size):
         if pipe.full(export=True):
             finish()
-        pipe.submit(tiles[i:i + batch_size], hip.CH_SWAP, tag=i, export=True, rle=rle)
+        pipe.submit(tiles[i:i + batch_size], hip.CH_SWAP, tag=i, export=True, rle=rle, **(dict(nucfeat=True) if nucfeat else {}))
     while pipe.pending:
         finish()
     for i0 in redo:            # the per-detection path (later batches kept the packed path)
@@ -336,7 +348,7 @@ def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False):
         eng, B, stream, _ = pipe.collect()
         with torch.cuda.stream(stream):
             one = dict(tile=[], box=[], score=[], label=[], mask=[], ring=[])
-            _unpack(eng, B, i0, coords, P, one, exported=False)
+            _unpack(eng, B, i0, coords, P, one, exported=False, nucfeat=nucfeat)
             if one['tile']:
                 parts[i0] = _part_from_lists(one)
                 if rle:                                            # nothing of this batch was encoded on the device
@@ -346,6 +358,8 @@ def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False):
     rec = _records_from_parts([parts[k] for k in sorted(parts)])
     if rle and 'rle' not in rec:
         rec.update(rle=(np.zeros(0, np.uint8), np.zeros(0, np.int64)), rle_bbox=np.zeros((0, 4), np.int32), rle_host=0)
+    if nucfeat and 'feat' not in rec:
+        rec.update(feat=np.zeros((0, 256), np.float32))
     return rec
 
 
@@ -356,9 +370,12 @@ def _part_from_lists(rec):
     sizes = (cb[:, 3] - cb[:, 1]).astype(np.int64) * ((cb[:, 2] - cb[:, 0] + 31) // 32)
     ring_n = np.array([len(r) for r in rec['ring']], np.int64)
     ring_flat = np.concatenate([np.asarray(r, np.int64).reshape(-1, 2) for r in rec['ring']], 0) if n else np.zeros((0, 2), np.int64)
-    return dict(tile=np.asarray(rec['tile'], np.int64), box=np.stack(rec['box']).astype(np.float64), score=np.asarray(rec['score'], np.float64),
+    part = dict(tile=np.asarray(rec['tile'], np.int64), box=np.stack(rec['box']).astype(np.float64), score=np.asarray(rec['score'], np.float64),
                 label=np.asarray(rec['label'], np.int64), crop_box=cb.astype(np.int32), area=area.astype(np.int32),
                 bits=bits[:int(sizes.sum())], sizes=sizes, ring_n=ring_n, ring_flat=ring_flat)
+    if 'feat' in rec:
+        part.update(feat=np.stack(rec['feat']).astype(np.float32))
+    return part
 
 
 def _extend(rec, more):
@@ -366,6 +383,8 @@ def _extend(rec, more):
     for k in ('tile', 'box', 'score', 'label', 'ring'):
         rec[k].extend(list(more[k]))
     rec['mask'].extend(list(more['mask']))
+    if 'feat' in more:
+        rec.setdefault('feat', []).extend(list(more['feat']))
 
 
 def pack_masks(masks):
@@ -443,7 +462,9 @@ def pack_records(rec, keep=None, tile_base=0, rles=None):
     bits  int32   (words,): the bit-packed mask crops (the merge's input)
     blob  uint8   (bytes,): optional COCO RLE strings, concatenated
     rles: a list of `bytes`, one per record of `keep`, or the pair (uint8 blob, lengths) infer_tiles(rle=True) returns as rec['rle']: the
-    strings of ALL records of `rec` concatenated in record order, of which the records `keep` are taken here."""
+    strings of ALL records of `rec` concatenated in record order, of which the records `keep` are taken here.
+    Records that carry embeddings (rec['feat'], infer_tiles(nucfeat=True)) travel with one more part behind these five:
+    feat  float32 (n, 256): the rows of the records `keep`."""
     import torch
     if isinstance(rles, tuple):                                    # the device's blob + lengths: one gather, no per-record objects
         ball, lall = np.asarray(rles[0], np.uint8), np.asarray(rles[1], np.int64)
@@ -466,7 +487,7 @@ def pack_records(rec, keep=None, tile_base=0, rles=None):
         m = rec['mask'].subset(kp)
         crops = np.concatenate([m.boxes.astype(np.int64), m.areas[:, None].astype(np.int64), m.off[:, None]], 1) if n else np.zeros((0, 6), np.int64)
         return [torch.from_numpy(head), torch.from_numpy(verts), torch.from_numpy(crops), torch.from_numpy(m.bits.view(np.int32).copy()),
-                torch.from_numpy(rle_blob)]
+                torch.from_numpy(rle_blob)] + _feat_part(rec, kp)
     keep = list(range(len(rec['score']))) if keep is None else list(keep)
     n = len(keep)
     head = np.zeros((n, 9), np.float64)
@@ -481,7 +502,23 @@ def pack_records(rec, keep=None, tile_base=0, rles=None):
     if n == 0:
         mbits = np.zeros(0, np.uint32)
     return [torch.from_numpy(head), torch.from_numpy(verts), torch.from_numpy(crops), torch.from_numpy(mbits.view(np.int32).copy()),
-            torch.from_numpy(rle_blob)]
+            torch.from_numpy(rle_blob)] + _feat_part(rec, keep)
+
+
+def _feat_part(rec, keep):
+    """pack_records' sixth part: the embedding rows of the records `keep` (no part for records without embeddings)."""
+    import torch
+    if 'feat' not in rec:
+        return []
+    feat = np.asarray(rec['feat'], np.float32).reshape(-1, 256)
+    return [torch.from_numpy(np.ascontiguousarray(feat[np.asarray(list(keep), np.int64)]))]
+
+
+def gathered_features(gathered, kept=None, part=5):
+    """Rank 0 after the gather: the embedding rows of all ranks' records (part `part` of each rank's list: pack_records puts them at 5) in
+    the rank-major order merge_gathered indexes, or only the rows `kept` (what merge_gathered / merge_overlap returned), in that order."""
+    rows = np.concatenate([np.asarray(g[part].cpu().numpy(), np.float32).reshape(-1, 256) for g in gathered], 0)
+    return rows if kept is None else rows[np.asarray(kept, np.int64)]
 
 
 def merge_gathered(gathered, overlap_threshold=0.05, device=0, overlap='polygon'):

@@ -22,7 +22,11 @@ Output (like the reference, :659-693), for every detection that survives the per
   --mode coco   : coco_nuclei.json (per-tile images + RLE annotations) and <save_dir>/imgs/<id>/<annidx>.png
   --mode sql    : <id>_dql.db (contour table + R-tree)
   --mode all    : everything.
-  --det         : <save_dir>/<id>/infer/img_<x>_<y>.jpg overlays of every tile with detections (score >= --score-thr; :504-512)."""
+  --det         : <save_dir>/<id>/infer/img_<x>_<y>.jpg overlays of every tile with detections (score >= --score-thr; :504-512).
+  --nuclei-feat : (not in the reference) <id>_nuclei_feat.npz beside the documents: `features` float32 (n, 256), the FPN maps of a nucleus's tile
+                  averaged under its mask on the GPU (nuhtc_amd/nucfeat.py), with `nuclei_id` int64, `label` and `score`; row k belongs to the
+                  k-th feature of <id>.geojson and nuclei_id[k] = k -- with --merge to the k-th feature of <id>_merged.geojson, and
+                  nuclei_id[k] is that nucleus's position in <id>.geojson.  The documents are the same bytes with and without the flag."""
 import argparse
 import os
 import sys
@@ -74,6 +78,8 @@ def build_parser():
                    help="where --seg / --patch compute the tissue mask and select the tiles: 'host' (numpy / scipy) or 'gpu' (rank 0's own device; same files)")
     p.add_argument('--rle-on', choices=('host', 'gpu'), default='host', dest='rle_on',
                    help="where --mode coco / all encode the run-length masks: 'host' (numpy + a Python loop per nucleus) or 'gpu' (every rank's own device; same files)")
+    p.add_argument('--nuclei-feat', action='store_true', dest='nuclei_feat',
+                   help='also write <id>_nuclei_feat.npz: the 256-d embedding of every written nucleus (FPN maps averaged under its mask on the GPU), keyed by nuclei_id')
     return p
 
 
@@ -91,7 +97,8 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
     tiles = bag.view(lo, hi)                                  # this rank's tiles only, cut / decoded a batch at a time while earlier batches run
     want = lambda m: args.mode in (m, 'all')
     rle_gpu = want('coco') and args.rle_on == 'gpu'                  # strings and boxes come off the device with the records (nuhtc_rle_encode)
-    rec = wsi.infer_tiles(model, tiles, coords[lo:hi], args.batch_size, rle=rle_gpu)
+    nucfeat = bool(getattr(args, 'nuclei_feat', False))
+    rec = wsi.infer_tiles(model, tiles, coords[lo:hi], args.batch_size, rle=rle_gpu, **(dict(nucfeat=True) if nucfeat else {}))
     # contours are traced on the rank that owns the tile; two variable-length gathers: records, then ring vertices
     rings = rec['ring']                                              # traced on the GPU (nuhtc_mask_contours)
     keep = [i for i, r in enumerate(rings) if len(r) >= 3]          # reference :536 tests the CLOSED contour (mask2inst appends the first point): only one-pixel contours go
@@ -120,6 +127,7 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
     # the one exchange of the path: every rank's records (head, ring vertices, mask crops, RLE strings) in a single all-gather
     dev = torch.device('cuda', local_rank) if world > 1 and torch.cuda.is_available() else torch.device('cpu')
     parts = wsi.pack_records(rec, keep, tile_base=lo, rles=rles)
+    feat_part = parts.pop() if nucfeat else None                     # pack_records' sixth part: it travels behind the documents' parts
     if want('qupath'):
         # every rank writes the GeoJSON text of ITS records (the reference's one Python loop over all nuclei, :533-585 + json.dump :659-664,
         # is seconds per slide on the writing rank); the bytes travel in the same gather and rank 0 only concatenates
@@ -127,6 +135,9 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
         lab = h0[:, 5].astype(np.int32)
         ptxt, pstart = contours.ring_features_text(v0, h0[:, 6].astype(np.int64), lab, h0[:, 4], model.CLASSES)
         parts += [torch.from_numpy(ptxt), torch.from_numpy(pstart), torch.from_numpy(contours.point_features_text(h0[:, :4], lab, h0[:, 4], model.CLASSES))]
+    feat_at = len(parts)
+    if nucfeat:                                                       # the embeddings of this rank's records: one more part of the same gather
+        parts.append(feat_part)
     if rle_gpu:                                                       # bbox / area of the annotations: rank 0 parses no string
         kp = np.asarray(keep, np.int64)
         parts.append(torch.from_numpy(np.ascontiguousarray(rec['rle_bbox'][kp], np.int32)))
@@ -151,6 +162,7 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
     dsa, annts, per_tile = [], [], {}
     sql = outputs.SqlContourWriter(os.path.join(out_dir, name + '_dql.db')) if want('sql') else None
     n_records = int(sum(len(h) for h in heads))
+    feat_rows = None                                                  # rows of <id>_nuclei_feat.npz: every record, or the merge's survivors
     for h, v, bl, xb in zip(heads, vparts, bparts, xparts):
         if not (want('dsa') or want('coco') or sql):       # the per-record loop serves the other document kinds only
             break
@@ -185,6 +197,14 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
             kept = wsi.merge_gathered(gathered, args.overlap_threshold, device=local_rank if world > 1 else (torch.device(args.device).index or 0))
             outputs.write_text_list(os.path.join(out_dir, name + '_merged.geojson'), contours.join_features_text(body, start, kept))
             msg += f', {len(kept)} after the cross-tile merge'
+            feat_rows = np.asarray(kept, np.int64)
+    if nucfeat:
+        from nuhtc_amd import nucfeat as nf
+        hall = np.concatenate([h.cpu().numpy() for h in heads], 0)
+        rows = np.arange(n_records, dtype=np.int64) if feat_rows is None else feat_rows
+        nf.write_npz(os.path.join(out_dir, name + '_nuclei_feat.npz'), rows, wsi.gathered_features(gathered, rows, part=feat_at),
+                     hall[rows, 5].astype(np.int64), hall[rows, 4])
+        msg += f', {len(rows)} embeddings in {name}_nuclei_feat.npz'
     if want('dsa'):
         outputs.write_json(os.path.join(out_dir, name + '_dsa.json'), outputs.dsa_document(dsa))
     if want('coco'):
