@@ -752,6 +752,28 @@ int nuhtc_op_nucleus_pool(nuhtc_engine* e, const float* const maps[4], const int
                           const uint32_t* masks, int K, int H, int W, const int32_t* pairs_dev, const int32_t* n_dev, int n_max, float* out,
                           void* stream);
 
+/* Cell graph of a slide (csrc/cellgraph.hip; nuhtc_amd/cellgraph.py has the definition and its brute-force int64 restatement `graph_reference`):
+ * for every nucleus its k nearest nuclei within a radius, and the class census of that disc.  Not in the reference.  Engine-free like
+ * nuhtc_merge_overlap: every pointer is device memory of `device`, the call allocates and frees its own scratch, runs on `stream` and
+ * synchronises it before returning.  nuhtc_config is unchanged (no ABI bump).
+ *   points [n][2] int32: node positions in HALF pixels, px = rint(x0 + x1), py = rint(y0 + y1) of the record's box (half to even): twice the
+ *     centre <id>_point.geojson writes.  |p| < 2^27.  labels [n] int32.  0 <= n <= 2^28.
+ *   r: the radius in half pixels (2 x the radius in pixels), 1 .. 16384.  k: 1 .. 32.  num_classes C: 1 .. 14.
+ *   x_min, y_min, x_max, y_max: the bounding box of the points (inclusive), computed by the caller on the host (the grid geometry is derived
+ *     from it on the host: cell side = the smallest multiple of r whose grid over the box has at most 2^22 cells; ignored when n == 0).
+ * All arithmetic is integer.  The neighbours of i are the j != i with d2(i, j) = dx * dx + dy * dy <= r * r (the radius is inclusive;
+ * coincident points, d2 == 0, are neighbours of each other), ordered by (d2, j) ascending and cut to the first k:
+ *   neighbors   [n][k] int32: the row index j of each neighbour, -1 past the end of the list
+ *   d2          [n][k] int32: its squared distance in half pixels^2, -1 past the end of the list
+ *   class_count [n][C] int32: how many j != i within the radius have label c -- all of them, not only the first k; a label outside
+ *                             [0, C) is a neighbour like any other and is counted in no class.
+ * The result is a pure function of the input: bitwise the same on every call.  n == 0 returns NUHTC_OK and touches nothing; n == 1 gives
+ * -1 in every slot and zero counts.  NUHTC_E_INVALID, before anything is launched and with the outputs untouched: k, r, num_classes or n
+ * out of range, a null pointer with n > 0, a bounding box that is empty or reaches +-2^27 (so: any coordinate out of range).
+ * NUHTC_E_INVALID after the binning, the outputs still untouched: a point lies outside the stated bounding box. */
+int nuhtc_cell_graph(int device, const int32_t* points, const int32_t* labels, int64_t n, int num_classes, int r, int k, int x_min, int y_min,
+                     int x_max, int y_max, int32_t* neighbors, int32_t* d2, int32_t* class_count, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the launch stream (process-wide switch; off by default).
  * nuhtc_profile_read synchronises the device and writes one text line per kernel tag,
  * "tag launches total_ms algorithmic_flops algorithmic_bytes", then resets the records. */

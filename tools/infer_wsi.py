@@ -26,7 +26,12 @@ Output (like the reference, :659-693), for every detection that survives the per
   --nuclei-feat : (not in the reference) <id>_nuclei_feat.npz beside the documents: `features` float32 (n, 256), the FPN maps of a nucleus's tile
                   averaged under its mask on the GPU (nuhtc_amd/nucfeat.py), with `nuclei_id` int64, `label` and `score`; row k belongs to the
                   k-th feature of <id>.geojson and nuclei_id[k] = k -- with --merge to the k-th feature of <id>_merged.geojson, and
-                  nuclei_id[k] is that nucleus's position in <id>.geojson.  The documents are the same bytes with and without the flag."""
+                  nuclei_id[k] is that nucleus's position in <id>.geojson.  The documents are the same bytes with and without the flag.
+  --nuclei-graph: (not in the reference) <id>_nuclei_graph.npz beside the documents: for every row --nuclei-feat writes (every record, or the
+                  merge's survivors) its --graph-k nearest nuclei within --graph-radius px, their distances and the class census of that
+                  disc, built on rank 0's GPU after the gather (nuhtc_amd/cellgraph.py): `nuclei_id`, `xy` (the centres of
+                  <id>_point.geojson), `neighbors` (rows of this file, -1 = none), `dist` (px, inf = none), `class_count`, `label`.  Row-aligned
+                  with <id>_nuclei_feat.npz when both flags are given; every other file is the same bytes with and without the flag."""
 import argparse
 import os
 import sys
@@ -80,6 +85,12 @@ def build_parser():
                    help="where --mode coco / all encode the run-length masks: 'host' (numpy + a Python loop per nucleus) or 'gpu' (every rank's own device; same files)")
     p.add_argument('--nuclei-feat', action='store_true', dest='nuclei_feat',
                    help='also write <id>_nuclei_feat.npz: the 256-d embedding of every written nucleus (FPN maps averaged under its mask on the GPU), keyed by nuclei_id')
+    p.add_argument('--nuclei-graph', action='store_true', dest='nuclei_graph',
+                   help='also write <id>_nuclei_graph.npz: the --graph-k nearest nuclei of every written nucleus within --graph-radius, their distances and '
+                        'the class counts around it, built on the GPU (rows as in <id>_nuclei_feat.npz)')
+    p.add_argument('--graph-radius', type=float, default=64.0, dest='graph_radius',
+                   help='radius of --nuclei-graph in slide px, a multiple of 0.5 up to 8192 (default 64 px: 16 um at 40x)')
+    p.add_argument('--graph-k', type=int, default=8, dest='graph_k', help='neighbours kept per nucleus by --nuclei-graph, 1..32 (default 8)')
     return p
 
 
@@ -205,6 +216,15 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
         nf.write_npz(os.path.join(out_dir, name + '_nuclei_feat.npz'), rows, wsi.gathered_features(gathered, rows, part=feat_at),
                      hall[rows, 5].astype(np.int64), hall[rows, 4])
         msg += f', {len(rows)} embeddings in {name}_nuclei_feat.npz'
+    if getattr(args, 'nuclei_graph', False):                          # the edges to those rows: only what the gather already delivered
+        from nuhtc_amd import cellgraph
+        hall = np.concatenate([h.cpu().numpy() for h in heads], 0).reshape(-1, 9)
+        rows = np.arange(n_records, dtype=np.int64) if feat_rows is None else feat_rows
+        boxes, lab = hall[rows, :4], hall[rows, 5].astype(np.int64)
+        nb, d2, cc = cellgraph.build(cellgraph.quantize_centres(boxes), lab, len(model.CLASSES), args.graph_radius, args.graph_k,
+                                     device=local_rank if world > 1 else (torch.device(args.device).index or 0))
+        cellgraph.write_npz(os.path.join(out_dir, name + '_nuclei_graph.npz'), rows, cellgraph.centres(boxes), nb, d2, cc, lab, args.graph_radius, args.graph_k)
+        msg += f', {int((nb >= 0).sum())} edges (k {args.graph_k}, {args.graph_radius:g} px) in {name}_nuclei_graph.npz'
     if want('dsa'):
         outputs.write_json(os.path.join(out_dir, name + '_dsa.json'), outputs.dsa_document(dsa))
     if want('coco'):
@@ -241,6 +261,14 @@ def main(argv=None):
             raise SystemExit('--rle-on gpu: no GPU is visible (there is no fallback; --rle-on host is the host route)')
         if args.patch_size % 32:
             raise SystemExit(f'--rle-on gpu: --patch_size {args.patch_size} is not a multiple of 32 (the device encodes bit-packed rows of 32 pixels; use --rle-on host)')
+    if args.nuclei_graph:
+        from nuhtc_amd import cellgraph
+        if not torch.cuda.is_available():
+            raise SystemExit('--nuclei-graph: no GPU is visible (there is no fallback)')
+        try:
+            cellgraph.check_args(1, cellgraph.half_pixel_radius(args.graph_radius), args.graph_k)
+        except ValueError as e:
+            raise SystemExit(f'--nuclei-graph: {e}')
     # the process group is formed AFTER seg_and_patch: rank 0's host phase (segmentation, masks, patching, stitching of every slide of the
     # folder) has no time bound, and a rank waiting in an RCCL barrier is aborted by the watchdog after 10 minutes
     rank, local_rank, world = parallel.env_ranks()
