@@ -752,6 +752,34 @@ int nuhtc_op_nucleus_pool(nuhtc_engine* e, const float* const maps[4], const int
                           const uint32_t* masks, int K, int H, int W, const int32_t* pairs_dev, const int32_t* n_dev, int n_max, float* out,
                           void* stream);
 
+/* Per-nucleus morphometry and haematoxylin intensity (csrc/nucmorph.hip): INTEGERS ONLY, under the final mask M of a detection in its H x W
+ * frame (a pixel outside the frame counts as 0).  raw row, 16 int64: A (set pixels); x0, y0, x1, y1 (bounding rectangle, x1 / y1 exclusive,
+ * zeros when A == 0); Sx, Sy, Sxx, Syy, Sxy (sums of x, y, x^2, y^2, x y over the set pixels, tile pixels); E (pixel edges between a set
+ * pixel and an unset or out-of-frame 4-neighbour); n1, n2, n3 (the perimeter classes of skimage.measure.perimeter(neighbourhood=4): on
+ * the border image B = M & ~erode4(M), code = sum of B over the 3 x 3 neighbourhood weighted [[10,2,10],[2,1,2],[10,2,10]]; n1 counts
+ * codes 5, 7, 15, 17, 25, 27, n2 counts 21, 33, n3 counts 13, 23); hull2 (twice the area of the convex hull of the corners of the set
+ * pixels); 0 (reserved).  hist row, 256 int32: the histogram under M of h = clamp((k[0] L[R] + k[1] L[G] + k[2] L[B] + 2^27) >> 28, 0,
+ * 255) in int64 with a floor shift, L = lut_dev (DEVICE int32 [256]), k (HOST int32 [3]) the red, green and blue coefficients, |k| < 2^20
+ * and 0 <= L < 2^20 (nuhtc_amd/nucmorph.py stain_constants builds both).  Red is byte 0 of a pixel with NUHTC_CH_AS_IS and byte 2 with
+ * NUHTC_CH_SWAP, as in nuhtc_infer.  Nothing is floating point: a nucleus gives the same bits in any batch and on any call, and
+ * nuhtc_amd/nucmorph.py (morph_reference) restates every value in numpy and derives the named features from them on the host.
+ * A == 0, or an entry outside the batch, gives a zero row in both outputs.  nuhtc_config is unchanged (no ABI bump).
+ * nuhtc_nucleus_morph runs after nuhtc_infer and nuhtc_export_kept of the same batch: idx_dev / n_dev are that export's (entry d = b *
+ * max_per_img + r; n_dev[0] = kept detections), the masks are dets->masks, tiles_dev [B][tile_h][tile_w][3] uint8 is the batch nuhtc_infer
+ * was given (channel_mode too).  raw_dev [cap][16], hist_dev [cap][256]: row d for d < min(n_dev[0], cap), in the export's (tile, slot)
+ * order; later rows are not touched.  NUHTC_E_INVALID: a null pointer, B outside 1 .. max_batch, cap outside 1 .. 2^24, a tile side above
+ * 1024, an unknown channel_mode.  Enqueues one launch on `stream`; does not synchronise.
+ * nuhtc_op_nucleus_morph is the test entry point on raw arrays: tiles device [B][H][W][3] uint8; masks device [B][K][H][(W + 31) / 32] (bit
+ * x & 31 of word x >> 5; bits from W on are ignored); pairs_dev device int32 [n_max][2] = (tile, slot), an entry outside [0, B) x [0, K)
+ * gives a zero row; n = n_max when n_dev is NULL, else min(*n_dev, n_max); raw [n_max][16], hist [n_max][256], rows from n on are not
+ * written.  NUHTC_E_INVALID: a null pointer (n_dev excepted), B outside 1 .. 4096, K outside 1 .. 65536, H or W outside 1 .. 1024 (W need not
+ * be a multiple of 32), n_max outside 1 .. 2^24, an unknown channel_mode.  Synchronises `stream`. */
+int nuhtc_nucleus_morph(nuhtc_engine* e, const nuhtc_dets* dets, int B, const uint8_t* tiles_dev, int channel_mode, const int32_t* lut_dev,
+                        const int32_t k[3], const int64_t* idx_dev, const int32_t* n_dev, int cap, int64_t* raw_dev, int32_t* hist_dev, void* stream);
+int nuhtc_op_nucleus_morph(nuhtc_engine* e, const uint8_t* tiles, int channel_mode, const int32_t* lut_dev, const int32_t k[3], int B,
+                           const uint32_t* masks, int K, int H, int W, const int32_t* pairs_dev, const int32_t* n_dev, int n_max,
+                           int64_t* raw, int32_t* hist, void* stream);
+
 /* Cell graph of a slide (csrc/cellgraph.hip; nuhtc_amd/cellgraph.py has the definition and its brute-force int64 restatement `graph_reference`):
  * for every nucleus its k nearest nuclei within a radius, and the class census of that disc.  Not in the reference.  Engine-free like
  * nuhtc_merge_overlap: every pointer is device memory of `device`, the call allocates and frees its own scratch, runs on `stream` and

@@ -60,28 +60,9 @@ __global__ __launch_bounds__(256) void nucleus_pool_kernel(NucPoolParams p) {
   if (b < 0 || b >= p.B || r < 0 || r >= p.K) { *dst = 0.f; return; }          // an entry outside the batch: a zero row, nothing read
   const uint32_t* __restrict__ m = p.masks + (b * p.K + r) * (long long)p.H * p.wpr;
 
-  // ---- bounding rectangle and area of the mask
-  int y0 = INT_MAX, y1 = -1, x0 = INT_MAX, x1 = -1, area = 0;
-  for (int w = tid; w < p.H * p.wpr; w += 256) {
-    const unsigned v = m[w];
-    if (v) {
-      const int y = w / p.wpr, cw = w - y * p.wpr;
-      y0 = min(y0, y); y1 = max(y1, y);
-      x0 = min(x0, cw * 32 + __ffs(v) - 1); x1 = max(x1, cw * 32 + 31 - __clz(v));
-      area += __popc(v);
-    }
-  }
-  y0 = wave_min(y0); y1 = wave_max(y1); x0 = wave_min(x0); x1 = wave_max(x1); area = wave_sum(area);
-  if (lane == 0) { red[wave][0] = y0; red[wave][1] = y1; red[wave][2] = x0; red[wave][3] = x1; red[wave][4] = area; }
-  __syncthreads();
-  y0 = min(min(red[0][0], red[1][0]), min(red[2][0], red[3][0]));
-  y1 = max(max(red[0][1], red[1][1]), max(red[2][1], red[3][1]));
-  x0 = min(min(red[0][2], red[1][2]), min(red[2][2], red[3][2]));
-  x1 = max(max(red[0][3], red[1][3]), max(red[2][3], red[3][3]));
-  area = red[0][4] + red[1][4] + red[2][4] + red[3][4];
-  // the same in every lane: in scalar registers, so the loops below and the lane reads of the weights are scalar too
-  y0 = __builtin_amdgcn_readfirstlane(y0); y1 = __builtin_amdgcn_readfirstlane(y1); x0 = __builtin_amdgcn_readfirstlane(x0);
-  x1 = __builtin_amdgcn_readfirstlane(x1); area = __builtin_amdgcn_readfirstlane(area);
+  // ---- bounding rectangle and area of the mask (maskbits.h)
+  const MaskRect rc = block_mask_rect_256(m, p.H, p.wpr, ~0u, red);
+  const int y0 = rc.y0, y1 = rc.y1, x0 = rc.x0, x1 = rc.x1, area = rc.area;
   if (area == 0) { *dst = 0.f; return; }
 
   // ---- wave = level, lane = channel

@@ -176,6 +176,7 @@ class Engine:
         """Enqueue the whole path for a device-resident batch; outputs land in self.boxes/labels/counts/masks/keep."""
         B = tiles_dev.shape[0]
         self._last_tiles = tiles_dev          # (kept alive until the next call: buffer('img') is computed from them on request)
+        self._morph_src = (tiles_dev, channel_mode)     # what nuhtc_nucleus_morph reads: set by the inferences only, tiles and mode together
         self._check(self.lib.nuhtc_infer(self.h, ctypes.c_void_p(tiles_dev.data_ptr()), B, channel_mode, self._stream(),
                                          ctypes.byref(self.dets)))
         return B
@@ -204,6 +205,7 @@ class Engine:
     def infer_fixed_load_async(self, tiles_dev, rois_dev, n_dets, channel_mode=hip.CH_AS_IS):
         B, n_rois = tiles_dev.shape[0], rois_dev.shape[1]
         self._last_tiles = tiles_dev
+        self._morph_src = (tiles_dev, channel_mode)     # what nuhtc_nucleus_morph reads: set by the inferences only, tiles and mode together
         self._check(self.lib.nuhtc_infer_fixed_load(self.h, ctypes.c_void_p(tiles_dev.data_ptr()), B, channel_mode,
                                                     ctypes.c_void_p(rois_dev.data_ptr()), n_rois, n_dets, self._stream(),
                                                     ctypes.byref(self.dets)))
@@ -276,7 +278,7 @@ class Engine:
         return ln, off, data, bbox
 
     def export_async(self, B, cap=None, contour_cap=256, crop_words_per_det=128, rle=False, rle_bytes_per_det=256, rle_run_cap=hip.RLE_MAX_RUNS,
-                     nucfeat=False):
+                     nucfeat=False, nucmorph=False):
         """After infer_async: enqueue, on the current stream, everything the slide loop needs from the batch -- the outer
         contours (nuhtc_mask_contours), a gather of the kept detections, in (tile, slot) order (nuhtc_export_kept), and their
         masks cropped to their bounding rectangles into one word pool (nuhtc_export_crops) -- into fixed-capacity pinned host
@@ -289,7 +291,10 @@ class Engine:
         threads, two of them fill a CU's 2048 thread slots and 2 x 60 KB fit its 160 KB of LDS, so a smaller capacity would buy no occupancy
         and only send ragged masks to the host encoder.  The image width must be a multiple of 32 (the mask rows are the frame the strings describe).
         nucfeat=True: the embedding of every kept detection as well (nuhtc_nucleus_features: the FPN maps x0..x3 of its tile averaged under
-        its mask, nuhtc_amd.nucfeat.pool_reference): the blob gains feat [cap, 256] float32, 1 KB per detection in the same single copy."""
+        its mask, nuhtc_amd.nucfeat.pool_reference): the blob gains feat [cap, 256] float32, 1 KB per detection in the same single copy.
+        nucmorph=True: the morphometry integers of every kept detection as well (nuhtc_nucleus_morph on the tiles of the last infer_async,
+        which the caller keeps alive until the stream has passed this call; nuhtc_amd.nucmorph.morph_reference): the blob gains morph_raw
+        [cap, 16] int64 and morph_hist [cap, 256] int32, 1152 bytes per detection in the same single copy."""
         K, W = self.cfg.max_per_img, self.cfg.tile_h * (self.cfg.tile_w // 32)
         if rle and self.cfg.tile_w != self.image_hw[1]:
             raise ValueError(f'export_async(rle=True): image width {self.image_hw[1]} is not a multiple of 32')
@@ -300,7 +305,7 @@ class Engine:
         pool = cap * int(crop_words_per_det)
         rle_pool = cap * int(rle_bytes_per_det) if rle else 0
         ex = getattr(self, '_ex', None)
-        if ex is None or ex['cap'] != cap or ex['ccap'] != contour_cap or ex['pool'] != pool or ex['rle_pool'] != rle_pool or ex['nucfeat'] != bool(nucfeat):
+        if ex is None or ex['cap'] != cap or ex['ccap'] != contour_cap or ex['pool'] != pool or ex['rle_pool'] != rle_pool or ex['nucfeat'] != bool(nucfeat) or ex['nucmorph'] != bool(nucmorph):
             dev = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=self.device)
             names = dict(nk=((2,), torch.int32), idx=((cap,), torch.int64), boxes=((cap, 5), torch.float32), labels=((cap,), torch.int32),
                          cn=((cap,), torch.int32), crop_box=((cap, 4), torch.int32), crop_area=((cap,), torch.int32),
@@ -310,6 +315,8 @@ class Engine:
                              rle_bytes=((rle_pool,), torch.uint8))
             if nucfeat:
                 names.update(feat=((cap, 256), torch.float32))
+            if nucmorph:
+                names.update(morph_raw=((cap, 16), torch.int64), morph_hist=((cap, 256), torch.int32))
             # every field is a view into ONE device buffer and ONE pinned host buffer: a batch's results leave the device in a single
             # copy (each asynchronous copy on a compute stream costs a hand-over between the copy engine and the kernels)
             offs, total = {}, 0
@@ -323,7 +330,7 @@ class Engine:
             # export_async after the one that filled them (i.e. until the slot's next-but-one batch is enqueued)
             blob_hosts = [torch.zeros(total, dtype=torch.uint8).pin_memory() for _ in range(self.EXPORT_BUFFERS)]
             view = lambda blob, k: blob[offs[k]:offs[k] + int(np.prod(names[k][0])) * torch.empty(0, dtype=names[k][1]).element_size()].view(names[k][1]).view(*names[k][0])
-            ex = self._ex = dict(cap=cap, ccap=contour_cap, pool=pool, rle_pool=rle_pool, nucfeat=bool(nucfeat), blob_dev=blob_dev, blob_hosts=blob_hosts, turn=0,
+            ex = self._ex = dict(cap=cap, ccap=contour_cap, pool=pool, rle_pool=rle_pool, nucfeat=bool(nucfeat), nucmorph=bool(nucmorph), blob_dev=blob_dev, blob_hosts=blob_hosts, turn=0,
                                  hosts=[{k: view(b, k) for k in names} for b in blob_hosts], dev={k: view(blob_dev, k) for k in names})
             ex['dev']['words'] = dev(cap, W, dtype=torch.int32)          # full masks of the kept detections: device only
         self.contours_async(B, contour_cap)
@@ -342,6 +349,8 @@ class Engine:
                 raise HipError(f'nuhtc_rle_encode failed ({rc})')
         if nucfeat:     # behind nuhtc_export_kept on the same stream: the list and its length are read from idx / nk[0] on the device
             self._check(self.lib.nuhtc_nucleus_features(self.h, ctypes.byref(self.dets), B, vp(d['idx']), vp(d['nk']), cap, vp(d['feat']), self._stream()))
+        if nucmorph:    # likewise, on the tiles the inference read
+            self._nucleus_morph(B, vp(d['idx']), vp(d['nk']), cap, vp(d['morph_raw']), vp(d['morph_hist']))
         ex['turn'] = (ex['turn'] + 1) % self.EXPORT_BUFFERS
         ex['host'] = ex['hosts'][ex['turn']]
         ex['blob_hosts'][ex['turn']].copy_(ex['blob_dev'], non_blocking=True)
@@ -377,6 +386,8 @@ class Engine:
                      rle_total=int(roff[n]), rle_pool=self._ex['rle_pool'])
         if 'feat' in ex:            # exported with nucfeat=True: row k is the embedding of detection k
             g.update(feat=ex['feat'][:n].numpy())
+        if 'morph_raw' in ex:       # exported with nucmorph=True: row k holds the integers of detection k
+            g.update(morph_raw=ex['morph_raw'][:n].numpy(), morph_hist=ex['morph_hist'][:n].numpy())
         return g
 
     def nucleus_features(self, B, tile, slot):
@@ -391,6 +402,35 @@ class Engine:
         vp = lambda t: ctypes.c_void_p(t.data_ptr())
         self._check(self.lib.nuhtc_nucleus_features(self.h, ctypes.byref(self.dets), B, vp(idx), vp(cnt), n, vp(out), self._stream()))
         return out.cpu().numpy()
+
+    def _morph_constants(self):
+        """(device int32 [256] table, host int32 [3] coefficients) of the haematoxylin value, built once (nuhtc_amd.nucmorph.stain_constants)."""
+        if getattr(self, '_morph_k', None) is None:
+            from . import nucmorph
+            lut, k = nucmorph.stain_constants()
+            self._morph_lut = torch.from_numpy(lut).to(self.device)
+            self._morph_k = (ctypes.c_int32 * 3)(*[int(v) for v in k])
+        return self._morph_lut, self._morph_k
+
+    def _nucleus_morph(self, B, idx, n_dev, cap, raw, hist):
+        lut, k = self._morph_constants()
+        tiles, mode = self._morph_src
+        self._check(self.lib.nuhtc_nucleus_morph(self.h, ctypes.byref(self.dets), B, ctypes.c_void_p(tiles.data_ptr()), mode,
+                                                 ctypes.c_void_p(lut.data_ptr()), k, idx, n_dev, cap, raw, hist, self._stream()))
+
+    def nucleus_morph(self, B, tile, slot):
+        """Morphometry integers of the detections (tile[i], slot[i]) of the last infer_async, synchronously (nuhtc_nucleus_morph on a list
+        made here; export_async(nucmorph=True) is the asynchronous route) -> (raw int64 (n, 16), hist int32 (n, 256)) ndarrays."""
+        n = len(tile)
+        if n == 0:
+            return np.zeros((0, 16), np.int64), np.zeros((0, 256), np.int32)
+        idx = torch.from_numpy(np.asarray(tile, np.int64) * self.cfg.max_per_img + np.asarray(slot, np.int64)).to(self.device)
+        cnt = torch.tensor([n], dtype=torch.int32, device=self.device)
+        raw = torch.zeros(n, 16, dtype=torch.int64, device=self.device)
+        hist = torch.zeros(n, 256, dtype=torch.int32, device=self.device)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        self._nucleus_morph(B, vp(idx), vp(cnt), n, vp(raw), vp(hist))
+        return raw.cpu().numpy(), hist.cpu().numpy()
 
     def export_full_mask(self, k):
         """(tile_h, tile_w) bool mask of exported detection k of the last export_async (synchronous device read: the rare crop that
@@ -833,6 +873,34 @@ class Engine:
         self._check(self.lib.nuhtc_op_nucleus_pool(self.h, ptrs, i4([m.shape[1] for m in maps]), i4([m.shape[2] for m in maps]), i4(strides), B,
                                                    vp(masks), K, H, W, vp(pairs), vp(n) if n is not None else None, n_max, vp(out), self._stream()))
         return out
+
+    def op_nucleus_morph(self, tiles, masks, pairs, channel_mode=hip.CH_AS_IS, n=None, out=None):
+        """Per-nucleus morphometry integers on raw arrays (nuhtc_op_nucleus_morph; nuhtc_amd.nucmorph.morph_reference is the numpy
+        restatement).  tiles: contiguous uint8 device tensor (B, H, W, 3); masks: contiguous int32 device tensor (B, K, H, (W + 31) // 32), bit
+        x & 31 of word x >> 5; pairs: int32 device tensor (n_max, 2) of (tile, slot); channel_mode: which byte is red (CH_AS_IS: byte 0,
+        CH_SWAP: byte 2); n: None (all n_max entries) or an int32 device tensor whose first element is the number of entries (read on the
+        device); out: (raw int64 (n_max, 16), hist int32 (n_max, 256)) contiguous device tensors to write into (rows from n on stay as they
+        are), zero-filled ones otherwise.  -> (raw, hist).  Synchronous."""
+        for t, dt in ((tiles, torch.uint8), (masks, torch.int32), (pairs, torch.int32)):
+            if t.device != self.device or t.dtype != dt or not t.is_contiguous():
+                raise ValueError('op_nucleus_morph: contiguous tensors on the engine\'s device (uint8 tiles, int32 masks and pairs)')
+        if tiles.dim() != 4 or masks.dim() != 4 or tiles.shape[3] != 3 or tuple(pairs.shape[1:]) != (2,):
+            raise ValueError('op_nucleus_morph: tiles (B, H, W, 3), masks (B, K, H, (W + 31) // 32), pairs (n, 2)')
+        B, H, W = (int(v) for v in tiles.shape[:3])
+        K, n_max = int(masks.shape[1]), int(pairs.shape[0])
+        if tuple(masks.shape) != (B, K, H, (W + 31) // 32):
+            raise ValueError('op_nucleus_morph: tiles (B, H, W, 3), masks (B, K, H, (W + 31) // 32), pairs (n, 2)')
+        if out is None:
+            out = (torch.zeros(n_max, 16, dtype=torch.int64, device=self.device), torch.zeros(n_max, 256, dtype=torch.int32, device=self.device))
+        raw, hist = out
+        for t, dt, sh in ((raw, torch.int64, (n_max, 16)), (hist, torch.int32, (n_max, 256))):
+            if t.device != self.device or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != sh:
+                raise ValueError('op_nucleus_morph: out must be contiguous (int64 (n_max, 16), int32 (n_max, 256)) tensors on the engine\'s device')
+        lut, k = self._morph_constants()
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        self._check(self.lib.nuhtc_op_nucleus_morph(self.h, vp(tiles), int(channel_mode), vp(lut), k, B, vp(masks), K, H, W, vp(pairs),
+                                                    vp(n) if n is not None else None, n_max, vp(raw), vp(hist), self._stream()))
+        return raw, hist
 
     def op_eval_select(self, scores, counts, masks, fg_thr, thr, labels=None):
         """Score filter + greedy mask-NMS of `WSIDataset.evaluate` (nuhtc_op_eval_select): scores (B, K) float32, counts (B,), masks

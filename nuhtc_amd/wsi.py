@@ -25,7 +25,7 @@ def tile_grid(image, patch_size=256, step_size=192):
     return np.stack(tiles), np.array(coords, np.int64)
 
 
-def _gather_sync(eng, B, nucfeat=False):
+def _gather_sync(eng, B, nucfeat=False, nucmorph=False):
     """Synchronous twin of Engine.export_async / export_read (any number of kept detections)."""
     import torch
     K = eng.cfg.max_per_img
@@ -40,6 +40,8 @@ def _gather_sync(eng, B, nucfeat=False):
              words=eng.masks[sel[0], sel[1]].reshape(len(tile), -1).cpu().numpy().view(np.uint32))
     if nucfeat:
         g['feat'] = eng.nucleus_features(B, tile, slot)
+    if nucmorph:
+        g['morph_raw'], g['morph_hist'] = eng.nucleus_morph(B, tile, slot)
     return g
 
 
@@ -227,6 +229,9 @@ def _unpack_packed(eng, g, i0, coords, parts):
         parts[-1].update(rle_blob=blob, rle_len=ln, rle_bbox=bbox, rle_host=nh)
     if 'feat' in g:                                                       # exported with nucfeat=True: one embedding row per record
         parts[-1].update(feat=g['feat'][order])
+    if 'morph_raw' in g:                                                  # exported with nucmorph=True: one row of integers per record
+        from . import nucmorph
+        parts[-1].update(morph=nucmorph.pack_rows(g['morph_raw'][order], g['morph_hist'][order], org))
 
 
 def _records_from_parts(parts):
@@ -246,17 +251,19 @@ def _records_from_parts(parts):
         rec.update(rle=(cat('rle_blob'), cat('rle_len')), rle_bbox=cat('rle_bbox'), rle_host=int(sum(p['rle_host'] for p in parts)))
     if 'feat' in parts[0]:
         rec.update(feat=cat('feat'))
+    if 'morph' in parts[0]:
+        rec.update(morph=cat('morph'))
     return rec
 
 
-def _unpack(eng, B, i0, coords, P, rec, exported=False, nucfeat=False):
+def _unpack(eng, B, i0, coords, P, rec, exported=False, nucfeat=False, nucmorph=False):
     """Kept detections of one finished batch -> records in slide coordinates.  `exported`: the batch was submitted with
     export=True (its results already sit in the engine's pinned buffers); otherwise they are fetched here (nucfeat: with the
-    embeddings, appended to rec['feat'])."""
+    embeddings, appended to rec['feat']; nucmorph: with the morphometry rows, appended to rec['morph'])."""
     from . import contours as host
     g = eng.export_read() if exported else None
     if g is None:
-        g = _gather_sync(eng, B, nucfeat)
+        g = _gather_sync(eng, B, nucfeat, nucmorph)
     n = g['n']
     if n == 0:
         return
@@ -302,9 +309,12 @@ def _unpack(eng, B, i0, coords, P, rec, exported=False, nucfeat=False):
         rec['ring'].append(np.concatenate([c, c[:1]], 0) + np.array([ox, oy], np.int64))   # mask2inst + contour_map
         if 'feat' in g:
             rec.setdefault('feat', []).append(g['feat'][k])
+        if 'morph_raw' in g:
+            from . import nucmorph
+            rec.setdefault('morph', []).append(nucmorph.pack_rows(g['morph_raw'][k], g['morph_hist'][k], (ox, oy))[0])
 
 
-def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False, nucfeat=False):
+def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False, nucfeat=False, nucmorph=False):
     """Run the engine over `tiles` (N,P,P,3) and return per-detection records that survive the per-tile margin /
     min-area filter + mask-NMS (computed on the GPU, tools/infer_wsi.py:510-531), in slide coordinates.  `depth` engines
     are kept busy with up to two batches each (nuhtc_amd.pipeline): the host unpacks batch i while the GPU runs the next ones.
@@ -316,8 +326,13 @@ def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False, nucfeat
     records the host encoder (cocomask.encode) had to take: more runs than the device capacity, a string past the export pool, or a
     batch past the export capacity.
     nucfeat=True adds feat float32 (n, 256): the embedding of every record, the FPN maps of its tile averaged under its mask on the GPU
-    (nuhtc_nucleus_features; nuhtc_amd.nucfeat), row i for record i."""
+    (nuhtc_nucleus_features; nuhtc_amd.nucfeat), row i for record i.
+    nucmorph=True adds morph int64 (n, nucmorph.ROW = 146): the morphometry integers of every record, computed on the GPU under its mask from the tile's
+    pixels (nuhtc_nucleus_morph), with its tile's origin (nuhtc_amd.nucmorph.unpack_rows -> raw, hist, origin), row i for record i."""
     import torch
+    more = dict(nucfeat=True) if nucfeat else {}
+    if nucmorph:
+        more['nucmorph'] = True
     P = tiles.shape[1]
     parts = {}                 # first tile of the batch -> the batch's records (array form), joined in batch order at the end
     redo = []
@@ -340,7 +355,7 @@ def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False, nucfeat
     for i in range(0, len(tiles), batch_size):
         if pipe.full(export=True):
             finish()
-        pipe.submit(tiles[i:i + batch_size], hip.CH_SWAP, tag=i, export=True, rle=rle, **(dict(nucfeat=True) if nucfeat else {}))
+        pipe.submit(tiles[i:i + batch_size], hip.CH_SWAP, tag=i, export=True, rle=rle, **more)
     while pipe.pending:
         finish()
     for i0 in redo:            # the per-detection path (later batches kept the packed path)
@@ -348,7 +363,7 @@ def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False, nucfeat
         eng, B, stream, _ = pipe.collect()
         with torch.cuda.stream(stream):
             one = dict(tile=[], box=[], score=[], label=[], mask=[], ring=[])
-            _unpack(eng, B, i0, coords, P, one, exported=False, nucfeat=nucfeat)
+            _unpack(eng, B, i0, coords, P, one, exported=False, nucfeat=nucfeat, nucmorph=nucmorph)
             if one['tile']:
                 parts[i0] = _part_from_lists(one)
                 if rle:                                            # nothing of this batch was encoded on the device
@@ -360,6 +375,9 @@ def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False, nucfeat
         rec.update(rle=(np.zeros(0, np.uint8), np.zeros(0, np.int64)), rle_bbox=np.zeros((0, 4), np.int32), rle_host=0)
     if nucfeat and 'feat' not in rec:
         rec.update(feat=np.zeros((0, 256), np.float32))
+    if nucmorph and 'morph' not in rec:
+        from . import nucmorph as nm
+        rec.update(morph=np.zeros((0, nm.ROW), np.int64))
     return rec
 
 
@@ -375,6 +393,8 @@ def _part_from_lists(rec):
                 bits=bits[:int(sizes.sum())], sizes=sizes, ring_n=ring_n, ring_flat=ring_flat)
     if 'feat' in rec:
         part.update(feat=np.stack(rec['feat']).astype(np.float32))
+    if 'morph' in rec:
+        part.update(morph=np.stack(rec['morph']).astype(np.int64))
     return part
 
 
@@ -385,6 +405,8 @@ def _extend(rec, more):
     rec['mask'].extend(list(more['mask']))
     if 'feat' in more:
         rec.setdefault('feat', []).extend(list(more['feat']))
+    if 'morph' in more:
+        rec.setdefault('morph', []).extend(list(more['morph']))
 
 
 def pack_masks(masks):
@@ -464,7 +486,9 @@ def pack_records(rec, keep=None, tile_base=0, rles=None):
     rles: a list of `bytes`, one per record of `keep`, or the pair (uint8 blob, lengths) infer_tiles(rle=True) returns as rec['rle']: the
     strings of ALL records of `rec` concatenated in record order, of which the records `keep` are taken here.
     Records that carry embeddings (rec['feat'], infer_tiles(nucfeat=True)) travel with one more part behind these five:
-    feat  float32 (n, 256): the rows of the records `keep`."""
+    feat  float32 (n, 256): the rows of the records `keep`;
+    and records that carry morphometry rows (rec['morph'], infer_tiles(nucmorph=True)) with one more behind that:
+    morph int64 (n, nucmorph.ROW = 146): the rows of the records `keep`."""
     import torch
     if isinstance(rles, tuple):                                    # the device's blob + lengths: one gather, no per-record objects
         ball, lall = np.asarray(rles[0], np.uint8), np.asarray(rles[1], np.int64)
@@ -487,7 +511,7 @@ def pack_records(rec, keep=None, tile_base=0, rles=None):
         m = rec['mask'].subset(kp)
         crops = np.concatenate([m.boxes.astype(np.int64), m.areas[:, None].astype(np.int64), m.off[:, None]], 1) if n else np.zeros((0, 6), np.int64)
         return [torch.from_numpy(head), torch.from_numpy(verts), torch.from_numpy(crops), torch.from_numpy(m.bits.view(np.int32).copy()),
-                torch.from_numpy(rle_blob)] + _feat_part(rec, kp)
+                torch.from_numpy(rle_blob)] + _feat_part(rec, kp) + _morph_part(rec, kp)
     keep = list(range(len(rec['score']))) if keep is None else list(keep)
     n = len(keep)
     head = np.zeros((n, 9), np.float64)
@@ -502,7 +526,7 @@ def pack_records(rec, keep=None, tile_base=0, rles=None):
     if n == 0:
         mbits = np.zeros(0, np.uint32)
     return [torch.from_numpy(head), torch.from_numpy(verts), torch.from_numpy(crops), torch.from_numpy(mbits.view(np.int32).copy()),
-            torch.from_numpy(rle_blob)] + _feat_part(rec, keep)
+            torch.from_numpy(rle_blob)] + _feat_part(rec, keep) + _morph_part(rec, keep)
 
 
 def _feat_part(rec, keep):
@@ -512,6 +536,24 @@ def _feat_part(rec, keep):
         return []
     feat = np.asarray(rec['feat'], np.float32).reshape(-1, 256)
     return [torch.from_numpy(np.ascontiguousarray(feat[np.asarray(list(keep), np.int64)]))]
+
+
+def _morph_part(rec, keep):
+    """pack_records' part behind the embeddings: the morphometry rows of the records `keep` (no part for records without them)."""
+    import torch
+    if 'morph' not in rec:
+        return []
+    from . import nucmorph
+    rows = np.asarray(rec['morph'], np.int64).reshape(-1, nucmorph.ROW)
+    return [torch.from_numpy(np.ascontiguousarray(rows[np.asarray(list(keep), np.int64)]))]
+
+
+def gathered_morph(gathered, kept=None, part=5):
+    """Rank 0 after the gather: the morphometry rows of all ranks' records (part `part` of each rank's list) in the rank-major order
+    merge_gathered indexes, or only the rows `kept`, in that order -> int64 (n, nucmorph.ROW) (nuhtc_amd.nucmorph.unpack_rows)."""
+    from . import nucmorph
+    rows = np.concatenate([np.asarray(g[part].cpu().numpy(), np.int64).reshape(-1, nucmorph.ROW) for g in gathered], 0)
+    return rows if kept is None else rows[np.asarray(kept, np.int64)]
 
 
 def gathered_features(gathered, kept=None, part=5):

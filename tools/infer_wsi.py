@@ -31,7 +31,13 @@ Output (like the reference, :659-693), for every detection that survives the per
                   merge's survivors) its --graph-k nearest nuclei within --graph-radius px, their distances and the class census of that
                   disc, built on rank 0's GPU after the gather (nuhtc_amd/cellgraph.py): `nuclei_id`, `xy` (the centres of
                   <id>_point.geojson), `neighbors` (rows of this file, -1 = none), `dist` (px, inf = none), `class_count`, `label`.  Row-aligned
-                  with <id>_nuclei_feat.npz when both flags are given; every other file is the same bytes with and without the flag."""
+                  with <id>_nuclei_feat.npz when both flags are given; every other file is the same bytes with and without the flag.
+  --nuclei-morph: (the reference's tools/wsi_feat_extract.py table, computed on the GPU) <id>_nuclei_morph.npz beside the documents, for the
+                  same rows: `columns` and `values` float64 (n, F) -- size, shape, orientation, position and haematoxylin-intensity features
+                  under histomicstk's names, derived on the host (nuhtc_amd/nucmorph.py derive) from the integers every rank's GPU measured
+                  under the final mask (`raw` int64 (n, 16), `hist` int32 (n, 256), `origin`) -- with `nuclei_id`, `label`, `score`.
+                  Row-aligned with <id>_nuclei_feat.npz and <id>_nuclei_graph.npz; every other file is the same bytes with and without the
+                  flag.  There is no route without a GPU."""
 import argparse
 import os
 import sys
@@ -85,6 +91,9 @@ def build_parser():
                    help="where --mode coco / all encode the run-length masks: 'host' (numpy + a Python loop per nucleus) or 'gpu' (every rank's own device; same files)")
     p.add_argument('--nuclei-feat', action='store_true', dest='nuclei_feat',
                    help='also write <id>_nuclei_feat.npz: the 256-d embedding of every written nucleus (FPN maps averaged under its mask on the GPU), keyed by nuclei_id')
+    p.add_argument('--nuclei-morph', action='store_true', dest='nuclei_morph',
+                   help='also write <id>_nuclei_morph.npz: size, shape and haematoxylin-intensity features of every written nucleus, from integers '
+                        'measured under its mask on the GPU (rows as in <id>_nuclei_feat.npz)')
     p.add_argument('--nuclei-graph', action='store_true', dest='nuclei_graph',
                    help='also write <id>_nuclei_graph.npz: the --graph-k nearest nuclei of every written nucleus within --graph-radius, their distances and '
                         'the class counts around it, built on the GPU (rows as in <id>_nuclei_feat.npz)')
@@ -109,7 +118,11 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
     want = lambda m: args.mode in (m, 'all')
     rle_gpu = want('coco') and args.rle_on == 'gpu'                  # strings and boxes come off the device with the records (nuhtc_rle_encode)
     nucfeat = bool(getattr(args, 'nuclei_feat', False))
-    rec = wsi.infer_tiles(model, tiles, coords[lo:hi], args.batch_size, rle=rle_gpu, **(dict(nucfeat=True) if nucfeat else {}))
+    nucmorph = bool(getattr(args, 'nuclei_morph', False))
+    more = dict(nucfeat=True) if nucfeat else {}
+    if nucmorph:
+        more['nucmorph'] = True
+    rec = wsi.infer_tiles(model, tiles, coords[lo:hi], args.batch_size, rle=rle_gpu, **more)
     # contours are traced on the rank that owns the tile; two variable-length gathers: records, then ring vertices
     rings = rec['ring']                                              # traced on the GPU (nuhtc_mask_contours)
     keep = [i for i, r in enumerate(rings) if len(r) >= 3]          # reference :536 tests the CLOSED contour (mask2inst appends the first point): only one-pixel contours go
@@ -138,6 +151,7 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
     # the one exchange of the path: every rank's records (head, ring vertices, mask crops, RLE strings) in a single all-gather
     dev = torch.device('cuda', local_rank) if world > 1 and torch.cuda.is_available() else torch.device('cpu')
     parts = wsi.pack_records(rec, keep, tile_base=lo, rles=rles)
+    morph_part = parts.pop() if nucmorph else None                   # pack_records' last part, behind the embeddings
     feat_part = parts.pop() if nucfeat else None                     # pack_records' sixth part: it travels behind the documents' parts
     if want('qupath'):
         # every rank writes the GeoJSON text of ITS records (the reference's one Python loop over all nuclei, :533-585 + json.dump :659-664,
@@ -149,6 +163,9 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
     feat_at = len(parts)
     if nucfeat:                                                       # the embeddings of this rank's records: one more part of the same gather
         parts.append(feat_part)
+    morph_at = len(parts)
+    if nucmorph:                                                      # and their morphometry integers
+        parts.append(morph_part)
     if rle_gpu:                                                       # bbox / area of the annotations: rank 0 parses no string
         kp = np.asarray(keep, np.int64)
         parts.append(torch.from_numpy(np.ascontiguousarray(rec['rle_bbox'][kp], np.int32)))
@@ -216,6 +233,13 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
         nf.write_npz(os.path.join(out_dir, name + '_nuclei_feat.npz'), rows, wsi.gathered_features(gathered, rows, part=feat_at),
                      hall[rows, 5].astype(np.int64), hall[rows, 4])
         msg += f', {len(rows)} embeddings in {name}_nuclei_feat.npz'
+    if nucmorph:
+        from nuhtc_amd import nucmorph as nm
+        hall = np.concatenate([h.cpu().numpy() for h in heads], 0).reshape(-1, 9)
+        rows = np.arange(n_records, dtype=np.int64) if feat_rows is None else feat_rows
+        raw, hist, origin = nm.unpack_rows(wsi.gathered_morph(gathered, rows, part=morph_at))
+        nm.write_npz(os.path.join(out_dir, name + '_nuclei_morph.npz'), rows, raw, hist, hall[rows, 5].astype(np.int64), hall[rows, 4], origin)
+        msg += f', {len(rows)} rows of {len(nm.COLUMNS)} features in {name}_nuclei_morph.npz'
     if getattr(args, 'nuclei_graph', False):                          # the edges to those rows: only what the gather already delivered
         from nuhtc_amd import cellgraph
         hall = np.concatenate([h.cpu().numpy() for h in heads], 0).reshape(-1, 9)
@@ -261,6 +285,8 @@ def main(argv=None):
             raise SystemExit('--rle-on gpu: no GPU is visible (there is no fallback; --rle-on host is the host route)')
         if args.patch_size % 32:
             raise SystemExit(f'--rle-on gpu: --patch_size {args.patch_size} is not a multiple of 32 (the device encodes bit-packed rows of 32 pixels; use --rle-on host)')
+    if args.nuclei_morph and not torch.cuda.is_available():
+        raise SystemExit('--nuclei-morph: no GPU is visible (there is no fallback)')
     if args.nuclei_graph:
         from nuhtc_amd import cellgraph
         if not torch.cuda.is_available():
