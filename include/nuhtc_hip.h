@@ -780,6 +780,30 @@ int nuhtc_op_nucleus_morph(nuhtc_engine* e, const uint8_t* tiles, int channel_mo
                            const uint32_t* masks, int K, int H, int W, const int32_t* pairs_dev, const int32_t* n_dev, int n_max,
                            int64_t* raw, int32_t* hist, void* stream);
 
+/* Per-nucleus grey-level co-occurrence counts for the Haralick texture features (csrc/nuctex.hip): INTEGERS ONLY, under the final mask M
+ * of a detection in its H x W frame.  The grey level of a pixel is q = h >> 4, h the haematoxylin value of nuhtc_nucleus_morph (the same
+ * lut_dev, k and channel_mode): 16 levels.  tex row, int32 [2][136]: for the offsets (dy, dx) = (0, 1) and (1, 0), cell t(a, b) = 16 a -
+ * a (a - 1) / 2 + (b - a) (the upper triangle in row-major order, a <= b) counts the unordered pixel pairs {p, p + offset} with both
+ * pixels set in M and inside the frame whose levels are {a, b}.  The symmetric matrix of Haralick is G[a][b] = G[b][a] = the cell for a < b
+ * and twice the cell on the diagonal.  Nothing is floating point: a nucleus gives the same bits in any batch and on any call, and
+ * nuhtc_amd/nuctex.py (glcm_reference) restates the counts in numpy and derives the 26 named features from them on the host.  A mask
+ * without a pair (empty, one pixel, a checkerboard), or an entry outside the batch, gives a zero row.  nuhtc_config is unchanged (no
+ * ABI bump).
+ * nuhtc_nucleus_texture runs after nuhtc_infer and nuhtc_export_kept of the same batch, with the arguments of nuhtc_nucleus_morph and
+ * one output: tex_dev [cap][2][136], row d for d < min(n_dev[0], cap), in the export's (tile, slot) order; later rows are not touched.
+ * NUHTC_E_INVALID: a null pointer, B outside 1 .. max_batch, cap outside 1 .. 2^24, a tile side above 1024, an unknown channel_mode.
+ * Enqueues one launch on `stream`; does not synchronise.
+ * nuhtc_op_nucleus_texture is the test entry point on raw arrays, with the arguments of nuhtc_op_nucleus_morph: tex [n_max][2][136], rows
+ * from n = (n_dev ? min(*n_dev, n_max) : n_max) on are not written; a (tile, slot) outside [0, B) x [0, K) gives a zero row.
+ * NUHTC_E_INVALID: a null pointer (n_dev excepted), B outside 1 .. 4096, K outside 1 .. 65536, H or W outside 1 .. 1024 (W need not be a
+ * multiple of 32; a full 1024-px frame holds 1 047 552 pairs an offset, the largest count), n_max outside 1 .. 2^24, an unknown
+ * channel_mode.  Synchronises `stream`. */
+int nuhtc_nucleus_texture(nuhtc_engine* e, const nuhtc_dets* dets, int B, const uint8_t* tiles_dev, int channel_mode, const int32_t* lut_dev,
+                          const int32_t k[3], const int64_t* idx_dev, const int32_t* n_dev, int cap, int32_t* tex_dev, void* stream);
+int nuhtc_op_nucleus_texture(nuhtc_engine* e, const uint8_t* tiles, int channel_mode, const int32_t* lut_dev, const int32_t k[3], int B,
+                             const uint32_t* masks, int K, int H, int W, const int32_t* pairs_dev, const int32_t* n_dev, int n_max,
+                             int32_t* tex, void* stream);
+
 /* Cell graph of a slide (csrc/cellgraph.hip; nuhtc_amd/cellgraph.py has the definition and its brute-force int64 restatement `graph_reference`):
  * for every nucleus its k nearest nuclei within a radius, and the class census of that disc.  Not in the reference.  Engine-free like
  * nuhtc_merge_overlap: every pointer is device memory of `device`, the call allocates and frees its own scratch, runs on `stream` and

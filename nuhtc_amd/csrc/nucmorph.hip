@@ -13,7 +13,7 @@
 //   3. one thread per mask word: the border word B = M & ~(up & down & left & right) of the rows [yb - 1, ye + 1), the neighbours'
 //      bits carried across the word boundaries from the margin words, into a second LDS band; for the rows [yb, ye) also the crack
 //      edges (popcounts of M & ~neighbour), the moments (a set-bit loop: int32 sums of x and x^2 per word, int64 per thread) and the
-//      histogram (three bytes of the tile per set pixel, the table in LDS, one LDS integer add per pixel);
+//      histogram (haematoxylin_value of haematoxylin.h: three bytes of the tile per set pixel, the table in LDS; one LDS integer add per pixel);
 //   4. one thread per row: its leftmost and rightmost set pixel, for the hull; one thread per border word: the 3 x 3 code of every
 //      border pixel from three 34-bit windows of B, classified by three 64-bit membership masks;
 //   5. integer wave and block sums (any grouping gives the same bits), then one thread per side of the hull runs its monotone chain over
@@ -22,13 +22,13 @@
 // LDS: 2 x 8 KB bands, 4 KB row extents, 2 KB histogram and table: 22.3 KB a workgroup.  The padding bits of a row's last word are
 // masked off on every read, so no tile pixel at x >= W is ever addressed.
 #include "engine.h"
+#include "haematoxylin.h"
 #include "maskbits.h"
 #include "nucmorph_host.h"
 
 namespace {
 
 constexpr int MW = 2048;          // words of one LDS band (mask, and border): at least 5 rows of the widest rectangle (34 words a row)
-constexpr int FIX_SHIFT = 28;     // 2^16 of the table times 2^12 of the coefficients
 constexpr unsigned long long CODES_1 = (1ull << 5) | (1ull << 7) | (1ull << 15) | (1ull << 17) | (1ull << 25) | (1ull << 27);
 constexpr unsigned long long CODES_2 = (1ull << 21) | (1ull << 33);
 constexpr unsigned long long CODES_3 = (1ull << 13) | (1ull << 23);
@@ -116,8 +116,7 @@ __global__ __launch_bounds__(256) void nucleus_morph_kernel(NucMorphParams p) {
       for (unsigned bits = v; bits; bits &= bits - 1) {
         const int bit = __ffs(bits) - 1, x = xb + bit;
         s1 += x; s2 += x * x;
-        const long long acc = kb0 * lut[px[bit * 3]] + kb1 * lut[px[bit * 3 + 1]] + kb2 * lut[px[bit * 3 + 2]] + (1ll << (FIX_SHIFT - 1));
-        atomicAdd(&hist[(int)min(max(acc >> FIX_SHIFT, 0ll), 255ll)], 1);
+        atomicAdd(&hist[haematoxylin_value(px + bit * 3, lut, kb0, kb1, kb2)], 1);
       }
       const int cnt = __popc(v);
       sx += s1; sy += (long long)y * cnt; sxx += s2; syy += (long long)y * y * cnt; sxy += (long long)y * s1;
@@ -186,12 +185,6 @@ int launch_nucleus_morph(const NucMorphParams& p, hipStream_t s) {
   return launched() ? 0 : NUHTC_E_HIP;
 }
 
-// byte c of a pixel is red (k[0]), green or blue: the mapping of patch_embed_tiles_kernel (swin.hip), where NUHTC_CH_SWAP reads network
-// channel c (0 = red) from byte 2 - c
-void fill_coefficients(NucMorphParams& p, const int32_t k[3], int channel_mode) {
-  for (int c = 0; c < 3; ++c) p.kb[channel_mode == NUHTC_CH_SWAP ? 2 - c : c] = k[c];
-}
-
 }  // namespace
 
 extern "C" {
@@ -208,7 +201,7 @@ int nuhtc_nucleus_morph(nuhtc_engine* e, const nuhtc_dets* dets, int B, const ui
   NucMorphParams p{};
   p.tiles = tiles_dev; p.masks = dets->masks; p.idx = idx_dev; p.n_dev = n_dev; p.lut = lut_dev; p.n_max = cap;
   p.B = B; p.K = c.max_per_img; p.H = c.tile_h; p.W = c.tile_w; p.wpr = c.tile_w / 32; p.pitch = c.tile_w; p.raw = raw_dev; p.hist = hist_dev;
-  fill_coefficients(p, k, channel_mode);
+  haematoxylin_byte_coefficients(p.kb, k, channel_mode);
   HIP_CHECK(e, hipSetDevice(e->device));
   const int rc = launch_nucleus_morph(p, (hipStream_t)stream);
   if (rc) FAIL(e, rc, "nucleus_morph launch failed");
@@ -223,7 +216,7 @@ int nuhtc_op_nucleus_morph(nuhtc_engine* e, const uint8_t* tiles, int channel_mo
   NucMorphParams p{};
   p.tiles = tiles; p.masks = masks; p.pairs = pairs_dev; p.n_dev = n_dev; p.lut = lut_dev; p.n_max = n_max;
   p.B = B; p.K = K; p.H = H; p.W = W; p.wpr = (W + 31) / 32; p.pitch = W; p.raw = raw; p.hist = hist;
-  fill_coefficients(p, k, channel_mode);
+  haematoxylin_byte_coefficients(p.kb, k, channel_mode);
   HIP_CHECK(e, hipSetDevice(e->device));
   hipStream_t s = (hipStream_t)stream;
   return op_finish(e, launch_nucleus_morph(p, s), s, "nucleus_morph launch failed", "nucleus_morph kernel failed");

@@ -176,7 +176,7 @@ class Engine:
         """Enqueue the whole path for a device-resident batch; outputs land in self.boxes/labels/counts/masks/keep."""
         B = tiles_dev.shape[0]
         self._last_tiles = tiles_dev          # (kept alive until the next call: buffer('img') is computed from them on request)
-        self._morph_src = (tiles_dev, channel_mode)     # what nuhtc_nucleus_morph reads: set by the inferences only, tiles and mode together
+        self._morph_src = (tiles_dev, channel_mode)     # what nuhtc_nucleus_morph / nuhtc_nucleus_texture read: set by the inferences only, tiles and mode together
         self._check(self.lib.nuhtc_infer(self.h, ctypes.c_void_p(tiles_dev.data_ptr()), B, channel_mode, self._stream(),
                                          ctypes.byref(self.dets)))
         return B
@@ -205,7 +205,7 @@ class Engine:
     def infer_fixed_load_async(self, tiles_dev, rois_dev, n_dets, channel_mode=hip.CH_AS_IS):
         B, n_rois = tiles_dev.shape[0], rois_dev.shape[1]
         self._last_tiles = tiles_dev
-        self._morph_src = (tiles_dev, channel_mode)     # what nuhtc_nucleus_morph reads: set by the inferences only, tiles and mode together
+        self._morph_src = (tiles_dev, channel_mode)     # what nuhtc_nucleus_morph / nuhtc_nucleus_texture read: set by the inferences only, tiles and mode together
         self._check(self.lib.nuhtc_infer_fixed_load(self.h, ctypes.c_void_p(tiles_dev.data_ptr()), B, channel_mode,
                                                     ctypes.c_void_p(rois_dev.data_ptr()), n_rois, n_dets, self._stream(),
                                                     ctypes.byref(self.dets)))
@@ -278,7 +278,7 @@ class Engine:
         return ln, off, data, bbox
 
     def export_async(self, B, cap=None, contour_cap=256, crop_words_per_det=128, rle=False, rle_bytes_per_det=256, rle_run_cap=hip.RLE_MAX_RUNS,
-                     nucfeat=False, nucmorph=False):
+                     nucfeat=False, nucmorph=False, nuctex=False):
         """After infer_async: enqueue, on the current stream, everything the slide loop needs from the batch -- the outer
         contours (nuhtc_mask_contours), a gather of the kept detections, in (tile, slot) order (nuhtc_export_kept), and their
         masks cropped to their bounding rectangles into one word pool (nuhtc_export_crops) -- into fixed-capacity pinned host
@@ -294,7 +294,9 @@ class Engine:
         its mask, nuhtc_amd.nucfeat.pool_reference): the blob gains feat [cap, 256] float32, 1 KB per detection in the same single copy.
         nucmorph=True: the morphometry integers of every kept detection as well (nuhtc_nucleus_morph on the tiles of the last infer_async,
         which the caller keeps alive until the stream has passed this call; nuhtc_amd.nucmorph.morph_reference): the blob gains morph_raw
-        [cap, 16] int64 and morph_hist [cap, 256] int32, 1152 bytes per detection in the same single copy."""
+        [cap, 16] int64 and morph_hist [cap, 256] int32, 1152 bytes per detection in the same single copy.
+        nuctex=True: the grey-level co-occurrence counts of every kept detection as well (nuhtc_nucleus_texture, on the same tiles;
+        nuhtc_amd.nuctex.glcm_reference): the blob gains tex [cap, 2, 136] int32, 1088 bytes per detection in the same single copy."""
         K, W = self.cfg.max_per_img, self.cfg.tile_h * (self.cfg.tile_w // 32)
         if rle and self.cfg.tile_w != self.image_hw[1]:
             raise ValueError(f'export_async(rle=True): image width {self.image_hw[1]} is not a multiple of 32')
@@ -305,7 +307,7 @@ class Engine:
         pool = cap * int(crop_words_per_det)
         rle_pool = cap * int(rle_bytes_per_det) if rle else 0
         ex = getattr(self, '_ex', None)
-        if ex is None or ex['cap'] != cap or ex['ccap'] != contour_cap or ex['pool'] != pool or ex['rle_pool'] != rle_pool or ex['nucfeat'] != bool(nucfeat) or ex['nucmorph'] != bool(nucmorph):
+        if ex is None or ex['cap'] != cap or ex['ccap'] != contour_cap or ex['pool'] != pool or ex['rle_pool'] != rle_pool or ex['nucfeat'] != bool(nucfeat) or ex['nucmorph'] != bool(nucmorph) or ex['nuctex'] != bool(nuctex):
             dev = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=self.device)
             names = dict(nk=((2,), torch.int32), idx=((cap,), torch.int64), boxes=((cap, 5), torch.float32), labels=((cap,), torch.int32),
                          cn=((cap,), torch.int32), crop_box=((cap, 4), torch.int32), crop_area=((cap,), torch.int32),
@@ -317,6 +319,8 @@ class Engine:
                 names.update(feat=((cap, 256), torch.float32))
             if nucmorph:
                 names.update(morph_raw=((cap, 16), torch.int64), morph_hist=((cap, 256), torch.int32))
+            if nuctex:
+                names.update(tex=((cap, 2, 136), torch.int32))
             # every field is a view into ONE device buffer and ONE pinned host buffer: a batch's results leave the device in a single
             # copy (each asynchronous copy on a compute stream costs a hand-over between the copy engine and the kernels)
             offs, total = {}, 0
@@ -330,7 +334,7 @@ class Engine:
             # export_async after the one that filled them (i.e. until the slot's next-but-one batch is enqueued)
             blob_hosts = [torch.zeros(total, dtype=torch.uint8).pin_memory() for _ in range(self.EXPORT_BUFFERS)]
             view = lambda blob, k: blob[offs[k]:offs[k] + int(np.prod(names[k][0])) * torch.empty(0, dtype=names[k][1]).element_size()].view(names[k][1]).view(*names[k][0])
-            ex = self._ex = dict(cap=cap, ccap=contour_cap, pool=pool, rle_pool=rle_pool, nucfeat=bool(nucfeat), nucmorph=bool(nucmorph), blob_dev=blob_dev, blob_hosts=blob_hosts, turn=0,
+            ex = self._ex = dict(cap=cap, ccap=contour_cap, pool=pool, rle_pool=rle_pool, nucfeat=bool(nucfeat), nucmorph=bool(nucmorph), nuctex=bool(nuctex), blob_dev=blob_dev, blob_hosts=blob_hosts, turn=0,
                                  hosts=[{k: view(b, k) for k in names} for b in blob_hosts], dev={k: view(blob_dev, k) for k in names})
             ex['dev']['words'] = dev(cap, W, dtype=torch.int32)          # full masks of the kept detections: device only
         self.contours_async(B, contour_cap)
@@ -351,6 +355,8 @@ class Engine:
             self._check(self.lib.nuhtc_nucleus_features(self.h, ctypes.byref(self.dets), B, vp(d['idx']), vp(d['nk']), cap, vp(d['feat']), self._stream()))
         if nucmorph:    # likewise, on the tiles the inference read
             self._nucleus_morph(B, vp(d['idx']), vp(d['nk']), cap, vp(d['morph_raw']), vp(d['morph_hist']))
+        if nuctex:
+            self._nucleus_texture(B, vp(d['idx']), vp(d['nk']), cap, vp(d['tex']))
         ex['turn'] = (ex['turn'] + 1) % self.EXPORT_BUFFERS
         ex['host'] = ex['hosts'][ex['turn']]
         ex['blob_hosts'][ex['turn']].copy_(ex['blob_dev'], non_blocking=True)
@@ -388,6 +394,8 @@ class Engine:
             g.update(feat=ex['feat'][:n].numpy())
         if 'morph_raw' in ex:       # exported with nucmorph=True: row k holds the integers of detection k
             g.update(morph_raw=ex['morph_raw'][:n].numpy(), morph_hist=ex['morph_hist'][:n].numpy())
+        if 'tex' in ex:             # exported with nuctex=True: row k holds the co-occurrence counts of detection k
+            g.update(tex=ex['tex'][:n].numpy())
         return g
 
     def nucleus_features(self, B, tile, slot):
@@ -431,6 +439,25 @@ class Engine:
         vp = lambda t: ctypes.c_void_p(t.data_ptr())
         self._nucleus_morph(B, vp(idx), vp(cnt), n, vp(raw), vp(hist))
         return raw.cpu().numpy(), hist.cpu().numpy()
+
+    def _nucleus_texture(self, B, idx, n_dev, cap, tex):
+        lut, k = self._morph_constants()
+        tiles, mode = self._morph_src
+        self._check(self.lib.nuhtc_nucleus_texture(self.h, ctypes.byref(self.dets), B, ctypes.c_void_p(tiles.data_ptr()), mode,
+                                                   ctypes.c_void_p(lut.data_ptr()), k, idx, n_dev, cap, tex, self._stream()))
+
+    def nucleus_texture(self, B, tile, slot):
+        """Co-occurrence counts of the detections (tile[i], slot[i]) of the last infer_async, synchronously (nuhtc_nucleus_texture on a list
+        made here; export_async(nuctex=True) is the asynchronous route) -> int32 (n, 2, 136) ndarray."""
+        n = len(tile)
+        if n == 0:
+            return np.zeros((0, 2, 136), np.int32)
+        idx = torch.from_numpy(np.asarray(tile, np.int64) * self.cfg.max_per_img + np.asarray(slot, np.int64)).to(self.device)
+        cnt = torch.tensor([n], dtype=torch.int32, device=self.device)
+        tex = torch.zeros(n, 2, 136, dtype=torch.int32, device=self.device)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        self._nucleus_texture(B, vp(idx), vp(cnt), n, vp(tex))
+        return tex.cpu().numpy()
 
     def export_full_mask(self, k):
         """(tile_h, tile_w) bool mask of exported detection k of the last export_async (synchronous device read: the rare crop that
@@ -901,6 +928,29 @@ class Engine:
         self._check(self.lib.nuhtc_op_nucleus_morph(self.h, vp(tiles), int(channel_mode), vp(lut), k, B, vp(masks), K, H, W, vp(pairs),
                                                     vp(n) if n is not None else None, n_max, vp(raw), vp(hist), self._stream()))
         return raw, hist
+
+    def op_nucleus_texture(self, tiles, masks, pairs, channel_mode=hip.CH_AS_IS, n=None, out=None):
+        """Per-nucleus grey-level co-occurrence counts on raw arrays (nuhtc_op_nucleus_texture; nuhtc_amd.nuctex.glcm_reference is the numpy
+        restatement).  tiles, masks, pairs, channel_mode and n as in op_nucleus_morph; out: a contiguous int32 (n_max, 2, 136) device tensor to
+        write into (rows from n on stay as they are), a zero-filled one otherwise.  -> out.  Synchronous."""
+        for t, dt in ((tiles, torch.uint8), (masks, torch.int32), (pairs, torch.int32)):
+            if t.device != self.device or t.dtype != dt or not t.is_contiguous():
+                raise ValueError('op_nucleus_texture: contiguous tensors on the engine\'s device (uint8 tiles, int32 masks and pairs)')
+        if tiles.dim() != 4 or masks.dim() != 4 or tiles.shape[3] != 3 or tuple(pairs.shape[1:]) != (2,):
+            raise ValueError('op_nucleus_texture: tiles (B, H, W, 3), masks (B, K, H, (W + 31) // 32), pairs (n, 2)')
+        B, H, W = (int(v) for v in tiles.shape[:3])
+        K, n_max = int(masks.shape[1]), int(pairs.shape[0])
+        if tuple(masks.shape) != (B, K, H, (W + 31) // 32):
+            raise ValueError('op_nucleus_texture: tiles (B, H, W, 3), masks (B, K, H, (W + 31) // 32), pairs (n, 2)')
+        if out is None:
+            out = torch.zeros(n_max, 2, 136, dtype=torch.int32, device=self.device)
+        if out.device != self.device or out.dtype != torch.int32 or not out.is_contiguous() or tuple(out.shape) != (n_max, 2, 136):
+            raise ValueError('op_nucleus_texture: out must be a contiguous int32 (n_max, 2, 136) tensor on the engine\'s device')
+        lut, k = self._morph_constants()
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        self._check(self.lib.nuhtc_op_nucleus_texture(self.h, vp(tiles), int(channel_mode), vp(lut), k, B, vp(masks), K, H, W, vp(pairs),
+                                                      vp(n) if n is not None else None, n_max, vp(out), self._stream()))
+        return out
 
     def op_eval_select(self, scores, counts, masks, fg_thr, thr, labels=None):
         """Score filter + greedy mask-NMS of `WSIDataset.evaluate` (nuhtc_op_eval_select): scores (B, K) float32, counts (B,), masks

@@ -155,7 +155,8 @@ EXPORTS = ['nuhtc_default_config', 'nuhtc_create', 'nuhtc_destroy', 'nuhtc_last_
            'nuhtc_eval_batch', 'nuhtc_op_eval_select', 'nuhtc_op_eval_pairs', 'nuhtc_op_eval_render', 'nuhtc_op_eval_joint',
            'nuhtc_stitch_gather', 'nuhtc_stitch_pairs', 'nuhtc_stitch_render', 'nuhtc_op_stitch_gather', 'nuhtc_op_stitch_pairs', 'nuhtc_op_stitch_render',
            'nuhtc_tissue_mask', 'nuhtc_points_polygon_test', 'nuhtc_grid_in_contour', 'nuhtc_rle_encode',
-           'nuhtc_nucleus_features', 'nuhtc_op_nucleus_pool', 'nuhtc_cell_graph', 'nuhtc_nucleus_morph', 'nuhtc_op_nucleus_morph']
+           'nuhtc_nucleus_features', 'nuhtc_op_nucleus_pool', 'nuhtc_cell_graph', 'nuhtc_nucleus_morph', 'nuhtc_op_nucleus_morph',
+           'nuhtc_nucleus_texture', 'nuhtc_op_nucleus_texture']
 
 _lib = None
 
@@ -232,6 +233,8 @@ def load():
     lib.nuhtc_cell_graph.argtypes = [ci, vp, vp, ctypes.c_int64, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]
     lib.nuhtc_nucleus_morph.argtypes = [vp, ctypes.POINTER(Dets), ci, vp, ci, vp, i4, vp, vp, ci, vp, vp, vp]
     lib.nuhtc_op_nucleus_morph.argtypes = [vp, vp, ci, vp, i4, ci, vp, ci, ci, ci, vp, vp, ci, vp, vp, vp]
+    lib.nuhtc_nucleus_texture.argtypes = [vp, ctypes.POINTER(Dets), ci, vp, ci, vp, i4, vp, vp, ci, vp, vp]
+    lib.nuhtc_op_nucleus_texture.argtypes = [vp, vp, ci, vp, i4, ci, vp, ci, ci, ci, vp, vp, ci, vp, vp]
     lib.nuhtc_export_kept.argtypes = [vp, ctypes.POINTER(Dets), ci, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.nuhtc_export_crops.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, ci, vp]
     lib.nuhtc_profile_enable.argtypes = [ci]

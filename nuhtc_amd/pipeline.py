@@ -61,11 +61,12 @@ class EnginePipeline:
     def _held(self, slot):
         return [p for p in self.pending if p[0] == slot]
 
-    def submit(self, tiles, channel_mode, tag=None, export=False, rle=False, nucfeat=False, nucmorph=False):
+    def submit(self, tiles, channel_mode, tag=None, export=False, rle=False, nucfeat=False, nucmorph=False, nuctex=False):
         """Enqueue one batch (host ndarray / tensor, or device tensor) on the next slot; returns the slot's engine.
         Raises when that slot cannot take another batch (collect() first: see full()).  export=True also enqueues
         Engine.export_async (rle=True: with the COCO run-length strings of the kept detections; nucfeat=True: with their embeddings; nucmorph=True: with
-        their morphometry integers, read from the batch's device tiles, which stay referenced here until collect())."""
+        their morphometry integers, nuctex=True: with their co-occurrence counts, both read from the batch's device tiles, which stay referenced here until
+        collect())."""
         slot = self.next
         held = self._held(slot)
         if held and (not export or len(held) >= self.per_slot or any(p[5] is None for p in held)):
@@ -96,6 +97,8 @@ class EnginePipeline:
                     kw['nucfeat'] = True
                 if nucmorph:
                     kw['nucmorph'] = True
+                if nuctex:
+                    kw['nuctex'] = True
                 turn = eng.export_async(B, **kw)
             ev = torch.cuda.Event()
             ev.record(st)

@@ -25,7 +25,7 @@ def tile_grid(image, patch_size=256, step_size=192):
     return np.stack(tiles), np.array(coords, np.int64)
 
 
-def _gather_sync(eng, B, nucfeat=False, nucmorph=False):
+def _gather_sync(eng, B, nucfeat=False, nucmorph=False, nuctex=False):
     """Synchronous twin of Engine.export_async / export_read (any number of kept detections)."""
     import torch
     K = eng.cfg.max_per_img
@@ -42,6 +42,8 @@ def _gather_sync(eng, B, nucfeat=False, nucmorph=False):
         g['feat'] = eng.nucleus_features(B, tile, slot)
     if nucmorph:
         g['morph_raw'], g['morph_hist'] = eng.nucleus_morph(B, tile, slot)
+    if nuctex:
+        g['tex'] = eng.nucleus_texture(B, tile, slot)
     return g
 
 
@@ -232,6 +234,9 @@ def _unpack_packed(eng, g, i0, coords, parts):
     if 'morph_raw' in g:                                                  # exported with nucmorph=True: one row of integers per record
         from . import nucmorph
         parts[-1].update(morph=nucmorph.pack_rows(g['morph_raw'][order], g['morph_hist'][order], org))
+    if 'tex' in g:                                                        # exported with nuctex=True: one row of counts per record
+        from . import nuctex
+        parts[-1].update(tex=nuctex.pack_rows(g['tex'][order]))
 
 
 def _records_from_parts(parts):
@@ -253,17 +258,20 @@ def _records_from_parts(parts):
         rec.update(feat=cat('feat'))
     if 'morph' in parts[0]:
         rec.update(morph=cat('morph'))
+    if 'tex' in parts[0]:
+        rec.update(tex=cat('tex'))
     return rec
 
 
-def _unpack(eng, B, i0, coords, P, rec, exported=False, nucfeat=False, nucmorph=False):
+def _unpack(eng, B, i0, coords, P, rec, exported=False, nucfeat=False, nucmorph=False, nuctex=False):
     """Kept detections of one finished batch -> records in slide coordinates.  `exported`: the batch was submitted with
     export=True (its results already sit in the engine's pinned buffers); otherwise they are fetched here (nucfeat: with the
-    embeddings, appended to rec['feat']; nucmorph: with the morphometry rows, appended to rec['morph'])."""
+    embeddings, appended to rec['feat']; nucmorph: with the morphometry rows, appended to rec['morph']; nuctex: with the
+    co-occurrence rows, appended to rec['tex'])."""
     from . import contours as host
     g = eng.export_read() if exported else None
     if g is None:
-        g = _gather_sync(eng, B, nucfeat, nucmorph)
+        g = _gather_sync(eng, B, nucfeat, nucmorph, nuctex)
     n = g['n']
     if n == 0:
         return
@@ -312,9 +320,12 @@ def _unpack(eng, B, i0, coords, P, rec, exported=False, nucfeat=False, nucmorph=
         if 'morph_raw' in g:
             from . import nucmorph
             rec.setdefault('morph', []).append(nucmorph.pack_rows(g['morph_raw'][k], g['morph_hist'][k], (ox, oy))[0])
+        if 'tex' in g:
+            from . import nuctex as nt
+            rec.setdefault('tex', []).append(nt.pack_rows(g['tex'][k])[0])
 
 
-def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False, nucfeat=False, nucmorph=False):
+def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False, nucfeat=False, nucmorph=False, nuctex=False):
     """Run the engine over `tiles` (N,P,P,3) and return per-detection records that survive the per-tile margin /
     min-area filter + mask-NMS (computed on the GPU, tools/infer_wsi.py:510-531), in slide coordinates.  `depth` engines
     are kept busy with up to two batches each (nuhtc_amd.pipeline): the host unpacks batch i while the GPU runs the next ones.
@@ -328,11 +339,15 @@ def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False, nucfeat
     nucfeat=True adds feat float32 (n, 256): the embedding of every record, the FPN maps of its tile averaged under its mask on the GPU
     (nuhtc_nucleus_features; nuhtc_amd.nucfeat), row i for record i.
     nucmorph=True adds morph int64 (n, nucmorph.ROW = 146): the morphometry integers of every record, computed on the GPU under its mask from the tile's
-    pixels (nuhtc_nucleus_morph), with its tile's origin (nuhtc_amd.nucmorph.unpack_rows -> raw, hist, origin), row i for record i."""
+    pixels (nuhtc_nucleus_morph), with its tile's origin (nuhtc_amd.nucmorph.unpack_rows -> raw, hist, origin), row i for record i.
+    nuctex=True adds tex int64 (n, nuctex.ROW = 136): the grey-level co-occurrence counts of every record, taken on the GPU under its mask from the
+    tile's pixels (nuhtc_nucleus_texture; nuhtc_amd.nuctex.unpack_rows -> glcm int32 (n, 2, 136)), row i for record i."""
     import torch
     more = dict(nucfeat=True) if nucfeat else {}
     if nucmorph:
         more['nucmorph'] = True
+    if nuctex:
+        more['nuctex'] = True
     P = tiles.shape[1]
     parts = {}                 # first tile of the batch -> the batch's records (array form), joined in batch order at the end
     redo = []
@@ -363,7 +378,7 @@ def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False, nucfeat
         eng, B, stream, _ = pipe.collect()
         with torch.cuda.stream(stream):
             one = dict(tile=[], box=[], score=[], label=[], mask=[], ring=[])
-            _unpack(eng, B, i0, coords, P, one, exported=False, nucfeat=nucfeat, nucmorph=nucmorph)
+            _unpack(eng, B, i0, coords, P, one, exported=False, nucfeat=nucfeat, nucmorph=nucmorph, nuctex=nuctex)
             if one['tile']:
                 parts[i0] = _part_from_lists(one)
                 if rle:                                            # nothing of this batch was encoded on the device
@@ -378,6 +393,9 @@ def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False, nucfeat
     if nucmorph and 'morph' not in rec:
         from . import nucmorph as nm
         rec.update(morph=np.zeros((0, nm.ROW), np.int64))
+    if nuctex and 'tex' not in rec:
+        from . import nuctex as nt
+        rec.update(tex=np.zeros((0, nt.ROW), np.int64))
     return rec
 
 
@@ -395,6 +413,8 @@ def _part_from_lists(rec):
         part.update(feat=np.stack(rec['feat']).astype(np.float32))
     if 'morph' in rec:
         part.update(morph=np.stack(rec['morph']).astype(np.int64))
+    if 'tex' in rec:
+        part.update(tex=np.stack(rec['tex']).astype(np.int64))
     return part
 
 
@@ -407,6 +427,8 @@ def _extend(rec, more):
         rec.setdefault('feat', []).extend(list(more['feat']))
     if 'morph' in more:
         rec.setdefault('morph', []).extend(list(more['morph']))
+    if 'tex' in more:
+        rec.setdefault('tex', []).extend(list(more['tex']))
 
 
 def pack_masks(masks):
@@ -488,7 +510,9 @@ def pack_records(rec, keep=None, tile_base=0, rles=None):
     Records that carry embeddings (rec['feat'], infer_tiles(nucfeat=True)) travel with one more part behind these five:
     feat  float32 (n, 256): the rows of the records `keep`;
     and records that carry morphometry rows (rec['morph'], infer_tiles(nucmorph=True)) with one more behind that:
-    morph int64 (n, nucmorph.ROW = 146): the rows of the records `keep`."""
+    morph int64 (n, nucmorph.ROW = 146): the rows of the records `keep`;
+    and records that carry co-occurrence rows (rec['tex'], infer_tiles(nuctex=True)) with one more behind that:
+    tex   int64 (n, nuctex.ROW = 136): the rows of the records `keep`."""
     import torch
     if isinstance(rles, tuple):                                    # the device's blob + lengths: one gather, no per-record objects
         ball, lall = np.asarray(rles[0], np.uint8), np.asarray(rles[1], np.int64)
@@ -511,7 +535,7 @@ def pack_records(rec, keep=None, tile_base=0, rles=None):
         m = rec['mask'].subset(kp)
         crops = np.concatenate([m.boxes.astype(np.int64), m.areas[:, None].astype(np.int64), m.off[:, None]], 1) if n else np.zeros((0, 6), np.int64)
         return [torch.from_numpy(head), torch.from_numpy(verts), torch.from_numpy(crops), torch.from_numpy(m.bits.view(np.int32).copy()),
-                torch.from_numpy(rle_blob)] + _feat_part(rec, kp) + _morph_part(rec, kp)
+                torch.from_numpy(rle_blob)] + _feat_part(rec, kp) + _morph_part(rec, kp) + _tex_part(rec, kp)
     keep = list(range(len(rec['score']))) if keep is None else list(keep)
     n = len(keep)
     head = np.zeros((n, 9), np.float64)
@@ -526,7 +550,7 @@ def pack_records(rec, keep=None, tile_base=0, rles=None):
     if n == 0:
         mbits = np.zeros(0, np.uint32)
     return [torch.from_numpy(head), torch.from_numpy(verts), torch.from_numpy(crops), torch.from_numpy(mbits.view(np.int32).copy()),
-            torch.from_numpy(rle_blob)] + _feat_part(rec, keep) + _morph_part(rec, keep)
+            torch.from_numpy(rle_blob)] + _feat_part(rec, keep) + _morph_part(rec, keep) + _tex_part(rec, keep)
 
 
 def _feat_part(rec, keep):
@@ -553,6 +577,24 @@ def gathered_morph(gathered, kept=None, part=5):
     merge_gathered indexes, or only the rows `kept`, in that order -> int64 (n, nucmorph.ROW) (nuhtc_amd.nucmorph.unpack_rows)."""
     from . import nucmorph
     rows = np.concatenate([np.asarray(g[part].cpu().numpy(), np.int64).reshape(-1, nucmorph.ROW) for g in gathered], 0)
+    return rows if kept is None else rows[np.asarray(kept, np.int64)]
+
+
+def _tex_part(rec, keep):
+    """pack_records' part behind the morphometry: the co-occurrence rows of the records `keep` (no part for records without them)."""
+    import torch
+    if 'tex' not in rec:
+        return []
+    from . import nuctex
+    rows = np.asarray(rec['tex'], np.int64).reshape(-1, nuctex.ROW)
+    return [torch.from_numpy(np.ascontiguousarray(rows[np.asarray(list(keep), np.int64)]))]
+
+
+def gathered_texture(gathered, kept=None, part=5):
+    """Rank 0 after the gather: the co-occurrence rows of all ranks' records (part `part` of each rank's list) in the rank-major order
+    merge_gathered indexes, or only the rows `kept`, in that order -> int64 (n, nuctex.ROW) (nuhtc_amd.nuctex.unpack_rows)."""
+    from . import nuctex
+    rows = np.concatenate([np.asarray(g[part].cpu().numpy(), np.int64).reshape(-1, nuctex.ROW) for g in gathered], 0)
     return rows if kept is None else rows[np.asarray(kept, np.int64)]
 
 

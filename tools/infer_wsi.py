@@ -37,7 +37,13 @@ Output (like the reference, :659-693), for every detection that survives the per
                   under histomicstk's names, derived on the host (nuhtc_amd/nucmorph.py derive) from the integers every rank's GPU measured
                   under the final mask (`raw` int64 (n, 16), `hist` int32 (n, 256), `origin`) -- with `nuclei_id`, `label`, `score`.
                   Row-aligned with <id>_nuclei_feat.npz and <id>_nuclei_graph.npz; every other file is the same bytes with and without the
-                  flag.  There is no route without a GPU."""
+                  flag.  There is no route without a GPU.
+  --nuclei-texture: (the 26 Haralick columns of the same table) <id>_nuclei_texture.npz beside the documents, for the same rows: `columns`
+                  and `values` float64 (n, 26) -- Haralick.<feature>.Mean / .Range over the offsets (0, 1) and (1, 0), derived on the host
+                  (nuhtc_amd/nuctex.py derive) from the grey-level co-occurrence counts every rank's GPU took under the final mask (`glcm`
+                  int32 (n, 2, 136): 16 levels of the haematoxylin value, the upper triangle) -- with `nuclei_id`, `label`, `score`.
+                  Row-aligned with the other per-nucleus files; every other file is the same bytes with and without the flag.  There is no
+                  route without a GPU."""
 import argparse
 import os
 import sys
@@ -94,6 +100,9 @@ def build_parser():
     p.add_argument('--nuclei-morph', action='store_true', dest='nuclei_morph',
                    help='also write <id>_nuclei_morph.npz: size, shape and haematoxylin-intensity features of every written nucleus, from integers '
                         'measured under its mask on the GPU (rows as in <id>_nuclei_feat.npz)')
+    p.add_argument('--nuclei-texture', action='store_true', dest='nuclei_texture',
+                   help='also write <id>_nuclei_texture.npz: the 26 Haralick texture features of every written nucleus, from grey-level co-occurrence '
+                        'counts taken under its mask on the GPU (rows as in <id>_nuclei_feat.npz)')
     p.add_argument('--nuclei-graph', action='store_true', dest='nuclei_graph',
                    help='also write <id>_nuclei_graph.npz: the --graph-k nearest nuclei of every written nucleus within --graph-radius, their distances and '
                         'the class counts around it, built on the GPU (rows as in <id>_nuclei_feat.npz)')
@@ -122,6 +131,9 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
     more = dict(nucfeat=True) if nucfeat else {}
     if nucmorph:
         more['nucmorph'] = True
+    nuctex = bool(getattr(args, 'nuclei_texture', False))
+    if nuctex:
+        more['nuctex'] = True
     rec = wsi.infer_tiles(model, tiles, coords[lo:hi], args.batch_size, rle=rle_gpu, **more)
     # contours are traced on the rank that owns the tile; two variable-length gathers: records, then ring vertices
     rings = rec['ring']                                              # traced on the GPU (nuhtc_mask_contours)
@@ -151,7 +163,8 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
     # the one exchange of the path: every rank's records (head, ring vertices, mask crops, RLE strings) in a single all-gather
     dev = torch.device('cuda', local_rank) if world > 1 and torch.cuda.is_available() else torch.device('cpu')
     parts = wsi.pack_records(rec, keep, tile_base=lo, rles=rles)
-    morph_part = parts.pop() if nucmorph else None                   # pack_records' last part, behind the embeddings
+    tex_part = parts.pop() if nuctex else None                       # pack_records' last part, behind the morphometry
+    morph_part = parts.pop() if nucmorph else None                   # behind the embeddings
     feat_part = parts.pop() if nucfeat else None                     # pack_records' sixth part: it travels behind the documents' parts
     if want('qupath'):
         # every rank writes the GeoJSON text of ITS records (the reference's one Python loop over all nuclei, :533-585 + json.dump :659-664,
@@ -166,6 +179,9 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
     morph_at = len(parts)
     if nucmorph:                                                      # and their morphometry integers
         parts.append(morph_part)
+    tex_at = len(parts)
+    if nuctex:                                                        # and their co-occurrence counts
+        parts.append(tex_part)
     if rle_gpu:                                                       # bbox / area of the annotations: rank 0 parses no string
         kp = np.asarray(keep, np.int64)
         parts.append(torch.from_numpy(np.ascontiguousarray(rec['rle_bbox'][kp], np.int32)))
@@ -240,6 +256,13 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
         raw, hist, origin = nm.unpack_rows(wsi.gathered_morph(gathered, rows, part=morph_at))
         nm.write_npz(os.path.join(out_dir, name + '_nuclei_morph.npz'), rows, raw, hist, hall[rows, 5].astype(np.int64), hall[rows, 4], origin)
         msg += f', {len(rows)} rows of {len(nm.COLUMNS)} features in {name}_nuclei_morph.npz'
+    if nuctex:
+        from nuhtc_amd import nuctex as nt
+        hall = np.concatenate([h.cpu().numpy() for h in heads], 0).reshape(-1, 9)
+        rows = np.arange(n_records, dtype=np.int64) if feat_rows is None else feat_rows
+        nt.write_npz(os.path.join(out_dir, name + '_nuclei_texture.npz'), rows, nt.unpack_rows(wsi.gathered_texture(gathered, rows, part=tex_at)),
+                     hall[rows, 5].astype(np.int64), hall[rows, 4])
+        msg += f', {len(rows)} rows of {len(nt.COLUMNS)} features in {name}_nuclei_texture.npz'
     if getattr(args, 'nuclei_graph', False):                          # the edges to those rows: only what the gather already delivered
         from nuhtc_amd import cellgraph
         hall = np.concatenate([h.cpu().numpy() for h in heads], 0).reshape(-1, 9)
@@ -287,6 +310,8 @@ def main(argv=None):
             raise SystemExit(f'--rle-on gpu: --patch_size {args.patch_size} is not a multiple of 32 (the device encodes bit-packed rows of 32 pixels; use --rle-on host)')
     if args.nuclei_morph and not torch.cuda.is_available():
         raise SystemExit('--nuclei-morph: no GPU is visible (there is no fallback)')
+    if args.nuclei_texture and not torch.cuda.is_available():
+        raise SystemExit('--nuclei-texture: no GPU is visible (there is no fallback)')
     if args.nuclei_graph:
         from nuhtc_amd import cellgraph
         if not torch.cuda.is_available():
