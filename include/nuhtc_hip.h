@@ -360,6 +360,36 @@ typedef struct nuhtc_wmsa_args {
   int32_t shifted, pipe, out_order;
 } nuhtc_wmsa_args;
 int nuhtc_op_window_msa(nuhtc_engine* e, const nuhtc_wmsa_args* a, void* stream);
+/* The front of the path and the small dense kernels, op by op, as test entry points.  Each goes through the host code nuhtc_finalize and the step
+ * use for the same launch (resize tables, weight repacking, the lateral's GEMM parameters, the pooling's chunk layout), with private scratch that
+ * is freed before the call returns.  Pointers are device memory unless named *_host.  Each synchronises `stream`.
+ * nuhtc_op_patch_embed: tiles [B][th][tw][3] uint8 with the image in the top-left valid_h x valid_w -> cv2's 8-bit linear resize by scale_factor,
+ *   channel swap (channel_mode), Normalize (mean[3], std[3]: HOST), zero Pad to a multiple of 32 (Hn x Wn), the 4x4 stride-4 convolution (w_host
+ *   [96][3][4][4], b_host [96]) and LayerNorm(96) (ln_g_host, ln_b_host) -> tok [B * Hn/4 * Wn/4][96] by patch_embed_tiles_kernel; img (may be NULL)
+ *   [B][Hn][Wn][3], the normalised padded image by preproc_kernel from the same tables.  Refuses what nuhtc_create refuses of a scale: outside
+ *   [1, 8], or scale_factor * valid size not an integer (any resized size >= 1 is served here).
+ * nuhtc_op_layernorm: y [rows][C] = LayerNorm(x [rows][C]) (eps 1e-5) by the kernels launch_layernorm picks without a row map: C in {96, 192, 384, 768}.
+ * nuhtc_op_merge_ln: PatchMerging's gather + LayerNorm(4C) of the fp32 pipe: x [B][H][W][C] -> y [B * H/2 * W/2][4C], column k = (kh*2+kw)*C + c;
+ *   g, b [4C] in THAT order (nuhtc_finalize permutes the checkpoint's nn.Unfold order c*4 + kh*2+kw into it).  H, W even, C in {96, 192, 384}.
+ * nuhtc_op_fpn_lateral: out [B][H][W][64] = X W^T + bias (+ parent [B][H/2][W/2][64] at (y / 2, x / 2), NULL: the top level), parameters as run_fpn
+ *   fills them.  X [B*H*W][C]; W_host [64][C], bias_host [64].  With ln_g_host / ln_b_host [C] the rows are LayerNorm'ed in the product's A path
+ *   (split pipe: the norm folded into W and bias as nuhtc_finalize folds it, statistics by ln_stats_kernel as one partial per 96 columns -- what the
+ *   producers' epilogues leave); with both NULL X is used as it is and the product runs on the fp32 MFMA kernel (the fp32 pipe's form).
+ * nuhtc_op_sem_fuse: out [B][H][W][64] = relu(g0) + sum_i relu(bilinear_align_corners(g_i [B][H >> i][W >> i][64] -> H x W)), i = 1..3; H, W % 8 == 0.
+ * nuhtc_op_pointwise64: y [row] = w [64] . x [row][64] + b [1].  rows_dev NULL: the fixed-row launch over `rows` rows (sigmoid must be 0); else the
+ *   grid-strided launch sized by the capacity `rows`, limited on the device to min(rows, *rows_dev * rows_mul) rows, y = sigmoid(.) when `sigmoid`.
+ * nuhtc_op_fpn_mean_pool: maps[l] [B][hw[l]][64] -> feat [B][256] = the per-channel means, level-major (the pooling of nuhtc_features). */
+int nuhtc_op_patch_embed(nuhtc_engine* e, const uint8_t* tiles_dev, int B, int th, int tw, int valid_h, int valid_w, float scale_factor, int channel_mode,
+                         const float* mean, const float* std, const float* w_host, const float* b_host, const float* ln_g_host, const float* ln_b_host,
+                         float* tok_dev, float* img_dev, void* stream);
+int nuhtc_op_layernorm(nuhtc_engine* e, const float* x_dev, const float* g_dev, const float* b_dev, float* y_dev, int rows, int C, void* stream);
+int nuhtc_op_merge_ln(nuhtc_engine* e, const float* x_dev, const float* g_dev, const float* b_dev, float* y_dev, int B, int H, int W, int C, void* stream);
+int nuhtc_op_fpn_lateral(nuhtc_engine* e, const float* X_dev, int B, int H, int W, int C, const float* W_host, const float* bias_host, const float* ln_g_host,
+                         const float* ln_b_host, const float* parent_dev, float* out_dev, void* stream);
+int nuhtc_op_sem_fuse(nuhtc_engine* e, const float* g0, const float* g1, const float* g2, const float* g3, float* out, int B, int H, int W, void* stream);
+int nuhtc_op_pointwise64(nuhtc_engine* e, const float* x_dev, const float* w_dev, const float* b_dev, float* y_dev, int rows, const int32_t* rows_dev,
+                         int rows_mul, int sigmoid, void* stream);
+int nuhtc_op_fpn_mean_pool(nuhtc_engine* e, const float* const maps[4], const int32_t hw[4], int B, float* feat_dev, void* stream);
 /* The detection tail of nuhtc_infer, op by op, as test entry points (csrc/roi.hip: everything behind the RoI features that turns numbers into
  * decisions).  Each fills the parameter block nuhtc_infer fills and calls the same launch function; integer arrays a kernel indexes with
  * (*r_dev, roi_off / roi_cnt, det_off / det_counts) are read back and checked against the stated capacities first.  All pointers are device

@@ -38,6 +38,39 @@ void nuhtc_default_config(nuhtc_config* c) {
   c->features_only = 0;
 }
 
+// ---- the front of the path, host side: what nuhtc_create / nuhtc_finalize / run_backbone and nuhtc_op_patch_embed share
+// the per-axis factors new / old (mmdet Resize: w_scale, h_scale) must both equal scale_factor, i.e. scale * size is an integer
+static bool resize_ok(int vh, int vw, float scale) {
+  const double sh = (double)vh * scale, sw = (double)vw * scale;
+  return scale >= 1.0f && scale <= 8.0f && sh == floor(sh) && sw == floor(sw);
+}
+// img_shape (Hv, Wv) = mmcv.rescale_size of the valid image, pad_shape (Hn, Wn) = Pad(size_divisor=32) of it, and cv2's per-axis tables
+struct ResizeGeom {
+  int Hv, Wv, Hn, Wn;
+  std::vector<int> tx, ty;
+};
+static ResizeGeom resize_geom(int vh, int vw, float scale) {
+  ResizeGeom r;
+  r.Hv = (int)(vh * (double)scale + 0.5); r.Wv = (int)(vw * (double)scale + 0.5);
+  r.Hn = (r.Hv + 31) / 32 * 32; r.Wn = (r.Wv + 31) / 32 * 32;
+  cv_linear_tables(vw, r.Wv, true, r.tx);
+  cv_linear_tables(vh, r.Hv, false, r.ty);
+  return r;
+}
+// Normalize's constants as the kernels take them: mean[3], then 1 / std[3] (mmcv.imnormalize multiplies by the float64 reciprocal)
+static void norm_consts(const float mean[3], const float std[3], float mi[6]) {
+  for (int i = 0; i < 3; ++i) { mi[i] = mean[i]; mi[3 + i] = (float)(1.0 / (double)std[i]); }
+}
+// patch embedding weight [96][3][4][4] -> [48][96], k = (kh*4+kw)*3 + c
+static std::vector<float> pack_patch_embed(const float* w) {
+  std::vector<float> p(48 * 96);
+  for (int o = 0; o < 96; ++o)
+    for (int ch = 0; ch < 3; ++ch)
+      for (int kh = 0; kh < 4; ++kh)
+        for (int kw = 0; kw < 4; ++kw) p[((kh * 4 + kw) * 3 + ch) * 96 + o] = w[((o * 3 + ch) * 4 + kh) * 4 + kw];
+  return p;
+}
+
 const char* nuhtc_last_error(const nuhtc_engine* e) { return e ? e->err.c_str() : g_create_error.c_str(); }
 
 int nuhtc_create(const nuhtc_config* cfg, int device, nuhtc_engine** out) {
@@ -49,12 +82,11 @@ int nuhtc_create(const nuhtc_config* cfg, int device, nuhtc_engine** out) {
     // resized image = mmcv.rescale_size: int(size*scale + 0.5); the per-axis factors new/old (mmdet Resize: w_scale, h_scale) must
     // both equal scale_factor, i.e. scale*size is an integer.  Pad(size_divisor=32) then rounds the network input up.
     const int vh = cfg->valid_h ? cfg->valid_h : cfg->tile_h, vw = cfg->valid_w ? cfg->valid_w : cfg->tile_w;
-    const double sh = (double)vh * cfg->scale_factor, sw = (double)vw * cfg->scale_factor;
-    if (!(cfg->scale_factor >= 1.0f && cfg->scale_factor <= 8.0f) || sh != floor(sh) || sw != floor(sw)) {
+    if (!resize_ok(vh, vw, cfg->scale_factor)) {
       g_create_error = "scale_factor (80/mag) must be in [1,8] and scale_factor * image size must be integers";
       return NUHTC_E_INVALID;
     }
-    if (sh < 32 || sw < 32) { g_create_error = "the resized image must be at least 32 x 32"; return NUHTC_E_INVALID; }
+    if ((double)vh * cfg->scale_factor < 32 || (double)vw * cfg->scale_factor < 32) { g_create_error = "the resized image must be at least 32 x 32"; return NUHTC_E_INVALID; }
   }
   // class logits live in rows of 16 floats: num_classes + 2 (objectness pair) values per RoI, see bbox_tail_kernel
   if (cfg->num_classes < 1 || cfg->num_classes > 14) { g_create_error = "num_classes out of range (1..14)"; return NUHTC_E_INVALID; }
@@ -420,6 +452,14 @@ static MergePack pack_merge(const float* g, const float* b, const float* w, int 
   return m;
 }
 
+// nuhtc_features' pooling (csrc/pool.hip): the chunk layout of four maps of hw[l] pixels, and the bytes of the slab of partial sums for B tiles
+static int pool_layout(const int hw[4], PoolLevels& p) {
+  const int rc = pool_chunks(hw, p.choff);
+  for (int l = 0; l < 4; ++l) p.hw[l] = hw[l];
+  return rc;
+}
+static size_t pool_slab_bytes(const PoolLevels& p, int B) { return (size_t)B * p.choff[4] * 64 * sizeof(double); }
+
 // The route of a Swin block, from what is known at finalize.  The fp32 pipe has the plain kernels only; on the split pipe the block runs through the
 // fused kernels of mlp.hip where they exist for its channel count (stage 1), else with its two norms in the A path of the QKV / fc1 linears.
 static BlockRoute block_route(int matrix_pipe, int C) {
@@ -434,17 +474,13 @@ int nuhtc_finalize(nuhtc_engine* e) {
   const nuhtc_config& c = e->cfg;
   const int B = c.max_batch;
   e->vh = c.valid_h ? c.valid_h : c.tile_h; e->vw = c.valid_w ? c.valid_w : c.tile_w;
-  e->Hv = (int)(e->vh * (double)c.scale_factor + 0.5); e->Wv = (int)(e->vw * (double)c.scale_factor + 0.5);   // img_shape
-  const int Hn = (e->Hv + 31) / 32 * 32, Wn = (e->Wv + 31) / 32 * 32;                                            // pad_shape
+  const ResizeGeom rg = resize_geom(e->vh, e->vw, c.scale_factor);
+  e->Hv = rg.Hv; e->Wv = rg.Wv;             // img_shape
+  const int Hn = rg.Hn, Wn = rg.Wn;         // pad_shape
   e->Hn = Hn; e->Wn = Wn;
   int rc;
   std::vector<float> on_g_host[4], on_b_host[4];      // the stages' output norms, for the fold into the FPN laterals
-  {
-    std::vector<int> tx, ty;
-    cv_linear_tables(e->vw, e->Wv, true, tx);
-    cv_linear_tables(e->vh, e->Hv, false, ty);
-    if ((rc = upload(e, &e->rs_xtab, tx)) || (rc = upload(e, &e->rs_ytab, ty))) return rc;
-  }
+  if ((rc = upload(e, &e->rs_xtab, rg.tx)) || (rc = upload(e, &e->rs_ytab, rg.ty))) return rc;
   // ---- geometry
   for (int s = 0; s < 4; ++s) {
     stage_dims(e->st[s], Hn >> (2 + s), Wn >> (2 + s), 96 << s);
@@ -456,12 +492,7 @@ int nuhtc_finalize(nuhtc_engine* e) {
     RAW(b, "backbone.patch_embed.projection.bias", 96);
     RAW(g, "backbone.patch_embed.norm.weight", 96);
     RAW(be, "backbone.patch_embed.norm.bias", 96);
-    std::vector<float> p(48 * 96);
-    for (int o = 0; o < 96; ++o)
-      for (int ch = 0; ch < 3; ++ch)
-        for (int kh = 0; kh < 4; ++kh)
-          for (int kw = 0; kw < 4; ++kw) p[((kh * 4 + kw) * 3 + ch) * 96 + o] = w->data[((o * 3 + ch) * 4 + kh) * 4 + kw];
-    if ((rc = upload(e, &e->pe_w, p)) || (rc = upload(e, &e->pe_b, b->data)) || (rc = upload(e, &e->pe_g, g->data)) ||
+    if ((rc = upload(e, &e->pe_w, pack_patch_embed(w->data.data()))) || (rc = upload(e, &e->pe_b, b->data)) || (rc = upload(e, &e->pe_g, g->data)) ||
         (rc = upload(e, &e->pe_beta, be->data)))
       return rc;
   }
@@ -551,9 +582,8 @@ int nuhtc_finalize(nuhtc_engine* e) {
   {      // ---- nuhtc_features: chunk layout of the four maps and the slab of the pooling's partial sums (csrc/pool.hip)
     int hw[4];
     for (int l = 0; l < 4; ++l) hw[l] = e->st[l].H * e->st[l].W;
-    if ((rc = pool_chunks(hw, e->pool.choff))) FAIL(e, rc, "pool_chunks: empty FPN level");
-    for (int l = 0; l < 4; ++l) e->pool.hw[l] = hw[l];
-    if ((rc = dev_alloc(e, (void**)&e->pool_slab, (size_t)B * e->pool.choff[4] * 64 * sizeof(double)))) return rc;
+    if ((rc = pool_layout(hw, e->pool))) FAIL(e, rc, "pool_chunks: empty FPN level");
+    if ((rc = dev_alloc(e, (void**)&e->pool_slab, pool_slab_bytes(e->pool, B)))) return rc;
   }
   const bool heads = !c.features_only;      // a features-only engine packs and allocates nothing behind the FPN
   // ---- RPN: 3x3 conv, then cls(3)+reg(12) fused into one N=32 pointwise layer (cols 0-2 cls, 3-14 reg, rest 0)
@@ -732,7 +762,7 @@ int run_backbone(nuhtc_engine* e, int B, hipStream_t s) {
   auto linear = [&](GemmParams p) { p.throughput = e->cfg.schedule == NUHTC_SCHED_THROUGHPUT; return egemm(e, p, s); };
   {      // resize + Normalize + Pad inside the patch embedding: one launch, no `img` tensor (profiles/r05_preproc_fused.txt)
     float mi[6];
-    for (int i = 0; i < 3; ++i) { mi[i] = e->cfg.mean[i]; mi[3 + i] = (float)(1.0 / (double)e->cfg.std[i]); }
+    norm_consts(e->cfg.mean, e->cfg.std, mi);
     RUN(launch_patch_embed_tiles(e->in_tiles, B, e->cfg.tile_h, e->cfg.tile_w, Hn, Wn, e->Hv, e->Wv, e->rs_xtab, e->rs_ytab, e->in_swap, mi, e->pe_w, e->pe_b, e->pe_g, e->pe_beta,
                                  e->tokA, s));
   }
@@ -811,16 +841,25 @@ int run_backbone(nuhtc_engine* e, int B, hipStream_t s) {
   return 0;
 }
 
+// An FPN lateral (fpn.py:152-179) of B maps of H x W tokens of C channels: out = A W^T + bias, + the nearest-upsampled coarser lateral
+// `parent` [B][H/2][W/2][64] in the epilogue (null: the top level).  ln_part: the rows are LayerNorm'ed in the product's A path (gemm.hip A_LN;
+// W, bias with the norm folded in) from C / 96 partials per row.
+static GemmParams lateral_params(const float* A, const float* W, const float* bias, float* out, int B, int H, int Wd, int C, const float* ln_part,
+                                 const float* parent) {
+  GemmParams p = gp(A, W, bias, out, B * H * Wd, 64, C);
+  if (ln_part) { p.amode = A_LN; p.ln_part = ln_part; p.ln_nparts = C / 96; }
+  if (parent) { p.up = parent; p.upH = H; p.upW = Wd; }
+  return p;
+}
+
 int run_fpn(nuhtc_engine* e, int B, hipStream_t s, bool sem_lateral) {
   // FPN (mmdet/models/necks/fpn.py:152-179): laterals coarse->fine with the nearest-upsampled coarser lateral added in the epilogue
   for (int i = 3; i >= 0; --i) {
     const StageGeom& g = e->st[i];
-    GemmParams p = gp(e->c[i], e->lat_w[i], e->lat_b[i], e->lat[i], B * g.H * g.W, 64, g.C);
-    if (e->out_ln_folded) {      // c[i] = LayerNorm(tok[i]) is never written: the lateral takes the stage's raw tokens and its partials (gemm.hip A_LN)
-      p.A = e->tok[i]; p.W = e->lat_wln[i]; p.bias = e->lat_bln[i];
-      p.amode = A_LN; p.ln_part = e->ln_out[i]; p.ln_nparts = g.C / 96;
-    }
-    if (i < 3) { p.up = e->lat[i + 1]; p.upH = g.H; p.upW = g.W; }
+    const float* parent = i < 3 ? e->lat[i + 1] : nullptr;
+    // with the output norm folded, c[i] = LayerNorm(tok[i]) is never written: the lateral takes the stage's raw tokens and its partials
+    const GemmParams p = e->out_ln_folded ? lateral_params(e->tok[i], e->lat_wln[i], e->lat_bln[i], e->lat[i], B, g.H, g.W, g.C, e->ln_out[i], parent)
+                                          : lateral_params(e->c[i], e->lat_w[i], e->lat_b[i], e->lat[i], B, g.H, g.W, g.C, nullptr, parent);
     RUN(egemm(e, p, s));
   }
   for (int i = 0; i < 4; ++i) {
@@ -1058,7 +1097,7 @@ int nuhtc_get_buffer(nuhtc_engine* e, const char* name, void** ptr, int64_t* sha
     // the pre-processing runs inside the patch embedding: the normalised image is computed now, by preproc_kernel, from the tiles of the last call
     // (which must still be what they were: parity tests read `img` right after the call)
     float mi[6];
-    for (int i = 0; i < 3; ++i) { mi[i] = e->cfg.mean[i]; mi[3 + i] = (float)(1.0 / (double)e->cfg.std[i]); }
+    norm_consts(e->cfg.mean, e->cfg.std, mi);
     HIP_CHECK(e, hipSetDevice(e->device));
     HIP_CHECK(e, hipDeviceSynchronize());
     const int rc = launch_preproc(e->in_tiles, e->img, e->last_batch, e->cfg.tile_h, e->cfg.tile_w, e->Hn, e->Wn, e->Hv, e->Wv, e->rs_xtab, e->rs_ytab, e->in_swap, mi, nullptr);
@@ -1294,6 +1333,121 @@ int nuhtc_op_window_msa(nuhtc_engine* e, const nuhtc_wmsa_args* a, void* stream)
   if (!ok || !sc.ok()) FAIL(e, NUHTC_E_HIP, "window_msa op: scratch upload failed");
   rc = run_attn_front(e, g, w, B, sh, a->x, xw, qkv, a->out, a->out_order == NUHTC_ORDER_TOKEN ? g.map[sh] : g.cidx[sh], nullptr, st, qkv_split, s);
   return op_finish(e, rc, s, "window_msa launch failed", "window_msa kernels failed");
+}
+
+// ---- the front of the path and the small dense kernels, op by op (tests/test_hip_front.py): each entry goes through the host code the engine
+// uses for the same launch (resize_geom, norm_consts, pack_patch_embed, lateral_params + fold_ln, pool_layout)
+int nuhtc_op_patch_embed(nuhtc_engine* e, const uint8_t* tiles_dev, int B, int th, int tw, int valid_h, int valid_w, float scale_factor, int channel_mode,
+                         const float* mean, const float* std, const float* w_host, const float* b_host, const float* ln_g_host, const float* ln_b_host,
+                         float* tok_dev, float* img_dev, void* stream) {
+  if (!e || !tiles_dev || !mean || !std || !w_host || !b_host || !ln_g_host || !ln_b_host || !tok_dev) return NUHTC_E_INVALID;
+  if (B < 1 || th < 1 || tw < 1 || valid_h < 1 || valid_w < 1 || valid_h > th || valid_w > tw) FAIL(e, NUHTC_E_INVALID, "patch_embed op: valid_h / valid_w must lie in [1, tile]");
+  if (channel_mode != NUHTC_CH_AS_IS && channel_mode != NUHTC_CH_SWAP) FAIL(e, NUHTC_E_INVALID, "patch_embed op: unknown channel mode");
+  if (!resize_ok(valid_h, valid_w, scale_factor)) FAIL(e, NUHTC_E_INVALID, "patch_embed op: scale_factor must be in [1,8] and scale_factor * image size must be integers");
+  const ResizeGeom rg = resize_geom(valid_h, valid_w, scale_factor);
+  if ((long long)B * rg.Hn * rg.Wn * 6 >= (1ll << 31)) FAIL(e, NUHTC_E_INVALID, "patch_embed op: size out of range");
+  HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
+  float mi[6];
+  norm_consts(mean, std, mi);
+  DevScratch sc;
+  const int *xtab = sc.upload(rg.tx), *ytab = sc.upload(rg.ty);
+  const float *w = sc.upload(pack_patch_embed(w_host)), *b = sc.upload(b_host, 96), *g = sc.upload(ln_g_host, 96), *beta = sc.upload(ln_b_host, 96);
+  if (!sc.ok()) FAIL(e, NUHTC_E_HIP, "patch_embed op: scratch upload failed");
+  const int swap = channel_mode == NUHTC_CH_SWAP;
+  int rc = launch_patch_embed_tiles(tiles_dev, B, th, tw, rg.Hn, rg.Wn, rg.Hv, rg.Wv, xtab, ytab, swap, mi, w, b, g, beta, tok_dev, s);
+  if (!rc && img_dev) rc = launch_preproc(tiles_dev, img_dev, B, th, tw, rg.Hn, rg.Wn, rg.Hv, rg.Wv, xtab, ytab, swap, mi, s);
+  return op_finish(e, rc, s, "patch_embed launch failed", "patch_embed kernels failed");
+}
+
+int nuhtc_op_layernorm(nuhtc_engine* e, const float* x_dev, const float* g_dev, const float* b_dev, float* y_dev, int rows, int C, void* stream) {
+  if (!e || !x_dev || !g_dev || !b_dev || !y_dev) return NUHTC_E_INVALID;
+  if (rows < 1 || (C != 96 && C != 192 && C != 384 && C != 768) || (long long)rows * C >= (1ll << 31)) FAIL(e, NUHTC_E_INVALID, "layernorm op: rows >= 1, C in {96, 192, 384, 768}");
+  HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = launch_layernorm(x_dev, nullptr, g_dev, b_dev, y_dev, rows, C, s);
+  return op_finish(e, rc, s, "layernorm launch failed", "layernorm kernel failed");
+}
+
+int nuhtc_op_merge_ln(nuhtc_engine* e, const float* x_dev, const float* g_dev, const float* b_dev, float* y_dev, int B, int H, int W, int C, void* stream) {
+  if (!e || !x_dev || !g_dev || !b_dev || !y_dev) return NUHTC_E_INVALID;
+  if (B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1)) FAIL(e, NUHTC_E_INVALID, "merge_ln op: H and W must be even (the network input is a multiple of 32)");
+  if ((C != 96 && C != 192 && C != 384) || (long long)B * H * W * C >= (1ll << 31)) FAIL(e, NUHTC_E_INVALID, "merge_ln op: C in {96, 192, 384}");
+  HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = launch_merge_ln(x_dev, g_dev, b_dev, y_dev, B, H, W, C, s);
+  return op_finish(e, rc, s, "merge_ln launch failed", "merge_ln kernel failed");
+}
+
+int nuhtc_op_fpn_lateral(nuhtc_engine* e, const float* X_dev, int B, int H, int W, int C, const float* W_host, const float* bias_host, const float* ln_g_host,
+                         const float* ln_b_host, const float* parent_dev, float* out_dev, void* stream) {
+  if (!e || !X_dev || !W_host || !bias_host || !out_dev || (ln_g_host == nullptr) != (ln_b_host == nullptr)) return NUHTC_E_INVALID;
+  if (B < 1 || H < 1 || W < 1 || (C != 96 && C != 192 && C != 384 && C != 768) || (long long)B * H * W * C >= (1ll << 31)) FAIL(e, NUHTC_E_INVALID, "fpn_lateral op: size out of range");
+  if (parent_dev && ((H & 1) || (W & 1))) FAIL(e, NUHTC_E_INVALID, "fpn_lateral op: a map with a parent has even sides");
+  HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int T = B * H * W;
+  DevScratch sc;
+  GemmParams p;
+  int rc = 0;
+  if (ln_g_host) {      // the split pipe's form: the stage's output norm folded into the lateral, statistics as the producers' epilogues leave them
+    std::vector<float> wl, bl;
+    fold_ln(W_host, bias_host, ln_g_host, ln_b_host, 64, C, wl, bl);
+    std::vector<unsigned short> split;
+    if ((rc = gemm_make_split(wl.data(), 64, C, split))) FAIL(e, rc, "gemm_make_split failed");
+    float* st = sc.alloc<float>((size_t)T * (C / 96) * 2 * sizeof(float));
+    p = lateral_params(X_dev, sc.upload(wl), sc.upload(bl), out_dev, B, H, W, C, st, parent_dev);
+    p.Wsplit = sc.upload(split);
+    if (!sc.ok()) FAIL(e, NUHTC_E_HIP, "fpn_lateral op: scratch upload failed");
+    rc = launch_ln_stats(X_dev, st, T * (C / 96), 96, s);
+  } else {              // the fp32 pipe's form: the norm ran before (layernorm_kernel), the weight has no split
+    p = lateral_params(X_dev, sc.upload(W_host, (size_t)64 * C), sc.upload(bias_host, 64), out_dev, B, H, W, C, nullptr, parent_dev);
+    if (!sc.ok()) FAIL(e, NUHTC_E_HIP, "fpn_lateral op: scratch upload failed");
+  }
+  if (!rc) rc = launch_gemm(p, s);
+  return op_finish(e, rc, s, "fpn_lateral launch failed", "fpn_lateral kernels failed");
+}
+
+int nuhtc_op_sem_fuse(nuhtc_engine* e, const float* g0, const float* g1, const float* g2, const float* g3, float* out, int B, int H, int W, void* stream) {
+  if (!e || !g0 || !g1 || !g2 || !g3 || !out) return NUHTC_E_INVALID;
+  if (B < 1 || H < 8 || W < 8 || H % 8 || W % 8 || (long long)B * H * W * 64 >= (1ll << 31)) FAIL(e, NUHTC_E_INVALID, "sem_fuse op: H and W must be multiples of 8 (level 0 of a network input that is a multiple of 32)");
+  HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = launch_sem_fuse(g0, g1, g2, g3, out, B, H, W, s);
+  return op_finish(e, rc, s, "sem_fuse launch failed", "sem_fuse kernel failed");
+}
+
+int nuhtc_op_pointwise64(nuhtc_engine* e, const float* x_dev, const float* w_dev, const float* b_dev, float* y_dev, int rows, const int32_t* rows_dev,
+                         int rows_mul, int sigmoid, void* stream) {
+  if (!e || !x_dev || !w_dev || !b_dev || !y_dev) return NUHTC_E_INVALID;
+  if (rows < 1 || (long long)rows * 64 >= (1ll << 31)) FAIL(e, NUHTC_E_INVALID, "pointwise64 op: rows out of range");
+  if (!rows_dev && sigmoid) FAIL(e, NUHTC_E_INVALID, "pointwise64 op: the fixed-row form has no sigmoid");
+  if (rows_dev && rows_mul < 1) FAIL(e, NUHTC_E_INVALID, "pointwise64 op: rows_mul must be >= 1");
+  HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = rows_dev ? launch_conv1x1_n1_dev(x_dev, w_dev, b_dev, y_dev, rows, rows_dev, rows_mul, sigmoid ? 1 : 0, s)
+                          : launch_conv1x1_n1(x_dev, w_dev, b_dev, y_dev, rows, 64, s);
+  return op_finish(e, rc, s, "pointwise64 launch failed", "pointwise64 kernel failed");
+}
+
+int nuhtc_op_fpn_mean_pool(nuhtc_engine* e, const float* const maps[4], const int32_t hw[4], int B, float* feat_dev, void* stream) {
+  if (!e || !maps || !hw || !feat_dev || B < 1) return NUHTC_E_INVALID;
+  PoolLevels p{};
+  int hwi[4];
+  for (int l = 0; l < 4; ++l) {
+    if (!maps[l] || hw[l] < 1 || (long long)B * hw[l] * 64 >= (1ll << 31)) FAIL(e, NUHTC_E_INVALID, "fpn_mean_pool op: null or empty level");
+    hwi[l] = hw[l];
+    p.x[l] = maps[l];
+  }
+  int rc = pool_layout(hwi, p);
+  if (rc) FAIL(e, rc, "pool_chunks: empty FPN level");
+  HIP_CHECK(e, hipSetDevice(e->device));
+  hipStream_t s = (hipStream_t)stream;
+  DevScratch sc;
+  double* slab = sc.alloc<double>(pool_slab_bytes(p, B));
+  if (!sc.ok()) FAIL(e, NUHTC_E_HIP, "fpn_mean_pool op: scratch allocation failed");
+  rc = launch_fpn_mean_pool(p, B, slab, feat_dev, s);
+  return op_finish(e, rc, s, "fpn_mean_pool launch failed", "fpn_mean_pool kernels failed");
 }
 
 #ifdef NUHTC_DEV

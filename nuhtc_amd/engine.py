@@ -688,6 +688,79 @@ class Engine:
         self._check(self.lib.nuhtc_op_window_msa(self.h, ctypes.byref(a), self._stream()))
         return out
 
+    # ------------------------------------------------------------------ the front and the small dense kernels, op by op
+    def op_patch_embed(self, tiles, valid_hw, scale, channel_mode, mean, std, w, b, ln_g, ln_b, want_img=True):
+        """Resize + Normalize + Pad + patch embedding + LayerNorm(96) of device uint8 tiles (B, th, tw, 3) whose image is the top-left
+        valid_hw (nuhtc_op_patch_embed); w (96, 3, 4, 4), b, ln_g, ln_b (96,) anywhere.  -> (tok (B * Hn/4 * Wn/4, 96), img (B, Hn, Wn, 3) or
+        None): the tokens by patch_embed_tiles_kernel, the normalised padded image by preproc_kernel from the same tables."""
+        B, th, tw, _ = tiles.shape
+        h = lambda t: np.ascontiguousarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, dtype=np.float32)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        wh, bh, gh, lbh = h(w), h(b), h(ln_g), h(ln_b)
+        if wh.shape != (96, 3, 4, 4) or bh.shape != (96,) or gh.shape != (96,) or lbh.shape != (96,) or tiles.dtype != torch.uint8:
+            raise ValueError('op_patch_embed: uint8 tiles, w (96, 3, 4, 4), b / ln_g / ln_b (96,)')
+        Hv, Wv = int(valid_hw[0] * float(scale) + 0.5), int(valid_hw[1] * float(scale) + 0.5)
+        Hn, Wn = -(-Hv // 32) * 32, -(-Wv // 32) * 32
+        tok = torch.empty(B * (Hn // 4) * (Wn // 4), 96, dtype=torch.float32, device=self.device)
+        img = torch.empty(B, Hn, Wn, 3, dtype=torch.float32, device=self.device) if want_img else None
+        f3 = lambda v: (ctypes.c_float * 3)(*[float(x) for x in v])
+        self._check(self.lib.nuhtc_op_patch_embed(self.h, tiles.data_ptr(), B, th, tw, int(valid_hw[0]), int(valid_hw[1]), float(scale), int(channel_mode),
+                                                  f3(mean), f3(std), vp(wh), vp(bh), vp(gh), vp(lbh), tok.data_ptr(),
+                                                  img.data_ptr() if img is not None else None, self._stream()))
+        return tok, img
+
+    def op_layernorm(self, x, g, b, out=None):
+        """LayerNorm (eps 1e-5) of the rows of x (rows, C) by the plain kernels of csrc/swin.hip (nuhtc_op_layernorm); all on the device."""
+        rows, C = x.shape
+        if out is None:
+            out = torch.empty_like(x)
+        self._check(self.lib.nuhtc_op_layernorm(self.h, x.data_ptr(), g.data_ptr(), b.data_ptr(), out.data_ptr(), rows, C, self._stream()))
+        return out
+
+    def op_merge_ln(self, x, g, b, out=None):
+        """PatchMerging's gather + LayerNorm(4C) (merge_ln_kernel): x (B, H, W, C), g / b (4C,) in the kernel's order k = (kh*2+kw)*C + c, all
+        on the device.  -> (B * H/2 * W/2, 4C)."""
+        B, H, W, C = x.shape
+        if out is None:
+            out = torch.empty(B * (H // 2) * (W // 2), 4 * C, dtype=torch.float32, device=self.device)
+        self._check(self.lib.nuhtc_op_merge_ln(self.h, x.data_ptr(), g.data_ptr(), b.data_ptr(), out.data_ptr(), B, H, W, C, self._stream()))
+        return out
+
+    def op_fpn_lateral(self, x, w, bias, ln_g=None, ln_b=None, parent=None):
+        """An FPN lateral as run_fpn launches it (nuhtc_op_fpn_lateral): x (B, H, W, C) on the device, w (64, C), bias (64,), ln_g / ln_b (C,)
+        anywhere (None: no norm, the fp32 pipe's form), parent (B, H/2, W/2, 64) on the device or None.  -> (B, H, W, 64)."""
+        B, H, W, C = x.shape
+        h = lambda t: np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32) if t is not None else None
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+        wh, bh, gh, lbh = h(w), h(bias), h(ln_g), h(ln_b)
+        out = torch.empty(B, H, W, 64, dtype=torch.float32, device=self.device)
+        self._check(self.lib.nuhtc_op_fpn_lateral(self.h, x.data_ptr(), B, H, W, C, vp(wh), vp(bh), vp(gh), vp(lbh),
+                                                  parent.data_ptr() if parent is not None else None, out.data_ptr(), self._stream()))
+        return out
+
+    def op_sem_fuse(self, g0, g1, g2, g3):
+        """relu(g0) + sum of relu(align-corners bilinear upsampling of g1..g3) (sem_fuse_kernel); g_i (B, H >> i, W >> i, 64) on the device."""
+        B, H, W, _ = g0.shape
+        out = torch.empty_like(g0)
+        self._check(self.lib.nuhtc_op_sem_fuse(self.h, g0.data_ptr(), g1.data_ptr(), g2.data_ptr(), g3.data_ptr(), out.data_ptr(), B, H, W, self._stream()))
+        return out
+
+    def op_pointwise64(self, x, w, b, out, rows_dev=None, rows_mul=1, sigmoid=False):
+        """out[row] = w . x[row] + b over the rows of x (rows, 64) (conv1x1_n1_kernel), all on the device; rows_dev (device int32 (1,)) selects the
+        grid-strided form limited to min(rows, rows_dev * rows_mul) rows, with a sigmoid on request.  Writes into `out` (rows,)."""
+        self._check(self.lib.nuhtc_op_pointwise64(self.h, x.data_ptr(), w.data_ptr(), b.data_ptr(), out.data_ptr(), x.shape[0],
+                                                  rows_dev.data_ptr() if rows_dev is not None else None, int(rows_mul), int(bool(sigmoid)), self._stream()))
+        return out
+
+    def op_fpn_mean_pool(self, maps):
+        """Per-channel means of four maps (B, hw_l, 64) on the device -> (B, 256), level-major (the pooling of nuhtc_features, csrc/pool.hip)."""
+        B = maps[0].shape[0]
+        ptrs = (ctypes.c_void_p * 4)(*[m.data_ptr() for m in maps])
+        hw = (ctypes.c_int32 * 4)(*[int(m.shape[1]) for m in maps])
+        feat = torch.empty(B, 256, dtype=torch.float32, device=self.device)
+        self._check(self.lib.nuhtc_op_fpn_mean_pool(self.h, ptrs, hw, B, feat.data_ptr(), self._stream()))
+        return feat
+
     # ------------------------------------------------------------------ the detection tail, op by op (csrc/roi.hip)
     def _i32(self, v):
         return v if isinstance(v, torch.Tensor) else torch.tensor(np.atleast_1d(np.asarray(v)), dtype=torch.int32, device=self.device)

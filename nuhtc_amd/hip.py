@@ -156,7 +156,9 @@ EXPORTS = ['nuhtc_default_config', 'nuhtc_create', 'nuhtc_destroy', 'nuhtc_last_
            'nuhtc_stitch_gather', 'nuhtc_stitch_pairs', 'nuhtc_stitch_render', 'nuhtc_op_stitch_gather', 'nuhtc_op_stitch_pairs', 'nuhtc_op_stitch_render',
            'nuhtc_tissue_mask', 'nuhtc_points_polygon_test', 'nuhtc_grid_in_contour', 'nuhtc_rle_encode',
            'nuhtc_nucleus_features', 'nuhtc_op_nucleus_pool', 'nuhtc_cell_graph', 'nuhtc_nucleus_morph', 'nuhtc_op_nucleus_morph',
-           'nuhtc_nucleus_texture', 'nuhtc_op_nucleus_texture']
+           'nuhtc_nucleus_texture', 'nuhtc_op_nucleus_texture',
+           'nuhtc_op_patch_embed', 'nuhtc_op_layernorm', 'nuhtc_op_merge_ln', 'nuhtc_op_fpn_lateral', 'nuhtc_op_sem_fuse', 'nuhtc_op_pointwise64',
+           'nuhtc_op_fpn_mean_pool']
 
 _lib = None
 
@@ -202,6 +204,14 @@ def load():
     lib.nuhtc_op_cc_proposals.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.nuhtc_op_conv3.argtypes = [vp, ctypes.POINTER(Conv3Args), vp]
     lib.nuhtc_op_window_msa.argtypes = [vp, ctypes.POINTER(WmsaArgs), vp]
+    f3 = ctypes.POINTER(cf)
+    lib.nuhtc_op_patch_embed.argtypes = [vp, vp, ci, ci, ci, ci, ci, cf, ci, f3, f3, vp, vp, vp, vp, vp, vp, vp]
+    lib.nuhtc_op_layernorm.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp]
+    lib.nuhtc_op_merge_ln.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
+    lib.nuhtc_op_fpn_lateral.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+    lib.nuhtc_op_sem_fuse.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]
+    lib.nuhtc_op_pointwise64.argtypes = [vp, vp, vp, vp, vp, ci, vp, ci, ci, vp]
+    lib.nuhtc_op_fpn_mean_pool.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int32), ci, vp, vp]
     lib.nuhtc_op_bbox_tail.argtypes = [vp, ctypes.POINTER(BboxTailArgs), vp]
     lib.nuhtc_op_det_post.argtypes = [vp, ctypes.POINTER(DetPostArgs), vp]
     lib.nuhtc_op_paste.argtypes = [vp, ctypes.POINTER(PasteArgs), vp]
