@@ -20,19 +20,16 @@
 // about 100 + 36 + 9 + 4 cells = 37 KB of map rows, all L2 hits behind the inference that wrote them.
 #include <climits>
 
-#include "engine.h"
 #include "maskbits.h"
+#include "nucleus_list.h"
 
 namespace {
 
 struct NucPoolParams {
   const float* x[4];       // level maps [B][Hl][Wl][64]
   int Hl[4], Wl[4], stride[4];
-  const uint32_t* masks;   // [B][K][H][wpr], bit x & 31 of word x >> 5
-  const int64_t* idx;      // entry d = tile * K + slot (idx_dev of nuhtc_export_kept) ...
-  const int32_t* pairs;    // ... or, when idx is null, (tile, slot) at pairs[2 d]
-  const int32_t* n_dev;    // entries = min(*n_dev, n_max); null: n_max
-  int n_max, B, K, H, wpr;
+  NucleusList list;
+  NucleusMasks m;          // the padding bits of a row's last word are zero: W is not read
   float* out;              // [n_max][256]
 };
 
@@ -49,21 +46,20 @@ __device__ __forceinline__ int row_popc(const uint32_t* __restrict__ row, int cx
 
 __global__ __launch_bounds__(256) void nucleus_pool_kernel(NucPoolParams p) {
   __shared__ int red[4][5];
-  const int d = blockIdx.x;
-  const int n = p.n_dev ? min(*p.n_dev, p.n_max) : p.n_max;
-  if (d >= n) return;                                   // rows past the count are not written
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int d = blockIdx.x, H = p.m.H, wpr = p.m.wpr;
   long long b, r;
-  if (p.idx) { const long long i = p.idx[d]; b = i / p.K; r = i - b * p.K; }
-  else { b = p.pairs[2 * d]; r = p.pairs[2 * d + 1]; }
+  const NucleusEntry at = nucleus_entry(p.list, d, b, r);
+  if (at == NUCLEUS_PAST) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float* __restrict__ dst = p.out + (long long)d * 256 + tid;
-  if (b < 0 || b >= p.B || r < 0 || r >= p.K) { *dst = 0.f; return; }          // an entry outside the batch: a zero row, nothing read
-  const uint32_t* __restrict__ m = p.masks + (b * p.K + r) * (long long)p.H * p.wpr;
+  const auto zero_row = [&] { *dst = 0.f; };
+  if (at == NUCLEUS_OUTSIDE) { zero_row(); return; }
+  const uint32_t* __restrict__ m = nucleus_mask(p.m, p.list.K, b, r);
 
   // ---- bounding rectangle and area of the mask (maskbits.h)
-  const MaskRect rc = block_mask_rect_256(m, p.H, p.wpr, ~0u, red);
+  const MaskRect rc = block_mask_rect_256(m, H, wpr, ~0u, red);
   const int y0 = rc.y0, y1 = rc.y1, x0 = rc.x0, x1 = rc.x1, area = rc.area;
-  if (area == 0) { *dst = 0.f; return; }
+  if (area == 0) { zero_row(); return; }
 
   // ---- wave = level, lane = channel
   const int s = p.stride[wave], Hl = p.Hl[wave], Wl = p.Wl[wave];
@@ -71,12 +67,12 @@ __global__ __launch_bounds__(256) void nucleus_pool_kernel(NucPoolParams p) {
   const int i0 = y0 / s, i1 = min(y1 / s, Hl - 1), j0 = x0 / s, j1 = min(x1 / s, Wl - 1);
   float acc = 0.f;
   for (int i = i0; i <= i1; ++i) {
-    const int ry0 = i * s, ry1 = min(ry0 + s, p.H);
+    const int ry0 = i * s, ry1 = min(ry0 + s, H);
     for (int jb = j0; jb <= j1; jb += 64) {
       int wgt = 0;                                       // lane t: the weight of cell (i, jb + t)
       if (jb + lane <= j1) {
-        const int cx0 = (jb + lane) * s, cx1 = min(cx0 + s, p.wpr * 32);
-        for (int y = ry0; y < ry1; ++y) wgt += row_popc(m + (long long)y * p.wpr, cx0, cx1);
+        const int cx0 = (jb + lane) * s, cx1 = min(cx0 + s, wpr * 32);
+        for (int y = ry0; y < ry1; ++y) wgt += row_popc(m + (long long)y * wpr, cx0, cx1);
       }
       const int cnt = min(64, j1 - jb + 1);
       const float* __restrict__ row = xl + ((long long)i * Wl + jb) * 64;
@@ -99,10 +95,10 @@ __global__ __launch_bounds__(256) void nucleus_pool_kernel(NucPoolParams p) {
 }
 
 int launch_nucleus_pool(const NucPoolParams& p, hipStream_t s) {
-  if (p.n_max < 1) return 0;
+  if (p.list.n_max < 1) return 0;
   // the bytes of a batch depend on its masks: the profile records the time alone
   ProfScope ps("nucleus_pool", 0, 0, s);
-  hipLaunchKernelGGL(nucleus_pool_kernel, dim3((unsigned)p.n_max), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(nucleus_pool_kernel, dim3((unsigned)p.list.n_max), dim3(256), 0, s, p);
   return launched() ? 0 : NUHTC_E_HIP;
 }
 
@@ -112,21 +108,16 @@ extern "C" {
 
 int nuhtc_nucleus_features(nuhtc_engine* e, const nuhtc_dets* dets, int B, const int64_t* idx_dev, const int32_t* n_dev, int cap, float* feat_dev,
                            void* stream) {
-  if (!e) return NUHTC_E_INVALID;
-  if (!e->finalized) FAIL(e, NUHTC_E_STATE, "nuhtc_nucleus_features before nuhtc_finalize");
-  if (e->cfg.features_only) FAIL(e, NUHTC_E_STATE, "this engine was created with features_only = 1: it has no detections to pool under");
-  if (!dets || !dets->masks || !idx_dev || !n_dev || !feat_dev || B < 1 || B > e->cfg.max_batch || cap < 1)
-    FAIL(e, NUHTC_E_INVALID, "bad nuhtc_nucleus_features arguments");
-  const nuhtc_config& c = e->cfg;
   NucPoolParams p{};
+  if (const int rc = nucleus_engine_route(e, "nuhtc_nucleus_features", "pool under", dets, B, idx_dev, n_dev, cap, feat_dev && B >= 1 && cap >= 1, p.list, p.m)) return rc;
+  const nuhtc_config& c = e->cfg;
   const int sf = (int)c.scale_factor;
   for (int l = 0; l < 4; ++l) {
     // a map cell of stride 4 << l in network pixels covers (4 << l) / scale_factor mask pixels: whole pixels for scale factors 1, 2 and 4
     if ((float)sf != c.scale_factor || sf < 1 || (4 << l) % sf) FAIL(e, NUHTC_E_INVALID, "nuhtc_nucleus_features: scale_factor must be 1, 2 or 4 (whole mask pixels per map cell)");
     p.x[l] = e->x[l]; p.Hl[l] = e->st[l].H; p.Wl[l] = e->st[l].W; p.stride[l] = (4 << l) / sf;
   }
-  p.masks = dets->masks; p.idx = idx_dev; p.n_dev = n_dev; p.n_max = cap;
-  p.B = B; p.K = c.max_per_img; p.H = c.tile_h; p.wpr = c.tile_w / 32; p.out = feat_dev;
+  p.out = feat_dev;
   HIP_CHECK(e, hipSetDevice(e->device));
   const int rc = launch_nucleus_pool(p, (hipStream_t)stream);
   if (rc) FAIL(e, rc, "nucleus_pool launch failed");
@@ -144,8 +135,8 @@ int nuhtc_op_nucleus_pool(nuhtc_engine* e, const float* const maps[4], const int
       FAIL(e, NUHTC_E_INVALID, "nucleus_pool op: a level map is missing or does not cover the H x W image at its stride");
     p.x[l] = maps[l]; p.Hl[l] = h[l]; p.Wl[l] = w[l]; p.stride[l] = strides[l];
   }
-  p.masks = masks; p.pairs = pairs_dev; p.n_dev = n_dev; p.n_max = n_max;
-  p.B = B; p.K = K; p.H = H; p.wpr = (W + 31) / 32; p.out = out;
+  nucleus_op_route(B, masks, K, H, W, pairs_dev, n_dev, n_max, p.list, p.m);
+  p.out = out;
   HIP_CHECK(e, hipSetDevice(e->device));
   hipStream_t s = (hipStream_t)stream;
   return op_finish(e, launch_nucleus_pool(p, s), s, "nucleus_pool launch failed", "nucleus_pool kernel failed");

@@ -21,9 +21,8 @@
 //   6. 16 int64 and 256 int32 per nucleus leave with ordinary vector stores.
 // LDS: 2 x 8 KB bands, 4 KB row extents, 2 KB histogram and table: 22.3 KB a workgroup.  The padding bits of a row's last word are
 // masked off on every read, so no tile pixel at x >= W is ever addressed.
-#include "engine.h"
-#include "haematoxylin.h"
 #include "maskbits.h"
+#include "nucleus_list.h"
 #include "nucmorph_host.h"
 
 namespace {
@@ -35,14 +34,9 @@ constexpr unsigned long long CODES_3 = (1ull << 13) | (1ull << 23);
 static_assert(MW >= NUCMORPH_MAX_SIDE + 1 && MW / (NUCMORPH_MAX_SIDE / 32 + 2) >= 5, "a band holds a hull stack and five rows of any rectangle");
 
 struct NucMorphParams {
-  const uint8_t* tiles;    // [B][H][pitch][3]
-  const uint32_t* masks;   // [B][K][H][wpr], bit x & 31 of word x >> 5
-  const int64_t* idx;      // entry d = tile * K + slot (idx_dev of nuhtc_export_kept) ...
-  const int32_t* pairs;    // ... or, when idx is null, (tile, slot) at pairs[2 d]
-  const int32_t* n_dev;    // entries = min(*n_dev, n_max); null: n_max
-  const int32_t* lut;      // [256]
-  int kb[3];               // the coefficient of byte 0, 1, 2 of a pixel (channel_mode resolved on the host)
-  int n_max, B, K, H, W, wpr, pitch;
+  NucleusList list;
+  NucleusMasks m;
+  NucleusTiles t;
   int64_t* raw;            // [n_max][16]
   int32_t* hist;           // [n_max][256]
 };
@@ -54,36 +48,30 @@ __global__ __launch_bounds__(256) void nucleus_morph_kernel(NucMorphParams p) {
   __shared__ long long redl[4][5];
   __shared__ int redi[4][4];
   __shared__ long long side[2];
-  const int d = blockIdx.x;
-  const int n = p.n_dev ? min(*p.n_dev, p.n_max) : p.n_max;
-  if (d >= n) return;                                   // rows past the count are not written
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int d = blockIdx.x, H = p.m.H, wpr = p.m.wpr;
   long long b, r;
-  if (p.idx) { const long long i = p.idx[d]; b = i / p.K; r = i - b * p.K; }
-  else { b = p.pairs[2 * d]; r = p.pairs[2 * d + 1]; }
+  const NucleusEntry at = nucleus_entry(p.list, d, b, r);
+  if (at == NUCLEUS_PAST) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int64_t* __restrict__ raw = p.raw + (long long)d * NUCMORPH_RAW;
   int32_t* __restrict__ hout = p.hist + (long long)d * NUCMORPH_BINS;
-  if (b < 0 || b >= p.B || r < 0 || r >= p.K) {         // an entry outside the batch: a zero row, nothing read
+  const auto zero_row = [&] {
     if (tid < NUCMORPH_RAW) raw[tid] = 0;
     hout[tid] = 0;
-    return;
-  }
-  const uint32_t* __restrict__ m = p.masks + (b * p.K + r) * (long long)p.H * p.wpr;
-  const uint8_t* __restrict__ tile = p.tiles + b * (long long)p.H * p.pitch * 3;
-  const unsigned last = (p.W & 31) ? (1u << (p.W & 31)) - 1u : ~0u;
+  };
+  if (at == NUCLEUS_OUTSIDE) { zero_row(); return; }
+  const uint32_t* __restrict__ m = nucleus_mask(p.m, p.list.K, b, r);
+  const uint8_t* __restrict__ tile = nucleus_tile(p.t, H, b);
+  const unsigned last = nucleus_last_word(p.m);
 
-  const MaskRect rc = block_mask_rect_256(m, p.H, p.wpr, last, red);
-  if (rc.area == 0) {
-    if (tid < NUCMORPH_RAW) raw[tid] = 0;
-    hout[tid] = 0;
-    return;
-  }
+  const MaskRect rc = block_mask_rect_256(m, H, wpr, last, red);
+  if (rc.area == 0) { zero_row(); return; }
   hist[tid] = 0;
-  lut[tid] = p.lut[tid];
+  lut[tid] = p.t.lut[tid];
   const int x0 = rc.x0, y0 = rc.y0, x1 = rc.x1, y1 = rc.y1;                 // inclusive
   const int wx0 = x0 >> 5, nw = (x1 >> 5) - wx0 + 1, pitch = nw + 2;       // staged words of a row: one margin word on either side
   const int band = MW / pitch - 4;                                          // rows of codes per band
-  const long long kb0 = p.kb[0], kb1 = p.kb[1], kb2 = p.kb[2];
+  const long long kb0 = p.t.kb[0], kb1 = p.t.kb[1], kb2 = p.t.kb[2];
   long long sx = 0, sy = 0, sxx = 0, syy = 0, sxy = 0;
   int E = 0, n1 = 0, n2 = 0, n3 = 0;
   for (int yb = y0; yb <= y1; yb += band) {
@@ -92,9 +80,9 @@ __global__ __launch_bounds__(256) void nucleus_morph_kernel(NucMorphParams p) {
     for (int i = tid; i < rows * pitch; i += 256) {
       const int rr = i / pitch, c = i - rr * pitch, y = yb - 2 + rr, w = wx0 - 1 + c;
       unsigned v = 0;
-      if (y >= 0 && y < p.H && c >= 1 && c <= nw) {
-        v = m[y * p.wpr + w];
-        if (w == p.wpr - 1) v &= last;
+      if (y >= 0 && y < H && c >= 1 && c <= nw) {
+        v = m[y * wpr + w];
+        if (w == wpr - 1) v &= last;
       }
       Ms[i] = v;
       Bs[i] = 0;
@@ -111,7 +99,7 @@ __global__ __launch_bounds__(256) void nucleus_morph_kernel(NucMorphParams p) {
       if (rr < 2 || rr >= rows - 2) continue;
       const int y = yb - 2 + rr, xb = (wx0 + c - 1) * 32;
       E += __popc(v & ~up) + __popc(v & ~dn) + __popc(v & ~lf) + __popc(v & ~rt);
-      const uint8_t* __restrict__ px = tile + ((long long)y * p.pitch + xb) * 3;
+      const uint8_t* __restrict__ px = tile + ((long long)y * p.t.pitch + xb) * 3;
       int s1 = 0, s2 = 0;
       for (unsigned bits = v; bits; bits &= bits - 1) {
         const int bit = __ffs(bits) - 1, x = xb + bit;
@@ -181,7 +169,7 @@ __global__ __launch_bounds__(256) void nucleus_morph_kernel(NucMorphParams p) {
 int launch_nucleus_morph(const NucMorphParams& p, hipStream_t s) {
   // the bytes of a batch depend on its masks: the profile records the time alone
   ProfScope ps("nucleus_morph", 0, 0, s);
-  hipLaunchKernelGGL(nucleus_morph_kernel, dim3((unsigned)p.n_max), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(nucleus_morph_kernel, dim3((unsigned)p.list.n_max), dim3(256), 0, s, p);
   return launched() ? 0 : NUHTC_E_HIP;
 }
 
@@ -191,17 +179,10 @@ extern "C" {
 
 int nuhtc_nucleus_morph(nuhtc_engine* e, const nuhtc_dets* dets, int B, const uint8_t* tiles_dev, int channel_mode, const int32_t* lut_dev,
                         const int32_t k[3], const int64_t* idx_dev, const int32_t* n_dev, int cap, int64_t* raw_dev, int32_t* hist_dev, void* stream) {
-  if (!e) return NUHTC_E_INVALID;
-  if (!e->finalized) FAIL(e, NUHTC_E_STATE, "nuhtc_nucleus_morph before nuhtc_finalize");
-  if (e->cfg.features_only) FAIL(e, NUHTC_E_STATE, "this engine was created with features_only = 1: it has no detections to measure");
-  if (!dets || !dets->masks || !tiles_dev || !lut_dev || !k || !idx_dev || !n_dev || !raw_dev || !hist_dev || B > e->cfg.max_batch)
-    FAIL(e, NUHTC_E_INVALID, "bad nuhtc_nucleus_morph arguments");
-  const nuhtc_config& c = e->cfg;
-  if (const char* why = nucmorph_args_error(B, c.max_per_img, c.tile_h, c.tile_w, c.tile_w, cap, channel_mode)) FAIL(e, NUHTC_E_INVALID, why);
   NucMorphParams p{};
-  p.tiles = tiles_dev; p.masks = dets->masks; p.idx = idx_dev; p.n_dev = n_dev; p.lut = lut_dev; p.n_max = cap;
-  p.B = B; p.K = c.max_per_img; p.H = c.tile_h; p.W = c.tile_w; p.wpr = c.tile_w / 32; p.pitch = c.tile_w; p.raw = raw_dev; p.hist = hist_dev;
-  haematoxylin_byte_coefficients(p.kb, k, channel_mode);
+  if (const int rc = nucleus_engine_route(e, "nuhtc_nucleus_morph", "measure", dets, B, idx_dev, n_dev, cap, tiles_dev && lut_dev && k && raw_dev && hist_dev, p.list, p.m)) return rc;
+  if (const int rc = nucleus_tiles_args(e, "nucleus_morph", p.list, p.m, tiles_dev, channel_mode, lut_dev, k, p.t)) return rc;
+  p.raw = raw_dev; p.hist = hist_dev;
   HIP_CHECK(e, hipSetDevice(e->device));
   const int rc = launch_nucleus_morph(p, (hipStream_t)stream);
   if (rc) FAIL(e, rc, "nucleus_morph launch failed");
@@ -212,11 +193,10 @@ int nuhtc_op_nucleus_morph(nuhtc_engine* e, const uint8_t* tiles, int channel_mo
                            const uint32_t* masks, int K, int H, int W, const int32_t* pairs_dev, const int32_t* n_dev, int n_max,
                            int64_t* raw, int32_t* hist, void* stream) {
   if (!e || !tiles || !lut_dev || !k || !masks || !pairs_dev || !raw || !hist) return NUHTC_E_INVALID;
-  if (const char* why = nucmorph_args_error(B, K, H, W, W, n_max, channel_mode)) FAIL(e, NUHTC_E_INVALID, why);
   NucMorphParams p{};
-  p.tiles = tiles; p.masks = masks; p.pairs = pairs_dev; p.n_dev = n_dev; p.lut = lut_dev; p.n_max = n_max;
-  p.B = B; p.K = K; p.H = H; p.W = W; p.wpr = (W + 31) / 32; p.pitch = W; p.raw = raw; p.hist = hist;
-  haematoxylin_byte_coefficients(p.kb, k, channel_mode);
+  nucleus_op_route(B, masks, K, H, W, pairs_dev, n_dev, n_max, p.list, p.m);
+  if (const int rc = nucleus_tiles_args(e, "nucleus_morph", p.list, p.m, tiles, channel_mode, lut_dev, k, p.t)) return rc;
+  p.raw = raw; p.hist = hist;
   HIP_CHECK(e, hipSetDevice(e->device));
   hipStream_t s = (hipStream_t)stream;
   return op_finish(e, launch_nucleus_morph(p, s), s, "nucleus_morph launch failed", "nucleus_morph kernel failed");

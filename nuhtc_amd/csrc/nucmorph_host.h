@@ -1,8 +1,10 @@
-// The parts of the per-nucleus morphometry (nucmorph.hip) that are plain C++ and run on the host as well: the limits of the entry points
-// and one side of the convex hull.  Header-only and free of HIP calls, so a host program can exercise them under a sanitizer
-// (tools/dev/nucmorph_host_check.cpp); the kernel calls the same hull_chain2.
+// The part of the per-nucleus morphometry (nucmorph.hip) that is plain C++ and runs on the host as well: one side of the convex hull
+// (the limits of the entry points are nucleus_sizes_error of nucleus_list.h).  Header-only, so a host program can exercise it under a
+// sanitizer (tools/dev/nucmorph_host_check.cpp); the kernel calls the same hull_chain2.
 #pragma once
 #include <cstdint>
+
+#include "nucleus_list.h"
 
 #if defined(__HIPCC__)
 #define NUCMORPH_HD __host__ __device__
@@ -10,18 +12,8 @@
 #define NUCMORPH_HD
 #endif
 
-enum { NUCMORPH_MAX_SIDE = 1024, NUCMORPH_RAW = 16, NUCMORPH_BINS = 256 };
+enum { NUCMORPH_MAX_SIDE = NUCLEUS_MAX_SIDE, NUCMORPH_RAW = 16, NUCMORPH_BINS = 256 };
 constexpr uint32_t NUCMORPH_EMPTY_ROW = 0xffffffffu;
-
-// what is wrong with the sizes of a morphometry call, or null.  The frame side is bounded by the per-row extents the kernel keeps
-// (NUCMORPH_MAX_SIDE entries, 16 bits a coordinate); pitch = pixels per tile row (>= W).
-inline const char* nucmorph_args_error(int B, int K, int H, int W, int pitch, int n_max, int channel_mode) {
-  if (B < 1 || B > 4096 || K < 1 || K > 65536) return "nucleus_morph: B 1..4096, K 1..65536";
-  if (H < 1 || H > NUCMORPH_MAX_SIDE || W < 1 || W > NUCMORPH_MAX_SIDE || pitch < W || pitch > NUCMORPH_MAX_SIDE) return "nucleus_morph: H and W 1..1024, row pitch W..1024";
-  if (n_max < 1 || n_max > (1 << 24)) return "nucleus_morph: n_max 1..2^24";
-  if (channel_mode != 0 && channel_mode != 1) return "nucleus_morph: channel_mode is NUHTC_CH_AS_IS or NUHTC_CH_SWAP";
-  return nullptr;
-}
 
 // One side of the convex hull of the pixel corners of a mask, as twice the integral over Y of that side's x: ext[i] = l | r << 16, the
 // leftmost and rightmost set pixel of pixel row i of the bounding rectangle (NUCMORPH_EMPTY_ROW: none), rows >= 1 of them.  Lattice row

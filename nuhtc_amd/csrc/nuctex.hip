@@ -18,22 +18,16 @@
 //   5. the four copies are summed and leave with ordinary vector stores.
 // Integer adds in any grouping give the same bits: a row is bitwise repeatable across runs and batch splits.
 // LDS: 4 x 272 counters, the table, the rectangle scan's 20 ints: 5.4 KB a workgroup.
-#include "engine.h"
-#include "haematoxylin.h"
 #include "maskbits.h"
+#include "nucleus_list.h"
 #include "nuctex_host.h"
 
 namespace {
 
 struct NucTexParams {
-  const uint8_t* tiles;    // [B][H][pitch][3]
-  const uint32_t* masks;   // [B][K][H][wpr], bit x & 31 of word x >> 5
-  const int64_t* idx;      // entry d = tile * K + slot (idx_dev of nuhtc_export_kept) ...
-  const int32_t* pairs;    // ... or, when idx is null, (tile, slot) at pairs[2 d]
-  const int32_t* n_dev;    // entries = min(*n_dev, n_max); null: n_max
-  const int32_t* lut;      // [256]
-  int kb[3];               // the coefficient of byte 0, 1, 2 of a pixel (channel_mode resolved on the host)
-  int n_max, B, K, H, W, wpr, pitch;
+  NucleusList list;
+  NucleusMasks m;
+  NucleusTiles t;
   int32_t* tex;            // [n_max][2][136]
 };
 
@@ -55,46 +49,41 @@ __global__ __launch_bounds__(256) void nucleus_texture_kernel(NucTexParams p) {
   __shared__ int cnt[4][NUCTEX_ROW];
   __shared__ int lut[256];
   __shared__ int red[4][5];
-  const int d = blockIdx.x;
-  const int n = p.n_dev ? min(*p.n_dev, p.n_max) : p.n_max;
-  if (d >= n) return;                                   // rows past the count are not written
-  const int tid = threadIdx.x, wave = tid >> 6;
+  const int d = blockIdx.x, H = p.m.H, wpr = p.m.wpr;
   long long b, r;
-  if (p.idx) { const long long i = p.idx[d]; b = i / p.K; r = i - b * p.K; }
-  else { b = p.pairs[2 * d]; r = p.pairs[2 * d + 1]; }
+  const NucleusEntry at = nucleus_entry(p.list, d, b, r);
+  if (at == NUCLEUS_PAST) return;
+  const int tid = threadIdx.x, wave = tid >> 6;
   int32_t* __restrict__ out = p.tex + (long long)d * NUCTEX_ROW;
-  if (b < 0 || b >= p.B || r < 0 || r >= p.K) {         // an entry outside the batch: a zero row, nothing read
+  const auto zero_row = [&] {
     for (int i = tid; i < NUCTEX_ROW; i += 256) out[i] = 0;
-    return;
-  }
-  const uint32_t* __restrict__ m = p.masks + (b * p.K + r) * (long long)p.H * p.wpr;
-  const uint8_t* __restrict__ tile = p.tiles + b * (long long)p.H * p.pitch * 3;
-  const unsigned last = (p.W & 31) ? (1u << (p.W & 31)) - 1u : ~0u;
+  };
+  if (at == NUCLEUS_OUTSIDE) { zero_row(); return; }
+  const uint32_t* __restrict__ m = nucleus_mask(p.m, p.list.K, b, r);
+  const uint8_t* __restrict__ tile = nucleus_tile(p.t, H, b);
+  const unsigned last = nucleus_last_word(p.m);
 
-  const MaskRect rc = block_mask_rect_256(m, p.H, p.wpr, last, red);
-  if (rc.area < 2) {                                    // no pixel, or one: no pair
-    for (int i = tid; i < NUCTEX_ROW; i += 256) out[i] = 0;
-    return;
-  }
+  const MaskRect rc = block_mask_rect_256(m, H, wpr, last, red);
+  if (rc.area < 2) { zero_row(); return; }              // no pixel, or one: no pair
   for (int i = tid; i < 4 * NUCTEX_ROW; i += 256) (&cnt[0][0])[i] = 0;
-  lut[tid] = p.lut[tid];
+  lut[tid] = p.t.lut[tid];
   __syncthreads();
   int* __restrict__ mine = cnt[wave];
   const int wx0 = rc.x0 >> 5, nw = (rc.x1 >> 5) - wx0 + 1, rows = rc.y1 - rc.y0 + 1;
-  const long long kb0 = p.kb[0], kb1 = p.kb[1], kb2 = p.kb[2];
-  const long long below = (long long)p.pitch * 3;
+  const long long kb0 = p.t.kb[0], kb1 = p.t.kb[1], kb2 = p.t.kb[2];
+  const long long below = (long long)p.t.pitch * 3;
   PendingCell right{0, 0}, down{0, 0};
   for (int i = tid; i < rows * nw; i += 256) {
     const int rr = i / nw, w = wx0 + i - rr * nw, y = rc.y0 + rr;
-    const uint32_t* q = m + y * p.wpr + w;
+    const uint32_t* q = m + y * wpr + w;
     unsigned v = q[0];
-    if (w == p.wpr - 1) v &= last;
+    if (w == wpr - 1) v &= last;
     if (!v) continue;
     unsigned nx = 0, dn = 0;
-    if (w + 1 < p.wpr) { nx = q[1]; if (w + 1 == p.wpr - 1) nx &= last; }
-    if (y + 1 < p.H) { dn = q[p.wpr]; if (w == p.wpr - 1) dn &= last; }
+    if (w + 1 < wpr) { nx = q[1]; if (w + 1 == wpr - 1) nx &= last; }
+    if (y + 1 < H) { dn = q[wpr]; if (w == wpr - 1) dn &= last; }
     const unsigned R = v & ((v >> 1) | (nx << 31)), D = v & dn;
-    const uint8_t* __restrict__ px = tile + ((long long)y * p.pitch + w * 32) * 3;
+    const uint8_t* __restrict__ px = tile + ((long long)y * p.t.pitch + w * 32) * 3;
     int prev = 0;                                       // the level of pixel bit - 1 whenever that pixel is in R
     for (unsigned bits = R | (R << 1) | D; bits; bits &= bits - 1) {        // every pixel of this word that is in a pair of this word
       const int bit = __ffs(bits) - 1;
@@ -115,7 +104,7 @@ __global__ __launch_bounds__(256) void nucleus_texture_kernel(NucTexParams p) {
 int launch_nucleus_texture(const NucTexParams& p, hipStream_t s) {
   // the bytes of a batch depend on its masks: the profile records the time alone
   ProfScope ps("nucleus_texture", 0, 0, s);
-  hipLaunchKernelGGL(nucleus_texture_kernel, dim3((unsigned)p.n_max), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(nucleus_texture_kernel, dim3((unsigned)p.list.n_max), dim3(256), 0, s, p);
   return launched() ? 0 : NUHTC_E_HIP;
 }
 
@@ -125,17 +114,10 @@ extern "C" {
 
 int nuhtc_nucleus_texture(nuhtc_engine* e, const nuhtc_dets* dets, int B, const uint8_t* tiles_dev, int channel_mode, const int32_t* lut_dev,
                           const int32_t k[3], const int64_t* idx_dev, const int32_t* n_dev, int cap, int32_t* tex_dev, void* stream) {
-  if (!e) return NUHTC_E_INVALID;
-  if (!e->finalized) FAIL(e, NUHTC_E_STATE, "nuhtc_nucleus_texture before nuhtc_finalize");
-  if (e->cfg.features_only) FAIL(e, NUHTC_E_STATE, "this engine was created with features_only = 1: it has no detections to measure");
-  if (!dets || !dets->masks || !tiles_dev || !lut_dev || !k || !idx_dev || !n_dev || !tex_dev || B > e->cfg.max_batch)
-    FAIL(e, NUHTC_E_INVALID, "bad nuhtc_nucleus_texture arguments");
-  const nuhtc_config& c = e->cfg;
-  if (const char* why = nuctex_args_error(B, c.max_per_img, c.tile_h, c.tile_w, c.tile_w, cap, channel_mode)) FAIL(e, NUHTC_E_INVALID, why);
   NucTexParams p{};
-  p.tiles = tiles_dev; p.masks = dets->masks; p.idx = idx_dev; p.n_dev = n_dev; p.lut = lut_dev; p.n_max = cap;
-  p.B = B; p.K = c.max_per_img; p.H = c.tile_h; p.W = c.tile_w; p.wpr = c.tile_w / 32; p.pitch = c.tile_w; p.tex = tex_dev;
-  haematoxylin_byte_coefficients(p.kb, k, channel_mode);
+  if (const int rc = nucleus_engine_route(e, "nuhtc_nucleus_texture", "measure", dets, B, idx_dev, n_dev, cap, tiles_dev && lut_dev && k && tex_dev, p.list, p.m)) return rc;
+  if (const int rc = nucleus_tiles_args(e, "nucleus_texture", p.list, p.m, tiles_dev, channel_mode, lut_dev, k, p.t)) return rc;
+  p.tex = tex_dev;
   HIP_CHECK(e, hipSetDevice(e->device));
   const int rc = launch_nucleus_texture(p, (hipStream_t)stream);
   if (rc) FAIL(e, rc, "nucleus_texture launch failed");
@@ -146,11 +128,10 @@ int nuhtc_op_nucleus_texture(nuhtc_engine* e, const uint8_t* tiles, int channel_
                              const uint32_t* masks, int K, int H, int W, const int32_t* pairs_dev, const int32_t* n_dev, int n_max,
                              int32_t* tex, void* stream) {
   if (!e || !tiles || !lut_dev || !k || !masks || !pairs_dev || !tex) return NUHTC_E_INVALID;
-  if (const char* why = nuctex_args_error(B, K, H, W, W, n_max, channel_mode)) FAIL(e, NUHTC_E_INVALID, why);
   NucTexParams p{};
-  p.tiles = tiles; p.masks = masks; p.pairs = pairs_dev; p.n_dev = n_dev; p.lut = lut_dev; p.n_max = n_max;
-  p.B = B; p.K = K; p.H = H; p.W = W; p.wpr = (W + 31) / 32; p.pitch = W; p.tex = tex;
-  haematoxylin_byte_coefficients(p.kb, k, channel_mode);
+  nucleus_op_route(B, masks, K, H, W, pairs_dev, n_dev, n_max, p.list, p.m);
+  if (const int rc = nucleus_tiles_args(e, "nucleus_texture", p.list, p.m, tiles, channel_mode, lut_dev, k, p.t)) return rc;
+  p.tex = tex;
   HIP_CHECK(e, hipSetDevice(e->device));
   hipStream_t s = (hipStream_t)stream;
   return op_finish(e, launch_nucleus_texture(p, s), s, "nucleus_texture launch failed", "nucleus_texture kernel failed");

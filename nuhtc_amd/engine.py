@@ -12,7 +12,7 @@ import sys
 import numpy as np
 import torch
 
-from . import hip
+from . import hip, nuclei
 
 
 class HipError(RuntimeError):
@@ -297,6 +297,7 @@ class Engine:
         [cap, 16] int64 and morph_hist [cap, 256] int32, 1152 bytes per detection in the same single copy.
         nuctex=True: the grey-level co-occurrence counts of every kept detection as well (nuhtc_nucleus_texture, on the same tiles;
         nuhtc_amd.nuctex.glcm_reference): the blob gains tex [cap, 2, 136] int32, 1088 bytes per detection in the same single copy."""
+        sel = nuclei.select(nucfeat=nucfeat, nucmorph=nucmorph, nuctex=nuctex)    # below this line no kind is named (nuhtc_amd.nuclei)
         K, W = self.cfg.max_per_img, self.cfg.tile_h * (self.cfg.tile_w // 32)
         if rle and self.cfg.tile_w != self.image_hw[1]:
             raise ValueError(f'export_async(rle=True): image width {self.image_hw[1]} is not a multiple of 32')
@@ -307,7 +308,7 @@ class Engine:
         pool = cap * int(crop_words_per_det)
         rle_pool = cap * int(rle_bytes_per_det) if rle else 0
         ex = getattr(self, '_ex', None)
-        if ex is None or ex['cap'] != cap or ex['ccap'] != contour_cap or ex['pool'] != pool or ex['rle_pool'] != rle_pool or ex['nucfeat'] != bool(nucfeat) or ex['nucmorph'] != bool(nucmorph) or ex['nuctex'] != bool(nuctex):
+        if ex is None or ex['cap'] != cap or ex['ccap'] != contour_cap or ex['pool'] != pool or ex['rle_pool'] != rle_pool or ex['kinds'] != sel:
             dev = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=self.device)
             names = dict(nk=((2,), torch.int32), idx=((cap,), torch.int64), boxes=((cap, 5), torch.float32), labels=((cap,), torch.int32),
                          cn=((cap,), torch.int32), crop_box=((cap, 4), torch.int32), crop_area=((cap,), torch.int32),
@@ -315,12 +316,8 @@ class Engine:
             if rle:
                 names.update(rle_len=((cap,), torch.int32), rle_off=((cap + 1,), torch.int32), rle_bbox=((cap, 4), torch.int32),
                              rle_bytes=((rle_pool,), torch.uint8))
-            if nucfeat:
-                names.update(feat=((cap, 256), torch.float32))
-            if nucmorph:
-                names.update(morph_raw=((cap, 16), torch.int64), morph_hist=((cap, 256), torch.int32))
-            if nuctex:
-                names.update(tex=((cap, 2, 136), torch.int32))
+            for kind in sel:
+                names.update({f: ((cap,) + tail, getattr(torch, dt)) for f, tail, dt in kind.fields})
             # every field is a view into ONE device buffer and ONE pinned host buffer: a batch's results leave the device in a single
             # copy (each asynchronous copy on a compute stream costs a hand-over between the copy engine and the kernels)
             offs, total = {}, 0
@@ -334,7 +331,7 @@ class Engine:
             # export_async after the one that filled them (i.e. until the slot's next-but-one batch is enqueued)
             blob_hosts = [torch.zeros(total, dtype=torch.uint8).pin_memory() for _ in range(self.EXPORT_BUFFERS)]
             view = lambda blob, k: blob[offs[k]:offs[k] + int(np.prod(names[k][0])) * torch.empty(0, dtype=names[k][1]).element_size()].view(names[k][1]).view(*names[k][0])
-            ex = self._ex = dict(cap=cap, ccap=contour_cap, pool=pool, rle_pool=rle_pool, nucfeat=bool(nucfeat), nucmorph=bool(nucmorph), nuctex=bool(nuctex), blob_dev=blob_dev, blob_hosts=blob_hosts, turn=0,
+            ex = self._ex = dict(cap=cap, ccap=contour_cap, pool=pool, rle_pool=rle_pool, kinds=sel, blob_dev=blob_dev, blob_hosts=blob_hosts, turn=0,
                                  hosts=[{k: view(b, k) for k in names} for b in blob_hosts], dev={k: view(blob_dev, k) for k in names})
             ex['dev']['words'] = dev(cap, W, dtype=torch.int32)          # full masks of the kept detections: device only
         self.contours_async(B, contour_cap)
@@ -351,12 +348,8 @@ class Engine:
                                            vp(d['rle_len']), vp(d['rle_off']), vp(d['rle_bytes']), rle_pool, vp(d['rle_bbox']), self._stream())
             if rc:
                 raise HipError(f'nuhtc_rle_encode failed ({rc})')
-        if nucfeat:     # behind nuhtc_export_kept on the same stream: the list and its length are read from idx / nk[0] on the device
-            self._check(self.lib.nuhtc_nucleus_features(self.h, ctypes.byref(self.dets), B, vp(d['idx']), vp(d['nk']), cap, vp(d['feat']), self._stream()))
-        if nucmorph:    # likewise, on the tiles the inference read
-            self._nucleus_morph(B, vp(d['idx']), vp(d['nk']), cap, vp(d['morph_raw']), vp(d['morph_hist']))
-        if nuctex:
-            self._nucleus_texture(B, vp(d['idx']), vp(d['nk']), cap, vp(d['tex']))
+        for kind in sel:    # behind nuhtc_export_kept on the same stream: the list and its length are read from idx / nk[0] on the device
+            self._nucleus_async(kind, B, d['idx'], d['nk'], cap, [d[f] for f, _, _ in kind.fields])
         ex['turn'] = (ex['turn'] + 1) % self.EXPORT_BUFFERS
         ex['host'] = ex['hosts'][ex['turn']]
         ex['blob_hosts'][ex['turn']].copy_(ex['blob_dev'], non_blocking=True)
@@ -390,74 +383,54 @@ class Engine:
             roff = ex['rle_off'].numpy()
             g.update(rle_len=ex['rle_len'][:n].numpy(), rle_off=roff[:n], rle_bbox=ex['rle_bbox'][:n].numpy(), rle_bytes=ex['rle_bytes'].numpy(),
                      rle_total=int(roff[n]), rle_pool=self._ex['rle_pool'])
-        if 'feat' in ex:            # exported with nucfeat=True: row k is the embedding of detection k
-            g.update(feat=ex['feat'][:n].numpy())
-        if 'morph_raw' in ex:       # exported with nucmorph=True: row k holds the integers of detection k
-            g.update(morph_raw=ex['morph_raw'][:n].numpy(), morph_hist=ex['morph_hist'][:n].numpy())
-        if 'tex' in ex:             # exported with nuctex=True: row k holds the co-occurrence counts of detection k
-            g.update(tex=ex['tex'][:n].numpy())
+        for kind in self._ex['kinds']:      # row k of every field belongs to detection k
+            g.update({f: ex[f][:n].numpy() for f, _, _ in kind.fields})
         return g
+
+    def _nucleus_async(self, kind, B, idx, n_dev, cap, outs):
+        """Enqueue the kernel of one kind of per-nucleus measurement (nuhtc_amd.nuclei) on the current stream: the entries idx[:min(n_dev[0],
+        cap)] (device tensors: tile * max_per_img + slot, as nuhtc_export_kept writes them) of the last infer_async into the device tensors
+        `outs`, one per field of the kind.  The kinds that read pixels read the tiles of that inference."""
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        src = ()
+        if kind.reads_tiles:
+            (lut, k), (tiles, mode) = self._morph_constants(), self._morph_src
+            src = (vp(tiles), mode, vp(lut), k)
+        self._check(getattr(self.lib, kind.call)(self.h, ctypes.byref(self.dets), B, *src, vp(idx), vp(n_dev), cap, *[vp(o) for o in outs], self._stream()))
+
+    def _nucleus_sync(self, kind, B, tile, slot):
+        """The fields of one kind for the detections (tile[i], slot[i]) of the last infer_async, on a list made here -> tuple of ndarrays."""
+        n = len(tile)
+        if n == 0:
+            return tuple(np.zeros((0,) + tail, dt) for _, tail, dt in kind.fields)
+        idx = torch.from_numpy(np.asarray(tile, np.int64) * self.cfg.max_per_img + np.asarray(slot, np.int64)).to(self.device)
+        cnt = torch.tensor([n], dtype=torch.int32, device=self.device)
+        outs = [torch.zeros(n, *tail, dtype=getattr(torch, dt), device=self.device) for _, tail, dt in kind.fields]
+        self._nucleus_async(kind, B, idx, cnt, n, outs)
+        return tuple(o.cpu().numpy() for o in outs)
 
     def nucleus_features(self, B, tile, slot):
         """Embeddings of the detections (tile[i], slot[i]) of the last infer_async, synchronously (nuhtc_nucleus_features on a list made
         here; export_async(nucfeat=True) is the asynchronous route) -> float32 (n, 256) ndarray."""
-        n = len(tile)
-        if n == 0:
-            return np.zeros((0, 256), np.float32)
-        idx = torch.from_numpy(np.asarray(tile, np.int64) * self.cfg.max_per_img + np.asarray(slot, np.int64)).to(self.device)
-        cnt = torch.tensor([n], dtype=torch.int32, device=self.device)
-        out = torch.zeros(n, 256, dtype=torch.float32, device=self.device)
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())
-        self._check(self.lib.nuhtc_nucleus_features(self.h, ctypes.byref(self.dets), B, vp(idx), vp(cnt), n, vp(out), self._stream()))
-        return out.cpu().numpy()
+        return self._nucleus_sync(nuclei.FEAT, B, tile, slot)[0]
 
     def _morph_constants(self):
-        """(device int32 [256] table, host int32 [3] coefficients) of the haematoxylin value, built once (nuhtc_amd.nucmorph.stain_constants)."""
+        """(device int32 [256] table, host int32 [3] coefficients) of the haematoxylin value, built once (nuclei.stain_constants)."""
         if getattr(self, '_morph_k', None) is None:
-            from . import nucmorph
-            lut, k = nucmorph.stain_constants()
+            lut, k = nuclei.stain_constants()
             self._morph_lut = torch.from_numpy(lut).to(self.device)
             self._morph_k = (ctypes.c_int32 * 3)(*[int(v) for v in k])
         return self._morph_lut, self._morph_k
 
-    def _nucleus_morph(self, B, idx, n_dev, cap, raw, hist):
-        lut, k = self._morph_constants()
-        tiles, mode = self._morph_src
-        self._check(self.lib.nuhtc_nucleus_morph(self.h, ctypes.byref(self.dets), B, ctypes.c_void_p(tiles.data_ptr()), mode,
-                                                 ctypes.c_void_p(lut.data_ptr()), k, idx, n_dev, cap, raw, hist, self._stream()))
-
     def nucleus_morph(self, B, tile, slot):
         """Morphometry integers of the detections (tile[i], slot[i]) of the last infer_async, synchronously (nuhtc_nucleus_morph on a list
-        made here; export_async(nucmorph=True) is the asynchronous route) -> (raw int64 (n, 16), hist int32 (n, 256)) ndarrays."""
-        n = len(tile)
-        if n == 0:
-            return np.zeros((0, 16), np.int64), np.zeros((0, 256), np.int32)
-        idx = torch.from_numpy(np.asarray(tile, np.int64) * self.cfg.max_per_img + np.asarray(slot, np.int64)).to(self.device)
-        cnt = torch.tensor([n], dtype=torch.int32, device=self.device)
-        raw = torch.zeros(n, 16, dtype=torch.int64, device=self.device)
-        hist = torch.zeros(n, 256, dtype=torch.int32, device=self.device)
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())
-        self._nucleus_morph(B, vp(idx), vp(cnt), n, vp(raw), vp(hist))
-        return raw.cpu().numpy(), hist.cpu().numpy()
-
-    def _nucleus_texture(self, B, idx, n_dev, cap, tex):
-        lut, k = self._morph_constants()
-        tiles, mode = self._morph_src
-        self._check(self.lib.nuhtc_nucleus_texture(self.h, ctypes.byref(self.dets), B, ctypes.c_void_p(tiles.data_ptr()), mode,
-                                                   ctypes.c_void_p(lut.data_ptr()), k, idx, n_dev, cap, tex, self._stream()))
+        made here; the asynchronous route is export_async) -> (raw int64 (n, 16), hist int32 (n, 256)) ndarrays."""
+        return self._nucleus_sync(nuclei.MORPH, B, tile, slot)
 
     def nucleus_texture(self, B, tile, slot):
         """Co-occurrence counts of the detections (tile[i], slot[i]) of the last infer_async, synchronously (nuhtc_nucleus_texture on a list
-        made here; export_async(nuctex=True) is the asynchronous route) -> int32 (n, 2, 136) ndarray."""
-        n = len(tile)
-        if n == 0:
-            return np.zeros((0, 2, 136), np.int32)
-        idx = torch.from_numpy(np.asarray(tile, np.int64) * self.cfg.max_per_img + np.asarray(slot, np.int64)).to(self.device)
-        cnt = torch.tensor([n], dtype=torch.int32, device=self.device)
-        tex = torch.zeros(n, 2, 136, dtype=torch.int32, device=self.device)
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())
-        self._nucleus_texture(B, vp(idx), vp(cnt), n, vp(tex))
-        return tex.cpu().numpy()
+        made here; the asynchronous route is export_async) -> int32 (n, 2, 136) ndarray."""
+        return self._nucleus_sync(nuclei.TEX, B, tile, slot)[0]
 
     def export_full_mask(self, k):
         """(tile_h, tile_w) bool mask of exported detection k of the last export_async (synchronous device read: the rare crop that
@@ -974,28 +947,38 @@ class Engine:
                                                    vp(masks), K, H, W, vp(pairs), vp(n) if n is not None else None, n_max, vp(out), self._stream()))
         return out
 
+    def _op_nucleus_check(self, op, tiles, masks, pairs):
+        """The tiles / masks / pairs of the ops that read tile pixels (`op`: the name in the messages) -> B, K, H, W, n_max."""
+        for t, dt in ((tiles, torch.uint8), (masks, torch.int32), (pairs, torch.int32)):
+            if t.device != self.device or t.dtype != dt or not t.is_contiguous():
+                raise ValueError(f'{op}: contiguous tensors on the engine\'s device (uint8 tiles, int32 masks and pairs)')
+        if tiles.dim() != 4 or masks.dim() != 4 or tiles.shape[3] != 3 or tuple(pairs.shape[1:]) != (2,):
+            raise ValueError(f'{op}: tiles (B, H, W, 3), masks (B, K, H, (W + 31) // 32), pairs (n, 2)')
+        B, H, W = (int(v) for v in tiles.shape[:3])
+        K, n_max = int(masks.shape[1]), int(pairs.shape[0])
+        if tuple(masks.shape) != (B, K, H, (W + 31) // 32):
+            raise ValueError(f'{op}: tiles (B, H, W, 3), masks (B, K, H, (W + 31) // 32), pairs (n, 2)')
+        return B, K, H, W, n_max
+
+    def _op_nucleus_out(self, out, n_max, fields, error):
+        """The output tensors of a per-nucleus op, one per (shape behind n_max, dtype) of `fields`: zero-filled ones for None, else checked."""
+        if out is None:
+            return tuple(torch.zeros(n_max, *tail, dtype=dt, device=self.device) for tail, dt in fields)
+        for t, (tail, dt) in zip(out, fields):
+            if t.device != self.device or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != (n_max,) + tail:
+                raise ValueError(error)
+        return tuple(out)
+
     def op_nucleus_morph(self, tiles, masks, pairs, channel_mode=hip.CH_AS_IS, n=None, out=None):
-        """Per-nucleus morphometry integers on raw arrays (nuhtc_op_nucleus_morph; nuhtc_amd.nucmorph.morph_reference is the numpy
-        restatement).  tiles: contiguous uint8 device tensor (B, H, W, 3); masks: contiguous int32 device tensor (B, K, H, (W + 31) // 32), bit
+        """Per-nucleus morphometry integers on raw arrays (nuhtc_op_nucleus_morph; the numpy restatement is morph_reference of
+        the module nuclei.MORPH draws on).  tiles: contiguous uint8 device tensor (B, H, W, 3); masks: contiguous int32 device tensor (B, K, H, (W + 31) // 32), bit
         x & 31 of word x >> 5; pairs: int32 device tensor (n_max, 2) of (tile, slot); channel_mode: which byte is red (CH_AS_IS: byte 0,
         CH_SWAP: byte 2); n: None (all n_max entries) or an int32 device tensor whose first element is the number of entries (read on the
         device); out: (raw int64 (n_max, 16), hist int32 (n_max, 256)) contiguous device tensors to write into (rows from n on stay as they
         are), zero-filled ones otherwise.  -> (raw, hist).  Synchronous."""
-        for t, dt in ((tiles, torch.uint8), (masks, torch.int32), (pairs, torch.int32)):
-            if t.device != self.device or t.dtype != dt or not t.is_contiguous():
-                raise ValueError('op_nucleus_morph: contiguous tensors on the engine\'s device (uint8 tiles, int32 masks and pairs)')
-        if tiles.dim() != 4 or masks.dim() != 4 or tiles.shape[3] != 3 or tuple(pairs.shape[1:]) != (2,):
-            raise ValueError('op_nucleus_morph: tiles (B, H, W, 3), masks (B, K, H, (W + 31) // 32), pairs (n, 2)')
-        B, H, W = (int(v) for v in tiles.shape[:3])
-        K, n_max = int(masks.shape[1]), int(pairs.shape[0])
-        if tuple(masks.shape) != (B, K, H, (W + 31) // 32):
-            raise ValueError('op_nucleus_morph: tiles (B, H, W, 3), masks (B, K, H, (W + 31) // 32), pairs (n, 2)')
-        if out is None:
-            out = (torch.zeros(n_max, 16, dtype=torch.int64, device=self.device), torch.zeros(n_max, 256, dtype=torch.int32, device=self.device))
-        raw, hist = out
-        for t, dt, sh in ((raw, torch.int64, (n_max, 16)), (hist, torch.int32, (n_max, 256))):
-            if t.device != self.device or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != sh:
-                raise ValueError('op_nucleus_morph: out must be contiguous (int64 (n_max, 16), int32 (n_max, 256)) tensors on the engine\'s device')
+        B, K, H, W, n_max = self._op_nucleus_check('op_nucleus_morph', tiles, masks, pairs)
+        raw, hist = self._op_nucleus_out(out, n_max, (((16,), torch.int64), ((256,), torch.int32)),
+                                         'op_nucleus_morph: out must be contiguous (int64 (n_max, 16), int32 (n_max, 256)) tensors on the engine\'s device')
         lut, k = self._morph_constants()
         vp = lambda t: ctypes.c_void_p(t.data_ptr())
         self._check(self.lib.nuhtc_op_nucleus_morph(self.h, vp(tiles), int(channel_mode), vp(lut), k, B, vp(masks), K, H, W, vp(pairs),
@@ -1003,22 +986,12 @@ class Engine:
         return raw, hist
 
     def op_nucleus_texture(self, tiles, masks, pairs, channel_mode=hip.CH_AS_IS, n=None, out=None):
-        """Per-nucleus grey-level co-occurrence counts on raw arrays (nuhtc_op_nucleus_texture; nuhtc_amd.nuctex.glcm_reference is the numpy
-        restatement).  tiles, masks, pairs, channel_mode and n as in op_nucleus_morph; out: a contiguous int32 (n_max, 2, 136) device tensor to
+        """Per-nucleus grey-level co-occurrence counts on raw arrays (nuhtc_op_nucleus_texture; the numpy restatement is glcm_reference of
+        the module nuclei.TEX draws on).  tiles, masks, pairs, channel_mode and n as in op_nucleus_morph; out: a contiguous int32 (n_max, 2, 136) device tensor to
         write into (rows from n on stay as they are), a zero-filled one otherwise.  -> out.  Synchronous."""
-        for t, dt in ((tiles, torch.uint8), (masks, torch.int32), (pairs, torch.int32)):
-            if t.device != self.device or t.dtype != dt or not t.is_contiguous():
-                raise ValueError('op_nucleus_texture: contiguous tensors on the engine\'s device (uint8 tiles, int32 masks and pairs)')
-        if tiles.dim() != 4 or masks.dim() != 4 or tiles.shape[3] != 3 or tuple(pairs.shape[1:]) != (2,):
-            raise ValueError('op_nucleus_texture: tiles (B, H, W, 3), masks (B, K, H, (W + 31) // 32), pairs (n, 2)')
-        B, H, W = (int(v) for v in tiles.shape[:3])
-        K, n_max = int(masks.shape[1]), int(pairs.shape[0])
-        if tuple(masks.shape) != (B, K, H, (W + 31) // 32):
-            raise ValueError('op_nucleus_texture: tiles (B, H, W, 3), masks (B, K, H, (W + 31) // 32), pairs (n, 2)')
-        if out is None:
-            out = torch.zeros(n_max, 2, 136, dtype=torch.int32, device=self.device)
-        if out.device != self.device or out.dtype != torch.int32 or not out.is_contiguous() or tuple(out.shape) != (n_max, 2, 136):
-            raise ValueError('op_nucleus_texture: out must be a contiguous int32 (n_max, 2, 136) tensor on the engine\'s device')
+        B, K, H, W, n_max = self._op_nucleus_check('op_nucleus_texture', tiles, masks, pairs)
+        out, = self._op_nucleus_out(None if out is None else (out,), n_max, (((2, 136), torch.int32),),
+                                    'op_nucleus_texture: out must be a contiguous int32 (n_max, 2, 136) tensor on the engine\'s device')
         lut, k = self._morph_constants()
         vp = lambda t: ctypes.c_void_p(t.data_ptr())
         self._check(self.lib.nuhtc_op_nucleus_texture(self.h, vp(tiles), int(channel_mode), vp(lut), k, B, vp(masks), K, H, W, vp(pairs),

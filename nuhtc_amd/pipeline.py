@@ -25,6 +25,7 @@ import collections
 import numpy as np
 import torch
 
+from . import nuclei
 from .engine import Engine
 
 
@@ -67,6 +68,7 @@ class EnginePipeline:
         Engine.export_async (rle=True: with the COCO run-length strings of the kept detections; nucfeat=True: with their embeddings; nucmorph=True: with
         their morphometry integers, nuctex=True: with their co-occurrence counts, both read from the batch's device tiles, which stay referenced here until
         collect())."""
+        sel = nuclei.select(nucfeat=nucfeat, nucmorph=nucmorph, nuctex=nuctex)
         slot = self.next
         held = self._held(slot)
         if held and (not export or len(held) >= self.per_slot or any(p[5] is None for p in held)):
@@ -92,14 +94,7 @@ class EnginePipeline:
             else:
                 B = eng.infer_async(dev, channel_mode)
             if export:                      # contours + gather of the kept detections into pinned host buffers, still asynchronous
-                kw = dict(rle=True) if rle else {}
-                if nucfeat:
-                    kw['nucfeat'] = True
-                if nucmorph:
-                    kw['nucmorph'] = True
-                if nuctex:
-                    kw['nuctex'] = True
-                turn = eng.export_async(B, **kw)
+                turn = eng.export_async(B, **(dict(rle=True) if rle else {}), **nuclei.keywords(sel))      # only what was asked for is named
             ev = torch.cuda.Event()
             ev.record(st)
         self.pending.append((slot, B, ev, tag, (dev, src), turn))

@@ -6,7 +6,7 @@ OpenSlide / h5py are not available offline, so tiles come from arrays (`tile_gri
 .npz with `tiles` + `coords`)."""
 import numpy as np
 
-from . import hip
+from . import hip, nuclei
 
 
 def tile_grid(image, patch_size=256, step_size=192):
@@ -25,8 +25,8 @@ def tile_grid(image, patch_size=256, step_size=192):
     return np.stack(tiles), np.array(coords, np.int64)
 
 
-def _gather_sync(eng, B, nucfeat=False, nucmorph=False, nuctex=False):
-    """Synchronous twin of Engine.export_async / export_read (any number of kept detections)."""
+def _gather_sync(eng, B, sel=()):
+    """Synchronous twin of Engine.export_async / export_read (any number of kept detections; sel: the kinds of nuhtc_amd.nuclei to measure)."""
     import torch
     K = eng.cfg.max_per_img
     eng.contours_async(B)
@@ -34,16 +34,12 @@ def _gather_sync(eng, B, nucfeat=False, nucmorph=False, nuctex=False):
     keep = eng.keep[:B].cpu().numpy()
     kept = (keep != 0) & (np.arange(K)[None, :] < counts[:, None])
     tile, slot = np.nonzero(kept)
-    sel = torch.from_numpy(np.stack([tile, slot])).to(eng.device)
-    g = dict(n=len(tile), tile=tile, slot=slot, boxes=eng.boxes[sel[0], sel[1]].cpu().numpy(), labels=eng.labels[sel[0], sel[1]].cpu().numpy(),
-             cn=eng.contour_n[sel[0], sel[1]].cpu().numpy(), xy=eng.contour_xy[sel[0], sel[1]].cpu().numpy(),
-             words=eng.masks[sel[0], sel[1]].reshape(len(tile), -1).cpu().numpy().view(np.uint32))
-    if nucfeat:
-        g['feat'] = eng.nucleus_features(B, tile, slot)
-    if nucmorph:
-        g['morph_raw'], g['morph_hist'] = eng.nucleus_morph(B, tile, slot)
-    if nuctex:
-        g['tex'] = eng.nucleus_texture(B, tile, slot)
+    at = torch.from_numpy(np.stack([tile, slot])).to(eng.device)
+    g = dict(n=len(tile), tile=tile, slot=slot, boxes=eng.boxes[at[0], at[1]].cpu().numpy(), labels=eng.labels[at[0], at[1]].cpu().numpy(),
+             cn=eng.contour_n[at[0], at[1]].cpu().numpy(), xy=eng.contour_xy[at[0], at[1]].cpu().numpy(),
+             words=eng.masks[at[0], at[1]].reshape(len(tile), -1).cpu().numpy().view(np.uint32))
+    for kind in sel:
+        g.update(zip((f for f, _, _ in kind.fields), eng._nucleus_sync(kind, B, tile, slot)))
     return g
 
 
@@ -229,14 +225,13 @@ def _unpack_packed(eng, g, i0, coords, parts):
     if 'rle_len' in g:                                                    # exported with rle=True: the strings travel with the records
         blob, ln, bbox, nh = _rle_of_records(g, order, cb, bits, sizes, (eng.cfg.tile_h, eng.cfg.tile_w))
         parts[-1].update(rle_blob=blob, rle_len=ln, rle_bbox=bbox, rle_host=nh)
-    if 'feat' in g:                                                       # exported with nucfeat=True: one embedding row per record
-        parts[-1].update(feat=g['feat'][order])
-    if 'morph_raw' in g:                                                  # exported with nucmorph=True: one row of integers per record
-        from . import nucmorph
-        parts[-1].update(morph=nucmorph.pack_rows(g['morph_raw'][order], g['morph_hist'][order], org))
-    if 'tex' in g:                                                        # exported with nuctex=True: one row of counts per record
-        from . import nuctex
-        parts[-1].update(tex=nuctex.pack_rows(g['tex'][order]))
+    for kind in _measured(g):                                             # one travelling row per record
+        parts[-1][kind.key] = kind.rows([g[f][order] for f, _, _ in kind.fields], org)
+
+
+def _measured(g):
+    """The kinds of nuhtc_amd.nuclei whose fields a batch's gather (export_read, _gather_sync) holds."""
+    return tuple(k for k in nuclei.KINDS if k.fields[0][0] in g)
 
 
 def _records_from_parts(parts):
@@ -254,24 +249,18 @@ def _records_from_parts(parts):
     masks.arrays = dict(tile=tile, box=box, score=score, label=label, rings=rings)   # the scalar fields as whole-slide arrays
     if 'rle_len' in parts[0]:
         rec.update(rle=(cat('rle_blob'), cat('rle_len')), rle_bbox=cat('rle_bbox'), rle_host=int(sum(p['rle_host'] for p in parts)))
-    if 'feat' in parts[0]:
-        rec.update(feat=cat('feat'))
-    if 'morph' in parts[0]:
-        rec.update(morph=cat('morph'))
-    if 'tex' in parts[0]:
-        rec.update(tex=cat('tex'))
+    rec.update({kind.key: cat(kind.key) for kind in nuclei.carried(parts[0])})
     return rec
 
 
-def _unpack(eng, B, i0, coords, P, rec, exported=False, nucfeat=False, nucmorph=False, nuctex=False):
+def _unpack(eng, B, i0, coords, P, rec, exported=False, sel=()):
     """Kept detections of one finished batch -> records in slide coordinates.  `exported`: the batch was submitted with
-    export=True (its results already sit in the engine's pinned buffers); otherwise they are fetched here (nucfeat: with the
-    embeddings, appended to rec['feat']; nucmorph: with the morphometry rows, appended to rec['morph']; nuctex: with the
-    co-occurrence rows, appended to rec['tex'])."""
+    export=True (its results already sit in the engine's pinned buffers); otherwise they are fetched here (with the rows of the kinds
+    `sel` of nuhtc_amd.nuclei, appended to rec[kind.key])."""
     from . import contours as host
     g = eng.export_read() if exported else None
     if g is None:
-        g = _gather_sync(eng, B, nucfeat, nucmorph, nuctex)
+        g = _gather_sync(eng, B, sel)
     n = g['n']
     if n == 0:
         return
@@ -315,14 +304,8 @@ def _unpack(eng, B, i0, coords, P, rec, exported=False, nucfeat=False, nucmorph=
             full = np.unpackbits(g['words'][k].reshape(P, W).view(np.uint8), axis=-1, bitorder='little').astype(bool)
             c = host.trace_outer_contour(full)
         rec['ring'].append(np.concatenate([c, c[:1]], 0) + np.array([ox, oy], np.int64))   # mask2inst + contour_map
-        if 'feat' in g:
-            rec.setdefault('feat', []).append(g['feat'][k])
-        if 'morph_raw' in g:
-            from . import nucmorph
-            rec.setdefault('morph', []).append(nucmorph.pack_rows(g['morph_raw'][k], g['morph_hist'][k], (ox, oy))[0])
-        if 'tex' in g:
-            from . import nuctex as nt
-            rec.setdefault('tex', []).append(nt.pack_rows(g['tex'][k])[0])
+        for kind in _measured(g):
+            rec.setdefault(kind.key, []).append(kind.rows([g[f][k:k + 1] for f, _, _ in kind.fields], (ox, oy))[0])
 
 
 def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False, nucfeat=False, nucmorph=False, nuctex=False):
@@ -343,11 +326,7 @@ def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False, nucfeat
     nuctex=True adds tex int64 (n, nuctex.ROW = 136): the grey-level co-occurrence counts of every record, taken on the GPU under its mask from the
     tile's pixels (nuhtc_nucleus_texture; nuhtc_amd.nuctex.unpack_rows -> glcm int32 (n, 2, 136)), row i for record i."""
     import torch
-    more = dict(nucfeat=True) if nucfeat else {}
-    if nucmorph:
-        more['nucmorph'] = True
-    if nuctex:
-        more['nuctex'] = True
+    sel = nuclei.select(nucfeat=nucfeat, nucmorph=nucmorph, nuctex=nuctex)
     P = tiles.shape[1]
     parts = {}                 # first tile of the batch -> the batch's records (array form), joined in batch order at the end
     redo = []
@@ -370,7 +349,7 @@ def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False, nucfeat
     for i in range(0, len(tiles), batch_size):
         if pipe.full(export=True):
             finish()
-        pipe.submit(tiles[i:i + batch_size], hip.CH_SWAP, tag=i, export=True, rle=rle, **more)
+        pipe.submit(tiles[i:i + batch_size], hip.CH_SWAP, tag=i, export=True, rle=rle, **nuclei.keywords(sel))
     while pipe.pending:
         finish()
     for i0 in redo:            # the per-detection path (later batches kept the packed path)
@@ -378,7 +357,7 @@ def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False, nucfeat
         eng, B, stream, _ = pipe.collect()
         with torch.cuda.stream(stream):
             one = dict(tile=[], box=[], score=[], label=[], mask=[], ring=[])
-            _unpack(eng, B, i0, coords, P, one, exported=False, nucfeat=nucfeat, nucmorph=nucmorph, nuctex=nuctex)
+            _unpack(eng, B, i0, coords, P, one, exported=False, sel=sel)
             if one['tile']:
                 parts[i0] = _part_from_lists(one)
                 if rle:                                            # nothing of this batch was encoded on the device
@@ -388,14 +367,8 @@ def infer_tiles(model, tiles, coords, batch_size=16, depth=4, rle=False, nucfeat
     rec = _records_from_parts([parts[k] for k in sorted(parts)])
     if rle and 'rle' not in rec:
         rec.update(rle=(np.zeros(0, np.uint8), np.zeros(0, np.int64)), rle_bbox=np.zeros((0, 4), np.int32), rle_host=0)
-    if nucfeat and 'feat' not in rec:
-        rec.update(feat=np.zeros((0, 256), np.float32))
-    if nucmorph and 'morph' not in rec:
-        from . import nucmorph as nm
-        rec.update(morph=np.zeros((0, nm.ROW), np.int64))
-    if nuctex and 'tex' not in rec:
-        from . import nuctex as nt
-        rec.update(tex=np.zeros((0, nt.ROW), np.int64))
+    for kind in sel:
+        rec.setdefault(kind.key, np.zeros((0, kind.width), kind.dtype))
     return rec
 
 
@@ -409,12 +382,7 @@ def _part_from_lists(rec):
     part = dict(tile=np.asarray(rec['tile'], np.int64), box=np.stack(rec['box']).astype(np.float64), score=np.asarray(rec['score'], np.float64),
                 label=np.asarray(rec['label'], np.int64), crop_box=cb.astype(np.int32), area=area.astype(np.int32),
                 bits=bits[:int(sizes.sum())], sizes=sizes, ring_n=ring_n, ring_flat=ring_flat)
-    if 'feat' in rec:
-        part.update(feat=np.stack(rec['feat']).astype(np.float32))
-    if 'morph' in rec:
-        part.update(morph=np.stack(rec['morph']).astype(np.int64))
-    if 'tex' in rec:
-        part.update(tex=np.stack(rec['tex']).astype(np.int64))
+    part.update({kind.key: np.stack(rec[kind.key]).astype(kind.dtype) for kind in nuclei.carried(rec)})
     return part
 
 
@@ -423,12 +391,8 @@ def _extend(rec, more):
     for k in ('tile', 'box', 'score', 'label', 'ring'):
         rec[k].extend(list(more[k]))
     rec['mask'].extend(list(more['mask']))
-    if 'feat' in more:
-        rec.setdefault('feat', []).extend(list(more['feat']))
-    if 'morph' in more:
-        rec.setdefault('morph', []).extend(list(more['morph']))
-    if 'tex' in more:
-        rec.setdefault('tex', []).extend(list(more['tex']))
+    for kind in nuclei.carried(more):
+        rec.setdefault(kind.key, []).extend(list(more[kind.key]))
 
 
 def pack_masks(masks):
@@ -507,12 +471,9 @@ def pack_records(rec, keep=None, tile_base=0, rles=None):
     blob  uint8   (bytes,): optional COCO RLE strings, concatenated
     rles: a list of `bytes`, one per record of `keep`, or the pair (uint8 blob, lengths) infer_tiles(rle=True) returns as rec['rle']: the
     strings of ALL records of `rec` concatenated in record order, of which the records `keep` are taken here.
-    Records that carry embeddings (rec['feat'], infer_tiles(nucfeat=True)) travel with one more part behind these five:
-    feat  float32 (n, 256): the rows of the records `keep`;
-    and records that carry morphometry rows (rec['morph'], infer_tiles(nucmorph=True)) with one more behind that:
-    morph int64 (n, nucmorph.ROW = 146): the rows of the records `keep`;
-    and records that carry co-occurrence rows (rec['tex'], infer_tiles(nuctex=True)) with one more behind that:
-    tex   int64 (n, nuctex.ROW = 136): the rows of the records `keep`."""
+    Records that carry per-nucleus rows (rec[kind.key] for the kinds of nuhtc_amd.nuclei that infer_tiles was asked for) travel with one
+    more part per kind behind these five, in the order of nuclei.KINDS: (n, kind.width) of kind.dtype, the rows of the records `keep`
+    (feat float32 (n, 256), morph int64 (n, 146), tex int64 (n, 136))."""
     import torch
     if isinstance(rles, tuple):                                    # the device's blob + lengths: one gather, no per-record objects
         ball, lall = np.asarray(rles[0], np.uint8), np.asarray(rles[1], np.int64)
@@ -535,7 +496,7 @@ def pack_records(rec, keep=None, tile_base=0, rles=None):
         m = rec['mask'].subset(kp)
         crops = np.concatenate([m.boxes.astype(np.int64), m.areas[:, None].astype(np.int64), m.off[:, None]], 1) if n else np.zeros((0, 6), np.int64)
         return [torch.from_numpy(head), torch.from_numpy(verts), torch.from_numpy(crops), torch.from_numpy(m.bits.view(np.int32).copy()),
-                torch.from_numpy(rle_blob)] + _feat_part(rec, kp) + _morph_part(rec, kp) + _tex_part(rec, kp)
+                torch.from_numpy(rle_blob)] + _row_parts(rec, kp)
     keep = list(range(len(rec['score']))) if keep is None else list(keep)
     n = len(keep)
     head = np.zeros((n, 9), np.float64)
@@ -550,59 +511,27 @@ def pack_records(rec, keep=None, tile_base=0, rles=None):
     if n == 0:
         mbits = np.zeros(0, np.uint32)
     return [torch.from_numpy(head), torch.from_numpy(verts), torch.from_numpy(crops), torch.from_numpy(mbits.view(np.int32).copy()),
-            torch.from_numpy(rle_blob)] + _feat_part(rec, keep) + _morph_part(rec, keep) + _tex_part(rec, keep)
+            torch.from_numpy(rle_blob)] + _row_parts(rec, keep)
 
 
-def _feat_part(rec, keep):
-    """pack_records' sixth part: the embedding rows of the records `keep` (no part for records without embeddings)."""
+def _row_parts(rec, keep):
+    """pack_records' parts behind the five document parts: per kind the records carry, the rows of the records `keep`."""
     import torch
-    if 'feat' not in rec:
-        return []
-    feat = np.asarray(rec['feat'], np.float32).reshape(-1, 256)
-    return [torch.from_numpy(np.ascontiguousarray(feat[np.asarray(list(keep), np.int64)]))]
+    keep = np.asarray(list(keep), np.int64)
+    return [torch.from_numpy(np.ascontiguousarray(np.asarray(rec[kind.key], kind.dtype).reshape(-1, kind.width)[keep])) for kind in nuclei.carried(rec)]
 
 
-def _morph_part(rec, keep):
-    """pack_records' part behind the embeddings: the morphometry rows of the records `keep` (no part for records without them)."""
-    import torch
-    if 'morph' not in rec:
-        return []
-    from . import nucmorph
-    rows = np.asarray(rec['morph'], np.int64).reshape(-1, nucmorph.ROW)
-    return [torch.from_numpy(np.ascontiguousarray(rows[np.asarray(list(keep), np.int64)]))]
-
-
-def gathered_morph(gathered, kept=None, part=5):
-    """Rank 0 after the gather: the morphometry rows of all ranks' records (part `part` of each rank's list) in the rank-major order
-    merge_gathered indexes, or only the rows `kept`, in that order -> int64 (n, nucmorph.ROW) (nuhtc_amd.nucmorph.unpack_rows)."""
-    from . import nucmorph
-    rows = np.concatenate([np.asarray(g[part].cpu().numpy(), np.int64).reshape(-1, nucmorph.ROW) for g in gathered], 0)
-    return rows if kept is None else rows[np.asarray(kept, np.int64)]
-
-
-def _tex_part(rec, keep):
-    """pack_records' part behind the morphometry: the co-occurrence rows of the records `keep` (no part for records without them)."""
-    import torch
-    if 'tex' not in rec:
-        return []
-    from . import nuctex
-    rows = np.asarray(rec['tex'], np.int64).reshape(-1, nuctex.ROW)
-    return [torch.from_numpy(np.ascontiguousarray(rows[np.asarray(list(keep), np.int64)]))]
-
-
-def gathered_texture(gathered, kept=None, part=5):
-    """Rank 0 after the gather: the co-occurrence rows of all ranks' records (part `part` of each rank's list) in the rank-major order
-    merge_gathered indexes, or only the rows `kept`, in that order -> int64 (n, nuctex.ROW) (nuhtc_amd.nuctex.unpack_rows)."""
-    from . import nuctex
-    rows = np.concatenate([np.asarray(g[part].cpu().numpy(), np.int64).reshape(-1, nuctex.ROW) for g in gathered], 0)
+def gathered_rows(kind, gathered, kept=None, part=5):
+    """Rank 0 after the gather: the rows of one kind (nuhtc_amd.nuclei) of all ranks' records (part `part` of each rank's list: pack_records
+    puts the first kind the records carry at 5) in the rank-major order merge_gathered indexes, or only the rows `kept` (what
+    merge_gathered / merge_overlap returned), in that order -> (n, kind.width) of kind.dtype."""
+    rows = np.concatenate([np.asarray(g[part].cpu().numpy(), kind.dtype).reshape(-1, kind.width) for g in gathered], 0)
     return rows if kept is None else rows[np.asarray(kept, np.int64)]
 
 
 def gathered_features(gathered, kept=None, part=5):
-    """Rank 0 after the gather: the embedding rows of all ranks' records (part `part` of each rank's list: pack_records puts them at 5) in
-    the rank-major order merge_gathered indexes, or only the rows `kept` (what merge_gathered / merge_overlap returned), in that order."""
-    rows = np.concatenate([np.asarray(g[part].cpu().numpy(), np.float32).reshape(-1, 256) for g in gathered], 0)
-    return rows if kept is None else rows[np.asarray(kept, np.int64)]
+    """gathered_rows of the embeddings -> float32 (n, 256)."""
+    return gathered_rows(nuclei.FEAT, gathered, kept, part)
 
 
 def merge_gathered(gathered, overlap_threshold=0.05, device=0, overlap='polygon'):

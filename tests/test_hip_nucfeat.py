@@ -120,6 +120,31 @@ def test_op_width_not_a_multiple_of_32(eng):
     assert not bad[:3].any() and np.array_equal(bad[3], got[0])
 
 
+def test_op_out_of_range_pairs_count_and_sentinel(eng):
+    """The pool's twin of the morphometry and texture tests of this name (the three kernels resolve a list entry through one helper,
+    csrc/nucleus_list.h): entries outside the batch give exact zero rows, rows from the device count on keep what they held."""
+    rng = np.random.default_rng(4)
+    B, K, H, W, strides = 2, 3, 64, 64, (2, 4, 8, 16)
+    maps = [rng.standard_normal((B, H // s, W // s, 64)).astype(np.float32) for s in strides]
+    assert [m.shape[1] for m in maps] == [32, 16, 8, 4]
+    masks = np.zeros((B, K, H, W), bool)
+    masks[0, 1, 5:21, 28:37] = True                                                   # crosses the word boundary at x = 32
+    masks[1, 2, 40:64, 50:64] = True                                                  # touches the right and the bottom edge
+    masks[0, 0, 1:9, 1:9] = True
+    masks[1, 0, 30:33, 2:60] = True
+    pairs = np.array([(0, 1), (B, 0), (1, 2), (0, -1), (0, 0), (1, 0)], np.int32)
+    n = 4
+    out = torch.full((len(pairs), 256), -7.5, dtype=torch.float32, device=eng.device)
+    eng.op_nucleus_pool([_dev(eng, m) for m in maps], strides, _dev(eng, nucfeat.pack_mask_words(masks)), _dev(eng, pairs),
+                        n=torch.tensor([n], dtype=torch.int32, device=eng.device), out=out)
+    got = out.cpu().numpy()
+    assert (got[n:] == -7.5).all()                                                    # rows 4 and 5: past the count, untouched
+    assert (got[[1, 3]] == 0).all()                                                   # tile = B, slot = -1: zero rows
+    worst = _check(got[[0, 2]], maps, strides, masks, pairs[[0, 2]], '64x64 at strides 2 / 4 / 8 / 16')
+    print(f'64 x 64, maps 32 / 16 / 8 / 4, rows 0 and 2 of {n}: largest error / bound {worst:.3f}')
+    assert np.abs(got[0]).max() > 0 and np.abs(got[2]).max() > 0
+
+
 def test_op_refuses_maps_that_do_not_cover_the_image(eng):
     from nuhtc_amd.engine import HipError
     rng = np.random.default_rng(2)

@@ -11,7 +11,6 @@ every step without embeddings, the other with (Engine.export_async(nucfeat=True)
                         1 KB per detection of the export capacity.
 bench.py (the detection path without any export) is the project's headline benchmark and is not changed by this tool."""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -31,7 +30,7 @@ def main(argv=None):
     ap.add_argument('--repeats', type=int, default=3)
     args = ap.parse_args(argv)
     import torch
-    from nuhtc_amd import hip, synth, weights
+    from nuhtc_amd import hip, nuclei, synth, weights
     from nuhtc_amd.engine import Engine
     if not torch.cuda.is_available():
         raise SystemExit('bench_nucfeat.py needs a GPU (there is no fallback)')
@@ -67,16 +66,12 @@ def main(argv=None):
     if g is None:
         raise SystemExit('the batch held more kept detections than the export buffers')
     d, cap = e._ex['dev'], e._ex['cap']
-    vp = lambda t: ctypes.c_void_p(t.data_ptr())
     kms = []
     with torch.cuda.stream(e.stream):
-        sp = ctypes.c_void_p(e.stream.cuda_stream)
         for i in range(12):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(e.stream)
-            rc = e.lib.nuhtc_nucleus_features(e.h, ctypes.byref(e.dets), B, vp(d['idx']), vp(d['nk']), cap, vp(d['feat']), sp)
-            if rc:
-                raise SystemExit(f'nuhtc_nucleus_features failed ({rc})')
+            e._nucleus_async(nuclei.FEAT, B, d['idx'], d['nk'], cap, [d['feat']])
             e1.record(e.stream)
             e.stream.synchronize()
             if i >= 2:

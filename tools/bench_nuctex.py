@@ -14,7 +14,6 @@ the same run, on the same kept masks: those kernels also scan one mask per workg
                         of the export capacity, the morphometry 1152, the embeddings 1024.
 bench.py (the detection path without any export) is the project's headline benchmark and is not changed by this tool."""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -34,7 +33,7 @@ def main(argv=None):
     ap.add_argument('--repeats', type=int, default=3)
     args = ap.parse_args(argv)
     import torch
-    from nuhtc_amd import hip, nucmorph, nuctex, synth, weights
+    from nuhtc_amd import hip, nuclei, nucmorph, nuctex, synth, weights
     from nuhtc_amd.engine import Engine
     if not torch.cuda.is_available():
         raise SystemExit('bench_nuctex.py needs a GPU (there is no fallback)')
@@ -66,8 +65,6 @@ def main(argv=None):
         for k in kinds:
             ms[k].append(1e3 * steps(k, args.steps) / args.steps)
     # ---- the kernels alone, on the last export of the engine that carries their rows
-    vp = lambda t: ctypes.c_void_p(t.data_ptr())
-
     def alone(k, call):
         e = engines[k]
         out = []
@@ -82,12 +79,12 @@ def main(argv=None):
                     out.append(e0.elapsed_time(e1))
         return out
 
-    def call_feat(e, d, cap):
-        e._check(e.lib.nuhtc_nucleus_features(e.h, ctypes.byref(e.dets), B, vp(d['idx']), vp(d['nk']), cap, vp(d['feat']), e._stream()))
+    def kernel(name, kind):
+        return alone(name, lambda e, d, cap: e._nucleus_async(kind, B, d['idx'], d['nk'], cap, [d[f] for f, _, _ in kind.fields]))
 
-    k_tex = alone('tex', lambda e, d, cap: e._nucleus_texture(B, vp(d['idx']), vp(d['nk']), cap, vp(d['tex'])))
-    k_morph = alone('morph', lambda e, d, cap: e._nucleus_morph(B, vp(d['idx']), vp(d['nk']), cap, vp(d['morph_raw']), vp(d['morph_hist'])))
-    k_feat = alone('feat', call_feat)
+    k_tex = kernel('tex', nuclei.TEX)
+    k_morph = kernel('morph', nuclei.MORPH)
+    k_feat = kernel('feat', nuclei.FEAT)
     g = {k: engines[k].export_read() for k in kinds}
     if any(v is None for v in g.values()):
         raise SystemExit('the batch held more kept detections than the export buffers')

@@ -1,5 +1,5 @@
-// Host check of the plain-C++ parts of the per-nucleus morphometry (nuhtc_amd/csrc/nucmorph_host.h: the limits of the entry points
-// and hull_chain2, the hull code the kernel runs), meant to be built with a sanitizer and run on the host -- it never touches a GPU:
+// Host check of the plain-C++ parts of the per-nucleus morphometry (nuhtc_amd/csrc/nucleus_list.h: the limits of the entry
+// points; nucmorph_host.h: hull_chain2, the hull code the kernel runs), meant to be built with a sanitizer and run on the host -- it never touches a GPU:
 //
 //   hipcc -x hip --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
 //         -I nuhtc_amd/csrc tools/dev/nucmorph_host_check.cpp -o /tmp/nucmorph_host_check && /tmp/nucmorph_host_check
@@ -63,7 +63,7 @@ int main() {
       {1, 1, 8, 8, 8, 0, 0, false},        {1, 1, 8, 8, 8, (1 << 24) + 1, 0, false},          {1, 1, 8, 8, 8, 1, 2, false},
       {1, 1, 8, 8, 8, 1, -1, false},       {-2147483647 - 1, 1, 8, 8, 8, 1, 0, false},        {1, 1, 2147483647, 2147483647, 2147483647, 1, 0, false}};
   for (const auto& c : cases)
-    if ((nucmorph_args_error(c.B, c.K, c.H, c.W, c.pitch, c.n, c.mode) == nullptr) != c.ok) { std::printf("FAIL limits B %d K %d H %d W %d\n", c.B, c.K, c.H, c.W); ++bad; }
+    if (nucleus_sizes_error("nucleus_morph", c.B, c.K, c.H, c.W, c.pitch, c.n, c.mode).empty() != c.ok) { std::printf("FAIL limits B %d K %d H %d W %d\n", c.B, c.K, c.H, c.W); ++bad; }
   // ---- the hull: designed rows, then random masks up to the largest frame
   bad += check_mask({{5}}, 3, "one pixel");
   bad += check_mask({{0}, {}, {}, {1023}}, 0, "two pixels, empty rows between");

@@ -1,5 +1,5 @@
-// Host check of the plain-C++ parts of the per-nucleus texture counts (nuhtc_amd/csrc/nuctex_host.h: the limits of the entry points and
-// nuctex_cell, the index the kernel adds at), meant to be built with a sanitizer and run on the host -- it never touches a GPU:
+// Host check of the plain-C++ parts of the per-nucleus texture counts (nuhtc_amd/csrc/nucleus_list.h: the limits of the entry points;
+// nuctex_host.h: nuctex_cell, the index the kernel adds at), meant to be built with a sanitizer and run on the host -- it never touches a GPU:
 //
 //   hipcc -x hip --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
 //         -I nuhtc_amd/csrc tools/dev/nuctex_host_check.cpp -o /tmp/nuctex_host_check && /tmp/nuctex_host_check
@@ -61,7 +61,7 @@ int main() {
       {1, 1, 8, 8, 8, 0, 0, false},        {1, 1, 8, 8, 8, (1 << 24) + 1, 0, false},          {1, 1, 8, 8, 8, 1, 2, false},
       {1, 1, 8, 8, 8, 1, -1, false},       {-2147483647 - 1, 1, 8, 8, 8, 1, 0, false},        {1, 1, 2147483647, 2147483647, 2147483647, 1, 0, false}};
   for (const auto& c : cases)
-    if ((nuctex_args_error(c.B, c.K, c.H, c.W, c.pitch, c.n, c.mode) == nullptr) != c.ok) { std::printf("FAIL limits B %d K %d H %d W %d\n", c.B, c.K, c.H, c.W); ++bad; }
+    if (nucleus_sizes_error("nucleus_texture", c.B, c.K, c.H, c.W, c.pitch, c.n, c.mode).empty() != c.ok) { std::printf("FAIL limits B %d K %d H %d W %d\n", c.B, c.K, c.H, c.W); ++bad; }
   // ---- the triangle index: every unordered pair of levels has its own cell, in row-major order, and none lies past the triangle
   {
     int next = 0;

@@ -120,21 +120,14 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
     """The reference's per-slide loop (:460-693): tiles -> detections -> per-tile filter + mask-NMS -> records -> the one gather ->
     rank 0 writes the documents.  The tile list is sharded in contiguous blocks over the ranks."""
     import torch
-    from nuhtc_amd import contours, parallel, wsi
+    from nuhtc_amd import contours, nuclei, parallel, wsi
     coords = bag.coords
     lo, hi = parallel.shard_range(len(bag), rank, world)
     tiles = bag.view(lo, hi)                                  # this rank's tiles only, cut / decoded a batch at a time while earlier batches run
     want = lambda m: args.mode in (m, 'all')
     rle_gpu = want('coco') and args.rle_on == 'gpu'                  # strings and boxes come off the device with the records (nuhtc_rle_encode)
-    nucfeat = bool(getattr(args, 'nuclei_feat', False))
-    nucmorph = bool(getattr(args, 'nuclei_morph', False))
-    more = dict(nucfeat=True) if nucfeat else {}
-    if nucmorph:
-        more['nucmorph'] = True
-    nuctex = bool(getattr(args, 'nuclei_texture', False))
-    if nuctex:
-        more['nuctex'] = True
-    rec = wsi.infer_tiles(model, tiles, coords[lo:hi], args.batch_size, rle=rle_gpu, **more)
+    sel = nuclei.select(**{k.keyword: getattr(args, k.cli, False) for k in nuclei.KINDS})     # the per-nucleus tables asked for
+    rec = wsi.infer_tiles(model, tiles, coords[lo:hi], args.batch_size, rle=rle_gpu, **nuclei.keywords(sel))
     # contours are traced on the rank that owns the tile; two variable-length gathers: records, then ring vertices
     rings = rec['ring']                                              # traced on the GPU (nuhtc_mask_contours)
     keep = [i for i, r in enumerate(rings) if len(r) >= 3]          # reference :536 tests the CLOSED contour (mask2inst appends the first point): only one-pixel contours go
@@ -163,9 +156,7 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
     # the one exchange of the path: every rank's records (head, ring vertices, mask crops, RLE strings) in a single all-gather
     dev = torch.device('cuda', local_rank) if world > 1 and torch.cuda.is_available() else torch.device('cpu')
     parts = wsi.pack_records(rec, keep, tile_base=lo, rles=rles)
-    tex_part = parts.pop() if nuctex else None                       # pack_records' last part, behind the morphometry
-    morph_part = parts.pop() if nucmorph else None                   # behind the embeddings
-    feat_part = parts.pop() if nucfeat else None                     # pack_records' sixth part: it travels behind the documents' parts
+    parts, row_parts = parts[:5], parts[5:]                          # one part per selected kind: they travel behind the documents' parts
     if want('qupath'):
         # every rank writes the GeoJSON text of ITS records (the reference's one Python loop over all nuclei, :533-585 + json.dump :659-664,
         # is seconds per slide on the writing rank); the bytes travel in the same gather and rank 0 only concatenates
@@ -173,15 +164,8 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
         lab = h0[:, 5].astype(np.int32)
         ptxt, pstart = contours.ring_features_text(v0, h0[:, 6].astype(np.int64), lab, h0[:, 4], model.CLASSES)
         parts += [torch.from_numpy(ptxt), torch.from_numpy(pstart), torch.from_numpy(contours.point_features_text(h0[:, :4], lab, h0[:, 4], model.CLASSES))]
-    feat_at = len(parts)
-    if nucfeat:                                                       # the embeddings of this rank's records: one more part of the same gather
-        parts.append(feat_part)
-    morph_at = len(parts)
-    if nucmorph:                                                      # and their morphometry integers
-        parts.append(morph_part)
-    tex_at = len(parts)
-    if nuctex:                                                        # and their co-occurrence counts
-        parts.append(tex_part)
+    rows_at = len(parts)                                              # the rows of this rank's records, kind by kind: more parts of the same gather
+    parts += row_parts
     if rle_gpu:                                                       # bbox / area of the annotations: rank 0 parses no string
         kp = np.asarray(keep, np.int64)
         parts.append(torch.from_numpy(np.ascontiguousarray(rec['rle_bbox'][kp], np.int32)))
@@ -242,31 +226,16 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
             outputs.write_text_list(os.path.join(out_dir, name + '_merged.geojson'), contours.join_features_text(body, start, kept))
             msg += f', {len(kept)} after the cross-tile merge'
             feat_rows = np.asarray(kept, np.int64)
-    if nucfeat:
-        from nuhtc_amd import nucfeat as nf
-        hall = np.concatenate([h.cpu().numpy() for h in heads], 0)
-        rows = np.arange(n_records, dtype=np.int64) if feat_rows is None else feat_rows
-        nf.write_npz(os.path.join(out_dir, name + '_nuclei_feat.npz'), rows, wsi.gathered_features(gathered, rows, part=feat_at),
-                     hall[rows, 5].astype(np.int64), hall[rows, 4])
-        msg += f', {len(rows)} embeddings in {name}_nuclei_feat.npz'
-    if nucmorph:
-        from nuhtc_amd import nucmorph as nm
+    graph = getattr(args, 'nuclei_graph', False)
+    if sel or graph:                                                  # the rows of the per-nucleus files, and their labels and scores
         hall = np.concatenate([h.cpu().numpy() for h in heads], 0).reshape(-1, 9)
         rows = np.arange(n_records, dtype=np.int64) if feat_rows is None else feat_rows
-        raw, hist, origin = nm.unpack_rows(wsi.gathered_morph(gathered, rows, part=morph_at))
-        nm.write_npz(os.path.join(out_dir, name + '_nuclei_morph.npz'), rows, raw, hist, hall[rows, 5].astype(np.int64), hall[rows, 4], origin)
-        msg += f', {len(rows)} rows of {len(nm.COLUMNS)} features in {name}_nuclei_morph.npz'
-    if nuctex:
-        from nuhtc_amd import nuctex as nt
-        hall = np.concatenate([h.cpu().numpy() for h in heads], 0).reshape(-1, 9)
-        rows = np.arange(n_records, dtype=np.int64) if feat_rows is None else feat_rows
-        nt.write_npz(os.path.join(out_dir, name + '_nuclei_texture.npz'), rows, nt.unpack_rows(wsi.gathered_texture(gathered, rows, part=tex_at)),
-                     hall[rows, 5].astype(np.int64), hall[rows, 4])
-        msg += f', {len(rows)} rows of {len(nt.COLUMNS)} features in {name}_nuclei_texture.npz'
-    if getattr(args, 'nuclei_graph', False):                          # the edges to those rows: only what the gather already delivered
+    for i, kind in enumerate(sel):
+        kind.write(os.path.join(out_dir, name + kind.suffix), rows, wsi.gathered_rows(kind, gathered, rows, part=rows_at + i),
+                   hall[rows, 5].astype(np.int64), hall[rows, 4])
+        msg += f', {len(rows)} {kind.said} in {name}{kind.suffix}'
+    if graph:                                                         # the edges to those rows: only what the gather already delivered
         from nuhtc_amd import cellgraph
-        hall = np.concatenate([h.cpu().numpy() for h in heads], 0).reshape(-1, 9)
-        rows = np.arange(n_records, dtype=np.int64) if feat_rows is None else feat_rows
         boxes, lab = hall[rows, :4], hall[rows, 5].astype(np.int64)
         nb, d2, cc = cellgraph.build(cellgraph.quantize_centres(boxes), lab, len(model.CLASSES), args.graph_radius, args.graph_k,
                                      device=local_rank if world > 1 else (torch.device(args.device).index or 0))
