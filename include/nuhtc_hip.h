@@ -834,6 +834,27 @@ int nuhtc_op_nucleus_texture(nuhtc_engine* e, const uint8_t* tiles, int channel_
                              const uint32_t* masks, int K, int H, int W, const int32_t* pairs_dev, const int32_t* n_dev, int n_max,
                              int32_t* tex, void* stream);
 
+/* Nuclei of a WRITTEN GeoJSON in front of the two measurement ops above (csrc/ringfeat.hip; nuhtc_amd/ringfeat.py, tools/wsi_feat_extract.py):
+ * every nucleus gets a square frame of side S (32, 64, 128 or 256) whose pixel (0, 0) is the slide pixel origin[i] = (x, y); the masks and
+ * frames below are what nuhtc_op_nucleus_morph / nuhtc_op_nucleus_texture read with B = n, K = 1, H = W = S and the pairs (i, 0).
+ * Engine-free: every pointer is device memory of `device`; each call enqueues ONE launch on `stream` and does not synchronise.
+ * nuhtc_config is unchanged (no ABI bump).
+ * nuhtc_op_ring_fill: verts [nv][2] int32 slide pixels, ring i = the vertices [ring_off[i], ring_off[i + 1]) (ring_off int64 [n + 1]), the
+ *   closing vertex NOT repeated; origin int32 [n][2].  masks [n][S][S / 32] uint32, bit x & 31 of word x >> 5: the pixels inside or on the
+ *   ring, the set nuhtc_fill_rings defines (the border drawn by integer steps along every edge; outside = everything 4-reachable from
+ *   beyond the frame without stepping on the border; the mask is everything else -- holes filled, a region a ring winds round twice
+ *   inside), bit for bit.  status int32 [n]: 0 = filled; 1 = a vertex lies outside the frame; 2 = an edge is off the eight chain
+ *   directions (not a traced ring), or the ring has no vertex or leaves [0, nv).  With a status other than 0 the mask is all zeros.
+ *   A call writes the masks and statuses of its n rings and nothing else; the same input gives the same bits on every call.
+ * nuhtc_op_frame_gather: block [bh][bw][3] uint8, a part of the slide whose pixel (0, 0) is the slide pixel (bx, by); the same origin
+ *   array.  frames [n][S][S][3] uint8 (4-byte aligned): the frame at origin[i], 0 where it leaves the block.
+ * NUHTC_E_INVALID, before anything is launched: a null pointer, S not one of the four sides, n outside 1 .. 4096 (the measurement ops'
+ * limit on B), nv < 1, bh or bw outside 1 .. 32768. */
+int nuhtc_op_ring_fill(int device, const int32_t* verts, int64_t nv, const int64_t* ring_off, const int32_t* origin, int n, int S,
+                       uint32_t* masks, int32_t* status, void* stream);
+int nuhtc_op_frame_gather(int device, const uint8_t* block, int bh, int bw, int bx, int by, const int32_t* origin, int n, int S,
+                          uint8_t* frames, void* stream);
+
 /* Cell graph of a slide (csrc/cellgraph.hip; nuhtc_amd/cellgraph.py has the definition and its brute-force int64 restatement `graph_reference`):
  * for every nucleus its k nearest nuclei within a radius, and the class census of that disc.  Not in the reference.  Engine-free like
  * nuhtc_merge_overlap: every pointer is device memory of `device`, the call allocates and frees its own scratch, runs on `stream` and

@@ -1,0 +1,364 @@
+"""Per-nucleus feature table from a WRITTEN GeoJSON: the reference's tools/wsi_feat_extract.py (one crop per nucleus, the polygon filled
+into a mask, histomicstk on a CPU pool, an SQLite table `nuclei_features`) on the GPU.  The measurements are the project's existing
+ones -- nuhtc_op_nucleus_morph and nuhtc_op_nucleus_texture, nucmorph.derive and nuctex.derive, all unchanged; this module is the path
+in front of them and behind them:
+
+    parse      GeoJSON features -> integer rings, rectangles, scores, labels, class names, nuclei_id
+    measure    the slide in blocks, per block and frame size: nuhtc_op_frame_gather (slide pixels -> one frame per nucleus),
+               nuhtc_op_ring_fill (ring -> bit mask, csrc/ringfeat.hip), the two measurement ops -> raw, hist, glcm (integers)
+    table      nucmorph.derive beside nuctex.derive -> the named float64 columns
+    write_db / read_db / missing_ids     the SQLite file and the reference's resume rule
+
+What is measured is the nucleus the DOCUMENT describes: the traced ring with its holes filled (contours.fill_rings defines the pixel set;
+the device equals it bit for bit), independent of the tile frames of the run that wrote it.  Only traced rings are measured -- integer
+vertices, edges along the eight chain directions: what tools/infer_wsi.py writes, here and in the reference.  Anything else is left out
+and counted by reason (REASONS).  Level 0 only: rings are level-0 coordinates.
+
+A nucleus's frame is the square of side S = 32, 64, 128 or 256 (the smallest that holds its rectangle) whose corner is the rectangle's
+minimum corner; raw is in frame pixels and `origin` is that corner, which derive needs for the Identifier.* columns (slide pixels).
+
+The measurement ops want an engine handle, but not a finalized one: nuhtc_create validates the config and allocates NOTHING on the
+device (every allocation is nuhtc_finalize's), so measure() makes a handle from the default config, never finalizes it, and destroys it
+on the way out.  No config file, no checkpoint."""
+import ctypes
+import os
+import sqlite3
+
+import numpy as np
+
+from . import nucmorph, nuctex
+
+SIDES = (32, 64, 128, 256)
+MAX_SIDE = SIDES[-1]
+HALO = MAX_SIDE                 # a block is read with this many pixels to the right and below: a frame never leaves its block's read
+CHUNK = 4096                    # the measurement ops' limit on B
+REASONS = ('non_integer', 'no_ring', 'too_large', 'off_slide', 'not_traced')
+TABLE = 'nuclei_features'
+DB_NAME = 'nuclei_feat.db'
+
+
+def bucket(side):
+    """The frame side of a rectangle whose larger side is `side` pixels (1 .. 256)."""
+    for s in SIDES:
+        if side <= s:
+            return s
+    raise ValueError(f'a rectangle of side {side} has no frame (at most {MAX_SIDE})')
+
+
+def parse(features):
+    """GeoJSON features -> dict(rings: list of int32 (k, 2) without the closing vertex, rect int64 (n, 4) = x_min, y_min, x_max, y_max
+    of the vertices (inclusive), score float64 (n,), label int64 (n,), type: list of str, nuclei_id int64 (n,), left_out: {reason:
+    count}).  One entry per Polygon feature that can be measured; nuclei_id is properties.nuclei_id where present, the feature's
+    position in the list otherwise.  Left out and counted: 'non_integer' (a coordinate that is not an integer), 'no_ring' (no ring,
+    or a ring without a vertex), 'too_large' (a rectangle wider or taller than 256 pixels).  A feature that is no Polygon is skipped
+    without a count."""
+    left = {r: 0 for r in REASONS}
+    rings, rect, score, label, kind, ids = [], [], [], [], [], []
+    for pos, f in enumerate(features):
+        geom = f.get('geometry') or {}
+        if geom.get('type') != 'Polygon':
+            continue
+        coords = geom.get('coordinates') or []
+        try:
+            r = np.asarray(coords[0], np.float64) if len(coords) else np.zeros((0, 2))
+        except (TypeError, ValueError):
+            r = np.zeros((0, 2))
+        if r.ndim != 2 or r.shape[1] != 2 or len(r) == 0:
+            left['no_ring'] += 1
+            continue
+        if not np.isfinite(r).all() or not np.array_equal(r, np.rint(r)) or np.abs(r).max() >= 2 ** 30:
+            left['non_integer'] += 1
+            continue
+        r = r.astype(np.int64)
+        if len(r) > 1 and (r[0] == r[-1]).all():
+            r = r[:-1]
+        x0, y0, x1, y1 = int(r[:, 0].min()), int(r[:, 1].min()), int(r[:, 0].max()), int(r[:, 1].max())
+        if x1 - x0 + 1 > MAX_SIDE or y1 - y0 + 1 > MAX_SIDE:
+            left['too_large'] += 1
+            continue
+        props = f.get('properties') or {}
+        rings.append(np.ascontiguousarray(r, np.int32))
+        rect.append((x0, y0, x1, y1))
+        score.append(float(props.get('score', 0.0)))
+        label.append(int(props.get('label', 0)))
+        kind.append(str((props.get('classification') or {}).get('name', '')))
+        ids.append(int(props['nuclei_id']) if 'nuclei_id' in props else pos)
+    return dict(rings=rings, rect=np.asarray(rect, np.int64).reshape(-1, 4), score=np.asarray(score, np.float64),
+                label=np.asarray(label, np.int64), type=kind, nuclei_id=np.asarray(ids, np.int64), left_out=left)
+
+
+def frame_sides(rect):
+    """rect int (n, 4) -> int64 (n,): the frame side of every rectangle."""
+    rect = np.asarray(rect, np.int64).reshape(-1, 4)
+    side = np.maximum(rect[:, 2] - rect[:, 0], rect[:, 3] - rect[:, 1]) + 1
+    return np.array([bucket(int(s)) for s in side], np.int64)
+
+
+def block_plan(rect, slide_hw, block=2048):
+    """The walk of measure(): -> (blocks, off_slide).  blocks: list of (x, y, w, h, idx) -- the part of the slide [x, x + w) x [y, y + h)
+    that is read for the block (`block` pixels and a 256-pixel halo to the right and below, cut at the slide's edge) and the rows idx of
+    `rect` it owns, row-major over the blocks that own any.  A nucleus belongs to the block that holds its rectangle's minimum corner;
+    its rectangle is at most 256 pixels wide and tall, so it lies inside what the block reads.  off_slide: the rows whose rectangle
+    leaves the slide (owned by no block)."""
+    rect = np.asarray(rect, np.int64).reshape(-1, 4)
+    H, W = int(slide_hw[0]), int(slide_hw[1])
+    block = int(block)
+    if block < 1:
+        raise ValueError('block_plan: block must be positive')
+    inside = (rect[:, 0] >= 0) & (rect[:, 1] >= 0) & (rect[:, 2] < W) & (rect[:, 3] < H)
+    idx = np.nonzero(inside)[0]
+    key = (rect[idx, 1] // block) * ((W + block - 1) // block + 1) + rect[idx, 0] // block
+    order = np.argsort(key, kind='stable')
+    blocks = []
+    for k in np.unique(key):
+        own = idx[order[np.searchsorted(key[order], k, 'left'):np.searchsorted(key[order], k, 'right')]]
+        bx, by = int(rect[own[0], 0] // block) * block, int(rect[own[0], 1] // block) * block
+        blocks.append((bx, by, min(block + HALO, W - bx), min(block + HALO, H - by), own))
+    return blocks, np.nonzero(~inside)[0]
+
+
+def _slide_hw(slide):
+    if hasattr(slide, 'read_region'):
+        w, h = slide.dimensions if hasattr(slide, 'dimensions') else slide.level_dimensions[0]
+        return int(h), int(w)
+    return int(slide.shape[0]), int(slide.shape[1])
+
+
+def read_block(slide, x, y, w, h):
+    """(h, w, 3) uint8 RGB, contiguous: level 0 of the slide at (x, y) -- an array slide is sliced, anything with read_region is asked."""
+    if hasattr(slide, 'read_region'):
+        a = slide.read_region((int(x), int(y)), 0, (int(w), int(h)))
+        if hasattr(a, 'convert'):
+            a = a.convert('RGB')
+        a = np.asarray(a)
+    else:
+        a = slide[y:y + h, x:x + w]
+    a = np.ascontiguousarray(np.asarray(a)[..., :3], np.uint8)
+    if not a.flags.writeable:              # a whole row band of a read-only memory map is contiguous as it is: the upload wants its own copy
+        a = a.copy()
+    if a.shape != (h, w, 3):
+        raise ValueError(f'the slide gave {a.shape} for a {h} x {w} block')
+    return a
+
+
+class _Ops:
+    """The four device steps on torch tensors of one device: the two kernels of csrc/ringfeat.hip (engine-free) and the two measurement
+    ops behind a never-finalized engine handle (module docstring)."""
+
+    def __init__(self, device=0):
+        import torch
+        from . import hip
+        if not torch.cuda.is_available():
+            raise RuntimeError('no HIP device visible: the per-nucleus measurements have no CPU path')
+        self.torch, self.hip, self.lib = torch, hip, hip.load()
+        self.index = device if isinstance(device, int) else (torch.device(device).index or 0)
+        self.device = torch.device('cuda', self.index)
+        cfg = hip.default_config()
+        self.h = ctypes.c_void_p()
+        rc = self.lib.nuhtc_create(ctypes.byref(cfg), self.index, ctypes.byref(self.h))
+        if rc:
+            raise RuntimeError(f'nuhtc_create failed ({rc}): {self.lib.nuhtc_last_error(None).decode()}')
+        lut, k = nucmorph.stain_constants()
+        self.lut = torch.from_numpy(lut).to(self.device)
+        self.k = (ctypes.c_int32 * 3)(*[int(v) for v in k])
+
+    def close(self):
+        if self.h:
+            self.lib.nuhtc_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _stream(self):
+        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _need(self, t, dtype, what):
+        if t.device != self.device or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f'{what}: a contiguous {dtype} tensor on {self.device}')
+        return ctypes.c_void_p(t.data_ptr())
+
+    def gather(self, block, bx, by, origin, S):
+        """block uint8 (bh, bw, 3) whose pixel (0, 0) is the slide pixel (bx, by), origin int32 (n, 2) -> frames uint8 (n, S, S, 3)."""
+        t = self.torch
+        n = int(origin.shape[0])
+        frames = t.empty(n, S, S, 3, dtype=t.uint8, device=self.device)
+        rc = self.lib.nuhtc_op_frame_gather(self.index, self._need(block, t.uint8, 'block'), int(block.shape[0]), int(block.shape[1]), int(bx), int(by),
+                                            self._need(origin, t.int32, 'origin'), n, int(S), ctypes.c_void_p(frames.data_ptr()), self._stream())
+        if rc:
+            raise RuntimeError(f'nuhtc_op_frame_gather failed ({rc})')
+        return frames
+
+    def fill(self, verts, ring_off, origin, S):
+        """verts int32 (nv, 2), ring_off int64 (n + 1,), origin int32 (n, 2) -> (masks int32 (n, S, S // 32), status int32 (n,))."""
+        t = self.torch
+        n = int(origin.shape[0])
+        masks = t.empty(n, S, S // 32, dtype=t.int32, device=self.device)
+        status = t.empty(n, dtype=t.int32, device=self.device)
+        if int(ring_off.shape[0]) != n + 1:
+            raise ValueError('fill: ring_off has one entry more than origin has rows')
+        rc = self.lib.nuhtc_op_ring_fill(self.index, self._need(verts, t.int32, 'verts'), int(verts.shape[0]), self._need(ring_off, t.int64, 'ring_off'),
+                                         self._need(origin, t.int32, 'origin'), n, int(S), ctypes.c_void_p(masks.data_ptr()),
+                                         ctypes.c_void_p(status.data_ptr()), self._stream())
+        if rc:
+            raise RuntimeError(f'nuhtc_op_ring_fill failed ({rc})')
+        return masks, status
+
+    def _fail(self, name, rc):
+        raise RuntimeError(f'{name} failed ({rc}): {self.lib.nuhtc_last_error(self.h).decode()}')
+
+    def morph_tex(self, frames, masks):
+        """frames uint8 (n, S, S, 3), masks int32 (n, S, S // 32) -> (raw int64 (n, 16), hist int32 (n, 256), glcm int32 (n, 2, 136)):
+        the two measurement ops with B = n, K = 1 and the pairs (i, 0)."""
+        t = self.torch
+        n, S = int(frames.shape[0]), int(frames.shape[1])
+        pairs = t.zeros(n, 2, dtype=t.int32, device=self.device)
+        pairs[:, 0] = t.arange(n, dtype=t.int32, device=self.device)
+        raw = t.empty(n, nucmorph.RAW, dtype=t.int64, device=self.device)
+        hist = t.empty(n, nucmorph.BINS, dtype=t.int32, device=self.device)
+        glcm = t.empty(n, len(nuctex.OFFSETS), nuctex.CELLS, dtype=t.int32, device=self.device)
+        vp = lambda x: ctypes.c_void_p(x.data_ptr())
+        rc = self.lib.nuhtc_op_nucleus_morph(self.h, vp(frames), self.hip.CH_AS_IS, vp(self.lut), self.k, n, vp(masks), 1, S, S, vp(pairs), None, n,
+                                             vp(raw), vp(hist), self._stream())
+        if rc:
+            self._fail('nuhtc_op_nucleus_morph', rc)
+        rc = self.lib.nuhtc_op_nucleus_texture(self.h, vp(frames), self.hip.CH_AS_IS, vp(self.lut), self.k, n, vp(masks), 1, S, S, vp(pairs), None, n,
+                                               vp(glcm), self._stream())
+        if rc:
+            self._fail('nuhtc_op_nucleus_texture', rc)
+        return raw, hist, glcm
+
+
+def pack_rings(rings):
+    """list of (k, 2) integer rings -> (verts int32 (sum k, 2), ring_off int64 (n + 1,))."""
+    lens = np.array([len(r) for r in rings], np.int64)
+    verts = np.ascontiguousarray(np.concatenate([np.asarray(r, np.int32).reshape(-1, 2) for r in rings], 0)) if len(rings) else np.zeros((0, 2), np.int32)
+    return verts, np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+
+
+def measure(slide, features, device=0, block=2048, timings=None):
+    """slide: an (H, W, 3) uint8 RGB array (a memory-mapped .npy slide) or anything with read_region (level 0 is read); features: GeoJSON
+    features, or the result of parse().  The slide is walked in blocks of `block` pixels (block_plan): every block that owns a nucleus is
+    read once and uploaded once, and per block and frame side, in chunks of at most 4096 nuclei, the gather, the ring fill and the two
+    measurement ops run on the device.  -> dict(raw int64 (n, 16), hist int32 (n, 256), glcm int32 (n, 2, 136), origin int64 (n, 2), rect,
+    score, label, type, nuclei_id, left_out) for the n measured nuclei, in the order of the features.  left_out counts parse()'s reasons,
+    'off_slide' (the rectangle leaves the slide) and 'not_traced' (the ring fill's status 2: an edge off the chain directions).
+    `timings`: a dict that receives the seconds spent in read, upload, gather, fill and measure (each stage synchronised: for
+    tools/bench_ringfeat.py)."""
+    import time
+    import torch
+    p = features if isinstance(features, dict) and 'rings' in features else parse(features)
+    left = dict(p['left_out'])
+    n = len(p['rings'])
+    rect = p['rect']
+    raw, hist = np.zeros((n, nucmorph.RAW), np.int64), np.zeros((n, nucmorph.BINS), np.int32)
+    glcm = np.zeros((n, len(nuctex.OFFSETS), nuctex.CELLS), np.int32)
+    keep = np.zeros(n, bool)
+    blocks, off = block_plan(rect, _slide_hw(slide), block)
+    left['off_slide'] += len(off)
+    sides = frame_sides(rect) if n else np.zeros(0, np.int64)
+
+    def lap(name, t0):
+        if timings is not None:
+            torch.cuda.synchronize(ops.device)
+            timings[name] = timings.get(name, 0.0) + time.perf_counter() - t0
+        return time.perf_counter()
+
+    with _Ops(device) as ops, torch.cuda.device(ops.device):
+        for bx, by, bw, bh, own in blocks:
+            t0 = time.perf_counter()
+            host = read_block(slide, bx, by, bw, bh)
+            t0 = lap('read', t0)
+            dev = torch.from_numpy(host).to(ops.device)
+            t0 = lap('upload', t0)
+            for S in SIDES:
+                mine = own[sides[own] == S]
+                for c0 in range(0, len(mine), CHUNK):
+                    idx = mine[c0:c0 + CHUNK]
+                    verts, ring_off = pack_rings([p['rings'][i] for i in idx])
+                    origin = torch.from_numpy(np.ascontiguousarray(rect[idx, :2], np.int32)).to(ops.device)
+                    verts_d, off_d = torch.from_numpy(verts).to(ops.device), torch.from_numpy(ring_off).to(ops.device)
+                    t0 = time.perf_counter()
+                    frames = ops.gather(dev, bx, by, origin, S)
+                    t0 = lap('gather', t0)
+                    masks, status = ops.fill(verts_d, off_d, origin, S)
+                    t0 = lap('fill', t0)
+                    r, h, g = ops.morph_tex(frames, masks)
+                    t0 = lap('measure', t0)
+                    st = status.cpu().numpy()
+                    if (st == 1).any():
+                        raise RuntimeError('ring fill: a vertex outside its own frame (the frame is the rectangle of the vertices: this cannot happen)')
+                    ok = st == 0
+                    left['not_traced'] += int((~ok).sum())
+                    raw[idx], hist[idx], glcm[idx], keep[idx] = r.cpu().numpy(), h.cpu().numpy(), g.cpu().numpy(), ok
+    sel = np.nonzero(keep)[0]
+    return dict(raw=raw[sel], hist=hist[sel], glcm=glcm[sel], origin=rect[sel, :2].copy(), rect=rect[sel], score=p['score'][sel], label=p['label'][sel],
+                type=[p['type'][i] for i in sel], nuclei_id=p['nuclei_id'][sel], left_out=left)
+
+
+def table(m):
+    """measure()'s result -> (columns, float64 (n, 55)): nucmorph.derive(raw, hist, origin) beside nuctex.derive(glcm)."""
+    c1, v1 = nucmorph.derive(m['raw'], m['hist'], m['origin'])
+    c2, v2 = nuctex.derive(m['glcm'])
+    return tuple(c1) + tuple(c2), np.concatenate([v1, v2], 1)
+
+
+def db_columns():
+    """[(name, SQLite type)] of the table `nuclei_features`, in order: Label (always 1, as histomicstk labels a one-nucleus crop), the 29
+    nucmorph.COLUMNS and the 26 nuctex.COLUMNS (REAL; every '.' of a name replaced by '_', as the reference does before to_sql), score,
+    type, class_id, nuclei_id, and the vertex extremes x_min, y_min, x_max, y_max."""
+    cols = [('Label', 'INTEGER')] + [(c.replace('.', '_'), 'REAL') for c in nucmorph.COLUMNS + nuctex.COLUMNS]
+    return cols + [('score', 'REAL'), ('type', 'TEXT'), ('class_id', 'INTEGER'), ('nuclei_id', 'INTEGER'),
+                   ('x_min', 'INTEGER'), ('y_min', 'INTEGER'), ('x_max', 'INTEGER'), ('y_max', 'INTEGER')]
+
+
+def write_db(path, values, score, kind, class_id, nuclei_id, rect):
+    """Appends one row per nucleus to the table nuclei_features of the SQLite file `path` (created with db_columns() when missing):
+    values float (n, 55) = table()[1].  A file of any size is kept -- the reference deletes a database under 1 MB as broken; a complete
+    small table is complete.  -> the number of rows written."""
+    values = np.asarray(values, np.float64).reshape(-1, len(nucmorph.COLUMNS) + len(nuctex.COLUMNS))
+    rect = np.asarray(rect, np.int64).reshape(-1, 4)
+    n = len(values)
+    if not (len(score) == len(kind) == len(class_id) == len(nuclei_id) == len(rect) == n):
+        raise ValueError('write_db: one row per nucleus in every field')
+    cols = db_columns()
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    conn = sqlite3.connect(path)
+    try:
+        conn.execute(f'CREATE TABLE IF NOT EXISTS {TABLE} ({", ".join(f"{c} {t}" for c, t in cols)})')
+        rows = [(1, *map(float, values[i]), float(score[i]), str(kind[i]), int(class_id[i]), int(nuclei_id[i]), *map(int, rect[i])) for i in range(n)]
+        conn.executemany(f'INSERT INTO {TABLE} ({", ".join(c for c, _ in cols)}) VALUES ({", ".join("?" * len(cols))})', rows)
+        conn.commit()
+    finally:
+        conn.close()
+    return n
+
+
+def read_db(path):
+    """-> dict(columns: [(name, type)], rows: list of tuples in rowid order) of the table nuclei_features; None when the file or the table
+    does not exist."""
+    if not os.path.exists(path):
+        return None
+    conn = sqlite3.connect(path)
+    try:
+        info = conn.execute(f'PRAGMA table_info({TABLE})').fetchall()
+        if not info:
+            return None
+        return dict(columns=[(r[1], r[2]) for r in info], rows=conn.execute(f'SELECT * FROM {TABLE} ORDER BY rowid').fetchall())
+    finally:
+        conn.close()
+
+
+def missing_ids(path, nuclei_id):
+    """The reference's resume rule: the ids of `nuclei_id` that the table of `path` does not hold yet, in their order (all of them when
+    there is no table; none when it holds every one: the slide is done)."""
+    ids = [int(i) for i in nuclei_id]
+    got = read_db(path)
+    if got is None:
+        return ids
+    at = [c for c, _ in got['columns']].index('nuclei_id')
+    have = {r[at] for r in got['rows']}
+    return [i for i in ids if i not in have]

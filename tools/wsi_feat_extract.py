@@ -1,0 +1,123 @@
+#!/usr/bin/env python
+"""Same command line as the reference's tools/wsi_feat_extract.py: a per-nucleus feature table for every slide of a folder, from the
+GeoJSON a detection run wrote, into <segdir>/<id>/nuclei_feat.db (SQLite, one table `nuclei_features`).
+
+    python tools/wsi_feat_extract.py DATADIR --segdir SEGDIR [--start 0] [--end N] [--mag 40] [--reverse] [--bs_size 1024]
+                                     [--num_workers 8] [--slide_ext .svs] [--geojson merged|plain] [--device 0]
+
+For every slide id (the sorted, extension-stripped names in DATADIR, sliced as the reference slices them) it reads
+<segdir>/<id>/<id>_merged.geojson (`--geojson plain`: <id>.geojson, whose nuclei_id is the position in the file), opens the slide as
+tools/infer_wsi.py does (`.npy` array slides, tiled `.tif` / `.svs`) and measures every nucleus ON THE GPU (nuhtc_amd/ringfeat.py: the
+slide is walked in blocks, frames are gathered and rings filled on the device, then the project's morphometry and texture kernels run).
+There is no fallback without a GPU.  A slide without its GeoJSON is reported and skipped.
+
+The table: Label (always 1), the 29 columns of nuhtc_amd/nucmorph.py and the 26 of nuhtc_amd/nuctex.py ('.' replaced by '_', as the
+reference does), score, type, class_id, nuclei_id, x_min, y_min, x_max, y_max (the vertex extremes).  What those modules state holds here:
+  * the intensity scale (Nucleus.Intensity.*) and the grey levels (Haralick.*) are THE PROJECT'S OWN fixed-point haematoxylin scale, not
+    histomicstk's 8-bit stain image and crop-dependent grey limits: the columns have histomicstk's names and meaning, not its numbers;
+  * Identifier.* are slide pixels at level 0;
+  * histomicstk's FSD, gradient, Hu-moment and fractal-dimension columns are not produced.
+Only TRACED RINGS are measured -- integer vertices on pixel centres, edges along the eight chain directions: what tools/infer_wsi.py
+writes, here and in the reference.  The measured pixels are the ring's border and everything it encloses (holes filled).  Arbitrary
+polygons (float coordinates, other edge directions), nuclei wider or taller than 256 pixels and rings that leave the slide are left out
+and counted; the closing line on stderr gives, per slide, the rows written and the rows left out by reason.
+
+Resume, as the reference: a database that already holds every nuclei_id of the file skips the slide; otherwise only the missing nuclei
+are measured and appended.  NOT as the reference: a database under 1 MB is kept -- the reference deletes it as broken, but a complete
+small table is complete.
+
+--mag is accepted for parity.  Rings are level-0 coordinates and are measured in level-0 pixels at every magnification (the reference
+upsamples its crops by 40 / mag first); with --mag other than 40 that is said once on stderr.  --bs_size and --num_workers are accepted
+and not used: batches are the blocks of the slide walk, and there is no worker pool."""
+import json
+import os
+import sys
+from argparse import ArgumentParser
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def build_parser():
+    """tools/wsi_feat_extract.py:239-250 of the reference, then three flags of our own."""
+    p = ArgumentParser(allow_abbrev=False)
+    p.add_argument('datadir', help='path to folder containing raw wsi image files')
+    p.add_argument('--segdir', help='path to folder containing segmentation files')
+    p.add_argument('--start', type=int, default=0, help='start index')
+    p.add_argument('--end', type=int, default=None, help='end index')
+    p.add_argument('--mag', type=int, default=40, help='magnification of the slide')
+    p.add_argument('--reverse', action='store_true', default=False, help='reverse the order of slide ids')
+    p.add_argument('--bs_size', type=int, default=1024, help='batch size for nuclei feature extraction')
+    p.add_argument('--num_workers', type=int, default=8, help='number of workers for parallel processing')
+    # ---- not in the reference
+    p.add_argument('--slide_ext', type=str, default='.svs', help='ext name of wsi (.svs, .tif, .npy)')
+    p.add_argument('--geojson', choices=('merged', 'plain'), default='merged', help='<id>_merged.geojson or <id>.geojson')
+    p.add_argument('--device', type=int, default=0, help='GPU of the measurement')
+    return p
+
+
+def parse_args(argv=None):
+    return build_parser().parse_args(argv)
+
+
+def slide_ids(datadir, start=0, end=None, reverse=False):
+    """tools/wsi_feat_extract.py:132-141 of the reference: sorted, extension-stripped names, reversed first and sliced after."""
+    ids = sorted(os.path.splitext(name)[0] for name in os.listdir(datadir))
+    if reverse:
+        ids = ids[::-1]
+    return ids[start:end] if end is not None else ids[start:]
+
+
+def extract_slide(slide_path, geojson_path, db_path, device=0, log=print):
+    """One slide -> (rows written, {reason: left out}), or None when the table already holds every nucleus of the file."""
+    from nuhtc_amd import ringfeat, slides
+    with open(geojson_path) as f:
+        features = json.load(f)
+    every = [int(f['properties']['nuclei_id']) if 'nuclei_id' in (f.get('properties') or {}) else k for k, f in enumerate(features)]
+    todo = set(ringfeat.missing_ids(db_path, every))
+    if not todo:
+        return None
+    if len(todo) < len(every):
+        log(f'skipped {len(every) - len(todo)}/{len(every)} nuclei')
+        log(f'left {len(todo)} nuclei')
+    # only the missing nuclei are measured, each under the id it has in the whole file (a nucleus left out before is tried, and left
+    # out, again)
+    features = [dict(f, properties=dict(f.get('properties') or {}, nuclei_id=i)) for f, i in zip(features, every) if i in todo]
+    m = ringfeat.measure(slides.open_array_slide(slide_path), features, device=device)
+    _, values = ringfeat.table(m)
+    n = ringfeat.write_db(db_path, values, m['score'], m['type'], m['label'], m['nuclei_id'], m['rect'])
+    return n, m['left_out']
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit('wsi_feat_extract.py needs a GPU (there is no fallback)')
+    if args.mag != 40:
+        print(f'--mag {args.mag}: rings are level-0 coordinates and are measured in level-0 pixels; the reference would upsample every crop by '
+              f'{40 / args.mag:g} first, this tool does not', file=sys.stderr)
+    ids = slide_ids(args.datadir, args.start, args.end, args.reverse)
+    suffix = '_merged.geojson' if args.geojson == 'merged' else '.geojson'
+    report = []
+    for k, sid in enumerate(ids):
+        print(f'\n[{k + 1}/{len(ids)}]process: {sid}')
+        gj = os.path.join(args.segdir, sid, sid + suffix)
+        if not os.path.exists(gj):
+            print(f'not found {sid}, skipped\n')
+            continue
+        spath = os.path.join(args.datadir, sid + args.slide_ext)
+        if not os.path.exists(spath):
+            print(f'no slide {spath}, skipped\n')
+            continue
+        got = extract_slide(spath, gj, os.path.join(args.segdir, sid, 'nuclei_feat.db'), device=args.device)
+        if got is None:
+            print(f'skipped:{sid}\n')
+            continue
+        n, left = got
+        print(f'{sid}: {n} rows')
+        report.append(f'{sid}: {n} rows written, left out ' + (', '.join(f'{v} {r}' for r, v in left.items() if v) or 'none'))
+    print('; '.join(report) if report else 'no slide measured', file=sys.stderr)
+
+
+if __name__ == '__main__':
+    main()
