@@ -834,6 +834,24 @@ int nuhtc_op_nucleus_texture(nuhtc_engine* e, const uint8_t* tiles, int channel_
                              const uint32_t* masks, int K, int H, int W, const int32_t* pairs_dev, const int32_t* n_dev, int n_max,
                              int32_t* tex, void* stream);
 
+/* Per-nucleus gradient integers for the Nucleus.Gradient.* features (csrc/nucgrad.hip): INTEGERS ONLY, under the mask M of a list entry in
+ * its H x W frame.  h is the haematoxylin value of nuhtc_op_nucleus_morph (the same lut_dev, k and channel_mode); (gx2, gy2) is twice
+ * numpy's np.gradient of h over the frame (central differences inside, twice the one-sided difference at the frame's edges, 0 along an
+ * axis of one pixel; a neighbour outside M but inside the frame counts with its pixel); q = gx2^2 + gy2^2; m = isqrt(4 q), the magnitude
+ * in quarter grey levels, 0 .. 1442.  grad row, 18 int64: A (set pixels); S1, S2, S3, S4 (the sums over M of m, m^2, m^3, m^4); mn, mx (the
+ * least and greatest m); n_edge (the pixels of M with m >= edge_thr whose q is greater than q of the first and not less than q of the
+ * second neighbour along the gradient's sector -- OpenCV's integer rule on |gx2|, |gy2| with tan 22.5 = 13573 / 2^15; a neighbour
+ * outside the frame has q = 0); hist[10] (np.histogram(m, bins=10) in integers: bin min((m - mn) * 10 / (mx - mn), 9), bin 5 for all
+ * when mx == mn).  nuhtc_amd/nucgrad.py (grad_reference) restates the row in numpy and derives the eight named features on the host.
+ * An empty mask, or an entry outside the batch, gives a zero row.  nuhtc_config is unchanged (no ABI bump).
+ * nuhtc_op_nucleus_gradient works on raw arrays, with the arguments, limits and error codes of nuhtc_op_nucleus_texture and a handle
+ * that need not be finalized; in addition edge_thr (quarter grey levels) outside 1 .. 1442 gives NUHTC_E_INVALID.  grad [n_max][18], rows
+ * from n = (n_dev ? min(*n_dev, n_max) : n_max) on are not written.  Synchronises `stream`.  There is no engine-route entry point: the
+ * columns are produced from a written GeoJSON (nuhtc_amd/ringfeat.py). */
+int nuhtc_op_nucleus_gradient(nuhtc_engine* e, const uint8_t* tiles, int channel_mode, const int32_t* lut_dev, const int32_t k[3], int B,
+                              const uint32_t* masks, int K, int H, int W, const int32_t* pairs_dev, const int32_t* n_dev, int n_max,
+                              int edge_thr, int64_t* grad, void* stream);
+
 /* Nuclei of a WRITTEN GeoJSON in front of the two measurement ops above (csrc/ringfeat.hip; nuhtc_amd/ringfeat.py, tools/wsi_feat_extract.py):
  * every nucleus gets a square frame of side S (32, 64, 128 or 256) whose pixel (0, 0) is the slide pixel origin[i] = (x, y); the masks and
  * frames below are what nuhtc_op_nucleus_morph / nuhtc_op_nucleus_texture read with B = n, K = 1, H = W = S and the pairs (i, 0).

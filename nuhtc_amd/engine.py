@@ -998,6 +998,20 @@ class Engine:
                                                       vp(n) if n is not None else None, n_max, vp(out), self._stream()))
         return out
 
+    def op_nucleus_gradient(self, tiles, masks, pairs, channel_mode=hip.CH_AS_IS, edge_thr=1, n=None, out=None):
+        """Per-nucleus gradient integers on raw arrays (nuhtc_op_nucleus_gradient; the numpy restatement is nuhtc_amd.nucgrad.grad_reference).
+        tiles, masks, pairs, channel_mode and n as in op_nucleus_morph; edge_thr: the edge threshold T in quarter grey levels, 1 .. 1442;
+        out: a contiguous int64 (n_max, 18) device tensor to write into (rows from n on stay as they are), a zero-filled one otherwise.
+        -> out.  Synchronous."""
+        B, K, H, W, n_max = self._op_nucleus_check('op_nucleus_gradient', tiles, masks, pairs)
+        out, = self._op_nucleus_out(None if out is None else (out,), n_max, (((18,), torch.int64),),
+                                    'op_nucleus_gradient: out must be a contiguous int64 (n_max, 18) tensor on the engine\'s device')
+        lut, k = self._morph_constants()
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        self._check(self.lib.nuhtc_op_nucleus_gradient(self.h, vp(tiles), int(channel_mode), vp(lut), k, B, vp(masks), K, H, W, vp(pairs),
+                                                       vp(n) if n is not None else None, n_max, int(edge_thr), vp(out), self._stream()))
+        return out
+
     def op_eval_select(self, scores, counts, masks, fg_thr, thr, labels=None):
         """Score filter + greedy mask-NMS of `WSIDataset.evaluate` (nuhtc_op_eval_select): scores (B, K) float32, counts (B,), masks
         (B, K, H, W // 32) int32 words on the device -> (sel (B, K) kept slots in visiting order, -1 behind them; nsel (B,); sel_labels)."""

@@ -7,6 +7,7 @@ in front of them and behind them:
     measure    the slide in blocks, per block and frame size: nuhtc_op_frame_gather (slide pixels -> one frame per nucleus),
                nuhtc_op_ring_fill (ring -> bit mask, csrc/ringfeat.hip), the two measurement ops -> raw, hist, glcm (integers)
     table      nucmorph.derive beside nuctex.derive -> the named float64 columns
+    (gradient=True: nuhtc_op_nucleus_gradient on a second, wider frame per nucleus and nucgrad.derive -> eight more columns; below)
     write_db / read_db / missing_ids     the SQLite file and the reference's resume rule
 
 What is measured is the nucleus the DOCUMENT describes: the traced ring with its holes filled (contours.fill_rings defines the pixel set;
@@ -17,6 +18,15 @@ and counted by reason (REASONS).  Level 0 only: rings are level-0 coordinates.
 A nucleus's frame is the square of side S = 32, 64, 128 or 256 (the smallest that holds its rectangle) whose corner is the rectangle's
 minimum corner; raw is in frame pixels and `origin` is that corner, which derive needs for the Identifier.* columns (slide pixels).
 
+Gradient frames (measure(gradient=True), `gradient_frames`).  The frames above have no margin, which is right for kernels that read only
+the pixels under the mask and wrong for a gradient, which reads the neighbours of every mask pixel (histomicstk's crop has a margin of 5
+pixels).  With the selection every nucleus ADDITIONALLY gets a gradient frame whose corner is max(rect_min - 2, 0) per axis and whose side
+is the smallest of 32 / 64 / 128 / 256 that holds the rectangle and 2 pixels beyond it; ring fill and gather for these frames are the
+same two ops in the same block walk and chunking (the block is read with 2 more pixels to the left and above), and the morphometry and
+texture frames and their values are unchanged.  A nucleus whose rectangle plus margin exceeds 256 pixels has no gradient frame: its row
+of `grad` is zero, `grad_ok` is False and the eight columns are NULL in the table.  Pixels of a gradient frame beyond the slide read as
+zeros, as the gather defines: a nucleus within 2 pixels of the slide's right or lower edge sees a black margin there.
+
 The measurement ops want an engine handle, but not a finalized one: nuhtc_create validates the config and allocates NOTHING on the
 device (every allocation is nuhtc_finalize's), so measure() makes a handle from the default config, never finalizes it, and destroys it
 on the way out.  No config file, no checkpoint."""
@@ -26,11 +36,12 @@ import sqlite3
 
 import numpy as np
 
-from . import nucmorph, nuctex
+from . import nucgrad, nucmorph, nuctex
 
 SIDES = (32, 64, 128, 256)
 MAX_SIDE = SIDES[-1]
 HALO = MAX_SIDE                 # a block is read with this many pixels to the right and below: a frame never leaves its block's read
+GRAD_MARGIN = 2                 # pixels of a gradient frame round the rectangle (the doubled central difference reads 1, the edge test 2)
 CHUNK = 4096                    # the measurement ops' limit on B
 REASONS = ('non_integer', 'no_ring', 'too_large', 'off_slide', 'not_traced')
 TABLE = 'nuclei_features'
@@ -92,6 +103,25 @@ def frame_sides(rect):
     rect = np.asarray(rect, np.int64).reshape(-1, 4)
     side = np.maximum(rect[:, 2] - rect[:, 0], rect[:, 3] - rect[:, 1]) + 1
     return np.array([bucket(int(s)) for s in side], np.int64)
+
+
+def gradient_frames(rect):
+    """rect int (n, 4) -> (origin int64 (n, 2), side int64 (n,)): the gradient frame of every rectangle (module docstring) -- the corner
+    max(rect_min - 2, 0) per axis and the smallest side that reaches 2 pixels beyond rect_max; side 0 where 256 is not enough."""
+    rect = np.asarray(rect, np.int64).reshape(-1, 4)
+    origin = np.maximum(rect[:, :2] - GRAD_MARGIN, 0)
+    need = (rect[:, 2:] + GRAD_MARGIN + 1 - origin).max(1) if len(rect) else np.zeros(0, np.int64)
+    return origin, np.array([bucket(int(s)) if s <= MAX_SIDE else 0 for s in need], np.int64)
+
+
+def add_gradient_flags(parser):
+    """The command-line form of the gradient selection (tools/wsi_feat_extract.py): --gradient and --edge-thr LEVELS, grey levels per
+    pixel; nucgrad.threshold turns LEVELS into T."""
+    parser.add_argument('--gradient', action='store_true', default=False,
+                        help='add the eight Nucleus.Gradient.* columns (nuhtc_amd/nucgrad.py): the magnitude statistics, and Canny.Sum / Canny.Mean as '
+                             'the project\'s own edge count (thresholded local maxima of the gradient; scikit-image\'s Canny is not reproduced)')
+    parser.add_argument('--edge-thr', type=float, default=0.25, metavar='LEVELS',
+                        help='with --gradient: the least gradient of an edge pixel in grey levels per pixel, 0.25 .. 360.5 in steps of 0.25')
 
 
 def block_plan(rect, slide_hw, block=2048):
@@ -231,6 +261,21 @@ class _Ops:
             self._fail('nuhtc_op_nucleus_texture', rc)
         return raw, hist, glcm
 
+    def gradient(self, frames, masks, edge_thr=nucgrad.T_DEFAULT):
+        """frames uint8 (n, S, S, 3), masks int32 (n, S, S // 32) -> grad int64 (n, 18): nuhtc_op_nucleus_gradient with B = n, K = 1 and
+        the pairs (i, 0)."""
+        t = self.torch
+        n, S = int(frames.shape[0]), int(frames.shape[1])
+        pairs = t.zeros(n, 2, dtype=t.int32, device=self.device)
+        pairs[:, 0] = t.arange(n, dtype=t.int32, device=self.device)
+        grad = t.empty(n, nucgrad.ROW, dtype=t.int64, device=self.device)
+        vp = lambda x: ctypes.c_void_p(x.data_ptr())
+        rc = self.lib.nuhtc_op_nucleus_gradient(self.h, vp(frames), self.hip.CH_AS_IS, vp(self.lut), self.k, n, vp(masks), 1, S, S, vp(pairs), None, n,
+                                                int(edge_thr), vp(grad), self._stream())
+        if rc:
+            self._fail('nuhtc_op_nucleus_gradient', rc)
+        return grad
+
 
 def pack_rings(rings):
     """list of (k, 2) integer rings -> (verts int32 (sum k, 2), ring_off int64 (n + 1,))."""
@@ -239,7 +284,7 @@ def pack_rings(rings):
     return verts, np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
 
 
-def measure(slide, features, device=0, block=2048, timings=None):
+def measure(slide, features, device=0, block=2048, timings=None, gradient=False, edge_thr=nucgrad.T_DEFAULT):
     """slide: an (H, W, 3) uint8 RGB array (a memory-mapped .npy slide) or anything with read_region (level 0 is read); features: GeoJSON
     features, or the result of parse().  The slide is walked in blocks of `block` pixels (block_plan): every block that owns a nucleus is
     read once and uploaded once, and per block and frame side, in chunks of at most 4096 nuclei, the gather, the ring fill and the two
@@ -247,7 +292,9 @@ def measure(slide, features, device=0, block=2048, timings=None):
     score, label, type, nuclei_id, left_out) for the n measured nuclei, in the order of the features.  left_out counts parse()'s reasons,
     'off_slide' (the rectangle leaves the slide) and 'not_traced' (the ring fill's status 2: an edge off the chain directions).
     `timings`: a dict that receives the seconds spent in read, upload, gather, fill and measure (each stage synchronised: for
-    tools/bench_ringfeat.py)."""
+    tools/bench_ringfeat.py).  gradient=True: the result gains grad int64 (n, 18), the rows of nuhtc_amd.nucgrad measured on the gradient
+    frames (module docstring) with the edge threshold `edge_thr` (quarter grey levels, 1 .. 1442), and grad_ok bool (n,), False where
+    the rectangle plus margin exceeds 256 pixels (a zero row); every other field is the same bytes as without."""
     import time
     import torch
     p = features if isinstance(features, dict) and 'rings' in features else parse(features)
@@ -257,6 +304,12 @@ def measure(slide, features, device=0, block=2048, timings=None):
     raw, hist = np.zeros((n, nucmorph.RAW), np.int64), np.zeros((n, nucmorph.BINS), np.int32)
     glcm = np.zeros((n, len(nuctex.OFFSETS), nuctex.CELLS), np.int32)
     keep = np.zeros(n, bool)
+    if gradient:
+        if not nucgrad.T_MIN <= int(edge_thr) <= nucgrad.T_MAX:
+            raise ValueError(f'measure: edge_thr {edge_thr} outside {nucgrad.T_MIN} .. {nucgrad.T_MAX} quarter levels')
+        grad = np.zeros((n, nucgrad.ROW), np.int64)
+        gorigin, gsides = gradient_frames(rect)
+    margin = GRAD_MARGIN if gradient else 0
     blocks, off = block_plan(rect, _slide_hw(slide), block)
     left['off_slide'] += len(off)
     sides = frame_sides(rect) if n else np.zeros(0, np.int64)
@@ -270,6 +323,9 @@ def measure(slide, features, device=0, block=2048, timings=None):
     with _Ops(device) as ops, torch.cuda.device(ops.device):
         for bx, by, bw, bh, own in blocks:
             t0 = time.perf_counter()
+            if margin:                               # gradient frames start up to `margin` pixels before the block
+                bw, bh = bw + bx - max(bx - margin, 0), bh + by - max(by - margin, 0)
+                bx, by = max(bx - margin, 0), max(by - margin, 0)
             host = read_block(slide, bx, by, bw, bh)
             t0 = lap('read', t0)
             dev = torch.from_numpy(host).to(ops.device)
@@ -294,42 +350,90 @@ def measure(slide, features, device=0, block=2048, timings=None):
                     ok = st == 0
                     left['not_traced'] += int((~ok).sum())
                     raw[idx], hist[idx], glcm[idx], keep[idx] = r.cpu().numpy(), h.cpu().numpy(), g.cpu().numpy(), ok
+            for S in SIDES if gradient else ():
+                mine = own[gsides[own] == S]
+                for c0 in range(0, len(mine), CHUNK):
+                    idx = mine[c0:c0 + CHUNK]
+                    verts, ring_off = pack_rings([p['rings'][i] for i in idx])
+                    origin = torch.from_numpy(np.ascontiguousarray(gorigin[idx], np.int32)).to(ops.device)
+                    verts_d, off_d = torch.from_numpy(verts).to(ops.device), torch.from_numpy(ring_off).to(ops.device)
+                    t0 = time.perf_counter()
+                    frames = ops.gather(dev, bx, by, origin, S)
+                    t0 = lap('gather', t0)
+                    masks, _ = ops.fill(verts_d, off_d, origin, S)          # a ring that is not traced: a zero mask, a zero row, and no row in the result
+                    t0 = lap('fill', t0)
+                    g = ops.gradient(frames, masks, edge_thr)
+                    t0 = lap('measure', t0)
+                    grad[idx] = g.cpu().numpy()
     sel = np.nonzero(keep)[0]
-    return dict(raw=raw[sel], hist=hist[sel], glcm=glcm[sel], origin=rect[sel, :2].copy(), rect=rect[sel], score=p['score'][sel], label=p['label'][sel],
-                type=[p['type'][i] for i in sel], nuclei_id=p['nuclei_id'][sel], left_out=left)
+    out = dict(raw=raw[sel], hist=hist[sel], glcm=glcm[sel], origin=rect[sel, :2].copy(), rect=rect[sel], score=p['score'][sel], label=p['label'][sel],
+               type=[p['type'][i] for i in sel], nuclei_id=p['nuclei_id'][sel], left_out=left)
+    if gradient:
+        out.update(grad=grad[sel], grad_ok=gsides[sel] > 0, grad_origin=gorigin[sel])
+    return out
 
 
-def table(m):
-    """measure()'s result -> (columns, float64 (n, 55)): nucmorph.derive(raw, hist, origin) beside nuctex.derive(glcm)."""
+def table_columns(gradient=False):
+    """The names of table()'s columns: the 29 nucmorph.COLUMNS, the 26 nuctex.COLUMNS and, with the selection, the 8 nucgrad.COLUMNS."""
+    return nucmorph.COLUMNS + nuctex.COLUMNS + (nucgrad.COLUMNS if gradient else ())
+
+
+def table(m, gradient=False):
+    """measure()'s result -> (columns, float64 (n, 55)): nucmorph.derive(raw, hist, origin) beside nuctex.derive(glcm).  gradient=True (of
+    a measure(gradient=True)): (n, 63), nucgrad.derive(grad) behind them, NaN in the eight columns of a nucleus without a gradient frame."""
     c1, v1 = nucmorph.derive(m['raw'], m['hist'], m['origin'])
     c2, v2 = nuctex.derive(m['glcm'])
-    return tuple(c1) + tuple(c2), np.concatenate([v1, v2], 1)
+    if not gradient:
+        return tuple(c1) + tuple(c2), np.concatenate([v1, v2], 1)
+    c3, v3 = nucgrad.derive(m['grad'])
+    v3 = np.where(np.asarray(m['grad_ok'], bool)[:, None], v3, np.nan)
+    return tuple(c1) + tuple(c2) + tuple(c3), np.concatenate([v1, v2, v3], 1)
 
 
-def db_columns():
+def db_columns(gradient=False):
     """[(name, SQLite type)] of the table `nuclei_features`, in order: Label (always 1, as histomicstk labels a one-nucleus crop), the 29
-    nucmorph.COLUMNS and the 26 nuctex.COLUMNS (REAL; every '.' of a name replaced by '_', as the reference does before to_sql), score,
-    type, class_id, nuclei_id, and the vertex extremes x_min, y_min, x_max, y_max."""
-    cols = [('Label', 'INTEGER')] + [(c.replace('.', '_'), 'REAL') for c in nucmorph.COLUMNS + nuctex.COLUMNS]
+    nucmorph.COLUMNS and the 26 nuctex.COLUMNS (REAL; every '.' of a name replaced by '_', as the reference does before to_sql), with
+    the selection the 8 nucgrad.COLUMNS in the same form, score, type, class_id, nuclei_id, and the vertex extremes x_min, y_min, x_max,
+    y_max."""
+    cols = [('Label', 'INTEGER')] + [(c.replace('.', '_'), 'REAL') for c in table_columns(gradient)]
     return cols + [('score', 'REAL'), ('type', 'TEXT'), ('class_id', 'INTEGER'), ('nuclei_id', 'INTEGER'),
                    ('x_min', 'INTEGER'), ('y_min', 'INTEGER'), ('x_max', 'INTEGER'), ('y_max', 'INTEGER')]
 
 
-def write_db(path, values, score, kind, class_id, nuclei_id, rect):
-    """Appends one row per nucleus to the table nuclei_features of the SQLite file `path` (created with db_columns() when missing):
-    values float (n, 55) = table()[1].  A file of any size is kept -- the reference deletes a database under 1 MB as broken; a complete
-    small table is complete.  -> the number of rows written."""
-    values = np.asarray(values, np.float64).reshape(-1, len(nucmorph.COLUMNS) + len(nuctex.COLUMNS))
+def column_mismatch(path, gradient=False):
+    """None when `path` holds no table nuclei_features or one with exactly the columns of db_columns(gradient); otherwise what differs,
+    in words: such a table is neither appended to nor altered."""
+    got = read_db(path)
+    if got is None:
+        return None
+    have, want = [c for c, _ in got['columns']], [c for c, _ in db_columns(gradient)]
+    if have == want:
+        return None
+    extra, lack = [c for c in have if c not in want], [c for c in want if c not in have]
+    return ('it has columns that were not requested: ' + ', '.join(extra) if extra else '') + ('; ' if extra and lack else '') + \
+           ('it lacks the requested columns: ' + ', '.join(lack) if lack else '') or 'its columns are in another order'
+
+
+def write_db(path, values, score, kind, class_id, nuclei_id, rect, gradient=False):
+    """Appends one row per nucleus to the table nuclei_features of the SQLite file `path` (created with db_columns(gradient) when
+    missing): values float (n, 55) = table()[1], or (n, 63) = table(gradient=True)[1], whose NaN are written as NULL.  A file of any size
+    is kept -- the reference deletes a database under 1 MB as broken; a complete small table is complete.  ValueError, with the file
+    untouched, when it holds a table with another column set (column_mismatch).  -> the number of rows written."""
+    values = np.asarray(values, np.float64).reshape(-1, len(table_columns(gradient)))
     rect = np.asarray(rect, np.int64).reshape(-1, 4)
     n = len(values)
     if not (len(score) == len(kind) == len(class_id) == len(nuclei_id) == len(rect) == n):
         raise ValueError('write_db: one row per nucleus in every field')
-    cols = db_columns()
+    cols = db_columns(gradient)
+    why = column_mismatch(path, gradient)
+    if why:
+        raise ValueError(f'write_db: {path} holds another column set ({why})')
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     conn = sqlite3.connect(path)
     try:
         conn.execute(f'CREATE TABLE IF NOT EXISTS {TABLE} ({", ".join(f"{c} {t}" for c, t in cols)})')
-        rows = [(1, *map(float, values[i]), float(score[i]), str(kind[i]), int(class_id[i]), int(nuclei_id[i]), *map(int, rect[i])) for i in range(n)]
+        real = (lambda v: None if v != v else float(v)) if gradient else float
+        rows = [(1, *map(real, values[i]), float(score[i]), str(kind[i]), int(class_id[i]), int(nuclei_id[i]), *map(int, rect[i])) for i in range(n)]
         conn.executemany(f'INSERT INTO {TABLE} ({", ".join(c for c, _ in cols)}) VALUES ({", ".join("?" * len(cols))})', rows)
         conn.commit()
     finally:

@@ -4,6 +4,7 @@ GeoJSON a detection run wrote, into <segdir>/<id>/nuclei_feat.db (SQLite, one ta
 
     python tools/wsi_feat_extract.py DATADIR --segdir SEGDIR [--start 0] [--end N] [--mag 40] [--reverse] [--bs_size 1024]
                                      [--num_workers 8] [--slide_ext .svs] [--geojson merged|plain] [--device 0]
+                                     [--gradient [--edge-thr LEVELS]]
 
 For every slide id (the sorted, extension-stripped names in DATADIR, sliced as the reference slices them) it reads
 <segdir>/<id>/<id>_merged.geojson (`--geojson plain`: <id>.geojson, whose nuclei_id is the position in the file), opens the slide as
@@ -16,14 +17,24 @@ reference does), score, type, class_id, nuclei_id, x_min, y_min, x_max, y_max (t
   * the intensity scale (Nucleus.Intensity.*) and the grey levels (Haralick.*) are THE PROJECT'S OWN fixed-point haematoxylin scale, not
     histomicstk's 8-bit stain image and crop-dependent grey limits: the columns have histomicstk's names and meaning, not its numbers;
   * Identifier.* are slide pixels at level 0;
-  * histomicstk's FSD, gradient, Hu-moment and fractal-dimension columns are not produced.
+  * histomicstk's FSD, Hu-moment and fractal-dimension columns are not produced.
+--gradient adds the eight Nucleus.Gradient.* columns of nuhtc_amd/nucgrad.py between the Haralick columns and score: the gradient
+magnitude of the same haematoxylin scale (Mag.Mean, Mag.Std in grey levels per pixel, Mag.Skewness, Mag.Kurtosis, Mag.HistEntropy and
+Mag.HistEnergy of a ten-bin histogram over the nucleus's own range) and an edge count (Canny.Sum, Canny.Mean).  The edge count is THE
+PROJECT'S OWN definition -- the mask pixels whose gradient is at least --edge-thr grey levels per pixel (default 0.25) and a local maximum
+along its quantised direction; scikit-image's Canny with its Gaussian smoothing and hysteresis, which histomicstk calls, is NOT
+reproduced: the two columns have its names and meaning, not its numbers.  The gradient is taken on a frame with a margin of 2 pixels
+round the nucleus's rectangle (pixels beyond the slide read as zeros); a nucleus whose rectangle plus that margin exceeds 256 pixels has
+NULL in the eight columns and is counted on stderr.  The other columns are the same bytes with and without the flag.
 Only TRACED RINGS are measured -- integer vertices on pixel centres, edges along the eight chain directions: what tools/infer_wsi.py
 writes, here and in the reference.  The measured pixels are the ring's border and everything it encloses (holes filled).  Arbitrary
 polygons (float coordinates, other edge directions), nuclei wider or taller than 256 pixels and rings that leave the slide are left out
 and counted; the closing line on stderr gives, per slide, the rows written and the rows left out by reason.
 
 Resume, as the reference: a database that already holds every nuclei_id of the file skips the slide; otherwise only the missing nuclei
-are measured and appended.  NOT as the reference: a database under 1 MB is kept -- the reference deletes it as broken, but a complete
+are measured and appended.  A database whose columns differ from the requested ones (written without --gradient and run with it, or the
+other way round) is neither appended to nor altered: the slide is skipped with a message that names the file and the difference.
+NOT as the reference: a database under 1 MB is kept -- the reference deletes it as broken, but a complete
 small table is complete.
 
 --mag is accepted for parity.  Rings are level-0 coordinates and are measured in level-0 pixels at every magnification (the reference
@@ -38,7 +49,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def build_parser():
-    """tools/wsi_feat_extract.py:239-250 of the reference, then three flags of our own."""
+    """tools/wsi_feat_extract.py:239-250 of the reference, then three flags of our own and the two of the gradient selection
+    (--gradient, --edge-thr: nuhtc_amd.ringfeat.add_gradient_flags, beside what they select)."""
     p = ArgumentParser(allow_abbrev=False)
     p.add_argument('datadir', help='path to folder containing raw wsi image files')
     p.add_argument('--segdir', help='path to folder containing segmentation files')
@@ -52,6 +64,8 @@ def build_parser():
     p.add_argument('--slide_ext', type=str, default='.svs', help='ext name of wsi (.svs, .tif, .npy)')
     p.add_argument('--geojson', choices=('merged', 'plain'), default='merged', help='<id>_merged.geojson or <id>.geojson')
     p.add_argument('--device', type=int, default=0, help='GPU of the measurement')
+    from nuhtc_amd import ringfeat
+    ringfeat.add_gradient_flags(p)
     return p
 
 
@@ -67,9 +81,14 @@ def slide_ids(datadir, start=0, end=None, reverse=False):
     return ids[start:end] if end is not None else ids[start:]
 
 
-def extract_slide(slide_path, geojson_path, db_path, device=0, log=print):
-    """One slide -> (rows written, {reason: left out}), or None when the table already holds every nucleus of the file."""
+def extract_slide(slide_path, geojson_path, db_path, device=0, log=print, gradient=False, edge_thr=1):
+    """One slide -> (rows written, {reason: left out}), or None when the table already holds every nucleus of the file.  gradient=True:
+    with the gradient columns (edge_thr in quarter grey levels), -> (rows written, {reason: left out}, rows without a gradient frame).
+    An existing table with another column set: a string that says what differs, and the file is not touched."""
     from nuhtc_amd import ringfeat, slides
+    why = ringfeat.column_mismatch(db_path, gradient)
+    if why:
+        return why
     with open(geojson_path) as f:
         features = json.load(f)
     every = [int(f['properties']['nuclei_id']) if 'nuclei_id' in (f.get('properties') or {}) else k for k, f in enumerate(features)]
@@ -82,10 +101,15 @@ def extract_slide(slide_path, geojson_path, db_path, device=0, log=print):
     # only the missing nuclei are measured, each under the id it has in the whole file (a nucleus left out before is tried, and left
     # out, again)
     features = [dict(f, properties=dict(f.get('properties') or {}, nuclei_id=i)) for f, i in zip(features, every) if i in todo]
-    m = ringfeat.measure(slides.open_array_slide(slide_path), features, device=device)
-    _, values = ringfeat.table(m)
-    n = ringfeat.write_db(db_path, values, m['score'], m['type'], m['label'], m['nuclei_id'], m['rect'])
-    return n, m['left_out']
+    if not gradient:
+        m = ringfeat.measure(slides.open_array_slide(slide_path), features, device=device)
+        _, values = ringfeat.table(m)
+        n = ringfeat.write_db(db_path, values, m['score'], m['type'], m['label'], m['nuclei_id'], m['rect'])
+        return n, m['left_out']
+    m = ringfeat.measure(slides.open_array_slide(slide_path), features, device=device, gradient=True, edge_thr=edge_thr)
+    _, values = ringfeat.table(m, gradient=True)
+    n = ringfeat.write_db(db_path, values, m['score'], m['type'], m['label'], m['nuclei_id'], m['rect'], gradient=True)
+    return n, m['left_out'], int((~m['grad_ok']).sum())
 
 
 def main(argv=None):
@@ -93,6 +117,13 @@ def main(argv=None):
     import torch
     if not torch.cuda.is_available():
         raise SystemExit('wsi_feat_extract.py needs a GPU (there is no fallback)')
+    edge_thr = 1
+    if args.gradient:
+        from nuhtc_amd import nucgrad
+        try:
+            edge_thr = nucgrad.threshold(args.edge_thr)
+        except ValueError as e:
+            raise SystemExit(f'--edge-thr: {e}')
     if args.mag != 40:
         print(f'--mag {args.mag}: rings are level-0 coordinates and are measured in level-0 pixels; the reference would upsample every crop by '
               f'{40 / args.mag:g} first, this tool does not', file=sys.stderr)
@@ -109,13 +140,19 @@ def main(argv=None):
         if not os.path.exists(spath):
             print(f'no slide {spath}, skipped\n')
             continue
-        got = extract_slide(spath, gj, os.path.join(args.segdir, sid, 'nuclei_feat.db'), device=args.device)
+        db = os.path.join(args.segdir, sid, 'nuclei_feat.db')
+        got = extract_slide(spath, gj, db, device=args.device, gradient=args.gradient, edge_thr=edge_thr)
         if got is None:
             print(f'skipped:{sid}\n')
             continue
-        n, left = got
+        if isinstance(got, str):
+            print(f'skipped:{sid}: {db} was written with other columns and is left as it is ({got})\n')
+            report.append(f'{sid}: skipped, {db} holds other columns ({got})')
+            continue
+        n, left = got[:2]
         print(f'{sid}: {n} rows')
-        report.append(f'{sid}: {n} rows written, left out ' + (', '.join(f'{v} {r}' for r, v in left.items() if v) or 'none'))
+        report.append(f'{sid}: {n} rows written, left out ' + (', '.join(f'{v} {r}' for r, v in left.items() if v) or 'none') +
+                      (f', {got[2]} without gradient columns (rectangle plus margin over 256 px)' if args.gradient and got[2] else ''))
     print('; '.join(report) if report else 'no slide measured', file=sys.stderr)
 
 
