@@ -852,6 +852,23 @@ int nuhtc_op_nucleus_gradient(nuhtc_engine* e, const uint8_t* tiles, int channel
                               const uint32_t* masks, int K, int H, int W, const int32_t* pairs_dev, const int32_t* n_dev, int n_max,
                               int edge_thr, int64_t* grad, void* stream);
 
+/* Per-nucleus shape integers for the Shape.HuMoments1..7 and Shape.FractalDimension features (csrc/nucshape.hip): INTEGERS ONLY, a pure
+ * function of the mask M of a list entry in its H x W frame; no tile is read.  x is the column, y the row, both frame pixels.  shape row,
+ * 24 int64: A (set pixels); x0, y0, x1, y1 (the bounding rectangle, x1 and y1 exclusive; all 0 when A == 0); Sx, Sy, Sxx, Sxy, Syy, Sxxx,
+ * Sxxy, Sxyy, Syyy (the sums over M of x, y, x^2, x y, y^2, x^3, x^2 y, x y^2, y^3); N_1 .. N_10 (the box counts: with s = 2^j, the s x s
+ * squares anchored at (x0, y0) -- box (i, k) covers x0 + i s <= x < x0 + (i + 1) s, y0 + k s <= y < y0 + (k + 1) s -- that hold at least
+ * one set pixel and at least one unset position among their s^2 positions, a position outside the rectangle being unset whether or not
+ * it lies inside the frame; all ten are written, sizes larger than the rectangle included).  nuhtc_amd/nucshape.py (shape_reference)
+ * restates the row in numpy and derives the eight named features on the host.  An empty mask, or an entry outside the batch, gives a
+ * zero row.  nuhtc_config is unchanged (no ABI bump).
+ * nuhtc_op_nucleus_shape works on raw arrays, with the masks, the list, the limits and the error codes of nuhtc_op_nucleus_texture (B 1 ..
+ * 4096, K 1 .. 65536, H and W 1 .. 1024, W need not be a multiple of 32 and bits from W on are ignored, n_max 1 .. 2^24; a null pointer
+ * other than n_dev is NUHTC_E_INVALID) and a handle that need not be finalized.  shape [n_max][24], rows from n = (n_dev ? min(*n_dev,
+ * n_max) : n_max) on are not written.  Synchronises `stream`.  There is no engine-route entry point: the op takes the engine's masks as
+ * they are, and the columns are produced from a written GeoJSON (nuhtc_amd/ringfeat.py). */
+int nuhtc_op_nucleus_shape(nuhtc_engine* e, int B, const uint32_t* masks, int K, int H, int W, const int32_t* pairs_dev, const int32_t* n_dev,
+                           int n_max, int64_t* shape, void* stream);
+
 /* Nuclei of a WRITTEN GeoJSON in front of the two measurement ops above (csrc/ringfeat.hip; nuhtc_amd/ringfeat.py, tools/wsi_feat_extract.py):
  * every nucleus gets a square frame of side S (32, 64, 128 or 256) whose pixel (0, 0) is the slide pixel origin[i] = (x, y); the masks and
  * frames below are what nuhtc_op_nucleus_morph / nuhtc_op_nucleus_texture read with B = n, K = 1, H = W = S and the pairs (i, 0).

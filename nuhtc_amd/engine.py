@@ -1012,6 +1012,28 @@ class Engine:
                                                        vp(n) if n is not None else None, n_max, int(edge_thr), vp(out), self._stream()))
         return out
 
+    def op_nucleus_shape(self, masks, pairs, W=None, n=None, out=None):
+        """Per-nucleus shape integers on raw arrays (nuhtc_op_nucleus_shape; the numpy restatement is nuhtc_amd.nucshape.shape_reference).
+        No tile is read.  masks: contiguous int32 device tensor (B, K, H, (W + 31) // 32), bit x & 31 of word x >> 5; W: the frame's width
+        (None: 32 times the words of a row); pairs and n as in op_nucleus_morph; out: a contiguous int64 (n_max, 24) device tensor to write
+        into (rows from n on stay as they are), a zero-filled one otherwise.  -> out.  Synchronous."""
+        for t in (masks, pairs):
+            if t.device != self.device or t.dtype != torch.int32 or not t.is_contiguous():
+                raise ValueError('op_nucleus_shape: contiguous int32 masks and pairs on the engine\'s device')
+        if masks.dim() != 4 or tuple(pairs.shape[1:]) != (2,):
+            raise ValueError('op_nucleus_shape: masks (B, K, H, (W + 31) // 32), pairs (n, 2)')
+        B, K, H, wpr = (int(v) for v in masks.shape)
+        W = wpr * 32 if W is None else int(W)
+        if (W + 31) // 32 != wpr:
+            raise ValueError('op_nucleus_shape: masks (B, K, H, (W + 31) // 32), pairs (n, 2)')
+        n_max = int(pairs.shape[0])
+        out, = self._op_nucleus_out(None if out is None else (out,), n_max, (((24,), torch.int64),),
+                                    'op_nucleus_shape: out must be a contiguous int64 (n_max, 24) tensor on the engine\'s device')
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        self._check(self.lib.nuhtc_op_nucleus_shape(self.h, B, vp(masks), K, H, W, vp(pairs), vp(n) if n is not None else None, n_max, vp(out),
+                                                    self._stream()))
+        return out
+
     def op_eval_select(self, scores, counts, masks, fg_thr, thr, labels=None):
         """Score filter + greedy mask-NMS of `WSIDataset.evaluate` (nuhtc_op_eval_select): scores (B, K) float32, counts (B,), masks
         (B, K, H, W // 32) int32 words on the device -> (sel (B, K) kept slots in visiting order, -1 behind them; nsel (B,); sel_labels)."""

@@ -8,6 +8,9 @@ in front of them and behind them:
                nuhtc_op_ring_fill (ring -> bit mask, csrc/ringfeat.hip), the two measurement ops -> raw, hist, glcm (integers)
     table      nucmorph.derive beside nuctex.derive -> the named float64 columns
     (gradient=True: nuhtc_op_nucleus_gradient on a second, wider frame per nucleus and nucgrad.derive -> eight more columns; below)
+    (shape=True: nuhtc_op_nucleus_shape on the same masks and nucshape.derive -> the seven Shape.HuMoments* and Shape.FractalDimension,
+               last among the feature columns; nothing outside the mask is read, so the frames above serve, and every measured nucleus
+               has its row -- there is no NULL case)
     write_db / read_db / missing_ids     the SQLite file and the reference's resume rule
 
 What is measured is the nucleus the DOCUMENT describes: the traced ring with its holes filled (contours.fill_rings defines the pixel set;
@@ -36,7 +39,7 @@ import sqlite3
 
 import numpy as np
 
-from . import nucgrad, nucmorph, nuctex
+from . import nucgrad, nucmorph, nucshape, nuctex
 
 SIDES = (32, 64, 128, 256)
 MAX_SIDE = SIDES[-1]
@@ -122,6 +125,13 @@ def add_gradient_flags(parser):
                              'the project\'s own edge count (thresholded local maxima of the gradient; scikit-image\'s Canny is not reproduced)')
     parser.add_argument('--edge-thr', type=float, default=0.25, metavar='LEVELS',
                         help='with --gradient: the least gradient of an edge pixel in grey levels per pixel, 0.25 .. 360.5 in steps of 0.25')
+
+
+def add_shape_flags(parser):
+    """The command-line form of the shape selection (tools/wsi_feat_extract.py): --shape."""
+    parser.add_argument('--shape', action='store_true', default=False,
+                        help='add Shape.HuMoments1..7 (scikit-image\'s moments_hu, which histomicstk calls) and Shape.FractalDimension (histomicstk\'s '
+                             'name and meaning; the box counts are the project\'s own definition, nuhtc_amd/nucshape.py) behind the other feature columns')
 
 
 def block_plan(rect, slide_hw, block=2048):
@@ -276,6 +286,19 @@ class _Ops:
             self._fail('nuhtc_op_nucleus_gradient', rc)
         return grad
 
+    def shape(self, masks):
+        """masks int32 (n, S, S // 32) -> shape int64 (n, 24): nuhtc_op_nucleus_shape with B = n, K = 1 and the pairs (i, 0)."""
+        t = self.torch
+        n, S = int(masks.shape[0]), int(masks.shape[1])
+        pairs = t.zeros(n, 2, dtype=t.int32, device=self.device)
+        pairs[:, 0] = t.arange(n, dtype=t.int32, device=self.device)
+        rows = t.empty(n, nucshape.ROW, dtype=t.int64, device=self.device)
+        vp = lambda x: ctypes.c_void_p(x.data_ptr())
+        rc = self.lib.nuhtc_op_nucleus_shape(self.h, n, vp(masks), 1, S, S, vp(pairs), None, n, vp(rows), self._stream())
+        if rc:
+            self._fail('nuhtc_op_nucleus_shape', rc)
+        return rows
+
 
 def pack_rings(rings):
     """list of (k, 2) integer rings -> (verts int32 (sum k, 2), ring_off int64 (n + 1,))."""
@@ -284,7 +307,7 @@ def pack_rings(rings):
     return verts, np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
 
 
-def measure(slide, features, device=0, block=2048, timings=None, gradient=False, edge_thr=nucgrad.T_DEFAULT):
+def measure(slide, features, device=0, block=2048, timings=None, gradient=False, edge_thr=nucgrad.T_DEFAULT, shape=False):
     """slide: an (H, W, 3) uint8 RGB array (a memory-mapped .npy slide) or anything with read_region (level 0 is read); features: GeoJSON
     features, or the result of parse().  The slide is walked in blocks of `block` pixels (block_plan): every block that owns a nucleus is
     read once and uploaded once, and per block and frame side, in chunks of at most 4096 nuclei, the gather, the ring fill and the two
@@ -294,7 +317,9 @@ def measure(slide, features, device=0, block=2048, timings=None, gradient=False,
     `timings`: a dict that receives the seconds spent in read, upload, gather, fill and measure (each stage synchronised: for
     tools/bench_ringfeat.py).  gradient=True: the result gains grad int64 (n, 18), the rows of nuhtc_amd.nucgrad measured on the gradient
     frames (module docstring) with the edge threshold `edge_thr` (quarter grey levels, 1 .. 1442), and grad_ok bool (n,), False where
-    the rectangle plus margin exceeds 256 pixels (a zero row); every other field is the same bytes as without."""
+    the rectangle plus margin exceeds 256 pixels (a zero row); every other field is the same bytes as without.  shape=True: the result
+    gains shape int64 (n, 24), the rows of nuhtc_amd.nucshape measured on the masks of the morphometry; every other field is the same
+    bytes as without."""
     import time
     import torch
     p = features if isinstance(features, dict) and 'rings' in features else parse(features)
@@ -304,6 +329,8 @@ def measure(slide, features, device=0, block=2048, timings=None, gradient=False,
     raw, hist = np.zeros((n, nucmorph.RAW), np.int64), np.zeros((n, nucmorph.BINS), np.int32)
     glcm = np.zeros((n, len(nuctex.OFFSETS), nuctex.CELLS), np.int32)
     keep = np.zeros(n, bool)
+    if shape:
+        rows = np.zeros((n, nucshape.ROW), np.int64)
     if gradient:
         if not nucgrad.T_MIN <= int(edge_thr) <= nucgrad.T_MAX:
             raise ValueError(f'measure: edge_thr {edge_thr} outside {nucgrad.T_MIN} .. {nucgrad.T_MAX} quarter levels')
@@ -343,6 +370,8 @@ def measure(slide, features, device=0, block=2048, timings=None, gradient=False,
                     masks, status = ops.fill(verts_d, off_d, origin, S)
                     t0 = lap('fill', t0)
                     r, h, g = ops.morph_tex(frames, masks)
+                    if shape:
+                        rows[idx] = ops.shape(masks).cpu().numpy()
                     t0 = lap('measure', t0)
                     st = status.cpu().numpy()
                     if (st == 1).any():
@@ -370,43 +399,51 @@ def measure(slide, features, device=0, block=2048, timings=None, gradient=False,
                type=[p['type'][i] for i in sel], nuclei_id=p['nuclei_id'][sel], left_out=left)
     if gradient:
         out.update(grad=grad[sel], grad_ok=gsides[sel] > 0, grad_origin=gorigin[sel])
+    if shape:
+        out.update(shape=rows[sel])
     return out
 
 
-def table_columns(gradient=False):
-    """The names of table()'s columns: the 29 nucmorph.COLUMNS, the 26 nuctex.COLUMNS and, with the selection, the 8 nucgrad.COLUMNS."""
-    return nucmorph.COLUMNS + nuctex.COLUMNS + (nucgrad.COLUMNS if gradient else ())
+def table_columns(gradient=False, shape=False):
+    """The names of table()'s columns: the 29 nucmorph.COLUMNS, the 26 nuctex.COLUMNS and, with the selections, the 8 nucgrad.COLUMNS and
+    then the 8 nucshape.COLUMNS."""
+    return nucmorph.COLUMNS + nuctex.COLUMNS + (nucgrad.COLUMNS if gradient else ()) + (nucshape.COLUMNS if shape else ())
 
 
-def table(m, gradient=False):
+def table(m, gradient=False, shape=False):
     """measure()'s result -> (columns, float64 (n, 55)): nucmorph.derive(raw, hist, origin) beside nuctex.derive(glcm).  gradient=True (of
-    a measure(gradient=True)): (n, 63), nucgrad.derive(grad) behind them, NaN in the eight columns of a nucleus without a gradient frame."""
+    a measure(gradient=True)): (n, 63), nucgrad.derive(grad) behind them, NaN in the eight columns of a nucleus without a gradient frame.
+    shape=True (of a measure(shape=True)): eight more columns, nucshape.derive(shape), last -- behind the gradient's when both are
+    selected (n, 71), behind the texture's otherwise (n, 63); they are never NaN."""
     c1, v1 = nucmorph.derive(m['raw'], m['hist'], m['origin'])
     c2, v2 = nuctex.derive(m['glcm'])
-    if not gradient:
-        return tuple(c1) + tuple(c2), np.concatenate([v1, v2], 1)
-    c3, v3 = nucgrad.derive(m['grad'])
-    v3 = np.where(np.asarray(m['grad_ok'], bool)[:, None], v3, np.nan)
-    return tuple(c1) + tuple(c2) + tuple(c3), np.concatenate([v1, v2, v3], 1)
+    cols, vals = tuple(c1) + tuple(c2), [v1, v2]
+    if gradient:
+        c3, v3 = nucgrad.derive(m['grad'])
+        cols, vals = cols + tuple(c3), vals + [np.where(np.asarray(m['grad_ok'], bool)[:, None], v3, np.nan)]
+    if shape:
+        c4, v4 = nucshape.derive(m['shape'])
+        cols, vals = cols + tuple(c4), vals + [v4]
+    return cols, np.concatenate(vals, 1)
 
 
-def db_columns(gradient=False):
+def db_columns(gradient=False, shape=False):
     """[(name, SQLite type)] of the table `nuclei_features`, in order: Label (always 1, as histomicstk labels a one-nucleus crop), the 29
     nucmorph.COLUMNS and the 26 nuctex.COLUMNS (REAL; every '.' of a name replaced by '_', as the reference does before to_sql), with
-    the selection the 8 nucgrad.COLUMNS in the same form, score, type, class_id, nuclei_id, and the vertex extremes x_min, y_min, x_max,
-    y_max."""
-    cols = [('Label', 'INTEGER')] + [(c.replace('.', '_'), 'REAL') for c in table_columns(gradient)]
+    the selections the 8 nucgrad.COLUMNS and then the 8 nucshape.COLUMNS in the same form, score, type, class_id, nuclei_id, and the vertex
+    extremes x_min, y_min, x_max, y_max."""
+    cols = [('Label', 'INTEGER')] + [(c.replace('.', '_'), 'REAL') for c in table_columns(gradient, shape)]
     return cols + [('score', 'REAL'), ('type', 'TEXT'), ('class_id', 'INTEGER'), ('nuclei_id', 'INTEGER'),
                    ('x_min', 'INTEGER'), ('y_min', 'INTEGER'), ('x_max', 'INTEGER'), ('y_max', 'INTEGER')]
 
 
-def column_mismatch(path, gradient=False):
-    """None when `path` holds no table nuclei_features or one with exactly the columns of db_columns(gradient); otherwise what differs,
-    in words: such a table is neither appended to nor altered."""
+def column_mismatch(path, gradient=False, shape=False):
+    """None when `path` holds no table nuclei_features or one with exactly the columns of db_columns(gradient, shape); otherwise what
+    differs, in words: such a table is neither appended to nor altered."""
     got = read_db(path)
     if got is None:
         return None
-    have, want = [c for c, _ in got['columns']], [c for c, _ in db_columns(gradient)]
+    have, want = [c for c, _ in got['columns']], [c for c, _ in db_columns(gradient, shape)]
     if have == want:
         return None
     extra, lack = [c for c in have if c not in want], [c for c in want if c not in have]
@@ -414,18 +451,19 @@ def column_mismatch(path, gradient=False):
            ('it lacks the requested columns: ' + ', '.join(lack) if lack else '') or 'its columns are in another order'
 
 
-def write_db(path, values, score, kind, class_id, nuclei_id, rect, gradient=False):
-    """Appends one row per nucleus to the table nuclei_features of the SQLite file `path` (created with db_columns(gradient) when
-    missing): values float (n, 55) = table()[1], or (n, 63) = table(gradient=True)[1], whose NaN are written as NULL.  A file of any size
+def write_db(path, values, score, kind, class_id, nuclei_id, rect, gradient=False, shape=False):
+    """Appends one row per nucleus to the table nuclei_features of the SQLite file `path` (created with db_columns(gradient, shape) when
+    missing): values float (n, 55) = table()[1], or (n, 63) = table(gradient=True)[1], whose NaN are written as NULL; with shape=True
+    eight columns more, table(gradient, shape)[1].  A file of any size
     is kept -- the reference deletes a database under 1 MB as broken; a complete small table is complete.  ValueError, with the file
     untouched, when it holds a table with another column set (column_mismatch).  -> the number of rows written."""
-    values = np.asarray(values, np.float64).reshape(-1, len(table_columns(gradient)))
+    values = np.asarray(values, np.float64).reshape(-1, len(table_columns(gradient, shape)))
     rect = np.asarray(rect, np.int64).reshape(-1, 4)
     n = len(values)
     if not (len(score) == len(kind) == len(class_id) == len(nuclei_id) == len(rect) == n):
         raise ValueError('write_db: one row per nucleus in every field')
-    cols = db_columns(gradient)
-    why = column_mismatch(path, gradient)
+    cols = db_columns(gradient, shape)
+    why = column_mismatch(path, gradient, shape)
     if why:
         raise ValueError(f'write_db: {path} holds another column set ({why})')
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)

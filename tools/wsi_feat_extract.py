@@ -4,7 +4,7 @@ GeoJSON a detection run wrote, into <segdir>/<id>/nuclei_feat.db (SQLite, one ta
 
     python tools/wsi_feat_extract.py DATADIR --segdir SEGDIR [--start 0] [--end N] [--mag 40] [--reverse] [--bs_size 1024]
                                      [--num_workers 8] [--slide_ext .svs] [--geojson merged|plain] [--device 0]
-                                     [--gradient [--edge-thr LEVELS]]
+                                     [--gradient [--edge-thr LEVELS]] [--shape]
 
 For every slide id (the sorted, extension-stripped names in DATADIR, sliced as the reference slices them) it reads
 <segdir>/<id>/<id>_merged.geojson (`--geojson plain`: <id>.geojson, whose nuclei_id is the position in the file), opens the slide as
@@ -17,7 +17,8 @@ reference does), score, type, class_id, nuclei_id, x_min, y_min, x_max, y_max (t
   * the intensity scale (Nucleus.Intensity.*) and the grey levels (Haralick.*) are THE PROJECT'S OWN fixed-point haematoxylin scale, not
     histomicstk's 8-bit stain image and crop-dependent grey limits: the columns have histomicstk's names and meaning, not its numbers;
   * Identifier.* are slide pixels at level 0;
-  * histomicstk's FSD, Hu-moment and fractal-dimension columns are not produced.
+  * of histomicstk's shape families, the Hu moments and the fractal dimension come with --shape (below); FSD (Shape.FSD1..6) is the
+    only histomicstk family that is not produced.
 --gradient adds the eight Nucleus.Gradient.* columns of nuhtc_amd/nucgrad.py between the Haralick columns and score: the gradient
 magnitude of the same haematoxylin scale (Mag.Mean, Mag.Std in grey levels per pixel, Mag.Skewness, Mag.Kurtosis, Mag.HistEntropy and
 Mag.HistEnergy of a ten-bin histogram over the nucleus's own range) and an edge count (Canny.Sum, Canny.Mean).  The edge count is THE
@@ -26,14 +27,21 @@ along its quantised direction; scikit-image's Canny with its Gaussian smoothing 
 reproduced: the two columns have its names and meaning, not its numbers.  The gradient is taken on a frame with a margin of 2 pixels
 round the nucleus's rectangle (pixels beyond the slide read as zeros); a nucleus whose rectangle plus that margin exceeds 256 pixels has
 NULL in the eight columns and is counted on stderr.  The other columns are the same bytes with and without the flag.
+--shape adds the eight columns of nuhtc_amd/nucshape.py last among the feature columns (behind the gradient columns when both flags are
+given, behind the Haralick columns otherwise, before score): Shape.HuMoments1..7, scikit-image's moments_hu of the mask (its (row,
+column) convention, which decides the sign of the seventh), and Shape.FractalDimension, minus the slope of ln N on ln s over the box
+sizes s = 4, 8, .. up to the rectangle's smaller side -- histomicstk's names and meaning; the box counts are the project's own definition
+(boxes anchored at the rectangle's corner, written from the numpy-100 recipe histomicstk uses, not compared with histomicstk itself).
+Both are functions of the mask alone and every measured nucleus has them: there is no NULL.  The other columns are the same bytes with
+and without the flag.
 Only TRACED RINGS are measured -- integer vertices on pixel centres, edges along the eight chain directions: what tools/infer_wsi.py
 writes, here and in the reference.  The measured pixels are the ring's border and everything it encloses (holes filled).  Arbitrary
 polygons (float coordinates, other edge directions), nuclei wider or taller than 256 pixels and rings that leave the slide are left out
 and counted; the closing line on stderr gives, per slide, the rows written and the rows left out by reason.
 
 Resume, as the reference: a database that already holds every nuclei_id of the file skips the slide; otherwise only the missing nuclei
-are measured and appended.  A database whose columns differ from the requested ones (written without --gradient and run with it, or the
-other way round) is neither appended to nor altered: the slide is skipped with a message that names the file and the difference.
+are measured and appended.  A database whose columns differ from the requested ones (written without --gradient or --shape and run with
+it, or the other way round) is neither appended to nor altered: the slide is skipped with a message that names the file and the difference.
 NOT as the reference: a database under 1 MB is kept -- the reference deletes it as broken, but a complete
 small table is complete.
 
@@ -49,8 +57,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def build_parser():
-    """tools/wsi_feat_extract.py:239-250 of the reference, then three flags of our own and the two of the gradient selection
-    (--gradient, --edge-thr: nuhtc_amd.ringfeat.add_gradient_flags, beside what they select)."""
+    """tools/wsi_feat_extract.py:239-250 of the reference, then three flags of our own, the two of the gradient selection (--gradient,
+    --edge-thr: nuhtc_amd.ringfeat.add_gradient_flags, beside what they select) and the one of the shape selection (--shape:
+    add_shape_flags)."""
     p = ArgumentParser(allow_abbrev=False)
     p.add_argument('datadir', help='path to folder containing raw wsi image files')
     p.add_argument('--segdir', help='path to folder containing segmentation files')
@@ -66,6 +75,7 @@ def build_parser():
     p.add_argument('--device', type=int, default=0, help='GPU of the measurement')
     from nuhtc_amd import ringfeat
     ringfeat.add_gradient_flags(p)
+    ringfeat.add_shape_flags(p)
     return p
 
 
@@ -81,12 +91,13 @@ def slide_ids(datadir, start=0, end=None, reverse=False):
     return ids[start:end] if end is not None else ids[start:]
 
 
-def extract_slide(slide_path, geojson_path, db_path, device=0, log=print, gradient=False, edge_thr=1):
+def extract_slide(slide_path, geojson_path, db_path, device=0, log=print, gradient=False, edge_thr=1, shape=False):
     """One slide -> (rows written, {reason: left out}), or None when the table already holds every nucleus of the file.  gradient=True:
     with the gradient columns (edge_thr in quarter grey levels), -> (rows written, {reason: left out}, rows without a gradient frame).
-    An existing table with another column set: a string that says what differs, and the file is not touched."""
+    shape=True: with the shape columns; the return value keeps its form.  An existing table with another column set: a string that says
+    what differs, and the file is not touched."""
     from nuhtc_amd import ringfeat, slides
-    why = ringfeat.column_mismatch(db_path, gradient)
+    why = ringfeat.column_mismatch(db_path, gradient, shape)
     if why:
         return why
     with open(geojson_path) as f:
@@ -102,13 +113,13 @@ def extract_slide(slide_path, geojson_path, db_path, device=0, log=print, gradie
     # out, again)
     features = [dict(f, properties=dict(f.get('properties') or {}, nuclei_id=i)) for f, i in zip(features, every) if i in todo]
     if not gradient:
-        m = ringfeat.measure(slides.open_array_slide(slide_path), features, device=device)
-        _, values = ringfeat.table(m)
-        n = ringfeat.write_db(db_path, values, m['score'], m['type'], m['label'], m['nuclei_id'], m['rect'])
+        m = ringfeat.measure(slides.open_array_slide(slide_path), features, device=device, shape=shape)
+        _, values = ringfeat.table(m, shape=shape)
+        n = ringfeat.write_db(db_path, values, m['score'], m['type'], m['label'], m['nuclei_id'], m['rect'], shape=shape)
         return n, m['left_out']
-    m = ringfeat.measure(slides.open_array_slide(slide_path), features, device=device, gradient=True, edge_thr=edge_thr)
-    _, values = ringfeat.table(m, gradient=True)
-    n = ringfeat.write_db(db_path, values, m['score'], m['type'], m['label'], m['nuclei_id'], m['rect'], gradient=True)
+    m = ringfeat.measure(slides.open_array_slide(slide_path), features, device=device, gradient=True, edge_thr=edge_thr, shape=shape)
+    _, values = ringfeat.table(m, gradient=True, shape=shape)
+    n = ringfeat.write_db(db_path, values, m['score'], m['type'], m['label'], m['nuclei_id'], m['rect'], gradient=True, shape=shape)
     return n, m['left_out'], int((~m['grad_ok']).sum())
 
 
@@ -141,7 +152,7 @@ def main(argv=None):
             print(f'no slide {spath}, skipped\n')
             continue
         db = os.path.join(args.segdir, sid, 'nuclei_feat.db')
-        got = extract_slide(spath, gj, db, device=args.device, gradient=args.gradient, edge_thr=edge_thr)
+        got = extract_slide(spath, gj, db, device=args.device, gradient=args.gradient, edge_thr=edge_thr, shape=args.shape)
         if got is None:
             print(f'skipped:{sid}\n')
             continue
