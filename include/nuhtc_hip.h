@@ -220,7 +220,9 @@ enum {
  * (about 120 bytes per detection, plus a copy of `bits` in polygon mode), runs on `stream` and synchronises it before
  * returning.  A detection may have any number of higher-scored overlapping neighbours (24 are kept inline, the rest in a
  * spill pool that is grown and the pass repeated when it runs out); NUHTC_E_CAPACITY only if 2^30 spill entries do not
- * suffice.  NUHTC_E_INVALID in polygon mode if a crop exceeds about 430x430 pixels. */
+ * suffice.  The decision rounds run until nothing changes, however long a chain of overlapping neighbours is (one level per
+ * launch); every detection is decided after at most n launches, and NUHTC_E_CAPACITY is returned, never a keep set, should
+ * that bound be passed.  NUHTC_E_INVALID in polygon mode if a crop exceeds about 430x430 pixels. */
 int nuhtc_merge_overlap(int device, const int32_t* boxes, const float* scores, const int32_t* areas, const uint32_t* bits,
                         const int64_t* bit_off, int64_t n, int64_t n_words, int overlap, double thr, int x_min, int y_min,
                         int x_max, int y_max, uint8_t* keep_dev, void* stream);

@@ -27,7 +27,7 @@
 //      suppressor list -- 24 inline entries, further ones in chunks of a spill pool that the host grows and retries if it
 //      runs out (a pair is handled in the one cell that holds the top-left of the box overlap);
 //   3. rounds of: undecided i becomes dead if a suppressor is alive, alive if all suppressors are dead -- until nothing
-//      changes (chains are short: a handful of rounds).
+//      changes (chains are short: a handful of rounds; a chain of n neighbours with monotonic priorities takes n launches).
 // Integer work throughout.  (Wave reductions: block_prims.h.)
 #include <algorithm>
 #include <cstring>
@@ -568,7 +568,12 @@ extern "C" int nuhtc_merge_overlap(int device, const int32_t* boxes, const float
     if (attempt >= 6 || a.spill_cap >= (1 << 30)) return NUHTC_E_CAPACITY;
     a.spill_cap = (int)std::min<long long>(std::max<long long>((long long)h_flags[2] + 1024, 4LL * a.spill_cap), 1LL << 30);
   }
-  for (int round = 0; round < 4096; ++round) {
+  // rounds until a check finds no change.  Every launch decides at least the undecided detection of the highest priority (all its
+  // suppressors are decided), so n launches decide everything and one more check sees no change; along a chain of neighbours
+  // one launch advances one level only (the lanes of a wave read before any of them writes).  Beyond that bound something is
+  // wrong: an error, never a keep set with undecided detections dropped
+  for (long long round = 0;; ++round) {
+    if (round > n / 4 + 2) return NUHTC_E_CAPACITY;
     if (hipMemsetAsync(a.flags, 0, sizeof(int), s) != hipSuccess) return NUHTC_E_HIP;
     for (int k = 0; k < 4; ++k) hipLaunchKernelGGL(merge_round_kernel, dim3(nb), dim3(256), 0, s, a);
     if (hipMemcpyAsync(h_flags, a.flags, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return NUHTC_E_HIP;
