@@ -892,6 +892,25 @@ int nuhtc_op_ring_fill(int device, const int32_t* verts, int64_t nv, const int64
 int nuhtc_op_frame_gather(int device, const uint8_t* block, int bh, int bw, int bx, int by, const int32_t* origin, int n, int S,
                           uint8_t* frames, void* stream);
 
+/* Per-nucleus Fourier-descriptor integers for the Shape.FSD1..6 features (csrc/nucfsd.hip): INTEGERS ONLY, a pure function of the ORDERED
+ * RING of a nucleus -- the verts / ring_off of nuhtc_op_ring_fill above, read the same way; no mask, no frame, no tile.  Engine-free like
+ * nuhtc_op_ring_fill: every pointer is device memory of `device`; the call enqueues ONE launch on `stream` and does not synchronise.
+ * Edge e of a ring of n vertices runs from vertex e to vertex (e + 1) mod n; it is on the chain when dx == 0, dy == 0 or |dx| == |dy|
+ * (max(|dx|, |dy|) axial unit steps of length 1, or diagonal ones of length sqrt 2; a zero-length edge contributes nothing).  a_e and b_e
+ * are the axial and diagonal steps on the edges before e, A and B the totals: the perimeter is A + B sqrt 2.
+ * rows [n][644] int32: status, A, B, n, then for each sample k = 0 .. 127 the five numbers x_e, y_e, d_e, a_e, b_e of the edge e(k) that
+ *   holds the point at k / 128 of the perimeter: its start vertex, its Freeman code (0 = east, counter-clockwise on the screen, as
+ *   nuhtc_mask_contours numbers them; 0 for a zero-length edge) and its start length.  e(k) is the largest e with a_e + b_e sqrt 2 <=
+ *   (k / 128) (A + B sqrt 2), decided exactly in integers as the sign of p + q sqrt 2 with p = 128 a_e - k A, q = 128 b_e - k B (that of
+ *   p and q where they agree, otherwise p^2 against 2 q^2 in int64): a sample on a vertex belongs to the edge that leaves it.
+ * status [n] int32, also word 0 of the row: 0 = measured; 1 = degenerate (no vertex, or A + B == 0); 2 = not a traced ring (an edge off
+ *   the chain, or ring_off leaves [0, nv] or decreases: nuhtc_op_ring_fill's 2); 3 = A + B > 2^24 steps (beyond it the int64 squares are
+ *   not safe).  With a status other than 0 the other 643 words of the row are 0.  A ring may have any number of vertices.
+ * nuhtc_amd/nucfsd.py (fsd_reference) restates the row in numpy and derives the six named features on the host.  A call writes the rows
+ * and statuses of its n rings and nothing else; the same input gives the same bits on every call.  nuhtc_config is unchanged (no ABI
+ * bump).  NUHTC_E_INVALID, before anything is launched: a null pointer, n outside 1 .. 4096, nv outside 1 .. 2^30. */
+int nuhtc_op_ring_fsd(int device, const int32_t* verts, int64_t nv, const int64_t* ring_off, int n, int32_t* rows, int32_t* status, void* stream);
+
 /* Cell graph of a slide (csrc/cellgraph.hip; nuhtc_amd/cellgraph.py has the definition and its brute-force int64 restatement `graph_reference`):
  * for every nucleus its k nearest nuclei within a radius, and the class census of that disc.  Not in the reference.  Engine-free like
  * nuhtc_merge_overlap: every pointer is device memory of `device`, the call allocates and frees its own scratch, runs on `stream` and

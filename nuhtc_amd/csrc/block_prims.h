@@ -1,5 +1,5 @@
 // Device building blocks shared by the kernels of several translation units (gfx950, wave64), one copy of each: full-wave reductions,
-// the descending-score sort keys, the LDS bitonic sort, next_pow2 and the 1024-thread exclusive scan.  Header-only; every function is
+// the descending-score sort keys, the LDS bitonic sort, next_pow2 and the block-wide exclusive scan.  Header-only; every function is
 // __forceinline__ and keeps one fixed operation order, so a kernel computes the same bits whichever file it lives in.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -72,25 +72,31 @@ __device__ __forceinline__ void bitonic_sort_u64(unsigned long long* key, int np
     }
 }
 
-// block-wide exclusive scan of one int per thread (blockDim.x == 1024), returns exclusive prefix, *total gets the sum; lds16: 17 ints
-__device__ __forceinline__ int block_exscan_1024(int v, int* lds16, int* total) {
+// block-wide exclusive scan of one int per thread (blockDim.x == NT, a multiple of 64 up to 1024), returns exclusive prefix, *total gets
+// the sum; lds: NT / 64 + 1 ints
+template <int NT>
+__device__ __forceinline__ int block_exscan(int v, int* lds, int* total) {
+  constexpr int NW = NT / 64;
+  static_assert(NT % 64 == 0 && NW >= 1 && NW <= 16, "whole waves, and their sums scanned by one");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int incl = v;
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) { int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-  if (lane == 63) lds16[wave] = incl;
+  if (lane == 63) lds[wave] = incl;
   __syncthreads();
   if (wave == 0) {
-    int w = lane < 16 ? lds16[lane] : 0;
+    int w = lane < NW ? lds[lane] : 0;
     int wi = w;
 #pragma unroll
-    for (int o = 1; o < 16; o <<= 1) { int t = __shfl_up(wi, o); if (lane >= o) wi += t; }
-    if (lane < 16) lds16[lane] = wi - w;
-    if (lane == 15) lds16[16] = wi;
+    for (int o = 1; o < NW; o <<= 1) { int t = __shfl_up(wi, o); if (lane >= o) wi += t; }
+    if (lane < NW) lds[lane] = wi - w;
+    if (lane == NW - 1) lds[NW] = wi;
   }
   __syncthreads();
-  int res = lds16[wave] + incl - v;
-  *total = lds16[16];
+  int res = lds[wave] + incl - v;
+  *total = lds[NW];
   __syncthreads();
   return res;
 }
+// blockDim.x == 1024; lds16: 17 ints
+__device__ __forceinline__ int block_exscan_1024(int v, int* lds16, int* total) { return block_exscan<1024>(v, lds16, total); }

@@ -156,7 +156,7 @@ EXPORTS = ['nuhtc_default_config', 'nuhtc_create', 'nuhtc_destroy', 'nuhtc_last_
            'nuhtc_stitch_gather', 'nuhtc_stitch_pairs', 'nuhtc_stitch_render', 'nuhtc_op_stitch_gather', 'nuhtc_op_stitch_pairs', 'nuhtc_op_stitch_render',
            'nuhtc_tissue_mask', 'nuhtc_points_polygon_test', 'nuhtc_grid_in_contour', 'nuhtc_rle_encode',
            'nuhtc_nucleus_features', 'nuhtc_op_nucleus_pool', 'nuhtc_cell_graph', 'nuhtc_nucleus_morph', 'nuhtc_op_nucleus_morph',
-           'nuhtc_nucleus_texture', 'nuhtc_op_nucleus_texture', 'nuhtc_op_nucleus_gradient', 'nuhtc_op_nucleus_shape', 'nuhtc_op_ring_fill', 'nuhtc_op_frame_gather',
+           'nuhtc_nucleus_texture', 'nuhtc_op_nucleus_texture', 'nuhtc_op_nucleus_gradient', 'nuhtc_op_nucleus_shape', 'nuhtc_op_ring_fill', 'nuhtc_op_frame_gather', 'nuhtc_op_ring_fsd',
            'nuhtc_op_patch_embed', 'nuhtc_op_layernorm', 'nuhtc_op_merge_ln', 'nuhtc_op_fpn_lateral', 'nuhtc_op_sem_fuse', 'nuhtc_op_pointwise64',
            'nuhtc_op_fpn_mean_pool']
 
@@ -249,6 +249,7 @@ def load():
     lib.nuhtc_op_nucleus_shape.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, ci, vp, vp]
     lib.nuhtc_op_ring_fill.argtypes =[ci, vp, ctypes.c_int64, vp, vp, ci, ci, vp, vp, vp]
     lib.nuhtc_op_frame_gather.argtypes = [ci, vp, ci, ci, ci, ci, vp, ci, ci, vp, vp]
+    lib.nuhtc_op_ring_fsd.argtypes = [ci, vp, ctypes.c_int64, vp, ci, vp, vp, vp]
     lib.nuhtc_export_kept.argtypes = [vp, ctypes.POINTER(Dets), ci, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.nuhtc_export_crops.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, ci, vp]
     lib.nuhtc_profile_enable.argtypes = [ci]

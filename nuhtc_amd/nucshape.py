@@ -6,7 +6,7 @@ of the integers (np.add.reduceat on the rectangle's crop); the device must equal
 function of its mask: no tile, no stain table.  histomicstk's names and meaning; the box counts are the project's own definition --
 written from the numpy-100 #87 box-counting recipe that histomicstk uses for Shape.FractalDimension, and not compared with histomicstk
 itself, which is not a dependency.  The Hu moments are scikit-image's (regionprops(...).moments_hu of 0.18.3, which histomicstk calls;
-tests/golden/nucshape_skimage.npz).  histomicstk's third shape family, Shape.FSD1..6, is NOT produced.
+tests/golden/nucshape_skimage.npz).  histomicstk's third shape family, Shape.FSD1..6, is a function of the ring, not of the mask: nucfsd.py.
 
 Mask.  A binary mask M in an H x W frame; x is the column, y the row, both frame pixels.
 

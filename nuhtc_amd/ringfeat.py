@@ -11,6 +11,9 @@ in front of them and behind them:
     (shape=True: nuhtc_op_nucleus_shape on the same masks and nucshape.derive -> the seven Shape.HuMoments* and Shape.FractalDimension,
                last among the feature columns; nothing outside the mask is read, so the frames above serve, and every measured nucleus
                has its row -- there is no NULL case)
+    (fsd=True: nuhtc_op_ring_fsd on the rings and offsets the fill already uploaded -- no mask, no frame -- and nucfsd.derive -> the six
+               Shape.FSD*, last among the feature columns, behind the shape columns when both are selected; a ring the fill kept is
+               traced, has a vertex and at most 256 pixels a side, so its row has the status 0 or 1 and there is no NULL case either)
     write_db / read_db / missing_ids     the SQLite file and the reference's resume rule
 
 What is measured is the nucleus the DOCUMENT describes: the traced ring with its holes filled (contours.fill_rings defines the pixel set;
@@ -39,7 +42,7 @@ import sqlite3
 
 import numpy as np
 
-from . import nucgrad, nucmorph, nucshape, nuctex
+from . import nucfsd, nucgrad, nucmorph, nucshape, nuctex
 
 SIDES = (32, 64, 128, 256)
 MAX_SIDE = SIDES[-1]
@@ -132,6 +135,13 @@ def add_shape_flags(parser):
     parser.add_argument('--shape', action='store_true', default=False,
                         help='add Shape.HuMoments1..7 (scikit-image\'s moments_hu, which histomicstk calls) and Shape.FractalDimension (histomicstk\'s '
                              'name and meaning; the box counts are the project\'s own definition, nuhtc_amd/nucshape.py) behind the other feature columns')
+
+
+def add_fsd_flags(parser):
+    """The command-line form of the Fourier-descriptor selection (tools/wsi_feat_extract.py): --fsd."""
+    parser.add_argument('--fsd', action='store_true', default=False,
+                        help='add Shape.FSD1..6 (histomicstk\'s names and meaning, the project\'s own definition, nuhtc_amd/nucfsd.py: the ring walked in '
+                             'contour order and resampled exactly at 128 points; not compared with histomicstk) last among the feature columns')
 
 
 def block_plan(rect, slide_hw, block=2048):
@@ -299,6 +309,18 @@ class _Ops:
             self._fail('nuhtc_op_nucleus_shape', rc)
         return rows
 
+    def fsd(self, verts, ring_off):
+        """verts int32 (nv, 2), ring_off int64 (n + 1,) -> rows int32 (n, 644): nuhtc_op_ring_fsd on the arrays of fill()."""
+        t = self.torch
+        n = int(ring_off.shape[0]) - 1
+        rows = t.empty(n, nucfsd.ROW, dtype=t.int32, device=self.device)
+        status = t.empty(n, dtype=t.int32, device=self.device)
+        rc = self.lib.nuhtc_op_ring_fsd(self.index, self._need(verts, t.int32, 'verts'), int(verts.shape[0]), self._need(ring_off, t.int64, 'ring_off'), n,
+                                        ctypes.c_void_p(rows.data_ptr()), ctypes.c_void_p(status.data_ptr()), self._stream())
+        if rc:
+            raise RuntimeError(f'nuhtc_op_ring_fsd failed ({rc})')
+        return rows
+
 
 def pack_rings(rings):
     """list of (k, 2) integer rings -> (verts int32 (sum k, 2), ring_off int64 (n + 1,))."""
@@ -307,7 +329,7 @@ def pack_rings(rings):
     return verts, np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
 
 
-def measure(slide, features, device=0, block=2048, timings=None, gradient=False, edge_thr=nucgrad.T_DEFAULT, shape=False):
+def measure(slide, features, device=0, block=2048, timings=None, gradient=False, edge_thr=nucgrad.T_DEFAULT, shape=False, fsd=False):
     """slide: an (H, W, 3) uint8 RGB array (a memory-mapped .npy slide) or anything with read_region (level 0 is read); features: GeoJSON
     features, or the result of parse().  The slide is walked in blocks of `block` pixels (block_plan): every block that owns a nucleus is
     read once and uploaded once, and per block and frame side, in chunks of at most 4096 nuclei, the gather, the ring fill and the two
@@ -319,7 +341,8 @@ def measure(slide, features, device=0, block=2048, timings=None, gradient=False,
     frames (module docstring) with the edge threshold `edge_thr` (quarter grey levels, 1 .. 1442), and grad_ok bool (n,), False where
     the rectangle plus margin exceeds 256 pixels (a zero row); every other field is the same bytes as without.  shape=True: the result
     gains shape int64 (n, 24), the rows of nuhtc_amd.nucshape measured on the masks of the morphometry; every other field is the same
-    bytes as without."""
+    bytes as without.  fsd=True: the result gains fsd int32 (n, 644), the rows of nuhtc_amd.nucfsd measured on the rings and offsets the
+    fill uploaded (nothing more is uploaded); every other field is the same bytes as without."""
     import time
     import torch
     p = features if isinstance(features, dict) and 'rings' in features else parse(features)
@@ -331,6 +354,8 @@ def measure(slide, features, device=0, block=2048, timings=None, gradient=False,
     keep = np.zeros(n, bool)
     if shape:
         rows = np.zeros((n, nucshape.ROW), np.int64)
+    if fsd:
+        frows = np.zeros((n, nucfsd.ROW), np.int32)
     if gradient:
         if not nucgrad.T_MIN <= int(edge_thr) <= nucgrad.T_MAX:
             raise ValueError(f'measure: edge_thr {edge_thr} outside {nucgrad.T_MIN} .. {nucgrad.T_MAX} quarter levels')
@@ -372,6 +397,8 @@ def measure(slide, features, device=0, block=2048, timings=None, gradient=False,
                     r, h, g = ops.morph_tex(frames, masks)
                     if shape:
                         rows[idx] = ops.shape(masks).cpu().numpy()
+                    if fsd:
+                        frows[idx] = ops.fsd(verts_d, off_d).cpu().numpy()
                     t0 = lap('measure', t0)
                     st = status.cpu().numpy()
                     if (st == 1).any():
@@ -401,20 +428,23 @@ def measure(slide, features, device=0, block=2048, timings=None, gradient=False,
         out.update(grad=grad[sel], grad_ok=gsides[sel] > 0, grad_origin=gorigin[sel])
     if shape:
         out.update(shape=rows[sel])
+    if fsd:
+        out.update(fsd=frows[sel])
     return out
 
 
-def table_columns(gradient=False, shape=False):
-    """The names of table()'s columns: the 29 nucmorph.COLUMNS, the 26 nuctex.COLUMNS and, with the selections, the 8 nucgrad.COLUMNS and
-    then the 8 nucshape.COLUMNS."""
-    return nucmorph.COLUMNS + nuctex.COLUMNS + (nucgrad.COLUMNS if gradient else ()) + (nucshape.COLUMNS if shape else ())
+def table_columns(gradient=False, shape=False, fsd=False):
+    """The names of table()'s columns: the 29 nucmorph.COLUMNS, the 26 nuctex.COLUMNS and, with the selections, the 8 nucgrad.COLUMNS, then
+    the 8 nucshape.COLUMNS and then the 6 nucfsd.COLUMNS."""
+    return nucmorph.COLUMNS + nuctex.COLUMNS + (nucgrad.COLUMNS if gradient else ()) + (nucshape.COLUMNS if shape else ()) + (nucfsd.COLUMNS if fsd else ())
 
 
-def table(m, gradient=False, shape=False):
+def table(m, gradient=False, shape=False, fsd=False):
     """measure()'s result -> (columns, float64 (n, 55)): nucmorph.derive(raw, hist, origin) beside nuctex.derive(glcm).  gradient=True (of
     a measure(gradient=True)): (n, 63), nucgrad.derive(grad) behind them, NaN in the eight columns of a nucleus without a gradient frame.
     shape=True (of a measure(shape=True)): eight more columns, nucshape.derive(shape), last -- behind the gradient's when both are
-    selected (n, 71), behind the texture's otherwise (n, 63); they are never NaN."""
+    selected (n, 71), behind the texture's otherwise (n, 63); they are never NaN.  fsd=True (of a measure(fsd=True)): six more columns,
+    nucfsd.derive(fsd), behind all of these; they are never NaN."""
     c1, v1 = nucmorph.derive(m['raw'], m['hist'], m['origin'])
     c2, v2 = nuctex.derive(m['glcm'])
     cols, vals = tuple(c1) + tuple(c2), [v1, v2]
@@ -424,26 +454,29 @@ def table(m, gradient=False, shape=False):
     if shape:
         c4, v4 = nucshape.derive(m['shape'])
         cols, vals = cols + tuple(c4), vals + [v4]
+    if fsd:
+        c5, v5 = nucfsd.derive(m['fsd'])
+        cols, vals = cols + tuple(c5), vals + [v5]
     return cols, np.concatenate(vals, 1)
 
 
-def db_columns(gradient=False, shape=False):
+def db_columns(gradient=False, shape=False, fsd=False):
     """[(name, SQLite type)] of the table `nuclei_features`, in order: Label (always 1, as histomicstk labels a one-nucleus crop), the 29
     nucmorph.COLUMNS and the 26 nuctex.COLUMNS (REAL; every '.' of a name replaced by '_', as the reference does before to_sql), with
-    the selections the 8 nucgrad.COLUMNS and then the 8 nucshape.COLUMNS in the same form, score, type, class_id, nuclei_id, and the vertex
-    extremes x_min, y_min, x_max, y_max."""
-    cols = [('Label', 'INTEGER')] + [(c.replace('.', '_'), 'REAL') for c in table_columns(gradient, shape)]
+    the selections the 8 nucgrad.COLUMNS, then the 8 nucshape.COLUMNS and then the 6 nucfsd.COLUMNS in the same form, score, type, class_id,
+    nuclei_id, and the vertex extremes x_min, y_min, x_max, y_max."""
+    cols = [('Label', 'INTEGER')] + [(c.replace('.', '_'), 'REAL') for c in table_columns(gradient, shape, fsd)]
     return cols + [('score', 'REAL'), ('type', 'TEXT'), ('class_id', 'INTEGER'), ('nuclei_id', 'INTEGER'),
                    ('x_min', 'INTEGER'), ('y_min', 'INTEGER'), ('x_max', 'INTEGER'), ('y_max', 'INTEGER')]
 
 
-def column_mismatch(path, gradient=False, shape=False):
-    """None when `path` holds no table nuclei_features or one with exactly the columns of db_columns(gradient, shape); otherwise what
+def column_mismatch(path, gradient=False, shape=False, fsd=False):
+    """None when `path` holds no table nuclei_features or one with exactly the columns of db_columns(gradient, shape, fsd); otherwise what
     differs, in words: such a table is neither appended to nor altered."""
     got = read_db(path)
     if got is None:
         return None
-    have, want = [c for c, _ in got['columns']], [c for c, _ in db_columns(gradient, shape)]
+    have, want = [c for c, _ in got['columns']], [c for c, _ in db_columns(gradient, shape, fsd)]
     if have == want:
         return None
     extra, lack = [c for c in have if c not in want], [c for c in want if c not in have]
@@ -451,19 +484,19 @@ def column_mismatch(path, gradient=False, shape=False):
            ('it lacks the requested columns: ' + ', '.join(lack) if lack else '') or 'its columns are in another order'
 
 
-def write_db(path, values, score, kind, class_id, nuclei_id, rect, gradient=False, shape=False):
-    """Appends one row per nucleus to the table nuclei_features of the SQLite file `path` (created with db_columns(gradient, shape) when
+def write_db(path, values, score, kind, class_id, nuclei_id, rect, gradient=False, shape=False, fsd=False):
+    """Appends one row per nucleus to the table nuclei_features of the SQLite file `path` (created with db_columns(gradient, shape, fsd) when
     missing): values float (n, 55) = table()[1], or (n, 63) = table(gradient=True)[1], whose NaN are written as NULL; with shape=True
-    eight columns more, table(gradient, shape)[1].  A file of any size
+    eight columns more, with fsd=True six more, table(gradient, shape, fsd)[1].  A file of any size
     is kept -- the reference deletes a database under 1 MB as broken; a complete small table is complete.  ValueError, with the file
     untouched, when it holds a table with another column set (column_mismatch).  -> the number of rows written."""
-    values = np.asarray(values, np.float64).reshape(-1, len(table_columns(gradient, shape)))
+    values = np.asarray(values, np.float64).reshape(-1, len(table_columns(gradient, shape, fsd)))
     rect = np.asarray(rect, np.int64).reshape(-1, 4)
     n = len(values)
     if not (len(score) == len(kind) == len(class_id) == len(nuclei_id) == len(rect) == n):
         raise ValueError('write_db: one row per nucleus in every field')
-    cols = db_columns(gradient, shape)
-    why = column_mismatch(path, gradient, shape)
+    cols = db_columns(gradient, shape, fsd)
+    why = column_mismatch(path, gradient, shape, fsd)
     if why:
         raise ValueError(f'write_db: {path} holds another column set ({why})')
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)

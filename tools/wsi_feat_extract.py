@@ -4,7 +4,7 @@ GeoJSON a detection run wrote, into <segdir>/<id>/nuclei_feat.db (SQLite, one ta
 
     python tools/wsi_feat_extract.py DATADIR --segdir SEGDIR [--start 0] [--end N] [--mag 40] [--reverse] [--bs_size 1024]
                                      [--num_workers 8] [--slide_ext .svs] [--geojson merged|plain] [--device 0]
-                                     [--gradient [--edge-thr LEVELS]] [--shape]
+                                     [--gradient [--edge-thr LEVELS]] [--shape] [--fsd]
 
 For every slide id (the sorted, extension-stripped names in DATADIR, sliced as the reference slices them) it reads
 <segdir>/<id>/<id>_merged.geojson (`--geojson plain`: <id>.geojson, whose nuclei_id is the position in the file), opens the slide as
@@ -17,8 +17,9 @@ reference does), score, type, class_id, nuclei_id, x_min, y_min, x_max, y_max (t
   * the intensity scale (Nucleus.Intensity.*) and the grey levels (Haralick.*) are THE PROJECT'S OWN fixed-point haematoxylin scale, not
     histomicstk's 8-bit stain image and crop-dependent grey limits: the columns have histomicstk's names and meaning, not its numbers;
   * Identifier.* are slide pixels at level 0;
-  * of histomicstk's shape families, the Hu moments and the fractal dimension come with --shape (below); FSD (Shape.FSD1..6) is the
-    only histomicstk family that is not produced.
+  * of histomicstk's shape families, the Hu moments and the fractal dimension come with --shape and the Fourier descriptors
+    (Shape.FSD1..6) with --fsd (both below): every histomicstk family is produced.  FSD is the
+    only histomicstk family that is not produced from the mask: it is a function of the ordered ring.
 --gradient adds the eight Nucleus.Gradient.* columns of nuhtc_amd/nucgrad.py between the Haralick columns and score: the gradient
 magnitude of the same haematoxylin scale (Mag.Mean, Mag.Std in grey levels per pixel, Mag.Skewness, Mag.Kurtosis, Mag.HistEntropy and
 Mag.HistEnergy of a ten-bin histogram over the nucleus's own range) and an edge count (Canny.Sum, Canny.Mean).  The edge count is THE
@@ -34,13 +35,19 @@ sizes s = 4, 8, .. up to the rectangle's smaller side -- histomicstk's names and
 (boxes anchored at the rectangle's corner, written from the numpy-100 recipe histomicstk uses, not compared with histomicstk itself).
 Both are functions of the mask alone and every measured nucleus has them: there is no NULL.  The other columns are the same bytes with
 and without the flag.
+--fsd adds the six columns of nuhtc_amd/nucfsd.py, Shape.FSD1..6, last among the feature columns (behind the shape columns when both flags
+are given, before score): the share of six frequency bands in the spectrum of the boundary's tangent angle, taken at 128 points spaced
+evenly along the perimeter.  histomicstk's names and meaning, THE PROJECT'S OWN DEFINITION, not compared with histomicstk: the ring is
+walked in CONTOUR order (histomicstk hands its routine the boundary pixels in raster order), and the resampling is exact -- the GPU decides
+in integers which edge of the ring holds each point (csrc/nucfsd.hip, on the rings the fill already uploaded).  Every measured nucleus
+has them: there is no NULL.  The other columns are the same bytes with and without the flag.
 Only TRACED RINGS are measured -- integer vertices on pixel centres, edges along the eight chain directions: what tools/infer_wsi.py
 writes, here and in the reference.  The measured pixels are the ring's border and everything it encloses (holes filled).  Arbitrary
 polygons (float coordinates, other edge directions), nuclei wider or taller than 256 pixels and rings that leave the slide are left out
 and counted; the closing line on stderr gives, per slide, the rows written and the rows left out by reason.
 
 Resume, as the reference: a database that already holds every nuclei_id of the file skips the slide; otherwise only the missing nuclei
-are measured and appended.  A database whose columns differ from the requested ones (written without --gradient or --shape and run with
+are measured and appended.  A database whose columns differ from the requested ones (written without --gradient, --shape or --fsd and run with
 it, or the other way round) is neither appended to nor altered: the slide is skipped with a message that names the file and the difference.
 NOT as the reference: a database under 1 MB is kept -- the reference deletes it as broken, but a complete
 small table is complete.
@@ -57,9 +64,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def build_parser():
-    """tools/wsi_feat_extract.py:239-250 of the reference, then three flags of our own, the two of the gradient selection (--gradient,
-    --edge-thr: nuhtc_amd.ringfeat.add_gradient_flags, beside what they select) and the one of the shape selection (--shape:
-    add_shape_flags)."""
+    """tools/wsi_feat_extract.py:239-250 of the reference, then four flags of our own, the two of the gradient selection (--gradient,
+    --edge-thr: nuhtc_amd.ringfeat.add_gradient_flags, beside what they select), the one of the shape selection (--shape:
+    add_shape_flags) and the one of the Fourier-descriptor selection (--fsd: add_fsd_flags)."""
     p = ArgumentParser(allow_abbrev=False)
     p.add_argument('datadir', help='path to folder containing raw wsi image files')
     p.add_argument('--segdir', help='path to folder containing segmentation files')
@@ -76,6 +83,7 @@ def build_parser():
     from nuhtc_amd import ringfeat
     ringfeat.add_gradient_flags(p)
     ringfeat.add_shape_flags(p)
+    ringfeat.add_fsd_flags(p)
     return p
 
 
@@ -91,13 +99,13 @@ def slide_ids(datadir, start=0, end=None, reverse=False):
     return ids[start:end] if end is not None else ids[start:]
 
 
-def extract_slide(slide_path, geojson_path, db_path, device=0, log=print, gradient=False, edge_thr=1, shape=False):
+def extract_slide(slide_path, geojson_path, db_path, device=0, log=print, gradient=False, edge_thr=1, shape=False, fsd=False):
     """One slide -> (rows written, {reason: left out}), or None when the table already holds every nucleus of the file.  gradient=True:
     with the gradient columns (edge_thr in quarter grey levels), -> (rows written, {reason: left out}, rows without a gradient frame).
-    shape=True: with the shape columns; the return value keeps its form.  An existing table with another column set: a string that says
+    shape=True, fsd=True: with the shape columns, with the Fourier descriptors; the return value keeps its form.  An existing table with another column set: a string that says
     what differs, and the file is not touched."""
     from nuhtc_amd import ringfeat, slides
-    why = ringfeat.column_mismatch(db_path, gradient, shape)
+    why = ringfeat.column_mismatch(db_path, gradient, shape, fsd)
     if why:
         return why
     with open(geojson_path) as f:
@@ -113,13 +121,13 @@ def extract_slide(slide_path, geojson_path, db_path, device=0, log=print, gradie
     # out, again)
     features = [dict(f, properties=dict(f.get('properties') or {}, nuclei_id=i)) for f, i in zip(features, every) if i in todo]
     if not gradient:
-        m = ringfeat.measure(slides.open_array_slide(slide_path), features, device=device, shape=shape)
-        _, values = ringfeat.table(m, shape=shape)
-        n = ringfeat.write_db(db_path, values, m['score'], m['type'], m['label'], m['nuclei_id'], m['rect'], shape=shape)
+        m = ringfeat.measure(slides.open_array_slide(slide_path), features, device=device, shape=shape, fsd=fsd)
+        _, values = ringfeat.table(m, shape=shape, fsd=fsd)
+        n = ringfeat.write_db(db_path, values, m['score'], m['type'], m['label'], m['nuclei_id'], m['rect'], shape=shape, fsd=fsd)
         return n, m['left_out']
-    m = ringfeat.measure(slides.open_array_slide(slide_path), features, device=device, gradient=True, edge_thr=edge_thr, shape=shape)
-    _, values = ringfeat.table(m, gradient=True, shape=shape)
-    n = ringfeat.write_db(db_path, values, m['score'], m['type'], m['label'], m['nuclei_id'], m['rect'], gradient=True, shape=shape)
+    m = ringfeat.measure(slides.open_array_slide(slide_path), features, device=device, gradient=True, edge_thr=edge_thr, shape=shape, fsd=fsd)
+    _, values = ringfeat.table(m, gradient=True, shape=shape, fsd=fsd)
+    n = ringfeat.write_db(db_path, values, m['score'], m['type'], m['label'], m['nuclei_id'], m['rect'], gradient=True, shape=shape, fsd=fsd)
     return n, m['left_out'], int((~m['grad_ok']).sum())
 
 
@@ -152,7 +160,7 @@ def main(argv=None):
             print(f'no slide {spath}, skipped\n')
             continue
         db = os.path.join(args.segdir, sid, 'nuclei_feat.db')
-        got = extract_slide(spath, gj, db, device=args.device, gradient=args.gradient, edge_thr=edge_thr, shape=args.shape)
+        got = extract_slide(spath, gj, db, device=args.device, gradient=args.gradient, edge_thr=edge_thr, shape=args.shape, fsd=args.fsd)
         if got is None:
             print(f'skipped:{sid}\n')
             continue
