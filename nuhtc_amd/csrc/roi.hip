@@ -231,8 +231,9 @@ __device__ __forceinline__ MapPlan map_plan(const RoiFeatParams& p, const float*
 // copies the three footprints (FPN level 0, semantic embedding, FPN level 1) into LDS with direct global->LDS loads
 // (one 256-byte pixel per instruction, no VGPR staging, all in flight at once), builds the per-axis bilinear tables
 // of the regular sampling grid once (14 sample columns + 14 sample rows per map, computed by 28 lanes in parallel), and
-// then evaluates the 49 bins from LDS with exactly the arithmetic of roi_bin() (same products, same summation order), so
-// both paths are bit-identical.  RoIs with a larger footprint fall back to the global-memory path.
+// then evaluates the bins from LDS: the 14x14 kernel with exactly the arithmetic of roi_bin() (bin_lds2: same products, same
+// summation order, bit-identical to the gather form), the 7x7 kernels in separable form (sep_build / sep_column below).  RoIs
+// with a larger footprint take the stream, big-box or giant forms.
 #define TP0 12
 #define TP1 7
 #define TS0 8      // small-tile variant of the LDS path
@@ -264,7 +265,7 @@ __device__ __forceinline__ int half_max(int v) {
   return v;
 }
 
-struct LevelPlan { AxisEnt ent; int fx0, fy0, fw, fh; bool ok, empty; };
+struct LevelPlan { AxisEnt ent; int fx0, fy0, fw, fh; bool ok, empty, valid; };   // valid: this lane's sample lies on the map
 
 // lanes 0..n-1 build the x entries, lanes 32..32+n-1 the y entries of a P x P bin grid with gsamp samples per bin and axis; the
 // footprint fits the tile when it is at most tp x tp pixels
@@ -280,6 +281,7 @@ __device__ __forceinline__ LevelPlan plan_level(const RoiGeom& g, int P, int gsa
   bool valid;
   lp.ent = axis_entry(c, is_y ? H : W, valid);
   valid = valid && active;
+  lp.valid = valid;
   const int lo = half_min(valid ? lp.ent.lo : (1 << 30));
   const int hi = half_max(valid ? lp.ent.hi : -1);
   const int x_lo = __shfl(lo, 0), x_hi = __shfl(hi, 0), y_lo = __shfl(lo, 32), y_hi = __shfl(hi, 32);
@@ -969,19 +971,87 @@ __device__ __forceinline__ void lds_front(const RoiFeatParams& p, int b, const L
   __syncthreads();
 }
 
+// ---- the 7x7 box-head features from the staged footprints, in separable form.  A bin is  sum_y sum_x wy[y] * wx[x] * F[y][x]  with the
+// merged per-axis weights of its 2 samples (see merged_weight).  On a footprint of at most 12 (7) pixels the bins are under 2 (1.2) pixels
+// wide, a bin's two samples are half a bin apart, so their low pixels differ by at most one and the bin touches at most SEP_J = 3 pixels per
+// axis.  A half-wave (32 lanes x 2 channels, packed fp32) owns one bin COLUMN: per footprint row it contracts the column's 3 pixels from
+// LDS to one value (3 ds_read_b64, 3 packed multiply-adds) and adds it into the column's 7 bins with the row's dense y weights (7 packed
+// fmas; the weights of bins the row does not touch are 0, and adding 0 * t is exact: the maps are finite).  Per RoI and map that is
+// rows * 7 * 10 packed fmas and no per-tap weight or address arithmetic, against 196 samples * (4 weight products + 4 taps) of the
+// sample loop (bin_lds2, which the 14x14 kernel keeps).  Rows enter a bin's sum in ascending order: a box's features depend on nothing
+// but the box.  Rounding differs from the sample loop's by a few 1e-7 relative, within the same first-order bound: reference weight 1,
+// merged x and y weights 1 each (one add; / 2 is exact), x chain 3, y chain 3 (a bin has 3 non-zero rows), maps and tables 4, x0 + sem 1.
+#define SEP_J 3
+template <int TR>
+struct SepTabs {
+  __attribute__((aligned(16))) float wy[TR][8];   // merged y weight of bin ph at footprint row yr: wy[yr][ph] ([7] is padding)
+  __attribute__((aligned(16))) float wx[7][4];    // merged x weight of bin pw at its tap j ([3] is padding)
+  __attribute__((aligned(16))) int xo[7][4];      // element offset of that tap's pixel in a staged row (a tap past the row's end has
+};                                                // weight 0 and reads the row's last pixel: nothing outside the staged footprint is read)
+
+// item t (0 .. 7 * TR + 20) of a map's tables, from the plan's samples, which sit in the lanes of every wave (x samples of bin q in lanes
+// 2q, 2q + 1, y samples in lanes 32 + 2q, 33 + 2q; pixel indices relative to the footprint, invalid samples with zero weights)
+template <int TR>
+__device__ __forceinline__ void sep_build(const LevelPlan& lp, SepTabs<TR>* tb, int t) {
+  const bool is_y = t < 7 * TR;
+  const int u = is_y ? t : t - 7 * TR;
+  const bool act = is_y || u < 7 * SEP_J;
+  const int k = is_y ? u / 7 : u / SEP_J;                               // y: footprint row; x: bin
+  const int q = !act ? 0 : is_y ? u - 7 * k : k;                        // bin
+  const int j = u - SEP_J * k;                                          // x: tap
+  const int src = (is_y ? 32 : 0) + 2 * q;
+  const int key = lp.ent.lo | (lp.ent.hi << 8) | (lp.valid ? 1 << 16 : 0);
+  const int k0 = __shfl(key, src), k1 = __shfl(key, src + 1);
+  const float sl0 = __shfl(lp.ent.l, src), sh0 = __shfl(lp.ent.h, src), sl1 = __shfl(lp.ent.l, src + 1), sh1 = __shfl(lp.ent.h, src + 1);
+  const int lo0 = k0 & 255, hi0 = (k0 >> 8) & 255, lo1 = k1 & 255, hi1 = (k1 >> 8) & 255;
+  const bool v0 = (k0 >> 16) != 0, v1 = (k1 >> 16) != 0;
+  const int first = v0 ? (v1 ? min(lo0, lo1) : lo0) : (v1 ? lo1 : 0);   // the bin's first pixel
+  const int px = is_y ? k : first + j;
+  float w = 0.f;                                                        // merged_weight(): sample order, / samples per axis
+  if (v0) { if (lo0 == px) w += sh0; if (hi0 == px) w += sl0; }
+  if (v1) { if (lo1 == px) w += sh1; if (hi1 == px) w += sl1; }
+  w = w / 2.0f;
+  if (is_y) tb->wy[k][q] = w;
+  else if (act) { tb->wx[q][j] = w; tb->xo[q][j] = max(min(px, lp.fw - 1), 0) * 64; }
+}
+
+// bin column pw of one staged map into acc[ph] (two channels per lane; `tile` includes the lane's first channel)
+template <int TR>
+__device__ __forceinline__ void sep_column(const float* tile, const SepTabs<TR>* tb, int pw, int fw, int fh, v2f (&acc)[7]) {
+  const v4f wx = *reinterpret_cast<const v4f*>(tb->wx[pw]);
+  const int o0 = tb->xo[pw][0], o1 = tb->xo[pw][1], o2 = tb->xo[pw][2];
+  const v2f wx0 = {wx.x, wx.x}, wx1 = {wx.y, wx.y}, wx2 = {wx.z, wx.z};
+  const int pitch = fw * 64;
+#pragma unroll 2          // (two rows' reads in flight; unrolled further the kernel passes 80 VGPRs and loses the residency its LDS allows)
+  for (int yr = 0; yr < fh; ++yr) {
+    const float* row = tile + yr * pitch;
+    v2f t = wx0 * *reinterpret_cast<const v2f*>(row + o0);
+    t = __builtin_elementwise_fma(wx1, *reinterpret_cast<const v2f*>(row + o1), t);
+    t = __builtin_elementwise_fma(wx2, *reinterpret_cast<const v2f*>(row + o2), t);
+    const v4f ya = *reinterpret_cast<const v4f*>(tb->wy[yr]), yb = *reinterpret_cast<const v4f*>(tb->wy[yr] + 4);
+    const float wy[7] = {ya.x, ya.y, ya.z, ya.w, yb.x, yb.y, yb.z};
+#pragma unroll
+    for (int ph = 0; ph < 7; ++ph) {
+      const v2f w2 = {wy[ph], wy[ph]};
+      acc[ph] = __builtin_elementwise_fma(w2, t, acc[ph]);
+    }
+  }
+}
+
 template <int T0, int T1, int FLAG>
 __global__ __launch_bounds__(256) void roi_feat7_lds_kernel(RoiFeatParams p) {
   __shared__ float tile0[T0 * T0 * 64];
   __shared__ float tile1[T1 * T1 * 64];
-  __shared__ AxisEnt tab[2][2][16];
-  // one RoI per block: the 4 waves share the staged footprints and split the 49 bins, so each SIMD holds 4 waves of
-  // 4 different RoIs (LDS allows 4 blocks per CU) and the LDS / global latencies of one hide behind the others
+  __shared__ SepTabs<T0> tab0;
+  __shared__ SepTabs<T1> tab1;
+  // one RoI per block: the 4 waves share the staged footprints and split the 7 bin columns by half-wave, so each SIMD holds waves
+  // of different RoIs and the LDS / global latencies of one hide behind the others
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = blockIdx.x;
   if (r >= *p.r_dev || p.fb_flag[r] != FLAG) return;
   const float* roi = p.rois + (long long)r * 5;
   const int b = (int)roi[0];
-  const int cp2 = 2 * (lane & 31), hw = lane >> 5;     // bin loop: 2 channels per lane, one bin per half-wave
+  const int cp2 = 2 * (lane & 31), pw = threadIdx.x >> 5;     // 2 channels per lane, one bin column per half-wave (the eighth has none)
   v2f gsum[2];
   attn_term(p, roi, b, cp2, gsum);
   float* out = p.out + (long long)r * 49 * 64;
@@ -991,19 +1061,29 @@ __global__ __launch_bounds__(256) void roi_feat7_lds_kernel(RoiFeatParams p) {
   const LevelPlan l1 = plan_level(g1, 7, 2, p.H1, p.W1, T1, lane);
   // one sample per 14x14 semantic bin: one interpolation of the pre-added map x0 + sem serves both terms (see sem_separate)
   if (!(sem_g1 && l0.ok && l1.ok)) return;   // (cannot happen: roi_classify_kernel ran the same test)
-  lds_front(p, b, l0, l1, tile0, tile1, tab, lane, wave);
+  // the footprints are requested first and land while the merged weights are built: waves 0, 1 build level 0's tables, waves 2, 3 level 1's
+  stage_tile(p.x0sem, p.H0, p.W0, b, l0, tile0, lane, wave);
+  stage_tile(p.x1, p.H1, p.W1, b, l1, tile1, lane, wave);
+  if (wave < 2) sep_build<T0>(l0, &tab0, threadIdx.x);
+  else sep_build<T1>(l1, &tab1, threadIdx.x - 128);
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (pw >= 7) return;
   const v2f zero2 = {0.f, 0.f};
-  for (int pair = wave; pair < 25; pair += 4) {         // bins 2*pair and 2*pair + 1 (bin 49 does not exist)
-    const int bin = 2 * pair + hw;
-    const bool live = bin < 49;
-    const int bc = live ? bin : 48;
-    const int ph = bc / 7, pw = bc - ph * 7;
+  v2f a0[7], a1[7];
+#pragma unroll
+  for (int ph = 0; ph < 7; ++ph) a0[ph] = a1[ph] = zero2;
+  // (an empty footprint has no rows: the level's term stays 0)
+  sep_column<T0>(tile0 + cp2, &tab0, pw, __builtin_amdgcn_readfirstlane(l0.fw), __builtin_amdgcn_readfirstlane(l0.fh), a0);
+  sep_column<T1>(tile1 + cp2, &tab1, pw, __builtin_amdgcn_readfirstlane(l1.fw), __builtin_amdgcn_readfirstlane(l1.fh), a1);
+#pragma unroll
+  for (int ph = 0; ph < 7; ++ph) {
     v2f v = zero2;
-    v += l0.empty ? zero2 : bin_lds2<2>(tile0 + cp2, tab[0][0], tab[0][1], pw, ph);
-    v += l1.empty ? zero2 : bin_lds2<2>(tile1 + cp2, tab[1][0], tab[1][1], pw, ph);
+    v += a0[ph];
+    v += a1[ph];
     v += gsum[0];
     v += gsum[1];
-    if (live) *reinterpret_cast<v2f*>(out + bin * 64 + cp2) = v;
+    *reinterpret_cast<v2f*>(out + (ph * 7 + pw) * 64 + cp2) = v;
   }
 }
 
