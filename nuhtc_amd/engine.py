@@ -12,7 +12,7 @@ import sys
 import numpy as np
 import torch
 
-from . import hip, nuclei
+from . import hip, nuclei, ringfeat
 
 
 class HipError(RuntimeError):
@@ -947,27 +947,43 @@ class Engine:
                                                    vp(masks), K, H, W, vp(pairs), vp(n) if n is not None else None, n_max, vp(out), self._stream()))
         return out
 
-    def _op_nucleus_check(self, op, tiles, masks, pairs):
-        """The tiles / masks / pairs of the ops that read tile pixels (`op`: the name in the messages) -> B, K, H, W, n_max."""
-        for t, dt in ((tiles, torch.uint8), (masks, torch.int32), (pairs, torch.int32)):
+    def _op_nucleus_check(self, op, tiles, masks, pairs, W=None):
+        """The tiles / masks / pairs of a mask-list op (`op`: the name in the messages) -> B, K, H, W, n_max.  tiles=None: the ops that read
+        no tile; W is then the frame's width (None: 32 times the words of a row)."""
+        lone = tiles is None
+        kinds, forms = ('contiguous int32 masks and pairs on the engine\'s device', 'masks (B, K, H, (W + 31) // 32), pairs (n, 2)') if lone else \
+                       ('contiguous tensors on the engine\'s device (uint8 tiles, int32 masks and pairs)', 'tiles (B, H, W, 3), masks (B, K, H, (W + 31) // 32), pairs (n, 2)')
+        for t, dt in ((masks, torch.int32), (pairs, torch.int32)) + (() if lone else ((tiles, torch.uint8),)):
             if t.device != self.device or t.dtype != dt or not t.is_contiguous():
-                raise ValueError(f'{op}: contiguous tensors on the engine\'s device (uint8 tiles, int32 masks and pairs)')
-        if tiles.dim() != 4 or masks.dim() != 4 or tiles.shape[3] != 3 or tuple(pairs.shape[1:]) != (2,):
-            raise ValueError(f'{op}: tiles (B, H, W, 3), masks (B, K, H, (W + 31) // 32), pairs (n, 2)')
-        B, H, W = (int(v) for v in tiles.shape[:3])
+                raise ValueError(f'{op}: {kinds}')
+        if masks.dim() != 4 or tuple(pairs.shape[1:]) != (2,) or not (lone or (tiles.dim() == 4 and tiles.shape[3] == 3)):
+            raise ValueError(f'{op}: {forms}')
+        B, H, W = (int(masks.shape[0]), int(masks.shape[2]), int(masks.shape[3]) * 32 if W is None else int(W)) if lone else (int(v) for v in tiles.shape[:3])
         K, n_max = int(masks.shape[1]), int(pairs.shape[0])
         if tuple(masks.shape) != (B, K, H, (W + 31) // 32):
-            raise ValueError(f'{op}: tiles (B, H, W, 3), masks (B, K, H, (W + 31) // 32), pairs (n, 2)')
+            raise ValueError(f'{op}: {forms}')
         return B, K, H, W, n_max
 
-    def _op_nucleus_out(self, out, n_max, fields, error):
-        """The output tensors of a per-nucleus op, one per (shape behind n_max, dtype) of `fields`: zero-filled ones for None, else checked."""
+    def _op_nucleus_out(self, op, out, n_max, fields):
+        """The output tensors of a per-nucleus op, one per (name, shape behind n_max, dtype) of `fields`: zero-filled ones for None, else
+        checked."""
         if out is None:
-            return tuple(torch.zeros(n_max, *tail, dtype=dt, device=self.device) for tail, dt in fields)
-        for t, (tail, dt) in zip(out, fields):
-            if t.device != self.device or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != (n_max,) + tail:
-                raise ValueError(error)
+            return tuple(torch.zeros(n_max, *tail, dtype=getattr(torch, dt), device=self.device) for _, tail, dt in fields)
+        for t, (_, tail, dt) in zip(out, fields):
+            if t.device != self.device or t.dtype != getattr(torch, dt) or not t.is_contiguous() or tuple(t.shape) != (n_max,) + tail:
+                said = ', '.join(f'{dt} (n_max, {", ".join(str(v) for v in tail)})' for _, tail, dt in fields)
+                raise ValueError(f'{op}: out must be ' + (f'a contiguous {said} tensor' if len(fields) == 1 else f'contiguous ({said}) tensors') + ' on the engine\'s device')
         return tuple(out)
+
+    def _op_nucleus(self, fam, tiles, masks, pairs, W, channel_mode, n, out, ints=()):
+        """One mask-list op on raw arrays: `fam`, the entry of ringfeat.FAMILIES, names the C entry and its output fields; the checks,
+        the outputs and hip.op_nucleus.  -> the output tensor, or the tuple of them where the entry has several."""
+        op, one = fam.call[len('nuhtc_'):], len(fam.fields) == 1
+        B, K, H, W, n_max = self._op_nucleus_check(op, tiles, masks, pairs, W)
+        outs = self._op_nucleus_out(op, (out,) if one and out is not None else out, n_max, fam.fields)
+        self._check(hip.op_nucleus(self.lib, self.h, fam, (B, K, H, W), masks, pairs, outs, self._stream(), tiles,
+                                   None if tiles is None else self._morph_constants(), channel_mode, n, ints))
+        return outs[0] if one else outs
 
     def op_nucleus_morph(self, tiles, masks, pairs, channel_mode=hip.CH_AS_IS, n=None, out=None):
         """Per-nucleus morphometry integers on raw arrays (nuhtc_op_nucleus_morph; the numpy restatement is morph_reference of
@@ -976,63 +992,27 @@ class Engine:
         CH_SWAP: byte 2); n: None (all n_max entries) or an int32 device tensor whose first element is the number of entries (read on the
         device); out: (raw int64 (n_max, 16), hist int32 (n_max, 256)) contiguous device tensors to write into (rows from n on stay as they
         are), zero-filled ones otherwise.  -> (raw, hist).  Synchronous."""
-        B, K, H, W, n_max = self._op_nucleus_check('op_nucleus_morph', tiles, masks, pairs)
-        raw, hist = self._op_nucleus_out(out, n_max, (((16,), torch.int64), ((256,), torch.int32)),
-                                         'op_nucleus_morph: out must be contiguous (int64 (n_max, 16), int32 (n_max, 256)) tensors on the engine\'s device')
-        lut, k = self._morph_constants()
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())
-        self._check(self.lib.nuhtc_op_nucleus_morph(self.h, vp(tiles), int(channel_mode), vp(lut), k, B, vp(masks), K, H, W, vp(pairs),
-                                                    vp(n) if n is not None else None, n_max, vp(raw), vp(hist), self._stream()))
-        return raw, hist
+        return self._op_nucleus(ringfeat.MORPH, tiles, masks, pairs, None, channel_mode, n, out)
 
     def op_nucleus_texture(self, tiles, masks, pairs, channel_mode=hip.CH_AS_IS, n=None, out=None):
         """Per-nucleus grey-level co-occurrence counts on raw arrays (nuhtc_op_nucleus_texture; the numpy restatement is glcm_reference of
         the module nuclei.TEX draws on).  tiles, masks, pairs, channel_mode and n as in op_nucleus_morph; out: a contiguous int32 (n_max, 2, 136) device tensor to
         write into (rows from n on stay as they are), a zero-filled one otherwise.  -> out.  Synchronous."""
-        B, K, H, W, n_max = self._op_nucleus_check('op_nucleus_texture', tiles, masks, pairs)
-        out, = self._op_nucleus_out(None if out is None else (out,), n_max, (((2, 136), torch.int32),),
-                                    'op_nucleus_texture: out must be a contiguous int32 (n_max, 2, 136) tensor on the engine\'s device')
-        lut, k = self._morph_constants()
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())
-        self._check(self.lib.nuhtc_op_nucleus_texture(self.h, vp(tiles), int(channel_mode), vp(lut), k, B, vp(masks), K, H, W, vp(pairs),
-                                                      vp(n) if n is not None else None, n_max, vp(out), self._stream()))
-        return out
+        return self._op_nucleus(ringfeat.TEX, tiles, masks, pairs, None, channel_mode, n, out)
 
     def op_nucleus_gradient(self, tiles, masks, pairs, channel_mode=hip.CH_AS_IS, edge_thr=1, n=None, out=None):
         """Per-nucleus gradient integers on raw arrays (nuhtc_op_nucleus_gradient; the numpy restatement is nuhtc_amd.nucgrad.grad_reference).
         tiles, masks, pairs, channel_mode and n as in op_nucleus_morph; edge_thr: the edge threshold T in quarter grey levels, 1 .. 1442;
         out: a contiguous int64 (n_max, 18) device tensor to write into (rows from n on stay as they are), a zero-filled one otherwise.
         -> out.  Synchronous."""
-        B, K, H, W, n_max = self._op_nucleus_check('op_nucleus_gradient', tiles, masks, pairs)
-        out, = self._op_nucleus_out(None if out is None else (out,), n_max, (((18,), torch.int64),),
-                                    'op_nucleus_gradient: out must be a contiguous int64 (n_max, 18) tensor on the engine\'s device')
-        lut, k = self._morph_constants()
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())
-        self._check(self.lib.nuhtc_op_nucleus_gradient(self.h, vp(tiles), int(channel_mode), vp(lut), k, B, vp(masks), K, H, W, vp(pairs),
-                                                       vp(n) if n is not None else None, n_max, int(edge_thr), vp(out), self._stream()))
-        return out
+        return self._op_nucleus(ringfeat.GRADIENT, tiles, masks, pairs, None, channel_mode, n, out, (edge_thr,))
 
     def op_nucleus_shape(self, masks, pairs, W=None, n=None, out=None):
         """Per-nucleus shape integers on raw arrays (nuhtc_op_nucleus_shape; the numpy restatement is nuhtc_amd.nucshape.shape_reference).
         No tile is read.  masks: contiguous int32 device tensor (B, K, H, (W + 31) // 32), bit x & 31 of word x >> 5; W: the frame's width
         (None: 32 times the words of a row); pairs and n as in op_nucleus_morph; out: a contiguous int64 (n_max, 24) device tensor to write
         into (rows from n on stay as they are), a zero-filled one otherwise.  -> out.  Synchronous."""
-        for t in (masks, pairs):
-            if t.device != self.device or t.dtype != torch.int32 or not t.is_contiguous():
-                raise ValueError('op_nucleus_shape: contiguous int32 masks and pairs on the engine\'s device')
-        if masks.dim() != 4 or tuple(pairs.shape[1:]) != (2,):
-            raise ValueError('op_nucleus_shape: masks (B, K, H, (W + 31) // 32), pairs (n, 2)')
-        B, K, H, wpr = (int(v) for v in masks.shape)
-        W = wpr * 32 if W is None else int(W)
-        if (W + 31) // 32 != wpr:
-            raise ValueError('op_nucleus_shape: masks (B, K, H, (W + 31) // 32), pairs (n, 2)')
-        n_max = int(pairs.shape[0])
-        out, = self._op_nucleus_out(None if out is None else (out,), n_max, (((24,), torch.int64),),
-                                    'op_nucleus_shape: out must be a contiguous int64 (n_max, 24) tensor on the engine\'s device')
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())
-        self._check(self.lib.nuhtc_op_nucleus_shape(self.h, B, vp(masks), K, H, W, vp(pairs), vp(n) if n is not None else None, n_max, vp(out),
-                                                    self._stream()))
-        return out
+        return self._op_nucleus(ringfeat.SHAPE, None, masks, pairs, W, hip.CH_AS_IS, n, out)
 
     def op_eval_select(self, scores, counts, masks, fg_thr, thr, labels=None):
         """Score filter + greedy mask-NMS of `WSIDataset.evaluate` (nuhtc_op_eval_select): scores (B, K) float32, counts (B,), masks

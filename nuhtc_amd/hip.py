@@ -288,6 +288,19 @@ def default_config():
     return cfg
 
 
+def op_nucleus(lib, h, spec, dims, masks, pairs, outs, stream, tiles=None, stain=None, channel_mode=CH_AS_IS, n=None, ints=()):
+    """THE argument list of the mask-list ops nuhtc_op_nucleus_{morph,texture,gradient,shape} (Engine.op_nucleus_* and ringfeat._Ops call
+    nothing else).  spec: anything with .call (the C entry) and .reads ('tiles': the entry takes tiles, channel mode, stain table and
+    coefficients in front of the masks; 'masks': it does not) -- an entry of ringfeat.FAMILIES; dims = (B, K, H, W) of the masks, ints; tiles,
+    masks, pairs, outs (one per output field, in the entry's order) and n (None: all of pairs) are checked device tensors; stain = (device
+    table, host coefficients); ints: the entry's extra integers, passed behind n_max.  -> the entry's return code."""
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())
+    src = (vp(tiles), int(channel_mode), vp(stain[0]), stain[1]) if spec.reads == 'tiles' else ()
+    B, K, H, W = dims
+    return getattr(lib, spec.call)(h, *src, B, vp(masks), K, H, W, vp(pairs), vp(n) if n is not None else None, int(pairs.shape[0]),
+                                   *[int(i) for i in ints], *[vp(o) for o in outs], stream)
+
+
 BIND_REASON = {0: 'bound', -1: 'not a PCI address', -2: 'no such HIP device', -3: "the thread's own CPU mask excludes the GPU's NUMA node",
                -5: 'the host exposes no NUMA node for the device'}
 bind_reason = 'never called'          # why the last bind_host_thread of this process returned what it did (BIND_REASON)

@@ -7,14 +7,12 @@ in front of them and behind them:
     measure    the slide in blocks, per block and frame size: nuhtc_op_frame_gather (slide pixels -> one frame per nucleus),
                nuhtc_op_ring_fill (ring -> bit mask, csrc/ringfeat.hip), the two measurement ops -> raw, hist, glcm (integers)
     table      nucmorph.derive beside nuctex.derive -> the named float64 columns
-    (gradient=True: nuhtc_op_nucleus_gradient on a second, wider frame per nucleus and nucgrad.derive -> eight more columns; below)
-    (shape=True: nuhtc_op_nucleus_shape on the same masks and nucshape.derive -> the seven Shape.HuMoments* and Shape.FractalDimension,
-               last among the feature columns; nothing outside the mask is read, so the frames above serve, and every measured nucleus
-               has its row -- there is no NULL case)
-    (fsd=True: nuhtc_op_ring_fsd on the rings and offsets the fill already uploaded -- no mask, no frame -- and nucfsd.derive -> the six
-               Shape.FSD*, last among the feature columns, behind the shape columns when both are selected; a ring the fill kept is
-               traced, has a vertex and at most 256 pixels a side, so its row has the status 0 or 1 and there is no NULL case either)
     write_db / read_db / missing_ids     the SQLite file and the reference's resume rule
+
+Morphometry and texture are two of the five FAMILIES of measurements (the table below: what each is measured on, its C entry, its
+integers, its columns); gradient=True, shape=True and fsd=True select the other three.  measure, table, table_columns, db_columns,
+column_mismatch and write_db turn these keywords into a selection (`select`) at entry; everything below iterates that selection and
+names no family.
 
 What is measured is the nucleus the DOCUMENT describes: the traced ring with its holes filled (contours.fill_rings defines the pixel set;
 the device equals it bit for bit), independent of the tile frames of the run that wrote it.  Only traced rings are measured -- integer
@@ -39,10 +37,12 @@ on the way out.  No config file, no checkpoint."""
 import ctypes
 import os
 import sqlite3
+from collections import namedtuple
 
 import numpy as np
 
 from . import nucfsd, nucgrad, nucmorph, nucshape, nuctex
+from .nuclei import stain_constants
 
 SIDES = (32, 64, 128, 256)
 MAX_SIDE = SIDES[-1]
@@ -144,6 +144,67 @@ def add_fsd_flags(parser):
                              'contour order and resampled exactly at 128 points; not compared with histomicstk) last among the feature columns')
 
 
+# keyword   the argument of measure / table / table_columns / db_columns / column_mismatch / write_db that selects the family; None: always
+# flags     parser -> None: adds the family's command-line flags (tools/wsi_feat_extract.py); None: it has none
+# frame     the frames it is measured on, a Plan of PLANS: 'plain' (frame_sides, at the rectangle's corner) or 'margin' (gradient_frames)
+# call      the C entry; reads: what it takes -- 'tiles' (the frames' pixels and the masks), 'masks', or 'rings' (the vertices and offsets
+#           the fill uploaded: the ring, no frame; such a family rides on the plain frames' walk)
+# ints      its extra integer arguments: (keyword of measure, least, most, what the values are called)
+# fields    its result: (name in measure()'s dict, shape behind n, dtype)
+# derive    (the fields of some nuclei, their origins (n, 2)) -> (columns, float64 (n, len(columns)))
+# columns   the names of its table columns
+# lacking   None: every measured nucleus has the family.  Otherwise what the tool's closing line calls a nucleus without its frame;
+#           measure() then adds <first field>_ok and <first field>_origin, table() has NaN in its columns and write_db writes NULL
+Family = namedtuple('Family', 'keyword flags frame call reads ints fields derive columns lacking')
+
+MORPH = Family(None, None, 'plain', 'nuhtc_op_nucleus_morph', 'tiles', (), (('raw', (nucmorph.RAW,), 'int64'), ('hist', (nucmorph.BINS,), 'int32')),
+               lambda f, origin: nucmorph.derive(f[0], f[1], origin), nucmorph.COLUMNS, None)
+TEX = Family(None, None, 'plain', 'nuhtc_op_nucleus_texture', 'tiles', (), (('glcm', (len(nuctex.OFFSETS), nuctex.CELLS), 'int32'),),
+             lambda f, origin: nuctex.derive(f[0]), nuctex.COLUMNS, None)
+# the rows of nuhtc_amd.nucgrad on a second, wider frame per nucleus (module docstring), with the edge threshold `edge_thr` (quarter grey
+# levels); a nucleus whose rectangle plus margin exceeds 256 pixels has no such frame: a zero row, grad_ok False, NULL in the eight columns
+GRADIENT = Family('gradient', add_gradient_flags, 'margin', 'nuhtc_op_nucleus_gradient', 'tiles', (('edge_thr', nucgrad.T_MIN, nucgrad.T_MAX, 'quarter levels'),),
+                  (('grad', (nucgrad.ROW,), 'int64'),), lambda f, origin: nucgrad.derive(f[0]), nucgrad.COLUMNS,
+                  'gradient columns (rectangle plus margin over 256 px)')
+# the rows of nuhtc_amd.nucshape (the seven Shape.HuMoments* and Shape.FractalDimension) on the masks of the morphometry: nothing outside
+# the mask is read, so the plain frames serve, and every measured nucleus has its row
+SHAPE = Family('shape', add_shape_flags, 'plain', 'nuhtc_op_nucleus_shape', 'masks', (), (('shape', (nucshape.ROW,), 'int64'),),
+               lambda f, origin: nucshape.derive(f[0]), nucshape.COLUMNS, None)
+# the rows of nuhtc_amd.nucfsd (the six Shape.FSD*) on the rings and offsets the fill already uploaded -- no mask, no frame, nothing more
+# is uploaded; a ring the fill kept is traced, has a vertex and at most 256 pixels a side, so its row has the status 0 or 1: no NULL either
+FSD = Family('fsd', add_fsd_flags, 'plain', 'nuhtc_op_ring_fsd', 'rings', (), (('fsd', (nucfsd.ROW,), 'int32'),),
+             lambda f, origin: nucfsd.derive(f[0]), nucfsd.COLUMNS, None)
+FAMILIES = (MORPH, TEX, GRADIENT, SHAPE, FSD)               # the order of the table's columns, and of the launches on one chunk of a plan's frames
+EDGE_THR = nucgrad.T_DEFAULT                                # measure()'s default of the gradient's extra integer
+
+# frame     the `frame` of the families measured on it
+# frames    rect (n, 4) -> (origin int64 (n, 2), side int64 (n,); 0: the nucleus has no such frame)
+# margin    pixels a frame may start before its rectangle: every block is read with so many more to the left and above
+# strict    what the fill's status means.  True: 1 raises, 2 is counted 'not_traced' and the nucleus has no row in the result.  False: it is
+#           ignored -- a ring that is not traced gives a zero mask and a zero row here, and the strict plan takes the nucleus out
+Plan = namedtuple('Plan', 'frame frames margin strict')
+PLANS = (Plan('plain', lambda rect: (rect[:, :2], frame_sides(rect)), 0, True), Plan('margin', gradient_frames, GRAD_MARGIN, False))
+
+
+def select(**keywords):
+    """gradient= / shape= / fsd= -> the selected families, in the order of FAMILIES whatever the order of the keywords; the families
+    without a keyword are always among them.  TypeError for a keyword that selects no family."""
+    for k in keywords:
+        if k not in [f.keyword for f in FAMILIES if f.keyword]:
+            raise TypeError(f'{k!r} selects no family of nuclei measurements (' + ', '.join(f.keyword for f in FAMILIES if f.keyword) + ')')
+    return tuple(f for f in FAMILIES if f.keyword is None or keywords.get(f.keyword))
+
+
+def _ok(fam):
+    """The key of measure()'s result that says which nuclei have the family `fam` (one with `lacking`)."""
+    return fam.fields[0][0] + '_ok'
+
+
+def lacking(m, **keywords):
+    """measure()'s result -> {keyword: the nuclei that lack that family's frame}, an entry per selected family with `lacking`."""
+    return {f.keyword: int((~m[_ok(f)]).sum()) for f in select(**keywords) if f.lacking}
+
+
 def block_plan(rect, slide_hw, block=2048):
     """The walk of measure(): -> (blocks, off_slide).  blocks: list of (x, y, w, h, idx) -- the part of the slide [x, x + w) x [y, y + h)
     that is read for the block (`block` pixels and a 256-pixel halo to the right and below, cut at the slide's edge) and the rows idx of
@@ -192,8 +253,8 @@ def read_block(slide, x, y, w, h):
 
 
 class _Ops:
-    """The four device steps on torch tensors of one device: the two kernels of csrc/ringfeat.hip (engine-free) and the two measurement
-    ops behind a never-finalized engine handle (module docstring)."""
+    """The device steps on torch tensors of one device: the two kernels of csrc/ringfeat.hip (engine-free) and `run`, any entry of FAMILIES
+    -- the mask-list ops behind a never-finalized engine handle (module docstring)."""
 
     def __init__(self, device=0):
         import torch
@@ -208,7 +269,7 @@ class _Ops:
         rc = self.lib.nuhtc_create(ctypes.byref(cfg), self.index, ctypes.byref(self.h))
         if rc:
             raise RuntimeError(f'nuhtc_create failed ({rc}): {self.lib.nuhtc_last_error(None).decode()}')
-        lut, k = nucmorph.stain_constants()
+        lut, k = stain_constants()                  # the haematoxylin value of the entries that read 'tiles'
         self.lut = torch.from_numpy(lut).to(self.device)
         self.k = (ctypes.c_int32 * 3)(*[int(v) for v in k])
 
@@ -257,69 +318,32 @@ class _Ops:
             raise RuntimeError(f'nuhtc_op_ring_fill failed ({rc})')
         return masks, status
 
-    def _fail(self, name, rc):
-        raise RuntimeError(f'{name} failed ({rc}): {self.lib.nuhtc_last_error(self.h).decode()}')
-
-    def morph_tex(self, frames, masks):
-        """frames uint8 (n, S, S, 3), masks int32 (n, S, S // 32) -> (raw int64 (n, 16), hist int32 (n, 256), glcm int32 (n, 2, 136)):
-        the two measurement ops with B = n, K = 1 and the pairs (i, 0)."""
+    def pairs(self, n):
+        """int32 (n, 2) on the device: the pairs (i, 0) of the mask-list ops with B = n and K = 1."""
         t = self.torch
-        n, S = int(frames.shape[0]), int(frames.shape[1])
         pairs = t.zeros(n, 2, dtype=t.int32, device=self.device)
         pairs[:, 0] = t.arange(n, dtype=t.int32, device=self.device)
-        raw = t.empty(n, nucmorph.RAW, dtype=t.int64, device=self.device)
-        hist = t.empty(n, nucmorph.BINS, dtype=t.int32, device=self.device)
-        glcm = t.empty(n, len(nuctex.OFFSETS), nuctex.CELLS, dtype=t.int32, device=self.device)
-        vp = lambda x: ctypes.c_void_p(x.data_ptr())
-        rc = self.lib.nuhtc_op_nucleus_morph(self.h, vp(frames), self.hip.CH_AS_IS, vp(self.lut), self.k, n, vp(masks), 1, S, S, vp(pairs), None, n,
-                                             vp(raw), vp(hist), self._stream())
-        if rc:
-            self._fail('nuhtc_op_nucleus_morph', rc)
-        rc = self.lib.nuhtc_op_nucleus_texture(self.h, vp(frames), self.hip.CH_AS_IS, vp(self.lut), self.k, n, vp(masks), 1, S, S, vp(pairs), None, n,
-                                               vp(glcm), self._stream())
-        if rc:
-            self._fail('nuhtc_op_nucleus_texture', rc)
-        return raw, hist, glcm
+        return pairs
 
-    def gradient(self, frames, masks, edge_thr=nucgrad.T_DEFAULT):
-        """frames uint8 (n, S, S, 3), masks int32 (n, S, S // 32) -> grad int64 (n, 18): nuhtc_op_nucleus_gradient with B = n, K = 1 and
-        the pairs (i, 0)."""
+    def run(self, fam, pairs, frames=None, masks=None, verts=None, ring_off=None, ints=()):
+        """One entry of FAMILIES on one chunk of n nuclei -> its fields, device tensors (n, ...) in the entry's order.  pairs: pairs(n); of
+        frames uint8 (n, S, S, 3), masks int32 (n, S, S // 32) and the verts and ring_off of fill(), what the entry reads; ints: its extra
+        integers.  A mask-list op runs with B = n and K = 1 behind the never-finalized handle, a ring op on the arrays of fill()."""
         t = self.torch
-        n, S = int(frames.shape[0]), int(frames.shape[1])
-        pairs = t.zeros(n, 2, dtype=t.int32, device=self.device)
-        pairs[:, 0] = t.arange(n, dtype=t.int32, device=self.device)
-        grad = t.empty(n, nucgrad.ROW, dtype=t.int64, device=self.device)
-        vp = lambda x: ctypes.c_void_p(x.data_ptr())
-        rc = self.lib.nuhtc_op_nucleus_gradient(self.h, vp(frames), self.hip.CH_AS_IS, vp(self.lut), self.k, n, vp(masks), 1, S, S, vp(pairs), None, n,
-                                                int(edge_thr), vp(grad), self._stream())
+        n = int(pairs.shape[0])
+        outs = [t.empty(n, *tail, dtype=getattr(t, dt), device=self.device) for _, tail, dt in fam.fields]
+        if fam.reads == 'rings':
+            status = t.empty(n, dtype=t.int32, device=self.device)
+            rc = getattr(self.lib, fam.call)(self.index, self._need(verts, t.int32, 'verts'), int(verts.shape[0]), self._need(ring_off, t.int64, 'ring_off'), n,
+                                             *[ctypes.c_void_p(o.data_ptr()) for o in outs], ctypes.c_void_p(status.data_ptr()), self._stream())
+            if rc:
+                raise RuntimeError(f'{fam.call} failed ({rc})')
+            return outs
+        S = int(masks.shape[1])
+        rc = self.hip.op_nucleus(self.lib, self.h, fam, (n, 1, S, S), masks, pairs, outs, self._stream(), tiles=frames, stain=(self.lut, self.k), ints=ints)
         if rc:
-            self._fail('nuhtc_op_nucleus_gradient', rc)
-        return grad
-
-    def shape(self, masks):
-        """masks int32 (n, S, S // 32) -> shape int64 (n, 24): nuhtc_op_nucleus_shape with B = n, K = 1 and the pairs (i, 0)."""
-        t = self.torch
-        n, S = int(masks.shape[0]), int(masks.shape[1])
-        pairs = t.zeros(n, 2, dtype=t.int32, device=self.device)
-        pairs[:, 0] = t.arange(n, dtype=t.int32, device=self.device)
-        rows = t.empty(n, nucshape.ROW, dtype=t.int64, device=self.device)
-        vp = lambda x: ctypes.c_void_p(x.data_ptr())
-        rc = self.lib.nuhtc_op_nucleus_shape(self.h, n, vp(masks), 1, S, S, vp(pairs), None, n, vp(rows), self._stream())
-        if rc:
-            self._fail('nuhtc_op_nucleus_shape', rc)
-        return rows
-
-    def fsd(self, verts, ring_off):
-        """verts int32 (nv, 2), ring_off int64 (n + 1,) -> rows int32 (n, 644): nuhtc_op_ring_fsd on the arrays of fill()."""
-        t = self.torch
-        n = int(ring_off.shape[0]) - 1
-        rows = t.empty(n, nucfsd.ROW, dtype=t.int32, device=self.device)
-        status = t.empty(n, dtype=t.int32, device=self.device)
-        rc = self.lib.nuhtc_op_ring_fsd(self.index, self._need(verts, t.int32, 'verts'), int(verts.shape[0]), self._need(ring_off, t.int64, 'ring_off'), n,
-                                        ctypes.c_void_p(rows.data_ptr()), ctypes.c_void_p(status.data_ptr()), self._stream())
-        if rc:
-            raise RuntimeError(f'nuhtc_op_ring_fsd failed ({rc})')
-        return rows
+            raise RuntimeError(f'{fam.call} failed ({rc}): {self.lib.nuhtc_last_error(self.h).decode()}')
+        return outs
 
 
 def pack_rings(rings):
@@ -329,42 +353,37 @@ def pack_rings(rings):
     return verts, np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
 
 
-def measure(slide, features, device=0, block=2048, timings=None, gradient=False, edge_thr=nucgrad.T_DEFAULT, shape=False, fsd=False):
+def measure(slide, features, device=0, block=2048, timings=None, edge_thr=EDGE_THR, **keywords):
     """slide: an (H, W, 3) uint8 RGB array (a memory-mapped .npy slide) or anything with read_region (level 0 is read); features: GeoJSON
     features, or the result of parse().  The slide is walked in blocks of `block` pixels (block_plan): every block that owns a nucleus is
-    read once and uploaded once, and per block and frame side, in chunks of at most 4096 nuclei, the gather, the ring fill and the two
-    measurement ops run on the device.  -> dict(raw int64 (n, 16), hist int32 (n, 256), glcm int32 (n, 2, 136), origin int64 (n, 2), rect,
-    score, label, type, nuclei_id, left_out) for the n measured nuclei, in the order of the features.  left_out counts parse()'s reasons,
-    'off_slide' (the rectangle leaves the slide) and 'not_traced' (the ring fill's status 2: an edge off the chain directions).
-    `timings`: a dict that receives the seconds spent in read, upload, gather, fill and measure (each stage synchronised: for
-    tools/bench_ringfeat.py).  gradient=True: the result gains grad int64 (n, 18), the rows of nuhtc_amd.nucgrad measured on the gradient
-    frames (module docstring) with the edge threshold `edge_thr` (quarter grey levels, 1 .. 1442), and grad_ok bool (n,), False where
-    the rectangle plus margin exceeds 256 pixels (a zero row); every other field is the same bytes as without.  shape=True: the result
-    gains shape int64 (n, 24), the rows of nuhtc_amd.nucshape measured on the masks of the morphometry; every other field is the same
-    bytes as without.  fsd=True: the result gains fsd int32 (n, 644), the rows of nuhtc_amd.nucfsd measured on the rings and offsets the
-    fill uploaded (nothing more is uploaded); every other field is the same bytes as without."""
+    read once and uploaded once, and per block, plan of frames (PLANS) and frame side, in chunks of at most 4096 nuclei, the gather, the
+    ring fill and the selected families of that plan run on the device.  -> dict(raw int64 (n, 16), hist int32 (n, 256), glcm int32 (n, 2,
+    136), origin int64 (n, 2), rect, score, label, type, nuclei_id, left_out) for the n measured nuclei, in the order of the features.
+    left_out counts parse()'s reasons, 'off_slide' (the rectangle leaves the slide) and 'not_traced' (the ring fill's status 2: an edge
+    off the chain directions).  `timings`: a dict that receives the seconds spent in read, upload, gather, fill and measure (each stage
+    synchronised: for tools/bench_ringfeat.py).  gradient=True, shape=True, fsd=True (`select`): the result gains the fields of that
+    family -- grad int64 (n, 18) with the edge threshold `edge_thr` (quarter grey levels, 1 .. 1442), shape int64 (n, 24), fsd int32
+    (n, 644) -- and for a family a nucleus can lack (gradient: the rectangle plus margin exceeds 256 pixels) grad_ok bool (n,), False at
+    such a nucleus's zero row, and grad_origin int64 (n, 2); every other field is the same bytes as without."""
+    sel = select(**keywords)
     import time
     import torch
     p = features if isinstance(features, dict) and 'rings' in features else parse(features)
     left = dict(p['left_out'])
     n = len(p['rings'])
     rect = p['rect']
-    raw, hist = np.zeros((n, nucmorph.RAW), np.int64), np.zeros((n, nucmorph.BINS), np.int32)
-    glcm = np.zeros((n, len(nuctex.OFFSETS), nuctex.CELLS), np.int32)
+    ints = dict(edge_thr=edge_thr)
+    for f in sel:
+        for name, lo, hi, unit in f.ints:
+            if not lo <= int(ints[name]) <= hi:
+                raise ValueError(f'measure: {name} {ints[name]} outside {lo} .. {hi} {unit}')
+    res = {name: np.zeros((n,) + tail, dt) for f in sel for name, tail, dt in f.fields}
     keep = np.zeros(n, bool)
-    if shape:
-        rows = np.zeros((n, nucshape.ROW), np.int64)
-    if fsd:
-        frows = np.zeros((n, nucfsd.ROW), np.int32)
-    if gradient:
-        if not nucgrad.T_MIN <= int(edge_thr) <= nucgrad.T_MAX:
-            raise ValueError(f'measure: edge_thr {edge_thr} outside {nucgrad.T_MIN} .. {nucgrad.T_MAX} quarter levels')
-        grad = np.zeros((n, nucgrad.ROW), np.int64)
-        gorigin, gsides = gradient_frames(rect)
-    margin = GRAD_MARGIN if gradient else 0
+    plans = [(plan, [f for f in sel if f.frame == plan.frame]) for plan in PLANS]
+    plans = [(plan, fams, *plan.frames(rect)) for plan, fams in plans if fams]          # (plan, its selected families, origin (n, 2), side (n,))
+    margin = max(plan.margin for plan, *_ in plans)
     blocks, off = block_plan(rect, _slide_hw(slide), block)
     left['off_slide'] += len(off)
-    sides = frame_sides(rect) if n else np.zeros(0, np.int64)
 
     def lap(name, t0):
         if timings is not None:
@@ -375,108 +394,86 @@ def measure(slide, features, device=0, block=2048, timings=None, gradient=False,
     with _Ops(device) as ops, torch.cuda.device(ops.device):
         for bx, by, bw, bh, own in blocks:
             t0 = time.perf_counter()
-            if margin:                               # gradient frames start up to `margin` pixels before the block
+            if margin:                               # frames with a margin start up to `margin` pixels before the block
                 bw, bh = bw + bx - max(bx - margin, 0), bh + by - max(by - margin, 0)
                 bx, by = max(bx - margin, 0), max(by - margin, 0)
             host = read_block(slide, bx, by, bw, bh)
             t0 = lap('read', t0)
             dev = torch.from_numpy(host).to(ops.device)
             t0 = lap('upload', t0)
-            for S in SIDES:
-                mine = own[sides[own] == S]
-                for c0 in range(0, len(mine), CHUNK):
-                    idx = mine[c0:c0 + CHUNK]
-                    verts, ring_off = pack_rings([p['rings'][i] for i in idx])
-                    origin = torch.from_numpy(np.ascontiguousarray(rect[idx, :2], np.int32)).to(ops.device)
-                    verts_d, off_d = torch.from_numpy(verts).to(ops.device), torch.from_numpy(ring_off).to(ops.device)
-                    t0 = time.perf_counter()
-                    frames = ops.gather(dev, bx, by, origin, S)
-                    t0 = lap('gather', t0)
-                    masks, status = ops.fill(verts_d, off_d, origin, S)
-                    t0 = lap('fill', t0)
-                    r, h, g = ops.morph_tex(frames, masks)
-                    if shape:
-                        rows[idx] = ops.shape(masks).cpu().numpy()
-                    if fsd:
-                        frows[idx] = ops.fsd(verts_d, off_d).cpu().numpy()
-                    t0 = lap('measure', t0)
-                    st = status.cpu().numpy()
-                    if (st == 1).any():
-                        raise RuntimeError('ring fill: a vertex outside its own frame (the frame is the rectangle of the vertices: this cannot happen)')
-                    ok = st == 0
-                    left['not_traced'] += int((~ok).sum())
-                    raw[idx], hist[idx], glcm[idx], keep[idx] = r.cpu().numpy(), h.cpu().numpy(), g.cpu().numpy(), ok
-            for S in SIDES if gradient else ():
-                mine = own[gsides[own] == S]
-                for c0 in range(0, len(mine), CHUNK):
-                    idx = mine[c0:c0 + CHUNK]
-                    verts, ring_off = pack_rings([p['rings'][i] for i in idx])
-                    origin = torch.from_numpy(np.ascontiguousarray(gorigin[idx], np.int32)).to(ops.device)
-                    verts_d, off_d = torch.from_numpy(verts).to(ops.device), torch.from_numpy(ring_off).to(ops.device)
-                    t0 = time.perf_counter()
-                    frames = ops.gather(dev, bx, by, origin, S)
-                    t0 = lap('gather', t0)
-                    masks, _ = ops.fill(verts_d, off_d, origin, S)          # a ring that is not traced: a zero mask, a zero row, and no row in the result
-                    t0 = lap('fill', t0)
-                    g = ops.gradient(frames, masks, edge_thr)
-                    t0 = lap('measure', t0)
-                    grad[idx] = g.cpu().numpy()
-    sel = np.nonzero(keep)[0]
-    out = dict(raw=raw[sel], hist=hist[sel], glcm=glcm[sel], origin=rect[sel, :2].copy(), rect=rect[sel], score=p['score'][sel], label=p['label'][sel],
-               type=[p['type'][i] for i in sel], nuclei_id=p['nuclei_id'][sel], left_out=left)
-    if gradient:
-        out.update(grad=grad[sel], grad_ok=gsides[sel] > 0, grad_origin=gorigin[sel])
-    if shape:
-        out.update(shape=rows[sel])
-    if fsd:
-        out.update(fsd=frows[sel])
+            for plan, fams, origins, sides in plans:
+                for S in SIDES:
+                    mine = own[sides[own] == S]
+                    for c0 in range(0, len(mine), CHUNK):
+                        idx = mine[c0:c0 + CHUNK]
+                        verts, ring_off = pack_rings([p['rings'][i] for i in idx])
+                        origin = torch.from_numpy(np.ascontiguousarray(origins[idx], np.int32)).to(ops.device)
+                        verts_d, off_d = torch.from_numpy(verts).to(ops.device), torch.from_numpy(ring_off).to(ops.device)
+                        t0 = time.perf_counter()
+                        frames = ops.gather(dev, bx, by, origin, S) if any(f.reads == 'tiles' for f in fams) else None
+                        t0 = lap('gather', t0)
+                        masks, status = ops.fill(verts_d, off_d, origin, S)
+                        t0 = lap('fill', t0)
+                        pairs = ops.pairs(len(idx))
+                        got = [ops.run(f, pairs, frames, masks, verts_d, off_d, [ints[name] for name, *_ in f.ints]) for f in fams]
+                        t0 = lap('measure', t0)
+                        if plan.strict:
+                            st = status.cpu().numpy()
+                            if (st == 1).any():
+                                raise RuntimeError('ring fill: a vertex outside its own frame (the frame is the rectangle of the vertices: this cannot happen)')
+                            keep[idx] = st == 0
+                            left['not_traced'] += int((st != 0).sum())
+                        for f, outs in zip(fams, got):
+                            for (name, _, _), o in zip(f.fields, outs):
+                                res[name][idx] = o.cpu().numpy()
+    rows = np.nonzero(keep)[0]
+    out = {name: a[rows] for name, a in res.items()}
+    out.update(origin=rect[rows, :2].copy(), rect=rect[rows], score=p['score'][rows], label=p['label'][rows], type=[p['type'][i] for i in rows],
+               nuclei_id=p['nuclei_id'][rows], left_out=left)
+    for plan, fams, origins, sides in plans:
+        for f in fams:
+            if f.lacking:
+                out.update({_ok(f): sides[rows] > 0, f.fields[0][0] + '_origin': origins[rows]})
     return out
 
 
-def table_columns(gradient=False, shape=False, fsd=False):
-    """The names of table()'s columns: the 29 nucmorph.COLUMNS, the 26 nuctex.COLUMNS and, with the selections, the 8 nucgrad.COLUMNS, then
-    the 8 nucshape.COLUMNS and then the 6 nucfsd.COLUMNS."""
-    return nucmorph.COLUMNS + nuctex.COLUMNS + (nucgrad.COLUMNS if gradient else ()) + (nucshape.COLUMNS if shape else ()) + (nucfsd.COLUMNS if fsd else ())
+def table_columns(**keywords):
+    """The names of table()'s columns: the COLUMNS of the selected families in the order of FAMILIES -- the 29 of nucmorph, the 26 of
+    nuctex and, with the selections, the 8 of nucgrad, then the 8 of nucshape and then the 6 of nucfsd."""
+    return sum((f.columns for f in select(**keywords)), ())
 
 
-def table(m, gradient=False, shape=False, fsd=False):
+def table(m, **keywords):
     """measure()'s result -> (columns, float64 (n, 55)): nucmorph.derive(raw, hist, origin) beside nuctex.derive(glcm).  gradient=True (of
     a measure(gradient=True)): (n, 63), nucgrad.derive(grad) behind them, NaN in the eight columns of a nucleus without a gradient frame.
     shape=True (of a measure(shape=True)): eight more columns, nucshape.derive(shape), last -- behind the gradient's when both are
     selected (n, 71), behind the texture's otherwise (n, 63); they are never NaN.  fsd=True (of a measure(fsd=True)): six more columns,
     nucfsd.derive(fsd), behind all of these; they are never NaN."""
-    c1, v1 = nucmorph.derive(m['raw'], m['hist'], m['origin'])
-    c2, v2 = nuctex.derive(m['glcm'])
-    cols, vals = tuple(c1) + tuple(c2), [v1, v2]
-    if gradient:
-        c3, v3 = nucgrad.derive(m['grad'])
-        cols, vals = cols + tuple(c3), vals + [np.where(np.asarray(m['grad_ok'], bool)[:, None], v3, np.nan)]
-    if shape:
-        c4, v4 = nucshape.derive(m['shape'])
-        cols, vals = cols + tuple(c4), vals + [v4]
-    if fsd:
-        c5, v5 = nucfsd.derive(m['fsd'])
-        cols, vals = cols + tuple(c5), vals + [v5]
+    cols, vals = (), []
+    for f in select(**keywords):
+        c, v = f.derive([m[name] for name, _, _ in f.fields], m['origin'])
+        cols, vals = cols + tuple(c), vals + [np.where(np.asarray(m[_ok(f)], bool)[:, None], v, np.nan) if f.lacking else v]
     return cols, np.concatenate(vals, 1)
 
 
-def db_columns(gradient=False, shape=False, fsd=False):
+def db_columns(**keywords):
     """[(name, SQLite type)] of the table `nuclei_features`, in order: Label (always 1, as histomicstk labels a one-nucleus crop), the 29
     nucmorph.COLUMNS and the 26 nuctex.COLUMNS (REAL; every '.' of a name replaced by '_', as the reference does before to_sql), with
     the selections the 8 nucgrad.COLUMNS, then the 8 nucshape.COLUMNS and then the 6 nucfsd.COLUMNS in the same form, score, type, class_id,
     nuclei_id, and the vertex extremes x_min, y_min, x_max, y_max."""
-    cols = [('Label', 'INTEGER')] + [(c.replace('.', '_'), 'REAL') for c in table_columns(gradient, shape, fsd)]
+    cols = [('Label', 'INTEGER')] + [(c.replace('.', '_'), 'REAL') for c in table_columns(**keywords)]
     return cols + [('score', 'REAL'), ('type', 'TEXT'), ('class_id', 'INTEGER'), ('nuclei_id', 'INTEGER'),
                    ('x_min', 'INTEGER'), ('y_min', 'INTEGER'), ('x_max', 'INTEGER'), ('y_max', 'INTEGER')]
 
 
-def column_mismatch(path, gradient=False, shape=False, fsd=False):
-    """None when `path` holds no table nuclei_features or one with exactly the columns of db_columns(gradient, shape, fsd); otherwise what
+def column_mismatch(path, **keywords):
+    """None when `path` holds no table nuclei_features or one with exactly the columns of db_columns(**keywords); otherwise what
     differs, in words: such a table is neither appended to nor altered."""
+    want = [c for c, _ in db_columns(**keywords)]
     got = read_db(path)
     if got is None:
         return None
-    have, want = [c for c, _ in got['columns']], [c for c, _ in db_columns(gradient, shape, fsd)]
+    have = [c for c, _ in got['columns']]
     if have == want:
         return None
     extra, lack = [c for c in have if c not in want], [c for c in want if c not in have]
@@ -484,27 +481,32 @@ def column_mismatch(path, gradient=False, shape=False, fsd=False):
            ('it lacks the requested columns: ' + ', '.join(lack) if lack else '') or 'its columns are in another order'
 
 
-def write_db(path, values, score, kind, class_id, nuclei_id, rect, gradient=False, shape=False, fsd=False):
-    """Appends one row per nucleus to the table nuclei_features of the SQLite file `path` (created with db_columns(gradient, shape, fsd) when
-    missing): values float (n, 55) = table()[1], or (n, 63) = table(gradient=True)[1], whose NaN are written as NULL; with shape=True
-    eight columns more, with fsd=True six more, table(gradient, shape, fsd)[1].  A file of any size
-    is kept -- the reference deletes a database under 1 MB as broken; a complete small table is complete.  ValueError, with the file
-    untouched, when it holds a table with another column set (column_mismatch).  -> the number of rows written."""
-    values = np.asarray(values, np.float64).reshape(-1, len(table_columns(gradient, shape, fsd)))
+def write_db(path, values, score, kind, class_id, nuclei_id, rect, **keywords):
+    """Appends one row per nucleus to the table nuclei_features of the SQLite file `path` (created with db_columns(**keywords) when
+    missing): values float (n, 55) = table()[1], or with gradient=True (n, 63), with shape=True eight columns more, with fsd=True six
+    more, table(m, **keywords)[1].  A NaN in a column of a family that a nucleus can lack (table()) is written as NULL; a NaN anywhere
+    else is a ValueError.  A file of any size is kept -- the reference deletes a database under 1 MB as broken; a complete small table is
+    complete.  ValueError, with the file untouched, when it holds a table with another column set (column_mismatch).  -> the number of
+    rows written."""
+    sel = select(**keywords)
+    values = np.asarray(values, np.float64).reshape(-1, sum(len(f.columns) for f in sel))
     rect = np.asarray(rect, np.int64).reshape(-1, 4)
     n = len(values)
     if not (len(score) == len(kind) == len(class_id) == len(nuclei_id) == len(rect) == n):
         raise ValueError('write_db: one row per nucleus in every field')
-    cols = db_columns(gradient, shape, fsd)
-    why = column_mismatch(path, gradient, shape, fsd)
+    if np.isnan(values[:, [not f.lacking for f in sel for _ in f.columns]]).any():
+        raise ValueError('write_db: a NaN in a column that every nucleus has')
+    cols = db_columns(**keywords)
+    why = column_mismatch(path, **keywords)
     if why:
         raise ValueError(f'write_db: {path} holds another column set ({why})')
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     conn = sqlite3.connect(path)
     try:
         conn.execute(f'CREATE TABLE IF NOT EXISTS {TABLE} ({", ".join(f"{c} {t}" for c, t in cols)})')
-        real = (lambda v: None if v != v else float(v)) if gradient else float
-        rows = [(1, *map(real, values[i]), float(score[i]), str(kind[i]), int(class_id[i]), int(nuclei_id[i]), *map(int, rect[i])) for i in range(n)]
+        real = values.astype(object)                 # Python floats, and None where a nucleus lacks a family
+        real[np.isnan(values)] = None
+        rows = [(1, *real[i], float(score[i]), str(kind[i]), int(class_id[i]), int(nuclei_id[i]), *map(int, rect[i])) for i in range(n)]
         conn.executemany(f'INSERT INTO {TABLE} ({", ".join(c for c, _ in cols)}) VALUES ({", ".join("?" * len(cols))})', rows)
         conn.commit()
     finally:

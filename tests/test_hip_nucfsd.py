@@ -178,7 +178,7 @@ def test_measure_with_fsd_equals_the_restatement(hip_device):
     assert np.array_equal(val[:, :55], ringfeat.table(plain)[1]) and np.array_equal(val[:, 55:], nf.derive(want)[1])
     every = ringfeat.measure(slide, feats, device=0, block=128, gradient=True, shape=True, fsd=True)
     cols, val2 = ringfeat.table(every, gradient=True, shape=True, fsd=True)
-    assert cols == ringfeat.table_columns(True, True, True) and val2.shape == (n, 77) and every['fsd'].tobytes() == m['fsd'].tobytes()
+    assert cols == ringfeat.table_columns(gradient=True, shape=True, fsd=True) and val2.shape == (n, 77) and every['fsd'].tobytes() == m['fsd'].tobytes()
     assert np.array_equal(val2[:, 71:], val[:, 55:]) and np.array_equal(val2[:, :55], val[:, :55])
     assert cols[63:71] == ns.COLUMNS and cols[71:] == nf.COLUMNS
 
@@ -223,7 +223,7 @@ def test_tool_with_and_without_fsd(hip_device, tmp_path):
     assert f's1: {len(feats) - 5} rows written' in err and f'skipped 5/{len(feats)} nuclei' in out
     assert ringfeat.missing_ids(db('fsd'), range(len(feats))) == []
     a, b, c = (ringfeat.read_db(db(d)) for d in ('plain', 'fsd', 'every'))
-    assert a['columns'] == ringfeat.db_columns() and b['columns'] == ringfeat.db_columns(fsd=True) and c['columns'] == ringfeat.db_columns(True, True, True)
+    assert a['columns'] == ringfeat.db_columns() and b['columns'] == ringfeat.db_columns(fsd=True) and c['columns'] == ringfeat.db_columns(gradient=True, shape=True, fsd=True)
     under = lambda cols: [x.replace('.', '_') for x in cols]
     assert [x for x, _ in b['columns'][56:62]] == under(nf.COLUMNS) == [x for x, _ in c['columns'][72:78]]
     assert [x for x, _ in c['columns'][56:64]] == under(ng.COLUMNS) and [x for x, _ in c['columns'][64:72]] == under(ns.COLUMNS)
@@ -238,5 +238,5 @@ def test_tool_with_and_without_fsd(hip_device, tmp_path):
     out, err = _run_tool(base('plain') + ['--fsd'])
     assert 'skipped:s1' in out and db('plain') in out and 'Shape_FSD1' in out and db('plain') in err
     assert 'Shape_HuMoments1' in ringfeat.column_mismatch(db('fsd'), shape=True, fsd=True) and 'Shape_FSD1' in ringfeat.column_mismatch(db('fsd'))
-    assert 'Shape_FSD1' in ringfeat.column_mismatch(db('every'), True, True) and ringfeat.column_mismatch(db('every'), True, True, True) is None
+    assert 'Shape_FSD1' in ringfeat.column_mismatch(db('every'), gradient=True, shape=True) and ringfeat.column_mismatch(db('every'), gradient=True, shape=True, fsd=True) is None
     assert {d: open(db(d), 'rb').read() for d in segs} == before

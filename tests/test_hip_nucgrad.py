@@ -264,7 +264,7 @@ def test_measure_with_gradient_equals_the_restatement(hip_device):
     one = ringfeat.measure(slide, feats, device=0, block=2048, gradient=True, edge_thr=T)       # the block size changes nothing
     assert one['grad'].tobytes() == m['grad'].tobytes() and one['grad_ok'].tobytes() == m['grad_ok'].tobytes()
     cols, val = ringfeat.table(m, gradient=True)
-    assert cols == ringfeat.table_columns(True) and val.shape == (n, 63)
+    assert cols == ringfeat.table_columns(gradient=True) and val.shape == (n, 63)
     bad = [i for i in range(n) if not m['grad_ok'][i]]
     assert len(bad) == 1 and np.isnan(val[bad[0], 55:]).all() and np.isfinite(np.delete(val, bad[0], 0)).all() and np.isfinite(val[:, :55]).all()
     assert np.array_equal(val[:, :55], ringfeat.table(plain)[1])

@@ -223,7 +223,7 @@ def test_measure_with_shape_equals_the_restatement(hip_device):
     assert np.array_equal(val[:, :55], ringfeat.table(plain)[1]) and np.array_equal(val[:, 55:], ns.derive(want)[1])
     both = ringfeat.measure(slide, feats, device=0, block=128, gradient=True, shape=True)
     cols, val2 = ringfeat.table(both, gradient=True, shape=True)
-    assert cols == ringfeat.table_columns(True, True) and val2.shape == (n, 71) and both['shape'].tobytes() == m['shape'].tobytes()
+    assert cols == ringfeat.table_columns(gradient=True, shape=True) and val2.shape == (n, 71) and both['shape'].tobytes() == m['shape'].tobytes()
     assert np.array_equal(val2[:, 63:], val[:, 55:]) and np.array_equal(val2[:, :55], val[:, :55])
 
 
@@ -262,7 +262,7 @@ def test_tool_with_and_without_shape(hip_device, tmp_path):
         _, err = _run_tool(base(d) + flags[d])
         assert f's1: {len(feats)} rows written, left out none' in err
     a, b, c = (ringfeat.read_db(db(d)) for d in ('plain', 'shape', 'both'))
-    assert a['columns'] == ringfeat.db_columns() and b['columns'] == ringfeat.db_columns(shape=True) and c['columns'] == ringfeat.db_columns(True, True)
+    assert a['columns'] == ringfeat.db_columns() and b['columns'] == ringfeat.db_columns(shape=True) and c['columns'] == ringfeat.db_columns(gradient=True, shape=True)
     assert [x for x, _ in b['columns'][56:64]] == [x.replace('.', '_') for x in ns.COLUMNS] == [x for x, _ in c['columns'][64:72]]
     assert [x for x, _ in c['columns'][56:64]] == [x.replace('.', '_') for x in ng.COLUMNS]
     m = ringfeat.measure(slide, feats, device=0)
@@ -275,5 +275,5 @@ def test_tool_with_and_without_shape(hip_device, tmp_path):
     before = {d: open(db(d), 'rb').read() for d in segs}
     out, err = _run_tool(base('plain') + ['--shape'])
     assert 'skipped:s1' in out and db('plain') in out and 'Shape_HuMoments1' in out and db('plain') in err
-    assert 'Shape_HuMoments1' in ringfeat.column_mismatch(db('both'), gradient=True) and ringfeat.column_mismatch(db('both'), True, True) is None
+    assert 'Shape_HuMoments1' in ringfeat.column_mismatch(db('both'), gradient=True) and ringfeat.column_mismatch(db('both'), gradient=True, shape=True) is None
     assert {d: open(db(d), 'rb').read() for d in segs} == before

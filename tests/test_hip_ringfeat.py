@@ -237,6 +237,7 @@ def _placed_masks():
     out = [(n, c[n], (x, y)) for n, x, y in at]
     out.append(('side 70', big70, (10, 180)))
     out.append(('side 130', big130, (128, 140)))
+    out.append(('254 px', np.ones((6, 254), bool), (3, 290)))                                  # its rectangle plus a margin of 2 exceeds 256
     for n, m, (x, y) in out:
         assert x + m.shape[1] <= SLIDE_W and y + m.shape[0] <= SLIDE_H, n
     return out
@@ -313,6 +314,28 @@ def test_measure_equals_the_restatement(scene):
     assert one['left_out'] == m['left_out'] and one['type'] == m['type']
 
 
+def test_all_families_at_once_equal_each_alone_and_the_plain_call(scene):
+    """One walk with every family selected against the walks with one or none: every field byte for byte, at both block sizes -- the
+    frame plans share the block, the rings and the chunking, and must not reach into each other."""
+    slide, feats, n_kept, placed, _ = scene
+    every = ringfeat.measure(slide, feats, device=0, block=128, gradient=True, shape=True, fsd=True)
+    parts = [ringfeat.measure(slide, feats, device=0, block=128, **kw) for kw in ({}, dict(gradient=True), dict(shape=True), dict(fsd=True))]
+    parts.append(ringfeat.measure(slide, feats, device=0, block=2048, gradient=True, shape=True, fsd=True))
+    assert set(every) == set(parts[0]) | {'grad', 'grad_ok', 'grad_origin', 'shape', 'fsd'} == set(parts[4])
+    assert [sorted(set(m) - set(parts[0])) for m in parts[:4]] == [[], ['grad', 'grad_ok', 'grad_origin'], ['shape'], ['fsd']]
+    for m in parts:
+        for k, v in m.items():
+            if isinstance(v, np.ndarray):
+                assert every[k].dtype == v.dtype and every[k].shape == v.shape and every[k].tobytes() == v.tobytes(), k
+            else:
+                assert every[k] == v, k
+    assert len(every['raw']) == n_kept and every['shape'].any() and every['fsd'].any()
+    lack = [n for (n, _, _), ok in zip(placed, every['grad_ok']) if not ok]
+    assert lack == ['254 px'] and not every['grad'][~every['grad_ok']].any() and every['grad'][every['grad_ok']].any(1).all()
+    cols, val = ringfeat.table(every, gradient=True, shape=True, fsd=True)
+    assert val.shape == (n_kept, 77) and np.array_equal(np.isnan(val), ~every['grad_ok'][:, None] & (np.arange(77) >= 55)[None] & (np.arange(77) < 63)[None])
+
+
 def _run_tool(cmd, limit=120):
     p = subprocess.run(['timeout', '-k', '10', str(limit), sys.executable, TOOL] + cmd, cwd=ROOT, capture_output=True, text=True)
     print(p.stdout[-2000:], p.stderr[-2000:])
@@ -344,7 +367,7 @@ def test_tool_writes_resumes_and_reads_plain_files(scene, tmp_path):
         assert r[56] == feats[i]['properties']['score'] and r[57] == CLASSES[i % 5] and r[58] == i % 5 and r[59] == ids[i]
         ring = np.asarray(feats[i]['geometry']['coordinates'][0])
         assert list(r[60:]) == [ring[:, 0].min(), ring[:, 1].min(), ring[:, 0].max(), ring[:, 1].max()]
-    # a second run: the slide is skipped and the file stays as it is (a table of 23 rows is far below 1 MB)
+    # a second run: the slide is skipped and the file stays as it is (a table of 24 rows is far below 1 MB)
     before = open(db, 'rb').read()
     assert len(before) < 1 << 20
     out, _ = _run_tool(base)

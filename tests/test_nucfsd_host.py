@@ -243,9 +243,9 @@ def test_db_columns_order_for_every_selection(tmp_path):
         got = ringfeat.db_columns(gradient=g, shape=s, fsd=f)
         assert [c for c, _ in got] == want, (g, s, f)
         assert all(t == 'REAL' for c, t in got if c.startswith('Shape_FSD'))
-        assert list(ringfeat.table_columns(g, s, f)) == [c for c in nucmorph.COLUMNS + nuctex.COLUMNS] + (list(nucgrad.COLUMNS) if g else []) + \
+        assert list(ringfeat.table_columns(gradient=g, shape=s, fsd=f)) == [c for c in nucmorph.COLUMNS + nuctex.COLUMNS] + (list(nucgrad.COLUMNS) if g else []) + \
                (list(nucshape.COLUMNS) if s else []) + (list(nf.COLUMNS) if f else [])
-    assert ringfeat.db_columns() == ringfeat.db_columns(fsd=False) and ringfeat.table_columns(False, True) == ringfeat.table_columns(False, True, False)
+    assert ringfeat.db_columns() == ringfeat.db_columns(fsd=False) and ringfeat.table_columns(gradient=False, shape=True) == ringfeat.table_columns(gradient=False, shape=True, fsd=False)
     # a table written with one selection is refused by every other, in both directions, and left alone
     n = 2
     rect = np.array([[0, 0, 3, 3], [4, 4, 9, 9]])

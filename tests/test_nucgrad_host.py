@@ -188,9 +188,9 @@ def test_db_with_gradient_columns_and_resume_rule(tmp_path):
     for ra, rb, k in zip(a['rows'], b['rows'], range(n)):
         assert rb[:56] == ra[:56] and rb[64:] == ra[56:]
         assert list(rb[56:64]) == (grad[k].tolist() if ok[k] else [None] * 8)                    # no gradient frame: NULL
-    assert rf.column_mismatch(plain, False) is None and rf.column_mismatch(with_g, True) is None
-    assert rf.column_mismatch(str(tmp_path / 'none.db'), True) is None
-    assert 'Nucleus_Gradient_Mag_Mean' in rf.column_mismatch(plain, True) and 'Nucleus_Gradient_Mag_Mean' in rf.column_mismatch(with_g, False)
+    assert rf.column_mismatch(plain, gradient=False) is None and rf.column_mismatch(with_g, gradient=True) is None
+    assert rf.column_mismatch(str(tmp_path / 'none.db'), gradient=True) is None
+    assert 'Nucleus_Gradient_Mag_Mean' in rf.column_mismatch(plain, gradient=True) and 'Nucleus_Gradient_Mag_Mean' in rf.column_mismatch(with_g, gradient=False)
     with pytest.raises(ValueError):
         rf.write_db(plain, wide, *args, gradient=True)                                           # never appended to under another column set
     with pytest.raises(ValueError):

@@ -164,21 +164,21 @@ def test_table_and_db_columns_of_the_four_sets(tmp_path):
         at = 56 + 8 * g
         assert len(with_s) == len(without) + 8 and with_s[:at] == without[:at] and with_s[at + 8:] == without[at:] and without[at][0] == 'score'
         assert with_s[at] == ('Shape_HuMoments1', 'REAL') and with_s[at + 7] == ('Shape_FractalDimension', 'REAL')
-    assert rf.db_columns(False, False) == plain
+    assert rf.db_columns(gradient=False, shape=False) == plain
     n = 3
     args = (np.linspace(0.5, 0.9, n), ['a', 'b', 'c'], [1, 2, 3], [7, 8, 9], np.arange(n * 4).reshape(n, 4))
     sets = [(False, False), (True, False), (False, True), (True, True)]
-    values = {s: np.arange(n * len(rf.table_columns(*s)), dtype=np.float64).reshape(n, -1) + 0.25 for s in sets}
+    values = {s: np.arange(n * len(rf.table_columns(gradient=s[0], shape=s[1])), dtype=np.float64).reshape(n, -1) + 0.25 for s in sets}
     path = {s: str(tmp_path / f'g{int(s[0])}s{int(s[1])}.db') for s in sets}
     for s in sets:
         assert rf.write_db(path[s], values[s], *args, gradient=s[0], shape=s[1]) == n
         got = rf.read_db(path[s])
-        assert got['columns'] == rf.db_columns(*s)
+        assert got['columns'] == rf.db_columns(gradient=s[0], shape=s[1])
         assert [list(r[1:1 + values[s].shape[1]]) for r in got['rows']] == values[s].tolist()
     for s in sets:                                                                              # the four sets are told apart, each from each
         before = open(path[s], 'rb').read()
         for t in sets:
-            why = rf.column_mismatch(path[s], *t)
+            why = rf.column_mismatch(path[s], gradient=t[0], shape=t[1])
             assert (why is None) == (s == t), (s, t, why)
             if s[1] != t[1]:
                 assert 'Shape_HuMoments1' in why

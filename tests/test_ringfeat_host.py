@@ -1,6 +1,8 @@
 """Host side of the per-nucleus table from a written GeoJSON (nuhtc_amd/ringfeat.py, tools/wsi_feat_extract.py): parsing, frame sides,
 the block walk, the SQLite file with its resume rule, and the tool's command line.  No GPU."""
 import ast
+import itertools
+import json
 import os
 import sqlite3
 
@@ -138,11 +140,16 @@ def test_tool_flags_and_defaults():
     assert ast.get_docstring(tree) and '1 MB' in ast.get_docstring(tree) and 'traced rings' in ast.get_docstring(tree).lower()
 
 
-def test_tool_slide_ids_follow_the_reference_slices(tmp_path):
+def _tool():
     import importlib.util
     spec = importlib.util.spec_from_file_location('tool_wsi_feat_extract', TOOL)
     tool = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(tool)
+    return tool
+
+
+def test_tool_slide_ids_follow_the_reference_slices(tmp_path):
+    tool = _tool()
     for name in ('b.npy', 'a.svs', 'c.tif', 'd.npy'):
         (tmp_path / name).write_bytes(b'')
     d = str(tmp_path)
@@ -152,3 +159,62 @@ def test_tool_slide_ids_follow_the_reference_slices(tmp_path):
     a = tool.parse_args(['data', '--segdir', 'seg'])
     assert (a.datadir, a.segdir, a.start, a.end, a.mag, a.reverse, a.bs_size, a.num_workers, a.slide_ext, a.geojson, a.device) \
         == ('data', 'seg', 0, None, 40, False, 1024, 8, '.svs', 'merged', 0)
+
+
+def test_select_keeps_the_order_of_the_table_and_refuses_other_keywords(tmp_path):
+    F = ringfeat.FAMILIES
+    assert [f.keyword for f in F] == [None, None, 'gradient', 'shape', 'fsd'] and [f.columns for f in F[:2]] == [nucmorph.COLUMNS, nuctex.COLUMNS]
+    assert ringfeat.select() == ringfeat.select(gradient=False, shape=False, fsd=False) == F[:2]
+    assert ringfeat.select(fsd=True, shape=True, gradient=True) == ringfeat.select(gradient=True, shape=True, fsd=True) == F
+    assert ringfeat.select(fsd=True, gradient=True) == ringfeat.select(gradient=True, shape=False, fsd=True) == F[:3] + F[4:]
+    assert ringfeat.select(shape=True) == F[:2] + F[3:4]
+    for call in (ringfeat.select, ringfeat.table_columns, ringfeat.db_columns, lambda **k: ringfeat.column_mismatch(str(tmp_path / 'no.db'), **k),
+                 lambda **k: ringfeat.table({}, **k), lambda **k: ringfeat.write_db(str(tmp_path / 'no.db'), *_rows(2), **k),
+                 lambda **k: ringfeat.measure(None, [], **k)):
+        with pytest.raises(TypeError):
+            call(cytoplasm=True)
+        with pytest.raises(TypeError):
+            call(gradient=True, Shape=True)
+    assert not os.path.exists(str(tmp_path / 'no.db'))
+
+
+def test_columns_and_help_of_every_selection_equal_the_recorded_ones(monkeypatch):
+    """tests/golden/ringfeat_columns.json: table_columns, db_columns and the tool's --help as they were before the families became a table."""
+    with open(os.path.join(ROOT, 'tests', 'golden', 'ringfeat_columns.json')) as f:
+        gold = json.load(f)
+    assert sorted(gold['table']) == sorted(gold['db']) == sorted(''.join(b) for b in itertools.product('01', repeat=3))
+    for g, s, f in itertools.product((False, True), repeat=3):
+        key = ''.join('01'[v] for v in (g, s, f))
+        assert list(ringfeat.table_columns(gradient=g, shape=s, fsd=f)) == gold['table'][key], key
+        assert [list(c) for c in ringfeat.db_columns(gradient=g, shape=s, fsd=f)] == gold['db'][key], key
+    monkeypatch.setenv('COLUMNS', str(gold['help_columns']))
+    parser = _tool().build_parser()
+    parser.prog = 'wsi_feat_extract.py'
+    assert parser.format_help() == gold['help']
+
+
+def test_nan_is_null_in_a_family_a_nucleus_can_lack_and_refused_elsewhere(tmp_path):
+    assert [bool(f.lacking) for f in ringfeat.FAMILIES] == [False, False, True, False, False]
+    n, every = 3, dict(gradient=True, shape=True, fsd=True)
+    args = (np.linspace(0.5, 0.9, n), ['a', 'b', 'c'], [1, 2, 3], [7, 8, 9], np.arange(n * 4).reshape(n, 4))
+    vals = np.arange(n * 77, dtype=np.float64).reshape(n, 77) + 0.5
+    vals[1, 55:63] = np.nan                                                     # the eight gradient columns of one nucleus
+    path = str(tmp_path / 'every.db')
+    assert ringfeat.write_db(path, vals, *args, **every) == n
+    rows = ringfeat.read_db(path)['rows']
+    assert list(rows[1][56:64]) == [None] * 8 and list(rows[1][1:56]) == vals[1, :55].tolist() and list(rows[1][64:78]) == vals[1, 63:].tolist()
+    assert [list(r[1:78]) for r in (rows[0], rows[2])] == vals[[0, 2]].tolist()
+    before = open(path, 'rb').read()
+    for col in (0, 28, 29, 54, 63, 70, 71, 76):                                 # first and last column of each of the other four families
+        bad = vals.copy()
+        bad[2, col] = np.nan
+        with pytest.raises(ValueError):
+            ringfeat.write_db(path, bad, *args, **every)
+    with pytest.raises(ValueError):                                             # without the family that can be lacking: no NaN at all
+        ringfeat.write_db(str(tmp_path / 'plain.db'), np.where(np.arange(55) == 7, np.nan, vals[:, :55]), *args)
+    assert not os.path.exists(str(tmp_path / 'plain.db'))
+    with pytest.raises(ValueError):                                             # a foreign column set
+        ringfeat.write_db(path, vals[:, :55], *args)
+    with pytest.raises(ValueError):
+        ringfeat.write_db(path, vals[:, :63], *args, gradient=True)
+    assert open(path, 'rb').read() == before

@@ -94,8 +94,12 @@ def main(argv=None):
         block, origin, verts_d, off_d = dev(canvas), dev(parsed['rect'][idx, :2].astype(np.int32)), dev(verts), dev(off)
         frames = ops.gather(block, 0, 0, origin, S)
         masks, status = ops.fill(verts_d, off_d, origin, S)
-        calls = {'gather': lambda: ops.gather(block, 0, 0, origin, S), 'fill': lambda: ops.fill(verts_d, off_d, origin, S),
-                 'measure': lambda: ops.morph_tex(frames, masks)}
+        fams = ringfeat.select()        # the families that are always selected
+
+        def measure():                  # as one chunk of ringfeat.measure(): the pairs, then every family of the selection
+            pairs = ops.pairs(len(idx))
+            return [ops.run(fam, pairs, frames, masks) for fam in fams]
+        calls = {'gather': lambda: ops.gather(block, 0, 0, origin, S), 'fill': lambda: ops.fill(verts_d, off_d, origin, S), 'measure': measure}
         for name, call in calls.items():
             ms = []
             for i in range(12):

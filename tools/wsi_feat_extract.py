@@ -64,9 +64,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def build_parser():
-    """tools/wsi_feat_extract.py:239-250 of the reference, then four flags of our own, the two of the gradient selection (--gradient,
-    --edge-thr: nuhtc_amd.ringfeat.add_gradient_flags, beside what they select), the one of the shape selection (--shape:
-    add_shape_flags) and the one of the Fourier-descriptor selection (--fsd: add_fsd_flags)."""
+    """tools/wsi_feat_extract.py:239-250 of the reference, then flags of our own: three here, and those of every family of measurements
+    that has any (nuhtc_amd.ringfeat.FAMILIES: --gradient and --edge-thr, --shape, --fsd, each defined beside what it selects)."""
     p = ArgumentParser(allow_abbrev=False)
     p.add_argument('datadir', help='path to folder containing raw wsi image files')
     p.add_argument('--segdir', help='path to folder containing segmentation files')
@@ -81,9 +80,9 @@ def build_parser():
     p.add_argument('--geojson', choices=('merged', 'plain'), default='merged', help='<id>_merged.geojson or <id>.geojson')
     p.add_argument('--device', type=int, default=0, help='GPU of the measurement')
     from nuhtc_amd import ringfeat
-    ringfeat.add_gradient_flags(p)
-    ringfeat.add_shape_flags(p)
-    ringfeat.add_fsd_flags(p)
+    for fam in ringfeat.FAMILIES:
+        if fam.flags:
+            fam.flags(p)
     return p
 
 
@@ -99,13 +98,13 @@ def slide_ids(datadir, start=0, end=None, reverse=False):
     return ids[start:end] if end is not None else ids[start:]
 
 
-def extract_slide(slide_path, geojson_path, db_path, device=0, log=print, gradient=False, edge_thr=1, shape=False, fsd=False):
-    """One slide -> (rows written, {reason: left out}), or None when the table already holds every nucleus of the file.  gradient=True:
-    with the gradient columns (edge_thr in quarter grey levels), -> (rows written, {reason: left out}, rows without a gradient frame).
-    shape=True, fsd=True: with the shape columns, with the Fourier descriptors; the return value keeps its form.  An existing table with another column set: a string that says
+def extract_slide(slide_path, geojson_path, db_path, device=0, log=print, edge_thr=1, **keywords):
+    """One slide -> (rows written, {reason: left out}, {keyword: nuclei without that family's columns}), or None when the table already
+    holds every nucleus of the file.  keywords: gradient=, shape=, fsd= of nuhtc_amd.ringfeat (edge_thr in quarter grey levels); the
+    third part has an entry per selected family that a nucleus can lack.  An existing table with another column set: a string that says
     what differs, and the file is not touched."""
     from nuhtc_amd import ringfeat, slides
-    why = ringfeat.column_mismatch(db_path, gradient, shape, fsd)
+    why = ringfeat.column_mismatch(db_path, **keywords)
     if why:
         return why
     with open(geojson_path) as f:
@@ -120,15 +119,10 @@ def extract_slide(slide_path, geojson_path, db_path, device=0, log=print, gradie
     # only the missing nuclei are measured, each under the id it has in the whole file (a nucleus left out before is tried, and left
     # out, again)
     features = [dict(f, properties=dict(f.get('properties') or {}, nuclei_id=i)) for f, i in zip(features, every) if i in todo]
-    if not gradient:
-        m = ringfeat.measure(slides.open_array_slide(slide_path), features, device=device, shape=shape, fsd=fsd)
-        _, values = ringfeat.table(m, shape=shape, fsd=fsd)
-        n = ringfeat.write_db(db_path, values, m['score'], m['type'], m['label'], m['nuclei_id'], m['rect'], shape=shape, fsd=fsd)
-        return n, m['left_out']
-    m = ringfeat.measure(slides.open_array_slide(slide_path), features, device=device, gradient=True, edge_thr=edge_thr, shape=shape, fsd=fsd)
-    _, values = ringfeat.table(m, gradient=True, shape=shape, fsd=fsd)
-    n = ringfeat.write_db(db_path, values, m['score'], m['type'], m['label'], m['nuclei_id'], m['rect'], gradient=True, shape=shape, fsd=fsd)
-    return n, m['left_out'], int((~m['grad_ok']).sum())
+    m = ringfeat.measure(slides.open_array_slide(slide_path), features, device=device, edge_thr=edge_thr, **keywords)
+    _, values = ringfeat.table(m, **keywords)
+    n = ringfeat.write_db(db_path, values, m['score'], m['type'], m['label'], m['nuclei_id'], m['rect'], **keywords)
+    return n, m['left_out'], ringfeat.lacking(m, **keywords)
 
 
 def main(argv=None):
@@ -146,6 +140,9 @@ def main(argv=None):
     if args.mag != 40:
         print(f'--mag {args.mag}: rings are level-0 coordinates and are measured in level-0 pixels; the reference would upsample every crop by '
               f'{40 / args.mag:g} first, this tool does not', file=sys.stderr)
+    from nuhtc_amd import ringfeat
+    keywords = {f.keyword: getattr(args, f.keyword) for f in ringfeat.FAMILIES if f.keyword}
+    said = {f.keyword: f.lacking for f in ringfeat.FAMILIES}
     ids = slide_ids(args.datadir, args.start, args.end, args.reverse)
     suffix = '_merged.geojson' if args.geojson == 'merged' else '.geojson'
     report = []
@@ -160,7 +157,7 @@ def main(argv=None):
             print(f'no slide {spath}, skipped\n')
             continue
         db = os.path.join(args.segdir, sid, 'nuclei_feat.db')
-        got = extract_slide(spath, gj, db, device=args.device, gradient=args.gradient, edge_thr=edge_thr, shape=args.shape, fsd=args.fsd)
+        got = extract_slide(spath, gj, db, device=args.device, edge_thr=edge_thr, **keywords)
         if got is None:
             print(f'skipped:{sid}\n')
             continue
@@ -168,10 +165,10 @@ def main(argv=None):
             print(f'skipped:{sid}: {db} was written with other columns and is left as it is ({got})\n')
             report.append(f'{sid}: skipped, {db} holds other columns ({got})')
             continue
-        n, left = got[:2]
+        n, left, lack = got
         print(f'{sid}: {n} rows')
         report.append(f'{sid}: {n} rows written, left out ' + (', '.join(f'{v} {r}' for r, v in left.items() if v) or 'none') +
-                      (f', {got[2]} without gradient columns (rectangle plus margin over 256 px)' if args.gradient and got[2] else ''))
+                      ''.join(f', {v} without {said[k]}' for k, v in lack.items() if v))
     print('; '.join(report) if report else 'no slide measured', file=sys.stderr)
 
 
