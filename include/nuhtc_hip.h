@@ -933,6 +933,28 @@ int nuhtc_op_ring_fsd(int device, const int32_t* verts, int64_t nv, const int64_
 int nuhtc_cell_graph(int device, const int32_t* points, const int32_t* labels, int64_t n, int num_classes, int r, int k, int x_min, int y_min,
                      int x_max, int y_max, int32_t* neighbors, int32_t* d2, int32_t* class_count, void* stream);
 
+/* Spatial statistics of a slide (csrc/cellspatial.hip; nuhtc_amd/spatial.py has the definition and its brute-force int64 restatement
+ * `spatial_reference`): pair-distance histograms by class pair and the nearest nucleus of every class for every nucleus.  Not in the
+ * reference.  Engine-free like nuhtc_cell_graph: points, labels and the three outputs are device memory of `device`, the call allocates and
+ * frees its own scratch, runs on `stream` and synchronises it before returning.  nuhtc_config is unchanged (no ABI bump).
+ *   points [n][2] int32: node positions in HALF pixels (as for nuhtc_cell_graph), |p| < 2^27.  labels [n] int32.  0 <= n <= 2^28.
+ *   num_classes C: 1 .. 14.  edges [num_bins] int32 in HOST memory: the bin edges e_1 < .. < e_B in half pixels, strictly increasing,
+ *     1 <= B <= 32, e_1 >= 1, e_B <= 16384.
+ *   x_min, y_min, x_max, y_max: the bounding box of the points (inclusive), computed by the caller on the host (cell side = the smallest
+ *     multiple of e_B whose grid over the box has at most 2^18 cells; ignored when n == 0).
+ * All arithmetic is integer.  The bin of an ordered pair (i, j), i != j, d2 = dx * dx + dy * dy, is the smallest t with d2 <= e_t^2 (edges
+ * inclusive; no bin beyond e_B; coincident points fall in bin 0):
+ *   pair_hist [C][C][B] int64: the ordered pairs with label_i = a, label_j = b in bin t, not cumulative; a label outside [0, C) is counted in
+ *                              no row and no column.
+ *   nn_d2     [n][C] int32:    the least d2 from i to a j != i of class c with d2 <= e_B^2, -1 for none; written for every i.
+ *   class_n   [C] int64:       the points of each class.
+ * The call zeroes pair_hist and class_n itself.  The result is a pure function of the input: bitwise the same on every call.  n == 0
+ * zeroes pair_hist and class_n and returns NUHTC_OK; n == 1 gives nn_d2 = -1.  NUHTC_E_INVALID, before anything is launched and with the
+ * outputs untouched: B, the edges, num_classes or n out of range, a null pointer, a bounding box that is empty or reaches +-2^27 (so: any
+ * coordinate out of range).  NUHTC_E_INVALID after the binning, the outputs still untouched: a point lies outside the stated bounding box. */
+int nuhtc_cell_spatial(int device, const int32_t* points, const int32_t* labels, int64_t n, int num_classes, const int32_t* edges, int num_bins,
+                       int x_min, int y_min, int x_max, int y_max, int64_t* pair_hist, int32_t* nn_d2, int64_t* class_n, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the launch stream (process-wide switch; off by default).
  * nuhtc_profile_read synchronises the device and writes one text line per kernel tag,
  * "tag launches total_ms algorithmic_flops algorithmic_bytes", then resets the records. */

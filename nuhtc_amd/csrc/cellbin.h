@@ -1,0 +1,128 @@
+// Binning of half-pixel points into a uniform grid (gfx950), shared by the cell graph (cellgraph.hip) and the pair histograms
+// (cellspatial.hip): a histogram of the points per key (atomics), an exclusive scan of the keys (block_exscan_1024 of block_prims.h on 16
+// keys per thread: per-chunk totals, a scan of the totals, the chunks again with their base), and a scatter of (x, y, label, index)
+// records into key order.  A key is a cell, or a (cell, class) pair (cell_key of cellspatial_host.h, which also holds the geometry).  The
+// order of the records INSIDE a key is atomic arrival order; nothing downstream may depend on it.  A point outside the stated bounding
+// box raises the flag and is left out: the caller's later kernels test the flag and write nothing.
+#pragma once
+#include "block_prims.h"
+#include "cellspatial_host.h"
+#include "common.h"
+
+namespace {
+
+constexpr int CB_SCAN_PER = 16;                       // keys per thread of the scan
+constexpr int CB_CHUNK = 1024 * CB_SCAN_PER;          // keys per workgroup of the scan
+
+struct CellBin {
+  const int32_t* points;    // [n][2] half pixels
+  const int32_t* labels;    // [n]
+  int n;
+  int x_min, y_min, x_max, y_max, side, ncx, ncy;
+  int sub;                  // keys per cell: 1, or C + 1 (the classes and one more for a label outside them)
+  int* cell_count;          // [nchunk * CB_CHUNK], zero past the keys; counted up by the histogram, down again by the scatter
+  int* cell_start;          // [nchunk * CB_CHUNK]: entry k = records in front of key k (entry ncx * ncy * sub: all of them)
+  int* chunk_base;          // [1024]: records in front of each scan chunk
+  int4* recs;               // [n] (x, y, label, index) in key order
+  int* flag;                // != 0: a point lies outside the stated bounding box
+};
+
+// the key of a point, or -1 (and the flag) when it lies outside the box the grid was laid over
+__device__ __forceinline__ int cb_key_of(const CellBin& a, int x, int y, int label) {
+  if (x < a.x_min || x > a.x_max || y < a.y_min || y > a.y_max) { *a.flag = 1; return -1; }
+  return cell_key(cell_index(x, y, a.x_min, a.y_min, a.side, a.ncx), label, a.sub);
+}
+
+__global__ __launch_bounds__(256) void cb_count_kernel(CellBin a) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n) return;
+  const int c = cb_key_of(a, a.points[2 * i], a.points[2 * i + 1], a.labels[i]);
+  if (c >= 0) atomicAdd(&a.cell_count[c], 1);
+}
+
+// sum of the 16 keys of this thread (two 32-byte halves: 16-byte vector loads)
+__device__ __forceinline__ int cb_load16(const int* __restrict__ src, int v[CB_SCAN_PER]) {
+  int s = 0;
+#pragma unroll
+  for (int q = 0; q < CB_SCAN_PER / 4; ++q) {
+    const int4 w = reinterpret_cast<const int4*>(src)[q];
+    v[4 * q] = w.x; v[4 * q + 1] = w.y; v[4 * q + 2] = w.z; v[4 * q + 3] = w.w;
+    s += w.x + w.y + w.z + w.w;
+  }
+  return s;
+}
+
+__global__ __launch_bounds__(1024) void cb_chunk_total_kernel(CellBin a) {
+  __shared__ int lds16[17];
+  int v[CB_SCAN_PER], total;
+  const int s = cb_load16(a.cell_count + (size_t)blockIdx.x * CB_CHUNK + threadIdx.x * CB_SCAN_PER, v);
+  block_exscan_1024(s, lds16, &total);
+  if (threadIdx.x == 0) a.chunk_base[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(1024) void cb_chunk_scan_kernel(CellBin a, int nchunk) {
+  __shared__ int lds16[17];
+  int total;
+  const int v = (int)threadIdx.x < nchunk ? a.chunk_base[threadIdx.x] : 0;
+  const int ex = block_exscan_1024(v, lds16, &total);
+  if ((int)threadIdx.x < nchunk) a.chunk_base[threadIdx.x] = ex;
+}
+
+__global__ __launch_bounds__(1024) void cb_cell_scan_kernel(CellBin a) {
+  __shared__ int lds16[17];
+  int v[CB_SCAN_PER], total;
+  const size_t at = (size_t)blockIdx.x * CB_CHUNK + threadIdx.x * CB_SCAN_PER;
+  const int s = cb_load16(a.cell_count + at, v);
+  int acc = a.chunk_base[blockIdx.x] + block_exscan_1024(s, lds16, &total);
+#pragma unroll
+  for (int q = 0; q < CB_SCAN_PER / 4; ++q) {
+    int4 w;
+    w.x = acc; acc += v[4 * q];
+    w.y = acc; acc += v[4 * q + 1];
+    w.z = acc; acc += v[4 * q + 2];
+    w.w = acc; acc += v[4 * q + 3];
+    reinterpret_cast<int4*>(a.cell_start + at)[q] = w;
+  }
+}
+
+__global__ __launch_bounds__(256) void cb_scatter_kernel(CellBin a) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n) return;
+  const int x = a.points[2 * i], y = a.points[2 * i + 1], label = a.labels[i];
+  const int c = cb_key_of(a, x, y, label);
+  if (c < 0) return;
+  const int pos = a.cell_start[c] + atomicSub(&a.cell_count[c], 1) - 1;       // the key fills from its end; the counts return to zero
+  a.recs[pos] = make_int4(x, y, label, i);
+}
+
+// Lays the grid of `reach`-multiple cells (at most max_cells of them) over the box, allocates the tables and the records from `tmp` and
+// clears the counts and the flag on s.  n >= 1, the box and the reach already checked.  Returns the number of scan chunks, or 0 when an
+// allocation or a memset failed.
+inline int cellbin_setup(CellBin& a, const int32_t* points, const int32_t* labels, int n, int x_min, int y_min, int x_max, int y_max, int reach,
+                         int max_cells, int sub, DevScratch& tmp, hipStream_t s) {
+  a.points = points; a.labels = labels; a.n = n; a.sub = sub;
+  a.x_min = x_min; a.y_min = y_min; a.x_max = x_max; a.y_max = y_max;
+  a.side = cell_grid_side(x_min, y_min, x_max, y_max, reach, max_cells);
+  a.ncx = (int)cell_cells_along(x_min, x_max, a.side); a.ncy = (int)cell_cells_along(y_min, y_max, a.side);
+  const int nkey = a.ncx * a.ncy * sub;                          // <= 2^22
+  const int nchunk = (nkey + 1 + CB_CHUNK - 1) / CB_CHUNK;       // + 1: the entry behind the last key holds the total; at most 257
+  const size_t keys_bytes = (size_t)nchunk * CB_CHUNK * sizeof(int);
+  a.cell_count = tmp.alloc<int>(keys_bytes); a.cell_start = tmp.alloc<int>(keys_bytes);
+  a.chunk_base = tmp.alloc<int>(1024 * sizeof(int)); a.flag = tmp.alloc<int>(sizeof(int));
+  a.recs = tmp.alloc<int4>((size_t)n * sizeof(int4));
+  if (!tmp.ok()) return 0;
+  if (hipMemsetAsync(a.cell_count, 0, keys_bytes, s) != hipSuccess || hipMemsetAsync(a.flag, 0, sizeof(int), s) != hipSuccess) return 0;
+  return nchunk;
+}
+
+// the five launches of the binning, on s
+inline void cellbin_launch(const CellBin& a, int nchunk, hipStream_t s) {
+  const unsigned nb = (unsigned)((a.n + 255) / 256);
+  hipLaunchKernelGGL(cb_count_kernel, dim3(nb), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(cb_chunk_total_kernel, dim3(nchunk), dim3(1024), 0, s, a);
+  hipLaunchKernelGGL(cb_chunk_scan_kernel, dim3(1), dim3(1024), 0, s, a, nchunk);
+  hipLaunchKernelGGL(cb_cell_scan_kernel, dim3(nchunk), dim3(1024), 0, s, a);
+  hipLaunchKernelGGL(cb_scatter_kernel, dim3(nb), dim3(256), 0, s, a);
+}
+
+}  // namespace

@@ -32,6 +32,13 @@ Output (like the reference, :659-693), for every detection that survives the per
                   disc, built on rank 0's GPU after the gather (nuhtc_amd/cellgraph.py): `nuclei_id`, `xy` (the centres of
                   <id>_point.geojson), `neighbors` (rows of this file, -1 = none), `dist` (px, inf = none), `class_count`, `label`.  Row-aligned
                   with <id>_nuclei_feat.npz when both flags are given; every other file is the same bytes with and without the flag.
+  --nuclei-spatial: (not in the reference) <id>_nuclei_spatial.npz beside the documents, for the same rows as --nuclei-graph: the counts of
+                  ordered pairs of nuclei by class pair and distance bin (edges at --spatial-step px, 2 x --spatial-step, .. up to
+                  --spatial-bins of them: 256 px by default) and every nucleus's distance to the nearest nucleus of each class, counted
+                  on rank 0's GPU after the gather (nuhtc_amd/spatial.py): `pair_hist`, `class_n`, `nn_d2` / `nn_dist`, `edges_px`, the
+                  derived `mean_within` and `G`, and `K_tiles_area` / `L_tiles_area`, Ripley's K and L under the area of the inferred
+                  tiles (`tiles_area_px` = tiles x step_size^2; no edge correction, no estimate of the tissue area).  Every other file
+                  is the same bytes with and without the flag.  There is no route without a GPU.
   --nuclei-morph: (the reference's tools/wsi_feat_extract.py table, computed on the GPU) <id>_nuclei_morph.npz beside the documents, for the
                   same rows: `columns` and `values` float64 (n, F) -- size, shape, orientation, position and haematoxylin-intensity features
                   under histomicstk's names, derived on the host (nuhtc_amd/nucmorph.py derive) from the integers every rank's GPU measured
@@ -109,6 +116,13 @@ def build_parser():
     p.add_argument('--graph-radius', type=float, default=64.0, dest='graph_radius',
                    help='radius of --nuclei-graph in slide px, a multiple of 0.5 up to 8192 (default 64 px: 16 um at 40x)')
     p.add_argument('--graph-k', type=int, default=8, dest='graph_k', help='neighbours kept per nucleus by --nuclei-graph, 1..32 (default 8)')
+    p.add_argument('--nuclei-spatial', action='store_true', dest='nuclei_spatial',
+                   help='also write <id>_nuclei_spatial.npz: pair counts by class pair and distance bin and the nearest nucleus of every class for every '
+                        'written nucleus, counted on the GPU (rows as in <id>_nuclei_feat.npz)')
+    p.add_argument('--spatial-step', type=float, default=8.0, dest='spatial_step',
+                   help='width of a distance bin of --nuclei-spatial in slide px, a multiple of 0.5 (default 8 px)')
+    p.add_argument('--spatial-bins', type=int, default=32, dest='spatial_bins',
+                   help='distance bins of --nuclei-spatial, 1..32; the reach is step x bins <= 8192 px (default 32: 256 px, 64 um at 40x)')
     return p
 
 
@@ -227,7 +241,8 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
             msg += f', {len(kept)} after the cross-tile merge'
             feat_rows = np.asarray(kept, np.int64)
     graph = getattr(args, 'nuclei_graph', False)
-    if sel or graph:                                                  # the rows of the per-nucleus files, and their labels and scores
+    spatial_on = getattr(args, 'nuclei_spatial', False)
+    if sel or graph or spatial_on:                                    # the rows of the per-nucleus files, and their labels and scores
         hall = np.concatenate([h.cpu().numpy() for h in heads], 0).reshape(-1, 9)
         rows = np.arange(n_records, dtype=np.int64) if feat_rows is None else feat_rows
     for i, kind in enumerate(sel):
@@ -241,6 +256,15 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
                                      device=local_rank if world > 1 else (torch.device(args.device).index or 0))
         cellgraph.write_npz(os.path.join(out_dir, name + '_nuclei_graph.npz'), rows, cellgraph.centres(boxes), nb, d2, cc, lab, args.graph_radius, args.graph_k)
         msg += f', {int((nb >= 0).sum())} edges (k {args.graph_k}, {args.graph_radius:g} px) in {name}_nuclei_graph.npz'
+    if spatial_on:                                                    # pair counts over the same rows, from the same gathered boxes
+        from nuhtc_amd import cellgraph, spatial
+        boxes, lab = hall[rows, :4], hall[rows, 5].astype(np.int64)
+        edges = spatial.edges_from_step(args.spatial_step, args.spatial_bins)
+        ph, nn, cn = spatial.build(cellgraph.quantize_centres(boxes), lab, len(model.CLASSES), edges,
+                                   device=local_rank if world > 1 else (torch.device(args.device).index or 0))
+        spatial.write_npz(os.path.join(out_dir, name + '_nuclei_spatial.npz'), rows, cellgraph.centres(boxes), lab, edges, ph, nn, cn,
+                          tiles_area_px=float(len(bag)) * float(args.step_size) ** 2)
+        msg += f', {int(ph.sum())} ordered pairs within {edges[-1] / 2:g} px ({len(edges)} bins) in {name}_nuclei_spatial.npz'
     if want('dsa'):
         outputs.write_json(os.path.join(out_dir, name + '_dsa.json'), outputs.dsa_document(dsa))
     if want('coco'):
@@ -289,6 +313,14 @@ def main(argv=None):
             cellgraph.check_args(1, cellgraph.half_pixel_radius(args.graph_radius), args.graph_k)
         except ValueError as e:
             raise SystemExit(f'--nuclei-graph: {e}')
+    if args.nuclei_spatial:
+        from nuhtc_amd import spatial
+        try:
+            spatial.edges_from_step(args.spatial_step, args.spatial_bins)
+        except ValueError as e:
+            raise SystemExit(f'--nuclei-spatial: {e}')
+        if not torch.cuda.is_available():
+            raise SystemExit('--nuclei-spatial: no GPU is visible (there is no fallback)')
     # the process group is formed AFTER seg_and_patch: rank 0's host phase (segmentation, masks, patching, stitching of every slide of the
     # folder) has no time bound, and a rank waiting in an RCCL barrier is aborted by the watchdog after 10 minutes
     rank, local_rank, world = parallel.env_ranks()
