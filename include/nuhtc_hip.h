@@ -955,6 +955,33 @@ int nuhtc_cell_graph(int device, const int32_t* points, const int32_t* labels, i
 int nuhtc_cell_spatial(int device, const int32_t* points, const int32_t* labels, int64_t n, int num_classes, const int32_t* edges, int num_bins,
                        int x_min, int y_min, int x_max, int y_max, int64_t* pair_hist, int32_t* nn_d2, int64_t* class_n, void* stream);
 
+/* Nucleus clusters of a slide (csrc/cellcluster.hip; nuhtc_amd/clusters.py has the definition and its brute-force int64 restatement
+ * `cluster_reference`): DBSCAN with a deterministic choice for border points.  Not in the reference.  Engine-free like the cell graph's
+ * call: points, labels and the eight outputs are device memory of `device`, the call allocates and frees its own scratch, runs on `stream`
+ * and synchronises it before returning.  nuhtc_config is unchanged (no ABI bump).
+ *   points [n][2] int32: node positions in HALF pixels (as for the cell graph), |p| < 2^27.  labels [n] int32.  0 <= n <= 2^24: the dense
+ *     numbering scans one flag per point in at most 1024 chunks of 16384, and no slide has that many nuclei.
+ *   num_classes C: 1 .. 14.  r: the radius in half pixels, 1 .. 16384.  min_pts >= 1.  by_class: 0 or 1.
+ *   x_min, y_min, x_max, y_max: the bounding box of the points (inclusive), computed by the caller on the host (cell side = the smallest
+ *     multiple of r whose grid over the box has at most 2^22 cells; ignored when n == 0).
+ * All arithmetic is integer.  adj(i, j): dx * dx + dy * dy <= r * r (inclusive; adj(i, i) holds; coincident points are adjacent) and, with
+ * by_class, labels[i] == labels[j] (plain equality, also for labels outside [0, C)).  degree[i] = the number of j with adj(i, j), i among
+ * them; i is a core point when degree[i] >= min_pts.  Clusters are the connected components of adj among core points, the root of a
+ * cluster is its smallest core row, and clusters are numbered 0 .. m - 1 by ascending root.  A non-core point with an adjacent core point
+ * (a border point) joins the cluster of the adjacent core point with the smallest (d2, j); every other point is noise.
+ *   cluster [n] int32: the cluster of every point, -1 for noise.  core [n] uint8: 1 for a core point.  degree [n] int32.
+ *   Per cluster, n rows of capacity each, the first m written and the rest untouched:
+ *   size [.] int32, n_core [.] int32, class_count [.][C] int32 (a label outside [0, C) is counted in no class),
+ *   sum_xy [.][2] int64 (half pixels), bbox [.][4] int32 (x_min, y_min, x_max, y_max, half pixels).
+ *   m: HOST memory, the number of clusters, written on success only.
+ * The result is a pure function of the input: bitwise the same on every call.  n == 0 sets m = 0, launches nothing and returns NUHTC_OK.
+ * NUHTC_E_INVALID, before anything is launched and with the outputs untouched: n, num_classes, r, min_pts or by_class out of range, a null
+ * pointer (m always, the others with n > 0), a bounding box that is empty or reaches +-2^27 (so: any coordinate out of range).
+ * NUHTC_E_INVALID after the binning, the outputs still untouched: a point lies outside the stated bounding box. */
+int nuhtc_cell_clusters(int device, const int32_t* points, const int32_t* labels, int64_t n, int num_classes, int r, int min_pts, int by_class,
+                        int x_min, int y_min, int x_max, int y_max, int32_t* cluster, uint8_t* core, int32_t* degree, int32_t* size,
+                        int32_t* n_core, int32_t* class_count, int64_t* sum_xy, int32_t* bbox, int64_t* m, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the launch stream (process-wide switch; off by default).
  * nuhtc_profile_read synchronises the device and writes one text line per kernel tag,
  * "tag launches total_ms algorithmic_flops algorithmic_bytes", then resets the records. */

@@ -39,6 +39,14 @@ Output (like the reference, :659-693), for every detection that survives the per
                   derived `mean_within` and `G`, and `K_tiles_area` / `L_tiles_area`, Ripley's K and L under the area of the inferred
                   tiles (`tiles_area_px` = tiles x step_size^2; no edge correction, no estimate of the tissue area).  Every other file
                   is the same bytes with and without the flag.  There is no route without a GPU.
+  --nuclei-clusters: (not in the reference) <id>_nuclei_clusters.npz beside the documents, for the same rows as --nuclei-graph: which
+                  nuclei belong together -- DBSCAN within --cluster-radius px (32 by default) and --cluster-min nuclei (5, the nucleus itself
+                  counted), over all nuclei or, with --cluster-by class, among nuclei of one label -- found on rank 0's GPU after the gather
+                  (nuhtc_amd/clusters.py): per nucleus `cluster` (-1 = isolated), `core`, `degree`; per cluster `size`, `n_core`,
+                  `class_count`, `sum_xy`, `bbox` (half pixels) and the derived `centroid_px`, `bbox_px`, `class_fraction`; per slide
+                  `n_clusters`, `n_noise`, `class_clustered_share`.  A border nucleus joins the nearest core nucleus's cluster (ties: the
+                  smaller row), so the file is a pure function of the rows.  Every other file is the same bytes with and without the flag.
+                  There is no route without a GPU.
   --nuclei-morph: (the reference's tools/wsi_feat_extract.py table, computed on the GPU) <id>_nuclei_morph.npz beside the documents, for the
                   same rows: `columns` and `values` float64 (n, F) -- size, shape, orientation, position and haematoxylin-intensity features
                   under histomicstk's names, derived on the host (nuhtc_amd/nucmorph.py derive) from the integers every rank's GPU measured
@@ -123,6 +131,15 @@ def build_parser():
                    help='width of a distance bin of --nuclei-spatial in slide px, a multiple of 0.5 (default 8 px)')
     p.add_argument('--spatial-bins', type=int, default=32, dest='spatial_bins',
                    help='distance bins of --nuclei-spatial, 1..32; the reach is step x bins <= 8192 px (default 32: 256 px, 64 um at 40x)')
+    p.add_argument('--nuclei-clusters', action='store_true', dest='nuclei_clusters',
+                   help='also write <id>_nuclei_clusters.npz: the DBSCAN cluster of every written nucleus (-1: isolated) and the size, class counts, '
+                        'centroid and box of every cluster, found on the GPU (rows as in <id>_nuclei_feat.npz)')
+    p.add_argument('--cluster-radius', type=float, default=32.0, dest='cluster_radius',
+                   help='radius of --nuclei-clusters in slide px, a multiple of 0.5 up to 8192 (default 32 px: 8 um at 40x)')
+    p.add_argument('--cluster-min', type=int, default=5, dest='cluster_min',
+                   help='nuclei within the radius, the nucleus itself counted, that make a core nucleus of --nuclei-clusters (default 5)')
+    p.add_argument('--cluster-by', choices=('any', 'class'), default='any', dest='cluster_by',
+                   help="--nuclei-clusters over all nuclei ('any') or only among nuclei of the same label ('class')")
     return p
 
 
@@ -242,7 +259,8 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
             feat_rows = np.asarray(kept, np.int64)
     graph = getattr(args, 'nuclei_graph', False)
     spatial_on = getattr(args, 'nuclei_spatial', False)
-    if sel or graph or spatial_on:                                    # the rows of the per-nucleus files, and their labels and scores
+    clusters_on = getattr(args, 'nuclei_clusters', False)
+    if sel or graph or spatial_on or clusters_on:                                    # the rows of the per-nucleus files, and their labels and scores
         hall = np.concatenate([h.cpu().numpy() for h in heads], 0).reshape(-1, 9)
         rows = np.arange(n_records, dtype=np.int64) if feat_rows is None else feat_rows
     for i, kind in enumerate(sel):
@@ -265,6 +283,16 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
         spatial.write_npz(os.path.join(out_dir, name + '_nuclei_spatial.npz'), rows, cellgraph.centres(boxes), lab, edges, ph, nn, cn,
                           tiles_area_px=float(len(bag)) * float(args.step_size) ** 2)
         msg += f', {int(ph.sum())} ordered pairs within {edges[-1] / 2:g} px ({len(edges)} bins) in {name}_nuclei_spatial.npz'
+    if clusters_on:                                                   # which of the same rows belong together
+        from nuhtc_amd import clusters
+        boxes, lab = hall[rows, :4], hall[rows, 5].astype(np.int64)
+        by = clusters.BY[args.cluster_by]
+        found = clusters.build(clusters.quantize_centres(boxes), lab, len(model.CLASSES), args.cluster_radius, args.cluster_min, by,
+                               device=local_rank if world > 1 else (torch.device(args.device).index or 0))
+        clusters.write_npz(os.path.join(out_dir, name + '_nuclei_clusters.npz'), rows, clusters.centres(boxes), lab, *found,
+                           radius_px=args.cluster_radius, min_pts=args.cluster_min, by_class=by)
+        msg += (f', {len(found[3])} clusters and {int((found[0] < 0).sum())} isolated nuclei ({args.cluster_radius:g} px, {args.cluster_min} nuclei, '
+                f'by {args.cluster_by}) in {name}_nuclei_clusters.npz')
     if want('dsa'):
         outputs.write_json(os.path.join(out_dir, name + '_dsa.json'), outputs.dsa_document(dsa))
     if want('coco'):
@@ -321,6 +349,14 @@ def main(argv=None):
             raise SystemExit(f'--nuclei-spatial: {e}')
         if not torch.cuda.is_available():
             raise SystemExit('--nuclei-spatial: no GPU is visible (there is no fallback)')
+    if args.nuclei_clusters:
+        from nuhtc_amd import clusters
+        try:
+            clusters.check_args(1, clusters.half_pixel_radius(args.cluster_radius), args.cluster_min, clusters.BY[args.cluster_by])
+        except ValueError as e:
+            raise SystemExit(f'--nuclei-clusters: {e}')
+        if not torch.cuda.is_available():
+            raise SystemExit('--nuclei-clusters: no GPU is visible (there is no fallback)')
     # the process group is formed AFTER seg_and_patch: rank 0's host phase (segmentation, masks, patching, stitching of every slide of the
     # folder) has no time bound, and a rank waiting in an RCCL barrier is aborted by the watchdog after 10 minutes
     rank, local_rank, world = parallel.env_ranks()
