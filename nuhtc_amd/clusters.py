@@ -33,7 +33,9 @@ parent never exceeds its child -- so the smallest row of a component is its root
 scan.  `derive` makes the float64 side on the host: centroids and boxes in px, class fractions per cluster, and the slide's counts."""
 import numpy as np
 
-from .cellgraph import COORD_LIMIT, MAX_CLASSES, MAX_R, cell_side, centres, half_pixel_radius, quantize_centres  # noqa: F401 (the one copy)
+from . import cellpoints
+from .cellgraph import cell_side  # noqa: F401 (the cell graph's grid, re-exported)
+from .cellpoints import COORD_LIMIT, MAX_CLASSES, MAX_R, centres, half_pixel_radius, quantize_centres  # noqa: F401 (re-exported)
 
 MAX_POINTS = 1 << 24
 MAX_MIN_PTS = (1 << 31) - 1
@@ -76,24 +78,13 @@ def cluster_reference(points, labels, num_classes, r, min_pts, by_class):
     (24 bytes each): meant for a few thousand points, or more where few are adjacent.  The components come from that list by repeated
     minimum over the core-core pairs and pointer jumping, with no grid and no tree."""
     check_args(num_classes, r, min_pts, by_class)
-    p = np.asarray(points, np.int64).reshape(-1, 2)
-    lab = np.asarray(labels, np.int64).reshape(-1)
+    p, lab = cellpoints.reference_points(points, labels, 'cluster_reference')
     n, C, r, min_pts, by_class = len(p), int(num_classes), int(r), int(min_pts), int(by_class)
-    if len(lab) != n:
-        raise ValueError('cluster_reference: one label per point')
-    if n and np.abs(p).max() >= COORD_LIMIT:
-        raise ValueError('cluster_reference: a coordinate lies outside |p| < 2**27')
     idx = np.arange(n, dtype=np.int64)
     none = np.iinfo(np.int64).max
     degree = np.zeros(n, np.int64)
     ii, jj, dd = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]      # every adjacent ordered pair and its d2
-    for i0 in range(0, n, 256):
-        rows = idx[i0:i0 + 256]
-        d2 = p[rows, None, 0] - p[None, :, 0]
-        d2 *= d2
-        dy = p[rows, None, 1] - p[None, :, 1]
-        dy *= dy
-        d2 += dy
+    for rows, d2 in cellpoints.pair_blocks(p, 256):
         adj = d2 <= r * r
         if by_class:
             adj &= lab[rows, None] == lab[None, :]
@@ -131,25 +122,11 @@ def call(points, labels, num_classes, r, min_pts, by_class, cluster, core, degre
     """nuhtc_cell_clusters on torch tensors of cuda:`device` (points, labels, cluster, degree, size, n_core, class_count, bbox int32; core
     uint8; sum_xy int64; contiguous; the per-cluster tensors with n rows; r in HALF pixels) -> (the library's return code, m), nothing
     raised: the code is 0 or hip.E_INVALID / hip.E_HIP, m the number of clusters (None unless the code is 0).  bounds = (x_min, y_min,
-    x_max, y_max) of the points, computed here on the host when not given."""
+    x_max, y_max) of the points, computed on the host when not given."""
     import ctypes
-    import torch
-    from . import hip
-    lib = hip.load()
-    n = int(points.shape[0])
-    if bounds is None:
-        if n:
-            ph = points.cpu().numpy()
-            bounds = (int(ph[:, 0].min()), int(ph[:, 1].min()), int(ph[:, 0].max()), int(ph[:, 1].max()))
-        else:
-            bounds = (0, 0, 0, 0)
-    vp = lambda t: ctypes.c_void_p(t.data_ptr())
-    dev = torch.device('cuda', device)
     m = ctypes.c_int64(-1)
-    with torch.cuda.device(dev):
-        rc = lib.nuhtc_cell_clusters(int(device), vp(points), vp(labels), n, int(num_classes), int(r), int(min_pts), int(by_class),
-                                     *(int(b) for b in bounds), vp(cluster), vp(core), vp(degree), vp(size), vp(n_core), vp(class_count),
-                                     vp(sum_xy), vp(bbox), ctypes.byref(m), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    rc = cellpoints.launch('nuhtc_cell_clusters', device, points, labels, (int(num_classes), int(r), int(min_pts), int(by_class)),
+                           (cluster, core, degree, size, n_core, class_count, sum_xy, bbox), bounds, extra=(ctypes.byref(m),))
     return rc, (int(m.value) if rc == 0 else None)
 
 
@@ -162,29 +139,18 @@ def outputs(n, num_classes, device, fill=0):
 
 
 def build(points, labels, num_classes, radius_px, min_pts, by_class=0, device=0):
-    """The clusters of `points` (int (n, 2) half pixels, see cellgraph.quantize_centres) with `labels` (n,) on cuda:`device`: numpy in,
+    """The clusters of `points` (int (n, 2) half pixels, see cellpoints.quantize_centres) with `labels` (n,) on cuda:`device`: numpy in,
     the eight arrays of `cluster_reference` out (the per-cluster ones cut to their m rows).  There is no host route: without the library or
     a GPU this raises."""
-    import torch
-    from . import hip
-    p = np.ascontiguousarray(np.asarray(points).reshape(-1, 2), np.int32)
-    if not np.array_equal(p, np.asarray(points).reshape(-1, 2)):
-        raise ValueError('clusters: the points are not int32 half pixels')
-    lab = np.ascontiguousarray(np.asarray(labels).reshape(-1), np.int32)
+    p, lab = cellpoints.as_points(points, labels, 'clusters')
     n, C, r = len(p), int(num_classes), half_pixel_radius(radius_px)
-    if len(lab) != n:
-        raise ValueError('clusters: one label per point')
     if n > MAX_POINTS:
         raise ValueError(f'clusters: at most 2**24 points (got {n})')
     check_args(C, r, min_pts, by_class)
-    dev = torch.device('cuda', device)
-    bounds = (int(p[:, 0].min()), int(p[:, 1].min()), int(p[:, 0].max()), int(p[:, 1].max())) if n else None
+    dev, p_d, lab_d, bounds = cellpoints.upload(p, lab, device)
     out = outputs(n, C, dev)
-    rc, m = call(torch.from_numpy(p).to(dev), torch.from_numpy(lab).to(dev), C, r, int(min_pts), int(by_class), *out, bounds=bounds, device=device)
-    if rc == hip.E_INVALID:
-        raise ValueError('nuhtc_cell_clusters: invalid arguments (a coordinate outside |p| < 2**27?)')
-    if rc:
-        raise RuntimeError(f'nuhtc_cell_clusters failed ({rc})')
+    rc, m = call(p_d, lab_d, C, r, int(min_pts), int(by_class), *out, bounds=bounds, device=device)
+    cellpoints.raise_for(rc, 'nuhtc_cell_clusters')
     return tuple(t.cpu().numpy() for t in out[:3]) + tuple(t[:m].cpu().numpy() for t in out[3:])
 
 
@@ -221,10 +187,8 @@ def write_npz(path, nuclei_id, xy, label, cluster, core, degree, size, n_core, c
       cluster int32 (n,) (-1: noise), core uint8 (n,), degree int32 (n,)
       size, n_core int32 (m,), class_count int32 (m, C), sum_xy int64 (m, 2), bbox int32 (m, 4): the integers of the definition
       the arrays of `derive` (DERIVED_KEYS), and radius_px float64, min_pts int64, by_class int64 as 0-d arrays."""
-    nuclei_id = np.ascontiguousarray(nuclei_id, np.int64).reshape(-1)
-    n = len(nuclei_id)
-    xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
-    label = np.ascontiguousarray(label, np.int64).reshape(-1)
+    head = cellpoints.npz_header(nuclei_id, xy, label)
+    n = len(head['label'])
     cluster = np.ascontiguousarray(cluster, np.int32).reshape(-1)
     core = np.ascontiguousarray(core, np.uint8).reshape(-1)
     degree = np.ascontiguousarray(degree, np.int32).reshape(-1)
@@ -234,16 +198,16 @@ def write_npz(path, nuclei_id, xy, label, cluster, core, degree, size, n_core, c
     class_count = np.ascontiguousarray(class_count, np.int32)
     sum_xy = np.ascontiguousarray(sum_xy, np.int64).reshape(-1, 2)
     bbox = np.ascontiguousarray(bbox, np.int32).reshape(-1, 4)
-    if not (len(xy) == len(label) == len(cluster) == len(core) == len(degree) == n):
+    if not (len(cluster) == len(core) == len(degree) == n):
         raise ValueError('write_npz: one row per nucleus in every per-nucleus field')
     if class_count.ndim != 2 or not (len(n_core) == len(class_count) == len(sum_xy) == len(bbox) == m):
         raise ValueError('write_npz: one row per cluster in every per-cluster field')
     if n and cluster.max() >= m:
         raise ValueError('write_npz: a nucleus lies in a cluster the tables do not hold')
     check_args(class_count.shape[1], half_pixel_radius(radius_px), min_pts, by_class)
-    d = derive(cluster, label, class_count.shape[1], size, class_count, sum_xy, bbox)
+    d = derive(cluster, head['label'], class_count.shape[1], size, class_count, sum_xy, bbox)
     with open(path, 'wb') as f:
-        np.savez(f, nuclei_id=nuclei_id, xy=xy, label=label, cluster=cluster, core=core, degree=degree, size=size, n_core=n_core,
+        np.savez(f, **head, cluster=cluster, core=core, degree=degree, size=size, n_core=n_core,
                  class_count=class_count, sum_xy=sum_xy, bbox=bbox, radius_px=np.asarray(float(radius_px), np.float64),
                  min_pts=np.asarray(int(min_pts), np.int64), by_class=np.asarray(int(by_class), np.int64), **d)
     return path
@@ -251,5 +215,4 @@ def write_npz(path, nuclei_id, xy, label, cluster, core, degree, size, n_core, c
 
 def read_npz(path):
     """-> dict of the arrays of a file write_npz wrote (NPZ_KEYS)."""
-    with np.load(path) as z:
-        return {key: z[key] for key in NPZ_KEYS}
+    return cellpoints.read_npz(path, NPZ_KEYS)

@@ -1,18 +1,28 @@
-// Binning of half-pixel points into a uniform grid (gfx950), shared by the cell graph (cellgraph.hip) and the pair histograms
-// (cellspatial.hip): a histogram of the points per key (atomics), an exclusive scan of the keys (block_exscan_1024 of block_prims.h on 16
-// keys per thread: per-chunk totals, a scan of the totals, the chunks again with their base), and a scatter of (x, y, label, index)
-// records into key order.  A key is a cell, or a (cell, class) pair (cell_key of cellspatial_host.h, which also holds the geometry).  The
-// order of the records INSIDE a key is atomic arrival order; nothing downstream may depend on it.  A point outside the stated bounding
-// box raises the flag and is left out: the caller's later kernels test the flag and write nothing.
+// What the per-slide analyses of half-pixel points share on the device (gfx950) -- the cell graph (cellgraph.hip), the pair histograms
+// (cellspatial.hip) and the clusters (cellcluster.hip); cellgrid_host.h holds the plain-C++ side (limits, geometry, keys, pair distance).
+//   binning   a histogram of the points per key (atomics), an exclusive scan of the keys, and a scatter of (x, y, label, index) records
+//             into key order.  A key is a cell, or a (cell, class) pair (cell_key).  The order of the records INSIDE a key is atomic
+//             arrival order; nothing downstream may depend on it.  A point outside the stated bounding box raises the flag and is left
+//             out: the caller's later kernels test the flag and write nothing.
+//   scan      exclusive scan of up to 1024 chunks of CB_CHUNK ints (ExScan, exscan_launch): block_exscan_1024 of block_prims.h on 16
+//             ints per thread -- per-chunk totals, a scan of the totals, the chunks again with their base.
+//   sweep     cell_sweep: the records within reach of a point, from the 3 x 3 cells around it (one key per cell).
+//   epilogue  cellbin_finish: the flag read back, the stream synchronised, the return code.
 #pragma once
 #include "block_prims.h"
-#include "cellspatial_host.h"
+#include "cellgrid_host.h"
 #include "common.h"
 
 namespace {
 
-constexpr int CB_SCAN_PER = 16;                       // keys per thread of the scan
-constexpr int CB_CHUNK = 1024 * CB_SCAN_PER;          // keys per workgroup of the scan
+constexpr int CB_SCAN_PER = 16;                       // ints per thread of the scan
+constexpr int CB_CHUNK = 1024 * CB_SCAN_PER;          // ints per workgroup of the scan
+
+struct ExScan {
+  const int* in;            // [nchunk * CB_CHUNK], zero past the values
+  int* out;                 // [nchunk * CB_CHUNK]: entry k = the sum of the values in front of k
+  int* chunk_base;          // [1024]: the sum in front of each chunk
+};
 
 struct CellBin {
   const int32_t* points;    // [n][2] half pixels
@@ -40,7 +50,7 @@ __global__ __launch_bounds__(256) void cb_count_kernel(CellBin a) {
   if (c >= 0) atomicAdd(&a.cell_count[c], 1);
 }
 
-// sum of the 16 keys of this thread (two 32-byte halves: 16-byte vector loads)
+// sum of the 16 ints of this thread (two 32-byte halves: 16-byte vector loads)
 __device__ __forceinline__ int cb_load16(const int* __restrict__ src, int v[CB_SCAN_PER]) {
   int s = 0;
 #pragma unroll
@@ -52,15 +62,15 @@ __device__ __forceinline__ int cb_load16(const int* __restrict__ src, int v[CB_S
   return s;
 }
 
-__global__ __launch_bounds__(1024) void cb_chunk_total_kernel(CellBin a) {
+__global__ __launch_bounds__(1024) void cb_chunk_total_kernel(ExScan a) {
   __shared__ int lds16[17];
   int v[CB_SCAN_PER], total;
-  const int s = cb_load16(a.cell_count + (size_t)blockIdx.x * CB_CHUNK + threadIdx.x * CB_SCAN_PER, v);
+  const int s = cb_load16(a.in + (size_t)blockIdx.x * CB_CHUNK + threadIdx.x * CB_SCAN_PER, v);
   block_exscan_1024(s, lds16, &total);
   if (threadIdx.x == 0) a.chunk_base[blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(1024) void cb_chunk_scan_kernel(CellBin a, int nchunk) {
+__global__ __launch_bounds__(1024) void cb_chunk_scan_kernel(ExScan a, int nchunk) {
   __shared__ int lds16[17];
   int total;
   const int v = (int)threadIdx.x < nchunk ? a.chunk_base[threadIdx.x] : 0;
@@ -68,11 +78,11 @@ __global__ __launch_bounds__(1024) void cb_chunk_scan_kernel(CellBin a, int nchu
   if ((int)threadIdx.x < nchunk) a.chunk_base[threadIdx.x] = ex;
 }
 
-__global__ __launch_bounds__(1024) void cb_cell_scan_kernel(CellBin a) {
+__global__ __launch_bounds__(1024) void cb_cell_scan_kernel(ExScan a) {
   __shared__ int lds16[17];
   int v[CB_SCAN_PER], total;
   const size_t at = (size_t)blockIdx.x * CB_CHUNK + threadIdx.x * CB_SCAN_PER;
-  const int s = cb_load16(a.cell_count + at, v);
+  const int s = cb_load16(a.in + at, v);
   int acc = a.chunk_base[blockIdx.x] + block_exscan_1024(s, lds16, &total);
 #pragma unroll
   for (int q = 0; q < CB_SCAN_PER / 4; ++q) {
@@ -81,7 +91,7 @@ __global__ __launch_bounds__(1024) void cb_cell_scan_kernel(CellBin a) {
     w.y = acc; acc += v[4 * q + 1];
     w.z = acc; acc += v[4 * q + 2];
     w.w = acc; acc += v[4 * q + 3];
-    reinterpret_cast<int4*>(a.cell_start + at)[q] = w;
+    reinterpret_cast<int4*>(a.out + at)[q] = w;
   }
 }
 
@@ -115,14 +125,52 @@ inline int cellbin_setup(CellBin& a, const int32_t* points, const int32_t* label
   return nchunk;
 }
 
+// the three launches of the scan over nchunk * CB_CHUNK padded ints (nchunk <= 1024), on s
+inline void exscan_launch(const ExScan& a, int nchunk, hipStream_t s) {
+  hipLaunchKernelGGL(cb_chunk_total_kernel, dim3(nchunk), dim3(1024), 0, s, a);
+  hipLaunchKernelGGL(cb_chunk_scan_kernel, dim3(1), dim3(1024), 0, s, a, nchunk);
+  hipLaunchKernelGGL(cb_cell_scan_kernel, dim3(nchunk), dim3(1024), 0, s, a);
+}
+
 // the five launches of the binning, on s
 inline void cellbin_launch(const CellBin& a, int nchunk, hipStream_t s) {
   const unsigned nb = (unsigned)((a.n + 255) / 256);
   hipLaunchKernelGGL(cb_count_kernel, dim3(nb), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(cb_chunk_total_kernel, dim3(nchunk), dim3(1024), 0, s, a);
-  hipLaunchKernelGGL(cb_chunk_scan_kernel, dim3(1), dim3(1024), 0, s, a, nchunk);
-  hipLaunchKernelGGL(cb_cell_scan_kernel, dim3(nchunk), dim3(1024), 0, s, a);
+  exscan_launch(ExScan{a.cell_count, a.cell_start, a.chunk_base}, nchunk, s);
   hipLaunchKernelGGL(cb_scatter_kernel, dim3(nb), dim3(256), 0, s, a);
+}
+
+// f(j, o, d2) for every record o at position j that passes pre(o) and lies within `reach` of the record `me` -- me itself included
+// (d2 == 0, o.w == me.w) unless pre refuses it -- on a grid with ONE key per cell: the three rows of the 3 x 3 cells around me, each one
+// contiguous range of records.  The lanes of a wave sit in the same or adjacent cells and read the same records: one 16-byte load per
+// record, the same address across most of the wave.  pre runs BEFORE the distance: a compare of two loaded words that spares the
+// multiplies (with the test inside f instead, cc_degree_kernel compiled to 40 VGPRs for 22).
+template <typename P, typename F>
+__device__ __forceinline__ void cell_sweep(const CellBin& g, const int4 me, int reach, P&& pre, F&& f) {
+  const int cx = (me.x - g.x_min) / g.side, cy = (me.y - g.y_min) / g.side;
+  const int cx0 = max(cx - 1, 0), cx1 = min(cx + 1, g.ncx - 1), reach2 = reach * reach;
+  for (int gy = max(cy - 1, 0); gy <= min(cy + 1, g.ncy - 1); ++gy) {
+    const int j0 = g.cell_start[gy * g.ncx + cx0], j1 = g.cell_start[gy * g.ncx + cx1 + 1];
+    for (int j = j0; j < j1; ++j) {
+      const int4 o = g.recs[j];
+      if (!pre(o)) continue;
+      const int d2 = cell_pair_d2(o.x - me.x, o.y - me.y, reach, reach2);
+      if (d2 >= 0) f(j, o, d2);
+    }
+  }
+}
+
+// The end of an entry point: were the launches accepted, the binning's flag read back (and, where the caller has one, one more int of
+// its own: extra_dev -> *extra_host, written only on success), the stream synchronised.  -> 0, NUHTC_E_INVALID when a point lay outside
+// the stated box, NUHTC_E_HIP.
+inline int cellbin_finish(const CellBin& a, hipStream_t s, const int* extra_dev = nullptr, int* extra_host = nullptr) {
+  int h_flag = 0, h_extra = 0;
+  if (!launched() || hipMemcpyAsync(&h_flag, a.flag, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess) return NUHTC_E_HIP;
+  if (extra_dev && hipMemcpyAsync(&h_extra, extra_dev, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess) return NUHTC_E_HIP;
+  if (hipStreamSynchronize(s) != hipSuccess) return NUHTC_E_HIP;
+  if (h_flag) return NUHTC_E_INVALID;
+  if (extra_host) *extra_host = h_extra;
+  return 0;
 }
 
 }  // namespace

@@ -9,11 +9,11 @@
 // arithmetic only: the result is a pure function of the input and bitwise the same on every call.
 //
 // Stages, all on the caller's stream, every one a launch of its own; no kernel waits on another workgroup:
-//   binning    cellbin.h unchanged, reach r, ONE key per cell in both modes.  by_class compares the label in the sweep (`o.z != me.z`) and
+//   binning    cellbin.h, reach r, ONE key per cell in both modes.  by_class compares the label in the sweep (`o.z != me.z`, cc_sweep) and
 //              does not sort on (cell, class): those keys fold every label outside 0 .. C - 1 into one run, while adjacency here is plain
 //              equality of labels, so the run of "the others" would need the compare anyway; one key per cell keeps the graph's 2^22-cell
 //              grid and one set of kernels for both modes, and the compare costs one instruction on a record that is loaded in any case.
-//   degree     one thread per record in cell order, the 3 x 3 sweep of cg_search_kernel (three contiguous ranges of records).  Writes
+//   degree     one thread per record in cell order, the 3 x 3 sweep of cellbin.h (cell_sweep, the point itself included).  Writes
 //              degree and core by original row, the degree again in CELL order (rdeg: the later sweeps read a candidate's core flag next
 //              to its record, not through its row), and parent[row] = row for a core point.
 //   hook       every core point sweeps once more and unites itself with each adjacent core point of a SMALLER row (every pair once).
@@ -29,9 +29,9 @@
 //   resolve    core points walk to their root (plain loads: the hooking is a finished launch).  A non-core point with degree > 1 sweeps
 //              for the smallest (d2 << 32 | j) among its adjacent core points and takes that point's root; the others are noise (-1).
 //              Writes root[row] and rootflag[row] = 1 where root == row.
-//   numbering  exclusive scan of rootflag by the scan kernels of cellbin.h (block_exscan_1024, chunk totals / their scan / the chunks
-//              with their base) -- at most 1024 chunks of 16384 flags, which is why n <= 2^24.  Then cluster[i] = rank[root[i]], the row
-//              rank[i] of every table is cleared where rootflag[i] (bbox to its identity), and m = rank[n - 1] + rootflag[n - 1].
+//   numbering  exclusive scan of rootflag into rank by the scan of cellbin.h (exscan_launch) -- at most 1024 chunks of 16384 flags, which
+//              is why n <= 2^24.  Then cluster[i] = rank[root[i]], the row rank[i] of every table is cleared where rootflag[i] (bbox to
+//              its identity), and m = rank[n - 1] + rootflag[n - 1].
 //   tables     one thread per record in cell order; 32-bit atomic adds for size, n_core and class_count, 64-bit adds for sum_xy, atomic
 //              min / max for bbox.  Threads run in cell order, so a wave holds few clusters: the wave takes the cluster of its first
 //              uncounted lane, reduces over the lanes of that cluster (ballot counts, wave_sum / wave_min / wave_max of block_prims.h
@@ -45,7 +45,7 @@
 // temporaries only), and the call returns NUHTC_E_INVALID.
 //
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, profiles/cell_clusters_resources.txt), VGPRs / SGPRs: the three sweeps --
-// cc_degree_kernel 22 / 34, cc_hook_kernel 22 / 42, cc_resolve_kernel 24 / 46 -- no scratch and no LDS in any of them; cc_number_kernel
+// cc_degree_kernel 22 / 38, cc_hook_kernel 22 / 44, cc_resolve_kernel 23 / 48 -- no scratch and no LDS in any of them; cc_number_kernel
 // 14 / 28, cc_tables_kernel 36 / 32 (wave shuffles only), neither with scratch or LDS.  Registers and LDS never limit the occupancy (8
 // waves per SIMD everywhere): the 32-wave cap of a CU does.
 #include <algorithm>
@@ -79,23 +79,10 @@ struct CellClusterArgs {
   int32_t* bbox;            // [.][4] x_min, y_min, x_max, y_max
 };
 
-// f(j, o, d2) for every record o at position j with adj(me, o), the point itself included: the three rows of the 3 x 3 cells, each one
-// contiguous range of records
+// f(j, o, d2) for every record o at position j with adj(me, o), the point itself included
 template <typename F>
 __device__ __forceinline__ void cc_sweep(const CellBin& g, const int4 me, int r, int by_class, F&& f) {
-  const int cx = (me.x - g.x_min) / g.side, cy = (me.y - g.y_min) / g.side;
-  const int cx0 = max(cx - 1, 0), cx1 = min(cx + 1, g.ncx - 1), r2 = r * r;
-  for (int gy = max(cy - 1, 0); gy <= min(cy + 1, g.ncy - 1); ++gy) {
-    const int j0 = g.cell_start[gy * g.ncx + cx0], j1 = g.cell_start[gy * g.ncx + cx1 + 1];
-    for (int j = j0; j < j1; ++j) {
-      const int4 o = g.recs[j];
-      const int dx = o.x - me.x, dy = o.y - me.y;        // |p| < 2^27: no overflow
-      if (dx > r || dx < -r || dy > r || dy < -r || (by_class && o.z != me.z)) continue;
-      const int dd = dx * dx + dy * dy;                  // <= 2 * 16384^2 = 2^29
-      if (dd > r2) continue;
-      f(j, o, dd);
-    }
-  }
+  cell_sweep(g, me, r, [&](const int4& o) { return !by_class || o.z == me.z; }, f);
 }
 
 __global__ __launch_bounds__(CC_NT) void cc_degree_kernel(CellClusterArgs a) {
@@ -237,10 +224,9 @@ __global__ __launch_bounds__(CC_NT) void cc_tables_kernel(CellClusterArgs a) {
 extern "C" int nuhtc_cell_clusters(int device, const int32_t* points, const int32_t* labels, int64_t n, int num_classes, int r, int min_pts,
                                    int by_class, int x_min, int y_min, int x_max, int y_max, int32_t* cluster, uint8_t* core, int32_t* degree,
                                    int32_t* size, int32_t* n_core, int32_t* class_count, int64_t* sum_xy, int32_t* bbox, int64_t* m, void* stream) {
-  if (n < 0 || n > CC_MAX_POINTS || r < 1 || r > 16384 || min_pts < 1 || num_classes < 1 || num_classes > 14 || (by_class != 0 && by_class != 1) || !m)
+  if (!cell_call_ok(n, CC_MAX_POINTS, num_classes, r, x_min, y_min, x_max, y_max) || min_pts < 1 || (by_class != 0 && by_class != 1) || !m)
     return NUHTC_E_INVALID;
   if (n > 0 && (!points || !labels || !cluster || !core || !degree || !size || !n_core || !class_count || !sum_xy || !bbox)) return NUHTC_E_INVALID;
-  if (n > 0 && !cell_box_ok(x_min, y_min, x_max, y_max)) return NUHTC_E_INVALID;
   if (n == 0) { *m = 0; return 0; }
   if (hipSetDevice(device) != hipSuccess) return NUHTC_E_HIP;
   hipStream_t s = (hipStream_t)stream;
@@ -256,9 +242,7 @@ extern "C" int nuhtc_cell_clusters(int device, const int32_t* points, const int3
   const size_t flag_bytes = (size_t)fchunk * CB_CHUNK * sizeof(int);
   a.rdeg = tmp.alloc<int>((size_t)n * sizeof(int)); a.parent = tmp.alloc<int>((size_t)n * sizeof(int)); a.root = tmp.alloc<int>((size_t)n * sizeof(int));
   a.rootflag = tmp.alloc<int>(flag_bytes); a.rank = tmp.alloc<int>(flag_bytes); a.m_dev = tmp.alloc<int>(sizeof(int));
-  CellBin scan;        // the root flags as the "counts" of the scan kernels of cellbin.h
-  memset(&scan, 0, sizeof(scan));
-  scan.cell_count = a.rootflag; scan.cell_start = a.rank; scan.chunk_base = tmp.alloc<int>(1024 * sizeof(int));
+  const ExScan scan{a.rootflag, a.rank, tmp.alloc<int>(1024 * sizeof(int))};
   if (!tmp.ok()) return NUHTC_E_HIP;
   if (hipMemsetAsync(a.rootflag, 0, flag_bytes, s) != hipSuccess || hipMemsetAsync(a.m_dev, 0, sizeof(int), s) != hipSuccess) return NUHTC_E_HIP;
   const unsigned nb = (unsigned)((n + CC_NT - 1) / CC_NT);
@@ -280,20 +264,15 @@ extern "C" int nuhtc_cell_clusters(int device, const int32_t* points, const int3
   }
   {
     ProfScope ps("cell_clusters_number", 0, 0, s);
-    hipLaunchKernelGGL(cb_chunk_total_kernel, dim3(fchunk), dim3(1024), 0, s, scan);
-    hipLaunchKernelGGL(cb_chunk_scan_kernel, dim3(1), dim3(1024), 0, s, scan, fchunk);
-    hipLaunchKernelGGL(cb_cell_scan_kernel, dim3(fchunk), dim3(1024), 0, s, scan);
+    exscan_launch(scan, fchunk, s);
     hipLaunchKernelGGL(cc_number_kernel, dim3(nb), dim3(CC_NT), 0, s, a);
   }
   {
     ProfScope ps("cell_clusters_tables", 0, 0, s);
     hipLaunchKernelGGL(cc_tables_kernel, dim3(nb), dim3(CC_NT), 0, s, a);
   }
-  int h_flag = 0, h_m = 0;
-  if (!launched() || hipMemcpyAsync(&h_flag, a.b.flag, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipMemcpyAsync(&h_m, a.m_dev, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-    return NUHTC_E_HIP;
-  if (h_flag) return NUHTC_E_INVALID;
-  *m = h_m;
-  return 0;
+  int h_m = 0;
+  const int rc = cellbin_finish(a.b, s, a.m_dev, &h_m);
+  if (rc == 0) *m = h_m;
+  return rc;
 }

@@ -1,0 +1,60 @@
+// The uniform grid over half-pixel points that the per-slide analyses share (cellbin.h; cellgraph.hip, cellspatial.hip, cellcluster.hip):
+// the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell and the
+// (cell, class) key of a point, and the squared distance of a pair within reach.  Header-only, so a host program can exercise them under a
+// sanitizer (tools/dev/cellspatial_host_check.cpp); the kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
+#pragma once
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define CELL_HD __host__ __device__
+#else
+#define CELL_HD
+#endif
+
+constexpr int CELL_COORD_LIMIT = 1 << 27;              // |p| < 2^27 half pixels
+constexpr int64_t CELL_MAX_POINTS = (int64_t)1 << 28;
+constexpr int CELL_MAX_REACH = 16384;                  // half pixels: the largest radius or bin edge
+constexpr int CELL_MAX_CLASSES = 14;
+
+// ---- grid geometry over the inclusive bounding box
+CELL_HD inline long long cell_cells_along(int lo, int hi, long long side) { return ((long long)hi - lo) / side + 1; }
+
+// the cell side: the smallest multiple m * r of the reach r whose grid over the box has at most max_cells cells, so side >= r and the
+// 3 x 3 cells around a point hold its whole disc.  The cell count does not grow with m: bisection; at hi the grid is one cell.
+inline int cell_grid_side(int x_min, int y_min, int x_max, int y_max, int r, int max_cells) {
+  long long lo = 1, hi = (1LL << 29) / r + 1;
+  while (lo < hi) {
+    const long long m = (lo + hi) / 2;
+    if (cell_cells_along(x_min, x_max, m * r) * cell_cells_along(y_min, y_max, m * r) <= max_cells) hi = m; else lo = m + 1;
+  }
+  return (int)(lo * r);
+}
+
+// the cell of a point INSIDE the box (the caller has compared it with the box)
+CELL_HD inline int cell_index(int x, int y, int x_min, int y_min, int side, int ncx) { return ((y - y_min) / side) * ncx + (x - x_min) / side; }
+
+// ---- the class of a label among C classes: itself, or C for a label outside 0 .. C - 1 (counted in no row and no column)
+CELL_HD inline int cs_class(int label, int C) { return (unsigned)label < (unsigned)C ? label : C; }
+
+// the counting-sort key: `sub` keys per cell.  sub == 1: the cell alone; sub == C + 1: (cell, class)
+CELL_HD inline int cell_key(int cell, int label, int sub) { return sub == 1 ? cell : cell * sub + cs_class(label, sub - 1); }
+
+// ---- the squared distance of a pair, dx = x_j - x_i and dy = y_j - y_i, or -1 when the pair is out of reach (reach2 = reach * reach;
+// the reach is inclusive).  Why nothing overflows, stated here once: |p| < 2^27 makes |dx|, |dy| < 2^28, so the differences are exact
+// int32; the box test against the reach comes BEFORE the products, so they are taken only of |dx|, |dy| <= reach <= 16384 = 2^14, and
+// d2 <= 2 * 2^28 = 2^29 < 2^31.
+CELL_HD inline int cell_pair_d2(int dx, int dy, int reach, int reach2) {
+  if (dx > reach || dx < -reach || dy > reach || dy < -reach) return -1;
+  const int d2 = dx * dx + dy * dy;
+  return d2 > reach2 ? -1 : d2;
+}
+
+// ---- the front checks of an entry point, before anything is launched: the limits every analysis shares (its own n limit passed in),
+// and, when there are points, the bounding box
+inline bool cell_box_ok(int x_min, int y_min, int x_max, int y_max) {
+  return x_min <= x_max && y_min <= y_max && x_min > -CELL_COORD_LIMIT && y_min > -CELL_COORD_LIMIT && x_max < CELL_COORD_LIMIT && y_max < CELL_COORD_LIMIT;
+}
+inline bool cell_call_ok(int64_t n, int64_t max_n, int C, int reach, int x_min, int y_min, int x_max, int y_max) {
+  if (n < 0 || n > max_n || C < 1 || C > CELL_MAX_CLASSES || reach < 1 || reach > CELL_MAX_REACH) return false;
+  return n == 0 || cell_box_ok(x_min, y_min, x_max, y_max);
+}

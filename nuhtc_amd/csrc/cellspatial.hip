@@ -9,16 +9,16 @@
 // the arrival order of any atomic and is bitwise the same on every call.
 //
 // Stages, all on the caller's stream:
-//   geometry   on the HOST from the caller's bounding box (cell_grid_side of cellspatial_host.h): the cell side is the smallest multiple of
+//   geometry   on the HOST from the caller's bounding box (cell_grid_side of cellgrid_host.h): the cell side is the smallest multiple of
 //              e_B whose grid has at most 2^18 cells -- 2^18 and not the graph's 2^22, because every cell has C + 1 keys.
-//   binning    cellbin.h, the one copy shared with cellgraph.hip, on the key cell * (C + 1) + class (class C: a label out of range): the
+//   binning    cellbin.h on the key cell * (C + 1) + class (class C: a label out of range): the
 //              records come out sorted by (cell, class).
 //   search     one thread per record in that order, 256 per workgroup, a grid-stride loop over the blocks of 256 records.  The class loop
 //              is OUTSIDE the cell loop: for each candidate class b a thread walks the (at most nine) runs of class-b records of its
 //              3 x 3 cells -- nine contiguous ranges, the same or neighbouring ones across the wave, one 16-byte load per record.  That
 //              differs from the shape the issue sketched (a flush at the end of every run): a thread flushes once per class instead of
 //              once per (cell, class) run, nine times fewer adds into the shared table, for 18 reads of the start table per class.
-//              Per pair: the box test against e_B (so no product can overflow: d2 <= 2 * 16384^2 = 2^29), d2, cs_bin_of (five exact
+//              Per pair: cell_pair_d2 of cellgrid_host.h (the box test against e_B, then d2 <= 2^29), cs_bin_of (five exact
 //              integer compares against the table of e_t^2 <= 2^28 in LDS), one add to the thread's PRIVATE counter of that bin, and the
 //              running minimum in a register.  The private counters are LDS, slot-major (counter t of thread tid at word t * 256 + tid):
 //              no atomics and no bank conflicts.  At the end of a class the thread writes nn_d2[i][b]; then the workgroup meets at a
@@ -36,18 +36,19 @@
 // (<= n^2 <= 2^56).  Record positions and the start table are int32 and n <= 2^28.  So the accepted n stays 2^28 and no early flush is
 // needed.
 //
-// Resources (hipcc -Rpass-analysis=kernel-resource-usage): cs_search_kernel takes 29 VGPRs, 77 SGPRs and no scratch; cs_zero_kernel 6 and 14;
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage): cs_search_kernel takes 30 VGPRs, 78 SGPRs and no scratch; cs_zero_kernel 6 and 14;
 // the binning kernels at most 31 and 26, none with scratch (profiles/cell_spatial_resources.txt).  LDS per workgroup is dynamic,
 // cs_lds_bytes(C, B) = 8 C^2 B + 1024 B + 1216 bytes: 40,384 B at the tool's C = 5, B = 32 (3 workgroups = 12 waves per CU), 84,160 B at
 // C = 14, B = 32 (1 workgroup).
 //
-// Everything that decides an index or a limit -- the grid geometry, the (cell, class) key, the bin lookup, the LDS carve and the rotated
-// column -- is plain C++ in cellspatial_host.h, and tools/dev/cellspatial_host_check.cpp runs exactly those functions on the host under
+// Everything that decides an index or a limit -- the grid geometry, the (cell, class) key and the pair distance (cellgrid_host.h), the bin
+// lookup, the LDS carve and the rotated column (cellspatial_host.h) -- is plain C++, and tools/dev/cellspatial_host_check.cpp runs exactly those functions on the host under
 // -fsanitize=address,undefined against counts over all pairs of small point sets.  The kernel code itself is not sanitized.
 #include <algorithm>
 #include <cstring>
 
 #include "cellbin.h"
+#include "cellspatial_host.h"
 
 namespace {
 
@@ -68,7 +69,7 @@ __global__ __launch_bounds__(256) void cs_zero_kernel(CellSpatialArgs a) {
   if (i < a.C) a.class_n[i] = 0;
 }
 
-// as compiled: 29 VGPRs, 77 SGPRs, no scratch, no static LDS (the dynamic carve above); registers allow 8 waves per SIMD, so LDS sets the occupancy
+// as compiled: 30 VGPRs, 78 SGPRs, no scratch, no static LDS (the dynamic carve above); registers allow 8 waves per SIMD, so LDS sets the occupancy
 __global__ __launch_bounds__(CS_NT) void cs_search_kernel(CellSpatialArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char cs_lds[];
   const CellBin& g = a.b;
@@ -104,10 +105,8 @@ __global__ __launch_bounds__(CS_NT) void cs_search_kernel(CellSpatialArgs a) {
           const int j0 = g.cell_start[key], j1 = g.cell_start[key + 1];
           for (int j = j0; j < j1; ++j) {
             const int4 o = g.recs[j];
-            const int dx = o.x - me.x, dy = o.y - me.y;  // |p| < 2^27: no overflow
-            if (o.w == me.w || dx > reach || dx < -reach || dy > reach || dy < -reach) continue;
-            const int dd = dx * dx + dy * dy;            // <= 2 * 16384^2 = 2^29
-            if (dd > reach2) continue;
+            const int dd = cell_pair_d2(o.x - me.x, o.y - me.y, reach, reach2);
+            if (dd < 0 || o.w == me.w) continue;
             best = min(best, dd);
             priv[cs_priv_at(cs_bin_of(e2, dd), tid)] += 1;
           }
@@ -143,8 +142,9 @@ extern "C" int nuhtc_cell_spatial(int device, const int32_t* points, const int32
                                   void* stream) {
   CellSpatialArgs a;
   memset(&a, 0, sizeof(a));
-  if (!cs_args_ok(n, num_classes, edges, num_bins, a.e2) || !pair_hist || !class_n) return NUHTC_E_INVALID;
-  if (n > 0 && (!points || !labels || !nn_d2 || !cell_box_ok(x_min, y_min, x_max, y_max))) return NUHTC_E_INVALID;
+  if (!cs_edges_ok(edges, num_bins, a.e2) || !cell_call_ok(n, CELL_MAX_POINTS, num_classes, edges[num_bins - 1], x_min, y_min, x_max, y_max))
+    return NUHTC_E_INVALID;
+  if (!pair_hist || !class_n || (n > 0 && (!points || !labels || !nn_d2))) return NUHTC_E_INVALID;
   if (hipSetDevice(device) != hipSuccess) return NUHTC_E_HIP;
   hipStream_t s = (hipStream_t)stream;
   const int C = num_classes, B = num_bins;
@@ -170,8 +170,5 @@ extern "C" int nuhtc_cell_spatial(int device, const int32_t* points, const int32
     ProfScope ps("cell_spatial_search", 0, 0, s);
     hipLaunchKernelGGL(cs_search_kernel, dim3(std::min(a.nblk, 2048)), dim3(CS_NT), lds, s, a);
   }
-  int h_flag = 0;
-  if (!launched() || hipMemcpyAsync(&h_flag, a.b.flag, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-    return NUHTC_E_HIP;
-  return h_flag ? NUHTC_E_INVALID : 0;
+  return cellbin_finish(a.b, s);
 }

@@ -36,9 +36,10 @@ the intensity class_n[b] / area is what the counts are compared with, and this m
 one -- the inferred tiles' area, the number of tiles x step_size ** 2 -- and labels K and L as resting on it."""
 import numpy as np
 
-from .cellgraph import COORD_LIMIT
+from . import cellpoints
+from .cellpoints import COORD_LIMIT, MAX_CLASSES, distances_px  # noqa: F401 (re-exported)
 
-MAX_BINS, MAX_EDGE, MAX_CLASSES = 32, 16384, 14
+MAX_BINS, MAX_EDGE = 32, cellpoints.MAX_R
 MAX_CELLS = 1 << 18
 
 NPZ_KEYS = ('nuclei_id', 'xy', 'label', 'edges_px', 'pair_hist', 'nn_dist', 'class_n', 'nn_d2', 'mean_within', 'G', 'tiles_area_px',
@@ -74,38 +75,25 @@ def edges_from_step(step_px, bins):
 
 def cell_side(x_min, y_min, x_max, y_max, reach):
     """The grid cell side the device uses over the inclusive bounding box: the smallest multiple of e_B with at most 2**18 cells."""
-    m = 1
-    while ((int(x_max) - int(x_min)) // (m * reach) + 1) * ((int(y_max) - int(y_min)) // (m * reach) + 1) > MAX_CELLS:
-        m += 1
-    return m * reach
+    return cellpoints.cell_side(x_min, y_min, x_max, y_max, reach, MAX_CELLS)
 
 
 def spatial_reference(points, labels, num_classes, edges):
     """The definition, pair by pair in int64: points int (n, 2) half pixels, labels int (n,), edges in HALF pixels ->
     (pair_hist int64 (C, C, B), nn_d2 int32 (n, C), class_n int64 (C,)).  O(n^2) time, rows in blocks of 512: for n of a few thousand."""
     e = check_args(num_classes, edges).astype(np.int64)
-    p = np.asarray(points, np.int64).reshape(-1, 2)
-    lab = np.asarray(labels, np.int64).reshape(-1)
+    p, lab = cellpoints.reference_points(points, labels, 'spatial_reference')
     n, C, B = len(p), int(num_classes), len(e)
-    if len(lab) != n:
-        raise ValueError('spatial_reference: one label per point')
-    if n and np.abs(p).max() >= COORD_LIMIT:
-        raise ValueError('spatial_reference: a coordinate lies outside |p| < 2**27')
     e2 = e * e
     known = (lab >= 0) & (lab < C)
     cls = np.where(known, lab, 0)
     pair_hist = np.zeros(C * C * B, np.int64)
     nn_d2 = np.full((n, C), -1, np.int32)
     class_n = np.bincount(lab[known], minlength=C).astype(np.int64)
-    idx = np.arange(n, dtype=np.int64)
     none = np.iinfo(np.int64).max
-    for i0 in range(0, n, 512):
-        rows = idx[i0:i0 + 512]
-        dx = p[rows, None, 0] - p[None, :, 0]
-        dy = p[rows, None, 1] - p[None, :, 1]
-        d2 = dx * dx + dy * dy
+    for rows, d2 in cellpoints.pair_blocks(p, 512):
         within = d2 <= e2[-1]
-        within[rows - i0, rows] = False                                      # j != i (a coincident OTHER point stays)
+        within[rows - rows[0], rows] = False                                 # j != i (a coincident OTHER point stays)
         t = np.searchsorted(e2, d2, side='left')                             # the smallest t with d2 <= e2[t]
         counted = within & known[rows, None] & known[None, :]
         flat = (cls[rows, None] * C + cls[None, :]) * B + t
@@ -119,52 +107,27 @@ def spatial_reference(points, labels, num_classes, edges):
 def call(points, labels, num_classes, edges, pair_hist, nn_d2, class_n, bounds=None, device=0):
     """nuhtc_cell_spatial on torch tensors of cuda:`device` (points, labels, nn_d2 int32; pair_hist, class_n int64; contiguous) -> the
     library's return code, nothing raised: 0 or hip.E_INVALID / hip.E_HIP.  `edges` are HALF pixels and are read on the host (a sequence, an
-    array or a tensor).  bounds = (x_min, y_min, x_max, y_max) of the points, computed here on the host when not given."""
+    array or a tensor).  bounds = (x_min, y_min, x_max, y_max) of the points, computed on the host when not given."""
     import ctypes
-    import torch
-    from . import hip
-    lib = hip.load()
-    n = int(points.shape[0])
-    if bounds is None:
-        if n:
-            ph = points.cpu().numpy()
-            bounds = (int(ph[:, 0].min()), int(ph[:, 1].min()), int(ph[:, 0].max()), int(ph[:, 1].max()))
-        else:
-            bounds = (0, 0, 0, 0)
-    if isinstance(edges, torch.Tensor):
+    if hasattr(edges, 'cpu'):
         edges = edges.cpu().numpy()
     e = np.ascontiguousarray(np.asarray(edges).reshape(-1), np.int32)
     e_host = (ctypes.c_int32 * max(len(e), 1))(*e.tolist())
-    vp = lambda t: ctypes.c_void_p(t.data_ptr())
-    dev = torch.device('cuda', device)
-    with torch.cuda.device(dev):
-        return lib.nuhtc_cell_spatial(int(device), vp(points), vp(labels), n, int(num_classes), e_host, len(e), *(int(b) for b in bounds),
-                                      vp(pair_hist), vp(nn_d2), vp(class_n), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    return cellpoints.launch('nuhtc_cell_spatial', device, points, labels, (int(num_classes), e_host, len(e)), (pair_hist, nn_d2, class_n), bounds)
 
 
 def build(points, labels, num_classes, edges, device=0):
-    """The statistics of `points` (int (n, 2) half pixels, see cellgraph.quantize_centres) with `labels` (n,) on cuda:`device`: numpy in,
+    """The statistics of `points` (int (n, 2) half pixels, see cellpoints.quantize_centres) with `labels` (n,) on cuda:`device`: numpy in,
     (pair_hist int64 (C, C, B), nn_d2 int32 (n, C), class_n int64 (C,)) out.  There is no host route: without the library or a GPU this
     raises."""
     import torch
-    from . import hip
-    p = np.ascontiguousarray(np.asarray(points).reshape(-1, 2), np.int32)
-    if not np.array_equal(p, np.asarray(points).reshape(-1, 2)):
-        raise ValueError('spatial statistics: the points are not int32 half pixels')
-    lab = np.ascontiguousarray(np.asarray(labels).reshape(-1), np.int32)
+    p, lab = cellpoints.as_points(points, labels, 'spatial statistics')
     n, C = len(p), int(num_classes)
-    if len(lab) != n:
-        raise ValueError('spatial statistics: one label per point')
     e = check_args(C, edges)
-    dev = torch.device('cuda', device)
-    bounds = (int(p[:, 0].min()), int(p[:, 1].min()), int(p[:, 0].max()), int(p[:, 1].max())) if n else None
+    dev, p_d, lab_d, bounds = cellpoints.upload(p, lab, device)
     out = [torch.zeros((C, C, len(e)), dtype=torch.int64, device=dev), torch.full((n, C), -1, dtype=torch.int32, device=dev),
            torch.zeros((C,), dtype=torch.int64, device=dev)]
-    rc = call(torch.from_numpy(p).to(dev), torch.from_numpy(lab).to(dev), C, e, *out, bounds=bounds, device=device)
-    if rc == hip.E_INVALID:
-        raise ValueError('nuhtc_cell_spatial: invalid arguments (a coordinate outside |p| < 2**27?)')
-    if rc:
-        raise RuntimeError(f'nuhtc_cell_spatial failed ({rc})')
+    cellpoints.raise_for(call(p_d, lab_d, C, e, *out, bounds=bounds, device=device), 'nuhtc_cell_spatial')
     return tuple(t.cpu().numpy() for t in out)
 
 
@@ -202,12 +165,6 @@ def derive(pair_hist, nn_d2, labels, class_n, edges, area_px=None):
     return out
 
 
-def distances_px(nn_d2):
-    """nn_d2 int (n, C) half pixels^2 -> float32 (n, C): sqrt(d2) / 2 in pixels, computed in float64 and then cast; inf where d2 is -1."""
-    d2 = np.asarray(nn_d2, np.int64)
-    return np.where(d2 >= 0, np.sqrt(np.maximum(d2, 0).astype(np.float64)) / 2, np.inf).astype(np.float32)
-
-
 def write_npz(path, nuclei_id, xy, label, edges, pair_hist, nn_d2, class_n, tiles_area_px):
     """<id>_nuclei_spatial.npz, row i for the i-th row of <id>_nuclei_feat.npz:
       nuclei_id   int64 (n,)      the nucleus's position in <id>.geojson
@@ -219,20 +176,17 @@ def write_npz(path, nuclei_id, xy, label, edges, pair_hist, nn_d2, class_n, tile
       mean_within, G float64 (C, C, B): `derive`
       tiles_area_px float64 0-d: the area K and L rest on (the inferred tiles: tiles x step_size^2), and
       K_tiles_area, L_tiles_area float64 (C, C, B): `derive` with that area -- Ripley's K and L only as far as that area is the tissue's."""
-    nuclei_id = np.ascontiguousarray(nuclei_id, np.int64).reshape(-1)
-    n = len(nuclei_id)
-    xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
-    label = np.ascontiguousarray(label, np.int64).reshape(-1)
+    head = cellpoints.npz_header(nuclei_id, xy, label)
     pair_hist = np.ascontiguousarray(pair_hist, np.int64)
     class_n = np.ascontiguousarray(class_n, np.int64).reshape(-1)
     C = len(class_n)
     nn_d2 = np.ascontiguousarray(nn_d2, np.int32).reshape(-1, C)
     e = check_args(C, edges)
-    if not (len(xy) == len(label) == len(nn_d2) == n) or pair_hist.shape != (C, C, len(e)):
+    if len(nn_d2) != len(head['label']) or pair_hist.shape != (C, C, len(e)):
         raise ValueError('write_npz: one row per nucleus, pair_hist (C, C, B)')
-    d = derive(pair_hist, nn_d2, label, class_n, e, area_px=tiles_area_px)
+    d = derive(pair_hist, nn_d2, head['label'], class_n, e, area_px=tiles_area_px)
     with open(path, 'wb') as f:
-        np.savez(f, nuclei_id=nuclei_id, xy=xy, label=label, edges_px=e.astype(np.float64) / 2, pair_hist=pair_hist, nn_dist=distances_px(nn_d2),
+        np.savez(f, **head, edges_px=e.astype(np.float64) / 2, pair_hist=pair_hist, nn_dist=distances_px(nn_d2),
                  class_n=class_n, nn_d2=nn_d2, mean_within=d['mean_within'], G=d['G'], tiles_area_px=np.asarray(float(tiles_area_px), np.float64),
                  K_tiles_area=d['K'], L_tiles_area=d['L'])
     return path
@@ -240,5 +194,4 @@ def write_npz(path, nuclei_id, xy, label, edges, pair_hist, nn_d2, class_n, tile
 
 def read_npz(path):
     """-> dict of the arrays of a file write_npz wrote (NPZ_KEYS)."""
-    with np.load(path) as z:
-        return {key: z[key] for key in NPZ_KEYS}
+    return cellpoints.read_npz(path, NPZ_KEYS)

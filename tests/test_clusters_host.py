@@ -153,6 +153,18 @@ def test_min_pts_one_is_connected_components_against_scipy(seed):
     assert np.array_equal(size, np.bincount(c))
 
 
+def test_a_lattice_wider_than_the_radius_with_min_pts_one_is_one_cluster_per_row():
+    """The construction of tests/test_hip_cellpoints.py (the root numbering across scan chunks) at n = 40: spacing 3 r, rows shuffled."""
+    n, r = 40, 8
+    at = np.arange(n)
+    p = (np.stack([at % 7, at // 7], 1) * 3 * r - 1000)[np.random.default_rng(5).permutation(n)]
+    lab = np.arange(n) % 3
+    cluster, core, degree, size, n_core, class_count, sum_xy, bbox = cl.cluster_reference(p, lab, 3, r, 1, 0)
+    assert len(size) == n and np.array_equal(cluster, np.arange(n)) and core.all() and (degree == 1).all()
+    assert (size == 1).all() and (n_core == 1).all() and np.array_equal(class_count, np.eye(3, dtype=np.int32)[lab])
+    assert np.array_equal(sum_xy, p) and np.array_equal(bbox, np.concatenate([p, p], 1))
+
+
 def test_derive_against_numpy_on_a_small_table():
     p, lab, C = np.array([[0, 0], [6, 8], [3, 3], [100, 0], [300, 1], [301, 4], [299, 0]]), np.array([0, 1, 1, 2, 5, 1, 1]), 4
     out = cl.cluster_reference(p, lab, C, 10, 2, 0)

@@ -39,6 +39,7 @@ def main(argv=None):
     import torch
     from scipy.spatial import cKDTree
     from nuhtc_amd import cellgraph as cg
+    from nuhtc_amd import cellpoints
     from nuhtc_amd import hip
     if not torch.cuda.is_available():
         raise SystemExit('bench_cellgraph.py needs a GPU (there is no fallback)')
@@ -48,7 +49,7 @@ def main(argv=None):
     pts = rng.integers(0, 2 * args.extent, (n, 2)).astype(np.int32)
     lab = rng.integers(0, C, n).astype(np.int32)
     dev = torch.device('cuda', 0)
-    bounds = (int(pts[:, 0].min()), int(pts[:, 1].min()), int(pts[:, 0].max()), int(pts[:, 1].max()))
+    bounds = cellpoints.bounds_of(pts)
     p_d, l_d = torch.from_numpy(pts).to(dev), torch.from_numpy(lab).to(dev)
     out = [torch.full((n, w), -1, dtype=torch.int32, device=dev) for w in (k, k, C)]
     ms = []

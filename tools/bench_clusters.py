@@ -31,11 +31,12 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 def measure(name, pts, lab, C, r, args):
     import torch
     from nuhtc_amd import cellgraph as cg
+    from nuhtc_amd import cellpoints
     from nuhtc_amd import clusters as cl
     from nuhtc_amd import hip
     n, by = len(pts), cl.BY[args.by]
     dev = torch.device('cuda', 0)
-    bounds = (int(pts[:, 0].min()), int(pts[:, 1].min()), int(pts[:, 0].max()), int(pts[:, 1].max()))
+    bounds = cellpoints.bounds_of(pts)
     p_d, l_d = torch.from_numpy(pts).to(dev), torch.from_numpy(lab).to(dev)
     out = cl.outputs(n, C, dev)
     gout = [torch.full((n, w), -1, dtype=torch.int32, device=dev) for w in (8, 8, C)]

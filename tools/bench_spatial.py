@@ -44,11 +44,12 @@ def measure(name, pts, lab, C, edges, args):
     import torch
     from scipy.spatial import cKDTree
     from nuhtc_amd import cellgraph as cg
+    from nuhtc_amd import cellpoints
     from nuhtc_amd import hip
     from nuhtc_amd import spatial as sp
     n, B = len(pts), len(edges)
     dev = torch.device('cuda', 0)
-    bounds = (int(pts[:, 0].min()), int(pts[:, 1].min()), int(pts[:, 0].max()), int(pts[:, 1].max()))
+    bounds = cellpoints.bounds_of(pts)
     p_d, l_d = torch.from_numpy(pts).to(dev), torch.from_numpy(lab).to(dev)
     out = [torch.zeros((C, C, B), dtype=torch.int64, device=dev), torch.full((n, C), -1, dtype=torch.int32, device=dev),
            torch.zeros((C,), dtype=torch.int64, device=dev)]

@@ -1,6 +1,6 @@
-// Host check of the plain-C++ parts of the pair-histogram kernels (nuhtc_amd/csrc/cellspatial_host.h: the grid geometry, the (cell, class)
-// key, the bin lookup, the LDS carve and the rotated column of the row sums, the limits of the entry point), meant to be built with a
-// sanitizer and run on the host -- it never touches a GPU, and the kernel code itself (cellspatial.hip, cellbin.h) is NOT sanitized:
+// Host check of the plain-C++ parts of the per-slide point kernels (nuhtc_amd/csrc/cellgrid_host.h: the grid geometry, the (cell, class)
+// key, the pair distance within reach, the front checks of the entry points; cellspatial_host.h: the bin lookup, the LDS carve and the
+// rotated column of the row sums, the check of the bin edges), meant to be built with a sanitizer and run on the host -- it never touches a GPU, and the kernel code itself (cellspatial.hip, cellbin.h) is NOT sanitized:
 //
 //   hipcc -x hip --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
 //         -I nuhtc_amd/csrc tools/dev/cellspatial_host_check.cpp -o /tmp/cellspatial_host_check && /tmp/cellspatial_host_check
@@ -8,7 +8,7 @@
 // Small point sets are taken the way the kernels take them: the grid from cell_grid_side, a counting sort on cell_key into a start table
 // of exactly keys + 1 entries, then for every record, class by class, the runs of its 3 x 3 cells, the bin from cs_bin_of, the private
 // counter at cs_priv_at inside a heap block of exactly cs_lds_bytes(C, B) bytes carved by the cs_lds_*_off functions, the row sums over
-// cs_rotated_column into the table at cs_table_at -- so an index past a table, a run or the carve is reported -- and compared with plain
+// cs_rotated_column into the table at cs_table_at, every pair through cell_pair_d2 -- so an index past a table, a run or the carve is reported -- and compared with plain
 // counts over all pairs.
 #include <cstdio>
 #include <cstdlib>
@@ -20,6 +20,11 @@
 #include "cellspatial_host.h"
 
 struct Result { std::vector<long long> hist; std::vector<int> nn; std::vector<long long> cn; };
+
+// the front of nuhtc_cell_spatial: the edges, then the shared limits with e_B as the reach (no points: no box)
+static bool cs_args_ok(int64_t n, int C, const int* edges, int B, int e2[CS_MAX_BINS]) {
+  return cs_edges_ok(edges, B, e2) && cell_call_ok(n, CELL_MAX_POINTS, C, edges[B - 1], 0, 0, 0, 0);
+}
 
 static Result plain_way(const std::vector<int>& p, const std::vector<int>& lab, int C, const std::vector<int>& e) {
   const int n = (int)lab.size(), B = (int)e.size();
@@ -96,10 +101,8 @@ static Result kernel_way(const std::vector<int>& p, const std::vector<int>& lab,
           for (int gx = std::max(cx - 1, 0); gx <= std::min(cx + 1, ncx - 1); ++gx) {
             const int key = cell_key(gy * ncx + gx, b, sub);
             for (int j = start[key]; j < start[key + 1]; ++j) {
-              const int dx = recs[4 * j] - mx, dy = recs[4 * j + 1] - my;
-              if (recs[4 * j + 3] == mi || dx > reach || dx < -reach || dy > reach || dy < -reach) continue;
-              const int dd = dx * dx + dy * dy;
-              if (dd > reach2) continue;
+              const int dd = cell_pair_d2(recs[4 * j] - mx, recs[4 * j + 1] - my, reach, reach2);
+              if (dd < 0 || recs[4 * j + 3] == mi) continue;
               best = std::min(best, dd);
               priv[cs_priv_at(cs_bin_of(e2l, dd), tid)] += 1;
             }
@@ -154,6 +157,25 @@ int main() {
     const int L = CELL_COORD_LIMIT;
     if (!cell_box_ok(-L + 1, -L + 1, L - 1, L - 1) || cell_box_ok(-L, 0, 0, 0) || cell_box_ok(0, 0, L, 0) || cell_box_ok(0, 0, 0, L) || cell_box_ok(0, -L, 0, 0) ||
         cell_box_ok(1, 0, 0, 0) || cell_box_ok(0, 1, 0, 0)) { std::printf("FAIL box limits\n"); ++bad; }
+  }
+  // ---- the pair distance at the limits, against 64-bit arithmetic: differences up to 2^28 - 1, the reach at both ends of its range
+  for (int reach : {1, CELL_MAX_REACH}) {
+    const int big = (1 << 28) - 1, at[] = {0, 1, reach - 1, reach, reach + 1, big};
+    for (int ax : at) for (int ay : at) for (int sx : {-1, 1}) for (int sy : {-1, 1}) {
+      const int dx = sx * ax, dy = sy * ay;
+      const long long d2 = (long long)dx * dx + (long long)dy * dy, want = d2 <= (long long)reach * reach ? d2 : -1;
+      if (cell_pair_d2(dx, dy, reach, reach * reach) != want) { std::printf("FAIL pair d2 dx %d dy %d reach %d\n", dx, dy, reach); ++bad; }
+    }
+  }
+  // ---- the front checks the entry points share
+  {
+    const int L = CELL_COORD_LIMIT;
+    struct { int64_t n, max_n; int C, reach, x0, y0, x1, y1; bool ok; } call[] = {
+        {0, 1 << 24, 1, 1, 5, 5, 0, 0, true}, {1, 1 << 24, 14, 16384, -L + 1, -L + 1, L - 1, L - 1, true}, {1, 1 << 24, 1, 1, 5, 5, 0, 0, false},
+        {(1 << 24) + 1, 1 << 24, 1, 1, 0, 0, 0, 0, false}, {-1, 1 << 24, 1, 1, 0, 0, 0, 0, false}, {1, 1, 0, 1, 0, 0, 0, 0, false},
+        {1, 1, 15, 1, 0, 0, 0, 0, false}, {1, 1, 1, 0, 0, 0, 0, 0, false}, {1, 1, 1, 16385, 0, 0, 0, 0, false}, {1, 1, 1, 1, -L, 0, 0, 0, false}};
+    for (const auto& c : call)
+      if (cell_call_ok(c.n, c.max_n, c.C, c.reach, c.x0, c.y0, c.x1, c.y1) != c.ok) { std::printf("FAIL call limits n %lld C %d reach %d\n", (long long)c.n, c.C, c.reach); ++bad; }
   }
   // ---- the LDS carve: aligned, in order, nothing overlaps, the last index of every part inside the block, within a CU's 160 KiB
   for (int C = 1; C <= CS_MAX_CLASSES; ++C)

@@ -267,29 +267,28 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
         kind.write(os.path.join(out_dir, name + kind.suffix), rows, wsi.gathered_rows(kind, gathered, rows, part=rows_at + i),
                    hall[rows, 5].astype(np.int64), hall[rows, 4])
         msg += f', {len(rows)} {kind.said} in {name}{kind.suffix}'
-    if graph:                                                         # the edges to those rows: only what the gather already delivered
+    if graph or spatial_on or clusters_on:                            # one point set for the three: only what the gather already delivered
+        from nuhtc_amd import cellpoints
+        boxes, lab = hall[rows, :4], hall[rows, 5].astype(np.int64)
+        pts, xy = cellpoints.quantize_centres(boxes), cellpoints.centres(boxes)
+        on = local_rank if world > 1 else (torch.device(args.device).index or 0)
+    if graph:                                                         # the edges to those rows
         from nuhtc_amd import cellgraph
-        boxes, lab = hall[rows, :4], hall[rows, 5].astype(np.int64)
-        nb, d2, cc = cellgraph.build(cellgraph.quantize_centres(boxes), lab, len(model.CLASSES), args.graph_radius, args.graph_k,
-                                     device=local_rank if world > 1 else (torch.device(args.device).index or 0))
-        cellgraph.write_npz(os.path.join(out_dir, name + '_nuclei_graph.npz'), rows, cellgraph.centres(boxes), nb, d2, cc, lab, args.graph_radius, args.graph_k)
+        nb, d2, cc = cellgraph.build(pts, lab, len(model.CLASSES), args.graph_radius, args.graph_k, device=on)
+        cellgraph.write_npz(os.path.join(out_dir, name + '_nuclei_graph.npz'), rows, xy, nb, d2, cc, lab, args.graph_radius, args.graph_k)
         msg += f', {int((nb >= 0).sum())} edges (k {args.graph_k}, {args.graph_radius:g} px) in {name}_nuclei_graph.npz'
-    if spatial_on:                                                    # pair counts over the same rows, from the same gathered boxes
-        from nuhtc_amd import cellgraph, spatial
-        boxes, lab = hall[rows, :4], hall[rows, 5].astype(np.int64)
+    if spatial_on:                                                    # pair counts over the same rows
+        from nuhtc_amd import spatial
         edges = spatial.edges_from_step(args.spatial_step, args.spatial_bins)
-        ph, nn, cn = spatial.build(cellgraph.quantize_centres(boxes), lab, len(model.CLASSES), edges,
-                                   device=local_rank if world > 1 else (torch.device(args.device).index or 0))
-        spatial.write_npz(os.path.join(out_dir, name + '_nuclei_spatial.npz'), rows, cellgraph.centres(boxes), lab, edges, ph, nn, cn,
+        ph, nn, cn = spatial.build(pts, lab, len(model.CLASSES), edges, device=on)
+        spatial.write_npz(os.path.join(out_dir, name + '_nuclei_spatial.npz'), rows, xy, lab, edges, ph, nn, cn,
                           tiles_area_px=float(len(bag)) * float(args.step_size) ** 2)
         msg += f', {int(ph.sum())} ordered pairs within {edges[-1] / 2:g} px ({len(edges)} bins) in {name}_nuclei_spatial.npz'
     if clusters_on:                                                   # which of the same rows belong together
         from nuhtc_amd import clusters
-        boxes, lab = hall[rows, :4], hall[rows, 5].astype(np.int64)
         by = clusters.BY[args.cluster_by]
-        found = clusters.build(clusters.quantize_centres(boxes), lab, len(model.CLASSES), args.cluster_radius, args.cluster_min, by,
-                               device=local_rank if world > 1 else (torch.device(args.device).index or 0))
-        clusters.write_npz(os.path.join(out_dir, name + '_nuclei_clusters.npz'), rows, clusters.centres(boxes), lab, *found,
+        found = clusters.build(pts, lab, len(model.CLASSES), args.cluster_radius, args.cluster_min, by, device=on)
+        clusters.write_npz(os.path.join(out_dir, name + '_nuclei_clusters.npz'), rows, xy, lab, *found,
                            radius_px=args.cluster_radius, min_pts=args.cluster_min, by_class=by)
         msg += (f', {len(found[3])} clusters and {int((found[0] < 0).sum())} isolated nuclei ({args.cluster_radius:g} px, {args.cluster_min} nuclei, '
                 f'by {args.cluster_by}) in {name}_nuclei_clusters.npz')
