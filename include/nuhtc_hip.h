@@ -982,6 +982,34 @@ int nuhtc_cell_clusters(int device, const int32_t* points, const int32_t* labels
                         int x_min, int y_min, int x_max, int y_max, int32_t* cluster, uint8_t* core, int32_t* degree, int32_t* size,
                         int32_t* n_core, int32_t* class_count, int64_t* sum_xy, int32_t* bbox, int64_t* m, void* stream);
 
+/* Minimum spanning forest of a slide's nuclei (csrc/cellmst.hip; nuhtc_amd/mst.py holds the definition and the brute-force restatement
+ * `mst_reference`): the minimum spanning tree descriptors of a tissue section, and the single-linkage dendrogram of the slide up to the
+ * radius.  Not in the reference.  Engine-free like the clusters' call: points, labels and the three outputs are device memory of `device`,
+ * the call allocates and frees its own scratch, runs on `stream` and synchronises it (once per Boruvka round and once at the end) before
+ * returning.  nuhtc_config is unchanged (no ABI bump).
+ *   points [n][2] int32: node positions in HALF pixels (as for the cell graph), |p| < 2^27.  labels [n] int32.  0 <= n <= 2^24: a row takes
+ *     24 bits of the 64-bit pick key, and the edge order scans one count per point in at most 1024 chunks of 16384.
+ *   num_classes C: 1 .. 14 (checked; the labels are only compared with each other).  r: the radius in half pixels, 1 .. 16384.
+ *   by_class: 0 or 1.  x_min, y_min, x_max, y_max: the bounding box of the points (inclusive), computed by the caller on the host (cell
+ *     side = the smallest multiple of r whose grid over the box has at most 2^22 cells; ignored when n == 0).
+ * All arithmetic is integer.  An EDGE is an unordered pair i < j with dx * dx + dy * dy <= r * r (inclusive; coincident points are joined
+ * with d2 = 0) and, with by_class, labels[i] == labels[j] (plain equality, also for labels outside [0, C)).  Edges are ordered by the key
+ * (d2, i, j), lexicographically: a strict total order, so the minimum spanning forest of the edge set is unique -- what Kruskal's
+ * algorithm returns on the edges in ascending key order.  That forest is the result.
+ *   edges [n][2] int32 and edge_d2 [n] int32 (n rows of capacity, the first m written and the rest untouched): the forest's edges (i, j),
+ *     i < j, in ascending (i, j) order, and their squared lengths in half pixels.
+ *   tree [n] int32: the tree of every point, numbered 0 .. T - 1 by ascending smallest row; an isolated point is a tree of size 1.
+ *   m, trees, rounds: HOST memory, written on success only: the edges (m = n - T), T, and the Boruvka rounds that added an edge.
+ * The result is a pure function of the input: bitwise the same on every call.  n == 0 sets m = trees = rounds = 0, launches nothing and
+ * returns NUHTC_OK.
+ * NUHTC_E_INVALID, before anything is launched and with the outputs untouched: n, num_classes, r or by_class out of range, a null pointer
+ * (m, trees, rounds always, the others with n > 0), a bounding box that is empty or reaches +-2^27 (so: any coordinate out of range).
+ * NUHTC_E_INVALID after the binning, the outputs still untouched: a point lies outside the stated bounding box.
+ * NUHTC_E_HIP: a HIP call failed, or round 25 still added edges (impossible for n <= 2^24: every round halves the components). */
+int nuhtc_cell_mst(int device, const int32_t* points, const int32_t* labels, int64_t n, int num_classes, int r, int by_class,
+                   int x_min, int y_min, int x_max, int y_max, int32_t* edges, int32_t* edge_d2, int32_t* tree,
+                   int64_t* m, int64_t* trees, int64_t* rounds, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the launch stream (process-wide switch; off by default).
  * nuhtc_profile_read synchronises the device and writes one text line per kernel tag,
  * "tag launches total_ms algorithmic_flops algorithmic_bytes", then resets the records. */

@@ -53,6 +53,7 @@
 #include <cstring>
 
 #include "cellbin.h"
+#include "cellunion.h"
 
 namespace {
 
@@ -100,31 +101,7 @@ __global__ __launch_bounds__(CC_NT) void cc_degree_kernel(CellClusterArgs a) {
   a.parent[me.w] = core ? me.w : -1;
 }
 
-__device__ __forceinline__ int cc_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root above core row x as far as this thread can see it, halving the path on the way; every step goes to a smaller row
-__device__ __forceinline__ int cc_find(int* parent, int x) {
-  int p = cc_load(parent + x);
-  while (p != x) {
-    const int gp = cc_load(parent + p);
-    if (gp != p) atomicMin(parent + x, gp);
-    x = p;
-    p = gp;
-  }
-  return x;
-}
-
-// one tree for the components of core rows a and b.  max(hi, lo) falls with every failed CAS: the loop ends whatever other threads do
-__device__ __forceinline__ void cc_unite(int* parent, int a, int b) {
-  int hi = cc_find(parent, a), lo = cc_find(parent, b);
-  while (hi != lo) {
-    if (hi < lo) { const int t = hi; hi = lo; lo = t; }
-    const int old = atomicCAS(parent + hi, hi, lo);
-    if (old == hi) return;
-    hi = cc_find(parent, old);                           // hi was linked meanwhile: old (< hi) is its parent
-    lo = cc_find(parent, lo);
-  }
-}
+// cc_load, cc_find, cc_unite and cc_root: cellunion.h, shared with cellmst.hip
 
 __global__ __launch_bounds__(CC_NT) void cc_hook_kernel(CellClusterArgs a) {
   const CellBin& g = a.b;
@@ -136,12 +113,6 @@ __global__ __launch_bounds__(CC_NT) void cc_hook_kernel(CellClusterArgs a) {
   cc_sweep(g, me, a.r, a.by_class, [&](int j, const int4& o, int) {
     if (o.w < me.w && a.rdeg[j] >= min_pts) cc_unite(a.parent, me.w, o.w);
   });
-}
-
-// the root of core row x once the hooking is complete
-__device__ __forceinline__ int cc_root(const int* __restrict__ parent, int x) {
-  for (int p = parent[x]; p != x; p = parent[x]) x = p;
-  return x;
 }
 
 __global__ __launch_bounds__(CC_NT) void cc_resolve_kernel(CellClusterArgs a) {

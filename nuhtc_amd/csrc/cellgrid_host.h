@@ -1,7 +1,8 @@
-// The uniform grid over half-pixel points that the per-slide analyses share (cellbin.h; cellgraph.hip, cellspatial.hip, cellcluster.hip):
-// the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell and the
-// (cell, class) key of a point, and the squared distance of a pair within reach.  Header-only, so a host program can exercise them under a
-// sanitizer (tools/dev/cellspatial_host_check.cpp); the kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
+// The uniform grid over half-pixel points that the per-slide analyses share (cellbin.h; cellgraph.hip, cellspatial.hip, cellcluster.hip,
+// cellmst.hip): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
+// and the (cell, class) key of a point, the squared distance of a pair within reach, and the edge key of the spanning forest.  Header-only,
+// so a host program can exercise them under a sanitizer (tools/dev/cellspatial_host_check.cpp, tools/dev/cellmst_host_check.cpp); the
+// kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
 #pragma once
 #include <cstdint>
 
@@ -48,6 +49,21 @@ CELL_HD inline int cell_pair_d2(int dx, int dy, int reach, int reach2) {
   const int d2 = dx * dx + dy * dy;
   return d2 > reach2 ? -1 : d2;
 }
+
+// ---- the edge key of the minimum spanning forest (cellmst.hip): edges are ordered by (d2, lo, hi) with lo < hi the two rows.  The bit
+// budget, stated here once: an edge has d2 <= reach^2 <= 16384^2 = 2^28, which takes 29 bits (0 .. 2^28 inclusive), and rows are
+// < 2^24 (MST_MAX_POINTS), 24 bits each: 29 + 24 + 24 = 77 bits, more than one 64-bit atomic holds.  The front (d2, lo) is 53 bits and
+// fits: mst_key packs it so that the unsigned order of the packed words IS the lexicographic order of (d2, lo); hi is compared apart.
+// MST_NO_KEY, all ones, is above every key (a key is < 2^53).
+constexpr int MST_ROW_BITS = 24;
+constexpr int64_t MST_MAX_POINTS = (int64_t)1 << MST_ROW_BITS;
+constexpr int MST_MAX_D2 = CELL_MAX_REACH * CELL_MAX_REACH;        // 2^28
+constexpr unsigned long long MST_NO_KEY = ~0ull;
+CELL_HD inline unsigned long long mst_key(int d2, int lo) { return ((unsigned long long)(unsigned)d2 << MST_ROW_BITS) | (unsigned long long)(unsigned)lo; }
+CELL_HD inline int mst_key_d2(unsigned long long key) { return (int)(key >> MST_ROW_BITS); }
+CELL_HD inline int mst_key_lo(unsigned long long key) { return (int)(key & (((unsigned long long)1 << MST_ROW_BITS) - 1)); }
+// is the edge (key a, hi a) in front of the edge (key b, hi b)?  The strict total order of the definition
+CELL_HD inline bool mst_edge_less(unsigned long long ka, int ha, unsigned long long kb, int hb) { return ka < kb || (ka == kb && ha < hb); }
 
 // ---- the front checks of an entry point, before anything is launched: the limits every analysis shares (its own n limit passed in),
 // and, when there are points, the bounding box

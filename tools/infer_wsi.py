@@ -47,6 +47,14 @@ Output (like the reference, :659-693), for every detection that survives the per
                   `n_clusters`, `n_noise`, `class_clustered_share`.  A border nucleus joins the nearest core nucleus's cluster (ties: the
                   smaller row), so the file is a pure function of the rows.  Every other file is the same bytes with and without the flag.
                   There is no route without a GPU.
+  --nuclei-mst:   (not in the reference) <id>_nuclei_mst.npz beside the documents, for the same rows as --nuclei-graph: the minimum
+                  spanning forest of the nuclei over the edges of at most --mst-radius px (64 by default), over all nuclei or, with
+                  --mst-by class, among nuclei of one label -- built on rank 0's GPU after the gather (nuhtc_amd/mst.py): `edges` (rows of
+                  this file, i < j, ascending), `edge_d2` (half pixels squared), `tree` per nucleus, and the derived `edge_len_px`,
+                  `mst_degree`, `tree_size`, `tree_length_px`, `edge_class_count`, `n_trees`, `n_edges`, `length_mean_px`,
+                  `length_std_px`, `length_min_max_ratio`, `length_disorder`.  Ties are broken by (d2, i, j), so the file is a pure
+                  function of the rows; cutting the forest at any length t <= radius gives the components of the t-radius graph.  Every
+                  other file is the same bytes with and without the flag.  There is no route without a GPU.
   --nuclei-morph: (the reference's tools/wsi_feat_extract.py table, computed on the GPU) <id>_nuclei_morph.npz beside the documents, for the
                   same rows: `columns` and `values` float64 (n, F) -- size, shape, orientation, position and haematoxylin-intensity features
                   under histomicstk's names, derived on the host (nuhtc_amd/nucmorph.py derive) from the integers every rank's GPU measured
@@ -140,6 +148,13 @@ def build_parser():
                    help='nuclei within the radius, the nucleus itself counted, that make a core nucleus of --nuclei-clusters (default 5)')
     p.add_argument('--cluster-by', choices=('any', 'class'), default='any', dest='cluster_by',
                    help="--nuclei-clusters over all nuclei ('any') or only among nuclei of the same label ('class')")
+    p.add_argument('--nuclei-mst', action='store_true', dest='nuclei_mst',
+                   help='also write <id>_nuclei_mst.npz: the minimum spanning forest of the written nuclei (edges, their lengths, the tree of every '
+                        'nucleus and the edge-length statistics), built on the GPU (rows as in <id>_nuclei_feat.npz)')
+    p.add_argument('--mst-radius', type=float, default=64.0, dest='mst_radius',
+                   help='longest edge of --nuclei-mst in slide px, a multiple of 0.5 up to 8192 (default 64 px: 16 um at 40x)')
+    p.add_argument('--mst-by', choices=('any', 'class'), default='any', dest='mst_by',
+                   help="--nuclei-mst over all nuclei ('any') or only among nuclei of the same label ('class')")
     return p
 
 
@@ -260,14 +275,15 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
     graph = getattr(args, 'nuclei_graph', False)
     spatial_on = getattr(args, 'nuclei_spatial', False)
     clusters_on = getattr(args, 'nuclei_clusters', False)
-    if sel or graph or spatial_on or clusters_on:                                    # the rows of the per-nucleus files, and their labels and scores
+    mst_on = getattr(args, 'nuclei_mst', False)
+    if sel or graph or spatial_on or clusters_on or mst_on:                                    # the rows of the per-nucleus files, and their labels and scores
         hall = np.concatenate([h.cpu().numpy() for h in heads], 0).reshape(-1, 9)
         rows = np.arange(n_records, dtype=np.int64) if feat_rows is None else feat_rows
     for i, kind in enumerate(sel):
         kind.write(os.path.join(out_dir, name + kind.suffix), rows, wsi.gathered_rows(kind, gathered, rows, part=rows_at + i),
                    hall[rows, 5].astype(np.int64), hall[rows, 4])
         msg += f', {len(rows)} {kind.said} in {name}{kind.suffix}'
-    if graph or spatial_on or clusters_on:                            # one point set for the three: only what the gather already delivered
+    if graph or spatial_on or clusters_on or mst_on:                  # one point set for the four: only what the gather already delivered
         from nuhtc_amd import cellpoints
         boxes, lab = hall[rows, :4], hall[rows, 5].astype(np.int64)
         pts, xy = cellpoints.quantize_centres(boxes), cellpoints.centres(boxes)
@@ -292,6 +308,13 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
                            radius_px=args.cluster_radius, min_pts=args.cluster_min, by_class=by)
         msg += (f', {len(found[3])} clusters and {int((found[0] < 0).sum())} isolated nuclei ({args.cluster_radius:g} px, {args.cluster_min} nuclei, '
                 f'by {args.cluster_by}) in {name}_nuclei_clusters.npz')
+    if mst_on:                                                        # the shortest edges that hold the same rows together
+        from nuhtc_amd import mst
+        by = mst.BY[args.mst_by]
+        e, ed2, tree, n_e, n_t = mst.build(pts, lab, len(model.CLASSES), args.mst_radius, by, device=on)
+        mst.write_npz(os.path.join(out_dir, name + '_nuclei_mst.npz'), rows, xy, lab, e, ed2, tree, len(model.CLASSES),
+                      radius_px=args.mst_radius, by_class=by)
+        msg += f', {n_e} forest edges in {n_t} trees ({args.mst_radius:g} px, by {args.mst_by}) in {name}_nuclei_mst.npz'
     if want('dsa'):
         outputs.write_json(os.path.join(out_dir, name + '_dsa.json'), outputs.dsa_document(dsa))
     if want('coco'):
@@ -356,6 +379,14 @@ def main(argv=None):
             raise SystemExit(f'--nuclei-clusters: {e}')
         if not torch.cuda.is_available():
             raise SystemExit('--nuclei-clusters: no GPU is visible (there is no fallback)')
+    if args.nuclei_mst:
+        from nuhtc_amd import mst
+        try:
+            mst.check_args(1, mst.half_pixel_radius(args.mst_radius), mst.BY[args.mst_by])
+        except ValueError as e:
+            raise SystemExit(f'--nuclei-mst: {e}')
+        if not torch.cuda.is_available():
+            raise SystemExit('--nuclei-mst: no GPU is visible (there is no fallback)')
     # the process group is formed AFTER seg_and_patch: rank 0's host phase (segmentation, masks, patching, stitching of every slide of the
     # folder) has no time bound, and a rank waiting in an RCCL barrier is aborted by the watchdog after 10 minutes
     rank, local_rank, world = parallel.env_ranks()
