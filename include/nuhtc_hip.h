@@ -1010,6 +1010,36 @@ int nuhtc_cell_mst(int device, const int32_t* points, const int32_t* labels, int
                    int x_min, int y_min, int x_max, int y_max, int32_t* edges, int32_t* edge_d2, int32_t* tree,
                    int64_t* m, int64_t* trees, int64_t* rounds, void* stream);
 
+/* Proximity graphs of a slide's nuclei (csrc/cellprox.hip; nuhtc_amd/proximity.py holds the definition and the brute-force restatement
+ * `proximity_reference`): the Gabriel graph and the relative neighbourhood graph (RNG), the parameter-free "who touches whom" relations,
+ * both subgraphs of the Delaunay graph and both supergraphs of the minimum spanning forest at the same radius.  Not in the reference.
+ * Engine-free like the forest's call: points, labels and the four outputs are device memory of `device`, the call allocates and frees
+ * its own scratch, runs on `stream` and synchronises it (once after the count, once at the end) before returning.  nuhtc_config is
+ * unchanged (no ABI bump).
+ *   points [n][2] int32: node positions in HALF pixels, |p| < 2^27.  labels [n] int32.  0 <= n <= 2^24 (one count per point is scanned in
+ *     at most 1024 chunks of 16384).  num_classes C: 1 .. 14 (checked; the labels are only compared with each other).  r: the radius in
+ *     half pixels, 1 .. 16384.  by_class: 0 or 1.  edge_cap: the rows of capacity of the three edge arrays, 0 .. 2^31 - 1.
+ *   x_min, y_min, x_max, y_max: the bounding box of the points (inclusive), computed by the caller on the host (ignored when n == 0).
+ * All arithmetic is integer; write d2(a, b) for the squared distance.  A CANDIDATE is an unordered pair i < j with d2(i, j) <= r * r
+ * (inclusive) and, with by_class, labels[i] == labels[j] (plain equality, also for labels outside [0, C)).  A WITNESS is any other row k,
+ * with by_class of the same label.  The candidate is a GABRIEL edge when no witness has d2(i, k) + d2(j, k) < d2(i, j), and an RNG edge
+ * when no witness has max(d2(i, k), d2(j, k)) < d2(i, j): both strict, so a witness on the circle or at equal distance does not block,
+ * and coincident points are joined (d2 = 0, rng = 1).  Every RNG edge is a Gabriel edge.
+ *   edges [edge_cap][2] int32, edge_d2 [edge_cap] int32, edge_rng [edge_cap] uint8: the Gabriel edges (i, j), i < j, in ascending (i, j)
+ *     order, their squared lengths, and 1 where the edge is an RNG edge too.  Written ONLY when m <= edge_cap (the first m rows, the rest
+ *     untouched); with m > edge_cap the three arrays are untouched, the call still returns NUHTC_OK, and the caller calls again with
+ *     edge_cap = m.  m is not bounded by a multiple of n: k coincident points are a clique of k (k - 1) / 2 edges.
+ *   degree [n][2] int32: the Gabriel and the RNG edges at every row, always written.
+ *   m, m_rng: HOST memory, written on success only: the Gabriel edges and how many of them are RNG edges.
+ * The result is a pure function of the input: bitwise the same on every call.  n == 0 sets m = m_rng = 0, launches nothing and returns
+ * NUHTC_OK.
+ * NUHTC_E_INVALID, before anything is launched and with the outputs untouched: n, num_classes, r, by_class or edge_cap out of range, a
+ * null pointer (m, m_rng always, the others with n > 0), a bounding box that is empty or reaches +-2^27.
+ * NUHTC_E_INVALID after the binning, the outputs still untouched: a point lies outside the stated bounding box. */
+int nuhtc_cell_proximity(int device, const int32_t* points, const int32_t* labels, int64_t n, int num_classes, int r, int by_class,
+                         int64_t edge_cap, int x_min, int y_min, int x_max, int y_max, int32_t* edges, int32_t* edge_d2,
+                         uint8_t* edge_rng, int32_t* degree, int64_t* m, int64_t* m_rng, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the launch stream (process-wide switch; off by default).
  * nuhtc_profile_read synchronises the device and writes one text line per kernel tag,
  * "tag launches total_ms algorithmic_flops algorithmic_bytes", then resets the records. */

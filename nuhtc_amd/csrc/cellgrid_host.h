@@ -1,7 +1,7 @@
 // The uniform grid over half-pixel points that the per-slide analyses share (cellbin.h; cellgraph.hip, cellspatial.hip, cellcluster.hip,
-// cellmst.hip): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
+// cellmst.hip, cellprox.hip): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
 // and the (cell, class) key of a point, the squared distance of a pair within reach, and the edge key of the spanning forest.  Header-only,
-// so a host program can exercise them under a sanitizer (tools/dev/cellspatial_host_check.cpp, tools/dev/cellmst_host_check.cpp); the
+// so a host program can exercise them under a sanitizer (tools/dev/cellspatial_host_check.cpp, tools/dev/cellmst_host_check.cpp, tools/dev/cellprox_host_check.cpp); the
 // kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
 #pragma once
 #include <cstdint>
@@ -64,6 +64,19 @@ CELL_HD inline int mst_key_d2(unsigned long long key) { return (int)(key >> MST_
 CELL_HD inline int mst_key_lo(unsigned long long key) { return (int)(key & (((unsigned long long)1 << MST_ROW_BITS) - 1)); }
 // is the edge (key a, hi a) in front of the edge (key b, hi b)?  The strict total order of the definition
 CELL_HD inline bool mst_edge_less(unsigned long long ka, int ha, unsigned long long kb, int hb) { return ka < kb || (ka == kb && ha < hb); }
+
+// ---- the two emptiness tests of the proximity graphs (cellprox.hip): does the witness k block the candidate pair (i, j)?  Functions of
+// the three squared distances alone.  dij = d2(i, j) >= 0 is the candidate's (within reach), dik = d2(i, k) >= 0 the witness's from the
+// end the sweep runs around, and djk = cell_pair_d2 of (j, k): -1 when k is out of j's reach, and then k blocks in neither test -- it is
+// farther from j than the reach, hence farther than dij.  Why nothing overflows, stated here once: every d2 that is not -1 is at most
+// reach^2 <= 16384^2 = 2^28, so dik + djk <= 2^29 < 2^31.  Both tests are STRICT: a witness on the circle with diameter ij (a right
+// angle at k: dik + djk == dij) and a witness as far from an end as the other end is (max == dij) do not block; a witness coincident
+// with an end never blocks (dik == 0 gives djk == dij, and dik == dij is not < dij), so neither end needs to be told from a witness.
+// Gabriel-blocked implies RNG-blocked (two non-negative terms with a sum below dij are each below it): every RNG edge is a Gabriel edge.
+CELL_HD inline bool prox_gabriel_blocked(int dik, int djk, int dij) { return djk >= 0 && dik + djk < dij; }
+CELL_HD inline bool prox_rng_blocked(int dik, int djk, int dij) { return djk >= 0 && dik < dij && djk < dij; }
+// an edge's d2 (<= 2^28) and its RNG bit in one int while the segments are put in order
+constexpr int PROX_RNG_BIT = 1 << 30;
 
 // ---- the front checks of an entry point, before anything is launched: the limits every analysis shares (its own n limit passed in),
 // and, when there are points, the bounding box

@@ -55,6 +55,14 @@ Output (like the reference, :659-693), for every detection that survives the per
                   `length_std_px`, `length_min_max_ratio`, `length_disorder`.  Ties are broken by (d2, i, j), so the file is a pure
                   function of the rows; cutting the forest at any length t <= radius gives the components of the t-radius graph.  Every
                   other file is the same bytes with and without the flag.  There is no route without a GPU.
+  --nuclei-proximity: (not in the reference) <id>_nuclei_proximity.npz beside the documents, for the same rows as --nuclei-graph: the Gabriel
+                  graph and the relative neighbourhood graph (RNG) of the nuclei, the parameter-free "who touches whom" relations, over
+                  the pairs at most --proximity-radius px apart (64 by default), over all nuclei or, with --proximity-by class, among
+                  nuclei of one label -- built on rank 0's GPU after the gather (nuhtc_amd/proximity.py): `edges` (the Gabriel edges, rows
+                  of this file, i < j, ascending), `edge_d2` (half pixels squared), `edge_rng` (1: an RNG edge too), `degree` (n, 2), and
+                  the derived `edge_len_px`, `gabriel_class_count`, `rng_class_count`, `mean_len_px`, `other_class_share`,
+                  `gabriel_class_enrichment`, `n_edges`, `n_rng`.  Both graphs are unique without a tie rule, so the file is a pure
+                  function of the rows.  Every other file is the same bytes with and without the flag.  There is no route without a GPU.
   --nuclei-morph: (the reference's tools/wsi_feat_extract.py table, computed on the GPU) <id>_nuclei_morph.npz beside the documents, for the
                   same rows: `columns` and `values` float64 (n, F) -- size, shape, orientation, position and haematoxylin-intensity features
                   under histomicstk's names, derived on the host (nuhtc_amd/nucmorph.py derive) from the integers every rank's GPU measured
@@ -155,6 +163,13 @@ def build_parser():
                    help='longest edge of --nuclei-mst in slide px, a multiple of 0.5 up to 8192 (default 64 px: 16 um at 40x)')
     p.add_argument('--mst-by', choices=('any', 'class'), default='any', dest='mst_by',
                    help="--nuclei-mst over all nuclei ('any') or only among nuclei of the same label ('class')")
+    p.add_argument('--nuclei-proximity', action='store_true', dest='nuclei_proximity',
+                   help='also write <id>_nuclei_proximity.npz: the Gabriel graph and the relative neighbourhood graph of the written nuclei (edges, '
+                        'their lengths, the degrees, which classes touch), built on the GPU; rows as in --nuclei-graph')
+    p.add_argument('--proximity-radius', type=float, default=64.0, dest='proximity_radius',
+                   help='longest edge of --nuclei-proximity in slide px, a multiple of 0.5 up to 8192 (default 64 px: 16 um at 40x)')
+    p.add_argument('--proximity-by', choices=('any', 'class'), default='any', dest='proximity_by',
+                   help="--nuclei-proximity over all nuclei ('any') or only among nuclei of the same label ('class')")
     return p
 
 
@@ -276,14 +291,15 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
     spatial_on = getattr(args, 'nuclei_spatial', False)
     clusters_on = getattr(args, 'nuclei_clusters', False)
     mst_on = getattr(args, 'nuclei_mst', False)
-    if sel or graph or spatial_on or clusters_on or mst_on:                                    # the rows of the per-nucleus files, and their labels and scores
+    prox_on = getattr(args, 'nuclei_proximity', False)
+    if sel or graph or spatial_on or clusters_on or mst_on or prox_on:                                    # the rows of the per-nucleus files, and their labels and scores
         hall = np.concatenate([h.cpu().numpy() for h in heads], 0).reshape(-1, 9)
         rows = np.arange(n_records, dtype=np.int64) if feat_rows is None else feat_rows
     for i, kind in enumerate(sel):
         kind.write(os.path.join(out_dir, name + kind.suffix), rows, wsi.gathered_rows(kind, gathered, rows, part=rows_at + i),
                    hall[rows, 5].astype(np.int64), hall[rows, 4])
         msg += f', {len(rows)} {kind.said} in {name}{kind.suffix}'
-    if graph or spatial_on or clusters_on or mst_on:                  # one point set for the four: only what the gather already delivered
+    if graph or spatial_on or clusters_on or mst_on or prox_on:       # one point set for the five: only what the gather already delivered
         from nuhtc_amd import cellpoints
         boxes, lab = hall[rows, :4], hall[rows, 5].astype(np.int64)
         pts, xy = cellpoints.quantize_centres(boxes), cellpoints.centres(boxes)
@@ -315,6 +331,14 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
         mst.write_npz(os.path.join(out_dir, name + '_nuclei_mst.npz'), rows, xy, lab, e, ed2, tree, len(model.CLASSES),
                       radius_px=args.mst_radius, by_class=by)
         msg += f', {n_e} forest edges in {n_t} trees ({args.mst_radius:g} px, by {args.mst_by}) in {name}_nuclei_mst.npz'
+    if prox_on:                                                       # which of the same rows touch: the Gabriel graph and the RNG
+        from nuhtc_amd import proximity
+        by = proximity.BY[args.proximity_by]
+        e, ed2, erng, deg, n_e, n_r = proximity.build(pts, lab, len(model.CLASSES), args.proximity_radius, by, device=on)
+        proximity.write_npz(os.path.join(out_dir, name + '_nuclei_proximity.npz'), rows, xy, lab, e, ed2, erng, deg, len(model.CLASSES),
+                            radius_px=args.proximity_radius, by_class=by)
+        msg += (f', {n_e} Gabriel edges, {n_r} of them RNG edges ({args.proximity_radius:g} px, by {args.proximity_by}) '
+                f'in {name}_nuclei_proximity.npz')
     if want('dsa'):
         outputs.write_json(os.path.join(out_dir, name + '_dsa.json'), outputs.dsa_document(dsa))
     if want('coco'):
@@ -387,6 +411,14 @@ def main(argv=None):
             raise SystemExit(f'--nuclei-mst: {e}')
         if not torch.cuda.is_available():
             raise SystemExit('--nuclei-mst: no GPU is visible (there is no fallback)')
+    if args.nuclei_proximity:
+        from nuhtc_amd import proximity
+        try:
+            proximity.check_args(1, proximity.half_pixel_radius(args.proximity_radius), proximity.BY[args.proximity_by])
+        except ValueError as e:
+            raise SystemExit(f'--nuclei-proximity: {e}')
+        if not torch.cuda.is_available():
+            raise SystemExit('--nuclei-proximity: no GPU is visible (there is no fallback)')
     # the process group is formed AFTER seg_and_patch: rank 0's host phase (segmentation, masks, patching, stitching of every slide of the
     # folder) has no time bound, and a rank waiting in an RCCL barrier is aborted by the watchdog after 10 minutes
     rank, local_rank, world = parallel.env_ranks()
