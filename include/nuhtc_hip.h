@@ -1040,6 +1040,30 @@ int nuhtc_cell_proximity(int device, const int32_t* points, const int32_t* label
                          int64_t edge_cap, int x_min, int y_min, int x_max, int y_max, int32_t* edges, int32_t* edge_d2,
                          uint8_t* edge_rng, int32_t* degree, int64_t* m, int64_t* m_rng, void* stream);
 
+/* Nucleus density maps of a slide (csrc/celldensity.hip; nuhtc_amd/density.py holds the definition and the brute-force restatement
+ * `density_reference`): class-wise kernel rasters of the nucleus centres on a lattice anchored at the slide's origin -- "where on the slide".
+ * Not in the reference.  Engine-free like the forest's and the proximity call: points, labels and the two outputs are device memory of
+ * `device`, the call allocates and frees its own scratch, runs on `stream` and synchronises it before returning.  nuhtc_config is unchanged
+ * (no ABI bump).
+ *   points [n][2] int32: node positions in HALF pixels, |p| < 2^27.  labels [n] int32.  0 <= n <= 2^24.  num_classes C: 1 .. 14.
+ *   h: the bandwidth in half pixels, 1 .. 16384.  s: the pitch in half pixels, 1 .. 2^20.
+ *   gx0, gy0, W, H: the window in lattice units; W, H >= 1, W * H <= 2^24, and every site coordinate |g * s| < 2^28 (checked in 64 bits).
+ *     Any window is accepted: a sub-window, one partly off the points, or one nowhere near them (all zeros).
+ *   x_min, y_min, x_max, y_max: the bounding box of the points (inclusive), computed by the caller on the host (ignored when n == 0).
+ * Site (u, v) lies at q = ((gx0 + u) * s, (gy0 + v) * s): the lattice is anchored at the slide's origin, not at the points, so maps of
+ * different runs and radii align.  For every class c in 0 .. C - 1 and every site:
+ *   count [C][H][W] int32: the points i with labels[i] == c and d2(q, p_i) <= h * h (the radius is inclusive).
+ *   weight [C][H][W] int64: the sum over those points of h * h - d2(q, p_i) (the Epanechnikov kernel, un-normalised).
+ * A point with a label outside 0 .. C - 1 is counted nowhere; a point exactly at distance h adds 1 to count and 0 to weight.  All
+ * arithmetic is integer: |q - p| < 2^28 + 2^27 is an exact int32, the box test against h comes before the products, a term is at most 2^28
+ * and a weight below 2^52.  Both outputs are always fully written on success, zeros included; with n == 0 both are cleared and nothing
+ * else runs.  The result is a pure function of the input: bitwise the same on every call.
+ * NUHTC_E_INVALID, before anything is launched and with the outputs untouched: n, num_classes, h, s or the window out of range, a null
+ * pointer (count, weight always, the others with n > 0), with n > 0 a bounding box that is empty or reaches +-2^27.
+ * NUHTC_E_INVALID after the binning, the outputs still untouched: a point lies outside the stated bounding box. */
+int nuhtc_cell_density(int device, const int32_t* points, const int32_t* labels, int64_t n, int num_classes, int h, int s, int gx0, int gy0,
+                       int W, int H, int x_min, int y_min, int x_max, int y_max, int32_t* count, int64_t* weight, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the launch stream (process-wide switch; off by default).
  * nuhtc_profile_read synchronises the device and writes one text line per kernel tag,
  * "tag launches total_ms algorithmic_flops algorithmic_bytes", then resets the records. */

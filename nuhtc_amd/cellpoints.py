@@ -1,4 +1,4 @@
-"""What the per-slide point analyses -- cellgraph.py, spatial.py, clusters.py, mst.py, proximity.py, which hold the definitions -- do in the same way: half-pixel
+"""What the per-slide point analyses -- cellgraph.py, spatial.py, clusters.py, mst.py, proximity.py, density.py, which hold the definitions -- do in the same way: half-pixel
 nucleus centres with one label each, the grid over the host-computed bounding box, the pair loop of the brute-force references, the one
 call into the library and the header of the .npz files.  |p| < 2**27 and a reach of at most 16384 half pixels keep every squared distance
 within reach an exact int32 on the device (csrc/cellgrid_host.h has the argument); the references restate it in int64."""

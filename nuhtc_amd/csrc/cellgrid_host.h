@@ -1,8 +1,8 @@
 // The uniform grid over half-pixel points that the per-slide analyses share (cellbin.h; cellgraph.hip, cellspatial.hip, cellcluster.hip,
-// cellmst.hip, cellprox.hip): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
+// cellmst.hip, cellprox.hip, celldensity.hip): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
 // and the (cell, class) key of a point, the squared distance of a pair within reach, and the edge key of the spanning forest.  Header-only,
-// so a host program can exercise them under a sanitizer (tools/dev/cellspatial_host_check.cpp, tools/dev/cellmst_host_check.cpp, tools/dev/cellprox_host_check.cpp); the
-// kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
+// so a host program can exercise them under a sanitizer (tools/dev/cellspatial_host_check.cpp, tools/dev/cellmst_host_check.cpp, tools/dev/cellprox_host_check.cpp,
+// tools/dev/celldensity_host_check.cpp); the kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
 #pragma once
 #include <cstdint>
 
@@ -77,6 +77,54 @@ CELL_HD inline bool prox_gabriel_blocked(int dik, int djk, int dij) { return djk
 CELL_HD inline bool prox_rng_blocked(int dik, int djk, int dij) { return djk >= 0 && dik < dij && djk < dij; }
 // an edge's d2 (<= 2^28) and its RNG bit in one int while the segments are put in order
 constexpr int PROX_RNG_BIT = 1 << 30;
+
+// ---- the density rasters (celldensity.hip): the queries are lattice SITES q = (g * s), not points, and a site may lie outside the box on
+// every side.  The bit budget, stated here once: a site has |q| < 2^28 (checked on the host in 64 bits) and a point |p| < 2^27, so
+// |q - p| < 2^28 + 2^27 < 2^31 and the differences are exact int32 -- the same holds for q - x_min and for q +- h - x_min (h <= 2^14).
+// The box test against h comes BEFORE the products (cell_pair_d2), so d2 <= h * h <= 2^28 and each term h * h - d2 lies in 0 .. 2^28.
+// With n <= 2^24 points a weight stays below 2^24 * 2^28 = 2^52: `weight` is int64; `count` <= 2^24 is int32.
+constexpr int DENS_SITE_LIMIT = 1 << 28;               // |g * s| < 2^28 half pixels
+constexpr int DENS_MAX_PITCH = 1 << 20;
+constexpr int64_t DENS_MAX_SITES = (int64_t)1 << 24;
+constexpr int DENS_TILE = 16;                          // a workgroup owns DENS_TILE x DENS_TILE sites
+
+// floor(a / b) for b > 0 (the / of C++ truncates toward zero, which is not the floor left of the origin)
+CELL_HD inline int cell_floor_div(int a, int b) { return a / b - (a % b < 0); }
+
+// the cell a coordinate falls in along one axis of a grid that starts at `origin`: the floor, so negative left of the box and >= the
+// number of cells right of it (|v - origin| < 2^31 by the budget above)
+CELL_HD inline int site_cell(int v, int origin, int side) { return cell_floor_div(v - origin, side); }
+
+// the cells of one axis (nc of them) that the interval lo .. hi can touch, clamped to the grid: c0 .. c1, EMPTY (c0 > c1) when the interval
+// lies wholly outside.  For a site q with lo = q - h and hi = q + h these are at most three cells (side >= h), the site's own and its
+// neighbours as far as they exist; for a tile of sites it is the tile's footprint grown by h.
+CELL_HD inline void site_cell_range(int lo, int hi, int origin, int side, int nc, int* c0, int* c1) {
+  const int a = site_cell(lo, origin, side), b = site_cell(hi, origin, side);
+  *c0 = a > 0 ? a : 0;
+  *c1 = b < nc - 1 ? b : nc - 1;
+}
+
+// what a point at (dx, dy) from a site adds to the site's weight, h * h - d2, or -1 when it is out of reach (h2 = h * h; inclusive: a
+// point exactly at distance h adds 0 and is counted)
+CELL_HD inline int dens_term(int dx, int dy, int h, int h2) {
+  const int d2 = cell_pair_d2(dx, dy, h, h2);
+  return d2 < 0 ? -1 : h2 - d2;
+}
+
+// which kernel takes the sites.  A tile of 16 x 16 sites staged through LDS tests every record of its footprint, about 15 s + 2 h + side
+// along each axis, against every site; a site on its own tests the records of its (at most) three cells, about 2 h + side along each axis.
+// The staged test is cheaper (a broadcast LDS read against a global load), the direct one tests fewer records as soon as the sites of a
+// tile are far apart: the tile is taken while its footprint is at most twice as long as one site's (measured on both sides of the rule:
+// profiles/cell_density.json).
+CELL_HD inline bool dens_route_staged(int s, int h, int side) { return (long long)(DENS_TILE - 1) * s <= 2LL * h + side; }
+
+// the window of sites: W, H >= 1, W * H <= 2^24, and every site coordinate within +-2^28, all in 64 bits
+inline bool dens_window_ok(int s, int gx0, int gy0, int W, int H) {
+  if (s < 1 || s > DENS_MAX_PITCH || W < 1 || H < 1 || (int64_t)W * H > DENS_MAX_SITES) return false;
+  const int64_t lim = DENS_SITE_LIMIT;
+  const int64_t xa = (int64_t)gx0 * s, xb = ((int64_t)gx0 + W - 1) * s, ya = (int64_t)gy0 * s, yb = ((int64_t)gy0 + H - 1) * s;
+  return xa > -lim && xa < lim && xb > -lim && xb < lim && ya > -lim && ya < lim && yb > -lim && yb < lim;
+}
 
 // ---- the front checks of an entry point, before anything is launched: the limits every analysis shares (its own n limit passed in),
 // and, when there are points, the bounding box

@@ -63,6 +63,15 @@ Output (like the reference, :659-693), for every detection that survives the per
                   the derived `edge_len_px`, `gabriel_class_count`, `rng_class_count`, `mean_len_px`, `other_class_share`,
                   `gabriel_class_enrichment`, `n_edges`, `n_rng`.  Both graphs are unique without a tie rule, so the file is a pure
                   function of the rows.  Every other file is the same bytes with and without the flag.  There is no route without a GPU.
+  --nuclei-density: (not in the reference) <id>_nuclei_density.npz beside the documents, from the same rows as --nuclei-graph: class-wise
+                  density maps of the nuclei ("where on the slide": a TIL map, a cellularity map, a heat map for a viewer) on a lattice of
+                  --density-pitch px (64 by default) anchored at the slide's origin, with the Epanechnikov kernel of --density-bandwidth
+                  px (128 by default) -- built on rank 0's GPU after the gather (nuhtc_amd/density.py): `count` int32 and `weight` int64
+                  (C, H, W), exact integers (the nuclei within the bandwidth of every site, and the sum of h^2 - d^2 over them in half
+                  pixels), the derived `density_per_px2`, `share`, `class_total`, `colocalisation`, `peak_site`, and `bandwidth_px`,
+                  `pitch_px`, `origin_px` (the px position of site (0, 0)), `window` (gx0, gy0, W, H in lattice units).  No tissue-area
+                  normalisation and no edge correction.  Every other file is the same bytes with and without the flag.  There is no route
+                  without a GPU.
   --nuclei-morph: (the reference's tools/wsi_feat_extract.py table, computed on the GPU) <id>_nuclei_morph.npz beside the documents, for the
                   same rows: `columns` and `values` float64 (n, F) -- size, shape, orientation, position and haematoxylin-intensity features
                   under histomicstk's names, derived on the host (nuhtc_amd/nucmorph.py derive) from the integers every rank's GPU measured
@@ -170,6 +179,13 @@ def build_parser():
                    help='longest edge of --nuclei-proximity in slide px, a multiple of 0.5 up to 8192 (default 64 px: 16 um at 40x)')
     p.add_argument('--proximity-by', choices=('any', 'class'), default='any', dest='proximity_by',
                    help="--nuclei-proximity over all nuclei ('any') or only among nuclei of the same label ('class')")
+    p.add_argument('--nuclei-density', action='store_true', dest='nuclei_density',
+                   help='also write <id>_nuclei_density.npz: class-wise density maps of the written nuclei on a lattice anchored at the slide origin '
+                        '(counts and Epanechnikov weights per site, exact integers), built on the GPU; from the rows of --nuclei-graph')
+    p.add_argument('--density-bandwidth', type=float, default=128.0, dest='density_bandwidth',
+                   help='kernel radius of --nuclei-density in slide px, a multiple of 0.5 up to 8192 (default 128 px: 32 um at 40x)')
+    p.add_argument('--density-pitch', type=float, default=64.0, dest='density_pitch',
+                   help='distance between the sites of --nuclei-density in slide px, a multiple of 0.5 (default 64 px)')
     return p
 
 
@@ -292,14 +308,15 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
     clusters_on = getattr(args, 'nuclei_clusters', False)
     mst_on = getattr(args, 'nuclei_mst', False)
     prox_on = getattr(args, 'nuclei_proximity', False)
-    if sel or graph or spatial_on or clusters_on or mst_on or prox_on:                                    # the rows of the per-nucleus files, and their labels and scores
+    dens_on = getattr(args, 'nuclei_density', False)
+    if sel or graph or spatial_on or clusters_on or mst_on or prox_on or dens_on:                                    # the rows of the per-nucleus files, and their labels and scores
         hall = np.concatenate([h.cpu().numpy() for h in heads], 0).reshape(-1, 9)
         rows = np.arange(n_records, dtype=np.int64) if feat_rows is None else feat_rows
     for i, kind in enumerate(sel):
         kind.write(os.path.join(out_dir, name + kind.suffix), rows, wsi.gathered_rows(kind, gathered, rows, part=rows_at + i),
                    hall[rows, 5].astype(np.int64), hall[rows, 4])
         msg += f', {len(rows)} {kind.said} in {name}{kind.suffix}'
-    if graph or spatial_on or clusters_on or mst_on or prox_on:       # one point set for the five: only what the gather already delivered
+    if graph or spatial_on or clusters_on or mst_on or prox_on or dens_on:       # one point set for the six: only what the gather already delivered
         from nuhtc_amd import cellpoints
         boxes, lab = hall[rows, :4], hall[rows, 5].astype(np.int64)
         pts, xy = cellpoints.quantize_centres(boxes), cellpoints.centres(boxes)
@@ -339,6 +356,14 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
                             radius_px=args.proximity_radius, by_class=by)
         msg += (f', {n_e} Gabriel edges, {n_r} of them RNG edges ({args.proximity_radius:g} px, by {args.proximity_by}) '
                 f'in {name}_nuclei_proximity.npz')
+    if dens_on:                                                       # where on the slide the same rows lie: class-wise kernel rasters
+        from nuhtc_amd import density
+        cnt, wgt, win = density.build(pts, lab, len(model.CLASSES), args.density_bandwidth, args.density_pitch, device=on)
+        density.write_npz(os.path.join(out_dir, name + '_nuclei_density.npz'), rows, xy, lab, cnt, wgt, win, args.density_bandwidth, args.density_pitch)
+        peaks = density.derive(cnt, wgt, density.half_pixel_radius(args.density_bandwidth))['peak_site']
+        peak_px = ', '.join('none' if u < 0 else f'({(win[0] + u) * args.density_pitch:g}, {(win[1] + v) * args.density_pitch:g})' for u, v in peaks.tolist())
+        msg += (f', density maps of {win[2]} x {win[3]} sites ({args.density_bandwidth:g} px bandwidth, {args.density_pitch:g} px pitch; '
+                f'peak px per class: {peak_px}) in {name}_nuclei_density.npz')
     if want('dsa'):
         outputs.write_json(os.path.join(out_dir, name + '_dsa.json'), outputs.dsa_document(dsa))
     if want('coco'):
@@ -419,6 +444,14 @@ def main(argv=None):
             raise SystemExit(f'--nuclei-proximity: {e}')
         if not torch.cuda.is_available():
             raise SystemExit('--nuclei-proximity: no GPU is visible (there is no fallback)')
+    if args.nuclei_density:
+        from nuhtc_amd import density
+        try:
+            density.check_args(1, density.half_pixel_radius(args.density_bandwidth), density.half_pixel_radius(args.density_pitch))
+        except ValueError as e:
+            raise SystemExit(f'--nuclei-density: {e}')
+        if not torch.cuda.is_available():
+            raise SystemExit('--nuclei-density: no GPU is visible (there is no fallback)')
     # the process group is formed AFTER seg_and_patch: rank 0's host phase (segmentation, masks, patching, stitching of every slide of the
     # folder) has no time bound, and a rank waiting in an RCCL barrier is aborted by the watchdog after 10 minutes
     rank, local_rank, world = parallel.env_ranks()
