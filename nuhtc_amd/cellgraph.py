@@ -80,10 +80,10 @@ def build(points, labels, num_classes, radius_px, k, device=0):
     (neighbors int32 (n, k), d2 int32 (n, k), class_count int32 (n, num_classes)) out.  There is no host route: without the library or a
     GPU this raises."""
     import torch
-    p, lab = cellpoints.as_points(points, labels, 'cell graph')
-    n, C, k, r = len(p), int(num_classes), int(k), half_pixel_radius(radius_px)
+    C, k, r = int(num_classes), int(k), half_pixel_radius(radius_px)
     check_args(C, r, k)
-    dev, p_d, lab_d, bounds = cellpoints.upload(p, lab, device)
+    p, lab, dev, p_d, lab_d, bounds = cellpoints.resident(points, labels, 'cell graph', device, bounded=False)
+    n = len(p)
     out = [torch.full((n, w), fill, dtype=torch.int32, device=dev) for w, fill in ((k, -1), (k, -1), (C, 0))]
     cellpoints.raise_for(call(p_d, lab_d, C, r, k, *out, bounds=bounds, device=device), 'nuhtc_cell_graph')
     return tuple(t.cpu().numpy() for t in out)

@@ -1,11 +1,13 @@
 """What the per-slide point analyses -- cellgraph.py, spatial.py, clusters.py, mst.py, proximity.py, density.py, which hold the definitions -- do in the same way: half-pixel
 nucleus centres with one label each, the grid over the host-computed bounding box, the pair loop of the brute-force references, the one
-call into the library and the header of the .npz files.  |p| < 2**27 and a reach of at most 16384 half pixels keep every squared distance
+call into the library, the opening of a `build`, the header of the .npz files, and the checks and the census more than one of them holds
+(slidepoints.py is the table that runs them for the slide path).  |p| < 2**27 and a reach of at most 16384 half pixels keep every squared distance
 within reach an exact int32 on the device (csrc/cellgrid_host.h has the argument); the references restate it in int64."""
 import numpy as np
 
 MAX_R, MAX_CLASSES = 16384, 14
 COORD_LIMIT = 1 << 27                 # |p| < 2**27 half pixels
+MAX_POINTS = 1 << 24                  # of clusters, mst, proximity and density
 
 
 def centres(boxes):
@@ -56,6 +58,29 @@ def as_points(points, labels, what):
     return p, lab
 
 
+def check_radius_args(what, num_classes, r, by_class):
+    """num_classes 1..14, r 1..16384 half pixels, by_class 0 or 1: ValueError, in the name of `what`, otherwise."""
+    whole = all(float(v) == int(v) for v in (num_classes, r, by_class))
+    if not (whole and 1 <= int(num_classes) <= MAX_CLASSES and 1 <= int(r) <= MAX_R and int(by_class) in (0, 1)):
+        raise ValueError(f'{what}: num_classes 1..{MAX_CLASSES}, r 1..{MAX_R} half pixels, by_class 0 or 1 '
+                         f'(got num_classes={num_classes}, r={r}, by_class={by_class})')
+
+
+def class_pair_census(la, lb, C):
+    """The labels int64 (m,) at the two ends of m edges -> int64 (C, C): the edges by [min label, max label] (upper triangle); an edge
+    touching a label outside 0..C-1 is counted nowhere."""
+    known = (la >= 0) & (la < C) & (lb >= 0) & (lb < C)
+    census = np.zeros((C, C), np.int64)
+    np.add.at(census, (np.minimum(la, lb)[known], np.maximum(la, lb)[known]), 1)
+    return census
+
+
+def check_edge_rows(edges, n):
+    """edges int (m, 2) of a write_npz: ValueError unless every edge is (i, j) with i < j, both among the n rows of the file."""
+    if len(edges) and not ((edges[:, 0] < edges[:, 1]).all() and edges.min() >= 0 and edges.max() < n):
+        raise ValueError('write_npz: an edge is (i, j) with i < j, both rows of the file')
+
+
 def reference_points(points, labels, what):
     """-> (points int64 (n, 2), labels int64 (n,)) for a brute-force reference; ValueError unless one label each and |p| < 2**27."""
     p = np.asarray(points, np.int64).reshape(-1, 2)
@@ -104,6 +129,15 @@ def upload(p, lab, device):
     import torch
     dev = torch.device('cuda', device)
     return dev, torch.from_numpy(p).to(dev), torch.from_numpy(lab).to(dev), (bounds_of(p) if len(p) else None)
+
+
+def resident(points, labels, what, device, bounded=True):
+    """How a `build` opens once its arguments are checked: as_points, at most MAX_POINTS of them when `bounded`, upload ->
+    (p, lab) + upload's four."""
+    p, lab = as_points(points, labels, what)
+    if bounded and len(p) > MAX_POINTS:
+        raise ValueError(f'{what}: at most 2**24 points (got {len(p)})')
+    return (p, lab) + upload(p, lab, device)
 
 
 def raise_for(rc, name):

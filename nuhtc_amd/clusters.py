@@ -35,9 +35,8 @@ import numpy as np
 
 from . import cellpoints
 from .cellgraph import cell_side  # noqa: F401 (the cell graph's grid, re-exported)
-from .cellpoints import COORD_LIMIT, MAX_CLASSES, MAX_R, centres, half_pixel_radius, quantize_centres  # noqa: F401 (re-exported)
+from .cellpoints import COORD_LIMIT, MAX_CLASSES, MAX_POINTS, MAX_R, centres, half_pixel_radius, quantize_centres  # noqa: F401 (re-exported)
 
-MAX_POINTS = 1 << 24
 MAX_MIN_PTS = (1 << 31) - 1
 INT_NAMES = ('cluster', 'core', 'degree', 'size', 'n_core', 'class_count', 'sum_xy', 'bbox')
 DERIVED_KEYS = ('centroid_px', 'bbox_px', 'class_fraction', 'n_clusters', 'n_noise', 'class_n', 'class_clustered', 'class_clustered_share')
@@ -142,12 +141,10 @@ def build(points, labels, num_classes, radius_px, min_pts, by_class=0, device=0)
     """The clusters of `points` (int (n, 2) half pixels, see cellpoints.quantize_centres) with `labels` (n,) on cuda:`device`: numpy in,
     the eight arrays of `cluster_reference` out (the per-cluster ones cut to their m rows).  There is no host route: without the library or
     a GPU this raises."""
-    p, lab = cellpoints.as_points(points, labels, 'clusters')
-    n, C, r = len(p), int(num_classes), half_pixel_radius(radius_px)
-    if n > MAX_POINTS:
-        raise ValueError(f'clusters: at most 2**24 points (got {n})')
+    C, r = int(num_classes), half_pixel_radius(radius_px)
     check_args(C, r, min_pts, by_class)
-    dev, p_d, lab_d, bounds = cellpoints.upload(p, lab, device)
+    p, lab, dev, p_d, lab_d, bounds = cellpoints.resident(points, labels, 'clusters', device)
+    n = len(p)
     out = outputs(n, C, dev)
     rc, m = call(p_d, lab_d, C, r, int(min_pts), int(by_class), *out, bounds=bounds, device=device)
     cellpoints.raise_for(rc, 'nuhtc_cell_clusters')

@@ -40,9 +40,8 @@ near the tissue border sees fewer nuclei, and nothing compensates for that."""
 import numpy as np
 
 from . import cellpoints
-from .cellpoints import COORD_LIMIT, MAX_CLASSES, MAX_R, centres, half_pixel_radius, quantize_centres  # noqa: F401 (re-exported)
+from .cellpoints import COORD_LIMIT, MAX_CLASSES, MAX_POINTS, MAX_R, centres, half_pixel_radius, quantize_centres  # noqa: F401 (re-exported)
 
-MAX_POINTS = 1 << 24
 MAX_SITES = 1 << 24
 MAX_PITCH = 1 << 20
 SITE_LIMIT = 1 << 28                  # |g * s| < 2**28 half pixels

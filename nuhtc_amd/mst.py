@@ -32,9 +32,8 @@ edge lengths in px, node degrees, tree sizes and lengths, the class-pair census 
 import numpy as np
 
 from . import cellpoints
-from .cellpoints import COORD_LIMIT, MAX_CLASSES, MAX_R, centres, half_pixel_radius, quantize_centres  # noqa: F401 (re-exported)
+from .cellpoints import COORD_LIMIT, MAX_CLASSES, MAX_POINTS, MAX_R, centres, half_pixel_radius, quantize_centres  # noqa: F401 (re-exported)
 
-MAX_POINTS = 1 << 24
 INT_NAMES = ('edges', 'edge_d2', 'tree')
 DERIVED_KEYS = ('edge_len_px', 'mst_degree', 'tree_size', 'tree_length_px', 'edge_class_count', 'n_trees', 'n_edges',
                 'length_mean_px', 'length_std_px', 'length_min_max_ratio', 'length_disorder')
@@ -44,10 +43,7 @@ BY = {'any': 0, 'class': 1}
 
 def check_args(num_classes, r, by_class):
     """num_classes 1..14, r 1..16384 half pixels, by_class 0 or 1: ValueError otherwise."""
-    whole = all(float(v) == int(v) for v in (num_classes, r, by_class))
-    if not (whole and 1 <= int(num_classes) <= MAX_CLASSES and 1 <= int(r) <= MAX_R and int(by_class) in (0, 1)):
-        raise ValueError(f'mst: num_classes 1..{MAX_CLASSES}, r 1..{MAX_R} half pixels, by_class 0 or 1 '
-                         f'(got num_classes={num_classes}, r={r}, by_class={by_class})')
+    cellpoints.check_radius_args('mst', num_classes, r, by_class)
 
 
 def mst_reference(points, labels, num_classes, r, by_class):
@@ -115,12 +111,10 @@ def build(points, labels, num_classes, radius_px, by_class=0, device=0, with_rou
     """The forest of `points` (int (n, 2) half pixels, see cellpoints.quantize_centres) with `labels` (n,) on cuda:`device`: numpy in, the
     five results of `mst_reference` out (edges and edge_d2 cut to their m rows), and the device's `rounds` behind them when `with_rounds`.
     There is no host route: without the library or a GPU this raises."""
-    p, lab = cellpoints.as_points(points, labels, 'mst')
-    n, C, r = len(p), int(num_classes), half_pixel_radius(radius_px)
-    if n > MAX_POINTS:
-        raise ValueError(f'mst: at most 2**24 points (got {n})')
+    C, r = int(num_classes), half_pixel_radius(radius_px)
     check_args(C, r, by_class)
-    dev, p_d, lab_d, bounds = cellpoints.upload(p, lab, device)
+    p, lab, dev, p_d, lab_d, bounds = cellpoints.resident(points, labels, 'mst', device)
+    n = len(p)
     out = outputs(n, dev)
     rc, m, t, rounds = call(p_d, lab_d, C, r, int(by_class), *out, bounds=bounds, device=device)
     cellpoints.raise_for(rc, 'nuhtc_cell_mst')
@@ -153,10 +147,7 @@ def derive(edges, edge_d2, tree, labels, num_classes):
     degree = np.bincount(e.reshape(-1), minlength=n).astype(np.int32)
     tree_size = np.bincount(tr, minlength=t).astype(np.int32)
     tree_length = np.bincount(tr[e[:, 0]], weights=length, minlength=t).astype(np.float64) if m else np.zeros(t, np.float64)
-    la, lb = lab[e[:, 0]], lab[e[:, 1]]
-    known = (la >= 0) & (la < C) & (lb >= 0) & (lb < C)
-    census = np.zeros((C, C), np.int64)
-    np.add.at(census, (np.minimum(la, lb)[known], np.maximum(la, lb)[known]), 1)
+    census = cellpoints.class_pair_census(lab[e[:, 0]], lab[e[:, 1]], C)
     mean = float(length.mean()) if m else 0.0
     std = float(length.std()) if m else 0.0
     longest = float(length.max()) if m else 0.0
@@ -180,8 +171,7 @@ def write_npz(path, nuclei_id, xy, label, edges, edge_d2, tree, num_classes, rad
     tree = np.ascontiguousarray(tree, np.int32).reshape(-1)
     if len(tree) != n or len(edges) != len(edge_d2):
         raise ValueError('write_npz: one tree per nucleus and one d2 per edge')
-    if len(edges) and not ((edges[:, 0] < edges[:, 1]).all() and edges.min() >= 0 and edges.max() < n):
-        raise ValueError('write_npz: an edge is (i, j) with i < j, both rows of the file')
+    cellpoints.check_edge_rows(edges, n)
     check_args(num_classes, half_pixel_radius(radius_px), by_class)
     d = derive(edges, edge_d2, tree, head['label'], num_classes)
     with open(path, 'wb') as f:

@@ -41,9 +41,8 @@ share of neighbours of another label, and the census over what shuffled labels w
 import numpy as np
 
 from . import cellpoints
-from .cellpoints import COORD_LIMIT, MAX_CLASSES, MAX_R, centres, half_pixel_radius, quantize_centres  # noqa: F401 (re-exported)
+from .cellpoints import COORD_LIMIT, MAX_CLASSES, MAX_POINTS, MAX_R, centres, half_pixel_radius, quantize_centres  # noqa: F401 (re-exported)
 
-MAX_POINTS = 1 << 24
 INT_NAMES = ('edges', 'edge_d2', 'edge_rng', 'degree')
 DERIVED_KEYS = ('edge_len_px', 'gabriel_class_count', 'rng_class_count', 'mean_len_px', 'other_class_share', 'gabriel_class_enrichment',
                 'n_edges', 'n_rng')
@@ -53,10 +52,7 @@ BY = {'any': 0, 'class': 1}
 
 def check_args(num_classes, r, by_class):
     """num_classes 1..14, r 1..16384 half pixels, by_class 0 or 1: ValueError otherwise."""
-    whole = all(float(v) == int(v) for v in (num_classes, r, by_class))
-    if not (whole and 1 <= int(num_classes) <= MAX_CLASSES and 1 <= int(r) <= MAX_R and int(by_class) in (0, 1)):
-        raise ValueError(f'proximity: num_classes 1..{MAX_CLASSES}, r 1..{MAX_R} half pixels, by_class 0 or 1 '
-                         f'(got num_classes={num_classes}, r={r}, by_class={by_class})')
+    cellpoints.check_radius_args('proximity', num_classes, r, by_class)
 
 
 def first_edge_cap(n):
@@ -122,12 +118,10 @@ def build(points, labels, num_classes, radius_px, by_class=0, device=0, with_cal
     the six results of `proximity_reference` out, and the number of device calls it took behind them when `with_calls`.  The first call has
     room for `first_edge_cap(n)` edges; when there are more (many coincident points) the device says how many and writes no edge, and ONE
     second call has room for exactly that many.  There is no host route: without the library or a GPU this raises."""
-    p, lab = cellpoints.as_points(points, labels, 'proximity')
-    n, C, r = len(p), int(num_classes), half_pixel_radius(radius_px)
-    if n > MAX_POINTS:
-        raise ValueError(f'proximity: at most 2**24 points (got {n})')
+    C, r = int(num_classes), half_pixel_radius(radius_px)
     check_args(C, r, by_class)
-    dev, p_d, lab_d, bounds = cellpoints.upload(p, lab, device)
+    p, lab, dev, p_d, lab_d, bounds = cellpoints.resident(points, labels, 'proximity', device)
+    n = len(p)
     cap, calls = first_edge_cap(n), 1
     out = outputs(n, cap, dev)
     rc, m, m_rng = call(p_d, lab_d, C, r, int(by_class), cap, *out, bounds=bounds, device=device)
@@ -143,13 +137,6 @@ def build(points, labels, num_classes, radius_px, by_class=0, device=0, with_cal
             raise RuntimeError(f'nuhtc_cell_proximity: {m} edges on the second call, {cap} on the first')
     got = (out[0][:m].cpu().numpy(), out[1][:m].cpu().numpy(), out[2][:m].cpu().numpy(), out[3][:n].cpu().numpy(), m, m_rng)
     return got + (calls,) if with_calls else got
-
-
-def _census(la, lb, C):
-    known = (la >= 0) & (la < C) & (lb >= 0) & (lb < C)
-    census = np.zeros((C, C), np.int64)
-    np.add.at(census, (np.minimum(la, lb)[known], np.maximum(la, lb)[known]), 1)
-    return census
 
 
 def derive(edges, edge_d2, edge_rng, degree, labels, num_classes):
@@ -177,7 +164,7 @@ def derive(edges, edge_d2, edge_rng, degree, labels, num_classes):
         raise ValueError('derive: degree is not the number of edges at every row')
     length = np.sqrt(d2.astype(np.float64)) / 2
     la, lb = lab[e[:, 0]], lab[e[:, 1]]
-    gabriel, rng_count = _census(la, lb, C), _census(la[rng], lb[rng], C)
+    gabriel, rng_count = cellpoints.class_pair_census(la, lb, C), cellpoints.class_pair_census(la[rng], lb[rng], C)
     mean_len = np.zeros((n, 2), np.float64)
     for col, keep in ((0, np.ones(m, bool)), (1, rng)):
         total = np.bincount(e[keep].reshape(-1), weights=np.repeat(length[keep], 2), minlength=n) if keep.any() else np.zeros(n)
@@ -211,8 +198,7 @@ def write_npz(path, nuclei_id, xy, label, edges, edge_d2, edge_rng, degree, num_
     degree = np.ascontiguousarray(degree, np.int32).reshape(-1, 2)
     if len(degree) != n or not len(edges) == len(edge_d2) == len(edge_rng):
         raise ValueError('write_npz: one degree row per nucleus, one d2 and one rng flag per edge')
-    if len(edges) and not ((edges[:, 0] < edges[:, 1]).all() and edges.min() >= 0 and edges.max() < n):
-        raise ValueError('write_npz: an edge is (i, j) with i < j, both rows of the file')
+    cellpoints.check_edge_rows(edges, n)
     check_args(num_classes, half_pixel_radius(radius_px), by_class)
     d = derive(edges, edge_d2, edge_rng, degree, head['label'], num_classes)
     with open(path, 'wb') as f:

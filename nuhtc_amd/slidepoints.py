@@ -1,0 +1,110 @@
+"""The per-slide point analyses of the slide path as ONE table: which flag of tools/infer_wsi.py selects each, how its arguments become
+the parameters of its module (cellgraph, spatial, clusters, mst, proximity, density: they hold the definitions), which file it writes
+beside the documents and what the closing message says of it.  cellpoints.py is what the six modules share and is imported by them; this
+module imports them, one at a time and only when its flag is given.
+
+The order of ANALYSES is fixed: it is the order of the files and of the clauses of the closing message.  `select` turns the parsed
+arguments into a selection, `run` works a selection off on one point set; both name no analysis.  A new analysis is a module with
+check_args / build / write_npz and one row here (plus its argparse lines in the tool)."""
+import importlib
+import os
+from collections import namedtuple
+
+from . import cellpoints
+
+# cli, flag, suffix   the argparse attribute, the flag as the user types it and the file beside the documents
+# module   the module of nuhtc_amd that holds the definition, imported on first use (`module_of`)
+# params   (module, args) -> the parameters `build` takes behind num_classes, in the units of the command line; ValueError when unusable
+# check    (module, params) -> the module's check_args on them with one class (the model is not loaded yet); ValueError
+# write    (module, path, (nuclei_id, xy, label), what build returned, num_classes, params, context) -> write_npz
+# said     (module, what build returned, params) -> the clause of the closing message, without ' in <file>'
+Analysis = namedtuple('Analysis', 'cli flag suffix module params check write said')
+
+BY_NAMES = ('any', 'class')                   # the modules' BY, backwards
+_half = cellpoints.half_pixel_radius
+
+
+def module_of(an):
+    return importlib.import_module('.' + an.module, __package__)
+
+
+def _analysis(word, module, params, check, write, said):
+    return Analysis('nuclei_' + word, '--nuclei-' + word, f'_nuclei_{word}.npz', module, params, check, write, said)
+
+
+def _density_said(m, found, p):
+    cnt, wgt, win = found
+    peaks = m.derive(cnt, wgt, _half(p[0]))['peak_site']
+    peak_px = ', '.join('none' if u < 0 else f'({(win[0] + u) * p[1]:g}, {(win[1] + v) * p[1]:g})' for u, v in peaks.tolist())
+    return f'density maps of {win[2]} x {win[3]} sites ({p[0]:g} px bandwidth, {p[1]:g} px pitch; peak px per class: {peak_px})'
+
+
+ANALYSES = (
+    _analysis('graph', 'cellgraph',                                   # the edges to the rows
+              lambda m, a: (a.graph_radius, a.graph_k),
+              lambda m, p: m.check_args(1, _half(p[0]), p[1]),
+              lambda m, path, head, found, C, p, ctx: m.write_npz(path, head[0], head[1], *found, head[2], *p),
+              lambda m, found, p: f'{int((found[0] >= 0).sum())} edges (k {p[1]}, {p[0]:g} px)'),
+    _analysis('spatial', 'spatial',                                   # pair counts over the same rows
+              lambda m, a: (m.edges_from_step(a.spatial_step, a.spatial_bins),),
+              lambda m, p: None,
+              lambda m, path, head, found, C, p, ctx: m.write_npz(path, *head, p[0], *found, tiles_area_px=ctx['tiles_area_px']),
+              lambda m, found, p: f'{int(found[0].sum())} ordered pairs within {p[0][-1] / 2:g} px ({len(p[0])} bins)'),
+    _analysis('clusters', 'clusters',                                 # which of the same rows belong together
+              lambda m, a: (a.cluster_radius, a.cluster_min, m.BY[a.cluster_by]),
+              lambda m, p: m.check_args(1, _half(p[0]), p[1], p[2]),
+              lambda m, path, head, found, C, p, ctx: m.write_npz(path, *head, *found, radius_px=p[0], min_pts=p[1], by_class=p[2]),
+              lambda m, found, p: (f'{len(found[3])} clusters and {int((found[0] < 0).sum())} isolated nuclei ({p[0]:g} px, {p[1]} nuclei, '
+                                   f'by {BY_NAMES[p[2]]})')),
+    _analysis('mst', 'mst',                                           # the shortest edges that hold the same rows together
+              lambda m, a: (a.mst_radius, m.BY[a.mst_by]),
+              lambda m, p: m.check_args(1, _half(p[0]), p[1]),
+              lambda m, path, head, found, C, p, ctx: m.write_npz(path, *head, *found[:3], C, radius_px=p[0], by_class=p[1]),
+              lambda m, found, p: f'{found[3]} forest edges in {found[4]} trees ({p[0]:g} px, by {BY_NAMES[p[1]]})'),
+    _analysis('proximity', 'proximity',                               # which of the same rows touch: the Gabriel graph and the RNG
+              lambda m, a: (a.proximity_radius, m.BY[a.proximity_by]),
+              lambda m, p: m.check_args(1, _half(p[0]), p[1]),
+              lambda m, path, head, found, C, p, ctx: m.write_npz(path, *head, *found[:4], C, radius_px=p[0], by_class=p[1]),
+              lambda m, found, p: f'{found[4]} Gabriel edges, {found[5]} of them RNG edges ({p[0]:g} px, by {BY_NAMES[p[1]]})'),
+    _analysis('density', 'density',                                   # where on the slide the same rows lie: class-wise kernel rasters
+              lambda m, a: (a.density_bandwidth, a.density_pitch),
+              lambda m, p: m.check_args(1, _half(p[0]), _half(p[1])),
+              lambda m, path, head, found, C, p, ctx: m.write_npz(path, *head, *found, *p),
+              _density_said),
+)
+
+
+def select(args, need_gpu=True):
+    """The parsed arguments of tools/infer_wsi.py -> the selection: ((analysis, params), ..) of the flags given, in the order of ANALYSES.
+    SystemExit in the name of the flag when its arguments are unusable and then, with need_gpu, when no GPU is visible.  A flag the
+    namespace does not hold is not given."""
+    chosen = []
+    for an in ANALYSES:
+        if not getattr(args, an.cli, False):
+            continue
+        m = module_of(an)
+        try:
+            params = an.params(m, args)
+            an.check(m, params)
+        except ValueError as e:
+            raise SystemExit(f'{an.flag}: {e}')
+        if need_gpu:
+            import torch
+            if not torch.cuda.is_available():
+                raise SystemExit(f'{an.flag}: no GPU is visible (there is no fallback)')
+        chosen.append((an, params))
+    return tuple(chosen)
+
+
+def run(selection, rows, boxes, labels, num_classes, out_dir, name, device, context):
+    """A selection on ONE point set: the boxes (n, 4) of the rows `rows` of the per-nucleus files, quantised once, with `labels` (n,), on
+    cuda:`device`.  Every selected analysis is built and written as <out_dir>/<name><suffix>; context = dict(tiles_area_px=..) is what a
+    file states beyond its own flags.  -> the clauses of the closing message, in the order of ANALYSES."""
+    pts, xy = cellpoints.quantize_centres(boxes), cellpoints.centres(boxes)
+    clauses = []
+    for an, params in selection:
+        m = module_of(an)
+        found = m.build(pts, labels, num_classes, *params, device=device)
+        an.write(m, os.path.join(out_dir, name + an.suffix), (rows, xy, labels), found, num_classes, params, context)
+        clauses.append(f'{an.said(m, found, params)} in {name}{an.suffix}')
+    return clauses

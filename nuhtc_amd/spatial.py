@@ -121,10 +121,10 @@ def build(points, labels, num_classes, edges, device=0):
     (pair_hist int64 (C, C, B), nn_d2 int32 (n, C), class_n int64 (C,)) out.  There is no host route: without the library or a GPU this
     raises."""
     import torch
-    p, lab = cellpoints.as_points(points, labels, 'spatial statistics')
-    n, C = len(p), int(num_classes)
+    C = int(num_classes)
     e = check_args(C, edges)
-    dev, p_d, lab_d, bounds = cellpoints.upload(p, lab, device)
+    p, lab, dev, p_d, lab_d, bounds = cellpoints.resident(points, labels, 'spatial statistics', device, bounded=False)
+    n = len(p)
     out = [torch.zeros((C, C, len(e)), dtype=torch.int64, device=dev), torch.full((n, C), -1, dtype=torch.int32, device=dev),
            torch.zeros((C,), dtype=torch.int64, device=dev)]
     cellpoints.raise_for(call(p_d, lab_d, C, e, *out, bounds=bounds, device=device), 'nuhtc_cell_spatial')

@@ -4,20 +4,16 @@ points in one cell, slide-scale offsets, a grid whose 2^22-cell cap lifts the ce
 arguments, bitwise repeatability, and tools/infer_wsi.py --nuclei-graph end to end."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+import points_util
 from nuhtc_amd import cellgraph as cg
 from nuhtc_amd import hip, nucfeat
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CFG = os.path.join(ROOT, 'configs', 'nuhtc', 'htc_lite_swin_pannuke_infer.py')
-TOOL = os.path.join(ROOT, 'tools', 'infer_wsi.py')
 
 
 def _equal(got, want, what):
@@ -151,29 +147,15 @@ def test_a_coordinate_out_of_range_is_refused(hip_device):
 
 
 # ---- 8: the tool
-def _run(cmd, env=None, limit=300):
-    p = subprocess.run(['timeout', '-k', '10', str(limit), sys.executable, TOOL] + cmd, env=env, cwd=ROOT, capture_output=True, text=True)
-    print(p.stdout[-2000:], p.stderr[-2000:])
-    assert p.returncode == 0, p.returncode
-    return p.stdout
+_run = points_util.run_tool
 
 
 def test_cli_nuclei_graph(hip_device, tmp_path):
     """tools/infer_wsi.py --nuclei-feat --nuclei-graph on the synthetic .npy slide of tests/test_hip_nucfeat.py, plain, with --merge and on two
     ranks: one row per row of <id>_nuclei_feat.npz, the centres of <id>_point.geojson, the graph graph_reference gives on them, and every
     other file byte for byte as without the flag."""
-    from nuhtc_amd import synth, weights
-    ck = tmp_path / 'w.pth'
-    torch.save(dict(state_dict=weights.bench_state_dict(0, obj_bias=0.0)), ck)
-    slide = np.concatenate([np.concatenate(list(synth.nuclei_tiles(5, 64, start=r * 5)), 1) for r in range(3)], 0)    # 192 x 320
-    np.save(tmp_path / 's1.npy', slide)
-    base = [str(tmp_path / 's1.npy'), CFG, str(ck), '--patch_size', '64', '--step_size', '48', '--batch_size', '8', '--mode', 'qupath', '--nuclei-feat']
+    base, env, two, folder = points_util.slide_runs(tmp_path, '--nuclei-feat')
     graph = ['--nuclei-graph', '--graph-radius', '24', '--graph-k', '6']
-    env = dict(os.environ, NUHTC_HOST_AFFINITY='0')
-    two = dict(env, NUHTC_ONE_DEVICE='1', NUHTC_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0', OMP_NUM_THREADS='4')
-    for key in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
-        two.pop(key, None)
-    folder = lambda d: tmp_path / d / 'nuclei' / 's1'
     docs = lambda d: {f: open(folder(d) / f, 'rb').read() for f in sorted(os.listdir(folder(d))) if f.endswith('.geojson')}
     feat = lambda d: nucfeat.read_npz(str(folder(d) / 's1_nuclei_feat.npz'))
     _run(base + ['--save_dir', str(tmp_path / 'plain0')], env)

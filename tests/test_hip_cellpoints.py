@@ -1,12 +1,16 @@
 """GPU tests of what the three per-slide point analyses share (nuhtc_amd/cellpoints.py; csrc/cellbin.h: the binning, the 3 x 3 sweep, the
 scan, the epilogue): the cell graph, the spatial statistics and the clusters of ONE point set agree with each other where their definitions
 overlap, each equals its own brute-force reference, and the clusters' root numbering is right where the roots lie in more than one chunk
-of the scan."""
+of the scan.  And the loop that runs all six for the slide path (nuhtc_amd/slidepoints.py) on one hand-placed set of boxes."""
+import argparse
+import os
+
 import numpy as np
 import pytest
 
 from nuhtc_amd import cellgraph as cg
 from nuhtc_amd import clusters as cl
+from nuhtc_amd import density, mst, proximity, slidepoints
 from nuhtc_amd import spatial as sp
 
 pytestmark = pytest.mark.gpu
@@ -80,3 +84,66 @@ def test_the_root_numbering_crosses_scan_chunks(hip_device):
     assert np.array_equal(cluster, np.arange(n)) and core.all() and (degree == 1).all()
     assert (size == 1).all() and (n_core == 1).all() and np.array_equal(class_count, np.eye(3, dtype=np.int32)[lab])
     assert np.array_equal(sum_xy, p.astype(np.int64)) and np.array_equal(bbox, np.concatenate([p, p], 1))
+
+
+def _placed_boxes():
+    """60 boxes of 6 x 4 px, 5 classes: 56 on a jittered 8 x 7 lattice of 9 px whose centres fall on whole and half pixels, two with the centre
+    (120, 40) and one label, and two of one label exactly 10 px apart -- (200, 100) and (206, 108) -- away from the rest."""
+    at = np.arange(56)
+    cx = np.concatenate([20 + 9.0 * (at % 8) + (at * 7 % 5) * 0.5, [120, 120, 200, 206]])
+    cy = np.concatenate([15 + 9.0 * (at // 8) + (at * 3 % 4) * 0.5, [40, 40, 100, 108]])
+    lab = np.concatenate([(at // 8 + (at % 8 >= 5)) % 5, [1, 1, 2, 2]]).astype(np.int64)     # runs along the rows: `class` mode keeps edges
+    return np.stack([cx - 3, cy - 2, cx + 3, cy + 2], 1), lab
+
+
+def test_the_loop_of_the_slide_path_runs_all_six_on_one_set_of_boxes(hip_device, tmp_path):
+    """slidepoints.run, as tools/infer_wsi.py calls it, with every analysis selected at a radius of 10 px (not a default) and `class` mode
+    where there is one: exactly the six files, one header, each file's integers equal to its module's reference on the file's own xy and
+    label, the clauses in table order; and a selection of the last entry alone writes one file."""
+    boxes, lab = _placed_boxes()
+    rows = 2 * np.arange(len(lab), dtype=np.int64) + 1
+    args = argparse.Namespace(nuclei_graph=True, graph_radius=10.0, graph_k=3, nuclei_spatial=True, spatial_step=2.5, spatial_bins=4,
+                              nuclei_clusters=True, cluster_radius=10.0, cluster_min=2, cluster_by='class', nuclei_mst=True, mst_radius=10.0,
+                              mst_by='class', nuclei_proximity=True, proximity_radius=10.0, proximity_by='class', nuclei_density=True,
+                              density_bandwidth=10.0, density_pitch=7.5)
+    chosen = slidepoints.select(args)
+    assert [an for an, _ in chosen] == list(slidepoints.ANALYSES)
+    all_dir, one_dir = tmp_path / 'all', tmp_path / 'one'
+    os.makedirs(all_dir), os.makedirs(one_dir)
+    said = slidepoints.run(chosen, rows, boxes, lab, 5, str(all_dir), 't', 0, dict(tiles_area_px=6 * 48.0 ** 2))
+    assert sorted(os.listdir(all_dir)) == sorted('t' + an.suffix for an in slidepoints.ANALYSES)
+    assert len(said) == 6 and all(clause.endswith(f' in t{an.suffix}') for clause, an in zip(said, slidepoints.ANALYSES)), said
+    z = {an.module: slidepoints.module_of(an).read_npz(str(all_dir / ('t' + an.suffix))) for an in slidepoints.ANALYSES}
+    xy = np.stack([(boxes[:, 0] + boxes[:, 2]) / 2, (boxes[:, 1] + boxes[:, 3]) / 2], 1)
+    for name, f in z.items():
+        assert np.array_equal(f['nuclei_id'], rows) and np.array_equal(f['xy'], xy) and np.array_equal(f['label'], lab), name
+        assert f['nuclei_id'].dtype == np.int64 and f['xy'].dtype == np.float64 and f['label'].dtype == np.int64, name
+    p = np.rint(2 * xy).astype(np.int32)
+    assert (p % 2 == 1).any() and np.array_equal(p[56], p[57]) and ((p[58] - p[59]) ** 2).sum() == 20 * 20      # the set is what it says
+
+    def same(name, got, want):
+        assert len(got) == len(want), name
+        for i, (g, w) in enumerate(zip(got, want)):
+            assert np.asarray(g).dtype == np.asarray(w).dtype and np.array_equal(g, w), (name, i)
+    nb, d2, cc = cg.graph_reference(p, lab, 5, 20, 3)
+    same('graph', [z['cellgraph'][k] for k in ('neighbors', 'dist', 'class_count')], [nb, cg.distances_px(d2), cc])
+    edges = sp.edges_from_step(2.5, 4)
+    same('spatial', [z['spatial'][k] for k in ('pair_hist', 'nn_d2', 'class_n')], sp.spatial_reference(p, lab, 5, edges))
+    assert float(z['spatial']['tiles_area_px']) == 6 * 48.0 ** 2 and z['spatial']['edges_px'].tolist() == [2.5, 5.0, 7.5, 10.0]
+    same('clusters', [z['clusters'][k] for k in cl.INT_NAMES], cl.cluster_reference(p, lab, 5, 20, 2, 1))
+    want = mst.mst_reference(p, lab, 5, 20, 1)
+    same('mst', [z['mst'][k] for k in mst.INT_NAMES], want[:3])
+    assert (int(z['mst']['n_edges']), int(z['mst']['n_trees'])) == want[3:]
+    forest = {tuple(e): int(d) for e, d in zip(z['mst']['edges'].tolist(), z['mst']['edge_d2'].tolist())}
+    assert forest[(56, 57)] == 0 and forest[(58, 59)] == 400                  # the coincident pair, and the pair AT the radius: inclusive
+    want = proximity.proximity_reference(p, lab, 5, 20, 1)
+    same('proximity', [z['proximity'][k] for k in proximity.INT_NAMES], want[:4])
+    assert (int(z['proximity']['n_edges']), int(z['proximity']['n_rng'])) == want[4:]
+    win = tuple(int(v) for v in z['density']['window'])
+    assert win == density.window((int(p[:, 0].min()), int(p[:, 1].min()), int(p[:, 0].max()), int(p[:, 1].max())), 20, 15)
+    same('density', [z['density'][k] for k in density.INT_NAMES], density.density_reference(p, lab, 5, 20, 15, win))
+    assert len(z['clusters']['size']) > 1 and (z['clusters']['cluster'] < 0).any() and int(z['mst']['n_edges']) > 10 and int(z['proximity']['n_edges']) > 10
+    assert int(z['clusters']['by_class']) == int(z['mst']['by_class']) == int(z['proximity']['by_class']) == 1
+    last = slidepoints.run(chosen[-1:], rows, boxes, lab, 5, str(one_dir), 't', 0, dict(tiles_area_px=6 * 48.0 ** 2))
+    assert os.listdir(one_dir) == ['t' + slidepoints.ANALYSES[-1].suffix] and last == said[-1:]
+    assert open(one_dir / 't_nuclei_density.npz', 'rb').read() == open(all_dir / 't_nuclei_density.npz', 'rb').read()

@@ -6,8 +6,6 @@ out of range, pitch against reach, other windows, a binning over two scan chunks
 the edge sizes, the refused arguments, and tools/infer_wsi.py --nuclei-density end to end.  The designed sets of tests/density_cases.py
 reach both kernels (staged through LDS, and every site on its own); which one ran is read from the library's profile."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,13 +13,11 @@ import torch
 
 import density_cases as DC
 import proximity_cases as PC
+import points_util
 from nuhtc_amd import cellgraph, cellpoints, hip
 from nuhtc_amd import density as dn
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CFG = os.path.join(ROOT, 'configs', 'nuhtc', 'htc_lite_swin_pannuke_infer.py')
-TOOL = os.path.join(ROOT, 'tools', 'infer_wsi.py')
 FAR = (((1 << 26) + 12345, -(1 << 26) - 321), (-(1 << 26) - 7, (1 << 26) + 50001))
 
 
@@ -252,11 +248,7 @@ def test_the_last_accepted_site_and_points_outside_the_box(hip_device):
 
 
 # ---- 12: the tool
-def _run(cmd, env=None, limit=300):
-    p = subprocess.run(['timeout', '-k', '10', str(limit), sys.executable, TOOL] + cmd, env=env, cwd=ROOT, capture_output=True, text=True)
-    print(p.stdout[-2000:], p.stderr[-2000:])
-    assert p.returncode == 0, p.returncode
-    return p.stdout
+_run = points_util.run_tool
 
 
 def test_cli_nuclei_density(hip_device, tmp_path):
@@ -264,18 +256,8 @@ def test_cli_nuclei_density(hip_device, tmp_path):
     rank and on two (three runs of the tool): the folder gains exactly the one file, every other file is the same bytes as without the
     flag, the rows are those of <id>_nuclei_graph.npz, the integers equal density_reference on the file's own xy and label, and every
     derived key equals `derive` of them."""
-    from nuhtc_amd import synth, weights
-    ck = tmp_path / 'w.pth'
-    torch.save(dict(state_dict=weights.bench_state_dict(0, obj_bias=0.0)), ck)
-    slide = np.concatenate([np.concatenate(list(synth.nuclei_tiles(5, 64, start=r * 5)), 1) for r in range(3)], 0)    # 192 x 320
-    np.save(tmp_path / 's1.npy', slide)
-    base = [str(tmp_path / 's1.npy'), CFG, str(ck), '--patch_size', '64', '--step_size', '48', '--batch_size', '8', '--mode', 'qupath', '--nuclei-graph']
+    base, env, two, folder = points_util.slide_runs(tmp_path, '--nuclei-graph')
     flags = ['--nuclei-density', '--density-bandwidth', '20', '--density-pitch', '7.5']
-    env = dict(os.environ, NUHTC_HOST_AFFINITY='0')
-    two = dict(env, NUHTC_ONE_DEVICE='1', NUHTC_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0', OMP_NUM_THREADS='4')
-    for key in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
-        two.pop(key, None)
-    folder = lambda d: tmp_path / d / 'nuclei' / 's1'
     files = lambda d: {f: open(folder(d) / f, 'rb').read() for f in sorted(os.listdir(folder(d)))}
     _run(base + ['--save_dir', str(tmp_path / 'merge0'), '--merge'], env)
     _run(base + flags + ['--save_dir', str(tmp_path / 'merge'), '--merge'], env)

@@ -7,21 +7,17 @@ and the radius, the lattice, witnesses across cell borders, the two label modes,
 many ties, the cap path, bitwise repeatability, permuted rows, the forest kernel as a cross-check, the refused arguments, and
 tools/infer_wsi.py --nuclei-proximity end to end."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import proximity_cases as PC
+import points_util
 from nuhtc_amd import cellgraph, hip, mst
 from nuhtc_amd import proximity as px
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CFG = os.path.join(ROOT, 'configs', 'nuhtc', 'htc_lite_swin_pannuke_infer.py')
-TOOL = os.path.join(ROOT, 'tools', 'infer_wsi.py')
 NAMES = px.INT_NAMES + ('m', 'm_rng')
 
 
@@ -194,29 +190,15 @@ def test_a_point_outside_the_stated_box_is_refused(hip_device):
 
 
 # ---- 5: the tool
-def _run(cmd, env=None, limit=300):
-    p = subprocess.run(['timeout', '-k', '10', str(limit), sys.executable, TOOL] + cmd, env=env, cwd=ROOT, capture_output=True, text=True)
-    print(p.stdout[-2000:], p.stderr[-2000:])
-    assert p.returncode == 0, p.returncode
-    return p.stdout
+_run = points_util.run_tool
 
 
 def test_cli_nuclei_proximity(hip_device, tmp_path):
     """tools/infer_wsi.py --nuclei-graph --nuclei-proximity on the synthetic .npy slide of tests/test_hip_clusters.py, with --merge on one
     rank and on two (three runs of the tool, to keep the test short): the folder gains exactly the one file, every other file is the same bytes as without the flag, the rows are those of
     <id>_nuclei_graph.npz, and the integers equal proximity_reference on the file's own xy and label."""
-    from nuhtc_amd import synth, weights
-    ck = tmp_path / 'w.pth'
-    torch.save(dict(state_dict=weights.bench_state_dict(0, obj_bias=0.0)), ck)
-    slide = np.concatenate([np.concatenate(list(synth.nuclei_tiles(5, 64, start=r * 5)), 1) for r in range(3)], 0)    # 192 x 320
-    np.save(tmp_path / 's1.npy', slide)
-    base = [str(tmp_path / 's1.npy'), CFG, str(ck), '--patch_size', '64', '--step_size', '48', '--batch_size', '8', '--mode', 'qupath', '--nuclei-graph']
+    base, env, two, folder = points_util.slide_runs(tmp_path, '--nuclei-graph')
     flags = ['--nuclei-proximity', '--proximity-radius', '20', '--proximity-by', 'class']
-    env = dict(os.environ, NUHTC_HOST_AFFINITY='0')
-    two = dict(env, NUHTC_ONE_DEVICE='1', NUHTC_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0', OMP_NUM_THREADS='4')
-    for key in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
-        two.pop(key, None)
-    folder = lambda d: tmp_path / d / 'nuclei' / 's1'
     files = lambda d: {f: open(folder(d) / f, 'rb').read() for f in sorted(os.listdir(folder(d)))}
     _run(base + ['--save_dir', str(tmp_path / 'merge0'), '--merge'], env)
     _run(base + flags + ['--save_dir', str(tmp_path / 'merge'), '--merge'], env)

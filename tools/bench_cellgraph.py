@@ -23,6 +23,10 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import bench_points as bp  # noqa: E402
+from bench_points import med  # noqa: E402
 
 
 def main(argv=None):
@@ -39,40 +43,19 @@ def main(argv=None):
     import torch
     from scipy.spatial import cKDTree
     from nuhtc_amd import cellgraph as cg
-    from nuhtc_amd import cellpoints
-    from nuhtc_amd import hip
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_cellgraph.py needs a GPU (there is no fallback)')
+    bp.need_gpu('bench_cellgraph.py')
     n, k, C = args.n, args.k, args.classes
     r = cg.half_pixel_radius(args.radius)
     rng = np.random.default_rng(0)
     pts = rng.integers(0, 2 * args.extent, (n, 2)).astype(np.int32)
     lab = rng.integers(0, C, n).astype(np.int32)
-    dev = torch.device('cuda', 0)
-    bounds = cellpoints.bounds_of(pts)
-    p_d, l_d = torch.from_numpy(pts).to(dev), torch.from_numpy(lab).to(dev)
+    dev, bounds, p_d, l_d = bp.resident(pts, lab)
     out = [torch.full((n, w), -1, dtype=torch.int32, device=dev) for w in (k, k, C)]
-    ms = []
-    for i in range(args.warmup + args.repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        rc = cg.call(p_d, l_d, C, r, k, *out, bounds=bounds)
-        e1.record()
-        torch.cuda.synchronize()
-        if rc:
-            raise SystemExit(f'nuhtc_cell_graph failed ({rc})')
-        if i >= args.warmup:
-            ms.append(e0.elapsed_time(e1))
-    hip.profile_enable(True)                                  # one more call for the split between the two stages (events around each)
-    cg.call(p_d, l_d, C, r, k, *out, bounds=bounds)
-    stages = {tag: round(v['ms'], 3) for tag, v in hip.profile_read().items() if tag.startswith('cell_graph')}
-    hip.profile_enable(False)
+    graph_call = lambda: cg.call(p_d, l_d, C, r, k, *out, bounds=bounds)
+    ms = bp.timed(graph_call, args.repeats, args.warmup)
+    stages = bp.stage_split(graph_call, 'cell_graph')
     nb_dev = out[0].cpu().numpy()
-    e2e = []
-    for i in range(3):
-        t0 = time.perf_counter()
-        got = cg.build(pts, lab, C, args.radius, k)
-        e2e.append(1e3 * (time.perf_counter() - t0))
+    e2e, got = bp.end_to_end(lambda: cg.build(pts, lab, C, args.radius, k))
     same = bool(np.array_equal(got[0], nb_dev))
     # ---- the host route on the same points (px, float64)
     xy = pts.astype(np.float64) / 2
@@ -85,17 +68,13 @@ def main(argv=None):
         dist, idx = tree.query(xy, k=k + 1, distance_upper_bound=args.radius * (1 + 1e-12), workers=w)
         host[w] = time.perf_counter() - t0
     edges_host = int(np.isfinite(dist[:, 1:]).sum())
-    med = lambda v: float(np.median(v))
     w_hi = max(host)
     out_line = dict(what=f'tools/bench_cellgraph.py: cell graph of {n} synthetic nucleus centres uniform on a {args.extent}-px square '
                          f'(one per {args.extent ** 2 / n:.0f} px^2), radius {args.radius:g} px, k {k}, {C} classes, one MI355X; device: '
                          f'{args.repeats} calls after {args.warmup} warm-up calls; host: scipy cKDTree build + query(k + 1, distance_upper_bound)',
                     n=n, extent_px=args.extent, px2_per_nucleus=round(args.extent ** 2 / n, 1), radius_px=args.radius, k=k, classes=C,
                     mean_neighbours_within_radius=round(float(out[2].sum().item()) / n, 3), edges_device=int((nb_dev >= 0).sum()), edges_host=edges_host,
-                    device_ms=[round(v, 3) for v in ms], device_ms_median=round(med(ms), 3),
-                    device_stage_ms=stages,
-                    device_end_to_end_ms=[round(v, 2) for v in e2e], device_end_to_end_ms_median=round(med(e2e), 2),
-                    device_calls_agree=same,
+                    **bp.device_columns(ms, stages, e2e, same),
                     host_tree_build_ms=round(1e3 * t_build, 1), host_query_ms_1_worker=round(1e3 * host[1], 1),
                     **{f'host_query_ms_{w_hi}_workers': round(1e3 * host[w_hi], 1)},
                     host_total_ms_1_worker=round(1e3 * (t_build + host[1]), 1), host_total_ms_best=round(1e3 * (t_build + min(host.values())), 1),

@@ -4,7 +4,7 @@
 
     python tools/bench_clusters.py [--n 500000] [--extent 36000] [--radius 32] [--min-pts 5] [--by any] [--classes 5] [--repeats 10] [--warmup 3]
 
-Synthetic nucleus centres from the generator of tools/bench_spatial.py: `--n` points uniform on a square of `--extent` px, and one CLUSTERED
+Synthetic nucleus centres from the generator of tools/bench_points.py: `--n` points uniform on a square of `--extent` px, and one CLUSTERED
 set of the same size (400 Gaussian clumps, sigma 300 px).  For each set:
   device_ms            nuhtc_cell_clusters alone, between two events, points and outputs resident on the device (every stage, its own scratch
                        allocation and final synchronisation included: it is one blocking call), `--repeats` after `--warmup`
@@ -16,8 +16,6 @@ set of the same size (400 Gaussian clumps, sigma 300 px).  For each set:
                        partition are the device's
   checked_against_reference  a window of the points small enough for brute force, through the device again, against clusters.cluster_reference
 bench.py is the project's headline benchmark and is not changed by this tool."""
-import argparse
-import json
 import os
 import sys
 import time
@@ -27,67 +25,35 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import bench_points as bp  # noqa: E402
+from bench_points import med  # noqa: E402
+
 
 def measure(name, pts, lab, C, r, args):
-    import torch
-    from nuhtc_amd import cellgraph as cg
-    from nuhtc_amd import cellpoints
     from nuhtc_amd import clusters as cl
-    from nuhtc_amd import hip
     n, by = len(pts), cl.BY[args.by]
-    dev = torch.device('cuda', 0)
-    bounds = cellpoints.bounds_of(pts)
-    p_d, l_d = torch.from_numpy(pts).to(dev), torch.from_numpy(lab).to(dev)
+    dev, bounds, p_d, l_d = bp.resident(pts, lab)
     out = cl.outputs(n, C, dev)
-    gout = [torch.full((n, w), -1, dtype=torch.int32, device=dev) for w in (8, 8, C)]
     found = {}
 
     def clusters_call():
         rc, found['m'] = cl.call(p_d, l_d, C, r, args.min_pts, by, *out, bounds=bounds)
         return rc
-
-    def timed(fn):
-        ms = []
-        for i in range(args.warmup + args.repeats):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            rc = fn()
-            e1.record()
-            torch.cuda.synchronize()
-            if rc:
-                raise SystemExit(f'the device call failed ({rc})')
-            if i >= args.warmup:
-                ms.append(e0.elapsed_time(e1))
-        return ms
-    ms = timed(clusters_call)
-    gms = timed(lambda: cg.call(p_d, l_d, C, r, 8, *gout, bounds=bounds))
-    hip.profile_enable(True)                                  # one more call for the split between the stages (events around each)
-    clusters_call()
-    stages = {tag: round(v['ms'], 3) for tag, v in hip.profile_read().items() if tag.startswith('cell_clusters')}
-    hip.profile_enable(False)
+    ms = bp.timed(clusters_call, args.repeats, args.warmup)
+    gms = bp.graph_yardstick(p_d, l_d, C, r, bounds, args)
+    stages = bp.stage_split(clusters_call, 'cell_clusters')
     m = found['m']
     dev_out = [t.cpu().numpy() for t in out[:3]] + [t[:m].cpu().numpy() for t in out[3:]]
-    e2e = []
-    for i in range(3):
-        t0 = time.perf_counter()
-        got = cl.build(pts, lab, C, r / 2, args.min_pts, by)
-        e2e.append(1e3 * (time.perf_counter() - t0))
+    e2e, got = bp.end_to_end(lambda: cl.build(pts, lab, C, r / 2, args.min_pts, by))
     same = bool(all(np.array_equal(a, b) for a, b in zip(got, dev_out)))
     # ---- a window small enough for brute force, through the device again and against the definition
-    lo = np.array([bounds[0], bounds[1]])
-    side = int(2 * args.extent * np.sqrt(min(1.0, args.check_n / max(n, 1))))
-    win = ((pts - lo) < side).all(1)
-    if win.sum() > 2 * args.check_n:                          # a dense corner of the clustered set
-        win &= np.cumsum(win) <= 2 * args.check_n
+    win = bp.brute_window(pts, bounds, args.extent, args.check_n)
     sub = cl.build(pts[win], lab[win], C, r / 2, args.min_pts, by)
     exact = bool(all(np.array_equal(a, b) for a, b in zip(sub, cl.cluster_reference(pts[win], lab[win], C, r, args.min_pts, by))))
-    med = lambda v: float(np.median(v))
     cluster, core = dev_out[0], dev_out[1].astype(bool)
     line = dict(points=name, n=n, clusters=int(m), largest_cluster=int(dev_out[3].max()) if m else 0, core=int(core.sum()),
                 border=int(((cluster >= 0) & ~core).sum()), noise=int((cluster < 0).sum()), mean_degree=round(float(dev_out[2].mean()), 2),
-                device_ms=[round(v, 3) for v in ms], device_ms_median=round(med(ms), 3), device_stage_ms=stages,
-                device_end_to_end_ms=[round(v, 2) for v in e2e], device_end_to_end_ms_median=round(med(e2e), 2), device_calls_agree=same,
-                graph_ms=[round(v, 3) for v in gms], graph_ms_median=round(med(gms), 3), device_over_graph=round(med(ms) / med(gms), 2),
+                **bp.device_columns(ms, stages, e2e, same), **bp.graph_columns(gms, ms),
                 checked_points=int(win.sum()), checked_against_reference=exact)
     # ---- the host: scikit-learn on the same points in px
     try:
@@ -113,32 +79,21 @@ def measure(name, pts, lab, C, r, args):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--n', type=int, default=500000)
-    ap.add_argument('--extent', type=int, default=36000, help='side of the square the centres are drawn on, px')
+    ap = bp.parser()
     ap.add_argument('--radius', type=float, default=32.0, help='px')
     ap.add_argument('--min-pts', type=int, default=5, dest='min_pts')
     ap.add_argument('--by', choices=('any', 'class'), default='any')
-    ap.add_argument('--classes', type=int, default=5)
-    ap.add_argument('--repeats', type=int, default=10)
-    ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--check-n', type=int, default=3000, dest='check_n', help='about how many points the brute-force check takes')
     args = ap.parse_args(argv)
-    import torch
-    from bench_spatial import point_sets
     from nuhtc_amd import clusters as cl
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_clusters.py needs a GPU (there is no fallback)')
+    bp.need_gpu('bench_clusters.py')
     C, r = args.classes, cl.half_pixel_radius(args.radius)
     cl.check_args(C, r, args.min_pts, cl.BY[args.by])
-    sets = [measure(name, p, lab, C, r, args) for name, (p, lab) in point_sets(args.n, args.extent, C).items()]
+    sets = [measure(name, p, lab, C, r, args) for name, (p, lab) in bp.point_sets(args.n, args.extent, C).items()]
     line = dict(what=f'tools/bench_clusters.py: DBSCAN clusters of {args.n} synthetic nucleus centres on a {args.extent}-px square, radius {args.radius:g} px, '
                      f'min_pts {args.min_pts}, by {args.by}, {C} classes, one MI355X; device: {args.repeats} calls after {args.warmup} warm-up calls; '
                      f'yardstick: nuhtc_cell_graph k 8 at the same radius; host: sklearn.cluster.DBSCAN',
                 n=args.n, extent_px=args.extent, radius_px=args.radius, min_pts=args.min_pts, by=args.by, classes=C, sets=sets)
-    print(json.dumps(line))
-    if not all(s['device_calls_agree'] and s['checked_against_reference'] and s.get('sklearn_core_noise_and_core_partition_agree', True) for s in sets):
-        raise SystemExit('a check failed: see device_calls_agree / checked_against_reference / sklearn_core_noise_and_core_partition_agree')
+    bp.report(line, ('device_calls_agree', 'checked_against_reference', 'sklearn_core_noise_and_core_partition_agree'))
 
 
 if __name__ == '__main__':

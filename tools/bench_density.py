@@ -5,7 +5,7 @@
     python tools/bench_density.py [--n 1000000] [--extent 50000] [--bandwidth 128] [--pitch 64] [--classes 5] [--repeats 10] [--warmup 3]
                                   [--also LABEL=path/to/libnuhtc_hip.so ...] [--rounds 2] [--more-shapes]
 
-Synthetic nucleus centres from the generator of tools/bench_spatial.py: `--n` points uniform on a square of `--extent` px, and one CLUSTERED
+Synthetic nucleus centres from the generator of tools/bench_points.py: `--n` points uniform on a square of `--extent` px, and one CLUSTERED
 set of the same size (400 Gaussian clumps, sigma 300 px), at the defaults of tools/infer_wsi.py --nuclei-density.  For each set:
   device_ms            nuhtc_cell_density alone, between two events, points and outputs resident on the device, the default window (every
                        stage, its own scratch allocation and the final synchronisation included: it is one blocking call), `--repeats`
@@ -22,9 +22,7 @@ set of the same size (400 Gaussian clumps, sigma 300 px), at the defaults of too
 With --more-shapes the shipped and the --also builds are timed at further (bandwidth, pitch) pairs on the uniform set: where the rule that
 picks the kernel (dens_route_staged of csrc/cellgrid_host.h) has to hold.  bench.py is the project's headline benchmark and is not changed
 by this tool."""
-import argparse
 import ctypes
-import json
 import os
 import sys
 import time
@@ -33,6 +31,9 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import bench_points as bp  # noqa: E402
+from bench_points import med, timed  # noqa: E402
 
 
 def host_route(pts, lab, C, h, s, win):
@@ -53,25 +54,6 @@ def host_route(pts, lab, C, h, s, win):
             np.add.at(count, at, 1)
             np.add.at(weight, at, h * h - d2[hit])
     return count.astype(np.int32), weight, 1e3 * (time.perf_counter() - t0)
-
-
-def timed(fn, repeats, warmup):
-    import torch
-    ms = []
-    for i in range(warmup + repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        rc = fn()
-        e1.record()
-        torch.cuda.synchronize()
-        if rc:
-            raise SystemExit(f'the device call failed ({rc})')
-        if i >= warmup:
-            ms.append(e0.elapsed_time(e1))
-    return ms
-
-
-med = lambda v: float(np.median(v))
 
 
 def variant_calls(also, p_d, l_d, n, C, h, s, win, bounds, dev):
@@ -97,21 +79,15 @@ def rounds_of(calls, args):
 
 def measure(name, pts, lab, C, h, s, args, also):
     import torch
-    from nuhtc_amd import cellpoints, hip
     from nuhtc_amd import density as dn
     n = len(pts)
-    dev = torch.device('cuda', 0)
-    bounds = cellpoints.bounds_of(pts)
+    dev, bounds, p_d, l_d = bp.resident(pts, lab)
     win = dn.window(bounds, h, s)
-    p_d, l_d = torch.from_numpy(pts).to(dev), torch.from_numpy(lab).to(dev)
     out = dn.outputs(C, win, dev)
     shipped = lambda: dn.call(p_d, l_d, C, h, s, win, *out, bounds=bounds)
     ms = timed(shipped, args.repeats, args.warmup)
     count, weight = out[0].cpu().numpy(), out[1].cpu().numpy()
-    hip.profile_enable(True)                                  # one more call for the split between the stages (events around each)
-    shipped()
-    stages = {tag: round(v['ms'], 3) for tag, v in hip.profile_read().items() if tag.startswith('cell_density')}
-    hip.profile_enable(False)
+    stages = bp.stage_split(shipped, 'cell_density')
     variants = {}
     if also:
         calls = {'shipped': shipped}
@@ -124,11 +100,7 @@ def measure(name, pts, lab, C, h, s, args, also):
         variants['shipped'] = {}
         for label, v in rounds_of(calls, args).items():
             variants[label]['ms'] = v
-    e2e = []
-    for i in range(3):
-        t0 = time.perf_counter()
-        got = dn.build(pts, lab, C, h / 2, s / 2)
-        e2e.append(1e3 * (time.perf_counter() - t0))
+    e2e, got = bp.end_to_end(lambda: dn.build(pts, lab, C, h / 2, s / 2))
     same = bool(np.array_equal(got[0], count) and np.array_equal(got[1], weight) and got[2] == win)
     # ---- a sub-window small enough for brute force, through the device again and against the definition
     sub = (win[0] + win[2] // 3, win[1] + win[3] // 3, min(40, win[2]), min(30, win[3]))
@@ -143,8 +115,7 @@ def measure(name, pts, lab, C, h, s, args, also):
     agree = bool(np.array_equal(hc, count) and np.array_equal(hw, weight))
     return dict(points=name, n=n, window=list(win), sites=int(win[2] * win[3]), class_total=count.reshape(C, -1).sum(1).tolist(),
                 mean_count_per_site=round(float(count.sum()) / (win[2] * win[3]), 2),
-                device_ms=[round(v, 3) for v in ms], device_ms_median=round(med(ms), 3), device_stage_ms=stages,
-                device_end_to_end_ms=[round(v, 2) for v in e2e], device_end_to_end_ms_median=round(med(e2e), 2), device_calls_agree=same,
+                **bp.device_columns(ms, stages, e2e, same),
                 variants=variants, checked_sites=int(sub[2] * sub[3]), checked_points=int(near.sum()), checked_against_reference=exact,
                 host_ms=round(host_ms, 1), host_over_device_call=round(host_ms / med(ms), 1), host_over_device_end_to_end=round(host_ms / med(e2e), 1),
                 host_rasters_agree=agree)
@@ -153,11 +124,8 @@ def measure(name, pts, lab, C, h, s, args, also):
 def more_shapes(pts, lab, C, args, also):
     """The shipped and the --also builds at further (bandwidth, pitch) pairs in px on one set: the rule against the measurement."""
     import torch
-    from nuhtc_amd import cellpoints, hip
     from nuhtc_amd import density as dn
-    dev = torch.device('cuda', 0)
-    bounds = cellpoints.bounds_of(pts)
-    p_d, l_d = torch.from_numpy(pts).to(dev), torch.from_numpy(lab).to(dev)
+    dev, bounds, p_d, l_d = bp.resident(pts, lab)
     rows = []
     for bw, pitch in ((128, 32), (128, 16), (128, 8), (64, 64), (32, 4), (16, 64)):
         h, s = dn.half_pixel_radius(bw), dn.half_pixel_radius(pitch)
@@ -166,10 +134,7 @@ def more_shapes(pts, lab, C, args, also):
             continue
         out = dn.outputs(C, win, dev)
         shipped = lambda: dn.call(p_d, l_d, C, h, s, win, *out, bounds=bounds)
-        hip.profile_enable(True)
-        shipped()
-        took = sorted(tag for tag in hip.profile_read() if tag in ('cell_density_tile', 'cell_density_site'))
-        hip.profile_enable(False)
+        took = sorted(tag for tag in bp.stage_split(shipped, 'cell_density_') if tag in ('cell_density_tile', 'cell_density_site'))
         calls = {'shipped': shipped}
         same = {}
         for label, (call, vout) in variant_calls(also, p_d, l_d, len(pts), C, h, s, win, bounds, dev).items():
@@ -183,34 +148,19 @@ def more_shapes(pts, lab, C, args, also):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--n', type=int, default=1000000)
-    ap.add_argument('--extent', type=int, default=50000, help='side of the square the centres are drawn on, px')
+    ap = bp.parser(n=1000000, extent=50000, check_n=False)
     ap.add_argument('--bandwidth', type=float, default=128.0, help='px')
     ap.add_argument('--pitch', type=float, default=64.0, help='px')
-    ap.add_argument('--classes', type=int, default=5)
-    ap.add_argument('--repeats', type=int, default=10)
-    ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--also', action='append', default=[], metavar='LABEL=LIB', help='another build of the library to time in alternating rounds')
     ap.add_argument('--rounds', type=int, default=2, help='alternating rounds of the shipped library and the --also builds')
     ap.add_argument('--more-shapes', action='store_true', dest='more_shapes', help='time further (bandwidth, pitch) pairs on the uniform set')
     args = ap.parse_args(argv)
-    import torch
-    from bench_spatial import point_sets
-    from nuhtc_amd import hip
     from nuhtc_amd import density as dn
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_density.py needs a GPU (there is no fallback)')
+    bp.need_gpu('bench_density.py')
     C, h, s = args.classes, dn.half_pixel_radius(args.bandwidth), dn.half_pixel_radius(args.pitch)
     dn.check_args(C, h, s)
-    shipped = hip.load().nuhtc_cell_density
-    also = {}
-    for spec in args.also:
-        label, path = spec.split('=', 1)
-        fn = ctypes.CDLL(os.path.abspath(path)).nuhtc_cell_density
-        fn.argtypes, fn.restype = shipped.argtypes, shipped.restype
-        also[label] = fn
-    point = point_sets(args.n, args.extent, C)
+    also = bp.also_builds(args.also, 'nuhtc_cell_density')
+    point = bp.point_sets(args.n, args.extent, C)
     sets = [measure(name, p, lab, C, h, s, args, also) for name, (p, lab) in point.items()]
     line = dict(what=f'tools/bench_density.py: class-wise density maps of {args.n} synthetic nucleus centres on a {args.extent}-px square, bandwidth '
                      f'{args.bandwidth:g} px, pitch {args.pitch:g} px, {C} classes, one MI355X; device: {args.repeats} calls after {args.warmup} warm-up '
@@ -219,12 +169,9 @@ def main(argv=None):
                 n=args.n, extent_px=args.extent, bandwidth_px=args.bandwidth, pitch_px=args.pitch, classes=C, sets=sets)
     if args.more_shapes:
         line['more_shapes_uniform'] = more_shapes(*point['uniform'], C, args, also)
-    print(json.dumps(line))
-    ok = all(s_['device_calls_agree'] and s_['checked_against_reference'] and s_['host_rasters_agree']
-             and all(v.get('equals_shipped', True) for v in s_['variants'].values()) for s_ in sets)
-    ok = ok and all(all(r['equals_shipped'].values()) for r in line.get('more_shapes_uniform', []))
-    if not ok:
-        raise SystemExit('a check failed: see device_calls_agree / checked_against_reference / host_rasters_agree / equals_shipped')
+    same = [v.get('equals_shipped', True) for s_ in sets for v in s_['variants'].values()]
+    same += [ok for r in line.get('more_shapes_uniform', []) for ok in r['equals_shipped'].values()]
+    bp.report(line, ('device_calls_agree', 'checked_against_reference', 'host_rasters_agree'), (('equals_shipped', all(same)),))
 
 
 if __name__ == '__main__':

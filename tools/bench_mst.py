@@ -4,7 +4,7 @@
 
     python tools/bench_mst.py [--n 500000] [--extent 36000] [--radius 64] [--by any] [--classes 5] [--repeats 10] [--warmup 3]
 
-Synthetic nucleus centres from the generator of tools/bench_spatial.py: `--n` points uniform on a square of `--extent` px, and one CLUSTERED
+Synthetic nucleus centres from the generator of tools/bench_points.py: `--n` points uniform on a square of `--extent` px, and one CLUSTERED
 set of the same size (400 Gaussian clumps, sigma 300 px).  For each set:
   device_ms            nuhtc_cell_mst alone, between two events, points and outputs resident on the device (every stage, its own scratch
                        allocation, the one int read back per round and the final synchronisation included: it is one blocking call),
@@ -18,8 +18,6 @@ set of the same size (400 Gaussian clumps, sigma 300 px).  For each set:
                        under ties scipy's forest may be another one of the same weight.  Skipped with a note when scipy is not importable.
   checked_against_reference  a window of the points small enough for brute force, through the device again, against mst.mst_reference
 bench.py is the project's headline benchmark and is not changed by this tool."""
-import argparse
-import json
 import os
 import sys
 import time
@@ -29,65 +27,35 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import bench_points as bp  # noqa: E402
+from bench_points import med  # noqa: E402
+
 
 def measure(name, pts, lab, C, r, args):
-    import torch
-    from nuhtc_amd import cellgraph as cg
-    from nuhtc_amd import cellpoints, hip, mst
+    from nuhtc_amd import mst
     n, by = len(pts), mst.BY[args.by]
-    dev = torch.device('cuda', 0)
-    bounds = cellpoints.bounds_of(pts)
-    p_d, l_d = torch.from_numpy(pts).to(dev), torch.from_numpy(lab).to(dev)
+    dev, bounds, p_d, l_d = bp.resident(pts, lab)
     out = mst.outputs(n, dev)
-    gout = [torch.full((n, w), -1, dtype=torch.int32, device=dev) for w in (8, 8, C)]
     found = {}
 
     def mst_call():
         rc, found['m'], found['T'], found['rounds'] = mst.call(p_d, l_d, C, r, by, *out, bounds=bounds)
         return rc
-
-    def timed(fn):
-        ms = []
-        for i in range(args.warmup + args.repeats):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            rc = fn()
-            e1.record()
-            torch.cuda.synchronize()
-            if rc:
-                raise SystemExit(f'the device call failed ({rc})')
-            if i >= args.warmup:
-                ms.append(e0.elapsed_time(e1))
-        return ms
-    ms = timed(mst_call)
-    gms = timed(lambda: cg.call(p_d, l_d, C, r, 8, *gout, bounds=bounds))
-    hip.profile_enable(True)                                  # one more call for the split between the stages (events around each)
-    mst_call()
-    stages = {tag: round(v['ms'], 3) for tag, v in hip.profile_read().items() if tag.startswith('cell_mst')}
-    hip.profile_enable(False)
+    ms = bp.timed(mst_call, args.repeats, args.warmup)
+    gms = bp.graph_yardstick(p_d, l_d, C, r, bounds, args)
+    stages = bp.stage_split(mst_call, 'cell_mst')
     m = found['m']
     dev_out = [out[0][:m].cpu().numpy(), out[1][:m].cpu().numpy(), out[2].cpu().numpy()]
-    e2e = []
-    for i in range(3):
-        t0 = time.perf_counter()
-        got = mst.build(pts, lab, C, r / 2, by)
-        e2e.append(1e3 * (time.perf_counter() - t0))
+    e2e, got = bp.end_to_end(lambda: mst.build(pts, lab, C, r / 2, by))
     same = bool(all(np.array_equal(a, b) for a, b in zip(got[:3], dev_out)) and got[3:] == (m, found['T']))
     # ---- a window small enough for brute force, through the device again and against the definition
-    lo = np.array([bounds[0], bounds[1]])
-    side = int(2 * args.extent * np.sqrt(min(1.0, args.check_n / max(n, 1))))
-    win = ((pts - lo) < side).all(1)
-    if win.sum() > 2 * args.check_n:                          # a dense corner of the clustered set
-        win &= np.cumsum(win) <= 2 * args.check_n
+    win = bp.brute_window(pts, bounds, args.extent, args.check_n)
     sub, ref = mst.build(pts[win], lab[win], C, r / 2, by), mst.mst_reference(pts[win], lab[win], C, r, by)
     exact = bool(all(np.array_equal(a, b) for a, b in zip(sub[:3], ref[:3])) and sub[3:] == ref[3:])
-    med = lambda v: float(np.median(v))
     total_d2 = int(dev_out[1].astype(np.int64).sum())
     line = dict(points=name, n=n, m=int(m), T=int(found['T']), rounds=int(found['rounds']), total_d2=total_d2,
                 largest_tree=int(np.bincount(dev_out[2]).max()), mean_edge_px=round(float(np.sqrt(dev_out[1].astype(np.float64)).mean() / 2), 3) if m else 0.0,
-                device_ms=[round(v, 3) for v in ms], device_ms_median=round(med(ms), 3), device_stage_ms=stages,
-                device_end_to_end_ms=[round(v, 2) for v in e2e], device_end_to_end_ms_median=round(med(e2e), 2), device_calls_agree=same,
-                graph_ms=[round(v, 3) for v in gms], graph_ms_median=round(med(gms), 3), device_over_graph=round(med(ms) / med(gms), 2),
+                **bp.device_columns(ms, stages, e2e, same), **bp.graph_columns(gms, ms),
                 checked_points=int(win.sum()), checked_against_reference=exact)
     # ---- the host: scipy on the same points
     try:
@@ -117,31 +85,20 @@ def measure(name, pts, lab, C, r, args):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--n', type=int, default=500000)
-    ap.add_argument('--extent', type=int, default=36000, help='side of the square the centres are drawn on, px')
+    ap = bp.parser()
     ap.add_argument('--radius', type=float, default=64.0, help='px')
     ap.add_argument('--by', choices=('any', 'class'), default='any')
-    ap.add_argument('--classes', type=int, default=5)
-    ap.add_argument('--repeats', type=int, default=10)
-    ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--check-n', type=int, default=3000, dest='check_n', help='about how many points the brute-force check takes')
     args = ap.parse_args(argv)
-    import torch
-    from bench_spatial import point_sets
     from nuhtc_amd import mst
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_mst.py needs a GPU (there is no fallback)')
+    bp.need_gpu('bench_mst.py')
     C, r = args.classes, mst.half_pixel_radius(args.radius)
     mst.check_args(C, r, mst.BY[args.by])
-    sets = [measure(name, p, lab, C, r, args) for name, (p, lab) in point_sets(args.n, args.extent, C).items()]
+    sets = [measure(name, p, lab, C, r, args) for name, (p, lab) in bp.point_sets(args.n, args.extent, C).items()]
     line = dict(what=f'tools/bench_mst.py: minimum spanning forest of {args.n} synthetic nucleus centres on a {args.extent}-px square, radius {args.radius:g} px, '
                      f'by {args.by}, {C} classes, one MI355X; device: {args.repeats} calls after {args.warmup} warm-up calls; '
                      f'yardstick: nuhtc_cell_graph k 8 at the same radius; host: scipy cKDTree.sparse_distance_matrix + csgraph.minimum_spanning_tree',
                 n=args.n, extent_px=args.extent, radius_px=args.radius, by=args.by, classes=C, sets=sets)
-    print(json.dumps(line))
-    if not all(s['device_calls_agree'] and s['checked_against_reference'] and s.get('scipy_m_and_total_d2_agree', True) for s in sets):
-        raise SystemExit('a check failed: see device_calls_agree / checked_against_reference / scipy_m_and_total_d2_agree')
+    bp.report(line, ('device_calls_agree', 'checked_against_reference', 'scipy_m_and_total_d2_agree'))
 
 
 if __name__ == '__main__':

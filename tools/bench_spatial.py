@@ -17,8 +17,6 @@ same size: 400 Gaussian clumps (sigma 300 px) on the same square, the labels ske
   checked_against_reference  the timed result against spatial.spatial_reference on a window of the points small enough for brute force
                        (the points of a corner square, run through the device again), and the device's cumulative counts against the trees'
 bench.py is the project's headline benchmark and is not changed by this tool."""
-import argparse
-import json
 import os
 import sys
 import time
@@ -27,66 +25,29 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-
-def point_sets(n, extent, C, seed=0):
-    rng = np.random.default_rng(seed)
-    uniform = (rng.integers(0, 2 * extent, (n, 2)).astype(np.int32), rng.integers(0, C, n).astype(np.int32))
-    centre = rng.uniform(0, 2 * extent, (400, 2))
-    p = centre[rng.integers(0, 400, n)] + rng.normal(0, 2 * 300, (n, 2))
-    p = np.clip(np.rint(p), 0, 2 * extent - 1).astype(np.int32)
-    share = np.array([60, 25, 10, 4, 1][:C], np.float64) if C <= 5 else np.ones(C)
-    lab = rng.choice(C, n, p=share / share.sum()).astype(np.int32)
-    return dict(uniform=uniform, clustered=(p, lab))
+import bench_points as bp  # noqa: E402
+from bench_points import med  # noqa: E402
 
 
 def measure(name, pts, lab, C, edges, args):
     import torch
     from scipy.spatial import cKDTree
-    from nuhtc_amd import cellgraph as cg
-    from nuhtc_amd import cellpoints
-    from nuhtc_amd import hip
     from nuhtc_amd import spatial as sp
     n, B = len(pts), len(edges)
-    dev = torch.device('cuda', 0)
-    bounds = cellpoints.bounds_of(pts)
-    p_d, l_d = torch.from_numpy(pts).to(dev), torch.from_numpy(lab).to(dev)
+    dev, bounds, p_d, l_d = bp.resident(pts, lab)
     out = [torch.zeros((C, C, B), dtype=torch.int64, device=dev), torch.full((n, C), -1, dtype=torch.int32, device=dev),
            torch.zeros((C,), dtype=torch.int64, device=dev)]
-    gout = [torch.full((n, w), -1, dtype=torch.int32, device=dev) for w in (8, 8, C)]
-
-    def timed(fn):
-        ms = []
-        for i in range(args.warmup + args.repeats):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            rc = fn()
-            e1.record()
-            torch.cuda.synchronize()
-            if rc:
-                raise SystemExit(f'the device call failed ({rc})')
-            if i >= args.warmup:
-                ms.append(e0.elapsed_time(e1))
-        return ms
-    ms = timed(lambda: sp.call(p_d, l_d, C, edges, *out, bounds=bounds))
-    gms = timed(lambda: cg.call(p_d, l_d, C, int(edges[-1]), 8, *gout, bounds=bounds))
-    hip.profile_enable(True)                                  # one more call for the split between the stages (events around each)
-    sp.call(p_d, l_d, C, edges, *out, bounds=bounds)
-    stages = {tag: round(v['ms'], 3) for tag, v in hip.profile_read().items() if tag.startswith('cell_spatial')}
-    hip.profile_enable(False)
+    spatial_call = lambda: sp.call(p_d, l_d, C, edges, *out, bounds=bounds)
+    ms = bp.timed(spatial_call, args.repeats, args.warmup)
+    gms = bp.graph_yardstick(p_d, l_d, C, int(edges[-1]), bounds, args)
+    stages = bp.stage_split(spatial_call, 'cell_spatial')
     ph_dev = out[0].cpu().numpy()
-    e2e = []
-    for i in range(3):
-        t0 = time.perf_counter()
-        got = sp.build(pts, lab, C, edges)
-        e2e.append(1e3 * (time.perf_counter() - t0))
+    e2e, got = bp.end_to_end(lambda: sp.build(pts, lab, C, edges))
     same = bool(np.array_equal(got[0], ph_dev) and np.array_equal(got[1], out[1].cpu().numpy()) and np.array_equal(got[2], out[2].cpu().numpy()))
     # ---- a window small enough for brute force, through the device again and against the definition
-    lo = np.array([bounds[0], bounds[1]])
-    side = int(2 * args.extent * np.sqrt(min(1.0, args.check_n / max(n, 1))))
-    win = ((pts - lo) < side).all(1)
-    if win.sum() > 2 * args.check_n:                          # a dense corner of the clustered set
-        win &= np.cumsum(win) <= 2 * args.check_n
+    win = bp.brute_window(pts, bounds, args.extent, args.check_n)
     sub = sp.build(pts[win], lab[win], C, edges)
     ref = sp.spatial_reference(pts[win], lab[win], C, edges)
     exact = bool(all(np.array_equal(a, b) for a, b in zip(sub, ref)))
@@ -102,11 +63,8 @@ def measure(name, pts, lab, C, edges, args):
     t_count = time.perf_counter() - t0
     cum = np.array(cum, np.int64).reshape(C, C, B) - np.eye(C, dtype=np.int64)[:, :, None] * got[2][:, None, None]
     host_agrees = bool(np.array_equal(np.cumsum(ph_dev, 2), cum))
-    med = lambda v: float(np.median(v))
     return dict(points=name, n=n, ordered_pairs_within_reach=int(ph_dev.sum()), mean_neighbours_within_reach=round(float(ph_dev.sum()) / max(int(got[2].sum()), 1), 2),
-                class_n=got[2].tolist(), device_ms=[round(v, 3) for v in ms], device_ms_median=round(med(ms), 3), device_stage_ms=stages,
-                device_end_to_end_ms=[round(v, 2) for v in e2e], device_end_to_end_ms_median=round(med(e2e), 2), device_calls_agree=same,
-                graph_ms=[round(v, 3) for v in gms], graph_ms_median=round(med(gms), 3),
+                class_n=got[2].tolist(), **bp.device_columns(ms, stages, e2e, same), **bp.graph_columns(gms),
                 host_tree_build_ms=round(1e3 * t_build, 1), host_count_ms=round(1e3 * t_count, 1), host_workers=args.workers,
                 host_total_over_device_call=round(1e3 * (t_build + t_count) / med(ms), 2),
                 host_total_over_device_end_to_end=round(1e3 * (t_build + t_count) / med(e2e), 2),
@@ -114,31 +72,21 @@ def measure(name, pts, lab, C, edges, args):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--n', type=int, default=500000)
-    ap.add_argument('--extent', type=int, default=36000, help='side of the square the centres are drawn on, px')
+    ap = bp.parser()
     ap.add_argument('--step', type=float, default=8.0)
     ap.add_argument('--bins', type=int, default=32)
-    ap.add_argument('--classes', type=int, default=5)
-    ap.add_argument('--repeats', type=int, default=10)
-    ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--workers', type=int, default=16)
-    ap.add_argument('--check-n', type=int, default=3000, dest='check_n', help='about how many points the brute-force check takes')
     args = ap.parse_args(argv)
-    import torch
     from nuhtc_amd import spatial as sp
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_spatial.py needs a GPU (there is no fallback)')
+    bp.need_gpu('bench_spatial.py')
     C = args.classes
     edges = sp.edges_from_step(args.step, args.bins)
-    sets = [measure(name, p, lab, C, edges, args) for name, (p, lab) in point_sets(args.n, args.extent, C).items()]
+    sets = [measure(name, p, lab, C, edges, args) for name, (p, lab) in bp.point_sets(args.n, args.extent, C).items()]
     line = dict(what=f'tools/bench_spatial.py: pair histograms of {args.n} synthetic nucleus centres on a {args.extent}-px square, {args.bins} bins of '
                      f'{args.step:g} px (reach {edges[-1] / 2:g} px), {C} classes, one MI355X; device: {args.repeats} calls after {args.warmup} warm-up calls; '
                      f'yardstick: nuhtc_cell_graph k 8 at the same reach; host: scipy cKDTree.count_neighbors per ordered class pair',
                 n=args.n, extent_px=args.extent, step_px=args.step, bins=args.bins, reach_px=float(edges[-1]) / 2, classes=C, sets=sets)
-    print(json.dumps(line))
-    if not all(s['device_calls_agree'] and s['checked_against_reference'] and s['host_cumulative_counts_agree'] for s in sets):
-        raise SystemExit('a check failed: see device_calls_agree / checked_against_reference / host_cumulative_counts_agree')
+    bp.report(line, ('device_calls_agree', 'checked_against_reference', 'host_cumulative_counts_agree'))
 
 
 if __name__ == '__main__':

@@ -197,7 +197,7 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
     """The reference's per-slide loop (:460-693): tiles -> detections -> per-tile filter + mask-NMS -> records -> the one gather ->
     rank 0 writes the documents.  The tile list is sharded in contiguous blocks over the ranks."""
     import torch
-    from nuhtc_amd import contours, nuclei, parallel, wsi
+    from nuhtc_amd import contours, nuclei, parallel, slidepoints, wsi
     coords = bag.coords
     lo, hi = parallel.shard_range(len(bag), rank, world)
     tiles = bag.view(lo, hi)                                  # this rank's tiles only, cut / decoded a batch at a time while earlier batches run
@@ -303,67 +303,19 @@ def run_slide(args, model, bag, slide_id, rank, local_rank, world):
             outputs.write_text_list(os.path.join(out_dir, name + '_merged.geojson'), contours.join_features_text(body, start, kept))
             msg += f', {len(kept)} after the cross-tile merge'
             feat_rows = np.asarray(kept, np.int64)
-    graph = getattr(args, 'nuclei_graph', False)
-    spatial_on = getattr(args, 'nuclei_spatial', False)
-    clusters_on = getattr(args, 'nuclei_clusters', False)
-    mst_on = getattr(args, 'nuclei_mst', False)
-    prox_on = getattr(args, 'nuclei_proximity', False)
-    dens_on = getattr(args, 'nuclei_density', False)
-    if sel or graph or spatial_on or clusters_on or mst_on or prox_on or dens_on:                                    # the rows of the per-nucleus files, and their labels and scores
+    points = slidepoints.select(args)                                 # the per-slide point analyses asked for
+    if sel or points:                                                 # the rows of the per-nucleus files, and their labels and scores
         hall = np.concatenate([h.cpu().numpy() for h in heads], 0).reshape(-1, 9)
         rows = np.arange(n_records, dtype=np.int64) if feat_rows is None else feat_rows
     for i, kind in enumerate(sel):
         kind.write(os.path.join(out_dir, name + kind.suffix), rows, wsi.gathered_rows(kind, gathered, rows, part=rows_at + i),
                    hall[rows, 5].astype(np.int64), hall[rows, 4])
         msg += f', {len(rows)} {kind.said} in {name}{kind.suffix}'
-    if graph or spatial_on or clusters_on or mst_on or prox_on or dens_on:       # one point set for the six: only what the gather already delivered
-        from nuhtc_amd import cellpoints
-        boxes, lab = hall[rows, :4], hall[rows, 5].astype(np.int64)
-        pts, xy = cellpoints.quantize_centres(boxes), cellpoints.centres(boxes)
-        on = local_rank if world > 1 else (torch.device(args.device).index or 0)
-    if graph:                                                         # the edges to those rows
-        from nuhtc_amd import cellgraph
-        nb, d2, cc = cellgraph.build(pts, lab, len(model.CLASSES), args.graph_radius, args.graph_k, device=on)
-        cellgraph.write_npz(os.path.join(out_dir, name + '_nuclei_graph.npz'), rows, xy, nb, d2, cc, lab, args.graph_radius, args.graph_k)
-        msg += f', {int((nb >= 0).sum())} edges (k {args.graph_k}, {args.graph_radius:g} px) in {name}_nuclei_graph.npz'
-    if spatial_on:                                                    # pair counts over the same rows
-        from nuhtc_amd import spatial
-        edges = spatial.edges_from_step(args.spatial_step, args.spatial_bins)
-        ph, nn, cn = spatial.build(pts, lab, len(model.CLASSES), edges, device=on)
-        spatial.write_npz(os.path.join(out_dir, name + '_nuclei_spatial.npz'), rows, xy, lab, edges, ph, nn, cn,
-                          tiles_area_px=float(len(bag)) * float(args.step_size) ** 2)
-        msg += f', {int(ph.sum())} ordered pairs within {edges[-1] / 2:g} px ({len(edges)} bins) in {name}_nuclei_spatial.npz'
-    if clusters_on:                                                   # which of the same rows belong together
-        from nuhtc_amd import clusters
-        by = clusters.BY[args.cluster_by]
-        found = clusters.build(pts, lab, len(model.CLASSES), args.cluster_radius, args.cluster_min, by, device=on)
-        clusters.write_npz(os.path.join(out_dir, name + '_nuclei_clusters.npz'), rows, xy, lab, *found,
-                           radius_px=args.cluster_radius, min_pts=args.cluster_min, by_class=by)
-        msg += (f', {len(found[3])} clusters and {int((found[0] < 0).sum())} isolated nuclei ({args.cluster_radius:g} px, {args.cluster_min} nuclei, '
-                f'by {args.cluster_by}) in {name}_nuclei_clusters.npz')
-    if mst_on:                                                        # the shortest edges that hold the same rows together
-        from nuhtc_amd import mst
-        by = mst.BY[args.mst_by]
-        e, ed2, tree, n_e, n_t = mst.build(pts, lab, len(model.CLASSES), args.mst_radius, by, device=on)
-        mst.write_npz(os.path.join(out_dir, name + '_nuclei_mst.npz'), rows, xy, lab, e, ed2, tree, len(model.CLASSES),
-                      radius_px=args.mst_radius, by_class=by)
-        msg += f', {n_e} forest edges in {n_t} trees ({args.mst_radius:g} px, by {args.mst_by}) in {name}_nuclei_mst.npz'
-    if prox_on:                                                       # which of the same rows touch: the Gabriel graph and the RNG
-        from nuhtc_amd import proximity
-        by = proximity.BY[args.proximity_by]
-        e, ed2, erng, deg, n_e, n_r = proximity.build(pts, lab, len(model.CLASSES), args.proximity_radius, by, device=on)
-        proximity.write_npz(os.path.join(out_dir, name + '_nuclei_proximity.npz'), rows, xy, lab, e, ed2, erng, deg, len(model.CLASSES),
-                            radius_px=args.proximity_radius, by_class=by)
-        msg += (f', {n_e} Gabriel edges, {n_r} of them RNG edges ({args.proximity_radius:g} px, by {args.proximity_by}) '
-                f'in {name}_nuclei_proximity.npz')
-    if dens_on:                                                       # where on the slide the same rows lie: class-wise kernel rasters
-        from nuhtc_amd import density
-        cnt, wgt, win = density.build(pts, lab, len(model.CLASSES), args.density_bandwidth, args.density_pitch, device=on)
-        density.write_npz(os.path.join(out_dir, name + '_nuclei_density.npz'), rows, xy, lab, cnt, wgt, win, args.density_bandwidth, args.density_pitch)
-        peaks = density.derive(cnt, wgt, density.half_pixel_radius(args.density_bandwidth))['peak_site']
-        peak_px = ', '.join('none' if u < 0 else f'({(win[0] + u) * args.density_pitch:g}, {(win[1] + v) * args.density_pitch:g})' for u, v in peaks.tolist())
-        msg += (f', density maps of {win[2]} x {win[3]} sites ({args.density_bandwidth:g} px bandwidth, {args.density_pitch:g} px pitch; '
-                f'peak px per class: {peak_px}) in {name}_nuclei_density.npz')
+    if points:                                                        # one point set for all of them: only what the gather already delivered
+        said = slidepoints.run(points, rows, hall[rows, :4], hall[rows, 5].astype(np.int64), len(model.CLASSES), out_dir, name,
+                               local_rank if world > 1 else (torch.device(args.device).index or 0),
+                               dict(tiles_area_px=float(len(bag)) * float(args.step_size) ** 2))
+        msg += ''.join(', ' + clause for clause in said)
     if want('dsa'):
         outputs.write_json(os.path.join(out_dir, name + '_dsa.json'), outputs.dsa_document(dsa))
     if want('coco'):
@@ -391,7 +343,7 @@ def main(argv=None):
         from nuhtc_amd import parallel
         raise SystemExit(parallel.self_launch(args.gpus, __file__, sys.argv[1:] if argv is None else argv))
     import torch
-    from nuhtc_amd import parallel, slides, tilestore
+    from nuhtc_amd import parallel, slidepoints, slides, tilestore
     from nuhtc_amd.apis import init_detector
     if args.seg_on == 'gpu' and not torch.cuda.is_available():
         raise SystemExit('--seg-on gpu: no GPU is visible (there is no fallback; --seg-on host is the host route)')
@@ -404,54 +356,7 @@ def main(argv=None):
         raise SystemExit('--nuclei-morph: no GPU is visible (there is no fallback)')
     if args.nuclei_texture and not torch.cuda.is_available():
         raise SystemExit('--nuclei-texture: no GPU is visible (there is no fallback)')
-    if args.nuclei_graph:
-        from nuhtc_amd import cellgraph
-        if not torch.cuda.is_available():
-            raise SystemExit('--nuclei-graph: no GPU is visible (there is no fallback)')
-        try:
-            cellgraph.check_args(1, cellgraph.half_pixel_radius(args.graph_radius), args.graph_k)
-        except ValueError as e:
-            raise SystemExit(f'--nuclei-graph: {e}')
-    if args.nuclei_spatial:
-        from nuhtc_amd import spatial
-        try:
-            spatial.edges_from_step(args.spatial_step, args.spatial_bins)
-        except ValueError as e:
-            raise SystemExit(f'--nuclei-spatial: {e}')
-        if not torch.cuda.is_available():
-            raise SystemExit('--nuclei-spatial: no GPU is visible (there is no fallback)')
-    if args.nuclei_clusters:
-        from nuhtc_amd import clusters
-        try:
-            clusters.check_args(1, clusters.half_pixel_radius(args.cluster_radius), args.cluster_min, clusters.BY[args.cluster_by])
-        except ValueError as e:
-            raise SystemExit(f'--nuclei-clusters: {e}')
-        if not torch.cuda.is_available():
-            raise SystemExit('--nuclei-clusters: no GPU is visible (there is no fallback)')
-    if args.nuclei_mst:
-        from nuhtc_amd import mst
-        try:
-            mst.check_args(1, mst.half_pixel_radius(args.mst_radius), mst.BY[args.mst_by])
-        except ValueError as e:
-            raise SystemExit(f'--nuclei-mst: {e}')
-        if not torch.cuda.is_available():
-            raise SystemExit('--nuclei-mst: no GPU is visible (there is no fallback)')
-    if args.nuclei_proximity:
-        from nuhtc_amd import proximity
-        try:
-            proximity.check_args(1, proximity.half_pixel_radius(args.proximity_radius), proximity.BY[args.proximity_by])
-        except ValueError as e:
-            raise SystemExit(f'--nuclei-proximity: {e}')
-        if not torch.cuda.is_available():
-            raise SystemExit('--nuclei-proximity: no GPU is visible (there is no fallback)')
-    if args.nuclei_density:
-        from nuhtc_amd import density
-        try:
-            density.check_args(1, density.half_pixel_radius(args.density_bandwidth), density.half_pixel_radius(args.density_pitch))
-        except ValueError as e:
-            raise SystemExit(f'--nuclei-density: {e}')
-        if not torch.cuda.is_available():
-            raise SystemExit('--nuclei-density: no GPU is visible (there is no fallback)')
+    slidepoints.select(args)                                  # the per-slide point analyses: their arguments, then a GPU
     # the process group is formed AFTER seg_and_patch: rank 0's host phase (segmentation, masks, patching, stitching of every slide of the
     # folder) has no time bound, and a rank waiting in an RCCL barrier is aborted by the watchdog after 10 minutes
     rank, local_rank, world = parallel.env_ranks()
