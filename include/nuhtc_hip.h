@@ -1064,6 +1064,38 @@ int nuhtc_cell_proximity(int device, const int32_t* points, const int32_t* label
 int nuhtc_cell_density(int device, const int32_t* points, const int32_t* labels, int64_t n, int num_classes, int h, int s, int gx0, int gy0,
                        int W, int H, int x_min, int y_min, int x_max, int y_max, int32_t* count, int64_t* weight, void* stream);
 
+/* Nuclei by region (csrc/cellregion.hip; nuhtc_amd/regions.py holds the definition and the brute-force restatement `regions_reference`):
+ * an exact point-in-polygon census of the nucleus centres against annotated regions -- "how many nuclei of each class lie in this
+ * region".  Not in the reference.  Engine-free like the density call: every pointer but `slots` is device memory of `device`, the call
+ * allocates and frees its own scratch, runs on `stream` and synchronises it before returning.  nuhtc_config is unchanged (no ABI bump).
+ *   points [n][2] int32: node positions in HALF pixels, |p| < 2^27.  labels [n] int32.  0 <= n <= 2^24.  num_classes C: 1 .. 14.
+ *   edges [E][4] int32 (ax, ay, bx, by): the edges of the regions' rings in half pixels, every |v| < 2^27, 16-byte aligned; a ring's
+ *     closing edge is included, a zero-length edge is legal.  0 <= E <= 2^22.
+ *   edge_region [E] int32: the region of every edge, in 0 .. G - 1 and non-decreasing.  0 <= G <= 2^16 (G == 0 needs E == 0).
+ *   slab: the height in half pixels, 1 .. 16384, of the horizontal slabs the points and the edges are binned by.  Every output is
+ *     independent of it; it decides the time only.
+ *   slot_cap: 0 .. 2^28, the (edge, slab) records the call may hold: an edge has one record per slab its y-range meets inside the box.
+ *     *slots (host memory, never null) receives the number M the call needs whenever it returns NUHTC_OK.  With M > slot_cap nothing
+ *     else is written: call again with slot_cap >= M (nuhtc_amd/regions.py states M exactly on the host).
+ *   x_min, y_min, x_max, y_max: the bounding box of the points (inclusive), computed by the caller on the host (ignored when n == 0).
+ * Inside is even-odd and half-open: an edge with ay != by straddles p when (ay <= py) != (by <= py); oriented upward (lo -> hi) it is
+ * crossed when (hi - lo) x (p - lo) > 0, an exact int64 cross product (differences < 2^28, products < 2^56); p is inside region g when an
+ * odd number of g's edges are crossed.  Ring orientation, holes and multipolygons need no special case; regions that share an edge tile.
+ * p is ON an edge when the cross product on a -> b is 0 and p lies in the edge's closed bounding box.
+ *   region [n] int32: the LARGEST region index that holds the point, -1 for none.   depth [n] int32: how many regions hold it.
+ *   on_boundary [n] uint8: 1 when the point lies on an edge of any region.
+ *   census [G][C] int64: the points of label c inside region g, counted in EVERY region that holds them; a label outside 0 .. C - 1 is
+ *     counted nowhere.
+ * All four are always fully written on success with M <= slot_cap (n == 0: census is cleared).  The result is a pure function of the
+ * input: bitwise the same on every call.
+ * NUHTC_E_INVALID, before anything is launched and with the outputs untouched: n, num_classes, E, G, slab or slot_cap out of range, a
+ * null pointer where the count is not 0, with n > 0 a bounding box that is empty or reaches +-2^27.
+ * NUHTC_E_INVALID after the first kernels, the outputs still untouched: a vertex outside +-2^27, an edge_region outside 0 .. G - 1 or
+ * decreasing, a point outside the stated bounding box. */
+int nuhtc_cell_regions(int device, const int32_t* points, const int32_t* labels, int64_t n, int num_classes, const int32_t* edges,
+                       const int32_t* edge_region, int64_t E, int64_t G, int slab, int64_t slot_cap, int x_min, int y_min, int x_max, int y_max,
+                       int32_t* region, int32_t* depth, uint8_t* on_boundary, int64_t* census, int64_t* slots, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the launch stream (process-wide switch; off by default).
  * nuhtc_profile_read synchronises the device and writes one text line per kernel tag,
  * "tag launches total_ms algorithmic_flops algorithmic_bytes", then resets the records. */

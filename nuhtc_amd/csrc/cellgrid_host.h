@@ -1,8 +1,8 @@
 // The uniform grid over half-pixel points that the per-slide analyses share (cellbin.h; cellgraph.hip, cellspatial.hip, cellcluster.hip,
-// cellmst.hip, cellprox.hip, celldensity.hip): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
+// cellmst.hip, cellprox.hip, celldensity.hip, cellregion.hip): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
 // and the (cell, class) key of a point, the squared distance of a pair within reach, and the edge key of the spanning forest.  Header-only,
 // so a host program can exercise them under a sanitizer (tools/dev/cellspatial_host_check.cpp, tools/dev/cellmst_host_check.cpp, tools/dev/cellprox_host_check.cpp,
-// tools/dev/celldensity_host_check.cpp); the kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
+// tools/dev/celldensity_host_check.cpp, tools/dev/cellregion_host_check.cpp); the kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
 #pragma once
 #include <cstdint>
 
@@ -124,6 +124,57 @@ inline bool dens_window_ok(int s, int gx0, int gy0, int W, int H) {
   const int64_t lim = DENS_SITE_LIMIT;
   const int64_t xa = (int64_t)gx0 * s, xb = ((int64_t)gx0 + W - 1) * s, ya = (int64_t)gy0 * s, yb = ((int64_t)gy0 + H - 1) * s;
   return xa > -lim && xa < lim && xb > -lim && xb < lim && ya > -lim && ya < lim && yb > -lim && yb < lim;
+}
+
+// ---- nuclei by region (cellregion.hip): the second input is not the points but polygon EDGES (ax, ay, bx, by), and the test is a
+// point against an edge.  The bit budget, stated here once: a point and a vertex both have |v| < 2^27, so every difference (hi - lo,
+// p - lo, b - a, p - a) is below 2^28 in magnitude and exact in int32; a product of two of them is below 2^56 and the difference of two
+// products below 2^57: the cross product is exact in int64 (float64 holds 53 bits and decides the side of a long thin edge wrongly).
+// The slab of a y inside the box is (y - y_min) / side with 0 <= y - y_min < 2^28.
+constexpr int64_t REGION_MAX_EDGES = (int64_t)1 << 22;
+constexpr int64_t REGION_MAX_REGIONS = (int64_t)1 << 16;
+constexpr int64_t REGION_MAX_SLOTS = (int64_t)1 << 28;  // (edge, slab) records of one call: the cap a caller may state
+constexpr int REGION_MAX_CELLS = 1 << 22;
+constexpr int REGION_STAGE = 256;                      // edge records staged through LDS at a time = threads of a workgroup
+
+// is the edge a -> b crossed by the ray from p towards +x?  Half-open in y: the edge straddles p when exactly one end has y <= p.y; the
+// straddling edge is oriented upward (lo the end with the smaller y) and crossed when p lies strictly on its -x side.
+CELL_HD inline bool region_crossed(int ax, int ay, int bx, int by, int px, int py) {
+  if ((ay <= py) == (by <= py)) return false;
+  const bool up = ay < by;
+  const int lx = up ? ax : bx, ly = up ? ay : by, hx = up ? bx : ax, hy = up ? by : ay;
+  return (int64_t)(hx - lx) * (py - ly) - (int64_t)(hy - ly) * (px - lx) > 0;
+}
+
+// does p lie ON the edge a -> b?  The cross product on a -> b is 0 and p is in the closed bounding box of the edge (a zero-length edge:
+// p == a).  The box comes first: it spares the products for nearly every edge.
+CELL_HD inline bool region_on_edge(int ax, int ay, int bx, int by, int px, int py) {
+  if (px < (ax < bx ? ax : bx) || px > (ax < bx ? bx : ax) || py < (ay < by ? ay : by) || py > (ay < by ? by : ay)) return false;
+  return (int64_t)(bx - ax) * (py - ay) - (int64_t)(by - ay) * (px - ax) == 0;
+}
+
+// the slabs (rows of the points' grid: slab k holds y_min + k * side .. y_min + (k + 1) * side - 1) that the closed y-range of an edge
+// meets, clipped to the points' box: s0 .. s1, or false when no point of the box can cross or touch the edge -- it lies wholly above,
+// below or LEFT of the box (a crossed edge lies beyond p towards +x, a touched one holds p in its bounding box).  An edge wholly right
+// of the box stays: every ray runs that way.
+CELL_HD inline bool region_slab_range(int ax, int ay, int bx, int by, int x_min, int y_min, int y_max, int side, int* s0, int* s1) {
+  const int ylo = ay < by ? ay : by, yhi = ay < by ? by : ay;
+  if (yhi < y_min || ylo > y_max || (ax < x_min && bx < x_min)) return false;
+  *s0 = ((ylo > y_min ? ylo : y_min) - y_min) / side;
+  *s1 = ((yhi < y_max ? yhi : y_max) - y_min) / side;
+  return true;
+}
+
+// an edge the entry point accepts: both ends within the coordinate range, its region among the G regions and not below the region of
+// the edge in front of it (prev_region; 0 in front of the first edge)
+CELL_HD inline bool region_edge_ok(int ax, int ay, int bx, int by, int region, int prev_region, int G) {
+  const int L = CELL_COORD_LIMIT;
+  return ax > -L && ax < L && ay > -L && ay < L && bx > -L && bx < L && by > -L && by < L && region >= 0 && region < G && prev_region <= region;
+}
+
+inline bool region_call_ok(int64_t E, int64_t G, int slab, int64_t slot_cap) {
+  return E >= 0 && E <= REGION_MAX_EDGES && G >= 0 && G <= REGION_MAX_REGIONS && slab >= 1 && slab <= CELL_MAX_REACH && slot_cap >= 0 &&
+         slot_cap <= REGION_MAX_SLOTS;
 }
 
 // ---- the front checks of an entry point, before anything is launched: the limits every analysis shares (its own n limit passed in),

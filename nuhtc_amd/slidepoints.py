@@ -1,11 +1,15 @@
 """The per-slide point analyses of the slide path as ONE table: which flag of tools/infer_wsi.py selects each, how its arguments become
-the parameters of its module (cellgraph, spatial, clusters, mst, proximity, density: they hold the definitions), which file it writes
-beside the documents and what the closing message says of it.  cellpoints.py is what the six modules share and is imported by them; this
+the parameters of its module (cellgraph, spatial, clusters, mst, proximity, density, regions: they hold the definitions), which file it writes
+beside the documents and what the closing message says of it.  cellpoints.py is what the modules share and is imported by them; this
 module imports them, one at a time and only when its flag is given.
 
 The order of ANALYSES is fixed: it is the order of the files and of the clauses of the closing message.  `select` turns the parsed
 arguments into a selection, `run` works a selection off on one point set; both name no analysis.  A new analysis is a module with
-check_args / build / write_npz and one row here (plus its argparse lines in the tool)."""
+check_args / build / write_npz and one row here (plus its argparse lines in the tool).
+
+ANALYSES is the table of the analyses of the points ALONE.  An analysis with a second input -- regions.py: the points against the regions
+of a GeoJSON -- is a row of WITH_INPUT behind it, handled by `select` and `run` after the six: the same columns, and one more that
+fetches the second input for a slide, or says that the slide has none (then nothing is written for it)."""
 import importlib
 import os
 from collections import namedtuple
@@ -18,7 +22,9 @@ from . import cellpoints
 # check    (module, params) -> the module's check_args on them with one class (the model is not loaded yet); ValueError
 # write    (module, path, (nuclei_id, xy, label), what build returned, num_classes, params, context) -> write_npz
 # said     (module, what build returned, params) -> the clause of the closing message, without ' in <file>'
-Analysis = namedtuple('Analysis', 'cli flag suffix module params check write said')
+# second   rows of WITH_INPUT only: (module, params, slide name) -> the second input `build` takes behind num_classes, or None when the
+#          slide has none; `missing` (params, slide name) -> the clause that says so
+Analysis = namedtuple('Analysis', 'cli flag suffix module params check write said second missing', defaults=(None, None))
 
 BY_NAMES = ('any', 'class')                   # the modules' BY, backwards
 _half = cellpoints.half_pixel_radius
@@ -74,12 +80,35 @@ ANALYSES = (
 )
 
 
+WITH_INPUT = (
+    _analysis('regions', 'regions',                                   # which annotated regions hold the same rows: the census per region
+              lambda m, a: (a.nuclei_regions, a.regions_order),
+              lambda m, p: m.source_check(p[0]),
+              lambda m, path, head, found, C, p, ctx: m.write_npz(path, *head, *found[1], found[0], p[1]),
+              lambda m, found, p: (f'{int((found[1][1] > 0).sum())} nuclei inside {len(found[0].names)} regions of {os.path.basename(found[2])} '
+                                   f'({int(found[1][2].sum())} on a boundary, order {p[1]})'))
+    ._replace(second=lambda m, p, name: m.source_for(p[0], name),
+              missing=lambda p, name: f'no {name}.geojson in {p[0]}: no {name}_nuclei_regions.npz'),
+)
+
+
+def _build(an, m, pts, labels, num_classes, params, name, device):
+    """What `run` writes from: build's results, or for a row of WITH_INPUT (the table read, build's results, the file), None without a file."""
+    if an.second is None:
+        return m.build(pts, labels, num_classes, *params, device=device)
+    source = an.second(m, params, name)
+    if source is None:
+        return None
+    table = m.read_geojson(source, params[1])
+    return table, m.build(pts, labels, num_classes, table.edges, table.edge_region, len(table.names), device=device), source
+
+
 def select(args, need_gpu=True):
     """The parsed arguments of tools/infer_wsi.py -> the selection: ((analysis, params), ..) of the flags given, in the order of ANALYSES.
     SystemExit in the name of the flag when its arguments are unusable and then, with need_gpu, when no GPU is visible.  A flag the
     namespace does not hold is not given."""
     chosen = []
-    for an in ANALYSES:
+    for an in ANALYSES + WITH_INPUT:
         if not getattr(args, an.cli, False):
             continue
         m = module_of(an)
@@ -104,7 +133,10 @@ def run(selection, rows, boxes, labels, num_classes, out_dir, name, device, cont
     clauses = []
     for an, params in selection:
         m = module_of(an)
-        found = m.build(pts, labels, num_classes, *params, device=device)
+        found = _build(an, m, pts, labels, num_classes, params, name, device)
+        if found is None:
+            clauses.append(an.missing(params, name))
+            continue
         an.write(m, os.path.join(out_dir, name + an.suffix), (rows, xy, labels), found, num_classes, params, context)
         clauses.append(f'{an.said(m, found, params)} in {name}{an.suffix}')
     return clauses

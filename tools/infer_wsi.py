@@ -72,6 +72,16 @@ Output (like the reference, :659-693), for every detection that survives the per
                   `pitch_px`, `origin_px` (the px position of site (0, 0)), `window` (gx0, gy0, W, H in lattice units).  No tissue-area
                   normalisation and no edge correction.  Every other file is the same bytes with and without the flag.  There is no route
                   without a GPU.
+  --nuclei-regions PATH: (not in the reference) <id>_nuclei_regions.npz beside the documents, from the same rows as --nuclei-graph: which
+                  annotated regions hold each nucleus, and the nuclei of each class inside every region.  PATH is a GeoJSON of Polygon and
+                  MultiPolygon features (QuPath annotations, a tissue outline) used for every slide, or a directory holding
+                  <slide_id>.geojson; a slide without a file gets no output and a clause saying so.  Even-odd and half-open in exact
+                  integers on half pixels, built on rank 0's GPU after the gather (nuhtc_amd/regions.py): `region` (the largest index
+                  holding the nucleus, -1: none; with --regions-order area the features are sorted by descending area, so that is the
+                  innermost), `depth`, `on_boundary`, `census` int64 (G, C), the derived `area_px2`, `density_per_px2`, `class_fraction`,
+                  `n_inside`, `n_outside`, `class_share_inside`, and the regions themselves: `names`, `ring_start`, `edges`, `edge_region`,
+                  `area2`, `order`.  The area is the one the file states (shoelace; not verified).  Every other file is the same bytes
+                  with and without the flag.  There is no route without a GPU.
   --nuclei-morph: (the reference's tools/wsi_feat_extract.py table, computed on the GPU) <id>_nuclei_morph.npz beside the documents, for the
                   same rows: `columns` and `values` float64 (n, F) -- size, shape, orientation, position and haematoxylin-intensity features
                   under histomicstk's names, derived on the host (nuhtc_amd/nucmorph.py derive) from the integers every rank's GPU measured
@@ -186,6 +196,11 @@ def build_parser():
                    help='kernel radius of --nuclei-density in slide px, a multiple of 0.5 up to 8192 (default 128 px: 32 um at 40x)')
     p.add_argument('--density-pitch', type=float, default=64.0, dest='density_pitch',
                    help='distance between the sites of --nuclei-density in slide px, a multiple of 0.5 (default 64 px)')
+    p.add_argument('--nuclei-regions', default=None, dest='nuclei_regions', metavar='PATH',
+                   help='also write <id>_nuclei_regions.npz: which regions of a GeoJSON (one file for every slide, or a directory of <slide_id>.geojson) '
+                        'hold each written nucleus and the nuclei per class inside every region, exact, built on the GPU; from the rows of --nuclei-graph')
+    p.add_argument('--regions-order', choices=('file', 'area'), default='file', dest='regions_order',
+                   help="the regions of --nuclei-regions in file order ('file') or by descending area, so that a nucleus's region is the innermost ('area')")
     return p
 
 
