@@ -1096,6 +1096,33 @@ int nuhtc_cell_regions(int device, const int32_t* points, const int32_t* labels,
                        const int32_t* edge_region, int64_t E, int64_t G, int slab, int64_t slot_cap, int x_min, int y_min, int x_max, int y_max,
                        int32_t* region, int32_t* depth, uint8_t* on_boundary, int64_t* census, int64_t* slots, void* stream);
 
+/* Neighbourhood enrichment of a slide (csrc/cellenrich.hip; nuhtc_amd/enrichment.py holds the definition and the brute-force restatement
+ * `enrichment_reference`): the class-pair contact counts of the nucleus centres, observed and under num_perms label permutations -- the
+ * integers of the neighbourhood-enrichment permutation test (positions kept, labels shuffled).  Not in the reference.  Engine-free like
+ * the spatial call: points, labels and the three outputs are device memory of `device`, the call allocates and frees its own scratch,
+ * runs on `stream` and synchronises it before returning.  nuhtc_config is unchanged (no ABI bump).
+ *   points [n][2] int32: node positions in HALF pixels, |p| < 2^27.  labels [n] int32.  0 <= n <= 2^24.  num_classes C: 1 .. 14.
+ *   r: the contact radius in half pixels, 1 .. 16384, inclusive.  num_perms P: 1 .. 1024.  seed: any 32-bit value.
+ *   x_min, y_min, x_max, y_max: the bounding box of the points (inclusive), computed by the caller on the host (cell side = the smallest
+ *     multiple of r whose grid over the box has at most 2^22 cells; ignored when n == 0).
+ * All arithmetic is integer.  An ordered pair (i, j), i != j, is a contact when dx * dx + dy * dy <= r * r; coincident points are
+ * contacts.  Permutation p = 1 .. P of the rows is pi_p, a keyed six-round Feistel network with cycle-walking, an exact function of
+ * (n, seed, p) (csrc/cellenrich_host.h); the shuffled labels are lab_p[i] = labels[pi_p(i)], every row taking part.
+ *   observed    [C][C] int64:    the contacts with label_i = a and label_j = b; a label outside [0, C) is counted in no row and no column.
+ *   perm_counts [P][C][C] int64: row p - 1 is the same count under lab_p.
+ *   class_n     [C] int64:       the points of each class.
+ * The call zeroes all three itself.  The result is a pure function of the input, the ORDER of the rows included (pi acts on row
+ * numbers; observed and class_n do not depend on it): bitwise the same on every call.  n == 0 zeroes the outputs and returns NUHTC_OK.
+ * NUHTC_E_INVALID, before anything is launched and with the outputs untouched: num_perms, r, num_classes or n out of range, a null
+ * pointer, a bounding box that is empty or reaches +-2^27 (so: any coordinate out of range).  NUHTC_E_INVALID after the binning, the
+ * outputs still untouched: a point lies outside the stated bounding box. */
+int nuhtc_cell_enrichment(int device, const int32_t* points, const int32_t* labels, int64_t n, int num_classes, int r, int num_perms,
+                          uint32_t seed, int x_min, int y_min, int x_max, int y_max, int64_t* observed, int64_t* perm_counts, int64_t* class_n,
+                          void* stream);
+/* The generator alone, on the HOST (no GPU is touched): out[i] = pi_p(i) for i < n, through the same header the kernels use.
+ * 0 <= n <= 2^24, 1 <= p <= 1024; NUHTC_E_INVALID otherwise or when out is null with n > 0. */
+int nuhtc_enrichment_permutation(int64_t n, uint32_t seed, int p, int32_t* out);
+
 /* Per-kernel timing with HIP events recorded on the launch stream (process-wide switch; off by default).
  * nuhtc_profile_read synchronises the device and writes one text line per kernel tag,
  * "tag launches total_ms algorithmic_flops algorithmic_bytes", then resets the records. */

@@ -1,8 +1,8 @@
 // The uniform grid over half-pixel points that the per-slide analyses share (cellbin.h; cellgraph.hip, cellspatial.hip, cellcluster.hip,
-// cellmst.hip, cellprox.hip, celldensity.hip, cellregion.hip): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
+// cellmst.hip, cellprox.hip, celldensity.hip, cellregion.hip, cellenrich.hip): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
 // and the (cell, class) key of a point, the squared distance of a pair within reach, and the edge key of the spanning forest.  Header-only,
 // so a host program can exercise them under a sanitizer (tools/dev/cellspatial_host_check.cpp, tools/dev/cellmst_host_check.cpp, tools/dev/cellprox_host_check.cpp,
-// tools/dev/celldensity_host_check.cpp, tools/dev/cellregion_host_check.cpp); the kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
+// tools/dev/celldensity_host_check.cpp, tools/dev/cellregion_host_check.cpp, tools/dev/cellenrich_host_check.cpp); the kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
 #pragma once
 #include <cstdint>
 

@@ -1,5 +1,5 @@
 """The per-slide point analyses of the slide path as ONE table: which flag of tools/infer_wsi.py selects each, how its arguments become
-the parameters of its module (cellgraph, spatial, clusters, mst, proximity, density, regions: they hold the definitions), which file it writes
+the parameters of its module (cellgraph, spatial, clusters, mst, proximity, density, enrichment, regions: they hold the definitions), which file it writes
 beside the documents and what the closing message says of it.  cellpoints.py is what the modules share and is imported by them; this
 module imports them, one at a time and only when its flag is given.
 
@@ -9,7 +9,11 @@ check_args / build / write_npz and one row here (plus its argparse lines in the 
 
 ANALYSES is the table of the analyses of the points ALONE.  An analysis with a second input -- regions.py: the points against the regions
 of a GeoJSON -- is a row of WITH_INPUT behind it, handled by `select` and `run` after the six: the same columns, and one more that
-fetches the second input for a slide, or says that the slide has none (then nothing is written for it)."""
+fetches the second input for a slide, or says that the slide has none (then nothing is written for it).
+
+AGAINST_CHANCE, between the two, holds the analyses that hold the points against a null model on the same points -- enrichment.py: the
+label-permutation test.  Its rows have the columns of ANALYSES and take no second input; `select` visits ANALYSES, AGAINST_CHANCE and
+WITH_INPUT in that order."""
 import importlib
 import os
 from collections import namedtuple
@@ -80,6 +84,23 @@ ANALYSES = (
 )
 
 
+def _enrichment_said(m, found, p):
+    obs, perm, cn = found
+    z = m.derive(obs, perm)['z']
+    a, b = divmod(int(abs(z).argmax()), len(cn))
+    return (f'{int(obs.sum())} contacts within {p[0]:g} px against {p[1]} label permutations (seed {p[2]}; largest |z|: class {a} next to '
+            f'class {b}, z {z[a, b]:+.2f})')
+
+
+AGAINST_CHANCE = (
+    _analysis('enrichment', 'enrichment',                             # whether the same rows' classes touch more often than chance
+              lambda m, a: (a.enrichment_radius, a.enrichment_perms, a.enrichment_seed),
+              lambda m, p: m.check_args(1, _half(p[0]), p[1], p[2]),
+              lambda m, path, head, found, C, p, ctx: m.write_npz(path, *head, *found, radius_px=p[0], seed=p[2]),
+              _enrichment_said),
+)
+
+
 WITH_INPUT = (
     _analysis('regions', 'regions',                                   # which annotated regions hold the same rows: the census per region
               lambda m, a: (a.nuclei_regions, a.regions_order),
@@ -104,11 +125,12 @@ def _build(an, m, pts, labels, num_classes, params, name, device):
 
 
 def select(args, need_gpu=True):
-    """The parsed arguments of tools/infer_wsi.py -> the selection: ((analysis, params), ..) of the flags given, in the order of ANALYSES.
+    """The parsed arguments of tools/infer_wsi.py -> the selection: ((analysis, params), ..) of the flags given, in the order of ANALYSES, AGAINST_CHANCE
+    and WITH_INPUT.
     SystemExit in the name of the flag when its arguments are unusable and then, with need_gpu, when no GPU is visible.  A flag the
     namespace does not hold is not given."""
     chosen = []
-    for an in ANALYSES + WITH_INPUT:
+    for an in ANALYSES + AGAINST_CHANCE + WITH_INPUT:
         if not getattr(args, an.cli, False):
             continue
         m = module_of(an)

@@ -72,6 +72,16 @@ Output (like the reference, :659-693), for every detection that survives the per
                   `pitch_px`, `origin_px` (the px position of site (0, 0)), `window` (gx0, gy0, W, H in lattice units).  No tissue-area
                   normalisation and no edge correction.  Every other file is the same bytes with and without the flag.  There is no route
                   without a GPU.
+  --nuclei-enrichment: (not in the reference) <id>_nuclei_enrichment.npz beside the documents, from the same rows as --nuclei-graph: whether
+                  nuclei of one class lie next to nuclei of another more often than chance -- the neighbourhood-enrichment permutation
+                  test (histoCAT, squidpy's nhood_enrichment).  The contacts (ordered pairs at most --enrichment-radius px apart, 64 by
+                  default) are counted by class pair under the observed labels and under --enrichment-perms shuffles of the labels over
+                  the same positions (1000 by default; the generator is a function of the row count, --enrichment-seed and the shuffle's
+                  number, so the file is a pure function of the rows IN THEIR ORDER), on rank 0's GPU after the gather
+                  (nuhtc_amd/enrichment.py): `observed` int64 (C, C), `perm_counts` int64 (P, C, C), `class_n`, the derived `mean`, `std`,
+                  `z`, `p_enriched`, `p_depleted`, and `radius_px`, `perms`, `seed`.  No area and no edge correction are needed: the null
+                  model lives on the same points.  Every other file is the same bytes with and without the flag.  There is no route
+                  without a GPU.
   --nuclei-regions PATH: (not in the reference) <id>_nuclei_regions.npz beside the documents, from the same rows as --nuclei-graph: which
                   annotated regions hold each nucleus, and the nuclei of each class inside every region.  PATH is a GeoJSON of Polygon and
                   MultiPolygon features (QuPath annotations, a tissue outline) used for every slide, or a directory holding
@@ -196,6 +206,15 @@ def build_parser():
                    help='kernel radius of --nuclei-density in slide px, a multiple of 0.5 up to 8192 (default 128 px: 32 um at 40x)')
     p.add_argument('--density-pitch', type=float, default=64.0, dest='density_pitch',
                    help='distance between the sites of --nuclei-density in slide px, a multiple of 0.5 (default 64 px)')
+    p.add_argument('--nuclei-enrichment', action='store_true', dest='nuclei_enrichment',
+                   help='also write <id>_nuclei_enrichment.npz: the contacts of the written nuclei by class pair, observed and under label permutations, '
+                        'with z-scores and empirical p-values (the neighbourhood-enrichment test), counted on the GPU; from the rows of --nuclei-graph')
+    p.add_argument('--enrichment-radius', type=float, default=64.0, dest='enrichment_radius',
+                   help='contact radius of --nuclei-enrichment in slide px, a multiple of 0.5 up to 8192 (default 64 px: 16 um at 40x)')
+    p.add_argument('--enrichment-perms', type=int, default=1000, dest='enrichment_perms',
+                   help='label permutations of --nuclei-enrichment, 1..1024 (default 1000)')
+    p.add_argument('--enrichment-seed', type=int, default=0, dest='enrichment_seed',
+                   help='seed of the permutations of --nuclei-enrichment, 0..2**32-1 (default 0)')
     p.add_argument('--nuclei-regions', default=None, dest='nuclei_regions', metavar='PATH',
                    help='also write <id>_nuclei_regions.npz: which regions of a GeoJSON (one file for every slide, or a directory of <slide_id>.geojson) '
                         'hold each written nucleus and the nuclei per class inside every region, exact, built on the GPU; from the rows of --nuclei-graph')
