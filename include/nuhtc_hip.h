@@ -1096,6 +1096,31 @@ int nuhtc_cell_regions(int device, const int32_t* points, const int32_t* labels,
                        const int32_t* edge_region, int64_t E, int64_t G, int slab, int64_t slot_cap, int x_min, int y_min, int x_max, int y_max,
                        int32_t* region, int32_t* depth, uint8_t* on_boundary, int64_t* census, int64_t* slots, void* stream);
 
+/* Margin bands (csrc/cellmargin.hip; nuhtc_amd/margin.py holds the definition and the brute-force restatement `margin_reference`): the
+ * nuclei of each class by distance to the boundary of every region, inside it and outside it -- the invasive-margin profile.  A sibling
+ * of nuhtc_cell_regions with the same points, labels, edges, edge_region, slab, slot_cap / *slots protocol and bounding box, engine-free
+ * like it.  Not in the reference.  nuhtc_config is unchanged (no ABI bump).
+ *   thresholds [B] int32, HOST memory: e_0 < e_1 < .. < e_{B-1} in half pixels, 1 <= e_0, e_{B-1} <= 16384, 1 <= B <= 32.
+ *   slot_cap: an edge has one record per slab of the box that its y-range grown by e_{B-1} meets (nuhtc_amd/margin.py states M exactly).
+ * near(p, a -> b, e), inclusive and in exact integers: with d = b - a, w = p - a, L2 = d.d, s = w.d -- |w|^2 <= e^2 when L2 == 0 or
+ * s <= 0; |p - b|^2 <= e^2 when s >= L2; else (d x w)^2 <= e^2 * L2, a 128-bit unsigned compare (cross < 2^57; e^2 * L2 < 2^85).
+ * band(p, g) = the smallest t with near(p, edge, e_t) for some edge of g, B when none.  inside(p, g) is the even-odd, half-open rule of
+ * nuhtc_cell_regions.
+ *   band_census [G][2][B][C] int64: the points of label c with band(p, g) == t and inside(p, g) == side (0 outside, 1 inside); a point is
+ *     counted for every region it is near, a label outside 0 .. C - 1 nowhere, a band of B nowhere.
+ *   census [G][C] int64: the points of label c inside region g -- the census of nuhtc_cell_regions.
+ *   band [n] int32: the minimum over g of band(p, g), B when none.   band_region [n] int32: the smallest g that attains it, -1 when none.
+ *   band_inside [n] uint8: inside(p, band_region), 0 when there is none.
+ * All five are always fully written on success with M <= slot_cap (n == 0: the two tables are cleared).  The result is a pure function
+ * of the input: bitwise the same on every call.
+ * NUHTC_E_INVALID, before anything is launched and with the outputs untouched: everything nuhtc_cell_regions refuses there, B outside
+ * 1 .. 32, thresholds null, not strictly increasing or outside 1 .. 16384, a null pointer where the count is not 0.
+ * NUHTC_E_INVALID after the first kernels, the outputs still untouched: as nuhtc_cell_regions. */
+int nuhtc_cell_margin(int device, const int32_t* points, const int32_t* labels, int64_t n, int num_classes, const int32_t* edges,
+                      const int32_t* edge_region, int64_t E, int64_t G, const int32_t* thresholds, int B, int slab, int64_t slot_cap, int x_min,
+                      int y_min, int x_max, int y_max, int64_t* band_census, int64_t* census, int32_t* band, int32_t* band_region,
+                      uint8_t* band_inside, int64_t* slots, void* stream);
+
 /* Neighbourhood enrichment of a slide (csrc/cellenrich.hip; nuhtc_amd/enrichment.py holds the definition and the brute-force restatement
  * `enrichment_reference`): the class-pair contact counts of the nucleus centres, observed and under num_perms label permutations -- the
  * integers of the neighbourhood-enrichment permutation test (positions kept, labels shuffled).  Not in the reference.  Engine-free like

@@ -1,8 +1,8 @@
 // The uniform grid over half-pixel points that the per-slide analyses share (cellbin.h; cellgraph.hip, cellspatial.hip, cellcluster.hip,
-// cellmst.hip, cellprox.hip, celldensity.hip, cellregion.hip, cellenrich.hip): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
+// cellmst.hip, cellprox.hip, celldensity.hip, cellregion.hip, cellmargin.hip, cellenrich.hip): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
 // and the (cell, class) key of a point, the squared distance of a pair within reach, and the edge key of the spanning forest.  Header-only,
 // so a host program can exercise them under a sanitizer (tools/dev/cellspatial_host_check.cpp, tools/dev/cellmst_host_check.cpp, tools/dev/cellprox_host_check.cpp,
-// tools/dev/celldensity_host_check.cpp, tools/dev/cellregion_host_check.cpp, tools/dev/cellenrich_host_check.cpp); the kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
+// tools/dev/celldensity_host_check.cpp, tools/dev/cellregion_host_check.cpp, tools/dev/cellmargin_host_check.cpp, tools/dev/cellenrich_host_check.cpp); the kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
 #pragma once
 #include <cstdint>
 
@@ -175,6 +175,87 @@ CELL_HD inline bool region_edge_ok(int ax, int ay, int bx, int by, int region, i
 inline bool region_call_ok(int64_t E, int64_t G, int slab, int64_t slot_cap) {
   return E >= 0 && E <= REGION_MAX_EDGES && G >= 0 && G <= REGION_MAX_REGIONS && slab >= 1 && slab <= CELL_MAX_REACH && slot_cap >= 0 &&
          slot_cap <= REGION_MAX_SLOTS;
+}
+
+// ---- margin bands (cellmargin.hip): "is p within e half pixels of the edge a -> b", for thresholds 1 <= e <= 16384.  The bit budget,
+// stated here once: with d = b - a and w = p - a (every difference below 2^28), L2 = d.d, s = w.d, |w|^2 and |p - b|^2 are sums of two
+// products below 2^56 each, below 2^57 and exact in int64, and so is the cross product d x w.  Past either end of the edge the question
+// is |w|^2 <= e^2 (or |p - b|^2), an int64 compare.  Beside the edge the squared distance is the rational cross^2 / L2 and the question
+// is cross^2 <= e^2 * L2: cross^2 < 2^114, and e^2 <= 2^28 times L2 < 2^57 is below 2^85 -- both sides fit 128 bits, held as two
+// 64-bit words.  Float64 decides about 1 % of designed exact-threshold pairs wrongly (tests/margin_cases.py has one).
+constexpr int MARGIN_MAX_BANDS = 32;
+
+// the full product a * b of two 64-bit words: the one place the 128-bit arithmetic is written
+CELL_HD inline void margin_mul_wide(uint64_t a, uint64_t b, uint64_t* hi, uint64_t* lo) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  *hi = __umul64hi(a, b);
+  *lo = a * b;
+#else
+  const unsigned __int128 p = (unsigned __int128)a * b;
+  *hi = (uint64_t)(p >> 64);
+  *lo = (uint64_t)p;
+#endif
+}
+
+// what the edge a -> b measures of p, once for every threshold: past an end (or on a zero-length edge) *q = the squared distance to
+// that end and *l2 = 0; beside the edge *q = |d x w| and *l2 = L2 > 0, the squared distance being q^2 / l2
+CELL_HD inline void margin_measure(int ax, int ay, int bx, int by, int px, int py, uint64_t* q, uint64_t* l2) {
+  const int64_t dx = bx - ax, dy = by - ay, wx = px - ax, wy = py - ay;
+  const int64_t L2 = dx * dx + dy * dy, s = wx * dx + wy * dy;
+  *l2 = 0;
+  if (L2 == 0 || s <= 0) { *q = (uint64_t)(wx * wx + wy * wy); return; }
+  if (s >= L2) {
+    const int64_t vx = px - bx, vy = py - by;
+    *q = (uint64_t)(vx * vx + vy * vy);
+    return;
+  }
+  const int64_t cr = dx * wy - dy * wx;
+  *q = (uint64_t)(cr < 0 ? -cr : cr);
+  *l2 = (uint64_t)L2;
+}
+
+// is the measured (q, l2) within e?  Inclusive.  l2 == 0: q <= e^2; else q^2 <= e^2 * l2 as (hi, lo) words
+CELL_HD inline bool margin_within(uint64_t q, uint64_t l2, int e) {
+  const uint64_t e2 = (uint64_t)((int64_t)e * e);
+  if (l2 == 0) return q <= e2;
+  uint64_t lh, ll, rh, rl;
+  margin_mul_wide(q, q, &lh, &ll);
+  margin_mul_wide(e2, l2, &rh, &rl);
+  return lh < rh || (lh == rh && ll <= rl);
+}
+
+CELL_HD inline bool margin_near(int ax, int ay, int bx, int by, int px, int py, int e) {
+  uint64_t q, l2;
+  margin_measure(ax, ay, bx, by, px, py, &q, &l2);
+  return margin_within(q, l2, e);
+}
+
+// can p be within r of an edge with the bounding box x0 .. x1, y0 .. y1?  Four compares, before any product
+CELL_HD inline bool margin_box_near(int x0, int y0, int x1, int y1, int px, int py, int r) {
+  return px >= x0 - r && px <= x1 + r && py >= y0 - r && py <= y1 + r;
+}
+
+// region_slab_range with the edge's y-range GROWN by R = the largest threshold: the slabs whose points can cross the edge or lie within
+// R of it.  No record when the grown range misses the box in y or the edge lies wholly left of x_min - R (it can be neither crossed nor
+// near); an edge right of the box stays for the parity.  R == 0 is region_slab_range.  |v| < 2^27 and R <= 2^14: no sum overflows.
+CELL_HD inline bool margin_slab_range(int ax, int ay, int bx, int by, int R, int x_min, int y_min, int y_max, int side, int* s0, int* s1) {
+  const int ylo = (ay < by ? ay : by) - R, yhi = (ay < by ? by : ay) + R;
+  if (yhi < y_min || ylo > y_max || (ax < x_min - R && bx < x_min - R)) return false;
+  *s0 = ((ylo > y_min ? ylo : y_min) - y_min) / side;
+  *s1 = ((yhi < y_max ? yhi : y_max) - y_min) / side;
+  return true;
+}
+
+// the thresholds row: 1 .. 32 of them, strictly increasing, within 1 .. 16384 half pixels
+inline bool margin_thresholds_ok(const int32_t* t, int B) {
+  if (!t || B < 1 || B > MARGIN_MAX_BANDS || t[0] < 1 || t[B - 1] > CELL_MAX_REACH) return false;
+  for (int k = 1; k < B; ++k)
+    if (t[k] <= t[k - 1]) return false;
+  return true;
+}
+
+inline bool margin_call_ok(int64_t E, int64_t G, int slab, int64_t slot_cap, const int32_t* thresholds, int B) {
+  return region_call_ok(E, G, slab, slot_cap) && margin_thresholds_ok(thresholds, B);
 }
 
 // ---- the front checks of an entry point, before anything is launched: the limits every analysis shares (its own n limit passed in),

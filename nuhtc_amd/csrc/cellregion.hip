@@ -14,16 +14,10 @@
 //   geometry   on the HOST from the caller's bounding box (cell_grid_side): cells of side >= slab, at most 2^22 of them.  A grid row is
 //              a horizontal SLAB of the box, and with one key per cell its points are one contiguous run of the records.
 //   binning    cellbin.h, reach slab, one key per cell.
-//   edges      rg_check_kernel  every edge against the limits (a vertex outside +-2^27, a region outside 0 .. G - 1 or below the one in
-//                               front of it raise the binning's flag) and the number of slabs it meets (region_slab_range: clipped to the
-//                               box; an edge wholly above, below or left of the box meets none), summed in 64 bits: M, the (edge, slab)
-//                               records the call needs.  Every later kernel first compares M with the caller's slot_cap (rg_go): no int32
-//                               sees M, or a sum of slab counts, before that.
-//              rg_count_kernel  the edges per slab (atomics), then exscan_launch of cellbin.h over the slabs.
-//              rg_emit_kernel   the records (edge, slab) into their slab's segment, in atomic arrival order.
-//              rg_place_kernel  every record to its final place: the segment's start plus the NUMBER of records of the segment with a
-//                               smaller edge index.  No sort and nothing left of the arrival order: a segment is in edge order, hence
-//                               grouped by region, ascending.
+//   edges      celledges.h (shared with cellmargin.hip), with region_slab_range as the slabs an edge has a record in: clipped to the
+//              box; an edge wholly above, below or left of the box meets none.  rg_check_kernel states M, the (edge, slab) records the
+//              call needs, and every later kernel first compares M with the caller's slot_cap (rg_go); count, scan, emit, place leave
+//              every slab's records in edge order, hence grouped by region, ascending.
 //   crossing   rg_cross_kernel  one workgroup per 256 consecutive point records.  For each slab that holds some of them (the records are
 //                               in row order, so these are few) the slab's edge records go through LDS 256 at a time -- coordinates and
 //                               region gathered once per workgroup -- and every thread of that slab takes each staged edge by a broadcast
@@ -46,7 +40,7 @@
 #include <climits>
 #include <cstring>
 
-#include "cellbin.h"
+#include "celledges.h"
 
 namespace {
 
@@ -68,53 +62,8 @@ struct CellRegionArgs {
   unsigned long long* census;         // [G][C]
 };
 
-// may this call write?  No edge or point was refused, and the records fit the caller's cap.  Uniform over the grid.
-__device__ __forceinline__ bool rg_go(const CellRegionArgs& a) { return *a.b.flag == 0 && *a.total <= a.slot_cap; }
-
 __device__ __forceinline__ bool rg_range(const CellRegionArgs& a, const int4 e, int* s0, int* s1) {
   return region_slab_range(e.x, e.y, e.z, e.w, a.b.x_min, a.b.y_min, a.b.y_max, a.b.side, s0, s1);
-}
-
-__global__ __launch_bounds__(256) void rg_check_kernel(CellRegionArgs a) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  int nslab = 0;
-  if (e < a.E) {
-    const int4 ed = a.edges[e];
-    if (!region_edge_ok(ed.x, ed.y, ed.z, ed.w, a.edge_region[e], e ? a.edge_region[e - 1] : 0, a.G)) {
-      *a.b.flag = 1;
-    } else if (a.have_grid) {
-      int s0, s1;
-      if (rg_range(a, ed, &s0, &s1)) nslab = s1 - s0 + 1;        // at most 2^22 rows: 64 lanes of them stay below 2^31
-    }
-  }
-  const int sum = wave_sum(nslab);
-  if ((threadIdx.x & 63) == 0 && sum) atomicAdd(a.total, (unsigned long long)sum);
-}
-
-__global__ __launch_bounds__(256) void rg_count_kernel(CellRegionArgs a) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= a.E || !rg_go(a)) return;
-  int s0, s1;
-  if (!rg_range(a, a.edges[e], &s0, &s1)) return;
-  for (int s = s0; s <= s1; ++s) atomicAdd(&a.slab_count[s], 1);
-}
-
-__global__ __launch_bounds__(256) void rg_emit_kernel(CellRegionArgs a) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= a.E || !rg_go(a)) return;
-  int s0, s1;
-  if (!rg_range(a, a.edges[e], &s0, &s1)) return;
-  for (int s = s0; s <= s1; ++s) a.emitted[a.slab_start[s] + atomicSub(&a.slab_count[s], 1) - 1] = make_int2(e, s);
-}
-
-__global__ __launch_bounds__(256) void rg_place_kernel(CellRegionArgs a) {
-  const unsigned long long j = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
-  if (!rg_go(a) || j >= *a.total) return;
-  const int2 me = a.emitted[j];
-  const int k0 = a.slab_start[me.y], k1 = a.slab_start[me.y + 1];
-  int rank = 0;
-  for (int k = k0; k < k1; ++k) rank += a.emitted[k].x < me.x;     // an edge is in a segment once: the ranks are a permutation
-  a.slots[k0 + rank] = me.x;
 }
 
 __global__ __launch_bounds__(256) void rg_zero_kernel(CellRegionArgs a) {
@@ -204,56 +153,20 @@ extern "C" int nuhtc_cell_regions(int device, const int32_t* points, const int32
   a.E = (int)E; a.G = (int)G; a.C = num_classes; a.slot_cap = (unsigned long long)slot_cap;
   a.region = region; a.depth = depth; a.on_boundary = on_boundary; a.census = reinterpret_cast<unsigned long long*>(census);
   DevScratch tmp;      // every temporary of the call, freed on the way out
-  int nchunk = 0, schunk = 1;
-  if (n > 0) {
-    nchunk = cellbin_setup(a.b, points, labels, (int)n, x_min, y_min, x_max, y_max, slab, REGION_MAX_CELLS, 1, tmp, st);
-    if (!nchunk) return NUHTC_E_HIP;
-    a.have_grid = 1;
-    schunk = (a.b.ncy + 1 + CB_CHUNK - 1) / CB_CHUNK;            // + 1: the entry behind the last slab holds the total; at most 257
-  } else {
-    a.b.flag = tmp.alloc<int>(sizeof(int));
-    if (!tmp.ok() || hipMemsetAsync(a.b.flag, 0, sizeof(int), st) != hipSuccess) return NUHTC_E_HIP;
-  }
-  // ONE allocation for the tables of this file, carved in 256-byte steps: the slab counts with M behind them (one memset), the slab
-  // starts, the scan's chunk bases and the two record tables
-  const size_t step = 256, slab_bytes = (size_t)schunk * CB_CHUNK * sizeof(int), cap = (size_t)(slot_cap > 0 ? slot_cap : 1);
-  const size_t emit_up = (cap * sizeof(int2) + step - 1) / step * step, slot_up = (cap * sizeof(int) + step - 1) / step * step;
-  const size_t bytes = 2 * slab_bytes + 2 * step + 1024 * sizeof(int) + emit_up + slot_up;
-  char* base = tmp.alloc<char>(bytes);
-  if (!tmp.ok()) return NUHTC_E_HIP;
-  size_t at = 0;
-  auto carve = [&](size_t b) { char* p = base + at; at += (b + step - 1) / step * step; return p; };
-  a.slab_count = reinterpret_cast<int*>(carve(slab_bytes));
-  a.total = reinterpret_cast<unsigned long long*>(carve(sizeof(unsigned long long)));
-  a.slab_start = reinterpret_cast<int*>(carve(slab_bytes));
-  int* chunk_base = reinterpret_cast<int*>(carve(1024 * sizeof(int)));
-  a.emitted = reinterpret_cast<int2*>(carve(cap * sizeof(int2)));
-  a.slots = reinterpret_cast<int*>(carve(cap * sizeof(int)));
-  if (at > bytes) return NUHTC_E_HIP;
-  if (hipMemsetAsync(a.slab_count, 0, slab_bytes + step, st) != hipSuccess) return NUHTC_E_HIP;
-  const unsigned eb = (unsigned)((E + 255) / 256);
+  int nchunk, schunk, *chunk_base;
+  if (!edge_tables(a, points, labels, n, x_min, y_min, x_max, y_max, slab, slot_cap, tmp, st, &nchunk, &schunk, &chunk_base)) return NUHTC_E_HIP;
   if (n > 0) {
     ProfScope ps("cell_regions_bin", 0, 0, st);
     cellbin_launch(a.b, nchunk, st);
   }
   {
     ProfScope ps("cell_regions_edges", 0, 0, st);
-    if (eb) hipLaunchKernelGGL(rg_check_kernel, dim3(eb), dim3(256), 0, st, a);
-    if (n > 0) {
-      if (eb) hipLaunchKernelGGL(rg_count_kernel, dim3(eb), dim3(256), 0, st, a);
-      exscan_launch(ExScan{a.slab_count, a.slab_start, chunk_base}, schunk, st);
-      if (eb) hipLaunchKernelGGL(rg_emit_kernel, dim3(eb), dim3(256), 0, st, a);
-      if (eb && slot_cap > 0) hipLaunchKernelGGL(rg_place_kernel, dim3((unsigned)((slot_cap + 255) / 256)), dim3(256), 0, st, a);
-    }
+    edge_launch(a, E, n, slot_cap, schunk, chunk_base, st);
   }
   {
     ProfScope ps("cell_regions_cross", 0, 0, st);
     if (G > 0) hipLaunchKernelGGL(rg_zero_kernel, dim3((unsigned)((G * num_classes + 255) / 256)), dim3(256), 0, st, a);
     if (n > 0) hipLaunchKernelGGL(rg_cross_kernel, dim3((unsigned)((n + REGION_STAGE - 1) / REGION_STAGE)), dim3(REGION_STAGE), 0, st, a);
   }
-  unsigned long long h_total = 0;
-  if (hipMemcpyAsync(&h_total, a.total, sizeof(h_total), hipMemcpyDeviceToHost, st) != hipSuccess) return NUHTC_E_HIP;
-  const int rc = cellbin_finish(a.b, st);                // synchronises: h_total has arrived
-  if (rc == 0) *slots = (int64_t)h_total;
-  return rc;
+  return edge_finish(a, st, slots);
 }

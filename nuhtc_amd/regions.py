@@ -39,10 +39,12 @@ With n == 0 or G == 0, region is all -1 and the others are zeros.
 `regions_reference` is the brute-force int64 restatement (every point against every edge, no grid): the oracle the device result must EQUAL.
 `derive` makes the float64 side on the host from the area the file states.
 
-Out of scope.  The distance from a nucleus to the region boundary (invasive-margin bands): the squared distance to a segment is the
-rational cross**2 / len**2, and comparing two such values takes more than 128 bits at these coordinate ranges -- there is no exact integer
-statement of it to test against.  Self-intersecting or improperly nested rings are not detected: even-odd is still well defined on them,
-but `area2` is then not the area of what is inside."""
+Beside it.  The distance from a nucleus to the region boundary as BANDS (the invasive-margin profile) is margin.py: "is the distance at
+most e" is cross**2 <= e**2 * len**2, which fits 128 bits for e <= 16384 half pixels, so bands are exact.  Still out of scope: a
+per-nucleus distance VALUE (the squared distance to a segment is the rational cross**2 / len**2, and comparing two such values takes more
+than 128 bits at these coordinate ranges) and the area of a band (the area of an offset polygon is no integer statement).
+Self-intersecting or improperly nested rings are not detected: even-odd is still well defined on them, but `area2` is then not the area
+of what is inside."""
 import json
 import os
 from collections import namedtuple
@@ -202,6 +204,18 @@ def as_edges(edges, edge_region, G, what='regions'):
     return e, er
 
 
+def inside_block(px, py, e, start):
+    """The even-odd, half-open rule of the definition for a block of points against every region: px, py int64 (b, 1), e int64 (E, 4),
+    start int (G + 1,) the run of every region's edges -> bool (b, G).  The ONE numpy statement of it (margin.py takes its sides here)."""
+    ax, ay, bx, by = e[:, 0], e[:, 1], e[:, 2], e[:, 3]
+    up = ay < by
+    lx, ly, hx, hy = np.where(up, ax, bx), np.where(up, ay, by), np.where(up, bx, ax), np.where(up, by, ay)
+    crossed = ((ay[None] <= py) != (by[None] <= py)) & ((hx - lx)[None] * (py - ly[None]) - (hy - ly)[None] * (px - lx[None]) > 0)
+    cs = np.zeros((len(px), len(e) + 1), np.int64)
+    np.cumsum(crossed, 1, out=cs[:, 1:])
+    return ((cs[:, start[1:]] - cs[:, start[:-1]]) & 1).astype(bool)        # odd crossings of the region's run of edges
+
+
 def regions_reference(points, labels, num_classes, edges, edge_region, G, block=1024):
     """The definition in int64: points int (n, 2) half pixels, labels int (n,), edges int (E, 4), edge_region int (E,) ->
     (region int32 (n,), depth int32 (n,), on_boundary uint8 (n,), census int64 (G, C)).  Every point against EVERY edge, no grid, `block`
@@ -216,18 +230,13 @@ def regions_reference(points, labels, num_classes, edges, edge_region, G, block=
         return region, depth, on, census
     e = e.astype(np.int64)
     ax, ay, bx, by = e[:, 0], e[:, 1], e[:, 2], e[:, 3]
-    up = ay < by
-    lx, ly, hx, hy = np.where(up, ax, bx), np.where(up, ay, by), np.where(up, bx, ax), np.where(up, by, ay)
-    x0, x1, y0, y1 = np.minimum(ax, bx), np.maximum(ax, bx), ly, hy
+    x0, x1, y0, y1 = np.minimum(ax, bx), np.maximum(ax, bx), np.minimum(ay, by), np.maximum(ay, by)
     start = np.searchsorted(er, np.arange(G + 1))
     block = max(1, min(int(block), (1 << 21) // max(E, G)))                  # a temporary of at most 16 MiB
     known = (lab >= 0) & (lab < C)
     for i0 in range(0, n, block):
         px, py = p[i0:i0 + block, 0, None], p[i0:i0 + block, 1, None]
-        crossed = ((ay[None] <= py) != (by[None] <= py)) & ((hx - lx)[None] * (py - ly[None]) - (hy - ly)[None] * (px - lx[None]) > 0)
-        cs = np.zeros((len(px), E + 1), np.int64)
-        np.cumsum(crossed, 1, out=cs[:, 1:])
-        inside = ((cs[:, start[1:]] - cs[:, start[:-1]]) & 1).astype(bool)    # (b, G): odd crossings of the region's run of edges
+        inside = inside_block(px, py, e, start)
         depth[i0:i0 + block] = inside.sum(1)
         region[i0:i0 + block] = np.where(inside.any(1), G - 1 - np.argmax(inside[:, ::-1], 1), -1)
         touch = ((bx - ax)[None] * (py - ay[None]) - (by - ay)[None] * (px - ax[None]) == 0) & (px >= x0[None]) & (px <= x1[None]) & (py >= y0[None]) & (py <= y1[None])

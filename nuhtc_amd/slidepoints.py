@@ -1,5 +1,5 @@
 """The per-slide point analyses of the slide path as ONE table: which flag of tools/infer_wsi.py selects each, how its arguments become
-the parameters of its module (cellgraph, spatial, clusters, mst, proximity, density, enrichment, regions: they hold the definitions), which file it writes
+the parameters of its module (cellgraph, spatial, clusters, mst, proximity, density, enrichment, regions, margin: they hold the definitions), which file it writes
 beside the documents and what the closing message says of it.  cellpoints.py is what the modules share and is imported by them; this
 module imports them, one at a time and only when its flag is given.
 
@@ -8,8 +8,9 @@ arguments into a selection, `run` works a selection off on one point set; both n
 check_args / build / write_npz and one row here (plus its argparse lines in the tool).
 
 ANALYSES is the table of the analyses of the points ALONE.  An analysis with a second input -- regions.py: the points against the regions
-of a GeoJSON -- is a row of WITH_INPUT behind it, handled by `select` and `run` after the six: the same columns, and one more that
-fetches the second input for a slide, or says that the slide has none (then nothing is written for it).
+of a GeoJSON, and margin.py: the same points by distance to the regions' boundaries -- is a row of WITH_INPUT behind it, handled by
+`select` and `run` after the six: the same columns, one more that fetches the second input for a slide, or says that the slide has none
+(then nothing is written for it), and two that say how the input is read and what `build` takes behind it.
 
 AGAINST_CHANCE, between the two, holds the analyses that hold the points against a null model on the same points -- enrichment.py: the
 label-permutation test.  Its rows have the columns of ANALYSES and take no second input; `select` visits ANALYSES, AGAINST_CHANCE and
@@ -27,8 +28,9 @@ from . import cellpoints
 # write    (module, path, (nuclei_id, xy, label), what build returned, num_classes, params, context) -> write_npz
 # said     (module, what build returned, params) -> the clause of the closing message, without ' in <file>'
 # second   rows of WITH_INPUT only: (module, params, slide name) -> the second input `build` takes behind num_classes, or None when the
-#          slide has none; `missing` (params, slide name) -> the clause that says so
-Analysis = namedtuple('Analysis', 'cli flag suffix module params check write said second missing', defaults=(None, None))
+#          slide has none; `missing` (params, slide name) -> the clause that says so; `order` (params) -> the order the module's
+#          read_geojson puts the regions in; `more` (params) -> what `build` takes behind (edges, edge_region, G)
+Analysis = namedtuple('Analysis', 'cli flag suffix module params check write said second missing order more', defaults=(None, None, None, None))
 
 BY_NAMES = ('any', 'class')                   # the modules' BY, backwards
 _half = cellpoints.half_pixel_radius
@@ -109,7 +111,17 @@ WITH_INPUT = (
               lambda m, found, p: (f'{int((found[1][1] > 0).sum())} nuclei inside {len(found[0].names)} regions of {os.path.basename(found[2])} '
                                    f'({int(found[1][2].sum())} on a boundary, order {p[1]})'))
     ._replace(second=lambda m, p, name: m.source_for(p[0], name),
-              missing=lambda p, name: f'no {name}.geojson in {p[0]}: no {name}_nuclei_regions.npz'),
+              missing=lambda p, name: f'no {name}.geojson in {p[0]}: no {name}_nuclei_regions.npz',
+              order=lambda p: p[1], more=lambda p: ()),
+    _analysis('margin', 'margin',                                     # how far from the regions' boundaries the same rows lie: the bands per region
+              lambda m, a: (a.nuclei_margin, m.thresholds_from_step(a.margin_step, a.margin_bands)),
+              lambda m, p: m.source_check(p[0]),
+              lambda m, path, head, found, C, p, ctx: m.write_npz(path, *head, *found[1], p[1], found[0]),
+              lambda m, found, p: (f'{int((found[1][2] < len(p[1])).sum())} nuclei within {p[1][-1] / 2:g} px of the boundaries of {len(found[0].names)} '
+                                   f'regions of {os.path.basename(found[2])} ({len(p[1])} bands)'))
+    ._replace(second=lambda m, p, name: m.source_for(p[0], name),
+              missing=lambda p, name: f'no {name}.geojson in {p[0]}: no {name}_nuclei_margin.npz',
+              order=lambda p: 'file', more=lambda p: (p[1],)),
 )
 
 
@@ -120,8 +132,8 @@ def _build(an, m, pts, labels, num_classes, params, name, device):
     source = an.second(m, params, name)
     if source is None:
         return None
-    table = m.read_geojson(source, params[1])
-    return table, m.build(pts, labels, num_classes, table.edges, table.edge_region, len(table.names), device=device), source
+    table = m.read_geojson(source, an.order(params))
+    return table, m.build(pts, labels, num_classes, table.edges, table.edge_region, len(table.names), *an.more(params), device=device), source
 
 
 def select(args, need_gpu=True):

@@ -92,6 +92,18 @@ Output (like the reference, :659-693), for every detection that survives the per
                   `n_inside`, `n_outside`, `class_share_inside`, and the regions themselves: `names`, `ring_start`, `edges`, `edge_region`,
                   `area2`, `order`.  The area is the one the file states (shoelace; not verified).  Every other file is the same bytes
                   with and without the flag.  There is no route without a GPU.
+  --nuclei-margin PATH: (not in the reference) <id>_nuclei_margin.npz beside the documents, from the same rows as --nuclei-graph: the nuclei
+                  of each class by distance to the boundary of every region, inside it and outside it -- the invasive-margin profile
+                  ("distance to annotation" in bands).  PATH as for --nuclei-regions (a GeoJSON for every slide, or a directory of
+                  <slide_id>.geojson; a slide without a file gets no output and a clause saying so), the regions in file order.  The bands
+                  are --margin-bands steps of --margin-step px (10 of 50 by default: 0-50, 50-100, ..; step x bands <= 8192 px).  "Is the
+                  distance at most e" is decided in exact integers on half pixels, inclusive, on rank 0's GPU after the gather
+                  (nuhtc_amd/margin.py): `band_census` int64 (G, 2, B, C) [region][0 outside / 1 inside][band][class], `census` int64
+                  (G, C) (the nuclei inside, as --nuclei-regions counts them), per nucleus `band` (the nearest band over all regions, B:
+                  none), `band_region`, `band_inside`, `thresholds`, the derived `band_edges_px`, `inside_beyond`, `profile`,
+                  `class_fraction`, `n_near`, and the regions themselves: `names`, `ring_start`, `edges`, `edge_region`, `area2`.  No
+                  per-nucleus distance value and no density per band (a band's area is no integer statement).  Every other file is the
+                  same bytes with and without the flag.  There is no route without a GPU.
   --nuclei-morph: (the reference's tools/wsi_feat_extract.py table, computed on the GPU) <id>_nuclei_morph.npz beside the documents, for the
                   same rows: `columns` and `values` float64 (n, F) -- size, shape, orientation, position and haematoxylin-intensity features
                   under histomicstk's names, derived on the host (nuhtc_amd/nucmorph.py derive) from the integers every rank's GPU measured
@@ -220,6 +232,13 @@ def build_parser():
                         'hold each written nucleus and the nuclei per class inside every region, exact, built on the GPU; from the rows of --nuclei-graph')
     p.add_argument('--regions-order', choices=('file', 'area'), default='file', dest='regions_order',
                    help="the regions of --nuclei-regions in file order ('file') or by descending area, so that a nucleus's region is the innermost ('area')")
+    p.add_argument('--nuclei-margin', default=None, dest='nuclei_margin', metavar='PATH',
+                   help='also write <id>_nuclei_margin.npz: the written nuclei per class by distance band to the boundary of every region of a GeoJSON '
+                        '(PATH as for --nuclei-regions), inside and outside it, exact, built on the GPU; from the rows of --nuclei-graph')
+    p.add_argument('--margin-step', type=float, default=50.0, dest='margin_step',
+                   help='width of a band of --nuclei-margin in slide px, a multiple of 0.5 (default 50 px)')
+    p.add_argument('--margin-bands', type=int, default=10, dest='margin_bands',
+                   help='bands of --nuclei-margin on either side of a boundary, 1..32, step x bands at most 8192 px (default 10)')
     return p
 
 
