@@ -1064,6 +1064,35 @@ int nuhtc_cell_proximity(int device, const int32_t* points, const int32_t* label
 int nuhtc_cell_density(int device, const int32_t* points, const int32_t* labels, int64_t n, int num_classes, int h, int s, int gx0, int gy0,
                        int W, int H, int x_min, int y_min, int x_max, int y_max, int32_t* count, int64_t* weight, void* stream);
 
+/* Nucleus territories of a slide (csrc/cellterritory.hip; nuhtc_amd/territory.py holds the definition and the brute-force restatement
+ * `territory_reference`): the nearest-nucleus raster on the lattice of the density maps -- which nucleus, and so which class, each
+ * piece of the plane belongs to (the Voronoi family in raster form).  Not in the reference.  Engine-free like the density call: every
+ * array is device memory of `device`, the call allocates and frees its own scratch, runs on `stream` and synchronises it before
+ * returning.  nuhtc_config is unchanged (no ABI bump).
+ *   points [n][2] int32: node positions in HALF pixels, |p| < 2^27.  labels [n] int32.  0 <= n <= 2^24.  num_classes C: 1 .. 14.
+ *   reach R: half pixels, 1 .. 16384.  s: the pitch in half pixels, 1 .. 2^20.
+ *   gx0, gy0, W, H: the window in lattice units; W, H >= 1, W * H <= 2^28, and every site coordinate |g * s| < 2^28 (checked in 64 bits).
+ *   x_min, y_min, x_max, y_max: the bounding box of the points (inclusive), computed by the caller on the host (ignored when n == 0).
+ * Site (u, v) lies at q = ((gx0 + u) * s, (gy0 + v) * s).  The rows with a label in 0 .. C - 1 compete; any other row owns nothing and
+ * blocks nothing.
+ *   owner [H][W] int32: the competitor i that minimises (d2(q, p_i), i) among those with d2 <= R * R (inclusive; a tie goes to the
+ *     smaller row), or -1.  It does not depend on the window: a sub-window is a slice of the full map.
+ *   nearest_d2 [H][W] int32: that d2, or -1.
+ * The tallies are over the window (a site's 4-neighbours are those inside it) and are zeroed by the call:
+ *   area [n] int32: the sites a row owns.  border [n] int32: its sites with a 4-neighbour whose owner differs (-1 differs).
+ *   open [n] int32, 0 / 1: the row owns a site on the window's outer row or column, or one with a 4-neighbour nobody owns.
+ *   contact [C][C] int64: over every ordered pair (site, 4-neighbour) with owners i != j, both >= 0, one count at [label_i][label_j].
+ *   class_sites [C] int64: the sites owned by each class.  free_sites [1] int64: the sites nobody owns.
+ * All arithmetic is integer: q - p is an exact int32, the box test against R comes before the products, d2 <= 2^28, and (d2, row) is one
+ * 64-bit key.  With n == 0 the maps are -1, the tables zero and free_sites = W * H.  A pure function of the input: bitwise the same on
+ * every call.
+ * NUHTC_E_INVALID, before anything is launched and with the outputs untouched: n, num_classes, reach, s or the window out of range, a
+ * null pointer (the maps and the three tables always, the others with n > 0), with n > 0 a bounding box that is empty or reaches +-2^27.
+ * NUHTC_E_INVALID after the binning, the outputs still untouched: a point lies outside the stated bounding box. */
+int nuhtc_cell_territory(int device, const int32_t* points, const int32_t* labels, int64_t n, int num_classes, int reach, int s, int gx0,
+                         int gy0, int W, int H, int x_min, int y_min, int x_max, int y_max, int32_t* owner, int32_t* nearest_d2, int32_t* area,
+                         int32_t* border, int32_t* open, int64_t* contact, int64_t* class_sites, int64_t* free_sites, void* stream);
+
 /* Nuclei by region (csrc/cellregion.hip; nuhtc_amd/regions.py holds the definition and the brute-force restatement `regions_reference`):
  * an exact point-in-polygon census of the nucleus centres against annotated regions -- "how many nuclei of each class lie in this
  * region".  Not in the reference.  Engine-free like the density call: every pointer but `slots` is device memory of `device`, the call

@@ -1,8 +1,8 @@
 // The uniform grid over half-pixel points that the per-slide analyses share (cellbin.h; cellgraph.hip, cellspatial.hip, cellcluster.hip,
-// cellmst.hip, cellprox.hip, celldensity.hip, cellregion.hip, cellmargin.hip, cellenrich.hip): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
+// cellmst.hip, cellprox.hip, celldensity.hip, cellterritory.hip, cellregion.hip, cellmargin.hip, cellenrich.hip): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
 // and the (cell, class) key of a point, the squared distance of a pair within reach, and the edge key of the spanning forest.  Header-only,
 // so a host program can exercise them under a sanitizer (tools/dev/cellspatial_host_check.cpp, tools/dev/cellmst_host_check.cpp, tools/dev/cellprox_host_check.cpp,
-// tools/dev/celldensity_host_check.cpp, tools/dev/cellregion_host_check.cpp, tools/dev/cellmargin_host_check.cpp, tools/dev/cellenrich_host_check.cpp); the kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
+// tools/dev/celldensity_host_check.cpp, tools/dev/cellregion_host_check.cpp, tools/dev/cellmargin_host_check.cpp, tools/dev/cellenrich_host_check.cpp, tools/dev/cellterritory_host_check.cpp); the kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
 #pragma once
 #include <cstdint>
 
@@ -121,6 +121,51 @@ CELL_HD inline bool dens_route_staged(int s, int h, int side) { return (long lon
 // the window of sites: W, H >= 1, W * H <= 2^24, and every site coordinate within +-2^28, all in 64 bits
 inline bool dens_window_ok(int s, int gx0, int gy0, int W, int H) {
   if (s < 1 || s > DENS_MAX_PITCH || W < 1 || H < 1 || (int64_t)W * H > DENS_MAX_SITES) return false;
+  const int64_t lim = DENS_SITE_LIMIT;
+  const int64_t xa = (int64_t)gx0 * s, xb = ((int64_t)gx0 + W - 1) * s, ya = (int64_t)gy0 * s, yb = ((int64_t)gy0 + H - 1) * s;
+  return xa > -lim && xa < lim && xb > -lim && xb < lim && ya > -lim && ya < lim && yb > -lim && yb < lim;
+}
+
+// ---- nucleus territories (cellterritory.hip): the sites of the density rasters again, but each site keeps ONE point -- the argmin of
+// (d2, row) over the points with a label in 0 .. C - 1 within the reach R (inclusive) -- instead of a sum over all of them.  The bit budget,
+// stated here once: the differences q - p are exact int32 as above; the box test against R comes BEFORE the products (cell_pair_d2), so
+// d2 <= R * R <= 2^28, 29 bits; a row is < 2^24.  (d2, row) packs into one 64-bit word with d2 in the high half, so the unsigned order of
+// the words IS the lexicographic order of the pairs and the argmin is one compare; TERR_NO_KEY, all ones, is above every key.  One int32
+// per site and map, so the window may hold 2^28 sites (density: 12 C bytes per site, 2^24); `area` <= 2^28 is int32.  The tally of a
+// workgroup is a 32-bit table [(C + 1)][(C + 1)], class C being "none": a site adds at most 4 to one entry (its four neighbours) and 1 to
+// its census entry, so a workgroup that took EVERY site of the largest window holds at most 4 * 2^28 = 2^30 in an entry: the table is
+// flushed once, at the end, and cannot overflow (terr_table_fits); the int64 outputs hold 4 * 2^28 with room to spare.
+constexpr int64_t TERR_MAX_SITES = (int64_t)1 << 28;
+constexpr unsigned long long TERR_NO_KEY = ~0ull;
+constexpr int TERR_TABLE_WORDS = (CELL_MAX_CLASSES + 1) * (CELL_MAX_CLASSES + 1);
+constexpr int TERR_PER_SITE = 4;                       // the most one site adds to one entry of the tally table
+
+CELL_HD inline unsigned long long terr_key(int d2, int row) { return ((unsigned long long)(unsigned)d2 << 32) | (unsigned long long)(unsigned)row; }
+CELL_HD inline int terr_key_d2(unsigned long long key) { return key == TERR_NO_KEY ? -1 : (int)(key >> 32); }
+CELL_HD inline int terr_key_row(unsigned long long key) { return key == TERR_NO_KEY ? -1 : (int)(key & 0xffffffffull); }
+
+// the key a point at (dx, dy) from a site offers, or TERR_NO_KEY when it does not compete (its label is outside 0 .. C - 1) or is out
+// of reach (R2 = R * R; inclusive)
+CELL_HD inline unsigned long long terr_offer(int dx, int dy, int label, int row, int C, int R, int R2) {
+  if ((unsigned)label >= (unsigned)C) return TERR_NO_KEY;
+  const int d2 = cell_pair_d2(dx, dy, R, R2);
+  return d2 < 0 ? TERR_NO_KEY : terr_key(d2, row);
+}
+
+// the tally table of a workgroup: entry [a][b] with a, b < C counts the ordered (site, 4-neighbour) pairs whose owners differ and have the
+// classes a and b; column C ("none") holds the census of the sites: [a][C] the sites owned by class a, [C][C] the sites nobody owns.
+// Row C is otherwise unused: a site nobody owns is in no contact.
+CELL_HD inline int terr_table_at(int a, int b, int C) { return a * (C + 1) + b; }
+CELL_HD inline bool terr_table_fits(int64_t sites_of_a_workgroup) { return sites_of_a_workgroup * TERR_PER_SITE <= (int64_t)0xffffffffll; }
+static_assert(TERR_MAX_SITES * TERR_PER_SITE <= (int64_t)0xffffffffll, "one flush at the end of the tally kernel is enough");
+
+// which kernel takes the sites: the rule of dens_route_staged (the two sweeps test the same records as density's two; measured on both
+// sides of the rule: profiles/cell_territory.json)
+CELL_HD inline bool terr_route_staged(int s, int R, int side) { return dens_route_staged(s, R, side); }
+
+// the window of sites: dens_window_ok with this analysis' own cap, W * H <= 2^28
+inline bool terr_window_ok(int s, int gx0, int gy0, int W, int H) {
+  if (s < 1 || s > DENS_MAX_PITCH || W < 1 || H < 1 || (int64_t)W * H > TERR_MAX_SITES) return false;
   const int64_t lim = DENS_SITE_LIMIT;
   const int64_t xa = (int64_t)gx0 * s, xb = ((int64_t)gx0 + W - 1) * s, ya = (int64_t)gy0 * s, yb = ((int64_t)gy0 + H - 1) * s;
   return xa > -lim && xa < lim && xb > -lim && xb < lim && ya > -lim && ya < lim && yb > -lim && yb < lim;

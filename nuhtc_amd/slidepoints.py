@@ -1,5 +1,5 @@
 """The per-slide point analyses of the slide path as ONE table: which flag of tools/infer_wsi.py selects each, how its arguments become
-the parameters of its module (cellgraph, spatial, clusters, mst, proximity, density, enrichment, regions, margin: they hold the definitions), which file it writes
+the parameters of its module (cellgraph, spatial, clusters, mst, proximity, density, territory, enrichment, regions, margin: they hold the definitions), which file it writes
 beside the documents and what the closing message says of it.  cellpoints.py is what the modules share and is imported by them; this
 module imports them, one at a time and only when its flag is given.
 
@@ -13,11 +13,17 @@ of a GeoJSON, and margin.py: the same points by distance to the regions' boundar
 (then nothing is written for it), and two that say how the input is read and what `build` takes behind it.
 
 AGAINST_CHANCE, between the two, holds the analyses that hold the points against a null model on the same points -- enrichment.py: the
-label-permutation test.  Its rows have the columns of ANALYSES and take no second input; `select` visits ANALYSES, AGAINST_CHANCE and
-WITH_INPUT in that order."""
+label-permutation test.  Its rows have the columns of ANALYSES and take no second input.
+
+OF_THE_PLANE, directly behind ANALYSES, holds the analyses that ask about the plane BETWEEN the points -- territory.py: which nucleus owns
+each site of a lattice.  Its rows have the columns of ANALYSES and take no second input; their window depends on the slide, so `run`
+reports a refusal of `build` (a default window above the cap) in the flag's name.  `select` visits ANALYSES, OF_THE_PLANE, AGAINST_CHANCE
+and WITH_INPUT in that order."""
 import importlib
 import os
 from collections import namedtuple
+
+import numpy as np
 
 from . import cellpoints
 
@@ -86,6 +92,25 @@ ANALYSES = (
 )
 
 
+def _territory_said(m, found, p):
+    (area, border, is_open, contact, class_sites, free_sites), win, maps = found
+    closed = (is_open == 0) & (area > 0)
+    px2 = area[closed] * float(p[1]) ** 2
+    median = f'{float(np.median(px2)):g} px^2' if closed.any() else 'none'
+    top = f'class {int(class_sites.argmax())} with {class_sites.max() / class_sites.sum():.1%} of the owned sites' if class_sites.sum() else 'nothing owned'
+    return (f'territories of {int((area > 0).sum())} nuclei on {win[2]} x {win[3]} sites ({p[0]:g} px reach, {p[1]:g} px pitch; {int(closed.sum())} '
+            f'closed, median area {median}; largest area share: {top})')
+
+
+OF_THE_PLANE = (
+    _analysis('territory', 'territory',                               # which of the same rows owns each piece of the plane: the nearest-nucleus raster
+              lambda m, a: (a.territory_reach, a.territory_pitch, None, bool(a.territory_maps)),     # build's reach_px, pitch_px, win, maps
+              lambda m, p: m.check_args(1, _half(p[0]), _half(p[1])),
+              lambda m, path, head, found, C, p, ctx: m.write_npz(path, *head, found[0], found[1], p[0], p[1], maps=found[2]),
+              _territory_said),
+)
+
+
 def _enrichment_said(m, found, p):
     obs, perm, cn = found
     z = m.derive(obs, perm)['z']
@@ -137,12 +162,12 @@ def _build(an, m, pts, labels, num_classes, params, name, device):
 
 
 def select(args, need_gpu=True):
-    """The parsed arguments of tools/infer_wsi.py -> the selection: ((analysis, params), ..) of the flags given, in the order of ANALYSES, AGAINST_CHANCE
-    and WITH_INPUT.
+    """The parsed arguments of tools/infer_wsi.py -> the selection: ((analysis, params), ..) of the flags given, in the order of ANALYSES, OF_THE_PLANE,
+    AGAINST_CHANCE and WITH_INPUT.
     SystemExit in the name of the flag when its arguments are unusable and then, with need_gpu, when no GPU is visible.  A flag the
     namespace does not hold is not given."""
     chosen = []
-    for an in ANALYSES + AGAINST_CHANCE + WITH_INPUT:
+    for an in ANALYSES + OF_THE_PLANE + AGAINST_CHANCE + WITH_INPUT:
         if not getattr(args, an.cli, False):
             continue
         m = module_of(an)
@@ -167,7 +192,12 @@ def run(selection, rows, boxes, labels, num_classes, out_dir, name, device, cont
     clauses = []
     for an, params in selection:
         m = module_of(an)
-        found = _build(an, m, pts, labels, num_classes, params, name, device)
+        try:
+            found = _build(an, m, pts, labels, num_classes, params, name, device)
+        except ValueError as e:
+            if an not in OF_THE_PLANE:
+                raise
+            raise SystemExit(f'{an.flag}: {e}')
         if found is None:
             clauses.append(an.missing(params, name))
             continue

@@ -72,6 +72,18 @@ Output (like the reference, :659-693), for every detection that survives the per
                   `pitch_px`, `origin_px` (the px position of site (0, 0)), `window` (gx0, gy0, W, H in lattice units).  No tissue-area
                   normalisation and no edge correction.  Every other file is the same bytes with and without the flag.  There is no route
                   without a GPU.
+  --nuclei-territory: (not in the reference) <id>_nuclei_territory.npz beside the documents, from the same rows as --nuclei-graph: which
+                  nucleus, and so which class, each piece of the plane belongs to -- the nearest-nucleus raster (the Voronoi family in
+                  raster form) on the lattice of --nuclei-density with a pitch of --territory-pitch px (4 by default): a site belongs to
+                  the nearest nucleus within --territory-reach px (64 by default, inclusive; a tie goes to the smaller row), or to
+                  nobody -- built on rank 0's GPU after the gather (nuhtc_amd/territory.py): per nucleus `area`, `border` (sites) and
+                  `open` (1: the reach or the window bounds the territory, not its neighbours -- its area is no Voronoi area), `contact`
+                  int64 (C, C) (the border between the territories of two classes, in site pairs), `class_sites`, `free_sites`, the
+                  derived `area_px2`, `closed`, `n_closed`, `closed_area_mean_px2`, `closed_area_std_px2`, `area_disorder`,
+                  `class_area_share`, `free_share`, `contact_share`, and `reach_px`, `pitch_px`, `origin_px`, `window`; with
+                  --territory-maps also the two rasters `owner` and `nearest_d2` int32 (H, W).  Exact integers, a pure function of the
+                  rows.  A default window above 2**28 sites is refused: coarsen the pitch.  Every other file is the same bytes with and
+                  without the flag.  There is no route without a GPU.
   --nuclei-enrichment: (not in the reference) <id>_nuclei_enrichment.npz beside the documents, from the same rows as --nuclei-graph: whether
                   nuclei of one class lie next to nuclei of another more often than chance -- the neighbourhood-enrichment permutation
                   test (histoCAT, squidpy's nhood_enrichment).  The contacts (ordered pairs at most --enrichment-radius px apart, 64 by
@@ -218,6 +230,15 @@ def build_parser():
                    help='kernel radius of --nuclei-density in slide px, a multiple of 0.5 up to 8192 (default 128 px: 32 um at 40x)')
     p.add_argument('--density-pitch', type=float, default=64.0, dest='density_pitch',
                    help='distance between the sites of --nuclei-density in slide px, a multiple of 0.5 (default 64 px)')
+    p.add_argument('--nuclei-territory', action='store_true', dest='nuclei_territory',
+                   help='also write <id>_nuclei_territory.npz: which written nucleus owns each site of a lattice anchored at the slide origin (the '
+                        'nearest-nucleus raster: territory areas, borders and class contacts, exact integers), built on the GPU; from the rows of --nuclei-graph')
+    p.add_argument('--territory-reach', type=float, default=64.0, dest='territory_reach',
+                   help='farthest a site of --nuclei-territory may lie from its nucleus in slide px, a multiple of 0.5 up to 8192 (default 64 px: 16 um at 40x)')
+    p.add_argument('--territory-pitch', type=float, default=4.0, dest='territory_pitch',
+                   help='distance between the sites of --nuclei-territory in slide px, a multiple of 0.5 (default 4 px)')
+    p.add_argument('--territory-maps', action='store_true', dest='territory_maps',
+                   help='--nuclei-territory also stores the rasters `owner` and `nearest_d2` (one int32 per site each)')
     p.add_argument('--nuclei-enrichment', action='store_true', dest='nuclei_enrichment',
                    help='also write <id>_nuclei_enrichment.npz: the contacts of the written nuclei by class pair, observed and under label permutations, '
                         'with z-scores and empirical p-values (the neighbourhood-enrichment test), counted on the GPU; from the rows of --nuclei-graph')
