@@ -1093,6 +1093,31 @@ int nuhtc_cell_territory(int device, const int32_t* points, const int32_t* label
                          int gy0, int W, int H, int x_min, int y_min, int x_max, int y_max, int32_t* owner, int32_t* nearest_d2, int32_t* area,
                          int32_t* border, int32_t* open, int64_t* contact, int64_t* class_sites, int64_t* free_sites, void* stream);
 
+/* Territory adjacency of a slide (csrc/celladjacency.hip; nuhtc_amd/adjacency.py holds the definition and the numpy restatement
+ * `adjacency_reference`): the discrete Delaunay graph of the nucleus centres, read off the owner map nuhtc_cell_territory wrote -- which
+ * nuclei are neighbours and how long their common border is.  Not in the reference.  Engine-free like the territory call: the map and the
+ * three outputs are device memory of `device`, the call allocates and frees its own scratch, runs on `stream` and synchronises it (once
+ * after the count, once at the end) before returning.  It takes no points and no labels: the map holds everything.  nuhtc_config is
+ * unchanged (no ABI bump).
+ *   owner [H][W] int32: every entry in -1 .. n - 1 (-1: nobody's).  W, H >= 1, W * H <= 2^28.  0 <= n <= 2^24.
+ *   edge_cap: the rows of capacity of `edges` and `shared`, 0 .. 2^31 - 1.
+ * A SITE PAIR is an unordered pair of 4-adjacent sites inside the window, counted once.  {i, j} with i < j is an EDGE when some site pair
+ * has the owners i and j, both >= 0; a site nobody owns makes no edge, and two territories that meet only diagonally are not adjacent.
+ *   edges [edge_cap][2] int32: the edges (i, j), i < j, in ascending (i, j) order.
+ *   shared [edge_cap] int32: the site pairs with the owners {i, j} -- the length of the common border in lattice steps, at most 2^29.
+ *     Both are written ONLY when m <= edge_cap (the first m rows, the rest untouched); with m > edge_cap both are untouched, the call still
+ *     returns NUHTC_OK, and the caller calls again with edge_cap >= m.
+ *   degree [n] int32: the distinct neighbours of every row, always written.
+ *   m: HOST memory, written on success only: the number of edges.
+ * Integer adds and a rank: a pure function of the map, bitwise the same on every call.  With n == 0 (every owner -1) m = 0.
+ * NUHTC_E_INVALID, before anything is launched and with the outputs untouched: W, H, n or edge_cap out of range, a null pointer (owner and
+ * m always, degree with n > 0, edges and shared with edge_cap > 0).
+ * NUHTC_E_INVALID after the first pass over the map, the outputs still untouched: an owner outside -1 .. n - 1 (no owner is used as an
+ * index before that pass has ended).
+ * NUHTC_E_HIP: a HIP call failed; an allocation that fails does so before any output is written. */
+int nuhtc_territory_adjacency(int device, const int32_t* owner, int W, int H, int64_t n, int64_t edge_cap, int32_t* edges, int32_t* shared,
+                              int32_t* degree, int64_t* m, void* stream);
+
 /* Nuclei by region (csrc/cellregion.hip; nuhtc_amd/regions.py holds the definition and the brute-force restatement `regions_reference`):
  * an exact point-in-polygon census of the nucleus centres against annotated regions -- "how many nuclei of each class lie in this
  * region".  Not in the reference.  Engine-free like the density call: every pointer but `slots` is device memory of `device`, the call

@@ -1,8 +1,8 @@
 // The uniform grid over half-pixel points that the per-slide analyses share (cellbin.h; cellgraph.hip, cellspatial.hip, cellcluster.hip,
-// cellmst.hip, cellprox.hip, celldensity.hip, cellterritory.hip, cellregion.hip, cellmargin.hip, cellenrich.hip): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
+// cellmst.hip, cellprox.hip, celldensity.hip, cellterritory.hip, celladjacency.hip, cellregion.hip, cellmargin.hip, cellenrich.hip): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
 // and the (cell, class) key of a point, the squared distance of a pair within reach, and the edge key of the spanning forest.  Header-only,
 // so a host program can exercise them under a sanitizer (tools/dev/cellspatial_host_check.cpp, tools/dev/cellmst_host_check.cpp, tools/dev/cellprox_host_check.cpp,
-// tools/dev/celldensity_host_check.cpp, tools/dev/cellregion_host_check.cpp, tools/dev/cellmargin_host_check.cpp, tools/dev/cellenrich_host_check.cpp, tools/dev/cellterritory_host_check.cpp); the kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
+// tools/dev/celldensity_host_check.cpp, tools/dev/cellregion_host_check.cpp, tools/dev/cellmargin_host_check.cpp, tools/dev/cellenrich_host_check.cpp, tools/dev/cellterritory_host_check.cpp, tools/dev/celladjacency_host_check.cpp); the kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
 #pragma once
 #include <cstdint>
 
@@ -169,6 +169,57 @@ inline bool terr_window_ok(int s, int gx0, int gy0, int W, int H) {
   const int64_t lim = DENS_SITE_LIMIT;
   const int64_t xa = (int64_t)gx0 * s, xb = ((int64_t)gx0 + W - 1) * s, ya = (int64_t)gy0 * s, yb = ((int64_t)gy0 + H - 1) * s;
   return xa > -lim && xa < lim && xb > -lim && xb < lim && ya > -lim && ya < lim && yb > -lim && yb < lim;
+}
+
+// ---- territory adjacency (celladjacency.hip): the discrete Delaunay graph read off a finished owner map.  A SITE PAIR is an unordered pair
+// of 4-adjacent sites inside the window, counted once: from its left or upper site, as that site's RIGHT or LOWER pair (adj_site_pairs).
+// It is an edge when the two owners differ and both are rows (adj_is_edge); its key holds the smaller row in the high word, so the
+// unsigned order of the keys IS the ascending (i, j) order of the edges, and no key is all ones (rows are below 2^24): ADJ_NO_KEY marks an
+// empty slot.  The bit budget, stated here once: a window has at most 2 * 2^28 = 2^29 site pairs, so the records M of a call, the edges m
+// and every entry of `shared` are at most 2^29 and fit an int32; a tile of 16 x 16 sites takes 2 * 256 = 512 of them, so its table of 1024
+// slots is at most half full; the call's table has next_pow2(2 M) >= 2 M slots (at least ADJ_MIN_SLOTS, at most 2^30) and holds at most M
+// keys, so it is at most half full as well: linear probing from adj_slot_of always meets the key or an empty slot.
+constexpr unsigned long long ADJ_NO_KEY = ~0ull;
+constexpr int ADJ_TILE_PAIRS = 2 * DENS_TILE * DENS_TILE;          // the site pairs a tile takes: a right and a lower one per site
+constexpr int ADJ_TILE_SLOTS = 1024;
+constexpr int64_t ADJ_MAX_RECORDS = 2 * TERR_MAX_SITES;           // 2^29
+constexpr int64_t ADJ_MIN_SLOTS = 1024;
+static_assert(2 * ADJ_TILE_PAIRS <= ADJ_TILE_SLOTS && (ADJ_TILE_SLOTS & (ADJ_TILE_SLOTS - 1)) == 0, "the tile table is at most half full: it cannot fill");
+static_assert(ADJ_MAX_RECORDS <= (int64_t)1 << 29, "M, m and shared fit an int32; the call's table has at most 2^30 slots");
+
+CELL_HD inline unsigned long long adj_key(int a, int b) {          // a != b, both rows
+  const unsigned lo = (unsigned)(a < b ? a : b), hi = (unsigned)(a < b ? b : a);
+  return ((unsigned long long)lo << 32) | (unsigned long long)hi;
+}
+CELL_HD inline int adj_key_lo(unsigned long long key) { return (int)(key >> 32); }
+CELL_HD inline int adj_key_hi(unsigned long long key) { return (int)(key & 0xffffffffull); }
+
+// an owner is -1 (nobody) or a row; two owners make an edge when they differ and both are rows.  A value outside -1 .. n - 1 makes none
+// (and the call is refused: adj_owner_ok is the check, and it comes before any owner is used as an index)
+CELL_HD inline bool adj_owner_ok(int o, int n) { return o >= -1 && o < n; }
+CELL_HD inline bool adj_is_edge(int a, int b, int n) { return a != b && (unsigned)a < (unsigned)n && (unsigned)b < (unsigned)n; }
+
+// the site pairs site (u, v) takes inside a window of W x H sites: bit 0 its right pair, bit 1 its lower one.  Over all sites every pair
+// of the window comes up exactly once
+CELL_HD inline int adj_site_pairs(int u, int v, int W, int H) { return (int)(u + 1 < W) | ((int)(v + 1 < H) << 1); }
+
+// where the probe of a key starts in a table of `slots` (a power of two) slots: the finaliser of MurmurHash3 over the 64 bits
+CELL_HD inline unsigned long long adj_slot_hash(unsigned long long key) {
+  key ^= key >> 33; key *= 0xff51afd7ed558ccdull;
+  key ^= key >> 33; key *= 0xc4ceb9fe1a85ec53ull;
+  return key ^ (key >> 33);
+}
+CELL_HD inline unsigned long long adj_slot_of(unsigned long long key, unsigned long long slots) { return adj_slot_hash(key) & (slots - 1); }
+
+// the slots of the call's table for M records: the power of two at or above 2 M, at least ADJ_MIN_SLOTS.  0 <= M <= 2^29
+CELL_HD inline int64_t adj_table_slots(int64_t M) {
+  int64_t slots = ADJ_MIN_SLOTS;
+  while (slots < 2 * M) slots <<= 1;
+  return slots;
+}
+
+inline bool adj_call_ok(int W, int H, int64_t n, int64_t edge_cap) {
+  return W >= 1 && H >= 1 && (int64_t)W * H <= TERR_MAX_SITES && n >= 0 && n <= MST_MAX_POINTS && edge_cap >= 0 && edge_cap <= (int64_t)INT32_MAX;
 }
 
 // ---- nuclei by region (cellregion.hip): the second input is not the points but polygon EDGES (ax, ay, bx, by), and the test is a

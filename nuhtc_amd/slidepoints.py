@@ -1,5 +1,5 @@
 """The per-slide point analyses of the slide path as ONE table: which flag of tools/infer_wsi.py selects each, how its arguments become
-the parameters of its module (cellgraph, spatial, clusters, mst, proximity, density, territory, enrichment, regions, margin: they hold the definitions), which file it writes
+the parameters of its module (cellgraph, spatial, clusters, mst, proximity, density, territory, adjacency, enrichment, regions, margin: they hold the definitions), which file it writes
 beside the documents and what the closing message says of it.  cellpoints.py is what the modules share and is imported by them; this
 module imports them, one at a time and only when its flag is given.
 
@@ -17,8 +17,12 @@ label-permutation test.  Its rows have the columns of ANALYSES and take no secon
 
 OF_THE_PLANE, directly behind ANALYSES, holds the analyses that ask about the plane BETWEEN the points -- territory.py: which nucleus owns
 each site of a lattice.  Its rows have the columns of ANALYSES and take no second input; their window depends on the slide, so `run`
-reports a refusal of `build` (a default window above the cap) in the flag's name.  `select` visits ANALYSES, OF_THE_PLANE, AGAINST_CHANCE
-and WITH_INPUT in that order."""
+reports a refusal of `build` (a default window above the cap) in the flag's name.
+
+OF_THE_BORDERS, directly behind OF_THE_PLANE, holds the analyses that ask where the pieces of that plane MEET -- adjacency.py: which
+territories touch, the discrete Delaunay graph.  Its rows have the columns of ANALYSES, take no second input, and share the late refusal
+of OF_THE_PLANE: they build the same window.  `select` visits ANALYSES, OF_THE_PLANE, OF_THE_BORDERS, AGAINST_CHANCE and WITH_INPUT in that
+order."""
 import importlib
 import os
 from collections import namedtuple
@@ -111,6 +115,23 @@ OF_THE_PLANE = (
 )
 
 
+def _adjacency_said(m, found, p):
+    (edges, shared, degree), (area, border, is_open, contact, class_sites, free_sites), win = found[:3]
+    closed = (is_open == 0) & (area > 0)
+    mean = f'{float(degree[closed].mean()):.2f}' if closed.any() else 'none'
+    return (f'{len(edges)} territory borders between {int((degree > 0).sum())} nuclei on {win[2]} x {win[3]} sites ({p[0]:g} px reach, {p[1]:g} px '
+            f'pitch; {int(closed.sum())} closed territories, mean neighbours {mean})')
+
+
+OF_THE_BORDERS = (
+    _analysis('adjacency', 'adjacency',                               # which of the same rows' territories touch: the discrete Delaunay graph
+              lambda m, a: (a.adjacency_reach, a.adjacency_pitch),    # build's reach_px, pitch_px
+              lambda m, p: m.check_args(1, _half(p[0]), _half(p[1])),
+              lambda m, path, head, found, C, p, ctx: m.write_npz(path, *head, found[0], found[1], found[2], p[0], p[1]),
+              _adjacency_said),
+)
+
+
 def _enrichment_said(m, found, p):
     obs, perm, cn = found
     z = m.derive(obs, perm)['z']
@@ -163,11 +184,11 @@ def _build(an, m, pts, labels, num_classes, params, name, device):
 
 def select(args, need_gpu=True):
     """The parsed arguments of tools/infer_wsi.py -> the selection: ((analysis, params), ..) of the flags given, in the order of ANALYSES, OF_THE_PLANE,
-    AGAINST_CHANCE and WITH_INPUT.
+    OF_THE_BORDERS, AGAINST_CHANCE and WITH_INPUT.
     SystemExit in the name of the flag when its arguments are unusable and then, with need_gpu, when no GPU is visible.  A flag the
     namespace does not hold is not given."""
     chosen = []
-    for an in ANALYSES + OF_THE_PLANE + AGAINST_CHANCE + WITH_INPUT:
+    for an in ANALYSES + OF_THE_PLANE + OF_THE_BORDERS + AGAINST_CHANCE + WITH_INPUT:
         if not getattr(args, an.cli, False):
             continue
         m = module_of(an)
@@ -195,7 +216,7 @@ def run(selection, rows, boxes, labels, num_classes, out_dir, name, device, cont
         try:
             found = _build(an, m, pts, labels, num_classes, params, name, device)
         except ValueError as e:
-            if an not in OF_THE_PLANE:
+            if an not in OF_THE_PLANE + OF_THE_BORDERS:
                 raise
             raise SystemExit(f'{an.flag}: {e}')
         if found is None:

@@ -46,8 +46,8 @@ Default window.  `window(bounds, R, s)` is density's with h = R: every site that
 `territory_reference` is the brute-force int64 restatement (every site against every row, no grid): the oracle the device result must
 EQUAL in every output.  `derive` makes the float64 side on the host.
 
-Out of scope: the adjacency as an edge list (the discrete Delaunay graph); the number of distinct neighbours per nucleus; the empty-space
-function F (derivable from nearest_d2 when the maps are kept); tissue clipping other than the reach -- a nucleus at the tissue border owns
+The adjacency as an edge list (the discrete Delaunay graph) and the number of distinct neighbours per nucleus are adjacency.py's, read off
+this module's owner map on the device.  Out of scope: the empty-space function F (derivable from nearest_d2 when the maps are kept); tissue clipping other than the reach -- a nucleus at the tissue border owns
 the plane up to R beyond it, and is `open`.  The exact Voronoi diagram stays out of scope; this is its lattice form, at the
 stated resolution s."""
 import numpy as np

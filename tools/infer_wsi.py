@@ -84,6 +84,17 @@ Output (like the reference, :659-693), for every detection that survives the per
                   --territory-maps also the two rasters `owner` and `nearest_d2` int32 (H, W).  Exact integers, a pure function of the
                   rows.  A default window above 2**28 sites is refused: coarsen the pitch.  Every other file is the same bytes with and
                   without the flag.  There is no route without a GPU.
+  --nuclei-adjacency: (not in the reference) <id>_nuclei_adjacency.npz beside the documents, from the same rows as --nuclei-graph: which
+                  nuclei are neighbours -- the discrete Delaunay graph: two nuclei are adjacent when their territories (the raster of
+                  --nuclei-territory, here with --adjacency-reach px, 64 by default, and --adjacency-pitch px, 4 by default) touch along
+                  a side of a site (4-adjacency: a diagonal meeting is none) -- built on rank 0's GPU after the gather
+                  (nuhtc_amd/adjacency.py): `edges` int32 (m, 2) in ascending (i, j) order, `shared` int32 (m,) (the common border in
+                  lattice steps), `degree` int32 (n,), the territory tallies the graph was read off (`area`, `border`, `open`, `contact`,
+                  `class_sites`, `free_sites`; `contact` is the graph's `shared` summed by class pair), the derived `edge_d2`, `edge_px`,
+                  `border_px`, `class_edge_count`, `class_border`, `neighbour_class`, `n_closed`, `closed_degree_mean`, `n_edges`, and
+                  `reach_px`, `pitch_px`, `window`.  Exact integers, a pure function of the rows.  A default window above 2**28 sites is
+                  refused: coarsen the pitch.  Every other file is the same bytes with and without the flag.  There is no route
+                  without a GPU.
   --nuclei-enrichment: (not in the reference) <id>_nuclei_enrichment.npz beside the documents, from the same rows as --nuclei-graph: whether
                   nuclei of one class lie next to nuclei of another more often than chance -- the neighbourhood-enrichment permutation
                   test (histoCAT, squidpy's nhood_enrichment).  The contacts (ordered pairs at most --enrichment-radius px apart, 64 by
@@ -239,6 +250,13 @@ def build_parser():
                    help='distance between the sites of --nuclei-territory in slide px, a multiple of 0.5 (default 4 px)')
     p.add_argument('--territory-maps', action='store_true', dest='territory_maps',
                    help='--nuclei-territory also stores the rasters `owner` and `nearest_d2` (one int32 per site each)')
+    p.add_argument('--nuclei-adjacency', action='store_true', dest='nuclei_adjacency',
+                   help='also write <id>_nuclei_adjacency.npz: which written nuclei are neighbours (the discrete Delaunay graph: their territories touch '
+                        'on the lattice; edges, shared border lengths and degrees, exact integers), built on the GPU; from the rows of --nuclei-graph')
+    p.add_argument('--adjacency-reach', type=float, default=64.0, dest='adjacency_reach',
+                   help='the reach of the territories of --nuclei-adjacency in slide px, a multiple of 0.5 up to 8192 (default 64 px)')
+    p.add_argument('--adjacency-pitch', type=float, default=4.0, dest='adjacency_pitch',
+                   help='distance between the sites of --nuclei-adjacency in slide px, a multiple of 0.5 (default 4 px)')
     p.add_argument('--nuclei-enrichment', action='store_true', dest='nuclei_enrichment',
                    help='also write <id>_nuclei_enrichment.npz: the contacts of the written nuclei by class pair, observed and under label permutations, '
                         'with z-scores and empirical p-values (the neighbourhood-enrichment test), counted on the GPU; from the rows of --nuclei-graph')
