@@ -1118,6 +1118,41 @@ int nuhtc_cell_territory(int device, const int32_t* points, const int32_t* label
 int nuhtc_territory_adjacency(int device, const int32_t* owner, int W, int H, int64_t n, int64_t edge_cap, int32_t* edges, int32_t* shared,
                               int32_t* degree, int64_t* m, void* stream);
 
+/* The alpha complex of a slide's nuclei (csrc/cellalpha.hip; nuhtc_amd/alphacomplex.py holds the definition and the brute-force
+ * restatement `alpha_reference`): the exact Delaunay edges within a radius -- the continuous statement of what nuhtc_territory_adjacency
+ * reads off a lattice, and a supergraph of the Gabriel graph of nuhtc_cell_proximity at radius 2 r.  Not in the reference.  Engine-free
+ * like the proximity call, with its argument order and its capacity protocol: points, labels and the five outputs are device memory of
+ * `device`, the call allocates and frees its own scratch, runs on `stream` and synchronises it (once after the count, once at the end)
+ * before returning.  nuhtc_config is unchanged (no ABI bump).
+ *   points [n][2] int32: node positions in HALF pixels, |p| < 2^27.  labels [n] int32.  0 <= n <= 2^24.  num_classes C: 1 .. 14 (checked;
+ *     the labels are only compared with each other).  r: the radius in half pixels, 1 .. 512; D = 2 r is the diameter.  by_class: 0 or 1.
+ *     edge_cap: the rows of capacity of the four edge arrays, 0 .. 2^31 - 1.
+ *   x_min, y_min, x_max, y_max: the bounding box of the points (inclusive), computed by the caller on the host (ignored when n == 0).
+ * A CANDIDATE is an unordered pair i < j with d2(i, j) <= D * D (inclusive) and, with by_class, labels[i] == labels[j] (plain equality).
+ * A WITNESS is any other row k, with by_class of the same label.  The candidate is an EDGE when some disc of radius <= r has both ends on
+ * its boundary and no witness strictly inside: with q = p_j - p_i the discs through both ends have the centres (q + t q_perp) / 2, t real,
+ * radius <= r is t^2 <= T^2 = (D^2 - d2) / d2, and a witness at rho = p_k - p_i with s = q x rho and m = rho . (rho - q) allows
+ * t <= m / s (s > 0), t >= m / s (s < 0), blocks the pair (s == 0, m < 0) or does not bind.  hi is the smallest upper bound, lo the
+ * largest lower one (either may be open); the pair is an edge when it is not blocked, hi >= -T, lo <= T and lo <= hi, all inclusive, so
+ * four cocircular points keep both diagonals.  Every decision is a comparison of two rationals in int64.
+ *   edges [edge_cap][2] int32: the edges (i, j), i < j, in ascending (i, j) order.  edge_d2 [edge_cap] int32: their squared lengths.
+ *   apex [edge_cap][2] int32: [0] the smallest row that attains hi when hi <= T, [1] the smallest that attains lo when lo >= -T, else -1:
+ *     the third corner of a triangle with an empty circumcircle of radius <= r on that side of the edge.
+ *   edge_gabriel [edge_cap] uint8: 1 where no witness has m < 0 (none strictly inside the disc with diameter ij).
+ *     All four are written ONLY when m <= edge_cap (the first m rows, the rest untouched); with m > edge_cap they are untouched, the call
+ *     still returns NUHTC_OK, and the caller calls again with edge_cap >= m.  m is not bounded by a multiple of n: k coincident points are
+ *     a clique of k (k - 1) / 2 edges (d2 = 0, both apexes -1, Gabriel).
+ *   degree [n][2] int32: the edges and the Gabriel edges at every row, always written.
+ *   m, m_gabriel: HOST memory, written on success only.
+ * The result is a pure function of the input: bitwise the same on every call.  n == 0 sets m = m_gabriel = 0, launches nothing and
+ * returns NUHTC_OK.
+ * NUHTC_E_INVALID, before anything is launched and with the outputs untouched: n, num_classes, r, by_class or edge_cap out of range, a
+ * null pointer (m, m_gabriel always, the others with n > 0), a bounding box that is empty or reaches +-2^27.
+ * NUHTC_E_INVALID after the binning, the outputs still untouched: a point lies outside the stated bounding box. */
+int nuhtc_cell_alpha(int device, const int32_t* points, const int32_t* labels, int64_t n, int num_classes, int r, int by_class,
+                     int64_t edge_cap, int x_min, int y_min, int x_max, int y_max, int32_t* edges, int32_t* edge_d2, int32_t* apex,
+                     uint8_t* edge_gabriel, int32_t* degree, int64_t* m, int64_t* m_gabriel, void* stream);
+
 /* Nuclei by region (csrc/cellregion.hip; nuhtc_amd/regions.py holds the definition and the brute-force restatement `regions_reference`):
  * an exact point-in-polygon census of the nucleus centres against annotated regions -- "how many nuclei of each class lie in this
  * region".  Not in the reference.  Engine-free like the density call: every pointer but `slots` is device memory of `device`, the call

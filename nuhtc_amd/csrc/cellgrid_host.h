@@ -1,8 +1,8 @@
 // The uniform grid over half-pixel points that the per-slide analyses share (cellbin.h; cellgraph.hip, cellspatial.hip, cellcluster.hip,
-// cellmst.hip, cellprox.hip, celldensity.hip, cellterritory.hip, celladjacency.hip, cellregion.hip, cellmargin.hip, cellenrich.hip): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
+// cellmst.hip, cellprox.hip, celldensity.hip, cellterritory.hip, celladjacency.hip, cellalpha.hip, cellregion.hip, cellmargin.hip, cellenrich.hip): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
 // and the (cell, class) key of a point, the squared distance of a pair within reach, and the edge key of the spanning forest.  Header-only,
 // so a host program can exercise them under a sanitizer (tools/dev/cellspatial_host_check.cpp, tools/dev/cellmst_host_check.cpp, tools/dev/cellprox_host_check.cpp,
-// tools/dev/celldensity_host_check.cpp, tools/dev/cellregion_host_check.cpp, tools/dev/cellmargin_host_check.cpp, tools/dev/cellenrich_host_check.cpp, tools/dev/cellterritory_host_check.cpp, tools/dev/celladjacency_host_check.cpp); the kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
+// tools/dev/celldensity_host_check.cpp, tools/dev/cellregion_host_check.cpp, tools/dev/cellmargin_host_check.cpp, tools/dev/cellenrich_host_check.cpp, tools/dev/cellterritory_host_check.cpp, tools/dev/celladjacency_host_check.cpp, tools/dev/cellalpha_host_check.cpp); the kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
 #pragma once
 #include <cstdint>
 
@@ -222,6 +222,81 @@ inline bool adj_call_ok(int W, int H, int64_t n, int64_t edge_cap) {
   return W >= 1 && H >= 1 && (int64_t)W * H <= TERR_MAX_SITES && n >= 0 && n <= MST_MAX_POINTS && edge_cap >= 0 && edge_cap <= (int64_t)INT32_MAX;
 }
 
+// ---- the alpha complex (cellalpha.hip): the exact Delaunay edges within a radius r (1 .. 512 half pixels, D = 2 r the diameter).  For a
+// candidate pair with q = p_j - p_i and d2 = |q|^2 <= D^2, the circles through both ends have the centres (q + t q_perp) / 2 and the squared
+// radius d2 (1 + t^2) / 4: radius <= r exactly when t^2 <= (D^2 - d2) / d2 = T^2.  A witness at rho = p_k - p_i has s = q x rho and
+// m = rho . (rho - q) and lies strictly inside circle t exactly when t s > m: s > 0 allows t <= m / s (the bound `hi` is the smallest such),
+// s < 0 allows t >= m / s (`lo`, the largest), s == 0 blocks the pair outright when m < 0 (strictly between the ends) and does not bind
+// otherwise (a witness coincident with an end has s = m = 0, so an end needs not be told from a witness).  The pair is an edge when it is
+// not blocked, hi >= -T, lo <= T and lo <= hi, all inclusive; it is Gabriel when no witness has m < 0 (m < 0 is d2(i, k) + d2(j, k) < d2(i, j)).
+// The bit budget, stated here once: a witness that binds within [-T, T] or kills the pair lies on or inside a circle of radius <= r
+// through both ends, hence within D of i and of j; alpha_witness skips every other one BEFORE any product of s or m is formed (two box
+// tests, then two squared distances of differences <= D = 2^10, each <= 2^21).  For the rest |rho| <= D and |rho - q| <= D give
+// |s| <= D^2 = 2^20 and |m| <= D^2 (Cauchy-Schwarz), exact in int32 (each a sum of two products below 2^20).  A bound is the fraction
+// (num, den) with den > 0, |num|, den <= 2^20: comparing two cross-multiplies to below 2^40 (alpha_frac_cmp), and comparing one with +-T is
+// a sign test followed by num^2 d2 <= den^2 (D^2 - d2), both sides below 2^40 * 2^20 = 2^60 (alpha_within_T): int64 throughout.
+constexpr int ALPHA_MAX_R = 512;                       // half pixels; the reach of the binning is D = 2 r <= 1024
+constexpr int ALPHA_GABRIEL_BIT = 1 << 30;             // an edge's d2 (<= 2^20) and its Gabriel bit in one int while the segments are put in order
+
+// the sign of a / b - c / d for b, d > 0
+CELL_HD inline int alpha_frac_cmp(int64_t a, int64_t b, int64_t c, int64_t d) {
+  const int64_t l = a * d, r = c * b;
+  return (l > r) - (l < r);
+}
+// |a / b| <= T, b > 0: a^2 d2 <= b^2 (D^2 - d2).  0 < d2 <= D2
+CELL_HD inline bool alpha_within_T(int64_t a, int64_t b, int d2, int D2) { return a * a * d2 <= b * b * (int64_t)(D2 - d2); }
+CELL_HD inline bool alpha_le_T(int64_t a, int64_t b, int d2, int D2) { return a <= 0 || alpha_within_T(a, b, d2, D2); }         // a / b <= T
+CELL_HD inline bool alpha_ge_neg_T(int64_t a, int64_t b, int d2, int D2) { return a >= 0 || alpha_within_T(a, b, d2, D2); }     // a / b >= -T
+
+// what the witnesses seen so far leave of a candidate: hi = hn / hd attained by row hk (hd == 0: open), lo = ln / ld by row lk
+struct AlphaState {
+  int hn, hd, hk, ln, ld, lk;
+  bool blocked, gabriel;
+};
+CELL_HD inline AlphaState alpha_open() { return AlphaState{0, 0, -1, 0, 0, -1, false, true}; }
+
+// one witness, row `row` at (rx, ry) from i, against the candidate with q = (qx, qy) and the diameter D (D2 = D * D).  -> whether a bound
+// moved or the pair was blocked (then alpha_dead is worth asking).  The smallest row that attains a bound is kept
+CELL_HD inline bool alpha_witness(AlphaState& st, int qx, int qy, int rx, int ry, int row, int D, int D2) {
+  const int ux = rx - qx, uy = ry - qy;                // from j: |p| < 2^27 keeps every difference an exact int32
+  if (rx > D || rx < -D || ry > D || ry < -D || ux > D || ux < -D || uy > D || uy < -D) return false;
+  if (rx * rx + ry * ry > D2 || ux * ux + uy * uy > D2) return false;
+  const int s = qx * ry - qy * rx, m = rx * ux + ry * uy;
+  if (m < 0) st.gabriel = false;
+  if (s == 0) {
+    if (m >= 0) return false;
+    st.blocked = true;
+    return true;
+  }
+  if (s > 0) {
+    const int c = st.hd ? alpha_frac_cmp(m, s, st.hn, st.hd) : -1;
+    if (c < 0) { st.hn = m; st.hd = s; st.hk = row; return true; }
+    if (c == 0 && row < st.hk) st.hk = row;
+    return false;
+  }
+  const int c = st.ld ? alpha_frac_cmp(-m, -s, st.ln, st.ld) : 1;
+  if (c > 0) { st.ln = -m; st.ld = -s; st.lk = row; return true; }
+  if (c == 0 && row < st.lk) st.lk = row;
+  return false;
+}
+
+// can no further witness make the candidate an edge?  (d2 > 0)
+CELL_HD inline bool alpha_dead(const AlphaState& st, int d2, int D2) {
+  if (st.blocked) return true;
+  if (st.hd && !alpha_ge_neg_T(st.hn, st.hd, d2, D2)) return true;
+  if (st.ld && !alpha_le_T(st.ln, st.ld, d2, D2)) return true;
+  return st.hd && st.ld && alpha_frac_cmp(st.ln, st.ld, st.hn, st.hd) > 0;
+}
+
+// the verdict once every witness is in: bit 0 the pair is an edge, bit 1 it is Gabriel as well; apex[0] the row that attains hi when
+// hi <= T, apex[1] the one that attains lo when lo >= -T, else -1 (written for an edge only)
+CELL_HD inline int alpha_verdict(const AlphaState& st, int d2, int D2, int* apex) {
+  if (alpha_dead(st, d2, D2)) return 0;
+  apex[0] = st.hd && alpha_le_T(st.hn, st.hd, d2, D2) ? st.hk : -1;
+  apex[1] = st.ld && alpha_ge_neg_T(st.ln, st.ld, d2, D2) ? st.lk : -1;
+  return 1 | ((int)st.gabriel << 1);
+}
+
 // ---- nuclei by region (cellregion.hip): the second input is not the points but polygon EDGES (ax, ay, bx, by), and the test is a
 // point against an edge.  The bit budget, stated here once: a point and a vertex both have |v| < 2^27, so every difference (hi - lo,
 // p - lo, b - a, p - a) is below 2^28 in magnitude and exact in int32; a product of two of them is below 2^56 and the difference of two
@@ -362,4 +437,8 @@ inline bool cell_box_ok(int x_min, int y_min, int x_max, int y_max) {
 inline bool cell_call_ok(int64_t n, int64_t max_n, int C, int reach, int x_min, int y_min, int x_max, int y_max) {
   if (n < 0 || n > max_n || C < 1 || C > CELL_MAX_CLASSES || reach < 1 || reach > CELL_MAX_REACH) return false;
   return n == 0 || cell_box_ok(x_min, y_min, x_max, y_max);
+}
+inline bool alpha_call_ok(int64_t n, int C, int r, int by_class, int64_t edge_cap, int x_min, int y_min, int x_max, int y_max) {
+  return r >= 1 && r <= ALPHA_MAX_R && (by_class == 0 || by_class == 1) && edge_cap >= 0 && edge_cap <= (int64_t)INT32_MAX &&
+         cell_call_ok(n, MST_MAX_POINTS, C, 2 * r, x_min, y_min, x_max, y_max);
 }

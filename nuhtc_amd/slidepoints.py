@@ -1,5 +1,5 @@
 """The per-slide point analyses of the slide path as ONE table: which flag of tools/infer_wsi.py selects each, how its arguments become
-the parameters of its module (cellgraph, spatial, clusters, mst, proximity, density, territory, adjacency, enrichment, regions, margin: they hold the definitions), which file it writes
+the parameters of its module (cellgraph, spatial, clusters, mst, proximity, density, territory, adjacency, alphacomplex, enrichment, regions, margin: they hold the definitions), which file it writes
 beside the documents and what the closing message says of it.  cellpoints.py is what the modules share and is imported by them; this
 module imports them, one at a time and only when its flag is given.
 
@@ -21,8 +21,12 @@ reports a refusal of `build` (a default window above the cap) in the flag's name
 
 OF_THE_BORDERS, directly behind OF_THE_PLANE, holds the analyses that ask where the pieces of that plane MEET -- adjacency.py: which
 territories touch, the discrete Delaunay graph.  Its rows have the columns of ANALYSES, take no second input, and share the late refusal
-of OF_THE_PLANE: they build the same window.  `select` visits ANALYSES, OF_THE_PLANE, OF_THE_BORDERS, AGAINST_CHANCE and WITH_INPUT in that
-order."""
+of OF_THE_PLANE: they build the same window.
+
+OF_THE_CIRCLES, directly behind OF_THE_BORDERS, holds the analyses that state those borders in the continuum, by empty circles through two
+points -- alphacomplex.py: the exact Delaunay edges and triangles within a radius, what adjacency.py reads off a lattice.  Its rows have
+the columns of ANALYSES and take no second input and no window.  `select` visits ANALYSES, OF_THE_PLANE, OF_THE_BORDERS, OF_THE_CIRCLES,
+AGAINST_CHANCE and WITH_INPUT in that order."""
 import importlib
 import os
 from collections import namedtuple
@@ -132,6 +136,16 @@ OF_THE_BORDERS = (
 )
 
 
+OF_THE_CIRCLES = (
+    _analysis('alpha', 'alphacomplex',                                # which of the same rows are Delaunay neighbours within a radius: the alpha complex
+              lambda m, a: (a.alpha_radius, m.BY[a.alpha_by]),
+              lambda m, p: m.check_args(1, _half(p[0]), p[1]),
+              lambda m, path, head, found, C, p, ctx: m.write_npz(path, *head, *found[:5], C, radius_px=p[0], by_class=p[1]),
+              lambda m, found, p: (f'{found[5]} alpha-complex edges, {found[6]} of them Gabriel edges, {int(((found[2] >= 0).sum(1) == 1).sum())} on the '
+                                   f'outline ({p[0]:g} px radius, by {BY_NAMES[p[1]]})')),
+)
+
+
 def _enrichment_said(m, found, p):
     obs, perm, cn = found
     z = m.derive(obs, perm)['z']
@@ -184,11 +198,11 @@ def _build(an, m, pts, labels, num_classes, params, name, device):
 
 def select(args, need_gpu=True):
     """The parsed arguments of tools/infer_wsi.py -> the selection: ((analysis, params), ..) of the flags given, in the order of ANALYSES, OF_THE_PLANE,
-    OF_THE_BORDERS, AGAINST_CHANCE and WITH_INPUT.
+    OF_THE_BORDERS, OF_THE_CIRCLES, AGAINST_CHANCE and WITH_INPUT.
     SystemExit in the name of the flag when its arguments are unusable and then, with need_gpu, when no GPU is visible.  A flag the
     namespace does not hold is not given."""
     chosen = []
-    for an in ANALYSES + OF_THE_PLANE + OF_THE_BORDERS + AGAINST_CHANCE + WITH_INPUT:
+    for an in ANALYSES + OF_THE_PLANE + OF_THE_BORDERS + OF_THE_CIRCLES + AGAINST_CHANCE + WITH_INPUT:
         if not getattr(args, an.cli, False):
             continue
         m = module_of(an)

@@ -1,5 +1,5 @@
 """What the bench tools of the per-slide point analyses (bench_cellgraph, bench_spatial, bench_clusters, bench_mst, bench_proximity,
-bench_density, bench_territory, bench_adjacency, bench_enrichment, bench_regions, bench_margin) do in the same way: the synthetic point sets, the shared arguments, the event-timed loop, the stage split under the
+bench_density, bench_territory, bench_adjacency, bench_alpha, bench_enrichment, bench_regions, bench_margin) do in the same way: the synthetic point sets, the shared arguments, the event-timed loop, the stage split under the
 library's profile, the wall-clock end-to-end loop, the window small enough for brute force, the cell-graph yardstick and the one JSON line.
 A helper, not a tool: each tool keeps its call, its summary columns and its host comparison."""
 import argparse

@@ -95,6 +95,18 @@ Output (like the reference, :659-693), for every detection that survives the per
                   `reach_px`, `pitch_px`, `window`.  Exact integers, a pure function of the rows.  A default window above 2**28 sites is
                   refused: coarsen the pitch.  Every other file is the same bytes with and without the flag.  There is no route
                   without a GPU.
+  --nuclei-alpha: (not in the reference) <id>_nuclei_alpha.npz beside the documents, for the same rows as --nuclei-graph: the alpha complex
+                  of the nucleus centres -- the exact Delaunay edges within a radius, the continuous statement of what
+                  --nuclei-adjacency reads off a lattice: two nuclei are joined when some circle of radius at most --alpha-radius px (32
+                  by default, so the longest edge is 64 px) passes through both and has no other nucleus strictly inside, over all nuclei
+                  or, with --alpha-by class, among nuclei of one label -- built on rank 0's GPU after the gather
+                  (nuhtc_amd/alphacomplex.py): `edges` int32 (m, 2) in ascending (i, j) order, `edge_d2`, `apex` int32 (m, 2) (the third
+                  corner of the empty circumcircle on either side, or -1), `edge_gabriel`, `degree` int32 (n, 2), the derived
+                  `edge_len_px`, `voronoi_px`, `edge_kind`, `triangles`, `triangle_area_px2`, `triangle_circumradius_px`,
+                  `class_edge_count`, `outline_class_count`, `on_outline`, `n_edges`, `n_gabriel`, `n_triangles`, `n_degenerate`,
+                  `alpha_area_px2`, and `radius_px`, `by_class`.  Exact integers (every decision compares two rationals in int64), unique
+                  without a tie rule: cocircular points keep both diagonals, and `n_degenerate` counts them.  Every other file is the
+                  same bytes with and without the flag.  There is no route without a GPU.
   --nuclei-enrichment: (not in the reference) <id>_nuclei_enrichment.npz beside the documents, from the same rows as --nuclei-graph: whether
                   nuclei of one class lie next to nuclei of another more often than chance -- the neighbourhood-enrichment permutation
                   test (histoCAT, squidpy's nhood_enrichment).  The contacts (ordered pairs at most --enrichment-radius px apart, 64 by
@@ -257,6 +269,13 @@ def build_parser():
                    help='the reach of the territories of --nuclei-adjacency in slide px, a multiple of 0.5 up to 8192 (default 64 px)')
     p.add_argument('--adjacency-pitch', type=float, default=4.0, dest='adjacency_pitch',
                    help='distance between the sites of --nuclei-adjacency in slide px, a multiple of 0.5 (default 4 px)')
+    p.add_argument('--nuclei-alpha', action='store_true', dest='nuclei_alpha',
+                   help='also write <id>_nuclei_alpha.npz: the alpha complex of the written nuclei (the exact Delaunay edges and triangles within a '
+                        'radius: edges, apexes, Gabriel flags and degrees, exact integers), built on the GPU; from the rows of --nuclei-graph')
+    p.add_argument('--alpha-radius', type=float, default=32.0, dest='alpha_radius',
+                   help='largest empty circle of --nuclei-alpha in slide px, a multiple of 0.5 up to 256 (default 32 px: the longest edge is 64 px)')
+    p.add_argument('--alpha-by', choices=('any', 'class'), default='any', dest='alpha_by',
+                   help="--nuclei-alpha over all nuclei ('any') or only among nuclei of the same label ('class')")
     p.add_argument('--nuclei-enrichment', action='store_true', dest='nuclei_enrichment',
                    help='also write <id>_nuclei_enrichment.npz: the contacts of the written nuclei by class pair, observed and under label permutations, '
                         'with z-scores and empirical p-values (the neighbourhood-enrichment test), counted on the GPU; from the rows of --nuclei-graph')
