@@ -1153,6 +1153,38 @@ int nuhtc_cell_alpha(int device, const int32_t* points, const int32_t* labels, i
                      int64_t edge_cap, int x_min, int y_min, int x_max, int y_max, int32_t* edges, int32_t* edge_d2, int32_t* apex,
                      uint8_t* edge_gabriel, int32_t* degree, int64_t* m, int64_t* m_gabriel, void* stream);
 
+/* The alpha-shape outline (csrc/celloutline.hip; nuhtc_amd/outline.py holds the definition and the plain walk `outline_reference`): the
+ * rings and the components of the alpha complex that nuhtc_cell_alpha left on the device.  Not in the reference.  Engine-free: every
+ * pointer but `counts` is device memory of `device`, the call allocates and frees its own scratch, runs on `stream` and synchronises it
+ * (once after the outline edges are counted, once at the end) before returning.  nuhtc_config is unchanged (no ABI bump).
+ *   points [n][2] int32, labels [n] int32: as given to nuhtc_cell_alpha; 0 <= n <= 2^24.  by_class: 0 or 1, as given there.
+ *   edges [m][2], edge_d2 [m], apex [m][2] int32: the first m rows of its outputs; 0 <= m <= 2^24 (the scans over the edges).
+ * A row is a REPRESENTATIVE unless it is the larger end of an edge with edge_d2 == 0; an edge between two representatives is KEPT.  A kept
+ * edge with exactly one apex gives one HALF-EDGE with the apex on its left (i -> j when apex[e][0] >= 0, else j -> i) and the id e.  The
+ * successor of u -> v is the half-edge v -> w met first when turning clockwise from v -> u, decided by signs of cross and dot products in
+ * int64.  The RINGS are the cycles of that map: led by their smallest id, written from the leader's tail onward, ordered by leader.  Two
+ * kept edges with an apex are joined when they are sides of one triangle (i, j, apex); a COMPONENT is numbered by the rank of its
+ * smallest edge index.
+ *   ring_vertex [m] int32: the rows in ring order, rings concatenated (the first h written).  ring_start [m + 1] int32: where each ring
+ *     begins (the first R + 1 written; ring_start[R] == h).  ring_area2 [m] int64: the shoelace sum of each ring in half pixels squared,
+ *     relative to its first vertex: positive for an outer ring, negative for a hole (the first R written).  component_of_ring [m] int32
+ *     (R written).  component [n] int32: the smallest component among the apexed kept edges at a representative, -1 for a row in no
+ *     triangle; any other row has its representative's value (all n written).  component_label [m] int32: with by_class the label all
+ *     rows of the component share, else -1 (the first K written).
+ *   counts: HOST memory, int64 [3] = h, R, K, written on success only.
+ * The result is a pure function of the input: bitwise the same on every call.  m == 0 writes ring_start[0] = 0 and component = -1.
+ * NUHTC_E_INVALID, before anything is launched and with the outputs untouched: n, m or by_class out of range, a null pointer (counts and
+ * ring_start always; points, labels and component with n > 0; the others with m > 0), m > 0 with n == 0.
+ * NUHTC_E_INVALID after the first kernels, the outputs still untouched: an edge that is not (i, j) with 0 <= i < j < n or does not come
+ * behind the edge in front of it, an apex outside -1 .. n - 1, an apex that is not strictly on its side of the edge (apex[e][0] left of
+ * i -> j, apex[e][1] right), a point of an edge or an apex outside |p| < 2^27.
+ * An edge list that passes these checks and is no alpha complex is worked off without any access outside the tables; its rings mean
+ * nothing. */
+int nuhtc_alpha_outline(int device, const int32_t* points, const int32_t* labels, int64_t n, int by_class, const int32_t* edges,
+                        const int32_t* edge_d2, const int32_t* apex, int64_t m, int32_t* ring_vertex, int32_t* ring_start,
+                        int64_t* ring_area2, int32_t* component_of_ring, int32_t* component, int32_t* component_label, int64_t* counts,
+                        void* stream);
+
 /* Nuclei by region (csrc/cellregion.hip; nuhtc_amd/regions.py holds the definition and the brute-force restatement `regions_reference`):
  * an exact point-in-polygon census of the nucleus centres against annotated regions -- "how many nuclei of each class lie in this
  * region".  Not in the reference.  Engine-free like the density call: every pointer but `slots` is device memory of `device`, the call

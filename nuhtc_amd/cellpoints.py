@@ -1,4 +1,4 @@
-"""What the per-slide point analyses -- cellgraph.py, spatial.py, clusters.py, mst.py, proximity.py, alphacomplex.py, density.py, territory.py, enrichment.py, and regions.py and margin.py with their second input, which hold the definitions -- do in the same way: half-pixel
+"""What the per-slide point analyses -- cellgraph.py, spatial.py, clusters.py, mst.py, proximity.py, alphacomplex.py, outline.py, density.py, territory.py, enrichment.py, and regions.py and margin.py with their second input, which hold the definitions -- do in the same way: half-pixel
 nucleus centres with one label each, the grid over the host-computed bounding box, the pair loop of the brute-force references, the one
 call into the library, the opening of a `build`, the header of the .npz files, and the checks and the census more than one of them holds
 (slidepoints.py is the table that runs them for the slide path).  |p| < 2**27 and a reach of at most 16384 half pixels keep every squared distance

@@ -1,8 +1,8 @@
 // The uniform grid over half-pixel points that the per-slide analyses share (cellbin.h; cellgraph.hip, cellspatial.hip, cellcluster.hip,
-// cellmst.hip, cellprox.hip, celldensity.hip, cellterritory.hip, celladjacency.hip, cellalpha.hip, cellregion.hip, cellmargin.hip, cellenrich.hip): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
+// cellmst.hip, cellprox.hip, celldensity.hip, cellterritory.hip, celladjacency.hip, cellalpha.hip, celloutline.hip, cellregion.hip, cellmargin.hip, cellenrich.hip): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
 // and the (cell, class) key of a point, the squared distance of a pair within reach, and the edge key of the spanning forest.  Header-only,
 // so a host program can exercise them under a sanitizer (tools/dev/cellspatial_host_check.cpp, tools/dev/cellmst_host_check.cpp, tools/dev/cellprox_host_check.cpp,
-// tools/dev/celldensity_host_check.cpp, tools/dev/cellregion_host_check.cpp, tools/dev/cellmargin_host_check.cpp, tools/dev/cellenrich_host_check.cpp, tools/dev/cellterritory_host_check.cpp, tools/dev/celladjacency_host_check.cpp, tools/dev/cellalpha_host_check.cpp); the kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
+// tools/dev/celldensity_host_check.cpp, tools/dev/cellregion_host_check.cpp, tools/dev/cellmargin_host_check.cpp, tools/dev/cellenrich_host_check.cpp, tools/dev/cellterritory_host_check.cpp, tools/dev/celladjacency_host_check.cpp, tools/dev/cellalpha_host_check.cpp, tools/dev/celloutline_host_check.cpp); the kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
 #pragma once
 #include <cstdint>
 
@@ -295,6 +295,46 @@ CELL_HD inline int alpha_verdict(const AlphaState& st, int d2, int D2, int* apex
   apex[0] = st.hd && alpha_le_T(st.hn, st.hd, d2, D2) ? st.hk : -1;
   apex[1] = st.ld && alpha_ge_neg_T(st.ln, st.ld, d2, D2) ? st.lk : -1;
   return 1 | ((int)st.gabriel << 1);
+}
+
+// ---- the alpha-shape outline (celloutline.hip): the rings of the alpha complex, traced by a successor map on the half-edges.  The
+// successor of the half-edge u -> v is the out-half-edge v -> w met first when turning CLOCKWISE from the direction a = u - v (through
+// the material, which lies on the left of u -> v); b = w - v is a candidate.  The clockwise angle from a to b falls in one of four
+// classes, told by the signs of a x b and a . b: 0 (the same direction: a x b == 0, a . b >= 0 -- no out-half-edge of an alpha complex has
+// it, the farther end would be blocked by the nearer), 1 (strictly between 0 and pi: a x b < 0), 2 (pi: a x b == 0, a . b < 0) and 3
+// (beyond pi: a x b > 0).  Two candidates of one class 1 or 3 lie within one open half-turn, where b1 comes first exactly when
+// b1 x b2 < 0.  The bit budget, stated here once: the vectors of an alpha complex are no longer than D = 2 r <= 1024, so every product is
+// at most 2^20 and every cross or dot product below 2^21; the entry point accepts ANY edge list between points with |p| < 2^27, and then
+// the differences are below 2^28, the products below 2^56 and their sums below 2^57: exact in int64 either way.
+constexpr int64_t OUTLINE_MAX_EDGES = (int64_t)1 << 24;            // the scans over the edges take 1024 chunks of 16384
+CELL_HD inline int outline_turn_class(int64_t ax, int64_t ay, int64_t bx, int64_t by) {
+  const int64_t cr = ax * by - ay * bx;
+  if (cr < 0) return 1;
+  if (cr > 0) return 3;
+  return ax * bx + ay * by < 0 ? 2 : 0;
+}
+// is b1 met strictly before b2 when turning clockwise from a?  (false for two candidates of one direction)
+CELL_HD inline bool outline_turn_before(int64_t ax, int64_t ay, int64_t b1x, int64_t b1y, int64_t b2x, int64_t b2y) {
+  const int c1 = outline_turn_class(ax, ay, b1x, b1y), c2 = outline_turn_class(ax, ay, b2x, b2y);
+  if (c1 != c2) return c1 < c2;
+  return (c1 & 1) && b1x * b2y - b1y * b2x < 0;
+}
+// one step of the successor choice, a fold over the out-half-edges at v in ANY order: does the candidate (b, id) replace the best so
+// far?  Two candidates of one direction (none in an alpha complex) are told apart by the smaller id, so the choice is a strict total
+// order and the fold's result does not depend on the order of the candidates.
+CELL_HD inline bool outline_better(int64_t ax, int64_t ay, int64_t bx, int64_t by, int id, int64_t best_x, int64_t best_y, int best_id) {
+  if (best_id < 0) return true;
+  if (outline_turn_before(ax, ay, bx, by, best_x, best_y)) return true;
+  if (outline_turn_before(ax, ay, best_x, best_y, bx, by)) return false;
+  return id < best_id;
+}
+// the side of the apex at rho = p_k - p_i of the edge q = p_j - p_i: > 0 on the left (apex[0]'s side), < 0 on the right (apex[1]'s)
+CELL_HD inline int64_t outline_side(int64_t qx, int64_t qy, int64_t rx, int64_t ry) { return qx * ry - qy * rx; }
+CELL_HD inline bool outline_coord_ok(int x, int y) { return x > -CELL_COORD_LIMIT && x < CELL_COORD_LIMIT && y > -CELL_COORD_LIMIT && y < CELL_COORD_LIMIT; }
+// the doubling rounds after which a jump covers h half-edges: the smallest k with 2^k >= h
+CELL_HD inline int outline_rounds(int64_t h) { int k = 0; while (((int64_t)1 << k) < h) ++k; return k; }
+inline bool outline_call_ok(int64_t n, int64_t m, int by_class) {
+  return n >= 0 && n <= ((int64_t)1 << 24) && m >= 0 && m <= OUTLINE_MAX_EDGES && (by_class == 0 || by_class == 1);
 }
 
 // ---- nuclei by region (cellregion.hip): the second input is not the points but polygon EDGES (ax, ay, bx, by), and the test is a

@@ -1,5 +1,6 @@
 // The lock-free union-find over rows that the per-slide point kernels share (gfx950) -- the clusters (cellcluster.hip: the core points)
-// and the minimum spanning forest (cellmst.hip: the two ends of every picked edge).  One forest `parent`, by row, with parent[x] <= x
+// and the minimum spanning forest (cellmst.hip: the two ends of every picked edge); the alpha-shape outline (celloutline.hip) runs it over
+// EDGE indices instead: the sides of one triangle.  One forest `parent`, by row, with parent[x] <= x
 // always: a root is only ever linked under a SMALLER index and the path halving writes an ancestor with atomicMin, so the smallest row of
 // a component is a root for ever and the final root IS that row -- canonical with no further pass.  Nothing here waits on another wave:
 // every loop is bounded by the thread's own arithmetic (cellcluster.hip states the argument in full).

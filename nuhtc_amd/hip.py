@@ -159,7 +159,7 @@ EXPORTS = ['nuhtc_default_config', 'nuhtc_create', 'nuhtc_destroy', 'nuhtc_last_
            'nuhtc_nucleus_texture', 'nuhtc_op_nucleus_texture', 'nuhtc_op_nucleus_gradient', 'nuhtc_op_nucleus_shape', 'nuhtc_op_ring_fill', 'nuhtc_op_frame_gather', 'nuhtc_op_ring_fsd',
            'nuhtc_op_patch_embed', 'nuhtc_op_layernorm', 'nuhtc_op_merge_ln', 'nuhtc_op_fpn_lateral', 'nuhtc_op_sem_fuse', 'nuhtc_op_pointwise64',
            'nuhtc_op_fpn_mean_pool', 'nuhtc_cell_spatial', 'nuhtc_cell_clusters', 'nuhtc_cell_mst', 'nuhtc_cell_proximity', 'nuhtc_cell_density', 'nuhtc_cell_regions', 'nuhtc_cell_margin',
-           'nuhtc_cell_enrichment', 'nuhtc_enrichment_permutation', 'nuhtc_cell_territory', 'nuhtc_territory_adjacency', 'nuhtc_cell_alpha']
+           'nuhtc_cell_enrichment', 'nuhtc_enrichment_permutation', 'nuhtc_cell_territory', 'nuhtc_territory_adjacency', 'nuhtc_cell_alpha', 'nuhtc_alpha_outline']
 
 _lib = None
 
@@ -248,6 +248,7 @@ def load():
     lib.nuhtc_cell_mst.argtypes = [ci, vp, vp, ctypes.c_int64, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp] + [ctypes.POINTER(ctypes.c_int64)] * 3 + [vp]
     lib.nuhtc_cell_proximity.argtypes = [ci, vp, vp, ctypes.c_int64, ci, ci, ci, ctypes.c_int64, ci, ci, ci, ci, vp, vp, vp, vp] + [ctypes.POINTER(ctypes.c_int64)] * 2 + [vp]
     lib.nuhtc_cell_alpha.argtypes = [ci, vp, vp, ctypes.c_int64, ci, ci, ci, ctypes.c_int64, ci, ci, ci, ci, vp, vp, vp, vp, vp] + [ctypes.POINTER(ctypes.c_int64)] * 2 + [vp]
+    lib.nuhtc_alpha_outline.argtypes = [ci, vp, vp, ctypes.c_int64, ci, vp, vp, vp, ctypes.c_int64, vp, vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int64), vp]
     lib.nuhtc_cell_density.argtypes = [ci, vp, vp, ctypes.c_int64] + [ci] * 11 + [vp, vp, vp]
     lib.nuhtc_cell_territory.argtypes = [ci, vp, vp, ctypes.c_int64] + [ci] * 11 + [vp] * 9
     lib.nuhtc_territory_adjacency.argtypes = [ci, vp, ci, ci, ctypes.c_int64, ctypes.c_int64, vp, vp, vp, ctypes.POINTER(ctypes.c_int64), vp]

@@ -1,5 +1,5 @@
 """The per-slide point analyses of the slide path as ONE table: which flag of tools/infer_wsi.py selects each, how its arguments become
-the parameters of its module (cellgraph, spatial, clusters, mst, proximity, density, territory, adjacency, alphacomplex, enrichment, regions, margin: they hold the definitions), which file it writes
+the parameters of its module (cellgraph, spatial, clusters, mst, proximity, density, territory, adjacency, alphacomplex, outline, enrichment, regions, margin: they hold the definitions), which file it writes
 beside the documents and what the closing message says of it.  cellpoints.py is what the modules share and is imported by them; this
 module imports them, one at a time and only when its flag is given.
 
@@ -25,8 +25,12 @@ of OF_THE_PLANE: they build the same window.
 
 OF_THE_CIRCLES, directly behind OF_THE_BORDERS, holds the analyses that state those borders in the continuum, by empty circles through two
 points -- alphacomplex.py: the exact Delaunay edges and triangles within a radius, what adjacency.py reads off a lattice.  Its rows have
-the columns of ANALYSES and take no second input and no window.  `select` visits ANALYSES, OF_THE_PLANE, OF_THE_BORDERS, OF_THE_CIRCLES,
-AGAINST_CHANCE and WITH_INPUT in that order."""
+the columns of ANALYSES and take no second input and no window.
+
+OF_THE_OUTLINES, directly behind OF_THE_CIRCLES, holds the analyses that close those circles' triangles into shapes -- outline.py: the
+rings and the components of the alpha complex, written as an .npz and, beside it, as a GeoJSON of regions that a later run reads with
+--nuclei-regions or --nuclei-margin.  Its rows have the columns of ANALYSES and take no second input and no window.  `select` visits
+ANALYSES, OF_THE_PLANE, OF_THE_BORDERS, OF_THE_CIRCLES, OF_THE_OUTLINES, AGAINST_CHANCE and WITH_INPUT in that order."""
 import importlib
 import os
 from collections import namedtuple
@@ -146,6 +150,24 @@ OF_THE_CIRCLES = (
 )
 
 
+def _outline_said(m, found, p):
+    ring_area2, component, K = found[2], found[4], found[8]
+    area, nuclei = np.zeros(K, np.int64), np.bincount(component[component >= 0], minlength=K)
+    np.add.at(area, found[3], ring_area2)
+    top = f'the largest of {area.max() / 8:g} px^2 with {int(nuclei[area.argmax()])} nuclei' if K else 'none'
+    return (f'{K} alpha-shape components in {found[7]} rings, {int((ring_area2 < 0).sum())} of them holes ({p[0]:g} px radius, by {BY_NAMES[p[1]]}; '
+            f'{top}; components of fewer than {p[2]} nuclei left out of the GeoJSON)')
+
+
+OF_THE_OUTLINES = (
+    _analysis('outline', 'outline',                                   # which shapes the same rows' triangles make: the rings and components of the alpha complex
+              lambda m, a: (a.outline_radius, m.BY[a.outline_by], a.outline_min_nuclei),
+              lambda m, p: m.check_args(1, _half(p[0]), p[1], p[2]),
+              lambda m, path, head, found, C, p, ctx: m.write_npz(path, *head, *found[:6], C, radius_px=p[0], by_class=p[1], min_nuclei=p[2]),
+              _outline_said),
+)
+
+
 def _enrichment_said(m, found, p):
     obs, perm, cn = found
     z = m.derive(obs, perm)['z']
@@ -198,11 +220,11 @@ def _build(an, m, pts, labels, num_classes, params, name, device):
 
 def select(args, need_gpu=True):
     """The parsed arguments of tools/infer_wsi.py -> the selection: ((analysis, params), ..) of the flags given, in the order of ANALYSES, OF_THE_PLANE,
-    OF_THE_BORDERS, OF_THE_CIRCLES, AGAINST_CHANCE and WITH_INPUT.
+    OF_THE_BORDERS, OF_THE_CIRCLES, OF_THE_OUTLINES, AGAINST_CHANCE and WITH_INPUT.
     SystemExit in the name of the flag when its arguments are unusable and then, with need_gpu, when no GPU is visible.  A flag the
     namespace does not hold is not given."""
     chosen = []
-    for an in ANALYSES + OF_THE_PLANE + OF_THE_BORDERS + OF_THE_CIRCLES + AGAINST_CHANCE + WITH_INPUT:
+    for an in ANALYSES + OF_THE_PLANE + OF_THE_BORDERS + OF_THE_CIRCLES + OF_THE_OUTLINES + AGAINST_CHANCE + WITH_INPUT:
         if not getattr(args, an.cli, False):
             continue
         m = module_of(an)

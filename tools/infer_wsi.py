@@ -107,6 +107,17 @@ Output (like the reference, :659-693), for every detection that survives the per
                   `alpha_area_px2`, and `radius_px`, `by_class`.  Exact integers (every decision compares two rationals in int64), unique
                   without a tie rule: cocircular points keep both diagonals, and `n_degenerate` counts them.  Every other file is the
                   same bytes with and without the flag.  There is no route without a GPU.
+  --nuclei-outline: (not in the reference) <id>_nuclei_outline.npz and <id>_nuclei_outline.geojson beside the documents, for the same rows
+                  as --nuclei-graph: the alpha shape of the nucleus centres as polygons -- the outline edges of the alpha complex at
+                  --outline-radius px (32 by default; the limits of --alpha-radius), over all nuclei or with --outline-by class among
+                  nuclei of one label, linked into rings and grouped into components on rank 0's GPU after the gather
+                  (nuhtc_amd/outline.py): `ring_vertex`, `ring_start`, `ring_area2` (positive: an outer ring, negative: a hole),
+                  `component_of_ring`, `component` (per nucleus, -1 in no triangle), `component_label`, the derived `area_px2`,
+                  `hole_area_px2`, `perimeter_px`, `n_holes`, `n_nuclei`, `class_count`, `n_components`, `n_rings`, `largest_component`,
+                  `area_share_by_label`, and `radius_px`, `by_class`.  The GeoJSON holds one Polygon per component with at least
+                  --outline-min-nuclei nuclei (3 by default), outer ring first, in the form --nuclei-regions and --nuclei-margin read in a
+                  LATER run.  Rings that touch themselves at a pinch vertex are written as they are.  Every other file is the same bytes
+                  with and without the flag.  There is no route without a GPU.
   --nuclei-enrichment: (not in the reference) <id>_nuclei_enrichment.npz beside the documents, from the same rows as --nuclei-graph: whether
                   nuclei of one class lie next to nuclei of another more often than chance -- the neighbourhood-enrichment permutation
                   test (histoCAT, squidpy's nhood_enrichment).  The contacts (ordered pairs at most --enrichment-radius px apart, 64 by
@@ -276,6 +287,16 @@ def build_parser():
                    help='largest empty circle of --nuclei-alpha in slide px, a multiple of 0.5 up to 256 (default 32 px: the longest edge is 64 px)')
     p.add_argument('--alpha-by', choices=('any', 'class'), default='any', dest='alpha_by',
                    help="--nuclei-alpha over all nuclei ('any') or only among nuclei of the same label ('class')")
+    p.add_argument('--nuclei-outline', action='store_true', dest='nuclei_outline',
+                   help='also write <id>_nuclei_outline.npz and <id>_nuclei_outline.geojson: the alpha shape of the written nuclei as polygons (the rings and '
+                        'components of the alpha complex, exact integers; the GeoJSON is what --nuclei-regions / --nuclei-margin read), traced on the GPU; '
+                        'from the rows of --nuclei-graph')
+    p.add_argument('--outline-radius', type=float, default=32.0, dest='outline_radius',
+                   help='largest empty circle of --nuclei-outline in slide px, a multiple of 0.5 up to 256 (default 32 px)')
+    p.add_argument('--outline-by', choices=('any', 'class'), default='any', dest='outline_by',
+                   help="--nuclei-outline over all nuclei ('any') or only among nuclei of the same label ('class')")
+    p.add_argument('--outline-min-nuclei', type=int, default=3, dest='outline_min_nuclei',
+                   help='components of --nuclei-outline with fewer nuclei are left out of the GeoJSON (default 3; the .npz holds them all)')
     p.add_argument('--nuclei-enrichment', action='store_true', dest='nuclei_enrichment',
                    help='also write <id>_nuclei_enrichment.npz: the contacts of the written nuclei by class pair, observed and under label permutations, '
                         'with z-scores and empirical p-values (the neighbourhood-enrichment test), counted on the GPU; from the rows of --nuclei-graph')
