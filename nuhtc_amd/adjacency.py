@@ -59,7 +59,7 @@ def first_edge_cap(n):
     planar -- but this is only a first guess on a LATTICE: four territories that meet near one point may all touch one another's sites
     pairwise along the two axes (the graph of the lattice need not be planar), and territories cut by the reach need not be convex.  The
     device says how many there are, and `build` calls once more."""
-    return 3 * int(n) + 64
+    return cellpoints.first_edge_cap(n, 3)
 
 
 def adjacency_reference(owner, n):
@@ -138,17 +138,8 @@ def build(points, labels, num_classes, reach_px, pitch_px, win=None, device=0, w
     cellpoints.raise_for(territory.call(p_d, lab_d, C, r, s, win, *terr, bounds=bounds, device=device), 'nuhtc_cell_territory')
     owner = terr[0]
     del terr[1]                                                               # nearest_d2: not needed, and as large as the map
-    cap, calls = first_edge_cap(n), 1
-    out = outputs(n, cap, dev)
-    rc, m = call(owner, n, cap, *out, device=device)
-    cellpoints.raise_for(rc, 'nuhtc_territory_adjacency')
-    if m > cap:
-        cap, calls = m, 2
-        out = outputs(n, cap, dev)
-        rc, m = call(owner, n, cap, *out, device=device)
-        cellpoints.raise_for(rc, 'nuhtc_territory_adjacency')
-        if m != cap:
-            raise RuntimeError(f'nuhtc_territory_adjacency: {m} edges on the second call, {cap} on the first')
+    out, m, _, calls = cellpoints.grow_to_fit(lambda cap, out: call(owner, n, cap, *out, device=device), lambda cap: outputs(n, cap, dev),
+                                              first_edge_cap(n), 'nuhtc_territory_adjacency', 'adjacency', limit=None)      # m <= 2**29 by the window's cap
     area, border, is_open, contact, class_sites, free_sites = (t.cpu().numpy() for t in terr[1:])
     tallies = (area, border, is_open.astype(np.uint8), contact, class_sites, free_sites.reshape(()))
     got = ((out[0][:m].cpu().numpy(), out[1][:m].cpu().numpy(), out[2][:n].cpu().numpy()), tallies, win)

@@ -78,7 +78,7 @@ def check_args(num_classes, r, by_class):
 def first_edge_cap(n):
     """The rows of capacity of `build`'s first call: a triangulation has fewer than 3 n edges, a lattice that keeps both diagonals of every
     cell fewer than 4 n; coincident and many cocircular points add to that."""
-    return 4 * int(n) + 64
+    return cellpoints.first_edge_cap(n, 4)
 
 
 def _smallest(num, den, valid, rows):
@@ -187,19 +187,9 @@ def build(points, labels, num_classes, radius_px, by_class=0, device=0, with_cal
     check_args(C, r, by_class)
     p, lab, dev, p_d, lab_d, bounds = cellpoints.resident(points, labels, 'alpha', device)
     n = len(p)
-    cap, calls = first_edge_cap(n), 1
-    out = outputs(n, cap, dev)
-    rc, m, m_gab = call(p_d, lab_d, C, r, int(by_class), cap, *out, bounds=bounds, device=device)
-    cellpoints.raise_for(rc, 'nuhtc_cell_alpha')
-    if m > cap:
-        if m >= 1 << 31:
-            raise ValueError(f'alpha: {m} edges, more than 2**31 - 1 (many coincident points)')
-        cap, calls = m, 2
-        out = outputs(n, cap, dev)
-        rc, m, m_gab = call(p_d, lab_d, C, r, int(by_class), cap, *out, bounds=bounds, device=device)
-        cellpoints.raise_for(rc, 'nuhtc_cell_alpha')
-        if m != cap:
-            raise RuntimeError(f'nuhtc_cell_alpha: {m} edges on the second call, {cap} on the first')
+    out, m, (m_gab,), calls = cellpoints.grow_to_fit(
+        lambda cap, out: call(p_d, lab_d, C, r, int(by_class), cap, *out, bounds=bounds, device=device),
+        lambda cap: outputs(n, cap, dev), first_edge_cap(n), 'nuhtc_cell_alpha', 'alpha')
     got = tuple(t[:m].cpu().numpy() for t in out[:4]) + (out[4][:n].cpu().numpy(), m, m_gab)
     return got + (calls,) if with_calls else got
 

@@ -149,6 +149,35 @@ def raise_for(rc, name):
         raise RuntimeError(f'{name} failed ({rc})')
 
 
+def first_edge_cap(n, per_point=4):
+    """The rows of capacity of the first call of an analysis that returns an edge list: per_point * n + 64.  A planar graph has fewer than
+    3 n edges; proximity.py and alphacomplex.py take 4 n (coincident and cocircular points add to a triangulation's count), adjacency.py
+    3 n (a first guess on a lattice).  The device says how many there are when this is too few."""
+    return int(per_point) * int(n) + 64
+
+
+def grow_to_fit(call, make_outputs, first_cap, entry_name, what, limit=1 << 31):
+    """The capacity protocol of the edge-list analyses (proximity.py, alphacomplex.py, adjacency.py), once: the first call has room for
+    first_cap edges; with m > cap the device has written no edge and says how many there are, and ONE second call has room for exactly
+    that many.  call(cap, out) -> (rc, m, *more) never raises; make_outputs(cap) -> out.  -> (out, m, more, calls).  raise_for after
+    each call; ValueError in the name of `what` for m >= limit (None: no such limit, where the device bounds m itself); RuntimeError when
+    the second call counts another m."""
+    cap, calls = int(first_cap), 1
+    out = make_outputs(cap)
+    rc, m, *more = call(cap, out)
+    raise_for(rc, entry_name)
+    if m > cap:
+        if limit is not None and m >= limit:
+            raise ValueError(f'{what}: {m} edges, more than 2**31 - 1 (many coincident points)')
+        cap, calls = m, 2
+        out = make_outputs(cap)
+        rc, m, *more = call(cap, out)
+        raise_for(rc, entry_name)
+        if m != cap:
+            raise RuntimeError(f'{entry_name}: {m} edges on the second call, {cap} on the first')
+    return out, m, tuple(more), calls
+
+
 def distances_px(d2):
     """d2 int, any shape, half pixels^2 -> float32: sqrt(d2) / 2 in pixels, computed in float64 and then cast; inf where d2 < 0 (none)."""
     d2 = np.asarray(d2, np.int64)

@@ -28,8 +28,8 @@
 //   place      only when m <= edge_cap (tested by every thread).  adj_gather_kernel: one thread per slot of the table; an occupied slot
 //              takes the next free place of its row's segment (an atomic on fill[i]: arrival order), where i goes into `edges` and (j,
 //              shared) into two temporaries.  adj_place_kernel: one thread per edge; its place in the segment is the number of edges
-//              there with a smaller j (counting, not sorting: j is distinct within a segment), where j and shared go.  Nothing of the
-//              arrival order or of the hash survives.
+//              there with a smaller j (cell_rank_in_segment of cellgrid_host.h, shared with cellprox.hip, cellalpha.hip and
+//              cellmst.hip), where j and shared go.  Nothing of the arrival order or of the hash survives.
 //
 // The rank costs (up-degree)^2 loads per row.  The up-degree is at most min(n - 1, 4 A) with A the sites a row owns; on a map of the
 // territories a row owns sites within the reach R of its point only, so A <= (floor(2 R / s) + 1)^2 whatever the points do; a territory
@@ -201,9 +201,8 @@ __global__ __launch_bounds__(ADJ_NT) void adj_place_kernel(AdjArgs a) {
   if (m > a.cap || p >= m) return;
   const int lo = a.edges[2 * p], hi = a.s_hi[p];
   if ((unsigned)lo >= (unsigned)a.n) return;             // cannot happen (the gather filled every segment): no index leaves the tables
-  const long long j0 = a.start[lo], j1 = j0 + a.up[lo];
-  long long at = j0;
-  for (long long j = j0; j < j1; ++j) at += a.s_hi[j] < hi;
+  const long long j0 = a.start[lo];
+  const long long at = cell_rank_in_segment(a.s_hi, j0, j0 + a.up[lo], hi);
   a.edges[2 * at + 1] = hi;                              // the even entries of the segment already hold lo, all the same
   a.shared[at] = a.s_cnt[p];
 }

@@ -21,7 +21,8 @@
 // "d2(i, k) < d2(i, j)" window does not apply.
 //
 // Stages, all on the caller's stream, every one a launch of its own; no kernel waits on another workgroup, and every loop runs over a
-// range of the binning's tables:
+// range of the binning's tables (celledgelist.h holds the frame -- the tables, the clear, the read-back, the order of the launches -- and
+// this file the wave kernel and the body of the place kernel):
 //   binning    cellbin.h, reach D, ONE key per cell; by_class is a compare in the sweep's predicate.
 //   count      degree cleared; then ONE WAVE per record i in cell order (alpha_wave_kernel): the records of its 3 x 3 cells are staged in
 //              LDS, the candidates j with a LARGER row sit across the lanes, 64 at a time -- every candidate is tested once, from the
@@ -36,79 +37,40 @@
 //   emit       the count stage again (the test is a pure function of the records, so the two passes agree), now with the apexes: the
 //              edges among 64 candidates are ranked by a ballot, and the record writes i into `edges` and (j, d2 | Gabriel bit, the
 //              apexes) into temporaries at its own segment -- private to the wave, no atomics.
-//   place      one thread per edge: its place in the segment is the number of edges there with a smaller j (counting, not sorting: the
-//              order inside a cell is atomic arrival order, and j is distinct within a segment), where j, d2, the apexes and the byte go.
+//   place      one thread per edge: its place in the segment is the number of edges there with a smaller j (cell_rank_in_segment of
+//              cellgrid_host.h), where j, d2, the apexes and the byte go.
 //
 // A point outside the stated box raises the binning's flag; every kernel tests it, nothing is written to the outputs, and the call
 // returns NUHTC_E_INVALID.
 //
-// Resources (hipcc -Rpass-analysis=kernel-resource-usage, profiles/cell_alpha_resources.txt): no LDS and no scratch in any shipped kernel.
-// Two dev probes of the witness loop, both timed against the shipped route in profiles/cell_alpha.json: -DNUHTC_ALPHA_DIRECT walks all of
-// the 3 x 3 cells around the record instead of the overlap window; -DNUHTC_ALPHA_WAVE is the other route altogether, one wave per record
-// with the candidates across the lanes and the witnesses staged in LDS (alpha_wave_kernel below).
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, profiles/cell_alpha_resources.txt): alpha_wave_kernel<false / true>, the shipped
+// count and emit stage, 30 / 32 VGPRs and 8 KB of LDS (5 waves per SIMD); alpha_place_kernel 14 VGPRs, no LDS; no scratch anywhere.  The
+// shipped library holds only these and the frame's clear kernel.  Two dev probes, both timed against the shipped route in
+// profiles/cell_alpha.json: -DNUHTC_ALPHA_THREAD is the route that was built first, one THREAD per record with the witnesses read from
+// global memory through the overlap window of the pair (alpha_test, alpha_count_kernel, alpha_emit_kernel and the kept verdicts, compiled
+// only then); -DNUHTC_ALPHA_DIRECT, on top of it, walks all of the 3 x 3 cells around the record instead of the window.
 #include <climits>
 #include <cstring>
 
-#include "cellbin.h"
+#include "celledgelist.h"
 
 namespace {
 
 constexpr int ALPHA_MAX_CELLS = 1 << 22;
 constexpr int ALPHA_NT = 256;
-constexpr int ALPHA_SLOTS = 64;       // pairs of 64-bit counters the totals are spread over (the wave probe adds one pair per record)
-constexpr int ALPHA_KEPT = 64;        // candidates per record whose verdict the count stage keeps for the emit stage
+constexpr int ALPHA_SLOTS = 64;       // pairs of 64-bit counters the totals are spread over (the wave route adds one pair per record)
 
 struct CellAlphaArgs {
   CellBin b;                          // the points, the grid and the records in cell order (cellbin.h, one key per cell)
-  int n, D, by_class;
-  long long m;                        // the edges, known on the host after the count stage
-  int* count;                         // [fchunk * CB_CHUNK] by row: the edges whose smaller row it is; zero past n
-  int* start;                         // [fchunk * CB_CHUNK] by row: the edges in front of its segment
-  unsigned long long* totals;         // [ALPHA_SLOTS][2] m, m_gabriel: summed on the host
+  EdgeList e;                         // the edges (celledgelist.h); totals: ALPHA_SLOTS pairs, m and m_gabriel
+  int D, by_class;
+#ifdef NUHTC_ALPHA_THREAD
   unsigned long long* kept;           // [n] by POSITION in cell order: which of the record's first 64 candidates are edges
-  int* s_hi;                          // [m] the larger row of every edge, segment by segment, sweep order inside
-  int* s_d2;                          // [m] its d2 | ALPHA_GABRIEL_BIT
-  int2* s_apex;                       // [m] its apexes
-  int32_t* edges; int32_t* edge_d2; int32_t* apex; uint8_t* edge_gabriel; int32_t* degree;
-};
-
-// bit 0: (me, o) at d2 is an edge; bit 1: it is Gabriel as well; apex[0..1] written for an edge.  The ends are not told from the
-// witnesses (cellgrid_host.h).  d2 == 0 consults no witness.  The witness loop runs over the WINDOW of cells that can hold a binding
-// witness: the overlap of the two boxes of half-width D around the ends, inside the 3 x 3 cells around me (at most three rows of at most
-// three cells, each row one contiguous range of records); the row of the pair's midpoint goes first, where the witnesses that kill a
-// pair are likeliest.
-__device__ __forceinline__ int alpha_test(const CellBin& g, const int4& me, const int4& o, int d2, int D, int D2, int by_class, int* apex) {
-  if (d2 == 0) { apex[0] = apex[1] = -1; return 3; }
-#ifdef NUHTC_ALPHA_DIRECT                               // (with -DNUHTC_ALPHA_THREAD)
-  const int cx = (me.x - g.x_min) / g.side, cy = (me.y - g.y_min) / g.side;
-  const int gx0 = max(cx - 1, 0), gx1 = min(cx + 1, g.ncx - 1), gy0 = max(cy - 1, 0), gy1 = min(cy + 1, g.ncy - 1);
-#else
-  const int xa = max(max(me.x, o.x) - D, g.x_min), xb = min(min(me.x, o.x) + D, g.x_max);
-  const int ya = max(max(me.y, o.y) - D, g.y_min), yb = min(min(me.y, o.y) + D, g.y_max);
-  const int gx0 = (xa - g.x_min) / g.side, gx1 = (xb - g.x_min) / g.side, gy0 = (ya - g.y_min) / g.side, gy1 = (yb - g.y_min) / g.side;
 #endif
-  const int gm = min(max(((me.y + o.y) / 2 - g.y_min) / g.side, gy0), gy1);
-  const int qx = o.x - me.x, qy = o.y - me.y;
-  AlphaState st = alpha_open();
-  bool dead = false;
-  for (int t = 0; t < 3 && !dead; ++t) {
-    const int gy = t == 0 ? gm : t == 1 ? gm - 1 : gm + 1;
-    if (gy < gy0 || gy > gy1) continue;
-    const int k1 = g.cell_start[gy * g.ncx + gx1 + 1];
-    for (int k = g.cell_start[gy * g.ncx + gx0]; k < k1 && !dead; ++k) {
-      const int4 c = g.recs[k];
-      if (by_class && c.z != me.z) continue;
-      if (alpha_witness(st, qx, qy, c.x - me.x, c.y - me.y, c.w, D, D2)) dead = alpha_dead(st, d2, D2);
-    }
-  }
-  return dead ? 0 : alpha_verdict(st, d2, D2, apex);
-}
-
-__device__ __forceinline__ unsigned long long alpha_wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned long long)__shfl_xor(v, o);
-  return v;
-}
+  int* s_d2;                          // [m] beside e.s_hi: the edge's d2 | ALPHA_GABRIEL_BIT
+  int2* s_apex;                       // [m] its apexes
+  int32_t* edge_d2; int32_t* apex; uint8_t* edge_gabriel;
+};
 
 #ifndef NUHTC_ALPHA_THREAD
 // The shipped route of the witness loop: ONE WAVE per record (a workgroup of 64 threads, so that its
@@ -117,29 +79,11 @@ __device__ __forceinline__ unsigned long long alpha_wave_sum(unsigned long long 
 // staged witnesses for its own candidate (the same LDS address across the wave: a broadcast read); alpha_witness passes the far ones
 // over.  The count form adds the degrees and the totals, the emit form ranks the edges of 64 candidates by a ballot and writes them to
 // the record's segment.  Both test every candidate: no kept flags.  profiles/cell_alpha.json has it against the thread-per-record route
-// (-DNUHTC_ALPHA_THREAD: alpha_count_kernel and alpha_emit_kernel with alpha_test, the route that was built first).
+// (-DNUHTC_ALPHA_THREAD below).
 constexpr int ALPHA_STAGE = 512;
 
-struct AlphaRows { int j0[3], n[3], total; };
-
-__device__ __forceinline__ AlphaRows alpha_rows(const CellBin& g, const int4& me) {
-  const int cx = (me.x - g.x_min) / g.side, cy = (me.y - g.y_min) / g.side;
-  const int cx0 = max(cx - 1, 0), cx1 = min(cx + 1, g.ncx - 1);
-  AlphaRows w;
-  w.total = 0;
-#pragma unroll
-  for (int t = 0; t < 3; ++t) {
-    const int gy = cy - 1 + t;
-    const bool in = gy >= 0 && gy < g.ncy;                 // a row outside the grid is empty
-    w.j0[t] = in ? g.cell_start[gy * g.ncx + cx0] : 0;
-    w.n[t] = in ? g.cell_start[gy * g.ncx + cx1 + 1] - w.j0[t] : 0;
-    w.total += w.n[t];
-  }
-  return w;
-}
-
 // the position among the records of the c-th record of the three rows, 0 <= c < w.total
-__device__ __forceinline__ int alpha_pos(const AlphaRows& w, int c) {
+__device__ __forceinline__ int alpha_pos(const CellRows& w, int c) {
   if (c < w.n[0]) return w.j0[0] + c;
   c -= w.n[0];
   return c < w.n[1] ? w.j0[1] + c : w.j0[2] + c - w.n[1];
@@ -155,11 +99,11 @@ __global__ __launch_bounds__(64) void alpha_wave_kernel(CellAlphaArgs a) {
   int room = 0;
   long long base = 0;
   if (EMIT) {
-    room = a.count[me.w];
+    room = a.e.count[me.w];
     if (!room) return;                                   // uniform: before any barrier
-    base = a.start[me.w];
+    base = a.e.start[me.w];
   }
-  const AlphaRows w = alpha_rows(g, me);
+  const CellRows w = cell_rows(g, me);
   const int by_class = a.by_class, D = a.D, D2 = a.D * a.D;
   const bool all = w.total <= ALPHA_STAGE;
   if (all) {
@@ -199,16 +143,16 @@ __global__ __launch_bounds__(64) void alpha_wave_kernel(CellAlphaArgs a) {
     if (!EMIT) {
       if (f & 1) {
         ++cnt;
-        atomicAdd(a.degree + 2 * o.w, 1);
-        if (f & 2) { ++cnt_gab; atomicAdd(a.degree + 2 * o.w + 1, 1); }
+        atomicAdd(a.e.degree + 2 * o.w, 1);
+        if (f & 2) { ++cnt_gab; atomicAdd(a.e.degree + 2 * o.w + 1, 1); }
       }
     } else {
       const unsigned long long edge = __ballot(f & 1);
       const int rank = at + __popcll(edge & ((1ull << lane) - 1));
       if ((f & 1) && rank < room) {                      // rank < room always (the two passes agree): no index leaves the segment
         const long long p = base + rank;
-        a.edges[2 * p] = me.w;
-        a.s_hi[p] = o.w;
+        a.e.edges[2 * p] = me.w;
+        a.e.s_hi[p] = o.w;
         a.s_d2[p] = d2 | (f & 2 ? ALPHA_GABRIEL_BIT : 0);
         a.s_apex[p] = make_int2(apex[0], apex[1]);
       }
@@ -216,20 +160,46 @@ __global__ __launch_bounds__(64) void alpha_wave_kernel(CellAlphaArgs a) {
     }
   }
   if (!EMIT) {
-    const unsigned long long m = alpha_wave_sum((unsigned long long)cnt), m_gab = alpha_wave_sum((unsigned long long)cnt_gab);
+    const unsigned long long m = (unsigned long long)wave_sum((long long)cnt), m_gab = (unsigned long long)wave_sum((long long)cnt_gab);
     if (lane == 0) {
-      a.count[me.w] = (int)m;                            // at most the records of nine cells
-      if (m) { atomicAdd(a.degree + 2 * me.w, (int)m); atomicAdd(a.totals + 2 * (q & (ALPHA_SLOTS - 1)), m); }
-      if (m_gab) { atomicAdd(a.degree + 2 * me.w + 1, (int)m_gab); atomicAdd(a.totals + 2 * (q & (ALPHA_SLOTS - 1)) + 1, m_gab); }
+      a.e.count[me.w] = (int)m;                          // at most the records of nine cells
+      if (m) { atomicAdd(a.e.degree + 2 * me.w, (int)m); atomicAdd(a.e.totals + 2 * (q & (ALPHA_SLOTS - 1)), m); }
+      if (m_gab) { atomicAdd(a.e.degree + 2 * me.w + 1, (int)m_gab); atomicAdd(a.e.totals + 2 * (q & (ALPHA_SLOTS - 1)) + 1, m_gab); }
     }
   }
 }
-#endif
 
-__global__ __launch_bounds__(ALPHA_NT) void alpha_clear_kernel(CellAlphaArgs a) {
-  if (*a.b.flag) return;                                 // the binning met a point outside the box: nothing is written
-  const int i = blockIdx.x * ALPHA_NT + threadIdx.x;
-  if (i < 2 * a.n) a.degree[i] = 0;                      // 2 n <= 2^25
+#else
+// dev probe (-DNUHTC_ALPHA_THREAD), the route that was built first: one THREAD per record, cell_sweep for the candidates and alpha_test
+// for each of them; the count stage keeps the verdict of a record's first ALPHA_KEPT candidates for the emit stage.
+constexpr int ALPHA_KEPT = 64;
+
+// bit 0: (me, o) at d2 is an edge; bit 1: it is Gabriel as well; apex[0..1] written for an edge.  The ends are not told from the
+// witnesses (cellgrid_host.h).  d2 == 0 consults no witness.  The witness loop runs over the WINDOW of cells that can hold a binding
+// witness: the overlap of the two boxes of half-width D around the ends (cell_pair_window of cellbin.h); the row of the pair's midpoint
+// goes first, where the witnesses that kill a pair are likeliest.
+__device__ __forceinline__ int alpha_test(const CellBin& g, const int4& me, const int4& o, int d2, int D, int D2, int by_class, int* apex) {
+  if (d2 == 0) { apex[0] = apex[1] = -1; return 3; }
+  CellWindow v = cell_pair_window(g, me, o, D);
+#ifdef NUHTC_ALPHA_DIRECT                               // all of the 3 x 3 cells around me, the midpoint's row still first
+  const int cx = (me.x - g.x_min) / g.side, cy = (me.y - g.y_min) / g.side;
+  v.gx0 = max(cx - 1, 0); v.gx1 = min(cx + 1, g.ncx - 1); v.gy0 = max(cy - 1, 0); v.gy1 = min(cy + 1, g.ncy - 1);
+  v.gm = min(max(((me.y + o.y) / 2 - g.y_min) / g.side, v.gy0), v.gy1);
+#endif
+  const int qx = o.x - me.x, qy = o.y - me.y;
+  AlphaState st = alpha_open();
+  bool dead = false;
+  for (int t = 0; t < 3 && !dead; ++t) {
+    const int gy = t == 0 ? v.gm : t == 1 ? v.gm - 1 : v.gm + 1;
+    if (gy < v.gy0 || gy > v.gy1) continue;
+    const int k1 = g.cell_start[gy * g.ncx + v.gx1 + 1];
+    for (int k = g.cell_start[gy * g.ncx + v.gx0]; k < k1 && !dead; ++k) {
+      const int4 c = g.recs[k];
+      if (by_class && c.z != me.z) continue;
+      if (alpha_witness(st, qx, qy, c.x - me.x, c.y - me.y, c.w, D, D2)) dead = alpha_dead(st, d2, D2);
+    }
+  }
+  return dead ? 0 : alpha_verdict(st, d2, D2, apex);
 }
 
 __global__ __launch_bounds__(ALPHA_NT) void alpha_count_kernel(CellAlphaArgs a) {
@@ -237,7 +207,7 @@ __global__ __launch_bounds__(ALPHA_NT) void alpha_count_kernel(CellAlphaArgs a) 
   if (*g.flag) return;                                   // uniform
   const int q = blockIdx.x * ALPHA_NT + threadIdx.x;
   int cnt = 0, cnt_gab = 0;                              // every lane of a wave takes part in the reduction: no early return
-  if (q < a.n) {
+  if (q < a.e.n) {
     const int4 me = g.recs[q];
     const int by_class = a.by_class, D = a.D, D2 = a.D * a.D;
     unsigned long long keep = 0;
@@ -249,30 +219,30 @@ __global__ __launch_bounds__(ALPHA_NT) void alpha_count_kernel(CellAlphaArgs a) 
       ++seen;
       if (!(f & 1)) return;
       ++cnt;
-      atomicAdd(a.degree + 2 * o.w, 1);
-      if (f & 2) { ++cnt_gab; atomicAdd(a.degree + 2 * o.w + 1, 1); }
+      atomicAdd(a.e.degree + 2 * o.w, 1);
+      if (f & 2) { ++cnt_gab; atomicAdd(a.e.degree + 2 * o.w + 1, 1); }
     });
-    a.count[me.w] = cnt;
+    a.e.count[me.w] = cnt;
     a.kept[q] = keep;
-    if (cnt) atomicAdd(a.degree + 2 * me.w, cnt);
-    if (cnt_gab) atomicAdd(a.degree + 2 * me.w + 1, cnt_gab);
+    if (cnt) atomicAdd(a.e.degree + 2 * me.w, cnt);
+    if (cnt_gab) atomicAdd(a.e.degree + 2 * me.w + 1, cnt_gab);
   }
-  const unsigned long long m = alpha_wave_sum((unsigned long long)cnt), m_gab = alpha_wave_sum((unsigned long long)cnt_gab);
+  const long long m = wave_sum((long long)cnt), m_gab = wave_sum((long long)cnt_gab);
   if ((threadIdx.x & 63) == 0) {
-    if (m) atomicAdd(a.totals, m);
-    if (m_gab) atomicAdd(a.totals + 1, m_gab);
+    if (m) atomicAdd(a.e.totals, (unsigned long long)m);
+    if (m_gab) atomicAdd(a.e.totals + 1, (unsigned long long)m_gab);
   }
 }
 
 __global__ __launch_bounds__(ALPHA_NT) void alpha_emit_kernel(CellAlphaArgs a) {
   const CellBin& g = a.b;
   const int q = blockIdx.x * ALPHA_NT + threadIdx.x;
-  if (q >= a.n) return;
+  if (q >= a.e.n) return;
   const int4 me = g.recs[q];
-  const int room = a.count[me.w];
+  const int room = a.e.count[me.w];
   if (!room) return;
   const int by_class = a.by_class, D = a.D, D2 = a.D * a.D;
-  const long long base = a.start[me.w];
+  const long long base = a.e.start[me.w];
   const unsigned long long keep = a.kept[q];
   int seen = 0, at = 0;
   cell_sweep(g, me, D, [&](const int4& o) { return o.w > me.w && (!by_class || o.z == me.z); }, [&](int, const int4& o, int d2) {
@@ -283,24 +253,24 @@ __global__ __launch_bounds__(ALPHA_NT) void alpha_emit_kernel(CellAlphaArgs a) {
     const int f = alpha_test(g, me, o, d2, D, D2, by_class, apex);
     if (!(f & 1)) return;
     const long long p = base + at++;
-    a.edges[2 * p] = me.w;
-    a.s_hi[p] = o.w;
+    a.e.edges[2 * p] = me.w;
+    a.e.s_hi[p] = o.w;
     a.s_d2[p] = d2 | (f & 2 ? ALPHA_GABRIEL_BIT : 0);
     a.s_apex[p] = make_int2(apex[0], apex[1]);
   });
 }
+#endif
 
 __global__ __launch_bounds__(ALPHA_NT) void alpha_place_kernel(CellAlphaArgs a) {
   const long long p = (long long)blockIdx.x * ALPHA_NT + threadIdx.x;
-  if (p >= a.m) return;
-  const int lo = a.edges[2 * p], hi = a.s_hi[p];
-  if ((unsigned)lo >= (unsigned)a.n) return;             // cannot happen (the emit stage filled every segment): no index leaves the tables
-  const long long j0 = a.start[lo], j1 = j0 + a.count[lo];
-  long long at = j0;
-  for (long long j = j0; j < j1; ++j) at += a.s_hi[j] < hi;
+  if (p >= a.e.m) return;
+  const int lo = a.e.edges[2 * p], hi = a.e.s_hi[p];
+  if ((unsigned)lo >= (unsigned)a.e.n) return;           // cannot happen (the emit stage filled every segment): no index leaves the tables
+  const long long j0 = a.e.start[lo];
+  const long long at = cell_rank_in_segment(a.e.s_hi, j0, j0 + a.e.count[lo], hi);
   const int d2 = a.s_d2[p];
   const int2 ap = a.s_apex[p];
-  a.edges[2 * at + 1] = hi;                              // the even entries of the segment already hold lo, all the same
+  a.e.edges[2 * at + 1] = hi;                            // the even entries of the segment already hold lo, all the same
   a.edge_d2[at] = d2 & (ALPHA_GABRIEL_BIT - 1);
   a.apex[2 * at] = ap.x; a.apex[2 * at + 1] = ap.y;
   a.edge_gabriel[at] = (uint8_t)((d2 & ALPHA_GABRIEL_BIT) != 0);
@@ -318,64 +288,34 @@ extern "C" int nuhtc_cell_alpha(int device, const int32_t* points, const int32_t
   hipStream_t s = (hipStream_t)stream;
   CellAlphaArgs a;
   memset(&a, 0, sizeof(a));
-  a.n = (int)n; a.D = 2 * r; a.by_class = by_class;
-  a.edges = edges; a.edge_d2 = edge_d2; a.apex = apex; a.edge_gabriel = edge_gabriel; a.degree = degree;
+  a.e.n = (int)n; a.D = 2 * r; a.by_class = by_class;
+  a.e.edges = edges; a.edge_d2 = edge_d2; a.apex = apex; a.edge_gabriel = edge_gabriel; a.e.degree = degree;
   DevScratch tmp;      // every temporary of the call, freed on the way out
   const int nchunk = cellbin_setup(a.b, points, labels, (int)n, x_min, y_min, x_max, y_max, a.D, ALPHA_MAX_CELLS, 1, tmp, s);
   if (!nchunk) return NUHTC_E_HIP;
-  const int fchunk = (int)((n + CB_CHUNK - 1) / CB_CHUNK);                 // scan chunks of the n counts: at most 1024
-  const size_t scan_bytes = (size_t)fchunk * CB_CHUNK * sizeof(int);
-  a.count = tmp.alloc<int>(scan_bytes); a.start = tmp.alloc<int>(scan_bytes);
-  const ExScan scan{a.count, a.start, tmp.alloc<int>(1024 * sizeof(int))};
-  a.totals = tmp.alloc<unsigned long long>(2 * ALPHA_SLOTS * sizeof(unsigned long long));
-#ifdef NUHTC_ALPHA_THREAD
-  a.kept = tmp.alloc<unsigned long long>((size_t)n * sizeof(unsigned long long));
-#endif
-  if (!tmp.ok()) return NUHTC_E_HIP;
-  if (hipMemsetAsync(a.count, 0, scan_bytes, s) != hipSuccess || hipMemsetAsync(a.totals, 0, 2 * ALPHA_SLOTS * sizeof(unsigned long long), s) != hipSuccess)
+  EdgeListRun h;
+  if (!edgelist_setup(a.e, h, {"cell_alpha_bin", "cell_alpha_count", "cell_alpha_scan", "cell_alpha_emit", "cell_alpha_place"}, ALPHA_SLOTS, tmp, s))
     return NUHTC_E_HIP;
+#ifndef NUHTC_ALPHA_THREAD
+  auto count = [&] { hipLaunchKernelGGL(alpha_wave_kernel<false>, dim3((unsigned)n), dim3(64), 0, s, a); };
+  auto emit = [&] { hipLaunchKernelGGL(alpha_wave_kernel<true>, dim3((unsigned)n), dim3(64), 0, s, a); };
+#else
+  a.kept = tmp.alloc<unsigned long long>((size_t)n * sizeof(unsigned long long));
+  if (!tmp.ok()) return NUHTC_E_HIP;
   const unsigned nb = (unsigned)((n + ALPHA_NT - 1) / ALPHA_NT);
-  {
-    ProfScope ps("cell_alpha_bin", 0, 0, s);
-    cellbin_launch(a.b, nchunk, s);
-  }
-  {
-    ProfScope ps("cell_alpha_count", 0, 0, s);
-    hipLaunchKernelGGL(alpha_clear_kernel, dim3((unsigned)((2 * n + ALPHA_NT - 1) / ALPHA_NT)), dim3(ALPHA_NT), 0, s, a);
-#ifndef NUHTC_ALPHA_THREAD
-    hipLaunchKernelGGL(alpha_wave_kernel<false>, dim3((unsigned)n), dim3(64), 0, s, a);
-#else
-    hipLaunchKernelGGL(alpha_count_kernel, dim3(nb), dim3(ALPHA_NT), 0, s, a);
+  auto count = [&] { hipLaunchKernelGGL(alpha_count_kernel, dim3(nb), dim3(ALPHA_NT), 0, s, a); };
+  auto emit = [&] { hipLaunchKernelGGL(alpha_emit_kernel, dim3(nb), dim3(ALPHA_NT), 0, s, a); };
 #endif
-  }
-  unsigned long long h_slots[2 * ALPHA_SLOTS], h_tot[2] = {0, 0};
-  if (hipMemcpyAsync(h_slots, a.totals, sizeof(h_slots), hipMemcpyDeviceToHost, s) != hipSuccess) return NUHTC_E_HIP;
-  int rc = cellbin_finish(a.b, s);                       // the flag, and the stream synchronised: the totals are here
+  long long gabriel = 0;
+  int rc = edgelist_count(a.b, nchunk, a.e, h, count, &gabriel, s);
   if (rc) return rc;
-  for (int k = 0; k < ALPHA_SLOTS; ++k) { h_tot[0] += h_slots[2 * k]; h_tot[1] += h_slots[2 * k + 1]; }
-  a.m = (long long)h_tot[0];
-  if (a.m > 0 && a.m <= edge_cap) {                      // a.m <= INT_MAX from here on: the int32 scan is safe
-    a.s_hi = tmp.alloc<int>((size_t)a.m * sizeof(int)); a.s_d2 = tmp.alloc<int>((size_t)a.m * sizeof(int));
-    a.s_apex = tmp.alloc<int2>((size_t)a.m * sizeof(int2));
+  if (a.e.m > 0 && a.e.m <= edge_cap) {
+    a.e.s_hi = tmp.alloc<int>((size_t)a.e.m * sizeof(int)); a.s_d2 = tmp.alloc<int>((size_t)a.e.m * sizeof(int));
+    a.s_apex = tmp.alloc<int2>((size_t)a.e.m * sizeof(int2));
     if (!tmp.ok()) return NUHTC_E_HIP;
-    {
-      ProfScope ps("cell_alpha_scan", 0, 0, s);
-      exscan_launch(scan, fchunk, s);
-    }
-    {
-      ProfScope ps("cell_alpha_emit", 0, 0, s);
-#ifndef NUHTC_ALPHA_THREAD
-      hipLaunchKernelGGL(alpha_wave_kernel<true>, dim3((unsigned)n), dim3(64), 0, s, a);
-#else
-      hipLaunchKernelGGL(alpha_emit_kernel, dim3(nb), dim3(ALPHA_NT), 0, s, a);
-#endif
-    }
-    {
-      ProfScope ps("cell_alpha_place", 0, 0, s);
-      hipLaunchKernelGGL(alpha_place_kernel, dim3((unsigned)((a.m + ALPHA_NT - 1) / ALPHA_NT)), dim3(ALPHA_NT), 0, s, a);
-    }
-    if (!launched() || hipStreamSynchronize(s) != hipSuccess) return NUHTC_E_HIP;
+    rc = edgelist_finish(h, emit, [&] { hipLaunchKernelGGL(alpha_place_kernel, dim3((unsigned)((a.e.m + ALPHA_NT - 1) / ALPHA_NT)), dim3(ALPHA_NT), 0, s, a); }, s);
+    if (rc) return rc;
   }
-  *m = a.m; *m_gabriel = (int64_t)h_tot[1];
+  *m = a.e.m; *m_gabriel = gabriel;
   return 0;
 }

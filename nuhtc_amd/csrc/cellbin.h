@@ -1,5 +1,5 @@
 // What the per-slide analyses of half-pixel points share on the device (gfx950) -- the cell graph (cellgraph.hip), the pair histograms
-// (cellspatial.hip), the clusters (cellcluster.hip), the minimum spanning forest (cellmst.hip), the proximity graphs (cellprox.hip), the alpha complex (cellalpha.hip), the density rasters (celldensity.hip), the territories (cellterritory.hip), the region census and the margin bands (cellregion.hip, cellmargin.hip: their edges are binned by celledges.h, on this scan) and the neighbourhood enrichment (cellenrich.hip); cellgrid_host.h holds the plain-C++ side (limits, geometry, keys, pair distance).
+// (cellspatial.hip), the clusters (cellcluster.hip), the minimum spanning forest (cellmst.hip), the proximity graphs (cellprox.hip), the alpha complex (cellalpha.hip), the density rasters (celldensity.hip), the territories (cellterritory.hip), the region census and the margin bands (cellregion.hip, cellmargin.hip: their edges are binned by celledges.h, on this scan) and the neighbourhood enrichment (cellenrich.hip); celledgelist.h holds the count / scan / emit / place frame of the analyses that return an edge list (cellprox.hip, cellalpha.hip), celladjacency.hip uses the scan alone; cellgrid_host.h holds the plain-C++ side (limits, geometry, keys, pair distance).
 //   binning   a histogram of the points per key (atomics), an exclusive scan of the keys, and a scatter of (x, y, label, index) records
 //             into key order.  A key is a cell, or a (cell, class) pair (cell_key).  The order of the records INSIDE a key is atomic
 //             arrival order; nothing downstream may depend on it.  A point outside the stated bounding box raises the flag and is left
@@ -7,6 +7,8 @@
 //   scan      exclusive scan of up to 1024 chunks of CB_CHUNK ints (ExScan, exscan_launch): block_exscan_1024 of block_prims.h on 16
 //             ints per thread -- per-chunk totals, a scan of the totals, the chunks again with their base.
 //   sweep     cell_sweep: the records within reach of a point, from the 3 x 3 cells around it (one key per cell).
+//   witness   cell_rows and cell_pair_window: the three row ranges of those cells, and the window of them that can hold a witness of a
+//             pair (the witness loops of cellprox.hip and cellalpha.hip).
 //   epilogue  cellbin_finish: the flag read back, the stream synchronised, the return code.
 #pragma once
 #include "block_prims.h"
@@ -158,6 +160,42 @@ __device__ __forceinline__ void cell_sweep(const CellBin& g, const int4 me, int 
       if (d2 >= 0) f(j, o, d2);
     }
   }
+}
+
+// ---- what the witness loops of cellprox.hip and cellalpha.hip share (the loops themselves differ in substance and stay apart)
+// The three rows of the 3 x 3 cells around me (cell_sweep's), each one contiguous range of records: row t starts at position j0[t] and
+// holds n[t] records, `total` in all; a row outside the grid is empty.
+struct CellRows { int j0[3], n[3], total; };
+
+__device__ __forceinline__ CellRows cell_rows(const CellBin& g, const int4& me) {
+  const int cx = (me.x - g.x_min) / g.side, cy = (me.y - g.y_min) / g.side;
+  const int cx0 = max(cx - 1, 0), cx1 = min(cx + 1, g.ncx - 1);
+  CellRows w;
+  w.total = 0;
+#pragma unroll
+  for (int t = 0; t < 3; ++t) {
+    const int gy = cy - 1 + t;
+    const bool in = gy >= 0 && gy < g.ncy;                 // a row outside the grid is empty
+    w.j0[t] = in ? g.cell_start[gy * g.ncx + cx0] : 0;
+    w.n[t] = in ? g.cell_start[gy * g.ncx + cx1 + 1] - w.j0[t] : 0;
+    w.total += w.n[t];
+  }
+  return w;
+}
+
+// The WINDOW of cells that can hold a witness of the pair (me, o) when a witness lies within d of BOTH ends: the overlap of the two boxes
+// of half-width d around the ends, clipped to the box of the grid -- columns gx0 .. gx1 of rows gy0 .. gy1, inside the 3 x 3 cells around
+// me when d <= side (at most three rows of at most three cells, each row one contiguous range of records).  gm is the row of the pair's
+// midpoint, clamped to the window: the row to walk first, where the witnesses that decide a pair are likeliest.
+struct CellWindow { int gx0, gx1, gy0, gy1, gm; };
+
+__device__ __forceinline__ CellWindow cell_pair_window(const CellBin& g, const int4& me, const int4& o, int d) {
+  const int xa = max(max(me.x, o.x) - d, g.x_min), xb = min(min(me.x, o.x) + d, g.x_max);
+  const int ya = max(max(me.y, o.y) - d, g.y_min), yb = min(min(me.y, o.y) + d, g.y_max);
+  CellWindow w;
+  w.gx0 = (xa - g.x_min) / g.side; w.gx1 = (xb - g.x_min) / g.side; w.gy0 = (ya - g.y_min) / g.side; w.gy1 = (yb - g.y_min) / g.side;
+  w.gm = min(max(((me.y + o.y) / 2 - g.y_min) / g.side, w.gy0), w.gy1);
+  return w;
 }
 
 // The end of an entry point: were the launches accepted, the binning's flag read back (and, where the caller has one, one more int of

@@ -1,6 +1,6 @@
 // The uniform grid over half-pixel points that the per-slide analyses share (cellbin.h; cellgraph.hip, cellspatial.hip, cellcluster.hip,
-// cellmst.hip, cellprox.hip, celldensity.hip, cellterritory.hip, celladjacency.hip, cellalpha.hip, celloutline.hip, cellregion.hip, cellmargin.hip, cellenrich.hip): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
-// and the (cell, class) key of a point, the squared distance of a pair within reach, and the edge key of the spanning forest.  Header-only,
+// cellmst.hip, cellprox.hip, celldensity.hip, cellterritory.hip, celladjacency.hip, cellalpha.hip, celloutline.hip, cellregion.hip, cellmargin.hip, cellenrich.hip; celledgelist.h, the frame of the edge-list analyses): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
+// and the (cell, class) key of a point, the squared distance of a pair within reach, the rank of an edge in its row's segment, and the edge key of the spanning forest.  Header-only,
 // so a host program can exercise them under a sanitizer (tools/dev/cellspatial_host_check.cpp, tools/dev/cellmst_host_check.cpp, tools/dev/cellprox_host_check.cpp,
 // tools/dev/celldensity_host_check.cpp, tools/dev/cellregion_host_check.cpp, tools/dev/cellmargin_host_check.cpp, tools/dev/cellenrich_host_check.cpp, tools/dev/cellterritory_host_check.cpp, tools/dev/celladjacency_host_check.cpp, tools/dev/cellalpha_host_check.cpp, tools/dev/celloutline_host_check.cpp); the kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
 #pragma once
@@ -48,6 +48,18 @@ CELL_HD inline int cell_pair_d2(int dx, int dy, int reach, int reach2) {
   if (dx > reach || dx < -reach || dy > reach || dy < -reach) return -1;
   const int d2 = dx * dx + dy * dy;
   return d2 > reach2 ? -1 : d2;
+}
+
+// ---- the place of an edge in the segment of its smaller row, for the analyses that return an edge list in ascending (i, j) order
+// (cellprox.hip, cellalpha.hip, celladjacency.hip, cellmst.hip: their place kernels, one thread per edge).  s_hi[j0 .. j1) holds the
+// larger row of every edge of the segment in ARRIVAL order (the order inside a cell or a hash table is atomic arrival order and must
+// not survive); the edge with the larger row `hi` belongs at j0 + the number of edges there with a smaller one.  Counting, not sorting:
+// j is distinct within a segment, so the places of a segment are a permutation of j0 .. j1 - 1, and the work is linear in the segment
+// for every edge, whatever its length.  An empty segment gives j0.
+CELL_HD inline long long cell_rank_in_segment(const int* s_hi, long long j0, long long j1, int hi) {
+  long long at = j0;
+  for (long long j = j0; j < j1; ++j) at += s_hi[j] < hi;
+  return at;
 }
 
 // ---- the edge key of the minimum spanning forest (cellmst.hip): edges are ordered by (d2, lo, hi) with lo < hi the two rows.  The bit

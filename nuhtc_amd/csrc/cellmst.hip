@@ -35,15 +35,15 @@
 //              of cellunion.h holds), best1 / best2 cleared.
 //   order      the canonical edge order without a sort: count the edges per lo (atomics), scan the n counts (exscan_launch, at most
 //              1024 chunks: why n <= 2^24), drop every edge into the segment of its lo in arrival order (the counts go back to zero),
-//              then one thread per edge writes it at start[lo] + the edges of the segment with a smaller hi -- hi is distinct within a
-//              segment.  The output is a pure function of the input; a star of coincident points stays parallel.
+//              then one thread per edge writes it at start[lo] + the edges of the segment with a smaller hi (cell_rank_in_segment of
+//              cellgrid_host.h) -- hi is distinct within a segment.  The output is a pure function of the input; a star of coincident points stays parallel.
 //   number     root flags where comp[row] == row, one scan, tree[i] = rank[comp[i]], T = rank[n - 1] + flag[n - 1].
 //
 // A point outside the stated box raises the binning's flag; every later kernel tests it, no edge is ever emitted, nothing is written to
 // the outputs, and the call returns NUHTC_E_INVALID.
 //
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, profiles/cell_mst_resources.txt), VGPRs / SGPRs: the sweep mst_pick_kernel
-// 30 / 50, mst_init_kernel 18 / 22, mst_place_kernel 16 / 20, mst_relabel_kernel 14 / 18, mst_emit_kernel 10 / 27, the others less; no
+// 30 / 50, mst_init_kernel 18 / 22, mst_place_kernel 14 / 18, mst_relabel_kernel 14 / 18, mst_emit_kernel 10 / 27, the others less; no
 // scratch and no LDS in any of them.  Registers never limit the occupancy (8 waves per SIMD everywhere): the 32-wave cap of a CU does.
 #include <algorithm>
 #include <climits>
@@ -192,8 +192,7 @@ __global__ __launch_bounds__(MST_NT) void mst_place_kernel(CellMstArgs a) {
   if (p >= a.m) return;
   const int lo = a.s_lo[p], hi = a.s_hi[p];
   const int j0 = a.sout[lo], j1 = a.sout[lo + 1];        // lo < hi <= n - 1: entry lo + 1 is inside the n counts
-  int at = j0;
-  for (int j = j0; j < j1; ++j) at += a.s_hi[j] < hi;
+  const int at = (int)cell_rank_in_segment(a.s_hi, j0, j1, hi);
   a.edges[2 * (size_t)at] = lo; a.edges[2 * (size_t)at + 1] = hi;
   a.edge_d2[at] = a.s_d2[p];
 }

@@ -14,7 +14,8 @@
 // grid of side >= r -- the cells the candidate itself was found in.
 //
 // Stages, all on the caller's stream, every one a launch of its own; no kernel waits on another workgroup, and every loop runs over a
-// range of the binning's tables:
+// range of the binning's tables (celledgelist.h holds the frame -- the tables, the clear, the read-back, the order of the launches -- and
+// this file the two sweeps and the body of the place kernel):
 //   binning    cellbin.h, reach r, ONE key per cell; by_class is a compare in the sweep's predicate.
 //   count      degree cleared; then one thread per record i in cell order sweeps its 3 x 3 cells (cell_sweep) for the candidates j with a
 //              LARGER row -- every candidate is tested once, from the record of its smaller row -- and for each one sweeps the same
@@ -30,21 +31,21 @@
 //   emit       the sweep of the count stage again: a candidate among the first 64 of its record reads its kept flags, a later one is
 //              tested again (the test is a pure function of the records, so the two passes agree).  The record writes i into `edges`
 //              and (j, d2 | rng bit) into two temporaries, at its own segment in sweep order -- private to the thread, no atomics.
-//   place      one thread per edge: its place in the segment is the number of edges there with a smaller j (counting, not sorting: the
-//              order inside a cell is atomic arrival order, and j is distinct within a segment), where j, d2 and the RNG byte go.
+//   place      one thread per edge: its place in the segment is the number of edges there with a smaller j (cell_rank_in_segment of
+//              cellgrid_host.h), where j, d2 and the RNG byte go.
 //
 // A point outside the stated box raises the binning's flag; every kernel tests it, nothing is written to the outputs, and the call
 // returns NUHTC_E_INVALID.
 //
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, profiles/cell_proximity_resources.txt), VGPRs / SGPRs: prox_count_kernel 42 / 92,
-// prox_emit_kernel 40 / 88, prox_place_kernel 14 / 22, prox_clear_kernel 3 / 12; no LDS and no scratch in any of them, 8 waves per SIMD
+// prox_emit_kernel 40 / 88, prox_place_kernel 14 / 22, el_clear_kernel 4 / 14; no LDS and no scratch in any of them, 8 waves per SIMD
 // everywhere.  Measured on 500 000 centres at 64 px (profiles/cell_proximity.json, two alternating rounds in one process): the window of
 // the witness loop against all nine cells (-DNUHTC_PROX_DIRECT) 1.63 against 1.63 ms per call on the uniform set and 5.4 - 5.6 against
 // 11.3 ms on the clustered one; the kept flags against testing twice (-DNUHTC_PROX_RETEST) 1.63 against 1.75 and 5.4 - 5.6 against 6.4 - 6.5.
 #include <climits>
 #include <cstring>
 
-#include "cellbin.h"
+#include "celledgelist.h"
 
 namespace {
 
@@ -54,41 +55,24 @@ constexpr int PROX_KEPT = 64;         // candidates per record whose flags the c
 
 struct CellProxArgs {
   CellBin b;                          // the points, the grid and the records in cell order (cellbin.h, one key per cell)
-  int n, r, by_class;
-  long long m;                        // the Gabriel edges, known on the host after the count stage
-  int* count;                         // [fchunk * CB_CHUNK] by row: the Gabriel edges whose smaller row it is; zero past n
-  int* start;                         // [fchunk * CB_CHUNK] by row: the edges in front of its segment
-  unsigned long long* totals;         // [2] m, m_rng
+  EdgeList e;                         // the Gabriel edges (celledgelist.h); totals: one pair, m and m_rng
+  int r, by_class;
   unsigned long long* kept;           // [n][2] by POSITION in cell order: the Gabriel and the RNG flags of the record's first 64 candidates
-  int* s_hi;                          // [m] the larger row of every edge, segment by segment, sweep order inside
-  int* s_d2;                          // [m] its d2 | PROX_RNG_BIT
-  int32_t* edges; int32_t* edge_d2; uint8_t* edge_rng; int32_t* degree;
+  int* s_d2;                          // [m] beside e.s_hi: the edge's d2 | PROX_RNG_BIT
+  int32_t* edge_d2; uint8_t* edge_rng;
 };
 
 #ifdef NUHTC_PROX_DIRECT
 // dev probe (-DNUHTC_PROX_DIRECT), the direct form that was measured first: the witness loop over ALL of the 3 x 3 cells around the
-// record, three rows that are each one contiguous range of records (cell_sweep's, held in registers); a row outside the grid is empty
-struct ProxRows { int j0[3], j1[3]; };
-
-__device__ __forceinline__ ProxRows prox_rows(const CellBin& g, const int4& me) {
-  const int cx = (me.x - g.x_min) / g.side, cy = (me.y - g.y_min) / g.side;
-  const int cx0 = max(cx - 1, 0), cx1 = min(cx + 1, g.ncx - 1);
-  ProxRows w;
-#pragma unroll
-  for (int t = 0; t < 3; ++t) {
-    const int gy = cy - 1 + t;
-    const bool in = gy >= 0 && gy < g.ncy;
-    w.j0[t] = in ? g.cell_start[gy * g.ncx + cx0] : 0;
-    w.j1[t] = in ? g.cell_start[gy * g.ncx + cx1 + 1] : 0;
-  }
-  return w;
-}
+// record, three rows that are each one contiguous range of records (cell_rows of cellbin.h, held in registers)
+using ProxRows = CellRows;
+__device__ __forceinline__ ProxRows prox_rows(const CellBin& g, const int4& me) { return cell_rows(g, me); }
 
 __device__ __forceinline__ int prox_flags(const CellBin& g, const ProxRows& w, const int4& me, const int4& o, int dij, int r, int r2, int by_class) {
   bool gab = true, rng = true;
 #pragma unroll
   for (int t = 0; t < 3; ++t) {
-    for (int k = w.j0[t]; k < w.j1[t] && gab; ++k) {
+    for (int k = w.j0[t]; k < w.j0[t] + w.n[t] && gab; ++k) {
       const int4 c = g.recs[k];
       if (by_class && c.z != me.z) continue;
       const int dik = cell_pair_d2(c.x - me.x, c.y - me.y, r, r2);
@@ -106,20 +90,16 @@ __device__ __forceinline__ ProxRows prox_rows(const CellBin&, const int4&) { ret
 // bit 0: (me, o) at d2 = dij is a Gabriel edge; bit 1: it is an RNG edge as well.  The ends are not told from the witnesses: an end, or a
 // point coincident with one, never blocks (cellgrid_host.h).  dij == 0 skips every witness: coincident points are joined, rng = 1.
 // The witness loop runs over the WINDOW of cells that can hold a blocker, near witnesses first: a blocker is nearer than sqrt(dij) to
-// BOTH ends, so it lies in the overlap of the two boxes of half-width d >= sqrt(dij) around them, inside the 3 x 3 cells around me (at
-// most three rows of at most three cells, each row one contiguous range of records); the row of the pair's midpoint goes first.
+// BOTH ends, so it lies in the overlap of the two boxes of half-width d >= sqrt(dij) around them (cell_pair_window of cellbin.h); the
+// row of the pair's midpoint goes first.
 __device__ __forceinline__ int prox_flags(const CellBin& g, const ProxRows&, const int4& me, const int4& o, int dij, int r, int r2, int by_class) {
-  const int d = (int)sqrtf((float)dij) + 1;              // dij <= 2^28: the float root is off by far less than 1
-  const int xa = max(max(me.x, o.x) - d, g.x_min), xb = min(min(me.x, o.x) + d, g.x_max);
-  const int ya = max(max(me.y, o.y) - d, g.y_min), yb = min(min(me.y, o.y) + d, g.y_max);
-  const int gx0 = (xa - g.x_min) / g.side, gx1 = (xb - g.x_min) / g.side, gy0 = (ya - g.y_min) / g.side, gy1 = (yb - g.y_min) / g.side;
-  const int gm = min(max(((me.y + o.y) / 2 - g.y_min) / g.side, gy0), gy1);
+  const CellWindow v = cell_pair_window(g, me, o, (int)sqrtf((float)dij) + 1);      // dij <= 2^28: the float root is off by far less than 1
   bool gab = true, rng = true;
   for (int t = 0; t < 3 && gab; ++t) {
-    const int gy = t == 0 ? gm : t == 1 ? gm - 1 : gm + 1;
-    if (gy < gy0 || gy > gy1) continue;
-    const int k1 = g.cell_start[gy * g.ncx + gx1 + 1];
-    for (int k = g.cell_start[gy * g.ncx + gx0]; k < k1 && gab; ++k) {
+    const int gy = t == 0 ? v.gm : t == 1 ? v.gm - 1 : v.gm + 1;
+    if (gy < v.gy0 || gy > v.gy1) continue;
+    const int k1 = g.cell_start[gy * g.ncx + v.gx1 + 1];
+    for (int k = g.cell_start[gy * g.ncx + v.gx0]; k < k1 && gab; ++k) {
       const int4 c = g.recs[k];
       if (by_class && c.z != me.z) continue;
       const int dik = cell_pair_d2(c.x - me.x, c.y - me.y, r, r2);
@@ -132,24 +112,12 @@ __device__ __forceinline__ int prox_flags(const CellBin& g, const ProxRows&, con
 }
 #endif
 
-__device__ __forceinline__ unsigned long long prox_wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned long long)__shfl_xor(v, o);
-  return v;
-}
-
-__global__ __launch_bounds__(PROX_NT) void prox_clear_kernel(CellProxArgs a) {
-  if (*a.b.flag) return;                                 // the binning met a point outside the box: nothing is written
-  const int i = blockIdx.x * PROX_NT + threadIdx.x;
-  if (i < 2 * a.n) a.degree[i] = 0;                      // 2 n <= 2^25
-}
-
 __global__ __launch_bounds__(PROX_NT) void prox_count_kernel(CellProxArgs a) {
   const CellBin& g = a.b;
   if (*g.flag) return;                                   // uniform
   const int q = blockIdx.x * PROX_NT + threadIdx.x;
   int cnt = 0, cnt_rng = 0;                              // every lane of a wave takes part in the reduction: no early return
-  if (q < a.n) {
+  if (q < a.e.n) {
     const int4 me = g.recs[q];
     const ProxRows w = prox_rows(g, me);
     const int by_class = a.by_class, r = a.r, r2 = a.r * a.r;
@@ -161,33 +129,33 @@ __global__ __launch_bounds__(PROX_NT) void prox_count_kernel(CellProxArgs a) {
       ++seen;
       if (!(f & 1)) return;
       ++cnt;
-      atomicAdd(a.degree + 2 * o.w, 1);
-      if (f & 2) { ++cnt_rng; atomicAdd(a.degree + 2 * o.w + 1, 1); }
+      atomicAdd(a.e.degree + 2 * o.w, 1);
+      if (f & 2) { ++cnt_rng; atomicAdd(a.e.degree + 2 * o.w + 1, 1); }
     });
-    a.count[me.w] = cnt;
+    a.e.count[me.w] = cnt;
 #ifndef NUHTC_PROX_RETEST
     a.kept[2 * (size_t)q] = keep_g; a.kept[2 * (size_t)q + 1] = keep_r;
 #endif
-    if (cnt) atomicAdd(a.degree + 2 * me.w, cnt);
-    if (cnt_rng) atomicAdd(a.degree + 2 * me.w + 1, cnt_rng);
+    if (cnt) atomicAdd(a.e.degree + 2 * me.w, cnt);
+    if (cnt_rng) atomicAdd(a.e.degree + 2 * me.w + 1, cnt_rng);
   }
-  const unsigned long long m = prox_wave_sum((unsigned long long)cnt), m_rng = prox_wave_sum((unsigned long long)cnt_rng);
+  const long long m = wave_sum((long long)cnt), m_rng = wave_sum((long long)cnt_rng);
   if ((threadIdx.x & 63) == 0) {
-    if (m) atomicAdd(a.totals, m);
-    if (m_rng) atomicAdd(a.totals + 1, m_rng);
+    if (m) atomicAdd(a.e.totals, (unsigned long long)m);
+    if (m_rng) atomicAdd(a.e.totals + 1, (unsigned long long)m_rng);
   }
 }
 
 __global__ __launch_bounds__(PROX_NT) void prox_emit_kernel(CellProxArgs a) {
   const CellBin& g = a.b;
   const int q = blockIdx.x * PROX_NT + threadIdx.x;
-  if (q >= a.n) return;
+  if (q >= a.e.n) return;
   const int4 me = g.recs[q];
-  const int room = a.count[me.w];
+  const int room = a.e.count[me.w];
   if (!room) return;
   const ProxRows w = prox_rows(g, me);
   const int by_class = a.by_class, r = a.r, r2 = a.r * a.r;
-  const long long base = a.start[me.w];
+  const long long base = a.e.start[me.w];
 #ifndef NUHTC_PROX_RETEST
   const unsigned long long keep_g = a.kept[2 * (size_t)q], keep_r = a.kept[2 * (size_t)q + 1];
 #endif
@@ -201,22 +169,21 @@ __global__ __launch_bounds__(PROX_NT) void prox_emit_kernel(CellProxArgs a) {
     ++seen;
     if (!(f & 1) || at >= room) return;                  // at < room always (the two passes agree): no index leaves the segment
     const long long p = base + at++;
-    a.edges[2 * p] = me.w;
-    a.s_hi[p] = o.w;
+    a.e.edges[2 * p] = me.w;
+    a.e.s_hi[p] = o.w;
     a.s_d2[p] = d2 | (f & 2 ? PROX_RNG_BIT : 0);
   });
 }
 
 __global__ __launch_bounds__(PROX_NT) void prox_place_kernel(CellProxArgs a) {
   const long long p = (long long)blockIdx.x * PROX_NT + threadIdx.x;
-  if (p >= a.m) return;
-  const int lo = a.edges[2 * p], hi = a.s_hi[p];
-  if ((unsigned)lo >= (unsigned)a.n) return;             // cannot happen (the emit stage filled every segment): no index leaves the tables
-  const long long j0 = a.start[lo], j1 = j0 + a.count[lo];
-  long long at = j0;
-  for (long long j = j0; j < j1; ++j) at += a.s_hi[j] < hi;
+  if (p >= a.e.m) return;
+  const int lo = a.e.edges[2 * p], hi = a.e.s_hi[p];
+  if ((unsigned)lo >= (unsigned)a.e.n) return;           // cannot happen (the emit stage filled every segment): no index leaves the tables
+  const long long j0 = a.e.start[lo];
+  const long long at = cell_rank_in_segment(a.e.s_hi, j0, j0 + a.e.count[lo], hi);
   const int d2 = a.s_d2[p];
-  a.edges[2 * at + 1] = hi;                              // the even entries of the segment already hold lo, all the same
+  a.e.edges[2 * at + 1] = hi;                            // the even entries of the segment already hold lo, all the same
   a.edge_d2[at] = d2 & (PROX_RNG_BIT - 1);
   a.edge_rng[at] = (uint8_t)((d2 & PROX_RNG_BIT) != 0);
 }
@@ -235,54 +202,28 @@ extern "C" int nuhtc_cell_proximity(int device, const int32_t* points, const int
   hipStream_t s = (hipStream_t)stream;
   CellProxArgs a;
   memset(&a, 0, sizeof(a));
-  a.n = (int)n; a.r = r; a.by_class = by_class;
-  a.edges = edges; a.edge_d2 = edge_d2; a.edge_rng = edge_rng; a.degree = degree;
+  a.e.n = (int)n; a.r = r; a.by_class = by_class;
+  a.e.edges = edges; a.edge_d2 = edge_d2; a.edge_rng = edge_rng; a.e.degree = degree;
   DevScratch tmp;      // every temporary of the call, freed on the way out
   const int nchunk = cellbin_setup(a.b, points, labels, (int)n, x_min, y_min, x_max, y_max, r, PROX_MAX_CELLS, 1, tmp, s);
   if (!nchunk) return NUHTC_E_HIP;
-  const int fchunk = (int)((n + CB_CHUNK - 1) / CB_CHUNK);                 // scan chunks of the n counts: at most 1024
-  const size_t scan_bytes = (size_t)fchunk * CB_CHUNK * sizeof(int);
-  a.count = tmp.alloc<int>(scan_bytes); a.start = tmp.alloc<int>(scan_bytes);
-  const ExScan scan{a.count, a.start, tmp.alloc<int>(1024 * sizeof(int))};
-  a.totals = tmp.alloc<unsigned long long>(2 * sizeof(unsigned long long));
+  EdgeListRun h;
+  if (!edgelist_setup(a.e, h, {"cell_prox_bin", "cell_prox_count", "cell_prox_scan", "cell_prox_emit", "cell_prox_place"}, 1, tmp, s)) return NUHTC_E_HIP;
 #ifndef NUHTC_PROX_RETEST
   a.kept = tmp.alloc<unsigned long long>((size_t)n * 2 * sizeof(unsigned long long));
-#endif
   if (!tmp.ok()) return NUHTC_E_HIP;
-  if (hipMemsetAsync(a.count, 0, scan_bytes, s) != hipSuccess || hipMemsetAsync(a.totals, 0, 2 * sizeof(unsigned long long), s) != hipSuccess)
-    return NUHTC_E_HIP;
+#endif
   const unsigned nb = (unsigned)((n + PROX_NT - 1) / PROX_NT);
-  {
-    ProfScope ps("cell_prox_bin", 0, 0, s);
-    cellbin_launch(a.b, nchunk, s);
-  }
-  {
-    ProfScope ps("cell_prox_count", 0, 0, s);
-    hipLaunchKernelGGL(prox_clear_kernel, dim3((unsigned)((2 * n + PROX_NT - 1) / PROX_NT)), dim3(PROX_NT), 0, s, a);
-    hipLaunchKernelGGL(prox_count_kernel, dim3(nb), dim3(PROX_NT), 0, s, a);
-  }
-  unsigned long long h_tot[2] = {0, 0};
-  if (hipMemcpyAsync(h_tot, a.totals, sizeof(h_tot), hipMemcpyDeviceToHost, s) != hipSuccess) return NUHTC_E_HIP;
-  int rc = cellbin_finish(a.b, s);                       // the flag, and the stream synchronised: the totals are here
+  long long rng = 0;
+  int rc = edgelist_count(a.b, nchunk, a.e, h, [&] { hipLaunchKernelGGL(prox_count_kernel, dim3(nb), dim3(PROX_NT), 0, s, a); }, &rng, s);
   if (rc) return rc;
-  a.m = (long long)h_tot[0];
-  if (a.m > 0 && a.m <= edge_cap) {                      // a.m <= INT_MAX from here on: the int32 scan is safe
-    a.s_hi = tmp.alloc<int>((size_t)a.m * sizeof(int)); a.s_d2 = tmp.alloc<int>((size_t)a.m * sizeof(int));
+  if (a.e.m > 0 && a.e.m <= edge_cap) {
+    a.e.s_hi = tmp.alloc<int>((size_t)a.e.m * sizeof(int)); a.s_d2 = tmp.alloc<int>((size_t)a.e.m * sizeof(int));
     if (!tmp.ok()) return NUHTC_E_HIP;
-    {
-      ProfScope ps("cell_prox_scan", 0, 0, s);
-      exscan_launch(scan, fchunk, s);
-    }
-    {
-      ProfScope ps("cell_prox_emit", 0, 0, s);
-      hipLaunchKernelGGL(prox_emit_kernel, dim3(nb), dim3(PROX_NT), 0, s, a);
-    }
-    {
-      ProfScope ps("cell_prox_place", 0, 0, s);
-      hipLaunchKernelGGL(prox_place_kernel, dim3((unsigned)((a.m + PROX_NT - 1) / PROX_NT)), dim3(PROX_NT), 0, s, a);
-    }
-    if (!launched() || hipStreamSynchronize(s) != hipSuccess) return NUHTC_E_HIP;
+    rc = edgelist_finish(h, [&] { hipLaunchKernelGGL(prox_emit_kernel, dim3(nb), dim3(PROX_NT), 0, s, a); },
+                         [&] { hipLaunchKernelGGL(prox_place_kernel, dim3((unsigned)((a.e.m + PROX_NT - 1) / PROX_NT)), dim3(PROX_NT), 0, s, a); }, s);
+    if (rc) return rc;
   }
-  *m = a.m; *m_rng = (int64_t)h_tot[1];
+  *m = a.e.m; *m_rng = rng;
   return 0;
 }

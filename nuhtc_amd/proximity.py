@@ -57,7 +57,7 @@ def check_args(num_classes, r, by_class):
 
 def first_edge_cap(n):
     """The rows of capacity of `build`'s first call: a planar graph has fewer than 3 n edges, coincident points add to that."""
-    return 4 * int(n) + 64
+    return cellpoints.first_edge_cap(n, 4)
 
 
 def proximity_reference(points, labels, num_classes, r, by_class):
@@ -122,19 +122,9 @@ def build(points, labels, num_classes, radius_px, by_class=0, device=0, with_cal
     check_args(C, r, by_class)
     p, lab, dev, p_d, lab_d, bounds = cellpoints.resident(points, labels, 'proximity', device)
     n = len(p)
-    cap, calls = first_edge_cap(n), 1
-    out = outputs(n, cap, dev)
-    rc, m, m_rng = call(p_d, lab_d, C, r, int(by_class), cap, *out, bounds=bounds, device=device)
-    cellpoints.raise_for(rc, 'nuhtc_cell_proximity')
-    if m > cap:
-        if m >= 1 << 31:
-            raise ValueError(f'proximity: {m} edges, more than 2**31 - 1 (many coincident points)')
-        cap, calls = m, 2
-        out = outputs(n, cap, dev)
-        rc, m, m_rng = call(p_d, lab_d, C, r, int(by_class), cap, *out, bounds=bounds, device=device)
-        cellpoints.raise_for(rc, 'nuhtc_cell_proximity')
-        if m != cap:
-            raise RuntimeError(f'nuhtc_cell_proximity: {m} edges on the second call, {cap} on the first')
+    out, m, (m_rng,), calls = cellpoints.grow_to_fit(
+        lambda cap, out: call(p_d, lab_d, C, r, int(by_class), cap, *out, bounds=bounds, device=device),
+        lambda cap: outputs(n, cap, dev), first_edge_cap(n), 'nuhtc_cell_proximity', 'proximity')
     got = (out[0][:m].cpu().numpy(), out[1][:m].cpu().numpy(), out[2][:m].cpu().numpy(), out[3][:n].cpu().numpy(), m, m_rng)
     return got + (calls,) if with_calls else got
 

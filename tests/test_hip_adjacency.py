@@ -75,6 +75,14 @@ def test_a_row_with_300_neighbours(hip_device, descending, upright):
     assert ref[2][300 if descending else 0] == 300 and ref[3] == 300 and (ref[1] == 2).all()
 
 
+def test_two_rows_of_130_sites_owner_0_with_129_neighbours(hip_device):
+    """Row 0 of the map is all owner 0, row 1 holds the owners 1 .. 129 and then 0: owner 0 is the smaller row of 129 edges, a segment
+    longer than 64 that the gather fills in arrival order over nine tiles and the place stage ranks."""
+    own = np.stack([np.zeros(130, np.int64), np.concatenate([np.arange(1, 130), [0]])])
+    ref = _check(own, 130, '2 x 130')
+    assert int((ref[0][:, 0] == 0).sum()) == 129 and ref[2][0] == 129 and ref[3] == 129 + 128
+
+
 # ---- 4: a full tile table
 @pytest.mark.parametrize('W, H, n, free', [(64, 64, 2000, 0.0), (53, 37, 40, 0.0), (53, 37, 40, 0.25)])
 def test_random_owners_at_every_site(hip_device, W, H, n, free):

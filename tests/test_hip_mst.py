@@ -64,6 +64,16 @@ def test_300_coincident_points_in_one_cell(hip_device):
     assert got[0][:2999].tolist() == [[0, k] for k in range(1, 3000)] and (got[1][:2999] == 0).all() and got[3] == 3004 and got[4] == 1 and (got[2] == 0).all()
 
 
+def test_100_coincident_points_a_segment_of_99_at_row_0(hip_device):
+    """The forest is the star of row 0 (the smallest keys are (0, 0, k)) and the five points around it: 104 edges, 100 of them in the one
+    segment of row 0 (its 99 coincident rows and the nearest of the five), longer than 64, ranked by the place stage."""
+    case = MC.coincident(100)
+    want = mst.mst_reference(*case)
+    assert want[3] == 104 and int((want[0][:, 0] == 0).sum()) == 100 and want[4] == 1
+    got, rounds = _build(case)
+    _equal(got, want, '100 coincident')
+
+
 # ---- 2: the designed sets, as they are and moved to the far corners of the coordinate range
 @pytest.fixture(scope='module')
 def small_references():

@@ -67,6 +67,20 @@ def test_300_coincident_points_in_one_cell(hip_device):
     assert int((got[1] == 0).sum()) == 44850 and (got[2][got[1] == 0] == 1).all() and got[0][:299].tolist() == [[0, k] for k in range(1, 300)]
 
 
+def test_130_coincident_points_a_segment_of_129_through_the_capacity_protocol(hip_device):
+    """Row 0 owns a segment of 129 edges: longer than one wave's ballot and than the 64 kept flags, so the place stage ranks a segment
+    whose tail the emit stage tested again.  First with room for 8 edges (nothing written but degree, m and m_rng), then for exactly m."""
+    p, lab = np.full((130, 2), [40, -12], np.int32), np.zeros(130, np.int32)
+    want = px.proximity_reference(p, lab, 3, 4, 0)
+    m = want[4]
+    assert m == 130 * 129 // 2 and int((want[0][:, 0] == 0).sum()) == 129
+    rc, counts, out = _raw(p, lab, 3, 4, 0, cap=8)
+    assert rc == hip.OK and counts == (m, want[5]) and all((o == 77).all() for o in out[:3]) and np.array_equal(out[3], want[3])
+    rc, counts, out = _raw(p, lab, 3, 4, 0, cap=m)
+    assert rc == hip.OK
+    _equal((out[0], out[1], out[2], out[3]) + counts, want, '130 coincident')
+
+
 # ---- 2: the designed sets, as they are and moved to the far corners of the coordinate range
 @pytest.fixture(scope='module')
 def small_references():

@@ -190,6 +190,43 @@ def test_check_args_accepts_the_limits_and_the_reference_checks_its_points():
     assert px.first_edge_cap(10) == 104
 
 
+def test_the_capacity_protocol_on_a_stub_call():
+    """cellpoints.grow_to_fit, which proximity.build, alphacomplex.build and adjacency.build run, against a call that is not the device."""
+    from nuhtc_amd import cellpoints, hip
+    log = []
+
+    def stub(answers):
+        answers = list(answers)
+
+        def call(cap, out):
+            log.append((cap, out))
+            return answers.pop(0)
+        return call
+
+    make = lambda cap: ['out', cap]
+    run = lambda answers, first_cap: cellpoints.grow_to_fit(stub(answers), make, first_cap, 'nuhtc_stub', 'stub')
+    assert run([(0, 7, 3)], 10) == (['out', 10], 7, (3,), 1) and log == [(10, ['out', 10])]                  # room enough: one call
+    assert run([(0, 10)], 10) == (['out', 10], 10, (), 1)                                                   # exactly enough, and nothing behind m
+    del log[:]
+    assert run([(0, 25, 4), (0, 25, 4)], 10) == (['out', 25], 25, (4,), 2)                                    # too small: ONE more, with room for exactly m
+    assert log == [(10, ['out', 10]), (25, ['out', 25])]
+    with pytest.raises(RuntimeError, match='nuhtc_stub: 26 edges on the second call, 25 on the first'):
+        run([(0, 25, 4), (0, 26, 4)], 10)
+    del log[:]
+    with pytest.raises(ValueError, match=r'stub: 2147483648 edges, more than 2\*\*31 - 1'):
+        run([(0, 1 << 31, 0)], 10)
+    assert len(log) == 1                                                                                     # no second call
+    assert run([(0, (1 << 31) - 1, 0), (0, (1 << 31) - 1, 0)], 10)[1] == (1 << 31) - 1
+    assert cellpoints.grow_to_fit(stub([(0, 1 << 31), (0, 1 << 31)]), make, 10, 'nuhtc_stub', 'stub', limit=None)[1:] == (1 << 31, (), 2)
+    with pytest.raises(ValueError, match='nuhtc_stub: invalid arguments'):
+        run([(hip.E_INVALID, None, None)], 10)
+    with pytest.raises(ValueError, match='nuhtc_stub: invalid arguments'):
+        run([(0, 25, 4), (hip.E_INVALID, None, None)], 10)
+    with pytest.raises(RuntimeError, match='nuhtc_stub failed'):
+        run([(hip.E_HIP, None)], 10)
+    assert cellpoints.first_edge_cap(10) == 104 and cellpoints.first_edge_cap(10, 3) == 94 and cellpoints.first_edge_cap(0) == 64
+
+
 def test_npz_round_trip(tmp_path):
     p, lab, C, r, by = PC.random_small(1)
     e, d2, flag, deg, m, m_rng = px.proximity_reference(p, lab, C, r, by)

@@ -45,58 +45,25 @@ def measure(name, pts, lab, C, r, s, args, also):
     territory = lambda: tr.call(p_d, l_d, C, r, s, win, *terr, bounds=bounds)
     terr_ms = timed(territory, args.repeats, args.warmup)
     owner = terr[0]
-    cap = adj.first_edge_cap(n)
-    out = adj.outputs(n, cap, dev)
-    found = {}
+    first_cap = adj.first_edge_cap(n)
+    cap, out, (_, m) = bp.grown(lambda cap, out: adj.call(owner, n, cap, *out), lambda cap: adj.outputs(n, cap, dev), first_cap)
+    found = dict(m=m)
 
     def shipped():
         rc, found['m'] = adj.call(owner, n, cap, *out)
         return rc
-    if shipped():
-        raise SystemExit('the device call failed')
-    torch.cuda.synchronize()
-    m, first_cap = found['m'], cap
-    if m > cap:                                            # the first guess was too small: the timed calls have room for exactly m
-        cap = m
-        out[:] = adj.outputs(n, cap, dev)
-        if shipped() or found['m'] != m:
-            raise SystemExit('the second device call failed')
-        torch.cuda.synchronize()
-    first = [t.clone() for t in out]
-    repeat = True
-
-    def checked():
-        nonlocal repeat
-        rc = shipped()
-        torch.cuda.synchronize()
-        repeat = repeat and found['m'] == m and all(torch.equal(a, b) for a, b in zip(out, first))
-        return rc
+    first, checked, repeated = bp.repeating(shipped, out, lambda: found['m'])
     for _ in range(3):
         checked()
     ms = timed(shipped, args.repeats, args.warmup)
     checked()
     stages = bp.stage_split(shipped, 'cell_adjacency')
-    variants = {}
-    if also:
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        calls = {'shipped': shipped}
-        for label, fn in also.items():
-            vout, vm = adj.outputs(n, cap, dev), ctypes.c_int64(-1)
-            call = lambda fn=fn, vout=vout, vm=vm: fn(0, vp(owner), win[2], win[3], n, cap, *(vp(t) for t in vout), ctypes.byref(vm), stream)
-            if call():
-                raise SystemExit(f'{label}: the device call failed')
-            torch.cuda.synchronize()
-            variants[label] = dict(equals_shipped=bool(vm.value == m and all(torch.equal(a, b) for a, b in zip(vout, first))))
-            calls[label] = call
-        variants['shipped'] = {}
-        rounds = {label: [] for label in calls}
-        for _ in range(args.rounds):
-            for label, call in calls.items():
-                rounds[label].append(round(med(timed(call, args.repeats, 1)), 3))
-        for label, v in rounds.items():
-            variants[label]['ms'] = v
-        del calls
+    vp, stream = bp.raw(dev)
+    held = {label: (adj.outputs(n, cap, dev), ctypes.c_int64(-1)) for label in also}
+    others = {label: (lambda fn=fn, vout=held[label][0], vm=held[label][1]: fn(0, vp(owner), win[2], win[3], n, cap, *(vp(t) for t in vout), ctypes.byref(vm), stream))
+              for label, fn in also.items()}
+    variants = bp.variants(shipped, others, lambda label: held[label][1].value == m and bp.tensors_equal(held[label][0], first), args)
+    del others, held
     e2e, built = bp.end_to_end(lambda: adj.build(pts, lab, C, r / 2, s / 2))
     got = [t.cpu().numpy() for t in first]
     same = bool(built[2] == win and np.array_equal(built[0][0], got[0][:m]) and np.array_equal(built[0][1], got[1][:m]) and np.array_equal(built[0][2], got[2]))
@@ -119,7 +86,7 @@ def measure(name, pts, lab, C, r, s, args, also):
     return dict(points=name, n=n, pitch_px=s / 2, window=list(win), sites=int(win[2] * win[3]), edges=int(m), edge_cap=int(cap), first_edge_cap=int(first_cap),
                 nuclei_with_neighbours=int((degree > 0).sum()), degree_max=int(degree.max()), closed=int(closed.sum()),
                 closed_degree_mean=round(float(degree[closed].mean()), 3) if closed.any() else 0.0, shared_sum=int(got[1][:m].sum()),
-                **bp.device_columns(ms, stages, e2e, same), device_calls_repeat=repeat, contact_agrees=agrees,
+                **bp.device_columns(ms, stages, e2e, same), device_calls_repeat=repeated(), contact_agrees=agrees,
                 territory_ms=[round(v, 3) for v in terr_ms], territory_ms_median=round(med(terr_ms), 3),
                 device_over_territory=round(med(ms) / med(terr_ms), 2), variants=variants, checked_sites=int(sub[2] * sub[3]),
                 checked_edges=int(ref[3]), checked_against_reference=exact)
@@ -130,8 +97,7 @@ def main(argv=None):
     ap.add_argument('--reach', type=float, default=64.0, help='px')
     ap.add_argument('--pitch', type=float, default=4.0, help='px')
     ap.add_argument('--coarse-pitch', type=float, default=32.0, dest='coarse_pitch', help='px; 0: the --pitch alone')
-    ap.add_argument('--also', action='append', default=[], metavar='LABEL=LIB', help='another build of the library to time in alternating rounds')
-    ap.add_argument('--rounds', type=int, default=2, help='alternating rounds of the shipped library and the --also builds')
+    bp.also_arguments(ap)
     args = ap.parse_args(argv)
     from nuhtc_amd import adjacency as adj
     bp.need_gpu('bench_adjacency.py')
@@ -148,8 +114,7 @@ def main(argv=None):
                      f'window; variants: median ms of {args.repeats} calls per round, {args.rounds} alternating rounds',
                 n=args.n, extent_px=args.extent, reach_px=args.reach, classes=C, sets=sets,
                 not_measured=['a whole slide with --nuclei-adjacency', '--gpus N', 'a window near 2**28 sites', 'a host Delaunay triangulation beside it'])
-    same = [v.get('equals_shipped', True) for s_ in sets for v in s_['variants'].values()]
-    bp.report(line, ('device_calls_agree', 'device_calls_repeat', 'contact_agrees', 'checked_against_reference'), (('equals_shipped', all(same)),))
+    bp.report(line, ('device_calls_agree', 'device_calls_repeat', 'contact_agrees', 'checked_against_reference'), (('equals_shipped', bp.all_equal_shipped(sets)),))
 
 
 if __name__ == '__main__':

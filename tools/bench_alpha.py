@@ -8,8 +8,9 @@ prints ONE JSON line (profiles/cell_alpha.json).
 Synthetic nucleus centres from the generator of tools/bench_points.py: `--n` points uniform on a square of `--extent` px, and one CLUSTERED
 set of the same size (400 Gaussian clumps, sigma 300 px).  For each set and each radius r of `--radii` (px):
   device_ms            nuhtc_cell_alpha alone, between two events, points and outputs resident on the device and room for 4 n + 64 edges
-                       (every stage, its own scratch allocation, the counts read back and the final synchronisation included: it is one
-                       blocking call), `--repeats` after `--warmup`
+                       or, when there are more, for exactly that many (every stage, its own scratch allocation, the counts read back and
+                       the final synchronisation included: it is one blocking call), `--repeats` after `--warmup`; the calls around the
+                       timed ones are compared bitwise with the first (device_calls_repeat)
   m, m_gabriel         the edges and how many of them are Gabriel edges; interior / outline / singular: the edges by their apexes
   device_stage_ms      one further call under the library's per-kernel profile: the cell_alpha_* stages
   device_end_to_end_ms alphacomplex.build from numpy to numpy: bounding box, upload, the call(s), download (wall clock)
@@ -72,15 +73,14 @@ def scipy_filter(pts, tri, r):
 
 
 def measure(name, pts, lab, C, radius_px, args, also, tri):
-    import torch
     from nuhtc_amd import alphacomplex as ax
     from nuhtc_amd import proximity as px
     n, by, r = len(pts), ax.BY[args.by], ax.half_pixel_radius(radius_px)
     dev, bounds, p_d, l_d = bp.resident(pts, lab)
-    cap = ax.first_edge_cap(n)
-    out = ax.outputs(n, cap, dev)
+    cap, out, (_, m, m_gab) = bp.grown(lambda cap, out: ax.call(p_d, l_d, C, r, by, cap, *out, bounds=bounds), lambda cap: ax.outputs(n, cap, dev),
+                                       ax.first_edge_cap(n))
     pout = px.outputs(n, cap, dev)
-    found, pfound = {}, {}
+    found, pfound = dict(m=m, m_gab=m_gab), {}
 
     def alpha_call():
         rc, found['m'], found['m_gab'] = ax.call(p_d, l_d, C, r, by, cap, *out, bounds=bounds)
@@ -91,46 +91,33 @@ def measure(name, pts, lab, C, radius_px, args, also, tri):
         return rc
 
     timed = lambda fn, warmup=args.warmup: bp.timed(fn, args.repeats, warmup)
+    first, checked, repeated = bp.repeating(alpha_call, out, lambda: (found['m'], found['m_gab']))
+    checked()
     ms = timed(alpha_call)
-    m = found['m']
-    if m > cap:
-        raise SystemExit(f'{m} edges, more than the {cap} the benchmark has room for')
-    dev_out = [t[:m].cpu().numpy() for t in out[:4]] + [out[4].cpu().numpy()]
+    checked()
+    dev_out = [t[:m].cpu().numpy() for t in first[:4]] + [first[4].cpu().numpy()]
     pms = timed(prox_call)
     gabriel = dev_out[3] == 1
-    same_gabriel = bool(pfound['m'] == found['m_gab'] and np.array_equal(dev_out[0][gabriel], pout[0][:pfound['m']].cpu().numpy()))
+    same_gabriel = bool(pfound['m'] == m_gab and np.array_equal(dev_out[0][gabriel], pout[0][:pfound['m']].cpu().numpy()))
     gms = bp.graph_yardstick(p_d, l_d, C, 2 * r, bounds, args)
     stages = bp.stage_split(alpha_call, 'cell_alpha')
-    variants = {}
-    if also:
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        calls = {'shipped': alpha_call}
-        for label, fn in also.items():
-            vout = ax.outputs(n, cap, dev)
-            vm, vg = ctypes.c_int64(-1), ctypes.c_int64(-1)
-            call = (lambda fn=fn, vout=vout, vm=vm, vg=vg: fn(0, vp(p_d), vp(l_d), n, C, r, by, cap, *bounds, *(vp(t) for t in vout),
-                                                              ctypes.byref(vm), ctypes.byref(vg), stream))
-            if call():
-                raise SystemExit(f'{label}: the device call failed')
-            same = bool(vm.value == m and vg.value == found['m_gab'] and all(np.array_equal(a[:m].cpu().numpy() if k < 4 else a.cpu().numpy(), b)
-                                                                          for k, (a, b) in enumerate(zip(vout, dev_out))))
-            variants[label] = dict(equals_shipped=same, ms=[])
-            calls[label] = call
-        variants['shipped'] = dict(ms=[])
-        for _ in range(args.rounds):
-            for label, call in calls.items():
-                variants[label]['ms'].append(round(med(timed(call, warmup=1)), 3))
+    vp, stream = bp.raw(dev)
+    held = {label: (ax.outputs(n, cap, dev), ctypes.c_int64(-1), ctypes.c_int64(-1)) for label in also}
+    others = {label: (lambda fn=fn, vout=held[label][0], vm=held[label][1], vg=held[label][2]:
+                      fn(0, vp(p_d), vp(l_d), n, C, r, by, cap, *bounds, *(vp(t) for t in vout), ctypes.byref(vm), ctypes.byref(vg), stream))
+              for label, fn in also.items()}
+    equals = lambda label: (held[label][1].value, held[label][2].value) == (m, m_gab) and bp.tensors_equal(held[label][0], first)
+    variants = bp.variants(alpha_call, others, equals, args)
     e2e, got = bp.end_to_end(lambda: ax.build(pts, lab, C, r / 2, by))
-    same = bool(all(np.array_equal(a, b) for a, b in zip(got[:5], dev_out)) and got[5:] == (m, found['m_gab']))
+    same = bool(all(np.array_equal(a, b) for a, b in zip(got[:5], dev_out)) and got[5:] == (m, m_gab))
     win = bp.brute_window(pts, bounds, args.extent, args.check_n)
     sub, ref = ax.build(pts[win], lab[win], C, r / 2, by), ax.alpha_reference(pts[win], lab[win], C, r, by)
     exact = bool(all(np.array_equal(a, b) for a, b in zip(sub[:5], ref[:5])) and sub[5:] == ref[5:])
     kind = (dev_out[2] >= 0).sum(1)
     d = ax.derive(*dev_out, pts, lab, C, r)
-    line = dict(points=name, radius_px=radius_px, n=n, m=int(m), m_gabriel=int(found['m_gab']), interior=int((kind == 2).sum()), outline=int((kind == 1).sum()),
+    line = dict(points=name, radius_px=radius_px, n=n, m=int(m), m_gabriel=int(m_gab), interior=int((kind == 2).sum()), outline=int((kind == 1).sum()),
                 singular=int((kind == 0).sum()), triangles=int(d['n_triangles']), degenerate=int(d['n_degenerate']), mean_degree=round(2 * m / n, 3),
-                **bp.device_columns(ms, stages, e2e, same), **bp.graph_columns(gms, ms),
+                **bp.device_columns(ms, stages, e2e, same), device_calls_repeat=repeated(), **bp.graph_columns(gms, ms),
                 proximity_ms=[round(v, 3) for v in pms], proximity_ms_median=round(med(pms), 3), device_over_proximity=round(med(ms) / med(pms), 2),
                 gabriel_equals_proximity=same_gabriel, variants=variants, checked_points=int(win.sum()), checked_against_reference=exact)
     if tri is None:
@@ -169,8 +156,7 @@ def main(argv=None):
     ap = bp.parser()
     ap.add_argument('--radii', type=float, nargs='+', default=[32.0, 64.0], help='px')
     ap.add_argument('--by', choices=('any', 'class'), default='any')
-    ap.add_argument('--also', action='append', default=[], metavar='LABEL=LIB', help='another build of the library to time in alternating rounds')
-    ap.add_argument('--rounds', type=int, default=2, help='alternating rounds of the shipped library and the --also builds')
+    bp.also_arguments(ap)
     args = ap.parse_args(argv)
     from nuhtc_amd import alphacomplex as ax
     bp.need_gpu('bench_alpha.py')
@@ -192,8 +178,8 @@ def main(argv=None):
                      f'nuhtc_cell_graph k 8 at radius 2 r; host: scipy.spatial.Delaunay + the circumradius filter in float64; variants: median ms of '
                      f'{args.repeats} calls per round, {args.rounds} alternating rounds',
                 n=args.n, extent_px=args.extent, radii_px=args.radii, by=args.by, classes=C, sets=sets)
-    bp.report(line, ('device_calls_agree', 'checked_against_reference', 'gabriel_equals_proximity', 'scipy_edge_counts_agree', 'scipy_difference_explained'),
-              (('equals_shipped', all(v.get('equals_shipped', True) for s in sets for v in s['variants'].values())),))
+    bp.report(line, ('device_calls_agree', 'device_calls_repeat', 'checked_against_reference', 'gabriel_equals_proximity', 'scipy_edge_counts_agree', 'scipy_difference_explained'),
+              (('equals_shipped', bp.all_equal_shipped(sets)),))
 
 
 if __name__ == '__main__':

@@ -22,7 +22,6 @@ set of the same size (400 Gaussian clumps, sigma 300 px), at the defaults of too
 With --more-shapes the shipped and the --also builds are timed at further (bandwidth, pitch) pairs on the uniform set: where the rule that
 picks the kernel (dens_route_staged of csrc/cellgrid_host.h) has to hold.  bench.py is the project's headline benchmark and is not changed
 by this tool."""
-import ctypes
 import os
 import sys
 import time
@@ -58,23 +57,13 @@ def host_route(pts, lab, C, h, s, win):
 
 def variant_calls(also, p_d, l_d, n, C, h, s, win, bounds, dev):
     """-> {label: (call, outputs)} for the --also builds on the resident points."""
-    import torch
     from nuhtc_amd import density as dn
-    vp = lambda t: ctypes.c_void_p(t.data_ptr())
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    vp, stream = bp.raw(dev)
     calls = {}
     for label, fn in also.items():
         vout = dn.outputs(C, win, dev)
         calls[label] = ((lambda fn=fn, vout=vout: fn(0, vp(p_d), vp(l_d), n, C, h, s, *win, *bounds, vp(vout[0]), vp(vout[1]), stream)), vout)
     return calls
-
-
-def rounds_of(calls, args):
-    out = {label: [] for label in calls}
-    for _ in range(args.rounds):
-        for label, call in calls.items():
-            out[label].append(round(med(timed(call, args.repeats, 1)), 3))
-    return out
 
 
 def measure(name, pts, lab, C, h, s, args, also):
@@ -88,18 +77,9 @@ def measure(name, pts, lab, C, h, s, args, also):
     ms = timed(shipped, args.repeats, args.warmup)
     count, weight = out[0].cpu().numpy(), out[1].cpu().numpy()
     stages = bp.stage_split(shipped, 'cell_density')
-    variants = {}
-    if also:
-        calls = {'shipped': shipped}
-        for label, (call, vout) in variant_calls(also, p_d, l_d, n, C, h, s, win, bounds, dev).items():
-            if call():
-                raise SystemExit(f'{label}: the device call failed')
-            torch.cuda.synchronize()
-            variants[label] = dict(equals_shipped=bool(np.array_equal(vout[0].cpu().numpy(), count) and np.array_equal(vout[1].cpu().numpy(), weight)))
-            calls[label] = call
-        variants['shipped'] = {}
-        for label, v in rounds_of(calls, args).items():
-            variants[label]['ms'] = v
+    held = variant_calls(also, p_d, l_d, n, C, h, s, win, bounds, dev)
+    variants = bp.variants(shipped, {label: call for label, (call, _) in held.items()}, lambda label: bp.tensors_equal(held[label][1], out), args)
+    del held
     e2e, got = bp.end_to_end(lambda: dn.build(pts, lab, C, h / 2, s / 2))
     same = bool(np.array_equal(got[0], count) and np.array_equal(got[1], weight) and got[2] == win)
     # ---- a sub-window small enough for brute force, through the device again and against the definition
@@ -142,7 +122,7 @@ def more_shapes(pts, lab, C, args, also):
             torch.cuda.synchronize()
             same[label] = bool(torch.equal(vout[0], out[0]) and torch.equal(vout[1], out[1]))
             calls[label] = call
-        rows.append(dict(bandwidth_px=bw, pitch_px=pitch, sites=int(win[2] * win[3]), shipped_kernel=took, ms=rounds_of(calls, args), equals_shipped=same))
+        rows.append(dict(bandwidth_px=bw, pitch_px=pitch, sites=int(win[2] * win[3]), shipped_kernel=took, ms=bp.alternating_rounds(calls, args.repeats, args.rounds), equals_shipped=same))
         del out
     return rows
 
@@ -151,8 +131,7 @@ def main(argv=None):
     ap = bp.parser(n=1000000, extent=50000, check_n=False)
     ap.add_argument('--bandwidth', type=float, default=128.0, help='px')
     ap.add_argument('--pitch', type=float, default=64.0, help='px')
-    ap.add_argument('--also', action='append', default=[], metavar='LABEL=LIB', help='another build of the library to time in alternating rounds')
-    ap.add_argument('--rounds', type=int, default=2, help='alternating rounds of the shipped library and the --also builds')
+    bp.also_arguments(ap)
     ap.add_argument('--more-shapes', action='store_true', dest='more_shapes', help='time further (bandwidth, pitch) pairs on the uniform set')
     args = ap.parse_args(argv)
     from nuhtc_amd import density as dn

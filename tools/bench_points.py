@@ -1,6 +1,7 @@
 """What the bench tools of the per-slide point analyses (bench_cellgraph, bench_spatial, bench_clusters, bench_mst, bench_proximity,
 bench_density, bench_territory, bench_adjacency, bench_alpha, bench_enrichment, bench_regions, bench_margin) do in the same way: the synthetic point sets, the shared arguments, the event-timed loop, the stage split under the
-library's profile, the wall-clock end-to-end loop, the window small enough for brute force, the cell-graph yardstick and the one JSON line.
+library's profile, the wall-clock end-to-end loop, the window small enough for brute force, the cell-graph yardstick, the capacity protocol of
+the edge-list calls with the check that every call repeats the first, the --also builds in alternating rounds and the one JSON line.
 A helper, not a tool: each tool keeps its call, its summary columns and its host comparison."""
 import argparse
 import json
@@ -130,6 +131,89 @@ def also_builds(specs, entry):
         fn.argtypes, fn.restype = shipped.argtypes, shipped.restype
         also[label] = fn
     return also
+
+
+def also_arguments(ap):
+    ap.add_argument('--also', action='append', default=[], metavar='LABEL=LIB', help='another build of the library to time in alternating rounds')
+    ap.add_argument('--rounds', type=int, default=2, help='alternating rounds of the shipped library and the --also builds')
+
+
+def raw(dev):
+    """-> (vp, stream): a tensor as the void pointer, and the device's current stream, for a call into an --also build."""
+    import ctypes
+    import torch
+    return (lambda t: ctypes.c_void_p(t.data_ptr())), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def alternating_rounds(calls, repeats, rounds):
+    """{label: call} -> {label: [median ms of `repeats` calls after one warm-up call, per round]}, the labels taking turns in every round."""
+    out = {label: [] for label in calls}
+    for _ in range(rounds):
+        for label, call in calls.items():
+            out[label].append(round(med(timed(call, repeats, 1)), 3))
+    return out
+
+
+def variants(shipped, others, equals, args):
+    """The --also builds beside the shipped one: others = {label: call}, each called once and compared (equals(label) -> whether its outputs
+    are the shipped ones), then `--rounds` alternating rounds of all of them -> {label: dict(equals_shipped, ms), 'shipped': dict(ms)}, or
+    {} without --also."""
+    import torch
+    if not others:
+        return {}
+    out, calls = {}, {'shipped': shipped}
+    for label, call in others.items():
+        if call():
+            raise SystemExit(f'{label}: the device call failed')
+        torch.cuda.synchronize()
+        out[label] = dict(equals_shipped=bool(equals(label)))
+        calls[label] = call
+    out['shipped'] = {}
+    for label, ms in alternating_rounds(calls, args.repeats, args.rounds).items():
+        out[label]['ms'] = ms
+    return out
+
+
+def tensors_equal(a, b):
+    """Two lists of output tensors made with the same shapes and fill: bitwise the same (the rows no call writes included)."""
+    import torch
+    return all(torch.equal(x, y) for x, y in zip(a, b))
+
+
+def all_equal_shipped(sets):
+    return all(v.get('equals_shipped', True) for s in sets for v in s['variants'].values())
+
+
+def grown(call, make_outputs, first_cap):
+    """The capacity protocol of an edge-list call, for a tool: call(cap, out) -> (rc, m, ...) at first_cap, and when m > cap once more with
+    room for exactly m -> (cap, out, what the last call returned)."""
+    import torch
+    cap, out = first_cap, make_outputs(first_cap)
+    got = call(cap, out)
+    if got[0]:
+        raise SystemExit('the device call failed')
+    torch.cuda.synchronize()
+    if got[1] > cap:                                          # the first guess was too small: the timed calls have room for exactly m
+        cap, out, m = got[1], make_outputs(got[1]), got[1]
+        got = call(cap, out)
+        if got[0] or got[1] != m:
+            raise SystemExit('the second device call failed')
+        torch.cuda.synchronize()
+    return cap, out, got
+
+
+def repeating(shipped, out, result):
+    """Clones `out` as the FIRST result -> (first, checked, repeated): checked() is shipped() followed by a bitwise compare of `out` and
+    result() with the first; repeated() says whether every checked call so far repeated it."""
+    import torch
+    first, first_result, ok = [t.clone() for t in out], result(), [True]
+
+    def checked():
+        rc = shipped()
+        torch.cuda.synchronize()
+        ok[0] = ok[0] and result() == first_result and tensors_equal(out, first)
+        return rc
+    return first, checked, lambda: ok[0]
 
 
 def report(line, checks, more=()):

@@ -8,8 +8,9 @@ JSON line (profiles/cell_proximity.json).
 Synthetic nucleus centres from the generator of tools/bench_points.py: `--n` points uniform on a square of `--extent` px, and one CLUSTERED
 set of the same size (400 Gaussian clumps, sigma 300 px).  For each set:
   device_ms            nuhtc_cell_proximity alone, between two events, points and outputs resident on the device and room for 4 n + 64 edges
-                       (every stage, its own scratch allocation, the counts read back and the final synchronisation included: it is one
-                       blocking call), `--repeats` after `--warmup`
+                       or, when there are more, for exactly that many (every stage, its own scratch allocation, the counts read back and
+                       the final synchronisation included: it is one blocking call), `--repeats` after `--warmup`; the calls around the
+                       timed ones are compared bitwise with the first (device_calls_repeat)
   m, m_rng             the Gabriel edges and how many of them are RNG edges
   device_stage_ms      one further call under the library's per-kernel profile: the cell_prox_* stages
   device_end_to_end_ms proximity.build from numpy to numpy: bounding box, upload, the call(s), download (wall clock)
@@ -73,26 +74,25 @@ def scipy_route(pts, lab, r, by):
 
 
 def measure(name, pts, lab, C, r, args, also):
-    import torch
     from nuhtc_amd import mst
     from nuhtc_amd import proximity as px
     n, by = len(pts), px.BY[args.by]
     dev, bounds, p_d, l_d = bp.resident(pts, lab)
-    cap = px.first_edge_cap(n)
-    out = px.outputs(n, cap, dev)
     mout = mst.outputs(n, dev)
-    found = {}
+    cap, out, (_, m, m_rng) = bp.grown(lambda cap, out: px.call(p_d, l_d, C, r, by, cap, *out, bounds=bounds), lambda cap: px.outputs(n, cap, dev),
+                                       px.first_edge_cap(n))
+    found = dict(m=m, m_rng=m_rng)
 
     def prox_call():
         rc, found['m'], found['m_rng'] = px.call(p_d, l_d, C, r, by, cap, *out, bounds=bounds)
         return rc
 
+    first, checked, repeated = bp.repeating(prox_call, out, lambda: (found['m'], found['m_rng']))
     timed = lambda fn, warmup=args.warmup: bp.timed(fn, args.repeats, warmup)
+    checked()
     ms = timed(prox_call)
-    m = found['m']
-    if m > cap:
-        raise SystemExit(f'{m} edges, more than the {cap} the benchmark has room for')
-    dev_out = [out[0][:m].cpu().numpy(), out[1][:m].cpu().numpy(), out[2][:m].cpu().numpy(), out[3].cpu().numpy()]
+    checked()
+    dev_out = [first[0][:m].cpu().numpy(), first[1][:m].cpu().numpy(), first[2][:m].cpu().numpy(), first[3].cpu().numpy()]
     gms = bp.graph_yardstick(p_d, l_d, C, r, bounds, args)
     mfound = {}
 
@@ -105,35 +105,22 @@ def measure(name, pts, lab, C, r, args, also):
     inside = bool(np.isin(code(forest), code(dev_out[0][dev_out[2] == 1])).all())
     stages = bp.stage_split(prox_call, 'cell_prox')
     # ---- other builds of the library, alternating with the shipped one in this process
-    variants = {}
-    if also:
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        calls = {'shipped': prox_call}
-        for label, fn in also.items():
-            vout = px.outputs(n, cap, dev)
-            vm, vr = ctypes.c_int64(-1), ctypes.c_int64(-1)
-            call = (lambda fn=fn, vout=vout, vm=vm, vr=vr: fn(0, vp(p_d), vp(l_d), n, C, r, by, cap, *bounds, *(vp(t) for t in vout),
-                                                              ctypes.byref(vm), ctypes.byref(vr), stream))
-            if call():
-                raise SystemExit(f'{label}: the device call failed')
-            same = bool(vm.value == m and vr.value == found['m_rng'] and all(np.array_equal(a[:m].cpu().numpy() if a.shape[0] == cap else a.cpu().numpy(), b)
-                                                                          for a, b in zip(vout, dev_out)))
-            variants[label] = dict(equals_shipped=same, ms=[])
-            calls[label] = call
-        variants['shipped'] = dict(ms=[])
-        for _ in range(args.rounds):
-            for label, call in calls.items():
-                variants[label]['ms'].append(round(med(timed(call, warmup=1)), 3))
+    vp, stream = bp.raw(dev)
+    held = {label: (px.outputs(n, cap, dev), ctypes.c_int64(-1), ctypes.c_int64(-1)) for label in also}
+    others = {label: (lambda fn=fn, vout=held[label][0], vm=held[label][1], vr=held[label][2]:
+                      fn(0, vp(p_d), vp(l_d), n, C, r, by, cap, *bounds, *(vp(t) for t in vout), ctypes.byref(vm), ctypes.byref(vr), stream))
+              for label, fn in also.items()}
+    equals = lambda label: (held[label][1].value, held[label][2].value) == (m, m_rng) and bp.tensors_equal(held[label][0], first)
+    variants = bp.variants(prox_call, others, equals, args)
     e2e, got = bp.end_to_end(lambda: px.build(pts, lab, C, r / 2, by))
-    same = bool(all(np.array_equal(a, b) for a, b in zip(got[:4], dev_out)) and got[4:] == (m, found['m_rng']))
+    same = bool(all(np.array_equal(a, b) for a, b in zip(got[:4], dev_out)) and got[4:] == (m, m_rng))
     # ---- a window small enough for brute force, through the device again and against the definition
     win = bp.brute_window(pts, bounds, args.extent, args.check_n)
     sub, ref = px.build(pts[win], lab[win], C, r / 2, by), px.proximity_reference(pts[win], lab[win], C, r, by)
     exact = bool(all(np.array_equal(a, b) for a, b in zip(sub[:4], ref[:4])) and sub[4:] == ref[4:])
-    line = dict(points=name, n=n, m=int(m), m_rng=int(found['m_rng']), mean_gabriel_degree=round(2 * m / n, 3), mean_rng_degree=round(2 * found['m_rng'] / n, 3),
+    line = dict(points=name, n=n, m=int(m), m_rng=int(m_rng), mean_gabriel_degree=round(2 * m / n, 3), mean_rng_degree=round(2 * m_rng / n, 3),
                 mean_edge_px=round(float(np.sqrt(dev_out[1].astype(np.float64)).mean() / 2), 3) if m else 0.0,
-                **bp.device_columns(ms, stages, e2e, same), **bp.graph_columns(gms, ms),
+                **bp.device_columns(ms, stages, e2e, same), device_calls_repeat=repeated(), **bp.graph_columns(gms, ms),
                 mst_ms=[round(v, 3) for v in mms], mst_ms_median=round(med(mms), 3), device_over_mst=round(med(ms) / med(mms), 2),
                 forest_edges=int(mfound['m']), forest_inside_rng=inside, variants=variants,
                 checked_points=int(win.sum()), checked_against_reference=exact)
@@ -155,8 +142,7 @@ def main(argv=None):
     ap = bp.parser()
     ap.add_argument('--radius', type=float, default=64.0, help='px')
     ap.add_argument('--by', choices=('any', 'class'), default='any')
-    ap.add_argument('--also', action='append', default=[], metavar='LABEL=LIB', help='another build of the library to time in alternating rounds')
-    ap.add_argument('--rounds', type=int, default=2, help='alternating rounds of the shipped library and the --also builds')
+    bp.also_arguments(ap)
     args = ap.parse_args(argv)
     from nuhtc_amd import proximity as px
     bp.need_gpu('bench_proximity.py')
@@ -169,8 +155,8 @@ def main(argv=None):
                      f'yardsticks: nuhtc_cell_graph k 8 and nuhtc_cell_mst at the same radius; host: scipy cKDTree.query_pairs + the two tests in numpy; '
                      f'variants: median ms of {args.repeats} calls per round, {args.rounds} alternating rounds',
                 n=args.n, extent_px=args.extent, radius_px=args.radius, by=args.by, classes=C, sets=sets)
-    bp.report(line, ('device_calls_agree', 'checked_against_reference', 'forest_inside_rng', 'scipy_edge_sets_agree'),
-              (('equals_shipped', all(v.get('equals_shipped', True) for s in sets for v in s['variants'].values())),))
+    bp.report(line, ('device_calls_agree', 'device_calls_repeat', 'checked_against_reference', 'forest_inside_rng', 'scipy_edge_sets_agree'),
+              (('equals_shipped', bp.all_equal_shipped(sets)),))
 
 
 if __name__ == '__main__':

@@ -24,7 +24,6 @@ set of the same size, at the defaults of tools/infer_wsi.py --nuclei-territory a
   checked_against_reference  a sub-window small enough for brute force, through the device again, against territory_reference on the
                        points within reach of it: every output
 bench.py is the project's headline benchmark and is not changed by this tool."""
-import ctypes
 import os
 import sys
 import time
@@ -72,10 +71,8 @@ def host_route(pts, lab, C, r, s, win, owner, nearest):
 
 def variant_calls(also, p_d, l_d, n, C, r, s, win, bounds, dev):
     """-> {label: (call, outputs)} for the --also builds on the resident points."""
-    import torch
     from nuhtc_amd import territory as tr
-    vp = lambda t: ctypes.c_void_p(t.data_ptr())
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    vp, stream = bp.raw(dev)
     calls = {}
     for label, fn in also.items():
         vout = tr.outputs(n, C, win, dev)
@@ -108,23 +105,9 @@ def measure(name, pts, lab, C, r, s, args, also):
     ms = timed(shipped, args.repeats, args.warmup)
     got = [t.cpu().numpy() for t in out]
     stages = bp.stage_split(shipped, 'cell_territory')
-    variants = {}
-    if also:
-        calls = {'shipped': shipped}
-        for label, (call, vout) in variant_calls(also, p_d, l_d, n, C, r, s, win, bounds, dev).items():
-            if call():
-                raise SystemExit(f'{label}: the device call failed')
-            torch.cuda.synchronize()
-            variants[label] = dict(equals_shipped=bool(all(torch.equal(a, b) for a, b in zip(vout, out))))
-            calls[label] = call
-        variants['shipped'] = {}
-        rounds = {label: [] for label in calls}
-        for _ in range(args.rounds):
-            for label, call in calls.items():
-                rounds[label].append(round(med(timed(call, args.repeats, 1)), 3))
-        for label, v in rounds.items():
-            variants[label]['ms'] = v
-        del calls
+    held = variant_calls(also, p_d, l_d, n, C, r, s, win, bounds, dev)
+    variants = bp.variants(shipped, {label: call for label, (call, _) in held.items()}, lambda label: bp.tensors_equal(held[label][1], out), args)
+    del held
     dens = density_yardstick(p_d, l_d, C, r, s, bounds, args)
     e2e, built = bp.end_to_end(lambda: tr.build(pts, lab, C, r / 2, s / 2))
     e2e_maps, built_maps = bp.end_to_end(lambda: tr.build(pts, lab, C, r / 2, s / 2, maps=True))
@@ -162,8 +145,7 @@ def main(argv=None):
     ap.add_argument('--reach', type=float, default=64.0, help='px')
     ap.add_argument('--pitch', type=float, default=4.0, help='px')
     ap.add_argument('--coarse-pitch', type=float, default=32.0, dest='coarse_pitch', help='px; 0: the --pitch alone')
-    ap.add_argument('--also', action='append', default=[], metavar='LABEL=LIB', help='another build of the library to time in alternating rounds')
-    ap.add_argument('--rounds', type=int, default=2, help='alternating rounds of the shipped library and the --also builds')
+    bp.also_arguments(ap)
     args = ap.parse_args(argv)
     from nuhtc_amd import territory as tr
     bp.need_gpu('bench_territory.py')
@@ -180,8 +162,7 @@ def main(argv=None):
                      f'cores; variants: median ms of {args.repeats} calls per round, {args.rounds} alternating rounds',
                 n=args.n, extent_px=args.extent, reach_px=args.reach, classes=C, sets=sets,
                 not_measured=['a whole slide with --nuclei-territory', '--gpus N', 'a window near 2**28 sites'])
-    same = [v.get('equals_shipped', True) for s_ in sets for v in s_['variants'].values()]
-    bp.report(line, ('device_calls_agree', 'checked_against_reference', 'host_agrees'), (('equals_shipped', all(same)),))
+    bp.report(line, ('device_calls_agree', 'checked_against_reference', 'host_agrees'), (('equals_shipped', bp.all_equal_shipped(sets)),))
 
 
 if __name__ == '__main__':

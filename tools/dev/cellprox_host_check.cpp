@@ -10,8 +10,11 @@
 // witness out of j's reach.  The graphs the kernels build, restated on small point sets with the header's functions the way the device
 // runs them -- from the smaller row, witnesses skipped unless d2(i, k) < d2(i, j), djk through cell_pair_d2, the ends not told from the
 // witnesses -- against the definition word for word in 64 bits with the ends excluded and no reach: the same edges and flags on every
-// set, with ties, coincident points and both label modes.  And the segment ordering of prox_place_kernel: every edge of a segment goes to
-// the count of the edges there with a smaller larger-row, with the d2 | rng packing undone -- a sorted segment for any arrival order.
+// set, with ties, coincident points and both label modes.  The segment ordering of prox_place_kernel: every edge of a segment goes to
+// the count of the edges there with a smaller larger-row, with the d2 | rng packing undone -- a sorted segment for any arrival order.  And
+// cell_rank_in_segment itself, the function the four place kernels (cellprox, cellalpha, celladjacency, cellmst) call: the ranks of a
+// shuffled segment of distinct values in the middle of a longer table are a permutation of j0 .. j1 - 1 in value order, whatever lies in
+// front of the segment and behind it; an empty segment and a segment of one entry.
 #include <algorithm>
 #include <cstdio>
 #include <random>
@@ -82,6 +85,24 @@ static bool place_ok(std::vector<int> s_hi, std::vector<int> s_d2) {
   return true;
 }
 
+// cell_rank_in_segment over the segment j0 .. j0 + len - 1 of a table with other values around it: a permutation in value order
+static bool rank_ok(size_t front, size_t len, size_t behind, std::mt19937& rng) {
+  std::vector<int> table(front + len + behind);
+  for (size_t k = 0; k < table.size(); ++k) table[k] = (int)(rng() % 1000);          // the neighbours: anything, smaller values among them
+  std::vector<int> value(len);
+  for (size_t k = 0; k < len; ++k) value[k] = (int)(7 * k + 2);
+  std::shuffle(value.begin(), value.end(), rng);
+  std::copy(value.begin(), value.end(), table.begin() + (long)front);
+  const long long j0 = (long long)front, j1 = j0 + (long long)len;
+  std::vector<int> placed(len, -1);
+  for (size_t k = 0; k < len; ++k) {
+    const long long at = cell_rank_in_segment(table.data(), j0, j1, value[k]);
+    if (at < j0 || at >= j1 || placed.at((size_t)(at - j0)) != -1) return false;
+    placed[(size_t)(at - j0)] = value[k];
+  }
+  return std::is_sorted(placed.begin(), placed.end());
+}
+
 int main() {
   int bad = 0;
   auto expect = [&](bool ok, const char* what) { if (!ok) { std::printf("FAIL %s\n", what); ++bad; } };
@@ -132,6 +153,17 @@ int main() {
     std::vector<int> s_hi(m), s_d2(m);
     for (size_t k = 0; k < m; ++k) { s_hi[k] = hi[order[k]]; s_d2[k] = d2[order[k]]; }
     if (!place_ok(s_hi, s_d2)) { std::printf("FAIL the order of a segment of %zu edges\n", m); ++bad; }
+  }
+  // ---- the shared rank: segments up to 300 long (past a wave's 64 and the 64 kept flags), empty and one-entry segments
+  for (int rep = 0; rep < 200; ++rep) {
+    const size_t len = rep < 3 ? (size_t)rep : rng() % 301;
+    if (!rank_ok(rng() % 40, len, rng() % 40, rng)) { std::printf("FAIL the ranks of a segment of %zu entries\n", len); ++bad; }
+  }
+  {
+    const std::vector<int> one = {5, 9, 1};
+    expect(cell_rank_in_segment(one.data(), 1, 1, 100) == 1 && cell_rank_in_segment(one.data(), 3, 3, -5) == 3, "an empty segment: its own start");
+    expect(cell_rank_in_segment(one.data(), 1, 2, 9) == 1 && cell_rank_in_segment(one.data(), 0, 1, 5) == 0, "a segment of one entry");
+    expect(cell_rank_in_segment(one.data(), 0, 3, 9) == 2 && cell_rank_in_segment(one.data(), 0, 3, 1) == 0 && cell_rank_in_segment(one.data(), 0, 3, 5) == 1, "three entries");
   }
   if (bad) std::printf("%d FAILED\n", bad); else std::printf("cellprox host check ok\n");
   return bad ? 1 : 0;
