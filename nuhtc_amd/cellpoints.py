@@ -1,6 +1,8 @@
 """What the per-slide point analyses -- cellgraph.py, spatial.py, clusters.py, mst.py, proximity.py, alphacomplex.py, outline.py, density.py, territory.py, enrichment.py, and regions.py and margin.py with their second input, which hold the definitions -- do in the same way: half-pixel
 nucleus centres with one label each, the grid over the host-computed bounding box, the pair loop of the brute-force references, the one
-call into the library, the opening of a `build`, the header of the .npz files, and the checks and the census more than one of them holds
+call into the library, the opening of a `build`, the capacity loop of a `build` whose device call may need more room than it was given
+(`grow_to_fit`: proximity.py, alphacomplex.py, adjacency.py, regions.py, margin.py), the header of the .npz files, and the checks and the
+census more than one of them holds
 (slidepoints.py is the table that runs them for the slide path).  |p| < 2**27 and a reach of at most 16384 half pixels keep every squared distance
 within reach an exact int32 on the device (csrc/cellgrid_host.h has the argument); the references restate it in int64."""
 import numpy as np
@@ -156,25 +158,29 @@ def first_edge_cap(n, per_point=4):
     return int(per_point) * int(n) + 64
 
 
-def grow_to_fit(call, make_outputs, first_cap, entry_name, what, limit=1 << 31):
-    """The capacity protocol of the edge-list analyses (proximity.py, alphacomplex.py, adjacency.py), once: the first call has room for
-    first_cap edges; with m > cap the device has written no edge and says how many there are, and ONE second call has room for exactly
-    that many.  call(cap, out) -> (rc, m, *more) never raises; make_outputs(cap) -> out.  -> (out, m, more, calls).  raise_for after
-    each call; ValueError in the name of `what` for m >= limit (None: no such limit, where the device bounds m itself); RuntimeError when
-    the second call counts another m."""
+def grow_to_fit(call, make_outputs, first_cap, entry_name, what, limit=1 << 31, refuse=None, unit='edges'):
+    """The capacity protocol of the project, once -- the edge lists of proximity.py, alphacomplex.py and adjacency.py, and the (edge, slab)
+    records of regions.py and margin.py: the first call has room for first_cap of them; with m > cap the device has written nothing
+    and says how many there are, and ONE second call has room for exactly that many.  call(cap, out) -> (rc, m, *more) never raises;
+    make_outputs(cap) -> out (the same tensors again where they do not depend on cap).  -> (out, m, more, calls).  raise_for after each
+    call; ValueError in the name of `what` for m >= limit (None: no such limit, where the device bounds m itself) -- or, for a caller
+    with another bound and wording, with the message refuse(m) returns (None: m is fine); RuntimeError when the second call counts
+    another m of `unit`."""
     cap, calls = int(first_cap), 1
     out = make_outputs(cap)
     rc, m, *more = call(cap, out)
     raise_for(rc, entry_name)
     if m > cap:
-        if limit is not None and m >= limit:
+        if refuse and refuse(m):
+            raise ValueError(refuse(m))
+        if not refuse and limit is not None and m >= limit:
             raise ValueError(f'{what}: {m} edges, more than 2**31 - 1 (many coincident points)')
         cap, calls = m, 2
         out = make_outputs(cap)
         rc, m, *more = call(cap, out)
         raise_for(rc, entry_name)
         if m != cap:
-            raise RuntimeError(f'{entry_name}: {m} edges on the second call, {cap} on the first')
+            raise RuntimeError(f'{entry_name}: {m} {unit} on the second call, {cap} on the first')
     return out, m, tuple(more), calls
 
 

@@ -376,13 +376,15 @@ CELL_HD inline bool region_on_edge(int ax, int ay, int bx, int by, int px, int p
   return (int64_t)(bx - ax) * (py - ay) - (int64_t)(by - ay) * (px - ax) == 0;
 }
 
-// the slabs (rows of the points' grid: slab k holds y_min + k * side .. y_min + (k + 1) * side - 1) that the closed y-range of an edge
-// meets, clipped to the points' box: s0 .. s1, or false when no point of the box can cross or touch the edge -- it lies wholly above,
-// below or LEFT of the box (a crossed edge lies beyond p towards +x, a touched one holds p in its bounding box).  An edge wholly right
-// of the box stays: every ray runs that way.
-CELL_HD inline bool region_slab_range(int ax, int ay, int bx, int by, int x_min, int y_min, int y_max, int side, int* s0, int* s1) {
-  const int ylo = ay < by ? ay : by, yhi = ay < by ? by : ay;
-  if (yhi < y_min || ylo > y_max || (ax < x_min && bx < x_min)) return false;
+// the slabs (rows of the points' grid: slab k holds y_min + k * side .. y_min + (k + 1) * side - 1) that the closed y-range of an edge,
+// GROWN by R, meets, clipped to the points' box: s0 .. s1, or false for none.  R == 0 (the census): false when no point of the box can
+// cross or touch the edge -- it lies wholly above, below or LEFT of the box (a crossed edge lies beyond p towards +x, a touched one
+// holds p in its bounding box).  R = the largest threshold (the margin bands): the slabs whose points can cross the edge or lie within
+// R of it; false when the grown range misses the box in y or the edge lies wholly left of x_min - R (it can be neither crossed nor
+// near).  An edge wholly right of the box stays: every ray runs that way.  |v| < 2^27 and R <= 2^14: no sum overflows.
+CELL_HD inline bool edge_slab_range(int ax, int ay, int bx, int by, int R, int x_min, int y_min, int y_max, int side, int* s0, int* s1) {
+  const int ylo = (ay < by ? ay : by) - R, yhi = (ay < by ? by : ay) + R;
+  if (yhi < y_min || ylo > y_max || (ax < x_min - R && bx < x_min - R)) return false;
   *s0 = ((ylo > y_min ? ylo : y_min) - y_min) / side;
   *s1 = ((yhi < y_max ? yhi : y_max) - y_min) / side;
   return true;
@@ -456,17 +458,6 @@ CELL_HD inline bool margin_near(int ax, int ay, int bx, int by, int px, int py, 
 // can p be within r of an edge with the bounding box x0 .. x1, y0 .. y1?  Four compares, before any product
 CELL_HD inline bool margin_box_near(int x0, int y0, int x1, int y1, int px, int py, int r) {
   return px >= x0 - r && px <= x1 + r && py >= y0 - r && py <= y1 + r;
-}
-
-// region_slab_range with the edge's y-range GROWN by R = the largest threshold: the slabs whose points can cross the edge or lie within
-// R of it.  No record when the grown range misses the box in y or the edge lies wholly left of x_min - R (it can be neither crossed nor
-// near); an edge right of the box stays for the parity.  R == 0 is region_slab_range.  |v| < 2^27 and R <= 2^14: no sum overflows.
-CELL_HD inline bool margin_slab_range(int ax, int ay, int bx, int by, int R, int x_min, int y_min, int y_max, int side, int* s0, int* s1) {
-  const int ylo = (ay < by ? ay : by) - R, yhi = (ay < by ? by : ay) + R;
-  if (yhi < y_min || ylo > y_max || (ax < x_min - R && bx < x_min - R)) return false;
-  *s0 = ((ylo > y_min ? ylo : y_min) - y_min) / side;
-  *s1 = ((yhi < y_max ? yhi : y_max) - y_min) / side;
-  return true;
 }
 
 // the thresholds row: 1 .. 32 of them, strictly increasing, within 1 .. 16384 half pixels

@@ -14,12 +14,13 @@
 //
 // Stages, all on the caller's stream:
 //   binning    cellbin.h, reach slab, one key per cell: a grid row is a slab and its points are one contiguous run of the records.
-//   edges      celledges.h with margin_slab_range: an edge has one record per slab of the box that its y-range GROWN by R = e_{B-1}
-//              meets, none when the grown range misses the box in y or the edge lies wholly left of x_min - R.  A point of a slab
-//              therefore sees every edge that can straddle it and every edge within R of it.  M, slot_cap and *slots as in the census.
-//   sweep      mg_sweep_kernel  one workgroup per 256 consecutive point records; the slab's edge records go through LDS 256 at a time
-//                               (the edge, its bounding box and its region, gathered once per workgroup) in edge order, so the region
-//                               changes are uniform over the workgroup.  Each lane carries (parity, best band) for the current region.
+//   edges      celledges.h with grow = R = e_{B-1}: an edge has one record per slab of the box that its y-range GROWN by R meets
+//              (edge_slab_range), none when the grown range misses the box in y or the edge lies wholly left of x_min - R.  A point of a
+//              slab therefore sees every edge that can straddle it and every edge within R of it.  M, slot_cap and *slots as in the census.
+//   sweep      mg_sweep_kernel  rg_walk of celledges.h, the walk of the census -- one workgroup per 256 consecutive point records; the
+//                               slab's edge records go through LDS 256 at a time in edge order, so the region changes are uniform over
+//                               the workgroup -- around MgSweep, which stages the edge's bounding box beside the walk's edge and region
+//                               (gathered once per workgroup).  Each lane carries (parity, best band) for the current region.
 //                               Per edge: the parity as in the census; a box reject against the threshold below the lane's best band
 //                               (four compares); only then margin_measure once and margin_within downwards while the band improves.
 //                               At a region change the lanes with a band add to band_census and the odd lanes to census -- per wave,
@@ -33,30 +34,16 @@
 //
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, profiles/cell_margin_resources.txt): no scratch in any kernel.
 //
-// Everything that decides a distance, an index or a limit -- margin_measure, margin_within, margin_box_near, margin_slab_range,
+// Everything that decides a distance, an index or a limit -- margin_measure, margin_within, margin_box_near, edge_slab_range,
 // margin_thresholds_ok, margin_call_ok (cellgrid_host.h) -- is plain C++, and tools/dev/cellmargin_host_check.cpp runs exactly those
 // functions on the host under -fsanitize=address,undefined against __int128 arithmetic and direct loops.  The kernel code itself is not
 // sanitized.
-#include <climits>
-#include <cstring>
-
 #include "celledges.h"
 
 namespace {
 
-struct CellMarginArgs {
-  CellBin b;                          // the points, the grid and the records in cell order (cellbin.h, one key per cell)
-  const int4* edges;                  // [E] (ax, ay, bx, by) half pixels
-  const int32_t* edge_region;         // [E] non-decreasing
-  int E, G, C;
-  int have_grid;                      // 0 with n == 0: the edges are checked, no slab is counted
-  unsigned long long slot_cap;        // the (edge, slab) records the caller left room for
-  unsigned long long* total;          // M: the records the call needs
-  int* slab_count;                    // as in CellRegionArgs
-  int* slab_start;
-  int2* emitted;
-  int* slots;
-  int B, R;                           // the thresholds and the largest of them
+struct CellMarginArgs : EdgeSlabs {   // grow == R = thr[B - 1]
+  int B;                              // the thresholds
   int thr[MARGIN_MAX_BANDS];          // [B] strictly increasing
   unsigned long long* band_census;    // [G][2][B][C]
   unsigned long long* census;         // [G][C]
@@ -64,10 +51,6 @@ struct CellMarginArgs {
   int32_t* band_region;               // [n]
   uint8_t* band_inside;               // [n]
 };
-
-__device__ __forceinline__ bool rg_range(const CellMarginArgs& a, const int4 e, int* s0, int* s1) {
-  return margin_slab_range(e.x, e.y, e.z, e.w, a.R, a.b.x_min, a.b.y_min, a.b.y_max, a.b.side, s0, s1);
-}
 
 __global__ __launch_bounds__(256) void mg_zero_kernel(CellMarginArgs a) {
   if (!rg_go(a)) return;
@@ -90,78 +73,53 @@ __device__ __forceinline__ void mg_wave_add(unsigned long long* table, int key) 
   }
 }
 
-// the end of a region's run of edges.  Called by every thread of the workgroup at once (the edge sequence is the workgroup's).
-__device__ __forceinline__ void mg_flush(const CellMarginArgs& a, int cur, bool mine, int parity, int best, int cls, int& nb, int& nr, int& ni) {
-  if (cur < 0) return;
-  const bool near = mine && best < a.B;
-  if (near && best < nb) { nb = best; nr = cur; ni = parity; }     // the regions come ascending: a tie keeps the smaller one
-  mg_wave_add(a.band_census + (size_t)cur * 2 * a.B * a.C, near && cls >= 0 ? (parity * a.B + best) * a.C + cls : -1);
-  mg_wave_add(a.census + (size_t)cur * a.C, mine && parity && cls >= 0 ? cls : -1);
-}
-
-__global__ __launch_bounds__(REGION_STAGE) void mg_sweep_kernel(CellMarginArgs a) {
-  __shared__ int4 st_edge[REGION_STAGE];
-  __shared__ int4 st_box[REGION_STAGE];
-  __shared__ int st_region[REGION_STAGE];
-  __shared__ int thr[MARGIN_MAX_BANDS];
-  __shared__ int next_row;
-  if (!rg_go(a)) return;                                 // uniform
-  const CellBin& g = a.b;
-  const int tid = threadIdx.x, j = blockIdx.x * REGION_STAGE + tid;
-  const bool have = j < g.n;
-  const int4 me = have ? g.recs[j] : make_int4(0, 0, -1, -1);
-  const int my_row = have ? (me.y - g.y_min) / g.side : INT_MAX;
-  const int cls = have && (unsigned)me.z < (unsigned)a.C ? me.z : -1;
-  const int B = a.B;
-  int nb = B, nr = -1, ni = 0;
-  if (tid < B) thr[tid] = a.thr[tid];
-  if (tid == 0) next_row = my_row;                       // thread 0 has a record: the grid is ceil(n / 256) workgroups
-  __syncthreads();
-  int row = next_row;
-  while (row != INT_MAX) {                               // the slabs that hold records of this workgroup, ascending
-    const bool mine = my_row == row;
-    const int k0 = a.slab_start[row], k1 = a.slab_start[row + 1];
-    int cur = -1, parity = 0, best = B;
-    for (int base = k0; base < k1; base += REGION_STAGE) {
-      __syncthreads();                                   // the chunk before this one has been read by everyone
-      if (base + tid < k1) {
-        const int e = a.slots[base + tid];
-        const int4 ed = a.edges[e];
-        st_edge[tid] = ed;
-        st_box[tid] = make_int4(min(ed.x, ed.z), min(ed.y, ed.w), max(ed.x, ed.z), max(ed.y, ed.w));
-        st_region[tid] = a.edge_region[e];
-      }
-      __syncthreads();
-      const int m = min(REGION_STAGE, k1 - base);
-      for (int k = 0; k < m; ++k) {
-        const int r = __builtin_amdgcn_readfirstlane(st_region[k]);
-        if (r != cur) {                                  // the same for every thread of the workgroup
-          mg_flush(a, cur, mine, parity, best, cls, nb, nr, ni);
-          cur = r; parity = 0; best = B;
-        }
-        if (mine) {
-          const int4 ed = st_edge[k];
-          parity ^= (int)region_crossed(ed.x, ed.y, ed.z, ed.w, me.x, me.y);
-          if (best > 0) {
-            const int4 bx = st_box[k];
-            if (margin_box_near(bx.x, bx.y, bx.z, bx.w, me.x, me.y, thr[best - 1])) {
-              uint64_t q, l2;
-              margin_measure(ed.x, ed.y, ed.z, ed.w, me.x, me.y, &q, &l2);
-              while (best > 0 && margin_within(q, l2, thr[best - 1])) --best;
-            }
-          }
-        }
+// what a lane carries through rg_walk: (parity, best band) of the current region, and its minimum (band, region, side) over all of them.
+// box and thr are the file's LDS beside the walk's: the bounding box of every staged edge, and the thresholds.
+struct MgSweep {
+  const CellMarginArgs& a;
+  int4* box;
+  int* thr;
+  int parity, best, nb, nr, ni;
+  // The four s_nop keep the loop over the staged edges (1.2 KiB of code) at the byte offset 0x3bc it had when the walk was written out in
+  // this kernel.  Measured on gfx950 (profiles/cell_margin.json, slab_walk_vs_parent): with the same instructions at 0x308 or 0x38c the
+  // sweep took 1.3 - 1.8 % longer, at 0x3bc it takes what it took.  They run once per workgroup; look at the offset again (llvm-objdump
+  // -d) when the prologue of rg_walk or of this kernel changes.
+  __device__ __forceinline__ void begin(int tid) {
+    if (tid < a.B) thr[tid] = a.thr[tid];
+    asm volatile("s_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0");
+  }
+  __device__ __forceinline__ void stage(int tid, const int4 ed) {
+    box[tid] = make_int4(min(ed.x, ed.z), min(ed.y, ed.w), max(ed.x, ed.z), max(ed.y, ed.w));
+  }
+  __device__ __forceinline__ void reset() { parity = 0; best = a.B; }
+  __device__ __forceinline__ void edge(int k, const int4 ed, const int4 me) {
+    parity ^= (int)region_crossed(ed.x, ed.y, ed.z, ed.w, me.x, me.y);
+    if (best > 0) {
+      const int4 bx = box[k];
+      if (margin_box_near(bx.x, bx.y, bx.z, bx.w, me.x, me.y, thr[best - 1])) {
+        uint64_t q, l2;
+        margin_measure(ed.x, ed.y, ed.z, ed.w, me.x, me.y, &q, &l2);
+        while (best > 0 && margin_within(q, l2, thr[best - 1])) --best;
       }
     }
-    mg_flush(a, cur, mine, parity, best, cls, nb, nr, ni);
-    __syncthreads();                                     // everyone has read next_row
-    if (tid == 0) next_row = INT_MAX;
-    __syncthreads();
-    if (have && my_row > row) atomicMin(&next_row, my_row);
-    __syncthreads();
-    row = next_row;
   }
-  if (have) { a.band[me.w] = nb; a.band_region[me.w] = nr; a.band_inside[me.w] = (uint8_t)ni; }
+  // the end of a region's run of edges
+  __device__ __forceinline__ void flush(int cur, bool mine, int cls) {
+    if (cur < 0) return;
+    const bool near = mine && best < a.B;
+    if (near && best < nb) { nb = best; nr = cur; ni = parity; }     // the regions come ascending: a tie keeps the smaller one
+    mg_wave_add(a.band_census + (size_t)cur * 2 * a.B * a.C, near && cls >= 0 ? (parity * a.B + best) * a.C + cls : -1);
+    mg_wave_add(a.census + (size_t)cur * a.C, mine && parity && cls >= 0 ? cls : -1);
+  }
+};
+
+__global__ __launch_bounds__(REGION_STAGE) void mg_sweep_kernel(CellMarginArgs a) {
+  __shared__ int4 st_box[REGION_STAGE];
+  __shared__ int thr[MARGIN_MAX_BANDS];
+  if (!rg_go(a)) return;                                 // uniform
+  MgSweep w{a, st_box, thr, 0, a.B, a.B, -1, 0};
+  const int4 me = rg_walk(a, w);
+  if (me.w >= 0) { a.band[me.w] = w.nb; a.band_region[me.w] = w.nr; a.band_inside[me.w] = (uint8_t)w.ni; }
 }
 
 }  // namespace
@@ -172,38 +130,18 @@ extern "C" int nuhtc_cell_margin(int device, const int32_t* points, const int32_
                                  int32_t* band_region, uint8_t* band_inside, int64_t* slots, void* stream) {
   if (!cell_call_ok(n, MST_MAX_POINTS, num_classes, slab, x_min, y_min, x_max, y_max) || !margin_call_ok(E, G, slab, slot_cap, thresholds, B))
     return NUHTC_E_INVALID;
-  if (!slots || (n > 0 && (!points || !labels || !band || !band_region || !band_inside)) || (E > 0 && (!edges || !edge_region)) ||
-      (G > 0 && (!band_census || !census)))
-    return NUHTC_E_INVALID;
-  if (reinterpret_cast<uintptr_t>(edges) & 15) return NUHTC_E_INVALID;        // an edge is one 16-byte load
-  if (hipSetDevice(device) != hipSuccess) return NUHTC_E_HIP;
-  hipStream_t st = (hipStream_t)stream;
-  CellMarginArgs a;
-  memset(&a, 0, sizeof(a));
-  a.edges = reinterpret_cast<const int4*>(edges); a.edge_region = edge_region;
-  a.E = (int)E; a.G = (int)G; a.C = num_classes; a.slot_cap = (unsigned long long)slot_cap;
-  a.B = B; a.R = thresholds[B - 1];
+  if ((n > 0 && (!band || !band_region || !band_inside)) || (G > 0 && (!band_census || !census))) return NUHTC_E_INVALID;
+  CellMarginArgs a{};
+  EdgeCall h;
+  const int rc = edge_front(a, h, device, points, labels, n, num_classes, edges, edge_region, E, G, thresholds[B - 1], slab, slot_cap, x_min, y_min,
+                            x_max, y_max, slots, stream);
+  if (rc) return rc;
+  a.B = B;
   for (int k = 0; k < B; ++k) a.thr[k] = thresholds[k];
   a.band_census = reinterpret_cast<unsigned long long*>(band_census); a.census = reinterpret_cast<unsigned long long*>(census);
   a.band = band; a.band_region = band_region; a.band_inside = band_inside;
-  DevScratch tmp;      // every temporary of the call, freed on the way out
-  int nchunk, schunk, *chunk_base;
-  if (!edge_tables(a, points, labels, n, x_min, y_min, x_max, y_max, slab, slot_cap, tmp, st, &nchunk, &schunk, &chunk_base)) return NUHTC_E_HIP;
-  if (n > 0) {
-    ProfScope ps("cell_margin_bin", 0, 0, st);
-    cellbin_launch(a.b, nchunk, st);
-  }
-  {
-    ProfScope ps("cell_margin_edges", 0, 0, st);
-    edge_launch(a, E, n, slot_cap, schunk, chunk_base, st);
-  }
-  {
-    ProfScope ps("cell_margin_sweep", 0, 0, st);
-    if (G > 0) {
-      const int64_t cells = G * (2 * B + 1) * num_classes;                    // at most 2^16 * 65 * 14
-      hipLaunchKernelGGL(mg_zero_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, a);
-    }
-    if (n > 0) hipLaunchKernelGGL(mg_sweep_kernel, dim3((unsigned)((n + REGION_STAGE - 1) / REGION_STAGE)), dim3(REGION_STAGE), 0, st, a);
-  }
-  return edge_finish(a, st, slots);
+  const int64_t cells = G * (2 * B + 1) * num_classes;                        // at most 2^16 * 65 * 14
+  return edge_run(a, h, EdgeTags{"cell_margin_bin", "cell_margin_edges", "cell_margin_sweep"},
+                  [&] { hipLaunchKernelGGL(mg_zero_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h.st, a); },
+                  [&] { hipLaunchKernelGGL(mg_sweep_kernel, dim3((unsigned)((n + REGION_STAGE - 1) / REGION_STAGE)), dim3(REGION_STAGE), 0, h.st, a); });
 }

@@ -14,57 +14,38 @@
 //   geometry   on the HOST from the caller's bounding box (cell_grid_side): cells of side >= slab, at most 2^22 of them.  A grid row is
 //              a horizontal SLAB of the box, and with one key per cell its points are one contiguous run of the records.
 //   binning    cellbin.h, reach slab, one key per cell.
-//   edges      celledges.h (shared with cellmargin.hip), with region_slab_range as the slabs an edge has a record in: clipped to the
-//              box; an edge wholly above, below or left of the box meets none.  rg_check_kernel states M, the (edge, slab) records the
-//              call needs, and every later kernel first compares M with the caller's slot_cap (rg_go); count, scan, emit, place leave
-//              every slab's records in edge order, hence grouped by region, ascending.
-//   crossing   rg_cross_kernel  one workgroup per 256 consecutive point records.  For each slab that holds some of them (the records are
-//                               in row order, so these are few) the slab's edge records go through LDS 256 at a time -- coordinates and
-//                               region gathered once per workgroup -- and every thread of that slab takes each staged edge by a broadcast
-//                               LDS read.  The edge sequence, and with it the region changes, are the same for every thread of the
-//                               workgroup: each thread carries (parity, depth, top, on-boundary), and at a region change the waves add
-//                               their odd lanes to census, one integer atomic per (wave, class present) -- a ballot per class, as the
-//                               cluster tables do.
+//   edges      celledges.h (shared with cellmargin.hip), with edge_slab_range at R = 0 as the slabs an edge has a record in: clipped to
+//              the box; an edge wholly above, below or left of the box meets none.  rg_check_kernel states M, the (edge, slab) records
+//              the call needs, and every later kernel first compares M with the caller's slot_cap (rg_go); count, scan, emit, place
+//              leave every slab's records in edge order, hence grouped by region, ascending.
+//   crossing   rg_cross_kernel  rg_walk of celledges.h -- one workgroup per 256 consecutive point records, the edge records of each of
+//                               their slabs staged through LDS 256 at a time, the region changes the same for every thread of the
+//                               workgroup -- around RgCross: each thread carries (parity, depth, top, on-boundary), and at a region
+//                               change the waves add their odd lanes to census, one integer atomic per (wave, class present) -- a
+//                               ballot per class, as the cluster tables do.
 //   outputs    every kernel that writes an output tests the flag and M first: a refused call leaves every output untouched, and so does a
 //              call whose slot_cap is below M (it returns 0 and reports M: the caller calls once more).  With n == 0 the edges are still
 //              checked and census is cleared.
-// No kernel waits on another workgroup; every loop runs over a range of a table.
+// No kernel waits on another workgroup; every loop runs over a range of a table.  The entry point is edge_front and edge_run of
+// celledges.h around its own checks, its four fields and its two launches.
 //
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, profiles/cell_regions_resources.txt): no scratch in any kernel; the crossing
 // kernel holds 256 x (16 + 4) B of staged edges and one int, 5124 B of LDS, so LDS never bounds the occupancy (160 KiB per CU); a
 // larger stage would only lengthen the time between barriers.
 //
-// Everything that decides an index, a side or a limit -- region_crossed, region_on_edge, region_slab_range, region_edge_ok,
+// Everything that decides an index, a side or a limit -- region_crossed, region_on_edge, edge_slab_range, region_edge_ok,
 // region_call_ok (cellgrid_host.h) -- is plain C++, and tools/dev/cellregion_host_check.cpp runs exactly those functions on the host
 // under -fsanitize=address,undefined against __int128 arithmetic and a direct loop.  The kernel code itself is not sanitized.
-#include <climits>
-#include <cstring>
-
 #include "celledges.h"
 
 namespace {
 
-struct CellRegionArgs {
-  CellBin b;                          // the points, the grid and the records in cell order (cellbin.h, one key per cell)
-  const int4* edges;                  // [E] (ax, ay, bx, by) half pixels
-  const int32_t* edge_region;         // [E] non-decreasing
-  int E, G, C;
-  int have_grid;                      // 0 with n == 0: the edges are checked, no slab is counted
-  unsigned long long slot_cap;        // the (edge, slab) records the caller left room for
-  unsigned long long* total;          // M: the records the call needs
-  int* slab_count;                    // [nchunk * CB_CHUNK] per slab, zero past them; counted up, and down again by the emit
-  int* slab_start;                    // [nchunk * CB_CHUNK] entry k = records in front of slab k (entry ncy: all of them)
-  int2* emitted;                      // [slot_cap] (edge, slab) in arrival order inside a slab's segment
-  int* slots;                         // [slot_cap] the edge of every record, slab by slab, in edge order
+struct CellRegionArgs : EdgeSlabs {   // grow == 0
   int32_t* region;                    // [n]
   int32_t* depth;                     // [n]
   uint8_t* on_boundary;               // [n]
   unsigned long long* census;         // [G][C]
 };
-
-__device__ __forceinline__ bool rg_range(const CellRegionArgs& a, const int4 e, int* s0, int* s1) {
-  return region_slab_range(e.x, e.y, e.z, e.w, a.b.x_min, a.b.y_min, a.b.y_max, a.b.side, s0, s1);
-}
 
 __global__ __launch_bounds__(256) void rg_zero_kernel(CellRegionArgs a) {
   if (!rg_go(a)) return;
@@ -84,56 +65,25 @@ __device__ __forceinline__ void rg_flush(const CellRegionArgs& a, int cur, bool 
   }
 }
 
-__global__ __launch_bounds__(REGION_STAGE) void rg_cross_kernel(CellRegionArgs a) {
-  __shared__ int4 st_edge[REGION_STAGE];
-  __shared__ int st_region[REGION_STAGE];
-  __shared__ int next_row;
-  if (!rg_go(a)) return;                                 // uniform
-  const CellBin& g = a.b;
-  const int tid = threadIdx.x, j = blockIdx.x * REGION_STAGE + tid;
-  const bool have = j < g.n;
-  const int4 me = have ? g.recs[j] : make_int4(0, 0, -1, -1);
-  const int my_row = have ? (me.y - g.y_min) / g.side : INT_MAX;
-  const int cls = have && (unsigned)me.z < (unsigned)a.C ? me.z : -1;
-  int top = -1, depth = 0, onb = 0;
-  if (tid == 0) next_row = my_row;                       // thread 0 has a record: the grid is ceil(n / 256) workgroups
-  __syncthreads();
-  int row = next_row;
-  while (row != INT_MAX) {                               // the slabs that hold records of this workgroup, ascending
-    const bool mine = my_row == row;
-    const int k0 = a.slab_start[row], k1 = a.slab_start[row + 1];
-    int cur = -1, parity = 0;
-    for (int base = k0; base < k1; base += REGION_STAGE) {
-      __syncthreads();                                   // the chunk before this one has been read by everyone
-      if (base + tid < k1) {
-        const int e = a.slots[base + tid];
-        st_edge[tid] = a.edges[e];
-        st_region[tid] = a.edge_region[e];
-      }
-      __syncthreads();
-      const int m = min(REGION_STAGE, k1 - base);
-      for (int k = 0; k < m; ++k) {
-        const int r = __builtin_amdgcn_readfirstlane(st_region[k]);
-        if (r != cur) {                                  // the same for every thread of the workgroup
-          rg_flush(a, cur, mine && parity, cls, depth, top);
-          cur = r; parity = 0;
-        }
-        const int4 ed = st_edge[k];
-        if (mine) {
-          parity ^= (int)region_crossed(ed.x, ed.y, ed.z, ed.w, me.x, me.y);
-          onb |= (int)region_on_edge(ed.x, ed.y, ed.z, ed.w, me.x, me.y);
-        }
-      }
-    }
-    rg_flush(a, cur, mine && parity, cls, depth, top);
-    __syncthreads();                                     // everyone has read next_row
-    if (tid == 0) next_row = INT_MAX;
-    __syncthreads();
-    if (have && my_row > row) atomicMin(&next_row, my_row);
-    __syncthreads();
-    row = next_row;
+// what a lane carries through rg_walk: the parity of the current region, and (depth, top, on-boundary) over all of them
+struct RgCross {
+  const CellRegionArgs& a;
+  int parity, top, depth, onb;
+  __device__ __forceinline__ void begin(int) {}
+  __device__ __forceinline__ void stage(int, const int4&) {}
+  __device__ __forceinline__ void reset() { parity = 0; }
+  __device__ __forceinline__ void edge(int, const int4 ed, const int4 me) {
+    parity ^= (int)region_crossed(ed.x, ed.y, ed.z, ed.w, me.x, me.y);
+    onb |= (int)region_on_edge(ed.x, ed.y, ed.z, ed.w, me.x, me.y);
   }
-  if (have) { a.region[me.w] = top; a.depth[me.w] = depth; a.on_boundary[me.w] = (uint8_t)onb; }
+  __device__ __forceinline__ void flush(int cur, bool mine, int cls) { rg_flush(a, cur, mine && parity, cls, depth, top); }
+};
+
+__global__ __launch_bounds__(REGION_STAGE) void rg_cross_kernel(CellRegionArgs a) {
+  if (!rg_go(a)) return;                                 // uniform
+  RgCross w{a, 0, -1, 0, 0};
+  const int4 me = rg_walk(a, w);
+  if (me.w >= 0) { a.region[me.w] = w.top; a.depth[me.w] = w.depth; a.on_boundary[me.w] = (uint8_t)w.onb; }
 }
 
 }  // namespace
@@ -142,31 +92,13 @@ extern "C" int nuhtc_cell_regions(int device, const int32_t* points, const int32
                                   const int32_t* edge_region, int64_t E, int64_t G, int slab, int64_t slot_cap, int x_min, int y_min, int x_max,
                                   int y_max, int32_t* region, int32_t* depth, uint8_t* on_boundary, int64_t* census, int64_t* slots, void* stream) {
   if (!cell_call_ok(n, MST_MAX_POINTS, num_classes, slab, x_min, y_min, x_max, y_max) || !region_call_ok(E, G, slab, slot_cap)) return NUHTC_E_INVALID;
-  if (!slots || (n > 0 && (!points || !labels || !region || !depth || !on_boundary)) || (E > 0 && (!edges || !edge_region)) || (G > 0 && !census))
-    return NUHTC_E_INVALID;
-  if (reinterpret_cast<uintptr_t>(edges) & 15) return NUHTC_E_INVALID;        // an edge is one 16-byte load
-  if (hipSetDevice(device) != hipSuccess) return NUHTC_E_HIP;
-  hipStream_t st = (hipStream_t)stream;
-  CellRegionArgs a;
-  memset(&a, 0, sizeof(a));
-  a.edges = reinterpret_cast<const int4*>(edges); a.edge_region = edge_region;
-  a.E = (int)E; a.G = (int)G; a.C = num_classes; a.slot_cap = (unsigned long long)slot_cap;
+  if ((n > 0 && (!region || !depth || !on_boundary)) || (G > 0 && !census)) return NUHTC_E_INVALID;
+  CellRegionArgs a{};
+  EdgeCall h;
+  const int rc = edge_front(a, h, device, points, labels, n, num_classes, edges, edge_region, E, G, 0, slab, slot_cap, x_min, y_min, x_max, y_max, slots, stream);
+  if (rc) return rc;
   a.region = region; a.depth = depth; a.on_boundary = on_boundary; a.census = reinterpret_cast<unsigned long long*>(census);
-  DevScratch tmp;      // every temporary of the call, freed on the way out
-  int nchunk, schunk, *chunk_base;
-  if (!edge_tables(a, points, labels, n, x_min, y_min, x_max, y_max, slab, slot_cap, tmp, st, &nchunk, &schunk, &chunk_base)) return NUHTC_E_HIP;
-  if (n > 0) {
-    ProfScope ps("cell_regions_bin", 0, 0, st);
-    cellbin_launch(a.b, nchunk, st);
-  }
-  {
-    ProfScope ps("cell_regions_edges", 0, 0, st);
-    edge_launch(a, E, n, slot_cap, schunk, chunk_base, st);
-  }
-  {
-    ProfScope ps("cell_regions_cross", 0, 0, st);
-    if (G > 0) hipLaunchKernelGGL(rg_zero_kernel, dim3((unsigned)((G * num_classes + 255) / 256)), dim3(256), 0, st, a);
-    if (n > 0) hipLaunchKernelGGL(rg_cross_kernel, dim3((unsigned)((n + REGION_STAGE - 1) / REGION_STAGE)), dim3(REGION_STAGE), 0, st, a);
-  }
-  return edge_finish(a, st, slots);
+  return edge_run(a, h, EdgeTags{"cell_regions_bin", "cell_regions_edges", "cell_regions_cross"},
+                  [&] { hipLaunchKernelGGL(rg_zero_kernel, dim3((unsigned)((G * num_classes + 255) / 256)), dim3(256), 0, h.st, a); },
+                  [&] { hipLaunchKernelGGL(rg_cross_kernel, dim3((unsigned)((n + REGION_STAGE - 1) / REGION_STAGE)), dim3(REGION_STAGE), 0, h.st, a); });
 }

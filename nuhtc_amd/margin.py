@@ -158,19 +158,11 @@ def choose_slab(bounds, thresholds):
 
 
 def slots_needed(edges, bounds, slab, thresholds):
-    """M, the (edge, slab) records the device call needs, stated exactly on the host: `cellpoints.cell_side` restates the grid, the rest
-    restates margin_slab_range of csrc/cellgrid_host.h -- with R = e_{B-1}, an edge has one record per slab of the box that its closed
-    y-range grown by R meets, none when the grown range lies above or below the box or the edge lies wholly left of x_min - R."""
-    e = np.asarray(edges, np.int64).reshape(-1, 4)
-    if len(e) == 0 or bounds is None:
+    """M, the (edge, slab) records the device call needs, stated exactly on the host: `regions.slots_needed` with every edge's y-range
+    grown by R = e_{B-1}.  Without edges or points it is 0 whatever the thresholds."""
+    if np.size(edges) == 0 or bounds is None:
         return 0
-    R = int(as_thresholds(thresholds)[-1])
-    x_min, y_min, x_max, y_max = (int(b) for b in bounds)
-    side = cellpoints.cell_side(x_min, y_min, x_max, y_max, int(slab), MAX_CELLS)
-    ylo, yhi = np.minimum(e[:, 1], e[:, 3]) - R, np.maximum(e[:, 1], e[:, 3]) + R
-    keep = (yhi >= y_min) & (ylo <= y_max) & ~((e[:, 0] < x_min - R) & (e[:, 2] < x_min - R))
-    s0, s1 = (np.maximum(ylo, y_min) - y_min) // side, (np.minimum(yhi, y_max) - y_min) // side
-    return int((s1 - s0 + 1)[keep].sum())
+    return regions.slots_needed(edges, bounds, slab, int(as_thresholds(thresholds)[-1]))
 
 
 def call(points, labels, num_classes, edges, edge_region, G, thresholds, slab, slot_cap, band_census, census, band, band_region, band_inside,
@@ -181,14 +173,10 @@ def call(points, labels, num_classes, edges, edge_region, G, thresholds, slab, s
     hip.E_HIP; M, the (edge, slab) records the call needs, is None unless the code is 0.  With M > slot_cap the outputs are untouched:
     call again with slot_cap >= M.  bounds = (x_min, y_min, x_max, y_max) of the points, computed on the host when not given."""
     import ctypes
-    m = ctypes.c_int64(-1)
-    vp = lambda t: ctypes.c_void_p(t.data_ptr())
     row = [int(v) for v in np.asarray(thresholds).reshape(-1).tolist()]
     thr = (ctypes.c_int32 * max(len(row), 1))(*row)
-    rc = cellpoints.launch('nuhtc_cell_margin', device, points, labels,
-                           (int(num_classes), vp(edges), vp(edge_region), int(edges.shape[0]), int(G), thr, len(row), int(slab), int(slot_cap)),
-                           (band_census, census, band, band_region, band_inside), bounds, extra=(ctypes.byref(m),))
-    return rc, (int(m.value) if rc == 0 else None)
+    return regions.call_entry('nuhtc_cell_margin', points, labels, num_classes, edges, edge_region, G, (thr, len(row)), slab, slot_cap,
+                              (band_census, census, band, band_region, band_inside), bounds, device)
 
 
 def outputs(n, G, num_classes, B, device, fill=0):
@@ -205,34 +193,13 @@ def build(points, labels, num_classes, edges, edge_region, G, thresholds, device
     The slab height is `choose_slab` unless given; the first call has room for `slots_needed` records -- exactly what the device counts --
     unless `slot_cap` says otherwise; when the device needs more it says how many and writes nothing, and ONE second call has room for
     exactly that many.  There is no host route: without the library or a GPU this raises."""
-    import torch
     C, G = int(num_classes), int(G)
     e, er = as_edges(edges, edge_region, G, 'margin')
     thr = as_thresholds(thresholds)
-    check_args(C, G, len(e), 1, thr)
-    p, lab, dev, p_d, lab_d, bounds = cellpoints.resident(points, labels, 'margin', device)
-    n, B = len(p), len(thr)
-    if n and np.abs(p).max() >= COORD_LIMIT:
-        raise ValueError('margin: a coordinate lies outside |p| < 2**27')
-    slab = choose_slab(bounds, thr) if slab is None and n else int(slab or 1)
-    check_args(C, G, len(e), slab, thr)
-    cap, calls = (slots_needed(e, bounds, slab, thr) if slot_cap is None else int(slot_cap)), 1
-    too_many = 'margin: {} (edge, slab) records, more than 2**28: a larger slab makes them fewer'
-    if cap > MAX_SLOTS:
-        raise ValueError(too_many.format(cap))
-    e_d, er_d = torch.from_numpy(e if len(e) else np.zeros((1, 4), np.int32)).to(dev), torch.from_numpy(er if len(e) else np.zeros(1, np.int32)).to(dev)
-    e_d, er_d = e_d[:len(e)], er_d[:len(e)]
-    out = outputs(n, G, C, B, dev)
-    rc, m = call(p_d, lab_d, C, e_d, er_d, G, thr, slab, cap, *out, bounds=bounds, device=device)
-    cellpoints.raise_for(rc, 'nuhtc_cell_margin')
-    if m > cap:
-        if m > MAX_SLOTS:
-            raise ValueError(too_many.format(m))
-        cap, calls = m, 2
-        rc, m = call(p_d, lab_d, C, e_d, er_d, G, thr, slab, cap, *out, bounds=bounds, device=device)
-        cellpoints.raise_for(rc, 'nuhtc_cell_margin')
-        if m != cap:
-            raise RuntimeError(f'nuhtc_cell_margin: {m} records on the second call, {cap} on the first')
+    out, n, calls = regions.build_entry('margin', 'nuhtc_cell_margin', points, labels, C, e, er, G, device, slab, slot_cap,
+                                        check=lambda *a: check_args(*a, thr), slab_rule=lambda bounds: choose_slab(bounds, thr), grow=int(thr[-1]),
+                                        make_outputs=lambda n, dev: outputs(n, G, C, len(thr), dev),
+                                        call=lambda front, back, bounds: call(*front, thr, *back, bounds=bounds, device=device))
     got = (out[0][:G].cpu().numpy(), out[1][:G].cpu().numpy(), out[2][:n].cpu().numpy(), out[3][:n].cpu().numpy(), out[4][:n].cpu().numpy())
     return got + (calls,) if with_calls else got
 
@@ -280,13 +247,11 @@ def write_npz(path, nuclei_id, xy, label, band_census, census, band, band_region
     band_inside = np.ascontiguousarray(band_inside, np.uint8).reshape(-1)
     if not len(band) == len(band_region) == len(band_inside) == n or census.ndim != 2 or len(census) != G or len(band_census) != G:
         raise ValueError('write_npz: one band, band_region and band_inside per nucleus, one row of census and band_census per region')
-    e, er = as_edges(table.edges, table.edge_region, G, 'write_npz')
-    check_args(census.shape[1], G, len(e), 1, thr)
+    t = regions.table_arrays(table, G)
+    check_args(census.shape[1], G, len(t['edges']), 1, thr)
     d = derive(band_census, census, thr)
     with open(path, 'wb') as f:
-        np.savez(f, **head, band_census=band_census, census=census, band=band, band_region=band_region, band_inside=band_inside, thresholds=thr, **d,
-                 names=np.asarray(table.names, dtype=np.str_).reshape(-1), ring_start=np.asarray(table.ring_start, np.int64), edges=e, edge_region=er,
-                 area2=np.asarray(table.area2, np.int64))
+        np.savez(f, **head, band_census=band_census, census=census, band=band, band_region=band_region, band_inside=band_inside, thresholds=thr, **d, **t)
     return path
 
 

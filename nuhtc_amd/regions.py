@@ -254,19 +254,33 @@ def choose_slab(bounds):
     return int(min(max(-(-(int(bounds[3]) - int(bounds[1]) + 1) // SLAB_ROWS), 1), MAX_R))
 
 
-def slots_needed(edges, bounds, slab):
+def slots_needed(edges, bounds, slab, grow=0):
     """M, the (edge, slab) records the device call needs, stated exactly on the host: `cellpoints.cell_side` restates the grid, the rest
-    restates region_slab_range of csrc/cellgrid_host.h -- an edge has one record per slab of the box its closed y-range meets, none when it
-    lies wholly above, below or left of the box."""
+    restates edge_slab_range of csrc/cellgrid_host.h -- an edge has one record per slab of the box that its closed y-range, grown by
+    `grow` (0 here, the largest threshold in margin.py), meets; none when the grown range lies above or below the box or the edge lies
+    wholly left of x_min - grow."""
     e = np.asarray(edges, np.int64).reshape(-1, 4)
     if len(e) == 0 or bounds is None:
         return 0
+    R = int(grow)
     x_min, y_min, x_max, y_max = (int(b) for b in bounds)
     side = cellpoints.cell_side(x_min, y_min, x_max, y_max, int(slab), MAX_CELLS)
-    ylo, yhi = np.minimum(e[:, 1], e[:, 3]), np.maximum(e[:, 1], e[:, 3])
-    keep = (yhi >= y_min) & (ylo <= y_max) & ~((e[:, 0] < x_min) & (e[:, 2] < x_min))
+    ylo, yhi = np.minimum(e[:, 1], e[:, 3]) - R, np.maximum(e[:, 1], e[:, 3]) + R
+    keep = (yhi >= y_min) & (ylo <= y_max) & ~((e[:, 0] < x_min - R) & (e[:, 2] < x_min - R))
     s0, s1 = (np.maximum(ylo, y_min) - y_min) // side, (np.minimum(yhi, y_max) - y_min) // side
     return int((s1 - s0 + 1)[keep].sum())
+
+
+def call_entry(name, points, labels, num_classes, edges, edge_region, G, more, slab, slot_cap, out, bounds, device):
+    """What `call` here and in margin.py do alike: the entry point `name`, whose scalars are (num_classes, edges, edge_region, E, G, *more,
+    slab, slot_cap), on the output tensors `out` -> (the library's return code, M or None)."""
+    import ctypes
+    m = ctypes.c_int64(-1)
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())
+    rc = cellpoints.launch(name, device, points, labels,
+                           (int(num_classes), vp(edges), vp(edge_region), int(edges.shape[0]), int(G), *more, int(slab), int(slot_cap)),
+                           out, bounds, extra=(ctypes.byref(m),))
+    return rc, (int(m.value) if rc == 0 else None)
 
 
 def call(points, labels, num_classes, edges, edge_region, G, slab, slot_cap, region, depth, on_boundary, census, bounds=None, device=0):
@@ -274,13 +288,8 @@ def call(points, labels, num_classes, edges, edge_region, G, slab, slot_cap, reg
     (n,), on_boundary uint8 (n,), census int64 (G, C); slab in HALF pixels) -> (the library's return code, M), nothing raised: the code is 0
     or hip.E_INVALID / hip.E_HIP; M, the (edge, slab) records the call needs, is None unless the code is 0.  With M > slot_cap the outputs
     are untouched: call again with slot_cap >= M.  bounds = (x_min, y_min, x_max, y_max) of the points, computed on the host when not given."""
-    import ctypes
-    m = ctypes.c_int64(-1)
-    vp = lambda t: ctypes.c_void_p(t.data_ptr())
-    rc = cellpoints.launch('nuhtc_cell_regions', device, points, labels,
-                           (int(num_classes), vp(edges), vp(edge_region), int(edges.shape[0]), int(G), int(slab), int(slot_cap)),
-                           (region, depth, on_boundary, census), bounds, extra=(ctypes.byref(m),))
-    return rc, (int(m.value) if rc == 0 else None)
+    return call_entry('nuhtc_cell_regions', points, labels, num_classes, edges, edge_region, G, (), slab, slot_cap,
+                      (region, depth, on_boundary, census), bounds, device)
 
 
 def outputs(n, G, num_classes, device, fill=0):
@@ -290,38 +299,42 @@ def outputs(n, G, num_classes, device, fill=0):
     return [torch.full(s, fill, dtype=t, device=device) for s, t in (((n,), torch.int32), ((n,), torch.int32), ((n,), torch.uint8), ((G, int(num_classes)), torch.int64))]
 
 
+def build_entry(what, entry, points, labels, C, e, er, G, device, slab, slot_cap, *, check, slab_rule, grow, call, make_outputs):
+    """What `build` here and in margin.py do alike behind `as_edges` (e, er) and their own checks, in the name of `what` around the entry
+    point `entry`.  The module passes, by keyword: check(C, G, E, slab), its check_args; slab_rule(bounds), its choose_slab; grow, by which
+    `slots_needed` grows an edge's y-range; call(front, back, bounds) -> (rc, M), its `call` on front = (points, labels, C, edges,
+    edge_region, G) and back = (slab, slot_cap, *outputs), its own scalars put between them; make_outputs(n, dev), its `outputs`.
+    -> (the output tensors, n, the number of device calls).  The capacity loop is `cellpoints.grow_to_fit`; the outputs are made once."""
+    import torch
+    check(C, G, len(e), 1)
+    p, lab, dev, p_d, lab_d, bounds = cellpoints.resident(points, labels, what, device)
+    n = len(p)
+    if n and np.abs(p).max() >= COORD_LIMIT:
+        raise ValueError(f'{what}: a coordinate lies outside |p| < 2**27')
+    slab = slab_rule(bounds) if slab is None and n else int(slab or 1)
+    check(C, G, len(e), slab)
+    refuse = lambda m: f'{what}: {m} (edge, slab) records, more than 2**28: a larger slab makes them fewer' if m > MAX_SLOTS else None
+    cap = slots_needed(e, bounds, slab, grow) if slot_cap is None else int(slot_cap)
+    if refuse(cap):                                          # the first cap too, before anything more is uploaded
+        raise ValueError(refuse(cap))
+    e_d, er_d = torch.from_numpy(e if len(e) else np.zeros((1, 4), np.int32)).to(dev), torch.from_numpy(er if len(e) else np.zeros(1, np.int32)).to(dev)
+    front, out = (p_d, lab_d, C, e_d[:len(e)], er_d[:len(e)], G), make_outputs(n, dev)
+    out, _, _, calls = cellpoints.grow_to_fit(lambda cap, out: call(front, (slab, cap, *out), bounds), lambda cap: out, cap, entry, what,
+                                              refuse=refuse, unit='records')
+    return out, n, calls
+
+
 def build(points, labels, num_classes, edges, edge_region, G, device=0, slab=None, slot_cap=None, with_calls=False):
     """The census of `points` (int (n, 2) half pixels, see cellpoints.quantize_centres) with `labels` (n,) against the regions on
     cuda:`device`: numpy in, the four results of `regions_reference` out, and the number of device calls behind them when `with_calls`.
     The slab height is `choose_slab` of the points' box unless given; the first call has room for `slots_needed` records -- exactly what
     the device counts -- unless `slot_cap` says otherwise; when the device needs more it says how many and writes nothing, and ONE second
     call has room for exactly that many.  There is no host route: without the library or a GPU this raises."""
-    import torch
     C, G = int(num_classes), int(G)
     e, er = as_edges(edges, edge_region, G)
-    check_args(C, G, len(e))
-    p, lab, dev, p_d, lab_d, bounds = cellpoints.resident(points, labels, 'regions', device)
-    n = len(p)
-    if n and np.abs(p).max() >= COORD_LIMIT:
-        raise ValueError('regions: a coordinate lies outside |p| < 2**27')
-    slab = choose_slab(bounds) if slab is None and n else int(slab or 1)
-    check_args(C, G, len(e), slab)
-    cap, calls = (slots_needed(e, bounds, slab) if slot_cap is None else int(slot_cap)), 1
-    if cap > MAX_SLOTS:
-        raise ValueError(f'regions: {cap} (edge, slab) records, more than 2**28: a larger slab makes them fewer')
-    e_d, er_d = torch.from_numpy(e if len(e) else np.zeros((1, 4), np.int32)).to(dev), torch.from_numpy(er if len(e) else np.zeros(1, np.int32)).to(dev)
-    e_d, er_d = e_d[:len(e)], er_d[:len(e)]
-    out = outputs(n, G, C, dev)
-    rc, m = call(p_d, lab_d, C, e_d, er_d, G, slab, cap, *out, bounds=bounds, device=device)
-    cellpoints.raise_for(rc, 'nuhtc_cell_regions')
-    if m > cap:
-        if m > MAX_SLOTS:
-            raise ValueError(f'regions: {m} (edge, slab) records, more than 2**28: a larger slab makes them fewer')
-        cap, calls = m, 2
-        rc, m = call(p_d, lab_d, C, e_d, er_d, G, slab, cap, *out, bounds=bounds, device=device)
-        cellpoints.raise_for(rc, 'nuhtc_cell_regions')
-        if m != cap:
-            raise RuntimeError(f'nuhtc_cell_regions: {m} records on the second call, {cap} on the first')
+    out, n, calls = build_entry('regions', 'nuhtc_cell_regions', points, labels, C, e, er, G, device, slab, slot_cap,
+                                check=check_args, slab_rule=choose_slab, grow=0, make_outputs=lambda n, dev: outputs(n, G, C, dev),
+                                call=lambda front, back, bounds: call(*front, *back, bounds=bounds, device=device))
     got = (out[0][:n].cpu().numpy(), out[1][:n].cpu().numpy(), out[2][:n].cpu().numpy(), out[3][:G].cpu().numpy())
     return got + (calls,) if with_calls else got
 
@@ -375,13 +388,20 @@ def write_npz(path, nuclei_id, xy, label, region, depth, on_boundary, census, ta
         raise ValueError('write_npz: one region, depth and on_boundary per nucleus, one census row and one area2 per region')
     if order not in ORDERS:
         raise ValueError(f"write_npz: order is 'file' or 'area' (got {order!r})")
-    e, er = as_edges(table.edges, table.edge_region, G, 'write_npz')
-    check_args(census.shape[1], G, len(e))
+    t = table_arrays(table, G)
+    check_args(census.shape[1], G, len(t['edges']))
     d = derive(census, table.area2, depth, head['label'])
     with open(path, 'wb') as f:
-        np.savez(f, **head, region=region, depth=depth, on_boundary=on_boundary, census=census, **d, names=np.asarray(table.names, dtype=np.str_).reshape(-1),
-                 ring_start=np.asarray(table.ring_start, np.int64), edges=e, edge_region=er, area2=np.asarray(table.area2, np.int64), order=np.asarray(order))
+        np.savez(f, **head, region=region, depth=depth, on_boundary=on_boundary, census=census, **d, **t, order=np.asarray(order))
     return path
+
+
+def table_arrays(table, G):
+    """The RegionTable behind a file, for a `write_npz` (here and in margin.py) -> dict in the order of the files' keys: names (G,) str,
+    ring_start int64, edges int32 (E, 4) and edge_region int32 (E,) checked by `as_edges` against G, area2 int64."""
+    e, er = as_edges(table.edges, table.edge_region, G, 'write_npz')
+    return dict(names=np.asarray(table.names, dtype=np.str_).reshape(-1), ring_start=np.asarray(table.ring_start, np.int64), edges=e, edge_region=er,
+                area2=np.asarray(table.area2, np.int64))
 
 
 def read_npz(path):

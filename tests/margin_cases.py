@@ -117,6 +117,16 @@ def staging():
     return _case(p, rng.integers(-1, 5, len(p)), 4, regions, (3, 6, 12, 25, 50))
 
 
+# ---- the walk of a workgroup through its slabs, at ONE slab height
+SLAB_WALK_SLAB = RC.SLAB_WALK_SLAB
+
+
+def slab_walk():
+    """`regions_cases.slab_walk` under thresholds up to R = 20: the records per slab are the census's (no grown y-range reaches another
+    slab), the middle slab of the first workgroup has none, and region 2 is farther than R from every point."""
+    return RC.slab_walk() + (np.asarray([3, 8, 20], np.int32),)
+
+
 # ---- many ties
 def random_lattice(seed, n=2000, regions=10):
     """`regions_cases.random_lattice` (everything on multiples of 4 within a square of 240, labels partly outside the classes) under

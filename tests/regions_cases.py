@@ -154,6 +154,47 @@ def staging():
     return _case(p, rng.integers(0, 4, len(p)), 4, regions)
 
 
+# ---- the walk of a workgroup through its slabs (csrc/celledges.h rg_walk), at ONE slab height
+SLAB_WALK_SLAB = 200
+
+
+def slab_walk():
+    """300 points on a box 1000 x 599 at slab height 200: 100 in slab 0, 60 in slab 1, 140 in slab 2, so the first workgroup of 256 records
+    lies in three slabs and the second one is partial.  Region 0: a square in slab 0 and a zigzag ring of 256 vertices in slab 2; region
+    1: a zigzag ring of 260 vertices inside it; region 2: a rectangle wholly right of the box beside slab 2 (kept for the parity; farther
+    than 20 from every point).  Every edge keeps 30 from the rows of slab 1, which has no edge record at all -- also with the y-ranges
+    grown by 20 (tests/margin_cases.py) -- and the records of slab 2 number 256 + 260 + 4: the region changes at record 256, exactly
+    between two staging passes, and at record 516, inside the last, partial pass."""
+    rng = np.random.default_rng(23)
+    cloud = lambda k, y0, y1: np.stack([rng.integers(0, 1001, k), rng.integers(y0, y1 + 1, k)], 1)
+
+    def ring(k, cy, rx, ry):
+        t = 2 * np.pi * np.arange(k) / k
+        wob = 1 + 0.15 * (np.arange(k) % 2)
+        return np.rint(np.stack([500 + rx * wob * np.cos(t), cy + ry * wob * np.sin(t)], 1)).astype(np.int64).tolist()
+    outer, inner = ring(256, 500, 400, 60), ring(260, 500, 200, 35)
+    on_ring = [outer[0], outer[64], inner[1], inner[131]]                                   # points ON vertices of both rings
+    p = np.concatenate([[[0, 0]], cloud(95, 0, 199), [[400, 40], [600, 150], [400, 95], [503, 150]], cloud(60, 200, 399),
+                        on_ring, cloud(135, 400, 599), [[1000, 599]]], 0)
+    return _case(p, rng.integers(-1, 4, len(p)), 3, [[rect(400, 40, 600, 150), outer], [inner], [rect(1100, 450, 1200, 550)]])
+
+
+def slab_layout(case, slab, grow=0):
+    """What a workgroup walks through, by a direct loop: (the points per slab, and per slab the regions of its edge records in edge
+    order) at slab height `slab` with every edge's y-range grown by `grow`.  For a box small enough that the cell side IS the slab."""
+    p, edges, er = case[0].astype(np.int64), case[3].astype(np.int64), case[4]
+    x_min, y_min, y_max = p[:, 0].min(), p[:, 1].min(), p[:, 1].max()
+    rows = (y_max - y_min) // slab + 1
+    records = [[] for _ in range(rows)]
+    for (ax, ay, bx, by), g in zip(edges.tolist(), er.tolist()):
+        if ax < x_min - grow and bx < x_min - grow:
+            continue
+        for s in range(rows):
+            if max(ay, by) + grow >= y_min + s * slab and min(ay, by) - grow <= min(y_min + (s + 1) * slab - 1, y_max):
+                records[s].append(g)
+    return np.bincount((p[:, 1] - y_min) // slab, minlength=rows).tolist(), records
+
+
 # ---- scale
 def chain(order):
     """The chain of tests/proximity_cases.py (20 000 points 8 apart on the line y = 11) under four regions: a long rectangle, a triangle whose

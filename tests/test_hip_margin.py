@@ -87,6 +87,17 @@ def test_the_designed_sets_reach_what_they_are_for(hip_device, references):
     assert all((q[2] == 0).all() for q in got) and (got[0][4].astype(int) + got[1][4] == 1).all()    # band 0 of both, inside exactly one
 
 
+def test_the_slab_walk_case_equals_the_reference(hip_device):
+    """`margin_cases.slab_walk` at its one slab height: a first workgroup whose records lie in three slabs, the middle one without an edge
+    record, a partial second workgroup, region changes at record 256 of a slab (between two staging passes) and inside its last, partial
+    pass, and a region behind both that is kept for the parity and never near (tests/test_margin_host.py checks that layout).  Every
+    output equals the restatement."""
+    case = MC.slab_walk()
+    got = mg.build(*case, slab=MC.SLAB_WALK_SLAB, with_calls=True)
+    assert got[5] == 1
+    _equal(got[:5], mg.margin_reference(*case), 'slab_walk')
+
+
 def test_census_equals_the_region_census_of_the_device(hip_device):
     for name in ('staging', 'holes_and_nested', 'random_lattice_1', 'around_the_box'):
         case = CASES[name]

@@ -76,6 +76,16 @@ def test_the_designed_sets_reach_what_they_are_for(hip_device):
     assert len(CASES['chain_shuffled'][0]) == 20000 and rg.choose_slab(cellpoints.bounds_of(CASES['chain_shuffled'][0])) == 1
 
 
+def test_the_slab_walk_case_equals_the_reference(hip_device):
+    """`regions_cases.slab_walk` at its one slab height: a first workgroup whose records lie in three slabs, the middle one without an edge
+    record, a partial second workgroup, and region changes at record 256 of a slab (between two staging passes) and inside its last,
+    partial pass (tests/test_regions_host.py checks that layout).  Every output equals the restatement."""
+    case = RC.slab_walk()
+    got = rg.build(*case, slab=RC.SLAB_WALK_SLAB, with_calls=True)
+    assert got[4] == 1
+    _equal(got[:4], rg.regions_reference(*case), 'slab_walk')
+
+
 # ---- 2: the second call
 def test_a_cap_below_the_records_writes_nothing_and_the_second_call_has_room(hip_device, references):
     case = CASES['staging']

@@ -167,6 +167,18 @@ def _slots_loop(edges, bounds, slab, R):
     return total
 
 
+def test_the_slab_walk_case_is_laid_out_as_it_says():
+    case = MC.slab_walk()
+    p, lab, C, edges, er, G, thr = case
+    points, records = MC.RC.slab_layout(case, MC.SLAB_WALK_SLAB, int(thr[-1]))
+    assert points == [100, 60, 140] and [len(r) for r in records] == [4, 0, 256 + 256 + 8]       # as in the census: no grown range reaches slab 1
+    assert records[2] == [0] * 256 + [1] * 260 + [2] * 4 and mg.slots_needed(edges, (0, 0, 1000, 599), MC.SLAB_WALK_SLAB, thr) == 524
+    bc, census, band, band_region, band_inside = mg.margin_reference(*case)
+    assert set(band.tolist()) == {0, 1, 2, 3} and set(band_inside.tolist()) == {0, 1} and set(band_region.tolist()) == {-1, 0, 1}
+    assert bc[:2].sum(axis=(0, 3)).all() and not bc[2].any() and not census[2].any()              # every band on both sides; region 2 is never near
+    assert np.array_equal(census, rg.regions_reference(*case[:6])[3])
+
+
 def test_slots_needed_and_choose_slab():
     for name in ('around_the_box', 'empty_slab', 'staging', 'regimes'):
         case = CASES[name]

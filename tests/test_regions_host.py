@@ -247,6 +247,39 @@ def test_check_args_and_as_edges():
         rg.regions_reference(np.array([[1 << 27, 0]]), [0], 1, e, er, G)
 
 
+def test_the_slab_walk_case_is_laid_out_as_it_says():
+    case = RC.slab_walk()
+    p, lab, C, edges, er, G = case
+    points, records = RC.slab_layout(case, RC.SLAB_WALK_SLAB)
+    assert points == [100, 60, 140] and len(p) == 300                                # records 0 .. 255 lie in three slabs; the second workgroup has 44
+    assert [len(r) for r in records] == [4, 0, 256 + 256 + 8]                       # the middle slab has no edge record at all
+    assert records[2] == [0] * 256 + [1] * 260 + [2] * 4                              # the changes: at record 256, and at 516 inside the last pass
+    assert rg.slots_needed(edges, (0, 0, 1000, 599), RC.SLAB_WALK_SLAB) == 524 and (edges[er == 2][:, [0, 2]] > 1000 + 20).all()
+    region, depth, on, census = rg.regions_reference(*case)
+    assert set(region.tolist()) == {-1, 0, 1} and depth.max() == 2 and on.sum() >= 4 and not census[2].any() and census[0].sum() > census[1].sum() > 0
+
+
+def test_the_record_protocol_on_a_stub_call():
+    """cellpoints.grow_to_fit as regions.build and margin.build run it: their refusal of more than 2**28 records in place of the edge
+    lists' limit, the outputs made once, and the wording of the records."""
+    from nuhtc_amd import cellpoints
+    refuse = lambda m: f'regions: {m} (edge, slab) records, more than 2**28: a larger slab makes them fewer' if m > rg.MAX_SLOTS else None
+    out, log = ['out'], []
+
+    def run(answers, first_cap):
+        answers = list(answers)
+        return cellpoints.grow_to_fit(lambda cap, o: log.append((cap, o)) or answers.pop(0), lambda cap: out, first_cap, 'nuhtc_stub', 'regions',
+                                      refuse=refuse, unit='records')
+    assert run([(0, 7)], 1 << 28) == (out, 7, (), 1) and run([(0, 9), (0, 9)], 3)[3] == 2 and all(o is out for _, o in log)
+    assert run([(0, 1 << 28), (0, 1 << 28)], 5)[1:] == (1 << 28, (), 2)                                  # 2**28 records are not too many
+    del log[:]
+    with pytest.raises(ValueError, match=r'regions: 268435457 \(edge, slab\) records, more than 2\*\*28: a larger slab makes them fewer'):
+        run([(0, (1 << 28) + 1)], 5)
+    assert len(log) == 1                                                                                 # no second call
+    with pytest.raises(RuntimeError, match='nuhtc_stub: 8 records on the second call, 9 on the first'):
+        run([(0, 9), (0, 8)], 3)
+
+
 def test_slots_needed_and_choose_slab():
     e = np.array([[0, -5, 0, 25], [3, 3, 9, 3], [-4, 0, -1, 20], [50, 9, 40, 10], [0, 21, 5, 30], [0, -9, 5, -1]], np.int64)
     # box (0, 0) .. (10, 20), slab 5: rows 0-4, 5-9, 10-14, 15-19, 20.  The first edge meets all five, the second one, the third lies left

@@ -1,5 +1,5 @@
 // Host check of the plain-C++ parts of the margin bands (nuhtc_amd/csrc/cellgrid_host.h: the distance test margin_near with its parts
-// margin_measure / margin_within / margin_mul_wide, the box reject margin_box_near, the record range margin_slab_range, and the limits
+// margin_measure / margin_within / margin_mul_wide, the box reject margin_box_near, the record range edge_slab_range, and the limits
 // margin_thresholds_ok / margin_call_ok), meant to be built with a sanitizer and run on the host -- it never touches a GPU, and the
 // kernel code itself (cellmargin.hip) is NOT sanitized:
 //
@@ -129,11 +129,12 @@ int main() {
       for (int e = 0; e < E; ++e) {
         const int ax = edges[4 * e], ay = edges[4 * e + 1], bx = edges[4 * e + 2], by = edges[4 * e + 3];
         int s0 = -1, s1 = -2;
-        const bool kept = margin_slab_range(ax, ay, bx, by, R, x_min, y_min, y_max, side, &s0, &s1);
+        const bool kept = edge_slab_range(ax, ay, bx, by, R, x_min, y_min, y_max, side, &s0, &s1);
         const long long ylo = (long long)std::min(ay, by) - R, yhi = (long long)std::max(ay, by) + R;
-        if (R == 0) {
-          int t0 = -1, t1 = -2;
-          const bool k0 = region_slab_range(ax, ay, bx, by, x_min, y_min, y_max, side, &t0, &t1);
+        if (R == 0) {                                     // the census's range, written without R: the closed y-range clipped to the box
+          const int lo = std::min(ay, by), hi = std::max(ay, by);
+          const bool k0 = hi >= y_min && lo <= y_max && !(ax < x_min && bx < x_min);
+          const int t0 = (std::max(lo, y_min) - y_min) / side, t1 = (std::min(hi, y_max) - y_min) / side;
           if (k0 != kept || (kept && (t0 != s0 || t1 != s1))) { std::printf("FAIL R == 0 is not the census's range, rep %d\n", rep); ++bad; }
         }
         for (int s = 0; s < ncy; ++s) {

@@ -1,5 +1,5 @@
 // Host check of the plain-C++ parts of the region census (nuhtc_amd/csrc/cellgrid_host.h: the crossing test region_crossed, the boundary
-// test region_on_edge, the slab range of an edge region_slab_range, and the limits region_edge_ok / region_call_ok), meant to be built
+// test region_on_edge, the slab range of an edge edge_slab_range at R = 0, and the limits region_edge_ok / region_call_ok), meant to be built
 // with a sanitizer and run on the host -- it never touches a GPU, and the kernel code itself (cellregion.hip) is NOT sanitized:
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I nuhtc_amd/csrc tools/dev/cellregion_host_check.cpp \
@@ -92,7 +92,7 @@ int main() {
     for (int e = 0; e < E; ++e) {
       const int ax = edges[4 * e], ay = edges[4 * e + 1], bx = edges[4 * e + 2], by = edges[4 * e + 3];
       int s0 = -1, s1 = -2;
-      const bool kept = region_slab_range(ax, ay, bx, by, x_min, y_min, y_max, side, &s0, &s1);
+      const bool kept = edge_slab_range(ax, ay, bx, by, 0, x_min, y_min, y_max, side, &s0, &s1);
       const int ylo = std::min(ay, by), yhi = std::max(ay, by);
       for (int s = 0; s < ncy; ++s) {
         const long long r0 = (long long)y_min + (long long)s * side, r1 = std::min<long long>(r0 + side - 1, y_max);
