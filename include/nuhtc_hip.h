@@ -1269,6 +1269,41 @@ int nuhtc_cell_enrichment(int device, const int32_t* points, const int32_t* labe
  * 0 <= n <= 2^24, 1 <= p <= 1024; NUHTC_E_INVALID otherwise or when out is null with n > 0. */
 int nuhtc_enrichment_permutation(int64_t n, uint32_t seed, int p, int32_t* out);
 
+/* Cellular neighbourhoods of a slide (csrc/cellhood.hip; nuhtc_amd/neighbourhoods.py holds the definition and the numpy restatement
+ * `neighbourhoods_reference`): the class composition of every nucleus's window -- itself and the neighbours nuhtc_cell_graph listed --
+ * clustered by k-means into num_types neighbourhood types, in integers throughout.  Not in the reference.  Engine-free like the outline
+ * call: it takes the tensors nuhtc_cell_graph took and left on the device and needs no points and no bounds; every pointer but `counts`
+ * is device memory of `device`, the call allocates and frees its own scratch, runs on `stream` and synchronises it (once per batch of
+ * 8 iterations, once at the end; with given centres once more at the start) before returning.  nuhtc_config is unchanged (no ABI bump).
+ *   neighbors [n][k] int32: row indices or -1, as nuhtc_cell_graph wrote them.  labels [n] int32.  0 <= n <= 2^24, 1 <= k <= 32.
+ *   num_classes C: 1 .. 14.  num_types K: 1 .. 32.  seed: any 32-bit value.  max_iter: 1 .. 1000.  centres_given: 0 or 1.
+ *   window [n][C] int32: w[i][c] = the rows of label c among row i and its listed neighbours; a label outside [0, C) is counted nowhere.
+ * centres_given == 0: k-means++ seeding in exact integers (draws u_j from the murmur3 finaliser; row_0 = u_0 mod n; then the smallest row
+ * whose inclusive prefix sum of the squared distances to the nearest chosen window exceeds u_j mod T, row_0 again when T == 0;
+ * centre = 1024 * window), then Lloyd on the fixed-point centres: argmin with ties to the smaller type, stop at the first iteration whose
+ * assignment repeats the one before (converged) or at max_iter, else centre = floor((2048 sum + members) / (2 members)) for every type
+ * with members.  centres_given == 1: centre_q holds the centres on entry, every entry 0 .. 34000; one assignment, no update.
+ *   hood [n] int32: the final type of each row.  centre_q [K][C] int32 (in/out): the centres the final assignment was made against.
+ *   centre_sum [K][C] int64, centre_n [K] int64: the window sums and members of that assignment.  seed_rows [K] int32: the seeding rows,
+ *     -1 with given centres.
+ *   counts: HOST memory, int64 [3] = n_iter (the iteration that stopped; 0 with given centres), converged (0 / 1), inertia (the sum over
+ *     the rows of the squared fixed-point distance to the row's centre), written on success only.
+ * The result is a pure function of the input, the ORDER of the rows included: bitwise the same on every call.  n == 0 writes centre_q
+ * (the given centres, or zeros), zero sums, seed_rows = -1 and counts = 0, 1, 0.
+ * NUHTC_E_INVALID, before anything is launched and with the outputs untouched: n, k, num_classes, num_types, max_iter or centres_given
+ * out of range, a null pointer (neighbors, labels, window and hood only with n > 0), a given centre outside 0 .. 34000.
+ * NUHTC_E_INVALID after the first kernels, the outputs still untouched: a neighbour index outside -1 .. n - 1. */
+int nuhtc_cell_neighbourhoods(int device, const int32_t* neighbors, const int32_t* labels, int64_t n, int k, int num_classes, int num_types,
+                              uint32_t seed, int max_iter, int centres_given, int32_t* centre_q, int32_t* window, int32_t* hood,
+                              int64_t* centre_sum, int64_t* centre_n, int32_t* seed_rows, int64_t* counts, void* stream);
+/* The rules of the neighbourhoods alone, on the HOST (no GPU is touched), through the same header the kernels use (csrc/cellhood_host.h).
+ * nuhtc_neighbourhood_draws: out[j] = u_j, j < num_types (1 .. 32).  nuhtc_neighbourhood_rule: what == 0, the pick: *out = the smallest
+ * i < x whose inclusive prefix a[i] exceeds t = y (0 <= y < a[x - 1]); what == 1, the rounding: *out = floor((2048 x + y) / (2 y)), z when
+ * y == 0; what == 2, the distance: *out = sum_c (1024 a[c] - b[c])^2 over x == y <= 14 classes, a[c] 0 .. 33, b[c] 0 .. 34000.
+ * NUHTC_E_INVALID for anything else. */
+int nuhtc_neighbourhood_draws(uint32_t seed, int num_types, uint64_t* out);
+int nuhtc_neighbourhood_rule(int what, const int64_t* a, const int64_t* b, int64_t x, int64_t y, int64_t z, int64_t* out);
+
 /* Per-kernel timing with HIP events recorded on the launch stream (process-wide switch; off by default).
  * nuhtc_profile_read synchronises the device and writes one text line per kernel tag,
  * "tag launches total_ms algorithmic_flops algorithmic_bytes", then resets the records. */

@@ -159,7 +159,8 @@ EXPORTS = ['nuhtc_default_config', 'nuhtc_create', 'nuhtc_destroy', 'nuhtc_last_
            'nuhtc_nucleus_texture', 'nuhtc_op_nucleus_texture', 'nuhtc_op_nucleus_gradient', 'nuhtc_op_nucleus_shape', 'nuhtc_op_ring_fill', 'nuhtc_op_frame_gather', 'nuhtc_op_ring_fsd',
            'nuhtc_op_patch_embed', 'nuhtc_op_layernorm', 'nuhtc_op_merge_ln', 'nuhtc_op_fpn_lateral', 'nuhtc_op_sem_fuse', 'nuhtc_op_pointwise64',
            'nuhtc_op_fpn_mean_pool', 'nuhtc_cell_spatial', 'nuhtc_cell_clusters', 'nuhtc_cell_mst', 'nuhtc_cell_proximity', 'nuhtc_cell_density', 'nuhtc_cell_regions', 'nuhtc_cell_margin',
-           'nuhtc_cell_enrichment', 'nuhtc_enrichment_permutation', 'nuhtc_cell_territory', 'nuhtc_territory_adjacency', 'nuhtc_cell_alpha', 'nuhtc_alpha_outline']
+           'nuhtc_cell_enrichment', 'nuhtc_enrichment_permutation', 'nuhtc_cell_territory', 'nuhtc_territory_adjacency', 'nuhtc_cell_alpha', 'nuhtc_alpha_outline',
+           'nuhtc_cell_neighbourhoods', 'nuhtc_neighbourhood_draws', 'nuhtc_neighbourhood_rule']
 
 _lib = None
 
@@ -258,6 +259,9 @@ def load():
                                       ci, ci, ci, ci, vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int64), vp]
     lib.nuhtc_cell_enrichment.argtypes = [ci, vp, vp, ctypes.c_int64, ci, ci, ci, ctypes.c_uint32, ci, ci, ci, ci, vp, vp, vp, vp]
     lib.nuhtc_enrichment_permutation.argtypes = [ctypes.c_int64, ctypes.c_uint32, ci, vp]
+    lib.nuhtc_cell_neighbourhoods.argtypes = [ci, vp, vp, ctypes.c_int64, ci, ci, ci, ctypes.c_uint32, ci, ci, vp, vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int64), vp]
+    lib.nuhtc_neighbourhood_draws.argtypes = [ctypes.c_uint32, ci, vp]
+    lib.nuhtc_neighbourhood_rule.argtypes = [ci, vp, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
     lib.nuhtc_nucleus_morph.argtypes = [vp, ctypes.POINTER(Dets), ci, vp, ci, vp, i4, vp, vp, ci, vp, vp, vp]
     lib.nuhtc_op_nucleus_morph.argtypes = [vp, vp, ci, vp, i4, ci, vp, ci, ci, ci, vp, vp, ci, vp, vp, vp]
     lib.nuhtc_nucleus_texture.argtypes = [vp, ctypes.POINTER(Dets), ci, vp, ci, vp, i4, vp, vp, ci, vp, vp]

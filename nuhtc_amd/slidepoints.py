@@ -1,5 +1,5 @@
 """The per-slide point analyses of the slide path as ONE table: which flag of tools/infer_wsi.py selects each, how its arguments become
-the parameters of its module (cellgraph, spatial, clusters, mst, proximity, density, territory, adjacency, alphacomplex, outline, enrichment, regions, margin: they hold the definitions), which file it writes
+the parameters of its module (cellgraph, spatial, clusters, mst, proximity, density, territory, adjacency, alphacomplex, outline, neighbourhoods, enrichment, regions, margin: they hold the definitions), which file it writes
 beside the documents and what the closing message says of it.  cellpoints.py is what the modules share and is imported by them; this
 module imports them, one at a time and only when its flag is given.
 
@@ -29,8 +29,14 @@ the columns of ANALYSES and take no second input and no window.
 
 OF_THE_OUTLINES, directly behind OF_THE_CIRCLES, holds the analyses that close those circles' triangles into shapes -- outline.py: the
 rings and the components of the alpha complex, written as an .npz and, beside it, as a GeoJSON of regions that a later run reads with
---nuclei-regions or --nuclei-margin.  Its rows have the columns of ANALYSES and take no second input and no window.  `select` visits
-ANALYSES, OF_THE_PLANE, OF_THE_BORDERS, OF_THE_CIRCLES, OF_THE_OUTLINES, AGAINST_CHANCE and WITH_INPUT in that order."""
+--nuclei-regions or --nuclei-margin.  Its rows have the columns of ANALYSES and take no second input and no window.
+
+OF_THE_COMPANY, directly behind OF_THE_OUTLINES, holds the analyses that ask what company each of the same rows keeps --
+neighbourhoods.py: the class composition of every nucleus's window of nearest neighbours, clustered into neighbourhood types.  Its rows
+have the columns of ANALYSES and take no second input and no window; the centres of an earlier run, when given, are read while the
+arguments are checked, and their class count is held against the model's only in `build`, so `run` reports that refusal in the flag's
+name too.  `select` visits ANALYSES, OF_THE_PLANE, OF_THE_BORDERS, OF_THE_CIRCLES, OF_THE_OUTLINES, OF_THE_COMPANY, AGAINST_CHANCE and
+WITH_INPUT in that order."""
 import importlib
 import os
 from collections import namedtuple
@@ -168,6 +174,30 @@ OF_THE_OUTLINES = (
 )
 
 
+def _neighbourhoods_params(m, a):
+    given = a.neighbourhood_centres
+    centres = m.read_centres(given, k=a.neighbourhood_k, radius_px=a.neighbourhood_radius) if given else None
+    types = len(centres) if given else a.neighbourhood_types               # given centres bring their own number of types
+    return (a.neighbourhood_radius, a.neighbourhood_k, types, a.neighbourhood_seed, a.neighbourhood_iters, centres)
+
+
+def _neighbourhoods_said(m, found, p):
+    hood, centre_sum, centre_n, n_iter, converged = found[1], found[3], found[4], found[7], found[8]
+    used, top = int((centre_n > 0).sum()), int(centre_n.argmax())
+    how = 'assigned to given centres' if p[5] is not None else f"{n_iter} iterations, {'converged' if converged else 'not converged'}; seed {p[3]}"
+    largest = (f'the largest, type {top}, holds {int(centre_n[top])} nuclei around class {int(centre_sum[top].argmax())}' if used else 'no nuclei')
+    return f'{used} of {len(centre_n)} neighbourhood types in use ({how}; k {p[1]}, {p[0]:g} px); {largest}'
+
+
+OF_THE_COMPANY = (
+    _analysis('neighbourhoods', 'neighbourhoods',                     # what company each of the same rows keeps: k-means of the kNN windows' class counts
+              _neighbourhoods_params,
+              lambda m, p: m.check_args(1, _half(p[0]), *p[1:5]),
+              lambda m, path, head, found, C, p, ctx: m.write_npz(path, *head, *found, radius_px=p[0], k=p[1], seed=p[3], max_iter=p[4]),
+              _neighbourhoods_said),
+)
+
+
 def _enrichment_said(m, found, p):
     obs, perm, cn = found
     z = m.derive(obs, perm)['z']
@@ -220,11 +250,11 @@ def _build(an, m, pts, labels, num_classes, params, name, device):
 
 def select(args, need_gpu=True):
     """The parsed arguments of tools/infer_wsi.py -> the selection: ((analysis, params), ..) of the flags given, in the order of ANALYSES, OF_THE_PLANE,
-    OF_THE_BORDERS, OF_THE_CIRCLES, OF_THE_OUTLINES, AGAINST_CHANCE and WITH_INPUT.
+    OF_THE_BORDERS, OF_THE_CIRCLES, OF_THE_OUTLINES, OF_THE_COMPANY, AGAINST_CHANCE and WITH_INPUT.
     SystemExit in the name of the flag when its arguments are unusable and then, with need_gpu, when no GPU is visible.  A flag the
     namespace does not hold is not given."""
     chosen = []
-    for an in ANALYSES + OF_THE_PLANE + OF_THE_BORDERS + OF_THE_CIRCLES + OF_THE_OUTLINES + AGAINST_CHANCE + WITH_INPUT:
+    for an in ANALYSES + OF_THE_PLANE + OF_THE_BORDERS + OF_THE_CIRCLES + OF_THE_OUTLINES + OF_THE_COMPANY + AGAINST_CHANCE + WITH_INPUT:
         if not getattr(args, an.cli, False):
             continue
         m = module_of(an)
@@ -252,7 +282,7 @@ def run(selection, rows, boxes, labels, num_classes, out_dir, name, device, cont
         try:
             found = _build(an, m, pts, labels, num_classes, params, name, device)
         except ValueError as e:
-            if an not in OF_THE_PLANE + OF_THE_BORDERS:
+            if an not in OF_THE_PLANE + OF_THE_BORDERS + OF_THE_COMPANY:
                 raise
             raise SystemExit(f'{an.flag}: {e}')
         if found is None:

@@ -118,6 +118,19 @@ Output (like the reference, :659-693), for every detection that survives the per
                   --outline-min-nuclei nuclei (3 by default), outer ring first, in the form --nuclei-regions and --nuclei-margin read in a
                   LATER run.  Rings that touch themselves at a pinch vertex are written as they are.  Every other file is the same bytes
                   with and without the flag.  There is no route without a GPU.
+  --nuclei-neighbourhoods: (not in the reference) <id>_nuclei_neighbourhoods.npz beside the documents, from the same rows as --nuclei-graph:
+                  what kind of tissue each nucleus sits in -- the cellular-neighbourhood analysis of CODEX / histoCAT / squidpy.  The class
+                  counts of every nucleus's window (itself and its --neighbourhood-k nearest neighbours within --neighbourhood-radius px;
+                  10 and 64 by default) are clustered by k-means into --neighbourhood-types types (8 by default; k-means++ from
+                  --neighbourhood-seed, at most --neighbourhood-iters Lloyd iterations, 100 by default), all in integers on rank 0's GPU
+                  after the gather (nuhtc_amd/neighbourhoods.py), so the file is a pure function of the rows IN THEIR ORDER: `window`
+                  int32 (n, C), `hood` (the type of each nucleus), `centre_q` (fixed point, 1024 = one nucleus), `centre_sum`, `centre_n`,
+                  `seed_rows`, `inertia`, `n_iter`, `converged`, the derived `composition`, `fraction`, `enrichment_log2`,
+                  `hood_class_count`, `hood_size`, `order_by_size`, `inertia_per_nucleus`, and `radius_px`, `k`, `types`, `seed`,
+                  `max_iter`, `centres_given`.  --neighbourhood-centres FILE.npz assigns against the centres of an earlier run's file
+                  without fitting (its k, radius and class count must be this run's; its number of types is taken): types defined on
+                  one slide, applied to a cohort.  No radius windows, no choice of K, no restarts.  Every other file is the same bytes
+                  with and without the flag.  There is no route without a GPU.
   --nuclei-enrichment: (not in the reference) <id>_nuclei_enrichment.npz beside the documents, from the same rows as --nuclei-graph: whether
                   nuclei of one class lie next to nuclei of another more often than chance -- the neighbourhood-enrichment permutation
                   test (histoCAT, squidpy's nhood_enrichment).  The contacts (ordered pairs at most --enrichment-radius px apart, 64 by
@@ -297,6 +310,21 @@ def build_parser():
                    help="--nuclei-outline over all nuclei ('any') or only among nuclei of the same label ('class')")
     p.add_argument('--outline-min-nuclei', type=int, default=3, dest='outline_min_nuclei',
                    help='components of --nuclei-outline with fewer nuclei are left out of the GeoJSON (default 3; the .npz holds them all)')
+    p.add_argument('--nuclei-neighbourhoods', action='store_true', dest='nuclei_neighbourhoods',
+                   help='also write <id>_nuclei_neighbourhoods.npz: the class counts of every written nucleus\'s window of nearest neighbours, clustered '
+                        'by integer k-means into neighbourhood types (the cellular-neighbourhood analysis), on the GPU; from the rows of --nuclei-graph')
+    p.add_argument('--neighbourhood-k', type=int, default=10, dest='neighbourhood_k',
+                   help='neighbours in the window of --nuclei-neighbourhoods beside the nucleus itself, 1..32 (default 10)')
+    p.add_argument('--neighbourhood-radius', type=float, default=64.0, dest='neighbourhood_radius',
+                   help='radius of that window in slide px, a multiple of 0.5 up to 8192 (default 64 px: 16 um at 40x)')
+    p.add_argument('--neighbourhood-types', type=int, default=8, dest='neighbourhood_types',
+                   help='neighbourhood types K of --nuclei-neighbourhoods, 1..32 (default 8)')
+    p.add_argument('--neighbourhood-seed', type=int, default=0, dest='neighbourhood_seed',
+                   help='seed of the k-means++ seeding of --nuclei-neighbourhoods, 0..2**32-1 (default 0)')
+    p.add_argument('--neighbourhood-iters', type=int, default=100, dest='neighbourhood_iters',
+                   help='most Lloyd iterations of --nuclei-neighbourhoods, 1..1000 (default 100)')
+    p.add_argument('--neighbourhood-centres', default=None, dest='neighbourhood_centres', metavar='FILE.npz',
+                   help='assign against the centres of an earlier <id>_nuclei_neighbourhoods.npz instead of fitting (same k, radius and classes)')
     p.add_argument('--nuclei-enrichment', action='store_true', dest='nuclei_enrichment',
                    help='also write <id>_nuclei_enrichment.npz: the contacts of the written nuclei by class pair, observed and under label permutations, '
                         'with z-scores and empirical p-values (the neighbourhood-enrichment test), counted on the GPU; from the rows of --nuclei-graph')
