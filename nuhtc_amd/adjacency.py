@@ -39,7 +39,7 @@ keys): the oracle the device result must EQUAL.  `derive` makes the float64 side
 Out of scope: 8-adjacency; the exact Delaunay triangulation and its triangles; the edges a window cuts off."""
 import numpy as np
 
-from . import cellpoints, territory
+from . import cellpoints, density, territory
 from .cellpoints import COORD_LIMIT, MAX_CLASSES, MAX_POINTS, MAX_R, centres, half_pixel_radius, quantize_centres  # noqa: F401 (re-exported)
 from .territory import MAX_PITCH, MAX_SITES, window  # noqa: F401 (the lattice, the cap and the default window are territory's)
 
@@ -50,7 +50,7 @@ NPZ_KEYS = ('nuclei_id', 'xy', 'label') + INT_NAMES + territory.INT_NAMES + DERI
 
 
 def check_args(num_classes, r, s, win=None):
-    """territory.check_args: num_classes 1..14, r 1..16384 and s 1..2**20 half pixels and, when given, the window: ValueError otherwise."""
+    """territory.check_args (density.check_lattice with territory's name and cap): ValueError otherwise."""
     territory.check_args(num_classes, r, s, win)
 
 
@@ -121,19 +121,7 @@ def build(points, labels, num_classes, reach_px, pitch_px, win=None, device=0, w
     is never copied off it), then the graph from the map: the first call has room for `first_edge_cap(n)` edges, and when there are more the
     device says how many and ONE second call has room for exactly that many.  Without `win` the window is territory's default one;
     ValueError when it exceeds 2**28 sites.  There is no host route: without the library or a GPU this raises."""
-    p, lab = cellpoints.as_points(points, labels, 'adjacency')
-    n, C, r, s = len(p), int(num_classes), half_pixel_radius(reach_px), half_pixel_radius(pitch_px)
-    if n > MAX_POINTS:
-        raise ValueError(f'adjacency: at most 2**24 points (got {n})')
-    check_args(C, r, s)
-    if n and np.abs(p).max() >= COORD_LIMIT:
-        raise ValueError('adjacency: a coordinate lies outside |p| < 2**27')
-    if win is None:
-        win = window(cellpoints.bounds_of(p), r, s) if n else (0, 0, 1, 1)
-        win = (win[0], win[1], max(win[2], 1), max(win[3], 1))
-    win = tuple(int(v) for v in win)
-    check_args(C, r, s, win)
-    dev, p_d, lab_d, bounds = cellpoints.upload(p, lab, device)
+    n, C, r, s, win, dev, p_d, lab_d, bounds = density.lattice_points('adjacency', check_args, points, labels, num_classes, reach_px, pitch_px, win, device)
     terr = territory.outputs(n, C, win, dev)
     cellpoints.raise_for(territory.call(p_d, lab_d, C, r, s, win, *terr, bounds=bounds, device=device), 'nuhtc_cell_territory')
     owner = terr[0]

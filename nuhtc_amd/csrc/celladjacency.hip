@@ -44,7 +44,7 @@
 // registers allow 8 waves per SIMD in all of them.
 //
 // Everything that decides an index or a limit -- the key and its halves, the slot hash, the slot count from M, the argument check, the
-// owner check and the pairs of a site at the window's edge (cellgrid_host.h) -- is plain C++, and tools/dev/celladjacency_host_check.cpp
+// owner check, the site of a thread (site_uv) and the pairs of a site at the window's edge (cellgrid_host.h) -- is plain C++, and tools/dev/celladjacency_host_check.cpp
 // runs exactly those functions on the host under -fsanitize=address,undefined.  The kernel code itself is not sanitized.
 //
 // MEASURED on one MI355X (tools/bench_adjacency.py -> profiles/cell_adjacency.json; 500 000 centres on a 36 000-px square, reach 64 px,
@@ -67,11 +67,11 @@
 #include <cstring>
 #include <vector>
 
-#include "cellbin.h"
+#include "cellsites.h"
 
 namespace {
 
-constexpr int ADJ_NT = DENS_TILE * DENS_TILE;           // 256 sites, one thread each
+constexpr int ADJ_NT = SITE_NT;                         // 256 sites, one thread each
 constexpr int ADJ_COUNTERS = 256;                       // words the workgroups spread their record counts over; the host sums them
 constexpr int ADJ_COUNTER_STRIDE = 16;                  // in 64-bit words: 128 B apart
 
@@ -145,7 +145,8 @@ __global__ __launch_bounds__(ADJ_NT) void adj_tile_kernel(AdjArgs a) {
   __shared__ unsigned cnt[INSERT ? ADJ_TILE_SLOTS : 1];
 #endif
   const int tid = threadIdx.x, W = a.W, H = a.H, n = a.n;
-  const int u = (int)(blockIdx.x % a.tiles_x) * DENS_TILE + (tid & (DENS_TILE - 1)), v = (int)(blockIdx.x / a.tiles_x) * DENS_TILE + tid / DENS_TILE;
+  int u, v;
+  site_uv(blockIdx.x, a.tiles_x, tid, &u, &v);
   const bool in = u < W && v < H;
   int me = -1, right = -1, lower = -1;                   // a pair that does not exist: (-1, -1), no edge
   if (in) {
@@ -233,10 +234,9 @@ extern "C" int nuhtc_territory_adjacency(int device, const int32_t* owner, int W
   AdjArgs a;
   memset(&a, 0, sizeof(a));
   a.owner = owner; a.W = W; a.H = H; a.n = (int)n; a.cap = edge_cap;
-  a.tiles_x = (W + DENS_TILE - 1) / DENS_TILE;
+  a.tiles_x = (W + SITE_TILE - 1) / SITE_TILE;
   a.edges = edges; a.shared = edge_shared; a.degree = degree;
-  // H = 1 gives the most tiles: (2^28 + 15) / 16 < 2^25
-  const unsigned tiles = (unsigned)a.tiles_x * (unsigned)((H + DENS_TILE - 1) / DENS_TILE);
+  const unsigned tiles = site_tiles(W, H);
   DevScratch tmp;      // every temporary of the call, freed on the way out
   constexpr size_t counter_words = (size_t)ADJ_COUNTERS * ADJ_COUNTER_STRIDE;
   a.records = tmp.alloc<unsigned long long>(counter_words * sizeof(unsigned long long)); a.bad = tmp.alloc<int>(sizeof(int));

@@ -1,5 +1,5 @@
 // What the per-slide analyses of half-pixel points share on the device (gfx950) -- the cell graph (cellgraph.hip), the pair histograms
-// (cellspatial.hip), the clusters (cellcluster.hip), the minimum spanning forest (cellmst.hip), the proximity graphs (cellprox.hip), the alpha complex (cellalpha.hip), the density rasters (celldensity.hip), the territories (cellterritory.hip), the region census and the margin bands (cellregion.hip, cellmargin.hip: their edges are binned by celledges.h, on this scan) and the neighbourhood enrichment (cellenrich.hip); celledgelist.h holds the count / scan / emit / place frame of the analyses that return an edge list (cellprox.hip, cellalpha.hip), celladjacency.hip uses the scan alone; cellgrid_host.h holds the plain-C++ side (limits, geometry, keys, pair distance).
+// (cellspatial.hip), the clusters (cellcluster.hip), the minimum spanning forest (cellmst.hip), the proximity graphs (cellprox.hip), the alpha complex (cellalpha.hip), the density rasters (celldensity.hip), the territories (cellterritory.hip), the region census and the margin bands (cellregion.hip, cellmargin.hip: their edges are binned by celledges.h, on this scan) and the neighbourhood enrichment (cellenrich.hip); cellsites.h holds the lattice and the staged / direct sweep of the site rasters (celldensity.hip, cellterritory.hip), celledges.h the slab walk of the analyses against polygon edges (cellregion.hip, cellmargin.hip), celledgelist.h holds the count / scan / emit / place frame of the analyses that return an edge list (cellprox.hip, cellalpha.hip), celladjacency.hip uses the scan alone; cellgrid_host.h holds the plain-C++ side (limits, geometry, keys, pair distance).
 //   binning   a histogram of the points per key (atomics), an exclusive scan of the keys, and a scatter of (x, y, label, index) records
 //             into key order.  A key is a cell, or a (cell, class) pair (cell_key).  The order of the records INSIDE a key is atomic
 //             arrival order; nothing downstream may depend on it.  A point outside the stated bounding box raises the flag and is left

@@ -1,5 +1,5 @@
 // The uniform grid over half-pixel points that the per-slide analyses share (cellbin.h; cellgraph.hip, cellspatial.hip, cellcluster.hip,
-// cellmst.hip, cellprox.hip, celldensity.hip, cellterritory.hip, celladjacency.hip, cellalpha.hip, celloutline.hip, cellregion.hip, cellmargin.hip, cellenrich.hip; celledgelist.h, the frame of the edge-list analyses): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
+// cellmst.hip, cellprox.hip, celldensity.hip, cellterritory.hip, celladjacency.hip, cellalpha.hip, celloutline.hip, cellregion.hip, cellmargin.hip, cellenrich.hip; celledgelist.h, the frame of the edge-list analyses; cellsites.h, the lattice and the sweep of the site rasters): the parts that are plain C++ and run on the host as well -- the limits, the grid geometry over the bounding box, the cell
 // and the (cell, class) key of a point, the squared distance of a pair within reach, the rank of an edge in its row's segment, and the edge key of the spanning forest.  Header-only,
 // so a host program can exercise them under a sanitizer (tools/dev/cellspatial_host_check.cpp, tools/dev/cellmst_host_check.cpp, tools/dev/cellprox_host_check.cpp,
 // tools/dev/celldensity_host_check.cpp, tools/dev/cellregion_host_check.cpp, tools/dev/cellmargin_host_check.cpp, tools/dev/cellenrich_host_check.cpp, tools/dev/cellterritory_host_check.cpp, tools/dev/celladjacency_host_check.cpp, tools/dev/cellalpha_host_check.cpp, tools/dev/celloutline_host_check.cpp); the kernels call the same functions.  nuhtc_amd/cellpoints.py states the same limits.
@@ -90,15 +90,15 @@ CELL_HD inline bool prox_rng_blocked(int dik, int djk, int dij) { return djk >= 
 // an edge's d2 (<= 2^28) and its RNG bit in one int while the segments are put in order
 constexpr int PROX_RNG_BIT = 1 << 30;
 
-// ---- the density rasters (celldensity.hip): the queries are lattice SITES q = (g * s), not points, and a site may lie outside the box on
+// ---- the site rasters (cellsites.h; celldensity.hip first): the queries are lattice SITES q = (g * s), not points, and a site may lie outside the box on
 // every side.  The bit budget, stated here once: a site has |q| < 2^28 (checked on the host in 64 bits) and a point |p| < 2^27, so
 // |q - p| < 2^28 + 2^27 < 2^31 and the differences are exact int32 -- the same holds for q - x_min and for q +- h - x_min (h <= 2^14).
 // The box test against h comes BEFORE the products (cell_pair_d2), so d2 <= h * h <= 2^28 and each term h * h - d2 lies in 0 .. 2^28.
 // With n <= 2^24 points a weight stays below 2^24 * 2^28 = 2^52: `weight` is int64; `count` <= 2^24 is int32.
-constexpr int DENS_SITE_LIMIT = 1 << 28;               // |g * s| < 2^28 half pixels
-constexpr int DENS_MAX_PITCH = 1 << 20;
+constexpr int SITE_LIMIT = 1 << 28;                    // |g * s| < 2^28 half pixels
+constexpr int SITE_MAX_PITCH = 1 << 20;
+constexpr int SITE_TILE = 16;                          // a workgroup owns SITE_TILE x SITE_TILE sites
 constexpr int64_t DENS_MAX_SITES = (int64_t)1 << 24;
-constexpr int DENS_TILE = 16;                          // a workgroup owns DENS_TILE x DENS_TILE sites
 
 // floor(a / b) for b > 0 (the / of C++ truncates toward zero, which is not the floor left of the origin)
 CELL_HD inline int cell_floor_div(int a, int b) { return a / b - (a % b < 0); }
@@ -116,6 +116,26 @@ CELL_HD inline void site_cell_range(int lo, int hi, int origin, int side, int nc
   *c1 = b < nc - 1 ? b : nc - 1;
 }
 
+// the cells a footprint x_lo .. x_hi, y_lo .. y_hi can touch on a grid of ncx x ncy cells that starts at (x_min, y_min): the rows cy0 .. cy1 and
+// in each the cells cx0 .. cx1.  A footprint beside the grid has NO ROW (cy0 > cy1), whichever axis it misses the grid on: the one loop
+// over the rows then reads nothing, and cx0 .. cx1 is never turned into an index.  The one place this rule is written: both forms of
+// site_sweep (cellsites.h) and the walk of the host checks (tools/dev/cellsites_check.h) call it.
+struct SiteCells { int cx0, cx1, cy0, cy1; };
+CELL_HD inline SiteCells site_cells(int x_lo, int x_hi, int y_lo, int y_hi, int x_min, int y_min, int side, int ncx, int ncy) {
+  SiteCells c;
+  site_cell_range(x_lo, x_hi, x_min, side, ncx, &c.cx0, &c.cx1);
+  site_cell_range(y_lo, y_hi, y_min, side, ncy, &c.cy0, &c.cy1);
+  if (c.cx0 > c.cx1) c.cy1 = c.cy0 - 1;
+  return c;
+}
+
+// the site (u, v) that thread tid of tile `tile` takes in a window with tiles_x tiles to a row: tiles in row-major order, and so are the
+// 16 x 16 sites of a tile.  (u, v) may lie past the window's edge in the last tile of a row or column.
+CELL_HD inline void site_uv(unsigned tile, int tiles_x, int tid, int* u, int* v) {
+  *u = (int)(tile % tiles_x) * SITE_TILE + (tid & (SITE_TILE - 1));
+  *v = (int)(tile / tiles_x) * SITE_TILE + tid / SITE_TILE;
+}
+
 // what a point at (dx, dy) from a site adds to the site's weight, h * h - d2, or -1 when it is out of reach (h2 = h * h; inclusive: a
 // point exactly at distance h adds 0 and is counted)
 CELL_HD inline int dens_term(int dx, int dy, int h, int h2) {
@@ -123,17 +143,18 @@ CELL_HD inline int dens_term(int dx, int dy, int h, int h2) {
   return d2 < 0 ? -1 : h2 - d2;
 }
 
-// which kernel takes the sites.  A tile of 16 x 16 sites staged through LDS tests every record of its footprint, about 15 s + 2 h + side
-// along each axis, against every site; a site on its own tests the records of its (at most) three cells, about 2 h + side along each axis.
-// The staged test is cheaper (a broadcast LDS read against a global load), the direct one tests fewer records as soon as the sites of a
-// tile are far apart: the tile is taken while its footprint is at most twice as long as one site's (measured on both sides of the rule:
-// profiles/cell_density.json).
-CELL_HD inline bool dens_route_staged(int s, int h, int side) { return (long long)(DENS_TILE - 1) * s <= 2LL * h + side; }
+// which kernel takes the sites, for every raster on this lattice.  A tile of 16 x 16 sites staged through LDS tests every record of its
+// footprint, about 15 s + 2 r + side along each axis, against every site; a site on its own tests the records of its (at most) three cells,
+// about 2 r + side along each axis.  The staged test is cheaper (a broadcast LDS read against a global load), the direct one tests fewer
+// records as soon as the sites of a tile are far apart: the tile is taken while its footprint is at most twice as long as one site's
+// (measured on both sides of the rule: profiles/cell_density.json, profiles/cell_territory.json).
+CELL_HD inline bool site_route_staged(int s, int reach, int side) { return (long long)(SITE_TILE - 1) * s <= 2LL * reach + side; }
 
-// the window of sites: W, H >= 1, W * H <= 2^24, and every site coordinate within +-2^28, all in 64 bits
-inline bool dens_window_ok(int s, int gx0, int gy0, int W, int H) {
-  if (s < 1 || s > DENS_MAX_PITCH || W < 1 || H < 1 || (int64_t)W * H > DENS_MAX_SITES) return false;
-  const int64_t lim = DENS_SITE_LIMIT;
+// the window of sites: W, H >= 1, W * H <= max_sites (DENS_MAX_SITES or TERR_MAX_SITES), and every site coordinate within +-2^28, all in
+// 64 bits
+inline bool site_window_ok(int s, int gx0, int gy0, int W, int H, int64_t max_sites) {
+  if (s < 1 || s > SITE_MAX_PITCH || W < 1 || H < 1 || (int64_t)W * H > max_sites) return false;
+  const int64_t lim = SITE_LIMIT;
   const int64_t xa = (int64_t)gx0 * s, xb = ((int64_t)gx0 + W - 1) * s, ya = (int64_t)gy0 * s, yb = ((int64_t)gy0 + H - 1) * s;
   return xa > -lim && xa < lim && xb > -lim && xb < lim && ya > -lim && ya < lim && yb > -lim && yb < lim;
 }
@@ -171,18 +192,6 @@ CELL_HD inline int terr_table_at(int a, int b, int C) { return a * (C + 1) + b; 
 CELL_HD inline bool terr_table_fits(int64_t sites_of_a_workgroup) { return sites_of_a_workgroup * TERR_PER_SITE <= (int64_t)0xffffffffll; }
 static_assert(TERR_MAX_SITES * TERR_PER_SITE <= (int64_t)0xffffffffll, "one flush at the end of the tally kernel is enough");
 
-// which kernel takes the sites: the rule of dens_route_staged (the two sweeps test the same records as density's two; measured on both
-// sides of the rule: profiles/cell_territory.json)
-CELL_HD inline bool terr_route_staged(int s, int R, int side) { return dens_route_staged(s, R, side); }
-
-// the window of sites: dens_window_ok with this analysis' own cap, W * H <= 2^28
-inline bool terr_window_ok(int s, int gx0, int gy0, int W, int H) {
-  if (s < 1 || s > DENS_MAX_PITCH || W < 1 || H < 1 || (int64_t)W * H > TERR_MAX_SITES) return false;
-  const int64_t lim = DENS_SITE_LIMIT;
-  const int64_t xa = (int64_t)gx0 * s, xb = ((int64_t)gx0 + W - 1) * s, ya = (int64_t)gy0 * s, yb = ((int64_t)gy0 + H - 1) * s;
-  return xa > -lim && xa < lim && xb > -lim && xb < lim && ya > -lim && ya < lim && yb > -lim && yb < lim;
-}
-
 // ---- territory adjacency (celladjacency.hip): the discrete Delaunay graph read off a finished owner map.  A SITE PAIR is an unordered pair
 // of 4-adjacent sites inside the window, counted once: from its left or upper site, as that site's RIGHT or LOWER pair (adj_site_pairs).
 // It is an edge when the two owners differ and both are rows (adj_is_edge); its key holds the smaller row in the high word, so the
@@ -192,7 +201,7 @@ inline bool terr_window_ok(int s, int gx0, int gy0, int W, int H) {
 // slots is at most half full; the call's table has next_pow2(2 M) >= 2 M slots (at least ADJ_MIN_SLOTS, at most 2^30) and holds at most M
 // keys, so it is at most half full as well: linear probing from adj_slot_of always meets the key or an empty slot.
 constexpr unsigned long long ADJ_NO_KEY = ~0ull;
-constexpr int ADJ_TILE_PAIRS = 2 * DENS_TILE * DENS_TILE;          // the site pairs a tile takes: a right and a lower one per site
+constexpr int ADJ_TILE_PAIRS = 2 * SITE_TILE * SITE_TILE;          // the site pairs a tile takes: a right and a lower one per site
 constexpr int ADJ_TILE_SLOTS = 1024;
 constexpr int64_t ADJ_MAX_RECORDS = 2 * TERR_MAX_SITES;           // 2^29
 constexpr int64_t ADJ_MIN_SLOTS = 1024;

@@ -14,12 +14,12 @@
 //   geometry   on the HOST from the caller's bounding box (cell_grid_side of cellgrid_host.h): cells of side >= R, at most 2^22 of them.
 //   binning    cellbin.h, reach R, ONE key per cell, and the zeroing of the per-row arrays and the tables (terr_zero_kernel, AFTER the
 //              binning and only if its flag is clear).
-//   owner      one workgroup per tile of 16 x 16 sites, one thread per site, no atomics.  A site may lie outside the box on any side:
-//              its cell is a floor and its cell range is clamped and may be empty (site_cell_range), as for density.  Every thread
-//              holds its best key (terr_key: d2 in the high word, the row in the low one) in two registers.  Two kernels, chosen on
-//              the host per call by terr_route_staged, the rule of the density maps:
-//                staged  (terr_tile_kernel)  the staged form of dens_tile_kernel: the tile's footprint grown by R, the records of each
-//                        cell row through LDS 256 at a time, every thread against every staged record.  LDS is the 4 KiB stage only.
+//   owner      one workgroup per tile of 16 x 16 sites, one thread per site, no atomics: the lattice, a thread's site and the sweep are
+//              cellsites.h's (site_sweep, with the barrier contract), shared with the density maps; terr_take and terr_write are this
+//              file's.  Every thread holds its best key (terr_key: d2 in the high word, the row in the low one) in two registers.  Two
+//              kernels, chosen on the host per call by site_route:
+//                staged  (terr_tile_kernel)  the records of the tile's footprint grown by R through LDS 256 at a time, every thread
+//                        against every staged record.  LDS is the 4 KiB stage only.
 //                direct  (terr_site_kernel)  every thread walks the (at most 3 x 3) cells its own disc can touch.
 //   tally      one thread per site in row-major order (a grid-stride loop over blocks of 256 sites) once the owner map is complete:
 //              its own owner and the four neighbours' inside the window.  area / border / open go to the per-row arrays by integer
@@ -37,7 +37,7 @@
 // terr_zero_kernel 9 VGPRs; registers allow 8 waves per SIMD in all of them.
 //
 // Measured on one MI355X (tools/bench_territory.py -> profiles/cell_territory.json; 500 000 centres on a 36 000-px square, reach 64 px,
-// C = 5, medians of 10 calls, the variants forced with -DNUHTC_TERRITORY_ROUTE / -DNUHTC_TERRITORY_PER_SITE in two alternating rounds in
+// C = 5, medians of 10 calls, the variants forced with -DNUHTC_SITE_ROUTE / -DNUHTC_TERRITORY_PER_SITE in two alternating rounds in
 // one process, every variant bitwise equal to the shipped call).  Pitch 4 px, 81.6 M sites: 2.05 ms per call uniform (binning 0.07,
 // owner 0.85, tally 0.92) and 1.85 ms clustered.  Pitch 32 px, 1.27 M sites: 0.47 and 0.53 ms.
 //   owner route, ms staged / direct: pitch 4 px 2.05 / 2.26 uniform and 1.83 / 2.08 clustered; pitch 32 px 0.53 / 0.45 and 0.78 / 0.55 --
@@ -46,24 +46,24 @@
 //              0.47 / 0.49 and 0.54 / 0.56 -- the wave-level reduction pays wherever territories span many sites and costs nothing
 //              where they do not.
 //
-// Everything that decides an index or a limit -- the floor cell, the clamped range, the key and its order, the offer of a record, the
-// table index, the flush bound, the window check and the route (cellgrid_host.h) -- is plain C++, and
-// tools/dev/cellterritory_host_check.cpp runs exactly those functions on the host under -fsanitize=address,undefined.  The kernel code
+// Everything that decides an index or a limit -- the floor cell, the clamped cells of a footprint, the key and its order, the offer of a
+// record, the table index, the flush bound, the window check and the route (cellgrid_host.h) -- is plain C++, and
+// tools/dev/cellterritory_host_check.cpp calls exactly those functions on the host under -fsanitize=address,undefined.  The kernel code
 // itself is not sanitized.
 #include <algorithm>
 #include <cstring>
 
-#include "cellbin.h"
+#include "cellsites.h"
 
 namespace {
 
 constexpr int TERR_MAX_CELLS = 1 << 22;
-constexpr int TERR_NT = DENS_TILE * DENS_TILE;          // 256 sites, one thread each
 constexpr int TERR_TALLY_BLOCKS = 2048;                 // workgroups of the tally kernel at most: one table flush each
 
 struct CellTerritoryArgs {
   CellBin b;                          // the points, the grid and the records in cell order (cellbin.h, one key per cell)
-  int C, R, s, gx0, gy0, W, H, tiles_x;
+  SiteLattice t;                      // reach = R
+  int C;
   int32_t* owner;                     // [H][W]
   int32_t* nearest_d2;                // [H][W]
   int32_t* area;                      // [n]
@@ -83,88 +83,44 @@ __global__ __launch_bounds__(256) void terr_zero_kernel(CellTerritoryArgs a) {
   if (i == 0) *a.free_sites = 0;
 }
 
-// the site of this thread: (u, v) in the window, whether it exists, and its position in half pixels.  A thread past the window's edge
-// takes the last site of its row or column (a valid coordinate) and writes nothing.
-struct TerrSite { int u, v, qx, qy; bool active; };
-__device__ __forceinline__ TerrSite terr_site_of(const CellTerritoryArgs& a) {
-  TerrSite t;
-  const int tid = threadIdx.x;
-  const int u = (int)(blockIdx.x % a.tiles_x) * DENS_TILE + (tid & (DENS_TILE - 1)), v = (int)(blockIdx.x / a.tiles_x) * DENS_TILE + tid / DENS_TILE;
-  t.active = u < a.W && v < a.H;
-  t.u = min(u, a.W - 1); t.v = min(v, a.H - 1);
-  t.qx = (a.gx0 + t.u) * a.s; t.qy = (a.gy0 + t.v) * a.s;
-  return t;
-}
-
-__device__ __forceinline__ void terr_take(const CellTerritoryArgs& a, const int4 o, const TerrSite& me, int R2, unsigned long long& best) {
-  const unsigned long long key = terr_offer(o.x - me.qx, o.y - me.qy, o.z, o.w, a.C, a.R, R2);
+__device__ __forceinline__ void terr_take(const CellTerritoryArgs& a, const int4 o, const Site& me, int R2, unsigned long long& best) {
+  const unsigned long long key = terr_offer(o.x - me.qx, o.y - me.qy, o.z, o.w, a.C, a.t.reach, R2);
   best = key < best ? key : best;
 }
 
-__device__ __forceinline__ void terr_write(const CellTerritoryArgs& a, const TerrSite& me, unsigned long long best) {
+__device__ __forceinline__ void terr_write(const CellTerritoryArgs& a, const Site& me, unsigned long long best) {
   if (!me.active) return;
-  const size_t at = (size_t)me.v * a.W + me.u;
+  const size_t at = (size_t)me.v * a.t.W + me.u;
   a.owner[at] = terr_key_row(best);
   a.nearest_d2[at] = terr_key_d2(best);
 }
 
-// staged: the records of the tile's footprint through LDS, 256 at a time.  Every loop bound is the tile's, uniform over the workgroup:
-// every thread meets every barrier.
-__global__ __launch_bounds__(TERR_NT) void terr_tile_kernel(CellTerritoryArgs a) {
-  __shared__ int4 stage[TERR_NT];
-  const CellBin& g = a.b;
-  if (*g.flag) return;                                   // the binning met a point outside the box: nothing is written (uniform)
-  const int tid = threadIdx.x, R = a.R, R2 = R * R;
-  const TerrSite me = terr_site_of(a);
+// both kernels: the flag, the best key, the sweep of cellsites.h (staged or direct), the write
+template <bool STAGED>
+__device__ __forceinline__ void terr_owner(const CellTerritoryArgs& a, int4* stage) {
+  if (*a.b.flag) return;                                 // the binning met a point outside the box: nothing is written (uniform)
+  const int R2 = a.t.reach * a.t.reach;
+  const Site me = site_of(a.t);
   unsigned long long best = TERR_NO_KEY;
-  const int u0 = (int)(blockIdx.x % a.tiles_x) * DENS_TILE, v0 = (int)(blockIdx.x / a.tiles_x) * DENS_TILE;
-  const int u1 = min(u0 + DENS_TILE, a.W) - 1, v1 = min(v0 + DENS_TILE, a.H) - 1;
-  int cx0, cx1, cy0, cy1;
-  site_cell_range((a.gx0 + u0) * a.s - R, (a.gx0 + u1) * a.s + R, g.x_min, g.side, g.ncx, &cx0, &cx1);
-  site_cell_range((a.gy0 + v0) * a.s - R, (a.gy0 + v1) * a.s + R, g.y_min, g.side, g.ncy, &cy0, &cy1);
-  if (cx0 > cx1) cy1 = cy0 - 1;                          // beside the grid: no row
-  for (int gy = cy0; gy <= cy1; ++gy) {
-    const int j0 = g.cell_start[gy * g.ncx + cx0], j1 = g.cell_start[gy * g.ncx + cx1 + 1];
-    for (int base = j0; base < j1; base += TERR_NT) {
-      __syncthreads();                                   // the chunk before this one has been read by everyone
-      if (base + tid < j1) stage[tid] = g.recs[base + tid];
-      __syncthreads();
-      const int m = min(TERR_NT, j1 - base);
-      for (int k = 0; k < m; ++k) terr_take(a, stage[k], me, R2, best);
-    }
-  }
+  site_sweep<STAGED>(a.b, a.t, me, stage, [&](const int4& o) { terr_take(a, o, me, R2, best); });
   terr_write(a, me, best);
 }
-
-// direct: every site walks the cells its own disc can touch
-__global__ __launch_bounds__(TERR_NT) void terr_site_kernel(CellTerritoryArgs a) {
-  const CellBin& g = a.b;
-  if (*g.flag) return;
-  const int R = a.R, R2 = R * R;
-  const TerrSite me = terr_site_of(a);
-  if (!me.active) return;                                // no barrier in this kernel
-  unsigned long long best = TERR_NO_KEY;
-  int cx0, cx1, cy0, cy1;
-  site_cell_range(me.qx - R, me.qx + R, g.x_min, g.side, g.ncx, &cx0, &cx1);
-  site_cell_range(me.qy - R, me.qy + R, g.y_min, g.side, g.ncy, &cy0, &cy1);
-  if (cx0 > cx1) cy1 = cy0 - 1;
-  for (int gy = cy0; gy <= cy1; ++gy) {
-    const int j0 = g.cell_start[gy * g.ncx + cx0], j1 = g.cell_start[gy * g.ncx + cx1 + 1];
-    for (int j = j0; j < j1; ++j) terr_take(a, g.recs[j], me, R2, best);
-  }
-  terr_write(a, me, best);
+__global__ __launch_bounds__(SITE_NT) void terr_tile_kernel(CellTerritoryArgs a) {
+  __shared__ int4 stage[SITE_NT];
+  terr_owner<true>(a, stage);
 }
+__global__ __launch_bounds__(SITE_NT) void terr_site_kernel(CellTerritoryArgs a) { terr_owner<false>(a, nullptr); }
 
 // the tallies of the finished owner map.  RUNS: one atomic per run of equal owners among the lanes of a wave; else one per site.
 template <bool RUNS>
-__global__ __launch_bounds__(TERR_NT) void terr_tally_kernel(CellTerritoryArgs a) {
+__global__ __launch_bounds__(SITE_NT) void terr_tally_kernel(CellTerritoryArgs a) {
   __shared__ unsigned table[TERR_TABLE_WORDS];
   if (*a.b.flag) return;                                 // uniform
-  const int tid = threadIdx.x, lane = tid & 63, C = a.C, W = a.W, H = a.H, total = W * H;      // total <= 2^28
-  for (int i = tid; i < TERR_TABLE_WORDS; i += TERR_NT) table[i] = 0;
+  const int tid = threadIdx.x, lane = tid & 63, C = a.C, W = a.t.W, H = a.t.H, total = W * H;      // total <= 2^28
+  for (int i = tid; i < TERR_TABLE_WORDS; i += SITE_NT) table[i] = 0;
   __syncthreads();
   const int32_t* __restrict__ owner = a.owner;
-  for (int base = blockIdx.x * TERR_NT; base < total; base += gridDim.x * TERR_NT) {          // uniform over the workgroup; < 2^28 + 2^19
+  for (int base = blockIdx.x * SITE_NT; base < total; base += gridDim.x * SITE_NT) {          // uniform over the workgroup; < 2^28 + 2^19
     const int k = base + tid;
     int me = -2;                                         // a lane past the last site: a run of its own, counted nowhere
     bool on_border = false, is_open = false;
@@ -206,7 +162,7 @@ __global__ __launch_bounds__(TERR_NT) void terr_tally_kernel(CellTerritoryArgs a
     }
   }
   __syncthreads();
-  for (int i = tid; i < (C + 1) * (C + 1); i += TERR_NT) {                                     // the flush: once (terr_table_fits)
+  for (int i = tid; i < (C + 1) * (C + 1); i += SITE_NT) {                                     // the flush: once (terr_table_fits)
     const unsigned t = table[i];
     if (!t) continue;
     const int ca = i / (C + 1), cb = i - ca * (C + 1);
@@ -221,7 +177,7 @@ extern "C" int nuhtc_cell_territory(int device, const int32_t* points, const int
                                     int gy0, int W, int H, int x_min, int y_min, int x_max, int y_max, int32_t* owner, int32_t* nearest_d2,
                                     int32_t* area, int32_t* border, int32_t* open, int64_t* contact, int64_t* class_sites, int64_t* free_sites,
                                     void* stream) {
-  if (!cell_call_ok(n, MST_MAX_POINTS, num_classes, reach, x_min, y_min, x_max, y_max) || !terr_window_ok(s, gx0, gy0, W, H)) return NUHTC_E_INVALID;
+  if (!cell_call_ok(n, MST_MAX_POINTS, num_classes, reach, x_min, y_min, x_max, y_max) || !site_window_ok(s, gx0, gy0, W, H, TERR_MAX_SITES)) return NUHTC_E_INVALID;
   if (!owner || !nearest_d2 || !contact || !class_sites || !free_sites || (n > 0 && (!points || !labels || !area || !border || !open))) return NUHTC_E_INVALID;
   if (hipSetDevice(device) != hipSuccess) return NUHTC_E_HIP;
   hipStream_t st = (hipStream_t)stream;
@@ -237,21 +193,13 @@ extern "C" int nuhtc_cell_territory(int device, const int32_t* points, const int
   }
   CellTerritoryArgs a;
   memset(&a, 0, sizeof(a));
-  a.C = C; a.R = reach; a.s = s; a.gx0 = gx0; a.gy0 = gy0; a.W = W; a.H = H;
-  a.tiles_x = (W + DENS_TILE - 1) / DENS_TILE;
+  a.t = site_lattice(reach, s, gx0, gy0, W, H); a.C = C;
   a.owner = owner; a.nearest_d2 = nearest_d2; a.area = area; a.border = border; a.open = open;
   a.contact = reinterpret_cast<unsigned long long*>(contact); a.class_sites = reinterpret_cast<unsigned long long*>(class_sites);
   a.free_sites = reinterpret_cast<unsigned long long*>(free_sites);
   DevScratch tmp;      // every temporary of the call, freed on the way out
   const int nchunk = cellbin_setup(a.b, points, labels, (int)n, x_min, y_min, x_max, y_max, reach, TERR_MAX_CELLS, 1, tmp, st);
   if (!nchunk) return NUHTC_E_HIP;
-  // H = 1 gives the most tiles: (2^28 + 15) / 16 < 2^25
-  const unsigned tiles = (unsigned)a.tiles_x * (unsigned)((H + DENS_TILE - 1) / DENS_TILE);
-#ifdef NUHTC_TERRITORY_ROUTE                              // dev probe: -DNUHTC_TERRITORY_ROUTE=1 staged, =2 direct, whatever the shape
-  const bool staged = NUHTC_TERRITORY_ROUTE == 1;
-#else
-  const bool staged = terr_route_staged(s, reach, a.b.side);
-#endif
   {
     ProfScope ps("cell_territory_bin", 0, 0, st);
     cellbin_launch(a.b, nchunk, st);
@@ -259,16 +207,15 @@ extern "C" int nuhtc_cell_territory(int device, const int32_t* points, const int
   }
   {
     ProfScope ps("cell_territory_owner", 0, 0, st);
-    if (staged) hipLaunchKernelGGL(terr_tile_kernel, dim3(tiles), dim3(TERR_NT), 0, st, a);
-    else hipLaunchKernelGGL(terr_site_kernel, dim3(tiles), dim3(TERR_NT), 0, st, a);
+    site_launch(site_route(s, reach, a.b.side), terr_tile_kernel, terr_site_kernel, site_tiles(W, H), 0, st, a);
   }
   {
     ProfScope ps("cell_territory_tally", 0, 0, st);
-    const unsigned blocks = (unsigned)std::min<size_t>((sites + TERR_NT - 1) / TERR_NT, TERR_TALLY_BLOCKS);
+    const unsigned blocks = (unsigned)std::min<size_t>((sites + SITE_NT - 1) / SITE_NT, TERR_TALLY_BLOCKS);
 #ifdef NUHTC_TERRITORY_PER_SITE                           // dev probe: one atomic per site instead of one per run of a wave
-    hipLaunchKernelGGL(terr_tally_kernel<false>, dim3(blocks), dim3(TERR_NT), 0, st, a);
+    hipLaunchKernelGGL(terr_tally_kernel<false>, dim3(blocks), dim3(SITE_NT), 0, st, a);
 #else
-    hipLaunchKernelGGL(terr_tally_kernel<true>, dim3(blocks), dim3(TERR_NT), 0, st, a);
+    hipLaunchKernelGGL(terr_tally_kernel<true>, dim3(blocks), dim3(SITE_NT), 0, st, a);
 #endif
   }
   return cellbin_finish(a.b, st);

@@ -50,22 +50,28 @@ DERIVED_KEYS = ('density_per_px2', 'share', 'class_total', 'colocalisation', 'pe
 NPZ_KEYS = ('nuclei_id', 'xy', 'label') + INT_NAMES + DERIVED_KEYS + ('bandwidth_px', 'pitch_px', 'origin_px', 'window')
 
 
-def check_args(num_classes, h, s, win=None):
-    """num_classes 1..14, h 1..16384 and s 1..2**20 half pixels, and, when given, the window (gx0, gy0, W, H): W, H >= 1, W * H <= 2**24 and
-    every site coordinate |g * s| < 2**28: ValueError otherwise."""
-    whole = all(float(v) == int(v) for v in (num_classes, h, s))
-    if not (whole and 1 <= int(num_classes) <= MAX_CLASSES and 1 <= int(h) <= MAX_R and 1 <= int(s) <= MAX_PITCH):
-        raise ValueError(f'density: num_classes 1..{MAX_CLASSES}, bandwidth 1..{MAX_R} and pitch 1..{MAX_PITCH} half pixels '
-                         f'(got num_classes={num_classes}, h={h}, s={s})')
+def check_lattice(name, reach_word, reach_letter, max_sites, num_classes, r, s, win=None):
+    """The argument check of every raster on this lattice (`name`: the module, for the messages; `reach_word`, `reach_letter`: what it calls r in
+    words and in its signature; max_sites: its cap, a power of two): num_classes 1..14, r 1..16384 and s 1..2**20 half pixels, and, when given, the window (gx0, gy0, W, H):
+    W, H >= 1, W * H <= max_sites and every site coordinate |g * s| < 2**28: ValueError otherwise."""
+    whole = all(float(v) == int(v) for v in (num_classes, r, s))
+    if not (whole and 1 <= int(num_classes) <= MAX_CLASSES and 1 <= int(r) <= MAX_R and 1 <= int(s) <= MAX_PITCH):
+        raise ValueError(f'{name}: num_classes 1..{MAX_CLASSES}, {reach_word} 1..{MAX_R} and pitch 1..{MAX_PITCH} half pixels '
+                         f'(got num_classes={num_classes}, {reach_letter}={r}, s={s})')
     if win is None:
         return
     if len(win) != 4 or not all(float(v) == int(v) for v in win):
-        raise ValueError(f'density: the window is four integers gx0, gy0, W, H (got {win})')
+        raise ValueError(f'{name}: the window is four integers gx0, gy0, W, H (got {win})')
     gx0, gy0, W, H = (int(v) for v in win)
-    if W < 1 or H < 1 or W * H > MAX_SITES:
-        raise ValueError(f'density: a window of {W} x {H} sites; W, H >= 1 and at most 2**24 sites: coarsen the pitch')
+    if W < 1 or H < 1 or W * H > max_sites:
+        raise ValueError(f'{name}: a window of {W} x {H} sites; W, H >= 1 and at most 2**{max_sites.bit_length() - 1} sites: coarsen the pitch')
     if max(abs(gx0), abs(gx0 + W - 1), abs(gy0), abs(gy0 + H - 1)) * int(s) >= SITE_LIMIT:
-        raise ValueError('density: a site lies outside |q| < 2**28 half pixels')
+        raise ValueError(f'{name}: a site lies outside |q| < 2**28 half pixels')
+
+
+def check_args(num_classes, h, s, win=None):
+    """`check_lattice` with this module's cap of 2**24 sites."""
+    check_lattice('density', 'bandwidth', 'h', MAX_SITES, num_classes, h, s, win)
 
 
 def window(bounds, h, s):
@@ -113,6 +119,33 @@ def call(points, labels, num_classes, h, s, win, count, weight, bounds=None, dev
                              (count, weight), bounds)
 
 
+def lattice_points(name, check, points, labels, num_classes, reach_px, pitch_px, win, device):
+    """The opening of a `build` on this lattice (`name`: the module, for the messages; `check`: its check_args): the points and labels as
+    cellpoints.as_points takes them, the caps on n and on the coordinates, r and s in half pixels, the window -- `win`, or the default one
+    of the points' bounding box with at least one site each way ((0, 0, 1, 1) for no points) -- checked, and the upload
+    -> (n, C, r, s, win, dev, points and labels on cuda:`device`, bounds)."""
+    p, lab = cellpoints.as_points(points, labels, name)
+    n, C, r, s = len(p), int(num_classes), half_pixel_radius(reach_px), half_pixel_radius(pitch_px)
+    if n > MAX_POINTS:
+        raise ValueError(f'{name}: at most 2**24 points (got {n})')
+    check(C, r, s)
+    if n and np.abs(p).max() >= COORD_LIMIT:
+        raise ValueError(f'{name}: a coordinate lies outside |p| < 2**27')
+    if win is None:
+        win = window(cellpoints.bounds_of(p), r, s) if n else (0, 0, 1, 1)
+        win = (win[0], win[1], max(win[2], 1), max(win[3], 1))
+    win = tuple(int(v) for v in win)
+    check(C, r, s, win)
+    return (n, C, r, s, win) + tuple(cellpoints.upload(p, lab, device))
+
+
+def lattice_npz(win, s, pitch_px):
+    """What a writer says of the lattice (s the pitch in HALF pixels): pitch_px float64 0-d; origin_px float64 (2,), the px position of site
+    (0, 0); window int64 (4,) gx0, gy0, W, H."""
+    return dict(pitch_px=np.asarray(float(pitch_px), np.float64), origin_px=np.array([win[0] * s / 2, win[1] * s / 2], np.float64),
+                window=np.asarray(win, np.int64))
+
+
 def outputs(num_classes, win, device, fill=0):
     """The two output tensors of `call` for a window on `device`, every entry `fill`."""
     import torch
@@ -125,19 +158,7 @@ def build(points, labels, num_classes, bandwidth_px, pitch_px, win=None, device=
     in, (count, weight, window) out.  Without `win` the window is the default one of the points' bounding box (one site at the origin for
     no points, or where the pitch steps over every site in reach); ValueError when it exceeds 2**24 sites.  There is no host route:
     without the library or a GPU this raises."""
-    p, lab = cellpoints.as_points(points, labels, 'density')
-    n, C, h, s = len(p), int(num_classes), half_pixel_radius(bandwidth_px), half_pixel_radius(pitch_px)
-    if n > MAX_POINTS:
-        raise ValueError(f'density: at most 2**24 points (got {n})')
-    check_args(C, h, s)
-    if n and np.abs(p).max() >= COORD_LIMIT:
-        raise ValueError('density: a coordinate lies outside |p| < 2**27')
-    if win is None:
-        win = window(cellpoints.bounds_of(p), h, s) if n else (0, 0, 1, 1)
-        win = (win[0], win[1], max(win[2], 1), max(win[3], 1))
-    win = tuple(int(v) for v in win)
-    check_args(C, h, s, win)
-    dev, p_d, lab_d, bounds = cellpoints.upload(p, lab, device)
+    _, C, h, s, win, dev, p_d, lab_d, bounds = lattice_points('density', check_args, points, labels, num_classes, bandwidth_px, pitch_px, win, device)
     out = outputs(C, win, dev)
     cellpoints.raise_for(call(p_d, lab_d, C, h, s, win, *out, bounds=bounds, device=device), 'nuhtc_cell_density')
     return out[0].cpu().numpy(), out[1].cpu().numpy(), win
@@ -181,7 +202,7 @@ def write_npz(path, nuclei_id, xy, label, count, weight, win, bandwidth_px, pitc
       nuclei_id int64 (n,), xy float64 (n, 2) (the unquantised centre in slide px), label int64 (n,)
       count int32 (C, H, W), weight int64 (C, H, W): the integers of the definition
       the arrays of `derive` (DERIVED_KEYS)
-      bandwidth_px, pitch_px float64 0-d; origin_px float64 (2,), the px position of site (0, 0); window int64 (4,) gx0, gy0, W, H."""
+      bandwidth_px float64 0-d, and pitch_px, origin_px and window of `lattice_npz`."""
     head = cellpoints.npz_header(nuclei_id, xy, label)
     count = np.ascontiguousarray(count, np.int32)
     weight = np.ascontiguousarray(weight, np.int64)
@@ -194,9 +215,7 @@ def write_npz(path, nuclei_id, xy, label, count, weight, win, bandwidth_px, pitc
         raise ValueError('write_npz: the rasters are not the window\'s H x W')
     d = derive(count, weight, h)
     with open(path, 'wb') as f:
-        np.savez(f, **head, count=count, weight=weight, **d, bandwidth_px=np.asarray(float(bandwidth_px), np.float64),
-                 pitch_px=np.asarray(float(pitch_px), np.float64), origin_px=np.array([win[0] * s / 2, win[1] * s / 2], np.float64),
-                 window=np.asarray(win, np.int64))
+        np.savez(f, **head, count=count, weight=weight, **d, bandwidth_px=np.asarray(float(bandwidth_px), np.float64), **lattice_npz(win, s, pitch_px))
     return path
 
 

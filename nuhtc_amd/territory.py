@@ -65,21 +65,8 @@ NPZ_KEYS = ('nuclei_id', 'xy', 'label') + INT_NAMES + DERIVED_KEYS + ('reach_px'
 
 
 def check_args(num_classes, r, s, win=None):
-    """num_classes 1..14, r 1..16384 and s 1..2**20 half pixels, and, when given, the window (gx0, gy0, W, H): W, H >= 1, W * H <= 2**28 and
-    every site coordinate |g * s| < 2**28: ValueError otherwise."""
-    whole = all(float(v) == int(v) for v in (num_classes, r, s))
-    if not (whole and 1 <= int(num_classes) <= MAX_CLASSES and 1 <= int(r) <= MAX_R and 1 <= int(s) <= MAX_PITCH):
-        raise ValueError(f'territory: num_classes 1..{MAX_CLASSES}, reach 1..{MAX_R} and pitch 1..{MAX_PITCH} half pixels '
-                         f'(got num_classes={num_classes}, r={r}, s={s})')
-    if win is None:
-        return
-    if len(win) != 4 or not all(float(v) == int(v) for v in win):
-        raise ValueError(f'territory: the window is four integers gx0, gy0, W, H (got {win})')
-    gx0, gy0, W, H = (int(v) for v in win)
-    if W < 1 or H < 1 or W * H > MAX_SITES:
-        raise ValueError(f'territory: a window of {W} x {H} sites; W, H >= 1 and at most 2**28 sites: coarsen the pitch')
-    if max(abs(gx0), abs(gx0 + W - 1), abs(gy0), abs(gy0 + H - 1)) * int(s) >= SITE_LIMIT:
-        raise ValueError('territory: a site lies outside |q| < 2**28 half pixels')
+    """density.check_lattice with this module's cap of 2**28 sites."""
+    density.check_lattice('territory', 'reach', 'r', MAX_SITES, num_classes, r, s, win)
 
 
 def tally(owner, labels, num_classes, n=None):
@@ -160,19 +147,7 @@ def build(points, labels, num_classes, reach_px, pitch_px, win=None, maps=False,
     maps=True and None otherwise: the two rasters are copied off the device only when asked for.  Without `win` the window is the default
     one of the points' bounding box (one site at the origin for no points, or where the pitch steps over every site in reach); ValueError
     when it exceeds 2**28 sites.  There is no host route: without the library or a GPU this raises."""
-    p, lab = cellpoints.as_points(points, labels, 'territory')
-    n, C, r, s = len(p), int(num_classes), half_pixel_radius(reach_px), half_pixel_radius(pitch_px)
-    if n > MAX_POINTS:
-        raise ValueError(f'territory: at most 2**24 points (got {n})')
-    check_args(C, r, s)
-    if n and np.abs(p).max() >= COORD_LIMIT:
-        raise ValueError('territory: a coordinate lies outside |p| < 2**27')
-    if win is None:
-        win = window(cellpoints.bounds_of(p), r, s) if n else (0, 0, 1, 1)
-        win = (win[0], win[1], max(win[2], 1), max(win[3], 1))
-    win = tuple(int(v) for v in win)
-    check_args(C, r, s, win)
-    dev, p_d, lab_d, bounds = cellpoints.upload(p, lab, device)
+    n, C, r, s, win, dev, p_d, lab_d, bounds = density.lattice_points('territory', check_args, points, labels, num_classes, reach_px, pitch_px, win, device)
     out = outputs(n, C, win, dev)
     cellpoints.raise_for(call(p_d, lab_d, C, r, s, win, *out, bounds=bounds, device=device), 'nuhtc_cell_territory')
     area, border, is_open, contact, class_sites, free_sites = (t.cpu().numpy() for t in out[2:])
@@ -221,7 +196,7 @@ def write_npz(path, nuclei_id, xy, label, tallies, win, reach_px, pitch_px, maps
       area, border int32 (n,), open uint8 (n,), contact int64 (C, C), class_sites int64 (C,), free_sites int64 0-d: the tallies of the
       definition, over the file's window
       the arrays of `derive` (DERIVED_KEYS)
-      reach_px, pitch_px float64 0-d; origin_px float64 (2,), the px position of site (0, 0); window int64 (4,) gx0, gy0, W, H
+      reach_px float64 0-d, and pitch_px, origin_px and window of density.lattice_npz
       with maps = (owner, nearest_d2): owner, nearest_d2 int32 (H, W) behind them."""
     head = cellpoints.npz_header(nuclei_id, xy, label)
     area, border, is_open, contact, class_sites, free_sites = tallies
@@ -247,8 +222,7 @@ def write_npz(path, nuclei_id, xy, label, tallies, win, reach_px, pitch_px, maps
     d = derive(area, is_open, contact, class_sites, free_sites, head['label'], s)
     with open(path, 'wb') as f:
         np.savez(f, **head, area=area, border=border, open=is_open, contact=contact, class_sites=class_sites, free_sites=free_sites, **d,
-                 reach_px=np.asarray(float(reach_px), np.float64), pitch_px=np.asarray(float(pitch_px), np.float64),
-                 origin_px=np.array([win[0] * s / 2, win[1] * s / 2], np.float64), window=np.asarray(win, np.int64), **more)
+                 reach_px=np.asarray(float(reach_px), np.float64), **density.lattice_npz(win, s, pitch_px), **more)
     return path
 
 

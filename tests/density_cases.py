@@ -116,6 +116,6 @@ LARGE_HS = [(20, 4), (30, 16), (5, 11)]                     # (h, s): sites far 
 
 
 def staged(case, side=None):
-    """Does the device stage this case through LDS?  The rule of csrc/cellgrid_host.h (dens_route_staged) restated: 15 s <= 2 h + side, the
+    """Does the device stage this case through LDS?  The rule of csrc/cellgrid_host.h (site_route_staged) restated: 15 s <= 2 h + side, the
     cell side being h for every box of these tests (fewer than 2**22 cells of side h)."""
     return 15 * case[4] <= 2 * case[3] + (case[3] if side is None else side)

@@ -4,7 +4,7 @@ left out.  The designed cases of tests/test_territory_host.py (the tie, the incl
 box on all four sides (as they are, mirrored, at the far corners of the coordinate range), windows that are no multiple of a tile,
 sub-windows, a window of many tiles in x, an argmin across staging chunks, labels out of range, a binning over two scan chunks, random sets
 full of ties (repeatable, independent of the row order), the edge sizes, the refused arguments, the profile tags, and tools/infer_wsi.py
---nuclei-territory end to end.  The cases lie on both sides of the rule that picks the owner kernel (terr_route_staged)."""
+--nuclei-territory end to end.  The cases lie on both sides of the rule that picks the owner kernel (site_route_staged)."""
 import os
 
 import numpy as np

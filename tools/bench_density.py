@@ -13,14 +13,14 @@ set of the same size (400 Gaussian clumps, sigma 300 px), at the defaults of too
   device_stage_ms      one further call under the library's per-kernel profile: the binning, and the kernel that took the sites
                        (cell_density_tile: staged through LDS; cell_density_site: every site on its own)
   device_end_to_end_ms density.build from numpy to numpy: bounding box, upload, the call, download (wall clock)
-  variants             with --also: other builds of the library (-DNUHTC_DENSITY_ROUTE=1 forces the staged kernel, =2 the direct one) timed
+  variants             with --also: other builds of the library (NUHTC_EXTRA_CFLAGS_CELLDENSITY=-DNUHTC_SITE_ROUTE=1 forces the staged kernel, =2 the direct one) timed
                        in `--rounds` alternating rounds with the shipped one, all in this process; each must return the shipped arrays
   host_ms              the yardstick: numpy with a per-point scatter -- for every offset of a point's site footprint one np.add.at over all
                        points into the int64 rasters; must equal the device
   checked_against_reference  a sub-window small enough for brute force, through the device again, against density_reference on the points
                        within reach of it
 With --more-shapes the shipped and the --also builds are timed at further (bandwidth, pitch) pairs on the uniform set: where the rule that
-picks the kernel (dens_route_staged of csrc/cellgrid_host.h) has to hold.  bench.py is the project's headline benchmark and is not changed
+picks the kernel (site_route_staged of csrc/cellgrid_host.h) has to hold.  bench.py is the project's headline benchmark and is not changed
 by this tool."""
 import os
 import sys

@@ -14,7 +14,7 @@ set of the same size, at the defaults of tools/infer_wsi.py --nuclei-territory a
   with_maps_end_to_end_ms  the same with maps=True: the two rasters come off the device as well
   density_ms           the yardstick on the device: nuhtc_cell_density at the same reach and the same pitch where its cap of 2**24 sites
                        admits the window, else at the smallest multiple of the pitch that it admits (density_pitch_px says which)
-  variants             with --also: other builds of the library (-DNUHTC_TERRITORY_ROUTE=1 forces the staged owner kernel, =2 the direct
+  variants             with --also: other builds of the library (NUHTC_EXTRA_CFLAGS_CELLTERRITORY=-DNUHTC_SITE_ROUTE=1 forces the staged owner kernel, =2 the direct
                        one; -DNUHTC_TERRITORY_PER_SITE one atomic per site in the tally instead of one per run of a wave) timed in
                        `--rounds` alternating rounds with the shipped one, all in this process; each must return the shipped arrays
   host_ms              the yardstick on the host: scipy.spatial.cKDTree.query(k=1, distance_upper_bound=reach) over the sites of the

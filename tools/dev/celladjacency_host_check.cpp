@@ -1,5 +1,5 @@
 // Host check of the plain-C++ parts of the territory adjacency (nuhtc_amd/csrc/cellgrid_host.h: the argument check adj_call_ok, the owner
-// check adj_owner_ok, the edge test adj_is_edge, the key adj_key with its order and its two halves, the pairs of a site adj_site_pairs,
+// check adj_owner_ok, the edge test adj_is_edge, the key adj_key with its order and its two halves, the site of a thread site_uv, the pairs of a site adj_site_pairs,
 // the slot hash adj_slot_hash / adj_slot_of and the slot count adj_table_slots), meant to be built with a sanitizer and run on the host --
 // it never touches a GPU, and the kernel code itself (celladjacency.hip) is NOT sanitized:
 //
@@ -46,13 +46,14 @@ static long long probe(std::vector<unsigned long long>& keys, unsigned long long
 static Graph chain(const std::vector<int>& own, int W, int H, int n) {
   Graph out;
   out.degree.assign(n, 0);
-  const int tiles_x = (W + DENS_TILE - 1) / DENS_TILE, tiles_y = (H + DENS_TILE - 1) / DENS_TILE;
+  const int tiles_x = (W + SITE_TILE - 1) / SITE_TILE, tiles_y = (H + SITE_TILE - 1) / SITE_TILE;
   std::vector<std::vector<std::pair<unsigned long long, unsigned>>> records(tiles_x * tiles_y);
   for (int tile = 0; tile < tiles_x * tiles_y; ++tile) {                                  // count and insert: the tile pass
     std::vector<unsigned long long> keys(ADJ_TILE_SLOTS, ADJ_NO_KEY);
     std::vector<unsigned> cnt(ADJ_TILE_SLOTS, 0);
-    for (int tid = 0; tid < DENS_TILE * DENS_TILE; ++tid) {
-      const int u = tile % tiles_x * DENS_TILE + (tid & (DENS_TILE - 1)), v = tile / tiles_x * DENS_TILE + tid / DENS_TILE;
+    for (int tid = 0; tid < SITE_TILE * SITE_TILE; ++tid) {
+      int u, v;
+      site_uv((unsigned)tile, tiles_x, tid, &u, &v);
       if (u >= W || v >= H) continue;
       const int at = v * W + u, pairs = adj_site_pairs(u, v, W, H), me = own.at(at);
       if (!adj_owner_ok(me, n)) out.bad = true;
